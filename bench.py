@@ -21,6 +21,14 @@ streams are all-gathered once per step over RCCL.  value = total tokens / max-ov
 
 ``--dry-run`` replaces the GPU work by fabricated token streams (gloo on CPU): it exercises the launch, sharding,
 gather, barrier and max-over-ranks plumbing and prints the same JSON shape with ``"dry_run": true``.
+
+A plain run only sets up, warms up, times the steps and prints the result line (``value``, ``ms_per_step``, the per-rank
+diagnostics of the timed steps).  ``--full`` adds everything else the line used to carry, each measured after the timed steps:
+the run-average ``roofline`` (a kernel sweep over 16 contexts), ``detokenise_ms``, and for the default configuration the
+secondary figures (``config3_shard_exact_fp32``, ``fast_mode_fp16``, ``config3_shard_fp16``, ``config2_shape_sample_fp16``,
+``dit_front_end_fp16``) and the ``cpu_baseline``.  ``--dump-outputs DIR`` writes what ``LMM.generate()`` returned in the last
+timed step on rank 0 (``tokens.npy``: the id stream of every row; ``meshNN_vertices.npy`` / ``meshNN_faces.npy``: each row's
+mesh), all float64; the inputs depend only on the arguments, so two builds can be compared file for file.
 """
 from __future__ import annotations
 
@@ -76,13 +84,20 @@ def parse_args(argv=None):
     ap.add_argument("--resume-len", type=int, default=0,
                     help="extra teacher-given tokens appended to the prefix (resume_ids): starts the decode at a longer "
                          "context; used by the PMC passes to measure attention traffic at the run's mean context length")
-    ap.add_argument("--cpu-steps", type=int, default=120, help="decode steps of the CPU baseline sample (0 = skip)")
+    ap.add_argument("--cpu-steps", type=int, default=120, help="decode steps of the CPU baseline sample (--full; 0 = skip)")
     ap.add_argument("--precision", choices=("fp32", "fp16"), default=None,
                     help="fp32 = exact mode (the mode whose ids are bit-exact vs the CPU path; configs[1]); fp16 = fast mode")
-    ap.add_argument("--no-fast-extra", action="store_true", help="skip the additional fp16 fast-mode / batch-32 measurements")
+    ap.add_argument("--no-fast-extra", action="store_true", help="--full: skip the additional fp16 fast-mode / batch-32 measurements")
     ap.add_argument("--dry-run", action="store_true", help="no GPU work: fabricated streams through the same multi-rank plumbing")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the roofline kernel sweep, the detokenise time and (default configuration) "
+                         "the secondary figures and the CPU baseline; a plain run reports the timed steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned in its last step (rank 0) as DIR/<name>.npy")
     ap.add_argument("--master-port", type=int, default=0)
     a = ap.parse_args(argv)
+    if a.dry_run and a.dump_outputs:
+        ap.error("--dump-outputs needs the real path: a dry run computes nothing to write")
     cfg = CONFIGS[a.config]
     a.overridden = [k for k, v in (("batch_per_gpu", a.batch_per_gpu), ("num_face", a.num_face), ("mode", a.mode),
                                    ("precision", a.precision), ("tokens", a.tokens)) if v is not None]
@@ -415,6 +430,27 @@ def config3_shard_extra(lmm, dev, points, num_face, T, precision, tok, NS=8):
             "roofline": roofline_block(prof, ends, L_ref, mean_L, PREFIX, T, NS, Bx, precision, dec_tok_s)}, toks
 
 
+DUMP_LIMIT_BYTES = 60_000_000      # the dump stays under 64 MB, .npy headers included
+
+
+def dump_outputs(out_dir, meshes, toks):
+    """What LMM.generate() handed back in the last timed step: the id stream of every row ([rows, len] -> tokens.npy) and each row's
+    mesh (meshNN_vertices.npy [V, 3], meshNN_faces.npy [F, 3]), all as float64 (ids and vertex indices are exact in it).  Rows are
+    kept in order while the files stay within DUMP_LIMIT_BYTES."""
+    os.makedirs(out_dir, exist_ok=True)
+    ids = np.stack([np.asarray(t) for t in toks]).astype(np.float64)
+    per_row = [ids[b].nbytes + (0 if m is None else np.asarray(m.vertices).size * 8 + np.asarray(m.faces).size * 8)
+               for b, m in enumerate(meshes)]
+    rows = int(np.searchsorted(np.cumsum(per_row), DUMP_LIMIT_BYTES, side="right"))
+    if rows < len(per_row):
+        print(f"[bench] --dump-outputs: first {rows} of {len(per_row)} rows (size limit)", file=sys.stderr)
+    np.save(os.path.join(out_dir, "tokens.npy"), ids[:rows])
+    for b in range(rows):
+        if meshes[b] is not None:
+            np.save(os.path.join(out_dir, f"mesh{b:02d}_vertices.npy"), np.asarray(meshes[b].vertices, dtype=np.float64))
+            np.save(os.path.join(out_dir, f"mesh{b:02d}_faces.npy"), np.asarray(meshes[b].faces, dtype=np.float64))
+
+
 def main(argv=None):
     args = parse_args(argv)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -446,7 +482,7 @@ def main(argv=None):
     t0 = time.time()
     lmm = LMM(opt, dev, precision=args.precision)
     esz = 4 if args.precision == "fp32" else 2
-    keep_sd = rank == 0 and world == 1 and args.cpu_steps > 0 and args.config == 1 and not args.overridden
+    keep_sd = args.full and rank == 0 and world == 1 and args.cpu_steps > 0 and args.config == 1 and not args.overridden
     sd = {}
     def items():
         for k, t in W.iter_state_dict(opt, 0, "perturbed"):
@@ -471,9 +507,9 @@ def main(argv=None):
     def one_step(step_idx):
         mine = D.shard_indices(n_items, rank, world)        # cloud index i runs on rank i mod world
         pcs = torch.cat([W.synthetic_point_cloud(step_idx * n_items + i, args.points) for i in mine]).to(dev)   # resident in HBM
-        _, toks = lmm.generate(pcs, args.num_face, tokenizer=tok_engine, max_new_tokens=T, min_new_tokens=T, resume_ids=resume,
-                               seed=(1000 + step_idx) if args.mode == "sample" else None, clean=True)
-        last_tokens[:] = [toks[0]]
+        meshes, toks = lmm.generate(pcs, args.num_face, tokenizer=tok_engine, max_new_tokens=T, min_new_tokens=T, resume_ids=resume,
+                                    seed=(1000 + step_idx) if args.mode == "sample" else None, clean=True)
+        last_out[:] = [meshes, toks]
         torch.cuda.synchronize()
         tg = time.perf_counter()
         streams = D.gather_token_streams([t[args.resume_len:] for t in toks], n_items, device=dev)
@@ -486,7 +522,7 @@ def main(argv=None):
             print(f"[bench +{time.time() - t0:.1f}s] {msg}", file=sys.stderr, flush=True)
 
     gather_ms = []
-    last_tokens = []
+    last_out = []
     for w in range(args.warmup):
         one_step(-1 - w)
     log("warmup done")
@@ -500,6 +536,9 @@ def main(argv=None):
     my_elapsed = time.perf_counter() - t_start
     elapsed = D.max_over_ranks(my_elapsed, dev)
     log(f"timed region done: {elapsed:.2f}s")
+    if args.dump_outputs and rank == 0 and last_out:
+        dump_outputs(args.dump_outputs, *last_out)
+        log(f"outputs of the last timed step written to {args.dump_outputs}")
     # what a first N > 1 run needs to explain itself: every rank's own wall time, decode rate and gather time (rank order)
     rk_wall = D.all_ranks(my_elapsed, dev)
     rk_dec = D.all_ranks(B * T / (float(np.mean(dec_ms)) / 1e3), dev)
@@ -525,18 +564,19 @@ def main(argv=None):
     # scripts/roofline_from_rocprof.py recomputes `frac` from profiles/*_kernel_stats.csv and checks the two agree.
     L0 = PREFIX + args.resume_len
     NS = 16 if T >= 64 else 1
-    prof, ends, L_ref, mean_L = decode_kernel_sweep(lmm.mesh_decoder, L0, T, NS)
-    ends["fit"] = attention_fit(ends["samples"], esz)
-    log("kernel sweep done")
-    roofline = roofline_block(prof, ends, L_ref, mean_L, L0, T, NS, B, args.precision, decode_only / world)
-    # detokenise by itself (host): the stream of the last timed step, both forms of the clean flag
-    detok = {}
-    if last_tokens:
-        for clean in (False, True):
-            td = time.perf_counter()
-            for _ in range(5):
-                save_mesh(last_tokens[0], opt, tokenizer=tok_engine, clean=clean)
-            detok["clean" if clean else "raw"] = round((time.perf_counter() - td) / 5 * 1e3, 3)
+    if args.full:
+        prof, ends, L_ref, mean_L = decode_kernel_sweep(lmm.mesh_decoder, L0, T, NS)
+        ends["fit"] = attention_fit(ends["samples"], esz)
+        log("kernel sweep done")
+        roofline = roofline_block(prof, ends, L_ref, mean_L, L0, T, NS, B, args.precision, decode_only / world)
+        # detokenise by itself (host): the stream of the last timed step, both forms of the clean flag
+        detok = {}
+        if last_out:
+            for clean in (False, True):
+                td = time.perf_counter()
+                for _ in range(5):
+                    save_mesh(last_out[1][0], opt, tokenizer=tok_engine, clean=clean)
+                detok["clean" if clean else "raw"] = round((time.perf_counter() - td) / 5 * 1e3, 3)
 
     cfg_name = CONFIGS[args.config]["name"] + (f" with {', '.join(args.overridden)} overridden" if args.overridden else "")
     out = {
@@ -555,13 +595,14 @@ def main(argv=None):
                    "batch_per_gpu": B, "generate_mode": args.mode, "precision": args.precision,
                    "parallelism": f"dp{world} (independent samples, full replica per GPU)"},
         "decode_only_tokens_per_s": round(decode_only, 2),
-        "detokenise_ms": {"per_sample_clean_true": detok.get("clean"), "per_sample_clean_false": detok.get("raw"),
-                          "note": "host time of save_mesh (ids -> vertices / faces, core/provider.py:39-66) for one 4000-token stream; INSIDE the timed "
-                                  "step with clean=True"},
         "per_rank": per_rank,
-        "roofline": roofline,
     }
-    if rank == 0 and world == 1 and args.config == 1 and not args.overridden and not args.no_fast_extra:
+    if args.full:
+        out["detokenise_ms"] = {"per_sample_clean_true": detok.get("clean"), "per_sample_clean_false": detok.get("raw"),
+                                "note": "host time of save_mesh (ids -> vertices / faces, core/provider.py:39-66) for one 4000-token stream; "
+                                        "INSIDE the timed step with clean=True"}
+        out["roofline"] = roofline
+    if args.full and rank == 0 and world == 1 and args.config == 1 and not args.overridden and not args.no_fast_extra:
         # BASELINE configs[3]'s shard (32 clouds per GPU) at FULL size in the exact mode - the mode whose greedy ids are bit-exact vs the
         # CPU reference (tests/test_gpu_parity.py::test_config4_shard_B32_T4000_row0_bit_exact) - on the headline's own context
         exact_toks = None

@@ -5,6 +5,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -53,3 +54,34 @@ def test_bench_without_gpu_fails_loudly():
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "0", "--layers", "2"], cwd=ROOT, env=env,
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
     assert p.returncode != 0 and ("HIP device" in p.stderr or "no CPU fallback" in p.stderr)
+
+
+def test_full_is_off_by_default_and_a_dry_run_cannot_dump():
+    import bench
+    assert bench.parse_args([]).full is False and bench.parse_args(["--full"]).full is True
+    assert bench.parse_args(["--dump-outputs", "d"]).dump_outputs == "d"
+    with pytest.raises(SystemExit):
+        bench.parse_args(["--dry-run", "--dump-outputs", "d"])
+
+
+def test_dump_outputs_writes_float64_arrays_within_the_size_limit(tmp_path, monkeypatch):
+    """--dump-outputs: the ids of every row and each row's mesh as float64 .npy (exact for ids and indices); rows are dropped from the
+    end, never cut, when the files would pass the limit."""
+    import bench
+    from edgerunner_amd.meto import Mesh
+    toks = [np.arange(40, dtype=np.int64) + 1000 * b for b in range(3)]
+    meshes = [Mesh(np.random.default_rng(b).random((5, 3)), np.arange(6, dtype=np.int64).reshape(2, 3) + b) for b in range(2)] + [None]
+    bench.dump_outputs(str(tmp_path / "all"), meshes, toks)
+    ids = np.load(tmp_path / "all" / "tokens.npy")
+    assert ids.dtype == np.float64 and np.array_equal(ids, np.stack(toks))
+    for b in range(2):
+        v, f = np.load(tmp_path / "all" / f"mesh{b:02d}_vertices.npy"), np.load(tmp_path / "all" / f"mesh{b:02d}_faces.npy")
+        assert v.dtype == f.dtype == np.float64
+        assert np.array_equal(v, meshes[b].vertices) and np.array_equal(f, meshes[b].faces)
+    assert sorted(os.listdir(tmp_path / "all")) == ["mesh00_faces.npy", "mesh00_vertices.npy", "mesh01_faces.npy", "mesh01_vertices.npy",
+                                                    "tokens.npy"]
+    row0 = 40 * 8 + 15 * 8 + 6 * 8
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", row0 + 10)
+    bench.dump_outputs(str(tmp_path / "cut"), meshes, toks)
+    assert np.array_equal(np.load(tmp_path / "cut" / "tokens.npy"), np.stack(toks[:1]))
+    assert sorted(os.listdir(tmp_path / "cut")) == ["mesh00_faces.npy", "mesh00_vertices.npy", "tokens.npy"]

@@ -251,3 +251,39 @@ def test_infer_dit_py_image_to_tokens(tmp_path):
                {"ER_CLIP_LAYERS": "2", "ER_DIT_STEPS": "3"})
     t16 = np.load(out16 / "img_0_1000f_tokens.npy")
     assert t16.ndim == 1 and (len(t16) == 0 or t16[0] == 2)      # first token is BOM (5 - 3)
+
+
+def test_bench_plain_run_dumps_its_last_step_and_full_adds_the_extras(arae_ckpt, tmp_path):
+    """A plain `bench.py` line reports the timed steps only; `--dump-outputs` writes what LMM.generate() returned in the last timed step
+    (same arguments -> the same files, equal to an in-process generate() of that step's cloud); `--full` adds the roofline block and the
+    detokenise time."""
+    import json
+    from edgerunner_amd import weights as W
+    from edgerunner_amd.meto import Engine
+    from edgerunner_amd.models import LMM
+    opt, sd, _ = arae_ckpt
+    args = ["--steps", 2, "--warmup", 1, "--layers", 2, "--tokens", 48]
+
+    def line(log):
+        return json.loads([ln for ln in log.splitlines() if ln.startswith("{")][-1])
+
+    lines = [line(run_script("bench.py", args + ["--dump-outputs", tmp_path / d], timeout=600)) for d in ("a", "b")]
+    for ln in lines:
+        assert ln["steps"] == 2 and ln["warmup"] == 1 and ln["ms_per_step"] > 0 and ln["value"] > 0 and ln["dtype"] == "f32"
+        assert not {"roofline", "detokenise_ms", "cpu_baseline", "fast_mode_fp16"} & set(ln)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b")) and "tokens.npy" in names and "mesh00_vertices.npy" in names
+    for n in names:
+        a, b = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert a.dtype == np.float64 and np.array_equal(a, b), n
+    # the last timed step (index 1) generates for cloud 1
+    m = LMM(opt, DEV, precision="fp32")
+    m.load_state_dict(sd, strict=True)
+    meshes, toks = m.generate(W.synthetic_point_cloud(1, 4096).to(DEV), 1000, tokenizer=Engine(opt.discrete_bins, backend=opt.meto_backend),
+                              max_new_tokens=48, min_new_tokens=48, clean=True)
+    assert np.array_equal(np.load(tmp_path / "a" / "tokens.npy"), np.stack(toks).astype(np.float64))
+    assert np.array_equal(np.load(tmp_path / "a" / "mesh00_vertices.npy"), meshes[0].vertices)
+    assert np.array_equal(np.load(tmp_path / "a" / "mesh00_faces.npy"), meshes[0].faces)
+    full = line(run_script("bench.py", ["--steps", 1, "--warmup", 0, "--layers", 2, "--tokens", 48, "--full", "--no-fast-extra",
+                                        "--cpu-steps", 0], timeout=600))
+    assert full["roofline"]["bound"] == "hbm" and full["detokenise_ms"]["per_sample_clean_true"] is not None
