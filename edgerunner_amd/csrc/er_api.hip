@@ -24,6 +24,7 @@
 #include "k_gemv_mfma.h"
 #include "k_head.h"
 #include "k_rowops.h"
+#include "k_score.h"
 #include "k_flash_attn.h"
 #include "k_flash_attn_f32.h"
 #include "meto_decode.h"
@@ -138,6 +139,7 @@ struct er_ctx {
     // scratch for prefill / encoder
     Buf p_hi, p_lo;           // fast-mode prefill: hi / lo fp16 halves of the activation a Linear is about to read (LDS-DMA GEMM, split form)
     Buf p_h, p_q, p_a, p_y, p_f, p_sc, p_qkv, p_ap, p_aml, e_a0, e_x, e_k, e_v, e_qln, e_q, e_sc, e_att, e_l, e_ln, e_u, e_g, e_lat, e_tmp, e_ids, e_stage;
+    Buf s_lg;                 // er_score: logits of every position when the caller passes no buffer for them
 };
 
 constexpr int ER_MAX_BATCH = 1023;   // h_pinned holds B ints + one flag
@@ -284,7 +286,7 @@ extern "C" int er_destroy(er_ctx* c) {
     free_kv(c);
     for (void* p : c->owned) hipFree(p);
     for (Buf* b : {&c->p_hi, &c->p_lo, &c->p_h, &c->p_q, &c->p_a, &c->p_y, &c->p_f, &c->p_sc, &c->p_qkv, &c->p_ap, &c->p_aml, &c->e_a0, &c->e_x, &c->e_k, &c->e_v, &c->e_qln,
-                   &c->e_q, &c->e_sc, &c->e_att, &c->e_l, &c->e_ln, &c->e_u, &c->e_g, &c->e_lat, &c->e_tmp, &c->e_ids, &c->e_stage})
+                   &c->e_q, &c->e_sc, &c->e_att, &c->e_l, &c->e_ln, &c->e_u, &c->e_g, &c->e_lat, &c->e_tmp, &c->e_ids, &c->e_stage, &c->s_lg})
         if (b->p) hipFree(b->p);
     if (c->ev0) hipEventDestroy(c->ev0);
     if (c->ev1) hipEventDestroy(c->ev1);
@@ -1070,6 +1072,71 @@ static int attention_full(const float* Q, int ldq, const float* Kp, int ldk, lon
 }
 
 // ------------------------------------------------------------------------------------ encode_cond
+// PointEncoderEmbed (core/transformer/point.py:186-206) of nb samples of N points each: the latent mean (posterior.mode(), :201)
+// into c->e_lat [nb][Lq][LD].  Shared by er_encode_cond (which projects it, core/models.py:124) and er_point_latent.
+static int point_latent_chunk(er_ctx* c, const float* pts, int nb, int N, hipStream_t st) {
+    const er_config& g = c->cfg;
+    const int PH = g.point_hidden_dim, Lq = g.point_latent_size, LD = g.point_latent_dim;
+    const int PHh = g.point_num_heads > 0 ? g.point_num_heads : 1, PD = PH / PHh;
+    if (N <= 0) return fail(ER_ERR_INVALID, "n_points must be > 0");
+    const size_t R = (size_t)nb * N, RQ = (size_t)nb * Lq;
+    ERCHK(ensure(c->e_a0, R * c->pe_kpad));
+    ERCHK(ensure(c->e_x, R * PH));
+    ERCHK(ensure(c->e_k, R * PH));
+    ERCHK(ensure(c->e_v, R * PH));
+    ERCHK(ensure(c->e_qln, (size_t)Lq * PH));
+    ERCHK(ensure(c->e_q, (size_t)Lq * PH));
+    ERCHK(ensure(c->e_att, RQ * PH));
+    ERCHK(ensure(c->e_l, RQ * PH));
+    ERCHK(ensure(c->e_ln, RQ * PH));
+    ERCHK(ensure(c->e_u, RQ * 8 * PH));
+    ERCHK(ensure(c->e_g, RQ * 4 * PH));
+    ERCHK(ensure(c->e_lat, RQ * LD));
+    // x = ln(point_embed(pts))                                          point.py:194
+    hipLaunchKernelGGL(point_embed_kernel, dim3(ew_grid((long long)R * c->pe_kpad)), dim3(ER_WG), 0, st, pts,
+                       c->pe_basis, c->e_a0.p, (long long)R, g.point_freq_dim, c->pe_kpad);
+    HIPRET(hipGetLastError());
+    HIPRET(linear(c->e_a0.p, c->pe_kpad, c->pe_mlp_w, c->pe_mlp_b, c->e_x.p, PH, (int)R, PH, c->pe_kpad, false, nullptr, 0, st));
+    HIPRET(launch_layernorm(c->e_x.p, c->pe_ln_w, c->pe_ln_b, c->e_x.p, (int)R, PH, PH, PH, g.ln_eps, st));
+    // cross attention: l = q + out_proj(attn(q_proj(ln1(q)), k_proj(x), v_proj(x)))   point.py:123-124
+    // (the learned queries and their projection are the same for every sample: computed once)
+    HIPRET(launch_layernorm(c->pe_query, c->ca_ln1_w, c->ca_ln1_b, c->e_qln.p, Lq, PH, PH, PH, g.ln_eps, st));
+    HIPRET(linear(c->e_qln.p, PH, c->ca_q_w, c->ca_q_b, c->e_q.p, PH, Lq, PH, PH, false, nullptr, 0, st));
+    HIPRET(linear(c->e_x.p, PH, c->ca_k_w, c->ca_k_b, c->e_k.p, PH, (int)R, PH, PH, false, nullptr, 0, st));
+    HIPRET(linear(c->e_x.p, PH, c->ca_v_w, c->ca_v_b, c->e_v.p, PH, (int)R, PH, PH, false, nullptr, 0, st));
+    if (PD == 64 || PD == 96) {
+        Flash32Args f{};
+        f.Q = c->e_q.p; f.ldq = PH; f.qs_b = 0; f.qs_h = PD;                      // queries shared by the batch
+        f.K = c->e_k.p; f.ldk = PH; f.ks_b = (long long)N * PH; f.ks_h = PD;
+        f.V = c->e_v.p; f.ldv = PH; f.vs_b = (long long)N * PH; f.vs_h = PD;
+        f.O = c->e_att.p; f.ldo = PH; f.os_b = (long long)Lq * PH; f.os_h = PD;
+        f.N = Lq; f.M = N; f.sqrt_d = sqrtf((float)PD); f.causal_off = 0;
+        HIPRET(launch_flash_attn_f32(f, PD, false, PHh, nb, st));
+    } else {
+        const int ldS = (N + 15) / 16 * 16;
+        ERCHK(ensure(c->e_sc, (size_t)PHh * Lq * ldS));
+        for (int b = 0; b < nb; ++b)
+            ERCHK(attention_full(c->e_q.p, PH, c->e_k.p + (size_t)b * N * PH, PH, PD, c->e_v.p + (size_t)b * N * PH, PH, PD,
+                                 c->e_att.p + (size_t)b * Lq * PH, PH, c->e_sc.p, PHh, PD, Lq, N, false, st));
+    }
+    {   // l = query_embed + out_proj(att): the residual table has Lq rows shared by every sample
+        GemmArgs ga = gemm_args_default();
+        ga.A = c->e_att.p; ga.B = c->ca_o_w; ga.C = c->e_l.p; ga.bias = c->ca_o_b; ga.resid = c->pe_query; ga.resid_mod = Lq;
+        ga.M = (int)RQ; ga.N = PH; ga.K = PH; ga.lda = PH; ga.ldb = PH; ga.ldc = PH; ga.ldr = PH;
+        HIPRET(launch_gemm(ga, 1, st));
+    }
+    // l = l + net2(GEGLU(net0(ln2(l))))                                   point.py:125, 68-84
+    HIPRET(launch_layernorm(c->e_l.p, c->ca_ln2_w, c->ca_ln2_b, c->e_ln.p, (int)RQ, PH, PH, PH, g.ln_eps, st));
+    HIPRET(linear(c->e_ln.p, PH, c->ff0_w, c->ff0_b, c->e_u.p, 8 * PH, (int)RQ, 8 * PH, PH, false, nullptr, 0, st));
+    hipLaunchKernelGGL(geglu_kernel, dim3(ew_grid((long long)RQ * 4 * PH)), dim3(ER_WG), 0, st, c->e_u.p, c->e_g.p,
+                       (long long)RQ, 4 * PH);
+    HIPRET(hipGetLastError());
+    HIPRET(linear(c->e_g.p, 4 * PH, c->ff2_w, c->ff2_b, c->e_l.p, PH, (int)RQ, PH, 4 * PH, false, c->e_l.p, PH, st));
+    // latent mean = linear(l)                                              point.py:201
+    HIPRET(linear(c->e_l.p, PH, c->lin_w, c->lin_b, c->e_lat.p, LD, (int)RQ, LD, PH, false, nullptr, 0, st));
+    return 0;
+}
+
 extern "C" int er_encode_cond(er_ctx* c, const float* conds, int B, int n_points, const int32_t* face_bucket,
                               float* cond_out, void* stream) {
     if (!c || !cond_out || B <= 0) return fail(ER_ERR_INVALID, "er_encode_cond: bad argument");
@@ -1077,14 +1144,12 @@ extern "C" int er_encode_cond(er_ctx* c, const float* conds, int B, int n_points
     HIPCHK(hipSetDevice(c->device));
     hipStream_t st = pick(c, stream);
     const er_config& g = c->cfg;
-    const int H = g.hidden_dim, C = g.num_cond_tokens, PH = g.point_hidden_dim, Lq = g.point_latent_size, LD = g.point_latent_dim;
+    const int H = g.hidden_dim, C = g.num_cond_tokens, Lq = g.point_latent_size, LD = g.point_latent_dim;
     const int n_lat = (g.cond_mode == ER_COND_NONE) ? 0 : Lq;
     const int n_face = g.num_face_buckets > 0 ? 1 : 0;
     if (n_lat + n_face != C) return fail(ER_ERR_INVALID, "num_cond_tokens %d != latent tokens %d + face token %d", C, n_lat, n_face);
     if (g.cond_mode != ER_COND_NONE && !conds) return fail(ER_ERR_INVALID, "er_encode_cond: conds is null");
     if (LD % 16) return fail(ER_ERR_UNSUPPORTED, "point_latent_dim must be a multiple of 16");
-
-    const int PHh = g.point_num_heads > 0 ? g.point_num_heads : 1, PD = PH / PHh;
     // samples are encoded in chunks of up to 32 (scratch for one chunk at N = 4096: ~5 GB); every GEMM / LayerNorm /
     // attention launch of a chunk covers all of its samples
     constexpr int ENC_CHUNK = 32;
@@ -1092,64 +1157,7 @@ extern "C" int er_encode_cond(er_ctx* c, const float* conds, int B, int n_points
         const int nb = std::min(ENC_CHUNK, B - b0);
         const float* lat = nullptr;   // [nb][Lq][LD]
         if (g.cond_mode == ER_COND_POINT) {
-            const int N = n_points;
-            if (N <= 0) return fail(ER_ERR_INVALID, "n_points must be > 0");
-            const size_t R = (size_t)nb * N, RQ = (size_t)nb * Lq;
-            ERCHK(ensure(c->e_a0, R * c->pe_kpad));
-            ERCHK(ensure(c->e_x, R * PH));
-            ERCHK(ensure(c->e_k, R * PH));
-            ERCHK(ensure(c->e_v, R * PH));
-            ERCHK(ensure(c->e_qln, (size_t)Lq * PH));
-            ERCHK(ensure(c->e_q, (size_t)Lq * PH));
-            ERCHK(ensure(c->e_att, RQ * PH));
-            ERCHK(ensure(c->e_l, RQ * PH));
-            ERCHK(ensure(c->e_ln, RQ * PH));
-            ERCHK(ensure(c->e_u, RQ * 8 * PH));
-            ERCHK(ensure(c->e_g, RQ * 4 * PH));
-            ERCHK(ensure(c->e_lat, RQ * LD));
-            const float* pts = conds + (size_t)b0 * N * 3;
-            // x = ln(point_embed(pts))                                          point.py:194
-            hipLaunchKernelGGL(point_embed_kernel, dim3(ew_grid((long long)R * c->pe_kpad)), dim3(ER_WG), 0, st, pts,
-                               c->pe_basis, c->e_a0.p, (long long)R, g.point_freq_dim, c->pe_kpad);
-            HIPRET(hipGetLastError());
-            HIPRET(linear(c->e_a0.p, c->pe_kpad, c->pe_mlp_w, c->pe_mlp_b, c->e_x.p, PH, (int)R, PH, c->pe_kpad, false, nullptr, 0, st));
-            HIPRET(launch_layernorm(c->e_x.p, c->pe_ln_w, c->pe_ln_b, c->e_x.p, (int)R, PH, PH, PH, g.ln_eps, st));
-            // cross attention: l = q + out_proj(attn(q_proj(ln1(q)), k_proj(x), v_proj(x)))   point.py:123-124
-            // (the learned queries and their projection are the same for every sample: computed once)
-            HIPRET(launch_layernorm(c->pe_query, c->ca_ln1_w, c->ca_ln1_b, c->e_qln.p, Lq, PH, PH, PH, g.ln_eps, st));
-            HIPRET(linear(c->e_qln.p, PH, c->ca_q_w, c->ca_q_b, c->e_q.p, PH, Lq, PH, PH, false, nullptr, 0, st));
-            HIPRET(linear(c->e_x.p, PH, c->ca_k_w, c->ca_k_b, c->e_k.p, PH, (int)R, PH, PH, false, nullptr, 0, st));
-            HIPRET(linear(c->e_x.p, PH, c->ca_v_w, c->ca_v_b, c->e_v.p, PH, (int)R, PH, PH, false, nullptr, 0, st));
-            if (PD == 64 || PD == 96) {
-                Flash32Args f{};
-                f.Q = c->e_q.p; f.ldq = PH; f.qs_b = 0; f.qs_h = PD;                      // queries shared by the batch
-                f.K = c->e_k.p; f.ldk = PH; f.ks_b = (long long)N * PH; f.ks_h = PD;
-                f.V = c->e_v.p; f.ldv = PH; f.vs_b = (long long)N * PH; f.vs_h = PD;
-                f.O = c->e_att.p; f.ldo = PH; f.os_b = (long long)Lq * PH; f.os_h = PD;
-                f.N = Lq; f.M = N; f.sqrt_d = sqrtf((float)PD); f.causal_off = 0;
-                HIPRET(launch_flash_attn_f32(f, PD, false, PHh, nb, st));
-            } else {
-                const int ldS = (N + 15) / 16 * 16;
-                ERCHK(ensure(c->e_sc, (size_t)PHh * Lq * ldS));
-                for (int b = 0; b < nb; ++b)
-                    ERCHK(attention_full(c->e_q.p, PH, c->e_k.p + (size_t)b * N * PH, PH, PD, c->e_v.p + (size_t)b * N * PH, PH, PD,
-                                         c->e_att.p + (size_t)b * Lq * PH, PH, c->e_sc.p, PHh, PD, Lq, N, false, st));
-            }
-            {   // l = query_embed + out_proj(att): the residual table has Lq rows shared by every sample
-                GemmArgs ga = gemm_args_default();
-                ga.A = c->e_att.p; ga.B = c->ca_o_w; ga.C = c->e_l.p; ga.bias = c->ca_o_b; ga.resid = c->pe_query; ga.resid_mod = Lq;
-                ga.M = (int)RQ; ga.N = PH; ga.K = PH; ga.lda = PH; ga.ldb = PH; ga.ldc = PH; ga.ldr = PH;
-                HIPRET(launch_gemm(ga, 1, st));
-            }
-            // l = l + net2(GEGLU(net0(ln2(l))))                                   point.py:125, 68-84
-            HIPRET(launch_layernorm(c->e_l.p, c->ca_ln2_w, c->ca_ln2_b, c->e_ln.p, (int)RQ, PH, PH, PH, g.ln_eps, st));
-            HIPRET(linear(c->e_ln.p, PH, c->ff0_w, c->ff0_b, c->e_u.p, 8 * PH, (int)RQ, 8 * PH, PH, false, nullptr, 0, st));
-            hipLaunchKernelGGL(geglu_kernel, dim3(ew_grid((long long)RQ * 4 * PH)), dim3(ER_WG), 0, st, c->e_u.p, c->e_g.p,
-                               (long long)RQ, 4 * PH);
-            HIPRET(hipGetLastError());
-            HIPRET(linear(c->e_g.p, 4 * PH, c->ff2_w, c->ff2_b, c->e_l.p, PH, (int)RQ, PH, 4 * PH, false, c->e_l.p, PH, st));
-            // latent mean = linear(l)                                              point.py:201
-            HIPRET(linear(c->e_l.p, PH, c->lin_w, c->lin_b, c->e_lat.p, LD, (int)RQ, LD, PH, false, nullptr, 0, st));
+            ERCHK(point_latent_chunk(c, conds + (size_t)b0 * n_points * 3, nb, n_points, st));
             lat = c->e_lat.p;
         } else if (g.cond_mode == ER_COND_POINT_LATENT) {
             lat = conds + (size_t)b0 * Lq * LD;
@@ -1217,14 +1225,26 @@ static hipError_t linear_tail(const float* A, const float* W, const float* bias,
     return gemv_groups<float, KS, RW, PRO_NONE, EPI>(t, rows, K, st);
 }
 
-extern "C" int er_prefill(er_ctx* c, const float* embeds, int B, int S, void* stream) {
-    if (!c || !embeds || B <= 0 || S <= 0) return fail(ER_ERR_INVALID, "er_prefill: bad argument");
+// Size checks of a full forward over B x S positions (er_prefill, er_score), before anything is launched.  The prefill kernels index
+// their [B * S][width] scratch rows with 32-bit products up to B * S * max(intermediate_dim, 3 * hidden_dim) (fc1's output is the widest):
+// such a product must stay below 2^31 (B = 8 at S = 43 011 and intermediate_dim 6144 is 2.11e9 - the edge).
+static int forward_check(er_ctx* c, const char* who, const float* embeds, int B, int S) {
+    if (!c || !embeds || B <= 0 || S <= 0) return fail(ER_ERR_INVALID, "%s: bad argument", who);
     ERCHK(er_finalize_weights(c));
-    if (c->B != B) return fail(ER_ERR_INVALID, "er_prefill: batch %d but KV cache reserved for %d (call er_kv_reserve)", B, c->B);
+    if (c->B != B) return fail(ER_ERR_INVALID, "%s: batch %d but KV cache reserved for %d (call er_kv_reserve)", who, B, c->B);
     if (S >= c->Lcap) return fail(ER_ERR_CAPACITY, "prefix length %d does not fit the reserved KV cache (%d)", S, c->Lcap);
+    const long long width = std::max({(long long)c->cfg.intermediate_dim, 3LL * c->cfg.hidden_dim, (long long)c->cfg.vocab_size});
+    if ((long long)B * S * width > 0x7fffffffLL)
+        return fail(ER_ERR_CAPACITY, "%s: %d x %d positions x %lld columns overflows the 32-bit row indexing of the prefill (split the batch)",
+                    who, B, S, width);
+    return 0;
+}
+
+// all layers over inputs_embeds [B, S, hidden]: K/V into cache positions [0, S), the last layer's pre-LN2 output of EVERY position in
+// c->p_y [B * S][hidden], the last position's copy in ypre and the generation state at position S (what er_prefill promises)
+static int prefill_run(er_ctx* c, const float* embeds, int B, int S, hipStream_t st) {
     HIPCHK(hipSetDevice(c->device));
     if (c->batched && !c->batched_valu) ERCHK(make_tiled_weights(c));
-    hipStream_t st = pick(c, stream);
     const er_config& g = c->cfg;
     const int H = g.hidden_dim, I = g.intermediate_dim, NH = g.num_heads, D = c->D;
     const int M = B * S;
@@ -1316,6 +1336,54 @@ extern "C" int er_prefill(er_ctx* c, const float* embeds, int B, int S, void* st
     HIPRET(hipGetLastError());
     c->base_pos = S;
     c->have_hidden = true;
+    return ER_OK;
+}
+
+extern "C" int er_prefill(er_ctx* c, const float* embeds, int B, int S, void* stream) {
+    ERCHK(forward_check(c, "er_prefill", embeds, B, S));
+    return prefill_run(c, embeds, B, S, pick(c, stream));
+}
+
+// ------------------------------------------------------------------------------------ scoring (LMM.forward, eval mode)
+extern "C" int er_score(er_ctx* c, const float* embeds, const int32_t* labels, int B, int S, float* nll_out, int32_t* pred_out,
+                        float* logits_out, float* loss_out, void* stream) {
+    ERCHK(forward_check(c, "er_score", embeds, B, S));
+    if (!labels || !nll_out || !loss_out) return fail(ER_ERR_INVALID, "er_score: labels, nll_out and loss_out are required");
+    hipStream_t st = pick(c, stream);
+    ERCHK(prefill_run(c, embeds, B, S, st));
+    const er_config& g = c->cfg;
+    const int H = g.hidden_dim, V = g.vocab_size, M = B * S;
+    const LayerW& last = c->layers[g.num_layers - 1];
+    // final LayerNorm of every position (the prefill leaves the last layer's LN2 to the head), into p_h: free once the layers ran
+    HIPRET(launch_layernorm(c->p_y.p, last.ln2w, last.ln2b, c->p_h.p, M, H, H, H, g.ln_eps, st));
+    float* lg = logits_out;
+    if (!lg) {
+        ERCHK(ensure(c->s_lg, (size_t)M * V));
+        lg = c->s_lg.p;
+    }
+    // lm_head over every position (modeling_opt.py:497): the prefill's own Linears, fp32 or fp16-stored weights (fp32-grade activations)
+    if (c->fast) ERCHK(linear_hs(c, c->p_h.p, H, c->lm_head_h, nullptr, lg, V, M, V, H, false, nullptr, 0, st));
+    else HIPRET(linear(c->p_h.p, H, c->lm_head, nullptr, lg, V, M, V, H, false, nullptr, 0, st));
+    HIPRET(launch_score_rows(lg, labels, M, S, V, nll_out, pred_out, st));
+    HIPRET(launch_score_reduce(nll_out, labels, M, S, loss_out, st));
+    return ER_OK;
+}
+
+extern "C" int er_point_latent(er_ctx* c, const float* conds, int B, int n_points, float* latent_out, float* kl_out, void* stream) {
+    if (!c || !conds || !latent_out || B <= 0) return fail(ER_ERR_INVALID, "er_point_latent: bad argument");
+    if (c->cfg.cond_mode != ER_COND_POINT) return fail(ER_ERR_UNSUPPORTED, "er_point_latent: the context has no point encoder (cond_mode %d)", c->cfg.cond_mode);
+    ERCHK(er_finalize_weights(c));
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t st = pick(c, stream);
+    const size_t per = (size_t)c->cfg.point_latent_size * c->cfg.point_latent_dim;
+    if ((long long)B * (long long)per > 0x7fffffffLL) return fail(ER_ERR_CAPACITY, "er_point_latent: batch %d too large", B);
+    constexpr int ENC_CHUNK = 32;        // as er_encode_cond
+    for (int b0 = 0; b0 < B; b0 += ENC_CHUNK) {
+        const int nb = std::min(ENC_CHUNK, B - b0);
+        ERCHK(point_latent_chunk(c, conds + (size_t)b0 * n_points * 3, nb, n_points, st));
+        HIPCHK(hipMemcpyAsync(latent_out + (size_t)b0 * per, c->e_lat.p, (size_t)nb * per * 4, hipMemcpyDeviceToDevice, st));
+    }
+    if (kl_out) HIPRET(launch_score_reduce(latent_out, nullptr, (int)((size_t)B * per), 0, kl_out, st));
     return ER_OK;
 }
 
@@ -1889,6 +1957,18 @@ extern "C" int er_k_layernorm(const float* x, const float* w, const float* b, fl
 
 extern "C" int er_k_softmax(float* s, int rows, int cols, int ld, int causal, void* stream) {
     HIPRET(launch_softmax_rows(s, rows, cols, (long long)ld, ld, 0LL, 1, causal, 0, (hipStream_t)stream));
+    return ER_OK;
+}
+
+extern "C" int er_k_score_rows(const float* logits, const int32_t* labels, int batch, int seq_len, int vocab, float* nll_out,
+                               int32_t* pred_out, float* loss_out, void* stream) {
+    if (!logits || !labels || !nll_out || batch <= 0 || seq_len <= 0 || vocab <= 0 || vocab > ER_HEAD_MAX_VOCAB ||
+        (long long)batch * seq_len * vocab > 0x7fffffffLL)
+        return fail(ER_ERR_INVALID, "er_k_score_rows: bad argument");
+    hipStream_t st = (hipStream_t)stream;
+    const int M = batch * seq_len;
+    HIPRET(launch_score_rows(logits, labels, M, seq_len, vocab, nll_out, pred_out, st));
+    if (loss_out) HIPRET(launch_score_reduce(nll_out, labels, M, seq_len, loss_out, st));
     return ER_OK;
 }
 

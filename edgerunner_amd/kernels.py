@@ -188,6 +188,20 @@ def softmax_(s, cols, causal=False):
     return s
 
 
+def score_rows(logits, labels):
+    """er_score's head on given logits [B, S, V] fp32 and labels int [B, S] -> (nll [B, S], pred [B, S] int32, loss [2] =
+    {mean NLL over supervised positions, count})."""
+    lib = native.load_library()
+    B, S, V = logits.shape
+    lab = labels.to(logits.device, torch.int32).contiguous()
+    nll = torch.empty((B, S), dtype=torch.float32, device=logits.device)
+    pred = torch.empty((B, S), dtype=torch.int32, device=logits.device)
+    loss = torch.empty((2,), dtype=torch.float32, device=logits.device)
+    native.check(lib.er_k_score_rows(native.ptr(logits), native.ptr(lab), B, S, V, native.ptr(nll), native.ptr(pred),
+                                     native.ptr(loss), _st()), "er_k_score_rows")
+    return nll, pred, loss
+
+
 def sample_head(logits, mode, grammar, step, last_tok, counter, unfinished, top_k=10, min_new=0, seed=0,
                 eos=2, pad=0):
     """One sampling-head step. Returns (next_tok, counter, unfinished) lists."""

@@ -5,8 +5,9 @@ Same constructor argument (``Options``), same checkpoint keys, same
 ``generate(conds, num_faces, resume_ids, tokenizer, max_new_tokens, clean)``
 signature and return value ``(meshes, all_tokens)``.  Differences, all additive:
 ``B > 1`` is allowed (independent rows, per-row grammar state), ``min_new_tokens``
-can be passed (benchmark rule: EOS suppressed until T), and training-only members
-(``forward``, image conditioner) are not part of this path.
+can be passed (benchmark rule: EOS suppressed until T).  ``forward`` / ``__call__`` score a batch the way the
+reference's eval loop does (core/models.py:147-202 under ``model.eval()``, main.py:244-268); training mode (backward,
+num-face dropout) and the image conditioner are not part of this path.
 """
 from __future__ import annotations
 
@@ -20,6 +21,23 @@ from .grammar import select_grammar
 from .shape_opt import BuiltinGrammar, NativeShapeOPT
 from .utils import quantize_num_faces
 from .weights import dims_from_options
+
+IGNORE_INDEX = -100           # F.cross_entropy's ignore_index: the reference's collate_fn writes it over cond tokens, BOS and padding
+_INDEX_LIMIT = 2 ** 31 - 1    # er_score / er_prefill: B * S * max(intermediate_dim, 3 * hidden_dim, vocab) must stay below 2^31
+
+
+def score_row_groups(batch: int, seq_len: int, dims, max_rows: int = 1023) -> List[tuple]:
+    """Consecutive row ranges [(start, end), ...] that ``LMM.forward`` scores one ``er_score`` call at a time.  Rows are independent
+    (causal attention, right padding), so a batch is cut wherever the 32-bit row indexing of the prefill (B * S * widest Linear
+    output < 2^31) or the context's batch limit (``max_rows``) would be exceeded; every group but the last is full."""
+    if batch <= 0 or seq_len <= 0:
+        raise ValueError(f"batch {batch} / seq_len {seq_len} must be positive")
+    width = max(dims.intermediate_dim, 3 * dims.hidden_dim, dims.vocab_size)
+    per = _INDEX_LIMIT // (seq_len * width)
+    if per < 1:
+        raise ValueError(f"one row of {seq_len} positions exceeds the 32-bit index range of the prefill ({seq_len} x {width})")
+    per = min(per, max_rows)
+    return [(b, min(b + per, batch)) for b in range(0, batch, per)]
 
 
 class _Embd:
@@ -144,6 +162,12 @@ class LMM:
         return self._cast(torch.float32)
 
     def eval(self):
+        self.training = False
+        return self
+
+    def train(self, mode: bool = True):
+        """Sets the flag ``forward`` checks: there is no training path here, so a training-mode forward raises."""
+        self.training = bool(mode)
         return self
 
     def to(self, device):
@@ -166,6 +190,78 @@ class LMM:
         nf = num_faces.tolist() if isinstance(num_faces, torch.Tensor) else list(num_faces)
         buckets = [quantize_num_faces(int(n)) for n in nf]
         return {"cond_embeds": self.mesh_decoder.encode_cond(conds, buckets)}
+
+    # -- scoring (the reference's eval-mode forward) --------------------------------------------------
+    def __call__(self, data, step_ratio=1):
+        return self.forward(data, step_ratio)
+
+    @torch.no_grad()
+    def forward(self, data, step_ratio=1):
+        """core/models.py:147-202 in eval mode: ``data`` is the reference's batch (``collate_fn``: conds, tokens, labels, masks,
+        num_faces, num_tokens).  Returns loss_ce (shifted cross entropy, mean over supervised positions), loss_kl (point mode:
+        0.5 * sum of the latent mean squared over the batch), loss = loss_ce + kl_weight * loss_kl, logits float32 [B, S, V] on the
+        device, and nll [B, S] (per-position -log p of the next label, 0 where ignored).  Logits at padded positions are not part
+        of the contract.  Right padding only (what collate_fn produces); ``step_ratio`` is unused, as in the reference."""
+        out = self.score(data)
+        out.pop("pred")
+        return out
+
+    @torch.no_grad()
+    def score(self, data) -> Dict[str, torch.Tensor]:
+        """``forward`` plus ``pred`` [B, S] int32: the argmax of every position's logits (lowest index on ties), from the same kernel
+        that computes ``nll``."""
+        if self.training:
+            raise NotImplementedError("LMM.forward in training mode (backward pass, num-face dropout) is not part of this path; "
+                                      "call .eval() first")
+        opt, d = self.opt, self.dims
+        tokens = torch.as_tensor(data["tokens"]).to("cpu", torch.long)
+        labels = torch.as_tensor(data["labels"]).to("cpu", torch.long)
+        masks = torch.as_tensor(data["masks"]).to("cpu").bool()
+        if tokens.dim() != 2 or labels.dim() != 2:
+            raise ValueError(f"tokens {tuple(tokens.shape)} / labels {tuple(labels.shape)} must be [B, length]")
+        B, S = labels.shape
+        if tokens.shape[0] != B or S != d.num_cond_tokens + tokens.shape[1]:
+            raise ValueError(f"labels {tuple(labels.shape)} do not cover the {d.num_cond_tokens} cond tokens + tokens "
+                             f"{tuple(tokens.shape)}")
+        if tuple(masks.shape) != (B, S):
+            raise ValueError(f"masks {tuple(masks.shape)} do not match labels {tuple(labels.shape)}")
+        lens = masks.sum(dim=1)
+        if not torch.equal(masks, torch.arange(S)[None, :] < lens[:, None]):
+            raise ValueError("masks must be ones followed by zeros in every row: only right padding (collate_fn's) is supported")
+        if (labels[~masks] != IGNORE_INDEX).any():
+            raise ValueError(f"labels must be {IGNORE_INDEX} wherever the mask is 0")
+        sup = labels != IGNORE_INDEX
+        if ((labels[sup] < 0) | (labels[sup] >= self.vocab_size)).any():
+            raise ValueError(f"labels outside [0, {self.vocab_size}) that are not {IGNORE_INDEX}")
+        conds = data.get("conds")
+        num_faces = data["num_faces"]
+        cond_embeds = self.encode_cond(conds, num_faces)["cond_embeds"]
+        dec = self.mesh_decoder
+        token_embeds = dec.model.embd(tokens)
+        inputs_embeds = torch.cat((cond_embeds, token_embeds), dim=1) if d.num_cond_tokens else token_embeds
+        dev = self.device
+        logits = torch.empty((B, S, self.vocab_size), dtype=torch.float32, device=dev)
+        nll = torch.empty((B, S), dtype=torch.float32, device=dev)
+        pred = torch.empty((B, S), dtype=torch.int32, device=dev)
+        groups = score_row_groups(B, S, d)
+        for b0, b1 in groups:
+            r = dec.score(inputs_embeds[b0:b1], labels[b0:b1], logits_out=logits[b0:b1], nll_out=nll[b0:b1], pred_out=pred[b0:b1])
+            loss = r["loss"]
+        if len(groups) > 1:      # the same fixed-order reduction over the whole batch (nll / pred come out bit-identical)
+            from .kernels import score_rows
+            with torch.cuda.device(dev):
+                _, _, loss = score_rows(logits, labels.to(dev))
+        results = {"loss_ce": loss[0]}
+        total = loss[0]
+        if d.cond_mode == "point":
+            _, kl = dec.point_latent(conds)
+            results["loss_kl"] = kl
+            total = total + opt.kl_weight * kl
+        results["loss"] = total
+        results["logits"] = logits
+        results["nll"] = nll
+        results["pred"] = pred
+        return results
 
     # -- generation ---------------------------------------------------------------------------
     @torch.no_grad()

@@ -180,6 +180,46 @@ class NativeShapeOPT:
         self._exit()
         return out
 
+    def score(self, inputs_embeds: torch.Tensor, labels: torch.Tensor, logits_out: Optional[torch.Tensor] = None,
+              nll_out: Optional[torch.Tensor] = None, pred_out: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+        """ShapeOPT.forward(inputs_embeds, labels) in eval mode through ``er_score``: every layer over [B, S] positions, LN + lm_head
+        over all of them, the shifted cross entropy.  ``labels`` int[B, S] as the reference's (unshifted, -100 = ignored).  The
+        ``*_out`` tensors (contiguous, on the device) receive the results when given.  Returns nll [B, S], pred [B, S] (int32
+        argmax), logits [B, S, V] or None (logits_out=False), loss float[2] = {mean NLL over supervised positions, count}.
+        Leaves the cache as ``prefill`` does (positions [0, S))."""
+        x = inputs_embeds.to(self.device, torch.float32).contiguous()
+        B, S, _ = x.shape
+        lab = labels.to(self.device, torch.int32).contiguous()
+        if tuple(lab.shape) != (B, S):
+            raise ValueError(f"labels {tuple(lab.shape)} do not match inputs_embeds [{B}, {S}]")
+        if self._reserved[0] != B or self._reserved[1] < S + 1:
+            self.reserve(B, S + 1)
+        with self._enter():
+            kw = dict(dtype=torch.float32, device=self.device)
+            nll = nll_out if nll_out is not None else torch.empty((B, S), **kw)
+            pred = pred_out if pred_out is not None else torch.empty((B, S), dtype=torch.int32, device=self.device)
+            logits = None if logits_out is False else (logits_out if logits_out is not None
+                                                        else torch.empty((B, S, self.dims.vocab_size), **kw))
+            loss = torch.empty((2,), **kw)
+            native.check(self.lib.er_score(self._ctx, native.ptr(x), native.ptr(lab), B, S, native.ptr(nll), native.ptr(pred),
+                                           native.ptr(logits), native.ptr(loss), self._sp()), "er_score")
+        self._exit()
+        return {"nll": nll, "pred": pred, "logits": logits, "loss": loss}
+
+    def point_latent(self, conds: torch.Tensor):
+        """PointEncoderEmbed's posterior.mode() [B, point_latent_size, point_latent_dim] and its kl() (0.5 * sum of squares over the
+        whole batch, a 0-dim tensor) through ``er_point_latent``."""
+        d = self.dims
+        x = conds.to(self.device, torch.float32).contiguous()
+        B, N = x.shape[0], x.shape[1]
+        with self._enter():
+            lat = torch.empty((B, d.point_latent_size, d.point_latent_dim), dtype=torch.float32, device=self.device)
+            kl = torch.empty((1,), dtype=torch.float32, device=self.device)
+            native.check(self.lib.er_point_latent(self._ctx, native.ptr(x), B, N, native.ptr(lat), native.ptr(kl), self._sp()),
+                         "er_point_latent")
+        self._exit()
+        return lat, kl[0]
+
     def feed(self, ids):
         ids = [int(v) for v in (ids.flatten().tolist() if isinstance(ids, torch.Tensor) else ids)]
         with self._enter():

@@ -126,6 +126,25 @@ int er_embed_tokens(er_ctx* ctx, const int32_t* ids_host, int batch, int n_token
  * hidden state of the last position ready for er_logits / er_decode. */
 int er_prefill(er_ctx* ctx, const float* embeds_dev, int batch, int seq_len, void* stream);
 
+/* LMM.forward in eval mode (core/models.py:147-202 -> ShapeOPT.forward with labels, modeling_opt.py:464-497).
+ * Runs all layers over inputs_embeds float[B,S,hidden] exactly as er_prefill does and leaves the context in the
+ * state er_prefill leaves it in.  It then applies final LayerNorm + lm_head to EVERY position and the shifted cross entropy:
+ * the target of position s is labels[b, s+1]; -100 and s = S-1 are ignored.
+ *   labels_dev   int32[B,S]       (unshifted, as the reference's `labels`)
+ *   nll_out_dev  float[B,S]       -log softmax(logits[b,s])[target]; 0 where ignored (NaN for a target outside [0, vocab))
+ *   pred_out_dev int32[B,S]       argmax of logits[b,s], first index on ties (torch.argmax); nullable
+ *   logits_out_dev float[B,S,V]   nullable (context scratch is used when null)
+ *   loss_out_dev float[2]         {mean NLL over supervised positions (NaN if none, like F.cross_entropy), count}
+ * ER_ERR_CAPACITY when S >= the reserved cache or B*S*max(intermediate_dim, 3*hidden_dim) >= 2^31 (er_prefill checks the same). */
+int er_score(er_ctx* ctx, const float* embeds_dev, const int32_t* labels_dev, int batch, int seq_len,
+             float* nll_out_dev, int32_t* pred_out_dev, float* logits_out_dev, float* loss_out_dev, void* stream);
+
+/* posterior.mode() of PointEncoderEmbed (point.py:201) float[B, point_latent_size, point_latent_dim], and
+ * kl_out_dev[0] = 0.5 * sum(mean^2) over the WHOLE batch tensor (DummyLatent.kl, point.py:32-34, then .mean() of a scalar);
+ * kl_out_dev nullable.  cond_mode POINT only (ER_ERR_UNSUPPORTED otherwise); conds_dev = float[B, n_points, 3]. */
+int er_point_latent(er_ctx* ctx, const float* conds_dev, int batch, int n_points, float* latent_out_dev,
+                    float* kl_out_dev, void* stream);
+
 /* logits[:, -1, :].float() of the most recent forward (prefill or er_feed): float[B, vocab]. */
 int er_logits(er_ctx* ctx, float* logits_out_dev, void* stream);
 
@@ -314,6 +333,10 @@ int er_k_layernorm(const float* x_dev, const float* w_dev, const float* b_dev, f
                    int rows, int cols, float eps, void* stream);
 /* rows of scores[rows, ld]: softmax over the first n_valid(row) columns (causal: row+1+causal_offset), zeros after */
 int er_k_softmax(float* s_dev, int rows, int cols, int ld, int causal, void* stream);
+/* er_score's head on given logits float[B,S,V] (V <= 1088): nll / pred per position as er_score defines them; loss_out_dev
+ * (nullable) = {mean NLL over supervised positions, count} from the fixed-order double reduction */
+int er_k_score_rows(const float* logits_dev, const int32_t* labels_dev, int batch, int seq_len, int vocab, float* nll_out_dev,
+                    int32_t* pred_out_dev, float* loss_out_dev, void* stream);
 /* one sampling-head step on given logits float[B,V]; state arrays are int[B] on device */
 int er_k_sample_head(const float* logits_dev, const er_decode_params* p, int vocab, int eos, int pad,
                      int batch, int step, const int32_t* last_tok_host, const int32_t* counter_host,
