@@ -71,6 +71,20 @@ struct Buf {   // grow-only device scratch
     size_t n = 0;
 };
 
+// PointEncoderEmbed (core/transformer/point.py:172-206): weights, shape and scratch.  Embedded in er_ctx (cond_mode POINT) and, after
+// er_dit_attach_point_encoder, in er_dit_ctx; the same helpers (pe_register_keys / pe_load_tensor / point_latent_chunk) serve both.
+struct PointEnc {
+    int PH = 0, heads = 0, Lq = 0, LD = 0, freq = 0;     // point_hidden_dim, point_num_heads, latent size / dim, point_freq_dim
+    float eps = 1e-5f;
+    float *query = nullptr, *basis = nullptr, *mlp_w = nullptr, *mlp_b = nullptr, *ln_w = nullptr, *ln_b = nullptr;
+    float *ca_ln1_w = nullptr, *ca_ln1_b = nullptr, *ca_ln2_w = nullptr, *ca_ln2_b = nullptr;
+    float *ca_q_w = nullptr, *ca_q_b = nullptr, *ca_k_w = nullptr, *ca_k_b = nullptr, *ca_v_w = nullptr, *ca_v_b = nullptr,
+          *ca_o_w = nullptr, *ca_o_b = nullptr;
+    float *ff0_w = nullptr, *ff0_b = nullptr, *ff2_w = nullptr, *ff2_b = nullptr, *lin_w = nullptr, *lin_b = nullptr;
+    int kpad = 0;            // padded input width of point_embed.mlp (51 -> 64)
+    Buf a0, x, k, v, qln, q, sc, att, l, ln, u, g, lat;   // scratch of point_latent_chunk; lat = the latent mean [nb][Lq][LD]
+};
+
 struct er_ctx {
     er_config cfg{};
     int device = 0;
@@ -82,14 +96,7 @@ struct er_ctx {
     _Float16* lm_head_h = nullptr;
     bool fast = false;       // fp16 weights + fp16 KV cache, fp32 accumulate
     float *proj_w = nullptr, *proj_b = nullptr, *normc_w = nullptr, *normc_b = nullptr;
-    // point encoder
-    float *pe_query = nullptr, *pe_basis = nullptr, *pe_mlp_w = nullptr, *pe_mlp_b = nullptr, *pe_ln_w = nullptr,
-          *pe_ln_b = nullptr;
-    float *ca_ln1_w = nullptr, *ca_ln1_b = nullptr, *ca_ln2_w = nullptr, *ca_ln2_b = nullptr;
-    float *ca_q_w = nullptr, *ca_q_b = nullptr, *ca_k_w = nullptr, *ca_k_b = nullptr, *ca_v_w = nullptr, *ca_v_b = nullptr,
-          *ca_o_w = nullptr, *ca_o_b = nullptr;
-    float *ff0_w = nullptr, *ff0_b = nullptr, *ff2_w = nullptr, *ff2_b = nullptr, *lin_w = nullptr, *lin_b = nullptr;
-    int pe_kpad = 0;         // padded input width of point_embed.mlp (51 -> 64)
+    PointEnc pe;             // point encoder (cond_mode POINT)
     std::map<std::string, bool> need;   // required keys -> loaded?
     std::vector<void*> owned;           // every hipMalloc'd weight block
     // KV cache
@@ -138,7 +145,7 @@ struct er_ctx {
     float last_decode_ms = 0.f;
     // scratch for prefill / encoder
     Buf p_hi, p_lo;           // fast-mode prefill: hi / lo fp16 halves of the activation a Linear is about to read (LDS-DMA GEMM, split form)
-    Buf p_h, p_q, p_a, p_y, p_f, p_sc, p_qkv, p_ap, p_aml, e_a0, e_x, e_k, e_v, e_qln, e_q, e_sc, e_att, e_l, e_ln, e_u, e_g, e_lat, e_tmp, e_ids, e_stage;
+    Buf p_h, p_q, p_a, p_y, p_f, p_sc, p_qkv, p_ap, p_aml, e_tmp, e_ids, e_stage;
     Buf s_lg;                 // er_score: logits of every position when the caller passes no buffer for them
 };
 
@@ -155,6 +162,11 @@ static int ensure(Buf& b, size_t n) {
     return 0;
 }
 
+static void pe_free(PointEnc& p) {
+    for (Buf* b : {&p.a0, &p.x, &p.k, &p.v, &p.qln, &p.q, &p.sc, &p.att, &p.l, &p.ln, &p.u, &p.g, &p.lat})
+        if (b->p) { hipFree(b->p); b->p = nullptr; b->n = 0; }
+}
+
 static hipStream_t pick(er_ctx* c, void* s) { return s ? (hipStream_t)s : c->own_stream; }
 
 extern "C" int er_abi_version(void) { return ER_ABI_VERSION; }
@@ -164,6 +176,25 @@ static const char* kKindNames[ER_NUM_KERNEL_KINDS] = {"qkv_gemv", "attn_decode",
                                                       "fc1_gemv", "fc2_gemv", "lm_head_gemv", "sample_head"};
 extern "C" const char* er_kernel_kind_name(int k) { return (k >= 0 && k < ER_NUM_KERNEL_KINDS) ? kKindNames[k] : "?"; }
 
+// every point_encoder.* key PointEncoderEmbed's state_dict holds, as "required, not loaded yet"
+static void pe_register_keys(std::map<std::string, bool>& n) {
+    auto lin = [&](const std::string& p) {
+        n[p + ".weight"] = false;
+        n[p + ".bias"] = false;
+    };
+    const std::string pe = "point_encoder";
+    n[pe + ".query_embed"] = false;
+    n[pe + ".point_embed.basis"] = false;
+    lin(pe + ".point_embed.mlp");
+    lin(pe + ".ln");
+    lin(pe + ".cross_att.ln1");
+    lin(pe + ".cross_att.ln2");
+    for (const char* p : {"q_proj", "k_proj", "v_proj", "out_proj"}) lin(pe + ".cross_att.att." + p);
+    lin(pe + ".cross_att.mlp.net.0");
+    lin(pe + ".cross_att.mlp.net.2");
+    lin(pe + ".linear");
+}
+
 static void register_keys(er_ctx* c) {
     auto& n = c->need;
     const er_config& g = c->cfg;
@@ -171,19 +202,7 @@ static void register_keys(er_ctx* c) {
         n[p + ".weight"] = false;
         if (bias) n[p + ".bias"] = false;
     };
-    if (g.cond_mode == ER_COND_POINT) {
-        const std::string pe = "point_encoder";
-        n[pe + ".query_embed"] = false;
-        n[pe + ".point_embed.basis"] = false;
-        lin(pe + ".point_embed.mlp");
-        lin(pe + ".ln");
-        lin(pe + ".cross_att.ln1");
-        lin(pe + ".cross_att.ln2");
-        for (const char* p : {"q_proj", "k_proj", "v_proj", "out_proj"}) lin(pe + ".cross_att.att." + p);
-        lin(pe + ".cross_att.mlp.net.0");
-        lin(pe + ".cross_att.mlp.net.2");
-        lin(pe + ".linear");
-    }
+    if (g.cond_mode == ER_COND_POINT) pe_register_keys(n);
     if (g.cond_mode != ER_COND_NONE) {
         lin("proj_cond");
         lin("norm_cond");
@@ -231,6 +250,8 @@ extern "C" int er_create(const er_config* cfg, int device, er_ctx** out) {
     c->fast = fast;
     c->kv_esz = fast ? 2 : 4;
     c->layers.resize(cfg->num_layers);
+    c->pe.PH = cfg->point_hidden_dim; c->pe.heads = cfg->point_num_heads; c->pe.Lq = cfg->point_latent_size;
+    c->pe.LD = cfg->point_latent_dim; c->pe.freq = cfg->point_freq_dim; c->pe.eps = cfg->ln_eps;
     const char* ng = getenv("ER_NO_GRAPH");
     c->use_graph = !(ng && ng[0] == '1');
     auto env_int = [](const char* name, int dflt) { const char* v = getenv(name); return (v && v[0]) ? atoi(v) : dflt; };
@@ -285,9 +306,10 @@ extern "C" int er_destroy(er_ctx* c) {
     hipDeviceSynchronize();
     free_kv(c);
     for (void* p : c->owned) hipFree(p);
-    for (Buf* b : {&c->p_hi, &c->p_lo, &c->p_h, &c->p_q, &c->p_a, &c->p_y, &c->p_f, &c->p_sc, &c->p_qkv, &c->p_ap, &c->p_aml, &c->e_a0, &c->e_x, &c->e_k, &c->e_v, &c->e_qln,
-                   &c->e_q, &c->e_sc, &c->e_att, &c->e_l, &c->e_ln, &c->e_u, &c->e_g, &c->e_lat, &c->e_tmp, &c->e_ids, &c->e_stage, &c->s_lg})
+    for (Buf* b : {&c->p_hi, &c->p_lo, &c->p_h, &c->p_q, &c->p_a, &c->p_y, &c->p_f, &c->p_sc, &c->p_qkv, &c->p_ap, &c->p_aml,
+                   &c->e_tmp, &c->e_ids, &c->e_stage, &c->s_lg})
         if (b->p) hipFree(b->p);
+    pe_free(c->pe);
     if (c->ev0) hipEventDestroy(c->ev0);
     if (c->ev1) hipEventDestroy(c->ev1);
     if (c->h_pinned) hipHostFree(c->h_pinned);
@@ -354,6 +376,67 @@ __global__ void cvt_streamed_kernel(const void* src, int dtype, float* dst32, _F
     }
 }
 
+// One point_encoder.* tensor into p: src = its raw bytes on the device (dtype, n elements); data / on_device = the caller's copy (the
+// small point_embed.mlp weight is padded on the host).  Plain fp32 storage in every precision.  Returns 1 for a key that is not the
+// encoder's.  The blocks are recorded in `owned`; the copies are complete when this returns (stream st is synchronised).
+static int pe_load_tensor(PointEnc& p, std::vector<void*>& owned, const std::string& key, const void* src, const void* data, int dtype,
+                          size_t n, int on_device, hipStream_t st) {
+    const int PH = p.PH;
+    const unsigned cgrid = (unsigned)std::min<size_t>((n + 255) / 256, 4096);
+    auto put = [&](float** dst, size_t want) -> int {
+        if (n != want) return fail(ER_ERR_INVALID, "er_load_tensor(%s): %zu elements, expected %zu", key.c_str(), n, want);
+        if (!*dst) {
+            HIPCHK(hipMalloc(dst, want * sizeof(float)));
+            owned.push_back(*dst);
+        }
+        hipLaunchKernelGGL(cvt_f32_kernel, dim3(cgrid), dim3(256), 0, st, src, dtype, *dst, want);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(st));
+        return 0;
+    };
+    if (key == "point_encoder.query_embed") return put(&p.query, (size_t)p.Lq * PH);
+    if (key == "point_encoder.point_embed.basis") return put(&p.basis, (size_t)3 * p.freq);
+    if (key == "point_encoder.point_embed.mlp.weight") {
+        // [PH][2F+3] -> zero-padded [PH][kpad] so the GEMM K is a multiple of 16
+        const int kin = 2 * p.freq + 3;
+        p.kpad = (kin + 15) / 16 * 16;
+        if (n != (size_t)PH * kin) return fail(ER_ERR_INVALID, "er_load_tensor(%s): %zu elements, expected %zu", key.c_str(), n, (size_t)PH * kin);
+        int err = 0;
+        std::vector<float> h = to_f32_host(data, dtype, n, on_device, &err);     // small tensor: padded on the host
+        if (err) return fail(ER_ERR_HIP, "er_load_tensor(%s): device read failed", key.c_str());
+        std::vector<float> padded((size_t)PH * p.kpad, 0.f);
+        for (int r = 0; r < PH; ++r) memcpy(&padded[(size_t)r * p.kpad], &h[(size_t)r * kin], kin * 4);
+        if (!p.mlp_w) {
+            HIPCHK(hipMalloc(&p.mlp_w, padded.size() * sizeof(float)));
+            owned.push_back(p.mlp_w);
+        }
+        HIPCHK(hipMemcpy(p.mlp_w, padded.data(), padded.size() * 4, hipMemcpyHostToDevice));
+        return 0;
+    }
+    if (key == "point_encoder.point_embed.mlp.bias") return put(&p.mlp_b, PH);
+    if (key == "point_encoder.ln.weight") return put(&p.ln_w, PH);
+    if (key == "point_encoder.ln.bias") return put(&p.ln_b, PH);
+    if (key == "point_encoder.cross_att.ln1.weight") return put(&p.ca_ln1_w, PH);
+    if (key == "point_encoder.cross_att.ln1.bias") return put(&p.ca_ln1_b, PH);
+    if (key == "point_encoder.cross_att.ln2.weight") return put(&p.ca_ln2_w, PH);
+    if (key == "point_encoder.cross_att.ln2.bias") return put(&p.ca_ln2_b, PH);
+    if (key == "point_encoder.cross_att.att.q_proj.weight") return put(&p.ca_q_w, (size_t)PH * PH);
+    if (key == "point_encoder.cross_att.att.q_proj.bias") return put(&p.ca_q_b, PH);
+    if (key == "point_encoder.cross_att.att.k_proj.weight") return put(&p.ca_k_w, (size_t)PH * PH);
+    if (key == "point_encoder.cross_att.att.k_proj.bias") return put(&p.ca_k_b, PH);
+    if (key == "point_encoder.cross_att.att.v_proj.weight") return put(&p.ca_v_w, (size_t)PH * PH);
+    if (key == "point_encoder.cross_att.att.v_proj.bias") return put(&p.ca_v_b, PH);
+    if (key == "point_encoder.cross_att.att.out_proj.weight") return put(&p.ca_o_w, (size_t)PH * PH);
+    if (key == "point_encoder.cross_att.att.out_proj.bias") return put(&p.ca_o_b, PH);
+    if (key == "point_encoder.cross_att.mlp.net.0.weight") return put(&p.ff0_w, (size_t)8 * PH * PH);
+    if (key == "point_encoder.cross_att.mlp.net.0.bias") return put(&p.ff0_b, (size_t)8 * PH);
+    if (key == "point_encoder.cross_att.mlp.net.2.weight") return put(&p.ff2_w, (size_t)PH * 4 * PH);
+    if (key == "point_encoder.cross_att.mlp.net.2.bias") return put(&p.ff2_b, PH);
+    if (key == "point_encoder.linear.weight") return put(&p.lin_w, (size_t)p.LD * PH);
+    if (key == "point_encoder.linear.bias") return put(&p.lin_b, p.LD);
+    return 1;
+}
+
 extern "C" int er_load_tensor(er_ctx* c, const char* key_c, const void* data, int dtype, int ndim, const int64_t* shape,
                               int on_device) {
     if (!c || !key_c || !data || ndim < 1 || ndim > 4) return fail(ER_ERR_INVALID, "er_load_tensor: bad argument");
@@ -366,7 +449,7 @@ extern "C" int er_load_tensor(er_ctx* c, const char* key_c, const void* data, in
     size_t n = 1;
     for (int i = 0; i < ndim; ++i) n *= (size_t)shape[i];
     const er_config& g = c->cfg;
-    const int H = g.hidden_dim, I = g.intermediate_dim, PH = g.point_hidden_dim;
+    const int H = g.hidden_dim, I = g.intermediate_dim;
     const size_t esz = (dtype == ER_F32) ? 4 : 2;
     // the tensor's raw bytes on the device: the caller's buffer, or one upload into the grow-only staging block
     const void* src = data;
@@ -449,41 +532,10 @@ extern "C" int er_load_tensor(er_ctx* c, const char* key_c, const void* data, in
     else if (key == "proj_cond.bias") rc = put(&c->proj_b, H);
     else if (key == "norm_cond.weight") rc = put(&c->normc_w, H);
     else if (key == "norm_cond.bias") rc = put(&c->normc_b, H);
-    else if (key == "point_encoder.query_embed") rc = put(&c->pe_query, (size_t)g.point_latent_size * PH);
-    else if (key == "point_encoder.point_embed.basis") rc = put(&c->pe_basis, (size_t)3 * g.point_freq_dim);
-    else if (key == "point_encoder.point_embed.mlp.weight") {
-        // [PH][2F+3] -> zero-padded [PH][kpad] so the GEMM K is a multiple of 16
-        const int kin = 2 * g.point_freq_dim + 3;
-        c->pe_kpad = (kin + 15) / 16 * 16;
-        ERCHK(expect((size_t)PH * kin));
-        int err = 0;
-        std::vector<float> h = to_f32_host(data, dtype, n, on_device, &err);     // small tensor: padded on the host
-        if (err) return fail(ER_ERR_HIP, "er_load_tensor(%s): device read failed", key_c);
-        std::vector<float> padded((size_t)PH * c->pe_kpad, 0.f);
-        for (int r = 0; r < PH; ++r) memcpy(&padded[(size_t)r * c->pe_kpad], &h[(size_t)r * kin], kin * 4);
-        if (!c->pe_mlp_w) ERCHK(dev_alloc(c, &c->pe_mlp_w, padded.size()));
-        HIPCHK(hipMemcpy(c->pe_mlp_w, padded.data(), padded.size() * 4, hipMemcpyHostToDevice));
-    } else if (key == "point_encoder.point_embed.mlp.bias") rc = put(&c->pe_mlp_b, PH);
-    else if (key == "point_encoder.ln.weight") rc = put(&c->pe_ln_w, PH);
-    else if (key == "point_encoder.ln.bias") rc = put(&c->pe_ln_b, PH);
-    else if (key == "point_encoder.cross_att.ln1.weight") rc = put(&c->ca_ln1_w, PH);
-    else if (key == "point_encoder.cross_att.ln1.bias") rc = put(&c->ca_ln1_b, PH);
-    else if (key == "point_encoder.cross_att.ln2.weight") rc = put(&c->ca_ln2_w, PH);
-    else if (key == "point_encoder.cross_att.ln2.bias") rc = put(&c->ca_ln2_b, PH);
-    else if (key == "point_encoder.cross_att.att.q_proj.weight") rc = put(&c->ca_q_w, (size_t)PH * PH);
-    else if (key == "point_encoder.cross_att.att.q_proj.bias") rc = put(&c->ca_q_b, PH);
-    else if (key == "point_encoder.cross_att.att.k_proj.weight") rc = put(&c->ca_k_w, (size_t)PH * PH);
-    else if (key == "point_encoder.cross_att.att.k_proj.bias") rc = put(&c->ca_k_b, PH);
-    else if (key == "point_encoder.cross_att.att.v_proj.weight") rc = put(&c->ca_v_w, (size_t)PH * PH);
-    else if (key == "point_encoder.cross_att.att.v_proj.bias") rc = put(&c->ca_v_b, PH);
-    else if (key == "point_encoder.cross_att.att.out_proj.weight") rc = put(&c->ca_o_w, (size_t)PH * PH);
-    else if (key == "point_encoder.cross_att.att.out_proj.bias") rc = put(&c->ca_o_b, PH);
-    else if (key == "point_encoder.cross_att.mlp.net.0.weight") rc = put(&c->ff0_w, (size_t)8 * PH * PH);
-    else if (key == "point_encoder.cross_att.mlp.net.0.bias") rc = put(&c->ff0_b, (size_t)8 * PH);
-    else if (key == "point_encoder.cross_att.mlp.net.2.weight") rc = put(&c->ff2_w, (size_t)PH * 4 * PH);
-    else if (key == "point_encoder.cross_att.mlp.net.2.bias") rc = put(&c->ff2_b, PH);
-    else if (key == "point_encoder.linear.weight") rc = put(&c->lin_w, (size_t)g.point_latent_dim * PH);
-    else if (key == "point_encoder.linear.bias") rc = put(&c->lin_b, g.point_latent_dim);
+    else if (key.rfind("point_encoder.", 0) == 0) {
+        rc = pe_load_tensor(c->pe, c->owned, key, src, data, dtype, n, on_device, c->own_stream);
+        if (rc == 1) return 1;
+    }
     else return 1;
     if (rc < 0) return rc;
     it->second = true;
@@ -1073,67 +1125,67 @@ static int attention_full(const float* Q, int ldq, const float* Kp, int ldk, lon
 
 // ------------------------------------------------------------------------------------ encode_cond
 // PointEncoderEmbed (core/transformer/point.py:186-206) of nb samples of N points each: the latent mean (posterior.mode(), :201)
-// into c->e_lat [nb][Lq][LD].  Shared by er_encode_cond (which projects it, core/models.py:124) and er_point_latent.
-static int point_latent_chunk(er_ctx* c, const float* pts, int nb, int N, hipStream_t st) {
-    const er_config& g = c->cfg;
-    const int PH = g.point_hidden_dim, Lq = g.point_latent_size, LD = g.point_latent_dim;
-    const int PHh = g.point_num_heads > 0 ? g.point_num_heads : 1, PD = PH / PHh;
+// into p.lat [nb][Lq][LD].  Shared by er_encode_cond (which projects it, core/models.py:124), er_point_latent and
+// er_dit_point_latent.
+static int point_latent_chunk(PointEnc& p, const float* pts, int nb, int N, hipStream_t st) {
+    const int PH = p.PH, Lq = p.Lq, LD = p.LD;
+    const int PHh = p.heads > 0 ? p.heads : 1, PD = PH / PHh;
     if (N <= 0) return fail(ER_ERR_INVALID, "n_points must be > 0");
     const size_t R = (size_t)nb * N, RQ = (size_t)nb * Lq;
-    ERCHK(ensure(c->e_a0, R * c->pe_kpad));
-    ERCHK(ensure(c->e_x, R * PH));
-    ERCHK(ensure(c->e_k, R * PH));
-    ERCHK(ensure(c->e_v, R * PH));
-    ERCHK(ensure(c->e_qln, (size_t)Lq * PH));
-    ERCHK(ensure(c->e_q, (size_t)Lq * PH));
-    ERCHK(ensure(c->e_att, RQ * PH));
-    ERCHK(ensure(c->e_l, RQ * PH));
-    ERCHK(ensure(c->e_ln, RQ * PH));
-    ERCHK(ensure(c->e_u, RQ * 8 * PH));
-    ERCHK(ensure(c->e_g, RQ * 4 * PH));
-    ERCHK(ensure(c->e_lat, RQ * LD));
+    ERCHK(ensure(p.a0, R * p.kpad));
+    ERCHK(ensure(p.x, R * PH));
+    ERCHK(ensure(p.k, R * PH));
+    ERCHK(ensure(p.v, R * PH));
+    ERCHK(ensure(p.qln, (size_t)Lq * PH));
+    ERCHK(ensure(p.q, (size_t)Lq * PH));
+    ERCHK(ensure(p.att, RQ * PH));
+    ERCHK(ensure(p.l, RQ * PH));
+    ERCHK(ensure(p.ln, RQ * PH));
+    ERCHK(ensure(p.u, RQ * 8 * PH));
+    ERCHK(ensure(p.g, RQ * 4 * PH));
+    ERCHK(ensure(p.lat, RQ * LD));
     // x = ln(point_embed(pts))                                          point.py:194
-    hipLaunchKernelGGL(point_embed_kernel, dim3(ew_grid((long long)R * c->pe_kpad)), dim3(ER_WG), 0, st, pts,
-                       c->pe_basis, c->e_a0.p, (long long)R, g.point_freq_dim, c->pe_kpad);
+    hipLaunchKernelGGL(point_embed_kernel, dim3(ew_grid((long long)R * p.kpad)), dim3(ER_WG), 0, st, pts,
+                       p.basis, p.a0.p, (long long)R, p.freq, p.kpad);
     HIPRET(hipGetLastError());
-    HIPRET(linear(c->e_a0.p, c->pe_kpad, c->pe_mlp_w, c->pe_mlp_b, c->e_x.p, PH, (int)R, PH, c->pe_kpad, false, nullptr, 0, st));
-    HIPRET(launch_layernorm(c->e_x.p, c->pe_ln_w, c->pe_ln_b, c->e_x.p, (int)R, PH, PH, PH, g.ln_eps, st));
+    HIPRET(linear(p.a0.p, p.kpad, p.mlp_w, p.mlp_b, p.x.p, PH, (int)R, PH, p.kpad, false, nullptr, 0, st));
+    HIPRET(launch_layernorm(p.x.p, p.ln_w, p.ln_b, p.x.p, (int)R, PH, PH, PH, p.eps, st));
     // cross attention: l = q + out_proj(attn(q_proj(ln1(q)), k_proj(x), v_proj(x)))   point.py:123-124
     // (the learned queries and their projection are the same for every sample: computed once)
-    HIPRET(launch_layernorm(c->pe_query, c->ca_ln1_w, c->ca_ln1_b, c->e_qln.p, Lq, PH, PH, PH, g.ln_eps, st));
-    HIPRET(linear(c->e_qln.p, PH, c->ca_q_w, c->ca_q_b, c->e_q.p, PH, Lq, PH, PH, false, nullptr, 0, st));
-    HIPRET(linear(c->e_x.p, PH, c->ca_k_w, c->ca_k_b, c->e_k.p, PH, (int)R, PH, PH, false, nullptr, 0, st));
-    HIPRET(linear(c->e_x.p, PH, c->ca_v_w, c->ca_v_b, c->e_v.p, PH, (int)R, PH, PH, false, nullptr, 0, st));
+    HIPRET(launch_layernorm(p.query, p.ca_ln1_w, p.ca_ln1_b, p.qln.p, Lq, PH, PH, PH, p.eps, st));
+    HIPRET(linear(p.qln.p, PH, p.ca_q_w, p.ca_q_b, p.q.p, PH, Lq, PH, PH, false, nullptr, 0, st));
+    HIPRET(linear(p.x.p, PH, p.ca_k_w, p.ca_k_b, p.k.p, PH, (int)R, PH, PH, false, nullptr, 0, st));
+    HIPRET(linear(p.x.p, PH, p.ca_v_w, p.ca_v_b, p.v.p, PH, (int)R, PH, PH, false, nullptr, 0, st));
     if (PD == 64 || PD == 96) {
         Flash32Args f{};
-        f.Q = c->e_q.p; f.ldq = PH; f.qs_b = 0; f.qs_h = PD;                      // queries shared by the batch
-        f.K = c->e_k.p; f.ldk = PH; f.ks_b = (long long)N * PH; f.ks_h = PD;
-        f.V = c->e_v.p; f.ldv = PH; f.vs_b = (long long)N * PH; f.vs_h = PD;
-        f.O = c->e_att.p; f.ldo = PH; f.os_b = (long long)Lq * PH; f.os_h = PD;
+        f.Q = p.q.p; f.ldq = PH; f.qs_b = 0; f.qs_h = PD;                      // queries shared by the batch
+        f.K = p.k.p; f.ldk = PH; f.ks_b = (long long)N * PH; f.ks_h = PD;
+        f.V = p.v.p; f.ldv = PH; f.vs_b = (long long)N * PH; f.vs_h = PD;
+        f.O = p.att.p; f.ldo = PH; f.os_b = (long long)Lq * PH; f.os_h = PD;
         f.N = Lq; f.M = N; f.sqrt_d = sqrtf((float)PD); f.causal_off = 0;
         HIPRET(launch_flash_attn_f32(f, PD, false, PHh, nb, st));
     } else {
         const int ldS = (N + 15) / 16 * 16;
-        ERCHK(ensure(c->e_sc, (size_t)PHh * Lq * ldS));
+        ERCHK(ensure(p.sc, (size_t)PHh * Lq * ldS));
         for (int b = 0; b < nb; ++b)
-            ERCHK(attention_full(c->e_q.p, PH, c->e_k.p + (size_t)b * N * PH, PH, PD, c->e_v.p + (size_t)b * N * PH, PH, PD,
-                                 c->e_att.p + (size_t)b * Lq * PH, PH, c->e_sc.p, PHh, PD, Lq, N, false, st));
+            ERCHK(attention_full(p.q.p, PH, p.k.p + (size_t)b * N * PH, PH, PD, p.v.p + (size_t)b * N * PH, PH, PD,
+                                 p.att.p + (size_t)b * Lq * PH, PH, p.sc.p, PHh, PD, Lq, N, false, st));
     }
     {   // l = query_embed + out_proj(att): the residual table has Lq rows shared by every sample
         GemmArgs ga = gemm_args_default();
-        ga.A = c->e_att.p; ga.B = c->ca_o_w; ga.C = c->e_l.p; ga.bias = c->ca_o_b; ga.resid = c->pe_query; ga.resid_mod = Lq;
+        ga.A = p.att.p; ga.B = p.ca_o_w; ga.C = p.l.p; ga.bias = p.ca_o_b; ga.resid = p.query; ga.resid_mod = Lq;
         ga.M = (int)RQ; ga.N = PH; ga.K = PH; ga.lda = PH; ga.ldb = PH; ga.ldc = PH; ga.ldr = PH;
         HIPRET(launch_gemm(ga, 1, st));
     }
     // l = l + net2(GEGLU(net0(ln2(l))))                                   point.py:125, 68-84
-    HIPRET(launch_layernorm(c->e_l.p, c->ca_ln2_w, c->ca_ln2_b, c->e_ln.p, (int)RQ, PH, PH, PH, g.ln_eps, st));
-    HIPRET(linear(c->e_ln.p, PH, c->ff0_w, c->ff0_b, c->e_u.p, 8 * PH, (int)RQ, 8 * PH, PH, false, nullptr, 0, st));
-    hipLaunchKernelGGL(geglu_kernel, dim3(ew_grid((long long)RQ * 4 * PH)), dim3(ER_WG), 0, st, c->e_u.p, c->e_g.p,
+    HIPRET(launch_layernorm(p.l.p, p.ca_ln2_w, p.ca_ln2_b, p.ln.p, (int)RQ, PH, PH, PH, p.eps, st));
+    HIPRET(linear(p.ln.p, PH, p.ff0_w, p.ff0_b, p.u.p, 8 * PH, (int)RQ, 8 * PH, PH, false, nullptr, 0, st));
+    hipLaunchKernelGGL(geglu_kernel, dim3(ew_grid((long long)RQ * 4 * PH)), dim3(ER_WG), 0, st, p.u.p, p.g.p,
                        (long long)RQ, 4 * PH);
     HIPRET(hipGetLastError());
-    HIPRET(linear(c->e_g.p, 4 * PH, c->ff2_w, c->ff2_b, c->e_l.p, PH, (int)RQ, PH, 4 * PH, false, c->e_l.p, PH, st));
+    HIPRET(linear(p.g.p, 4 * PH, p.ff2_w, p.ff2_b, p.l.p, PH, (int)RQ, PH, 4 * PH, false, p.l.p, PH, st));
     // latent mean = linear(l)                                              point.py:201
-    HIPRET(linear(c->e_l.p, PH, c->lin_w, c->lin_b, c->e_lat.p, LD, (int)RQ, LD, PH, false, nullptr, 0, st));
+    HIPRET(linear(p.l.p, PH, p.lin_w, p.lin_b, p.lat.p, LD, (int)RQ, LD, PH, false, nullptr, 0, st));
     return 0;
 }
 
@@ -1157,8 +1209,8 @@ extern "C" int er_encode_cond(er_ctx* c, const float* conds, int B, int n_points
         const int nb = std::min(ENC_CHUNK, B - b0);
         const float* lat = nullptr;   // [nb][Lq][LD]
         if (g.cond_mode == ER_COND_POINT) {
-            ERCHK(point_latent_chunk(c, conds + (size_t)b0 * n_points * 3, nb, n_points, st));
-            lat = c->e_lat.p;
+            ERCHK(point_latent_chunk(c->pe, conds + (size_t)b0 * n_points * 3, nb, n_points, st));
+            lat = c->pe.lat.p;
         } else if (g.cond_mode == ER_COND_POINT_LATENT) {
             lat = conds + (size_t)b0 * Lq * LD;
         }
@@ -1380,8 +1432,8 @@ extern "C" int er_point_latent(er_ctx* c, const float* conds, int B, int n_point
     constexpr int ENC_CHUNK = 32;        // as er_encode_cond
     for (int b0 = 0; b0 < B; b0 += ENC_CHUNK) {
         const int nb = std::min(ENC_CHUNK, B - b0);
-        ERCHK(point_latent_chunk(c, conds + (size_t)b0 * n_points * 3, nb, n_points, st));
-        HIPCHK(hipMemcpyAsync(latent_out + (size_t)b0 * per, c->e_lat.p, (size_t)nb * per * 4, hipMemcpyDeviceToDevice, st));
+        ERCHK(point_latent_chunk(c->pe, conds + (size_t)b0 * n_points * 3, nb, n_points, st));
+        HIPCHK(hipMemcpyAsync(latent_out + (size_t)b0 * per, c->pe.lat.p, (size_t)nb * per * 4, hipMemcpyDeviceToDevice, st));
     }
     if (kl_out) HIPRET(launch_score_reduce(latent_out, nullptr, (int)((size_t)B * per), 0, kl_out, st));
     return ER_OK;

@@ -3,6 +3,7 @@
 // Reference: core/transformer/dit.py (DiT, DiTLayer, TimestepEmbedding) and core/models_dit.py::MDiT.run.
 #pragma once
 #include "k_dit.h"
+#include "k_dit_loss.h"
 
 struct DitLayerW {
     float *sst = nullptr;                                   // scale_shift_table [6][C]
@@ -49,6 +50,12 @@ struct er_dit_ctx {
     const float** sst_ptrs = nullptr;      // device array of the layers' scale_shift_table pointers
     int kv2_mp = 0;                        // padded key count of the cross-attention V^T rows
     bool geglu_perm_valid = false;
+    int pred_type = ER_PRED_V_PREDICTION;  // what the DiT predicts (er_dit_set_prediction_type): the sampler's DDIM update and the loss target
+    // the reference's frozen point encoder (MDiT.point_encoder, core/models_dit.py:68-75), after er_dit_attach_point_encoder only
+    bool has_pe = false;
+    PointEnc pe;
+    std::map<std::string, bool> pe_need;   // its keys -> loaded?
+    Buf lcoef, lpart;                      // er_dit_loss: [sa | sb | w] per sample, partial sums (doubles)
 };
 
 static void dit_register(er_dit_ctx* c) {
@@ -139,8 +146,9 @@ extern "C" int er_dit_destroy(er_dit_ctx* c) {
         if (b->p) hipFree(b->p);
     for (Buf* b : {&c->x, &c->qkv, &c->att, &c->q2, &c->kv2, &c->u, &c->g, &c->sc, &c->tin, &c->temb0, &c->temb1, &c->temb,
                    &c->tsil, &c->tada, &c->gate, &c->t_dev, &c->xin, &c->pred, &c->czero, &c->ctmp, &c->x16, &c->att16, &c->g16,
-                   &c->qkv16, &c->vt16, &c->q2_16, &c->k2_16, &c->v2tmp16, &c->v2t16, &c->gates})
+                   &c->qkv16, &c->vt16, &c->q2_16, &c->k2_16, &c->v2tmp16, &c->v2t16, &c->gates, &c->lcoef, &c->lpart})
         if (b->p) hipFree(b->p);
+    pe_free(c->pe);
     if (c->own_stream) hipStreamDestroy(c->own_stream);
     delete c;
     return ER_OK;
@@ -151,6 +159,27 @@ extern "C" int er_dit_load_tensor(er_dit_ctx* c, const char* key, const void* da
     if (!c || !key || !data || ndim < 1 || ndim > 4) return fail(ER_ERR_INVALID, "er_dit_load_tensor: bad argument");
     HIPCHK(hipSetDevice(c->device));
     std::string k(key);
+    if (c->has_pe && k.rfind("point_encoder.", 0) == 0) {
+        auto pit = c->pe_need.find(k);
+        if (pit == c->pe_need.end()) return 1;
+        if (dtype != ER_F32 && dtype != ER_F16 && dtype != ER_BF16) return fail(ER_ERR_INVALID, "er_dit_load_tensor: dtype %d", dtype);
+        size_t n = 1;
+        for (int i = 0; i < ndim; ++i) n *= (size_t)shape[i];
+        const size_t esz = dtype == ER_F32 ? 4 : 2;
+        void* stage = nullptr;                 // the raw bytes on the device for the converting copy of pe_load_tensor
+        if (!on_device) {
+            HIPCHK(hipMalloc(&stage, n * esz));
+            if (hipMemcpy(stage, data, n * esz, hipMemcpyHostToDevice) != hipSuccess) {
+                hipFree(stage);
+                return fail(ER_ERR_HIP, "er_dit_load_tensor(%s): upload failed", key);
+            }
+        }
+        const int rc = pe_load_tensor(c->pe, c->owned, k, on_device ? data : stage, data, dtype, n, on_device, c->own_stream);
+        if (stage) hipFree(stage);
+        if (rc < 0) return rc;
+        pit->second = true;
+        return ER_OK;
+    }
     if (k.rfind("image_encoder.", 0) == 0 && k.find("image_encoder.vision_model.") != 0)
         k = "image_encoder.vision_model." + k.substr(strlen("image_encoder."));      // transformers >= 5 drops the prefix
     auto it = c->slots.find(k);
@@ -193,7 +222,91 @@ extern "C" int er_dit_finalize_weights(er_dit_ctx* c) {
     if (!c) return fail(ER_ERR_INVALID, "null ctx");
     for (auto& kv : c->slots)
         if (!kv.second.loaded) return fail(ER_ERR_MISSING, "tensor '%s' was never loaded", kv.first.c_str());
+    for (auto& kv : c->pe_need)
+        if (!kv.second) return fail(ER_ERR_MISSING, "tensor '%s' was never loaded (a point encoder is attached)", kv.first.c_str());
     return ER_OK;
+}
+
+extern "C" int er_dit_attach_point_encoder(er_dit_ctx* c, int point_hidden_dim, int point_num_heads, int point_freq_dim) {
+    if (!c) return fail(ER_ERR_INVALID, "null ctx");
+    if (c->has_pe) return fail(ER_ERR_INVALID, "er_dit_attach_point_encoder: a point encoder is already attached");
+    if (point_hidden_dim != 1024 || point_num_heads <= 0 || point_hidden_dim % point_num_heads)   // as er_create (cond_mode POINT)
+        return fail(ER_ERR_UNSUPPORTED, "point encoder width %d / heads %d not built (1024)", point_hidden_dim, point_num_heads);
+    if (point_freq_dim <= 0 || point_freq_dim % 3) return fail(ER_ERR_INVALID, "point_freq_dim %d must be a positive multiple of 3", point_freq_dim);
+    PointEnc& p = c->pe;
+    p.PH = point_hidden_dim; p.heads = point_num_heads; p.freq = point_freq_dim;
+    p.Lq = c->cfg.latent_size; p.LD = c->cfg.latent_dim; p.eps = 1e-5f;
+    pe_register_keys(c->pe_need);
+    c->has_pe = true;
+    return ER_OK;
+}
+
+extern "C" int er_dit_point_latent(er_dit_ctx* c, const float* points, int B, int n_points, float* latent_out, void* stream) {
+    if (!c || !points || !latent_out || B <= 0 || n_points <= 0) return fail(ER_ERR_INVALID, "er_dit_point_latent: bad argument");
+    if (!c->has_pe) return fail(ER_ERR_UNSUPPORTED, "er_dit_point_latent: no point encoder attached (er_dit_attach_point_encoder)");
+    ERCHK(er_dit_finalize_weights(c));
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t st = stream ? (hipStream_t)stream : c->own_stream;
+    const size_t per = (size_t)c->pe.Lq * c->pe.LD;
+    if ((long long)B * (long long)per > 0x7fffffffLL) return fail(ER_ERR_CAPACITY, "er_dit_point_latent: batch %d too large", B);
+    constexpr int ENC_CHUNK = 32;        // as er_point_latent
+    for (int b0 = 0; b0 < B; b0 += ENC_CHUNK) {
+        const int nb = std::min(ENC_CHUNK, B - b0);
+        ERCHK(point_latent_chunk(c->pe, points + (size_t)b0 * n_points * 3, nb, n_points, st));
+        HIPCHK(hipMemcpyAsync(latent_out + (size_t)b0 * per, c->pe.lat.p, (size_t)nb * per * 4, hipMemcpyDeviceToDevice, st));
+    }
+    return ER_OK;
+}
+
+extern "C" int er_dit_set_prediction_type(er_dit_ctx* c, int pred_type) {
+    if (!c) return fail(ER_ERR_INVALID, "null ctx");
+    if (pred_type != ER_PRED_V_PREDICTION && pred_type != ER_PRED_EPSILON)
+        return fail(ER_ERR_INVALID, "er_dit_set_prediction_type: %d is neither ER_PRED_V_PREDICTION nor ER_PRED_EPSILON", pred_type);
+    c->pred_type = pred_type;
+    return ER_OK;
+}
+
+constexpr int DIT_TRAIN_STEPS = 1000;     // num_train_timesteps of both schedulers (core/models_dit.py:80-101)
+
+// alphas_cumprod of the reference's DDPMScheduler / DDIMScheduler (scaled_linear betas 0.00085..0.012): the sampler's DDIM update and
+// the loss coefficients read this one table.  torch.linspace(sqrt(b0), sqrt(b1), T, fp32) ** 2 -> cumprod(1 - betas), all in fp32
+// like diffusers.
+static std::vector<float> dit_alphas_cumprod() {
+    const int T = DIT_TRAIN_STEPS;
+    std::vector<float> ac(T);
+    const float lo = (float)sqrt(0.00085), hi = (float)sqrt(0.012);
+    const float step = (hi - lo) / (float)(T - 1);
+    float prod = 1.0f;
+    for (int i = 0; i < T; ++i) {
+        const float r = (i < T / 2) ? lo + step * (float)i : hi - step * (float)(T - 1 - i);   // linspace is symmetric
+        const float beta = r * r;
+        prod *= (1.0f - beta);
+        ac[i] = prod;
+    }
+    return ac;
+}
+
+// Per-sample loss coefficients in fp32, as diffusers computes them (add_noise / get_velocity / compute_snr) and models_dit.py:165-177
+// weighs them: coef = [sa[B] | sb[B] | w[B]] with sa = sqrt(ac[t]), sb = sqrt(1 - ac[t]), snr = (sa / sb)^2 and
+// w = min(snr, gamma) / (snr + 1) (v-prediction) or / snr (epsilon); w = 1 when gamma is None (<= 0 or NaN).
+static int dit_loss_coefs(const int32_t* t, int B, int pred_type, float gamma, std::vector<float>& coef) {
+    const std::vector<float> ac = dit_alphas_cumprod();
+    coef.assign((size_t)3 * B, 0.f);
+    const bool weighted = gamma > 0.f;        // false for NaN too
+    for (int b = 0; b < B; ++b) {
+        if (t[b] < 0 || t[b] >= DIT_TRAIN_STEPS)
+            return fail(ER_ERR_INVALID, "timestep %d of sample %d is outside [0, %d)", t[b], b, DIT_TRAIN_STEPS);
+        const float a = ac[t[b]], sa = sqrtf(a), sb = sqrtf(1.0f - a);
+        float w = 1.0f;
+        if (weighted) {
+            const float r = sa / sb, snr = r * r, m = fminf(snr, gamma);
+            w = pred_type == ER_PRED_EPSILON ? m / snr : m / (snr + 1.0f);
+        }
+        coef[b] = sa;
+        coef[B + b] = sb;
+        coef[2 * B + b] = w;
+    }
+    return 0;
 }
 
 // Linear layer: fp32 MFMA, or (fast mode) fp16-input MFMA with the activation rounded to fp16 on the way in
@@ -553,21 +666,9 @@ extern "C" int er_dit_sample(er_dit_ctx* c, const float* cond, int B, int M, flo
     const er_dit_config& g = c->cfg;
     const int C = g.hidden_dim, N = g.latent_size, LD = g.latent_dim;
     const size_t nlat = (size_t)B * N * LD;
-    // DDIM tables (diffusers DDIMScheduler: scaled_linear betas in fp32, cumprod, leading spacing + offset 1)
-    const int T = 1000;
-    std::vector<float> ac(T);
-    {
-        // torch.linspace(sqrt(b0), sqrt(b1), T, fp32) ** 2 -> cumprod(1 - betas), all in fp32 like diffusers
-        const float lo = (float)sqrt(0.00085), hi = (float)sqrt(0.012);
-        const float step = (hi - lo) / (float)(T - 1);
-        float prod = 1.0f;
-        for (int i = 0; i < T; ++i) {
-            const float r = (i < T / 2) ? lo + step * (float)i : hi - step * (float)(T - 1 - i);   // linspace is symmetric
-            const float beta = r * r;
-            prod *= (1.0f - beta);
-            ac[i] = prod;
-        }
-    }
+    // DDIM tables (diffusers DDIMScheduler: leading spacing + offset 1)
+    const int T = DIT_TRAIN_STEPS;
+    const std::vector<float> ac = dit_alphas_cumprod();
     const int ratio = T / steps;
     // CFG batch: rows [0,B) = zero condition, rows [B,2B) = cond                   models_dit.py:211
     ERCHK(ensure(c->czero, (size_t)2 * B * M * C));
@@ -597,10 +698,80 @@ extern "C" int er_dit_sample(er_dit_ctx* c, const float* cond, int B, int M, flo
         if (dit_forward_impl(c, c->xin.p, B2, M, c->pred.p, c->temb.p + (size_t)k * B2 * C, c->tada.p + (size_t)k * B2 * 6 * C, st) < 0) return -1;
         const int prev = t - ratio;
         const float a_t = ac[t], a_p = prev >= 0 ? ac[prev] : ac[0];
-        hipLaunchKernelGGL(ddim_cfg_step_kernel, dim3((unsigned)((nlat + 255) / 256)), dim3(256), 0, st, latents, c->pred.p,
-                           (long long)nlat, guidance, sqrtf(a_t), sqrtf(1.0f - a_t), sqrtf(a_p), sqrtf(1.0f - a_p));
+        if (c->pred_type == ER_PRED_EPSILON)
+            hipLaunchKernelGGL(ddim_cfg_step_eps_kernel, dim3((unsigned)((nlat + 255) / 256)), dim3(256), 0, st, latents, c->pred.p,
+                               (long long)nlat, guidance, sqrtf(a_t), sqrtf(1.0f - a_t), sqrtf(a_p), sqrtf(1.0f - a_p));
+        else
+            hipLaunchKernelGGL(ddim_cfg_step_kernel, dim3((unsigned)((nlat + 255) / 256)), dim3(256), 0, st, latents, c->pred.p,
+                               (long long)nlat, guidance, sqrtf(a_t), sqrtf(1.0f - a_t), sqrtf(a_p), sqrtf(1.0f - a_p));
         HIPRET(hipGetLastError());
     }
     HIPCHK(hipStreamSynchronize(st));
+    return ER_OK;
+}
+
+// ------------------------------------------------------------------------------------ eval loss (MDiT.forward, core/models_dit.py:119-181)
+extern "C" int er_dit_loss(er_dit_ctx* c, const float* latents, const float* noise, const float* cond, const int32_t* timesteps, int B,
+                           int M, float snr_gamma, float* pred_out, float* mse_out, float* loss_out, void* stream) {
+    if (!c || !latents || !noise || !cond || !timesteps || !mse_out || !loss_out || B <= 0 || M <= 0)
+        return fail(ER_ERR_INVALID, "er_dit_loss: bad argument");
+    if (B > 65535) return fail(ER_ERR_CAPACITY, "er_dit_loss: batch %d too large", B);
+    std::vector<float> coef;
+    ERCHK(dit_loss_coefs(timesteps, B, c->pred_type, snr_gamma, coef));
+    ERCHK(er_dit_finalize_weights(c));
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t st = stream ? (hipStream_t)stream : c->own_stream;
+    const long long n = (long long)c->cfg.latent_size * c->cfg.latent_dim;
+    if ((long long)B * c->cfg.latent_size * 8 * c->cfg.hidden_dim > 0x7fffffffLL)      // the widest DiT activation (ff.net.0: 8 C per row)
+        return fail(ER_ERR_CAPACITY, "er_dit_loss: batch %d too large for 32-bit row indexing", B);
+    const int chunks = dit_loss_chunks(n);
+    ERCHK(ensure(c->lcoef, (size_t)3 * B));
+    ERCHK(ensure(c->lpart, (size_t)2 * B * chunks));
+    ERCHK(ensure(c->t_dev, (size_t)B));
+    ERCHK(ensure(c->xin, (size_t)B * n));
+    std::vector<float> th(B);
+    for (int b = 0; b < B; ++b) th[b] = (float)timesteps[b];
+    HIPCHK(hipMemcpyAsync(c->lcoef.p, coef.data(), coef.size() * sizeof(float), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(c->t_dev.p, th.data(), B * sizeof(float), hipMemcpyHostToDevice, st));
+    HIPCHK(hipStreamSynchronize(st));        // coef / th go out of scope
+    const float *sa = c->lcoef.p, *sb = sa + B, *w = sb + B;
+    float* pred = pred_out;
+    if (!pred) {
+        ERCHK(ensure(c->pred, (size_t)B * n));
+        pred = c->pred.p;
+    }
+    // noisy_latents = add_noise(nan_to_num(latents), noise, t); model_pred = dit(noisy_latents, cond, t)     models_dit.py:143-155
+    HIPRET(launch_dit_add_noise(latents, noise, c->xin.p, sa, sb, B, n, st));
+    ERCHK(dit_cross_kv(c, cond, B, M, st));
+    ERCHK(dit_time_embed(c, B, st));
+    if (dit_forward_impl(c, c->xin.p, B, M, pred, c->temb.p, c->tada.p, st) < 0) return -1;
+    HIPRET(launch_dit_loss(pred, latents, noise, sa, sb, w, B, n, c->pred_type, reinterpret_cast<double*>(c->lpart.p), mse_out, loss_out, st));
+    return ER_OK;
+}
+
+extern "C" int er_k_dit_loss(const float* pred, const float* x0, const float* eps, const int32_t* timesteps, int B, int n, int pred_type,
+                             float snr_gamma, float* mse_out, float* loss_out, void* stream) {
+    if (!pred || !eps || !timesteps || !mse_out || !loss_out || B <= 0 || B > 65535 || n <= 0 || n % 4 ||
+        (pred_type == ER_PRED_V_PREDICTION && !x0) || (pred_type != ER_PRED_V_PREDICTION && pred_type != ER_PRED_EPSILON))
+        return fail(ER_ERR_INVALID, "er_k_dit_loss: bad argument");
+    for (const void* p : {(const void*)pred, (const void*)x0, (const void*)eps})
+        if ((uintptr_t)p % 16) return fail(ER_ERR_INVALID, "er_k_dit_loss: operands must be 16-byte aligned");
+    std::vector<float> coef;
+    ERCHK(dit_loss_coefs(timesteps, B, pred_type, snr_gamma, coef));
+    hipStream_t st = (hipStream_t)stream;
+    const int chunks = dit_loss_chunks(n);
+    float* dcoef = nullptr;
+    double* part = nullptr;
+    HIPCHK(hipMalloc((void**)&dcoef, coef.size() * sizeof(float)));
+    if (hipMalloc((void**)&part, (size_t)B * chunks * sizeof(double)) != hipSuccess) {
+        hipFree(dcoef);
+        return fail(ER_ERR_HIP, "er_k_dit_loss: hipMalloc failed");
+    }
+    hipError_t e = hipMemcpyAsync(dcoef, coef.data(), coef.size() * sizeof(float), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = launch_dit_loss(pred, x0, eps, dcoef, dcoef + B, dcoef + 2 * B, B, n, pred_type, part, mse_out, loss_out, st);
+    const hipError_t e2 = hipStreamSynchronize(st);
+    hipFree(dcoef);
+    hipFree(part);
+    if (e != hipSuccess || e2 != hipSuccess) return fail(ER_ERR_HIP, "er_k_dit_loss: %s", hipGetErrorString(e != hipSuccess ? e : e2));
     return ER_OK;
 }

@@ -123,6 +123,18 @@ __global__ void ddim_cfg_step_kernel(float* latents, const float* pred, long lon
     latents[i] = sa_p * x0 + sb_p * eps;
 }
 
+// The same step for prediction_type 'epsilon' (diffusers DDIMScheduler.step, eta = 0): the model predicts the noise.
+//   eps = eps_uncond + g * (eps_cond - eps_uncond);  x0 = (x - sb_t*eps) / sa_t;  x <- sa_p*x0 + sb_p*eps
+__global__ void ddim_cfg_step_eps_kernel(float* latents, const float* pred, long long n, float guidance, float sa_t, float sb_t,
+                                         float sa_p, float sb_p) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float u = pred[i], c = pred[n + i], x = latents[i];
+    const float eps = u + guidance * (c - u);
+    const float x0 = (x - sb_t * eps) / sa_t;
+    latents[i] = sa_p * x0 + sb_p * eps;
+}
+
 }  // namespace er
 
 // ---------------------------------------------------------------------------------------------------

@@ -202,6 +202,21 @@ def score_rows(logits, labels):
     return nll, pred, loss
 
 
+def dit_loss(pred, x0, eps, timesteps, pred_type=native.ER_PRED_V_PREDICTION, snr_gamma=None):
+    """er_dit_loss's two loss kernels on given tensors [B, ...] fp32 (elements per sample a multiple of 4) -> (mse [B] unweighted,
+    loss [1] = mean of w * mse); snr_gamma None = unweighted."""
+    lib = native.load_library()
+    B = pred.shape[0]
+    n = pred[0].numel()
+    args = [t.to(pred.device, torch.float32).contiguous().clone() for t in (pred, x0, eps)]     # fresh (aligned) blocks
+    mse = torch.empty((B,), dtype=torch.float32, device=pred.device)
+    loss = torch.empty((1,), dtype=torch.float32, device=pred.device)
+    native.check(lib.er_k_dit_loss(*[native.ptr(t) for t in args], native.i32_array(torch.as_tensor(timesteps).flatten().tolist()), B, n,
+                                   int(pred_type), float("nan") if snr_gamma is None else float(snr_gamma), native.ptr(mse),
+                                   native.ptr(loss), _st()), "er_k_dit_loss")
+    return mse, loss
+
+
 def sample_head(logits, mode, grammar, step, last_tok, counter, unfinished, top_k=10, min_new=0, seed=0,
                 eos=2, pad=0):
     """One sampling-head step. Returns (next_tok, counter, unfinished) lists."""

@@ -5,14 +5,21 @@ classifier-free guidance -> latents ``[B, 2048, 64]`` that ``LMM.generate`` cons
 
 Built: the CLIP ViT-H/14 image encoder (``image_encoder.vision_model.*``; architecture only - its pretrained
 weights cannot be fetched here, so parity runs use synthetic weights), ``proj_cond``/``norm_cond``,
-``DiT.forward``, ``run`` (from noise, and the img2img branch with ``latents`` / ``strength``; ``num_repeat``).
-Out of scope: training ``forward``, background removal / recentering of the input photo (rembg, kiui: infer_dit.py:83-96).
+``DiT.forward``, ``run`` (from noise, and the img2img branch with ``latents`` / ``strength``; ``num_repeat``), both
+``noise_scheduler_predtype`` values, and ``forward`` in eval mode (core/models_dit.py:119-181, the loss main_dit.py's eval loop
+sums): on-device point encoding (``point_encoder=True``; the frozen PointEncoderEmbed), add_noise at the given or drawn timesteps,
+the DiT, and the min-SNR-weighted MSE against the v-prediction / epsilon target.  The point encoder runs in fp32 in both
+precisions (the reference runs it ``.half()``, core/models_dit.py:68-74).
+Out of scope: training (backward pass, CFG dropout), background removal / recentering of the input photo (rembg, kiui:
+infer_dit.py:83-96).
 """
 from __future__ import annotations
 
 import ctypes as C
+import dataclasses
 from typing import Dict, Optional
 
+import numpy as np
 import torch
 
 from . import native
@@ -26,22 +33,67 @@ def ddim_alphas_cumprod(num_train: int = 1000, beta_start: float = 0.00085, beta
     return torch.cumprod(1.0 - betas, dim=0)
 
 
+def dit_alphas_cumprod_f32() -> np.ndarray:
+    """The table the device sampler and loss read (csrc/er_dit.h, dit_alphas_cumprod): the same fp32 values as
+    ``ddim_alphas_cumprod`` up to the summation order of the cumulative product (<= 1e-6 relative), restated here operation by operation
+    so that host-side coefficients match the device's bit for bit."""
+    f = np.float32
+    lo, hi = f(np.sqrt(0.00085)), f(np.sqrt(0.012))
+    step = (hi - lo) / f(999)
+    out = np.empty(1000, dtype=np.float32)
+    prod = f(1.0)
+    for i in range(1000):
+        r = lo + step * f(i) if i < 500 else hi - step * f(999 - i)
+        prod = prod * (f(1.0) - r * r)
+        out[i] = prod
+    return out
+
+
+PREDICTION_TYPES = {"v_prediction": native.ER_PRED_V_PREDICTION, "epsilon": native.ER_PRED_EPSILON}
+
+
+def dit_loss_coefficients(timesteps, prediction_type: str = "v_prediction", snr_gamma: Optional[float] = 5.0):
+    """Per-sample coefficients of MDiT.forward (core/models_dit.py:143-177 with diffusers' add_noise / get_velocity / compute_snr),
+    in fp32 exactly as er_dit_loss computes them on the host: sa = sqrt(ac[t]), sb = sqrt(1 - ac[t]), snr = (sa / sb)^2 and the loss
+    weight w = min(snr, gamma) / (snr + 1) for v-prediction, / snr for epsilon, 1 when ``snr_gamma`` is None.  -> float32 tensors
+    (sa, sb, w) [B]; x_t = sa * nan_to_num(x0) + sb * noise."""
+    if prediction_type not in PREDICTION_TYPES:
+        raise ValueError(f"prediction_type {prediction_type!r}")
+    t = torch.as_tensor(timesteps).to("cpu", torch.long).flatten().numpy()
+    ac = dit_alphas_cumprod_f32()[t]
+    sa, sb = np.sqrt(ac), np.sqrt(np.float32(1.0) - ac)          # correctly rounded, as the host's sqrtf
+    if snr_gamma is None or not snr_gamma > 0:
+        w = np.ones_like(sa)
+    else:
+        snr = (sa / sb) * (sa / sb)
+        m = np.minimum(snr, np.float32(snr_gamma))
+        w = m / snr if prediction_type == "epsilon" else m / (snr + np.float32(1.0))
+    return tuple(torch.from_numpy(np.ascontiguousarray(v, dtype=np.float32)) for v in (sa, sb, w))
+
+
+def dit_loss_weights(timesteps, prediction_type: str = "v_prediction", snr_gamma: Optional[float] = 5.0) -> torch.Tensor:
+    """The loss weights w [B] of ``dit_loss_coefficients``."""
+    return dit_loss_coefficients(timesteps, prediction_type, snr_gamma)[2]
+
+
 class MDiT:
-    def __init__(self, opt, device="cuda:0", clip_layers: int = 32, precision: Optional[str] = "fp32"):
+    def __init__(self, opt, device="cuda:0", clip_layers: int = 32, precision: Optional[str] = "fp32", point_encoder: bool = False):
         """clip_layers: depth of the CLIP ViT image encoder to expect in the checkpoint (32 = ViT-H/14 as in the
         reference; 0 = no image encoder: get_cond then takes its last_hidden_state directly).
         precision: 'fp32' (exact), 'fp16' (every Linear on the fp16-input matrix cores, the reference's GPU dtype), or
-        None = module style: fp32 until ``.half()`` is called (reference infer_dit.py:70), context created on first use."""
+        None = module style: fp32 until ``.half()`` is called (reference infer_dit.py:70), context created on first use.
+        point_encoder: also hold the reference's frozen PointEncoderEmbed (``point_encoder.*`` keys, opt.point_hidden_dim /
+        point_num_heads, freq dim 24) for ``point_latent`` and ``forward`` on point clouds."""
         self.opt = opt
         self.clip_layers = clip_layers
         if precision not in (None, "fp32", "fp16"):
             raise ValueError(precision)
         self._fp16 = precision == "fp16"
-        if getattr(opt, "noise_scheduler_predtype", "v_prediction") != "v_prediction":
-            # the reference forwards this option to DDIMScheduler (core/models_dit.py:91); the device sampler
-            # (ddim_cfg_step_kernel) implements the v-prediction update only - refuse rather than sample wrong latents
-            raise NotImplementedError(f"noise_scheduler_predtype={opt.noise_scheduler_predtype!r}: the DDIM step kernel "
-                                      "implements 'v_prediction' (the released DiT checkpoints' target) only")
+        self.prediction_type = getattr(opt, "noise_scheduler_predtype", "v_prediction")
+        if self.prediction_type not in PREDICTION_TYPES:
+            raise ValueError(f"noise_scheduler_predtype={self.prediction_type!r}: 'v_prediction' or 'epsilon'")
+        self.point_encoder = bool(point_encoder)
+        self.training = False
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise native.NativeError("MDiT needs a HIP device; there is no CPU fallback")
@@ -70,6 +122,10 @@ class MDiT:
         self._ctx_h = C.c_void_p()
         idx = self.device.index if self.device.index is not None else torch.cuda.current_device()
         native.check(self.lib.er_dit_create(C.byref(cfg), idx, C.byref(self._ctx_h)), "er_dit_create")
+        native.check(self.lib.er_dit_set_prediction_type(self._ctx_h, PREDICTION_TYPES[self.prediction_type]), "er_dit_set_prediction_type")
+        if self.point_encoder:
+            native.check(self.lib.er_dit_attach_point_encoder(self._ctx_h, opt.point_hidden_dim, opt.point_num_heads, 24),
+                         "er_dit_attach_point_encoder")
         for sd, strict in self._sources:
             self._load_now(sd, strict)
         return self._ctx_h
@@ -102,6 +158,8 @@ class MDiT:
         want = {k for k, _, _ in dit_tensor_specs(self.opt)}
         if self.clip_layers > 0:
             want |= {k for k, _, _ in clip_tensor_specs(self.clip_layers)}
+        if self.point_encoder:
+            want |= point_encoder_keys(self.opt)
         def norm(k):                           # transformers >= 5 drops the "vision_model." level (er_dit.h accepts both)
             if k.startswith("image_encoder.") and not k.startswith("image_encoder.vision_model."):
                 return "image_encoder.vision_model." + k[len("image_encoder."):]
@@ -153,6 +211,12 @@ class MDiT:
         return self._cast(False)
 
     def eval(self):
+        self.training = False
+        return self
+
+    def train(self, mode: bool = True):
+        """Sets the flag ``forward`` checks: there is no training path (backward pass, CFG dropout), so a training-mode forward raises."""
+        self.training = bool(mode)
         return self
 
     def to(self, device):
@@ -245,3 +309,84 @@ class MDiT:
                                                 float(guidance_scale), init_step, self._sp()), "er_dit_sample")
         self._sync_out()
         return lat
+
+    @torch.no_grad()
+    def point_latent(self, points: torch.Tensor) -> torch.Tensor:
+        """posterior.mode() of the frozen point encoder (core/models_dit.py:140-141): points [B, N, 3] -> latents
+        [B, point_latent_size, point_latent_dim], fp32."""
+        if not self.point_encoder:
+            raise native.NativeError("MDiT.point_latent: this MDiT has no point encoder; create it with MDiT(..., point_encoder=True)")
+        x = torch.as_tensor(points).to(self.device, torch.float32).contiguous()
+        if x.dim() != 3 or x.shape[-1] != 3 or x.shape[1] == 0:
+            raise ValueError(f"points must be [B, N, 3], got {tuple(x.shape)}")
+        self._sync_in()
+        with torch.cuda.stream(self.stream):
+            out = torch.empty((x.shape[0], self.opt.point_latent_size, self.opt.point_latent_dim), dtype=torch.float32, device=self.device)
+            native.check(self.lib.er_dit_point_latent(self._ctx, native.ptr(x), x.shape[0], x.shape[1], native.ptr(out), self._sp()),
+                         "er_dit_point_latent")
+        self._sync_out()
+        return out
+
+    def __call__(self, data, step_ratio=1, **kwargs):
+        return self.forward(data, step_ratio, **kwargs)
+
+    @torch.no_grad()
+    def forward(self, data, step_ratio=1, noise: Optional[torch.Tensor] = None, timesteps=None,
+                generator: Optional[torch.Generator] = None, return_pred: bool = False) -> Dict[str, torch.Tensor]:
+        """core/models_dit.py:119-181 in eval mode (no CFG dropout; main_dit.py:216-230 sums ``out['loss']``).
+        data['cond']: images [B, 3, H, W] in [0, 1] or CLIP hidden states [B, 257, 1280]; data['points'] [B, N, 3] (encoded by the
+        frozen point encoder) or data['latents'] [B, point_latent_size, point_latent_dim] (used as the encoder's output).
+        ``noise`` / ``timesteps`` default to torch.randn / torch.randint(0, 1000) draws from ``generator``, in that order.
+        Returns loss (0-dim: mean over the batch of weights * mse), mse [B] (unweighted, per sample), weights [B] and timesteps [B];
+        with ``return_pred`` also pred (the DiT's output).  ``step_ratio`` is unused, as in the reference."""
+        if self.training:
+            raise NotImplementedError("MDiT.forward in training mode (backward pass, CFG dropout) is not part of this path; call .eval() first")
+        opt = self.opt
+        shape = (opt.point_latent_size, opt.point_latent_dim)
+        if "latents" in data and data["latents"] is not None:
+            lat = torch.as_tensor(data["latents"]).to(self.device, torch.float32).contiguous()
+        elif "points" in data and data["points"] is not None:
+            lat = self.point_latent(data["points"])
+        else:
+            raise ValueError("data needs 'points' [B, N, 3] or 'latents' [B, point_latent_size, point_latent_dim]")
+        if lat.dim() != 3 or tuple(lat.shape[1:]) != shape:
+            raise ValueError(f"latents must be [B, {shape[0]}, {shape[1]}], got {tuple(lat.shape)}")
+        B = lat.shape[0]
+        cond = self.get_cond(torch.as_tensor(data["cond"]))
+        if cond.shape[0] != B:
+            raise ValueError(f"cond has {cond.shape[0]} rows, the latents {B}")
+        gdev = generator.device if generator is not None else "cpu"
+        if noise is None:
+            noise = torch.randn((B,) + shape, generator=generator, device=gdev, dtype=torch.float32)
+        noise = torch.as_tensor(noise).to(self.device, torch.float32).contiguous()
+        if tuple(noise.shape) != tuple(lat.shape):
+            raise ValueError(f"noise must be {tuple(lat.shape)}, got {tuple(noise.shape)}")
+        if timesteps is None:
+            timesteps = torch.randint(0, 1000, (B,), generator=generator, device=gdev)
+        t = torch.as_tensor(timesteps).to("cpu", torch.long).flatten()
+        if t.numel() != B:
+            raise ValueError(f"timesteps must be [{B}], got {tuple(torch.as_tensor(timesteps).shape)}")
+        if ((t < 0) | (t >= 1000)).any():
+            raise ValueError(f"timesteps must lie in [0, 1000), got {t.tolist()}")
+        gamma = opt.snr_gamma
+        self._sync_in()
+        with torch.cuda.stream(self.stream):
+            pred = torch.empty_like(lat) if return_pred else None
+            mse = torch.empty((B,), dtype=torch.float32, device=self.device)
+            loss = torch.empty((1,), dtype=torch.float32, device=self.device)
+            native.check(self.lib.er_dit_loss(self._ctx, native.ptr(lat), native.ptr(noise), native.ptr(cond), native.i32_array(t.tolist()),
+                                              B, cond.shape[1], float("nan") if gamma is None else float(gamma), native.ptr(pred),
+                                              native.ptr(mse), native.ptr(loss), self._sp()), "er_dit_loss")
+        self._sync_out()
+        out = {"loss": loss[0], "mse": mse, "weights": dit_loss_weights(t, self.prediction_type, gamma).to(self.device),
+               "timesteps": t}
+        if return_pred:
+            out["pred"] = pred
+        return out
+
+
+def point_encoder_keys(opt) -> set:
+    """The ``point_encoder.*`` keys of a cond_mode='point' checkpoint (what MDiT(..., point_encoder=True) loads)."""
+    from .weights import dims_from_options, tensor_specs
+    d = dims_from_options(dataclasses.replace(opt, cond_mode="point"))
+    return {k for k, _, _ in tensor_specs(d) if k.startswith("point_encoder.")}

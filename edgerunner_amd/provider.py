@@ -69,3 +69,57 @@ def mesh_item(path: str, opt, tokenizer=None, rng: Optional[np.random.Generator]
     if (coords - 3 < 0).any():                      # core/provider.py:288-290
         raise ValueError(f"{path}: invalid token range {coords.min() - 3} - {coords.max() - 3}")
     return {"cond": cond, "coords": coords, "len": int(coords.shape[0]), "num_faces": int(f.shape[0]), "path": path, "azimuth": 0}
+
+
+# ------------------------------------------------------------------------------------ DiT pairs (core/provider_dit.py, eval branch)
+DIT_IMAGE_SIZE = 512          # the reference dataset's renders are 512 x 512 (provider_dit.py:105); infer_dit.py resizes to it (:97)
+
+
+def load_image(path: str) -> np.ndarray:
+    """An image as float32 [H, W, 3] in [0, 1]: RGB / RGBA / grey files readable by PIL, or .npy arrays [H, W, 3|4] in [0, 1]; alpha is
+    composited on white (reference infer_dit.py:93, provider_dit.py:116)."""
+    if path.endswith(".npy"):
+        a = np.load(path).astype(np.float32)
+    else:
+        from PIL import Image
+        a = np.asarray(Image.open(path)).astype(np.float32) / 255.0
+    if a.ndim == 2:
+        a = np.repeat(a[..., None], 3, axis=-1)
+    if a.shape[-1] == 4:
+        a = a[..., :3] * a[..., 3:4] + (1 - a[..., 3:4])
+    return a[..., :3]
+
+
+def dit_item(image_path: str, shape_path: str, opt, rng: Optional[np.random.Generator] = None) -> Dict:
+    """Dataset item of one (image, shape) pair as ``ObjaverseDataset.__getitem__`` of provider_dit.py:84-145 returns it in eval mode
+    (azimuth 0, no augmentation): ``cond`` = the image [3, 512, 512] in [0, 1] (bilinearly resized like infer_dit.py), ``points`` =
+    ``opt.point_num`` surface samples [N, 3] of the mesh normalised to bound 0.95, or a .npy cloud [N, 3] used as it is.  The surface
+    sampler is meshio's (seeded by ``rng``), not trimesh's."""
+    import torch.nn.functional as F
+    img = torch.from_numpy(np.ascontiguousarray(load_image(image_path))).permute(2, 0, 1).unsqueeze(0).float()
+    img = F.interpolate(img, (DIT_IMAGE_SIZE, DIT_IMAGE_SIZE), mode="bilinear", align_corners=False)[0]
+    if shape_path.lower().endswith(".npy"):
+        points = np.load(shape_path).astype(np.float32)
+        if points.ndim != 2 or points.shape[1] != 3:
+            raise ValueError(f"{shape_path}: a point cloud must be [N, 3], got {points.shape}")
+    else:
+        v, f = meshio.load_mesh(shape_path)
+        v = meshio.normalize_mesh(v, bound=0.95)
+        if rng is None:
+            rng = np.random.default_rng([int(opt.seed) & 0xFFFFFFFF, zlib.crc32(os.path.basename(shape_path).encode())])
+        points = meshio.sample_surface(v, f, opt.point_num, rng).astype(np.float32)
+    return {"cond": img.contiguous(), "points": torch.from_numpy(np.ascontiguousarray(points)), "image_path": image_path,
+            "shape_path": shape_path}
+
+
+def collate_dit(batch: List[Dict]) -> Dict:
+    """Stacks ``dit_item`` results into the batch ``MDiT.forward`` takes: cond [B, 3, 512, 512], points [B, N, 3] (every cloud of a
+    batch must have the same N, as the reference's default collate requires)."""
+    sizes = {tuple(item["points"].shape) for item in batch}
+    if len(sizes) != 1:
+        raise ValueError(f"point clouds of one batch must have the same shape, got {sorted(sizes)}")
+    return {
+        "cond": torch.stack([item["cond"] for item in batch], dim=0),
+        "points": torch.stack([item["points"] for item in batch], dim=0),
+        "paths": [(item["image_path"], item["shape_path"]) for item in batch],
+    }

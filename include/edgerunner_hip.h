@@ -202,7 +202,8 @@ typedef struct {
 typedef struct er_dit_ctx er_dit_ctx;
 int er_dit_create(const er_dit_config* cfg, int device, er_dit_ctx** out);
 int er_dit_destroy(er_dit_ctx* ctx);
-/* MDiT checkpoint keys: "dit.*", "proj_cond.*", "norm_cond.*" (others - image_encoder.*, point_encoder.* - are ignored: returns 1) */
+/* MDiT checkpoint keys: "dit.*", "proj_cond.*", "norm_cond.*", "image_encoder.vision_model.*" when clip_layers > 0, and
+ * "point_encoder.*" after er_dit_attach_point_encoder; any other key is ignored (returns 1) */
 int er_dit_load_tensor(er_dit_ctx* ctx, const char* key, const void* data, int dtype, int ndim,
                        const int64_t* shape, int on_device);
 int er_dit_finalize_weights(er_dit_ctx* ctx);
@@ -225,6 +226,29 @@ int er_dit_forward(er_dit_ctx* ctx, const float* x_dev, const float* c_dev, cons
  * latents_dev float[B, N, latent_dim] holds the starting latents on entry and the result on exit. */
 int er_dit_sample(er_dit_ctx* ctx, const float* cond_dev, int batch, int m_tokens, float* latents_dev,
                   int num_inference_steps, float guidance_scale, int init_step, void* stream);
+
+/* What the DiT predicts (Options.noise_scheduler_predtype, core/models_dit.py:80-101): the DDIM update of er_dit_sample (CFG is
+ * applied to the prediction either way) and the target of er_dit_loss.  ER_PRED_EPSILON: x0 = (x - sqrt(1-a_t) eps) / sqrt(a_t),
+ * x <- sqrt(a_p) x0 + sqrt(1-a_p) eps.  Default ER_PRED_V_PREDICTION. */
+typedef enum { ER_PRED_V_PREDICTION = 0, ER_PRED_EPSILON = 1 } er_pred_type;
+int er_dit_set_prediction_type(er_dit_ctx* ctx, int pred_type);
+/* Gives the context the frozen PointEncoderEmbed of MDiT (core/models_dit.py:68-75; point.py:172-206) with latent_size /
+ * latent_dim of the DiT config.  Afterwards er_dit_load_tensor takes the "point_encoder.*" keys and er_dit_finalize_weights
+ * requires them.  The encoder runs in fp32 in both DiT precisions (the reference runs it .half()). */
+int er_dit_attach_point_encoder(er_dit_ctx* ctx, int point_hidden_dim, int point_num_heads, int point_freq_dim);
+/* posterior.mode() of the attached encoder: points_dev float[B, n_points, 3] -> latent_out_dev float[B, latent_size, latent_dim]
+ * (as er_point_latent, without the KL term).  ER_ERR_UNSUPPORTED when no encoder is attached. */
+int er_dit_point_latent(er_dit_ctx* ctx, const float* points_dev, int batch, int n_points, float* latent_out_dev, void* stream);
+/* MDiT.forward in eval mode (core/models_dit.py:137-177, no CFG dropout) on given latents, noise and timesteps:
+ *   x_t = sqrt(a_t) nan_to_num(latents) + sqrt(1-a_t) noise; pred = DiT(x_t, cond_dev, t) (as er_dit_forward at integer t);
+ *   target = sqrt(a_t) noise - sqrt(1-a_t) nan_to_num(latents) (v-prediction) or noise (epsilon);
+ *   mse_out_dev[b] = mean((pred - target)^2) of sample b (unweighted), loss_out_dev[0] = mean_b(w_b mse_b) with
+ *   w = min(snr, snr_gamma) / (snr + 1) (v) or / snr (epsilon), snr = a_t / (1 - a_t); w = 1 when snr_gamma <= 0 or NaN (None).
+ * latents_dev / noise_dev float[B, latent_size, latent_dim], cond_dev float[B, m_tokens, hidden_dim], timesteps_host int32[B] in
+ * [0, 1000) (ER_ERR_INVALID otherwise), pred_out_dev (nullable) float[B, latent_size, latent_dim].  Reductions in double, fixed order. */
+int er_dit_loss(er_dit_ctx* ctx, const float* latents_dev, const float* noise_dev, const float* cond_dev,
+                const int32_t* timesteps_host, int batch, int m_tokens, float snr_gamma, float* pred_out_dev,
+                float* mse_out_dev, float* loss_out_dev, void* stream);
 
 /* ---- which kernels a decode context of this shape runs (pure host logic: callable without a device) ----
  * The rules live in ONE function that er_kv_reserve applies and this entry point reports; the environment knobs of
@@ -337,6 +361,10 @@ int er_k_softmax(float* s_dev, int rows, int cols, int ld, int causal, void* str
  * (nullable) = {mean NLL over supervised positions, count} from the fixed-order double reduction */
 int er_k_score_rows(const float* logits_dev, const int32_t* labels_dev, int batch, int seq_len, int vocab, float* nll_out_dev,
                     int32_t* pred_out_dev, float* loss_out_dev, void* stream);
+/* er_dit_loss's two loss kernels on given tensors float[B, n] (n % 4 == 0, 16-byte aligned; x0_dev may be NULL for epsilon):
+ * mse_out_dev float[B], loss_out_dev float[1] as er_dit_loss defines them */
+int er_k_dit_loss(const float* pred_dev, const float* x0_dev, const float* eps_dev, const int32_t* timesteps_host, int batch, int n,
+                  int pred_type, float snr_gamma, float* mse_out_dev, float* loss_out_dev, void* stream);
 /* one sampling-head step on given logits float[B,V]; state arrays are int[B] on device */
 int er_k_sample_head(const float* logits_dev, const er_decode_params* p, int vocab, int eos, int pad,
                      int batch, int step, const int32_t* last_tok_host, const int32_t* counter_host,
