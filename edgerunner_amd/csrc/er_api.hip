@@ -27,6 +27,7 @@
 #include "k_score.h"
 #include "k_flash_attn.h"
 #include "k_flash_attn_f32.h"
+#include "k_fps.h"
 #include "meto_decode.h"
 #include "meto_encode.h"
 
@@ -71,10 +72,12 @@ struct Buf {   // grow-only device scratch
     size_t n = 0;
 };
 
-// PointEncoderEmbed (core/transformer/point.py:172-206): weights, shape and scratch.  Embedded in er_ctx (cond_mode POINT) and, after
-// er_dit_attach_point_encoder, in er_dit_ctx; the same helpers (pe_register_keys / pe_load_tensor / point_latent_chunk) serve both.
+// PointEncoderEmbed (core/transformer/point.py:172-206) or, with mode ER_PE_DOWNSAMPLE, PointEncoder (:129-169): weights, shape and
+// scratch.  Embedded in er_ctx (cond_mode POINT) and, after er_dit_attach_point_encoder, in er_dit_ctx; the same helpers
+// (pe_register_keys / pe_load_tensor / point_latent_chunk) serve both.
 struct PointEnc {
     int PH = 0, heads = 0, Lq = 0, LD = 0, freq = 0;     // point_hidden_dim, point_num_heads, latent size / dim, point_freq_dim
+    int mode = ER_PE_EMBED;  // ER_PE_DOWNSAMPLE: the queries are the point embeddings of a farthest-point subsample (no query_embed)
     float eps = 1e-5f;
     float *query = nullptr, *basis = nullptr, *mlp_w = nullptr, *mlp_b = nullptr, *ln_w = nullptr, *ln_b = nullptr;
     float *ca_ln1_w = nullptr, *ca_ln1_b = nullptr, *ca_ln2_w = nullptr, *ca_ln2_b = nullptr;
@@ -83,6 +86,7 @@ struct PointEnc {
     float *ff0_w = nullptr, *ff0_b = nullptr, *ff2_w = nullptr, *ff2_b = nullptr, *lin_w = nullptr, *lin_b = nullptr;
     int kpad = 0;            // padded input width of point_embed.mlp (51 -> 64)
     Buf a0, x, k, v, qln, q, sc, att, l, ln, u, g, lat;   // scratch of point_latent_chunk; lat = the latent mean [nb][Lq][LD]
+    Buf q0, fidx, fdist;     // downsample mode: gathered query rows [nb][Lq][PH], FPS indices [nb][Lq] (int32), FPS distances (large N)
 };
 
 struct er_ctx {
@@ -163,7 +167,7 @@ static int ensure(Buf& b, size_t n) {
 }
 
 static void pe_free(PointEnc& p) {
-    for (Buf* b : {&p.a0, &p.x, &p.k, &p.v, &p.qln, &p.q, &p.sc, &p.att, &p.l, &p.ln, &p.u, &p.g, &p.lat})
+    for (Buf* b : {&p.a0, &p.x, &p.k, &p.v, &p.qln, &p.q, &p.sc, &p.att, &p.l, &p.ln, &p.u, &p.g, &p.lat, &p.q0, &p.fidx, &p.fdist})
         if (b->p) { hipFree(b->p); b->p = nullptr; b->n = 0; }
 }
 
@@ -176,14 +180,16 @@ static const char* kKindNames[ER_NUM_KERNEL_KINDS] = {"qkv_gemv", "attn_decode",
                                                       "fc1_gemv", "fc2_gemv", "lm_head_gemv", "sample_head"};
 extern "C" const char* er_kernel_kind_name(int k) { return (k >= 0 && k < ER_NUM_KERNEL_KINDS) ? kKindNames[k] : "?"; }
 
-// every point_encoder.* key PointEncoderEmbed's state_dict holds, as "required, not loaded yet"
-static void pe_register_keys(std::map<std::string, bool>& n) {
+// every point_encoder.* key the encoder's state_dict holds, as "required, not loaded yet" (PointEncoder, the downsample mode, has
+// no query_embed)
+static void pe_register_keys(std::map<std::string, bool>& n, int mode = ER_PE_EMBED) {
     auto lin = [&](const std::string& p) {
         n[p + ".weight"] = false;
         n[p + ".bias"] = false;
     };
     const std::string pe = "point_encoder";
-    n[pe + ".query_embed"] = false;
+    if (mode == ER_PE_EMBED) n[pe + ".query_embed"] = false;
+    else n.erase(pe + ".query_embed");
     n[pe + ".point_embed.basis"] = false;
     lin(pe + ".point_embed.mlp");
     lin(pe + ".ln");
@@ -202,7 +208,7 @@ static void register_keys(er_ctx* c) {
         n[p + ".weight"] = false;
         if (bias) n[p + ".bias"] = false;
     };
-    if (g.cond_mode == ER_COND_POINT) pe_register_keys(n);
+    if (g.cond_mode == ER_COND_POINT) pe_register_keys(n, c->pe.mode);
     if (g.cond_mode != ER_COND_NONE) {
         lin("proj_cond");
         lin("norm_cond");
@@ -394,7 +400,7 @@ static int pe_load_tensor(PointEnc& p, std::vector<void*>& owned, const std::str
         HIPCHK(hipStreamSynchronize(st));
         return 0;
     };
-    if (key == "point_encoder.query_embed") return put(&p.query, (size_t)p.Lq * PH);
+    if (key == "point_encoder.query_embed") return p.mode == ER_PE_EMBED ? put(&p.query, (size_t)p.Lq * PH) : 1;
     if (key == "point_encoder.point_embed.basis") return put(&p.basis, (size_t)3 * p.freq);
     if (key == "point_encoder.point_embed.mlp.weight") {
         // [PH][2F+3] -> zero-padded [PH][kpad] so the GEMM K is a multiple of 16
@@ -1126,39 +1132,58 @@ static int attention_full(const float* Q, int ldq, const float* Kp, int ldk, lon
 // ------------------------------------------------------------------------------------ encode_cond
 // PointEncoderEmbed (core/transformer/point.py:186-206) of nb samples of N points each: the latent mean (posterior.mode(), :201)
 // into p.lat [nb][Lq][LD].  Shared by er_encode_cond (which projects it, core/models.py:124), er_point_latent and
-// er_dit_point_latent.
+// er_dit_point_latent.  Mode ER_PE_DOWNSAMPLE is PointEncoder (:143-169): the queries are point_embed (before ln) of the Lq points a
+// farthest point sampling picks from each cloud (k_fps.h), one query table per sample.
 static int point_latent_chunk(PointEnc& p, const float* pts, int nb, int N, hipStream_t st) {
     const int PH = p.PH, Lq = p.Lq, LD = p.LD;
     const int PHh = p.heads > 0 ? p.heads : 1, PD = PH / PHh;
+    const bool ds = p.mode == ER_PE_DOWNSAMPLE;
     if (N <= 0) return fail(ER_ERR_INVALID, "n_points must be > 0");
+    if (ds && N < Lq)
+        return fail(ER_ERR_INVALID, "point_encoder_mode downsample samples point_latent_size = %d points per cloud; the clouds have %d", Lq, N);
     const size_t R = (size_t)nb * N, RQ = (size_t)nb * Lq;
+    const size_t QR = ds ? RQ : (size_t)Lq;   // rows of the query table: per sample (downsample) or one shared table (embed)
     ERCHK(ensure(p.a0, R * p.kpad));
     ERCHK(ensure(p.x, R * PH));
     ERCHK(ensure(p.k, R * PH));
     ERCHK(ensure(p.v, R * PH));
-    ERCHK(ensure(p.qln, (size_t)Lq * PH));
-    ERCHK(ensure(p.q, (size_t)Lq * PH));
+    ERCHK(ensure(p.qln, QR * PH));
+    ERCHK(ensure(p.q, QR * PH));
     ERCHK(ensure(p.att, RQ * PH));
     ERCHK(ensure(p.l, RQ * PH));
     ERCHK(ensure(p.ln, RQ * PH));
     ERCHK(ensure(p.u, RQ * 8 * PH));
     ERCHK(ensure(p.g, RQ * 4 * PH));
     ERCHK(ensure(p.lat, RQ * LD));
+    int32_t* fidx = nullptr;
+    if (ds) {
+        ERCHK(ensure(p.q0, RQ * PH));
+        ERCHK(ensure(p.fidx, RQ));
+        if (N > FPS_REG_MAX) ERCHK(ensure(p.fdist, R));
+        fidx = reinterpret_cast<int32_t*>(p.fidx.p);
+        // fps_indices = torch_cluster.fps(pc, batch, ratio = Lq / N)                  point.py:152-156
+        HIPRET(launch_fps(pts, nb, N, Lq, fidx, p.fdist.p, st));
+    }
     // x = ln(point_embed(pts))                                          point.py:194
     hipLaunchKernelGGL(point_embed_kernel, dim3(ew_grid((long long)R * p.kpad)), dim3(ER_WG), 0, st, pts,
                        p.basis, p.a0.p, (long long)R, p.freq, p.kpad);
     HIPRET(hipGetLastError());
     HIPRET(linear(p.a0.p, p.kpad, p.mlp_w, p.mlp_b, p.x.p, PH, (int)R, PH, p.kpad, false, nullptr, 0, st));
+    if (ds) {   // q = point_embed(pc[fps_indices]): the sampled rows of the point_embed output, before ln      point.py:157-158
+        hipLaunchKernelGGL(fps_gather_rows_kernel, dim3((unsigned)RQ), dim3(ER_WG), 0, st, p.x.p, fidx, N, Lq, PH, p.q0.p);
+        HIPRET(hipGetLastError());
+    }
     HIPRET(launch_layernorm(p.x.p, p.ln_w, p.ln_b, p.x.p, (int)R, PH, PH, PH, p.eps, st));
     // cross attention: l = q + out_proj(attn(q_proj(ln1(q)), k_proj(x), v_proj(x)))   point.py:123-124
-    // (the learned queries and their projection are the same for every sample: computed once)
-    HIPRET(launch_layernorm(p.query, p.ca_ln1_w, p.ca_ln1_b, p.qln.p, Lq, PH, PH, PH, p.eps, st));
-    HIPRET(linear(p.qln.p, PH, p.ca_q_w, p.ca_q_b, p.q.p, PH, Lq, PH, PH, false, nullptr, 0, st));
+    // (embed mode: the learned queries and their projection are the same for every sample: computed once)
+    const float* qsrc = ds ? p.q0.p : p.query;
+    HIPRET(launch_layernorm(qsrc, p.ca_ln1_w, p.ca_ln1_b, p.qln.p, (int)QR, PH, PH, PH, p.eps, st));
+    HIPRET(linear(p.qln.p, PH, p.ca_q_w, p.ca_q_b, p.q.p, PH, (int)QR, PH, PH, false, nullptr, 0, st));
     HIPRET(linear(p.x.p, PH, p.ca_k_w, p.ca_k_b, p.k.p, PH, (int)R, PH, PH, false, nullptr, 0, st));
     HIPRET(linear(p.x.p, PH, p.ca_v_w, p.ca_v_b, p.v.p, PH, (int)R, PH, PH, false, nullptr, 0, st));
     if (PD == 64 || PD == 96) {
         Flash32Args f{};
-        f.Q = p.q.p; f.ldq = PH; f.qs_b = 0; f.qs_h = PD;                      // queries shared by the batch
+        f.Q = p.q.p; f.ldq = PH; f.qs_b = ds ? (long long)Lq * PH : 0; f.qs_h = PD;   // embed: queries shared by the batch
         f.K = p.k.p; f.ldk = PH; f.ks_b = (long long)N * PH; f.ks_h = PD;
         f.V = p.v.p; f.ldv = PH; f.vs_b = (long long)N * PH; f.vs_h = PD;
         f.O = p.att.p; f.ldo = PH; f.os_b = (long long)Lq * PH; f.os_h = PD;
@@ -1168,12 +1193,12 @@ static int point_latent_chunk(PointEnc& p, const float* pts, int nb, int N, hipS
         const int ldS = (N + 15) / 16 * 16;
         ERCHK(ensure(p.sc, (size_t)PHh * Lq * ldS));
         for (int b = 0; b < nb; ++b)
-            ERCHK(attention_full(p.q.p, PH, p.k.p + (size_t)b * N * PH, PH, PD, p.v.p + (size_t)b * N * PH, PH, PD,
-                                 p.att.p + (size_t)b * Lq * PH, PH, p.sc.p, PHh, PD, Lq, N, false, st));
+            ERCHK(attention_full(p.q.p + (ds ? (size_t)b * Lq * PH : 0), PH, p.k.p + (size_t)b * N * PH, PH, PD,
+                                 p.v.p + (size_t)b * N * PH, PH, PD, p.att.p + (size_t)b * Lq * PH, PH, p.sc.p, PHh, PD, Lq, N, false, st));
     }
-    {   // l = query_embed + out_proj(att): the residual table has Lq rows shared by every sample
+    {   // l = q + out_proj(att): embed mode's residual table has Lq rows shared by every sample; downsample's has one per sample
         GemmArgs ga = gemm_args_default();
-        ga.A = p.att.p; ga.B = p.ca_o_w; ga.C = p.l.p; ga.bias = p.ca_o_b; ga.resid = p.query; ga.resid_mod = Lq;
+        ga.A = p.att.p; ga.B = p.ca_o_w; ga.C = p.l.p; ga.bias = p.ca_o_b; ga.resid = qsrc; ga.resid_mod = ds ? 0 : Lq;
         ga.M = (int)RQ; ga.N = PH; ga.K = PH; ga.lda = PH; ga.ldb = PH; ga.ldc = PH; ga.ldr = PH;
         HIPRET(launch_gemm(ga, 1, st));
     }
@@ -1436,6 +1461,19 @@ extern "C" int er_point_latent(er_ctx* c, const float* conds, int B, int n_point
         HIPCHK(hipMemcpyAsync(latent_out + (size_t)b0 * per, c->pe.lat.p, (size_t)nb * per * 4, hipMemcpyDeviceToDevice, st));
     }
     if (kl_out) HIPRET(launch_score_reduce(latent_out, nullptr, (int)((size_t)B * per), 0, kl_out, st));
+    return ER_OK;
+}
+
+extern "C" int er_set_point_encoder_mode(er_ctx* c, int mode) {
+    if (!c) return fail(ER_ERR_INVALID, "null ctx");
+    if (mode != ER_PE_EMBED && mode != ER_PE_DOWNSAMPLE)
+        return fail(ER_ERR_INVALID, "er_set_point_encoder_mode: %d is neither ER_PE_EMBED nor ER_PE_DOWNSAMPLE", mode);
+    if (c->cfg.cond_mode != ER_COND_POINT)
+        return fail(ER_ERR_UNSUPPORTED, "er_set_point_encoder_mode: the context has no point encoder (cond_mode %d)", c->cfg.cond_mode);
+    for (auto& kv : c->need)
+        if (kv.second) return fail(ER_ERR_INVALID, "er_set_point_encoder_mode: call it before the first er_load_tensor");
+    c->pe.mode = mode;
+    pe_register_keys(c->need, mode);
     return ER_OK;
 }
 
@@ -2064,6 +2102,18 @@ extern "C" int er_k_sample_head(const float* logits, const er_decode_params* p, 
 }
 
 // ------------------------------------------------------------------------------------ detokenise (host)
+extern "C" int er_k_fps(const float* pts, int B, int N, int S, int32_t* idx, void* stream) {
+    if (!pts || !idx || B <= 0 || B > 65535 || N <= 0 || S <= 0 || S > N) return fail(ER_ERR_INVALID, "er_k_fps: bad argument");
+    hipStream_t st = (hipStream_t)stream;
+    float* dist = nullptr;
+    if (N > FPS_REG_MAX) HIPCHK(hipMalloc((void**)&dist, (size_t)B * N * sizeof(float)));
+    hipError_t e = launch_fps(pts, B, N, S, idx, dist, st);
+    const hipError_t e2 = hipStreamSynchronize(st);
+    if (dist) hipFree(dist);
+    if (e != hipSuccess || e2 != hipSuccess) return fail(ER_ERR_HIP, "er_k_fps: %s", hipGetErrorString(e != hipSuccess ? e : e2));
+    return ER_OK;
+}
+
 extern "C" int er_meto_decode(const int32_t* tokens, int n, int bins, int backend, float* v, int32_t* f, int32_t* t, int32_t* nv,
                               int32_t* nf, int32_t* nt) {
     if (n < 0 || bins <= 0 || (n > 0 && !tokens) || !v || !f || !t || !nv || !nf || !nt)

@@ -258,6 +258,18 @@ extern "C" int er_dit_point_latent(er_dit_ctx* c, const float* points, int B, in
     return ER_OK;
 }
 
+extern "C" int er_dit_set_point_encoder_mode(er_dit_ctx* c, int mode) {
+    if (!c) return fail(ER_ERR_INVALID, "null ctx");
+    if (mode != ER_PE_EMBED && mode != ER_PE_DOWNSAMPLE)
+        return fail(ER_ERR_INVALID, "er_dit_set_point_encoder_mode: %d is neither ER_PE_EMBED nor ER_PE_DOWNSAMPLE", mode);
+    if (!c->has_pe) return fail(ER_ERR_UNSUPPORTED, "er_dit_set_point_encoder_mode: no point encoder attached (er_dit_attach_point_encoder)");
+    for (auto& kv : c->pe_need)
+        if (kv.second) return fail(ER_ERR_INVALID, "er_dit_set_point_encoder_mode: call it before the first point_encoder.* tensor");
+    c->pe.mode = mode;
+    pe_register_keys(c->pe_need, mode);
+    return ER_OK;
+}
+
 extern "C" int er_dit_set_prediction_type(er_dit_ctx* c, int pred_type) {
     if (!c) return fail(ER_ERR_INVALID, "null ctx");
     if (pred_type != ER_PRED_V_PREDICTION && pred_type != ER_PRED_EPSILON)

@@ -217,6 +217,17 @@ def dit_loss(pred, x0, eps, timesteps, pred_type=native.ER_PRED_V_PREDICTION, sn
     return mse, loss
 
 
+def fps(points, n_samples):
+    """Farthest point sampling of the downsample point encoder (csrc/k_fps.h) on clouds [B, N, 3] fp32 -> indices [B, n_samples]
+    int32, 0-based within each cloud: sample 0 is point 0, then the argmax of the running min squared distance, lowest index on ties."""
+    lib = native.load_library()
+    x = points.to(torch.float32).contiguous()
+    B, N = x.shape[0], x.shape[1]
+    idx = torch.empty((B, n_samples), dtype=torch.int32, device=x.device)
+    native.check(lib.er_k_fps(native.ptr(x), B, N, n_samples, native.ptr(idx), _st()), "er_k_fps")
+    return idx
+
+
 def sample_head(logits, mode, grammar, step, last_tok, counter, unfinished, top_k=10, min_new=0, seed=0,
                 eos=2, pad=0):
     """One sampling-head step. Returns (next_tok, counter, unfinished) lists."""

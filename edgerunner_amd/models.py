@@ -67,8 +67,8 @@ class LMM:
             raise ValueError(precision)
         if opt.cond_mode == "image":
             raise NotImplementedError("cond_mode='image' (CLIP conditioner) is outside the ArAE decode path")
-        if opt.cond_mode == "point" and opt.point_encoder_mode != "embed":
-            raise NotImplementedError("point_encoder_mode='downsample' needs torch_cluster FPS; ArAE uses 'embed'")
+        if opt.cond_mode == "point" and opt.point_encoder_mode not in ("embed", "downsample"):
+            raise ValueError(f"point_encoder_mode={opt.point_encoder_mode!r}: 'embed' or 'downsample'")
         self.dims = dims_from_options(opt)
         if (self.dims.hidden_dim, self.dims.intermediate_dim) != (1536, 6144) or self.dims.hidden_dim // max(self.dims.num_heads, 1) not in (96, 64):
             # the decode kernels stream 1536-wide rows in whole 1536-element slices (csrc/k_gemv.h); the reference's generic

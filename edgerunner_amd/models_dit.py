@@ -22,7 +22,10 @@ from typing import Dict, Optional
 import numpy as np
 import torch
 
+from types import SimpleNamespace
+
 from . import native
+from .shape_opt import check_clouds, point_encoder_mode_id
 
 CLIP_DIM = 1280   # laion/CLIP-ViT-H-14 hidden width (core/models_dit.py:56)
 
@@ -83,7 +86,8 @@ class MDiT:
         precision: 'fp32' (exact), 'fp16' (every Linear on the fp16-input matrix cores, the reference's GPU dtype), or
         None = module style: fp32 until ``.half()`` is called (reference infer_dit.py:70), context created on first use.
         point_encoder: also hold the reference's frozen PointEncoderEmbed (``point_encoder.*`` keys, opt.point_hidden_dim /
-        point_num_heads, freq dim 24) for ``point_latent`` and ``forward`` on point clouds."""
+        point_num_heads, freq dim 24) for ``point_latent`` and ``forward`` on point clouds; PointEncoder (farthest-point-sampled
+        queries, no query_embed) when opt.point_encoder_mode == 'downsample', as core/models_dit.py:68-75 chooses."""
         self.opt = opt
         self.clip_layers = clip_layers
         if precision not in (None, "fp32", "fp16"):
@@ -93,6 +97,9 @@ class MDiT:
         if self.prediction_type not in PREDICTION_TYPES:
             raise ValueError(f"noise_scheduler_predtype={self.prediction_type!r}: 'v_prediction' or 'epsilon'")
         self.point_encoder = bool(point_encoder)
+        self._pe_mode = getattr(opt, "point_encoder_mode", "embed")
+        if self.point_encoder:
+            point_encoder_mode_id(self._pe_mode)          # 'embed' or 'downsample' (ValueError otherwise)
         self.training = False
         self.device = torch.device(device)
         if self.device.type != "cuda":
@@ -126,6 +133,8 @@ class MDiT:
         if self.point_encoder:
             native.check(self.lib.er_dit_attach_point_encoder(self._ctx_h, opt.point_hidden_dim, opt.point_num_heads, 24),
                          "er_dit_attach_point_encoder")
+            native.check(self.lib.er_dit_set_point_encoder_mode(self._ctx_h, point_encoder_mode_id(self._pe_mode)),
+                         "er_dit_set_point_encoder_mode")
         for sd, strict in self._sources:
             self._load_now(sd, strict)
         return self._ctx_h
@@ -319,6 +328,7 @@ class MDiT:
         x = torch.as_tensor(points).to(self.device, torch.float32).contiguous()
         if x.dim() != 3 or x.shape[-1] != 3 or x.shape[1] == 0:
             raise ValueError(f"points must be [B, N, 3], got {tuple(x.shape)}")
+        check_clouds(x, SimpleNamespace(point_encoder_mode=self._pe_mode, point_latent_size=self.opt.point_latent_size))
         self._sync_in()
         with torch.cuda.stream(self.stream):
             out = torch.empty((x.shape[0], self.opt.point_latent_size, self.opt.point_latent_dim), dtype=torch.float32, device=self.device)

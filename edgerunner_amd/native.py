@@ -23,16 +23,17 @@ ER_GRAMMAR_NONE, ER_GRAMMAR_NAIVE9, ER_GRAMMAR_LR_ABSCO = 0, 1, 2
 ER_METO_LR_ABSCO, ER_METO_LR = 0, 1
 ER_NUM_KERNEL_KINDS = 8
 ER_PRED_V_PREDICTION, ER_PRED_EPSILON = 0, 1
+ER_PE_EMBED, ER_PE_DOWNSAMPLE = 0, 1
 
 # every symbol include/edgerunner_hip.h declares (tests/test_abi.py checks the .so exports them all)
 EXPORTS = [
     "er_abi_version", "er_last_error", "er_create", "er_destroy", "er_load_tensor", "er_finalize_weights",
-    "er_kv_reserve", "er_encode_cond", "er_embed_tokens", "er_prefill", "er_score", "er_point_latent", "er_logits", "er_feed", "er_decode",
+    "er_kv_reserve", "er_encode_cond", "er_embed_tokens", "er_prefill", "er_score", "er_point_latent", "er_set_point_encoder_mode", "er_logits", "er_feed", "er_decode",
     "er_meto_decode", "er_meto_encode", "er_dit_create", "er_dit_destroy", "er_dit_load_tensor",
     "er_dit_finalize_weights", "er_dit_project_cond", "er_dit_encode_image", "er_dit_forward", "er_dit_sample",
-    "er_dit_set_prediction_type", "er_dit_attach_point_encoder", "er_dit_point_latent", "er_dit_loss", "er_k_dit_loss",
+    "er_dit_set_prediction_type", "er_dit_attach_point_encoder", "er_dit_point_latent", "er_dit_set_point_encoder_mode", "er_dit_loss", "er_k_dit_loss",
     "er_set_row_streams", "er_plan_decode", "er_ctx_plan", "er_plan_gemm_tile", "er_kernel_kind_name", "er_profile_decode_kernels", "er_profile_decode_kernels_at", "er_last_decode_ms",
-    "er_k_gemv", "er_k_attn_decode", "er_k_attn_outproj3", "er_k_gemm", "er_k_gemm_f16", "er_k_gemm_hh", "er_k_gemm_hh_qkv", "er_k_gemm_hh_geglu", "er_k_gemm_f16s", "er_k_flash_attn_f16", "er_k_flash_attn_hh", "er_k_flash_attn_f32", "er_k_flash_attn_f16s", "er_k_layernorm", "er_k_softmax", "er_k_score_rows", "er_k_sample_head",
+    "er_k_gemv", "er_k_attn_decode", "er_k_attn_outproj3", "er_k_gemm", "er_k_gemm_f16", "er_k_gemm_hh", "er_k_gemm_hh_qkv", "er_k_gemm_hh_geglu", "er_k_gemm_f16s", "er_k_flash_attn_f16", "er_k_flash_attn_hh", "er_k_flash_attn_f32", "er_k_flash_attn_f16s", "er_k_layernorm", "er_k_softmax", "er_k_score_rows", "er_k_fps", "er_k_sample_head",
 ]
 
 
@@ -96,6 +97,7 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.er_logits.argtypes = [vp, vp, vp]
     lib.er_score.argtypes = [vp, vp, vp, ci, ci, vp, vp, vp, vp, vp]
     lib.er_point_latent.argtypes = [vp, vp, ci, ci, vp, vp, vp]
+    lib.er_set_point_encoder_mode.argtypes = [vp, ci]
     lib.er_feed.argtypes = [vp, C.POINTER(C.c_int32), vp]
     lib.er_decode.argtypes = [vp, C.POINTER(ErDecodeParams), vp, C.POINTER(C.c_int32), vp]
     lib.er_profile_decode_kernels.argtypes = [vp, ci, C.POINTER(C.c_float), C.POINTER(C.c_double), vp]
@@ -115,6 +117,8 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.er_dit_set_prediction_type.argtypes = [vp, ci]
     lib.er_dit_attach_point_encoder.argtypes = [vp, ci, ci, ci]
     lib.er_dit_point_latent.argtypes = [vp, vp, ci, ci, vp, vp]
+    lib.er_dit_set_point_encoder_mode.argtypes = [vp, ci]
+    lib.er_k_fps.argtypes = [vp, ci, ci, ci, vp, vp]
     lib.er_dit_loss.argtypes = [vp, vp, vp, vp, C.POINTER(C.c_int32), ci, ci, cf, vp, vp, vp, vp]
     lib.er_k_dit_loss.argtypes = [vp, vp, vp, C.POINTER(C.c_int32), ci, ci, ci, cf, vp, vp, vp]
     lib.er_plan_decode.argtypes = [ci, ci, ci, ci, ci, C.POINTER(ErDecodePlan)]

@@ -37,6 +37,30 @@ class BuiltinGrammar:
         return self._fn(batch_id, input_ids) if self._fn is not None else None
 
 
+_PE_MODES = {"embed": native.ER_PE_EMBED, "downsample": native.ER_PE_DOWNSAMPLE}
+
+
+def point_encoder_mode_id(mode: str) -> int:
+    if mode not in _PE_MODES:
+        raise ValueError(f"point_encoder_mode={mode!r}: 'embed' or 'downsample'")
+    return _PE_MODES[mode]
+
+
+def check_clouds(points: torch.Tensor, dims) -> None:
+    """The downsample encoder's preconditions on clouds [B, N, 3]: farthest point sampling picks point_latent_size points per cloud
+    (the reference's ``.view(B, latent_size, 3)`` needs N >= point_latent_size) and its argmax needs finite coordinates.  The embed
+    encoder reads any cloud, as before."""
+    if getattr(dims, "point_encoder_mode", "embed") != "downsample":
+        return
+    if points.dim() != 3 or points.shape[-1] != 3:
+        raise ValueError(f"point clouds must be [B, N, 3], got {tuple(points.shape)}")
+    if points.shape[1] < dims.point_latent_size:
+        raise ValueError(f"point_encoder_mode='downsample' samples point_latent_size={dims.point_latent_size} points per cloud; "
+                         f"the clouds have {points.shape[1]} (use at least point_latent_size points, e.g. --point_num)")
+    if not bool(torch.isfinite(points).all()):
+        raise ValueError("point_encoder_mode='downsample': the point clouds hold non-finite coordinates")
+
+
 class NativeShapeOPT:
     def __init__(self, dims: ModelDims, opt, device: torch.device, weight_dtype=torch.float32,
                  kv_dtype=torch.float32):
@@ -60,6 +84,9 @@ class NativeShapeOPT:
         self._ctx = C.c_void_p()
         idx = self.device.index if self.device.index is not None else torch.cuda.current_device()
         native.check(self.lib.er_create(C.byref(cfg), idx, C.byref(self._ctx)), "er_create")
+        if dims.cond_mode == "point":
+            native.check(self.lib.er_set_point_encoder_mode(self._ctx, point_encoder_mode_id(dims.point_encoder_mode)),
+                         "er_set_point_encoder_mode")
         self.stream = torch.cuda.Stream(device=self.device)
         self._reserved = (0, 0)
         self.last_decode_ms = 0.0
@@ -145,6 +172,8 @@ class NativeShapeOPT:
         if d.cond_mode != "none":
             conds = conds.to(self.device, torch.float32).contiguous()
             n_points = conds.shape[1]
+            if d.cond_mode == "point":
+                check_clouds(conds, d)
         with self._enter():
             out = torch.empty((B, d.num_cond_tokens, d.hidden_dim), dtype=torch.float32, device=self.device)
             native.check(self.lib.er_encode_cond(self._ctx, native.ptr(conds if d.cond_mode != "none" else None), B,
@@ -212,6 +241,7 @@ class NativeShapeOPT:
         d = self.dims
         x = conds.to(self.device, torch.float32).contiguous()
         B, N = x.shape[0], x.shape[1]
+        check_clouds(x, d)
         with self._enter():
             lat = torch.empty((B, d.point_latent_size, d.point_latent_dim), dtype=torch.float32, device=self.device)
             kl = torch.empty((1,), dtype=torch.float32, device=self.device)

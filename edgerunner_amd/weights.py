@@ -49,6 +49,7 @@ class ModelDims:
     num_face_buckets: int    # rows of embed_num_face (10)
     cond_mode: str
     use_num_face_cond: bool
+    point_encoder_mode: str = "embed"   # 'downsample': PointEncoder (core/transformer/point.py:129-169), no query_embed
 
     @property
     def head_dim(self) -> int:
@@ -75,6 +76,7 @@ def dims_from_options(opt) -> ModelDims:
         point_latent_size=opt.point_latent_size, point_latent_dim=opt.point_latent_dim,
         point_freq_dim=24, num_face_buckets=10,
         cond_mode=opt.cond_mode, use_num_face_cond=bool(opt.use_num_face_cond),
+        point_encoder_mode=getattr(opt, "point_encoder_mode", "embed"),
     )
 
 
@@ -98,7 +100,8 @@ def tensor_specs(d: ModelDims) -> List[Tuple[str, Tuple[int, ...], str]]:
 
     if d.cond_mode == "point":
         pe = "point_encoder"
-        specs.append((f"{pe}.query_embed", (1, d.point_latent_size, PH), f"normal:{1.0 / math.sqrt(PH)}"))
+        if d.point_encoder_mode == "embed":        # PointEncoder (downsample) has no learned query table
+            specs.append((f"{pe}.query_embed", (1, d.point_latent_size, PH), f"normal:{1.0 / math.sqrt(PH)}"))
         specs.append((f"{pe}.point_embed.basis", (3, d.point_freq_dim), "basis"))
         fin = 2 * d.point_freq_dim + 3
         linear(f"{pe}.point_embed.mlp", PH, fin, f"linear_w:{fin}")

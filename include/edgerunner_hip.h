@@ -145,6 +145,15 @@ int er_score(er_ctx* ctx, const float* embeds_dev, const int32_t* labels_dev, in
 int er_point_latent(er_ctx* ctx, const float* conds_dev, int batch, int n_points, float* latent_out_dev,
                     float* kl_out_dev, void* stream);
 
+/* Options.point_encoder_mode (core/options.py:49): ER_PE_EMBED = PointEncoderEmbed (learned query table, the default),
+ * ER_PE_DOWNSAMPLE = PointEncoder (point.py:129-169: the queries are point_embed of point_latent_size points picked per cloud by
+ * farthest point sampling, torch_cluster.fps with random_start=False: the first sample is point 0, then argmax of the running
+ * min squared distance, lowest index on ties).  Downsample checkpoints have no point_encoder.query_embed: it is not required and
+ * loading it returns 1 like any unknown key.  Downsample needs n_points >= point_latent_size (ER_ERR_INVALID otherwise).
+ * er_set_point_encoder_mode: cond_mode POINT, before the first er_load_tensor. */
+typedef enum { ER_PE_EMBED = 0, ER_PE_DOWNSAMPLE = 1 } er_point_encoder_mode;
+int er_set_point_encoder_mode(er_ctx* ctx, int mode);
+
 /* logits[:, -1, :].float() of the most recent forward (prefill or er_feed): float[B, vocab]. */
 int er_logits(er_ctx* ctx, float* logits_out_dev, void* stream);
 
@@ -239,6 +248,8 @@ int er_dit_attach_point_encoder(er_dit_ctx* ctx, int point_hidden_dim, int point
 /* posterior.mode() of the attached encoder: points_dev float[B, n_points, 3] -> latent_out_dev float[B, latent_size, latent_dim]
  * (as er_point_latent, without the KL term).  ER_ERR_UNSUPPORTED when no encoder is attached. */
 int er_dit_point_latent(er_dit_ctx* ctx, const float* points_dev, int batch, int n_points, float* latent_out_dev, void* stream);
+/* er_set_point_encoder_mode for the attached encoder: after er_dit_attach_point_encoder, before its first point_encoder.* key. */
+int er_dit_set_point_encoder_mode(er_dit_ctx* ctx, int mode);
 /* MDiT.forward in eval mode (core/models_dit.py:137-177, no CFG dropout) on given latents, noise and timesteps:
  *   x_t = sqrt(a_t) nan_to_num(latents) + sqrt(1-a_t) noise; pred = DiT(x_t, cond_dev, t) (as er_dit_forward at integer t);
  *   target = sqrt(a_t) noise - sqrt(1-a_t) nan_to_num(latents) (v-prediction) or noise (epsilon);
@@ -365,6 +376,9 @@ int er_k_score_rows(const float* logits_dev, const int32_t* labels_dev, int batc
  * mse_out_dev float[B], loss_out_dev float[1] as er_dit_loss defines them */
 int er_k_dit_loss(const float* pred_dev, const float* x0_dev, const float* eps_dev, const int32_t* timesteps_host, int batch, int n,
                   int pred_type, float snr_gamma, float* mse_out_dev, float* loss_out_dev, void* stream);
+/* farthest point sampling of the downsample encoder on given clouds points_dev float[B, n_points, 3] -> idx_out_dev
+ * int32[B, n_samples] (0-based within each cloud; 1 <= n_samples <= n_points, B <= 65535) */
+int er_k_fps(const float* points_dev, int batch, int n_points, int n_samples, int32_t* idx_out_dev, void* stream);
 /* one sampling-head step on given logits float[B,V]; state arrays are int[B] on device */
 int er_k_sample_head(const float* logits_dev, const er_decode_params* p, int vocab, int eos, int pad,
                      int batch, int step, const int32_t* last_tok_host, const int32_t* counter_host,

@@ -71,6 +71,8 @@ def max_rows_per_call(opt, model, max_new_tokens, device) -> int:
     scratch_row = (d.num_cond_tokens + 1) * (6 * d.hidden_dim + d.intermediate_dim) * 4
     if d.cond_mode == "point":                       # encoder scratch per sample at point_num points (K / V / x rows + the GEGLU buffers)
         scratch_row += (3 * opt.point_num + 14 * d.point_latent_size) * d.point_hidden_dim * 4
+        if d.point_encoder_mode == "downsample":     # per-sample query rows (gathered, ln1, q_proj) and the sampling indices
+            scratch_row += 3 * d.point_latent_size * d.point_hidden_dim * 4 + d.point_latent_size * 4
     _ = model.mesh_decoder                           # materialise the context: the weights are on the device from here on
     free, _total = torch.cuda.mem_get_info(device)
     cap = max(1, int(os.environ.get("ER_INFER_BATCH", "32")))
@@ -90,6 +92,9 @@ def main(argv=None):
     seed_everything(opt.seed)
     if opt.cond_mode not in ("point", "none"):
         raise SystemExit("infer.py serves cond_mode='point' (ArAE preset) and 'none'; see infer_dit.py for the image -> point_latent path")
+    if opt.cond_mode == "point" and opt.point_encoder_mode == "downsample" and opt.point_num < opt.point_latent_size:
+        raise SystemExit(f"[ERROR] point_encoder_mode=downsample samples point_latent_size={opt.point_latent_size} points per cloud: "
+                         f"--point_num {opt.point_num} is too small")
     if not torch.cuda.is_available():
         raise SystemExit("no HIP device visible: this path has no CPU fallback")
     device = torch.device("cuda", local)
