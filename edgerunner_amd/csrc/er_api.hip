@@ -72,9 +72,21 @@ struct Buf {   // grow-only device scratch
     size_t n = 0;
 };
 
+static int ensure(Buf& b, size_t n) {
+    if (b.n >= n) return 0;
+    if (b.p) hipFree(b.p);
+    b.p = nullptr;
+    b.n = 0;
+    HIPCHK(hipMalloc(&b.p, n * sizeof(float)));
+    b.n = n;
+    return 0;
+}
+
+#include "er_weights.h"
+
 // PointEncoderEmbed (core/transformer/point.py:172-206) or, with mode ER_PE_DOWNSAMPLE, PointEncoder (:129-169): weights, shape and
 // scratch.  Embedded in er_ctx (cond_mode POINT) and, after er_dit_attach_point_encoder, in er_dit_ctx; the same helpers
-// (pe_register_keys / pe_load_tensor / point_latent_chunk) serve both.
+// (pe_attach / pe_latent / point_latent_chunk) serve both.
 struct PointEnc {
     int PH = 0, heads = 0, Lq = 0, LD = 0, freq = 0;     // point_hidden_dim, point_num_heads, latent size / dim, point_freq_dim
     int mode = ER_PE_EMBED;  // ER_PE_DOWNSAMPLE: the queries are the point embeddings of a farthest-point subsample (no query_embed)
@@ -84,7 +96,7 @@ struct PointEnc {
     float *ca_q_w = nullptr, *ca_q_b = nullptr, *ca_k_w = nullptr, *ca_k_b = nullptr, *ca_v_w = nullptr, *ca_v_b = nullptr,
           *ca_o_w = nullptr, *ca_o_b = nullptr;
     float *ff0_w = nullptr, *ff0_b = nullptr, *ff2_w = nullptr, *ff2_b = nullptr, *lin_w = nullptr, *lin_b = nullptr;
-    int kpad = 0;            // padded input width of point_embed.mlp (51 -> 64)
+    int kpad = 0;            // padded input width of point_embed.mlp (51 -> 64), set by pe_attach
     Buf a0, x, k, v, qln, q, sc, att, l, ln, u, g, lat;   // scratch of point_latent_chunk; lat = the latent mean [nb][Lq][LD]
     Buf q0, fidx, fdist;     // downsample mode: gathered query rows [nb][Lq][PH], FPS indices [nb][Lq] (int32), FPS distances (large N)
 };
@@ -101,8 +113,7 @@ struct er_ctx {
     bool fast = false;       // fp16 weights + fp16 KV cache, fp32 accumulate
     float *proj_w = nullptr, *proj_b = nullptr, *normc_w = nullptr, *normc_b = nullptr;
     PointEnc pe;             // point encoder (cond_mode POINT)
-    std::map<std::string, bool> need;   // required keys -> loaded?
-    std::vector<void*> owned;           // every hipMalloc'd weight block
+    WeightTable w;           // every checkpoint key (register_weights)
     // KV cache
     int B = 0, Lcap = 0, S_splits = 0;
     void *kc = nullptr, *vc = nullptr;        // [layers][B][H][Lcap][D], fp32 or fp16 (fast)
@@ -149,22 +160,12 @@ struct er_ctx {
     float last_decode_ms = 0.f;
     // scratch for prefill / encoder
     Buf p_hi, p_lo;           // fast-mode prefill: hi / lo fp16 halves of the activation a Linear is about to read (LDS-DMA GEMM, split form)
-    Buf p_h, p_q, p_a, p_y, p_f, p_sc, p_qkv, p_ap, p_aml, e_tmp, e_ids, e_stage;
+    Buf p_h, p_q, p_a, p_y, p_f, p_sc, p_qkv, p_ap, p_aml, e_tmp, e_ids;
     Buf s_lg;                 // er_score: logits of every position when the caller passes no buffer for them
 };
 
 constexpr int ER_MAX_BATCH = 1023;   // h_pinned holds B ints + one flag
 constexpr int NBM = 32;   // batch rows per pass of the matrix-core decode projections (k_gemv_mfma.h)
-
-static int ensure(Buf& b, size_t n) {
-    if (b.n >= n) return 0;
-    if (b.p) hipFree(b.p);
-    b.p = nullptr;
-    b.n = 0;
-    HIPCHK(hipMalloc(&b.p, n * sizeof(float)));
-    b.n = n;
-    return 0;
-}
 
 static void pe_free(PointEnc& p) {
     for (Buf* b : {&p.a0, &p.x, &p.k, &p.v, &p.qln, &p.q, &p.sc, &p.att, &p.l, &p.ln, &p.u, &p.g, &p.lat, &p.q0, &p.fidx, &p.fdist})
@@ -180,57 +181,66 @@ static const char* kKindNames[ER_NUM_KERNEL_KINDS] = {"qkv_gemv", "attn_decode",
                                                       "fc1_gemv", "fc2_gemv", "lm_head_gemv", "sample_head"};
 extern "C" const char* er_kernel_kind_name(int k) { return (k >= 0 && k < ER_NUM_KERNEL_KINDS) ? kKindNames[k] : "?"; }
 
-// every point_encoder.* key the encoder's state_dict holds, as "required, not loaded yet" (PointEncoder, the downsample mode, has
-// no query_embed)
-static void pe_register_keys(std::map<std::string, bool>& n, int mode = ER_PE_EMBED) {
-    auto lin = [&](const std::string& p) {
-        n[p + ".weight"] = false;
-        n[p + ".bias"] = false;
-    };
-    const std::string pe = "point_encoder";
-    if (mode == ER_PE_EMBED) n[pe + ".query_embed"] = false;
-    else n.erase(pe + ".query_embed");
-    n[pe + ".point_embed.basis"] = false;
-    lin(pe + ".point_embed.mlp");
-    lin(pe + ".ln");
-    lin(pe + ".cross_att.ln1");
-    lin(pe + ".cross_att.ln2");
-    for (const char* p : {"q_proj", "k_proj", "v_proj", "out_proj"}) lin(pe + ".cross_att.att." + p);
-    lin(pe + ".cross_att.mlp.net.0");
-    lin(pe + ".cross_att.mlp.net.2");
-    lin(pe + ".linear");
-}
-
-static void register_keys(er_ctx* c) {
-    auto& n = c->need;
-    const er_config& g = c->cfg;
-    auto lin = [&](const std::string& p, bool bias = true) {
-        n[p + ".weight"] = false;
-        if (bias) n[p + ".bias"] = false;
-    };
-    if (g.cond_mode == ER_COND_POINT) pe_register_keys(n, c->pe.mode);
-    if (g.cond_mode != ER_COND_NONE) {
-        lin("proj_cond");
-        lin("norm_cond");
-    }
-    if (g.num_face_buckets > 0) n["embed_num_face.weight"] = false;
-    n["mesh_decoder.model.embd.weight"] = false;
-    n["mesh_decoder.model.embed_positions.weight"] = false;
-    for (int i = 0; i < g.num_layers; ++i) {
-        const std::string L = "mesh_decoder.model.layers." + std::to_string(i);
-        for (const char* p : {"k_proj", "v_proj", "q_proj", "out_proj"}) lin(L + ".self_attn." + p);
-        lin(L + ".self_attn_layer_norm");
-        lin(L + ".fc1");
-        lin(L + ".fc2");
-        lin(L + ".final_layer_norm");
-    }
-    n["mesh_decoder.lm_head.weight"] = false;
-}
-
-static int dev_alloc(er_ctx* c, float** p, size_t n) {
-    HIPCHK(hipMalloc(p, n * sizeof(float)));
-    c->owned.push_back(*p);
+// The encoder's point_encoder.* keys for `mode` (downsample checkpoints have no query_embed) into t, plain fp32 in every precision:
+// at er_create / er_dit_attach_point_encoder and on a mode change, which must come before the first tensor whose key starts with
+// `before` ("" = any key).
+static int pe_attach(WeightTable& t, PointEnc& p, int mode, const char* who, const char* before) {
+    if (mode != ER_PE_EMBED && mode != ER_PE_DOWNSAMPLE)
+        return fail(ER_ERR_INVALID, "%s: %d is neither ER_PE_EMBED nor ER_PE_DOWNSAMPLE", who, mode);
+    for (auto& kv : t.keys)
+        if (kv.second.loaded && kv.first.rfind(before, 0) == 0)
+            return fail(ER_ERR_INVALID, "%s: call it before any '%s*' tensor is loaded", who, before);
+    const size_t PH = p.PH, kin = 2 * p.freq + 3;
+    p.mode = mode;
+    p.kpad = (int)((kin + 15) / 16 * 16);   // so that the point_embed.mlp GEMM's K is a multiple of 16
+    const std::string pe = "point_encoder.";
+    if (mode == ER_PE_EMBED) t.add(pe + "query_embed", &p.query, (size_t)p.Lq * PH);
+    else t.keys.erase(pe + "query_embed");
+    t.add(pe + "point_embed.basis", &p.basis, (size_t)3 * p.freq);
+    t.lin(pe + "point_embed.mlp", &p.mlp_w, &p.mlp_b, PH, kin).pad(kin, p.kpad);
+    t.lin(pe + "ln", &p.ln_w, &p.ln_b, PH, 1);
+    t.lin(pe + "cross_att.ln1", &p.ca_ln1_w, &p.ca_ln1_b, PH, 1);
+    t.lin(pe + "cross_att.ln2", &p.ca_ln2_w, &p.ca_ln2_b, PH, 1);
+    t.lin(pe + "cross_att.att.q_proj", &p.ca_q_w, &p.ca_q_b, PH, PH);
+    t.lin(pe + "cross_att.att.k_proj", &p.ca_k_w, &p.ca_k_b, PH, PH);
+    t.lin(pe + "cross_att.att.v_proj", &p.ca_v_w, &p.ca_v_b, PH, PH);
+    t.lin(pe + "cross_att.att.out_proj", &p.ca_o_w, &p.ca_o_b, PH, PH);
+    t.lin(pe + "cross_att.mlp.net.0", &p.ff0_w, &p.ff0_b, 8 * PH, PH);
+    t.lin(pe + "cross_att.mlp.net.2", &p.ff2_w, &p.ff2_b, PH, 4 * PH);
+    t.lin(pe + "linear", &p.lin_w, &p.lin_b, p.LD, PH);
     return 0;
+}
+
+// every checkpoint key of the decoder context; fp16 mode keeps an fp16 copy of the streamed matrices
+static void register_weights(er_ctx* c) {
+    WeightTable& t = c->w;
+    const er_config& g = c->cfg;
+    const size_t H = g.hidden_dim, I = g.intermediate_dim, V = g.vocab_size;
+    t.fp16 = c->fast;
+    if (g.cond_mode == ER_COND_POINT) pe_attach(t, c->pe, ER_PE_EMBED, "er_create", "");
+    if (g.cond_mode != ER_COND_NONE) {
+        t.lin("proj_cond", &c->proj_w, &c->proj_b, H, g.point_latent_dim);
+        t.lin("norm_cond", &c->normc_w, &c->normc_b, H, 1);
+    }
+    if (g.num_face_buckets > 0) t.add("embed_num_face.weight", &c->embed_num_face, (size_t)g.num_face_buckets * H);
+    t.add("mesh_decoder.model.embd.weight", &c->embd, V * H);
+    t.add("mesh_decoder.model.embed_positions.weight", &c->posemb, (size_t)g.max_positions * H);
+    for (int i = 0; i < g.num_layers; ++i) {
+        LayerW& L = c->layers[i];
+        const std::string p = "mesh_decoder.model.layers." + std::to_string(i) + ".";
+        const char* qkv[3] = {"q_proj", "k_proj", "v_proj"};     // fused [3 H][H] (+ bias [3 H]) in q, k, v order
+        for (size_t j = 0; j < 3; ++j) {
+            const std::string q = p + "self_attn." + qkv[j];
+            t.add(q + ".weight", &L.wqkv, H * H).slice(3 * H * H, j * H * H).half(&L.wqkv_h);
+            t.add(q + ".bias", &L.bqkv, H).slice(3 * H, j * H);
+        }
+        t.lin(p + "self_attn.out_proj", &L.wo, &L.bo, H, H).half(&L.wo_h);
+        t.lin(p + "self_attn_layer_norm", &L.ln1w, &L.ln1b, H, 1);
+        t.lin(p + "fc1", &L.w1, &L.b1, I, H).half(&L.w1_h);
+        t.lin(p + "fc2", &L.w2, &L.b2, H, I).half(&L.w2_h);
+        t.lin(p + "final_layer_norm", &L.ln2w, &L.ln2b, H, 1);
+    }
+    t.add("mesh_decoder.lm_head.weight", &c->lm_head, V * H).half(&c->lm_head_h);
 }
 
 extern "C" int er_create(const er_config* cfg, int device, er_ctx** out) {
@@ -275,7 +285,7 @@ extern "C" int er_create(const er_config* cfg, int device, er_ctx** out) {
     HIPCHK(hipEventCreate(&c->ev0));
     HIPCHK(hipEventCreate(&c->ev1));
     HIPCHK(hipHostMalloc((void**)&c->h_pinned, 4096, hipHostMallocDefault));
-    register_keys(c);
+    register_weights(c);
     *out = c;
     return ER_OK;
 }
@@ -311,9 +321,9 @@ extern "C" int er_destroy(er_ctx* c) {
     hipSetDevice(c->device);
     hipDeviceSynchronize();
     free_kv(c);
-    for (void* p : c->owned) hipFree(p);
+    weights_free(c->w);
     for (Buf* b : {&c->p_hi, &c->p_lo, &c->p_h, &c->p_q, &c->p_a, &c->p_y, &c->p_f, &c->p_sc, &c->p_qkv, &c->p_ap, &c->p_aml,
-                   &c->e_tmp, &c->e_ids, &c->e_stage, &c->s_lg})
+                   &c->e_tmp, &c->e_ids, &c->s_lg})
         if (b->p) hipFree(b->p);
     pe_free(c->pe);
     if (c->ev0) hipEventDestroy(c->ev0);
@@ -325,240 +335,18 @@ extern "C" int er_destroy(er_ctx* c) {
 }
 
 // ------------------------------------------------------------------------------------ weights
-static std::vector<float> to_f32_host(const void* data, int dtype, size_t n, int on_device, int* err) {
-    std::vector<float> out(n);
-    const size_t esz = (dtype == ER_F32) ? 4 : 2;
-    std::vector<unsigned char> raw;
-    const unsigned char* src = (const unsigned char*)data;
-    if (on_device) {
-        raw.resize(n * esz);
-        if (hipMemcpy(raw.data(), data, n * esz, hipMemcpyDeviceToHost) != hipSuccess) { *err = 1; return out; }
-        src = raw.data();
-    }
-    if (dtype == ER_F32) {
-        memcpy(out.data(), src, n * 4);
-    } else if (dtype == ER_BF16) {
-        const uint16_t* h = (const uint16_t*)src;
-        for (size_t i = 0; i < n; ++i) { uint32_t u = (uint32_t)h[i] << 16; memcpy(&out[i], &u, 4); }
-    } else {  // IEEE fp16
-        const uint16_t* h = (const uint16_t*)src;
-        for (size_t i = 0; i < n; ++i) {
-            const uint32_t s = (h[i] >> 15) & 1, e = (h[i] >> 10) & 31, m = h[i] & 1023;
-            uint32_t u;
-            if (e == 0) {
-                if (m == 0) u = s << 31;
-                else { int sh = 0; uint32_t mm = m; while (!(mm & 1024)) { mm <<= 1; ++sh; } u = (s << 31) | ((127 - 15 - sh + 1) << 23) | ((mm & 1023) << 13); }
-            } else if (e == 31) u = (s << 31) | 0x7f800000u | (m << 13);
-            else u = (s << 31) | ((e - 15 + 127) << 23) | (m << 13);
-            memcpy(&out[i], &u, 4);
-        }
-    }
-    return out;
-}
-
-static bool ends_with(const std::string& s, const char* suf) {
-    const size_t n = strlen(suf);
-    return s.size() >= n && s.compare(s.size() - n, n, suf) == 0;
-}
-
-// dtype conversion on the device (round 1 converted every tensor through a host fp32 vector: 7.4 s for the 2.7 GB
-// checkpoint, most of it scalar fp16 loops)
-__device__ __forceinline__ float raw_to_f32(const void* src, int dtype, size_t i) {
-    if (dtype == ER_F32) return reinterpret_cast<const float*>(src)[i];
-    if (dtype == ER_F16) return (float)reinterpret_cast<const _Float16*>(src)[i];
-    const unsigned int u = (unsigned int)reinterpret_cast<const unsigned short*>(src)[i] << 16;      // bf16
-    return __uint_as_float(u);
-}
-__global__ void cvt_f32_kernel(const void* src, int dtype, float* dst, size_t n) {
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
-        dst[i] = raw_to_f32(src, dtype, i);
-}
-// streamed decoder matrix in fast mode: the fp16 copy (round to nearest even) and an fp32 copy of the SAME rounded values
-__global__ void cvt_streamed_kernel(const void* src, int dtype, float* dst32, _Float16* dst16, size_t n) {
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        const _Float16 hv = (_Float16)raw_to_f32(src, dtype, i);
-        dst16[i] = hv;
-        dst32[i] = (float)hv;
-    }
-}
-
-// One point_encoder.* tensor into p: src = its raw bytes on the device (dtype, n elements); data / on_device = the caller's copy (the
-// small point_embed.mlp weight is padded on the host).  Plain fp32 storage in every precision.  Returns 1 for a key that is not the
-// encoder's.  The blocks are recorded in `owned`; the copies are complete when this returns (stream st is synchronised).
-static int pe_load_tensor(PointEnc& p, std::vector<void*>& owned, const std::string& key, const void* src, const void* data, int dtype,
-                          size_t n, int on_device, hipStream_t st) {
-    const int PH = p.PH;
-    const unsigned cgrid = (unsigned)std::min<size_t>((n + 255) / 256, 4096);
-    auto put = [&](float** dst, size_t want) -> int {
-        if (n != want) return fail(ER_ERR_INVALID, "er_load_tensor(%s): %zu elements, expected %zu", key.c_str(), n, want);
-        if (!*dst) {
-            HIPCHK(hipMalloc(dst, want * sizeof(float)));
-            owned.push_back(*dst);
-        }
-        hipLaunchKernelGGL(cvt_f32_kernel, dim3(cgrid), dim3(256), 0, st, src, dtype, *dst, want);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipStreamSynchronize(st));
-        return 0;
-    };
-    if (key == "point_encoder.query_embed") return p.mode == ER_PE_EMBED ? put(&p.query, (size_t)p.Lq * PH) : 1;
-    if (key == "point_encoder.point_embed.basis") return put(&p.basis, (size_t)3 * p.freq);
-    if (key == "point_encoder.point_embed.mlp.weight") {
-        // [PH][2F+3] -> zero-padded [PH][kpad] so the GEMM K is a multiple of 16
-        const int kin = 2 * p.freq + 3;
-        p.kpad = (kin + 15) / 16 * 16;
-        if (n != (size_t)PH * kin) return fail(ER_ERR_INVALID, "er_load_tensor(%s): %zu elements, expected %zu", key.c_str(), n, (size_t)PH * kin);
-        int err = 0;
-        std::vector<float> h = to_f32_host(data, dtype, n, on_device, &err);     // small tensor: padded on the host
-        if (err) return fail(ER_ERR_HIP, "er_load_tensor(%s): device read failed", key.c_str());
-        std::vector<float> padded((size_t)PH * p.kpad, 0.f);
-        for (int r = 0; r < PH; ++r) memcpy(&padded[(size_t)r * p.kpad], &h[(size_t)r * kin], kin * 4);
-        if (!p.mlp_w) {
-            HIPCHK(hipMalloc(&p.mlp_w, padded.size() * sizeof(float)));
-            owned.push_back(p.mlp_w);
-        }
-        HIPCHK(hipMemcpy(p.mlp_w, padded.data(), padded.size() * 4, hipMemcpyHostToDevice));
-        return 0;
-    }
-    if (key == "point_encoder.point_embed.mlp.bias") return put(&p.mlp_b, PH);
-    if (key == "point_encoder.ln.weight") return put(&p.ln_w, PH);
-    if (key == "point_encoder.ln.bias") return put(&p.ln_b, PH);
-    if (key == "point_encoder.cross_att.ln1.weight") return put(&p.ca_ln1_w, PH);
-    if (key == "point_encoder.cross_att.ln1.bias") return put(&p.ca_ln1_b, PH);
-    if (key == "point_encoder.cross_att.ln2.weight") return put(&p.ca_ln2_w, PH);
-    if (key == "point_encoder.cross_att.ln2.bias") return put(&p.ca_ln2_b, PH);
-    if (key == "point_encoder.cross_att.att.q_proj.weight") return put(&p.ca_q_w, (size_t)PH * PH);
-    if (key == "point_encoder.cross_att.att.q_proj.bias") return put(&p.ca_q_b, PH);
-    if (key == "point_encoder.cross_att.att.k_proj.weight") return put(&p.ca_k_w, (size_t)PH * PH);
-    if (key == "point_encoder.cross_att.att.k_proj.bias") return put(&p.ca_k_b, PH);
-    if (key == "point_encoder.cross_att.att.v_proj.weight") return put(&p.ca_v_w, (size_t)PH * PH);
-    if (key == "point_encoder.cross_att.att.v_proj.bias") return put(&p.ca_v_b, PH);
-    if (key == "point_encoder.cross_att.att.out_proj.weight") return put(&p.ca_o_w, (size_t)PH * PH);
-    if (key == "point_encoder.cross_att.att.out_proj.bias") return put(&p.ca_o_b, PH);
-    if (key == "point_encoder.cross_att.mlp.net.0.weight") return put(&p.ff0_w, (size_t)8 * PH * PH);
-    if (key == "point_encoder.cross_att.mlp.net.0.bias") return put(&p.ff0_b, (size_t)8 * PH);
-    if (key == "point_encoder.cross_att.mlp.net.2.weight") return put(&p.ff2_w, (size_t)PH * 4 * PH);
-    if (key == "point_encoder.cross_att.mlp.net.2.bias") return put(&p.ff2_b, PH);
-    if (key == "point_encoder.linear.weight") return put(&p.lin_w, (size_t)p.LD * PH);
-    if (key == "point_encoder.linear.bias") return put(&p.lin_b, p.LD);
-    return 1;
-}
-
-extern "C" int er_load_tensor(er_ctx* c, const char* key_c, const void* data, int dtype, int ndim, const int64_t* shape,
+extern "C" int er_load_tensor(er_ctx* c, const char* key, const void* data, int dtype, int ndim, const int64_t* shape,
                               int on_device) {
-    if (!c || !key_c || !data || ndim < 1 || ndim > 4) return fail(ER_ERR_INVALID, "er_load_tensor: bad argument");
-    if (dtype != ER_F32 && dtype != ER_F16 && dtype != ER_BF16) return fail(ER_ERR_INVALID, "er_load_tensor: dtype %d", dtype);
+    if (!c || !key) return fail(ER_ERR_INVALID, "er_load_tensor: bad argument");
     HIPCHK(hipSetDevice(c->device));
-    const std::string key(key_c);
-    auto it = c->need.find(key);
-    if (it == c->need.end()) return 1;   // strict=False: unknown keys are ignored
-    c->tiled_valid = false;              // any reload invalidates the tiled copies of the batched path
-    size_t n = 1;
-    for (int i = 0; i < ndim; ++i) n *= (size_t)shape[i];
-    const er_config& g = c->cfg;
-    const int H = g.hidden_dim, I = g.intermediate_dim;
-    const size_t esz = (dtype == ER_F32) ? 4 : 2;
-    // the tensor's raw bytes on the device: the caller's buffer, or one upload into the grow-only staging block
-    const void* src = data;
-    if (!on_device) {
-        ERCHK(ensure(c->e_stage, (n * esz + 3) / 4));
-        HIPCHK(hipMemcpy(c->e_stage.p, data, n * esz, hipMemcpyHostToDevice));
-        src = c->e_stage.p;
-    }
-    const unsigned cgrid = (unsigned)std::min<size_t>((n + 255) / 256, 4096);
-
-    auto expect = [&](size_t want) -> int {
-        if (n != want) return fail(ER_ERR_INVALID, "er_load_tensor(%s): %zu elements, expected %zu", key_c, n, want);
-        return 0;
-    };
-    auto finish = [&]() -> int {          // the staging block / caller buffer may be reused as soon as we return
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipStreamSynchronize(c->own_stream));
-        return 0;
-    };
-    auto put = [&](float** dst, size_t want) -> int {   // plain copy into a fresh block
-        ERCHK(expect(want));
-        if (!*dst) ERCHK(dev_alloc(c, dst, want));
-        hipLaunchKernelGGL(cvt_f32_kernel, dim3(cgrid), dim3(256), 0, c->own_stream, src, dtype, *dst, want);
-        return finish();
-    };
-    // streamed decoder matrix: fp32 copy (+ fp16 copy and fp16-rounded fp32 values in fast mode)
-    auto put_w = [&](float** dst, _Float16** dst_h, size_t total, size_t off, size_t want) -> int {
-        ERCHK(expect(want));
-        if (!*dst) { ERCHK(dev_alloc(c, dst, total)); HIPCHK(hipMemset(*dst, 0, total * 4)); }
-        if (c->fast) {
-            if (!*dst_h) {
-                HIPCHK(hipMalloc((void**)dst_h, total * 2));
-                c->owned.push_back(*dst_h);
-                HIPCHK(hipMemset(*dst_h, 0, total * 2));
-            }
-            hipLaunchKernelGGL(cvt_streamed_kernel, dim3(cgrid), dim3(256), 0, c->own_stream, src, dtype, *dst + off, *dst_h + off, want);
-        } else {
-            hipLaunchKernelGGL(cvt_f32_kernel, dim3(cgrid), dim3(256), 0, c->own_stream, src, dtype, *dst + off, want);
-        }
-        return finish();
-    };
-    auto put_at = [&](float** dst, size_t total, size_t off, size_t want) -> int {   // slice of a fused block
-        ERCHK(expect(want));
-        if (!*dst) { ERCHK(dev_alloc(c, dst, total)); HIPCHK(hipMemset(*dst, 0, total * 4)); }
-        hipLaunchKernelGGL(cvt_f32_kernel, dim3(cgrid), dim3(256), 0, c->own_stream, src, dtype, *dst + off, want);
-        return finish();
-    };
-
-    int rc = 0;
-    const std::string dec = "mesh_decoder.model.layers.";
-    if (key.rfind(dec, 0) == 0) {
-        const size_t dot = key.find('.', dec.size());
-        const int li = atoi(key.substr(dec.size(), dot - dec.size()).c_str());
-        if (li < 0 || li >= g.num_layers) return fail(ER_ERR_INVALID, "layer index out of range in %s", key_c);
-        LayerW& L = c->layers[li];
-        const std::string rest = key.substr(dot + 1);
-        const size_t HH = (size_t)H * H;
-        if (rest == "self_attn.q_proj.weight") rc = put_w(&L.wqkv, &L.wqkv_h, 3 * HH, 0, HH);
-        else if (rest == "self_attn.k_proj.weight") rc = put_w(&L.wqkv, &L.wqkv_h, 3 * HH, HH, HH);
-        else if (rest == "self_attn.v_proj.weight") rc = put_w(&L.wqkv, &L.wqkv_h, 3 * HH, 2 * HH, HH);
-        else if (rest == "self_attn.q_proj.bias") rc = put_at(&L.bqkv, 3 * H, 0, H);
-        else if (rest == "self_attn.k_proj.bias") rc = put_at(&L.bqkv, 3 * H, H, H);
-        else if (rest == "self_attn.v_proj.bias") rc = put_at(&L.bqkv, 3 * H, 2 * H, H);
-        else if (rest == "self_attn.out_proj.weight") rc = put_w(&L.wo, &L.wo_h, HH, 0, HH);
-        else if (rest == "self_attn.out_proj.bias") rc = put(&L.bo, H);
-        else if (rest == "self_attn_layer_norm.weight") rc = put(&L.ln1w, H);
-        else if (rest == "self_attn_layer_norm.bias") rc = put(&L.ln1b, H);
-        else if (rest == "fc1.weight") rc = put_w(&L.w1, &L.w1_h, (size_t)I * H, 0, (size_t)I * H);
-        else if (rest == "fc1.bias") rc = put(&L.b1, I);
-        else if (rest == "fc2.weight") rc = put_w(&L.w2, &L.w2_h, (size_t)H * I, 0, (size_t)H * I);
-        else if (rest == "fc2.bias") rc = put(&L.b2, H);
-        else if (rest == "final_layer_norm.weight") rc = put(&L.ln2w, H);
-        else if (rest == "final_layer_norm.bias") rc = put(&L.ln2b, H);
-        else return 1;
-    } else if (key == "mesh_decoder.model.embd.weight") rc = put(&c->embd, (size_t)g.vocab_size * H);
-    else if (key == "mesh_decoder.model.embed_positions.weight") rc = put(&c->posemb, (size_t)g.max_positions * H);
-    else if (key == "mesh_decoder.lm_head.weight") rc = put_w(&c->lm_head, &c->lm_head_h, (size_t)g.vocab_size * H, 0, (size_t)g.vocab_size * H);
-    else if (key == "embed_num_face.weight") rc = put(&c->embed_num_face, (size_t)g.num_face_buckets * H);
-    else if (key == "proj_cond.weight") rc = put(&c->proj_w, (size_t)H * g.point_latent_dim);
-    else if (key == "proj_cond.bias") rc = put(&c->proj_b, H);
-    else if (key == "norm_cond.weight") rc = put(&c->normc_w, H);
-    else if (key == "norm_cond.bias") rc = put(&c->normc_b, H);
-    else if (key.rfind("point_encoder.", 0) == 0) {
-        rc = pe_load_tensor(c->pe, c->owned, key, src, data, dtype, n, on_device, c->own_stream);
-        if (rc == 1) return 1;
-    }
-    else return 1;
-    if (rc < 0) return rc;
-    it->second = true;
-    (void)ends_with;
-    return ER_OK;
+    const int rc = weights_load(c->w, c->own_stream, "er_load_tensor", key, data, dtype, ndim, shape, on_device);
+    if (rc != 1) c->tiled_valid = false;  // any reload invalidates the tiled copies of the batched path
+    return rc;
 }
 
 extern "C" int er_finalize_weights(er_ctx* c) {
     if (!c) return fail(ER_ERR_INVALID, "null ctx");
-    for (auto& kv : c->need)
-        if (!kv.second) return fail(ER_ERR_MISSING, "tensor '%s' was never loaded", kv.first.c_str());
-    if (c->e_stage.p) {                   // checkpoint complete: the upload staging block (up to one tensor) is not needed any more
-        hipFree(c->e_stage.p);
-        c->e_stage.p = nullptr;
-        c->e_stage.n = 0;
-    }
-    return ER_OK;
+    return weights_finalize(c->w);
 }
 
 // second copy of the qkv / fc1 / fc2 matrices in the layout the matrix-core batched kernels stream (made the first
@@ -567,7 +355,7 @@ template <typename WT>
 static int make_tiled(er_ctx* c, const void* src, void** dst, int N, int K) {
     if (!*dst) {
         HIPCHK(hipMalloc(dst, tiled_weight_bytes<WT>(N, K)));
-        c->owned.push_back(*dst);
+        c->w.owned.push_back(*dst);
     }
     hipLaunchKernelGGL((tile_weights_kernel<WT>), dim3(2048), dim3(ER_WG), 0, c->own_stream, reinterpret_cast<const WT*>(src),
                        reinterpret_cast<f32x4*>(*dst), N, K);
@@ -575,9 +363,7 @@ static int make_tiled(er_ctx* c, const void* src, void** dst, int N, int K) {
     return 0;
 }
 static int make_tiled_weights(er_ctx* c) {
-    if (c->tiled_valid) return 0;
-    for (auto& kv : c->need)
-        if (!kv.second) return 0;          // weights still loading: er_prefill comes back here
+    if (c->tiled_valid || weights_missing(c->w)) return 0;   // weights still loading: er_prefill comes back here
     const int H = c->cfg.hidden_dim, I = c->cfg.intermediate_dim;
     for (LayerW& L : c->layers) {
         if (c->fast) {
@@ -1133,7 +919,9 @@ static int attention_full(const float* Q, int ldq, const float* Kp, int ldk, lon
 // PointEncoderEmbed (core/transformer/point.py:186-206) of nb samples of N points each: the latent mean (posterior.mode(), :201)
 // into p.lat [nb][Lq][LD].  Shared by er_encode_cond (which projects it, core/models.py:124), er_point_latent and
 // er_dit_point_latent.  Mode ER_PE_DOWNSAMPLE is PointEncoder (:143-169): the queries are point_embed (before ln) of the Lq points a
-// farthest point sampling picks from each cloud (k_fps.h), one query table per sample.
+// farthest point sampling picks from each cloud (k_fps.h), one query table per sample.  Callers go through the samples in chunks of
+// up to ENC_CHUNK (scratch for one chunk at N = 4096: ~5 GB); every GEMM / LayerNorm / attention launch of a chunk covers all of them.
+constexpr int ENC_CHUNK = 32;
 static int point_latent_chunk(PointEnc& p, const float* pts, int nb, int N, hipStream_t st) {
     const int PH = p.PH, Lq = p.Lq, LD = p.LD;
     const int PHh = p.heads > 0 ? p.heads : 1, PD = PH / PHh;
@@ -1214,6 +1002,18 @@ static int point_latent_chunk(PointEnc& p, const float* pts, int nb, int N, hipS
     return 0;
 }
 
+// the latent means of B clouds of N points into latent_out [B][Lq][LD] (er_point_latent, er_dit_point_latent)
+static int pe_latent(PointEnc& p, const float* pts, int B, int N, float* latent_out, hipStream_t st, const char* who) {
+    const size_t per = (size_t)p.Lq * p.LD;
+    if ((long long)B * (long long)per > 0x7fffffffLL) return fail(ER_ERR_CAPACITY, "%s: batch %d too large", who, B);
+    for (int b0 = 0; b0 < B; b0 += ENC_CHUNK) {
+        const int nb = std::min(ENC_CHUNK, B - b0);
+        ERCHK(point_latent_chunk(p, pts + (size_t)b0 * N * 3, nb, N, st));
+        HIPCHK(hipMemcpyAsync(latent_out + (size_t)b0 * per, p.lat.p, (size_t)nb * per * 4, hipMemcpyDeviceToDevice, st));
+    }
+    return 0;
+}
+
 extern "C" int er_encode_cond(er_ctx* c, const float* conds, int B, int n_points, const int32_t* face_bucket,
                               float* cond_out, void* stream) {
     if (!c || !cond_out || B <= 0) return fail(ER_ERR_INVALID, "er_encode_cond: bad argument");
@@ -1227,9 +1027,6 @@ extern "C" int er_encode_cond(er_ctx* c, const float* conds, int B, int n_points
     if (n_lat + n_face != C) return fail(ER_ERR_INVALID, "num_cond_tokens %d != latent tokens %d + face token %d", C, n_lat, n_face);
     if (g.cond_mode != ER_COND_NONE && !conds) return fail(ER_ERR_INVALID, "er_encode_cond: conds is null");
     if (LD % 16) return fail(ER_ERR_UNSUPPORTED, "point_latent_dim must be a multiple of 16");
-    // samples are encoded in chunks of up to 32 (scratch for one chunk at N = 4096: ~5 GB); every GEMM / LayerNorm /
-    // attention launch of a chunk covers all of its samples
-    constexpr int ENC_CHUNK = 32;
     for (int b0 = 0; b0 < B; b0 += ENC_CHUNK) {
         const int nb = std::min(ENC_CHUNK, B - b0);
         const float* lat = nullptr;   // [nb][Lq][LD]
@@ -1452,29 +1249,17 @@ extern "C" int er_point_latent(er_ctx* c, const float* conds, int B, int n_point
     ERCHK(er_finalize_weights(c));
     HIPCHK(hipSetDevice(c->device));
     hipStream_t st = pick(c, stream);
-    const size_t per = (size_t)c->cfg.point_latent_size * c->cfg.point_latent_dim;
-    if ((long long)B * (long long)per > 0x7fffffffLL) return fail(ER_ERR_CAPACITY, "er_point_latent: batch %d too large", B);
-    constexpr int ENC_CHUNK = 32;        // as er_encode_cond
-    for (int b0 = 0; b0 < B; b0 += ENC_CHUNK) {
-        const int nb = std::min(ENC_CHUNK, B - b0);
-        ERCHK(point_latent_chunk(c->pe, conds + (size_t)b0 * n_points * 3, nb, n_points, st));
-        HIPCHK(hipMemcpyAsync(latent_out + (size_t)b0 * per, c->pe.lat.p, (size_t)nb * per * 4, hipMemcpyDeviceToDevice, st));
-    }
-    if (kl_out) HIPRET(launch_score_reduce(latent_out, nullptr, (int)((size_t)B * per), 0, kl_out, st));
+    ERCHK(pe_latent(c->pe, conds, B, n_points, latent_out, st, "er_point_latent"));
+    const size_t n = (size_t)B * c->pe.Lq * c->pe.LD;
+    if (kl_out) HIPRET(launch_score_reduce(latent_out, nullptr, (int)n, 0, kl_out, st));
     return ER_OK;
 }
 
 extern "C" int er_set_point_encoder_mode(er_ctx* c, int mode) {
     if (!c) return fail(ER_ERR_INVALID, "null ctx");
-    if (mode != ER_PE_EMBED && mode != ER_PE_DOWNSAMPLE)
-        return fail(ER_ERR_INVALID, "er_set_point_encoder_mode: %d is neither ER_PE_EMBED nor ER_PE_DOWNSAMPLE", mode);
     if (c->cfg.cond_mode != ER_COND_POINT)
         return fail(ER_ERR_UNSUPPORTED, "er_set_point_encoder_mode: the context has no point encoder (cond_mode %d)", c->cfg.cond_mode);
-    for (auto& kv : c->need)
-        if (kv.second) return fail(ER_ERR_INVALID, "er_set_point_encoder_mode: call it before the first er_load_tensor");
-    c->pe.mode = mode;
-    pe_register_keys(c->need, mode);
-    return ER_OK;
+    return pe_attach(c->w, c->pe, mode, "er_set_point_encoder_mode", "");
 }
 
 extern "C" int er_logits(er_ctx* c, float* out, void* stream) {

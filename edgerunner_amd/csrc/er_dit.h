@@ -1,5 +1,6 @@
-// DiT image-conditioned front-end behind the C ABI (er_dit_*): included at the end of er_api.hip so it can
-// reuse the prefill building blocks (the GEMM launchers, attention_full, ensure, fail, HIPCHK/HIPRET/ERCHK).
+// DiT image-conditioned front-end behind the C ABI (er_dit_*): included at the end of er_api.hip so it can reuse the prefill
+// building blocks (the GEMM launchers, attention_full, ensure, fail, HIPCHK/HIPRET/ERCHK), the weight table and loader
+// (er_weights.h) and the point encoder helpers.
 // Reference: core/transformer/dit.py (DiT, DiTLayer, TimestepEmbedding) and core/models_dit.py::MDiT.run.
 #pragma once
 #include "k_dit.h"
@@ -23,8 +24,6 @@ struct ClipLayerW {
     float *f1w = nullptr, *f1b = nullptr, *f2w = nullptr, *f2b = nullptr;
 };
 
-struct DitSlot { float** p; size_t n; bool loaded; };
-
 struct er_dit_ctx {
     er_dit_config cfg{};
     int device = 0;
@@ -37,10 +36,8 @@ struct er_dit_ctx {
     float *clip_cls = nullptr, *clip_patch_w = nullptr, *clip_pos = nullptr, *clip_prew = nullptr, *clip_preb = nullptr;
     int clip_kpad = 0;
     Buf cpx, ccol, cpatch, cx, ch, cq, ck, cv, catt, cf;
-    std::map<std::string, DitSlot> slots;
-    std::vector<void*> owned;
+    WeightTable w;                                       // every checkpoint key (dit_weights); w.half_of: the fp16 copies of fast mode
     bool fast = false;                                   // fp16-input MFMA for every Linear (weights stored fp16 too)
-    std::map<const float*, const _Float16*> half_of;     // fp32 weight block -> its fp16 copy
     Buf x, qkv, att, q2, kv2, u, g, sc, tin, temb0, temb1, temb, tsil, tada, gate, t_dev, xin, pred, czero, ctmp;
     // fp16 mode: fp16 copies of the activations that feed a Linear, written by their producers (k_gemm.h, gemm_hh_mfma_kernel)
     Buf x16, att16, g16;
@@ -53,38 +50,35 @@ struct er_dit_ctx {
     int pred_type = ER_PRED_V_PREDICTION;  // what the DiT predicts (er_dit_set_prediction_type): the sampler's DDIM update and the loss target
     // the reference's frozen point encoder (MDiT.point_encoder, core/models_dit.py:68-75), after er_dit_attach_point_encoder only
     bool has_pe = false;
-    PointEnc pe;
-    std::map<std::string, bool> pe_need;   // its keys -> loaded?
+    PointEnc pe;                           // its point_encoder.* keys join `w` when it is attached
     Buf lcoef, lpart;                      // er_dit_loss: [sa | sb | w] per sample, partial sums (doubles)
 };
 
-static void dit_register(er_dit_ctx* c) {
+// every checkpoint key of the DiT (+ CLIP) context; fp16 mode keeps an fp16 copy of the Linear and patch-conv weights (GEMM operands)
+static void dit_weights(er_dit_ctx* c) {
+    WeightTable& t = c->w;
     const er_dit_config& g = c->cfg;
     const size_t C = g.hidden_dim;
-    auto add = [&](const std::string& k, float** p, size_t n) { c->slots[k] = DitSlot{p, n, false}; };
-    auto lin = [&](const std::string& k, float** w, float** b, size_t out, size_t in) {
-        add(k + ".weight", w, out * in);
-        add(k + ".bias", b, out);
-    };
-    add("dit.pos_embed", &c->pos_embed, (size_t)g.latent_size * C);
-    add("dit.scale_shift_table", &c->sst2, 2 * C);
+    t.fp16 = c->fast;
+    auto lin = [&](const std::string& k, float** w, float** b, size_t out, size_t in) { t.lin(k, w, b, out, in).half(); };
+    auto norm = [&](const std::string& k, float** w, float** b, size_t n) { t.lin(k, w, b, n, 1); };
+    t.add("dit.pos_embed", &c->pos_embed, (size_t)g.latent_size * C);
+    t.add("dit.scale_shift_table", &c->sst2, 2 * C);
     lin("dit.proj_in", &c->proj_in_w, &c->proj_in_b, C, g.latent_dim);
     lin("dit.timestep_proj.linear_1", &c->tp1_w, &c->tp1_b, C, 256);
     lin("dit.timestep_proj.linear_2", &c->tp2_w, &c->tp2_b, C, C);
     lin("dit.adaln_linear", &c->adaln_w, &c->adaln_b, 6 * C, C);
     lin("dit.proj_out", &c->proj_out_w, &c->proj_out_b, g.latent_dim, C);
     lin("proj_cond", &c->projc_w, &c->projc_b, C, g.clip_dim);
-    add("norm_cond.weight", &c->normc_w, C);
-    add("norm_cond.bias", &c->normc_b, C);
+    norm("norm_cond", &c->normc_w, &c->normc_b, C);
     if (g.clip_layers > 0) {
         const std::string p = "image_encoder.vision_model";
         const size_t W = g.clip_dim, P = g.clip_patch, NT = (size_t)(g.clip_image_size / g.clip_patch) * (g.clip_image_size / g.clip_patch) + 1;
         c->clip_kpad = (int)((3 * P * P + 31) / 32 * 32);
-        add(p + ".embeddings.class_embedding", &c->clip_cls, W);
-        add(p + ".embeddings.patch_embedding.weight", &c->clip_patch_w, W * 3 * P * P);   // stored zero-padded to clip_kpad columns
-        add(p + ".embeddings.position_embedding.weight", &c->clip_pos, NT * W);
-        add(p + ".pre_layrnorm.weight", &c->clip_prew, W);
-        add(p + ".pre_layrnorm.bias", &c->clip_preb, W);
+        t.add(p + ".embeddings.class_embedding", &c->clip_cls, W);
+        t.add(p + ".embeddings.patch_embedding.weight", &c->clip_patch_w, W * 3 * P * P).pad(3 * P * P, c->clip_kpad).half();
+        t.add(p + ".embeddings.position_embedding.weight", &c->clip_pos, NT * W);
+        norm(p + ".pre_layrnorm", &c->clip_prew, &c->clip_preb, W);
         for (int i = 0; i < g.clip_layers; ++i) {
             ClipLayerW& L = c->clip[i];
             const std::string q = p + ".encoder.layers." + std::to_string(i);
@@ -92,8 +86,8 @@ static void dit_register(er_dit_ctx* c) {
             lin(q + ".self_attn.k_proj", &L.kw, &L.kb, W, W);
             lin(q + ".self_attn.v_proj", &L.vw, &L.vb, W, W);
             lin(q + ".self_attn.out_proj", &L.ow, &L.ob, W, W);
-            add(q + ".layer_norm1.weight", &L.ln1w, W); add(q + ".layer_norm1.bias", &L.ln1b, W);
-            add(q + ".layer_norm2.weight", &L.ln2w, W); add(q + ".layer_norm2.bias", &L.ln2b, W);
+            norm(q + ".layer_norm1", &L.ln1w, &L.ln1b, W);
+            norm(q + ".layer_norm2", &L.ln2w, &L.ln2b, W);
             lin(q + ".mlp.fc1", &L.f1w, &L.f1b, g.clip_mlp_dim, W);
             lin(q + ".mlp.fc2", &L.f2w, &L.f2b, W, g.clip_mlp_dim);
         }
@@ -101,7 +95,7 @@ static void dit_register(er_dit_ctx* c) {
     for (int i = 0; i < g.num_layers; ++i) {
         DitLayerW& L = c->layers[i];
         const std::string p = "dit.layers." + std::to_string(i);
-        add(p + ".scale_shift_table", &L.sst, 6 * C);
+        t.add(p + ".scale_shift_table", &L.sst, 6 * C);
         lin(p + ".attn1.qkv_proj", &L.qkv_w, &L.qkv_b, 3 * C, C);
         lin(p + ".attn1.out_proj", &L.o_w, &L.o_b, C, C);
         lin(p + ".attn2.q_proj", &L.q2_w, &L.q2_b, C, C);
@@ -132,7 +126,7 @@ extern "C" int er_dit_create(const er_dit_config* cfg, int device, er_dit_ctx** 
         c->clip.resize(cfg->clip_layers);
     }
     HIPCHK(hipStreamCreateWithFlags(&c->own_stream, hipStreamDefault));
-    dit_register(c);
+    dit_weights(c);
     *out = c;
     return ER_OK;
 }
@@ -141,7 +135,7 @@ extern "C" int er_dit_destroy(er_dit_ctx* c) {
     if (!c) return ER_OK;
     hipSetDevice(c->device);
     hipDeviceSynchronize();
-    for (void* p : c->owned) hipFree(p);
+    weights_free(c->w);
     for (Buf* b : {&c->cpx, &c->ccol, &c->cpatch, &c->cx, &c->ch, &c->cq, &c->ck, &c->cv, &c->catt, &c->cf})
         if (b->p) hipFree(b->p);
     for (Buf* b : {&c->x, &c->qkv, &c->att, &c->q2, &c->kv2, &c->u, &c->g, &c->sc, &c->tin, &c->temb0, &c->temb1, &c->temb,
@@ -156,75 +150,19 @@ extern "C" int er_dit_destroy(er_dit_ctx* c) {
 
 extern "C" int er_dit_load_tensor(er_dit_ctx* c, const char* key, const void* data, int dtype, int ndim, const int64_t* shape,
                                   int on_device) {
-    if (!c || !key || !data || ndim < 1 || ndim > 4) return fail(ER_ERR_INVALID, "er_dit_load_tensor: bad argument");
+    if (!c || !key) return fail(ER_ERR_INVALID, "er_dit_load_tensor: bad argument");
     HIPCHK(hipSetDevice(c->device));
     std::string k(key);
-    if (c->has_pe && k.rfind("point_encoder.", 0) == 0) {
-        auto pit = c->pe_need.find(k);
-        if (pit == c->pe_need.end()) return 1;
-        if (dtype != ER_F32 && dtype != ER_F16 && dtype != ER_BF16) return fail(ER_ERR_INVALID, "er_dit_load_tensor: dtype %d", dtype);
-        size_t n = 1;
-        for (int i = 0; i < ndim; ++i) n *= (size_t)shape[i];
-        const size_t esz = dtype == ER_F32 ? 4 : 2;
-        void* stage = nullptr;                 // the raw bytes on the device for the converting copy of pe_load_tensor
-        if (!on_device) {
-            HIPCHK(hipMalloc(&stage, n * esz));
-            if (hipMemcpy(stage, data, n * esz, hipMemcpyHostToDevice) != hipSuccess) {
-                hipFree(stage);
-                return fail(ER_ERR_HIP, "er_dit_load_tensor(%s): upload failed", key);
-            }
-        }
-        const int rc = pe_load_tensor(c->pe, c->owned, k, on_device ? data : stage, data, dtype, n, on_device, c->own_stream);
-        if (stage) hipFree(stage);
-        if (rc < 0) return rc;
-        pit->second = true;
-        return ER_OK;
-    }
     if (k.rfind("image_encoder.", 0) == 0 && k.find("image_encoder.vision_model.") != 0)
         k = "image_encoder.vision_model." + k.substr(strlen("image_encoder."));      // transformers >= 5 drops the prefix
-    auto it = c->slots.find(k);
-    if (it == c->slots.end()) return 1;
-    size_t n = 1;
-    for (int i = 0; i < ndim; ++i) n *= (size_t)shape[i];
-    if (n != it->second.n) return fail(ER_ERR_INVALID, "er_dit_load_tensor(%s): %zu elements, expected %zu", key, n, it->second.n);
-    int err = 0;
-    std::vector<float> h = to_f32_host(data, dtype, n, on_device, &err);
-    if (err) return fail(ER_ERR_HIP, "er_dit_load_tensor(%s): device read failed", key);
-    if (k == "image_encoder.vision_model.embeddings.patch_embedding.weight") {   // [W][3*P*P] -> zero-padded [W][kpad]
-        const size_t W = c->cfg.clip_dim, kin = n / W, kp = c->clip_kpad;
-        std::vector<float> padded(W * kp, 0.f);
-        for (size_t r = 0; r < W; ++r) memcpy(&padded[r * kp], &h[r * kin], kin * 4);
-        h.swap(padded);
-        n = W * kp;
-    }
-    if (!*it->second.p) {
-        HIPCHK(hipMalloc(it->second.p, n * 4));
-        c->owned.push_back(*it->second.p);
-    }
-    const bool is_matrix = k.size() > 7 && k.compare(k.size() - 7, 7, ".weight") == 0 && (ndim >= 2) &&
-                           k.find("position_embedding") == std::string::npos;     // GEMM operands only, not lookup tables
-    if (c->fast && is_matrix) {          // Linear / patch-conv weights: fp16 copy for the MFMA path, fp32 copy holds the same rounded values
-        std::vector<_Float16> hh(n);
-        for (size_t i = 0; i < n; ++i) { hh[i] = (_Float16)h[i]; h[i] = (float)hh[i]; }
-        _Float16* dh = nullptr;
-        HIPCHK(hipMalloc((void**)&dh, n * 2));
-        c->owned.push_back(dh);
-        HIPCHK(hipMemcpy(dh, hh.data(), n * 2, hipMemcpyHostToDevice));
-        c->half_of[*it->second.p] = dh;
-    }
-    HIPCHK(hipMemcpy(*it->second.p, h.data(), n * 4, hipMemcpyHostToDevice));
-    it->second.loaded = true;
-    c->geglu_perm_valid = false;          // any reload invalidates the permuted feed-forward operands
-    return ER_OK;
+    const int rc = weights_load(c->w, c->own_stream, "er_dit_load_tensor", k, data, dtype, ndim, shape, on_device);
+    if (rc != 1) c->geglu_perm_valid = false;          // any reload invalidates the permuted feed-forward operands
+    return rc;
 }
 
 extern "C" int er_dit_finalize_weights(er_dit_ctx* c) {
     if (!c) return fail(ER_ERR_INVALID, "null ctx");
-    for (auto& kv : c->slots)
-        if (!kv.second.loaded) return fail(ER_ERR_MISSING, "tensor '%s' was never loaded", kv.first.c_str());
-    for (auto& kv : c->pe_need)
-        if (!kv.second) return fail(ER_ERR_MISSING, "tensor '%s' was never loaded (a point encoder is attached)", kv.first.c_str());
-    return ER_OK;
+    return weights_finalize(c->w);
 }
 
 extern "C" int er_dit_attach_point_encoder(er_dit_ctx* c, int point_hidden_dim, int point_num_heads, int point_freq_dim) {
@@ -236,7 +174,7 @@ extern "C" int er_dit_attach_point_encoder(er_dit_ctx* c, int point_hidden_dim, 
     PointEnc& p = c->pe;
     p.PH = point_hidden_dim; p.heads = point_num_heads; p.freq = point_freq_dim;
     p.Lq = c->cfg.latent_size; p.LD = c->cfg.latent_dim; p.eps = 1e-5f;
-    pe_register_keys(c->pe_need);
+    ERCHK(pe_attach(c->w, p, ER_PE_EMBED, "er_dit_attach_point_encoder", "point_encoder."));
     c->has_pe = true;
     return ER_OK;
 }
@@ -246,28 +184,13 @@ extern "C" int er_dit_point_latent(er_dit_ctx* c, const float* points, int B, in
     if (!c->has_pe) return fail(ER_ERR_UNSUPPORTED, "er_dit_point_latent: no point encoder attached (er_dit_attach_point_encoder)");
     ERCHK(er_dit_finalize_weights(c));
     HIPCHK(hipSetDevice(c->device));
-    hipStream_t st = stream ? (hipStream_t)stream : c->own_stream;
-    const size_t per = (size_t)c->pe.Lq * c->pe.LD;
-    if ((long long)B * (long long)per > 0x7fffffffLL) return fail(ER_ERR_CAPACITY, "er_dit_point_latent: batch %d too large", B);
-    constexpr int ENC_CHUNK = 32;        // as er_point_latent
-    for (int b0 = 0; b0 < B; b0 += ENC_CHUNK) {
-        const int nb = std::min(ENC_CHUNK, B - b0);
-        ERCHK(point_latent_chunk(c->pe, points + (size_t)b0 * n_points * 3, nb, n_points, st));
-        HIPCHK(hipMemcpyAsync(latent_out + (size_t)b0 * per, c->pe.lat.p, (size_t)nb * per * 4, hipMemcpyDeviceToDevice, st));
-    }
-    return ER_OK;
+    return pe_latent(c->pe, points, B, n_points, latent_out, stream ? (hipStream_t)stream : c->own_stream, "er_dit_point_latent");
 }
 
 extern "C" int er_dit_set_point_encoder_mode(er_dit_ctx* c, int mode) {
     if (!c) return fail(ER_ERR_INVALID, "null ctx");
-    if (mode != ER_PE_EMBED && mode != ER_PE_DOWNSAMPLE)
-        return fail(ER_ERR_INVALID, "er_dit_set_point_encoder_mode: %d is neither ER_PE_EMBED nor ER_PE_DOWNSAMPLE", mode);
     if (!c->has_pe) return fail(ER_ERR_UNSUPPORTED, "er_dit_set_point_encoder_mode: no point encoder attached (er_dit_attach_point_encoder)");
-    for (auto& kv : c->pe_need)
-        if (kv.second) return fail(ER_ERR_INVALID, "er_dit_set_point_encoder_mode: call it before the first point_encoder.* tensor");
-    c->pe.mode = mode;
-    pe_register_keys(c->pe_need, mode);
-    return ER_OK;
+    return pe_attach(c->w, c->pe, mode, "er_dit_set_point_encoder_mode", "point_encoder.");
 }
 
 extern "C" int er_dit_set_prediction_type(er_dit_ctx* c, int pred_type) {
@@ -328,8 +251,8 @@ static hipError_t dlin(er_dit_ctx* c, const float* A, int lda, const float* W, c
     g.A = A; g.B = W; g.C = C; g.bias = bias; g.resid = resid; g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = K; g.ldc = ldc; g.ldr = ldr;
     g.gate = gate; g.gate_rows = gate_rows; g.gate_bstride = N;
     if (c->fast && K % 32 == 0) {
-        auto it = c->half_of.find(W);
-        if (it != c->half_of.end()) {
+        auto it = c->w.half_of.find(W);
+        if (it != c->w.half_of.end()) {
             g.B = reinterpret_cast<const float*>(it->second);
             return launch_gemm_f16(g, st);
         }
@@ -421,13 +344,13 @@ static int dit_build_geglu_perm(er_dit_ctx* c, hipStream_t st) {
     if (c->geglu_perm_valid) return 0;
     const int C = c->cfg.hidden_dim, F = 4 * C;
     for (auto& L : c->layers) {
-        auto it = c->half_of.find(L.ff0_w);
-        if (it == c->half_of.end()) return fail(ER_ERR_INVALID, "dit: no fp16 copy of ff.net.0.proj");
+        auto it = c->w.half_of.find(L.ff0_w);
+        if (it == c->w.half_of.end()) return fail(ER_ERR_INVALID, "dit: no fp16 copy of ff.net.0.proj");
         if (!L.ff0_p16) {
             HIPCHK(hipMalloc((void**)&L.ff0_p16, (size_t)2 * F * C * sizeof(_Float16)));
-            c->owned.push_back(L.ff0_p16);
+            c->w.owned.push_back(L.ff0_p16);
             HIPCHK(hipMalloc((void**)&L.ff0_bp, (size_t)2 * F * sizeof(float)));
-            c->owned.push_back(L.ff0_bp);
+            c->w.owned.push_back(L.ff0_bp);
         }
         hipLaunchKernelGGL(geglu_permute_kernel, dim3(2 * F), dim3(ER_WG), 0, st, it->second, L.ff0_b, L.ff0_p16, L.ff0_bp, F, C);
         HIPRET(hipGetLastError());
@@ -447,8 +370,8 @@ static hipError_t dlin16(er_dit_ctx* c, const _Float16* A16, int lda, const floa
     g.gate = gate; g.gate_rows = gate_rows; g.gate_bstride = N;
     g.c16 = c16; g.ldc16 = N;
     if (vt16) { g.vt16 = vt16; g.vt_col0 = 2 * (N / 3); g.vt_rows = vt_rows; g.vt_ld = vt_rows; }
-    auto it = c->half_of.find(W);
-    if (it == c->half_of.end()) return hipErrorInvalidValue;
+    auto it = c->w.half_of.find(W);
+    if (it == c->w.half_of.end()) return hipErrorInvalidValue;
     g.B = reinterpret_cast<const float*>(it->second);
     return launch_gemm_hh(g, st);
 }
@@ -529,7 +452,7 @@ static int dit_forward_impl(er_dit_ctx* c, const float* xin, int B, int M, float
         std::vector<const float*> hp;
         for (auto& L : c->layers) hp.push_back(L.sst);
         HIPCHK(hipMalloc((void**)&c->sst_ptrs, hp.size() * sizeof(float*)));
-        c->owned.push_back((void*)c->sst_ptrs);
+        c->w.owned.push_back((void*)c->sst_ptrs);
         HIPCHK(hipMemcpy((void*)c->sst_ptrs, hp.data(), hp.size() * sizeof(float*), hipMemcpyHostToDevice));
     }
     // fp16 activations for the LDS-DMA GEMM (all K of this path are multiples of 64 except none: C = 1024, 4C = 4096)

@@ -1,0 +1,127 @@
+// Checkpoint weights of a context (er_ctx, er_dit_ctx): every state_dict key is registered once, with where and how it is
+// stored, and one loader serves them all.  Included by er_api.hip after Buf / ensure / fail / HIPCHK.
+#pragma once
+
+struct WeightEntry {
+    float** dst = nullptr;        // the fp32 block
+    size_t n = 0;                 // elements of the checkpoint tensor
+    size_t total = 0, off = 0;    // elements of the block; the tensor lands at [off, ...)
+    size_t cols = 0, pitch = 0;   // rows of `cols` values stored `pitch` apart (pitch > cols: zero-padded rows)
+    bool f16 = false;             // fp16 mode: keep an fp16 copy (WeightTable::half_of); the fp32 block holds the same rounded values
+    _Float16** dst16 = nullptr;   // ... and publish it here too (nullable)
+    bool loaded = false;
+
+    // [off, off + n) of a fused block of `total` elements (q / k / v of one layer)
+    WeightEntry& slice(size_t total_, size_t off_) { total = total_; off = off_; return *this; }
+    // rows of kin values stored zero-padded to kpad columns, so that a GEMM's K is a whole number of tiles
+    WeightEntry& pad(size_t kin, size_t kpad) { cols = kin; pitch = kpad; total = n / kin * kpad; return *this; }
+    WeightEntry& half(_Float16** p = nullptr) { f16 = true; dst16 = p; return *this; }
+};
+
+struct WeightTable {
+    std::map<std::string, WeightEntry> keys;
+    std::map<const float*, _Float16*> half_of;   // fp32 block -> its fp16 copy (fp16 mode, entries with half())
+    std::vector<void*> owned;                    // every hipMalloc'd weight block (derived copies included)
+    Buf stage;                                   // upload of one host tensor: grow-only, freed by weights_finalize
+    bool fp16 = false;
+
+    // a block of its own; (re)registering a key resets it to "not loaded"
+    WeightEntry& add(const std::string& key, float** dst, size_t n) {
+        WeightEntry& e = keys[key] = WeightEntry{};
+        e.dst = dst; e.n = e.total = e.cols = e.pitch = n;
+        return e;
+    }
+    // name.weight [out][in] and name.bias [out] (in = 1: a LayerNorm's two vectors); returns the weight's entry
+    WeightEntry& lin(const std::string& name, float** w, float** b, size_t out, size_t in) {
+        add(name + ".bias", b, out);
+        return add(name + ".weight", w, out * in);
+    }
+};
+
+// fp32 / fp16 / bf16 source element i as fp32 (exact)
+__device__ __forceinline__ float raw_to_f32(const void* src, int dtype, size_t i) {
+    if (dtype == ER_F32) return reinterpret_cast<const float*>(src)[i];
+    if (dtype == ER_F16) return (float)reinterpret_cast<const _Float16*>(src)[i];
+    const unsigned int u = (unsigned int)reinterpret_cast<const unsigned short*>(src)[i] << 16;      // bf16
+    return __uint_as_float(u);
+}
+// n source elements into rows of `cols` values `pitch` apart; with dst16, the fp16 copy (round to nearest even) and fp32 values
+// that are the same rounded numbers
+__global__ void cvt_weights_kernel(const void* src, int dtype, float* dst32, _Float16* dst16, size_t n, size_t cols, size_t pitch) {
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        const size_t d = cols == pitch ? i : i / cols * pitch + i % cols;
+        float v = raw_to_f32(src, dtype, i);
+        if (dst16) {
+            const _Float16 hv = (_Float16)v;
+            dst16[d] = hv;
+            v = (float)hv;
+        }
+        dst32[d] = v;
+    }
+}
+
+template <typename T>
+static int weights_alloc(WeightTable& t, T** p, size_t n) {   // once per block, zeroed
+    if (*p) return 0;
+    HIPCHK(hipMalloc((void**)p, n * sizeof(T)));
+    t.owned.push_back(*p);
+    HIPCHK(hipMemset(*p, 0, n * sizeof(T)));
+    return 0;
+}
+
+// One checkpoint tensor (fp32 / fp16 / bf16, host or device memory) into its block, converted on the device.  Returns 1 for a key the
+// table does not hold; the copy is complete when this returns (the caller's buffer and the staging block may be reused).
+static int weights_load(WeightTable& t, hipStream_t st, const char* who, const std::string& key, const void* data, int dtype,
+                        int ndim, const int64_t* shape, int on_device) {
+    if (!data || !shape || ndim < 1 || ndim > 4) return fail(ER_ERR_INVALID, "%s: bad argument", who);
+    if (dtype != ER_F32 && dtype != ER_F16 && dtype != ER_BF16) return fail(ER_ERR_INVALID, "%s: dtype %d", who, dtype);
+    auto it = t.keys.find(key);
+    if (it == t.keys.end()) return 1;     // strict=False: unknown keys are ignored
+    WeightEntry& e = it->second;
+    size_t n = 1;
+    for (int i = 0; i < ndim; ++i) n *= (size_t)shape[i];
+    if (n != e.n) return fail(ER_ERR_INVALID, "%s(%s): %zu elements, expected %zu", who, key.c_str(), n, e.n);
+    const void* src = data;
+    if (!on_device) {
+        const size_t bytes = n * (dtype == ER_F32 ? 4 : 2);
+        ERCHK(ensure(t.stage, (bytes + 3) / 4));
+        HIPCHK(hipMemcpy(t.stage.p, data, bytes, hipMemcpyHostToDevice));
+        src = t.stage.p;
+    }
+    ERCHK(weights_alloc(t, e.dst, e.total));
+    _Float16* h = nullptr;
+    if (t.fp16 && e.f16) {
+        _Float16*& hb = t.half_of[*e.dst];
+        ERCHK(weights_alloc(t, &hb, e.total));
+        if (e.dst16) *e.dst16 = hb;
+        h = hb + e.off;
+    }
+    const unsigned grid = (unsigned)std::min<size_t>((n + 255) / 256, 4096);
+    hipLaunchKernelGGL(cvt_weights_kernel, dim3(grid), dim3(256), 0, st, src, dtype, *e.dst + e.off, h, n, e.cols, e.pitch);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(st));
+    e.loaded = true;
+    return 0;
+}
+
+// the first registered key that was never loaded, or null
+static const char* weights_missing(const WeightTable& t) {
+    for (auto& kv : t.keys)
+        if (!kv.second.loaded) return kv.first.c_str();
+    return nullptr;
+}
+
+static void weights_free(WeightTable& t) {
+    for (void* p : t.owned) hipFree(p);
+    if (t.stage.p) hipFree(t.stage.p);
+}
+
+static int weights_finalize(WeightTable& t) {
+    if (const char* k = weights_missing(t)) return fail(ER_ERR_MISSING, "tensor '%s' was never loaded", k);
+    if (t.stage.p) {                      // checkpoint complete: the upload staging block (up to one tensor) is not needed any more
+        hipFree(t.stage.p);
+        t.stage.p = nullptr;
+        t.stage.n = 0;
+    }
+    return 0;
+}

@@ -191,12 +191,7 @@ class MDiT:
     def _load_now(self, sd, strict):
         unexpected = []
         for key, t in sd.items():
-            t = t.detach().float().contiguous() if t.dtype not in (torch.float32, torch.float16, torch.bfloat16) else t.detach().contiguous()
-            dt = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}[t.dtype]
-            shape = (C.c_int64 * max(1, t.dim()))(*(list(t.shape) or [1]))
-            rc = native.check(self.lib.er_dit_load_tensor(self._ctx_h, key.encode(), native.ptr(t), dt, max(1, t.dim()), shape,
-                                                          1 if t.is_cuda else 0), f"er_dit_load_tensor({key})")
-            if rc == 1:
+            if native.load_tensor(self.lib.er_dit_load_tensor, self._ctx_h, key, t) == 1:
                 unexpected.append(key)
         rc = self.lib.er_dit_finalize_weights(self._ctx_h)
         missing = [self.lib.er_last_error().decode()] if rc < 0 else []

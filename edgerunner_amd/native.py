@@ -174,6 +174,19 @@ def ptr(t) -> C.c_void_p:
     return C.c_void_p(t.data_ptr())
 
 
+def load_tensor(fn, ctx, key: str, t) -> int:
+    """One checkpoint tensor through ``fn`` (er_load_tensor / er_dit_load_tensor): fp32 / fp16 / bf16 as they are, any other dtype
+    as fp32, from host or device memory.  Returns 1 for a key the context does not hold."""
+    import torch
+    dtypes = {torch.float32: ER_F32, torch.float16: ER_F16, torch.bfloat16: ER_BF16}
+    if t.dtype not in dtypes:
+        t = t.float()
+    t = t.detach().contiguous()
+    shape = (C.c_int64 * max(1, t.dim()))(*(list(t.shape) or [1]))
+    return check(fn(ctx, key.encode(), ptr(t), dtypes[t.dtype], max(1, t.dim()), shape, 1 if t.is_cuda else 0),
+                 f"{fn.__name__}({key})")
+
+
 def stream_ptr(stream) -> C.c_void_p:
     """hipStream_t of a torch.cuda.Stream (or the current stream when None)."""
     import torch

@@ -125,14 +125,7 @@ class NativeShapeOPT:
         return self._finish_load(strict, unexpected)
 
     def _load_one(self, key, t, unexpected):
-        if t.dtype not in _DT:
-            t = t.float()
-        t = t.detach().contiguous()
-        shape = (C.c_int64 * max(1, t.dim()))(*(list(t.shape) or [1]))
-        rc = native.check(self.lib.er_load_tensor(self._ctx, key.encode(), native.ptr(t), _DT[t.dtype],
-                                                  max(1, t.dim()), shape, 1 if t.is_cuda else 0),
-                          f"er_load_tensor({key})")
-        if rc == 1:
+        if native.load_tensor(self.lib.er_load_tensor, self._ctx, key, t) == 1:
             unexpected.append(key)
 
     def _finish_load(self, strict, unexpected):
