@@ -11,7 +11,9 @@
 #include <cstdlib>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "er_common.h"
@@ -67,21 +69,7 @@ struct LayerW {
     float *w1 = nullptr, *b1 = nullptr, *w2 = nullptr, *b2 = nullptr, *ln2w = nullptr, *ln2b = nullptr;
 };
 
-struct Buf {   // grow-only device scratch
-    float* p = nullptr;
-    size_t n = 0;
-};
-
-static int ensure(Buf& b, size_t n) {
-    if (b.n >= n) return 0;
-    if (b.p) hipFree(b.p);
-    b.p = nullptr;
-    b.n = 0;
-    HIPCHK(hipMalloc(&b.p, n * sizeof(float)));
-    b.n = n;
-    return 0;
-}
-
+#include "er_devbuf.h"
 #include "er_weights.h"
 
 // PointEncoderEmbed (core/transformer/point.py:172-206) or, with mode ER_PE_DOWNSAMPLE, PointEncoder (:129-169): weights, shape and
@@ -97,8 +85,40 @@ struct PointEnc {
           *ca_o_w = nullptr, *ca_o_b = nullptr;
     float *ff0_w = nullptr, *ff0_b = nullptr, *ff2_w = nullptr, *ff2_b = nullptr, *lin_w = nullptr, *lin_b = nullptr;
     int kpad = 0;            // padded input width of point_embed.mlp (51 -> 64), set by pe_attach
-    Buf a0, x, k, v, qln, q, sc, att, l, ln, u, g, lat;   // scratch of point_latent_chunk; lat = the latent mean [nb][Lq][LD]
-    Buf q0, fidx, fdist;     // downsample mode: gathered query rows [nb][Lq][PH], FPS indices [nb][Lq] (int32), FPS distances (large N)
+    DevBuf<float> a0, x, k, v, qln, q, sc, att, l, ln, u, g, lat;   // scratch of point_latent_chunk; lat = the latent mean [nb][Lq][LD]
+    DevBuf<float> q0, fdist;                              // downsample mode: gathered query rows [nb][Lq][PH], FPS distances (large N)
+    DevBuf<int32_t> fidx;                                 // ... and the FPS indices [nb][Lq]
+};
+
+// The generation state of b rows is one block of ints: seven per-row arrays, then the two scalars.
+static size_t gen_state_ints(size_t b) { return 7 * b + 8; }
+static GenState gen_state_carve(int* sb, size_t b) {
+    GenState s{};
+    s.tok = sb; s.pos = sb + b; s.counter = sb + 2 * b; s.ngen = sb + 3 * b; s.unfinished = sb + 4 * b;
+    s.eos_step = sb + 5 * b; s.base_pos = sb + 6 * b; s.n_unfinished = sb + 7 * b; s.error = sb + 7 * b + 1;
+    return s;
+}
+
+// Everything er_kv_reserve allocates for one (batch, Lcap).  It lives and dies as a whole: a new shape replaces the object, a reserve
+// that fails half way never installs its own, er_destroy drops it - and the captured step goes with the buffers it points into.
+struct KvMem {
+    DevBuf<char> kc, vc;          // KV cache [layers][B][H][Lcap][D], fp32 or fp16 (fast)
+    DevBuf<float> ypre, hbuf, ypre1, h1buf, qbuf, abuf, fbuf, logits;   // decode workspace ([B][...])
+    DevBuf<float> part, part_ml;  // attention partials; version 3: {m, l} of the partials
+    DevBuf<float> skpart;         // split-K partials of the batched projections (gemv_mfma_groups checks launches against skpart.n)
+    // fast-mode batches on the matrix cores: activations in the tiled hi | lo operand layout (k_gemv.h xt_entry), one image per producer
+    DevBuf<char> xt_h, xt_att, xt_f;     // LayerNorm rows (qkv / fc1 input), attention output, fc1 output
+    DevBuf<int> state_block;      // backing store of st
+    GenState st{};
+    DevBuf<DecodeParamsDev> d_params;
+    DevBuf<int> d_ids_tmp;
+    DevBuf<unsigned int> d_row_stream;   // [B] Philox stream id per row (identity until er_set_row_streams)
+    DevBuf<long long> d_out_ids;  // [B][Lcap] generated ids (graph writes here; copied to the caller at the end)
+    hipGraphExec_t step_exec = nullptr;  // hipGraph of one step
+    KvMem() = default;
+    KvMem(const KvMem&) = delete;
+    KvMem& operator=(const KvMem&) = delete;
+    ~KvMem() { if (step_exec) hipGraphExecDestroy(step_exec); }
 };
 
 struct er_ctx {
@@ -114,33 +134,18 @@ struct er_ctx {
     float *proj_w = nullptr, *proj_b = nullptr, *normc_w = nullptr, *normc_b = nullptr;
     PointEnc pe;             // point encoder (cond_mode POINT)
     WeightTable w;           // every checkpoint key (register_weights)
-    // KV cache
+    // KV cache + decode workspace of the reserved shape
     int B = 0, Lcap = 0, S_splits = 0;
-    void *kc = nullptr, *vc = nullptr;        // [layers][B][H][Lcap][D], fp32 or fp16 (fast)
+    std::unique_ptr<KvMem> kv = std::make_unique<KvMem>();   // never null; er_kv_reserve swaps in a new one
     int kv_esz = 4;
     long long kv_bstride = 0, kv_lstride = 0;
-    // decode workspace ([B][...])
-    float *ypre = nullptr, *hbuf = nullptr, *ypre1 = nullptr, *h1buf = nullptr, *qbuf = nullptr, *abuf = nullptr,
-          *fbuf = nullptr, *logits = nullptr, *part = nullptr;
-    int* state_block = nullptr;   // backing store of GenState
-    GenState st{};
-    DecodeParamsDev* d_params = nullptr;
-    int* d_ids_tmp = nullptr;
-    unsigned int* d_row_stream = nullptr;   // [B] Philox stream id per row (identity until er_set_row_streams)
-    long long* d_out_ids = nullptr;   // [B][Lcap] generated ids (graph writes here; copied to the caller at the end)
     int* h_pinned = nullptr;      // small pinned host buffer
     int base_pos = 0;             // prefill length of the current generation
     bool have_hidden = false;     // ypre holds a valid last-position state
-    // hipGraph of one step
-    hipGraphExec_t step_exec = nullptr;
     bool use_graph = true;
     bool batched = false;     // B > 4 (or ER_FORCE_BATCHED=1): weights streamed once per pass of 32 rows (matrix cores)
     bool batched_valu = false;   // ER_BATCHED_VALU=1: the older VALU kernels (one pass per 16 rows), kept for A/B runs
-    float* skpart = nullptr;  // split-K partials of the batched projections
-    size_t skpart_floats = 0; // ... and how many floats the block holds (checked by gemv_mfma_groups)
-    // fast-mode batches on the matrix cores: activations in the tiled hi | lo operand layout (k_gemv.h xt_entry), one image per producer
-    void *xt_h = nullptr, *xt_att = nullptr, *xt_f = nullptr;     // LayerNorm rows (qkv / fc1 input), attention output, fc1 output
-    bool xt = false;          // ER_XT=0 keeps the row-major fp32 inputs (A/B + parity matrix)
+    bool xt = false;          // fast-mode batches read the tiled activation images (KvMem::xt_*); ER_XT=0 keeps the row-major fp32 inputs (A/B + parity matrix)
     bool tiled_valid = false; // LayerW::*_t match the loaded weights
     // waves per workgroup of the qkv / fc1 GEMVs (env ER_NW_QKV: 4, 6 or 9; ER_NW_FC1: 4 or 12).  Exact mode: qkv 6 waves x 1 row
     // = 768 workgroups (3 per CU), fc1 4 waves x 2 rows = 768; fast mode: one fat workgroup per CU (9 / 12 waves x 2 rows).  The other
@@ -155,24 +160,20 @@ struct er_ctx {
     int decode_v = 3;         // single-row decode: 3 = balanced-chunk attention + merge fused into out_proj (one row, D = 96, 16 heads, Lcap <= 8192); ER_DECODE_V=2 = fixed 128-key chunks + merge kernel (also the fallback when the cache does not qualify)
     bool v3 = false;          // decode_v == 3 and the reserved cache qualifies
     int nch3 = 0;             // chunks per head of the balanced attention kernel
-    float* part_ml = nullptr; // version 3: {m, l} of the partials
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     float last_decode_ms = 0.f;
-    // scratch for prefill / encoder
-    Buf p_hi, p_lo;           // fast-mode prefill: hi / lo fp16 halves of the activation a Linear is about to read (LDS-DMA GEMM, split form)
-    Buf p_h, p_q, p_a, p_y, p_f, p_sc, p_qkv, p_ap, p_aml, e_tmp, e_ids;
-    Buf s_lg;                 // er_score: logits of every position when the caller passes no buffer for them
+    // scratch for prefill / encoder: grow-only, freed with the context
+    DevBuf<_Float16> p_hi, p_lo;   // fast-mode prefill: hi / lo fp16 halves of the activation a Linear is about to read (LDS-DMA GEMM, split form)
+    DevBuf<float> p_h, p_q, p_a, p_y, p_f, p_qkv, p_ap, p_aml, e_tmp;
+    DevBuf<int> e_ids;             // er_embed_tokens: the ids on the device
+    DevBuf<float> s_lg;            // er_score: logits of every position when the caller passes no buffer for them
 };
 
 constexpr int ER_MAX_BATCH = 1023;   // h_pinned holds B ints + one flag
 constexpr int NBM = 32;   // batch rows per pass of the matrix-core decode projections (k_gemv_mfma.h)
 
-static void pe_free(PointEnc& p) {
-    for (Buf* b : {&p.a0, &p.x, &p.k, &p.v, &p.qln, &p.q, &p.sc, &p.att, &p.l, &p.ln, &p.u, &p.g, &p.lat, &p.q0, &p.fidx, &p.fdist})
-        if (b->p) { hipFree(b->p); b->p = nullptr; b->n = 0; }
-}
-
-static hipStream_t pick(er_ctx* c, void* s) { return s ? (hipStream_t)s : c->own_stream; }
+template <typename Ctx>      // er_ctx, er_dit_ctx
+static hipStream_t pick(Ctx* c, void* s) { return s ? (hipStream_t)s : c->own_stream; }
 
 extern "C" int er_abi_version(void) { return ER_ABI_VERSION; }
 extern "C" const char* er_last_error(void) { return g_err; }
@@ -291,41 +292,16 @@ extern "C" int er_create(const er_config* cfg, int device, er_ctx** out) {
 }
 
 static void free_kv(er_ctx* c) {
-    for (void* p : {c->kc, c->vc, (void*)c->ypre, (void*)c->hbuf, (void*)c->ypre1, (void*)c->h1buf, (void*)c->qbuf,
-                    (void*)c->abuf, (void*)c->fbuf, (void*)c->logits, (void*)c->part})
-        if (p) hipFree(p);
-    c->kc = c->vc = c->ypre = c->hbuf = c->ypre1 = c->h1buf = c->qbuf = c->abuf = c->fbuf = c->logits = c->part = nullptr;
-    if (c->skpart) hipFree(c->skpart);
-    c->skpart = nullptr;
-    for (void** p : {&c->xt_h, &c->xt_att, &c->xt_f}) {
-        if (*p) hipFree(*p);
-        *p = nullptr;
-    }
-    if (c->part_ml) hipFree(c->part_ml);
-    c->part_ml = nullptr;
-    if (c->state_block) hipFree(c->state_block);
-    if (c->d_params) hipFree(c->d_params);
-    if (c->d_ids_tmp) hipFree(c->d_ids_tmp);
-    if (c->d_row_stream) hipFree(c->d_row_stream);
-    c->d_row_stream = nullptr;
-    if (c->d_out_ids) hipFree(c->d_out_ids);
-    c->d_out_ids = nullptr;
-    c->state_block = nullptr; c->d_params = nullptr; c->d_ids_tmp = nullptr;
-    if (c->step_exec) hipGraphExecDestroy(c->step_exec);
-    c->step_exec = nullptr;
+    c->kv = std::make_unique<KvMem>();
     c->B = 0; c->Lcap = 0;
+    c->have_hidden = false;
 }
 
+// The context's buffers, weight blocks and captured step are members: deleting the context frees them, once the device is idle.
 extern "C" int er_destroy(er_ctx* c) {
     if (!c) return ER_OK;
     hipSetDevice(c->device);
     hipDeviceSynchronize();
-    free_kv(c);
-    weights_free(c->w);
-    for (Buf* b : {&c->p_hi, &c->p_lo, &c->p_h, &c->p_q, &c->p_a, &c->p_y, &c->p_f, &c->p_sc, &c->p_qkv, &c->p_ap, &c->p_aml,
-                   &c->e_tmp, &c->e_ids, &c->s_lg})
-        if (b->p) hipFree(b->p);
-    pe_free(c->pe);
     if (c->ev0) hipEventDestroy(c->ev0);
     if (c->ev1) hipEventDestroy(c->ev1);
     if (c->h_pinned) hipHostFree(c->h_pinned);
@@ -354,8 +330,9 @@ extern "C" int er_finalize_weights(er_ctx* c) {
 template <typename WT>
 static int make_tiled(er_ctx* c, const void* src, void** dst, int N, int K) {
     if (!*dst) {
-        HIPCHK(hipMalloc(dst, tiled_weight_bytes<WT>(N, K)));
-        c->w.owned.push_back(*dst);
+        char* blk = nullptr;
+        ERCHK(c->w.alloc(&blk, tiled_weight_bytes<WT>(N, K)));
+        *dst = blk;
     }
     hipLaunchKernelGGL((tile_weights_kernel<WT>), dim3(2048), dim3(ER_WG), 0, c->own_stream, reinterpret_cast<const WT*>(src),
                        reinterpret_cast<f32x4*>(*dst), N, K);
@@ -430,7 +407,7 @@ extern "C" int er_plan_gemm_tile(int m, int n, int batch) {
 }
 
 // ------------------------------------------------------------------------------------ KV cache / workspace
-static int kv_alloc(er_ctx* c, int batch, int Lcap);
+static int kv_alloc(er_ctx* c, KvMem& m, int batch, int Lcap);
 
 extern "C" int er_kv_reserve(er_ctx* c, int batch, int max_len) {
     if (!c || batch <= 0 || max_len <= 0) return fail(ER_ERR_INVALID, "er_kv_reserve: bad argument");
@@ -442,52 +419,46 @@ extern "C" int er_kv_reserve(er_ctx* c, int batch, int max_len) {
     const int Lcap = (max_len + 31) / 32 * 32;
     if (c->B == batch && c->Lcap == Lcap) return ER_OK;
     HIPCHK(hipDeviceSynchronize());
-    free_kv(c);
-    const int rc_alloc = kv_alloc(c, batch, Lcap);
-    if (rc_alloc < 0) { free_kv(c); return rc_alloc; }     // a failed hipMalloc half way leaves nothing behind
+    free_kv(c);                                  // first: the old shape's memory makes room for the new one
+    auto m = std::make_unique<KvMem>();
+    ERCHK(kv_alloc(c, *m, batch, Lcap));         // a failed hipMalloc half way leaves nothing behind: m dies here
+    c->kv = std::move(m);
+    c->B = batch;
+    c->Lcap = Lcap;
     return ER_OK;
 }
 
-static int kv_alloc(er_ctx* c, int batch, int Lcap) {
+// the buffers of the new shape into m, and the decode plan that goes with it into c
+static int kv_alloc(er_ctx* c, KvMem& m, int batch, int Lcap) {
     const er_config& g = c->cfg;
     const int H = g.num_heads, D = c->D, hid = g.hidden_dim;
     c->kv_bstride = (long long)H * Lcap * D;
     c->kv_lstride = c->kv_bstride * batch;
-    const size_t kv_elems = (size_t)c->kv_lstride * g.num_layers;
-    HIPCHK(hipMalloc(&c->kc, kv_elems * c->kv_esz));
-    HIPCHK(hipMalloc(&c->vc, kv_elems * c->kv_esz));
+    const size_t kv_bytes = (size_t)c->kv_lstride * g.num_layers * c->kv_esz;
+    ERCHK(m.kc.ensure(kv_bytes));
+    ERCHK(m.vc.ensure(kv_bytes));
     // decode attention: one workgroup per (row, head, chunk of 32*steps keys)
     const int S = attn_num_chunks(Lcap, attn_chunk(ATTN_STEPS_DEFAULT, c->fast));
     c->S_splits = S;
     const size_t b = (size_t)batch;
-    HIPCHK(hipMalloc(&c->ypre, b * hid * 4));
-    HIPCHK(hipMalloc(&c->hbuf, b * hid * 4));
-    HIPCHK(hipMalloc(&c->ypre1, b * hid * 4));
-    HIPCHK(hipMalloc(&c->h1buf, b * hid * 4));
-    HIPCHK(hipMalloc(&c->qbuf, b * hid * 4));
-    HIPCHK(hipMalloc(&c->abuf, b * hid * 4));
-    HIPCHK(hipMalloc(&c->fbuf, b * g.intermediate_dim * 4));
-    HIPCHK(hipMalloc(&c->logits, b * g.vocab_size * 4));
+    for (DevBuf<float>* w : {&m.ypre, &m.hbuf, &m.ypre1, &m.h1buf, &m.qbuf, &m.abuf}) ERCHK(w->ensure(b * hid));
+    ERCHK(m.fbuf.ensure(b * g.intermediate_dim));
+    ERCHK(m.logits.ensure(b * g.vocab_size));
     c->nch3 = attn3_num_chunks(H);
-    HIPCHK(hipMalloc(&c->part, b * H * (size_t)std::max(S * (D + 2), c->nch3 * D) * 4));
-    HIPCHK(hipMalloc(&c->part_ml, b * H * (size_t)c->nch3 * 2 * 4));
-    HIPCHK(hipMalloc(&c->state_block, (7 * b + 8) * sizeof(int)));
-    int* sb = c->state_block;
-    c->st.tok = sb; c->st.pos = sb + b; c->st.counter = sb + 2 * b; c->st.ngen = sb + 3 * b;
-    c->st.unfinished = sb + 4 * b; c->st.eos_step = sb + 5 * b; c->st.base_pos = sb + 6 * b; c->st.n_unfinished = sb + 7 * b; c->st.error = sb + 7 * b + 1;
-    HIPCHK(hipMalloc(&c->d_params, sizeof(DecodeParamsDev)));
-    HIPCHK(hipMalloc(&c->d_ids_tmp, b * sizeof(int)));
-    HIPCHK(hipMalloc(&c->d_row_stream, b * sizeof(unsigned int)));
+    ERCHK(m.part.ensure(b * H * (size_t)std::max(S * (D + 2), c->nch3 * D)));
+    ERCHK(m.part_ml.ensure(b * H * (size_t)c->nch3 * 2));
+    ERCHK(m.state_block.ensure(gen_state_ints(b)));
+    m.st = gen_state_carve(m.state_block.p, b);
+    ERCHK(m.d_params.ensure(1));
+    ERCHK(m.d_ids_tmp.ensure(b));
+    ERCHK(m.d_row_stream.ensure(b));
     {
         std::vector<unsigned int> ident(b);
         for (size_t i = 0; i < b; ++i) ident[i] = (unsigned int)i;
-        HIPCHK(hipMemcpy(c->d_row_stream, ident.data(), b * sizeof(unsigned int), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(m.d_row_stream.p, ident.data(), b * sizeof(unsigned int), hipMemcpyHostToDevice));
     }
-    c->st.row_stream = c->d_row_stream;
-    HIPCHK(hipMalloc(&c->d_out_ids, b * (size_t)Lcap * sizeof(long long)));
-    c->B = batch;
-    c->Lcap = Lcap;
-    c->have_hidden = false;
+    m.st.row_stream = m.d_row_stream.p;
+    ERCHK(m.d_out_ids.ensure(b * (size_t)Lcap));
     const char* fb = getenv("ER_FORCE_BATCHED");
     er_decode_plan plan{};
     plan_decode(c->decode_v, c->attn_v_batched, fb && fb[0] == '1', batch, H, D, hid, Lcap, &plan);
@@ -503,17 +474,16 @@ static int kv_alloc(er_ctx* c, int batch, int Lcap) {
     c->xt = c->fast && c->batched && !c->batched_valu && !(xe && xe[0] == '0');
     // split-K partials of the batched projections.  A finish launched right behind its producer re-uses ONE [4][32][N] block; only the
     // tiled path defers finishes to a later launch (prep_rows_kernel, sk_part) and keeps a [16][32][hidden] block per group of 32 rows
-    c->skpart_floats = c->xt ? ((b + NBM - 1) / NBM) * (size_t)16 * NBM * (size_t)hid : (size_t)4 * NBM * (size_t)std::max(hid, g.vocab_size);
-    HIPCHK(hipMalloc(&c->skpart, c->skpart_floats * 4));
+    ERCHK(m.skpart.ensure(c->xt ? ((b + NBM - 1) / NBM) * (size_t)16 * NBM * (size_t)hid : (size_t)4 * NBM * (size_t)std::max(hid, g.vocab_size)));
     if (c->xt) {
         const size_t groups = (size_t)(batch + NBM - 1) / NBM;
         const size_t b_h = groups * (size_t)hid * 128, b_f = groups * (size_t)g.intermediate_dim * 128;
-        HIPCHK(hipMalloc(&c->xt_h, b_h));
-        HIPCHK(hipMalloc(&c->xt_att, b_h));
-        HIPCHK(hipMalloc(&c->xt_f, b_f));
-        HIPCHK(hipMemset(c->xt_h, 0, b_h));
-        HIPCHK(hipMemset(c->xt_att, 0, b_h));
-        HIPCHK(hipMemset(c->xt_f, 0, b_f));
+        ERCHK(m.xt_h.ensure(b_h));
+        ERCHK(m.xt_att.ensure(b_h));
+        ERCHK(m.xt_f.ensure(b_f));
+        HIPCHK(hipMemset(m.xt_h.p, 0, b_h));
+        HIPCHK(hipMemset(m.xt_att.p, 0, b_h));
+        HIPCHK(hipMemset(m.xt_f.p, 0, b_f));
     }
     return ER_OK;
 }
@@ -639,23 +609,23 @@ static hipError_t prep_rows(const GemvArgs& a, int B, hipStream_t st) {
 
 static AttnDecArgs attn_args(er_ctx* c, int layer) {
     AttnDecArgs a{};
-    a.q = c->qbuf;
-    a.kcache = (char*)c->kc + (long long)layer * c->kv_lstride * c->kv_esz;
-    a.vcache = (char*)c->vc + (long long)layer * c->kv_lstride * c->kv_esz;
+    a.q = c->kv->qbuf.p;
+    a.kcache = c->kv->kc.p + (long long)layer * c->kv_lstride * c->kv_esz;
+    a.vcache = c->kv->vc.p + (long long)layer * c->kv_lstride * c->kv_esz;
     a.chunk = attn_chunk(ATTN_STEPS_DEFAULT, c->fast);
-    a.pos = c->st.pos;
+    a.pos = c->kv->st.pos;
     a.fixed_len = c->prof_len;
     a.len_dev = nullptr;
-    a.part = c->part;
-    a.part_ml = c->part_ml;
-    a.out = c->abuf;
+    a.part = c->kv->part.p;
+    a.part_ml = c->kv->part_ml.p;
+    a.out = c->kv->abuf.p;
     a.H = c->cfg.num_heads;
     a.l_cap = c->Lcap;
     a.S = c->S_splits;
     a.hidden = c->cfg.hidden_dim;
     a.kv_bstride = c->kv_bstride;
     a.sqrt_d = sqrtf((float)c->D);
-    a.out_xt = (c->xt && c->stream_attn && c->B > 8) ? c->xt_att : nullptr;      // out_proj then reads the tiled image (launch_kind_t case 3)
+    a.out_xt = (c->xt && c->stream_attn && c->B > 8) ? c->kv->xt_att.p : nullptr;      // out_proj then reads the tiled image (launch_kind_t case 3)
     return a;
 }
 
@@ -679,31 +649,31 @@ static hipError_t launch_kind_t(er_ctx* c, int kind, int layer, hipStream_t st, 
         case 0: {   // qkv
             const LayerW& L = c->layers[layer];
             a.W = HALF ? (const void*)L.wqkv_h : (const void*)L.wqkv; a.bias = L.bqkv; a.N = 3 * H;
-            a.hout = c->hbuf; a.pos = c->st.pos;
-            a.q = c->qbuf;
-            a.kcache = (char*)c->kc + (long long)layer * c->kv_lstride * c->kv_esz;
-            a.vcache = (char*)c->vc + (long long)layer * c->kv_lstride * c->kv_esz;
+            a.hout = c->kv->hbuf.p; a.pos = c->kv->st.pos;
+            a.q = c->kv->qbuf.p;
+            a.kcache = c->kv->kc.p + (long long)layer * c->kv_lstride * c->kv_esz;
+            a.vcache = c->kv->vc.p + (long long)layer * c->kv_lstride * c->kv_esz;
             if (layer == 0) {
-                a.embd = c->embd; a.posemb = c->posemb; a.tok = c->st.tok;
+                a.embd = c->embd; a.posemb = c->posemb; a.tok = c->kv->st.tok;
             } else {
-                a.xin = c->ypre; a.ln_w = c->layers[layer - 1].ln2w; a.ln_b = c->layers[layer - 1].ln2b;
+                a.xin = c->kv->ypre.p; a.ln_w = c->layers[layer - 1].ln2w; a.ln_b = c->layers[layer - 1].ln2b;
             }
             if (c->batched) {
                 if constexpr (HALF) {
-                    a.xt_out = c->xt ? c->xt_h : nullptr;
+                    a.xt_out = c->xt ? c->kv->xt_h.p : nullptr;
                     if (c->xt && layer > 0) {      // the previous layer's fc2 deferred its split-K finish to this LayerNorm (case 5)
-                        a.sk_part = c->skpart; a.sk_bias = c->layers[layer - 1].b2; a.sk_resid = c->h1buf; a.sk_batch = B; a.sk_slices = 16;
+                        a.sk_part = c->kv->skpart.p; a.sk_bias = c->layers[layer - 1].b2; a.sk_resid = c->kv->h1buf.p; a.sk_batch = B; a.sk_slices = 16;
                     }
                 }
                 hipError_t e = layer == 0 ? prep_rows<PRO_EMBED>(a, B, st) : prep_rows<PRO_LN>(a, B, st);
                 a.sk_part = nullptr;
                 if (e != hipSuccess) return e;
-                a.xin = c->hbuf;
+                a.xin = c->kv->hbuf.p;
                 a.xt_out = nullptr;
                 if constexpr (HALF) {
-                    if (c->xt) { a.W = L.wqkv_t; a.xin = (const float*)c->xt_h; return gemv_mfma_groups<WT, EPI_QKV, true>(a, B, H, SkPart{c->skpart, c->skpart_floats}, st); }
+                    if (c->xt) { a.W = L.wqkv_t; a.xin = (const float*)c->kv->xt_h.p; return gemv_mfma_groups<WT, EPI_QKV, true>(a, B, H, SkPart{c->kv->skpart.p, c->kv->skpart.n}, st); }
                 }
-                if (!c->batched_valu) { a.W = L.wqkv_t; return gemv_mfma_groups<WT, EPI_QKV>(a, B, H, SkPart{c->skpart, c->skpart_floats}, st); }   // 144 tiles of 32 rows
+                if (!c->batched_valu) { a.W = L.wqkv_t; return gemv_mfma_groups<WT, EPI_QKV>(a, B, H, SkPart{c->kv->skpart.p, c->kv->skpart.n}, st); }   // 144 tiles of 32 rows
                 return gemv_batched_groups<WT, 1, 3, EPI_QKV>(a, B, H, st);   // 4608 rows = 192 workgroups x 24: one round
             }
             if (layer == 0) return gemv_nw<WT, PRO_EMBED, EPI_QKV>(c->nw_qkv, a, B, H, st);
@@ -722,60 +692,60 @@ static hipError_t launch_kind_t(er_ctx* c, int kind, int layer, hipStream_t st, 
             const LayerW& L = c->layers[layer];
             if (c->v3) {
                 OutMergeArgs m{};
-                m.W = HALF ? (const void*)L.wo_h : (const void*)L.wo; m.bias = L.bo; m.resid = c->hbuf; m.out = c->ypre1;
-                m.part_o = c->part; m.part_ml = c->part_ml; m.N = H;
+                m.W = HALF ? (const void*)L.wo_h : (const void*)L.wo; m.bias = L.bo; m.resid = c->kv->hbuf.p; m.out = c->kv->ypre1.p;
+                m.part_o = c->kv->part.p; m.part_ml = c->kv->part_ml.p; m.N = H;
                 return launch_outproj_merge<WT, 96>(m, c->nch3, st);
             }
-            a.W = HALF ? (const void*)L.wo_h : (const void*)L.wo; a.bias = L.bo; a.N = H; a.xin = c->abuf; a.out = c->ypre1; a.resid = c->hbuf;
+            a.W = HALF ? (const void*)L.wo_h : (const void*)L.wo; a.bias = L.bo; a.N = H; a.xin = c->kv->abuf.p; a.out = c->kv->ypre1.p; a.resid = c->kv->hbuf.p;
             // 48 row tiles of 32: the matrix-core kernel runs on 48 CUs only, but streams the matrix ONCE for 32 rows where the
             // VALU kernel needs a pass per 16
             if (c->batched && !c->batched_valu && B >= 5 && B <= 8) return gemv_outproj_rows8<WT>(a, B, st);
             if constexpr (HALF) {
                 // 4-wave workgroups (48 row tiles x 4 K-ranges of 384 instead of 48 x one of 1536); + bias + residual happen in fc1's
                 // LayerNorm-rows launch (case 4), which reads the four partials
-                if (c->xt && c->stream_attn && B > 8) { a.W = L.wo_t; a.xin = (const float*)c->xt_att; return gemv_mfma_groups<WT, EPI_RESID, true>(a, B, H, SkPart{c->skpart, c->skpart_floats}, st, true, true); }
+                if (c->xt && c->stream_attn && B > 8) { a.W = L.wo_t; a.xin = (const float*)c->kv->xt_att.p; return gemv_mfma_groups<WT, EPI_RESID, true>(a, B, H, SkPart{c->kv->skpart.p, c->kv->skpart.n}, st, true, true); }
             }
-            if (c->batched && !c->batched_valu) { a.W = L.wo_t; return gemv_mfma_groups<WT, EPI_RESID>(a, B, H, SkPart{c->skpart, c->skpart_floats}, st); }
+            if (c->batched && !c->batched_valu) { a.W = L.wo_t; return gemv_mfma_groups<WT, EPI_RESID>(a, B, H, SkPart{c->kv->skpart.p, c->kv->skpart.n}, st); }
             if (c->batched) return gemv_batched_groups<WT, 1, 1, EPI_RESID>(a, B, H, st);
             return gemv_groups<WT, 1, 1, PRO_NONE, EPI_RESID, 3>(a, B, H, st);     // 3 waves x 1 row: 512 workgroups = 2 per CU
         }
         case 4: {   // h1 = LN1(ypre1); f = relu(fc1 h1 + b)
             const LayerW& L = c->layers[layer];
-            a.W = HALF ? (const void*)L.w1_h : (const void*)L.w1; a.bias = L.b1; a.N = I; a.xin = c->ypre1; a.ln_w = L.ln1w; a.ln_b = L.ln1b;
-            a.hout = c->h1buf; a.out = c->fbuf;
+            a.W = HALF ? (const void*)L.w1_h : (const void*)L.w1; a.bias = L.b1; a.N = I; a.xin = c->kv->ypre1.p; a.ln_w = L.ln1w; a.ln_b = L.ln1b;
+            a.hout = c->kv->h1buf.p; a.out = c->kv->fbuf.p;
             if (c->batched) {
                 if constexpr (HALF) {
-                    a.xt_out = c->xt ? c->xt_h : nullptr;
+                    a.xt_out = c->xt ? c->kv->xt_h.p : nullptr;
                     if (c->xt && c->stream_attn && B > 8) {      // out_proj (case 3) left four K-range partials: ypre1 = ((sum) + bo) + h
-                        a.sk_part = c->skpart; a.sk_bias = L.bo; a.sk_resid = c->hbuf; a.sk_batch = B; a.sk_slices = 4;
+                        a.sk_part = c->kv->skpart.p; a.sk_bias = L.bo; a.sk_resid = c->kv->hbuf.p; a.sk_batch = B; a.sk_slices = 4;
                     }
                 }
                 hipError_t e = prep_rows<PRO_LN>(a, B, st);
                 a.sk_part = nullptr;
                 if (e != hipSuccess) return e;
-                a.xin = c->h1buf;
+                a.xin = c->kv->h1buf.p;
                 a.xt_out = nullptr;
                 if constexpr (HALF) {
                     if (c->xt) {      // input and output both tiled: fc2 below reads xt_f
-                        a.W = L.w1_t; a.xin = (const float*)c->xt_h; a.xt_out = c->xt_f;
-                        return gemv_mfma_groups<WT, EPI_RELU, true>(a, B, H, SkPart{c->skpart, c->skpart_floats}, st);
+                        a.W = L.w1_t; a.xin = (const float*)c->kv->xt_h.p; a.xt_out = c->kv->xt_f.p;
+                        return gemv_mfma_groups<WT, EPI_RELU, true>(a, B, H, SkPart{c->kv->skpart.p, c->kv->skpart.n}, st);
                     }
                 }
-                if (!c->batched_valu) { a.W = L.w1_t; return gemv_mfma_groups<WT, EPI_RELU>(a, B, H, SkPart{c->skpart, c->skpart_floats}, st); }   // 192 tiles of 32 rows
+                if (!c->batched_valu) { a.W = L.w1_t; return gemv_mfma_groups<WT, EPI_RELU>(a, B, H, SkPart{c->kv->skpart.p, c->kv->skpart.n}, st); }   // 192 tiles of 32 rows
                 return gemv_batched_groups<WT, 1, 3, EPI_RELU>(a, B, H, st);   // 6144 rows = 256 workgroups x 24
             }
             return gemv_nw<WT, PRO_LN, EPI_RELU>(c->nw_fc1, a, B, H, st);
         }
         case 5: {   // ypre = fc2 f + b + h1
             const LayerW& L = c->layers[layer];
-            a.W = HALF ? (const void*)L.w2_h : (const void*)L.w2; a.bias = L.b2; a.N = H; a.xin = c->fbuf; a.out = c->ypre; a.resid = c->h1buf;
+            a.W = HALF ? (const void*)L.w2_h : (const void*)L.w2; a.bias = L.b2; a.N = H; a.xin = c->kv->fbuf.p; a.out = c->kv->ypre.p; a.resid = c->kv->h1buf.p;
             if constexpr (HALF) {
                 // layers 0 .. nl-2 leave the four K-range partials to the next layer's LayerNorm launch (case 0); the last layer finishes
                 // into ypre, which the lm_head reads (after a prefill ypre comes from the GEMM path, so case 6 always reads ypre)
                 // 4-wave workgroups: 48 row tiles x 16 K-ranges of 384 (768 workgroups = 3 per CU instead of 192 on 192 CUs)
-                if (c->xt) { a.W = L.w2_t; a.xin = (const float*)c->xt_f; return gemv_mfma_groups<WT, EPI_RESID, true>(a, B, I, SkPart{c->skpart, c->skpart_floats}, st, layer + 1 < nl, true); }
+                if (c->xt) { a.W = L.w2_t; a.xin = (const float*)c->kv->xt_f.p; return gemv_mfma_groups<WT, EPI_RESID, true>(a, B, I, SkPart{c->kv->skpart.p, c->kv->skpart.n}, st, layer + 1 < nl, true); }
             }
-            if (c->batched && !c->batched_valu) { a.W = L.w2_t; return gemv_mfma_groups<WT, EPI_RESID>(a, B, I, SkPart{c->skpart, c->skpart_floats}, st); }   // 48 tiles x 4 K-ranges
+            if (c->batched && !c->batched_valu) { a.W = L.w2_t; return gemv_mfma_groups<WT, EPI_RESID>(a, B, I, SkPart{c->kv->skpart.p, c->kv->skpart.n}, st); }   // 48 tiles x 4 K-ranges
             if (c->batched) return gemv_batched_groups<WT, 4, 1, EPI_RESID>(a, B, I, st);
             if constexpr (HALF) {
                 // fast mode, one row: FAT workgroups like qkv's and fc1's - 4 or 6 rows per workgroup instead of 2 (384 / 256 workgroups
@@ -794,20 +764,20 @@ static hipError_t launch_kind_t(er_ctx* c, int kind, int layer, hipStream_t st, 
             return gemv_groups<WT, 4, 2, PRO_NONE, EPI_RESID>(a, B, I, st);
         }
         case 6: {   // logits = lm_head LN2_last(ypre)
-            a.W = HALF ? (const void*)c->lm_head_h : (const void*)c->lm_head; a.bias = nullptr; a.N = g.vocab_size; a.xin = c->ypre;
-            a.ln_w = c->layers[nl - 1].ln2w; a.ln_b = c->layers[nl - 1].ln2b; a.hout = nullptr; a.out = c->logits;
+            a.W = HALF ? (const void*)c->lm_head_h : (const void*)c->lm_head; a.bias = nullptr; a.N = g.vocab_size; a.xin = c->kv->ypre.p;
+            a.ln_w = c->layers[nl - 1].ln2w; a.ln_b = c->layers[nl - 1].ln2b; a.hout = nullptr; a.out = c->kv->logits.p;
             if (c->batched) {
-                a.hout = c->hbuf;
+                a.hout = c->kv->hbuf.p;
                 hipError_t e = prep_rows<PRO_LN>(a, B, st);
                 if (e != hipSuccess) return e;
-                a.xin = c->hbuf;
+                a.xin = c->kv->hbuf.p;
                 return gemv_batched_groups<WT, 1, 1, EPI_STORE>(a, B, H, st);
             }
             return gemv_groups<WT, 1, 1, PRO_LN, EPI_STORE>(a, B, H, st);
         }
         case 7:
-            hipLaunchKernelGGL(sample_head_kernel, dim3(B), dim3(ER_WG), sample_head_lds(g.vocab_size), st, c->logits,
-                               c->d_params, c->st, out_ids, out_ld);
+            hipLaunchKernelGGL(sample_head_kernel, dim3(B), dim3(ER_WG), sample_head_lds(g.vocab_size), st, c->kv->logits.p,
+                               c->kv->d_params.p, c->kv->st, out_ids, out_ld);
             return hipGetLastError();
     }
     return hipErrorInvalidValue;
@@ -878,10 +848,9 @@ static int linear_hs(er_ctx* c, const float* A, int lda, const _Float16* W, cons
     // (tests/test_gpu_kernels.py::test_gemm_f16s_forms_agree).
     constexpr int HS_MAX_ROWS = 4608;          // two 2050-token prefixes + slack
     if (K % XBK != 0 || M > HS_MAX_ROWS) { HIPRET(linear_h(A, lda, W, bias, C, ldc, M, N, K, relu, resid, ldr, st)); return 0; }
-    ERCHK(ensure(c->p_hi, (size_t)M * K / 2 + 8));
-    ERCHK(ensure(c->p_lo, (size_t)M * K / 2 + 8));
-    _Float16* hi = reinterpret_cast<_Float16*>(c->p_hi.p);
-    _Float16* lo = reinterpret_cast<_Float16*>(c->p_lo.p);
+    ERCHK(c->p_hi.ensure((size_t)M * K + F16_TAIL));
+    ERCHK(c->p_lo.ensure((size_t)M * K + F16_TAIL));
+    _Float16 *hi = c->p_hi.p, *lo = c->p_lo.p;
     hipLaunchKernelGGL(split_rows_f16_kernel, split_rows_grid(M, K), dim3(ER_WG), 0, st, A, hi, lo, (long long)M, K, lda);
     HIPRET(hipGetLastError());
     GemmArgs g = gemm_args_default();
@@ -931,24 +900,24 @@ static int point_latent_chunk(PointEnc& p, const float* pts, int nb, int N, hipS
         return fail(ER_ERR_INVALID, "point_encoder_mode downsample samples point_latent_size = %d points per cloud; the clouds have %d", Lq, N);
     const size_t R = (size_t)nb * N, RQ = (size_t)nb * Lq;
     const size_t QR = ds ? RQ : (size_t)Lq;   // rows of the query table: per sample (downsample) or one shared table (embed)
-    ERCHK(ensure(p.a0, R * p.kpad));
-    ERCHK(ensure(p.x, R * PH));
-    ERCHK(ensure(p.k, R * PH));
-    ERCHK(ensure(p.v, R * PH));
-    ERCHK(ensure(p.qln, QR * PH));
-    ERCHK(ensure(p.q, QR * PH));
-    ERCHK(ensure(p.att, RQ * PH));
-    ERCHK(ensure(p.l, RQ * PH));
-    ERCHK(ensure(p.ln, RQ * PH));
-    ERCHK(ensure(p.u, RQ * 8 * PH));
-    ERCHK(ensure(p.g, RQ * 4 * PH));
-    ERCHK(ensure(p.lat, RQ * LD));
+    ERCHK(p.a0.ensure(R * p.kpad));
+    ERCHK(p.x.ensure(R * PH));
+    ERCHK(p.k.ensure(R * PH));
+    ERCHK(p.v.ensure(R * PH));
+    ERCHK(p.qln.ensure(QR * PH));
+    ERCHK(p.q.ensure(QR * PH));
+    ERCHK(p.att.ensure(RQ * PH));
+    ERCHK(p.l.ensure(RQ * PH));
+    ERCHK(p.ln.ensure(RQ * PH));
+    ERCHK(p.u.ensure(RQ * 8 * PH));
+    ERCHK(p.g.ensure(RQ * 4 * PH));
+    ERCHK(p.lat.ensure(RQ * LD));
     int32_t* fidx = nullptr;
     if (ds) {
-        ERCHK(ensure(p.q0, RQ * PH));
-        ERCHK(ensure(p.fidx, RQ));
-        if (N > FPS_REG_MAX) ERCHK(ensure(p.fdist, R));
-        fidx = reinterpret_cast<int32_t*>(p.fidx.p);
+        ERCHK(p.q0.ensure(RQ * PH));
+        ERCHK(p.fidx.ensure(RQ));
+        if (N > FPS_REG_MAX) ERCHK(p.fdist.ensure(R));
+        fidx = p.fidx.p;
         // fps_indices = torch_cluster.fps(pc, batch, ratio = Lq / N)                  point.py:152-156
         HIPRET(launch_fps(pts, nb, N, Lq, fidx, p.fdist.p, st));
     }
@@ -979,7 +948,7 @@ static int point_latent_chunk(PointEnc& p, const float* pts, int nb, int N, hipS
         HIPRET(launch_flash_attn_f32(f, PD, false, PHh, nb, st));
     } else {
         const int ldS = (N + 15) / 16 * 16;
-        ERCHK(ensure(p.sc, (size_t)PHh * Lq * ldS));
+        ERCHK(p.sc.ensure((size_t)PHh * Lq * ldS));
         for (int b = 0; b < nb; ++b)
             ERCHK(attention_full(p.q.p + (ds ? (size_t)b * Lq * PH : 0), PH, p.k.p + (size_t)b * N * PH, PH, PD,
                                  p.v.p + (size_t)b * N * PH, PH, PD, p.att.p + (size_t)b * Lq * PH, PH, p.sc.p, PHh, PD, Lq, N, false, st));
@@ -1037,7 +1006,7 @@ extern "C" int er_encode_cond(er_ctx* c, const float* conds, int B, int n_points
             lat = conds + (size_t)b0 * Lq * LD;
         }
         if (lat) {   // norm_cond(proj_cond(latent))                               core/models.py:124 / 128-129
-            ERCHK(ensure(c->e_tmp, (size_t)nb * Lq * H));
+            ERCHK(c->e_tmp.ensure((size_t)nb * Lq * H));
             HIPRET(linear(lat, LD, c->proj_w, c->proj_b, c->e_tmp.p, H, nb * Lq, H, LD, false, nullptr, 0, st));
         }
         for (int b = 0; b < nb; ++b) {
@@ -1064,8 +1033,8 @@ extern "C" int er_embed_tokens(er_ctx* c, const int32_t* ids, int B, int R, floa
     for (int i = 0; i < n; ++i)
         if (ids[i] < 0 || ids[i] >= c->cfg.vocab_size) return fail(ER_ERR_INVALID, "token id %d out of range", ids[i]);
     // one gather launch (round 1 issued one hipMemcpyAsync per token: a 2000-token resume prefix was 2000 copies)
-    ERCHK(ensure(c->e_ids, (size_t)n));                     // grow-only int scratch (4-byte slots)
-    int* d_ids = reinterpret_cast<int*>(c->e_ids.p);
+    ERCHK(c->e_ids.ensure((size_t)n));
+    int* d_ids = c->e_ids.p;
     HIPCHK(hipMemcpyAsync(d_ids, ids, (size_t)n * sizeof(int), hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(gather_rows_kernel, dim3(n), dim3(ER_WG), 0, st, c->embd, d_ids, out, n, H, (long long)H);
     HIPRET(hipGetLastError());
@@ -1122,18 +1091,18 @@ static int prefill_run(er_ctx* c, const float* embeds, int B, int S, hipStream_t
     const er_config& g = c->cfg;
     const int H = g.hidden_dim, I = g.intermediate_dim, NH = g.num_heads, D = c->D;
     const int M = B * S;
-    ERCHK(ensure(c->p_h, (size_t)M * H));
-    ERCHK(ensure(c->p_q, (size_t)M * H));
-    ERCHK(ensure(c->p_a, (size_t)M * H));
-    ERCHK(ensure(c->p_y, (size_t)M * H));
-    ERCHK(ensure(c->p_f, (size_t)M * I));
+    ERCHK(c->p_h.ensure((size_t)M * H));
+    ERCHK(c->p_q.ensure((size_t)M * H));
+    ERCHK(c->p_a.ensure((size_t)M * H));
+    ERCHK(c->p_y.ensure((size_t)M * H));
+    ERCHK(c->p_f.ensure((size_t)M * I));
     float *h = c->p_h.p, *q = c->p_q.p, *a = c->p_a.p, *y = c->p_y.p, *f = c->p_f.p;
     const int tail = prefill_tail_rows(c, M), Mm = M - tail;
     // the causal attention of a single prefix is split over two key ranges per query tile (k_flash_attn_f32.h, KSP; same rule as the launcher)
     bool attn_ksplit = false;
     if (!c->fast && flash32_ksplit(S, NH, B, D, true)) {
-        ERCHK(ensure(c->p_ap, flash32_part_o_floats(B, NH, S, D)));
-        ERCHK(ensure(c->p_aml, flash32_part_ml_floats(B, NH, S)));
+        ERCHK(c->p_ap.ensure(flash32_part_o_floats(B, NH, S, D)));
+        ERCHK(c->p_aml.ensure(flash32_part_ml_floats(B, NH, S)));
         attn_ksplit = true;
     }
 
@@ -1142,8 +1111,8 @@ static int prefill_run(er_ctx* c, const float* embeds, int B, int S, hipStream_t
     HIPRET(hipGetLastError());
     for (int l = 0; l < g.num_layers; ++l) {
         const LayerW& L = c->layers[l];
-        char* kc = (char*)c->kc + (long long)l * c->kv_lstride * c->kv_esz;
-        char* vc = (char*)c->vc + (long long)l * c->kv_lstride * c->kv_esz;
+        char* kc = c->kv->kc.p + (long long)l * c->kv_lstride * c->kv_esz;
+        char* vc = c->kv->vc.p + (long long)l * c->kv_lstride * c->kv_esz;
         if (!c->fast) {
             // q,k,v projections; k,v go straight into the cache layout      modeling_opt.py:185-196
             GemmArgs qa = gemm_args_default();
@@ -1165,7 +1134,7 @@ static int prefill_run(er_ctx* c, const float* embeds, int B, int S, hipStream_t
         } else {
             // fast mode: fused projection into fp32 scratch [M][3H]; K/V rounded to the cache dtype (fp16) both in
             // the cache and in the scratch the prefix attention reads
-            ERCHK(ensure(c->p_qkv, (size_t)M * 3 * H));
+            ERCHK(c->p_qkv.ensure((size_t)M * 3 * H));
             float* qkv = c->p_qkv.p;
             ERCHK(linear_hs(c, h, H, L.wqkv_h, L.bqkv, qkv, 3 * H, M, 3 * H, H, false, nullptr, 0, st));
             hipLaunchKernelGGL(kv_scatter_half_kernel, kv_scatter_grid(M, H), dim3(ER_WG), 0, st, qkv,
@@ -1205,8 +1174,8 @@ static int prefill_run(er_ctx* c, const float* embeds, int B, int S, hipStream_t
     }
     // keep the last position's pre-LN2 state: the decode head applies LN2 + lm_head to it
     for (int b = 0; b < B; ++b)
-        HIPCHK(hipMemcpyAsync(c->ypre + (size_t)b * H, y + ((size_t)b * S + S - 1) * H, (size_t)H * 4, hipMemcpyDeviceToDevice, st));
-    hipLaunchKernelGGL(init_state_kernel, dim3((B + 63) / 64), dim3(64), 0, st, c->st, B, S);
+        HIPCHK(hipMemcpyAsync(c->kv->ypre.p + (size_t)b * H, y + ((size_t)b * S + S - 1) * H, (size_t)H * 4, hipMemcpyDeviceToDevice, st));
+    hipLaunchKernelGGL(init_state_kernel, dim3((B + 63) / 64), dim3(64), 0, st, c->kv->st, B, S);
     HIPRET(hipGetLastError());
     c->base_pos = S;
     c->have_hidden = true;
@@ -1232,7 +1201,7 @@ extern "C" int er_score(er_ctx* c, const float* embeds, const int32_t* labels, i
     HIPRET(launch_layernorm(c->p_y.p, last.ln2w, last.ln2b, c->p_h.p, M, H, H, H, g.ln_eps, st));
     float* lg = logits_out;
     if (!lg) {
-        ERCHK(ensure(c->s_lg, (size_t)M * V));
+        ERCHK(c->s_lg.ensure((size_t)M * V));
         lg = c->s_lg.p;
     }
     // lm_head over every position (modeling_opt.py:497): the prefill's own Linears, fp32 or fp16-stored weights (fp32-grade activations)
@@ -1268,13 +1237,13 @@ extern "C" int er_logits(er_ctx* c, float* out, void* stream) {
     HIPCHK(hipSetDevice(c->device));
     hipStream_t st = pick(c, stream);
     HIPRET(launch_kind(c, 6, 0, st, nullptr, 0));
-    HIPCHK(hipMemcpyAsync(out, c->logits, (size_t)c->B * c->cfg.vocab_size * 4, hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipMemcpyAsync(out, c->kv->logits.p, (size_t)c->B * c->cfg.vocab_size * 4, hipMemcpyDeviceToDevice, st));
     return ER_OK;
 }
 
 static int check_room(er_ctx* c, int extra) {
     // generated token t is fed at position base_pos + t
-    HIPCHK(hipMemcpy(c->h_pinned, c->st.ngen, sizeof(int), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(c->h_pinned, c->kv->st.ngen, sizeof(int), hipMemcpyDeviceToHost));
     const int used = c->base_pos + c->h_pinned[0];
     if (used + extra > c->Lcap) return fail(ER_ERR_CAPACITY, "KV cache full: %d + %d > %d", used, extra, c->Lcap);
     if (used + extra > c->cfg.max_positions) return fail(ER_ERR_CAPACITY, "position table exhausted (%d)", c->cfg.max_positions);
@@ -1292,8 +1261,8 @@ extern "C" int er_feed(er_ctx* c, const int32_t* ids, void* stream) {
         if (ids[b] < 0 || ids[b] >= c->cfg.vocab_size) return fail(ER_ERR_INVALID, "token id %d out of range", ids[b]);
         c->h_pinned[b] = ids[b];
     }
-    HIPCHK(hipMemcpyAsync(c->d_ids_tmp, c->h_pinned, c->B * sizeof(int), hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(force_token_kernel, dim3((c->B + 63) / 64), dim3(64), 0, st, c->d_ids_tmp, c->st, c->B);
+    HIPCHK(hipMemcpyAsync(c->kv->d_ids_tmp.p, c->h_pinned, c->B * sizeof(int), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(force_token_kernel, dim3((c->B + 63) / 64), dim3(64), 0, st, c->kv->d_ids_tmp.p, c->kv->st, c->B);
     HIPRET(hipGetLastError());
     HIPRET(enqueue_layers(c, st));
     HIPCHK(hipStreamSynchronize(st));   // h_pinned may be reused by the next call
@@ -1329,24 +1298,24 @@ extern "C" int er_decode(er_ctx* c, const er_decode_params* p, int64_t* out_ids,
     dp.mode = p->mode; dp.top_k = p->top_k; dp.grammar = p->grammar; dp.max_new = T; dp.min_new = p->min_new_tokens;
     dp.eos = c->cfg.eos_token_id; dp.pad = c->cfg.pad_token_id; dp.vocab = c->cfg.vocab_size;
     dp.seed_lo = (unsigned int)(p->seed & 0xffffffffu); dp.seed_hi = (unsigned int)(p->seed >> 32);
-    HIPCHK(hipMemcpy(c->d_params, &dp, sizeof(dp), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(reset_gen_kernel, dim3((B + 63) / 64), dim3(64), 0, st, c->st, B);
+    HIPCHK(hipMemcpy(c->kv->d_params.p, &dp, sizeof(dp), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(reset_gen_kernel, dim3((B + 63) / 64), dim3(64), 0, st, c->kv->st, B);
     HIPRET(hipGetLastError());
-    hipLaunchKernelGGL(fill_i64_kernel, dim3(ew_grid((long long)B * c->Lcap)), dim3(ER_WG), 0, st, c->d_out_ids,
+    hipLaunchKernelGGL(fill_i64_kernel, dim3(ew_grid((long long)B * c->Lcap)), dim3(ER_WG), 0, st, c->kv->d_out_ids.p,
                        (long long)B * c->Lcap, (long long)dp.pad);
     HIPRET(hipGetLastError());
 
     // one step = lm_head -> sampling head -> 24 layers on the chosen token; captured once, replayed T times
-    if (c->use_graph && !c->step_exec) {
+    if (c->use_graph && !c->kv->step_exec) {
         hipGraph_t graph = nullptr;
         HIPCHK(hipStreamBeginCapture(c->own_stream, hipStreamCaptureModeRelaxed));
-        hipError_t e = enqueue_step(c, c->own_stream, c->d_out_ids, c->Lcap);
+        hipError_t e = enqueue_step(c, c->own_stream, c->kv->d_out_ids.p, c->Lcap);
         hipError_t e2 = hipStreamEndCapture(c->own_stream, &graph);
         if (e != hipSuccess || e2 != hipSuccess) {
             if (graph) hipGraphDestroy(graph);
             return fail(ER_ERR_HIP, "graph capture failed: %s / %s", hipGetErrorString(e), hipGetErrorString(e2));
         }
-        HIPCHK(hipGraphInstantiate(&c->step_exec, graph, nullptr, nullptr, 0));
+        HIPCHK(hipGraphInstantiate(&c->kv->step_exec, graph, nullptr, nullptr, 0));
         hipGraphDestroy(graph);
     }
 
@@ -1355,20 +1324,20 @@ extern "C" int er_decode(er_ctx* c, const er_decode_params* p, int64_t* out_ids,
     bool all_done = false;
     HIPCHK(hipEventRecord(c->ev0, st));
     for (int t = 0; t < T; ++t) {
-        if (c->use_graph) HIPCHK(hipGraphLaunch(c->step_exec, st));
-        else HIPRET(enqueue_step(c, st, c->d_out_ids, c->Lcap));
+        if (c->use_graph) HIPCHK(hipGraphLaunch(c->kv->step_exec, st));
+        else HIPRET(enqueue_step(c, st, c->kv->d_out_ids.p, c->Lcap));
         steps_run = t + 1;
         if (steps_run >= p->min_new_tokens && steps_run < T && (steps_run % check_every) == 0) {
-            HIPCHK(hipMemcpyAsync(c->h_pinned, c->st.n_unfinished, sizeof(int), hipMemcpyDeviceToHost, st));
+            HIPCHK(hipMemcpyAsync(c->h_pinned, c->kv->st.n_unfinished, sizeof(int), hipMemcpyDeviceToHost, st));
             HIPCHK(hipStreamSynchronize(st));
             if (c->h_pinned[0] <= 0) { all_done = true; break; }
         }
     }
     HIPCHK(hipEventRecord(c->ev1, st));
-    HIPCHK(hipMemcpy2DAsync(out_ids, (size_t)T * sizeof(long long), c->d_out_ids, (size_t)c->Lcap * sizeof(long long),
+    HIPCHK(hipMemcpy2DAsync(out_ids, (size_t)T * sizeof(long long), c->kv->d_out_ids.p, (size_t)c->Lcap * sizeof(long long),
                             (size_t)T * sizeof(long long), B, hipMemcpyDeviceToDevice, st));
-    HIPCHK(hipMemcpyAsync(c->h_pinned, c->st.eos_step, B * sizeof(int), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(c->h_pinned + B, c->st.error, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(c->h_pinned, c->kv->st.eos_step, B * sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(c->h_pinned + B, c->kv->st.error, sizeof(int), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     HIPCHK(hipEventElapsedTime(&c->last_decode_ms, c->ev0, c->ev1));
     if (c->h_pinned[B] != 0)
@@ -1394,7 +1363,7 @@ extern "C" int er_set_row_streams(er_ctx* c, const uint32_t* ids, int n) {
     std::vector<unsigned int> h((size_t)c->B);
     for (int i = 0; i < c->B; ++i) h[i] = ids ? ids[i] : (unsigned int)i;
     HIPCHK(hipDeviceSynchronize());           // a running decode still reads the old ids
-    HIPCHK(hipMemcpy(c->d_row_stream, h.data(), h.size() * sizeof(unsigned int), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(c->kv->d_row_stream.p, h.data(), h.size() * sizeof(unsigned int), hipMemcpyHostToDevice));
     return ER_OK;
 }
 
@@ -1429,21 +1398,22 @@ static int profile_impl(er_ctx* c, int repeats, int use_graph, float* avg_us, do
     const er_config& g = c->cfg;
     const int B = c->B, H = g.hidden_dim, I = g.intermediate_dim, nl = g.num_layers, V = g.vocab_size;
     HIPCHK(hipStreamSynchronize(st));
-    HIPCHK(hipMemcpy(c->h_pinned, c->st.pos, sizeof(int), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(c->h_pinned, c->kv->st.pos, sizeof(int), hipMemcpyDeviceToHost));
     const double len = c->prof_len > 0 ? (double)c->prof_len : (double)c->h_pinned[0] + 1.0;
     // save the state the sweep scribbles on
     std::vector<float> save_y((size_t)B * H);
-    HIPCHK(hipMemcpy(save_y.data(), c->ypre, save_y.size() * 4, hipMemcpyDeviceToHost));
-    std::vector<int> save_state(7 * (size_t)B + 8);
-    HIPCHK(hipMemcpy(save_state.data(), c->state_block, save_state.size() * sizeof(int), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(save_y.data(), c->kv->ypre.p, save_y.size() * 4, hipMemcpyDeviceToHost));
+    std::vector<int> save_state(gen_state_ints(B));
+    HIPCHK(hipMemcpy(save_state.data(), c->kv->state_block.p, save_state.size() * sizeof(int), hipMemcpyDeviceToHost));
     std::vector<int> head_state = save_state;          // the head sweep runs at step 0 so it writes dummy_ids[b][0]
-    for (int b = 0; b < B; ++b) head_state[3 * (size_t)B + b] = 0;
+    for (int b = 0; b < B; ++b) gen_state_carve(head_state.data(), B).ngen[b] = 0;
     DecodeParamsDev dp{};
     dp.mode = 0; dp.top_k = 10; dp.grammar = 2; dp.max_new = 1 << 30; dp.min_new = 0;
     dp.eos = g.eos_token_id; dp.pad = g.pad_token_id; dp.vocab = V;
-    HIPCHK(hipMemcpy(c->d_params, &dp, sizeof(dp), hipMemcpyHostToDevice));
-    long long* dummy_ids = nullptr;
-    HIPCHK(hipMalloc(&dummy_ids, (size_t)B * 8 * sizeof(long long)));
+    HIPCHK(hipMemcpy(c->kv->d_params.p, &dp, sizeof(dp), hipMemcpyHostToDevice));
+    DevBuf<long long> dummy;             // freed on every return path; a failing one frees behind hipFree's own device synchronisation
+    ERCHK(dummy.ensure((size_t)B * 8));
+    long long* dummy_ids = dummy.p;
 
     const double w = c->fast ? 2.0 : 4.0;   // bytes per streamed weight / KV element
     bytes[0] = ((double)3 * H * H + 3 * H) * w + (double)B * (H + 3 * H) * w;
@@ -1487,7 +1457,7 @@ static int profile_impl(er_ctx* c, int repeats, int use_graph, float* avg_us, do
                 } else {
                     for (int l = 0; l < nl; ++l) {   // same number of back-to-back launches
                         if (kind == 7) {   // keep the head's step counter in range
-                            HIPCHK(hipMemcpyAsync(c->state_block, head_state.data(), head_state.size() * sizeof(int), hipMemcpyHostToDevice, st));
+                            HIPCHK(hipMemcpyAsync(c->kv->state_block.p, head_state.data(), head_state.size() * sizeof(int), hipMemcpyHostToDevice, st));
                         }
                         HIPRET(launch_kind(c, kind, 0, st, dummy_ids, 8));
                         ++launches;
@@ -1505,13 +1475,14 @@ static int profile_impl(er_ctx* c, int repeats, int use_graph, float* avg_us, do
         if (gexec) hipGraphExecDestroy(gexec);
     }
     HIPCHK(hipStreamSynchronize(st));
-    HIPCHK(hipMemcpy(c->ypre, save_y.data(), save_y.size() * 4, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(c->state_block, save_state.data(), save_state.size() * sizeof(int), hipMemcpyHostToDevice));
-    hipFree(dummy_ids);
+    HIPCHK(hipMemcpy(c->kv->ypre.p, save_y.data(), save_y.size() * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(c->kv->state_block.p, save_state.data(), save_state.size() * sizeof(int), hipMemcpyHostToDevice));
     return ER_OK;
 }
 
 // ------------------------------------------------------------------------------------ single-kernel entry points
+// Their temporaries are local DevBufs: allocated before the first launch, and freed by every return path - behind the explicit
+// hipStreamSynchronize on the paths that launched something.
 extern "C" int er_k_gemv(const float* w, const float* bias, const float* x, const float* ln_w, const float* ln_b,
                          const float* resid, float* y, float* xnorm_out, int B, int n, int k, int relu, float eps, void* stream) {
     hipStream_t st = (hipStream_t)stream;
@@ -1520,40 +1491,37 @@ extern "C" int er_k_gemv(const float* w, const float* bias, const float* x, cons
     a.out = y; a.resid = resid;
     hipError_t e;
     if (B > 4) {   // batched kernels: LayerNorm rows first (same arithmetic as the fused prologue), then passes of 32 (VALU: 16) rows
-        float* tmp = nullptr;
-        if (ln_w) {
-            if (k != 1536) return fail(ER_ERR_UNSUPPORTED, "er_k_gemv: LayerNorm prologue needs k=1536");
-            if (!xnorm_out) { HIPCHK(hipMalloc(&tmp, (size_t)B * k * 4)); a.hout = tmp; }
-            e = prep_rows<PRO_LN>(a, B, st);
-            if (e != hipSuccess) { if (tmp) hipFree(tmp); HIPRET(e); }
-            a.xin = a.hout;
-        }
+        DevBuf<float> tmp, part;
+        DevBuf<char> wt;                 // tiled copy of w for the matrix-core kernels (the decode step keeps one per matrix)
+        if (ln_w && k != 1536) return fail(ER_ERR_UNSUPPORTED, "er_k_gemv: LayerNorm prologue needs k=1536");
+        if (ln_w && !xnorm_out) ERCHK(tmp.ensure((size_t)B * k));
         const char* bv = getenv("ER_BATCHED_VALU");
         const bool valu = bv && bv[0] == '1';
-        float* part = nullptr;
-        void* wt = nullptr;              // tiled copy of w for the matrix-core kernels (the decode step keeps one per matrix)
         const bool mfma = !valu && ((k == 1536 && relu && !resid) || (k == 6144 && !relu && resid && !ln_w));
         if (mfma) {
-            HIPCHK(hipMalloc(&part, (size_t)4 * NBM * n * 4));
-            HIPCHK(hipMalloc(&wt, tiled_weight_bytes<float>(n, k)));
-            hipLaunchKernelGGL((tile_weights_kernel<float>), dim3(1024), dim3(ER_WG), 0, st, w, reinterpret_cast<f32x4*>(wt), n, k);
+            ERCHK(part.ensure((size_t)4 * NBM * n));
+            ERCHK(wt.ensure(tiled_weight_bytes<float>(n, k)));
         }
+        if (ln_w) {
+            if (tmp.p) a.hout = tmp.p;
+            e = prep_rows<PRO_LN>(a, B, st);
+            HIPRET(e);
+            a.xin = a.hout;
+        }
+        if (mfma) hipLaunchKernelGGL((tile_weights_kernel<float>), dim3(1024), dim3(ER_WG), 0, st, w, reinterpret_cast<f32x4*>(wt.p), n, k);
         GemvArgs am = a;
-        am.W = wt;
+        am.W = wt.p;
         if (k == 1536) {
-            if (relu && !resid) e = valu ? gemv_batched_groups<float, 1, 2, EPI_RELU>(a, B, k, st) : gemv_mfma_groups<float, EPI_RELU>(am, B, k, SkPart{part, (size_t)4 * NBM * n}, st);
+            if (relu && !resid) e = valu ? gemv_batched_groups<float, 1, 2, EPI_RELU>(a, B, k, st) : gemv_mfma_groups<float, EPI_RELU>(am, B, k, SkPart{part.p, part.n}, st);
             else if (!relu && !resid) e = gemv_batched_groups<float, 1, 1, EPI_STORE>(a, B, k, st);   // narrow: VALU kernel, as in the decode step
             else if (!relu && resid) e = gemv_batched_groups<float, 1, 1, EPI_RESID>(a, B, k, st);
             else e = hipErrorInvalidValue;
         } else if (k == 6144 && !relu && resid && !ln_w) {
-            e = valu ? gemv_batched_groups<float, 4, 1, EPI_RESID>(a, B, k, st) : gemv_mfma_groups<float, EPI_RESID>(am, B, k, SkPart{part, (size_t)4 * NBM * n}, st);
+            e = valu ? gemv_batched_groups<float, 4, 1, EPI_RESID>(a, B, k, st) : gemv_mfma_groups<float, EPI_RESID>(am, B, k, SkPart{part.p, part.n}, st);
         } else {
             e = hipErrorInvalidValue;
         }
-        if (wt) { hipStreamSynchronize(st); hipFree(wt); }
-        if (part) { hipStreamSynchronize(st); hipFree(part); }
         hipError_t e2 = hipStreamSynchronize(st);
-        if (tmp) hipFree(tmp);
         HIPRET(e);
         HIPRET(e2);
         return ER_OK;
@@ -1582,13 +1550,13 @@ extern "C" int er_k_attn_decode(const float* q, const void* k, const void* v, co
     if (steps != 2 && steps != 4 && steps != 8) return fail(ER_ERR_INVALID, "steps must be 2, 4 or 8 (chunk = 32*steps keys)");
     hipStream_t st = (hipStream_t)stream;
     const int S = attn_num_chunks(l_cap, attn_chunk(steps, kv_half != 0));
-    int* len_dev = nullptr;
-    float* part = nullptr;
-    HIPCHK(hipMalloc(&len_dev, B * sizeof(int)));
-    HIPCHK(hipMalloc(&part, (size_t)B * heads * S * (head_dim + 2) * 4));
-    HIPCHK(hipMemcpy(len_dev, len_host, B * sizeof(int), hipMemcpyHostToDevice));
+    DevBuf<int> len_dev;
+    DevBuf<float> part;
+    ERCHK(len_dev.ensure(B));
+    ERCHK(part.ensure((size_t)B * heads * S * (head_dim + 2)));
+    HIPCHK(hipMemcpy(len_dev.p, len_host, B * sizeof(int), hipMemcpyHostToDevice));
     AttnDecArgs a{};
-    a.q = q; a.kcache = k; a.vcache = v; a.len_dev = len_dev; a.part = part; a.out = out;
+    a.q = q; a.kcache = k; a.vcache = v; a.len_dev = len_dev.p; a.part = part.p; a.out = out;
     a.H = heads; a.l_cap = l_cap; a.S = S; a.hidden = heads * head_dim; a.chunk = attn_chunk(steps, kv_half != 0);
     a.kv_bstride = (long long)heads * l_cap * head_dim; a.sqrt_d = sqrtf((float)head_dim);
     hipError_t e;
@@ -1599,8 +1567,6 @@ extern "C" int er_k_attn_decode(const float* q, const void* k, const void* v, co
         if (e == hipSuccess) e = launch_attn_combine(a, head_dim, B, st);
     }
     hipError_t e2 = hipStreamSynchronize(st);
-    hipFree(len_dev);
-    hipFree(part);
     HIPRET(e);
     HIPRET(e2);
     return ER_OK;
@@ -1613,9 +1579,9 @@ extern "C" int er_k_attn_outproj3(const float* q, const void* k, const void* v, 
     if (len <= 0 || len > l_cap || !attn3_fits(l_cap, H)) return fail(ER_ERR_CAPACITY, "er_k_attn_outproj3: len %d / l_cap %d (<= %d)", len, l_cap, attn3_num_chunks(H) * ATTN3_CAP);
     hipStream_t st = (hipStream_t)stream;
     const int nch = attn3_num_chunks(H);
-    float *part = nullptr, *part_ml = nullptr;
-    HIPCHK(hipMalloc(&part, (size_t)H * nch * (D + 2) * 4));
-    part_ml = part + (size_t)H * nch * D;      // one allocation: nothing to leak on an error path
+    DevBuf<float> blk;                         // partial outputs, then their {m, l}
+    ERCHK(blk.ensure((size_t)H * nch * (D + 2)));
+    float *part = blk.p, *part_ml = part + (size_t)H * nch * D;
     AttnDecArgs a{};
     a.q = q; a.kcache = k; a.vcache = v; a.fixed_len = len; a.part = part; a.part_ml = part_ml;
     a.H = H; a.l_cap = l_cap; a.hidden = H * D; a.kv_bstride = (long long)H * l_cap * D; a.sqrt_d = sqrtf((float)D);
@@ -1624,7 +1590,6 @@ extern "C" int er_k_attn_outproj3(const float* q, const void* k, const void* v, 
     m.W = wo; m.bias = bo; m.resid = resid; m.out = y; m.part_o = part; m.part_ml = part_ml; m.N = H * D;
     if (e == hipSuccess) e = w_half ? launch_outproj_merge<_Float16, D>(m, nch, st) : launch_outproj_merge<float, D>(m, nch, st);
     hipError_t e2 = hipStreamSynchronize(st);
-    hipFree(part);
     HIPRET(e);
     HIPRET(e2);
     return ER_OK;
@@ -1656,8 +1621,9 @@ extern "C" int er_k_gemm_hh(const float* a, const void* w, const float* bias, co
                             int n, int k, int lda, int ldb, int ldc, int relu, void* stream) {
     if (k % 64 || (ldb & 7)) return fail(ER_ERR_INVALID, "er_k_gemm_hh: k must be a multiple of 64, ldb of 8");
     hipStream_t st = (hipStream_t)stream;
-    _Float16* a16 = nullptr;
-    HIPCHK(hipMalloc(&a16, (size_t)m * k * sizeof(_Float16)));
+    DevBuf<_Float16> a16b;
+    ERCHK(a16b.ensure((size_t)m * k));
+    _Float16* a16 = a16b.p;
     hipLaunchKernelGGL(cvt_rows_f16_kernel, dim3(ew_grid((long long)m * k)), dim3(ER_WG), 0, st, a, a16, (long long)m, k, lda, k);
     GemmArgs g = gemm_args_default();
     g.A = reinterpret_cast<const float*>(a16); g.B = reinterpret_cast<const float*>(w); g.C = cc; g.bias = bias; g.resid = resid;
@@ -1665,7 +1631,6 @@ extern "C" int er_k_gemm_hh(const float* a, const void* w, const float* bias, co
     g.c16 = reinterpret_cast<_Float16*>(c16_out); g.ldc16 = n;
     hipError_t e = launch_gemm_hh(g, st);
     hipError_t e2 = hipStreamSynchronize(st);
-    hipFree(a16);
     HIPRET(e);
     HIPRET(e2);
     return ER_OK;
@@ -1676,8 +1641,9 @@ extern "C" int er_k_gemm_hh_qkv(const float* a, const void* w, const float* bias
     if (k % 64 || n % 192 || m % 64 || rows_per_batch <= 0 || rows_per_batch % 64 || m % rows_per_batch)
         return fail(ER_ERR_INVALID, "er_k_gemm_hh_qkv: k, m, rows_per_batch multiples of 64, n of 192");
     hipStream_t st = (hipStream_t)stream;
-    _Float16* a16 = nullptr;
-    HIPCHK(hipMalloc(&a16, (size_t)m * k * sizeof(_Float16)));
+    DevBuf<_Float16> a16b;
+    ERCHK(a16b.ensure((size_t)m * k));
+    _Float16* a16 = a16b.p;
     hipLaunchKernelGGL(cvt_rows_f16_kernel, dim3(ew_grid((long long)m * k)), dim3(ER_WG), 0, st, a, a16, (long long)m, k, k, k);
     GemmArgs g = gemm_args_default();
     g.A = reinterpret_cast<const float*>(a16); g.B = reinterpret_cast<const float*>(w); g.bias = bias;
@@ -1686,7 +1652,6 @@ extern "C" int er_k_gemm_hh_qkv(const float* a, const void* w, const float* bias
     g.vt16 = reinterpret_cast<_Float16*>(vt_out); g.vt_col0 = 2 * (n / 3); g.vt_rows = rows_per_batch; g.vt_ld = rows_per_batch;
     hipError_t e = launch_gemm_hh(g, st, force_tile);
     hipError_t e2 = hipStreamSynchronize(st);
-    hipFree(a16);
     HIPRET(e);
     HIPRET(e2);
     return ER_OK;
@@ -1700,12 +1665,13 @@ extern "C" int er_k_gemm_hh_geglu(const float* a, const void* w, const float* bi
     if (k % 64 || f % 64 || m <= 0) return fail(ER_ERR_INVALID, "er_k_gemm_hh_geglu: k and f must be multiples of 64");
     if (force_tile != 0 && force_tile != 1 && force_tile != 2 && force_tile != 4) return fail(ER_ERR_INVALID, "er_k_gemm_hh_geglu: force_tile 0 / 1 / 2 / 4");
     hipStream_t st = (hipStream_t)stream;
-    // ONE scratch block, carved: fp16 copy of a | permuted weight | permuted bias (an early return on a failed allocation leaks nothing)
-    const size_t na = ((size_t)m * k * sizeof(_Float16) + 255) & ~(size_t)255, nw = ((size_t)2 * f * k * sizeof(_Float16) + 255) & ~(size_t)255;
-    char* blk = nullptr;
-    HIPCHK(hipMalloc((void**)&blk, na + nw + (size_t)2 * f * sizeof(float)));
-    _Float16 *a16 = reinterpret_cast<_Float16*>(blk), *wp = reinterpret_cast<_Float16*>(blk + na);
-    float* bp = reinterpret_cast<float*>(blk + na + nw);
+    DevBuf<_Float16> a16b, wpb;      // fp16 copy of a, permuted weight
+    DevBuf<float> bpb;               // permuted bias
+    ERCHK(a16b.ensure((size_t)m * k));
+    ERCHK(wpb.ensure((size_t)2 * f * k));
+    ERCHK(bpb.ensure((size_t)2 * f));
+    _Float16 *a16 = a16b.p, *wp = wpb.p;
+    float* bp = bpb.p;
     hipLaunchKernelGGL(cvt_rows_f16_kernel, dim3(ew_grid((long long)m * k)), dim3(ER_WG), 0, st, a, a16, (long long)m, k, k, k);
     hipLaunchKernelGGL(geglu_permute_kernel, dim3(2 * f), dim3(ER_WG), 0, st, reinterpret_cast<const _Float16*>(w), bias, wp, bp, f, k);
     GemmArgs g = gemm_args_default();
@@ -1714,7 +1680,6 @@ extern "C" int er_k_gemm_hh_geglu(const float* a, const void* w, const float* bi
     g.c16 = reinterpret_cast<_Float16*>(out16); g.ldc16 = f;
     hipError_t e = launch_gemm_hh_geglu(g, st, force_tile);
     hipError_t e2 = hipStreamSynchronize(st);
-    hipFree(blk);
     HIPRET(e);
     HIPRET(e2);
     return ER_OK;
@@ -1731,14 +1696,13 @@ extern "C" int er_k_gemm_f16s(const float* a, const void* w, const float* bias, 
     const char* form = getenv("ER_K_GEMM_F16S_FORM");
     const bool force_reg = form && form[0] == 'r';
     if (k % XBK == 0 && !(ldb & 7) && !force_reg) {      // the product path of the fast-mode prefill: split pass + LDS-DMA kernel (linear_hs)
-        _Float16 *hi = nullptr, *lo = nullptr;
-        HIPCHK(hipMalloc(&hi, (size_t)m * k * 2));
-        HIPCHK(hipMalloc(&lo, (size_t)m * k * 2));
-        hipLaunchKernelGGL(split_rows_f16_kernel, split_rows_grid(m, k), dim3(ER_WG), 0, st, a, hi, lo, (long long)m, k, lda);
-        g.A = reinterpret_cast<const float*>(hi); g.a_lo = lo; g.lda = k;
+        DevBuf<_Float16> hi, lo;
+        ERCHK(hi.ensure((size_t)m * k));
+        ERCHK(lo.ensure((size_t)m * k));
+        hipLaunchKernelGGL(split_rows_f16_kernel, split_rows_grid(m, k), dim3(ER_WG), 0, st, a, hi.p, lo.p, (long long)m, k, lda);
+        g.A = reinterpret_cast<const float*>(hi.p); g.a_lo = lo.p; g.lda = k;
         hipError_t e = launch_gemm_hh_split(g, st);
         hipError_t e2 = hipStreamSynchronize(st);
-        hipFree(hi); hipFree(lo);
         HIPRET(e);
         HIPRET(e2);
         return ER_OK;
@@ -1764,12 +1728,13 @@ extern "C" int er_k_flash_attn_f16(const float* q, const float* k, const float* 
 extern "C" int er_k_flash_attn_hh(const float* q, const float* k, const float* v, float* o, int B, int H, int N, int M, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     const int C = H * FA_D, Mp = (M + 63) / 64 * 64;
-    _Float16 *q16 = nullptr, *k16 = nullptr, *v16 = nullptr, *vt = nullptr, *o16 = nullptr;
-    HIPCHK(hipMalloc(&q16, (size_t)B * N * C * 2));
-    HIPCHK(hipMalloc(&k16, (size_t)B * M * C * 2));
-    HIPCHK(hipMalloc(&v16, (size_t)B * M * C * 2));
-    HIPCHK(hipMalloc(&vt, (size_t)B * H * 64 * Mp * 2));
-    HIPCHK(hipMalloc(&o16, (size_t)B * N * C * 2));
+    DevBuf<_Float16> q16b, k16b, v16b, vtb, o16b;
+    ERCHK(q16b.ensure((size_t)B * N * C));
+    ERCHK(k16b.ensure((size_t)B * M * C));
+    ERCHK(v16b.ensure((size_t)B * M * C));
+    ERCHK(vtb.ensure((size_t)B * H * 64 * Mp));
+    ERCHK(o16b.ensure((size_t)B * N * C));
+    _Float16 *q16 = q16b.p, *k16 = k16b.p, *v16 = v16b.p, *vt = vtb.p, *o16 = o16b.p;
     hipLaunchKernelGGL(cvt_rows_f16_kernel, dim3(ew_grid((long long)B * N * C)), dim3(ER_WG), 0, st, q, q16, (long long)B * N, C, C, C);
     hipLaunchKernelGGL(cvt_rows_f16_kernel, dim3(ew_grid((long long)B * M * C)), dim3(ER_WG), 0, st, k, k16, (long long)B * M, C, C, C);
     hipLaunchKernelGGL(cvt_rows_f16_kernel, dim3(ew_grid((long long)B * M * C)), dim3(ER_WG), 0, st, v, v16, (long long)B * M, C, C, C);
@@ -1781,7 +1746,6 @@ extern "C" int er_k_flash_attn_hh(const float* q, const float* k, const float* v
     hipError_t e = launch_flash_attn_hh(a, H, B, st);
     hipLaunchKernelGGL(cvt_f16_rows_f32_kernel, dim3(ew_grid((long long)B * N * C)), dim3(ER_WG), 0, st, o16, o, (long long)B * N * C);
     hipError_t e2 = hipStreamSynchronize(st);
-    for (void* p : {(void*)q16, (void*)k16, (void*)v16, (void*)vt, (void*)o16}) hipFree(p);
     HIPRET(e);
     HIPRET(e2);
     return ER_OK;
@@ -1798,14 +1762,14 @@ extern "C" int er_k_flash_attn_f32(const float* q, const float* k, const float* 
     a.qs_b = (long long)N * H * D; a.os_b = a.qs_b; a.ks_b = (long long)M * H * D; a.vs_b = a.ks_b;
     a.qs_h = a.ks_h = a.vs_h = a.os_h = D;
     a.sqrt_d = sqrtf((float)D); a.causal_off = M - N;
-    float *po = nullptr, *pml = nullptr;                   // key-range split of the causal prefill shape (k_flash_attn_f32.h, KSP)
+    DevBuf<float> po, pml;                                 // key-range split of the causal prefill shape (k_flash_attn_f32.h, KSP)
     if (flash32_ksplit(N, H, B, D, causal != 0)) {
-        HIPCHK(hipMalloc(&po, flash32_part_o_floats(B, H, N, D) * 4));
-        HIPCHK(hipMalloc(&pml, flash32_part_ml_floats(B, H, N) * 4));
-        a.part_o = po; a.part_ml = pml;
+        ERCHK(po.ensure(flash32_part_o_floats(B, H, N, D)));
+        ERCHK(pml.ensure(flash32_part_ml_floats(B, H, N)));
+        a.part_o = po.p; a.part_ml = pml.p;
     }
     hipError_t e = launch_flash_attn_f32(a, D, causal != 0, H, B, (hipStream_t)stream);
-    if (po) { hipStreamSynchronize((hipStream_t)stream); hipFree(po); hipFree(pml); }
+    if (po.p) hipStreamSynchronize((hipStream_t)stream);
     HIPRET(e);
     return ER_OK;
 }
@@ -1852,35 +1816,33 @@ extern "C" int er_k_sample_head(const float* logits, const er_decode_params* p, 
                                 int32_t* counter_out, int32_t* unfinished_out, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     const size_t b = (size_t)B;
-    int* sb = nullptr;
-    DecodeParamsDev* dpd = nullptr;
-    long long* ids = nullptr;
-    HIPCHK(hipMalloc(&sb, (7 * b + 8) * sizeof(int)));
-    HIPCHK(hipMalloc(&dpd, sizeof(DecodeParamsDev)));
-    HIPCHK(hipMalloc(&ids, b * (size_t)(step + 1) * sizeof(long long)));
-    std::vector<int> h(7 * b + 8, 0);
+    DevBuf<int> sb;
+    DevBuf<DecodeParamsDev> dpd;
+    DevBuf<long long> ids;
+    ERCHK(sb.ensure(gen_state_ints(b)));
+    ERCHK(dpd.ensure(1));
+    ERCHK(ids.ensure(b * (size_t)(step + 1)));
+    std::vector<int> h(gen_state_ints(b), 0);
+    const GenState hs = gen_state_carve(h.data(), b);      // the same state on the host
     for (size_t i = 0; i < b; ++i) {
-        h[i] = last_tok[i]; h[b + i] = 0; h[2 * b + i] = counter[i]; h[3 * b + i] = step;
-        h[4 * b + i] = unfinished[i]; h[5 * b + i] = -1; h[6 * b + i] = 0;
+        hs.tok[i] = last_tok[i]; hs.counter[i] = counter[i]; hs.ngen[i] = step;
+        hs.unfinished[i] = unfinished[i]; hs.eos_step[i] = -1;
     }
-    h[7 * b] = B;
-    HIPCHK(hipMemcpy(sb, h.data(), h.size() * sizeof(int), hipMemcpyHostToDevice));
-    GenState s{};
-    s.tok = sb; s.pos = sb + b; s.counter = sb + 2 * b; s.ngen = sb + 3 * b; s.unfinished = sb + 4 * b;
-    s.eos_step = sb + 5 * b; s.base_pos = sb + 6 * b; s.n_unfinished = sb + 7 * b; s.error = sb + 7 * b + 1;
+    *hs.n_unfinished = B;
+    HIPCHK(hipMemcpy(sb.p, h.data(), h.size() * sizeof(int), hipMemcpyHostToDevice));
+    const GenState s = gen_state_carve(sb.p, b);
     DecodeParamsDev dp{};
     dp.mode = p->mode; dp.top_k = p->top_k; dp.grammar = p->grammar; dp.max_new = step + 1; dp.min_new = p->min_new_tokens;
     dp.eos = eos; dp.pad = pad; dp.vocab = vocab;
     dp.seed_lo = (unsigned int)(p->seed & 0xffffffffu); dp.seed_hi = (unsigned int)(p->seed >> 32);
-    HIPCHK(hipMemcpy(dpd, &dp, sizeof(dp), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(sample_head_kernel, dim3(B), dim3(ER_WG), sample_head_lds(vocab), st, logits, dpd, s, ids, step + 1);
+    HIPCHK(hipMemcpy(dpd.p, &dp, sizeof(dp), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(sample_head_kernel, dim3(B), dim3(ER_WG), sample_head_lds(vocab), st, logits, dpd.p, s, ids.p, step + 1);
     hipError_t e = hipGetLastError();
     hipError_t e2 = hipStreamSynchronize(st);
     if (e == hipSuccess && e2 == hipSuccess) {
-        hipMemcpy(h.data(), sb, h.size() * sizeof(int), hipMemcpyDeviceToHost);
-        for (size_t i = 0; i < b; ++i) { next_tok[i] = h[i]; counter_out[i] = h[2 * b + i]; unfinished_out[i] = h[4 * b + i]; }
+        hipMemcpy(h.data(), sb.p, h.size() * sizeof(int), hipMemcpyDeviceToHost);
+        for (size_t i = 0; i < b; ++i) { next_tok[i] = hs.tok[i]; counter_out[i] = hs.counter[i]; unfinished_out[i] = hs.unfinished[i]; }
     }
-    hipFree(sb); hipFree(dpd); hipFree(ids);
     HIPRET(e);
     HIPRET(e2);
     return ER_OK;
@@ -1890,11 +1852,10 @@ extern "C" int er_k_sample_head(const float* logits, const er_decode_params* p, 
 extern "C" int er_k_fps(const float* pts, int B, int N, int S, int32_t* idx, void* stream) {
     if (!pts || !idx || B <= 0 || B > 65535 || N <= 0 || S <= 0 || S > N) return fail(ER_ERR_INVALID, "er_k_fps: bad argument");
     hipStream_t st = (hipStream_t)stream;
-    float* dist = nullptr;
-    if (N > FPS_REG_MAX) HIPCHK(hipMalloc((void**)&dist, (size_t)B * N * sizeof(float)));
-    hipError_t e = launch_fps(pts, B, N, S, idx, dist, st);
+    DevBuf<float> dist;
+    if (N > FPS_REG_MAX) ERCHK(dist.ensure((size_t)B * N));
+    hipError_t e = launch_fps(pts, B, N, S, idx, dist.p, st);
     const hipError_t e2 = hipStreamSynchronize(st);
-    if (dist) hipFree(dist);
     if (e != hipSuccess || e2 != hipSuccess) return fail(ER_ERR_HIP, "er_k_fps: %s", hipGetErrorString(e != hipSuccess ? e : e2));
     return ER_OK;
 }

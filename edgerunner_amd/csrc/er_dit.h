@@ -1,5 +1,5 @@
 // DiT image-conditioned front-end behind the C ABI (er_dit_*): included at the end of er_api.hip so it can reuse the prefill
-// building blocks (the GEMM launchers, attention_full, ensure, fail, HIPCHK/HIPRET/ERCHK), the weight table and loader
+// building blocks (the GEMM launchers, attention_full, DevBuf, pick, fail, HIPCHK/HIPRET/ERCHK), the weight table and loader
 // (er_weights.h) and the point encoder helpers.
 // Reference: core/transformer/dit.py (DiT, DiTLayer, TimestepEmbedding) and core/models_dit.py::MDiT.run.
 #pragma once
@@ -35,23 +35,25 @@ struct er_dit_ctx {
     std::vector<ClipLayerW> clip;
     float *clip_cls = nullptr, *clip_patch_w = nullptr, *clip_pos = nullptr, *clip_prew = nullptr, *clip_preb = nullptr;
     int clip_kpad = 0;
-    Buf cpx, ccol, cpatch, cx, ch, cq, ck, cv, catt, cf;
+    DevBuf<float> cpx, ccol, cpatch, cx, ch, cq, ck, cv, catt, cf;   // image encoder scratch
     WeightTable w;                                       // every checkpoint key (dit_weights); w.half_of: the fp16 copies of fast mode
     bool fast = false;                                   // fp16-input MFMA for every Linear (weights stored fp16 too)
-    Buf x, qkv, att, q2, kv2, u, g, sc, tin, temb0, temb1, temb, tsil, tada, gate, t_dev, xin, pred, czero, ctmp;
+    // scratch: grow-only, freed with the context
+    DevBuf<float> x, qkv, att, q2, kv2, u, g, sc, tin, temb0, temb1, temb, tsil, tada, t_dev, xin, pred, czero, ctmp;
     // fp16 mode: fp16 copies of the activations that feed a Linear, written by their producers (k_gemm.h, gemm_hh_mfma_kernel)
-    Buf x16, att16, g16;
+    DevBuf<_Float16> x16, att16, g16;
     // ... and q / k / v in fp16 with V transposed, for the LDS-DMA attention (k_flash_attn.h, flash_attn_hh_kernel)
-    Buf qkv16, vt16, q2_16, k2_16, v2tmp16, v2t16;
-    Buf gates;                             // [layer][2][B][C]: gate_msa / gate_mlp rows of every layer (one launch per forward)
-    const float** sst_ptrs = nullptr;      // device array of the layers' scale_shift_table pointers
+    DevBuf<_Float16> qkv16, vt16, q2_16, k2_16, v2tmp16, v2t16;
+    DevBuf<float> gates;                   // [layer][2][B][C]: gate_msa / gate_mlp rows of every layer (one launch per forward)
+    DevBuf<const float*> sst_ptrs;         // the layers' scale_shift_table pointers
     int kv2_mp = 0;                        // padded key count of the cross-attention V^T rows
     bool geglu_perm_valid = false;
     int pred_type = ER_PRED_V_PREDICTION;  // what the DiT predicts (er_dit_set_prediction_type): the sampler's DDIM update and the loss target
     // the reference's frozen point encoder (MDiT.point_encoder, core/models_dit.py:68-75), after er_dit_attach_point_encoder only
     bool has_pe = false;
     PointEnc pe;                           // its point_encoder.* keys join `w` when it is attached
-    Buf lcoef, lpart;                      // er_dit_loss: [sa | sb | w] per sample, partial sums (doubles)
+    DevBuf<float> lcoef;                   // er_dit_loss: [sa | sb | w] per sample
+    DevBuf<double> lpart;                  // ... and its partial sums
 };
 
 // every checkpoint key of the DiT (+ CLIP) context; fp16 mode keeps an fp16 copy of the Linear and patch-conv weights (GEMM operands)
@@ -131,18 +133,11 @@ extern "C" int er_dit_create(const er_dit_config* cfg, int device, er_dit_ctx** 
     return ER_OK;
 }
 
+// the buffers and weight blocks are members: deleting the context frees them, once the device is idle
 extern "C" int er_dit_destroy(er_dit_ctx* c) {
     if (!c) return ER_OK;
     hipSetDevice(c->device);
     hipDeviceSynchronize();
-    weights_free(c->w);
-    for (Buf* b : {&c->cpx, &c->ccol, &c->cpatch, &c->cx, &c->ch, &c->cq, &c->ck, &c->cv, &c->catt, &c->cf})
-        if (b->p) hipFree(b->p);
-    for (Buf* b : {&c->x, &c->qkv, &c->att, &c->q2, &c->kv2, &c->u, &c->g, &c->sc, &c->tin, &c->temb0, &c->temb1, &c->temb,
-                   &c->tsil, &c->tada, &c->gate, &c->t_dev, &c->xin, &c->pred, &c->czero, &c->ctmp, &c->x16, &c->att16, &c->g16,
-                   &c->qkv16, &c->vt16, &c->q2_16, &c->k2_16, &c->v2tmp16, &c->v2t16, &c->gates, &c->lcoef, &c->lpart})
-        if (b->p) hipFree(b->p);
-    pe_free(c->pe);
     if (c->own_stream) hipStreamDestroy(c->own_stream);
     delete c;
     return ER_OK;
@@ -184,7 +179,7 @@ extern "C" int er_dit_point_latent(er_dit_ctx* c, const float* points, int B, in
     if (!c->has_pe) return fail(ER_ERR_UNSUPPORTED, "er_dit_point_latent: no point encoder attached (er_dit_attach_point_encoder)");
     ERCHK(er_dit_finalize_weights(c));
     HIPCHK(hipSetDevice(c->device));
-    return pe_latent(c->pe, points, B, n_points, latent_out, stream ? (hipStream_t)stream : c->own_stream, "er_dit_point_latent");
+    return pe_latent(c->pe, points, B, n_points, latent_out, pick(c, stream), "er_dit_point_latent");
 }
 
 extern "C" int er_dit_set_point_encoder_mode(er_dit_ctx* c, int mode) {
@@ -264,9 +259,9 @@ extern "C" int er_dit_project_cond(er_dit_ctx* c, const float* clip_hidden, int 
     if (!c || !clip_hidden || !cond_out || B <= 0 || M <= 0) return fail(ER_ERR_INVALID, "er_dit_project_cond: bad argument");
     ERCHK(er_dit_finalize_weights(c));
     HIPCHK(hipSetDevice(c->device));
-    hipStream_t st = stream ? (hipStream_t)stream : c->own_stream;
+    hipStream_t st = pick(c, stream);
     const int C = c->cfg.hidden_dim;
-    ERCHK(ensure(c->ctmp, (size_t)B * M * C));
+    ERCHK(c->ctmp.ensure((size_t)B * M * C));
     HIPRET(dlin(c, clip_hidden, c->cfg.clip_dim, c->projc_w, c->projc_b, c->ctmp.p, C, B * M, C, c->cfg.clip_dim, nullptr, 0, nullptr, 1, st));
     HIPRET(launch_layernorm(c->ctmp.p, c->normc_w, c->normc_b, cond_out, B * M, C, C, C, 1e-5f, st));
     return ER_OK;
@@ -277,21 +272,21 @@ extern "C" int er_dit_encode_image(er_dit_ctx* c, const float* images, int B, in
     if (c->cfg.clip_layers <= 0) return fail(ER_ERR_UNSUPPORTED, "this context was created without the image encoder (clip_layers = 0)");
     ERCHK(er_dit_finalize_weights(c));
     HIPCHK(hipSetDevice(c->device));
-    hipStream_t st = stream ? (hipStream_t)stream : c->own_stream;
+    hipStream_t st = pick(c, stream);
     const er_dit_config& g = c->cfg;
     const int W = g.clip_dim, S = g.clip_image_size, P = g.clip_patch, G = S / P, NP = G * G, NT = NP + 1, H = g.clip_heads,
               D = W / H, F = g.clip_mlp_dim, R = B * NT, ldS = (NT + 15) / 16 * 16;
-    ERCHK(ensure(c->cpx, (size_t)B * 3 * S * S));
-    ERCHK(ensure(c->ccol, (size_t)B * NP * c->clip_kpad));
-    ERCHK(ensure(c->cpatch, (size_t)B * NP * W));
-    ERCHK(ensure(c->cx, (size_t)R * W));
-    ERCHK(ensure(c->ch, (size_t)R * W));
-    ERCHK(ensure(c->cq, (size_t)R * W));
-    ERCHK(ensure(c->ck, (size_t)R * W));
-    ERCHK(ensure(c->cv, (size_t)R * W));
-    ERCHK(ensure(c->catt, (size_t)R * W));
-    ERCHK(ensure(c->cf, (size_t)R * F));
-    ERCHK(ensure(c->sc, (size_t)H * NT * ldS));
+    ERCHK(c->cpx.ensure((size_t)B * 3 * S * S));
+    ERCHK(c->ccol.ensure((size_t)B * NP * c->clip_kpad));
+    ERCHK(c->cpatch.ensure((size_t)B * NP * W));
+    ERCHK(c->cx.ensure((size_t)R * W));
+    ERCHK(c->ch.ensure((size_t)R * W));
+    ERCHK(c->cq.ensure((size_t)R * W));
+    ERCHK(c->ck.ensure((size_t)R * W));
+    ERCHK(c->cv.ensure((size_t)R * W));
+    ERCHK(c->catt.ensure((size_t)R * W));
+    ERCHK(c->cf.ensure((size_t)R * F));
+    ERCHK(c->sc.ensure((size_t)H * NT * ldS));
     auto blocks = [](long long n) { return dim3((unsigned)((n + 255) / 256)); };
     hipLaunchKernelGGL(clip_preprocess_kernel, blocks((long long)B * 3 * S * S), dim3(256), 0, st, images, c->cpx.p, B, Himg, Wimg, S);
     HIPRET(hipGetLastError());
@@ -347,10 +342,8 @@ static int dit_build_geglu_perm(er_dit_ctx* c, hipStream_t st) {
         auto it = c->w.half_of.find(L.ff0_w);
         if (it == c->w.half_of.end()) return fail(ER_ERR_INVALID, "dit: no fp16 copy of ff.net.0.proj");
         if (!L.ff0_p16) {
-            HIPCHK(hipMalloc((void**)&L.ff0_p16, (size_t)2 * F * C * sizeof(_Float16)));
-            c->w.owned.push_back(L.ff0_p16);
-            HIPCHK(hipMalloc((void**)&L.ff0_bp, (size_t)2 * F * sizeof(float)));
-            c->w.owned.push_back(L.ff0_bp);
+            ERCHK(c->w.alloc(&L.ff0_p16, (size_t)2 * F * C));
+            ERCHK(c->w.alloc(&L.ff0_bp, (size_t)2 * F));
         }
         hipLaunchKernelGGL(geglu_permute_kernel, dim3(2 * F), dim3(ER_WG), 0, st, it->second, L.ff0_b, L.ff0_p16, L.ff0_bp, F, C);
         HIPRET(hipGetLastError());
@@ -379,12 +372,12 @@ static hipError_t dlin16(er_dit_ctx* c, const _Float16* A16, int lda, const floa
 // t_emb / t_adaln for B rows with timesteps already on the device (t_dev [B])
 static int dit_time_embed(er_dit_ctx* c, int B, hipStream_t st) {
     const int C = c->cfg.hidden_dim;
-    ERCHK(ensure(c->tin, (size_t)B * 256));
-    ERCHK(ensure(c->temb0, (size_t)B * C));
-    ERCHK(ensure(c->temb1, (size_t)B * C));
-    ERCHK(ensure(c->temb, (size_t)B * C));
-    ERCHK(ensure(c->tsil, (size_t)B * C));
-    ERCHK(ensure(c->tada, (size_t)B * 6 * C));
+    ERCHK(c->tin.ensure((size_t)B * 256));
+    ERCHK(c->temb0.ensure((size_t)B * C));
+    ERCHK(c->temb1.ensure((size_t)B * C));
+    ERCHK(c->temb.ensure((size_t)B * C));
+    ERCHK(c->tsil.ensure((size_t)B * C));
+    ERCHK(c->tada.ensure((size_t)B * 6 * C));
     hipLaunchKernelGGL(timestep_embed_kernel, dim3((B * 128 + 255) / 256), dim3(256), 0, st, c->t_dev.p, c->tin.p, B, 128);
     HIPRET(hipGetLastError());
     HIPRET(dlin(c, c->tin.p, 256, c->tp1_w, c->tp1_b, c->temb0.p, C, B, C, 256, nullptr, 0, nullptr, 1, st));
@@ -401,7 +394,7 @@ static int dit_time_embed(er_dit_ctx* c, int B, hipStream_t st) {
 // kv2 layout [layer][2][B*M][C]
 static int dit_cross_kv(er_dit_ctx* c, const float* cond, int B, int M, hipStream_t st) {
     const int C = c->cfg.hidden_dim, nl = c->cfg.num_layers;
-    ERCHK(ensure(c->kv2, (size_t)nl * 2 * B * M * C));
+    ERCHK(c->kv2.ensure((size_t)nl * 2 * B * M * C));
     for (int l = 0; l < nl; ++l) {
         const DitLayerW& L = c->layers[l];
         float* k2 = c->kv2.p + ((size_t)l * 2) * B * M * C;
@@ -412,15 +405,15 @@ static int dit_cross_kv(er_dit_ctx* c, const float* cond, int B, int M, hipStrea
     if (c->fast && C / c->cfg.num_heads == FA_D) {      // fp16 K and V^T (zero-padded to a multiple of 64 keys) for flash_attn_hh_kernel
         const int H = c->cfg.num_heads, Mp = (M + 63) / 64 * 64;
         c->kv2_mp = Mp;
-        ERCHK(ensure(c->k2_16, (size_t)nl * B * M * C / 2 + 8));
-        ERCHK(ensure(c->v2tmp16, (size_t)B * M * C / 2 + 8));
-        ERCHK(ensure(c->v2t16, (size_t)nl * B * H * 64 * Mp / 2 + 8));
+        ERCHK(c->k2_16.ensure((size_t)nl * B * M * C + F16_TAIL));
+        ERCHK(c->v2tmp16.ensure((size_t)B * M * C + F16_TAIL));
+        ERCHK(c->v2t16.ensure((size_t)nl * B * H * 64 * Mp + F16_TAIL));
         for (int l = 0; l < nl; ++l) {
             const float* k2 = c->kv2.p + ((size_t)l * 2) * B * M * C;
             const float* v2 = k2 + (size_t)B * M * C;
-            _Float16* k16 = reinterpret_cast<_Float16*>(c->k2_16.p) + (size_t)l * B * M * C;
-            _Float16* vtmp = reinterpret_cast<_Float16*>(c->v2tmp16.p);
-            _Float16* vt = reinterpret_cast<_Float16*>(c->v2t16.p) + (size_t)l * B * H * 64 * Mp;
+            _Float16* k16 = c->k2_16.p + (size_t)l * B * M * C;
+            _Float16* vtmp = c->v2tmp16.p;
+            _Float16* vt = c->v2t16.p + (size_t)l * B * H * 64 * Mp;
             hipLaunchKernelGGL(cvt_rows_f16_kernel, dim3(ew_grid((long long)B * M * C)), dim3(ER_WG), 0, st, k2, k16, (long long)B * M, C, C, C);
             hipLaunchKernelGGL(cvt_rows_f16_kernel, dim3(ew_grid((long long)B * M * C)), dim3(ER_WG), 0, st, v2, vtmp, (long long)B * M, C, C, C);
             hipLaunchKernelGGL(transpose_v_f16_kernel, dim3(Mp / 64, H, B), dim3(ER_WG), 0, st, vtmp, vt, M, Mp, C, (long long)M * C);
@@ -436,49 +429,50 @@ static int dit_forward_impl(er_dit_ctx* c, const float* xin, int B, int M, float
     const int C = g.hidden_dim, N = g.latent_size, H = g.num_heads, D = C / H, LD = g.latent_dim;
     const int R = B * N;
     const int ldS = (N + 15) / 16 * 16;
-    ERCHK(ensure(c->x, (size_t)R * C));
-    ERCHK(ensure(c->qkv, (size_t)R * 3 * C));
-    ERCHK(ensure(c->att, (size_t)R * C));
-    ERCHK(ensure(c->q2, (size_t)R * C));
-    ERCHK(ensure(c->u, (size_t)R * 8 * C));
-    ERCHK(ensure(c->g, (size_t)R * 4 * C));
+    ERCHK(c->x.ensure((size_t)R * C));
+    ERCHK(c->qkv.ensure((size_t)R * 3 * C));
+    ERCHK(c->att.ensure((size_t)R * C));
+    ERCHK(c->q2.ensure((size_t)R * C));
+    ERCHK(c->u.ensure((size_t)R * 8 * C));
+    ERCHK(c->g.ensure((size_t)R * 4 * C));
     // fp16 mode: fused attention on the fp16 matrix cores (no score matrix in HBM); ER_DIT_NO_FLASH=1 keeps the
     // materialised fp32 scores path for A/B measurements
     static const bool no_flash = getenv("ER_DIT_NO_FLASH") != nullptr;
     const bool flash = c->fast && D == FA_D && !no_flash;
-    if (!flash) ERCHK(ensure(c->sc, (size_t)H * N * ldS));
-    ERCHK(ensure(c->gates, (size_t)g.num_layers * 2 * B * C));
-    if (!c->sst_ptrs) {
+    if (!flash) ERCHK(c->sc.ensure((size_t)H * N * ldS));
+    ERCHK(c->gates.ensure((size_t)g.num_layers * 2 * B * C));
+    if (!c->sst_ptrs.p) {
         std::vector<const float*> hp;
         for (auto& L : c->layers) hp.push_back(L.sst);
-        HIPCHK(hipMalloc((void**)&c->sst_ptrs, hp.size() * sizeof(float*)));
-        c->w.owned.push_back((void*)c->sst_ptrs);
-        HIPCHK(hipMemcpy((void*)c->sst_ptrs, hp.data(), hp.size() * sizeof(float*), hipMemcpyHostToDevice));
+        DevBuf<const float*> d;
+        ERCHK(d.ensure(hp.size()));
+        HIPCHK(hipMemcpy(d.p, hp.data(), hp.size() * sizeof(float*), hipMemcpyHostToDevice));
+        c->sst_ptrs = std::move(d);        // only a filled table is kept
     }
     // fp16 activations for the LDS-DMA GEMM (all K of this path are multiples of 64 except none: C = 1024, 4C = 4096)
     // ... and the LDS-DMA attention wants whole 64-row tiles of latent tokens and cross K / V^T prepared (zero-padded) for THIS
     // condition length; any other shape keeps the fp32-operand fused attention + register-staged GEMMs below (x16 / att16 null)
     const bool hh = flash && C % 64 == 0 && N % 64 == 0 && c->kv2_mp == (M + 63) / 64 * 64;
     if (hh) {
-        ERCHK(ensure(c->x16, (size_t)R * C / 2 + 8));
-        ERCHK(ensure(c->att16, (size_t)R * C / 2 + 8));
-        ERCHK(ensure(c->g16, (size_t)R * 4 * C / 2 + 8));
+        ERCHK(c->x16.ensure((size_t)R * C + F16_TAIL));
+        ERCHK(c->att16.ensure((size_t)R * C + F16_TAIL));
+        ERCHK(c->g16.ensure((size_t)R * 4 * C + F16_TAIL));
     }
-    _Float16* x16 = hh ? reinterpret_cast<_Float16*>(c->x16.p) : nullptr;
-    _Float16* att16 = hh ? reinterpret_cast<_Float16*>(c->att16.p) : nullptr;
-    _Float16* g16 = hh ? reinterpret_cast<_Float16*>(c->g16.p) : nullptr;
+    _Float16* x16 = hh ? c->x16.p : nullptr;
+    _Float16* att16 = hh ? c->att16.p : nullptr;
+    _Float16* g16 = hh ? c->g16.p : nullptr;
     if (hh) ERCHK(dit_build_geglu_perm(c, st));
     if (hh) {
-        ERCHK(ensure(c->qkv16, (size_t)R * 3 * C / 2 + 8));
-        ERCHK(ensure(c->vt16, (size_t)R * C / 2 + 8));
-        ERCHK(ensure(c->q2_16, (size_t)R * C / 2 + 8));
+        ERCHK(c->qkv16.ensure((size_t)R * 3 * C + F16_TAIL));
+        ERCHK(c->vt16.ensure((size_t)R * C + F16_TAIL));
+        ERCHK(c->q2_16.ensure((size_t)R * C + F16_TAIL));
     }
-    _Float16* qkv16 = hh ? reinterpret_cast<_Float16*>(c->qkv16.p) : nullptr;
-    _Float16* vt16 = hh ? reinterpret_cast<_Float16*>(c->vt16.p) : nullptr;
-    _Float16* q2_16 = hh ? reinterpret_cast<_Float16*>(c->q2_16.p) : nullptr;
+    _Float16* qkv16 = hh ? c->qkv16.p : nullptr;
+    _Float16* vt16 = hh ? c->vt16.p : nullptr;
+    _Float16* q2_16 = hh ? c->q2_16.p : nullptr;
     {
         const long long ng = (long long)g.num_layers * 2 * B * C;
-        hipLaunchKernelGGL(adaln_gate_all_kernel, dim3((unsigned)((ng + 255) / 256)), dim3(256), 0, st, c->sst_ptrs, tada, c->gates.p,
+        hipLaunchKernelGGL(adaln_gate_all_kernel, dim3((unsigned)((ng + 255) / 256)), dim3(256), 0, st, c->sst_ptrs.p, tada, c->gates.p,
                            g.num_layers, B, C);
         HIPRET(hipGetLastError());
     }
@@ -531,8 +525,8 @@ static int dit_forward_impl(er_dit_ctx* c, const float* xin, int B, int M, float
         if (hh) {
             const int Mp = c->kv2_mp;
             FlashHArgs fh{};
-            fh.Q = q2_16; fh.K = reinterpret_cast<const _Float16*>(c->k2_16.p) + (size_t)l * B * M * C;
-            fh.Vt = reinterpret_cast<const _Float16*>(c->v2t16.p) + (size_t)l * B * H * 64 * Mp; fh.O16 = att16; fh.N = N; fh.M = M;
+            fh.Q = q2_16; fh.K = c->k2_16.p + (size_t)l * B * M * C;
+            fh.Vt = c->v2t16.p + (size_t)l * B * H * 64 * Mp; fh.O16 = att16; fh.N = N; fh.M = M;
             fh.ldq = fh.ldk = C; fh.ldvt = Mp; fh.ldo = C;
             fh.qs_b = (long long)N * C; fh.ks_b = (long long)M * C; fh.vts_h = 64LL * Mp; fh.vts_b = (long long)H * 64 * Mp; fh.os_b = (long long)N * C;
             fh.head_stride = D; fh.scale = 1.0f / sqrtf((float)D);
@@ -579,8 +573,8 @@ extern "C" int er_dit_forward(er_dit_ctx* c, const float* x, const float* cond, 
     if (!c || !x || !cond || !t_host || !out || B <= 0 || M <= 0) return fail(ER_ERR_INVALID, "er_dit_forward: bad argument");
     ERCHK(er_dit_finalize_weights(c));
     HIPCHK(hipSetDevice(c->device));
-    hipStream_t st = stream ? (hipStream_t)stream : c->own_stream;
-    ERCHK(ensure(c->t_dev, (size_t)B));
+    hipStream_t st = pick(c, stream);
+    ERCHK(c->t_dev.ensure((size_t)B));
     HIPCHK(hipMemcpyAsync(c->t_dev.p, t_host, B * sizeof(float), hipMemcpyHostToDevice, st));
     HIPCHK(hipStreamSynchronize(st));
     ERCHK(dit_cross_kv(c, cond, B, M, st));
@@ -597,7 +591,7 @@ extern "C" int er_dit_sample(er_dit_ctx* c, const float* cond, int B, int M, flo
                     (steps - 1) * (1000 / steps) + 1);
     ERCHK(er_dit_finalize_weights(c));
     HIPCHK(hipSetDevice(c->device));
-    hipStream_t st = stream ? (hipStream_t)stream : c->own_stream;
+    hipStream_t st = pick(c, stream);
     const er_dit_config& g = c->cfg;
     const int C = g.hidden_dim, N = g.latent_size, LD = g.latent_dim;
     const size_t nlat = (size_t)B * N * LD;
@@ -606,18 +600,18 @@ extern "C" int er_dit_sample(er_dit_ctx* c, const float* cond, int B, int M, flo
     const std::vector<float> ac = dit_alphas_cumprod();
     const int ratio = T / steps;
     // CFG batch: rows [0,B) = zero condition, rows [B,2B) = cond                   models_dit.py:211
-    ERCHK(ensure(c->czero, (size_t)2 * B * M * C));
+    ERCHK(c->czero.ensure((size_t)2 * B * M * C));
     HIPCHK(hipMemsetAsync(c->czero.p, 0, (size_t)B * M * C * 4, st));
     HIPCHK(hipMemcpyAsync(c->czero.p + (size_t)B * M * C, cond, (size_t)B * M * C * 4, hipMemcpyDeviceToDevice, st));
     ERCHK(dit_cross_kv(c, c->czero.p, 2 * B, M, st));
-    ERCHK(ensure(c->xin, 2 * nlat));
-    ERCHK(ensure(c->pred, 2 * nlat));
+    ERCHK(c->xin.ensure(2 * nlat));
+    ERCHK(c->pred.ensure(2 * nlat));
     // time embeddings of ALL the steps that will run, in one pass (round 6): the timesteps are known up front, so the three tiny Linears
     // (2 B rows each, ~13 us per launch on the 64 x 64-tile GEMM), the two SiLUs and the sinusoid run once over nrun x 2 B rows instead
     // of once per step, and the loop needs no host -> device copy and no stream synchronisation any more.  Rows are independent in every
     // one of these kernels: the embeddings are bit-identical to the per-step ones.
     const int nrun = steps - init_step, B2 = 2 * B;
-    ERCHK(ensure(c->t_dev, (size_t)nrun * B2));
+    ERCHK(c->t_dev.ensure((size_t)nrun * B2));
     {
         std::vector<float> th((size_t)nrun * B2);
         for (int k = 0; k < nrun; ++k)
@@ -655,15 +649,15 @@ extern "C" int er_dit_loss(er_dit_ctx* c, const float* latents, const float* noi
     ERCHK(dit_loss_coefs(timesteps, B, c->pred_type, snr_gamma, coef));
     ERCHK(er_dit_finalize_weights(c));
     HIPCHK(hipSetDevice(c->device));
-    hipStream_t st = stream ? (hipStream_t)stream : c->own_stream;
+    hipStream_t st = pick(c, stream);
     const long long n = (long long)c->cfg.latent_size * c->cfg.latent_dim;
     if ((long long)B * c->cfg.latent_size * 8 * c->cfg.hidden_dim > 0x7fffffffLL)      // the widest DiT activation (ff.net.0: 8 C per row)
         return fail(ER_ERR_CAPACITY, "er_dit_loss: batch %d too large for 32-bit row indexing", B);
     const int chunks = dit_loss_chunks(n);
-    ERCHK(ensure(c->lcoef, (size_t)3 * B));
-    ERCHK(ensure(c->lpart, (size_t)2 * B * chunks));
-    ERCHK(ensure(c->t_dev, (size_t)B));
-    ERCHK(ensure(c->xin, (size_t)B * n));
+    ERCHK(c->lcoef.ensure((size_t)3 * B));
+    ERCHK(c->lpart.ensure((size_t)B * chunks));
+    ERCHK(c->t_dev.ensure((size_t)B));
+    ERCHK(c->xin.ensure((size_t)B * n));
     std::vector<float> th(B);
     for (int b = 0; b < B; ++b) th[b] = (float)timesteps[b];
     HIPCHK(hipMemcpyAsync(c->lcoef.p, coef.data(), coef.size() * sizeof(float), hipMemcpyHostToDevice, st));
@@ -672,7 +666,7 @@ extern "C" int er_dit_loss(er_dit_ctx* c, const float* latents, const float* noi
     const float *sa = c->lcoef.p, *sb = sa + B, *w = sb + B;
     float* pred = pred_out;
     if (!pred) {
-        ERCHK(ensure(c->pred, (size_t)B * n));
+        ERCHK(c->pred.ensure((size_t)B * n));
         pred = c->pred.p;
     }
     // noisy_latents = add_noise(nan_to_num(latents), noise, t); model_pred = dit(noisy_latents, cond, t)     models_dit.py:143-155
@@ -680,7 +674,7 @@ extern "C" int er_dit_loss(er_dit_ctx* c, const float* latents, const float* noi
     ERCHK(dit_cross_kv(c, cond, B, M, st));
     ERCHK(dit_time_embed(c, B, st));
     if (dit_forward_impl(c, c->xin.p, B, M, pred, c->temb.p, c->tada.p, st) < 0) return -1;
-    HIPRET(launch_dit_loss(pred, latents, noise, sa, sb, w, B, n, c->pred_type, reinterpret_cast<double*>(c->lpart.p), mse_out, loss_out, st));
+    HIPRET(launch_dit_loss(pred, latents, noise, sa, sb, w, B, n, c->pred_type, c->lpart.p, mse_out, loss_out, st));
     return ER_OK;
 }
 
@@ -695,18 +689,13 @@ extern "C" int er_k_dit_loss(const float* pred, const float* x0, const float* ep
     ERCHK(dit_loss_coefs(timesteps, B, pred_type, snr_gamma, coef));
     hipStream_t st = (hipStream_t)stream;
     const int chunks = dit_loss_chunks(n);
-    float* dcoef = nullptr;
-    double* part = nullptr;
-    HIPCHK(hipMalloc((void**)&dcoef, coef.size() * sizeof(float)));
-    if (hipMalloc((void**)&part, (size_t)B * chunks * sizeof(double)) != hipSuccess) {
-        hipFree(dcoef);
-        return fail(ER_ERR_HIP, "er_k_dit_loss: hipMalloc failed");
-    }
-    hipError_t e = hipMemcpyAsync(dcoef, coef.data(), coef.size() * sizeof(float), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = launch_dit_loss(pred, x0, eps, dcoef, dcoef + B, dcoef + 2 * B, B, n, pred_type, part, mse_out, loss_out, st);
+    DevBuf<float> dcoef;
+    DevBuf<double> part;
+    ERCHK(dcoef.ensure(coef.size()));
+    ERCHK(part.ensure((size_t)B * chunks));
+    hipError_t e = hipMemcpyAsync(dcoef.p, coef.data(), coef.size() * sizeof(float), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = launch_dit_loss(pred, x0, eps, dcoef.p, dcoef.p + B, dcoef.p + 2 * B, B, n, pred_type, part.p, mse_out, loss_out, st);
     const hipError_t e2 = hipStreamSynchronize(st);
-    hipFree(dcoef);
-    hipFree(part);
     if (e != hipSuccess || e2 != hipSuccess) return fail(ER_ERR_HIP, "er_k_dit_loss: %s", hipGetErrorString(e != hipSuccess ? e : e2));
     return ER_OK;
 }

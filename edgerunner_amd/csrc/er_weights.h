@@ -1,5 +1,5 @@
 // Checkpoint weights of a context (er_ctx, er_dit_ctx): every state_dict key is registered once, with where and how it is
-// stored, and one loader serves them all.  Included by er_api.hip after Buf / ensure / fail / HIPCHK.
+// stored, and one loader serves them all.  The table owns every block it allocates.  Included by er_api.hip after er_devbuf.h.
 #pragma once
 
 struct WeightEntry {
@@ -21,9 +21,19 @@ struct WeightEntry {
 struct WeightTable {
     std::map<std::string, WeightEntry> keys;
     std::map<const float*, _Float16*> half_of;   // fp32 block -> its fp16 copy (fp16 mode, entries with half())
-    std::vector<void*> owned;                    // every hipMalloc'd weight block (derived copies included)
-    Buf stage;                                   // upload of one host tensor: grow-only, freed by weights_finalize
+    std::vector<DevBuf<char>> owned;             // every weight block (derived copies included); the entries and weight structs hold views
+    DevBuf<char> stage;                          // upload of one host tensor: grow-only, freed by weights_finalize
     bool fp16 = false;
+
+    // a block of n T that lives as long as the table
+    template <typename T>
+    int alloc(T** p, size_t n) {
+        DevBuf<char> b;
+        ERCHK(b.ensure(n * sizeof(T)));
+        *p = reinterpret_cast<T*>(b.p);
+        owned.push_back(std::move(b));
+        return 0;
+    }
 
     // a block of its own; (re)registering a key resets it to "not loaded"
     WeightEntry& add(const std::string& key, float** dst, size_t n) {
@@ -63,8 +73,7 @@ __global__ void cvt_weights_kernel(const void* src, int dtype, float* dst32, _Fl
 template <typename T>
 static int weights_alloc(WeightTable& t, T** p, size_t n) {   // once per block, zeroed
     if (*p) return 0;
-    HIPCHK(hipMalloc((void**)p, n * sizeof(T)));
-    t.owned.push_back(*p);
+    ERCHK(t.alloc(p, n));
     HIPCHK(hipMemset(*p, 0, n * sizeof(T)));
     return 0;
 }
@@ -84,7 +93,7 @@ static int weights_load(WeightTable& t, hipStream_t st, const char* who, const s
     const void* src = data;
     if (!on_device) {
         const size_t bytes = n * (dtype == ER_F32 ? 4 : 2);
-        ERCHK(ensure(t.stage, (bytes + 3) / 4));
+        ERCHK(t.stage.ensure((bytes + 3) / 4 * 4));      // whole 32-bit words
         HIPCHK(hipMemcpy(t.stage.p, data, bytes, hipMemcpyHostToDevice));
         src = t.stage.p;
     }
@@ -111,17 +120,8 @@ static const char* weights_missing(const WeightTable& t) {
     return nullptr;
 }
 
-static void weights_free(WeightTable& t) {
-    for (void* p : t.owned) hipFree(p);
-    if (t.stage.p) hipFree(t.stage.p);
-}
-
 static int weights_finalize(WeightTable& t) {
     if (const char* k = weights_missing(t)) return fail(ER_ERR_MISSING, "tensor '%s' was never loaded", k);
-    if (t.stage.p) {                      // checkpoint complete: the upload staging block (up to one tensor) is not needed any more
-        hipFree(t.stage.p);
-        t.stage.p = nullptr;
-        t.stage.n = 0;
-    }
+    t.stage.reset();                      // checkpoint complete: the upload staging block (up to one tensor) is not needed any more
     return 0;
 }
