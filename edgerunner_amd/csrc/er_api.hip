@@ -30,6 +30,7 @@
 #include "k_flash_attn.h"
 #include "k_flash_attn_f32.h"
 #include "k_fps.h"
+#include "k_fidelity.h"
 #include "meto_decode.h"
 #include "meto_encode.h"
 
@@ -1857,6 +1858,78 @@ extern "C" int er_k_fps(const float* pts, int B, int N, int S, int32_t* idx, voi
     hipError_t e = launch_fps(pts, B, N, S, idx, dist.p, st);
     const hipError_t e2 = hipStreamSynchronize(st);
     if (e != hipSuccess || e2 != hipSuccess) return fail(ER_ERR_HIP, "er_k_fps: %s", hipGetErrorString(e != hipSuccess ? e : e2));
+    return ER_OK;
+}
+
+// ------------------------------------------------------------------------------------ reconstruction fidelity (k_fidelity.h)
+extern "C" int er_k_nn_dist2(const float* a, const float* b, int B, int Na, int Nb, float* d2, int32_t* idx, void* stream) {
+    if (!a || !b || !d2 || B <= 0 || B > 65535 || Na <= 0 || Nb <= 0 || Na > FID_MAX_N || Nb > FID_MAX_N)
+        return fail(ER_ERR_INVALID, "er_k_nn_dist2: bad argument");
+    hipStream_t st = (hipStream_t)stream;
+    DevBuf<unsigned long long> packed;
+    ERCHK(packed.ensure((size_t)B * Na));
+    const hipError_t e = launch_nn_dist2(a, b, B, Na, Nb, d2, idx, packed.p, st);
+    const hipError_t e2 = hipStreamSynchronize(st);
+    if (e != hipSuccess || e2 != hipSuccess) return fail(ER_ERR_HIP, "er_k_nn_dist2: %s", hipGetErrorString(e != hipSuccess ? e : e2));
+    return ER_OK;
+}
+
+extern "C" int er_k_surface_sample(const float* vertices, const int32_t* faces, const int32_t* vert_offset, const int32_t* face_offset,
+                                   int B, int n, uint64_t seed, const uint32_t* stream_ids, float* points, int32_t* face_out,
+                                   void* stream) {
+    if (!vertices || !faces || !vert_offset || !face_offset || !points || B <= 0 || B > 65535 || n <= 0 || n > FID_MAX_N)
+        return fail(ER_ERR_INVALID, "er_k_surface_sample: bad argument");
+    std::vector<FidMesh> hm((size_t)B);
+    int max_faces = 0;
+    for (int m = 0; m < B; ++m) {
+        const int v0 = vert_offset[m], nv = vert_offset[m + 1] - v0, f0 = face_offset[m], nf = face_offset[m + 1] - f0;
+        if (v0 < 0 || nv < 0 || f0 < 0 || nf < 0) return fail(ER_ERR_INVALID, "er_k_surface_sample: offsets of mesh %d are not ascending", m);
+        if (nf == 0) return fail(ER_ERR_INVALID, "er_k_surface_sample: mesh %d has no faces", m);
+        if (nf > FID_MAX_FACES) return fail(ER_ERR_INVALID, "er_k_surface_sample: mesh %d has %d faces (at most %d)", m, nf, FID_MAX_FACES);
+        hm[m] = FidMesh{v0, nv, f0, nf, stream_ids ? stream_ids[m] : (unsigned)m};
+        max_faces = std::max(max_faces, nf);
+    }
+    hipStream_t st = (hipStream_t)stream;
+    DevBuf<FidMesh> meshes;
+    DevBuf<unsigned long long> cum, total;
+    DevBuf<int> bad;
+    ERCHK(meshes.ensure((size_t)B));
+    ERCHK(cum.ensure((size_t)face_offset[B]));
+    ERCHK(total.ensure((size_t)B));
+    ERCHK(bad.ensure((size_t)B));
+    HIPCHK(hipMemcpyAsync(meshes.p, hm.data(), hm.size() * sizeof(FidMesh), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(bad.p, 0, (size_t)B * sizeof(int), st));
+    const unsigned chunks = (unsigned)std::min((max_faces + ER_WG - 1) / ER_WG, 1024);
+    hipLaunchKernelGGL(face_weight_kernel, dim3(chunks, B), dim3(ER_WG), 0, st, vertices, faces, meshes.p, cum.p, bad.p);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(face_scan_kernel, dim3(B), dim3(ER_WG), 0, st, cum.p, meshes.p, total.p);
+    HIPCHK(hipGetLastError());
+    // the one blocking point: no vertex is read through an unchecked index, and no sample is drawn from a mesh without area
+    std::vector<unsigned long long> htotal((size_t)B);
+    std::vector<int> hbad((size_t)B);
+    HIPCHK(hipMemcpyAsync(htotal.data(), total.p, htotal.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(hbad.data(), bad.p, hbad.size() * sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    for (int m = 0; m < B; ++m) {
+        if (hbad[m]) return fail(ER_ERR_INVALID, "er_k_surface_sample: mesh %d has a face index outside its %d vertices", m, hm[m].nv);
+        if (htotal[m] == 0) return fail(ER_ERR_INVALID, "er_k_surface_sample: mesh %d has zero area", m);
+    }
+    hipLaunchKernelGGL(surface_sample_kernel, dim3((n + ER_WG - 1) / ER_WG, B), dim3(ER_WG), 0, st, vertices, faces, meshes.p, cum.p,
+                       total.p, n, (unsigned)(seed & 0xffffffffu), (unsigned)(seed >> 32), points, face_out);
+    const hipError_t e = hipGetLastError();
+    const hipError_t e2 = hipStreamSynchronize(st);
+    if (e != hipSuccess || e2 != hipSuccess) return fail(ER_ERR_HIP, "er_k_surface_sample: %s", hipGetErrorString(e != hipSuccess ? e : e2));
+    return ER_OK;
+}
+
+extern "C" int er_k_fidelity_metrics(const float* d2_ab, const float* d2_ba, int B, int Na, int Nb, float tau, double* metrics,
+                                     void* stream) {
+    if (!d2_ab || !d2_ba || !metrics || B <= 0 || B > 65535 || Na <= 0 || Nb <= 0 || Na > FID_MAX_N || Nb > FID_MAX_N)
+        return fail(ER_ERR_INVALID, "er_k_fidelity_metrics: bad argument");
+    hipStream_t st = (hipStream_t)stream;
+    const hipError_t e = launch_fidelity_metrics(d2_ab, d2_ba, B, Na, Nb, tau, metrics, st);
+    const hipError_t e2 = hipStreamSynchronize(st);
+    if (e != hipSuccess || e2 != hipSuccess) return fail(ER_ERR_HIP, "er_k_fidelity_metrics: %s", hipGetErrorString(e != hipSuccess ? e : e2));
     return ER_OK;
 }
 

@@ -228,6 +228,54 @@ def fps(points, n_samples):
     return idx
 
 
+def nn_dist2(a, b, return_idx=True):
+    """Nearest neighbour of every point of a [B, Na, 3] among b [B, Nb, 3] (csrc/k_fidelity.h; fp32, no distance matrix) ->
+    (d2 [B, Na] fp32 = min_j (dx*dx + dy*dy) + dz*dz, idx [B, Na] int32 = the j that attains it, lowest j on ties)."""
+    lib = native.load_library()
+    a = a.to(torch.float32).contiguous()
+    b = b.to(torch.float32).contiguous()
+    B, Na, Nb = a.shape[0], a.shape[1], b.shape[1]
+    d2 = torch.empty((B, Na), dtype=torch.float32, device=a.device)
+    idx = torch.empty((B, Na), dtype=torch.int32, device=a.device) if return_idx else None
+    native.check(lib.er_k_nn_dist2(native.ptr(a), native.ptr(b), B, Na, Nb, native.ptr(d2), native.ptr(idx), _st()), "er_k_nn_dist2")
+    return (d2, idx) if return_idx else d2
+
+
+def surface_sample(vertices, faces, vert_offsets, face_offsets, n_samples, seed=0, stream_ids=None, return_faces=True):
+    """n_samples area-weighted surface samples of each mesh of a concatenated batch: vertices [sum V, 3] fp32 and faces [sum F, 3]
+    int32 (indices local to their mesh) on the device, vert_offsets / face_offsets B + 1 host ints.  Sample i of mesh m draws
+    Philox4x32-10(key = seed, counter = (i, stream_ids[m] or m, 0x53555246, 0)) -> (points [B, n_samples, 3] fp32, faces
+    [B, n_samples] int32)."""
+    lib = native.load_library()
+    v = vertices.to(torch.float32).contiguous()
+    f = faces.to(torch.int32).contiguous()
+    B = len(vert_offsets) - 1
+    assert len(face_offsets) == B + 1 and int(vert_offsets[B]) <= v.shape[0] and int(face_offsets[B]) <= f.shape[0]
+    pts = torch.empty((B, n_samples, 3), dtype=torch.float32, device=v.device)
+    fo = torch.empty((B, n_samples), dtype=torch.int32, device=v.device) if return_faces else None
+    sid = None if stream_ids is None else (C.c_uint32 * B)(*[int(s) & 0xFFFFFFFF for s in stream_ids])
+    native.check(lib.er_k_surface_sample(native.ptr(v), native.ptr(f), native.i32_array(vert_offsets), native.i32_array(face_offsets), B,
+                                         int(n_samples), C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), sid, native.ptr(pts),
+                                         native.ptr(fo), _st()), "er_k_surface_sample")
+    return (pts, fo) if return_faces else pts
+
+
+FIDELITY_METRICS = ("chamfer_l1", "chamfer_l2", "hausdorff", "precision", "recall", "fscore", "mean_a2b", "mean_b2a")
+
+
+def fidelity_metrics(d2_ab, d2_ba, tau):
+    """d2_ab [B, Na] (reference cloud -> generated samples), d2_ba [B, Nb] (generated samples -> reference cloud), both squared
+    distances in fp32 -> [B, 8] float64 in the order of FIDELITY_METRICS (fixed-order double sums: the same bits from run to run)."""
+    lib = native.load_library()
+    d2_ab = d2_ab.to(torch.float32).contiguous()
+    d2_ba = d2_ba.to(torch.float32).contiguous()
+    B, Na, Nb = d2_ab.shape[0], d2_ab.shape[1], d2_ba.shape[1]
+    out = torch.empty((B, len(FIDELITY_METRICS)), dtype=torch.float64, device=d2_ab.device)
+    native.check(lib.er_k_fidelity_metrics(native.ptr(d2_ab), native.ptr(d2_ba), B, Na, Nb, float(tau), native.ptr(out), _st()),
+                 "er_k_fidelity_metrics")
+    return out
+
+
 def sample_head(logits, mode, grammar, step, last_tok, counter, unfinished, top_k=10, min_new=0, seed=0,
                 eos=2, pad=0):
     """One sampling-head step. Returns (next_tok, counter, unfinished) lists."""

@@ -34,6 +34,7 @@ EXPORTS = [
     "er_dit_set_prediction_type", "er_dit_attach_point_encoder", "er_dit_point_latent", "er_dit_set_point_encoder_mode", "er_dit_loss", "er_k_dit_loss",
     "er_set_row_streams", "er_plan_decode", "er_ctx_plan", "er_plan_gemm_tile", "er_kernel_kind_name", "er_profile_decode_kernels", "er_profile_decode_kernels_at", "er_last_decode_ms",
     "er_k_gemv", "er_k_attn_decode", "er_k_attn_outproj3", "er_k_gemm", "er_k_gemm_f16", "er_k_gemm_hh", "er_k_gemm_hh_qkv", "er_k_gemm_hh_geglu", "er_k_gemm_f16s", "er_k_flash_attn_f16", "er_k_flash_attn_hh", "er_k_flash_attn_f32", "er_k_flash_attn_f16s", "er_k_layernorm", "er_k_softmax", "er_k_score_rows", "er_k_fps", "er_k_sample_head",
+    "er_k_nn_dist2", "er_k_surface_sample", "er_k_fidelity_metrics",
 ]
 
 
@@ -119,6 +120,10 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.er_dit_point_latent.argtypes = [vp, vp, ci, ci, vp, vp]
     lib.er_dit_set_point_encoder_mode.argtypes = [vp, ci]
     lib.er_k_fps.argtypes = [vp, ci, ci, ci, vp, vp]
+    lib.er_k_nn_dist2.argtypes = [vp, vp, ci, ci, ci, vp, vp, vp]
+    lib.er_k_surface_sample.argtypes = [vp, vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), ci, ci, C.c_uint64, C.POINTER(C.c_uint32),
+                                        vp, vp, vp]
+    lib.er_k_fidelity_metrics.argtypes = [vp, vp, ci, ci, ci, cf, vp, vp]
     lib.er_dit_loss.argtypes = [vp, vp, vp, vp, C.POINTER(C.c_int32), ci, ci, cf, vp, vp, vp, vp]
     lib.er_k_dit_loss.argtypes = [vp, vp, vp, C.POINTER(C.c_int32), ci, ci, ci, cf, vp, vp, vp]
     lib.er_plan_decode.argtypes = [ci, ci, ci, ci, ci, C.POINTER(ErDecodePlan)]

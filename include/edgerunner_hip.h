@@ -379,6 +379,29 @@ int er_k_dit_loss(const float* pred_dev, const float* x0_dev, const float* eps_d
 /* farthest point sampling of the downsample encoder on given clouds points_dev float[B, n_points, 3] -> idx_out_dev
  * int32[B, n_samples] (0-based within each cloud; 1 <= n_samples <= n_points, B <= 65535) */
 int er_k_fps(const float* points_dev, int batch, int n_points, int n_samples, int32_t* idx_out_dev, void* stream);
+/* ---- reconstruction fidelity (csrc/k_fidelity.h): how close a generated mesh is to the cloud it was conditioned on.  All three
+ * entry points take B <= 65535 and block until their result is in place (like er_k_fps: their scratch is freed on return).
+ * er_k_nn_dist2: d2_out_dev[b,i] = min_j d(a[b,i], b[b,j]) with d = (dx*dx + dy*dy) + dz*dz in fp32, every operation rounded on its
+ * own; idx_out_dev[b,i] (nullable) = the j that attains it, lowest j on ties.  a_dev float[B,n_a,3], b_dev float[B,n_b,3], any
+ * n_a, n_b in [1, 2^30], B <= 65535.  No [n_a][n_b] buffer is allocated (scratch: 8 bytes per query). */
+int er_k_nn_dist2(const float* a_dev, const float* b_dev, int batch, int n_a, int n_b, float* d2_out_dev, int32_t* idx_out_dev,
+                  void* stream);
+/* n_samples area-weighted surface samples of each of `batch` meshes, concatenated: vertices_dev float[vert_offset_host[B],3],
+ * faces_dev int32[face_offset_host[B],3] with indices LOCAL to their mesh.  Bit-reproducible: face weights llrint(area * 2^32) from
+ * double arithmetic, sample i of mesh m draws Philox4x32-10(key = seed, counter = (i, stream id of m, 0x53555246, 0)); the stream id
+ * is m unless stream_ids_host gives it (a caller passes global job indices, as for er_set_row_streams, so a mesh's samples do not
+ * depend on what shares its batch).  Precondition: |coordinate| <= 8.  ER_ERR_INVALID names the mesh that has no faces, more than
+ * 2^22 faces, zero total area or a face index outside its vertices (checked before any vertex is read through it).  Blocks.
+ * points_out_dev float[B,n_samples,3], face_out_dev int32[B,n_samples] (the chosen face, local; nullable). */
+int er_k_surface_sample(const float* vertices_dev, const int32_t* faces_dev, const int32_t* vert_offset_host,
+                        const int32_t* face_offset_host, int batch, int n_samples, uint64_t seed, const uint32_t* stream_ids_host,
+                        float* points_out_dev, int32_t* face_out_dev, void* stream);
+/* d2_ab_dev float[B,n_a] (reference cloud -> generated samples), d2_ba_dev float[B,n_b] (generated samples -> reference cloud) ->
+ * metrics_out_dev double[B,8] = {chamfer_l1, chamfer_l2, hausdorff, precision, recall, fscore, mean_a2b, mean_b2a}: distances are
+ * sqrt((double)d2), "within" is distance < (double)tau, precision / recall are the shares of b / a within tau, fscore = 2PR/(P+R)
+ * (0 when P + R = 0).  Sums in double and in a fixed order.  n_a, n_b in [1, 2^30]. */
+int er_k_fidelity_metrics(const float* d2_ab_dev, const float* d2_ba_dev, int batch, int n_a, int n_b, float tau,
+                          double* metrics_out_dev, void* stream);
 /* one sampling-head step on given logits float[B,V]; state arrays are int[B] on device */
 int er_k_sample_head(const float* logits_dev, const er_decode_params* p, int vocab, int eos, int pad,
                      int batch, int step, const int32_t* last_tok_host, const int32_t* counter_host,
