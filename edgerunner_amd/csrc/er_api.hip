@@ -100,9 +100,37 @@ static GenState gen_state_carve(int* sb, size_t b) {
     return s;
 }
 
-// Everything er_kv_reserve allocates for one (batch, Lcap).  It lives and dies as a whole: a new shape replaces the object, a reserve
-// that fails half way never installs its own, er_destroy drops it - and the captured step goes with the buffers it points into.
+constexpr int NBM = 32;   // batch rows per pass of the matrix-core decode projections (k_gemv_mfma.h)
+// K-range partials per row that a 4-wave split-K launch leaves to a LATER launch: out_proj 1536 / 384, fc2 6144 / 384 (4 is also the most
+// a 16-wave launch leaves to its own finish: 6144 / 1536).  KvMem::skpart is sized from them; the launches that write and read pass them.
+constexpr int SK_SLICES_OUTPROJ = 4, SK_SLICES_FC2 = 16;
+static_assert(1536 / (4 * GM_KW) == SK_SLICES_OUTPROJ && 6144 / (4 * GM_KW) == SK_SLICES_FC2 && 6144 / (GM_WAVES * GM_KW) == SK_SLICES_OUTPROJ, "k_gemv_mfma.h");
+
+// Everything the decode step branches on for ONE reserved cache shape: kv_alloc computes it once into the KvMem it describes, it is
+// installed and dropped with that object, and launch_kind_t and the other readers take their decisions from here.
+struct DecodePlan {
+    int B = 0, Lcap = 0, layers = 0;            // B == 0: no cache reserved
+    long long kv_bstride = 0, kv_lstride = 0;   // elements per batch row / per layer of the cache
+    int S_splits = 0, nch3 = 0;                 // chunks per (row, head) of the fixed-chunk attention / per head of the balanced kernel
+    er_decode_plan sel{};                       // what plan_decode chose (er_ctx_plan reports it) ...
+    bool force_batched = false;                 // ... under this ER_FORCE_BATCHED
+    bool batched = false;       // B > 4 (or ER_FORCE_BATCHED=1): weights streamed once per pass of 32 rows (matrix cores)
+    bool valu = false;          // ER_BATCHED_VALU=1: the older VALU kernels (one pass per 16 rows), kept for A/B runs
+    bool mfma = false;          // batched and not valu: the projections run on the matrix cores and read the tiled weight copies
+    bool xt = false;            // fast-mode batches read the tiled activation images (KvMem::xt_*); ER_XT=0 keeps the row-major fp32 inputs (A/B + parity matrix)
+    bool stream_attn = false;   // batched, D == 96 and (forced or B*H >= 256: at least one streaming workgroup per CU)
+    bool v3 = false;            // decode_v == 3 and the reserved cache qualifies
+    bool outproj_rows8 = false; // mfma and 5..8 rows: out_proj is ONE pass of the VALU kernel (gemv_outproj_rows8)
+    // xt, streaming attention and B > 8: the attention writes the tiled image xt_att, out_proj reads it and leaves SK_SLICES_OUTPROJ partials, fc1's LayerNorm launch finishes them
+    bool outproj_partials = false;
+    // fc2 of `layer` leaves SK_SLICES_FC2 partials to the next layer's LayerNorm launch (which asks fc2_defers(layer - 1)); the last layer finishes into ypre, which the lm_head reads
+    bool fc2_defers(int layer) const { return xt && layer >= 0 && layer + 1 < layers; }
+};
+
+// Everything er_kv_reserve allocates for one (batch, Lcap), with the plan of that shape.  It lives and dies as a whole: a new shape replaces
+// the object, a reserve that fails half way never installs its own, er_destroy drops it - and the captured step goes with the buffers it points into.
 struct KvMem {
+    DecodePlan plan;
     DevBuf<char> kc, vc;          // KV cache [layers][B][H][Lcap][D], fp32 or fp16 (fast)
     DevBuf<float> ypre, hbuf, ypre1, h1buf, qbuf, abuf, fbuf, logits;   // decode workspace ([B][...])
     DevBuf<float> part, part_ml;  // attention partials; version 3: {m, l} of the partials
@@ -122,6 +150,20 @@ struct KvMem {
     ~KvMem() { if (step_exec) hipGraphExecDestroy(step_exec); }
 };
 
+struct DecodeKnobs {          // the environment knobs of the decode step, read once per context by er_create (read_knobs)
+    bool use_graph = true;    // ER_NO_GRAPH=1: eager launches
+    // waves per workgroup of the qkv / fc1 GEMVs (env ER_NW_QKV: 4, 6 or 9; ER_NW_FC1: 4 or 12).  Exact mode: qkv 6 waves x 1 row
+    // = 768 workgroups (3 per CU), fc1 4 waves x 2 rows = 768; fast mode: one fat workgroup per CU (9 / 12 waves x 2 rows).  The other
+    // shapes are fixed (out_proj 3 waves x 1 row, fc2 4 K-slices x 2 rows, 128-key chunks for the fixed-chunk attention): their
+    // round-1/2 knobs (ER_RW_*, ER_NW_OUT, ER_ATTN_STEPS, ER_ATTN_V, ER_COMBINE_V, ER_ATTN_GRID_HS, ER_OUT_VALU) are settled and gone
+    int nw_qkv = 6, nw_fc1 = 4;
+    int prefill_attn_f16s = -1;   // fast-mode prefix attention on the fp16 matrix cores with hi/lo-split q and p (k_flash_attn_f16s.h): on unless
+                                  // ER_PREFILL_ATTN_F16S=0 (the fp32-matrix-core kernel; kept for the parity matrix)
+    int attn_v_batched = 0;   // attention kernel at B > 4 (env ER_ATTN_V_BATCHED): 0 = auto (streaming when B*H >= 256, else split + merge), 1 = split kernel + merge, 3 = one streaming workgroup per (row, head), no merge
+    int decode_v = 3;         // single-row decode: 3 = balanced-chunk attention + merge fused into out_proj (one row, D = 96, 16 heads, Lcap <= 8192); ER_DECODE_V=2 = fixed 128-key chunks + merge kernel (also the fallback when the cache does not qualify)
+    int rw_fc2 = 6;           // fast mode, one row: rows per fc2 workgroup (env ER_RW_FC2: 2 / 4 / 6, anything else runs as 2; launch_kind_t case 5)
+};
+
 struct er_ctx {
     er_config cfg{};
     int device = 0;
@@ -135,32 +177,14 @@ struct er_ctx {
     float *proj_w = nullptr, *proj_b = nullptr, *normc_w = nullptr, *normc_b = nullptr;
     PointEnc pe;             // point encoder (cond_mode POINT)
     WeightTable w;           // every checkpoint key (register_weights)
-    // KV cache + decode workspace of the reserved shape
-    int B = 0, Lcap = 0, S_splits = 0;
-    std::unique_ptr<KvMem> kv = std::make_unique<KvMem>();   // never null; er_kv_reserve swaps in a new one
+    std::unique_ptr<KvMem> kv = std::make_unique<KvMem>();   // KV cache + decode workspace + plan of the reserved shape (kv->plan.B == 0: none); never null, er_kv_reserve swaps in a new one
     int kv_esz = 4;
-    long long kv_bstride = 0, kv_lstride = 0;
     int* h_pinned = nullptr;      // small pinned host buffer
     int base_pos = 0;             // prefill length of the current generation
     bool have_hidden = false;     // ypre holds a valid last-position state
-    bool use_graph = true;
-    bool batched = false;     // B > 4 (or ER_FORCE_BATCHED=1): weights streamed once per pass of 32 rows (matrix cores)
-    bool batched_valu = false;   // ER_BATCHED_VALU=1: the older VALU kernels (one pass per 16 rows), kept for A/B runs
-    bool xt = false;          // fast-mode batches read the tiled activation images (KvMem::xt_*); ER_XT=0 keeps the row-major fp32 inputs (A/B + parity matrix)
+    DecodeKnobs knobs;        // environment of er_create
     bool tiled_valid = false; // LayerW::*_t match the loaded weights
-    // waves per workgroup of the qkv / fc1 GEMVs (env ER_NW_QKV: 4, 6 or 9; ER_NW_FC1: 4 or 12).  Exact mode: qkv 6 waves x 1 row
-    // = 768 workgroups (3 per CU), fc1 4 waves x 2 rows = 768; fast mode: one fat workgroup per CU (9 / 12 waves x 2 rows).  The other
-    // shapes are fixed (out_proj 3 waves x 1 row, fc2 4 K-slices x 2 rows, 128-key chunks for the fixed-chunk attention): their
-    // round-1/2 knobs (ER_RW_*, ER_NW_OUT, ER_ATTN_STEPS, ER_ATTN_V, ER_COMBINE_V, ER_ATTN_GRID_HS, ER_OUT_VALU) are settled and gone
-    int nw_qkv = 6, nw_fc1 = 4;
-    int prefill_attn_f16s = -1;   // fast-mode prefix attention on the fp16 matrix cores with hi/lo-split q and p (k_flash_attn_f16s.h): on unless
-                                  // ER_PREFILL_ATTN_F16S=0 (the fp32-matrix-core kernel; kept for the parity matrix)
     int prof_len = 0;         // > 0: attention kernels run at this fixed length (er_profile_decode_kernels_at)
-    int attn_v_batched = 0;   // attention kernel at B > 4 (env ER_ATTN_V_BATCHED): 0 = auto (streaming when B*H >= 256, else split + merge), 1 = split kernel + merge, 3 = one streaming workgroup per (row, head), no merge
-    bool stream_attn = false; // batched, D == 96 and (forced or B*H >= 256: at least one streaming workgroup per CU)
-    int decode_v = 3;         // single-row decode: 3 = balanced-chunk attention + merge fused into out_proj (one row, D = 96, 16 heads, Lcap <= 8192); ER_DECODE_V=2 = fixed 128-key chunks + merge kernel (also the fallback when the cache does not qualify)
-    bool v3 = false;          // decode_v == 3 and the reserved cache qualifies
-    int nch3 = 0;             // chunks per head of the balanced attention kernel
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     float last_decode_ms = 0.f;
     // scratch for prefill / encoder: grow-only, freed with the context
@@ -171,10 +195,36 @@ struct er_ctx {
 };
 
 constexpr int ER_MAX_BATCH = 1023;   // h_pinned holds B ints + one flag
-constexpr int NBM = 32;   // batch rows per pass of the matrix-core decode projections (k_gemv_mfma.h)
 
 template <typename Ctx>      // er_ctx, er_dit_ctx
 static hipStream_t pick(Ctx* c, void* s) { return s ? (hipStream_t)s : c->own_stream; }
+
+static int env_int(const char* name, int dflt) { const char* v = getenv(name); return (v && v[0]) ? atoi(v) : dflt; }
+static bool env_is(const char* name, char ch) { const char* v = getenv(name); return v && v[0] == ch; }
+
+// the knobs a context keeps for its lifetime (er_create; er_plan_decode evaluates the same rules at call time)
+static DecodeKnobs read_knobs(bool fast) {
+    DecodeKnobs k;
+    k.use_graph = !env_is("ER_NO_GRAPH", '1');
+    // one fat workgroup per CU (qkv 9 waves x 2 rows, fc1 12 waves x 2 rows) pays with fp16 weights only: the LayerNorm prologue and
+    // its 18 KB of x / affine reads are then once per CU instead of three times (profiles/r03_fat_workgroups.log: fp16 +2.7 %, fp32 +-0)
+    k.nw_qkv = env_int("ER_NW_QKV", fast ? 9 : 6);
+    if (k.nw_qkv != 4 && k.nw_qkv != 9) k.nw_qkv = 6;
+    k.nw_fc1 = env_int("ER_NW_FC1", fast ? 12 : 4) == 12 ? 12 : 4;
+    k.prefill_attn_f16s = env_int("ER_PREFILL_ATTN_F16S", -1);
+    if (k.prefill_attn_f16s != 0 && k.prefill_attn_f16s != 1) k.prefill_attn_f16s = -1;
+    k.attn_v_batched = env_int("ER_ATTN_V_BATCHED", 0);
+    if (k.attn_v_batched != 1 && k.attn_v_batched != 3) k.attn_v_batched = 0;
+    k.decode_v = env_int("ER_DECODE_V", 3) == 2 ? 2 : 3;
+    const char* rw = getenv("ER_RW_FC2");
+    k.rw_fc2 = rw ? atoi(rw) : 6;
+    if (fast && k.rw_fc2 != 2 && k.rw_fc2 != 4 && k.rw_fc2 != 6) fprintf(stderr, "[edgerunner_hip] ER_RW_FC2=%s is not 2 / 4 / 6: using 2 rows per fc2 workgroup\n", rw);
+    return k;
+}
+
+// the three switches er_kv_reserve reads for the shape it reserves (tests flip them between two reserves of one context)
+struct ReserveKnobs { bool force_batched, batched_valu, xt; };
+static ReserveKnobs read_reserve_knobs() { return {env_is("ER_FORCE_BATCHED", '1'), env_is("ER_BATCHED_VALU", '1'), !env_is("ER_XT", '0')}; }
 
 extern "C" int er_abi_version(void) { return ER_ABI_VERSION; }
 extern "C" const char* er_last_error(void) { return g_err; }
@@ -270,19 +320,7 @@ extern "C" int er_create(const er_config* cfg, int device, er_ctx** out) {
     c->layers.resize(cfg->num_layers);
     c->pe.PH = cfg->point_hidden_dim; c->pe.heads = cfg->point_num_heads; c->pe.Lq = cfg->point_latent_size;
     c->pe.LD = cfg->point_latent_dim; c->pe.freq = cfg->point_freq_dim; c->pe.eps = cfg->ln_eps;
-    const char* ng = getenv("ER_NO_GRAPH");
-    c->use_graph = !(ng && ng[0] == '1');
-    auto env_int = [](const char* name, int dflt) { const char* v = getenv(name); return (v && v[0]) ? atoi(v) : dflt; };
-    // one fat workgroup per CU (qkv 9 waves x 2 rows, fc1 12 waves x 2 rows) pays with fp16 weights only: the LayerNorm prologue and
-    // its 18 KB of x / affine reads are then once per CU instead of three times (profiles/r03_fat_workgroups.log: fp16 +2.7 %, fp32 +-0)
-    c->nw_qkv = env_int("ER_NW_QKV", fast ? 9 : 6);
-    if (c->nw_qkv != 4 && c->nw_qkv != 9) c->nw_qkv = 6;
-    c->nw_fc1 = env_int("ER_NW_FC1", fast ? 12 : 4) == 12 ? 12 : 4;
-    c->prefill_attn_f16s = env_int("ER_PREFILL_ATTN_F16S", -1);
-    if (c->prefill_attn_f16s != 0 && c->prefill_attn_f16s != 1) c->prefill_attn_f16s = -1;
-    c->attn_v_batched = env_int("ER_ATTN_V_BATCHED", 0);
-    if (c->attn_v_batched != 1 && c->attn_v_batched != 3) c->attn_v_batched = 0;
-    c->decode_v = env_int("ER_DECODE_V", 3) == 2 ? 2 : 3;
+    c->knobs = read_knobs(fast);
     HIPCHK(hipStreamCreateWithFlags(&c->own_stream, hipStreamDefault));
     HIPCHK(hipEventCreate(&c->ev0));
     HIPCHK(hipEventCreate(&c->ev1));
@@ -290,12 +328,6 @@ extern "C" int er_create(const er_config* cfg, int device, er_ctx** out) {
     register_weights(c);
     *out = c;
     return ER_OK;
-}
-
-static void free_kv(er_ctx* c) {
-    c->kv = std::make_unique<KvMem>();
-    c->B = 0; c->Lcap = 0;
-    c->have_hidden = false;
 }
 
 // The context's buffers, weight blocks and captured step are members: deleting the context frees them, once the device is idle.
@@ -362,7 +394,8 @@ static int make_tiled_weights(er_ctx* c) {
 }
 
 // ------------------------------------------------------------------------------------ which decode kernels a cache shape gets
-// ONE place for the selection rules (kv_alloc applies them, er_plan_decode reports them; pure host logic):
+// ONE place for the selection rules (pure host logic).  er_plan_decode reports them for a hypothetical shape; kv_alloc derives the
+// DecodePlan of a reserved shape from them and stores it with that shape's memory:
 //   batched     : B > 4 (or forced) - weights streamed once per pass of 32 rows on the matrix cores
 //   version 3   : one row, 16 heads of 96, hidden 1536, reserved cache <= 16 chunks x 512 keys; else version 2
 //   attention B>4: streaming kernel when forced or (auto and B * heads >= 256: at least one workgroup per CU - at B = 16 it
@@ -380,25 +413,19 @@ static void plan_decode(int decode_v, int attn_v_batched, bool force_batched, in
     p->launches_per_layer = p->batched ? 0 : 5 + p->merge_launch;       // qkv, attention, (merge,) out_proj, fc1, fc2
 }
 
-static int env_int_(const char* name, int dflt) { const char* v = getenv(name); return (v && v[0]) ? atoi(v) : dflt; }
-
 extern "C" int er_plan_decode(int batch, int heads, int head_dim, int hidden, int l_cap, er_decode_plan* out) {
     if (!out || batch <= 0 || heads <= 0 || head_dim <= 0 || l_cap <= 0) return fail(ER_ERR_INVALID, "er_plan_decode: bad argument");
-    int dv = env_int_("ER_DECODE_V", 3) == 2 ? 2 : 3;
-    int avb = env_int_("ER_ATTN_V_BATCHED", 0);
-    if (avb != 1 && avb != 3) avb = 0;
-    const char* fb = getenv("ER_FORCE_BATCHED");
-    plan_decode(dv, avb, fb && fb[0] == '1', batch, heads, head_dim, hidden, (l_cap + 31) / 32 * 32, out);
+    const DecodeKnobs k = read_knobs(false);
+    plan_decode(k.decode_v, k.attn_v_batched, read_reserve_knobs().force_batched, batch, heads, head_dim, hidden, (l_cap + 31) / 32 * 32, out);
     return ER_OK;
 }
 
-// the plan of a LIVE context: its knobs were fixed at er_create and its cache by the last er_kv_reserve (er_plan_decode above
+// the plan of a LIVE context, as the last er_kv_reserve stored it: knobs of er_create, switches of that reserve (er_plan_decode above
 // evaluates the same rules for hypothetical shapes with the environment as it is at call time)
 extern "C" int er_ctx_plan(er_ctx* c, er_decode_plan* out) {
     if (!c || !out) return fail(ER_ERR_INVALID, "er_ctx_plan: null argument");
-    if (c->B <= 0) return fail(ER_ERR_INVALID, "er_ctx_plan: no cache reserved (call er_kv_reserve)");
-    plan_decode(c->decode_v, c->attn_v_batched, /*force_batched=*/c->batched && c->B <= 4, c->B, c->cfg.num_heads, c->D,
-                c->cfg.hidden_dim, c->Lcap, out);
+    if (c->kv->plan.B <= 0) return fail(ER_ERR_INVALID, "er_ctx_plan: no cache reserved (call er_kv_reserve)");
+    *out = c->kv->plan.sel;
     return ER_OK;
 }
 
@@ -418,36 +445,41 @@ extern "C" int er_kv_reserve(er_ctx* c, int batch, int max_len) {
     if (max_len > g.max_positions)
         return fail(ER_ERR_CAPACITY, "max_len %d exceeds the position table (%d)", max_len, g.max_positions);
     const int Lcap = (max_len + 31) / 32 * 32;
-    if (c->B == batch && c->Lcap == Lcap) return ER_OK;
+    if (c->kv->plan.B == batch && c->kv->plan.Lcap == Lcap) return ER_OK;
     HIPCHK(hipDeviceSynchronize());
-    free_kv(c);                                  // first: the old shape's memory makes room for the new one
+    c->kv = std::make_unique<KvMem>();           // first: the old shape's memory makes room for the new one (this plan says: no cache)
+    c->have_hidden = false;
     auto m = std::make_unique<KvMem>();
-    ERCHK(kv_alloc(c, *m, batch, Lcap));         // a failed hipMalloc half way leaves nothing behind: m dies here
-    c->kv = std::move(m);
-    c->B = batch;
-    c->Lcap = Lcap;
+    ERCHK(kv_alloc(c, *m, batch, Lcap));         // a failed hipMalloc half way leaves nothing behind: m and its plan die here
+    c->kv = std::move(m);                        // buffers and plan of the new shape, in one step
     return ER_OK;
 }
 
-// the buffers of the new shape into m, and the decode plan that goes with it into c
+// the buffers of the new shape and the decode plan that goes with them, both into m (of c, only the tiled weight copies may change)
 static int kv_alloc(er_ctx* c, KvMem& m, int batch, int Lcap) {
     const er_config& g = c->cfg;
     const int H = g.num_heads, D = c->D, hid = g.hidden_dim;
-    c->kv_bstride = (long long)H * Lcap * D;
-    c->kv_lstride = c->kv_bstride * batch;
-    const size_t kv_bytes = (size_t)c->kv_lstride * g.num_layers * c->kv_esz;
+    const ReserveKnobs rk = read_reserve_knobs();
+    DecodePlan& p = m.plan;
+    p.B = batch; p.Lcap = Lcap; p.layers = g.num_layers;
+    p.kv_bstride = (long long)H * Lcap * D; p.kv_lstride = p.kv_bstride * batch;
+    p.S_splits = attn_num_chunks(Lcap, attn_chunk(ATTN_STEPS_DEFAULT, c->fast));   // decode attention: one workgroup per (row, head, chunk of 32*steps keys)
+    p.nch3 = attn3_num_chunks(H);
+    p.force_batched = rk.force_batched; p.valu = rk.batched_valu;
+    plan_decode(c->knobs.decode_v, c->knobs.attn_v_batched, p.force_batched, batch, H, D, hid, Lcap, &p.sel);
+    p.batched = p.sel.batched != 0; p.mfma = p.batched && !p.valu; p.xt = c->fast && p.mfma && rk.xt;
+    p.stream_attn = p.sel.attn_kernel == ER_ATTN_STREAM; p.v3 = p.sel.decode_version == 3;
+    p.outproj_rows8 = p.mfma && batch >= 5 && batch <= 8;
+    p.outproj_partials = p.xt && p.stream_attn && batch > 8;
+    const size_t kv_bytes = (size_t)p.kv_lstride * g.num_layers * c->kv_esz;
     ERCHK(m.kc.ensure(kv_bytes));
     ERCHK(m.vc.ensure(kv_bytes));
-    // decode attention: one workgroup per (row, head, chunk of 32*steps keys)
-    const int S = attn_num_chunks(Lcap, attn_chunk(ATTN_STEPS_DEFAULT, c->fast));
-    c->S_splits = S;
     const size_t b = (size_t)batch;
     for (DevBuf<float>* w : {&m.ypre, &m.hbuf, &m.ypre1, &m.h1buf, &m.qbuf, &m.abuf}) ERCHK(w->ensure(b * hid));
     ERCHK(m.fbuf.ensure(b * g.intermediate_dim));
     ERCHK(m.logits.ensure(b * g.vocab_size));
-    c->nch3 = attn3_num_chunks(H);
-    ERCHK(m.part.ensure(b * H * (size_t)std::max(S * (D + 2), c->nch3 * D)));
-    ERCHK(m.part_ml.ensure(b * H * (size_t)c->nch3 * 2));
+    ERCHK(m.part.ensure(b * H * (size_t)std::max(p.S_splits * (D + 2), p.nch3 * D)));
+    ERCHK(m.part_ml.ensure(b * H * (size_t)p.nch3 * 2));
     ERCHK(m.state_block.ensure(gen_state_ints(b)));
     m.st = gen_state_carve(m.state_block.p, b);
     ERCHK(m.d_params.ensure(1));
@@ -460,24 +492,14 @@ static int kv_alloc(er_ctx* c, KvMem& m, int batch, int Lcap) {
     }
     m.st.row_stream = m.d_row_stream.p;
     ERCHK(m.d_out_ids.ensure(b * (size_t)Lcap));
-    const char* fb = getenv("ER_FORCE_BATCHED");
-    er_decode_plan plan{};
-    plan_decode(c->decode_v, c->attn_v_batched, fb && fb[0] == '1', batch, H, D, hid, Lcap, &plan);
-    c->batched = plan.batched != 0;
-    const char* bv = getenv("ER_BATCHED_VALU");
-    c->batched_valu = bv && bv[0] == '1';
-    if (c->batched && !c->batched_valu) ERCHK(make_tiled_weights(c));
-    c->stream_attn = plan.attn_kernel == ER_ATTN_STREAM;
-    c->v3 = plan.decode_version == 3;
-    // fast mode, matrix-core projections: the activations travel in the tiled hi | lo operand layout (k_gemv.h xt_entry).  One image
-    // of K x 128 bytes per group of 32 rows; zeroed once so that the rows of a last, partial group never hold NaN patterns.
-    const char* xe = getenv("ER_XT");
-    c->xt = c->fast && c->batched && !c->batched_valu && !(xe && xe[0] == '0');
+    if (p.mfma) ERCHK(make_tiled_weights(c));
     // split-K partials of the batched projections.  A finish launched right behind its producer re-uses ONE [4][32][N] block; only the
     // tiled path defers finishes to a later launch (prep_rows_kernel, sk_part) and keeps a [16][32][hidden] block per group of 32 rows
-    ERCHK(m.skpart.ensure(c->xt ? ((b + NBM - 1) / NBM) * (size_t)16 * NBM * (size_t)hid : (size_t)4 * NBM * (size_t)std::max(hid, g.vocab_size)));
-    if (c->xt) {
-        const size_t groups = (size_t)(batch + NBM - 1) / NBM;
+    const size_t groups = (b + NBM - 1) / NBM;
+    ERCHK(m.skpart.ensure(p.xt ? groups * SK_SLICES_FC2 * NBM * (size_t)hid : (size_t)SK_SLICES_OUTPROJ * NBM * (size_t)std::max(hid, g.vocab_size)));
+    // fast mode, matrix-core projections: the activations travel in the tiled hi | lo operand layout (k_gemv.h xt_entry).  One image
+    // of K x 128 bytes per group of 32 rows; zeroed once so that the rows of a last, partial group never hold NaN patterns.
+    if (p.xt) {
         const size_t b_h = groups * (size_t)hid * 128, b_f = groups * (size_t)g.intermediate_dim * 128;
         ERCHK(m.xt_h.ensure(b_h));
         ERCHK(m.xt_att.ensure(b_h));
@@ -490,30 +512,32 @@ static int kv_alloc(er_ctx* c, KvMem& m, int batch, int Lcap) {
 }
 
 // ------------------------------------------------------------------------------------ decode step
-struct StepPlan {   // which kinds to launch (profiling launches one kind at a time)
-    bool head = true, sample = true, layers = true;
-    int only_kind = -1;   // >= 0: launch just this kind
-    int only_layer = -1;
-};
+// a with every per-row pointer advanced to batch row row0 (K = width of an input row): what a pass of the three group loops below launches with.
+// The batched kernels read neither hout nor tok, and the tiled image of a group of 32 rows is K * 32 floats like its row-major form: one rule serves all.
+static GemvArgs gemv_args_at(const GemvArgs& a, int row0, int K) {
+    GemvArgs g = a;
+    if (g.xin) g.xin += (long long)row0 * K;
+    if (g.xt_out) g.xt_out = (char*)g.xt_out + (long long)row0 * a.N * 4;     // xt_entry() indexes inside a group
+    if (g.hout) g.hout += (long long)row0 * K;
+    if (g.tok) g.tok += row0;
+    if (g.pos) g.pos += row0;
+    if (g.out) g.out += (long long)row0 * a.N;
+    if (g.resid) g.resid += (long long)row0 * a.N;
+    if (g.q) g.q += (long long)row0 * a.hidden;
+    const long long kvb = (long long)row0 * a.kv_bstride * (a.kv_half ? 2 : 4);
+    if (g.kcache) g.kcache = (char*)g.kcache + kvb;
+    if (g.vcache) g.vcache = (char*)g.vcache + kvb;
+    return g;
+}
 
 template <typename WT, int KS, int RW, int PRO, int EPI, int NW = ER_NWAVES>
-static hipError_t gemv_groups(GemvArgs a, int B, int K, hipStream_t st) {
+static hipError_t gemv_groups(const GemvArgs& a, int B, int K, hipStream_t st) {
     // rows are processed in groups of up to 4 (one weight stream, 1..4 accumulators per row)
     int b = 0;
     while (b < B) {
         int nb = B - b;
         nb = nb >= 4 ? 4 : nb;
-        GemvArgs g = a;
-        if (g.xin) g.xin += (long long)b * K;
-        if (g.hout) g.hout += (long long)b * K;
-        if (g.tok) g.tok += b;
-        if (g.pos) g.pos += b;
-        if (g.out) g.out += (long long)b * a.N;
-        if (g.resid) g.resid += (long long)b * a.N;
-        if (g.q) g.q += (long long)b * a.hidden;
-        const long long kvb = (long long)b * a.kv_bstride * (a.kv_half ? 2 : 4);
-        if (g.kcache) g.kcache = (char*)g.kcache + kvb;
-        if (g.vcache) g.vcache = (char*)g.vcache + kvb;
+        const GemvArgs g = gemv_args_at(a, b, K);
         hipError_t e;
         if (nb == 4) e = launch_gemv<WT, KS, 4, RW, PRO, EPI, NW>(g, st);
         else if (nb == 3) e = launch_gemv<WT, KS, 3, RW, PRO, EPI, NW>(g, st);
@@ -554,19 +578,10 @@ static hipError_t gemv_outproj_rows8(const GemvArgs& a, int B, hipStream_t st) {
 // B > 4: weights streamed once per pass of up to 16 rows (gemv_batched_kernel)
 constexpr int NBB = 16;
 template <typename WT, int PH, int RW, int EPI>
-static hipError_t gemv_batched_groups(GemvArgs a, int B, int K, hipStream_t st) {
+static hipError_t gemv_batched_groups(const GemvArgs& a, int B, int K, hipStream_t st) {
     for (int b = 0; b < B; b += NBB) {
         const int nb = (B - b) < NBB ? (B - b) : NBB;
-        GemvArgs g = a;
-        g.xin += (long long)b * K;
-        if (g.pos) g.pos += b;
-        if (g.out) g.out += (long long)b * a.N;
-        if (g.resid) g.resid += (long long)b * a.N;
-        if (g.q) g.q += (long long)b * a.hidden;
-        const long long kvb = (long long)b * a.kv_bstride * (a.kv_half ? 2 : 4);
-        if (g.kcache) g.kcache = (char*)g.kcache + kvb;
-        if (g.vcache) g.vcache = (char*)g.vcache + kvb;
-        hipError_t e = launch_gemv_batched<WT, PH, NBB, RW, EPI>(g, nb, st);
+        hipError_t e = launch_gemv_batched<WT, PH, NBB, RW, EPI>(gemv_args_at(a, b, K), nb, st);
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
@@ -574,30 +589,18 @@ static hipError_t gemv_batched_groups(GemvArgs a, int B, int K, hipStream_t st) 
 // XT: a.xin is the tiled image of the input (a group of 32 rows is K * 32 floats there as well, so the group offsets coincide)
 struct SkPart { float* p; size_t floats; };       // the context's split-K partial block and its size
 template <typename WT, int EPI, bool XT = false>
-static hipError_t gemv_mfma_groups(GemvArgs a, int B, int K, SkPart part, hipStream_t st, bool defer_finish = false, bool narrow = false) {
+static hipError_t gemv_mfma_groups(const GemvArgs& a, int B, int K, SkPart part, hipStream_t st, bool defer_finish = false, bool narrow = false) {
+    const int slices = narrow ? K / (4 * GM_KW) : K / (GM_WAVES * GM_KW);
     {   // the block was sized in er_kv_reserve for K <= 6144 (4 wide / 16 narrow slices) and, when the finish is not deferred, for ONE
         // group at a time on an in-order stream: refuse anything that would overrun it instead of writing past the end
-        const size_t slices = narrow ? K / (4 * GM_KW) : K / (GM_WAVES * GM_KW), groups = (size_t)(B + NBM - 1) / NBM;
+        const size_t groups = (size_t)(B + NBM - 1) / NBM;
         const size_t need = (defer_finish ? groups : 1) * slices * NBM * (size_t)a.N;
         if (!part.p || need > part.floats) return hipErrorInvalidValue;
     }
     for (int b = 0; b < B; b += NBM) {
         const int nb = (B - b) < NBM ? (B - b) : NBM;
-        GemvArgs g = a;
-        if (g.xin) g.xin += (long long)b * K;
-        if (g.xt_out) g.xt_out = (char*)g.xt_out + (long long)b * a.N * 4;     // xt_entry() indexes inside a group
-        if (g.hout) g.hout += (long long)b * K;
-        if (g.tok) g.tok += b;
-        if (g.pos) g.pos += b;
-        if (g.out) g.out += (long long)b * a.N;
-        if (g.resid) g.resid += (long long)b * a.N;
-        if (g.q) g.q += (long long)b * a.hidden;
-        const long long kvb = (long long)b * a.kv_bstride * (a.kv_half ? 2 : 4);
-        if (g.kcache) g.kcache = (char*)g.kcache + kvb;
-        if (g.vcache) g.vcache = (char*)g.vcache + kvb;
         // deferred: every group keeps its own partial block (prep_rows_kernel: g * 4 * 32 * K floats)
-        const int slices = narrow ? K / (4 * GM_KW) : K / (GM_WAVES * GM_KW);
-        hipError_t e = launch_gemv_mfma<WT, EPI, XT>(g, nb, K, defer_finish ? part.p + (long long)(b / NBM) * slices * NBM * a.N : part.p, st, defer_finish, narrow);
+        hipError_t e = launch_gemv_mfma<WT, EPI, XT>(gemv_args_at(a, b, K), nb, K, defer_finish ? part.p + (long long)(b / NBM) * slices * NBM * a.N : part.p, st, defer_finish, narrow);
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
@@ -609,10 +612,11 @@ static hipError_t prep_rows(const GemvArgs& a, int B, hipStream_t st) {
 }
 
 static AttnDecArgs attn_args(er_ctx* c, int layer) {
+    const DecodePlan& p = c->kv->plan;
     AttnDecArgs a{};
     a.q = c->kv->qbuf.p;
-    a.kcache = c->kv->kc.p + (long long)layer * c->kv_lstride * c->kv_esz;
-    a.vcache = c->kv->vc.p + (long long)layer * c->kv_lstride * c->kv_esz;
+    a.kcache = c->kv->kc.p + (long long)layer * p.kv_lstride * c->kv_esz;
+    a.vcache = c->kv->vc.p + (long long)layer * p.kv_lstride * c->kv_esz;
     a.chunk = attn_chunk(ATTN_STEPS_DEFAULT, c->fast);
     a.pos = c->kv->st.pos;
     a.fixed_len = c->prof_len;
@@ -621,12 +625,12 @@ static AttnDecArgs attn_args(er_ctx* c, int layer) {
     a.part_ml = c->kv->part_ml.p;
     a.out = c->kv->abuf.p;
     a.H = c->cfg.num_heads;
-    a.l_cap = c->Lcap;
-    a.S = c->S_splits;
+    a.l_cap = p.Lcap;
+    a.S = p.S_splits;
     a.hidden = c->cfg.hidden_dim;
-    a.kv_bstride = c->kv_bstride;
+    a.kv_bstride = p.kv_bstride;
     a.sqrt_d = sqrtf((float)c->D);
-    a.out_xt = (c->xt && c->stream_attn && c->B > 8) ? c->kv->xt_att.p : nullptr;      // out_proj then reads the tiled image (launch_kind_t case 3)
+    a.out_xt = p.outproj_partials ? c->kv->xt_att.p : nullptr;      // out_proj then reads the tiled image
     return a;
 }
 
@@ -641,29 +645,30 @@ template <typename WT>
 static hipError_t launch_kind_t(er_ctx* c, int kind, int layer, hipStream_t st, long long* out_ids, int out_ld) {
     constexpr bool HALF = sizeof(WT) == 2;
     const er_config& g = c->cfg;
-    const int H = g.hidden_dim, I = g.intermediate_dim, B = c->B;
-    const int nl = g.num_layers;
+    const DecodePlan& p = c->kv->plan;
+    const int H = g.hidden_dim, I = g.intermediate_dim, B = p.B;
+    const SkPart sk{c->kv->skpart.p, c->kv->skpart.n};
     GemvArgs a{};
     a.eps = g.ln_eps;
-    a.hidden = H; a.head_dim = c->D; a.l_cap = c->Lcap; a.kv_bstride = c->kv_bstride; a.kv_half = HALF ? 1 : 0;
+    a.hidden = H; a.head_dim = c->D; a.l_cap = p.Lcap; a.kv_bstride = p.kv_bstride; a.kv_half = HALF ? 1 : 0;
     switch (kind) {
         case 0: {   // qkv
             const LayerW& L = c->layers[layer];
             a.W = HALF ? (const void*)L.wqkv_h : (const void*)L.wqkv; a.bias = L.bqkv; a.N = 3 * H;
             a.hout = c->kv->hbuf.p; a.pos = c->kv->st.pos;
             a.q = c->kv->qbuf.p;
-            a.kcache = c->kv->kc.p + (long long)layer * c->kv_lstride * c->kv_esz;
-            a.vcache = c->kv->vc.p + (long long)layer * c->kv_lstride * c->kv_esz;
+            a.kcache = c->kv->kc.p + (long long)layer * p.kv_lstride * c->kv_esz;
+            a.vcache = c->kv->vc.p + (long long)layer * p.kv_lstride * c->kv_esz;
             if (layer == 0) {
                 a.embd = c->embd; a.posemb = c->posemb; a.tok = c->kv->st.tok;
             } else {
                 a.xin = c->kv->ypre.p; a.ln_w = c->layers[layer - 1].ln2w; a.ln_b = c->layers[layer - 1].ln2b;
             }
-            if (c->batched) {
+            if (p.batched) {
                 if constexpr (HALF) {
-                    a.xt_out = c->xt ? c->kv->xt_h.p : nullptr;
-                    if (c->xt && layer > 0) {      // the previous layer's fc2 deferred its split-K finish to this LayerNorm (case 5)
-                        a.sk_part = c->kv->skpart.p; a.sk_bias = c->layers[layer - 1].b2; a.sk_resid = c->kv->h1buf.p; a.sk_batch = B; a.sk_slices = 16;
+                    a.xt_out = p.xt ? c->kv->xt_h.p : nullptr;
+                    if (p.fc2_defers(layer - 1)) {      // the previous layer's fc2 deferred its split-K finish to this LayerNorm (case 5)
+                        a.sk_part = sk.p; a.sk_bias = c->layers[layer - 1].b2; a.sk_resid = c->kv->h1buf.p; a.sk_batch = B; a.sk_slices = SK_SLICES_FC2;
                     }
                 }
                 hipError_t e = layer == 0 ? prep_rows<PRO_EMBED>(a, B, st) : prep_rows<PRO_LN>(a, B, st);
@@ -672,53 +677,53 @@ static hipError_t launch_kind_t(er_ctx* c, int kind, int layer, hipStream_t st, 
                 a.xin = c->kv->hbuf.p;
                 a.xt_out = nullptr;
                 if constexpr (HALF) {
-                    if (c->xt) { a.W = L.wqkv_t; a.xin = (const float*)c->kv->xt_h.p; return gemv_mfma_groups<WT, EPI_QKV, true>(a, B, H, SkPart{c->kv->skpart.p, c->kv->skpart.n}, st); }
+                    if (p.xt) { a.W = L.wqkv_t; a.xin = (const float*)c->kv->xt_h.p; return gemv_mfma_groups<WT, EPI_QKV, true>(a, B, H, sk, st); }
                 }
-                if (!c->batched_valu) { a.W = L.wqkv_t; return gemv_mfma_groups<WT, EPI_QKV>(a, B, H, SkPart{c->kv->skpart.p, c->kv->skpart.n}, st); }   // 144 tiles of 32 rows
+                if (p.mfma) { a.W = L.wqkv_t; return gemv_mfma_groups<WT, EPI_QKV>(a, B, H, sk, st); }   // 144 tiles of 32 rows
                 return gemv_batched_groups<WT, 1, 3, EPI_QKV>(a, B, H, st);   // 4608 rows = 192 workgroups x 24: one round
             }
-            if (layer == 0) return gemv_nw<WT, PRO_EMBED, EPI_QKV>(c->nw_qkv, a, B, H, st);
-            return gemv_nw<WT, PRO_LN, EPI_QKV>(c->nw_qkv, a, B, H, st);
+            if (layer == 0) return gemv_nw<WT, PRO_EMBED, EPI_QKV>(c->knobs.nw_qkv, a, B, H, st);
+            return gemv_nw<WT, PRO_LN, EPI_QKV>(c->knobs.nw_qkv, a, B, H, st);
         }
         // v2 holds a wave's whole K/V slice in flight (latency-bound single rows); with hundreds of workgroups per CU's
         // worth of work (B > 4) the leaner v1 (66-74 VGPRs, 6-7 waves per SIMD) streams faster: 570 vs 636 us at B = 32, L = 18050
         case 1:
-            if (c->v3) return launch_attn_partial3_d<96>(attn_args(c, layer), HALF, c->nch3, B, st);
-            if (c->stream_attn) return launch_attn_stream_d<96>(attn_args(c, layer), HALF, B, st);
-            return launch_attn_partial(attn_args(c, layer), c->D, ATTN_STEPS_DEFAULT, HALF, B, st, c->batched ? 1 : 2);
+            if (p.v3) return launch_attn_partial3_d<96>(attn_args(c, layer), HALF, p.nch3, B, st);
+            if (p.stream_attn) return launch_attn_stream_d<96>(attn_args(c, layer), HALF, B, st);
+            return launch_attn_partial(attn_args(c, layer), c->D, ATTN_STEPS_DEFAULT, HALF, B, st, p.batched ? 1 : 2);
         case 2:
-            if (c->v3 || c->stream_attn) return hipSuccess;      // the merge runs inside the out_proj kernel / there are no partials
+            if (!p.sel.merge_launch) return hipSuccess;      // the merge runs inside the out_proj kernel (version 3) / there are no partials (streaming)
             return launch_attn_combine(attn_args(c, layer), c->D, B, st);
         case 3: {   // out_proj + bias + residual(h) -> ypre1
             const LayerW& L = c->layers[layer];
-            if (c->v3) {
+            if (p.v3) {
                 OutMergeArgs m{};
                 m.W = HALF ? (const void*)L.wo_h : (const void*)L.wo; m.bias = L.bo; m.resid = c->kv->hbuf.p; m.out = c->kv->ypre1.p;
                 m.part_o = c->kv->part.p; m.part_ml = c->kv->part_ml.p; m.N = H;
-                return launch_outproj_merge<WT, 96>(m, c->nch3, st);
+                return launch_outproj_merge<WT, 96>(m, p.nch3, st);
             }
             a.W = HALF ? (const void*)L.wo_h : (const void*)L.wo; a.bias = L.bo; a.N = H; a.xin = c->kv->abuf.p; a.out = c->kv->ypre1.p; a.resid = c->kv->hbuf.p;
             // 48 row tiles of 32: the matrix-core kernel runs on 48 CUs only, but streams the matrix ONCE for 32 rows where the
             // VALU kernel needs a pass per 16
-            if (c->batched && !c->batched_valu && B >= 5 && B <= 8) return gemv_outproj_rows8<WT>(a, B, st);
+            if (p.outproj_rows8) return gemv_outproj_rows8<WT>(a, B, st);
             if constexpr (HALF) {
                 // 4-wave workgroups (48 row tiles x 4 K-ranges of 384 instead of 48 x one of 1536); + bias + residual happen in fc1's
                 // LayerNorm-rows launch (case 4), which reads the four partials
-                if (c->xt && c->stream_attn && B > 8) { a.W = L.wo_t; a.xin = (const float*)c->kv->xt_att.p; return gemv_mfma_groups<WT, EPI_RESID, true>(a, B, H, SkPart{c->kv->skpart.p, c->kv->skpart.n}, st, true, true); }
+                if (p.outproj_partials) { a.W = L.wo_t; a.xin = (const float*)c->kv->xt_att.p; return gemv_mfma_groups<WT, EPI_RESID, true>(a, B, H, sk, st, true, true); }
             }
-            if (c->batched && !c->batched_valu) { a.W = L.wo_t; return gemv_mfma_groups<WT, EPI_RESID>(a, B, H, SkPart{c->kv->skpart.p, c->kv->skpart.n}, st); }
-            if (c->batched) return gemv_batched_groups<WT, 1, 1, EPI_RESID>(a, B, H, st);
+            if (p.mfma) { a.W = L.wo_t; return gemv_mfma_groups<WT, EPI_RESID>(a, B, H, sk, st); }
+            if (p.batched) return gemv_batched_groups<WT, 1, 1, EPI_RESID>(a, B, H, st);
             return gemv_groups<WT, 1, 1, PRO_NONE, EPI_RESID, 3>(a, B, H, st);     // 3 waves x 1 row: 512 workgroups = 2 per CU
         }
         case 4: {   // h1 = LN1(ypre1); f = relu(fc1 h1 + b)
             const LayerW& L = c->layers[layer];
             a.W = HALF ? (const void*)L.w1_h : (const void*)L.w1; a.bias = L.b1; a.N = I; a.xin = c->kv->ypre1.p; a.ln_w = L.ln1w; a.ln_b = L.ln1b;
             a.hout = c->kv->h1buf.p; a.out = c->kv->fbuf.p;
-            if (c->batched) {
+            if (p.batched) {
                 if constexpr (HALF) {
-                    a.xt_out = c->xt ? c->kv->xt_h.p : nullptr;
-                    if (c->xt && c->stream_attn && B > 8) {      // out_proj (case 3) left four K-range partials: ypre1 = ((sum) + bo) + h
-                        a.sk_part = c->kv->skpart.p; a.sk_bias = L.bo; a.sk_resid = c->kv->hbuf.p; a.sk_batch = B; a.sk_slices = 4;
+                    a.xt_out = p.xt ? c->kv->xt_h.p : nullptr;
+                    if (p.outproj_partials) {      // out_proj (case 3) left four K-range partials: ypre1 = ((sum) + bo) + h
+                        a.sk_part = sk.p; a.sk_bias = L.bo; a.sk_resid = c->kv->hbuf.p; a.sk_batch = B; a.sk_slices = SK_SLICES_OUTPROJ;
                     }
                 }
                 hipError_t e = prep_rows<PRO_LN>(a, B, st);
@@ -727,15 +732,15 @@ static hipError_t launch_kind_t(er_ctx* c, int kind, int layer, hipStream_t st, 
                 a.xin = c->kv->h1buf.p;
                 a.xt_out = nullptr;
                 if constexpr (HALF) {
-                    if (c->xt) {      // input and output both tiled: fc2 below reads xt_f
+                    if (p.xt) {      // input and output both tiled: fc2 below reads xt_f
                         a.W = L.w1_t; a.xin = (const float*)c->kv->xt_h.p; a.xt_out = c->kv->xt_f.p;
-                        return gemv_mfma_groups<WT, EPI_RELU, true>(a, B, H, SkPart{c->kv->skpart.p, c->kv->skpart.n}, st);
+                        return gemv_mfma_groups<WT, EPI_RELU, true>(a, B, H, sk, st);
                     }
                 }
-                if (!c->batched_valu) { a.W = L.w1_t; return gemv_mfma_groups<WT, EPI_RELU>(a, B, H, SkPart{c->kv->skpart.p, c->kv->skpart.n}, st); }   // 192 tiles of 32 rows
+                if (p.mfma) { a.W = L.w1_t; return gemv_mfma_groups<WT, EPI_RELU>(a, B, H, sk, st); }   // 192 tiles of 32 rows
                 return gemv_batched_groups<WT, 1, 3, EPI_RELU>(a, B, H, st);   // 6144 rows = 256 workgroups x 24
             }
-            return gemv_nw<WT, PRO_LN, EPI_RELU>(c->nw_fc1, a, B, H, st);
+            return gemv_nw<WT, PRO_LN, EPI_RELU>(c->knobs.nw_fc1, a, B, H, st);
         }
         case 5: {   // ypre = fc2 f + b + h1
             const LayerW& L = c->layers[layer];
@@ -744,30 +749,24 @@ static hipError_t launch_kind_t(er_ctx* c, int kind, int layer, hipStream_t st, 
                 // layers 0 .. nl-2 leave the four K-range partials to the next layer's LayerNorm launch (case 0); the last layer finishes
                 // into ypre, which the lm_head reads (after a prefill ypre comes from the GEMM path, so case 6 always reads ypre)
                 // 4-wave workgroups: 48 row tiles x 16 K-ranges of 384 (768 workgroups = 3 per CU instead of 192 on 192 CUs)
-                if (c->xt) { a.W = L.w2_t; a.xin = (const float*)c->kv->xt_f.p; return gemv_mfma_groups<WT, EPI_RESID, true>(a, B, I, SkPart{c->kv->skpart.p, c->kv->skpart.n}, st, layer + 1 < nl, true); }
+                if (p.xt) { a.W = L.w2_t; a.xin = (const float*)c->kv->xt_f.p; return gemv_mfma_groups<WT, EPI_RESID, true>(a, B, I, sk, st, p.fc2_defers(layer), true); }
             }
-            if (c->batched && !c->batched_valu) { a.W = L.w2_t; return gemv_mfma_groups<WT, EPI_RESID>(a, B, I, SkPart{c->kv->skpart.p, c->kv->skpart.n}, st); }   // 48 tiles x 4 K-ranges
-            if (c->batched) return gemv_batched_groups<WT, 4, 1, EPI_RESID>(a, B, I, st);
+            if (p.mfma) { a.W = L.w2_t; return gemv_mfma_groups<WT, EPI_RESID>(a, B, I, sk, st); }   // 48 tiles x 4 K-ranges
+            if (p.batched) return gemv_batched_groups<WT, 4, 1, EPI_RESID>(a, B, I, st);
             if constexpr (HALF) {
                 // fast mode, one row: FAT workgroups like qkv's and fc1's - 4 or 6 rows per workgroup instead of 2 (384 / 256 workgroups
                 // instead of 768), so that a CU fetches the 24 KB input vector once or twice instead of three times beside its 72 KB of
                 // fp16 weights: fc2 5.60 -> 5.37 us at 6 rows, 5.68 at 4, ids unchanged (profiles/r05_ab_fc2_rows.log; ER_RW_FC2 = 2 / 4 / 6)
-                // (read ONCE per process, like every A/B knob of the step graph: the graph is captured with the first value; 2 / 4 / 6 only)
-                static const int rw = [] {
-                    const char* v = getenv("ER_RW_FC2");
-                    const int r = v ? atoi(v) : 6;
-                    if (r != 2 && r != 4 && r != 6) fprintf(stderr, "[edgerunner_hip] ER_RW_FC2=%s is not 2 / 4 / 6: using 2 rows per fc2 workgroup\n", v);
-                    return r;
-                }();
-                if (B == 1 && rw == 6) return launch_gemv<WT, 4, 1, 6, PRO_NONE, EPI_RESID>(a, st);
-                if (B == 1 && rw == 4) return launch_gemv<WT, 4, 1, 4, PRO_NONE, EPI_RESID>(a, st);
+                // (read at er_create, like every A/B knob of the step graph: the graph is captured with that value; 2 / 4 / 6 only)
+                if (B == 1 && c->knobs.rw_fc2 == 6) return launch_gemv<WT, 4, 1, 6, PRO_NONE, EPI_RESID>(a, st);
+                if (B == 1 && c->knobs.rw_fc2 == 4) return launch_gemv<WT, 4, 1, 4, PRO_NONE, EPI_RESID>(a, st);
             }
             return gemv_groups<WT, 4, 2, PRO_NONE, EPI_RESID>(a, B, I, st);
         }
         case 6: {   // logits = lm_head LN2_last(ypre)
             a.W = HALF ? (const void*)c->lm_head_h : (const void*)c->lm_head; a.bias = nullptr; a.N = g.vocab_size; a.xin = c->kv->ypre.p;
-            a.ln_w = c->layers[nl - 1].ln2w; a.ln_b = c->layers[nl - 1].ln2b; a.hout = nullptr; a.out = c->kv->logits.p;
-            if (c->batched) {
+            a.ln_w = c->layers[p.layers - 1].ln2w; a.ln_b = c->layers[p.layers - 1].ln2b; a.hout = nullptr; a.out = c->kv->logits.p;
+            if (p.batched) {
                 a.hout = c->kv->hbuf.p;
                 hipError_t e = prep_rows<PRO_LN>(a, B, st);
                 if (e != hipSuccess) return e;
@@ -1075,8 +1074,8 @@ static hipError_t linear_tail(const float* A, const float* W, const float* bias,
 static int forward_check(er_ctx* c, const char* who, const float* embeds, int B, int S) {
     if (!c || !embeds || B <= 0 || S <= 0) return fail(ER_ERR_INVALID, "%s: bad argument", who);
     ERCHK(er_finalize_weights(c));
-    if (c->B != B) return fail(ER_ERR_INVALID, "%s: batch %d but KV cache reserved for %d (call er_kv_reserve)", who, B, c->B);
-    if (S >= c->Lcap) return fail(ER_ERR_CAPACITY, "prefix length %d does not fit the reserved KV cache (%d)", S, c->Lcap);
+    if (c->kv->plan.B != B) return fail(ER_ERR_INVALID, "%s: batch %d but KV cache reserved for %d (call er_kv_reserve)", who, B, c->kv->plan.B);
+    if (S >= c->kv->plan.Lcap) return fail(ER_ERR_CAPACITY, "prefix length %d does not fit the reserved KV cache (%d)", S, c->kv->plan.Lcap);
     const long long width = std::max({(long long)c->cfg.intermediate_dim, 3LL * c->cfg.hidden_dim, (long long)c->cfg.vocab_size});
     if ((long long)B * S * width > 0x7fffffffLL)
         return fail(ER_ERR_CAPACITY, "%s: %d x %d positions x %lld columns overflows the 32-bit row indexing of the prefill (split the batch)",
@@ -1088,7 +1087,8 @@ static int forward_check(er_ctx* c, const char* who, const float* embeds, int B,
 // c->p_y [B * S][hidden], the last position's copy in ypre and the generation state at position S (what er_prefill promises)
 static int prefill_run(er_ctx* c, const float* embeds, int B, int S, hipStream_t st) {
     HIPCHK(hipSetDevice(c->device));
-    if (c->batched && !c->batched_valu) ERCHK(make_tiled_weights(c));
+    const DecodePlan& p = c->kv->plan;
+    if (p.mfma) ERCHK(make_tiled_weights(c));
     const er_config& g = c->cfg;
     const int H = g.hidden_dim, I = g.intermediate_dim, NH = g.num_heads, D = c->D;
     const int M = B * S;
@@ -1112,21 +1112,21 @@ static int prefill_run(er_ctx* c, const float* embeds, int B, int S, hipStream_t
     HIPRET(hipGetLastError());
     for (int l = 0; l < g.num_layers; ++l) {
         const LayerW& L = c->layers[l];
-        char* kc = c->kv->kc.p + (long long)l * c->kv_lstride * c->kv_esz;
-        char* vc = c->kv->vc.p + (long long)l * c->kv_lstride * c->kv_esz;
+        char* kc = c->kv->kc.p + (long long)l * p.kv_lstride * c->kv_esz;
+        char* vc = c->kv->vc.p + (long long)l * p.kv_lstride * c->kv_esz;
         if (!c->fast) {
             // q,k,v projections; k,v go straight into the cache layout      modeling_opt.py:185-196
             GemmArgs qa = gemm_args_default();
             qa.A = h; qa.lda = H; qa.B = L.wqkv; qa.ldb = H; qa.bias = L.bqkv; qa.C = q; qa.ldc = H;
             qa.M = M; qa.N = 3 * H; qa.K = H; qa.epi = GEPI_QKV;
-            qa.q = q; qa.kcache = (float*)kc; qa.vcache = (float*)vc; qa.S = S; qa.hidden = H; qa.head_dim = D; qa.l_cap = c->Lcap;
-            qa.kv_bstride = c->kv_bstride;
+            qa.q = q; qa.kcache = (float*)kc; qa.vcache = (float*)vc; qa.S = S; qa.hidden = H; qa.head_dim = D; qa.l_cap = p.Lcap;
+            qa.kv_bstride = p.kv_bstride;
             HIPRET(launch_gemm(qa, 1, st));
             {       // causal attention over the prefix, all samples and heads in one launch   modeling_opt.py:229
                 Flash32Args f{};
                 f.Q = q; f.ldq = H; f.qs_b = (long long)S * H; f.qs_h = D;
-                f.K = (float*)kc; f.ldk = D; f.ks_b = c->kv_bstride; f.ks_h = (long long)c->Lcap * D;
-                f.V = (float*)vc; f.ldv = D; f.vs_b = c->kv_bstride; f.vs_h = (long long)c->Lcap * D;
+                f.K = (float*)kc; f.ldk = D; f.ks_b = p.kv_bstride; f.ks_h = (long long)p.Lcap * D;
+                f.V = (float*)vc; f.ldv = D; f.vs_b = p.kv_bstride; f.vs_h = (long long)p.Lcap * D;
                 f.O = a; f.ldo = H; f.os_b = (long long)S * H; f.os_h = D;
                 f.N = S; f.M = S; f.sqrt_d = sqrtf((float)D); f.causal_off = 0;
                 if (attn_ksplit) { f.part_o = c->p_ap.p; f.part_ml = c->p_aml.p; }
@@ -1139,7 +1139,7 @@ static int prefill_run(er_ctx* c, const float* embeds, int B, int S, hipStream_t
             float* qkv = c->p_qkv.p;
             ERCHK(linear_hs(c, h, H, L.wqkv_h, L.bqkv, qkv, 3 * H, M, 3 * H, H, false, nullptr, 0, st));
             hipLaunchKernelGGL(kv_scatter_half_kernel, kv_scatter_grid(M, H), dim3(ER_WG), 0, st, qkv,
-                               (_Float16*)kc, (_Float16*)vc, M, S, H, D, c->Lcap, c->kv_bstride);
+                               (_Float16*)kc, (_Float16*)vc, M, S, H, D, p.Lcap, p.kv_bstride);
             HIPRET(hipGetLastError());
             {
                 Flash32Args f{};
@@ -1148,7 +1148,7 @@ static int prefill_run(er_ctx* c, const float* embeds, int B, int S, hipStream_t
                 f.V = qkv + 2 * H; f.ldv = 3 * H; f.vs_b = f.qs_b; f.vs_h = D;
                 f.O = a; f.ldo = H; f.os_b = (long long)S * H; f.os_h = D;
                 f.N = S; f.M = S; f.sqrt_d = sqrtf((float)D); f.causal_off = 0;
-                const bool f16s = D == 96 && c->prefill_attn_f16s != 0;
+                const bool f16s = D == 96 && c->knobs.prefill_attn_f16s != 0;
                 if (f16s) HIPRET(launch_flash_attn_f16s(f, D, true, NH, B, st));   // K / V in the scratch are fp16 values already
                 else HIPRET(launch_flash_attn_f32(f, D, true, NH, B, st));
             }
@@ -1238,7 +1238,7 @@ extern "C" int er_logits(er_ctx* c, float* out, void* stream) {
     HIPCHK(hipSetDevice(c->device));
     hipStream_t st = pick(c, stream);
     HIPRET(launch_kind(c, 6, 0, st, nullptr, 0));
-    HIPCHK(hipMemcpyAsync(out, c->kv->logits.p, (size_t)c->B * c->cfg.vocab_size * 4, hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipMemcpyAsync(out, c->kv->logits.p, (size_t)c->kv->plan.B * c->cfg.vocab_size * 4, hipMemcpyDeviceToDevice, st));
     return ER_OK;
 }
 
@@ -1246,7 +1246,7 @@ static int check_room(er_ctx* c, int extra) {
     // generated token t is fed at position base_pos + t
     HIPCHK(hipMemcpy(c->h_pinned, c->kv->st.ngen, sizeof(int), hipMemcpyDeviceToHost));
     const int used = c->base_pos + c->h_pinned[0];
-    if (used + extra > c->Lcap) return fail(ER_ERR_CAPACITY, "KV cache full: %d + %d > %d", used, extra, c->Lcap);
+    if (used + extra > c->kv->plan.Lcap) return fail(ER_ERR_CAPACITY, "KV cache full: %d + %d > %d", used, extra, c->kv->plan.Lcap);
     if (used + extra > c->cfg.max_positions) return fail(ER_ERR_CAPACITY, "position table exhausted (%d)", c->cfg.max_positions);
     return 0;
 }
@@ -1258,12 +1258,13 @@ extern "C" int er_feed(er_ctx* c, const int32_t* ids, void* stream) {
     hipStream_t st = pick(c, stream);
     HIPCHK(hipStreamSynchronize(st));
     ERCHK(check_room(c, 1));
-    for (int b = 0; b < c->B; ++b) {
+    const int B = c->kv->plan.B;
+    for (int b = 0; b < B; ++b) {
         if (ids[b] < 0 || ids[b] >= c->cfg.vocab_size) return fail(ER_ERR_INVALID, "token id %d out of range", ids[b]);
         c->h_pinned[b] = ids[b];
     }
-    HIPCHK(hipMemcpyAsync(c->kv->d_ids_tmp.p, c->h_pinned, c->B * sizeof(int), hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(force_token_kernel, dim3((c->B + 63) / 64), dim3(64), 0, st, c->kv->d_ids_tmp.p, c->kv->st, c->B);
+    HIPCHK(hipMemcpyAsync(c->kv->d_ids_tmp.p, c->h_pinned, B * sizeof(int), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(force_token_kernel, dim3((B + 63) / 64), dim3(64), 0, st, c->kv->d_ids_tmp.p, c->kv->st, B);
     HIPRET(hipGetLastError());
     HIPRET(enqueue_layers(c, st));
     HIPCHK(hipStreamSynchronize(st));   // h_pinned may be reused by the next call
@@ -1290,7 +1291,7 @@ extern "C" int er_decode(er_ctx* c, const er_decode_params* p, int64_t* out_ids,
     if (p->mode == ER_SAMPLE && p->top_k <= 0) return fail(ER_ERR_INVALID, "top_k must be > 0 in sample mode");
     HIPCHK(hipSetDevice(c->device));
     hipStream_t st = pick(c, stream);
-    const int B = c->B, T = p->max_new_tokens;
+    const int B = c->kv->plan.B, Lcap = c->kv->plan.Lcap, T = p->max_new_tokens;
     HIPCHK(hipStreamSynchronize(st));
     ERCHK(check_room(c, T));
     if (c->h_pinned[0] != 0) return fail(ER_ERR_INVALID, "er_decode must directly follow er_prefill (%d tokens already fed)", c->h_pinned[0]);
@@ -1302,15 +1303,15 @@ extern "C" int er_decode(er_ctx* c, const er_decode_params* p, int64_t* out_ids,
     HIPCHK(hipMemcpy(c->kv->d_params.p, &dp, sizeof(dp), hipMemcpyHostToDevice));
     hipLaunchKernelGGL(reset_gen_kernel, dim3((B + 63) / 64), dim3(64), 0, st, c->kv->st, B);
     HIPRET(hipGetLastError());
-    hipLaunchKernelGGL(fill_i64_kernel, dim3(ew_grid((long long)B * c->Lcap)), dim3(ER_WG), 0, st, c->kv->d_out_ids.p,
-                       (long long)B * c->Lcap, (long long)dp.pad);
+    hipLaunchKernelGGL(fill_i64_kernel, dim3(ew_grid((long long)B * Lcap)), dim3(ER_WG), 0, st, c->kv->d_out_ids.p,
+                       (long long)B * Lcap, (long long)dp.pad);
     HIPRET(hipGetLastError());
 
     // one step = lm_head -> sampling head -> 24 layers on the chosen token; captured once, replayed T times
-    if (c->use_graph && !c->kv->step_exec) {
+    if (c->knobs.use_graph && !c->kv->step_exec) {
         hipGraph_t graph = nullptr;
         HIPCHK(hipStreamBeginCapture(c->own_stream, hipStreamCaptureModeRelaxed));
-        hipError_t e = enqueue_step(c, c->own_stream, c->kv->d_out_ids.p, c->Lcap);
+        hipError_t e = enqueue_step(c, c->own_stream, c->kv->d_out_ids.p, Lcap);
         hipError_t e2 = hipStreamEndCapture(c->own_stream, &graph);
         if (e != hipSuccess || e2 != hipSuccess) {
             if (graph) hipGraphDestroy(graph);
@@ -1322,20 +1323,19 @@ extern "C" int er_decode(er_ctx* c, const er_decode_params* p, int64_t* out_ids,
 
     const int check_every = 32;
     int steps_run = 0;
-    bool all_done = false;
     HIPCHK(hipEventRecord(c->ev0, st));
     for (int t = 0; t < T; ++t) {
-        if (c->use_graph) HIPCHK(hipGraphLaunch(c->kv->step_exec, st));
-        else HIPRET(enqueue_step(c, st, c->kv->d_out_ids.p, c->Lcap));
+        if (c->knobs.use_graph) HIPCHK(hipGraphLaunch(c->kv->step_exec, st));
+        else HIPRET(enqueue_step(c, st, c->kv->d_out_ids.p, Lcap));
         steps_run = t + 1;
         if (steps_run >= p->min_new_tokens && steps_run < T && (steps_run % check_every) == 0) {
             HIPCHK(hipMemcpyAsync(c->h_pinned, c->kv->st.n_unfinished, sizeof(int), hipMemcpyDeviceToHost, st));
             HIPCHK(hipStreamSynchronize(st));
-            if (c->h_pinned[0] <= 0) { all_done = true; break; }
+            if (c->h_pinned[0] <= 0) break;
         }
     }
     HIPCHK(hipEventRecord(c->ev1, st));
-    HIPCHK(hipMemcpy2DAsync(out_ids, (size_t)T * sizeof(long long), c->kv->d_out_ids.p, (size_t)c->Lcap * sizeof(long long),
+    HIPCHK(hipMemcpy2DAsync(out_ids, (size_t)T * sizeof(long long), c->kv->d_out_ids.p, (size_t)Lcap * sizeof(long long),
                             (size_t)T * sizeof(long long), B, hipMemcpyDeviceToDevice, st));
     HIPCHK(hipMemcpyAsync(c->h_pinned, c->kv->st.eos_step, B * sizeof(int), hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(c->h_pinned + B, c->kv->st.error, sizeof(int), hipMemcpyDeviceToHost, st));
@@ -1343,7 +1343,6 @@ extern "C" int er_decode(er_ctx* c, const er_decode_params* p, int64_t* out_ids,
     HIPCHK(hipEventElapsedTime(&c->last_decode_ms, c->ev0, c->ev1));
     if (c->h_pinned[B] != 0)
         return fail(ER_ERR_INVALID, "er_decode: a row had no finite candidate score (non-finite logits); HF would raise in multinomial/argmax");
-    (void)all_done;
     // HF returns as many columns as steps it ran: it stops right after the step in which the last row emits EOS
     int last = -1;
     bool finished = true;
@@ -1358,11 +1357,12 @@ extern "C" int er_decode(er_ctx* c, const er_decode_params* p, int64_t* out_ids,
 
 extern "C" int er_set_row_streams(er_ctx* c, const uint32_t* ids, int n) {
     if (!c) return fail(ER_ERR_INVALID, "er_set_row_streams: null context");
-    if (c->B <= 0) return fail(ER_ERR_INVALID, "er_set_row_streams: no cache reserved (call er_kv_reserve)");
-    if (ids && n != c->B) return fail(ER_ERR_INVALID, "er_set_row_streams: %d ids for a batch of %d rows", n, c->B);
+    const int B = c->kv->plan.B;
+    if (B <= 0) return fail(ER_ERR_INVALID, "er_set_row_streams: no cache reserved (call er_kv_reserve)");
+    if (ids && n != B) return fail(ER_ERR_INVALID, "er_set_row_streams: %d ids for a batch of %d rows", n, B);
     HIPCHK(hipSetDevice(c->device));
-    std::vector<unsigned int> h((size_t)c->B);
-    for (int i = 0; i < c->B; ++i) h[i] = ids ? ids[i] : (unsigned int)i;
+    std::vector<unsigned int> h((size_t)B);
+    for (int i = 0; i < B; ++i) h[i] = ids ? ids[i] : (unsigned int)i;
     HIPCHK(hipDeviceSynchronize());           // a running decode still reads the old ids
     HIPCHK(hipMemcpy(c->kv->d_row_stream.p, h.data(), h.size() * sizeof(unsigned int), hipMemcpyHostToDevice));
     return ER_OK;
@@ -1384,7 +1384,7 @@ extern "C" int er_profile_decode_kernels(er_ctx* c, int repeats, float* avg_us, 
 extern "C" int er_profile_decode_kernels_at(er_ctx* c, int repeats, int context_len, int use_graph, float* avg_us, double* bytes,
                                             void* stream) {
     if (!c) return fail(ER_ERR_INVALID, "er_profile_decode_kernels: bad argument");
-    if (context_len < 0 || context_len > c->Lcap) return fail(ER_ERR_CAPACITY, "profile: context_len %d outside the reserved cache (%d)", context_len, c->Lcap);
+    if (context_len < 0 || context_len > c->kv->plan.Lcap) return fail(ER_ERR_CAPACITY, "profile: context_len %d outside the reserved cache (%d)", context_len, c->kv->plan.Lcap);
     c->prof_len = context_len;
     const int rc = profile_impl(c, repeats, use_graph, avg_us, bytes, stream);
     c->prof_len = 0;
@@ -1397,7 +1397,8 @@ static int profile_impl(er_ctx* c, int repeats, int use_graph, float* avg_us, do
     HIPCHK(hipSetDevice(c->device));
     hipStream_t st = pick(c, stream);
     const er_config& g = c->cfg;
-    const int B = c->B, H = g.hidden_dim, I = g.intermediate_dim, nl = g.num_layers, V = g.vocab_size;
+    const DecodePlan& p = c->kv->plan;
+    const int B = p.B, H = g.hidden_dim, I = g.intermediate_dim, nl = g.num_layers, V = g.vocab_size;
     HIPCHK(hipStreamSynchronize(st));
     HIPCHK(hipMemcpy(c->h_pinned, c->kv->st.pos, sizeof(int), hipMemcpyDeviceToHost));
     const double len = c->prof_len > 0 ? (double)c->prof_len : (double)c->h_pinned[0] + 1.0;
@@ -1419,20 +1420,20 @@ static int profile_impl(er_ctx* c, int repeats, int use_graph, float* avg_us, do
     const double w = c->fast ? 2.0 : 4.0;   // bytes per streamed weight / KV element
     bytes[0] = ((double)3 * H * H + 3 * H) * w + (double)B * (H + 3 * H) * w;
     bytes[1] = (double)B * 2.0 * len * H * w;
-    bytes[2] = (double)B * g.num_heads * c->S_splits * (c->D + 2) * w + (double)B * H * w;
+    bytes[2] = (double)B * g.num_heads * p.S_splits * (c->D + 2) * w + (double)B * H * w;
     bytes[3] = ((double)H * H + H) * w + (double)B * 3 * H * w;
     bytes[4] = ((double)I * H + I) * w + (double)B * (H + I) * w;
     bytes[5] = ((double)I * H + H) * w + (double)B * (I + 2 * H) * w;
     bytes[6] = ((double)V * H) * w + (double)B * (H + V) * w;
     bytes[7] = (double)B * V * w;
 
-    if (c->v3) {   // the merge is part of the out_proj launch: its partial reads are charged there
-        bytes[3] += (double)g.num_heads * c->nch3 * (c->D + 2) * 4.0;
+    if (p.v3) {   // the merge is part of the out_proj launch: its partial reads are charged there
+        bytes[3] += (double)g.num_heads * p.nch3 * (c->D + 2) * 4.0;
         bytes[2] = 0.0;
     }
     for (int kind = 0; kind < ER_NUM_KERNEL_KINDS; ++kind) {
         const bool per_layer = kind <= 5;
-        if ((c->v3 || c->stream_attn) && kind == 2) { avg_us[kind] = 0.f; continue; }
+        if (!p.sel.merge_launch && kind == 2) { avg_us[kind] = 0.f; continue; }
         // warm-up + timed sweeps
         hipGraphExec_t gexec = nullptr;
         if (use_graph && per_layer) {     // the nl launches of this kind as one replayable graph (what the generation loop replays)
@@ -1496,8 +1497,7 @@ extern "C" int er_k_gemv(const float* w, const float* bias, const float* x, cons
         DevBuf<char> wt;                 // tiled copy of w for the matrix-core kernels (the decode step keeps one per matrix)
         if (ln_w && k != 1536) return fail(ER_ERR_UNSUPPORTED, "er_k_gemv: LayerNorm prologue needs k=1536");
         if (ln_w && !xnorm_out) ERCHK(tmp.ensure((size_t)B * k));
-        const char* bv = getenv("ER_BATCHED_VALU");
-        const bool valu = bv && bv[0] == '1';
+        const bool valu = env_is("ER_BATCHED_VALU", '1');
         const bool mfma = !valu && ((k == 1536 && relu && !resid) || (k == 6144 && !relu && resid && !ln_w));
         if (mfma) {
             ERCHK(part.ensure((size_t)4 * NBM * n));
@@ -1694,8 +1694,7 @@ extern "C" int er_k_gemm_f16s(const float* a, const void* w, const float* bias, 
     g.A = a; g.B = reinterpret_cast<const float*>(w); g.C = cc; g.bias = bias; g.resid = resid; g.M = m; g.N = n; g.K = k;
     g.lda = lda; g.ldb = ldb; g.ldc = ldc; g.ldr = ldc; g.relu = relu;
     // ER_K_GEMM_F16S_FORM = reg / dma pins one of the two forms linear_hs chooses between (unit tests compare them bit for bit)
-    const char* form = getenv("ER_K_GEMM_F16S_FORM");
-    const bool force_reg = form && form[0] == 'r';
+    const bool force_reg = env_is("ER_K_GEMM_F16S_FORM", 'r');
     if (k % XBK == 0 && !(ldb & 7) && !force_reg) {      // the product path of the fast-mode prefill: split pass + LDS-DMA kernel (linear_hs)
         DevBuf<_Float16> hi, lo;
         ERCHK(hi.ensure((size_t)m * k));

@@ -262,8 +262,9 @@ int er_dit_loss(er_dit_ctx* ctx, const float* latents_dev, const float* noise_de
                 float* mse_out_dev, float* loss_out_dev, void* stream);
 
 /* ---- which kernels a decode context of this shape runs (pure host logic: callable without a device) ----
- * The rules live in ONE function that er_kv_reserve applies and this entry point reports; the environment knobs of
- * er_create (ER_DECODE_V, ER_ATTN_V_BATCHED, ER_FORCE_BATCHED) are honoured, l_cap is rounded up to 32 like er_kv_reserve. */
+ * The rules live in ONE function.  er_kv_reserve evaluates it once for the shape it reserves and stores the result, with everything
+ * the step derives from it, beside that shape's memory; er_plan_decode evaluates it for a hypothetical shape under the environment
+ * of the call (ER_DECODE_V, ER_ATTN_V_BATCHED, ER_FORCE_BATCHED are honoured, l_cap is rounded up to 32 like er_kv_reserve). */
 typedef enum { ER_ATTN_SPLIT1 = 1, ER_ATTN_SPLIT2 = 2, ER_ATTN_BALANCED = 3, ER_ATTN_STREAM = 4 } er_attn_kernel;
 typedef struct {
     int32_t batched;            /* 1: B > 4 path (matrix-core projections, weights once per 32 rows) */
@@ -275,7 +276,7 @@ typedef struct {
                                    layers x this + lm_head + sample_head launches */
 } er_decode_plan;
 int er_plan_decode(int batch, int heads, int head_dim, int hidden, int l_cap, er_decode_plan* out);
-/* the plan of a live context (knobs as read by er_create, cache as reserved by the last er_kv_reserve) */
+/* the stored plan of a live context (knobs as read by er_create, cache and ER_FORCE_BATCHED as of the last er_kv_reserve) */
 int er_ctx_plan(er_ctx* ctx, er_decode_plan* out);
 /* tile shape launch_gemm* picks for an [m, n] output in `batch` slices: 1 = 128x128, 2 = 64x128, 3 = 64x64 (ER_GEMM_TILE forces) */
 int er_plan_gemm_tile(int m, int n, int batch);
