@@ -33,6 +33,7 @@
 #include "k_fidelity.h"
 #include "meto_decode.h"
 #include "meto_encode.h"
+#include "er_queue_host.h"
 
 using namespace er;
 
@@ -142,6 +143,7 @@ struct KvMem {
     DevBuf<DecodeParamsDev> d_params;
     DevBuf<int> d_ids_tmp;
     DevBuf<unsigned int> d_row_stream;   // [B] Philox stream id per row (identity until er_set_row_streams)
+    DevBuf<int> d_row_budget;     // [B] token budget per row: INT_MAX (= er_decode's max_new_tokens decides) outside the queue mode
     DevBuf<long long> d_out_ids;  // [B][Lcap] generated ids (graph writes here; copied to the caller at the end)
     hipGraphExec_t step_exec = nullptr;  // hipGraph of one step
     KvMem() = default;
@@ -192,6 +194,10 @@ struct er_ctx {
     DevBuf<float> p_h, p_q, p_a, p_y, p_f, p_qkv, p_ap, p_aml, e_tmp;
     DevBuf<int> e_ids;             // er_embed_tokens: the ids on the device
     DevBuf<float> s_lg;            // er_score: logits of every position when the caller passes no buffer for them
+    // queue mode (er_queue_*): the host's view of the rows, the staging of an admission and of a look at the rows
+    erq::QueueHost q;
+    DevBuf<int> q_stage, q_look;   // [2 n_rows] stream ids | budgets of an admission; [3 B + 1] ngen | unfinished | eos_step | error
+    int* q_pinned = nullptr;       // host image of q_look
 };
 
 constexpr int ER_MAX_BATCH = 1023;   // h_pinned holds B ints + one flag
@@ -338,6 +344,7 @@ extern "C" int er_destroy(er_ctx* c) {
     if (c->ev0) hipEventDestroy(c->ev0);
     if (c->ev1) hipEventDestroy(c->ev1);
     if (c->h_pinned) hipHostFree(c->h_pinned);
+    if (c->q_pinned) hipHostFree(c->q_pinned);
     if (c->own_stream) hipStreamDestroy(c->own_stream);
     delete c;
     return ER_OK;
@@ -449,6 +456,7 @@ extern "C" int er_kv_reserve(er_ctx* c, int batch, int max_len) {
     HIPCHK(hipDeviceSynchronize());
     c->kv = std::make_unique<KvMem>();           // first: the old shape's memory makes room for the new one (this plan says: no cache)
     c->have_hidden = false;
+    c->q.end();                                  // a queue lives on the rows of one reserved shape
     auto m = std::make_unique<KvMem>();
     ERCHK(kv_alloc(c, *m, batch, Lcap));         // a failed hipMalloc half way leaves nothing behind: m and its plan die here
     c->kv = std::move(m);                        // buffers and plan of the new shape, in one step
@@ -491,6 +499,12 @@ static int kv_alloc(er_ctx* c, KvMem& m, int batch, int Lcap) {
         HIPCHK(hipMemcpy(m.d_row_stream.p, ident.data(), b * sizeof(unsigned int), hipMemcpyHostToDevice));
     }
     m.st.row_stream = m.d_row_stream.p;
+    ERCHK(m.d_row_budget.ensure(b));
+    {
+        const std::vector<int> open(b, 0x7fffffff);
+        HIPCHK(hipMemcpy(m.d_row_budget.p, open.data(), b * sizeof(int), hipMemcpyHostToDevice));
+    }
+    m.st.row_budget = m.d_row_budget.p;
     ERCHK(m.d_out_ids.ensure(b * (size_t)Lcap));
     if (p.mfma) ERCHK(make_tiled_weights(c));
     // split-K partials of the batched projections.  A finish launched right behind its producer re-uses ONE [4][32][N] block; only the
@@ -1073,6 +1087,7 @@ static hipError_t linear_tail(const float* A, const float* W, const float* bias,
 // such a product must stay below 2^31 (B = 8 at S = 43 011 and intermediate_dim 6144 is 2.11e9 - the edge).
 static int forward_check(er_ctx* c, const char* who, const float* embeds, int B, int S) {
     if (!c || !embeds || B <= 0 || S <= 0) return fail(ER_ERR_INVALID, "%s: bad argument", who);
+    if (c->q.active) return fail(ER_ERR_INVALID, "%s: a queue is open on this context (er_queue_end first)", who);
     ERCHK(er_finalize_weights(c));
     if (c->kv->plan.B != B) return fail(ER_ERR_INVALID, "%s: batch %d but KV cache reserved for %d (call er_kv_reserve)", who, B, c->kv->plan.B);
     if (S >= c->kv->plan.Lcap) return fail(ER_ERR_CAPACITY, "prefix length %d does not fit the reserved KV cache (%d)", S, c->kv->plan.Lcap);
@@ -1084,8 +1099,11 @@ static int forward_check(er_ctx* c, const char* who, const float* embeds, int B,
 }
 
 // all layers over inputs_embeds [B, S, hidden]: K/V into cache positions [0, S), the last layer's pre-LN2 output of EVERY position in
-// c->p_y [B * S][hidden], the last position's copy in ypre and the generation state at position S (what er_prefill promises)
-static int prefill_run(er_ctx* c, const float* embeds, int B, int S, hipStream_t st) {
+// c->p_y [B * S][hidden], the last position's copy in ypre and the generation state at position S (what er_prefill promises).
+// row0 >= 0 with in_queue: the B samples are cache rows [row0, row0 + B) of a larger reservation (er_queue_admit) - the cache base
+// pointers move by row0 rows, ypre receives rows [row0, row0 + B), and the generation state is left to the caller, so that no other
+// row is touched.
+static int prefill_run(er_ctx* c, const float* embeds, int B, int S, hipStream_t st, int row0 = 0, bool in_queue = false) {
     HIPCHK(hipSetDevice(c->device));
     const DecodePlan& p = c->kv->plan;
     if (p.mfma) ERCHK(make_tiled_weights(c));
@@ -1112,8 +1130,8 @@ static int prefill_run(er_ctx* c, const float* embeds, int B, int S, hipStream_t
     HIPRET(hipGetLastError());
     for (int l = 0; l < g.num_layers; ++l) {
         const LayerW& L = c->layers[l];
-        char* kc = c->kv->kc.p + (long long)l * p.kv_lstride * c->kv_esz;
-        char* vc = c->kv->vc.p + (long long)l * p.kv_lstride * c->kv_esz;
+        char* kc = c->kv->kc.p + ((long long)l * p.kv_lstride + (long long)row0 * p.kv_bstride) * c->kv_esz;
+        char* vc = c->kv->vc.p + ((long long)l * p.kv_lstride + (long long)row0 * p.kv_bstride) * c->kv_esz;
         if (!c->fast) {
             // q,k,v projections; k,v go straight into the cache layout      modeling_opt.py:185-196
             GemmArgs qa = gemm_args_default();
@@ -1175,7 +1193,8 @@ static int prefill_run(er_ctx* c, const float* embeds, int B, int S, hipStream_t
     }
     // keep the last position's pre-LN2 state: the decode head applies LN2 + lm_head to it
     for (int b = 0; b < B; ++b)
-        HIPCHK(hipMemcpyAsync(c->kv->ypre.p + (size_t)b * H, y + ((size_t)b * S + S - 1) * H, (size_t)H * 4, hipMemcpyDeviceToDevice, st));
+        HIPCHK(hipMemcpyAsync(c->kv->ypre.p + (size_t)(row0 + b) * H, y + ((size_t)b * S + S - 1) * H, (size_t)H * 4, hipMemcpyDeviceToDevice, st));
+    if (in_queue) return ER_OK;
     hipLaunchKernelGGL(init_state_kernel, dim3((B + 63) / 64), dim3(64), 0, st, c->kv->st, B, S);
     HIPRET(hipGetLastError());
     c->base_pos = S;
@@ -1282,6 +1301,24 @@ __global__ void reset_gen_kernel(GenState st, int B) {
     st.counter[b] = 0; st.unfinished[b] = 1; st.eos_step[b] = -1;
 }
 
+// one step = lm_head -> sampling head -> 24 layers on the chosen token; captured once per reserved shape, replayed by er_decode and
+// er_queue_run
+static int ensure_step_graph(er_ctx* c) {
+    if (!c->knobs.use_graph || c->kv->step_exec) return 0;
+    const int Lcap = c->kv->plan.Lcap;
+    hipGraph_t graph = nullptr;
+    HIPCHK(hipStreamBeginCapture(c->own_stream, hipStreamCaptureModeRelaxed));
+    hipError_t e = enqueue_step(c, c->own_stream, c->kv->d_out_ids.p, Lcap);
+    hipError_t e2 = hipStreamEndCapture(c->own_stream, &graph);
+    if (e != hipSuccess || e2 != hipSuccess) {
+        if (graph) hipGraphDestroy(graph);
+        return fail(ER_ERR_HIP, "graph capture failed: %s / %s", hipGetErrorString(e), hipGetErrorString(e2));
+    }
+    HIPCHK(hipGraphInstantiate(&c->kv->step_exec, graph, nullptr, nullptr, 0));
+    hipGraphDestroy(graph);
+    return 0;
+}
+
 extern "C" int er_decode(er_ctx* c, const er_decode_params* p, int64_t* out_ids, int32_t* n_steps, void* stream) {
     if (!c || !p || !out_ids || !n_steps) return fail(ER_ERR_INVALID, "er_decode: bad argument");
     if (!c->have_hidden) return fail(ER_ERR_INVALID, "er_decode: call er_prefill first");
@@ -1307,19 +1344,7 @@ extern "C" int er_decode(er_ctx* c, const er_decode_params* p, int64_t* out_ids,
                        (long long)B * Lcap, (long long)dp.pad);
     HIPRET(hipGetLastError());
 
-    // one step = lm_head -> sampling head -> 24 layers on the chosen token; captured once, replayed T times
-    if (c->knobs.use_graph && !c->kv->step_exec) {
-        hipGraph_t graph = nullptr;
-        HIPCHK(hipStreamBeginCapture(c->own_stream, hipStreamCaptureModeRelaxed));
-        hipError_t e = enqueue_step(c, c->own_stream, c->kv->d_out_ids.p, Lcap);
-        hipError_t e2 = hipStreamEndCapture(c->own_stream, &graph);
-        if (e != hipSuccess || e2 != hipSuccess) {
-            if (graph) hipGraphDestroy(graph);
-            return fail(ER_ERR_HIP, "graph capture failed: %s / %s", hipGetErrorString(e), hipGetErrorString(e2));
-        }
-        HIPCHK(hipGraphInstantiate(&c->kv->step_exec, graph, nullptr, nullptr, 0));
-        hipGraphDestroy(graph);
-    }
+    ERCHK(ensure_step_graph(c));
 
     const int check_every = 32;
     int steps_run = 0;
@@ -1366,6 +1391,179 @@ extern "C" int er_set_row_streams(er_ctx* c, const uint32_t* ids, int n) {
     HIPCHK(hipDeviceSynchronize());           // a running decode still reads the old ids
     HIPCHK(hipMemcpy(c->kv->d_row_stream.p, h.data(), h.size() * sizeof(unsigned int), hipMemcpyHostToDevice));
     return ER_OK;
+}
+
+// ------------------------------------------------------------------------------------ queue mode (continuous batching)
+// A free row: budget 0 (sample_head_kernel returns before it reads or writes anything of the row) and position 0 (its forward writes
+// K/V slot 0 of its own slice and attends that one key).  Nothing of it grows, and nothing reads what its forward leaves.
+__global__ void queue_park_kernel(GenState st, int* budget, int row0, int n) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int b = row0 + i;
+    st.tok[b] = 0; st.pos[b] = 0; st.counter[b] = 0; st.ngen[b] = 0;
+    st.unfinished[b] = 0; st.eos_step[b] = -1; st.base_pos[b] = 0;
+    budget[b] = 0;
+}
+// The generation state of rows [row0, row0 + n) right after their prefill of S positions (init_state_kernel for a row range), with the
+// rows' Philox stream ids and budgets from stage = {ids[n], budgets[n]}.
+__global__ void queue_admit_kernel(GenState st, unsigned int* row_stream, int* budget, const int* stage, int row0, int n, int S) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int b = row0 + i;
+    st.tok[b] = 0; st.pos[b] = S; st.counter[b] = 0; st.ngen[b] = 0;
+    st.unfinished[b] = 1; st.eos_step[b] = -1; st.base_pos[b] = S;
+    row_stream[b] = (unsigned int)stage[i];
+    budget[b] = stage[n + i];
+}
+// What the host looks at between two bursts, in one block: look = {ngen[B], unfinished[B], eos_step[B], error}.
+__global__ void queue_look_kernel(GenState st, int B, int* look) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b == 0) look[3 * B] = *st.error;
+    if (b >= B) return;
+    look[b] = st.ngen[b]; look[B + b] = st.unfinished[b]; look[2 * B + b] = st.eos_step[b];
+}
+__global__ void fill_i32_kernel(int* p, int n, int v) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) p[i] = v;
+}
+
+static int queue_open(er_ctx* c, const char* who) {
+    if (!c) return fail(ER_ERR_INVALID, "%s: null context", who);
+    if (!c->q.active) return fail(ER_ERR_INVALID, "%s: no queue is open (call er_queue_begin)", who);
+    HIPCHK(hipSetDevice(c->device));
+    return 0;
+}
+
+extern "C" int er_queue_begin(er_ctx* c, const er_decode_params* p, int check_every, void* stream) {
+    if (!c || !p) return fail(ER_ERR_INVALID, "er_queue_begin: bad argument");
+    if (c->q.active) return fail(ER_ERR_INVALID, "er_queue_begin: a queue is already open (er_queue_end first)");
+    const int B = c->kv->plan.B, Lcap = c->kv->plan.Lcap;
+    if (B <= 0) return fail(ER_ERR_INVALID, "er_queue_begin: no cache reserved (call er_kv_reserve)");
+    if (p->max_new_tokens <= 0) return fail(ER_ERR_INVALID, "max_new_tokens must be > 0");
+    if (p->mode != ER_GREEDY && p->mode != ER_SAMPLE) return fail(ER_ERR_INVALID, "bad mode");
+    if (p->grammar < 0 || p->grammar > 2) return fail(ER_ERR_INVALID, "bad grammar");
+    if (p->mode == ER_SAMPLE && p->top_k <= 0) return fail(ER_ERR_INVALID, "top_k must be > 0 in sample mode");
+    if (check_every < 0) return fail(ER_ERR_INVALID, "er_queue_begin: check_every %d", check_every);
+    ERCHK(er_finalize_weights(c));
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t st = pick(c, stream);
+    if (c->kv->plan.mfma) ERCHK(make_tiled_weights(c));
+    ERCHK(c->q_look.ensure((size_t)3 * B + 1));
+    if (c->q_pinned) { hipHostFree(c->q_pinned); c->q_pinned = nullptr; }
+    HIPCHK(hipHostMalloc((void**)&c->q_pinned, ((size_t)3 * B + 1) * sizeof(int), hipHostMallocDefault));
+    HIPCHK(hipStreamSynchronize(st));
+
+    DecodeParamsDev dp{};
+    dp.mode = p->mode; dp.top_k = p->top_k; dp.grammar = p->grammar; dp.max_new = p->max_new_tokens; dp.min_new = p->min_new_tokens;
+    dp.eos = c->cfg.eos_token_id; dp.pad = c->cfg.pad_token_id; dp.vocab = c->cfg.vocab_size;
+    dp.seed_lo = (unsigned int)(p->seed & 0xffffffffu); dp.seed_hi = (unsigned int)(p->seed >> 32);
+    HIPCHK(hipMemcpy(c->kv->d_params.p, &dp, sizeof(dp), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(queue_park_kernel, dim3((B + 63) / 64), dim3(64), 0, st, c->kv->st, c->kv->d_row_budget.p, 0, B);
+    HIPRET(hipGetLastError());
+    HIPCHK(hipMemsetAsync(c->kv->st.n_unfinished, 0, 2 * sizeof(int), st));                          // n_unfinished (unused here), error
+    HIPCHK(hipMemsetAsync(c->kv->ypre.p, 0, (size_t)B * c->cfg.hidden_dim * sizeof(float), st));   // a parked row's first forward reads its row
+    ERCHK(ensure_step_graph(c));
+    HIPCHK(hipStreamSynchronize(st));
+    c->have_hidden = false;
+    c->q.begin(B, Lcap, c->cfg.max_positions, p->max_new_tokens, check_every);
+    return ER_OK;
+}
+
+extern "C" int er_queue_admit(er_ctx* c, int row0, int n_rows, const float* embeds, int S, const uint32_t* stream_ids,
+                              const int32_t* max_new, void* stream) {
+    ERCHK(queue_open(c, "er_queue_admit"));
+    if (!embeds) return fail(ER_ERR_INVALID, "er_queue_admit: embeds is null");
+    const long long width = std::max({(long long)c->cfg.intermediate_dim, 3LL * c->cfg.hidden_dim, (long long)c->cfg.vocab_size});
+    const int rc = c->q.check_admit(row0, n_rows, S, max_new, width);
+    if (rc < 0) return fail(rc, "%s", c->q.why);
+    hipStream_t st = pick(c, stream);
+    std::vector<int> stage((size_t)2 * n_rows);
+    for (int i = 0; i < n_rows; ++i) {
+        stage[(size_t)i] = (int)(stream_ids ? stream_ids[i] : (uint32_t)(row0 + i));
+        stage[(size_t)n_rows + i] = c->q.budget_of(max_new, i);
+    }
+    ERCHK(c->q_stage.ensure(stage.size()));
+    HIPCHK(hipMemcpyAsync(c->q_stage.p, stage.data(), stage.size() * sizeof(int), hipMemcpyHostToDevice, st));
+    HIPCHK(hipEventRecord(c->ev0, st));
+    ERCHK(prefill_run(c, embeds, n_rows, S, st, row0, true));
+    hipLaunchKernelGGL(queue_admit_kernel, dim3((n_rows + 63) / 64), dim3(64), 0, st, c->kv->st, c->kv->d_row_stream.p,
+                       c->kv->d_row_budget.p, c->q_stage.p, row0, n_rows, S);
+    HIPRET(hipGetLastError());
+    HIPCHK(hipEventRecord(c->ev1, st));
+    HIPCHK(hipStreamSynchronize(st));         // `stage` and the caller's arrays are host memory
+    float ms = 0.f;
+    HIPCHK(hipEventElapsedTime(&ms, c->ev0, c->ev1));
+    c->q.stats.prefill_ms += ms;
+    c->q.admit(row0, n_rows, S, max_new);
+    return ER_OK;
+}
+
+extern "C" int er_queue_run(er_ctx* c, int32_t* done_rows, int32_t* n_done, void* stream) {
+    ERCHK(queue_open(c, "er_queue_run"));
+    if (!done_rows || !n_done) return fail(ER_ERR_INVALID, "er_queue_run: bad argument");
+    *n_done = c->q.list_done(done_rows);
+    if (*n_done > 0 || c->q.occupied() == 0) return ER_OK;
+    hipStream_t st = pick(c, stream);
+    const int B = c->q.slots, Lcap = c->kv->plan.Lcap;
+    HIPCHK(hipEventRecord(c->ev0, st));
+    while (*n_done == 0) {
+        const int burst = c->q.next_burst();
+        if (burst <= 0) return fail(ER_ERR_INVALID, "internal: er_queue_run has occupied rows but none is running");
+        for (int t = 0; t < burst; ++t) {
+            if (c->knobs.use_graph) HIPCHK(hipGraphLaunch(c->kv->step_exec, st));
+            else HIPRET(enqueue_step(c, st, c->kv->d_out_ids.p, Lcap));
+        }
+        c->q.advance(burst);
+        hipLaunchKernelGGL(queue_look_kernel, dim3((B + 63) / 64), dim3(64), 0, st, c->kv->st, B, c->q_look.p);
+        HIPRET(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(c->q_pinned, c->q_look.p, ((size_t)3 * B + 1) * sizeof(int), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        if (c->q_pinned[3 * B] != 0)
+            return fail(ER_ERR_INVALID, "er_queue_run: a row had no finite candidate score (non-finite logits); HF would raise in multinomial/argmax");
+        const int rc = c->q.collect(c->q_pinned, c->q_pinned + B, c->q_pinned + 2 * B, done_rows, n_done);
+        if (rc < 0) return fail(rc, "%s", c->q.why);
+    }
+    HIPCHK(hipEventRecord(c->ev1, st));
+    HIPCHK(hipStreamSynchronize(st));
+    float ms = 0.f;
+    HIPCHK(hipEventElapsedTime(&ms, c->ev0, c->ev1));
+    c->q.stats.decode_ms += ms;
+    return ER_OK;
+}
+
+extern "C" int er_queue_take(er_ctx* c, int row, int64_t* ids_out, int capacity, int32_t* n_tokens) {
+    ERCHK(queue_open(c, "er_queue_take"));
+    if (!ids_out || !n_tokens) return fail(ER_ERR_INVALID, "er_queue_take: bad argument");
+    const int rc = c->q.check_take(row, capacity);
+    if (rc < 0) return fail(rc, "%s", c->q.why);
+    const int n = c->q.rows[(size_t)row].n_tokens;
+    HIPCHK(hipMemcpy(ids_out, c->kv->d_out_ids.p + (size_t)row * c->kv->plan.Lcap, (size_t)n * sizeof(long long), hipMemcpyDeviceToHost));
+    hipLaunchKernelGGL(queue_park_kernel, dim3(1), dim3(64), 0, c->own_stream, c->kv->st, c->kv->d_row_budget.p, row, 1);
+    HIPRET(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(c->own_stream));
+    *n_tokens = n;
+    c->q.release(row);
+    return ER_OK;
+}
+
+extern "C" int er_queue_stats(er_ctx* c, er_queue_counters* out) {
+    if (!c || !out) return fail(ER_ERR_INVALID, "er_queue_stats: bad argument");
+    if (!c->q.active) return fail(ER_ERR_INVALID, "er_queue_stats: no queue is open");
+    *out = c->q.stats;
+    return ER_OK;
+}
+
+extern "C" int er_queue_end(er_ctx* c) {
+    ERCHK(queue_open(c, "er_queue_end"));
+    const int B = c->q.slots;
+    HIPCHK(hipDeviceSynchronize());
+    hipLaunchKernelGGL(fill_i32_kernel, dim3((B + 63) / 64), dim3(64), 0, c->own_stream, c->kv->d_row_budget.p, B, 0x7fffffff);
+    HIPRET(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(c->own_stream));
+    c->q.end();
+    c->have_hidden = false;
+    if (c->q_pinned) { hipHostFree(c->q_pinned); c->q_pinned = nullptr; }
+    return er_set_row_streams(c, nullptr, B);
 }
 
 extern "C" int er_last_decode_ms(er_ctx* c, float* ms) {

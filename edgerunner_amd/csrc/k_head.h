@@ -37,6 +37,8 @@ struct GenState {              // per-row arrays, all device
     const unsigned int* row_stream;   // per row: second Philox counter word of the sampler (null: the row index).  A caller that
                                // shards / batches independent jobs sets it to the GLOBAL job index, so a job's draws do not
                                // depend on which rows share its batch (er_set_row_streams)
+    const int* row_budget;     // per row: token budget of the job in that row (null: P.max_new for every row).  The queue mode
+                               // (er_queue_*) gives every job its own budget <= P.max_new and parks a free row with budget 0
 };
 
 // Philox4x32-10 (Salmon et al. 2011): counter-based, so a draw is a pure function of
@@ -97,7 +99,8 @@ __global__ __launch_bounds__(ER_WG) void sample_head_kernel(const float* logits,
     int* cand_i = reinterpret_cast<int*>(smem + 2 * V);   // [V] candidate ids (compacted)
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int t = st.ngen[b];
-    if (t >= P.max_new) return;                    // replay past the end: no-op
+    const int max_new = st.row_budget ? min(P.max_new, st.row_budget[b]) : P.max_new;
+    if (t >= max_new) return;                      // replay past the end (or a parked row of the queue mode): no-op
     const int last = st.tok[b];
     const bool running = st.unfinished[b] != 0;
     int counter = st.counter[b];

@@ -40,6 +40,64 @@ def score_row_groups(batch: int, seq_len: int, dims, max_rows: int = 1023) -> Li
     return [(b, min(b + per, batch)) for b in range(0, batch, per)]
 
 
+class _QueueJob:
+    """One job of ``LMM.generate_queue``: ``(conds, num_faces, resume_ids=None, stream=None, max_new_tokens=None)``."""
+
+    def __init__(self, index: int, spec, default_budget: int):
+        spec = tuple(spec)
+        if not 2 <= len(spec) <= 5:
+            raise ValueError(f"job {index}: (conds, num_faces[, resume_ids[, stream[, max_new_tokens]]]), got {len(spec)} fields")
+        conds, num_faces, resume, stream, budget = spec + (None,) * (5 - len(spec))
+        conds = torch.as_tensor(conds)
+        self.conds = conds[None] if conds.dim() == 2 else conds
+        if self.conds.dim() != 3 or self.conds.shape[0] != 1:
+            raise ValueError(f"job {index}: conds must be [N, C] or [1, N, C], got {tuple(conds.shape)}")
+        self.num_faces = int(num_faces)
+        self.resume = None if resume is None else torch.as_tensor(resume).to("cpu", torch.long).reshape(1, -1)
+        self.stream = index if stream is None else int(stream)
+        self.budget = int(default_budget if budget is None else budget)
+        if self.budget < 1:
+            raise ValueError(f"job {index}: max_new_tokens={self.budget}")
+
+
+class _QueueEngine:
+    """The engine ``edgerunner_amd.queue.QueueScheduler`` drives: admissions are prefills into cache rows of the native context."""
+
+    def __init__(self, lmm: "LMM", jobs: List[_QueueJob]):
+        self.lmm, self.jobs, self.dec = lmm, jobs, lmm.mesh_decoder
+        # exact mode: the jobs of one admit call that share a prefix length go through ONE forward pass (rows of a batched prefill
+        # give the ids of their single runs, as LMM.generate's batches do).  Fast mode: one row per pass - the fp16-weight Linears of
+        # the prefill pick their kernel by the row count of the pass, so only a one-row pass is bit-identical to the job run alone.
+        self.rows_per_pass = 1 if lmm.precision == "fp16" else 32
+
+    def embeds(self, job: _QueueJob) -> torch.Tensor:
+        """inputs_embeds [1, S, hidden] of the job, built exactly as LMM.generate_ids builds them for a batch of one."""
+        opt, dec = self.lmm.opt, self.dec
+        cond = self.lmm.encode_cond(job.conds, [job.num_faces])["cond_embeds"]
+        ids = torch.full((1, 1), opt.bos_token_id, dtype=torch.long)
+        if job.resume is not None:
+            ids = torch.cat((ids, job.resume), dim=1)
+        tok = dec.model.embd(ids)
+        return torch.cat((cond, tok), dim=1) if cond is not None else tok
+
+    def admit(self, slot0: int, job_ids) -> None:
+        embeds = [self.embeds(self.jobs[j]) for j in job_ids]
+        i = 0
+        while i < len(job_ids):
+            k = i + 1
+            while k < len(job_ids) and k - i < self.rows_per_pass and embeds[k].shape[1] == embeds[i].shape[1]:
+                k += 1
+            part = [self.jobs[j] for j in job_ids[i:k]]
+            self.dec.queue_admit(slot0 + i, torch.cat(embeds[i:k], dim=0), [p.stream for p in part], [p.budget for p in part])
+            i = k
+
+    def run(self):
+        return self.dec.queue_run()
+
+    def take(self, slot: int):
+        return self.dec.queue_take(slot, max(j.budget for j in self.jobs))
+
+
 class _Embd:
     """``mesh_decoder.model.embd`` lookalike (core/models.py:228)."""
 
@@ -294,6 +352,54 @@ class LMM:
             kwargs["do_sample"] = True
             kwargs["top_k"] = 10
         return self.mesh_decoder.generate(**kwargs)
+
+    @torch.no_grad()
+    def generate_queue(self, jobs, slots: int, tokenizer=None, max_new_tokens=None, min_new_tokens: int = 0,
+                       seed: Optional[int] = None, clean=True, check_every: int = 0):
+        """Serves independent jobs from ``slots`` cache rows (continuous batching, ``er_queue_*``) -> ``(meshes, all_tokens)`` in job
+        order, as ``generate`` returns them for one job each.  A job is ``(conds [N,3] or [1,N,3], num_faces, resume_ids=None,
+        stream=None, max_new_tokens=None)``; clouds of different sizes, different face counts and resume lengths may be mixed.  A job
+        leaves its slot when it emits EOS or reaches its budget and the next waiting job is prefilled into that slot, so - unlike a
+        ``generate`` batch - no row rides on after its end.  ``all_tokens[j]`` has the job's own length (no PAD) with the resume
+        prefix echoed; ``stream`` (default: the job's index) is the Philox stream of sample mode.  A job's ids are those of
+        ``generate`` on that job alone (fp32; fp16: within one kernel class, slots <= 4 or slots > 4).  Afterwards
+        ``last_queue_stats`` holds the ``er_queue_stats`` counters and ``last_queue_slots[j]`` the slot job j ran in."""
+        from .meto import Engine, save_mesh
+        from .queue import QueueScheduler
+        opt = self.opt
+        budget = opt.max_seq_length if max_new_tokens is None else int(max_new_tokens)
+        jobs = [_QueueJob(j, spec, budget) for j, spec in enumerate(jobs)]
+        self.last_queue_stats, self.last_queue_slots = {}, []
+        if not jobs:
+            return [], []
+        fn = BuiltinGrammar(select_grammar(opt, tokenizer is not None), self.vocab_size, opt.eos_token_id)
+        if fn.er_grammar == native.ER_GRAMMAR_NONE:
+            print("[WARN] prefix_allowed_tokens_fn is not defined for meto backend:", opt.meto_backend)
+        do_sample = opt.generate_mode == "sample"
+        if seed is None:      # as NativeShapeOPT._decode_device: the Philox key comes from torch's global CPU generator
+            seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if do_sample else 0
+        dec = self.mesh_decoder
+        prefix = lambda j: opt.num_cond_tokens + 1 + (0 if j.resume is None else j.resume.shape[1])
+        l_cap = max(prefix(j) + j.budget + 1 for j in jobs)
+        dec.queue_begin(int(slots), l_cap, max(j.budget for j in jobs), min_new_tokens, do_sample, 10, fn.er_grammar, seed, check_every)
+        try:
+            sched = QueueScheduler(int(slots))
+            ids = sched.serve(_QueueEngine(self, jobs), len(jobs))
+            self.last_queue_stats = dec.queue_stats()
+            self.last_queue_slots = list(sched.slot_of)
+        finally:
+            dec.queue_end()
+        meshes: List[Optional[object]] = []
+        all_tokens: List[np.ndarray] = []
+        for job, tokens in zip(jobs, ids):
+            if job.resume is not None:
+                tokens = np.concatenate((job.resume[0].numpy(), tokens), axis=0)
+            if tokenizer is None or isinstance(tokenizer, Engine):
+                meshes.append(save_mesh(tokens, opt, tokenizer=tokenizer, clean=clean))
+            else:
+                meshes.append(None)
+            all_tokens.append(tokens)
+        return meshes, all_tokens
 
     @torch.no_grad()
     def generate(self, conds, num_faces=1000, resume_ids=None, tokenizer=None, max_new_tokens=None, clean=True,

@@ -35,6 +35,7 @@ EXPORTS = [
     "er_set_row_streams", "er_plan_decode", "er_ctx_plan", "er_plan_gemm_tile", "er_kernel_kind_name", "er_profile_decode_kernels", "er_profile_decode_kernels_at", "er_last_decode_ms",
     "er_k_gemv", "er_k_attn_decode", "er_k_attn_outproj3", "er_k_gemm", "er_k_gemm_f16", "er_k_gemm_hh", "er_k_gemm_hh_qkv", "er_k_gemm_hh_geglu", "er_k_gemm_f16s", "er_k_flash_attn_f16", "er_k_flash_attn_hh", "er_k_flash_attn_f32", "er_k_flash_attn_f16s", "er_k_layernorm", "er_k_softmax", "er_k_score_rows", "er_k_fps", "er_k_sample_head",
     "er_k_nn_dist2", "er_k_surface_sample", "er_k_fidelity_metrics",
+    "er_queue_begin", "er_queue_admit", "er_queue_run", "er_queue_take", "er_queue_stats", "er_queue_end",
 ]
 
 
@@ -62,6 +63,11 @@ class ErDitConfig(C.Structure):
 class ErDecodeParams(C.Structure):
     _fields_ = [("mode", C.c_int32), ("top_k", C.c_int32), ("grammar", C.c_int32),
                 ("max_new_tokens", C.c_int32), ("min_new_tokens", C.c_int32), ("seed", C.c_uint64)]
+
+
+class ErQueueCounters(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ("steps", "admissions", "occupied_row_steps", "wait_row_steps", "parked_row_steps")] + \
+               [("prefill_ms", C.c_float), ("decode_ms", C.c_float)]
 
 
 class NativeError(RuntimeError):
@@ -130,6 +136,12 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.er_ctx_plan.argtypes = [vp, C.POINTER(ErDecodePlan)]
     lib.er_set_row_streams.argtypes = [vp, C.POINTER(C.c_uint32), ci]
     lib.er_plan_gemm_tile.argtypes = [ci, ci, ci]
+    lib.er_queue_begin.argtypes = [vp, C.POINTER(ErDecodeParams), ci, vp]
+    lib.er_queue_admit.argtypes = [vp, ci, ci, vp, ci, C.POINTER(C.c_uint32), C.POINTER(C.c_int32), vp]
+    lib.er_queue_run.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), vp]
+    lib.er_queue_take.argtypes = [vp, ci, C.POINTER(C.c_int64), ci, C.POINTER(C.c_int32)]
+    lib.er_queue_stats.argtypes = [vp, C.POINTER(ErQueueCounters)]
+    lib.er_queue_end.argtypes = [vp]
     lib.er_k_gemv.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, cf, vp]
     lib.er_k_attn_decode.argtypes = [vp, vp, vp, C.POINTER(C.c_int32), vp, ci, ci, ci, ci, ci, ci, ci, vp]
     lib.er_k_attn_outproj3.argtypes = [vp, vp, vp, ci, vp, vp, vp, vp, ci, ci, ci, vp]

@@ -330,6 +330,57 @@ class NativeShapeOPT:
             self.feed(nxt)
         return ids.to(self.device)
 
+    # -- queue mode (continuous batching): thin bindings of er_queue_* -------------------------
+    def queue_begin(self, slots: int, l_cap: int, max_new_tokens: int, min_new_tokens: int = 0, do_sample: bool = False,
+                    top_k: int = 10, grammar: int = native.ER_GRAMMAR_NONE, seed: int = 0, check_every: int = 0):
+        """Reserves ``slots`` cache rows of ``l_cap`` positions and opens the queue on them (every row parked)."""
+        if self._reserved[0] != slots or self._reserved[1] < l_cap:
+            self.reserve(slots, l_cap)
+        p = native.ErDecodeParams(mode=native.ER_SAMPLE if do_sample else native.ER_GREEDY, top_k=int(top_k), grammar=int(grammar),
+                                  max_new_tokens=int(max_new_tokens), min_new_tokens=int(min_new_tokens),
+                                  seed=int(seed) & 0xFFFFFFFFFFFFFFFF)
+        with self._enter():
+            native.check(self.lib.er_queue_begin(self._ctx, C.byref(p), int(check_every), self._sp()), "er_queue_begin")
+        self._exit()
+
+    def queue_admit(self, row0: int, inputs_embeds: torch.Tensor, stream_ids=None, budgets=None):
+        """Prefills rows [row0, row0 + n) from ``inputs_embeds`` [n, S, hidden] in one forward pass and starts their jobs."""
+        x = inputs_embeds.to(self.device, torch.float32).contiguous()
+        n, S, _ = x.shape
+        ids = None if stream_ids is None else (C.c_uint32 * n)(*[int(v) & 0xFFFFFFFF for v in stream_ids])
+        bud = None if budgets is None else native.i32_array(budgets)
+        if (ids is not None and len(stream_ids) != n) or (bud is not None and len(budgets) != n):
+            raise ValueError(f"queue_admit: {n} rows need {n} stream ids / budgets")
+        with self._enter():
+            native.check(self.lib.er_queue_admit(self._ctx, int(row0), n, native.ptr(x), S, ids, bud, self._sp()), "er_queue_admit")
+        self._exit()
+
+    def queue_run(self):
+        """Replays the step until a job is done: the rows of all done jobs ([] when no row is occupied)."""
+        rows = (C.c_int32 * max(1, self._reserved[0]))()
+        n = C.c_int32(0)
+        with self._enter():
+            native.check(self.lib.er_queue_run(self._ctx, rows, C.byref(n), self._sp()), "er_queue_run")
+        self._exit()
+        return [int(rows[i]) for i in range(n.value)]
+
+    def queue_take(self, row: int, capacity: int):
+        """The finished job's ids (int64 numpy array of its own length, no PAD); the row is free afterwards."""
+        import numpy as np
+        buf = np.empty((max(1, int(capacity)),), dtype=np.int64)
+        n = C.c_int32(0)
+        native.check(self.lib.er_queue_take(self._ctx, int(row), buf.ctypes.data_as(C.POINTER(C.c_int64)), int(capacity), C.byref(n)),
+                     "er_queue_take")
+        return buf[: n.value].copy()
+
+    def queue_stats(self) -> Dict[str, float]:
+        s = native.ErQueueCounters()
+        native.check(self.lib.er_queue_stats(self._ctx, C.byref(s)), "er_queue_stats")
+        return {n: (float if n.endswith("_ms") else int)(getattr(s, n)) for n, _ in native.ErQueueCounters._fields_}
+
+    def queue_end(self):
+        native.check(self.lib.er_queue_end(self._ctx), "er_queue_end")
+
     def plan(self):
         """Kernel selection of THIS context for its reserved cache (``er_ctx_plan``): dict of the ``er_decode_plan`` fields."""
         p = native.ErDecodePlan()

@@ -175,6 +175,47 @@ int er_decode(er_ctx* ctx, const er_decode_params* p, int64_t* out_ids_dev,
  * same property for its serial loop). */
 int er_set_row_streams(er_ctx* ctx, const uint32_t* ids_host, int n);
 
+/* ---- queue mode (continuous batching): a list of independent jobs served from the fixed rows ("slots") of one reserved cache.
+ * er_decode runs a batch until its LONGEST row ends; here a row is handed back as soon as its job emits EOS or spends its token
+ * budget, and the next job is prefilled into that row while the other rows keep their state.  Between two steps a row's whole state
+ * is its slice of the KV cache, its row of the last hidden state and its entries of the generation state, so a refill touches
+ * nothing else and the captured step is replayed unchanged.  A free ("parked") row still rides through the step (the grid is
+ * fixed): it has budget 0, so the sampling head leaves it alone, and sits at position 0, so its attention reads one key.
+ * Contract: a job's tokens are those of the same job run alone through er_prefill + er_decode with the same er_decode_params
+ * (max_new_tokens = its budget) and, in sample mode, the same stream id - whatever row it landed in and whatever shares the batch
+ * (exact mode: for every slot count; fast mode: within one kernel class, slots <= 4 or slots > 4).
+ * Call order: er_kv_reserve(slots, l_cap); er_queue_begin; { er_queue_admit ...; er_queue_run; er_queue_take ... }; er_queue_end.
+ * All calls block until their device work is complete.  While a queue is open er_prefill / er_score / er_decode / er_feed fail. */
+typedef struct {
+    int64_t steps;               /* step replays so far                                                    */
+    int64_t admissions;          /* rows admitted                                                          */
+    int64_t occupied_row_steps;  /* sum over steps of the rows that held a job (running or waiting)        */
+    int64_t wait_row_steps;      /* steps finished jobs spent in their row before er_queue_run listed them */
+    int64_t parked_row_steps;    /* sum over steps of the free rows                                        */
+    float prefill_ms, decode_ms; /* HIP events around the admissions' forward passes / the replay bursts   */
+} er_queue_counters;
+/* Opens the queue on the reserved cache: stores *p (max_new_tokens = the largest budget a job may have, the rest as for er_decode)
+ * and parks every row.  check_every = steps between two host looks at the rows (0: the 32 of er_decode). */
+int er_queue_begin(er_ctx* ctx, const er_decode_params* p, int check_every, void* stream);
+/* Prefills n_rows free rows [row0, row0 + n_rows) from embeds_dev float[n_rows, S, hidden] in ONE forward pass and starts their
+ * jobs: K/V into positions [0, S) of those rows' cache slices, the last position's state, the generation state at position S, the
+ * Philox stream ids (stream_ids_host[n_rows]; NULL: the row index) and the budgets (max_new_host[n_rows]; NULL: p->max_new_tokens).
+ * No other row is written.  ER_ERR_INVALID: a row is occupied / outside the slots, a budget outside [1, p->max_new_tokens];
+ * ER_ERR_CAPACITY: S + budget + 1 exceeds the reserved cache or the position table. */
+int er_queue_admit(er_ctx* ctx, int row0, int n_rows, const float* embeds_dev, int S, const uint32_t* stream_ids_host,
+                   const int32_t* max_new_host, void* stream);
+/* Replays the step until at least one occupied row is done (EOS emitted or budget spent) and lists every done row in
+ * done_rows_host[<= slots].  The host looks every check_every steps, and earlier when a row is about to spend its budget, so a done
+ * job waits fewer than check_every steps.  Returns at once with the rows that are already done, or with *n_done = 0 when no row is
+ * occupied.  Fails (ER_ERR_INVALID) when a row had no finite candidate score, as er_decode does. */
+int er_queue_run(er_ctx* ctx, int32_t* done_rows_host, int32_t* n_done, void* stream);
+/* The ids of the finished job in `row`: ids_out_host[0, *n_tokens), *n_tokens = index of EOS + 1, or the budget; no PAD.  Parks the row. */
+int er_queue_take(er_ctx* ctx, int row, int64_t* ids_out_host, int capacity, int32_t* n_tokens);
+int er_queue_stats(er_ctx* ctx, er_queue_counters* out);
+/* Closes the queue (jobs still in their rows are dropped) and leaves the context as a fresh er_kv_reserve does: row streams are the
+ * identity again, every row's budget is er_decode's max_new_tokens, er_prefill is required before er_decode. */
+int er_queue_end(er_ctx* ctx);
+
 /* ---- mesh tokenizer (host code, no device work): the reference's pybind11 module meto (meto/src/bindings.cpp,
  * meto.Engine(discrete_bins, verbose, backend), meto/meto/__init__.py:21-54) for the backends Options.meto_backend
  * admits (core/options.py:26). */

@@ -23,6 +23,11 @@ Reproducibility: in sample mode job j (its index in the reference's loop order) 
 the projections of calls with more than 4 rows run on the matrix cores and round differently from the 1..4-row kernels
 (both within 1e-5 of the fp16-storage model), so a near-tie can still resolve differently when the grouping changes;
 EDGERUNNER_PRECISION=fp32 with ER_INFER_BATCH <= 4 (or any fixed grouping) is bit-reproducible.
+
+ER_INFER_QUEUE=1 serves the rank's jobs through ``LMM.generate_queue`` instead: one set of min(ER_INFER_BATCH, jobs) cache rows for
+all face counts, a job leaves its row when it emits EOS and the next job is prefilled into that row, so no row rides on to the end
+of the longest job of its call.  Same output files and ``tokens_all.npz``; the log line of a job carries its own token count and
+the row it ran in.  Without the variable nothing changes.
 """
 from __future__ import annotations
 
@@ -142,7 +147,38 @@ def main(argv=None):
             meshio.save_points_obj(f"{opt.workspace}/{name}_pc.obj", clouds[path])
     rows_max = max_rows_per_call(opt, model, opt.test_max_seq_length, device)
     local_streams = {}
-    for num_faces, chunk in D.group_jobs(jobs, mine, lambda p: clouds[p].shape[0], rows_max):
+
+    def save_job(j, mesh, tokens, note):
+        path, i, num_faces = jobs[j]
+        name = os.path.splitext(os.path.basename(path))[0]
+        toks = trim_tokens(tokens)
+        filename = f"{name}_{i}" + (f"_{num_faces}f" if opt.use_num_face_cond else "")
+        np.save(f"{opt.workspace}/{filename}_tokens.npy", toks)
+        if mesh is not None:
+            mesh.export(f"{opt.workspace}/{filename}.ply")               # reference infer.py:120
+        local_streams[j] = toks
+        print(f"[INFO] Processing {path} --> {filename}.ply, {len(toks)} tokens, {note}")
+
+    if os.environ.get("ER_INFER_QUEUE") == "1" and mine:
+        # queue mode: all of the rank's jobs, whatever their face counts, share one set of cache rows; a job leaves its row at its
+        # own EOS and the next job takes the row (LMM.generate_queue).  Stream id = global job index, as in the batched path.
+        slots = min(rows_max, len(mine))
+        specs = [(torch.from_numpy(clouds[jobs[j][0]]).float(), jobs[j][2], None, j) for j in mine]
+        t0 = time.time()
+        meshes, tokens = model.generate_queue(specs, slots, tokenizer=tokenizer, max_new_tokens=opt.test_max_seq_length,
+                                              clean=True, seed=opt.seed)
+        torch.cuda.synchronize()
+        dt = time.time() - t0
+        st = model.last_queue_stats
+        for r, j in enumerate(mine):
+            save_job(j, meshes[r], tokens[r], f"{len(tokens[r])} generated, slot {model.last_queue_slots[r]} of {slots}")
+        print(f"[INFO] queue: {len(mine)} jobs on {slots} slots in {dt:.4f}s, {st['steps']} steps, {st['occupied_row_steps']} occupied / "
+              f"{st['wait_row_steps']} waiting / {st['parked_row_steps']} parked row-steps, prefill {st['prefill_ms']:.1f} ms, "
+              f"decode {st['decode_ms']:.1f} ms")
+        mine_groups = []
+    else:
+        mine_groups = D.group_jobs(jobs, mine, lambda p: clouds[p].shape[0], rows_max)
+    for num_faces, chunk in mine_groups:
         cond = torch.from_numpy(np.stack([clouds[jobs[j][0]] for j in chunk])).float().to(device)
         t0 = time.time()
         # sample mode: job j draws from the Philox stream (opt.seed, step, j) whatever rows share its call
@@ -151,16 +187,7 @@ def main(argv=None):
         torch.cuda.synchronize()
         dt = time.time() - t0
         for r, j in enumerate(chunk):
-            path, i, _ = jobs[j]
-            name = os.path.splitext(os.path.basename(path))[0]
-            toks = trim_tokens(tokens[r])
-            filename = f"{name}_{i}" + (f"_{num_faces}f" if opt.use_num_face_cond else "")
-            np.save(f"{opt.workspace}/{filename}_tokens.npy", toks)
-            if meshes[r] is not None:
-                meshes[r].export(f"{opt.workspace}/{filename}.ply")               # reference infer.py:120
-            local_streams[j] = toks
-            print(f"[INFO] Processing {path} --> {filename}.ply, {len(toks)} tokens, time = {dt:.4f}s "
-                  f"({len(chunk)} jobs in this call)")
+            save_job(j, meshes[r], tokens[r], f"time = {dt:.4f}s ({len(chunk)} jobs in this call)")
     # the one exchange of the sharded path: RCCL all-gather of the token streams (ids - 3, >= -3, so shift to >= 0)
     gathered = D.gather_token_streams([local_streams[j] + 3 for j in mine], len(jobs), device=device)
     if rank == 0:
