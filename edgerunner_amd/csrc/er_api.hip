@@ -1771,6 +1771,238 @@ extern "C" int er_k_attn_decode(const float* q, const void* k, const void* v, co
     return ER_OK;
 }
 
+extern "C" int er_k_attn_stream_xt(const float* q, const void* k, const void* v, const int32_t* len_host, float* out, void* out_xt, int B,
+                                   int heads, int l_cap, int kv_half, void* stream) {
+    constexpr int D = 96;
+    if (!q || !k || !v || !len_host || !out || B < 1 || heads < 1 || l_cap < 1) return fail(ER_ERR_INVALID, "er_k_attn_stream_xt: bad argument");
+    for (int b = 0; b < B; ++b)
+        if (len_host[b] < 1 || len_host[b] > l_cap) return fail(ER_ERR_CAPACITY, "er_k_attn_stream_xt: len[%d] = %d / l_cap %d", b, len_host[b], l_cap);
+    hipStream_t st = (hipStream_t)stream;
+    DevBuf<int> len_dev;
+    ERCHK(len_dev.ensure(B));
+    HIPCHK(hipMemcpy(len_dev.p, len_host, B * sizeof(int), hipMemcpyHostToDevice));
+    AttnDecArgs a{};
+    a.q = q; a.kcache = k; a.vcache = v; a.len_dev = len_dev.p; a.out = out; a.out_xt = out_xt;      // as attn_args: xt_att when out_proj reads the tiled image
+    a.H = heads; a.l_cap = l_cap; a.hidden = heads * D; a.kv_bstride = (long long)heads * l_cap * D; a.sqrt_d = sqrtf((float)D);
+    hipError_t e = launch_attn_stream_d<D>(a, kv_half != 0, B, st);      // launch_kind_t case 1, stream_attn
+    hipError_t e2 = hipStreamSynchronize(st);
+    HIPRET(e);
+    HIPRET(e2);
+    return ER_OK;
+}
+
+// ---- er_k_gemv_form: one decode projection in one of the forms launch_kind_t launches it in.  Every launch below names the `case` of
+// launch_kind_t it mirrors and uses that case's launcher and template arguments; what the step never launches is refused by
+// gemv_form_check before anything is allocated or launched.
+enum { GF_QKV = 0, GF_OUTPROJ = 3, GF_FC1 = 4, GF_FC2 = 5, GF_HEAD = 6, GF_PREP = 100 };     // launch_kind_t's kinds; GF_PREP: the prologue launch alone
+
+static int gemv_form_check(const er_k_gemv_form_args& f, int* proj_out) {
+    const int B = f.batch, n = f.n, k = f.k, pro = f.prologue, epi = f.epilogue, form = f.form;
+    const bool half = f.w_half != 0;
+    if (B < 1 || B > ER_MAX_BATCH || n < 1) return fail(ER_ERR_INVALID, "er_k_gemv_form: batch %d, n %d", B, n);
+    if (k != 1536 && k != 6144) return fail(ER_ERR_UNSUPPORTED, "er_k_gemv_form: k must be 1536 or 6144");
+    int proj;
+    if (form == ER_FORM_PREP) {
+        proj = GF_PREP;
+        if (k != 1536 || pro == ER_PRO_NONE) return fail(ER_ERR_UNSUPPORTED, "er_k_gemv_form: the prologue launch is built for k=1536 and LN / EMBED");
+        if (!f.xnorm_out) return fail(ER_ERR_INVALID, "er_k_gemv_form: ER_FORM_PREP needs xnorm_out");
+    } else {
+        if (!f.w) return fail(ER_ERR_INVALID, "er_k_gemv_form: null weights");
+        if (epi == ER_EPI_QKV && k == 1536 && pro != ER_PRO_NONE) proj = GF_QKV;
+        else if (epi == ER_EPI_RELU && k == 1536 && (pro == ER_PRO_LN || pro == ER_PRO_LN_SK)) proj = GF_FC1;
+        else if (epi == ER_EPI_RESID && pro == ER_PRO_NONE) proj = k == 1536 ? GF_OUTPROJ : GF_FC2;
+        else if (epi == ER_EPI_STORE && k == 1536 && pro == ER_PRO_LN) proj = GF_HEAD;
+        else return fail(ER_ERR_UNSUPPORTED, "er_k_gemv_form: no decode projection has k=%d, prologue %d, epilogue %d", k, pro, epi);
+    }
+    // operands of the prologue and the epilogue
+    if (pro == ER_PRO_NONE && !f.x) return fail(ER_ERR_INVALID, "er_k_gemv_form: null x");
+    if (pro == ER_PRO_LN && (!f.x || !f.ln_w || !f.ln_b)) return fail(ER_ERR_INVALID, "er_k_gemv_form: PRO_LN needs x, ln_w, ln_b");
+    if (pro == ER_PRO_EMBED && (!f.embd || !f.posemb || !f.tok || !f.pos)) return fail(ER_ERR_INVALID, "er_k_gemv_form: PRO_EMBED needs embd, posemb, tok, pos");
+    if (pro == ER_PRO_LN_SK) {
+        if (!f.sk_part || !f.sk_bias || !f.sk_resid || !f.ln_w || !f.ln_b) return fail(ER_ERR_INVALID, "er_k_gemv_form: PRO_LN_SK needs sk_part, sk_bias, sk_resid, ln_w, ln_b");
+        // only the tiled fast-mode path defers a finish: fc2's 16 partials to the next qkv (case 0), out_proj's 4 to fc1 (case 4)
+        if (!half || form == ER_FORM_ROW || form == ER_FORM_ROWS8) return fail(ER_ERR_UNSUPPORTED, "er_k_gemv_form: a deferred finish is read by the fast-mode batched prologue only");
+        const int want = proj == GF_QKV ? SK_SLICES_FC2 : proj == GF_FC1 ? SK_SLICES_OUTPROJ : f.sk_slices;
+        if ((f.sk_slices != SK_SLICES_OUTPROJ && f.sk_slices != SK_SLICES_FC2) || f.sk_slices != want)
+            return fail(ER_ERR_UNSUPPORTED, "er_k_gemv_form: sk_slices %d (qkv reads 16, fc1 reads 4)", f.sk_slices);
+    }
+    if (proj == GF_QKV) {
+        if (!f.q_out || !f.kcache || !f.vcache || !f.pos) return fail(ER_ERR_INVALID, "er_k_gemv_form: EPI_QKV needs q_out, kcache, vcache, pos");
+        if (f.heads < 1 || f.head_dim < 1 || f.l_cap < 1 || f.heads * f.head_dim != k || n != 3 * k)
+            return fail(ER_ERR_INVALID, "er_k_gemv_form: EPI_QKV needs heads * head_dim == k and n == 3 k");
+    } else if (proj != GF_PREP) {
+        if (!f.y && !(form == ER_FORM_MFMA_XT && proj == GF_FC1) && form != ER_FORM_NARROW_DEFER) return fail(ER_ERR_INVALID, "er_k_gemv_form: null y");
+        if (epi == ER_EPI_RESID && !f.resid && form != ER_FORM_NARROW_DEFER) return fail(ER_ERR_INVALID, "er_k_gemv_form: EPI_RESID needs resid");
+    }
+    if (f.prep_xt_out && !(half && pro != ER_PRO_NONE && (form == ER_FORM_MFMA_XT || form == ER_FORM_PREP)))
+        return fail(ER_ERR_UNSUPPORTED, "er_k_gemv_form: prep_xt_out is written in front of the tiled fp16 forms only");
+    // the form
+    const bool batched_form = form != ER_FORM_ROW && form != ER_FORM_ROWS8;
+    if (batched_form && B <= 4) return fail(ER_ERR_UNSUPPORTED, "er_k_gemv_form: the batched forms run at batch > 4");
+    switch (form) {
+        case ER_FORM_ROW: {
+            if (B > 4) return fail(ER_ERR_UNSUPPORTED, "er_k_gemv_form: the row kernel runs at batch <= 4");
+            bool ok = false;
+            if (proj == GF_QKV) ok = (f.nw == 4 && f.rw == 1) || (f.nw == 6 && f.rw == 1) || (f.nw == 9 && f.rw == 2);      // read_knobs: ER_NW_QKV
+            if (proj == GF_FC1) ok = (f.nw == 4 || f.nw == 12) && f.rw == 2;                                                // ER_NW_FC1
+            if (proj == GF_OUTPROJ) ok = f.nw == 3 && f.rw == 1;
+            if (proj == GF_FC2) ok = f.nw == 4 && (f.rw == 2 || (half && B == 1 && (f.rw == 4 || f.rw == 6)));              // ER_RW_FC2
+            if (proj == GF_HEAD) ok = f.nw == 4 && f.rw == 1;
+            if (!ok) return fail(ER_ERR_UNSUPPORTED, "er_k_gemv_form: no row kernel of %d waves x %d rows for this projection, batch %d", f.nw, f.rw, B);
+            break;
+        }
+        case ER_FORM_ROWS8:
+            if (proj != GF_OUTPROJ || B < 5 || B > 8) return fail(ER_ERR_UNSUPPORTED, "er_k_gemv_form: rows8 is out_proj at batch 5..8");
+            break;
+        case ER_FORM_VALU:
+            break;
+        case ER_FORM_MFMA:
+            if (proj == GF_HEAD) return fail(ER_ERR_UNSUPPORTED, "er_k_gemv_form: the lm_head stays on the VALU kernel");
+            break;
+        case ER_FORM_MFMA_XT:
+            if (!half || (proj != GF_QKV && proj != GF_FC1)) return fail(ER_ERR_UNSUPPORTED, "er_k_gemv_form: wide tiled form: fp16 qkv and fc1");
+            if (proj == GF_FC1 && (!f.xt_out || n % 4)) return fail(ER_ERR_INVALID, "er_k_gemv_form: the tiled fc1 writes xt_out (n a multiple of 4)");
+            break;
+        case ER_FORM_NARROW:
+            if (!half || proj != GF_FC2) return fail(ER_ERR_UNSUPPORTED, "er_k_gemv_form: narrow + finish kernel: fp16 fc2 (the last layer's)");
+            break;
+        case ER_FORM_NARROW_DEFER:
+            if (!half || (proj != GF_OUTPROJ && proj != GF_FC2)) return fail(ER_ERR_UNSUPPORTED, "er_k_gemv_form: narrow deferred: fp16 out_proj and fc2");
+            if (!f.part_out) return fail(ER_ERR_INVALID, "er_k_gemv_form: ER_FORM_NARROW_DEFER needs part_out");
+            break;
+        case ER_FORM_PREP:
+            break;
+        default:
+            return fail(ER_ERR_INVALID, "er_k_gemv_form: form %d", form);
+    }
+    *proj_out = proj;
+    return ER_OK;
+}
+
+template <typename WT>
+static int gemv_form_t(const er_k_gemv_form_args& f, int proj, hipStream_t st) {
+    constexpr bool HALF = sizeof(WT) == 2;
+    const int B = f.batch, n = f.n, k = f.k, form = f.form;
+    GemvArgs a{};
+    a.W = f.w; a.bias = f.bias; a.N = n; a.xin = f.x; a.ln_w = f.ln_w; a.ln_b = f.ln_b; a.eps = f.eps; a.hout = f.xnorm_out;
+    a.embd = f.embd; a.posemb = f.posemb; a.tok = f.tok; a.pos = f.pos;
+    a.out = f.y; a.resid = f.resid; a.q = f.q_out; a.kcache = f.kcache; a.vcache = f.vcache; a.kv_half = f.kv_half ? 1 : 0;
+    a.hidden = proj == GF_QKV ? f.heads * f.head_dim : 1536; a.head_dim = f.head_dim; a.l_cap = f.l_cap;
+    a.kv_bstride = (long long)f.heads * f.l_cap * f.head_dim;
+    hipError_t e = hipErrorInvalidValue;
+    if (form == ER_FORM_ROW) {
+        switch (proj) {
+            case GF_QKV:        // case 0, B <= 4
+                e = f.prologue == ER_PRO_EMBED ? gemv_nw<WT, PRO_EMBED, EPI_QKV>(f.nw, a, B, k, st) : gemv_nw<WT, PRO_LN, EPI_QKV>(f.nw, a, B, k, st);
+                break;
+            case GF_OUTPROJ: e = gemv_groups<WT, 1, 1, PRO_NONE, EPI_RESID, 3>(a, B, k, st); break;      // case 3
+            case GF_FC1: e = gemv_nw<WT, PRO_LN, EPI_RELU>(f.nw, a, B, k, st); break;                     // case 4
+            case GF_FC2:        // case 5
+                if constexpr (HALF) {
+                    if (f.rw == 6) { e = launch_gemv<WT, 4, 1, 6, PRO_NONE, EPI_RESID>(a, st); break; }
+                    if (f.rw == 4) { e = launch_gemv<WT, 4, 1, 4, PRO_NONE, EPI_RESID>(a, st); break; }
+                }
+                e = gemv_groups<WT, 4, 2, PRO_NONE, EPI_RESID>(a, B, k, st);
+                break;
+            case GF_HEAD: e = gemv_groups<WT, 1, 1, PRO_LN, EPI_STORE>(a, B, k, st); break;               // case 6
+        }
+        hipError_t e2 = hipStreamSynchronize(st);
+        HIPRET(e);
+        HIPRET(e2);
+        return ER_OK;
+    }
+    if (form == ER_FORM_ROWS8) {    // case 3, outproj_rows8
+        e = gemv_outproj_rows8<WT>(a, B, st);
+        hipError_t e2 = hipStreamSynchronize(st);
+        HIPRET(e);
+        HIPRET(e2);
+        return ER_OK;
+    }
+    // ---- the batched forms: temporaries first, then the prologue launch, the tiled weight copy and the projection
+    const bool tiled_in = form == ER_FORM_MFMA_XT || form == ER_FORM_NARROW || form == ER_FORM_NARROW_DEFER;
+    const bool mfma = form == ER_FORM_MFMA || tiled_in;
+    const size_t groups = (size_t)(B + NBM - 1) / NBM;
+    const int slices = tiled_in && form != ER_FORM_MFMA_XT ? k / (4 * GM_KW) : k / (GM_WAVES * GM_KW);
+    DevBuf<float> tmp, part;
+    DevBuf<char> wt, img;
+    if (f.prologue != ER_PRO_NONE && !f.xnorm_out) ERCHK(tmp.ensure((size_t)B * k));
+    if (mfma) {
+        ERCHK(wt.ensure(tiled_weight_bytes<WT>(n, k)));
+        if (form != ER_FORM_NARROW_DEFER) ERCHK(part.ensure((size_t)slices * NBM * n));
+    }
+    void* image = f.prep_xt_out;
+    if (form == ER_FORM_MFMA_XT && !image) {      // er_kv_reserve: one zeroed image of k * 128 bytes per group of 32 rows
+        ERCHK(img.ensure(groups * (size_t)k * 128));
+        HIPCHK(hipMemsetAsync(img.p, 0, groups * (size_t)k * 128, st));
+        image = img.p;
+    }
+    e = hipSuccess;
+    if (f.prologue != ER_PRO_NONE) {      // cases 0, 4, 6: prep_rows in front of the projection
+        if (tmp.p) a.hout = tmp.p;
+        if constexpr (HALF) {
+            a.xt_out = image;
+            if (f.prologue == ER_PRO_LN_SK) { a.sk_part = f.sk_part; a.sk_bias = f.sk_bias; a.sk_resid = f.sk_resid; a.sk_batch = B; a.sk_slices = f.sk_slices; }
+        }
+        e = f.prologue == ER_PRO_EMBED ? prep_rows<PRO_EMBED>(a, B, st) : prep_rows<PRO_LN>(a, B, st);
+        a.sk_part = nullptr;
+        a.xin = a.hout;
+        a.xt_out = nullptr;
+    }
+    if (e == hipSuccess && mfma) {
+        hipLaunchKernelGGL((tile_weights_kernel<WT>), dim3(2048), dim3(ER_WG), 0, st, reinterpret_cast<const WT*>(f.w), reinterpret_cast<f32x4*>(wt.p), n, k);   // make_tiled
+        e = hipGetLastError();
+        a.W = wt.p;
+    }
+    const SkPart sk = form == ER_FORM_NARROW_DEFER ? SkPart{f.part_out, groups * slices * NBM * (size_t)n} : SkPart{part.p, part.n};
+    if (e == hipSuccess && form != ER_FORM_PREP) {
+        e = hipErrorInvalidValue;
+        switch (proj) {
+            case GF_QKV:        // case 0, batched
+                if (form == ER_FORM_VALU) e = gemv_batched_groups<WT, 1, 3, EPI_QKV>(a, B, k, st);
+                else if (form == ER_FORM_MFMA) e = gemv_mfma_groups<WT, EPI_QKV>(a, B, k, sk, st);
+                else if constexpr (HALF) {
+                    if (form == ER_FORM_MFMA_XT) { a.xin = (const float*)image; e = gemv_mfma_groups<WT, EPI_QKV, true>(a, B, k, sk, st); }
+                }
+                break;
+            case GF_OUTPROJ:    // case 3 (a pass of 5..8 rows in the narrow form is what the last group of a larger batch runs)
+                if (form == ER_FORM_VALU) e = gemv_batched_groups<WT, 1, 1, EPI_RESID>(a, B, k, st);
+                else if (form == ER_FORM_MFMA) e = gemv_mfma_groups<WT, EPI_RESID>(a, B, k, sk, st);
+                else if constexpr (HALF) {
+                    if (form == ER_FORM_NARROW_DEFER) e = gemv_mfma_groups<WT, EPI_RESID, true>(a, B, k, sk, st, true, true);
+                }
+                break;
+            case GF_FC1:        // case 4, batched
+                if (form == ER_FORM_VALU) e = gemv_batched_groups<WT, 1, 3, EPI_RELU>(a, B, k, st);
+                else if (form == ER_FORM_MFMA) e = gemv_mfma_groups<WT, EPI_RELU>(a, B, k, sk, st);
+                else if constexpr (HALF) {
+                    if (form == ER_FORM_MFMA_XT) { a.xin = (const float*)image; a.xt_out = f.xt_out; e = gemv_mfma_groups<WT, EPI_RELU, true>(a, B, k, sk, st); }
+                }
+                break;
+            case GF_FC2:        // case 5, batched
+                if (form == ER_FORM_VALU) e = gemv_batched_groups<WT, 4, 1, EPI_RESID>(a, B, k, st);
+                else if (form == ER_FORM_MFMA) e = gemv_mfma_groups<WT, EPI_RESID>(a, B, k, sk, st);
+                else if constexpr (HALF) {
+                    if (form == ER_FORM_NARROW || form == ER_FORM_NARROW_DEFER) e = gemv_mfma_groups<WT, EPI_RESID, true>(a, B, k, sk, st, form == ER_FORM_NARROW_DEFER, true);
+                }
+                break;
+            case GF_HEAD:       // case 6, batched
+                if (form == ER_FORM_VALU) e = gemv_batched_groups<WT, 1, 1, EPI_STORE>(a, B, k, st);
+                break;
+        }
+    }
+    hipError_t e2 = hipStreamSynchronize(st);
+    HIPRET(e);
+    HIPRET(e2);
+    return ER_OK;
+}
+
+extern "C" int er_k_gemv_form(const er_k_gemv_form_args* f, void* stream) {
+    if (!f) return fail(ER_ERR_INVALID, "er_k_gemv_form: null args");
+    int proj = 0;
+    ERCHK(gemv_form_check(*f, &proj));
+    return f->w_half ? gemv_form_t<_Float16>(*f, proj, (hipStream_t)stream) : gemv_form_t<float>(*f, proj, (hipStream_t)stream);
+}
+
 extern "C" int er_k_attn_outproj3(const float* q, const void* k, const void* v, int len, const void* wo, const float* bo,
                                   const float* resid, float* y, int l_cap, int kv_half, int w_half, void* stream) {
     // version 3 of the single-row decode attention: balanced chunks (16 heads x 16 chunks) + the merge fused into out_proj

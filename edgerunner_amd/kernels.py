@@ -39,6 +39,126 @@ def attn_decode(q, k_cache, v_cache, lens, steps=4, variant=native.ER_ATTN_SPLIT
     return out
 
 
+def xt_pack_image(x):
+    """The tiled hi | lo activation image of x [B, K] fp32 (K a multiple of 4), as the fast-mode matrix-core projections exchange
+    it: a plain restatement of ``xt_entry`` / ``xt_pack`` in csrc/k_gemv.h.  Returns a half tensor [groups, K / 4, 32, 8]:
+    entry (k4, b) of group b >> 5 is 8 halves = hi(x[b, 4 k4 .. 4 k4 + 3]), lo(the same four) with hi = half(x) and
+    lo = half(x - float(hi)), both round-to-nearest-even; a group is K * 128 bytes, i.e. it starts K * 32 floats behind the previous
+    one; rows the batch does not have are zero."""
+    B, K = x.shape
+    assert x.dtype == torch.float32 and K % 4 == 0
+    G = (B + 31) // 32
+    xp = torch.zeros((G * 32, K), dtype=torch.float32, device=x.device)
+    xp[:B] = x
+    hi = xp.half()
+    lo = (xp - hi.float()).half()
+    hi, lo = (t.view(G, 32, K // 4, 4).permute(0, 2, 1, 3) for t in (hi, lo))
+    return torch.cat((hi, lo), dim=3).contiguous()
+
+
+def xt_unpack_image(img, B=None):
+    """Inverse of xt_pack_image: (hi, lo) as [B, K] half tensors (B None: every row of every group, 32 per group)."""
+    G, K4, _, _ = img.shape
+    hi, lo = (img[..., s].permute(0, 2, 1, 3).reshape(G * 32, K4 * 4) for s in (slice(0, 4), slice(4, 8)))
+    n = G * 32 if B is None else B
+    return hi[:n].contiguous(), lo[:n].contiguous()
+
+
+def _i32_dev(values, device, hi, what):
+    v = [int(t) for t in (values.tolist() if torch.is_tensor(values) else values)]
+    assert all(0 <= t < hi for t in v), f"{what} outside [0, {hi})"      # the kernels index with these unchecked
+    return torch.tensor(v, dtype=torch.int32, device=device)
+
+
+def gemv_form(form, epilogue, w, B, *, x=None, bias=None, ln=None, embed=None, sk=None, resid=None, qkv=None, nw=4, rw=1, eps=1e-5,
+              n=None, k=None, w_half=None, return_xnorm=False, prep_xt=False, prep_xt_image=None, xt_out_image=None):
+    """One decode projection in one of the forms the decode step launches it in (``er_k_gemv_form``; native.ER_FORM_* / ER_EPI_*).
+    w [n, k] fp32 or fp16 (None with ER_FORM_PREP).  The prologue is chosen by what is given:
+      ln=(ln_w, ln_b) with x [B, k]            LayerNorm rows
+      embed=(embd [V, k], posemb [P, k], tok, pos)   token + position rows (tok / pos: B ints)
+      ln=... with sk=(part, bias [k], resid [B, k], slices)   LayerNorm over a deferred split-K finish
+      none of them                             x itself - in the tiled forms (ER_FORM_NARROW*) x is xt_pack_image of the input
+    qkv=(kcache, vcache, pos[, q_out]) for ER_EPI_QKV: caches [B, heads, l_cap, head_dim] fp32 or fp16 are written in place at
+    pos[b].  prep_xt: also return the image the batched prologue launch writes (prep_xt_image: write into this one);
+    xt_out_image: the image the tiled fc1 writes (allocated zeroed when the form needs one).
+    Returns a dict: y, xnorm, q, part (ER_FORM_NARROW_DEFER: [groups, k / 384 * 32 * n] raw block), prep_xt, xt_out - those the call produced."""
+    lib = native.load_library()
+    dev = (x if x is not None else (embed[0] if embed is not None else sk[0])).device
+    if w is not None:
+        n, k = w.shape
+        w_half = w.dtype == torch.float16
+    a = native.ErKGemvFormArgs()
+    keep = [w, x, bias, resid]
+    a.w, a.bias, a.x, a.resid = (native.ptr(t).value for t in (w, bias, x, resid))
+    a.w_half, a.batch, a.n, a.k, a.epilogue, a.form, a.nw, a.rw, a.eps = int(bool(w_half)), B, n, k, epilogue, form, nw, rw, eps
+    pro = native.ER_PRO_NONE
+    if ln is not None:
+        pro = native.ER_PRO_LN
+        a.ln_w, a.ln_b = native.ptr(ln[0]).value, native.ptr(ln[1]).value
+    if embed is not None:
+        pro = native.ER_PRO_EMBED
+        embd, posemb, tok, pos = embed
+        tok_d, pos_d = _i32_dev(tok, dev, embd.shape[0], "token"), _i32_dev(pos, dev, posemb.shape[0], "position")
+        assert len(tok_d) == B and len(pos_d) == B and embd.shape[1] == k and posemb.shape[1] == k
+        keep += [tok_d, pos_d]
+        a.embd, a.posemb, a.tok, a.pos = (native.ptr(t).value for t in (embd, posemb, tok_d, pos_d))
+    if sk is not None:
+        pro = native.ER_PRO_LN_SK
+        part, sk_bias, sk_resid, slices = sk
+        groups = (B + 31) // 32
+        assert part.numel() >= groups * slices * 32 * k and sk_resid.shape == (B, k) and sk_bias.numel() == k
+        a.sk_part, a.sk_bias, a.sk_resid, a.sk_slices = native.ptr(part).value, native.ptr(sk_bias).value, native.ptr(sk_resid).value, slices
+    a.prologue = pro
+    if x is not None and pro in (native.ER_PRO_NONE, native.ER_PRO_LN):
+        tiled = form in (native.ER_FORM_NARROW, native.ER_FORM_NARROW_DEFER)
+        assert x.numel() * x.element_size() == ((B + 31) // 32 * 32 if tiled else B) * k * 4, "x does not hold B rows of k (tiled: whole groups)"
+    out = {}
+    if pro != native.ER_PRO_NONE and (return_xnorm or form == native.ER_FORM_PREP):
+        out["xnorm"] = torch.empty((B, k), dtype=torch.float32, device=dev)
+        a.xnorm_out = native.ptr(out["xnorm"]).value
+    if prep_xt or prep_xt_image is not None:
+        out["prep_xt"] = prep_xt_image if prep_xt_image is not None else torch.zeros(((B + 31) // 32, k // 4, 32, 8), dtype=torch.float16, device=dev)
+        assert out["prep_xt"].numel() == (B + 31) // 32 * k * 64
+        a.prep_xt_out = native.ptr(out["prep_xt"]).value
+    if epilogue == native.ER_EPI_QKV and form != native.ER_FORM_PREP:
+        kc, vc, pos = qkv[:3]
+        _, heads, l_cap, hd = kc.shape
+        assert kc.shape == vc.shape and kc.shape[0] == B and kc.dtype == vc.dtype and kc.dtype in (torch.float32, torch.float16)
+        pos_d = _i32_dev(pos, dev, l_cap, "cache position")
+        assert len(pos_d) == B
+        out["q"] = qkv[3] if len(qkv) > 3 else torch.empty((B, heads * hd), dtype=torch.float32, device=dev)
+        assert out["q"].shape == (B, heads * hd) and out["q"].dtype == torch.float32
+        keep += [pos_d]
+        a.pos = native.ptr(pos_d).value      # the decode step feeds the embedding and the cache append the same positions
+        a.q_out, a.kcache, a.vcache = native.ptr(out["q"]).value, native.ptr(kc).value, native.ptr(vc).value
+        a.kv_half, a.heads, a.head_dim, a.l_cap = int(kc.dtype == torch.float16), heads, hd, l_cap
+    elif form == native.ER_FORM_NARROW_DEFER:
+        out["part"] = torch.empty(((B + 31) // 32, (k // 384) * 32 * n), dtype=torch.float32, device=dev)
+        a.part_out = native.ptr(out["part"]).value
+    elif form == native.ER_FORM_MFMA_XT and epilogue == native.ER_EPI_RELU:
+        out["xt_out"] = xt_out_image if xt_out_image is not None else torch.zeros(((B + 31) // 32, n // 4, 32, 8), dtype=torch.float16, device=dev)
+        assert out["xt_out"].numel() == (B + 31) // 32 * n * 64
+        a.xt_out = native.ptr(out["xt_out"]).value
+    elif form != native.ER_FORM_PREP:
+        out["y"] = torch.empty((B, n), dtype=torch.float32, device=dev)
+        a.y = native.ptr(out["y"]).value
+    native.check(lib.er_k_gemv_form(C.byref(a), _st()), "er_k_gemv_form")
+    del keep
+    return out
+
+
+def attn_stream_xt(q, k_cache, v_cache, lens, out_xt):
+    """The streaming decode attention (head_dim 96) that also writes its rows into the tiled image out_xt (half
+    [groups, heads * 24, 32, 8], xt_pack_image's layout; written in place) -> out [B, heads * 96]."""
+    lib = native.load_library()
+    B, H, Lcap, D = k_cache.shape
+    assert D == 96 and out_xt.dtype == torch.float16 and out_xt.numel() == (B + 31) // 32 * H * D * 64
+    out = torch.empty((B, H * D), dtype=torch.float32, device=q.device)
+    native.check(lib.er_k_attn_stream_xt(native.ptr(q), native.ptr(k_cache), native.ptr(v_cache), native.i32_array(lens), native.ptr(out),
+                                         native.ptr(out_xt), B, H, Lcap, int(k_cache.dtype == torch.float16), _st()), "er_k_attn_stream_xt")
+    return out
+
+
 def attn_outproj3(q, k_cache, v_cache, length, wo, bo, resid):
     """Version-3 single-row path: y = Wo . attention(q, K[:length], V[:length]) + bo + resid.
     q [1536] fp32; caches [16,Lcap,96] fp32 or fp16; wo [1536,1536] fp32 or fp16."""

@@ -355,6 +355,56 @@ int er_k_gemv(const float* w_dev, const float* bias_dev, const float* x_dev, con
 int er_k_attn_decode(const float* q_dev, const void* k_dev, const void* v_dev, const int32_t* len_host,
                      float* out_dev, int batch, int heads, int head_dim, int l_cap, int steps, int kv_half,
                      int variant, void* stream);
+/* ONE decode projection in ONE of the forms the decode step launches it in (er_k_gemv reaches the fp32-weight, 4-wave forms only).
+ * The projection is named by (k, prologue, epilogue): qkv = 1536 / LN or EMBED / QKV (n = 3 * heads * head_dim, k = heads * head_dim),
+ * out_proj = 1536 / NONE / RESID, fc1 = 1536 / LN / RELU, fc2 = 6144 / NONE / RESID, lm_head = 1536 / LN / STORE; the entry launches
+ * it through the same launchers, with the same template arguments, as the decode step, and refuses every (projection, form, batch,
+ * weight type) the step never launches with ER_ERR_UNSUPPORTED before anything is launched.  Blocks until the work is complete. */
+typedef enum { ER_PRO_NONE = 0, ER_PRO_LN = 1, ER_PRO_EMBED = 2,
+               ER_PRO_LN_SK = 3      /* LayerNorm of ((p_0 + .. + p_{S-1}) + sk_bias) + sk_resid: a deferred split-K finish (batched forms) */
+} er_gemv_prologue;
+typedef enum { ER_EPI_STORE = 0, ER_EPI_RELU = 1, ER_EPI_RESID = 2, ER_EPI_QKV = 3 } er_gemv_epilogue;
+typedef enum {
+    ER_FORM_ROW = 0,           /* batch <= 4 (fp16 fc2 with rw 4 / 6: batch 1): the row kernel with nw waves x rw rows per workgroup */
+    ER_FORM_ROWS8 = 1,         /* out_proj, batch 5..8: one pass of the 3-wave row kernel */
+    ER_FORM_VALU = 2,          /* batch > 4: the VALU batched kernel, 16 rows per pass */
+    ER_FORM_MFMA = 3,          /* batch > 4: matrix cores, 16-wave workgroups, row-major fp32 input (qkv, out_proj, fc1, fc2) */
+    ER_FORM_MFMA_XT = 4,       /* the same reading the tiled hi | lo image (fp16 weights; qkv and fc1; fc1 writes xt_out INSTEAD of y) */
+    ER_FORM_NARROW = 5,        /* 4-wave workgroups, tiled input, split-K partials finished by the finish kernel (fp16 fc2) */
+    ER_FORM_NARROW_DEFER = 6,  /* the same with the partials left to the caller in part_out (fp16 out_proj: 4 slices, fc2: 16) */
+    ER_FORM_PREP = 7           /* only the batched forms' prologue launch: xnorm_out (required) and prep_xt_out */
+} er_gemv_form;
+typedef struct {
+    const void* w;             /* [n][k] row-major, fp32 or (w_half) fp16; the matrix-core forms tile a temporary copy */
+    const float* bias;         /* [n], nullable */
+    const float* x;            /* PRO_NONE: [B][k] fp32 - in the tiled forms the hi | lo image of it (k * 128 bytes per 32 rows); PRO_LN: the pre-LN rows */
+    const float *ln_w, *ln_b;  /* PRO_LN / PRO_LN_SK */
+    float* xnorm_out;          /* PRO_LN / PRO_EMBED / PRO_LN_SK: the prologue's rows [B][k], nullable except ER_FORM_PREP */
+    const float *embd, *posemb;/* PRO_EMBED: token table [V][k], position table [P][k] */
+    const int32_t* tok;        /* PRO_EMBED: device int32[B] */
+    const int32_t* pos;        /* PRO_EMBED / EPI_QKV: device int32[B], position of the token being fed */
+    const float* sk_part;      /* PRO_LN_SK: [groups][sk_slices][rows of the group][k] as ER_FORM_NARROW_DEFER leaves them */
+    const float *sk_bias, *sk_resid;   /* [k], [B][k] */
+    float* y;                  /* [B][n] (EPI_STORE / RELU / RESID) */
+    const float* resid;        /* EPI_RESID: [B][n] */
+    float* q_out;              /* EPI_QKV: [B][k] */
+    void *kcache, *vcache;     /* EPI_QKV: [B][heads][l_cap][head_dim], fp32 or (kv_half) fp16; row pos[b] is written */
+    void* prep_xt_out;         /* tiled image the batched prologue launch also writes (fp16 weights; caller zeroes it), nullable */
+    void* xt_out;              /* ER_FORM_MFMA_XT fc1: the tiled image of the output, n * 128 bytes per 32 rows (caller zeroes it) */
+    float* part_out;           /* ER_FORM_NARROW_DEFER: [groups][k / 384][rows of the group][n]; group g starts g * (k / 384) * 32 * n floats in */
+    int32_t w_half, kv_half;
+    int32_t batch, n, k;
+    int32_t prologue, epilogue, form;
+    int32_t nw, rw;            /* ER_FORM_ROW */
+    int32_t sk_slices;         /* PRO_LN_SK: 4 or 16 */
+    int32_t heads, head_dim, l_cap;    /* EPI_QKV */
+    float eps;
+} er_k_gemv_form_args;
+int er_k_gemv_form(const er_k_gemv_form_args* args, void* stream);
+/* The ER_ATTN_STREAM kernel of er_k_attn_decode (head_dim 96) that also writes its output rows into the tiled hi | lo image
+ * out_xt_dev (heads * 96 * 128 bytes per 32 rows; rows the batch does not have are left alone), as out_proj's tiled forms read it. */
+int er_k_attn_stream_xt(const float* q_dev, const void* k_dev, const void* v_dev, const int32_t* len_host, float* out_dev,
+                        void* out_xt_dev, int batch, int heads, int l_cap, int kv_half, void* stream);
 /* Version 3 of the single-row decode attention (env ER_DECODE_V=3), one row, 16 heads of 96:
  * y[1536] = Wo . softmax(q K^T / sqrt(D)) V + bo + resid over a [16,Lcap,96] cache holding len keys (Lcap <= 8192):
  * balanced chunks (16 per head) + the partial merge fused into the out_proj GEMV; w_half: Wo is fp16 */
