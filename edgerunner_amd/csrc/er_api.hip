@@ -34,6 +34,8 @@
 #include "meto_decode.h"
 #include "meto_encode.h"
 #include "er_queue_host.h"
+#include "er_decode_plan.h"
+#include "er_decode_proj.h"
 
 using namespace er;
 
@@ -101,32 +103,10 @@ static GenState gen_state_carve(int* sb, size_t b) {
     return s;
 }
 
-constexpr int NBM = 32;   // batch rows per pass of the matrix-core decode projections (k_gemv_mfma.h)
 // K-range partials per row that a 4-wave split-K launch leaves to a LATER launch: out_proj 1536 / 384, fc2 6144 / 384 (4 is also the most
 // a 16-wave launch leaves to its own finish: 6144 / 1536).  KvMem::skpart is sized from them; the launches that write and read pass them.
 constexpr int SK_SLICES_OUTPROJ = 4, SK_SLICES_FC2 = 16;
 static_assert(1536 / (4 * GM_KW) == SK_SLICES_OUTPROJ && 6144 / (4 * GM_KW) == SK_SLICES_FC2 && 6144 / (GM_WAVES * GM_KW) == SK_SLICES_OUTPROJ, "k_gemv_mfma.h");
-
-// Everything the decode step branches on for ONE reserved cache shape: kv_alloc computes it once into the KvMem it describes, it is
-// installed and dropped with that object, and launch_kind_t and the other readers take their decisions from here.
-struct DecodePlan {
-    int B = 0, Lcap = 0, layers = 0;            // B == 0: no cache reserved
-    long long kv_bstride = 0, kv_lstride = 0;   // elements per batch row / per layer of the cache
-    int S_splits = 0, nch3 = 0;                 // chunks per (row, head) of the fixed-chunk attention / per head of the balanced kernel
-    er_decode_plan sel{};                       // what plan_decode chose (er_ctx_plan reports it) ...
-    bool force_batched = false;                 // ... under this ER_FORCE_BATCHED
-    bool batched = false;       // B > 4 (or ER_FORCE_BATCHED=1): weights streamed once per pass of 32 rows (matrix cores)
-    bool valu = false;          // ER_BATCHED_VALU=1: the older VALU kernels (one pass per 16 rows), kept for A/B runs
-    bool mfma = false;          // batched and not valu: the projections run on the matrix cores and read the tiled weight copies
-    bool xt = false;            // fast-mode batches read the tiled activation images (KvMem::xt_*); ER_XT=0 keeps the row-major fp32 inputs (A/B + parity matrix)
-    bool stream_attn = false;   // batched, D == 96 and (forced or B*H >= 256: at least one streaming workgroup per CU)
-    bool v3 = false;            // decode_v == 3 and the reserved cache qualifies
-    bool outproj_rows8 = false; // mfma and 5..8 rows: out_proj is ONE pass of the VALU kernel (gemv_outproj_rows8)
-    // xt, streaming attention and B > 8: the attention writes the tiled image xt_att, out_proj reads it and leaves SK_SLICES_OUTPROJ partials, fc1's LayerNorm launch finishes them
-    bool outproj_partials = false;
-    // fc2 of `layer` leaves SK_SLICES_FC2 partials to the next layer's LayerNorm launch (which asks fc2_defers(layer - 1)); the last layer finishes into ypre, which the lm_head reads
-    bool fc2_defers(int layer) const { return xt && layer >= 0 && layer + 1 < layers; }
-};
 
 // Everything er_kv_reserve allocates for one (batch, Lcap), with the plan of that shape.  It lives and dies as a whole: a new shape replaces
 // the object, a reserve that fails half way never installs its own, er_destroy drops it - and the captured step goes with the buffers it points into.
@@ -150,20 +130,6 @@ struct KvMem {
     KvMem(const KvMem&) = delete;
     KvMem& operator=(const KvMem&) = delete;
     ~KvMem() { if (step_exec) hipGraphExecDestroy(step_exec); }
-};
-
-struct DecodeKnobs {          // the environment knobs of the decode step, read once per context by er_create (read_knobs)
-    bool use_graph = true;    // ER_NO_GRAPH=1: eager launches
-    // waves per workgroup of the qkv / fc1 GEMVs (env ER_NW_QKV: 4, 6 or 9; ER_NW_FC1: 4 or 12).  Exact mode: qkv 6 waves x 1 row
-    // = 768 workgroups (3 per CU), fc1 4 waves x 2 rows = 768; fast mode: one fat workgroup per CU (9 / 12 waves x 2 rows).  The other
-    // shapes are fixed (out_proj 3 waves x 1 row, fc2 4 K-slices x 2 rows, 128-key chunks for the fixed-chunk attention): their
-    // round-1/2 knobs (ER_RW_*, ER_NW_OUT, ER_ATTN_STEPS, ER_ATTN_V, ER_COMBINE_V, ER_ATTN_GRID_HS, ER_OUT_VALU) are settled and gone
-    int nw_qkv = 6, nw_fc1 = 4;
-    int prefill_attn_f16s = -1;   // fast-mode prefix attention on the fp16 matrix cores with hi/lo-split q and p (k_flash_attn_f16s.h): on unless
-                                  // ER_PREFILL_ATTN_F16S=0 (the fp32-matrix-core kernel; kept for the parity matrix)
-    int attn_v_batched = 0;   // attention kernel at B > 4 (env ER_ATTN_V_BATCHED): 0 = auto (streaming when B*H >= 256, else split + merge), 1 = split kernel + merge, 3 = one streaming workgroup per (row, head), no merge
-    int decode_v = 3;         // single-row decode: 3 = balanced-chunk attention + merge fused into out_proj (one row, D = 96, 16 heads, Lcap <= 8192); ER_DECODE_V=2 = fixed 128-key chunks + merge kernel (also the fallback when the cache does not qualify)
-    int rw_fc2 = 6;           // fast mode, one row: rows per fc2 workgroup (env ER_RW_FC2: 2 / 4 / 6, anything else runs as 2; launch_kind_t case 5)
 };
 
 struct er_ctx {
@@ -228,8 +194,6 @@ static DecodeKnobs read_knobs(bool fast) {
     return k;
 }
 
-// the three switches er_kv_reserve reads for the shape it reserves (tests flip them between two reserves of one context)
-struct ReserveKnobs { bool force_batched, batched_valu, xt; };
 static ReserveKnobs read_reserve_knobs() { return {env_is("ER_FORCE_BATCHED", '1'), env_is("ER_BATCHED_VALU", '1'), !env_is("ER_XT", '0')}; }
 
 extern "C" int er_abi_version(void) { return ER_ABI_VERSION; }
@@ -401,29 +365,16 @@ static int make_tiled_weights(er_ctx* c) {
 }
 
 // ------------------------------------------------------------------------------------ which decode kernels a cache shape gets
-// ONE place for the selection rules (pure host logic).  er_plan_decode reports them for a hypothetical shape; kv_alloc derives the
-// DecodePlan of a reserved shape from them and stores it with that shape's memory:
-//   batched     : B > 4 (or forced) - weights streamed once per pass of 32 rows on the matrix cores
-//   version 3   : one row, 16 heads of 96, hidden 1536, reserved cache <= 16 chunks x 512 keys; else version 2
-//   attention B>4: streaming kernel when forced or (auto and B * heads >= 256: at least one workgroup per CU - at B = 16 it
-//                  ties the split kernel and saves the merge launch, at B = 8 it is 1.5x slower), else split + merge
-static void plan_decode(int decode_v, int attn_v_batched, bool force_batched, int batch, int H, int D, int hid, int Lcap,
-                        er_decode_plan* p) {
-    p->batched = (batch > 4 || force_batched) ? 1 : 0;
-    p->attn_chunks = attn3_num_chunks(H);
-    const bool v3 = decode_v == 3 && batch == 1 && !p->batched && D == 96 && H == 16 && hid == 1536 && attn3_fits(Lcap, H);
-    p->decode_version = v3 ? 3 : 2;
-    const bool stream = p->batched && D == 96 && (attn_v_batched == 3 || (attn_v_batched == 0 && batch * H >= 256));
-    p->attn_kernel = !p->batched ? (v3 ? ER_ATTN_BALANCED : ER_ATTN_SPLIT2)
-                                 : (stream ? ER_ATTN_STREAM : ER_ATTN_SPLIT1);
-    p->merge_launch = (p->attn_kernel == ER_ATTN_SPLIT1 || p->attn_kernel == ER_ATTN_SPLIT2) ? 1 : 0;
-    p->launches_per_layer = p->batched ? 0 : 5 + p->merge_launch;       // qkv, attention, (merge,) out_proj, fc1, fc2
+// The selection rules are host-only code in er_decode_plan.h (plan_decode, make_decode_plan, proj_form); the attention kernels' chunking
+// enters them as numbers.
+static AttnChunking attn_chunking(int heads, bool fast) {
+    return {attn3_num_chunks(heads), attn3_num_chunks(heads) * ATTN3_CAP, attn_chunk(ATTN_STEPS_DEFAULT, fast)};
 }
 
 extern "C" int er_plan_decode(int batch, int heads, int head_dim, int hidden, int l_cap, er_decode_plan* out) {
     if (!out || batch <= 0 || heads <= 0 || head_dim <= 0 || l_cap <= 0) return fail(ER_ERR_INVALID, "er_plan_decode: bad argument");
     const DecodeKnobs k = read_knobs(false);
-    plan_decode(k.decode_v, k.attn_v_batched, read_reserve_knobs().force_batched, batch, heads, head_dim, hidden, (l_cap + 31) / 32 * 32, out);
+    plan_decode(k.decode_v, k.attn_v_batched, read_reserve_knobs().force_batched, batch, heads, head_dim, hidden, (l_cap + 31) / 32 * 32, attn_chunking(heads, false), out);
     return ER_OK;
 }
 
@@ -467,18 +418,8 @@ extern "C" int er_kv_reserve(er_ctx* c, int batch, int max_len) {
 static int kv_alloc(er_ctx* c, KvMem& m, int batch, int Lcap) {
     const er_config& g = c->cfg;
     const int H = g.num_heads, D = c->D, hid = g.hidden_dim;
-    const ReserveKnobs rk = read_reserve_knobs();
-    DecodePlan& p = m.plan;
-    p.B = batch; p.Lcap = Lcap; p.layers = g.num_layers;
-    p.kv_bstride = (long long)H * Lcap * D; p.kv_lstride = p.kv_bstride * batch;
-    p.S_splits = attn_num_chunks(Lcap, attn_chunk(ATTN_STEPS_DEFAULT, c->fast));   // decode attention: one workgroup per (row, head, chunk of 32*steps keys)
-    p.nch3 = attn3_num_chunks(H);
-    p.force_batched = rk.force_batched; p.valu = rk.batched_valu;
-    plan_decode(c->knobs.decode_v, c->knobs.attn_v_batched, p.force_batched, batch, H, D, hid, Lcap, &p.sel);
-    p.batched = p.sel.batched != 0; p.mfma = p.batched && !p.valu; p.xt = c->fast && p.mfma && rk.xt;
-    p.stream_attn = p.sel.attn_kernel == ER_ATTN_STREAM; p.v3 = p.sel.decode_version == 3;
-    p.outproj_rows8 = p.mfma && batch >= 5 && batch <= 8;
-    p.outproj_partials = p.xt && p.stream_attn && batch > 8;
+    m.plan = make_decode_plan(c->knobs, read_reserve_knobs(), c->fast, batch, Lcap, g.num_layers, H, D, hid, attn_chunking(H, c->fast));
+    const DecodePlan& p = m.plan;
     const size_t kv_bytes = (size_t)p.kv_lstride * g.num_layers * c->kv_esz;
     ERCHK(m.kc.ensure(kv_bytes));
     ERCHK(m.vc.ensure(kv_bytes));
@@ -526,105 +467,6 @@ static int kv_alloc(er_ctx* c, KvMem& m, int batch, int Lcap) {
 }
 
 // ------------------------------------------------------------------------------------ decode step
-// a with every per-row pointer advanced to batch row row0 (K = width of an input row): what a pass of the three group loops below launches with.
-// The batched kernels read neither hout nor tok, and the tiled image of a group of 32 rows is K * 32 floats like its row-major form: one rule serves all.
-static GemvArgs gemv_args_at(const GemvArgs& a, int row0, int K) {
-    GemvArgs g = a;
-    if (g.xin) g.xin += (long long)row0 * K;
-    if (g.xt_out) g.xt_out = (char*)g.xt_out + (long long)row0 * a.N * 4;     // xt_entry() indexes inside a group
-    if (g.hout) g.hout += (long long)row0 * K;
-    if (g.tok) g.tok += row0;
-    if (g.pos) g.pos += row0;
-    if (g.out) g.out += (long long)row0 * a.N;
-    if (g.resid) g.resid += (long long)row0 * a.N;
-    if (g.q) g.q += (long long)row0 * a.hidden;
-    const long long kvb = (long long)row0 * a.kv_bstride * (a.kv_half ? 2 : 4);
-    if (g.kcache) g.kcache = (char*)g.kcache + kvb;
-    if (g.vcache) g.vcache = (char*)g.vcache + kvb;
-    return g;
-}
-
-template <typename WT, int KS, int RW, int PRO, int EPI, int NW = ER_NWAVES>
-static hipError_t gemv_groups(const GemvArgs& a, int B, int K, hipStream_t st) {
-    // rows are processed in groups of up to 4 (one weight stream, 1..4 accumulators per row)
-    int b = 0;
-    while (b < B) {
-        int nb = B - b;
-        nb = nb >= 4 ? 4 : nb;
-        const GemvArgs g = gemv_args_at(a, b, K);
-        hipError_t e;
-        if (nb == 4) e = launch_gemv<WT, KS, 4, RW, PRO, EPI, NW>(g, st);
-        else if (nb == 3) e = launch_gemv<WT, KS, 3, RW, PRO, EPI, NW>(g, st);
-        else if (nb == 2) e = launch_gemv<WT, KS, 2, RW, PRO, EPI, NW>(g, st);
-        else e = launch_gemv<WT, KS, 1, RW, PRO, EPI, NW>(g, st);
-        if (e != hipSuccess) return e;
-        b += nb;
-    }
-    return hipSuccess;
-}
-
-// single-row GEMV with a LayerNorm / embedding prologue by waves per workgroup: 4 or 6 waves x 1 row (qkv), 4 waves x 2 rows (fc1),
-// or ONE fat workgroup per CU - 9 waves x 2 rows = 4608 qkv rows / 256, 12 waves x 2 rows = 6144 fc1 rows / 256
-template <typename WT, int PRO, int EPI>
-static hipError_t gemv_nw(int nw, GemvArgs a, int B, int K, hipStream_t st) {
-    if (nw == 6) return gemv_groups<WT, 1, 1, PRO, EPI, 6>(a, B, K, st);
-    if (nw == 9) return gemv_groups<WT, 1, 2, PRO, EPI, 9>(a, B, K, st);
-    if (nw == 12) return gemv_groups<WT, 1, 2, PRO, EPI, 12>(a, B, K, st);
-    if (EPI == EPI_QKV) return gemv_groups<WT, 1, 1, PRO, EPI>(a, B, K, st);
-    return gemv_groups<WT, 1, 2, PRO, EPI>(a, B, K, st);
-}
-
-// out_proj of 5..8 rows: ONE pass of the VALU kernel with 5..8 accumulators per weight row.  The matrix-core kernel has only 48
-// row tiles for this 1536-row matrix (48 of 256 CUs: 9.3 us at B = 5 against 4.9 us for the four-row VALU launch), which left the
-// aggregate rate of five rows below that of four (profiles/r03_batch_table_v2.log); same per-(row, batch row) arithmetic as every
-// other path.
-template <typename WT>
-static hipError_t gemv_outproj_rows8(const GemvArgs& a, int B, hipStream_t st) {
-    switch (B) {
-        case 5: return launch_gemv<WT, 1, 5, 1, PRO_NONE, EPI_RESID, 3>(a, st);
-        case 6: return launch_gemv<WT, 1, 6, 1, PRO_NONE, EPI_RESID, 3>(a, st);
-        case 7: return launch_gemv<WT, 1, 7, 1, PRO_NONE, EPI_RESID, 3>(a, st);
-        case 8: return launch_gemv<WT, 1, 8, 1, PRO_NONE, EPI_RESID, 3>(a, st);
-    }
-    return hipErrorInvalidValue;
-}
-
-// B > 4: weights streamed once per pass of up to 16 rows (gemv_batched_kernel)
-constexpr int NBB = 16;
-template <typename WT, int PH, int RW, int EPI>
-static hipError_t gemv_batched_groups(const GemvArgs& a, int B, int K, hipStream_t st) {
-    for (int b = 0; b < B; b += NBB) {
-        const int nb = (B - b) < NBB ? (B - b) : NBB;
-        hipError_t e = launch_gemv_batched<WT, PH, NBB, RW, EPI>(gemv_args_at(a, b, K), nb, st);
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
-}
-// XT: a.xin is the tiled image of the input (a group of 32 rows is K * 32 floats there as well, so the group offsets coincide)
-struct SkPart { float* p; size_t floats; };       // the context's split-K partial block and its size
-template <typename WT, int EPI, bool XT = false>
-static hipError_t gemv_mfma_groups(const GemvArgs& a, int B, int K, SkPart part, hipStream_t st, bool defer_finish = false, bool narrow = false) {
-    const int slices = narrow ? K / (4 * GM_KW) : K / (GM_WAVES * GM_KW);
-    {   // the block was sized in er_kv_reserve for K <= 6144 (4 wide / 16 narrow slices) and, when the finish is not deferred, for ONE
-        // group at a time on an in-order stream: refuse anything that would overrun it instead of writing past the end
-        const size_t groups = (size_t)(B + NBM - 1) / NBM;
-        const size_t need = (defer_finish ? groups : 1) * slices * NBM * (size_t)a.N;
-        if (!part.p || need > part.floats) return hipErrorInvalidValue;
-    }
-    for (int b = 0; b < B; b += NBM) {
-        const int nb = (B - b) < NBM ? (B - b) : NBM;
-        // deferred: every group keeps its own partial block (prep_rows_kernel: g * 4 * 32 * K floats)
-        hipError_t e = launch_gemv_mfma<WT, EPI, XT>(gemv_args_at(a, b, K), nb, K, defer_finish ? part.p + (long long)(b / NBM) * slices * NBM * a.N : part.p, st, defer_finish, narrow);
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
-}
-template <int PRO>
-static hipError_t prep_rows(const GemvArgs& a, int B, hipStream_t st) {
-    hipLaunchKernelGGL((prep_rows_kernel<PRO>), dim3(B), dim3(ER_WG), 0, st, a);
-    return hipGetLastError();
-}
-
 static AttnDecArgs attn_args(er_ctx* c, int layer) {
     const DecodePlan& p = c->kv->plan;
     AttnDecArgs a{};
@@ -655,49 +497,38 @@ static hipError_t launch_attn_combine(const AttnDecArgs& a, int D, int B, hipStr
     return D == 96 ? launch_attn_combine_d<96>(a, B, st) : launch_attn_combine_d<64>(a, B, st);
 }
 
+// A projection kind fills the operands from the context (plain weights, row-major input, and in io what the other forms read instead);
+// the form comes from proj_form and the launches from run_proj (er_decode_proj.h).
 template <typename WT>
 static hipError_t launch_kind_t(er_ctx* c, int kind, int layer, hipStream_t st, long long* out_ids, int out_ld) {
     constexpr bool HALF = sizeof(WT) == 2;
     const er_config& g = c->cfg;
     const DecodePlan& p = c->kv->plan;
+    const KvMem& kv = *c->kv;
     const int H = g.hidden_dim, I = g.intermediate_dim, B = p.B;
-    const SkPart sk{c->kv->skpart.p, c->kv->skpart.n};
+    const SkPart sk{kv.skpart.p, kv.skpart.n};
+    const auto form_of = [&](Proj proj, int l) { return proj_form(p, c->knobs, HALF, proj, l); };
     GemvArgs a{};
     a.eps = g.ln_eps;
     a.hidden = H; a.head_dim = c->D; a.l_cap = p.Lcap; a.kv_bstride = p.kv_bstride; a.kv_half = HALF ? 1 : 0;
+    ProjIo io;
     switch (kind) {
         case 0: {   // qkv
             const LayerW& L = c->layers[layer];
             a.W = HALF ? (const void*)L.wqkv_h : (const void*)L.wqkv; a.bias = L.bqkv; a.N = 3 * H;
-            a.hout = c->kv->hbuf.p; a.pos = c->kv->st.pos;
-            a.q = c->kv->qbuf.p;
-            a.kcache = c->kv->kc.p + (long long)layer * p.kv_lstride * c->kv_esz;
-            a.vcache = c->kv->vc.p + (long long)layer * p.kv_lstride * c->kv_esz;
+            a.hout = kv.hbuf.p; a.pos = kv.st.pos;
+            a.q = kv.qbuf.p;
+            a.kcache = kv.kc.p + (long long)layer * p.kv_lstride * c->kv_esz;
+            a.vcache = kv.vc.p + (long long)layer * p.kv_lstride * c->kv_esz;
             if (layer == 0) {
-                a.embd = c->embd; a.posemb = c->posemb; a.tok = c->kv->st.tok;
+                io.pro = PRO_EMBED; a.embd = c->embd; a.posemb = c->posemb; a.tok = kv.st.tok;
             } else {
-                a.xin = c->kv->ypre.p; a.ln_w = c->layers[layer - 1].ln2w; a.ln_b = c->layers[layer - 1].ln2b;
+                io.pro = PRO_LN; a.xin = kv.ypre.p; a.ln_w = c->layers[layer - 1].ln2w; a.ln_b = c->layers[layer - 1].ln2b;
+                // the previous layer's fc2 deferred its split-K finish to this LayerNorm
+                if (form_of(PROJ_FC2, layer - 1).defer) io.rd = {sk.p, c->layers[layer - 1].b2, kv.h1buf.p, SK_SLICES_FC2};
             }
-            if (p.batched) {
-                if constexpr (HALF) {
-                    a.xt_out = p.xt ? c->kv->xt_h.p : nullptr;
-                    if (p.fc2_defers(layer - 1)) {      // the previous layer's fc2 deferred its split-K finish to this LayerNorm (case 5)
-                        a.sk_part = sk.p; a.sk_bias = c->layers[layer - 1].b2; a.sk_resid = c->kv->h1buf.p; a.sk_batch = B; a.sk_slices = SK_SLICES_FC2;
-                    }
-                }
-                hipError_t e = layer == 0 ? prep_rows<PRO_EMBED>(a, B, st) : prep_rows<PRO_LN>(a, B, st);
-                a.sk_part = nullptr;
-                if (e != hipSuccess) return e;
-                a.xin = c->kv->hbuf.p;
-                a.xt_out = nullptr;
-                if constexpr (HALF) {
-                    if (p.xt) { a.W = L.wqkv_t; a.xin = (const float*)c->kv->xt_h.p; return gemv_mfma_groups<WT, EPI_QKV, true>(a, B, H, sk, st); }
-                }
-                if (p.mfma) { a.W = L.wqkv_t; return gemv_mfma_groups<WT, EPI_QKV>(a, B, H, sk, st); }   // 144 tiles of 32 rows
-                return gemv_batched_groups<WT, 1, 3, EPI_QKV>(a, B, H, st);   // 4608 rows = 192 workgroups x 24: one round
-            }
-            if (layer == 0) return gemv_nw<WT, PRO_EMBED, EPI_QKV>(c->knobs.nw_qkv, a, B, H, st);
-            return gemv_nw<WT, PRO_LN, EPI_QKV>(c->knobs.nw_qkv, a, B, H, st);
+            io.w_tiled = L.wqkv_t; io.x_image = kv.xt_h.p; io.pro_image = p.xt ? kv.xt_h.p : nullptr;
+            return run_proj<WT>(PROJ_QKV, form_of(PROJ_QKV, layer), io, a, B, H, sk, st);
         }
         // v2 holds a wave's whole K/V slice in flight (latency-bound single rows); with hundreds of workgroups per CU's
         // worth of work (B > 4) the leaner v1 (66-74 VGPRs, 6-7 waves per SIMD) streams faster: 570 vs 636 us at B = 32, L = 18050
@@ -716,78 +547,31 @@ static hipError_t launch_kind_t(er_ctx* c, int kind, int layer, hipStream_t st, 
                 m.part_o = c->kv->part.p; m.part_ml = c->kv->part_ml.p; m.N = H;
                 return launch_outproj_merge<WT, 96>(m, p.nch3, st);
             }
-            a.W = HALF ? (const void*)L.wo_h : (const void*)L.wo; a.bias = L.bo; a.N = H; a.xin = c->kv->abuf.p; a.out = c->kv->ypre1.p; a.resid = c->kv->hbuf.p;
-            // 48 row tiles of 32: the matrix-core kernel runs on 48 CUs only, but streams the matrix ONCE for 32 rows where the
-            // VALU kernel needs a pass per 16
-            if (p.outproj_rows8) return gemv_outproj_rows8<WT>(a, B, st);
-            if constexpr (HALF) {
-                // 4-wave workgroups (48 row tiles x 4 K-ranges of 384 instead of 48 x one of 1536); + bias + residual happen in fc1's
-                // LayerNorm-rows launch (case 4), which reads the four partials
-                if (p.outproj_partials) { a.W = L.wo_t; a.xin = (const float*)c->kv->xt_att.p; return gemv_mfma_groups<WT, EPI_RESID, true>(a, B, H, sk, st, true, true); }
-            }
-            if (p.mfma) { a.W = L.wo_t; return gemv_mfma_groups<WT, EPI_RESID>(a, B, H, sk, st); }
-            if (p.batched) return gemv_batched_groups<WT, 1, 1, EPI_RESID>(a, B, H, st);
-            return gemv_groups<WT, 1, 1, PRO_NONE, EPI_RESID, 3>(a, B, H, st);     // 3 waves x 1 row: 512 workgroups = 2 per CU
+            a.W = HALF ? (const void*)L.wo_h : (const void*)L.wo; a.bias = L.bo; a.N = H; a.xin = kv.abuf.p; a.out = kv.ypre1.p; a.resid = kv.hbuf.p;
+            io.w_tiled = L.wo_t; io.x_image = kv.xt_att.p;      // the streaming attention wrote the image (attn_args: out_xt)
+            return run_proj<WT>(PROJ_OUT, form_of(PROJ_OUT, layer), io, a, B, H, sk, st);
         }
         case 4: {   // h1 = LN1(ypre1); f = relu(fc1 h1 + b)
             const LayerW& L = c->layers[layer];
-            a.W = HALF ? (const void*)L.w1_h : (const void*)L.w1; a.bias = L.b1; a.N = I; a.xin = c->kv->ypre1.p; a.ln_w = L.ln1w; a.ln_b = L.ln1b;
-            a.hout = c->kv->h1buf.p; a.out = c->kv->fbuf.p;
-            if (p.batched) {
-                if constexpr (HALF) {
-                    a.xt_out = p.xt ? c->kv->xt_h.p : nullptr;
-                    if (p.outproj_partials) {      // out_proj (case 3) left four K-range partials: ypre1 = ((sum) + bo) + h
-                        a.sk_part = sk.p; a.sk_bias = L.bo; a.sk_resid = c->kv->hbuf.p; a.sk_batch = B; a.sk_slices = SK_SLICES_OUTPROJ;
-                    }
-                }
-                hipError_t e = prep_rows<PRO_LN>(a, B, st);
-                a.sk_part = nullptr;
-                if (e != hipSuccess) return e;
-                a.xin = c->kv->h1buf.p;
-                a.xt_out = nullptr;
-                if constexpr (HALF) {
-                    if (p.xt) {      // input and output both tiled: fc2 below reads xt_f
-                        a.W = L.w1_t; a.xin = (const float*)c->kv->xt_h.p; a.xt_out = c->kv->xt_f.p;
-                        return gemv_mfma_groups<WT, EPI_RELU, true>(a, B, H, sk, st);
-                    }
-                }
-                if (p.mfma) { a.W = L.w1_t; return gemv_mfma_groups<WT, EPI_RELU>(a, B, H, sk, st); }   // 192 tiles of 32 rows
-                return gemv_batched_groups<WT, 1, 3, EPI_RELU>(a, B, H, st);   // 6144 rows = 256 workgroups x 24
-            }
-            return gemv_nw<WT, PRO_LN, EPI_RELU>(c->knobs.nw_fc1, a, B, H, st);
+            a.W = HALF ? (const void*)L.w1_h : (const void*)L.w1; a.bias = L.b1; a.N = I; a.xin = kv.ypre1.p; a.ln_w = L.ln1w; a.ln_b = L.ln1b;
+            a.hout = kv.h1buf.p; a.out = kv.fbuf.p;
+            io.pro = PRO_LN;
+            // out_proj (case 3) left four K-range partials: ypre1 = ((sum) + bo) + h
+            if (form_of(PROJ_OUT, layer).defer) io.rd = {sk.p, L.bo, kv.hbuf.p, SK_SLICES_OUTPROJ};
+            io.w_tiled = L.w1_t; io.x_image = kv.xt_h.p; io.pro_image = p.xt ? kv.xt_h.p : nullptr; io.out_image = kv.xt_f.p;
+            return run_proj<WT>(PROJ_FC1, form_of(PROJ_FC1, layer), io, a, B, H, sk, st);
         }
         case 5: {   // ypre = fc2 f + b + h1
             const LayerW& L = c->layers[layer];
-            a.W = HALF ? (const void*)L.w2_h : (const void*)L.w2; a.bias = L.b2; a.N = H; a.xin = c->kv->fbuf.p; a.out = c->kv->ypre.p; a.resid = c->kv->h1buf.p;
-            if constexpr (HALF) {
-                // layers 0 .. nl-2 leave the four K-range partials to the next layer's LayerNorm launch (case 0); the last layer finishes
-                // into ypre, which the lm_head reads (after a prefill ypre comes from the GEMM path, so case 6 always reads ypre)
-                // 4-wave workgroups: 48 row tiles x 16 K-ranges of 384 (768 workgroups = 3 per CU instead of 192 on 192 CUs)
-                if (p.xt) { a.W = L.w2_t; a.xin = (const float*)c->kv->xt_f.p; return gemv_mfma_groups<WT, EPI_RESID, true>(a, B, I, sk, st, p.fc2_defers(layer), true); }
-            }
-            if (p.mfma) { a.W = L.w2_t; return gemv_mfma_groups<WT, EPI_RESID>(a, B, I, sk, st); }   // 48 tiles x 4 K-ranges
-            if (p.batched) return gemv_batched_groups<WT, 4, 1, EPI_RESID>(a, B, I, st);
-            if constexpr (HALF) {
-                // fast mode, one row: FAT workgroups like qkv's and fc1's - 4 or 6 rows per workgroup instead of 2 (384 / 256 workgroups
-                // instead of 768), so that a CU fetches the 24 KB input vector once or twice instead of three times beside its 72 KB of
-                // fp16 weights: fc2 5.60 -> 5.37 us at 6 rows, 5.68 at 4, ids unchanged (profiles/r05_ab_fc2_rows.log; ER_RW_FC2 = 2 / 4 / 6)
-                // (read at er_create, like every A/B knob of the step graph: the graph is captured with that value; 2 / 4 / 6 only)
-                if (B == 1 && c->knobs.rw_fc2 == 6) return launch_gemv<WT, 4, 1, 6, PRO_NONE, EPI_RESID>(a, st);
-                if (B == 1 && c->knobs.rw_fc2 == 4) return launch_gemv<WT, 4, 1, 4, PRO_NONE, EPI_RESID>(a, st);
-            }
-            return gemv_groups<WT, 4, 2, PRO_NONE, EPI_RESID>(a, B, I, st);
+            a.W = HALF ? (const void*)L.w2_h : (const void*)L.w2; a.bias = L.b2; a.N = H; a.xin = kv.fbuf.p; a.out = kv.ypre.p; a.resid = kv.h1buf.p;
+            io.w_tiled = L.w2_t; io.x_image = kv.xt_f.p;
+            return run_proj<WT>(PROJ_FC2, form_of(PROJ_FC2, layer), io, a, B, I, sk, st);
         }
         case 6: {   // logits = lm_head LN2_last(ypre)
-            a.W = HALF ? (const void*)c->lm_head_h : (const void*)c->lm_head; a.bias = nullptr; a.N = g.vocab_size; a.xin = c->kv->ypre.p;
-            a.ln_w = c->layers[p.layers - 1].ln2w; a.ln_b = c->layers[p.layers - 1].ln2b; a.hout = nullptr; a.out = c->kv->logits.p;
-            if (p.batched) {
-                a.hout = c->kv->hbuf.p;
-                hipError_t e = prep_rows<PRO_LN>(a, B, st);
-                if (e != hipSuccess) return e;
-                a.xin = c->kv->hbuf.p;
-                return gemv_batched_groups<WT, 1, 1, EPI_STORE>(a, B, H, st);
-            }
-            return gemv_groups<WT, 1, 1, PRO_LN, EPI_STORE>(a, B, H, st);
+            a.W = HALF ? (const void*)c->lm_head_h : (const void*)c->lm_head; a.bias = nullptr; a.N = g.vocab_size; a.xin = kv.ypre.p;
+            a.ln_w = c->layers[p.layers - 1].ln2w; a.ln_b = c->layers[p.layers - 1].ln2b; a.hout = p.batched ? kv.hbuf.p : nullptr; a.out = kv.logits.p;
+            io.pro = PRO_LN;
+            return run_proj<WT>(PROJ_HEAD, form_of(PROJ_HEAD, layer), io, a, B, H, sk, st);
         }
         case 7:
             hipLaunchKernelGGL(sample_head_kernel, dim3(B), dim3(ER_WG), sample_head_lds(g.vocab_size), st, c->kv->logits.p,
@@ -1683,60 +1467,76 @@ static int profile_impl(er_ctx* c, int repeats, int use_graph, float* avg_us, do
 // ------------------------------------------------------------------------------------ single-kernel entry points
 // Their temporaries are local DevBufs: allocated before the first launch, and freed by every return path - behind the explicit
 // hipStreamSynchronize on the paths that launched something.
+// One projection on caller-owned operands in a batched form, as er_k_gemv and er_k_gemv_form run it.  It first gets what a decode context
+// keeps per reserved shape: rows for the prologue's output when the caller wants none back, the tiled copy of the weights (make_tiled),
+// the split-K block (a deferred form leaves its partials in part_out instead) and, for the wide tiled form, one zeroed image of
+// K * 128 bytes per group of 32 rows unless the caller passed one.  Then run_proj - or, for ER_FORM_PREP, the prologue launch alone.
+template <typename WT>
+static int proj_entry(Proj proj, const ProjForm& f, ProjIo io, GemvArgs a, int B, int K, float* part_out, hipStream_t st) {
+    const int form = f.form, n = a.N;
+    const size_t groups = (size_t)(B + NBM - 1) / NBM;
+    const int slices = form == ER_FORM_NARROW || form == ER_FORM_NARROW_DEFER ? K / (4 * GM_KW) : K / (GM_WAVES * GM_KW);
+    DevBuf<float> tmp, part;
+    DevBuf<char> wt, img;
+    SkPart sk{nullptr, 0};
+    hipError_t e = hipSuccess;
+    if (form != ER_FORM_ROW && form != ER_FORM_ROWS8) {
+        if (io.pro != PRO_NONE && !a.hout) { ERCHK(tmp.ensure((size_t)B * K)); a.hout = tmp.p; }
+        if (form_mfma(form)) {
+            ERCHK(wt.ensure(tiled_weight_bytes<WT>(n, K)));
+            if (form != ER_FORM_NARROW_DEFER) ERCHK(part.ensure((size_t)slices * NBM * n));
+            sk = form == ER_FORM_NARROW_DEFER ? SkPart{part_out, groups * slices * NBM * (size_t)n} : SkPart{part.p, part.n};
+        }
+        if (form == ER_FORM_MFMA_XT) {
+            if (!io.pro_image) {
+                ERCHK(img.ensure(groups * (size_t)K * 128));
+                HIPCHK(hipMemsetAsync(img.p, 0, groups * (size_t)K * 128, st));
+                io.pro_image = img.p;
+            }
+            io.x_image = io.pro_image;
+        }
+        if (form_mfma(form)) {
+            hipLaunchKernelGGL((tile_weights_kernel<WT>), dim3(2048), dim3(ER_WG), 0, st, reinterpret_cast<const WT*>(a.W), reinterpret_cast<f32x4*>(wt.p), n, K);
+            e = hipGetLastError();
+            io.w_tiled = wt.p;
+        }
+    }
+    if (e == hipSuccess) e = form == ER_FORM_PREP ? launch_prologue(io.pro, a, B, io.rd, io.pro_image, st) : run_proj<WT>(proj, f, io, a, B, K, sk, st);
+    hipError_t e2 = hipStreamSynchronize(st);
+    HIPRET(e);
+    HIPRET(e2);
+    return ER_OK;
+}
+
+// (k, relu, resid) name the projection: fc1, lm_head and out_proj at k = 1536, fc2 at 6144.  batch <= 4: its fp32 4-wave row kernel,
+// which exists with the projection's own prologue only; batch > 4: the batched form (LayerNorm rows first when ln_w is given).
 extern "C" int er_k_gemv(const float* w, const float* bias, const float* x, const float* ln_w, const float* ln_b,
                          const float* resid, float* y, float* xnorm_out, int B, int n, int k, int relu, float eps, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     GemvArgs a{};
     a.W = w; a.bias = bias; a.N = n; a.xin = x; a.ln_w = ln_w; a.ln_b = ln_b; a.eps = eps; a.hout = xnorm_out;
     a.out = y; a.resid = resid;
-    hipError_t e;
-    if (B > 4) {   // batched kernels: LayerNorm rows first (same arithmetic as the fused prologue), then passes of 32 (VALU: 16) rows
-        DevBuf<float> tmp, part;
-        DevBuf<char> wt;                 // tiled copy of w for the matrix-core kernels (the decode step keeps one per matrix)
-        if (ln_w && k != 1536) return fail(ER_ERR_UNSUPPORTED, "er_k_gemv: LayerNorm prologue needs k=1536");
-        if (ln_w && !xnorm_out) ERCHK(tmp.ensure((size_t)B * k));
-        const bool valu = env_is("ER_BATCHED_VALU", '1');
-        const bool mfma = !valu && ((k == 1536 && relu && !resid) || (k == 6144 && !relu && resid && !ln_w));
-        if (mfma) {
-            ERCHK(part.ensure((size_t)4 * NBM * n));
-            ERCHK(wt.ensure(tiled_weight_bytes<float>(n, k)));
-        }
-        if (ln_w) {
-            if (tmp.p) a.hout = tmp.p;
-            e = prep_rows<PRO_LN>(a, B, st);
-            HIPRET(e);
-            a.xin = a.hout;
-        }
-        if (mfma) hipLaunchKernelGGL((tile_weights_kernel<float>), dim3(1024), dim3(ER_WG), 0, st, w, reinterpret_cast<f32x4*>(wt.p), n, k);
-        GemvArgs am = a;
-        am.W = wt.p;
-        if (k == 1536) {
-            if (relu && !resid) e = valu ? gemv_batched_groups<float, 1, 2, EPI_RELU>(a, B, k, st) : gemv_mfma_groups<float, EPI_RELU>(am, B, k, SkPart{part.p, part.n}, st);
-            else if (!relu && !resid) e = gemv_batched_groups<float, 1, 1, EPI_STORE>(a, B, k, st);   // narrow: VALU kernel, as in the decode step
-            else if (!relu && resid) e = gemv_batched_groups<float, 1, 1, EPI_RESID>(a, B, k, st);
-            else e = hipErrorInvalidValue;
-        } else if (k == 6144 && !relu && resid && !ln_w) {
-            e = valu ? gemv_batched_groups<float, 4, 1, EPI_RESID>(a, B, k, st) : gemv_mfma_groups<float, EPI_RESID>(am, B, k, SkPart{part.p, part.n}, st);
-        } else {
-            e = hipErrorInvalidValue;
-        }
-        hipError_t e2 = hipStreamSynchronize(st);
-        HIPRET(e);
-        HIPRET(e2);
-        return ER_OK;
+    const bool batched = B > 4;
+    if (batched && ln_w && k != 1536) return fail(ER_ERR_UNSUPPORTED, "er_k_gemv: LayerNorm prologue needs k=1536");
+    Proj proj = PROJ_FC2;
+    bool built = k == 6144 && !relu && resid && !ln_w;
+    if (k == 1536 && !(relu && resid)) {
+        proj = relu ? PROJ_FC1 : resid ? PROJ_OUT : PROJ_HEAD;
+        built = batched || (ln_w != nullptr) == (proj != PROJ_OUT);
     }
-    if (k == 1536) {
-        if (ln_w && relu && !resid) e = gemv_groups<float, 1, 2, PRO_LN, EPI_RELU>(a, B, k, st);
-        else if (ln_w && !relu && !resid) e = gemv_groups<float, 1, 1, PRO_LN, EPI_STORE>(a, B, k, st);
-        else if (!ln_w && !relu && resid) e = gemv_groups<float, 1, 1, PRO_NONE, EPI_RESID>(a, B, k, st);
-        else return fail(ER_ERR_UNSUPPORTED, "er_k_gemv: combination not instantiated for k=1536");
-    } else if (k == 6144) {
-        if (!ln_w && !relu && resid) e = gemv_groups<float, 4, 2, PRO_NONE, EPI_RESID>(a, B, k, st);
-        else return fail(ER_ERR_UNSUPPORTED, "er_k_gemv: combination not instantiated for k=6144");
-    } else {
-        return fail(ER_ERR_UNSUPPORTED, "er_k_gemv: k must be 1536 or 6144");
+    if (!built) {
+        if (batched) HIPRET(hipErrorInvalidValue);
+        if (k != 1536 && k != 6144) return fail(ER_ERR_UNSUPPORTED, "er_k_gemv: k must be 1536 or 6144");
+        return fail(ER_ERR_UNSUPPORTED, "er_k_gemv: combination not instantiated for k=%d", k);
     }
-    HIPRET(e);
+    const bool wide = proj == PROJ_FC1 || proj == PROJ_FC2;
+    ProjIo io;
+    io.pro = ln_w ? PRO_LN : PRO_NONE;
+    if (batched) {   // matrix cores for the fc1- and fc2-shaped cases unless ER_BATCHED_VALU=1, the VALU kernel for the narrow ones
+        const ProjForm f{wide && !env_is("ER_BATCHED_VALU", '1') ? ER_FORM_MFMA : ER_FORM_VALU, 0, 0, false};
+        return proj_entry<float>(proj, f, io, a, B, k, nullptr, st);
+    }
+    HIPRET(run_proj<float>(proj, ProjForm{ER_FORM_ROW, ER_NWAVES, wide ? 2 : 1, false}, io, a, B, k, SkPart{nullptr, 0}, st));
     return ER_OK;
 }
 
@@ -1791,27 +1591,25 @@ extern "C" int er_k_attn_stream_xt(const float* q, const void* k, const void* v,
     return ER_OK;
 }
 
-// ---- er_k_gemv_form: one decode projection in one of the forms launch_kind_t launches it in.  Every launch below names the `case` of
-// launch_kind_t it mirrors and uses that case's launcher and template arguments; what the step never launches is refused by
-// gemv_form_check before anything is allocated or launched.
-enum { GF_QKV = 0, GF_OUTPROJ = 3, GF_FC1 = 4, GF_FC2 = 5, GF_HEAD = 6, GF_PREP = 100 };     // launch_kind_t's kinds; GF_PREP: the prologue launch alone
-
-static int gemv_form_check(const er_k_gemv_form_args& f, int* proj_out) {
+// ---- er_k_gemv_form: one decode projection in one of the forms the decode step launches it in.  The entry goes through the step's own
+// launch table (run_proj / launch_proj) and takes "the step can launch this" from the step's own rule (proj_form_legal); what the step never
+// launches is refused by gemv_form_check before anything is allocated or launched.
+static int gemv_form_check(const er_k_gemv_form_args& f, Proj* proj_out) {
     const int B = f.batch, n = f.n, k = f.k, pro = f.prologue, epi = f.epilogue, form = f.form;
     const bool half = f.w_half != 0;
     if (B < 1 || B > ER_MAX_BATCH || n < 1) return fail(ER_ERR_INVALID, "er_k_gemv_form: batch %d, n %d", B, n);
     if (k != 1536 && k != 6144) return fail(ER_ERR_UNSUPPORTED, "er_k_gemv_form: k must be 1536 or 6144");
-    int proj;
-    if (form == ER_FORM_PREP) {
-        proj = GF_PREP;
+    Proj proj = PROJ_QKV;      // (unused by ER_FORM_PREP)
+    const bool prep = form == ER_FORM_PREP;
+    if (prep) {
         if (k != 1536 || pro == ER_PRO_NONE) return fail(ER_ERR_UNSUPPORTED, "er_k_gemv_form: the prologue launch is built for k=1536 and LN / EMBED");
         if (!f.xnorm_out) return fail(ER_ERR_INVALID, "er_k_gemv_form: ER_FORM_PREP needs xnorm_out");
     } else {
         if (!f.w) return fail(ER_ERR_INVALID, "er_k_gemv_form: null weights");
-        if (epi == ER_EPI_QKV && k == 1536 && pro != ER_PRO_NONE) proj = GF_QKV;
-        else if (epi == ER_EPI_RELU && k == 1536 && (pro == ER_PRO_LN || pro == ER_PRO_LN_SK)) proj = GF_FC1;
-        else if (epi == ER_EPI_RESID && pro == ER_PRO_NONE) proj = k == 1536 ? GF_OUTPROJ : GF_FC2;
-        else if (epi == ER_EPI_STORE && k == 1536 && pro == ER_PRO_LN) proj = GF_HEAD;
+        if (epi == ER_EPI_QKV && k == 1536 && pro != ER_PRO_NONE) proj = PROJ_QKV;
+        else if (epi == ER_EPI_RELU && k == 1536 && (pro == ER_PRO_LN || pro == ER_PRO_LN_SK)) proj = PROJ_FC1;
+        else if (epi == ER_EPI_RESID && pro == ER_PRO_NONE) proj = k == 1536 ? PROJ_OUT : PROJ_FC2;
+        else if (epi == ER_EPI_STORE && k == 1536 && pro == ER_PRO_LN) proj = PROJ_HEAD;
         else return fail(ER_ERR_UNSUPPORTED, "er_k_gemv_form: no decode projection has k=%d, prologue %d, epilogue %d", k, pro, epi);
     }
     // operands of the prologue and the epilogue
@@ -1820,185 +1618,52 @@ static int gemv_form_check(const er_k_gemv_form_args& f, int* proj_out) {
     if (pro == ER_PRO_EMBED && (!f.embd || !f.posemb || !f.tok || !f.pos)) return fail(ER_ERR_INVALID, "er_k_gemv_form: PRO_EMBED needs embd, posemb, tok, pos");
     if (pro == ER_PRO_LN_SK) {
         if (!f.sk_part || !f.sk_bias || !f.sk_resid || !f.ln_w || !f.ln_b) return fail(ER_ERR_INVALID, "er_k_gemv_form: PRO_LN_SK needs sk_part, sk_bias, sk_resid, ln_w, ln_b");
-        // only the tiled fast-mode path defers a finish: fc2's 16 partials to the next qkv (case 0), out_proj's 4 to fc1 (case 4)
+        // only the tiled fast-mode path defers a finish: fc2's 16 partials to the next layer's qkv, out_proj's 4 to fc1
         if (!half || form == ER_FORM_ROW || form == ER_FORM_ROWS8) return fail(ER_ERR_UNSUPPORTED, "er_k_gemv_form: a deferred finish is read by the fast-mode batched prologue only");
-        const int want = proj == GF_QKV ? SK_SLICES_FC2 : proj == GF_FC1 ? SK_SLICES_OUTPROJ : f.sk_slices;
+        const int want = prep ? f.sk_slices : proj == PROJ_QKV ? SK_SLICES_FC2 : proj == PROJ_FC1 ? SK_SLICES_OUTPROJ : f.sk_slices;
         if ((f.sk_slices != SK_SLICES_OUTPROJ && f.sk_slices != SK_SLICES_FC2) || f.sk_slices != want)
             return fail(ER_ERR_UNSUPPORTED, "er_k_gemv_form: sk_slices %d (qkv reads 16, fc1 reads 4)", f.sk_slices);
     }
-    if (proj == GF_QKV) {
+    if (!prep && proj == PROJ_QKV) {
         if (!f.q_out || !f.kcache || !f.vcache || !f.pos) return fail(ER_ERR_INVALID, "er_k_gemv_form: EPI_QKV needs q_out, kcache, vcache, pos");
         if (f.heads < 1 || f.head_dim < 1 || f.l_cap < 1 || f.heads * f.head_dim != k || n != 3 * k)
             return fail(ER_ERR_INVALID, "er_k_gemv_form: EPI_QKV needs heads * head_dim == k and n == 3 k");
-    } else if (proj != GF_PREP) {
-        if (!f.y && !(form == ER_FORM_MFMA_XT && proj == GF_FC1) && form != ER_FORM_NARROW_DEFER) return fail(ER_ERR_INVALID, "er_k_gemv_form: null y");
+    } else if (!prep) {
+        if (!f.y && !(form == ER_FORM_MFMA_XT && proj == PROJ_FC1) && form != ER_FORM_NARROW_DEFER) return fail(ER_ERR_INVALID, "er_k_gemv_form: null y");
         if (epi == ER_EPI_RESID && !f.resid && form != ER_FORM_NARROW_DEFER) return fail(ER_ERR_INVALID, "er_k_gemv_form: EPI_RESID needs resid");
     }
     if (f.prep_xt_out && !(half && pro != ER_PRO_NONE && (form == ER_FORM_MFMA_XT || form == ER_FORM_PREP)))
         return fail(ER_ERR_UNSUPPORTED, "er_k_gemv_form: prep_xt_out is written in front of the tiled fp16 forms only");
-    // the form
-    const bool batched_form = form != ER_FORM_ROW && form != ER_FORM_ROWS8;
-    if (batched_form && B <= 4) return fail(ER_ERR_UNSUPPORTED, "er_k_gemv_form: the batched forms run at batch > 4");
-    switch (form) {
-        case ER_FORM_ROW: {
-            if (B > 4) return fail(ER_ERR_UNSUPPORTED, "er_k_gemv_form: the row kernel runs at batch <= 4");
-            bool ok = false;
-            if (proj == GF_QKV) ok = (f.nw == 4 && f.rw == 1) || (f.nw == 6 && f.rw == 1) || (f.nw == 9 && f.rw == 2);      // read_knobs: ER_NW_QKV
-            if (proj == GF_FC1) ok = (f.nw == 4 || f.nw == 12) && f.rw == 2;                                                // ER_NW_FC1
-            if (proj == GF_OUTPROJ) ok = f.nw == 3 && f.rw == 1;
-            if (proj == GF_FC2) ok = f.nw == 4 && (f.rw == 2 || (half && B == 1 && (f.rw == 4 || f.rw == 6)));              // ER_RW_FC2
-            if (proj == GF_HEAD) ok = f.nw == 4 && f.rw == 1;
-            if (!ok) return fail(ER_ERR_UNSUPPORTED, "er_k_gemv_form: no row kernel of %d waves x %d rows for this projection, batch %d", f.nw, f.rw, B);
-            break;
-        }
-        case ER_FORM_ROWS8:
-            if (proj != GF_OUTPROJ || B < 5 || B > 8) return fail(ER_ERR_UNSUPPORTED, "er_k_gemv_form: rows8 is out_proj at batch 5..8");
-            break;
-        case ER_FORM_VALU:
-            break;
-        case ER_FORM_MFMA:
-            if (proj == GF_HEAD) return fail(ER_ERR_UNSUPPORTED, "er_k_gemv_form: the lm_head stays on the VALU kernel");
-            break;
-        case ER_FORM_MFMA_XT:
-            if (!half || (proj != GF_QKV && proj != GF_FC1)) return fail(ER_ERR_UNSUPPORTED, "er_k_gemv_form: wide tiled form: fp16 qkv and fc1");
-            if (proj == GF_FC1 && (!f.xt_out || n % 4)) return fail(ER_ERR_INVALID, "er_k_gemv_form: the tiled fc1 writes xt_out (n a multiple of 4)");
-            break;
-        case ER_FORM_NARROW:
-            if (!half || proj != GF_FC2) return fail(ER_ERR_UNSUPPORTED, "er_k_gemv_form: narrow + finish kernel: fp16 fc2 (the last layer's)");
-            break;
-        case ER_FORM_NARROW_DEFER:
-            if (!half || (proj != GF_OUTPROJ && proj != GF_FC2)) return fail(ER_ERR_UNSUPPORTED, "er_k_gemv_form: narrow deferred: fp16 out_proj and fc2");
-            if (!f.part_out) return fail(ER_ERR_INVALID, "er_k_gemv_form: ER_FORM_NARROW_DEFER needs part_out");
-            break;
-        case ER_FORM_PREP:
-            break;
-        default:
-            return fail(ER_ERR_INVALID, "er_k_gemv_form: form %d", form);
-    }
+    // the form: the step's rule, and the batched forms at batch > 4 only (the step reaches them below that under ER_FORCE_BATCHED=1)
+    if (form != ER_FORM_ROW && form != ER_FORM_ROWS8 && B <= 4) return fail(ER_ERR_UNSUPPORTED, "er_k_gemv_form: the batched forms run at batch > 4");
+    if (form < ER_FORM_ROW || form > ER_FORM_PREP) return fail(ER_ERR_INVALID, "er_k_gemv_form: form %d", form);
+    if (!prep && !proj_form_legal(proj, ProjForm{form, f.nw, f.rw, form == ER_FORM_NARROW_DEFER}, half, B))
+        return fail(ER_ERR_UNSUPPORTED, "er_k_gemv_form: the decode step never launches projection %d in form %d (%d waves x %d rows) with %s weights at batch %d",
+                    (int)proj, form, f.nw, f.rw, half ? "fp16" : "fp32", B);
+    if (form == ER_FORM_MFMA_XT && proj == PROJ_FC1 && (!f.xt_out || n % 4)) return fail(ER_ERR_INVALID, "er_k_gemv_form: the tiled fc1 writes xt_out (n a multiple of 4)");
+    if (form == ER_FORM_NARROW_DEFER && !f.part_out) return fail(ER_ERR_INVALID, "er_k_gemv_form: ER_FORM_NARROW_DEFER needs part_out");
     *proj_out = proj;
     return ER_OK;
 }
 
 template <typename WT>
-static int gemv_form_t(const er_k_gemv_form_args& f, int proj, hipStream_t st) {
-    constexpr bool HALF = sizeof(WT) == 2;
-    const int B = f.batch, n = f.n, k = f.k, form = f.form;
+static int gemv_form_t(const er_k_gemv_form_args& f, Proj proj, hipStream_t st) {
     GemvArgs a{};
-    a.W = f.w; a.bias = f.bias; a.N = n; a.xin = f.x; a.ln_w = f.ln_w; a.ln_b = f.ln_b; a.eps = f.eps; a.hout = f.xnorm_out;
+    a.W = f.w; a.bias = f.bias; a.N = f.n; a.xin = f.x; a.ln_w = f.ln_w; a.ln_b = f.ln_b; a.eps = f.eps; a.hout = f.xnorm_out;
     a.embd = f.embd; a.posemb = f.posemb; a.tok = f.tok; a.pos = f.pos;
     a.out = f.y; a.resid = f.resid; a.q = f.q_out; a.kcache = f.kcache; a.vcache = f.vcache; a.kv_half = f.kv_half ? 1 : 0;
-    a.hidden = proj == GF_QKV ? f.heads * f.head_dim : 1536; a.head_dim = f.head_dim; a.l_cap = f.l_cap;
+    a.hidden = f.form != ER_FORM_PREP && proj == PROJ_QKV ? f.heads * f.head_dim : 1536; a.head_dim = f.head_dim; a.l_cap = f.l_cap;
     a.kv_bstride = (long long)f.heads * f.l_cap * f.head_dim;
-    hipError_t e = hipErrorInvalidValue;
-    if (form == ER_FORM_ROW) {
-        switch (proj) {
-            case GF_QKV:        // case 0, B <= 4
-                e = f.prologue == ER_PRO_EMBED ? gemv_nw<WT, PRO_EMBED, EPI_QKV>(f.nw, a, B, k, st) : gemv_nw<WT, PRO_LN, EPI_QKV>(f.nw, a, B, k, st);
-                break;
-            case GF_OUTPROJ: e = gemv_groups<WT, 1, 1, PRO_NONE, EPI_RESID, 3>(a, B, k, st); break;      // case 3
-            case GF_FC1: e = gemv_nw<WT, PRO_LN, EPI_RELU>(f.nw, a, B, k, st); break;                     // case 4
-            case GF_FC2:        // case 5
-                if constexpr (HALF) {
-                    if (f.rw == 6) { e = launch_gemv<WT, 4, 1, 6, PRO_NONE, EPI_RESID>(a, st); break; }
-                    if (f.rw == 4) { e = launch_gemv<WT, 4, 1, 4, PRO_NONE, EPI_RESID>(a, st); break; }
-                }
-                e = gemv_groups<WT, 4, 2, PRO_NONE, EPI_RESID>(a, B, k, st);
-                break;
-            case GF_HEAD: e = gemv_groups<WT, 1, 1, PRO_LN, EPI_STORE>(a, B, k, st); break;               // case 6
-        }
-        hipError_t e2 = hipStreamSynchronize(st);
-        HIPRET(e);
-        HIPRET(e2);
-        return ER_OK;
-    }
-    if (form == ER_FORM_ROWS8) {    // case 3, outproj_rows8
-        e = gemv_outproj_rows8<WT>(a, B, st);
-        hipError_t e2 = hipStreamSynchronize(st);
-        HIPRET(e);
-        HIPRET(e2);
-        return ER_OK;
-    }
-    // ---- the batched forms: temporaries first, then the prologue launch, the tiled weight copy and the projection
-    const bool tiled_in = form == ER_FORM_MFMA_XT || form == ER_FORM_NARROW || form == ER_FORM_NARROW_DEFER;
-    const bool mfma = form == ER_FORM_MFMA || tiled_in;
-    const size_t groups = (size_t)(B + NBM - 1) / NBM;
-    const int slices = tiled_in && form != ER_FORM_MFMA_XT ? k / (4 * GM_KW) : k / (GM_WAVES * GM_KW);
-    DevBuf<float> tmp, part;
-    DevBuf<char> wt, img;
-    if (f.prologue != ER_PRO_NONE && !f.xnorm_out) ERCHK(tmp.ensure((size_t)B * k));
-    if (mfma) {
-        ERCHK(wt.ensure(tiled_weight_bytes<WT>(n, k)));
-        if (form != ER_FORM_NARROW_DEFER) ERCHK(part.ensure((size_t)slices * NBM * n));
-    }
-    void* image = f.prep_xt_out;
-    if (form == ER_FORM_MFMA_XT && !image) {      // er_kv_reserve: one zeroed image of k * 128 bytes per group of 32 rows
-        ERCHK(img.ensure(groups * (size_t)k * 128));
-        HIPCHK(hipMemsetAsync(img.p, 0, groups * (size_t)k * 128, st));
-        image = img.p;
-    }
-    e = hipSuccess;
-    if (f.prologue != ER_PRO_NONE) {      // cases 0, 4, 6: prep_rows in front of the projection
-        if (tmp.p) a.hout = tmp.p;
-        if constexpr (HALF) {
-            a.xt_out = image;
-            if (f.prologue == ER_PRO_LN_SK) { a.sk_part = f.sk_part; a.sk_bias = f.sk_bias; a.sk_resid = f.sk_resid; a.sk_batch = B; a.sk_slices = f.sk_slices; }
-        }
-        e = f.prologue == ER_PRO_EMBED ? prep_rows<PRO_EMBED>(a, B, st) : prep_rows<PRO_LN>(a, B, st);
-        a.sk_part = nullptr;
-        a.xin = a.hout;
-        a.xt_out = nullptr;
-    }
-    if (e == hipSuccess && mfma) {
-        hipLaunchKernelGGL((tile_weights_kernel<WT>), dim3(2048), dim3(ER_WG), 0, st, reinterpret_cast<const WT*>(f.w), reinterpret_cast<f32x4*>(wt.p), n, k);   // make_tiled
-        e = hipGetLastError();
-        a.W = wt.p;
-    }
-    const SkPart sk = form == ER_FORM_NARROW_DEFER ? SkPart{f.part_out, groups * slices * NBM * (size_t)n} : SkPart{part.p, part.n};
-    if (e == hipSuccess && form != ER_FORM_PREP) {
-        e = hipErrorInvalidValue;
-        switch (proj) {
-            case GF_QKV:        // case 0, batched
-                if (form == ER_FORM_VALU) e = gemv_batched_groups<WT, 1, 3, EPI_QKV>(a, B, k, st);
-                else if (form == ER_FORM_MFMA) e = gemv_mfma_groups<WT, EPI_QKV>(a, B, k, sk, st);
-                else if constexpr (HALF) {
-                    if (form == ER_FORM_MFMA_XT) { a.xin = (const float*)image; e = gemv_mfma_groups<WT, EPI_QKV, true>(a, B, k, sk, st); }
-                }
-                break;
-            case GF_OUTPROJ:    // case 3 (a pass of 5..8 rows in the narrow form is what the last group of a larger batch runs)
-                if (form == ER_FORM_VALU) e = gemv_batched_groups<WT, 1, 1, EPI_RESID>(a, B, k, st);
-                else if (form == ER_FORM_MFMA) e = gemv_mfma_groups<WT, EPI_RESID>(a, B, k, sk, st);
-                else if constexpr (HALF) {
-                    if (form == ER_FORM_NARROW_DEFER) e = gemv_mfma_groups<WT, EPI_RESID, true>(a, B, k, sk, st, true, true);
-                }
-                break;
-            case GF_FC1:        // case 4, batched
-                if (form == ER_FORM_VALU) e = gemv_batched_groups<WT, 1, 3, EPI_RELU>(a, B, k, st);
-                else if (form == ER_FORM_MFMA) e = gemv_mfma_groups<WT, EPI_RELU>(a, B, k, sk, st);
-                else if constexpr (HALF) {
-                    if (form == ER_FORM_MFMA_XT) { a.xin = (const float*)image; a.xt_out = f.xt_out; e = gemv_mfma_groups<WT, EPI_RELU, true>(a, B, k, sk, st); }
-                }
-                break;
-            case GF_FC2:        // case 5, batched
-                if (form == ER_FORM_VALU) e = gemv_batched_groups<WT, 4, 1, EPI_RESID>(a, B, k, st);
-                else if (form == ER_FORM_MFMA) e = gemv_mfma_groups<WT, EPI_RESID>(a, B, k, sk, st);
-                else if constexpr (HALF) {
-                    if (form == ER_FORM_NARROW || form == ER_FORM_NARROW_DEFER) e = gemv_mfma_groups<WT, EPI_RESID, true>(a, B, k, sk, st, form == ER_FORM_NARROW_DEFER, true);
-                }
-                break;
-            case GF_HEAD:       // case 6, batched
-                if (form == ER_FORM_VALU) e = gemv_batched_groups<WT, 1, 1, EPI_STORE>(a, B, k, st);
-                break;
-        }
-    }
-    hipError_t e2 = hipStreamSynchronize(st);
-    HIPRET(e);
-    HIPRET(e2);
-    return ER_OK;
+    ProjIo io;
+    io.pro = f.prologue == ER_PRO_NONE ? PRO_NONE : f.prologue == ER_PRO_EMBED ? PRO_EMBED : PRO_LN;
+    if (f.prologue == ER_PRO_LN_SK) io.rd = {f.sk_part, f.sk_bias, f.sk_resid, f.sk_slices};
+    io.pro_image = f.prep_xt_out; io.x_image = f.x; io.out_image = f.xt_out;      // the narrow forms' x IS the tiled image
+    return proj_entry<WT>(proj, ProjForm{f.form, f.nw, f.rw, f.form == ER_FORM_NARROW_DEFER}, io, a, f.batch, f.k, f.part_out, st);
 }
 
 extern "C" int er_k_gemv_form(const er_k_gemv_form_args* f, void* stream) {
     if (!f) return fail(ER_ERR_INVALID, "er_k_gemv_form: null args");
-    int proj = 0;
+    Proj proj = PROJ_QKV;
     ERCHK(gemv_form_check(*f, &proj));
     return f->w_half ? gemv_form_t<_Float16>(*f, proj, (hipStream_t)stream) : gemv_form_t<float>(*f, proj, (hipStream_t)stream);
 }

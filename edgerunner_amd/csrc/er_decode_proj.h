@@ -1,0 +1,223 @@
+// The launch table of the decode projections (qkv, out_proj, fc1, fc2, lm_head): the group loops over batch rows and launch_proj, the
+// ONLY function of the library that names a launcher with its template arguments for a decode projection.  The decode step
+// (launch_kind_t) and the two single-kernel entries (er_k_gemv, er_k_gemv_form) all get here through run_proj; which form a
+// projection takes is decided in csrc/er_decode_plan.h (proj_form), host-only.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "er_decode_plan.h"
+#include "k_gemv.h"
+#include "k_gemv_mfma.h"
+
+namespace er {
+
+constexpr int NBM = 32;   // batch rows per pass of the matrix-core decode projections (k_gemv_mfma.h)
+
+// a with every per-row pointer advanced to batch row row0 (K = width of an input row): what a pass of the three group loops below launches with.
+// The batched kernels read neither hout nor tok, and the tiled image of a group of 32 rows is K * 32 floats like its row-major form: one rule serves all.
+static GemvArgs gemv_args_at(const GemvArgs& a, int row0, int K) {
+    GemvArgs g = a;
+    if (g.xin) g.xin += (long long)row0 * K;
+    if (g.xt_out) g.xt_out = (char*)g.xt_out + (long long)row0 * a.N * 4;     // xt_entry() indexes inside a group
+    if (g.hout) g.hout += (long long)row0 * K;
+    if (g.tok) g.tok += row0;
+    if (g.pos) g.pos += row0;
+    if (g.out) g.out += (long long)row0 * a.N;
+    if (g.resid) g.resid += (long long)row0 * a.N;
+    if (g.q) g.q += (long long)row0 * a.hidden;
+    const long long kvb = (long long)row0 * a.kv_bstride * (a.kv_half ? 2 : 4);
+    if (g.kcache) g.kcache = (char*)g.kcache + kvb;
+    if (g.vcache) g.vcache = (char*)g.vcache + kvb;
+    return g;
+}
+
+template <typename WT, int KS, int RW, int PRO, int EPI, int NW = ER_NWAVES>
+static hipError_t gemv_groups(const GemvArgs& a, int B, int K, hipStream_t st) {
+    // rows are processed in groups of up to 4 (one weight stream, 1..4 accumulators per row)
+    int b = 0;
+    while (b < B) {
+        int nb = B - b;
+        nb = nb >= 4 ? 4 : nb;
+        const GemvArgs g = gemv_args_at(a, b, K);
+        hipError_t e;
+        if (nb == 4) e = launch_gemv<WT, KS, 4, RW, PRO, EPI, NW>(g, st);
+        else if (nb == 3) e = launch_gemv<WT, KS, 3, RW, PRO, EPI, NW>(g, st);
+        else if (nb == 2) e = launch_gemv<WT, KS, 2, RW, PRO, EPI, NW>(g, st);
+        else e = launch_gemv<WT, KS, 1, RW, PRO, EPI, NW>(g, st);
+        if (e != hipSuccess) return e;
+        b += nb;
+    }
+    return hipSuccess;
+}
+
+// single-row GEMV with a LayerNorm / embedding prologue by waves per workgroup: 4 or 6 waves x 1 row (qkv), 4 waves x 2 rows (fc1),
+// or ONE fat workgroup per CU - 9 waves x 2 rows = 4608 qkv rows / 256, 12 waves x 2 rows = 6144 fc1 rows / 256
+template <typename WT, int PRO, int EPI>
+static hipError_t gemv_nw(int nw, GemvArgs a, int B, int K, hipStream_t st) {
+    if (nw == 6) return gemv_groups<WT, 1, 1, PRO, EPI, 6>(a, B, K, st);
+    if (nw == 9) return gemv_groups<WT, 1, 2, PRO, EPI, 9>(a, B, K, st);
+    if (nw == 12) return gemv_groups<WT, 1, 2, PRO, EPI, 12>(a, B, K, st);
+    if (EPI == EPI_QKV) return gemv_groups<WT, 1, 1, PRO, EPI>(a, B, K, st);
+    return gemv_groups<WT, 1, 2, PRO, EPI>(a, B, K, st);
+}
+
+// out_proj of 5..8 rows: ONE pass of the VALU kernel with 5..8 accumulators per weight row.  The matrix-core kernel has only 48
+// row tiles for this 1536-row matrix (48 of 256 CUs: 9.3 us at B = 5 against 4.9 us for the four-row VALU launch), which left the
+// aggregate rate of five rows below that of four (profiles/r03_batch_table_v2.log); same per-(row, batch row) arithmetic as every
+// other path.
+template <typename WT>
+static hipError_t gemv_outproj_rows8(const GemvArgs& a, int B, hipStream_t st) {
+    switch (B) {
+        case 5: return launch_gemv<WT, 1, 5, 1, PRO_NONE, EPI_RESID, 3>(a, st);
+        case 6: return launch_gemv<WT, 1, 6, 1, PRO_NONE, EPI_RESID, 3>(a, st);
+        case 7: return launch_gemv<WT, 1, 7, 1, PRO_NONE, EPI_RESID, 3>(a, st);
+        case 8: return launch_gemv<WT, 1, 8, 1, PRO_NONE, EPI_RESID, 3>(a, st);
+    }
+    return hipErrorInvalidValue;
+}
+
+// B > 4: weights streamed once per pass of up to 16 rows (gemv_batched_kernel)
+constexpr int NBB = 16;
+template <typename WT, int PH, int RW, int EPI>
+static hipError_t gemv_batched_groups(const GemvArgs& a, int B, int K, hipStream_t st) {
+    for (int b = 0; b < B; b += NBB) {
+        const int nb = (B - b) < NBB ? (B - b) : NBB;
+        hipError_t e = launch_gemv_batched<WT, PH, NBB, RW, EPI>(gemv_args_at(a, b, K), nb, st);
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+// XT: a.xin is the tiled image of the input (a group of 32 rows is K * 32 floats there as well, so the group offsets coincide)
+struct SkPart { float* p; size_t floats; };       // the context's split-K partial block and its size
+template <typename WT, int EPI, bool XT = false>
+static hipError_t gemv_mfma_groups(const GemvArgs& a, int B, int K, SkPart part, hipStream_t st, bool defer_finish = false, bool narrow = false) {
+    const int slices = narrow ? K / (4 * GM_KW) : K / (GM_WAVES * GM_KW);
+    {   // the block was sized in er_kv_reserve for K <= 6144 (4 wide / 16 narrow slices) and, when the finish is not deferred, for ONE
+        // group at a time on an in-order stream: refuse anything that would overrun it instead of writing past the end
+        const size_t groups = (size_t)(B + NBM - 1) / NBM;
+        const size_t need = (defer_finish ? groups : 1) * slices * NBM * (size_t)a.N;
+        if (!part.p || need > part.floats) return hipErrorInvalidValue;
+    }
+    for (int b = 0; b < B; b += NBM) {
+        const int nb = (B - b) < NBM ? (B - b) : NBM;
+        // deferred: every group keeps its own partial block (prep_rows_kernel: g * 4 * 32 * K floats)
+        hipError_t e = launch_gemv_mfma<WT, EPI, XT>(gemv_args_at(a, b, K), nb, K, defer_finish ? part.p + (long long)(b / NBM) * slices * NBM * a.N : part.p, st, defer_finish, narrow);
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+template <int PRO>
+static hipError_t prep_rows(const GemvArgs& a, int B, hipStream_t st) {
+    hipLaunchKernelGGL((prep_rows_kernel<PRO>), dim3(B), dim3(ER_WG), 0, st, a);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------ the launch table
+// Projection `proj` in form `f` on the operands `a` (K = width of an input row).  The caller has pointed a.W at the tiled copy for the
+// matrix-core forms and a.xin at the tiled image for the tiled-input forms, and has run the batched forms' prologue (run_proj does all
+// three); pro names the prologue FUSED into the qkv row kernel (PRO_LN, or PRO_EMBED for layer 0; fc1 and lm_head always fuse PRO_LN).
+// Shapes: qkv 4608 rows = 192 VALU workgroups x 24 (one round) or 144 matrix-core tiles of 32; fc1 6144 rows = 256 x 24 or 192 tiles;
+// fc2 48 tiles x 4 (narrow: 16) K-ranges.  The XT kernels exist for fp16 weights only: their forms are compiled out for float.
+template <typename WT>
+static hipError_t launch_proj(Proj proj, const ProjForm& f, int pro, const GemvArgs& a, int B, int K, SkPart sk, hipStream_t st) {
+    constexpr bool HALF = sizeof(WT) == 2;
+    switch (f.form) {
+        case ER_FORM_ROW:
+            switch (proj) {
+                case PROJ_QKV:
+                    if (pro == PRO_EMBED) return gemv_nw<WT, PRO_EMBED, EPI_QKV>(f.nw, a, B, K, st);
+                    return gemv_nw<WT, PRO_LN, EPI_QKV>(f.nw, a, B, K, st);
+                case PROJ_OUT:
+                    if (f.nw == 3) return gemv_groups<WT, 1, 1, PRO_NONE, EPI_RESID, 3>(a, B, K, st);      // the step
+                    if constexpr (!HALF) {
+                        if (f.nw == ER_NWAVES) return gemv_groups<WT, 1, 1, PRO_NONE, EPI_RESID>(a, B, K, st);   // er_k_gemv (the prefill tail runs the same kernel: linear_tail)
+                    }
+                    break;
+                case PROJ_FC1: return gemv_nw<WT, PRO_LN, EPI_RELU>(f.nw, a, B, K, st);
+                case PROJ_FC2:
+                    if constexpr (HALF) {
+                        if (f.rw == 6 || f.rw == 4) {
+                            if (B != 1) break;
+                            return f.rw == 6 ? launch_gemv<WT, 4, 1, 6, PRO_NONE, EPI_RESID>(a, st) : launch_gemv<WT, 4, 1, 4, PRO_NONE, EPI_RESID>(a, st);
+                        }
+                    }
+                    return gemv_groups<WT, 4, 2, PRO_NONE, EPI_RESID>(a, B, K, st);
+                case PROJ_HEAD: return gemv_groups<WT, 1, 1, PRO_LN, EPI_STORE>(a, B, K, st);
+            }
+            break;
+        case ER_FORM_ROWS8:
+            if (proj == PROJ_OUT) return gemv_outproj_rows8<WT>(a, B, st);
+            break;
+        case ER_FORM_VALU:
+            switch (proj) {
+                case PROJ_QKV: return gemv_batched_groups<WT, 1, 3, EPI_QKV>(a, B, K, st);
+                case PROJ_OUT: return gemv_batched_groups<WT, 1, 1, EPI_RESID>(a, B, K, st);
+                case PROJ_FC1: return gemv_batched_groups<WT, 1, 3, EPI_RELU>(a, B, K, st);
+                case PROJ_FC2: return gemv_batched_groups<WT, 4, 1, EPI_RESID>(a, B, K, st);
+                case PROJ_HEAD: return gemv_batched_groups<WT, 1, 1, EPI_STORE>(a, B, K, st);
+            }
+            break;
+        case ER_FORM_MFMA:
+            switch (proj) {
+                case PROJ_QKV: return gemv_mfma_groups<WT, EPI_QKV>(a, B, K, sk, st);
+                case PROJ_FC1: return gemv_mfma_groups<WT, EPI_RELU>(a, B, K, sk, st);
+                case PROJ_OUT:
+                case PROJ_FC2: return gemv_mfma_groups<WT, EPI_RESID>(a, B, K, sk, st);
+                case PROJ_HEAD: break;
+            }
+            break;
+        case ER_FORM_MFMA_XT:
+            if constexpr (HALF) {
+                if (proj == PROJ_QKV) return gemv_mfma_groups<WT, EPI_QKV, true>(a, B, K, sk, st);
+                if (proj == PROJ_FC1) return gemv_mfma_groups<WT, EPI_RELU, true>(a, B, K, sk, st);      // writes a.xt_out, the image fc2 reads
+            }
+            break;
+        case ER_FORM_NARROW:
+        case ER_FORM_NARROW_DEFER:
+            if constexpr (HALF) {
+                if (proj == PROJ_FC2 || (proj == PROJ_OUT && f.defer)) return gemv_mfma_groups<WT, EPI_RESID, true>(a, B, K, sk, st, f.defer, true);
+            }
+            break;
+    }
+    return hipErrorInvalidValue;
+}
+
+// A split-K finish that the previous producer deferred to this prologue launch: rows = ((p_0 + .. + p_{slices-1}) + bias) + resid.
+struct SkRead { const float* part = nullptr; const float* bias = nullptr; const float* resid = nullptr; int slices = 0; };
+
+// The batched forms' prologue: LayerNorm (or token + position embedding) of B rows into a.hout by its own launch, optionally of the
+// rows a deferred split-K finish yields (rd.part) and optionally also into the tiled image `image`; the projection then reads a.hout.
+static hipError_t launch_prologue(int pro, GemvArgs& a, int B, const SkRead& rd, void* image, hipStream_t st) {
+    a.xt_out = image;
+    if (rd.part) { a.sk_part = rd.part; a.sk_bias = rd.bias; a.sk_resid = rd.resid; a.sk_batch = B; a.sk_slices = rd.slices; }
+    const hipError_t e = pro == PRO_EMBED ? prep_rows<PRO_EMBED>(a, B, st) : prep_rows<PRO_LN>(a, B, st);
+    a.xin = a.hout;
+    a.xt_out = nullptr;
+    a.sk_part = nullptr;
+    return e;
+}
+
+// What a projection launches with beside the GemvArgs of its row-major form (`a` of run_proj: plain weights, row-major input)
+struct ProjIo {
+    int pro = PRO_NONE;               // PRO_LN / PRO_EMBED: fused into the row kernels, launch_prologue in front of the batched forms
+    SkRead rd;                        // ... which then also finishes the previous producer's partials
+    void* pro_image = nullptr;        // ... and writes the tiled image of its rows
+    const void* w_tiled = nullptr;    // the weights as the matrix-core forms stream them (tile_weights_kernel)
+    const void* x_image = nullptr;    // the input as the tiled-input forms read it
+    void* out_image = nullptr;        // fc1, ER_FORM_MFMA_XT: the tiled image of the output
+};
+
+// (projection, form) -> launches: the prologue launch of a batched form, the operands the form reads, launch_proj.
+template <typename WT>
+static hipError_t run_proj(Proj proj, const ProjForm& f, const ProjIo& io, GemvArgs a, int B, int K, SkPart sk, hipStream_t st) {
+    if (io.pro != PRO_NONE && form_batched(f.form)) {
+        const hipError_t e = launch_prologue(io.pro, a, B, io.rd, io.pro_image, st);
+        if (e != hipSuccess) return e;
+    }
+    if (form_mfma(f.form)) a.W = io.w_tiled;
+    if (form_tiled_in(f.form)) a.xin = (const float*)io.x_image;
+    if (f.form == ER_FORM_MFMA_XT && proj == PROJ_FC1) a.xt_out = io.out_image;
+    return launch_proj<WT>(proj, f, io.pro, a, B, K, sk, st);
+}
+
+}   // namespace er

@@ -357,9 +357,10 @@ int er_k_attn_decode(const float* q_dev, const void* k_dev, const void* v_dev, c
                      int variant, void* stream);
 /* ONE decode projection in ONE of the forms the decode step launches it in (er_k_gemv reaches the fp32-weight, 4-wave forms only).
  * The projection is named by (k, prologue, epilogue): qkv = 1536 / LN or EMBED / QKV (n = 3 * heads * head_dim, k = heads * head_dim),
- * out_proj = 1536 / NONE / RESID, fc1 = 1536 / LN / RELU, fc2 = 6144 / NONE / RESID, lm_head = 1536 / LN / STORE; the entry launches
- * it through the same launchers, with the same template arguments, as the decode step, and refuses every (projection, form, batch,
- * weight type) the step never launches with ER_ERR_UNSUPPORTED before anything is launched.  Blocks until the work is complete. */
+ * out_proj = 1536 / NONE / RESID, fc1 = 1536 / LN / RELU, fc2 = 6144 / NONE / RESID, lm_head = 1536 / LN / STORE; the entry runs
+ * the decode step's own launch table (one function maps (projection, form) to launches for the step and for this entry) and refuses
+ * every (projection, form, batch, weight type) the step's own rule does not allow - and every batched form at batch <= 4 - with
+ * ER_ERR_UNSUPPORTED before anything is launched.  Blocks until the work is complete. */
 typedef enum { ER_PRO_NONE = 0, ER_PRO_LN = 1, ER_PRO_EMBED = 2,
                ER_PRO_LN_SK = 3      /* LayerNorm of ((p_0 + .. + p_{S-1}) + sk_bias) + sk_resid: a deferred split-K finish (batched forms) */
 } er_gemv_prologue;

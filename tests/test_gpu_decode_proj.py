@@ -1,5 +1,7 @@
-"""The fast-mode decode projections form by form, through ``er_k_gemv_form`` (the same launchers and template arguments as the decode
-step's launch_kind_t), against float64 torch on the device and against each other where the kernels promise equal bits.
+"""The fast-mode decode projections form by form, through ``er_k_gemv_form``: the entry runs the decode step's own launch table
+(run_proj / launch_proj, csrc/er_decode_proj.h) and refuses what the step's own rule (proj_form_legal, csrc/er_decode_plan.h) does not
+allow, so a test here runs the launch the step runs.  Against float64 torch on the device, and against each other where the kernels
+promise equal bits.
 
 Inputs as in test_gpu_kernels.py: seeded CPU generator, weights at scale 0.02, pre-LayerNorm rows randn * 2 + 0.3, relu(randn)
 in front of fc2.  fp16 weights are ``w.half()`` and the reference multiplies the stored values ``w.half().double()``.  One set of
@@ -11,28 +13,54 @@ slack[b, n] = sum_k |w[n, k]| |x[b, k] - (hi + lo)[b, k]| with hi / lo from kern
 reference side (for a LayerNorm'd input: the float64 LayerNorm rounded to float32) - the exact representation error of the split,
 independent of the code under test.  Every accuracy check prints its largest error and largest slack.
 
-launch_kind_t branch -> test (er_api.hip; every form runs with fp16 weights, rows8 also with fp32):
-  case 0 qkv   gemv_nw<PRO_LN | PRO_EMBED, EPI_QKV>, 4 / 6 / 9 waves   test_qkv_row_kernel, test_row_kernels_of_different_widths_give_equal_bits,
-                                                                      test_qkv_epilogue_writes_exactly_one_key_row[row-*], test_embed_prologue_fused_row_kernel
-               prep_rows<PRO_EMBED> (+ image)                          test_embed_prologue_prep_rows_and_its_image
-               prep_rows<PRO_LN> (+ image)                             test_batched_forms[qkv-* / fc1-* / head-valu], test_wide_form_on_tiled_input_equals_row_major
-               prep_rows<PRO_LN> reading 16 deferred slices            test_deferred_finish_equals_finish_then_layernorm[fc2-16-*]
-               wide XT / wide / VALU <1, 3, EPI_QKV>                   test_batched_forms[qkv-xt / qkv-mfma / qkv-valu], ...exactly_one_key_row[xt / mfma / valu]
-  case 1 attn  attn_stream_kernel with out_xt                          test_attn_stream_writes_tiled_image
-  case 3 out   gemv_outproj_rows8 NB = 5..8                            test_out_proj_rows8
-               narrow, 4 slices, deferred                              test_batched_forms[out-defer], test_deferred_finish...[out-4-*]
-               wide / VALU <1, 1, EPI_RESID> / 3-wave row kernel        test_batched_forms[out-mfma / out-valu], test_out_proj_three_wave_row_kernel
-  case 4 fc1   prep_rows<PRO_LN> reading 4 deferred slices             test_deferred_finish...[out-4-*]
-               wide XT writing the next image (DPP quad permute)       test_batched_forms[fc1-xt], test_wide_form_on_tiled_input_equals_row_major
-               wide / VALU <1, 3, EPI_RELU> / gemv_nw 4 and 12 waves   test_batched_forms[fc1-mfma / fc1-valu], test_fc1_row_kernel
-  case 5 fc2   narrow, 16 slices, deferred / splitk_finish S = 16      test_batched_forms[fc2-defer / fc2-narrow], test_deferred_finish...[fc2-16-*]
-               wide + splitk_finish S = 4 / VALU <4, 1, EPI_RESID>     test_batched_forms[fc2-mfma / fc2-valu]
-               RW = 2 / 4 / 6 row kernel                               test_fc2_row_kernel, test_row_kernels_of_different_widths_give_equal_bits
-  case 6 head  prep_rows + VALU <1, 1, EPI_STORE> / row kernel         test_lm_head_ragged_rows, test_batched_forms[head-valu]
-  every batched form                                                   test_batched_row_independent_of_neighbours, test_valu_batch_rows_equal_single_row_kernel
+(projection, form) -> test.  One line per form proj_form returns and launch_proj launches; waves x rows and weight types are the ones
+tests/host/decode_plan_check.cpp reaches (tests/test_decode_plan_cpu.py holds every reached tuple against this table).  fp16 lines are
+tested here; fp32 lines name the test that runs the form, or say that none does.
+  qkv  row     4x1,6x1,9x2  fp16  gemv_nw<PRO_LN | PRO_EMBED, EPI_QKV>          test_qkv_row_kernel, test_row_kernels_of_different_widths_give_equal_bits,
+                                                                                test_qkv_epilogue_writes_exactly_one_key_row[row-*], test_embed_prologue_fused_row_kernel
+  qkv  row     4x1,6x1      fp32  the same                                      test_gpu_parity.py: exact mode runs 6x1, test_decode_v2_and_4wave_qkv_small 4x1
+  qkv  row     9x2          fp32  the same                                      no test (ER_NW_QKV=9 in exact mode)
+  qkv  valu    -            fp16  prologue launch, VALU <1, 3, EPI_QKV>         test_batched_forms[qkv-valu], ...exactly_one_key_row[valu], test_valu_batch_rows_equal_single_row_kernel
+  qkv  mfma    -            fp16  prologue launch, wide                         test_batched_forms[qkv-mfma], ...exactly_one_key_row[mfma]
+  qkv  xt      -            fp16  prologue launch + image, wide XT              test_batched_forms[qkv-xt], ...exactly_one_key_row[xt], test_wide_form_on_tiled_input_equals_row_major,
+                                                                                test_embed_prologue_prep_rows_and_its_image; 16 deferred slices: test_deferred_finish...[fc2-16-*]
+  qkv  valu    -            fp32  as fp16                                       test_qkv_valu_fp32_weights
+  qkv  mfma    -            fp32  as fp16                                       test_gpu_parity.py test_batched_kernels_teacher_forced_logits_24_layers[fp32]
+  out  row     3x1          fp16  gemv_groups<1, 1, PRO_NONE, EPI_RESID, 3>     test_out_proj_three_wave_row_kernel
+  out  row     3x1          fp32  the same                                      test_gpu_parity.py test_decode_v2_and_4wave_qkv_small[ER_DECODE_V=2] (version 3 fuses out_proj into the merge)
+  out  rows8   3x1          fp16  gemv_outproj_rows8 NB = 5..8                  test_out_proj_rows8[*-False]
+  out  rows8   3x1          fp32  the same                                      test_out_proj_rows8[*-True]
+  out  valu    -            fp16  VALU <1, 1, EPI_RESID>                        test_batched_forms[out-valu]
+  out  mfma    -            fp16  wide                                          test_batched_forms[out-mfma]
+  out  defer   -            fp16  narrow, 4 slices, deferred                    test_batched_forms[out-defer], test_deferred_finish...[out-4-*]
+  out  valu    -            fp32  as fp16                                       test_gpu_kernels.py test_gemv_batched_matrix_core_rows, test_gemv_batched_valu_rows_bit_identical_to_single
+  out  mfma    -            fp32  as fp16                                       test_gpu_parity.py test_batched_kernels_teacher_forced_logits_24_layers[fp32]
+  fc1  row     4x2,12x2     fp16  gemv_nw<PRO_LN, EPI_RELU>                     test_fc1_row_kernel, test_row_kernels_of_different_widths_give_equal_bits
+  fc1  row     4x2          fp32  the same                                      test_gpu_kernels.py test_gemv_fc1_ln_relu
+  fc1  row     12x2         fp32  the same                                      no test (ER_NW_FC1=12 in exact mode)
+  fc1  valu    -            fp16  prologue launch, VALU <1, 3, EPI_RELU>        test_batched_forms[fc1-valu]
+  fc1  mfma    -            fp16  prologue launch, wide                         test_batched_forms[fc1-mfma]
+  fc1  xt      -            fp16  prologue launch + image, wide XT writing the  test_batched_forms[fc1-xt], test_wide_form_on_tiled_input_equals_row_major;
+                                  next image (DPP quad permute)                 4 deferred slices: test_deferred_finish...[out-4-*]
+  fc1  valu    -            fp32  as fp16                                       test_gpu_kernels.py test_gemv_batched_valu_rows_bit_identical_to_single
+  fc1  mfma    -            fp32  as fp16                                       test_gpu_kernels.py test_gemv_batched_matrix_core_rows
+  fc2  row     4x2,4x4,4x6  fp16  gemv_groups<4, 2> / launch_gemv<4, 1, 4 | 6>  test_fc2_row_kernel, test_row_kernels_of_different_widths_give_equal_bits
+  fc2  row     4x2          fp32  gemv_groups<4, 2, PRO_NONE, EPI_RESID>        test_gpu_kernels.py test_gemv_fc2_ksplit_resid
+  fc2  valu    -            fp16  VALU <4, 1, EPI_RESID>                        test_batched_forms[fc2-valu]
+  fc2  mfma    -            fp16  wide + splitk_finish S = 4                    test_batched_forms[fc2-mfma]
+  fc2  narrow  -            fp16  narrow + splitk_finish S = 16                 test_batched_forms[fc2-narrow], test_deferred_finish...[fc2-16-*]
+  fc2  defer   -            fp16  narrow, 16 slices, deferred                   test_batched_forms[fc2-defer], test_deferred_finish...[fc2-16-*]
+  fc2  valu    -            fp32  as fp16                                       test_gpu_kernels.py test_gemv_batched_valu_rows_bit_identical_to_single
+  fc2  mfma    -            fp32  as fp16                                       test_gpu_kernels.py test_gemv_batched_matrix_core_rows
+  head row     4x1          fp16  gemv_groups<1, 1, PRO_LN, EPI_STORE>          test_lm_head_ragged_rows[1-row / 4-row]
+  head row     4x1          fp32  the same                                      test_gpu_kernels.py test_gemv_head_ln_store_ragged_rows
+  head valu    -            fp16  prologue launch, VALU <1, 1, EPI_STORE>       test_lm_head_ragged_rows[5-valu / 19-valu], test_batched_forms[head-valu]
+  head valu    -            fp32  as fp16                                       test_gpu_kernels.py test_gemv_batched_matrix_core_rows
+every batched form: test_batched_row_independent_of_neighbours, test_valu_batch_rows_equal_single_row_kernel.  The streaming attention
+that writes out_proj's image (launch_kind_t case 1, attn_stream_kernel with out_xt): test_attn_stream_writes_tiled_image.
 Not reachable through the entry because the decode step never launches them: splitk_finish_kernel<EPI_QKV> (the qkv matrix has one
 K-range of 1536, so no split precedes its epilogue) and splitk_finish_kernel behind the narrow out_proj (always deferred).  The balanced
-single-row attention + merged out_proj (case 3, v3) has its own entry and tests in test_gpu_kernels.py.
+single-row attention + merged out_proj (launch_kind_t case 3, v3: no GEMV form) has its own entry and tests in test_gpu_kernels.py.
 
 Largest error / largest slack seen on an MI355X (B = 40 unless noted; bounds 2e-6 resp. 4e-6 + 1e-5 |ref| + slack): row kernels 4.5e-7
 (fc1), 5.6e-7 (fc2 rw = 6), rows8 5.5e-7 (fp32) / 4.3e-7 (fp16); VALU qkv 5.9e-7, fc1 6.1e-7, out 5.3e-7, fc2 7.0e-7, head 4.7e-7;
@@ -281,6 +309,12 @@ def test_batched_forms(name, form, B):
                 assert not hi[B:].any() and not lo[B:].any(), "image rows >= B written"
 
 
+@pytest.mark.parametrize("B", [5, 19])
+def test_qkv_valu_fp32_weights(B):
+    """The one fp32-weight form no other test launches: er_k_gemv has no QKV epilogue, and no whole-step test reserves with ER_BATCHED_VALU=1."""
+    accuracy("qkv", "valu", B, w32=True)
+
+
 # ------------------------------------------------------------------ B. stated bit identities
 @pytest.mark.parametrize("B", [5, 17, 40])
 def test_wide_form_on_tiled_input_equals_row_major(B):
@@ -403,7 +437,7 @@ def test_embed_prologue_prep_rows_and_its_image(B):
     assert torch.equal(o["prep_xt"], K.xt_pack_image(o["xnorm"])), "image != xt_pack(hout), or a row >= B was written"
     hi, lo = K.xt_unpack_image(o["prep_xt"])
     assert not hi[B:].any() and not lo[B:].any()
-    accuracy("qkv", "xt", B, pro="embed")      # the same launch in front of the projection (case 0, layer 0)
+    accuracy("qkv", "xt", B, pro="embed")      # the same launch in front of the projection (qkv, layer 0)
     # the LayerNorm prologue writes its image the same way
     o = K.gemv_form(nat.ER_FORM_PREP, 0, None, B, x=d.x[:B].contiguous(), ln=(d.lw, d.lb), n=HID, k=HID, w_half=True, prep_xt=True)
     assert torch.equal(o["prep_xt"], K.xt_pack_image(o["xnorm"]))
