@@ -36,6 +36,7 @@
 #include "er_queue_host.h"
 #include "er_decode_plan.h"
 #include "er_decode_proj.h"
+#include "k_mlp_sparse.h"
 
 using namespace er;
 
@@ -68,6 +69,7 @@ struct LayerW {
     // fp16-rounded values (used by the prefill GEMMs), so prefill and decode see one model
     _Float16 *wqkv_h = nullptr, *wo_h = nullptr, *w1_h = nullptr, *w2_h = nullptr;
     void *wqkv_t = nullptr, *wo_t = nullptr, *w1_t = nullptr, *w2_t = nullptr;   // tiled copies for the matrix-core batched kernels (k_gemv_mfma.h)
+    void* w2_kt = nullptr;   // fc2.weight k-major, [intermediate][hidden] in the streamed weight type: the fused single-row MLP (k_mlp_sparse.h)
     float *wqkv = nullptr, *bqkv = nullptr;   // fused [3*hidden][hidden] in q,k,v order
     float *wo = nullptr, *bo = nullptr, *ln1w = nullptr, *ln1b = nullptr;
     float *w1 = nullptr, *b1 = nullptr, *w2 = nullptr, *b2 = nullptr, *ln2w = nullptr, *ln2b = nullptr;
@@ -115,6 +117,8 @@ struct KvMem {
     DevBuf<char> kc, vc;          // KV cache [layers][B][H][Lcap][D], fp32 or fp16 (fast)
     DevBuf<float> ypre, hbuf, ypre1, h1buf, qbuf, abuf, fbuf, logits;   // decode workspace ([B][...])
     DevBuf<float> part, part_ml;  // attention partials; version 3: {m, l} of the partials
+    DevBuf<float> mlp_part;       // fused single-row MLP: the 256 chain vectors of one layer ([256][hidden]), rewritten by every launch
+    DevBuf<int> mlp_nnz;          // ... and the live neurons per (layer, workgroup) of the last step ([layers][256])
     DevBuf<float> skpart;         // split-K partials of the batched projections (gemv_mfma_groups checks launches against skpart.n)
     // fast-mode batches on the matrix cores: activations in the tiled hi | lo operand layout (k_gemv.h xt_entry), one image per producer
     DevBuf<char> xt_h, xt_att, xt_f;     // LayerNorm rows (qkv / fc1 input), attention output, fc1 output
@@ -152,6 +156,8 @@ struct er_ctx {
     bool have_hidden = false;     // ypre holds a valid last-position state
     DecodeKnobs knobs;        // environment of er_create
     bool tiled_valid = false; // LayerW::*_t match the loaded weights
+    bool kmajor_valid = false; // LayerW::w2_kt match the loaded weights
+    void* zero_row = nullptr;  // hidden zeros (fp32 size): what the fused MLP reads in place of a dead neuron's row
     int prof_len = 0;         // > 0: attention kernels run at this fixed length (er_profile_decode_kernels_at)
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     float last_decode_ms = 0.f;
@@ -191,6 +197,10 @@ static DecodeKnobs read_knobs(bool fast) {
     const char* rw = getenv("ER_RW_FC2");
     k.rw_fc2 = rw ? atoi(rw) : 6;
     if (fast && k.rw_fc2 != 2 && k.rw_fc2 != 4 && k.rw_fc2 != 6) fprintf(stderr, "[edgerunner_hip] ER_RW_FC2=%s is not 2 / 4 / 6: using 2 rows per fc2 workgroup\n", rw);
+    // exact mode: on (1076 -> 1102 tok/s, profiles/mlp_sparse_bench.log); fast mode: off - fewer bytes per neuron row, and the pair
+    // of launches lost its A/B (1542 -> 1501 tok/s decode, profiles/mlp_sparse_ab_decode.log)
+    k.mlp_v = env_int("ER_MLP_V", fast ? 0 : 1);
+    if (k.mlp_v != 1) k.mlp_v = 0;
     return k;
 }
 
@@ -320,7 +330,7 @@ extern "C" int er_load_tensor(er_ctx* c, const char* key, const void* data, int 
     if (!c || !key) return fail(ER_ERR_INVALID, "er_load_tensor: bad argument");
     HIPCHK(hipSetDevice(c->device));
     const int rc = weights_load(c->w, c->own_stream, "er_load_tensor", key, data, dtype, ndim, shape, on_device);
-    if (rc != 1) c->tiled_valid = false;  // any reload invalidates the tiled copies of the batched path
+    if (rc != 1) c->tiled_valid = c->kmajor_valid = false;  // any reload invalidates the tiled copies of the batched path and the k-major fc2 copies
     return rc;
 }
 
@@ -361,6 +371,29 @@ static int make_tiled_weights(er_ctx* c) {
     }
     HIPCHK(hipStreamSynchronize(c->own_stream));
     c->tiled_valid = true;
+    return 0;
+}
+
+// k-major copy of every fc2.weight and the zero row, made the first time a shape is reserved whose plan runs the fused single-row
+// MLP (0.9 GB fp32 / 0.45 GB fp16 at 24 layers: batch-only contexts never pay them); owned by the weight table like the tiled copies
+static int make_kmajor_weights(er_ctx* c) {
+    if (c->kmajor_valid || weights_missing(c->w)) return 0;   // weights still loading: er_prefill comes back here
+    const size_t H = c->cfg.hidden_dim, I = c->cfg.intermediate_dim, esz = c->fast ? 2 : 4;
+    if (!c->zero_row) {
+        char* z = nullptr;
+        ERCHK(weights_alloc(c->w, &z, H * 4));
+        c->zero_row = z;
+    }
+    for (LayerW& L : c->layers) {
+        if (!L.w2_kt) {
+            char* blk = nullptr;
+            ERCHK(c->w.alloc(&blk, I * H * esz));
+            L.w2_kt = blk;
+        }
+        HIPCHK(c->fast ? launch_transpose_w2<_Float16>(L.w2_h, L.w2_kt, c->own_stream) : launch_transpose_w2<float>(L.w2, L.w2_kt, c->own_stream));
+    }
+    HIPCHK(hipStreamSynchronize(c->own_stream));
+    c->kmajor_valid = true;
     return 0;
 }
 
@@ -448,6 +481,12 @@ static int kv_alloc(er_ctx* c, KvMem& m, int batch, int Lcap) {
     m.st.row_budget = m.d_row_budget.p;
     ERCHK(m.d_out_ids.ensure(b * (size_t)Lcap));
     if (p.mfma) ERCHK(make_tiled_weights(c));
+    if (p.mlp_fused) {
+        ERCHK(make_kmajor_weights(c));
+        ERCHK(m.mlp_part.ensure((size_t)MLP_WGS * hid));
+        ERCHK(m.mlp_nnz.ensure((size_t)g.num_layers * MLP_WGS));
+        HIPCHK(hipMemset(m.mlp_nnz.p, 0, m.mlp_nnz.n * sizeof(int)));
+    }
     // split-K partials of the batched projections.  A finish launched right behind its producer re-uses ONE [4][32][N] block; only the
     // tiled path defers finishes to a later launch (prep_rows_kernel, sk_part) and keeps a [16][32][hidden] block per group of 32 rows
     const size_t groups = (b + NBM - 1) / NBM;
@@ -495,6 +534,18 @@ static hipError_t launch_attn_partial(const AttnDecArgs& a, int D, int steps, bo
 }
 static hipError_t launch_attn_combine(const AttnDecArgs& a, int D, int B, hipStream_t st) {
     return D == 96 ? launch_attn_combine_d<96>(a, B, st) : launch_attn_combine_d<64>(a, B, st);
+}
+
+// the fused single-row MLP of `layer` on the context's buffers (kinds 4 and 5 of a plan with mlp_fused)
+static MlpArgs mlp_args(er_ctx* c, int layer) {
+    const LayerW& L = c->layers[layer];
+    const KvMem& kv = *c->kv;
+    MlpArgs m{};
+    m.W1 = c->fast ? (const void*)L.w1_h : (const void*)L.w1; m.b1 = L.b1; m.W2T = L.w2_kt; m.zero_row = c->zero_row;
+    m.xin = kv.ypre1.p; m.ln_w = L.ln1w; m.ln_b = L.ln1b; m.eps = c->cfg.ln_eps; m.hout = kv.h1buf.p;
+    m.part = kv.mlp_part.p; m.nnz = kv.mlp_nnz.p + (size_t)layer * MLP_WGS;
+    m.b2 = L.b2; m.resid = kv.h1buf.p; m.out = kv.ypre.p;
+    return m;
 }
 
 // A projection kind fills the operands from the context (plain weights, row-major input, and in io what the other forms read instead);
@@ -553,6 +604,10 @@ static hipError_t launch_kind_t(er_ctx* c, int kind, int layer, hipStream_t st, 
         }
         case 4: {   // h1 = LN1(ypre1); f = relu(fc1 h1 + b)
             const LayerW& L = c->layers[layer];
+            if (p.mlp_fused) {      // ... and the chain sums of fc2 over the live neurons; f stays in the workgroups
+                if (!c->kmajor_valid) return hipErrorInvalidValue;
+                return launch_mlp_fused<WT>(mlp_args(c, layer), st);
+            }
             a.W = HALF ? (const void*)L.w1_h : (const void*)L.w1; a.bias = L.b1; a.N = I; a.xin = kv.ypre1.p; a.ln_w = L.ln1w; a.ln_b = L.ln1b;
             a.hout = kv.h1buf.p; a.out = kv.fbuf.p;
             io.pro = PRO_LN;
@@ -563,6 +618,7 @@ static hipError_t launch_kind_t(er_ctx* c, int kind, int layer, hipStream_t st, 
         }
         case 5: {   // ypre = fc2 f + b + h1
             const LayerW& L = c->layers[layer];
+            if (p.mlp_fused) return launch_mlp_finish(mlp_args(c, layer), st);
             a.W = HALF ? (const void*)L.w2_h : (const void*)L.w2; a.bias = L.b2; a.N = H; a.xin = kv.fbuf.p; a.out = kv.ypre.p; a.resid = kv.h1buf.p;
             io.w_tiled = L.w2_t; io.x_image = kv.xt_f.p;
             return run_proj<WT>(PROJ_FC2, form_of(PROJ_FC2, layer), io, a, B, I, sk, st);
@@ -891,6 +947,7 @@ static int prefill_run(er_ctx* c, const float* embeds, int B, int S, hipStream_t
     HIPCHK(hipSetDevice(c->device));
     const DecodePlan& p = c->kv->plan;
     if (p.mfma) ERCHK(make_tiled_weights(c));
+    if (p.mlp_fused) ERCHK(make_kmajor_weights(c));
     const er_config& g = c->cfg;
     const int H = g.hidden_dim, I = g.intermediate_dim, NH = g.num_heads, D = c->D;
     const int M = B * S;
@@ -1232,6 +1289,7 @@ extern "C" int er_queue_begin(er_ctx* c, const er_decode_params* p, int check_ev
     HIPCHK(hipSetDevice(c->device));
     hipStream_t st = pick(c, stream);
     if (c->kv->plan.mfma) ERCHK(make_tiled_weights(c));
+    if (c->kv->plan.mlp_fused) ERCHK(make_kmajor_weights(c));
     ERCHK(c->q_look.ensure((size_t)3 * B + 1));
     if (c->q_pinned) { hipHostFree(c->q_pinned); c->q_pinned = nullptr; }
     HIPCHK(hipHostMalloc((void**)&c->q_pinned, ((size_t)3 * B + 1) * sizeof(int), hipHostMallocDefault));
@@ -1459,6 +1517,15 @@ static int profile_impl(er_ctx* c, int repeats, int use_graph, float* avg_us, do
         if (gexec) hipGraphExecDestroy(gexec);
     }
     HIPCHK(hipStreamSynchronize(st));
+    if (p.mlp_fused) {   // what the sweep's launches streamed: W1, the LIVE rows of W2T (counted by the kernel itself), the chain vectors
+        std::vector<int> nnz((size_t)nl * MLP_WGS);
+        HIPCHK(hipMemcpy(nnz.data(), c->kv->mlp_nnz.p, nnz.size() * sizeof(int), hipMemcpyDeviceToHost));
+        double live = 0.0;
+        for (int n : nnz) live += n;
+        const double part = (double)MLP_WGS * H * 4.0;
+        bytes[4] = ((double)I * H + live / nl * H) * w + ((double)I + 4 * H) * 4.0 + part;
+        bytes[5] = part + (double)3 * H * 4.0;
+    }
     HIPCHK(hipMemcpy(c->kv->ypre.p, save_y.data(), save_y.size() * 4, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(c->kv->state_block.p, save_state.data(), save_state.size() * sizeof(int), hipMemcpyHostToDevice));
     return ER_OK;
@@ -1666,6 +1733,40 @@ extern "C" int er_k_gemv_form(const er_k_gemv_form_args* f, void* stream) {
     Proj proj = PROJ_QKV;
     ERCHK(gemv_form_check(*f, &proj));
     return f->w_half ? gemv_form_t<_Float16>(*f, proj, (hipStream_t)stream) : gemv_form_t<float>(*f, proj, (hipStream_t)stream);
+}
+
+// ---- the fused single-row MLP on caller-owned operands.  er_k_mlp_transpose makes the k-major copy the decode context keeps per
+// layer; er_k_mlp_sparse enqueues one layer's two launches and returns - it allocates nothing and does not synchronise, so a caller
+// can capture it into a graph.
+extern "C" int er_k_mlp_transpose(const void* w2, void* w2t, int w_half, void* stream) {
+    if (!w2 || !w2t) return fail(ER_ERR_INVALID, "er_k_mlp_transpose: null argument");
+    hipStream_t st = (hipStream_t)stream;
+    HIPRET(w_half ? launch_transpose_w2<_Float16>(w2, w2t, st) : launch_transpose_w2<float>(w2, w2t, st));
+    return ER_OK;
+}
+
+extern "C" int er_k_mlp_sparse(const er_k_mlp_sparse_args* f, void* stream) {
+    if (!f) return fail(ER_ERR_INVALID, "er_k_mlp_sparse: null args");
+    if (!f->w1 || !f->b1 || !f->w2t || !f->zero_row || !f->b2 || !f->x || !f->ln_w || !f->ln_b || !f->h1_out || !f->y || !f->part)
+        return fail(ER_ERR_INVALID, "er_k_mlp_sparse: null operand");
+    hipStream_t st = (hipStream_t)stream;
+    MlpArgs m{};
+    m.W1 = f->w1; m.b1 = f->b1; m.W2T = f->w2t; m.zero_row = f->zero_row; m.xin = f->x; m.ln_w = f->ln_w; m.ln_b = f->ln_b; m.eps = f->eps;
+    m.hout = f->h1_out; m.part = f->part; m.nnz = f->nnz; m.b2 = f->b2; m.resid = f->h1_out; m.out = f->y;
+    HIPRET(f->w_half ? launch_mlp_fused<_Float16>(m, st) : launch_mlp_fused<float>(m, st));
+    HIPRET(launch_mlp_finish(m, st));
+    return ER_OK;
+}
+
+// live fc1 neurons per (layer, workgroup) of the last decode step: layers * 256 counts of 0 .. 24
+extern "C" int er_mlp_nnz(er_ctx* c, int32_t* out, int n) {
+    if (!c || !out) return fail(ER_ERR_INVALID, "er_mlp_nnz: null argument");
+    if (!c->kv->plan.mlp_fused) return fail(ER_ERR_INVALID, "er_mlp_nnz: the reserved shape does not run the fused MLP");
+    if (n != (int)c->kv->mlp_nnz.n) return fail(ER_ERR_INVALID, "er_mlp_nnz: %d counts asked, the context holds %zu (layers * 256)", n, c->kv->mlp_nnz.n);
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(out, c->kv->mlp_nnz.p, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
+    return ER_OK;
 }
 
 extern "C" int er_k_attn_outproj3(const float* q, const void* k, const void* v, int len, const void* wo, const float* bo,

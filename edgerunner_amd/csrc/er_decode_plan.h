@@ -19,6 +19,9 @@ struct DecodeKnobs {          // the environment knobs of the decode step, read 
     int attn_v_batched = 0;   // attention kernel at B > 4 (env ER_ATTN_V_BATCHED): 0 = auto (streaming when B*H >= 256, else split + merge), 1 = split kernel + merge, 3 = one streaming workgroup per (row, head), no merge
     int decode_v = 3;         // single-row decode: 3 = balanced-chunk attention + merge fused into out_proj (one row, D = 96, 16 heads, Lcap <= 8192); ER_DECODE_V=2 = fixed 128-key chunks + merge kernel (also the fallback when the cache does not qualify)
     int rw_fc2 = 6;           // fast mode, one row: rows per fc2 workgroup (env ER_RW_FC2: 2 / 4 / 6, anything else runs as 2; proj_form)
+    // single-row MLP (env ER_MLP_V): 0 = fc1 and fc2 as two row GEMVs, 1 = fused launch that skips the fc2 weights behind zero ReLU outputs
+    // + finish launch (k_mlp_sparse.h)
+    int mlp_v = 0;
 };
 
 // the three switches er_kv_reserve reads for the shape it reserves (tests flip them between two reserves of one context)
@@ -46,6 +49,7 @@ struct DecodePlan {
     bool xt = false;            // fast-mode batches read the tiled activation images (KvMem::xt_*); ER_XT=0 keeps the row-major fp32 inputs (A/B + parity matrix)
     bool stream_attn = false;   // batched, D == 96 and (forced or B*H >= 256: at least one streaming workgroup per CU)
     bool v3 = false;            // decode_v == 3 and the reserved cache qualifies
+    bool mlp_fused = false;     // mlp_v != 0, one row, not batched, hidden 1536: kinds 4 and 5 are the fused MLP launch and its finish
     bool outproj_rows8 = false; // mfma and 5..8 rows: out_proj is ONE pass of the VALU kernel (ER_FORM_ROWS8)
     // xt, streaming attention and B > 8: the attention writes the tiled image xt_att, out_proj reads it and leaves SK_SLICES_OUTPROJ partials, fc1's LayerNorm launch finishes them
     bool outproj_partials = false;
@@ -84,6 +88,7 @@ inline DecodePlan make_decode_plan(const DecodeKnobs& k, const ReserveKnobs& rk,
     plan_decode(k.decode_v, k.attn_v_batched, p.force_batched, batch, H, D, hid, Lcap, ch, &p.sel);
     p.batched = p.sel.batched != 0; p.mfma = p.batched && !p.valu; p.xt = fast && p.mfma && rk.xt;
     p.stream_attn = p.sel.attn_kernel == ER_ATTN_STREAM; p.v3 = p.sel.decode_version == 3;
+    p.mlp_fused = k.mlp_v != 0 && batch == 1 && !p.batched && hid == 1536;      // the kernel's fixed widths (intermediate = 4 * hidden)
     p.outproj_rows8 = p.mfma && batch >= 5 && batch <= 8;
     p.outproj_partials = p.xt && p.stream_attn && batch > 8;
     return p;

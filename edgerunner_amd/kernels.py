@@ -147,6 +147,37 @@ def gemv_form(form, epilogue, w, B, *, x=None, bias=None, ln=None, embed=None, s
     return out
 
 
+def mlp_transpose(w2):
+    """fc2.weight [1536, 6144] (fp32 or fp16) as the k-major copy [6144, 1536] the fused single-row MLP streams (``er_k_mlp_transpose``)."""
+    assert w2.shape == (1536, 6144) and w2.dtype in (torch.float32, torch.float16)
+    w2t = torch.empty((6144, 1536), dtype=w2.dtype, device=w2.device)
+    native.check(native.load_library().er_k_mlp_transpose(native.ptr(w2), native.ptr(w2t), int(w2.dtype == torch.float16), _st()), "er_k_mlp_transpose")
+    return w2t
+
+
+class MlpSparse:
+    """One layer's fused single-row MLP on fixed operands (``er_k_mlp_sparse``): ``launch()`` only enqueues the two launches on the
+    current stream - no allocation, no synchronisation - so it can be captured into a graph.  Results: ``y``, ``h1`` (LN(x)),
+    ``nnz`` (live neurons per workgroup); ``part`` is the scratch block of 256 chain vectors."""
+
+    def __init__(self, w1, b1, w2t, b2, x, ln_w, ln_b, eps=1e-5):
+        dev = x.device
+        assert w1.shape == (6144, 1536) and w2t.shape == (6144, 1536) and w1.dtype == w2t.dtype and x.numel() == 1536
+        self.keep = [w1, b1, w2t, b2, x, ln_w, ln_b]
+        self.zero_row = torch.zeros(1536, dtype=torch.float32, device=dev)
+        self.h1 = torch.empty(1536, dtype=torch.float32, device=dev)
+        self.y = torch.empty(1536, dtype=torch.float32, device=dev)
+        self.part = torch.empty((256, 1536), dtype=torch.float32, device=dev)
+        self.nnz = torch.zeros(256, dtype=torch.int32, device=dev)
+        a = self.args = native.ErKMlpSparseArgs()
+        a.w1, a.b1, a.w2t, a.zero_row, a.b2, a.x, a.ln_w, a.ln_b, a.h1_out, a.y, a.part, a.nnz = (
+            native.ptr(t).value for t in (w1, b1, w2t, self.zero_row, b2, x, ln_w, ln_b, self.h1, self.y, self.part, self.nnz))
+        a.w_half, a.eps = int(w1.dtype == torch.float16), eps
+
+    def launch(self):
+        native.check(native.load_library().er_k_mlp_sparse(C.byref(self.args), _st()), "er_k_mlp_sparse")
+
+
 def attn_stream_xt(q, k_cache, v_cache, lens, out_xt):
     """The streaming decode attention (head_dim 96) that also writes its rows into the tiled image out_xt (half
     [groups, heads * 24, 32, 8], xt_pack_image's layout; written in place) -> out [B, heads * 96]."""

@@ -33,7 +33,7 @@ EXPORTS = [
     "er_dit_finalize_weights", "er_dit_project_cond", "er_dit_encode_image", "er_dit_forward", "er_dit_sample",
     "er_dit_set_prediction_type", "er_dit_attach_point_encoder", "er_dit_point_latent", "er_dit_set_point_encoder_mode", "er_dit_loss", "er_k_dit_loss",
     "er_set_row_streams", "er_plan_decode", "er_ctx_plan", "er_plan_gemm_tile", "er_kernel_kind_name", "er_profile_decode_kernels", "er_profile_decode_kernels_at", "er_last_decode_ms",
-    "er_k_gemv", "er_k_gemv_form", "er_k_attn_decode", "er_k_attn_stream_xt", "er_k_attn_outproj3", "er_k_gemm", "er_k_gemm_f16", "er_k_gemm_hh", "er_k_gemm_hh_qkv", "er_k_gemm_hh_geglu", "er_k_gemm_f16s", "er_k_flash_attn_f16", "er_k_flash_attn_hh", "er_k_flash_attn_f32", "er_k_flash_attn_f16s", "er_k_layernorm", "er_k_softmax", "er_k_score_rows", "er_k_fps", "er_k_sample_head",
+    "er_k_gemv", "er_k_gemv_form", "er_k_mlp_transpose", "er_k_mlp_sparse", "er_mlp_nnz", "er_k_attn_decode", "er_k_attn_stream_xt", "er_k_attn_outproj3", "er_k_gemm", "er_k_gemm_f16", "er_k_gemm_hh", "er_k_gemm_hh_qkv", "er_k_gemm_hh_geglu", "er_k_gemm_f16s", "er_k_flash_attn_f16", "er_k_flash_attn_hh", "er_k_flash_attn_f32", "er_k_flash_attn_f16s", "er_k_layernorm", "er_k_softmax", "er_k_score_rows", "er_k_fps", "er_k_sample_head",
     "er_k_nn_dist2", "er_k_surface_sample", "er_k_fidelity_metrics",
     "er_queue_begin", "er_queue_admit", "er_queue_run", "er_queue_take", "er_queue_stats", "er_queue_end",
 ]
@@ -59,6 +59,11 @@ class ErKGemvFormArgs(C.Structure):
         "q_out", "kcache", "vcache", "prep_xt_out", "xt_out", "part_out")] + [(n, C.c_int32) for n in (
         "w_half", "kv_half", "batch", "n", "k", "prologue", "epilogue", "form", "nw", "rw", "sk_slices", "heads", "head_dim",
         "l_cap")] + [("eps", C.c_float)]
+
+
+class ErKMlpSparseArgs(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("w1", "b1", "w2t", "zero_row", "b2", "x", "ln_w", "ln_b", "h1_out", "y", "part", "nnz")] + \
+               [("w_half", C.c_int32), ("eps", C.c_float)]
 
 
 class ErConfig(C.Structure):
@@ -158,6 +163,9 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.er_queue_end.argtypes = [vp]
     lib.er_k_gemv.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, cf, vp]
     lib.er_k_gemv_form.argtypes = [C.POINTER(ErKGemvFormArgs), vp]
+    lib.er_k_mlp_transpose.argtypes = [vp, vp, ci, vp]
+    lib.er_k_mlp_sparse.argtypes = [C.POINTER(ErKMlpSparseArgs), vp]
+    lib.er_mlp_nnz.argtypes = [vp, C.POINTER(C.c_int32), ci]
     lib.er_k_attn_stream_xt.argtypes = [vp, vp, vp, C.POINTER(C.c_int32), vp, vp, ci, ci, ci, ci, vp]
     lib.er_k_attn_decode.argtypes = [vp, vp, vp, C.POINTER(C.c_int32), vp, ci, ci, ci, ci, ci, ci, ci, vp]
     lib.er_k_attn_outproj3.argtypes = [vp, vp, vp, ci, vp, vp, vp, vp, ci, ci, ci, vp]

@@ -387,6 +387,15 @@ class NativeShapeOPT:
         native.check(self.lib.er_ctx_plan(self._ctx, C.byref(p)), "er_ctx_plan")
         return {n: int(getattr(p, n)) for n, _ in native.ErDecodePlan._fields_}
 
+    def mlp_nnz(self):
+        """Live fc1 neurons per (layer, workgroup) that the fused single-row MLP counted in the last decode step (``er_mlp_nnz``):
+        int32 [num_layers, 256], each 0 .. 24.  Raises unless the reserved shape runs the fused MLP (one row, ``ER_MLP_V`` on)."""
+        import numpy as np
+        n = int(self.dims.num_layers) * 256
+        buf = np.empty((n,), dtype=np.int32)
+        native.check(self.lib.er_mlp_nnz(self._ctx, buf.ctypes.data_as(C.POINTER(C.c_int32)), n), "er_mlp_nnz")
+        return buf.reshape(-1, 256)
+
     # -- measurement -------------------------------------------------------------------------
     def profile_decode_kernels(self, repeats: int = 5, context_len: int = 0, use_graph: bool = False):
         """Per-kind average launch duration (HIP events on the launch stream) and algorithmic bytes per launch.

@@ -402,6 +402,32 @@ typedef struct {
     float eps;
 } er_k_gemv_form_args;
 int er_k_gemv_form(const er_k_gemv_form_args* args, void* stream);
+/* The fused single-row MLP of the decode step (hidden 1536, intermediate 6144): y = W2 . relu(W1 . LN(x) + b1) + b2 + LN(x) in two
+ * launches that fetch a row of the k-major fc2 copy only where the ReLU output is non-zero; bit-identical to fc1 (ER_PRO_LN /
+ * ER_EPI_RELU) followed by fc2 (ER_EPI_RESID) of er_k_gemv_form.  er_k_mlp_transpose builds w2t [6144][1536] from fc2.weight
+ * [1536][6144] (fp32, or fp16 with w_half).  er_k_mlp_sparse only enqueues: it allocates nothing and does not synchronise, so the
+ * pair of launches can be captured into a graph.  Every pointer is device memory. */
+int er_k_mlp_transpose(const void* w2_dev, void* w2t_dev, int w_half, void* stream);
+typedef struct er_k_mlp_sparse_args {
+    const void* w1;            /* [6144][1536] fp32 / fp16 */
+    const float* b1;           /* [6144] */
+    const void* w2t;           /* [6144][1536] fp32 / fp16 (er_k_mlp_transpose) */
+    const void* zero_row;      /* 6144 zero bytes */
+    const float* b2;           /* [1536] */
+    const float* x;            /* [1536] pre-LayerNorm input */
+    const float* ln_w;
+    const float* ln_b;
+    float* h1_out;             /* [1536] LN(x): written by the first launch, read as the residual by the second */
+    float* y;                  /* [1536] */
+    float* part;               /* [256][1536] scratch: every word is rewritten by every call */
+    int32_t* nnz;              /* [256] live neurons per workgroup (0 .. 24); may be null */
+    int32_t w_half;
+    float eps;
+} er_k_mlp_sparse_args;
+int er_k_mlp_sparse(const er_k_mlp_sparse_args* args, void* stream);
+/* Live fc1 neurons per (layer, workgroup) that the fused MLP counted in the last decode step of the reserved single-row shape:
+ * n = num_layers * 256 counts of 0 .. 24 into out (host memory). */
+int er_mlp_nnz(er_ctx* ctx, int32_t* out, int n);
 /* The ER_ATTN_STREAM kernel of er_k_attn_decode (head_dim 96) that also writes its output rows into the tiled hi | lo image
  * out_xt_dev (heads * 96 * 128 bytes per 32 rows; rows the batch does not have are left alone), as out_proj's tiled forms read it. */
 int er_k_attn_stream_xt(const float* q_dev, const void* k_dev, const void* v_dev, const int32_t* len_host, float* out_dev,
