@@ -1833,6 +1833,48 @@ extern "C" int er_k_gemm_hh(const float* a, const void* w, const float* bias, co
     return ER_OK;
 }
 
+// ---- er_k_gemm_epi: one GEMM family with the WHOLE plain epilogue the product uses (bias, / div, relu, adaLN gate rows, a residual
+// that may be one table shared by every batch, the fp16 copy).  It fills GemmArgs and calls the family's own launcher - no kernel of
+// its own - so ER_GEMM_TILE / ER_GEMM_F32_DMA / ER_GEMM_STREAM / force_tile select the form exactly as they do for the product.
+extern "C" int er_k_gemm_epi(const er_k_gemm_epi_args* f, void* stream) {
+    if (!f) return fail(ER_ERR_INVALID, "er_k_gemm_epi: null args");
+    const int fam = f->family;
+    if (fam < ER_GEMM_F32 || fam > ER_GEMM_HH) return fail(ER_ERR_INVALID, "er_k_gemm_epi: family %d", fam);
+    const bool hh = fam == ER_GEMM_HH;
+    if (!f->a || !f->w || (!f->c && !(hh && f->c16))) return fail(ER_ERR_INVALID, "er_k_gemm_epi: a, w and an output are required");
+    if (f->m <= 0 || f->n <= 0 || f->k <= 0 || f->ldc < f->n) return fail(ER_ERR_INVALID, "er_k_gemm_epi: m %d, n %d, k %d, ldc %d", f->m, f->n, f->k, f->ldc);
+    if (fam == ER_GEMM_F32 && (f->k % 16 || (f->lda & 3) || (f->ldb & 3))) return fail(ER_ERR_INVALID, "er_k_gemm_epi: fp32 needs k a multiple of 16, lda and ldb of 4");
+    if ((fam == ER_GEMM_F16 || fam == ER_GEMM_F16S) && (f->k % 32 || (f->lda & 3) || (f->ldb & 7)))
+        return fail(ER_ERR_INVALID, "er_k_gemm_epi: the fp16-weight families need k a multiple of 32, lda of 4, ldb of 8");
+    if (hh && (f->k % 64 || (f->ldb & 7))) return fail(ER_ERR_INVALID, "er_k_gemm_epi: the LDS-DMA fp16 family needs k a multiple of 64, ldb of 8");
+    if (f->lda < f->k || f->ldb < f->k) return fail(ER_ERR_INVALID, "er_k_gemm_epi: lda %d / ldb %d below k %d", f->lda, f->ldb, f->k);
+    if (f->c16 && !hh) return fail(ER_ERR_INVALID, "er_k_gemm_epi: c16 is written by the LDS-DMA fp16 family only");
+    if (f->force_tile < 0 || f->force_tile > 4 || (f->force_tile && !hh)) return fail(ER_ERR_INVALID, "er_k_gemm_epi: force_tile 0..4, LDS-DMA fp16 family only (the others read ER_GEMM_TILE)");
+    if (f->gate && (f->gate_rows <= 0 || f->gate_bstride < f->n)) return fail(ER_ERR_INVALID, "er_k_gemm_epi: a gate needs gate_rows > 0 and gate_bstride >= n");
+    if (f->resid && f->ldr < f->n) return fail(ER_ERR_INVALID, "er_k_gemm_epi: ldr %d below n %d", f->ldr, f->n);
+    if (f->resid_mod < 0 || (f->resid_mod && !f->resid)) return fail(ER_ERR_INVALID, "er_k_gemm_epi: resid_mod %d (>= 0, with a residual)", f->resid_mod);
+    hipStream_t st = (hipStream_t)stream;
+    GemmArgs g = gemm_args_default();
+    g.A = f->a; g.B = reinterpret_cast<const float*>(f->w); g.C = f->c; g.bias = f->bias;
+    g.resid = f->resid; g.ldr = f->ldr; g.resid_mod = f->resid_mod;
+    g.gate = f->gate; g.gate_rows = f->gate_rows; g.gate_bstride = f->gate_bstride;
+    g.M = f->m; g.N = f->n; g.K = f->k; g.lda = f->lda; g.ldb = f->ldb; g.ldc = f->ldc; g.kb_valid = f->k;
+    g.relu = f->relu; g.div = f->div;
+    if (fam == ER_GEMM_F32) { HIPRET(launch_gemm(g, 1, st)); return ER_OK; }
+    if (fam == ER_GEMM_F16) { HIPRET(launch_gemm_f16(g, st)); return ER_OK; }
+    if (fam == ER_GEMM_F16S) { HIPRET(launch_gemm_f16s(g, st)); return ER_OK; }
+    DevBuf<_Float16> a16b;      // the fp16 copy of A, as er_k_gemm_hh makes it
+    ERCHK(a16b.ensure((size_t)f->m * f->k));
+    hipLaunchKernelGGL(cvt_rows_f16_kernel, dim3(ew_grid((long long)f->m * f->k)), dim3(ER_WG), 0, st, f->a, a16b.p, (long long)f->m, f->k, f->lda, f->k);
+    g.A = reinterpret_cast<const float*>(a16b.p); g.lda = f->k;
+    g.c16 = reinterpret_cast<_Float16*>(f->c16); g.ldc16 = f->ldc;
+    hipError_t e = launch_gemm_hh(g, st, f->force_tile);
+    hipError_t e2 = hipStreamSynchronize(st);
+    HIPRET(e);
+    HIPRET(e2);
+    return ER_OK;
+}
+
 extern "C" int er_k_gemm_hh_qkv(const float* a, const void* w, const float* bias, void* qk16_out, void* vt_out, int m, int n, int k,
                                 int rows_per_batch, int force_tile, void* stream) {
     if (k % 64 || n % 192 || m % 64 || rows_per_batch <= 0 || rows_per_batch % 64 || m % rows_per_batch)

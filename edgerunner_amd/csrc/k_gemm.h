@@ -15,6 +15,7 @@
 // the current one is multiplied.
 #pragma once
 #include "er_common.h"
+#include "er_gemm_rows.h"
 
 namespace er {
 
@@ -68,17 +69,8 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 // evaluated five integer divisions and every option per ELEMENT in a 64-fold unrolled body: ~100 KB of code per kernel, which the
 // instruction cache could not hold - a fixed ~19 us per workgroup, i.e. the whole time of a K = 1024 GEMM
 // (profiles/r03_gemm_hh_probe.log).
-struct RowBatch {          // batch index (row / period) and row inside the batch for the rows [row0, row0 + span) (span 32: one MFMA block)
-    int q0, next, period;
-    bool fast;
-    __device__ __forceinline__ RowBatch(int row0, int period_, int span = 32) : period(period_) {
-        fast = period_ >= span;
-        q0 = period_ > 0 ? row0 / period_ : 0;
-        next = (q0 + 1) * period_;
-    }
-    __device__ __forceinline__ int batch(int gm) const { return fast ? q0 + (gm >= next ? 1 : 0) : gm / period; }
-    __device__ __forceinline__ int inner(int gm) const { return gm - batch(gm) * period; }
-};
+// RowBatch (er_gemm_rows.h, host-checkable) is that map; wave_row_batch / gate_row_pair are its forms for a wave that requests its
+// operands before it knows which of its rows exist.
 
 template <int TM, int TN>
 __device__ __forceinline__ void gemm_epilogue(const GemmArgs& g, float* C, const f32x16 (&acc)[TM][TN], int m0, int n0, int wm,
@@ -583,7 +575,10 @@ __device__ __forceinline__ void hh_epi_rows(const GemmArgs& g, const float* sw, 
             if (gn + 2 < g.N) bias.z = g.bias[gn + 2];
             if (gn + 3 < g.N) bias.w = g.bias[gn + 3];
         }
-        const RowBatch gb(mw, g.gate ? g.gate_rows : 0, WR), rb(mw, (g.resid && g.resid_mod > 0) ? g.resid_mod : 0, WR);
+        // anchored at min(mw, M - 1): a wave wholly beyond M (ragged last tile) still forms the addresses of its gate pair and of its
+        // pre-fetched residuals from rows clamped to M - 1, and those must stay inside the tables (er_gemm_rows.h)
+        const RowBatch gb = wave_row_batch(mw, g.M, g.gate ? g.gate_rows : 0, WR),
+                       rb = wave_row_batch(mw, g.M, (g.resid && g.resid_mod > 0) ? g.resid_mod : 0, WR);
         // 32-row blocks (TM = 1: the N = 1024 residual products of the DiT): the residual operands of all eight passes are requested before
         // the first is used (round 6) - with the loads inside a 4-fold unrolled pass loop a wave had 4 x 1 KB in flight, 16-32 KB per CU; in
         // situ 32.8 -> 32.0 us mean over the four products (profiles/r06_dit_trace_ab.log).  64-row blocks (TM = 2: q/k/v, the 256 x 256 tile)
@@ -597,8 +592,9 @@ __device__ __forceinline__ void hh_epi_rows(const GemmArgs& g, const float* sw, 
         int gb0 = 0, gb1 = 0;
         if (use_pre) { gate0 = pre_->gate0; gate1 = pre_->gate1; gb0 = pre_->gb0; gb1 = pre_->gb1; }
         else if (g.gate && vec) {
-            gb0 = gb.batch(mw);
-            gb1 = gb.batch(min(mw + WR - 1, g.M - 1));
+            const GatePair gp = gate_row_pair(gb, mw, g.M, WR);
+            gb0 = gp.gb0;
+            gb1 = gp.gb1;
             gate0 = *reinterpret_cast<const f32x4*>(g.gate + (long long)gb0 * g.gate_bstride + gn);
             gate1 = *reinterpret_cast<const f32x4*>(g.gate + (long long)gb1 * g.gate_bstride + gn);
         }

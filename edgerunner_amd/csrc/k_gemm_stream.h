@@ -72,8 +72,9 @@ __device__ __forceinline__ void gs_load_pre(const GemmArgs& g, HhEpiPre (&pre)[2
         pre[h].gate0 = pre[h].gate1 = one;
         pre[h].gb0 = pre[h].gb1 = 0;
         if (g.gate) {
-            pre[h].gb0 = min(m0h, g.M - 1) / g.gate_rows;
-            pre[h].gb1 = min(m0h + 31, g.M - 1) / g.gate_rows;
+            const GatePair gp = gate_row_pair(wave_row_batch(m0h, g.M, g.gate_rows, 32), m0h, g.M, 32);      // as hh_epi_rows<1, 2> forms it
+            pre[h].gb0 = gp.gb0;
+            pre[h].gb1 = gp.gb1;
             pre[h].gate0 = *reinterpret_cast<const f32x4*>(g.gate + (long long)pre[h].gb0 * g.gate_bstride + gn);
             pre[h].gate1 = *reinterpret_cast<const f32x4*>(g.gate + (long long)pre[h].gb1 * g.gate_bstride + gn);
         }

@@ -277,6 +277,36 @@ def gemm_f16s(a, w_half, bias=None, resid=None, relu=False):
     return c
 
 
+def _rows_ptr(t):
+    """Pointer of a 2-D tensor whose rows are contiguous (a view into a larger allocation is fine: the row stride is passed as ld)."""
+    if t is None:
+        return None
+    assert t.dim() == 2 and t.stride(1) == 1, "rows must be contiguous"
+    return t.data_ptr()
+
+
+def gemm_epi(family, a, w, c, *, bias=None, resid=None, resid_mod=0, gate=None, gate_rows=0, c16=None, relu=False, div=0.0, force_tile=0):
+    """One GEMM family with the whole plain epilogue (``er_k_gemm_epi``; native.ER_GEMM_F32 / F16 / F16S / HH), written in place:
+      c[m][n] = resid[m % resid_mod if resid_mod else m][n] + gate[m // gate_rows][n] * relu?((a . w^T)[m][n] (/ div) + bias[n]),  c16 = fp16(c)
+    a [M, K] fp32, w [N, K] fp32 (F32) or fp16, c [M, N] fp32 (None with c16), c16 [M, N] fp16 (HH only).  Every 2-D operand may be a
+    view with contiguous rows into a larger tensor: its row stride is the ld the kernel gets (gate: gate_bstride; c and c16 share ldc).
+    Which form runs is chosen as in the product: ER_GEMM_TILE, ER_GEMM_F32_DMA, ER_GEMM_STREAM, and force_tile for HH."""
+    lib = native.load_library()
+    f = native.ErKGemmEpiArgs()
+    M, K = a.shape
+    N = w.shape[0]
+    out = c if c is not None else c16
+    assert w.shape[1] == K and tuple(out.shape) == (M, N)
+    assert c is None or c16 is None or c16.stride(0) == c.stride(0), "c and c16 share one row stride"
+    f.a, f.w, f.resid, f.gate, f.c, f.c16 = (_rows_ptr(t) for t in (a, w, resid, gate, c, c16))
+    f.bias = native.ptr(bias).value
+    f.family, f.m, f.n, f.k, f.lda, f.ldb, f.ldc = family, M, N, K, a.stride(0), w.stride(0), out.stride(0)
+    f.ldr = resid.stride(0) if resid is not None else 0
+    f.resid_mod, f.gate_rows, f.gate_bstride = resid_mod, gate_rows, gate.stride(0) if gate is not None else 0
+    f.relu, f.div, f.force_tile = int(relu), float(div), force_tile
+    native.check(lib.er_k_gemm_epi(C.byref(f), _st()), "er_k_gemm_epi")
+
+
 def flash_attn_f16(q, k, v, heads):
     """q [B,N,H*64], k/v [B,M,H*64] fp32 -> softmax(q k^T / 8) v, [B,N,H*64] (fp16 operands, fp32 accumulate)."""
     lib = native.load_library()

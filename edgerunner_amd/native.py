@@ -33,7 +33,7 @@ EXPORTS = [
     "er_dit_finalize_weights", "er_dit_project_cond", "er_dit_encode_image", "er_dit_forward", "er_dit_sample",
     "er_dit_set_prediction_type", "er_dit_attach_point_encoder", "er_dit_point_latent", "er_dit_set_point_encoder_mode", "er_dit_loss", "er_k_dit_loss",
     "er_set_row_streams", "er_plan_decode", "er_ctx_plan", "er_plan_gemm_tile", "er_kernel_kind_name", "er_profile_decode_kernels", "er_profile_decode_kernels_at", "er_last_decode_ms",
-    "er_k_gemv", "er_k_gemv_form", "er_k_mlp_transpose", "er_k_mlp_sparse", "er_mlp_nnz", "er_k_attn_decode", "er_k_attn_stream_xt", "er_k_attn_outproj3", "er_k_gemm", "er_k_gemm_f16", "er_k_gemm_hh", "er_k_gemm_hh_qkv", "er_k_gemm_hh_geglu", "er_k_gemm_f16s", "er_k_flash_attn_f16", "er_k_flash_attn_hh", "er_k_flash_attn_f32", "er_k_flash_attn_f16s", "er_k_layernorm", "er_k_softmax", "er_k_score_rows", "er_k_fps", "er_k_sample_head",
+    "er_k_gemv", "er_k_gemv_form", "er_k_mlp_transpose", "er_k_mlp_sparse", "er_mlp_nnz", "er_k_attn_decode", "er_k_attn_stream_xt", "er_k_attn_outproj3", "er_k_gemm", "er_k_gemm_f16", "er_k_gemm_hh", "er_k_gemm_hh_qkv", "er_k_gemm_hh_geglu", "er_k_gemm_f16s", "er_k_gemm_epi", "er_k_flash_attn_f16", "er_k_flash_attn_hh", "er_k_flash_attn_f32", "er_k_flash_attn_f16s", "er_k_layernorm", "er_k_softmax", "er_k_score_rows", "er_k_fps", "er_k_sample_head",
     "er_k_nn_dist2", "er_k_surface_sample", "er_k_fidelity_metrics",
     "er_queue_begin", "er_queue_admit", "er_queue_run", "er_queue_take", "er_queue_stats", "er_queue_end",
 ]
@@ -64,6 +64,16 @@ class ErKGemvFormArgs(C.Structure):
 class ErKMlpSparseArgs(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("w1", "b1", "w2t", "zero_row", "b2", "x", "ln_w", "ln_b", "h1_out", "y", "part", "nnz")] + \
                [("w_half", C.c_int32), ("eps", C.c_float)]
+
+
+# er_k_gemm_epi: one GEMM family with the whole plain epilogue (include/edgerunner_hip.h)
+ER_GEMM_F32, ER_GEMM_F16, ER_GEMM_F16S, ER_GEMM_HH = range(4)
+
+
+class ErKGemmEpiArgs(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("a", "w", "bias", "resid", "gate", "c", "c16")] + [("gate_bstride", C.c_int64)] + \
+               [(n, C.c_int32) for n in ("family", "m", "n", "k", "lda", "ldb", "ldc", "ldr", "resid_mod", "gate_rows", "relu", "force_tile")] + \
+               [("div", C.c_float)]
 
 
 class ErConfig(C.Structure):
@@ -173,6 +183,7 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.er_k_gemm_f16.argtypes = [vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, vp]
     lib.er_k_gemm_f16s.argtypes = [vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, vp]
     lib.er_k_gemm_hh.argtypes = [vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, vp]
+    lib.er_k_gemm_epi.argtypes = [C.POINTER(ErKGemmEpiArgs), vp]
     lib.er_k_gemm_hh_qkv.argtypes = [vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, vp]
     lib.er_k_gemm_hh_geglu.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, vp]
     lib.er_k_flash_attn_f16.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, vp]

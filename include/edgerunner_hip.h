@@ -451,6 +451,33 @@ int er_k_gemm_f16(const float* a_dev, const void* w_half_dev, const float* bias_
  * DiT path the producing kernel writes that copy); c16_out_dev (optional) receives the result rounded to fp16 [m][n] */
 int er_k_gemm_hh(const float* a_dev, const void* w_half_dev, const float* bias_dev, const float* resid_dev, float* c_dev,
                  void* c16_out_dev, int m, int n, int k, int lda, int ldb, int ldc, int relu, void* stream);
+/* ONE GEMM family with the whole plain epilogue of the product:
+ *   C[m][n] = resid[(resid_mod ? m % resid_mod : m)][n] + gate[m / gate_rows][n] * relu?((A . W^T)[m][n] (/ div) + bias[n]),  c16 = fp16(C)
+ * (adaLN gate rows of the DiT blocks; one residual table shared by every batch: the point encoder's cross-attention out_proj).  The
+ * entry fills the launch arguments and calls the family's launcher - ER_GEMM_F32: er_k_gemm's kernels (w fp32; ER_GEMM_F32_DMA,
+ * ER_GEMM_TILE pick the form), ER_GEMM_F16 / ER_GEMM_F16S: er_k_gemm_f16's / the register-staged split kernels (w fp16; ER_GEMM_TILE),
+ * ER_GEMM_HH: the LDS-DMA fp16 kernels on an fp16 copy of a (w fp16; force_tile 1 / 2 / 3 = 128x128 / 64x128 / 64x64, 4 = 256x256,
+ * 0 = the product rule, which ER_GEMM_STREAM=2 turns into the streamed form).  a is fp32 [m][lda]; every ld* counts elements of its
+ * array; c16 (ER_GEMM_HH only, nullable) has row stride ldc as well; c may be null when c16 is given.  Nullable: bias, resid, gate.
+ * ER_ERR_INVALID before anything is launched: a gate with gate_rows <= 0, k not a multiple of 16 (F32) / 32 (F16, F16S) / 64 (HH),
+ * lda / ldb that break the 16-byte row alignment, c16 or force_tile outside ER_GEMM_HH.  ER_GEMM_HH blocks until the work is complete. */
+typedef enum { ER_GEMM_F32 = 0, ER_GEMM_F16 = 1, ER_GEMM_F16S = 2, ER_GEMM_HH = 3 } er_gemm_family;
+typedef struct er_k_gemm_epi_args {
+    const float* a;            /* [m][lda] fp32 */
+    const void* w;             /* [n][ldb] fp32 (ER_GEMM_F32) or fp16 */
+    const float* bias;         /* [n] */
+    const float* resid;        /* [resid_mod ? resid_mod : m][ldr] */
+    const float* gate;         /* row b at gate + b * gate_bstride, ceil(m / gate_rows) rows of n */
+    float* c;                  /* [m][ldc] */
+    void* c16;                 /* [m][ldc] fp16 */
+    int64_t gate_bstride;
+    int32_t family;            /* er_gemm_family */
+    int32_t m, n, k, lda, ldb, ldc, ldr;
+    int32_t resid_mod, gate_rows;
+    int32_t relu, force_tile;
+    float div;                 /* != 0: the product is divided by it before the bias */
+} er_k_gemm_epi_args;
+int er_k_gemm_epi(const er_k_gemm_epi_args* args, void* stream);
 /* the fused q/k/v projection of the DiT self-attention (core/transformer/dit.py:100-126 -> attention.py:176-178) as the LDS-DMA
  * kernel runs it: n = 3 * heads * 64 output columns, the first two thirds (q, k) rounded to fp16 into qk16_out_dev [m][n] (its V
  * columns are left untouched), the V third written by the GEMM epilogue as V^T per head into vt_out_dev
