@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "er_common.h"
+#include "k_attn_lanes.h"
 #include "k_attn_decode.h"
 #include "k_outproj_merge.h"
 #include "k_flash_attn_f16s.h"
@@ -400,14 +401,14 @@ static int make_kmajor_weights(er_ctx* c) {
 // ------------------------------------------------------------------------------------ which decode kernels a cache shape gets
 // The selection rules are host-only code in er_decode_plan.h (plan_decode, make_decode_plan, proj_form); the attention kernels' chunking
 // enters them as numbers.
-static AttnChunking attn_chunking(int heads, bool fast) {
-    return {attn3_num_chunks(heads), attn3_num_chunks(heads) * ATTN3_CAP, attn_chunk(ATTN_STEPS_DEFAULT, fast)};
+static AttnChunking attn_chunking(int heads) {
+    return {attn3_num_chunks(heads), attn3_num_chunks(heads) * ATTN3_CAP, attn_chunk(ATTN_STEPS_DEFAULT)};
 }
 
 extern "C" int er_plan_decode(int batch, int heads, int head_dim, int hidden, int l_cap, er_decode_plan* out) {
     if (!out || batch <= 0 || heads <= 0 || head_dim <= 0 || l_cap <= 0) return fail(ER_ERR_INVALID, "er_plan_decode: bad argument");
     const DecodeKnobs k = read_knobs(false);
-    plan_decode(k.decode_v, k.attn_v_batched, read_reserve_knobs().force_batched, batch, heads, head_dim, hidden, (l_cap + 31) / 32 * 32, attn_chunking(heads, false), out);
+    plan_decode(k.decode_v, k.attn_v_batched, read_reserve_knobs().force_batched, batch, heads, head_dim, hidden, (l_cap + 31) / 32 * 32, attn_chunking(heads), out);
     return ER_OK;
 }
 
@@ -451,7 +452,7 @@ extern "C" int er_kv_reserve(er_ctx* c, int batch, int max_len) {
 static int kv_alloc(er_ctx* c, KvMem& m, int batch, int Lcap) {
     const er_config& g = c->cfg;
     const int H = g.num_heads, D = c->D, hid = g.hidden_dim;
-    m.plan = make_decode_plan(c->knobs, read_reserve_knobs(), c->fast, batch, Lcap, g.num_layers, H, D, hid, attn_chunking(H, c->fast));
+    m.plan = make_decode_plan(c->knobs, read_reserve_knobs(), c->fast, batch, Lcap, g.num_layers, H, D, hid, attn_chunking(H));
     const DecodePlan& p = m.plan;
     const size_t kv_bytes = (size_t)p.kv_lstride * g.num_layers * c->kv_esz;
     ERCHK(m.kc.ensure(kv_bytes));
@@ -508,23 +509,17 @@ static int kv_alloc(er_ctx* c, KvMem& m, int batch, int Lcap) {
 // ------------------------------------------------------------------------------------ decode step
 static AttnDecArgs attn_args(er_ctx* c, int layer) {
     const DecodePlan& p = c->kv->plan;
-    AttnDecArgs a{};
+    AttnDecArgs a = attn_dec_args(c->cfg.num_heads, c->D, p.Lcap);
     a.q = c->kv->qbuf.p;
     a.kcache = c->kv->kc.p + (long long)layer * p.kv_lstride * c->kv_esz;
     a.vcache = c->kv->vc.p + (long long)layer * p.kv_lstride * c->kv_esz;
-    a.chunk = attn_chunk(ATTN_STEPS_DEFAULT, c->fast);
+    a.chunk = attn_chunk(ATTN_STEPS_DEFAULT);
     a.pos = c->kv->st.pos;
     a.fixed_len = c->prof_len;
-    a.len_dev = nullptr;
     a.part = c->kv->part.p;
     a.part_ml = c->kv->part_ml.p;
     a.out = c->kv->abuf.p;
-    a.H = c->cfg.num_heads;
-    a.l_cap = p.Lcap;
     a.S = p.S_splits;
-    a.hidden = c->cfg.hidden_dim;
-    a.kv_bstride = p.kv_bstride;
-    a.sqrt_d = sqrtf((float)c->D);
     a.out_xt = p.outproj_partials ? c->kv->xt_att.p : nullptr;      // out_proj then reads the tiled image
     return a;
 }
@@ -1615,16 +1610,15 @@ extern "C" int er_k_attn_decode(const float* q, const void* k, const void* v, co
     if (head_dim != 96 && head_dim != 64) return fail(ER_ERR_UNSUPPORTED, "head_dim %d", head_dim);
     if (steps != 2 && steps != 4 && steps != 8) return fail(ER_ERR_INVALID, "steps must be 2, 4 or 8 (chunk = 32*steps keys)");
     hipStream_t st = (hipStream_t)stream;
-    const int S = attn_num_chunks(l_cap, attn_chunk(steps, kv_half != 0));
+    const int S = attn_num_chunks(l_cap, attn_chunk(steps));
     DevBuf<int> len_dev;
     DevBuf<float> part;
     ERCHK(len_dev.ensure(B));
     ERCHK(part.ensure((size_t)B * heads * S * (head_dim + 2)));
     HIPCHK(hipMemcpy(len_dev.p, len_host, B * sizeof(int), hipMemcpyHostToDevice));
-    AttnDecArgs a{};
+    AttnDecArgs a = attn_dec_args(heads, head_dim, l_cap);
     a.q = q; a.kcache = k; a.vcache = v; a.len_dev = len_dev.p; a.part = part.p; a.out = out;
-    a.H = heads; a.l_cap = l_cap; a.S = S; a.hidden = heads * head_dim; a.chunk = attn_chunk(steps, kv_half != 0);
-    a.kv_bstride = (long long)heads * l_cap * head_dim; a.sqrt_d = sqrtf((float)head_dim);
+    a.S = S; a.chunk = attn_chunk(steps);
     hipError_t e;
     if (variant == ER_ATTN_STREAM) {       // the streaming kernel of the batched decode step (no partials)
         e = launch_attn_stream_d<96>(a, kv_half != 0, B, st);
@@ -1648,9 +1642,8 @@ extern "C" int er_k_attn_stream_xt(const float* q, const void* k, const void* v,
     DevBuf<int> len_dev;
     ERCHK(len_dev.ensure(B));
     HIPCHK(hipMemcpy(len_dev.p, len_host, B * sizeof(int), hipMemcpyHostToDevice));
-    AttnDecArgs a{};
+    AttnDecArgs a = attn_dec_args(heads, D, l_cap);
     a.q = q; a.kcache = k; a.vcache = v; a.len_dev = len_dev.p; a.out = out; a.out_xt = out_xt;      // as attn_args: xt_att when out_proj reads the tiled image
-    a.H = heads; a.l_cap = l_cap; a.hidden = heads * D; a.kv_bstride = (long long)heads * l_cap * D; a.sqrt_d = sqrtf((float)D);
     hipError_t e = launch_attn_stream_d<D>(a, kv_half != 0, B, st);      // launch_kind_t case 1, stream_attn
     hipError_t e2 = hipStreamSynchronize(st);
     HIPRET(e);
@@ -1779,9 +1772,8 @@ extern "C" int er_k_attn_outproj3(const float* q, const void* k, const void* v, 
     DevBuf<float> blk;                         // partial outputs, then their {m, l}
     ERCHK(blk.ensure((size_t)H * nch * (D + 2)));
     float *part = blk.p, *part_ml = part + (size_t)H * nch * D;
-    AttnDecArgs a{};
+    AttnDecArgs a = attn_dec_args(H, D, l_cap);
     a.q = q; a.kcache = k; a.vcache = v; a.fixed_len = len; a.part = part; a.part_ml = part_ml;
-    a.H = H; a.l_cap = l_cap; a.hidden = H * D; a.kv_bstride = (long long)H * l_cap * D; a.sqrt_d = sqrtf((float)D);
     hipError_t e = launch_attn_partial3_d<D>(a, kv_half != 0, nch, 1, st);
     OutMergeArgs m{};
     m.W = wo; m.bias = bo; m.resid = resid; m.out = y; m.part_o = part; m.part_ml = part_ml; m.N = H * D;

@@ -18,11 +18,7 @@
 #pragma once
 #include "er_common.h"
 #include "k_gemv.h"
-
-// timeline hooks of scripts/probes/attn_timeline_probe.hip (expand to nothing in the library build)
-#ifndef ER_TP
-#define ER_TP(i)
-#endif
+#include "k_attn_lanes.h"
 
 namespace er {
 
@@ -51,92 +47,26 @@ __device__ __forceinline__ int attn_len(const AttnDecArgs& a, int b) {
     return a.pos[b] + 1;
 }
 
-// 16 bytes of a key row as EPL floats
-template <typename KT> struct KVec;
-template <> struct KVec<float> { static constexpr int EPL = 4, LPK = 8; };      // 8 lanes x NV float4 per key row
-template <> struct KVec<_Float16> { static constexpr int EPL = 8, LPK = 4; };   // 4 lanes x NV (8 x fp16) per key row
-
-template <typename KT>
-__device__ __forceinline__ void kv_unpack(const f32x4& raw, float (&f)[KVec<KT>::EPL]) {
-    if constexpr (sizeof(KT) == 4) {
-        f[0] = raw.x; f[1] = raw.y; f[2] = raw.z; f[3] = raw.w;
-    } else {
-        typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-        const h8 h = __builtin_bit_cast(h8, raw);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) f[i] = (float)h[i];
-    }
-}
-
-// ---- fp16 cache: lanes mapped over PAIRS of key rows (round 5).
-//
-// A row of the fp16 cache is 96 halves = 192 bytes = one and a half 128-byte lines.  The first fp16 mapping gave a row to 4 lanes x
-// 3 loads, so load j of a wave read the j-th 64-byte THIRD of 16 rows: sixteen half-used lines per wave-instruction, every line
-// requested by two instructions - 12 % below the rate of whole-line requests at the same bytes (5.8 vs 5.15 us for 25 MB, 6.3 vs
-// 7.2 TB/s incremental: scripts/probes/attn_load_pattern_probe.hip, profiles/r05_attn_load_pattern_probe.log; the fp32 cache's
-// 384-byte rows already are whole lines and measure like a contiguous stream).  Two consecutive rows starting at an EVEN key are
-// 384 bytes = three whole lines, so 8 lanes x 3 loads take a pair (A, B): lane p of the group reads the p-th 16 bytes of line j.
-// In units of 8-half chunks ("parts" 0..11 of a row):
-//     load 0: row A part p          load 1: p < 4 ? row A part 8 + p : row B part p - 4          load 2: row B part 4 + p
-// Scores: a = t0 + (p < 4 ? t1 : 0), b = (p < 4 ? 0 : t1) + t2 summed over the 8 lanes; weights: pA on load 0, pA / pB on load 1,
-// pB on load 2.  Every part is accumulated by two (lane, load) slots 4 lanes apart; hpair_fold() adds them with row_ror:4.
-struct HPair {
-    int p; bool lo; int part1;
-    __device__ __forceinline__ explicit HPair(int lane) : p(lane & 7), lo((lane & 7) < 4), part1((lane & 7) < 4 ? 8 + (lane & 7) : (lane & 7) - 4) {}
-};
-
-__device__ __forceinline__ void hpair_load_q(const float* qp, const HPair& hp, float (&qv)[3][8]) {
-    const int part[3] = {hp.p, hp.part1, 4 + hp.p};
-#pragma unroll
-    for (int j = 0; j < 3; ++j)
-#pragma unroll
-        for (int e = 0; e < 8; e += 4) {
-            const f32x4 t = *reinterpret_cast<const f32x4*>(qp + part[j] * 8 + e);
-            qv[j][e] = t.x; qv[j][e + 1] = t.y; qv[j][e + 2] = t.z; qv[j][e + 3] = t.w;
-        }
-}
-// rA / rB: the rows this lane reads for key A / key B of its pair (a masked key reads a valid row: its weight is 0)
-__device__ __forceinline__ void hpair_load(const _Float16* base, int rA, int rB, const HPair& hp, f32x4 (&r)[3]) {
-    r[0] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(base + (long long)rA * 96 + hp.p * 8));
-    r[1] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(base + (long long)(hp.lo ? rA : rB) * 96 + hp.part1 * 8));
-    r[2] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(base + (long long)rB * 96 + (4 + hp.p) * 8));
-}
-__device__ __forceinline__ float hpair_dot8(const f32x4& raw, const float (&q)[8]) {
-    float f[8];
-    kv_unpack<_Float16>(raw, f);
-    float acc = 0.f;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) acc = fmaf(q[e], f[e], acc);
-    return acc;
-}
-__device__ __forceinline__ void hpair_scores(const f32x4 (&k)[3], const float (&qv)[3][8], const HPair& hp, float& sA, float& sB) {
-    const float t0 = hpair_dot8(k[0], qv[0]), t1 = hpair_dot8(k[1], qv[1]), t2 = hpair_dot8(k[2], qv[2]);
-    sA = lane_group_sum<8>(t0 + (hp.lo ? t1 : 0.f));
-    sB = lane_group_sum<8>((hp.lo ? 0.f : t1) + t2);
-}
-__device__ __forceinline__ void hpair_accum(const f32x4 (&v)[3], float pA, float pB, const HPair& hp, float (&o)[3][8]) {
-    const float w[3] = {pA, hp.lo ? pA : pB, pB};
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        float f[8];
-        kv_unpack<_Float16>(v[j], f);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) o[j][e] = fmaf(w[j], f[e], o[j][e]);
-    }
-}
-// o[j][e] already summed over the two lane groups of the row of 16 (o += row_ror<8>(o)): main = part p (all 8 lanes), hi = part 8 + p
-// (lanes p < 4 only)
-__device__ __forceinline__ void hpair_fold(const float (&o)[3][8], const HPair& hp, float (&main)[8], float (&hi)[8]) {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        main[e] = o[0][e] + row_ror<4>(hp.lo ? o[2][e] : o[1][e]);     // a lane hands its receiver (4 lanes below) what THAT lane lacks
-        hi[e] = o[1][e] + row_ror<4>(o[2][e]);
-    }
+// the fields that follow from the cache's shape [B][heads][l_cap][D]; every caller adds its pointers, lengths and chunking
+inline AttnDecArgs attn_dec_args(int heads, int D, int l_cap) {
+    AttnDecArgs a{};
+    a.H = heads; a.l_cap = l_cap; a.hidden = heads * D;
+    a.kv_bstride = (long long)heads * l_cap * D;
+    a.sqrt_d = sqrtf((float)D);
+    return a;
 }
 
 // grid (S, H, B), 256 threads.  LPK lanes cover one key row with NV 16-byte loads each (full 128-byte
 // lines per wave-instruction); a wave step covers 64/LPK keys, the workgroup chunk is 4*STEPS*(64/LPK) keys:
 // wave w, step i, lane group g -> key k0 + KPS*i + KPW*w + g.
+//
+// This is the round-1 kernel, kept statement for statement: ONE softmax over the workgroup (block_max / block_sum, six barriers), and an
+// order of its own that disagrees with what round 2 found for the kernels below: the K/V loads go BEFORE the q
+// load, the row form's loads are plain rather than nontemporal and there is no sched_barrier behind the loads.  Without that barrier
+// hipcc's schedule of this kernel moves with any textual change - handing only the q loader to KMap::load_q moves an instantiation by
+// six VGPRs - so it is NOT written over KMap / attn_wave_pass like the three kernels below: it uses the mapping's parts (KVec,
+// kv_unpack, HPair, hpair_*) directly, and a change of the cache layout, the mask or the score scale has to be made here as well.
+// Rewriting it is a performance change, to be measured as one.
 template <typename KT, int D, int STEPS>
 __global__ __launch_bounds__(ER_WG) void attn_decode_kernel(AttnDecArgs a) {
     constexpr int EPL = KVec<KT>::EPL, LPK = KVec<KT>::LPK;
@@ -324,190 +254,32 @@ __global__ __launch_bounds__(ER_WG) void attn_decode_kernel(AttnDecArgs a) {
 // critical path instead of six (block_max + block_sum + the output combine).
 template <typename KT, int D, int STEPS>
 __global__ __launch_bounds__(ER_WG) void attn_decode2_kernel(AttnDecArgs a) {
-    constexpr int EPL = KVec<KT>::EPL, LPK = KVec<KT>::LPK;
-    constexpr int NV = D / (EPL * LPK);
-    constexpr int KPW = 64 / LPK;
-    constexpr int KPS = ER_NWAVES * KPW;
-    constexpr int CHUNK = KPS * STEPS;
-    static_assert(D % (EPL * LPK) == 0, "head_dim must tile into 16-byte loads");
+    using M = KMap<KT, D>;
+    constexpr int CHUNK = ER_NWAVES * M::KPW * STEPS;
     __shared__ __attribute__((aligned(16))) float ored[ER_NWAVES * 4 * D];     // [wave][row of 16 lanes][dim]
     __shared__ float wm[ER_NWAVES], wl[ER_NWAVES];
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    const int p = lane & (LPK - 1), g = lane / LPK;
+    const int tid = threadIdx.x;
+    const M m(tid & 63);
     const int h = blockIdx.x, s = blockIdx.y, b = blockIdx.z;
     const int len = attn_len(a, b);
-    const int k0 = s * CHUNK;
+    const int k0 = s * CHUNK;                 // a multiple of the chunk: even, as the pair mapping needs it
     if (k0 >= len) return;
     const int k1 = min(len, k0 + CHUNK);
     const long long head_off = (long long)b * a.kv_bstride + (long long)h * a.l_cap * D;
     const KT* kb = reinterpret_cast<const KT*>(a.kcache) + head_off;
     const KT* vb = reinterpret_cast<const KT*>(a.vcache) + head_off;
-
-    if constexpr (sizeof(KT) == 2 && D == 96) {
-        // fp16 cache, 192-byte rows: the PAIR mapping (whole 128-byte lines, see above); k0 is a multiple of the chunk = even
-        const HPair hp(lane);
-        const int g8 = lane >> 3;
-        float qh[3][8];
-        hpair_load_q(a.q + (long long)b * a.hidden + h * D, hp, qh);
-        f32x4 kreg[STEPS][3], vreg[STEPS][3];
-        bool vA[STEPS], vB[STEPS];
-#pragma unroll
-        for (int i = 0; i < STEPS; ++i) {
-            const int kA = k0 + KPS * i + KPW * wid + 2 * g8;
-            vA[i] = kA < k1;
-            vB[i] = kA + 1 < k1;
-            hpair_load(kb, vA[i] ? kA : k0, vB[i] ? kA + 1 : k0, hp, kreg[i]);
-        }
-#pragma unroll
-        for (int i = 0; i < STEPS; ++i) {
-            const int kA = k0 + KPS * i + KPW * wid + 2 * g8;
-            hpair_load(vb, vA[i] ? kA : k0, vB[i] ? kA + 1 : k0, hp, vreg[i]);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        float scA[STEPS], scB[STEPS];
-        float mloc = -INFINITY;
-#pragma unroll
-        for (int i = 0; i < STEPS; ++i) {
-            float sA, sB;
-            hpair_scores(kreg[i], qh, hp, sA, sB);
-            scA[i] = vA[i] ? sA / a.sqrt_d : -INFINITY;
-            scB[i] = vB[i] ? sB / a.sqrt_d : -INFINITY;
-            mloc = fmaxf(mloc, fmaxf(scA[i], scB[i]));
-        }
-        const float m = wave_max(mloc);           // -inf when the wave holds no valid key
-        float oh[3][8];
-#pragma unroll
-        for (int j = 0; j < 3; ++j)
-#pragma unroll
-            for (int e = 0; e < 8; ++e) oh[j][e] = 0.f;
-        float lloc = 0.f;
-#pragma unroll
-        for (int i = 0; i < STEPS; ++i) {
-            const float pA = vA[i] ? expf(scA[i] - m) : 0.f, pB = vB[i] ? expf(scB[i] - m) : 0.f;
-            if (hp.p == 0) lloc += pA + pB;
-            hpair_accum(vreg[i], pA, pB, hp, oh);
-        }
-        const float l = wave_sum(lloc);
-#pragma unroll
-        for (int j = 0; j < 3; ++j)
-#pragma unroll
-            for (int e = 0; e < 8; ++e) oh[j][e] += row_ror<8>(oh[j][e]);
-        float om[8], ohi[8];
-        hpair_fold(oh, hp, om, ohi);
-        if ((lane & 15) < 8) {
-            float* dst = ored + (wid * 4 + (lane >> 4)) * D;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) dst[hp.p * 8 + e] = om[e];
-            if (hp.lo) {
-#pragma unroll
-                for (int e = 0; e < 8; ++e) dst[(8 + hp.p) * 8 + e] = ohi[e];
-            }
-        }
-        if (lane == 0) { wm[wid] = m; wl[wid] = l; }
-    } else {
-    // this lane's query elements first: vector loads return in issue order, so anything issued behind the K/V
-        // stream would only become usable after ALL of it has landed
-        float qv[NV][EPL];
-        const float* qp = a.q + (long long)b * a.hidden + h * D;
-#pragma unroll
-        for (int j = 0; j < NV; ++j)
-#pragma unroll
-            for (int e = 0; e < EPL; e += 4) {
-                const f32x4 t = *reinterpret_cast<const f32x4*>(qp + (j * LPK + p) * EPL + e);
-                qv[j][e] = t.x; qv[j][e + 1] = t.y; qv[j][e + 2] = t.z; qv[j][e + 3] = t.w;
-            }
-        f32x4 kreg[STEPS][NV], vreg[STEPS][NV];
-        bool valid[STEPS];
-#pragma unroll
-        for (int i = 0; i < STEPS; ++i) {
-            const int kk = k0 + KPS * i + KPW * wid + g;
-            valid[i] = kk < k1;
-            const f32x4* kr = reinterpret_cast<const f32x4*>(kb + (long long)(valid[i] ? kk : k0) * D);
-#pragma unroll
-            for (int j = 0; j < NV; ++j) kreg[i][j] = __builtin_nontemporal_load(kr + j * LPK + p);
-        }
-#pragma unroll
-        for (int i = 0; i < STEPS; ++i) {
-            const int kk = k0 + KPS * i + KPW * wid + g;
-            const f32x4* vr = reinterpret_cast<const f32x4*>(vb + (long long)(valid[i] ? kk : k0) * D);
-#pragma unroll
-            for (int j = 0; j < NV; ++j) vreg[i][j] = __builtin_nontemporal_load(vr + j * LPK + p);
-        }
-        __builtin_amdgcn_sched_barrier(0);        // every K and V load is issued before the first score is computed
-
-        float sc[STEPS];
-        float mloc = -INFINITY;
-#pragma unroll
-        for (int i = 0; i < STEPS; ++i) {
-            float acc = 0.f;
-#pragma unroll
-            for (int j = 0; j < NV; ++j) {
-                float kf[EPL];
-                kv_unpack<KT>(kreg[i][j], kf);
-#pragma unroll
-                for (int e = 0; e < EPL; ++e) acc = fmaf(qv[j][e], kf[e], acc);
-            }
-            acc = lane_group_sum<LPK>(acc);
-            sc[i] = valid[i] ? acc / a.sqrt_d : -INFINITY;
-            mloc = fmaxf(mloc, sc[i]);
-        }
-        const float m = wave_max(mloc);           // -inf when the wave holds no valid key (ragged tail of the last chunk)
-
-        float pw[STEPS];
-        float lloc = 0.f;
-#pragma unroll
-        for (int i = 0; i < STEPS; ++i) {
-            pw[i] = valid[i] ? expf(sc[i] - m) : 0.f;
-            if (p == 0) lloc += pw[i];
-        }
-        const float l = wave_sum(lloc);
-
-        float o[NV][EPL];
-#pragma unroll
-        for (int j = 0; j < NV; ++j)
-#pragma unroll
-            for (int e = 0; e < EPL; ++e) o[j][e] = 0.f;
-#pragma unroll
-        for (int i = 0; i < STEPS; ++i)
-#pragma unroll
-            for (int j = 0; j < NV; ++j) {
-                float vf[EPL];
-                kv_unpack<KT>(vreg[i][j], vf);
-#pragma unroll
-                for (int e = 0; e < EPL; ++e) o[j][e] = fmaf(pw[i], vf[e], o[j][e]);
-            }
-        // key groups sit LPK lanes apart: add them inside each row of 16 lanes with DPP rotations (VALU, no LDS crossbar), and
-        // leave the four rows of a wave to the LDS merge below (round 2a did all of it with 36 / 96 ds_bpermutes per lane)
-#pragma unroll
-        for (int j = 0; j < NV; ++j)
-#pragma unroll
-            for (int e = 0; e < EPL; ++e) {
-                o[j][e] += row_ror<8>(o[j][e]);
-                if (LPK == 4) o[j][e] += row_ror<4>(o[j][e]);
-            }
-        if ((lane & 15) < LPK) {
-            float* dst = ored + (wid * 4 + (lane >> 4)) * D;
-#pragma unroll
-            for (int j = 0; j < NV; ++j)
-#pragma unroll
-                for (int e = 0; e < EPL; ++e) dst[(j * LPK + p) * EPL + e] = o[j][e];
-        }
-        if (lane == 0) { wm[wid] = m; wl[wid] = l; }
-    }
+    // this lane's query elements first: vector loads return in issue order, so anything issued behind the K/V stream would only
+    // become usable after ALL of it has landed
+    float qv[M::NV][M::EPL];
+    m.load_q(a.q + (long long)b * a.hidden + h * D, qv);
+    attn_wave_pass<KT, D, STEPS, ER_NWAVES, D>(a, kb, vb, qv, k0, k1, ored, wm, wl);
     __syncthreads();
     if (tid < D) {
-        const float M = fmaxf(fmaxf(wm[0], wm[1]), fmaxf(wm[2], wm[3]));   // finite: the chunk holds at least one key
-        float ov = 0.f, lv = 0.f;
-#pragma unroll
-        for (int k = 0; k < ER_NWAVES; ++k) {
-            const float w = (wm[k] == -INFINITY) ? 0.f : expf(wm[k] - M);
-            const float* src = ored + k * 4 * D + tid;
-            ov = fmaf((src[0] + src[D]) + (src[2 * D] + src[3 * D]), w, ov);
-            lv = fmaf(wl[k], w, lv);
-        }
+        float ov, lv, mx;
+        attn_merge4<D>(ored, wm, wl, tid, ov, lv, mx);
         float* pout = a.part + (((long long)b * a.H + h) * a.S + s) * (D + 2);
         pout[2 + tid] = ov;
-        if (tid == 0) { pout[0] = M; pout[1] = lv; }
+        if (tid == 0) { pout[0] = mx; pout[1] = lv; }
     }
 }
 
@@ -585,100 +357,6 @@ __global__ __launch_bounds__(ER_WG) void attn_combine2_kernel(AttnDecArgs a) {
 constexpr int A3_LD = 97;     // row stride of the wave partials in LDS (D + 1: lanes that read a column down the rows hit 32 different banks)
 
 template <int D, int NW>
-__device__ __forceinline__ void attn3_merge_rows(float* ored, const float* wm, const float* wl, float* po, float* pml);
-
-template <typename KT, int D, int NS, int NW>
-__device__ __forceinline__ void attn3_body(const AttnDecArgs& a, const KT* kb, const KT* vb,
-                                           const float (&qv)[D / (KVec<KT>::EPL * KVec<KT>::LPK)][KVec<KT>::EPL], int k0, int k1,
-                                           float* ored, float* wm, float* wl, float* po, float* pml) {
-    constexpr int EPL = KVec<KT>::EPL, LPK = KVec<KT>::LPK;
-    constexpr int NV = D / (EPL * LPK);
-    constexpr int KPW = 64 / LPK;
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    const int p = lane & (LPK - 1), g = lane / LPK;
-    f32x4 kreg[NS][NV], vreg[NS][NV];
-    bool valid[NS];
-#pragma unroll
-    for (int i = 0; i < NS; ++i) {
-        const int kk = k0 + (i * NW + wid) * KPW + g;
-        valid[i] = kk < k1;
-        const f32x4* kr = reinterpret_cast<const f32x4*>(kb + (long long)(valid[i] ? kk : k0) * D);
-#pragma unroll
-        for (int j = 0; j < NV; ++j) kreg[i][j] = __builtin_nontemporal_load(kr + j * LPK + p);
-    }
-#pragma unroll
-    for (int i = 0; i < NS; ++i) {
-        const int kk = k0 + (i * NW + wid) * KPW + g;
-        const f32x4* vr = reinterpret_cast<const f32x4*>(vb + (long long)(valid[i] ? kk : k0) * D);
-#pragma unroll
-        for (int j = 0; j < NV; ++j) vreg[i][j] = __builtin_nontemporal_load(vr + j * LPK + p);
-    }
-    __builtin_amdgcn_sched_barrier(0);
-    ER_TP(2);
-
-    float sc[NS];
-    float mloc = -INFINITY;
-#pragma unroll
-    for (int i = 0; i < NS; ++i) {
-        float acc = 0.f;
-#pragma unroll
-        for (int j = 0; j < NV; ++j) {
-            float kf[EPL];
-            kv_unpack<KT>(kreg[i][j], kf);
-#pragma unroll
-            for (int e = 0; e < EPL; ++e) acc = fmaf(qv[j][e], kf[e], acc);
-        }
-        acc = lane_group_sum<LPK>(acc);
-        sc[i] = valid[i] ? acc / a.sqrt_d : -INFINITY;
-        mloc = fmaxf(mloc, sc[i]);
-    }
-    const float m = wave_max(mloc);           // -inf when the wave holds no valid key
-    ER_TP(3);
-    float pw[NS];
-    float lloc = 0.f;
-#pragma unroll
-    for (int i = 0; i < NS; ++i) {
-        pw[i] = valid[i] ? expf(sc[i] - m) : 0.f;
-        if (p == 0) lloc += pw[i];
-    }
-    const float l = wave_sum(lloc);
-    float o[NV][EPL];
-#pragma unroll
-    for (int j = 0; j < NV; ++j)
-#pragma unroll
-        for (int e = 0; e < EPL; ++e) o[j][e] = 0.f;
-#pragma unroll
-    for (int i = 0; i < NS; ++i)
-#pragma unroll
-        for (int j = 0; j < NV; ++j) {
-            float vf[EPL];
-            kv_unpack<KT>(vreg[i][j], vf);
-#pragma unroll
-            for (int e = 0; e < EPL; ++e) o[j][e] = fmaf(pw[i], vf[e], o[j][e]);
-        }
-    ER_TP(4);
-#pragma unroll
-    for (int j = 0; j < NV; ++j)
-#pragma unroll
-        for (int e = 0; e < EPL; ++e) {
-            o[j][e] += row_ror<8>(o[j][e]);
-            if (LPK == 4) o[j][e] += row_ror<4>(o[j][e]);
-        }
-    if ((lane & 15) < LPK) {
-        float* dst = ored + (wid * 4 + (lane >> 4)) * A3_LD;
-#pragma unroll
-        for (int j = 0; j < NV; ++j)
-#pragma unroll
-            for (int e = 0; e < EPL; ++e) dst[(j * LPK + p) * EPL + e] = o[j][e];
-    }
-    if (lane == 0) { wm[wid] = m; wl[wid] = l; }
-    __syncthreads();
-    ER_TP(5);
-    attn3_merge_rows<D, NW>(ored, wm, wl, po, pml);
-    ER_TP(7);
-}
-
-template <int D, int NW>
 __device__ __forceinline__ void attn3_merge_rows(float* ored, const float* wm, const float* wl, float* po, float* pml) {
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     // ONE barrier: the 4 * NW = 64 row partials {wave k, row r of 16 lanes} of a column meet in the 64 lanes of ONE wave - wave w
@@ -720,80 +398,15 @@ __device__ __forceinline__ void attn3_merge_rows(float* ored, const float* wm, c
     }
     if (tid == 63) { pml[0] = M; pml[1] = acc[CPW]; }
 }
-// the fp16-cache body of the balanced kernel on the PAIR mapping above (k0 even: the chunk length of the fp16 kernel is rounded up to
-// an even number of keys); everything behind the row partials - the one-barrier merge of the 4 * NW rows - is shared with the fp32 body
-template <int D, int NS, int NW>
-__device__ __forceinline__ void attn3_body_h(const AttnDecArgs& a, const _Float16* kb, const _Float16* vb, const float (&qv)[3][8], int k0, int k1,
-                                             float* ored, float* wm, float* wl, float* po, float* pml) {
-    static_assert(D == 96, "pair mapping: 96 halves per row");
-    constexpr int KPW = 16;
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    const HPair hp(lane);
-    const int g = lane >> 3;
-    f32x4 kreg[NS][3], vreg[NS][3];
-    bool vA[NS], vB[NS];
-#pragma unroll
-    for (int i = 0; i < NS; ++i) {
-        const int kA = k0 + (i * NW + wid) * KPW + 2 * g;
-        vA[i] = kA < k1;
-        vB[i] = kA + 1 < k1;
-        hpair_load(kb, vA[i] ? kA : k0, vB[i] ? kA + 1 : k0, hp, kreg[i]);
-    }
-#pragma unroll
-    for (int i = 0; i < NS; ++i) {
-        const int kA = k0 + (i * NW + wid) * KPW + 2 * g;
-        hpair_load(vb, vA[i] ? kA : k0, vB[i] ? kA + 1 : k0, hp, vreg[i]);
-    }
-    __builtin_amdgcn_sched_barrier(0);
-    ER_TP(2);
-    float scA[NS], scB[NS];
-    float mloc = -INFINITY;
-#pragma unroll
-    for (int i = 0; i < NS; ++i) {
-        float sA, sB;
-        hpair_scores(kreg[i], qv, hp, sA, sB);
-        scA[i] = vA[i] ? sA / a.sqrt_d : -INFINITY;
-        scB[i] = vB[i] ? sB / a.sqrt_d : -INFINITY;
-        mloc = fmaxf(mloc, fmaxf(scA[i], scB[i]));
-    }
-    const float m = wave_max(mloc);           // -inf when the wave holds no valid key
-    ER_TP(3);
-    float o[3][8];
-#pragma unroll
-    for (int j = 0; j < 3; ++j)
-#pragma unroll
-        for (int e = 0; e < 8; ++e) o[j][e] = 0.f;
-    float lloc = 0.f;
-#pragma unroll
-    for (int i = 0; i < NS; ++i) {
-        const float pA = vA[i] ? expf(scA[i] - m) : 0.f, pB = vB[i] ? expf(scB[i] - m) : 0.f;
-        if (hp.p == 0) lloc += pA + pB;
-        hpair_accum(vreg[i], pA, pB, hp, o);
-    }
-    const float l = wave_sum(lloc);
-    ER_TP(4);
-#pragma unroll
-    for (int j = 0; j < 3; ++j)
-#pragma unroll
-        for (int e = 0; e < 8; ++e) o[j][e] += row_ror<8>(o[j][e]);
-    float om[8], oh[8];
-    hpair_fold(o, hp, om, oh);
-    if ((lane & 15) < 8) {
-        float* dst = ored + (wid * 4 + (lane >> 4)) * A3_LD;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) dst[hp.p * 8 + e] = om[e];
-        if (hp.lo) {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) dst[(8 + hp.p) * 8 + e] = oh[e];
-        }
-    }
-    if (lane == 0) { wm[wid] = m; wl[wid] = l; }
+
+// behind a chunk's wave pass: ONE barrier, then the merge of the 4 * NW row partials
+template <int D, int NW>
+__device__ __forceinline__ void attn3_finish(float* ored, float* wm, float* wl, float* po, float* pml) {
     __syncthreads();
     ER_TP(5);
     attn3_merge_rows<D, NW>(ored, wm, wl, po, pml);
     ER_TP(7);
 }
-
 // Argument list: the length word's address, q, the cache and partial pointers and the two length integers lead as SCALARS (preloaded
 // into SGPRs at wave launch, see k_gemv.h gemv_kernel); the struct behind them supplies the rest, its copies of these fields are ignored.
 template <typename KT, int D, int STEPS, int NW>
@@ -801,7 +414,8 @@ __global__ __launch_bounds__(64 * NW) void attn_decode3_kernel(const int* plen, 
                                                                float* ppml, int pfixed, int padd, AttnDecArgs a_) {
     AttnDecArgs a = a_;
     a.len_src = plen; a.q = pq; a.kcache = pk; a.vcache = pv; a.part = ppart; a.part_ml = ppml; a.fixed_len = pfixed; a.len_add = padd;
-    constexpr int KPW = 64 / KVec<KT>::LPK;
+    using M = KMap<KT, D>;
+    constexpr int KPW = M::KPW;
     static_assert(NW == 16 && D % NW == 0 && D + 1 == A3_LD, "wave merge: the 4 * NW row partials of a column fill the 64 lanes of one wave");
     __shared__ __attribute__((aligned(16))) float ored[NW * 4 * A3_LD];
     __shared__ float wm[NW], wl[NW];
@@ -821,29 +435,18 @@ __global__ __launch_bounds__(64 * NW) void attn_decode3_kernel(const int* plen, 
         asm volatile("" ::"s"(p0), "s"(p1), "s"(p2), "s"(p3), "s"(p4), "s"(p5), "s"(s0), "s"(i0), "s"(i1), "s"(i2), "s"(i3), "s"(i4), "s"(f0));
     }
     const int lmem = a.len_src[b];
-    constexpr int EPL = KVec<KT>::EPL, LPK = KVec<KT>::LPK, NV = D / (EPL * LPK);
     float* po = a.part + (((long long)b * a.H + h) * nch + c) * D;
     float* pml = a.part_ml + (((long long)b * a.H + h) * nch + c) * 2;
     const long long head_off = (long long)b * a.kv_bstride + (long long)h * a.l_cap * D;
     const KT* kb = reinterpret_cast<const KT*>(a.kcache) + head_off;
     const KT* vb = reinterpret_cast<const KT*>(a.vcache) + head_off;
     const float* qp = a.q + (long long)b * a.hidden + h * D;
-    float qv[NV][EPL];
-    if constexpr (sizeof(KT) == 2) {
-        hpair_load_q(qp, HPair(threadIdx.x & 63), qv);          // pair mapping (fp16 cache): NV = 3 loads of EPL = 8 halves
-    } else {
-        const int p = threadIdx.x & (LPK - 1);
-#pragma unroll
-        for (int j = 0; j < NV; ++j)
-#pragma unroll
-            for (int e = 0; e < EPL; e += 4) {
-                const f32x4 t = *reinterpret_cast<const f32x4*>(qp + (j * LPK + p) * EPL + e);
-                qv[j][e] = t.x; qv[j][e + 1] = t.y; qv[j][e + 2] = t.z; qv[j][e + 3] = t.w;
-            }
-    }
+    const M m(threadIdx.x & 63);
+    float qv[M::NV][M::EPL];
+    m.load_q(qp, qv);
     const int len = a.fixed_len > 0 ? a.fixed_len : lmem + a.len_add;
     int clen = (len + nch - 1) >> __builtin_ctz(nch);            // <= STEPS * NW * KPW (the launcher checks l_cap and that nch is 16 / 32)
-    if constexpr (sizeof(KT) == 2) clen = (clen + 1) & ~1;       // fp16 cache: chunks start at even keys (a pair of rows = three whole lines)
+    if constexpr (M::NK == 2) clen = (clen + 1) & ~1;            // pair mapping: chunks start at even keys (a pair of rows = three whole lines)
     const int k0 = c * clen, k1 = min(len, k0 + clen);
     if (k0 >= k1) {                                        // empty chunk (len < nch): a partial the merge weighs with exp(-inf) = 0
         if (threadIdx.x < D) po[threadIdx.x] = 0.f;
@@ -852,15 +455,11 @@ __global__ __launch_bounds__(64 * NW) void attn_decode3_kernel(const int* plen, 
     }
     const int nsteps = (k1 - k0 + NW * KPW - 1) / (NW * KPW);      // workgroup-uniform
     ER_TP(1);
-    if constexpr (sizeof(KT) == 2) {
-        static_assert(sizeof(KT) != 2 || STEPS == 2, "fp16 cache: two wave-steps of 16 keys");
-        if (nsteps >= 2) attn3_body_h<D, 2, NW>(a, kb, vb, qv, k0, k1, ored, wm, wl, po, pml);
-        else attn3_body_h<D, 1, NW>(a, kb, vb, qv, k0, k1, ored, wm, wl, po, pml);
-    } else
-    if (STEPS >= 4 && nsteps >= 4) attn3_body<KT, D, (STEPS >= 4 ? 4 : 1), NW>(a, kb, vb, qv, k0, k1, ored, wm, wl, po, pml);
-    else if (STEPS >= 3 && nsteps == 3) attn3_body<KT, D, (STEPS >= 3 ? 3 : 1), NW>(a, kb, vb, qv, k0, k1, ored, wm, wl, po, pml);
-    else if (STEPS >= 2 && nsteps == 2) attn3_body<KT, D, (STEPS >= 2 ? 2 : 1), NW>(a, kb, vb, qv, k0, k1, ored, wm, wl, po, pml);
-    else attn3_body<KT, D, 1, NW>(a, kb, vb, qv, k0, k1, ored, wm, wl, po, pml);
+    const auto is = [nsteps](int n) { return n == STEPS ? nsteps >= n : nsteps == n; };      // (nsteps <= STEPS: the launcher checks l_cap)
+    if (STEPS >= 4 && is(4)) { attn_wave_pass<KT, D, (STEPS >= 4 ? 4 : 1), NW, A3_LD>(a, kb, vb, qv, k0, k1, ored, wm, wl); attn3_finish<D, NW>(ored, wm, wl, po, pml); }
+    else if (STEPS >= 3 && is(3)) { attn_wave_pass<KT, D, (STEPS >= 3 ? 3 : 1), NW, A3_LD>(a, kb, vb, qv, k0, k1, ored, wm, wl); attn3_finish<D, NW>(ored, wm, wl, po, pml); }
+    else if (STEPS >= 2 && is(2)) { attn_wave_pass<KT, D, (STEPS >= 2 ? 2 : 1), NW, A3_LD>(a, kb, vb, qv, k0, k1, ored, wm, wl); attn3_finish<D, NW>(ored, wm, wl, po, pml); }
+    else { attn_wave_pass<KT, D, 1, NW, A3_LD>(a, kb, vb, qv, k0, k1, ored, wm, wl); attn3_finish<D, NW>(ored, wm, wl, po, pml); }
 }
 
 constexpr int ATTN3_NW = 16;                   // waves per workgroup of the balanced kernel
@@ -896,156 +495,89 @@ inline hipError_t launch_attn_partial3_d(const AttnDecArgs& a_in, bool kv_half, 
 // up without rescaling: one DPP + LDS reduction at the very end, the four waves merged like four partials, and the
 // normalised head output written straight to out[b][h*D..] - no partials, no merge kernel.
 template <typename KT, int D, int STEPS>
-struct AttnTile { f32x4 k[STEPS][D / (KVec<KT>::EPL * KVec<KT>::LPK)], v[STEPS][D / (KVec<KT>::EPL * KVec<KT>::LPK)]; };
+struct AttnTile { f32x4 k[STEPS][KMap<KT, D>::NV], v[STEPS][KMap<KT, D>::NV]; };
 
+// wave-step i of a tile covers the KPW keys from kbase + (i * ER_NWAVES + wid) * KPW; a row past the end is clamped to len - 1 (never
+// reads the unused tail; its score is masked in attn_stream_reduce)
 template <typename KT, int D, int STEPS>
-__device__ __forceinline__ void attn_stream_load(AttnTile<KT, D, STEPS>& t, const KT* kb, const KT* vb, int kbase, int len, int wid,
-                                                 int g, int p) {
-    constexpr int EPL = KVec<KT>::EPL, LPK = KVec<KT>::LPK, NV = D / (EPL * LPK), KPW = 64 / LPK;
-    if constexpr (sizeof(KT) == 2) {              // fp16 cache: pair mapping (whole 128-byte lines), kbase is a multiple of the tile = even
-        const int lane = g * LPK + p;
-        const HPair hp(lane);
+__device__ __forceinline__ void attn_stream_load(AttnTile<KT, D, STEPS>& t, const KMap<KT, D>& m, const KT* kb, const KT* vb, int kbase, int len, int wid) {
+    using M = KMap<KT, D>;
 #pragma unroll
-        for (int i = 0; i < STEPS; ++i) {
-            const int kA = kbase + (i * ER_NWAVES + wid) * KPW + 2 * (lane >> 3);
-            hpair_load(kb, max(0, min(kA, len - 1)), max(0, min(kA + 1, len - 1)), hp, t.k[i]);
-        }
+    for (int i = 0; i < STEPS; ++i) {
+        int row[M::NK];
 #pragma unroll
-        for (int i = 0; i < STEPS; ++i) {
-            const int kA = kbase + (i * ER_NWAVES + wid) * KPW + 2 * (lane >> 3);
-            hpair_load(vb, max(0, min(kA, len - 1)), max(0, min(kA + 1, len - 1)), hp, t.v[i]);
-        }
-        return;
+        for (int n = 0; n < M::NK; ++n) row[n] = max(0, min(kbase + (i * ER_NWAVES + wid) * M::KPW + m.key0() + n, len - 1));
+        m.load(kb, row, t.k[i]);
     }
 #pragma unroll
     for (int i = 0; i < STEPS; ++i) {
-        const int kk = max(0, min(kbase + (i * ER_NWAVES + wid) * KPW + g, len - 1));    // clamped: never reads the unused tail
-        const f32x4* kr = reinterpret_cast<const f32x4*>(kb + (long long)kk * D);
+        int row[M::NK];
 #pragma unroll
-        for (int j = 0; j < NV; ++j) t.k[i][j] = __builtin_nontemporal_load(kr + j * LPK + p);
-    }
-#pragma unroll
-    for (int i = 0; i < STEPS; ++i) {
-        const int kk = max(0, min(kbase + (i * ER_NWAVES + wid) * KPW + g, len - 1));
-        const f32x4* vr = reinterpret_cast<const f32x4*>(vb + (long long)kk * D);
-#pragma unroll
-        for (int j = 0; j < NV; ++j) t.v[i][j] = __builtin_nontemporal_load(vr + j * LPK + p);
+        for (int n = 0; n < M::NK; ++n) row[n] = max(0, min(kbase + (i * ER_NWAVES + wid) * M::KPW + m.key0() + n, len - 1));
+        m.load(vb, row, t.v[i]);
     }
 }
 
 template <typename KT, int D, int STEPS>
-__device__ __forceinline__ void attn_stream_reduce(const AttnTile<KT, D, STEPS>& t, const float (&qv)[D / (KVec<KT>::EPL * KVec<KT>::LPK)][KVec<KT>::EPL],
-                                                   int kbase, int len, int wid, int g, int p, float sqrt_d, float& m_run, float& l_lane,
-                                                   float (&o)[D / (KVec<KT>::EPL * KVec<KT>::LPK)][KVec<KT>::EPL]) {
-    constexpr int EPL = KVec<KT>::EPL, LPK = KVec<KT>::LPK, NV = D / (EPL * LPK), KPW = 64 / LPK;
-    if constexpr (sizeof(KT) == 2) {              // fp16 cache: pair mapping, two keys (A, B) per 8 lanes
-        const int lane = g * LPK + p;
-        const HPair hp(lane);
-        float scA[STEPS], scB[STEPS];
-        float mloc = -INFINITY;
-#pragma unroll
-        for (int i = 0; i < STEPS; ++i) {
-            const int kA = kbase + (i * ER_NWAVES + wid) * KPW + 2 * (lane >> 3);
-            float sA, sB;
-            hpair_scores(t.k[i], qv, hp, sA, sB);
-            scA[i] = kA < len ? sA / sqrt_d : -INFINITY;
-            scB[i] = kA + 1 < len ? sB / sqrt_d : -INFINITY;
-            mloc = fmaxf(mloc, fmaxf(scA[i], scB[i]));
-        }
-        const float m_new = fmaxf(m_run, wave_max(mloc));
-        if (m_new == -INFINITY) return;
-        const float alpha = expf(m_run - m_new);
-        float pA[STEPS], pB[STEPS];
-        float ladd = 0.f;
-#pragma unroll
-        for (int i = 0; i < STEPS; ++i) {
-            pA[i] = expf(scA[i] - m_new);
-            pB[i] = expf(scB[i] - m_new);
-            ladd += pA[i] + pB[i];
-        }
-        l_lane = fmaf(l_lane, alpha, hp.p == 0 ? ladd : 0.f);
-#pragma unroll
-        for (int j = 0; j < NV; ++j)
-#pragma unroll
-            for (int e = 0; e < EPL; ++e) o[j][e] *= alpha;
-#pragma unroll
-        for (int i = 0; i < STEPS; ++i) hpair_accum(t.v[i], pA[i], pB[i], hp, o);
-        m_run = m_new;
-        return;
-    }
-    float sc[STEPS];
+__device__ __forceinline__ void attn_stream_reduce(const AttnTile<KT, D, STEPS>& t, const KMap<KT, D>& m, const float (&qv)[KMap<KT, D>::NV][KMap<KT, D>::EPL],
+                                                   int kbase, int len, int wid, float sqrt_d, float& m_run, float& l_lane,
+                                                   float (&o)[KMap<KT, D>::NV][KMap<KT, D>::EPL]) {
+    using M = KMap<KT, D>;
+    constexpr int NV = M::NV, EPL = M::EPL, NK = M::NK;
+    float sc[STEPS][NK];
     float mloc = -INFINITY;
 #pragma unroll
     for (int i = 0; i < STEPS; ++i) {
-        float acc = 0.f;
-#pragma unroll
-        for (int j = 0; j < NV; ++j) {
-            float kf[EPL];
-            kv_unpack<KT>(t.k[i][j], kf);
-#pragma unroll
-            for (int e = 0; e < EPL; ++e) acc = fmaf(qv[j][e], kf[e], acc);
+        const int kk = kbase + (i * ER_NWAVES + wid) * M::KPW + m.key0();
+        float d[NK];
+        m.dots(t.k[i], qv, d);
+        if constexpr (NK == 2) {                  // written out per key, as in attn_wave_pass
+            sc[i][0] = kk < len ? d[0] / sqrt_d : -INFINITY;
+            sc[i][1] = kk + 1 < len ? d[1] / sqrt_d : -INFINITY;
+            mloc = fmaxf(mloc, fmaxf(sc[i][0], sc[i][1]));
+        } else {
+            sc[i][0] = kk < len ? d[0] / sqrt_d : -INFINITY;
+            mloc = fmaxf(mloc, sc[i][0]);
         }
-        acc = lane_group_sum<LPK>(acc);
-        const bool valid = kbase + (i * ER_NWAVES + wid) * KPW + g < len;
-        sc[i] = valid ? acc / sqrt_d : -INFINITY;
-        mloc = fmaxf(mloc, sc[i]);
     }
     const float m_new = fmaxf(m_run, wave_max(mloc));
     if (m_new == -INFINITY) return;                      // wave-uniform: this wave has not seen a valid key yet
     const float alpha = expf(m_run - m_new);             // exp(-inf) = 0 on the first tile with keys
-    float pw[STEPS];
+    float pw[STEPS][NK];
     float ladd = 0.f;
 #pragma unroll
     for (int i = 0; i < STEPS; ++i) {
-        pw[i] = expf(sc[i] - m_new);                     // 0 for masked keys
-        ladd += pw[i];
+#pragma unroll
+        for (int n = 0; n < NK; ++n) pw[i][n] = expf(sc[i][n] - m_new);     // 0 for masked keys
+        ladd += M::wsum(pw[i]);
     }
-    l_lane = fmaf(l_lane, alpha, p == 0 ? ladd : 0.f);   // each key counted once (the LPK lanes of a key hold the same score)
+    l_lane = fmaf(l_lane, alpha, m.counts() ? ladd : 0.f);   // each key counted once (the lanes of a key hold the same score)
 #pragma unroll
     for (int j = 0; j < NV; ++j)
 #pragma unroll
         for (int e = 0; e < EPL; ++e) o[j][e] *= alpha;
 #pragma unroll
-    for (int i = 0; i < STEPS; ++i)
-#pragma unroll
-        for (int j = 0; j < NV; ++j) {
-            float vf[EPL];
-            kv_unpack<KT>(t.v[i][j], vf);
-#pragma unroll
-            for (int e = 0; e < EPL; ++e) o[j][e] = fmaf(pw[i], vf[e], o[j][e]);
-        }
+    for (int i = 0; i < STEPS; ++i) m.accum(t.v[i], pw[i], o);
     m_run = m_new;
 }
 
 template <typename KT, int D, int STEPS>
 __global__ __launch_bounds__(ER_WG) void attn_stream_kernel(AttnDecArgs a) {
-    static_assert(sizeof(KT) != 2 || D == 96, "fp16 cache: the pair mapping of this kernel is written for 192-byte rows");
-    constexpr int EPL = KVec<KT>::EPL, LPK = KVec<KT>::LPK;
-    constexpr int NV = D / (EPL * LPK);
-    constexpr int KPW = 64 / LPK;
-    constexpr int TILE = ER_NWAVES * STEPS * KPW;        // keys per workgroup iteration
+    using M = KMap<KT, D>;
+    static_assert(sizeof(KT) != 2 || M::NK == 2, "fp16 cache: tiles must start at even keys, which only the pair mapping (192-byte rows) asks for");
+    constexpr int NV = M::NV, EPL = M::EPL;
+    constexpr int TILE = ER_NWAVES * STEPS * M::KPW;     // keys per workgroup iteration
     __shared__ __attribute__((aligned(16))) float ored[ER_NWAVES * 4 * D];
     __shared__ float wm[ER_NWAVES], wl[ER_NWAVES];
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    const int p = lane & (LPK - 1), g = lane / LPK;
+    const M m(lane);
     const int h = blockIdx.x, b = blockIdx.y;
     const int len = attn_len(a, b);
     const long long head_off = (long long)b * a.kv_bstride + (long long)h * a.l_cap * D;
     const KT* kb = reinterpret_cast<const KT*>(a.kcache) + head_off;
     const KT* vb = reinterpret_cast<const KT*>(a.vcache) + head_off;
     float qv[NV][EPL];
-    const float* qp = a.q + (long long)b * a.hidden + h * D;
-    if constexpr (sizeof(KT) == 2) {
-        hpair_load_q(qp, HPair(lane), qv);
-    } else {
-#pragma unroll
-        for (int j = 0; j < NV; ++j)
-#pragma unroll
-            for (int e = 0; e < EPL; e += 4) {
-                const f32x4 t = *reinterpret_cast<const f32x4*>(qp + (j * LPK + p) * EPL + e);
-                qv[j][e] = t.x; qv[j][e + 1] = t.y; qv[j][e + 2] = t.z; qv[j][e + 3] = t.w;
-            }
-    }
+    m.load_q(a.q + (long long)b * a.hidden + h * D, qv);
     float o[NV][EPL];
 #pragma unroll
     for (int j = 0; j < NV; ++j)
@@ -1055,56 +587,26 @@ __global__ __launch_bounds__(ER_WG) void attn_stream_kernel(AttnDecArgs a) {
 
     const int nt = (len + TILE - 1) / TILE;               // >= 1
     AttnTile<KT, D, STEPS> ta, tb;
-    attn_stream_load<KT, D, STEPS>(ta, kb, vb, 0, len, wid, g, p);
+    attn_stream_load<KT, D, STEPS>(ta, m, kb, vb, 0, len, wid);
     for (int t = 0; t < nt; t += 2) {
-        attn_stream_load<KT, D, STEPS>(tb, kb, vb, (t + 1) * TILE, len, wid, g, p);   // past the end: every lane re-reads row len-1 (one L1 line set)
+        attn_stream_load<KT, D, STEPS>(tb, m, kb, vb, (t + 1) * TILE, len, wid);   // past the end: every lane re-reads row len-1 (one L1 line set)
         __builtin_amdgcn_sched_barrier(0);
-        attn_stream_reduce<KT, D, STEPS>(ta, qv, t * TILE, len, wid, g, p, a.sqrt_d, m_run, l_lane, o);
+        attn_stream_reduce<KT, D, STEPS>(ta, m, qv, t * TILE, len, wid, a.sqrt_d, m_run, l_lane, o);
         __builtin_amdgcn_sched_barrier(0);
-        attn_stream_load<KT, D, STEPS>(ta, kb, vb, (t + 2) * TILE, len, wid, g, p);
+        attn_stream_load<KT, D, STEPS>(ta, m, kb, vb, (t + 2) * TILE, len, wid);
         __builtin_amdgcn_sched_barrier(0);
-        if (t + 1 < nt) attn_stream_reduce<KT, D, STEPS>(tb, qv, (t + 1) * TILE, len, wid, g, p, a.sqrt_d, m_run, l_lane, o);
+        if (t + 1 < nt) attn_stream_reduce<KT, D, STEPS>(tb, m, qv, (t + 1) * TILE, len, wid, a.sqrt_d, m_run, l_lane, o);
         __builtin_amdgcn_sched_barrier(0);
     }
 
     // ---- the wave's lane groups share m_run: add their accumulators (rows of 16 lanes by DPP, the rest through LDS)
-#pragma unroll
-    for (int j = 0; j < NV; ++j)
-#pragma unroll
-        for (int e = 0; e < EPL; ++e) o[j][e] += row_ror<8>(o[j][e]);
     const float l = wave_sum(l_lane);
-    if constexpr (sizeof(KT) == 2) {          // pair mapping: every part sits in two (lane, load) slots 4 lanes apart
-        const HPair hp(lane);
-        float om[8], oh[8];
-        hpair_fold(o, hp, om, oh);
-        if ((lane & 15) < 8) {
-            float* dst = ored + (wid * 4 + (lane >> 4)) * D;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) dst[hp.p * 8 + e] = om[e];
-            if (hp.lo) {
-#pragma unroll
-                for (int e = 0; e < 8; ++e) dst[(8 + hp.p) * 8 + e] = oh[e];
-            }
-        }
-    } else if ((lane & 15) < LPK) {
-        float* dst = ored + (wid * 4 + (lane >> 4)) * D;
-#pragma unroll
-        for (int j = 0; j < NV; ++j)
-#pragma unroll
-            for (int e = 0; e < EPL; ++e) dst[(j * LPK + p) * EPL + e] = o[j][e];
-    }
+    attn_fold_store<D>(m, o, ored, wid, lane);
     if (lane == 0) { wm[wid] = m_run; wl[wid] = l; }
     __syncthreads();
     if (tid < D) {
-        const float M = fmaxf(fmaxf(wm[0], wm[1]), fmaxf(wm[2], wm[3]));   // finite: len >= 1
-        float ov = 0.f, lv = 0.f;
-#pragma unroll
-        for (int k = 0; k < ER_NWAVES; ++k) {
-            const float w = (wm[k] == -INFINITY) ? 0.f : expf(wm[k] - M);
-            const float* src = ored + k * 4 * D + tid;
-            ov = fmaf((src[0] + src[D]) + (src[2 * D] + src[3 * D]), w, ov);
-            lv = fmaf(wl[k], w, lv);
-        }
+        float ov, lv, mx;                                 // mx is finite: len >= 1
+        attn_merge4<D>(ored, wm, wl, tid, ov, lv, mx);
         const float r = ov / lv;
         a.out[(long long)b * a.hidden + h * D + tid] = r;
         if (a.out_xt) {        // element k = h D + tid of row b: halves (k & 3) [hi] and 4 + (k & 3) [lo] of entry (k >> 2, b)
@@ -1126,33 +628,27 @@ inline hipError_t launch_attn_stream_d(const AttnDecArgs& a, bool kv_half, int B
 }
 
 constexpr int ATTN_STEPS_DEFAULT = 4;          // fp32 KV: 128 keys per workgroup
-inline int attn_chunk(int steps, bool /*kv_half*/) { return 32 * steps; }   // fp16 KV: 64 keys/step x steps/2
+inline int attn_chunk(int steps) { return 32 * steps; }   // keys per workgroup; fp16 KV: 64 keys/step x steps/2
 inline int attn_num_chunks(int l_cap, int chunk) { return (l_cap + chunk - 1) / chunk; }
 
+// one (dtype, steps) instantiation of the fixed-chunk split kernels: version 2 = per-wave softmax, otherwise the round-1 kernel
+template <typename KT, int D, int NS>
+inline void launch_attn_partial_t(const AttnDecArgs& a, dim3 grid, hipStream_t st, int version) {
+    if (version == 2) hipLaunchKernelGGL((attn_decode2_kernel<KT, D, NS>), grid, dim3(ER_WG), 0, st, a);
+    else hipLaunchKernelGGL((attn_decode_kernel<KT, D, NS>), grid, dim3(ER_WG), 0, st, a);
+}
 // `steps` is the fp32 step count (chunk = 32*steps keys); fp16 KV uses half as many steps for the same chunk.
 template <int D>
 inline hipError_t launch_attn_partial_d(const AttnDecArgs& a, int steps, bool kv_half, int B, hipStream_t st, int version = 2) {
-    const dim3 grid(a.H, a.S, B), blk(ER_WG);      // heads fastest: XCD = head mod 8 (see attn_decode_kernel)
-    if (version == 2) {
-        if (!kv_half) {
-            if (steps == 2) hipLaunchKernelGGL((attn_decode2_kernel<float, D, 2>), grid, blk, 0, st, a);
-            else if (steps == 8) hipLaunchKernelGGL((attn_decode2_kernel<float, D, 8>), grid, blk, 0, st, a);
-            else hipLaunchKernelGGL((attn_decode2_kernel<float, D, 4>), grid, blk, 0, st, a);
-        } else {
-            if (steps == 2) hipLaunchKernelGGL((attn_decode2_kernel<_Float16, D, 1>), grid, blk, 0, st, a);
-            else if (steps == 8) hipLaunchKernelGGL((attn_decode2_kernel<_Float16, D, 4>), grid, blk, 0, st, a);
-            else hipLaunchKernelGGL((attn_decode2_kernel<_Float16, D, 2>), grid, blk, 0, st, a);
-        }
-        return hipGetLastError();
-    }
+    const dim3 grid(a.H, a.S, B);                  // heads fastest: XCD = head mod 8 (see attn_decode_kernel)
     if (!kv_half) {
-        if (steps == 2) hipLaunchKernelGGL((attn_decode_kernel<float, D, 2>), grid, blk, 0, st, a);
-        else if (steps == 8) hipLaunchKernelGGL((attn_decode_kernel<float, D, 8>), grid, blk, 0, st, a);
-        else hipLaunchKernelGGL((attn_decode_kernel<float, D, 4>), grid, blk, 0, st, a);
+        if (steps == 2) launch_attn_partial_t<float, D, 2>(a, grid, st, version);
+        else if (steps == 8) launch_attn_partial_t<float, D, 8>(a, grid, st, version);
+        else launch_attn_partial_t<float, D, 4>(a, grid, st, version);
     } else {
-        if (steps == 2) hipLaunchKernelGGL((attn_decode_kernel<_Float16, D, 1>), grid, blk, 0, st, a);
-        else if (steps == 8) hipLaunchKernelGGL((attn_decode_kernel<_Float16, D, 4>), grid, blk, 0, st, a);
-        else hipLaunchKernelGGL((attn_decode_kernel<_Float16, D, 2>), grid, blk, 0, st, a);
+        if (steps == 2) launch_attn_partial_t<_Float16, D, 1>(a, grid, st, version);
+        else if (steps == 8) launch_attn_partial_t<_Float16, D, 4>(a, grid, st, version);
+        else launch_attn_partial_t<_Float16, D, 2>(a, grid, st, version);
     }
     return hipGetLastError();
 }

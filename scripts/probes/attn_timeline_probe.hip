@@ -37,7 +37,7 @@ __global__ __launch_bounds__(64 * ATTN3_NW) void attn3_timed(AttnDecArgs a) {
     // same body as attn_decode3_kernel (k_attn_decode.h), which cannot be called as a function: restated dispatch (round-2 form of the
     // entry: the library kernel now batches its argument loads and hoists the length-independent work), shared arrays here
     constexpr int D = 96, NW = ATTN3_NW;
-    constexpr int KPW = 64 / KVec<KT>::LPK;
+    constexpr int KPW = KMap<KT, D>::KPW;
     __shared__ __attribute__((aligned(16))) float ored[NW * 4 * A3_LD];
     __shared__ float wm[NW], wl[NW];
     ER_TP(0);
@@ -58,34 +58,19 @@ __global__ __launch_bounds__(64 * ATTN3_NW) void attn3_timed(AttnDecArgs a) {
     const KT* kb = reinterpret_cast<const KT*>(a.kcache) + head_off;
     const KT* vb = reinterpret_cast<const KT*>(a.vcache) + head_off;
     const float* qp = a.q + (long long)b * a.hidden + h * D;
-    constexpr int EPL = KVec<KT>::EPL, LPK = KVec<KT>::LPK, NV = D / (EPL * LPK);
-    float qv[NV][EPL];
-    if constexpr (sizeof(KT) == 2) {
-        hpair_load_q(qp, HPair(threadIdx.x & 63), qv);          // round 5: the fp16 cache's pair mapping
-    } else {
-        const int p = threadIdx.x & (LPK - 1);
-#pragma unroll
-        for (int j = 0; j < NV; ++j)
-#pragma unroll
-            for (int e = 0; e < EPL; e += 4) {
-                const f32x4 t = *reinterpret_cast<const f32x4*>(qp + (j * LPK + p) * EPL + e);
-                qv[j][e] = t.x; qv[j][e + 1] = t.y; qv[j][e + 2] = t.z; qv[j][e + 3] = t.w;
-            }
-    }
+    float qv[KMap<KT, D>::NV][KMap<KT, D>::EPL];
+    KMap<KT, D>(threadIdx.x & 63).load_q(qp, qv);
     const int len = NEWENTRY ? (a.fixed_len > 0 ? a.fixed_len : lmem + a.len_add) : len_old;
     int clen = NEWENTRY ? ((len + nch - 1) >> __builtin_ctz(nch)) : (len + nch - 1) / nch;
     if constexpr (sizeof(KT) == 2) clen = (clen + 1) & ~1;
     const int k0 = c * clen, k1 = min(len, k0 + clen);
     const int nsteps = (k1 - k0 + NW * KPW - 1) / (NW * KPW);
     ER_TP(1);
-    if constexpr (sizeof(KT) == 2) {
-        if (nsteps >= 2) attn3_body_h<D, 2, NW>(a, kb, vb, qv, k0, k1, ored, wm, wl, po, pml);
-        else attn3_body_h<D, 1, NW>(a, kb, vb, qv, k0, k1, ored, wm, wl, po, pml);
-    } else
-    if (STEPS >= 4 && nsteps >= 4) attn3_body<KT, D, (STEPS >= 4 ? 4 : 1), NW>(a, kb, vb, qv, k0, k1, ored, wm, wl, po, pml);
-    else if (STEPS >= 3 && nsteps == 3) attn3_body<KT, D, (STEPS >= 3 ? 3 : 1), NW>(a, kb, vb, qv, k0, k1, ored, wm, wl, po, pml);
-    else if (STEPS >= 2 && nsteps == 2) attn3_body<KT, D, (STEPS >= 2 ? 2 : 1), NW>(a, kb, vb, qv, k0, k1, ored, wm, wl, po, pml);
-    else attn3_body<KT, D, 1, NW>(a, kb, vb, qv, k0, k1, ored, wm, wl, po, pml);
+    const auto is = [nsteps](int n) { return n == STEPS ? nsteps >= n : nsteps == n; };      // as attn_decode3_kernel
+    if (STEPS >= 4 && is(4)) { attn_wave_pass<KT, D, (STEPS >= 4 ? 4 : 1), NW, A3_LD>(a, kb, vb, qv, k0, k1, ored, wm, wl); attn3_finish<D, NW>(ored, wm, wl, po, pml); }
+    else if (STEPS >= 3 && is(3)) { attn_wave_pass<KT, D, (STEPS >= 3 ? 3 : 1), NW, A3_LD>(a, kb, vb, qv, k0, k1, ored, wm, wl); attn3_finish<D, NW>(ored, wm, wl, po, pml); }
+    else if (STEPS >= 2 && is(2)) { attn_wave_pass<KT, D, (STEPS >= 2 ? 2 : 1), NW, A3_LD>(a, kb, vb, qv, k0, k1, ored, wm, wl); attn3_finish<D, NW>(ored, wm, wl, po, pml); }
+    else { attn_wave_pass<KT, D, 1, NW, A3_LD>(a, kb, vb, qv, k0, k1, ored, wm, wl); attn3_finish<D, NW>(ored, wm, wl, po, pml); }
     if (threadIdx.x == 0) {
         unsigned long long* o = g_tp_out + ((long long)a.S * 256 + (blockIdx.x + 16 * blockIdx.y)) * 10;
         for (int i = 0; i < 10; ++i) o[i] = er_tp_dyn[i];

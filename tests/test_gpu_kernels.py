@@ -221,6 +221,29 @@ def test_attn_decode_streaming_kernel(half, lens):
         close(out[b], (w @ vc[b, :, :n].double()).reshape(H * D), 2e-6, 1e-5, f"streaming attn row {b} len {n}")
 
 
+@pytest.mark.parametrize("half", [False, True])
+@pytest.mark.parametrize("variant", ["split1", "split2", "stream"])
+def test_attn_decode_row_does_not_depend_on_its_batch(variant, half):
+    """A row's attention output is the same bits alone and as row 0 of a batch: workgroups are per (row, head, chunk) and read nothing
+    of other rows.  257 keys = one key in a third 128-key chunk and an odd tail in the fp16 cache's pair mapping; the other rows (33 and
+    2050 keys) have other chunk counts.  Same Lcap in both runs, unused tails NaN-poisoned."""
+    from edgerunner_amd import kernels as K, native
+    variant = {"split1": native.ER_ATTN_SPLIT1, "split2": native.ER_ATTN_SPLIT2, "stream": native.ER_ATTN_STREAM}[variant]
+    lens, H, D = [257, 33, 2050], 16, 96
+    B, Lcap = len(lens), 2112
+    q = rnd(B, H * D, seed=73)
+    kc, vc = rnd(B, H, Lcap, D, seed=74), rnd(B, H, Lcap, D, seed=75)
+    if half:
+        kc, vc = kc.half(), vc.half()
+    for b, n in enumerate(lens):
+        kc[b, :, n:] = float("nan")
+        vc[b, :, n:] = float("nan")
+    batch = K.attn_decode(q, kc, vc, lens, 4, variant)
+    alone = K.attn_decode(q[:1].contiguous(), kc[:1].contiguous(), vc[:1].contiguous(), lens[:1], 4, variant)
+    assert not torch.isnan(alone).any()
+    assert torch.equal(alone[0], batch[0])
+
+
 @pytest.mark.parametrize("length,lcap,kv16,w16", [(1, 64, False, False), (17, 64, False, False), (129, 160, False, False),
                                                   (2051, 6080, False, False), (4097, 6080, False, False),
                                                   (6049, 6080, False, False), (8192, 8192, False, False),
