@@ -19,6 +19,7 @@
 #include "er_common.h"
 #include "k_attn_lanes.h"
 #include "k_attn_decode.h"
+#include "k_attn_shared.h"
 #include "k_outproj_merge.h"
 #include "k_flash_attn_f16s.h"
 #include "k_gemm.h"
@@ -131,6 +132,11 @@ struct KvMem {
     DevBuf<int> d_row_budget;     // [B] token budget per row: INT_MAX (= er_decode's max_new_tokens decides) outside the queue mode
     DevBuf<long long> d_out_ids;  // [B][Lcap] generated ids (graph writes here; copied to the caller at the end)
     hipGraphExec_t step_exec = nullptr;  // hipGraph of one step
+    // prefix groups (er_set_prefix_groups; prefix_len == 0: none): the leader of every row, and for the prefix pass the rows of every group,
+    // group after group with the leader first, behind the groups' offsets
+    std::vector<int> grp_leader;
+    int prefix_len = 0, n_groups = 0;
+    DevBuf<int> grp_rows, grp_off, grp_leader_dev, grp_followers, grp_first;
     KvMem() = default;
     KvMem(const KvMem&) = delete;
     KvMem& operator=(const KvMem&) = delete;
@@ -437,7 +443,7 @@ extern "C" int er_kv_reserve(er_ctx* c, int batch, int max_len) {
     if (max_len > g.max_positions)
         return fail(ER_ERR_CAPACITY, "max_len %d exceeds the position table (%d)", max_len, g.max_positions);
     const int Lcap = (max_len + 31) / 32 * 32;
-    if (c->kv->plan.B == batch && c->kv->plan.Lcap == Lcap) return ER_OK;
+    if (c->kv->plan.B == batch && c->kv->plan.Lcap == Lcap) return c->kv->prefix_len ? er_set_prefix_groups(c, nullptr, 0, 0) : ER_OK;
     HIPCHK(hipDeviceSynchronize());
     c->kv = std::make_unique<KvMem>();           // first: the old shape's memory makes room for the new one (this plan says: no cache)
     c->have_hidden = false;
@@ -524,6 +530,16 @@ static AttnDecArgs attn_args(er_ctx* c, int layer) {
     return a;
 }
 
+// the two launches of a layer under prefix groups: the partials of the prefix chunks live in KvMem::part (ceil(P / 128) <= S_splits per (row, head))
+static AttnSharedArgs attn_shared_args(er_ctx* c, int layer) {
+    AttnSharedArgs s{};
+    s.a = attn_args(c, layer);
+    s.prefix_len = c->kv->prefix_len;
+    s.a.S = attn_shared_chunks(s.prefix_len);
+    s.grp_rows = c->kv->grp_rows.p; s.grp_off = c->kv->grp_off.p;
+    return s;
+}
+
 static hipError_t launch_attn_partial(const AttnDecArgs& a, int D, int steps, bool kv_half, int B, hipStream_t st, int ver = 2) {
     return D == 96 ? launch_attn_partial_d<96>(a, steps, kv_half, B, st, ver) : launch_attn_partial_d<64>(a, steps, kv_half, B, st, ver);
 }
@@ -580,10 +596,12 @@ static hipError_t launch_kind_t(er_ctx* c, int kind, int layer, hipStream_t st, 
         // worth of work (B > 4) the leaner v1 (66-74 VGPRs, 6-7 waves per SIMD) streams faster: 570 vs 636 us at B = 32, L = 18050
         case 1:
             if (p.v3) return launch_attn_partial3_d<96>(attn_args(c, layer), HALF, p.nch3, B, st);
+            if (p.shared_attn) return launch_attn_prefix_d<96>(attn_shared_args(c, layer), HALF, kv.n_groups, st);
             if (p.stream_attn) return launch_attn_stream_d<96>(attn_args(c, layer), HALF, B, st);
             return launch_attn_partial(attn_args(c, layer), c->D, ATTN_STEPS_DEFAULT, HALF, B, st, p.batched ? 1 : 2);
         case 2:
             if (!p.sel.merge_launch) return hipSuccess;      // the merge runs inside the out_proj kernel (version 3) / there are no partials (streaming)
+            if (p.shared_attn) return launch_attn_suffix_merge_d<96>(attn_shared_args(c, layer), HALF, B, st);
             return launch_attn_combine(attn_args(c, layer), c->D, B, st);
         case 3: {   // out_proj + bias + residual(h) -> ypre1
             const LayerW& L = c->layers[layer];
@@ -952,7 +970,9 @@ static int prefill_run(er_ctx* c, const float* embeds, int B, int S, hipStream_t
     ERCHK(c->p_y.ensure((size_t)M * H));
     ERCHK(c->p_f.ensure((size_t)M * I));
     float *h = c->p_h.p, *q = c->p_q.p, *a = c->p_a.p, *y = c->p_y.p, *f = c->p_f.p;
-    const int tail = prefill_tail_rows(c, M), Mm = M - tail;
+    // (under prefix groups every row takes the GEMM: the batch's last few positions through the GEMV kernels would give the last row other
+    // bits than its group, and the groups rest on same-input rows getting the same bits)
+    const int tail = c->kv->prefix_len ? 0 : prefill_tail_rows(c, M), Mm = M - tail;
     // the causal attention of a single prefix is split over two key ranges per query tile (k_flash_attn_f32.h, KSP; same rule as the launcher)
     bool attn_ksplit = false;
     if (!c->fast && flash32_ksplit(S, NH, B, D, true)) {
@@ -1038,15 +1058,94 @@ static int prefill_run(er_ctx* c, const float* embeds, int B, int S, hipStream_t
     return ER_OK;
 }
 
+// Behind a prefill with prefix groups: every follower's K/V [0, P) of all layers against its leader's, bit for bit, on the device.  Wrong
+// groups must be loud: the step would read the leader's prefix for a row that never had it.
+static int prefix_groups_check(er_ctx* c, hipStream_t st) {
+    KvMem& kv = *c->kv;
+    const DecodePlan& p = kv.plan;
+    const int followers = (int)kv.grp_followers.n;
+    if (!followers) return ER_OK;
+    PrefixCheckArgs a{};
+    a.kc = kv.kc.p; a.vc = kv.vc.p; a.followers = kv.grp_followers.p; a.leader = kv.grp_leader_dev.p;
+    a.head_bytes = (long long)p.Lcap * c->D * c->kv_esz; a.row_bytes = p.kv_bstride * c->kv_esz; a.layer_bytes = p.kv_lstride * c->kv_esz;
+    a.prefix_vecs = (long long)kv.prefix_len * c->D * c->kv_esz / 16;
+    a.layers = p.layers; a.first = kv.grp_first.p;
+    HIPCHK(hipMemsetAsync(kv.grp_first.p, 0x7f, sizeof(int), st));
+    HIPRET(launch_prefix_check(a, c->cfg.num_heads, followers, st));
+    int first = 0;
+    HIPCHK(hipMemcpyAsync(&first, kv.grp_first.p, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (first != 0x7f7f7f7f) {
+        c->have_hidden = false;
+        const int row = first / p.layers, layer = first % p.layers;
+        return fail(ER_ERR_INVALID, "er_prefill: prefix groups: the first %d cache positions of row %d differ from those of its leader, row %d, in layer %d "
+                    "(rows of one group need the same prefix; prefill again)", kv.prefix_len, row, kv.grp_leader[row], layer);
+    }
+    return ER_OK;
+}
+
 extern "C" int er_prefill(er_ctx* c, const float* embeds, int B, int S, void* stream) {
     ERCHK(forward_check(c, "er_prefill", embeds, B, S));
-    return prefill_run(c, embeds, B, S, pick(c, stream));
+    if (c->kv->prefix_len > S) return fail(ER_ERR_INVALID, "er_prefill: %d positions but the prefix groups share %d", S, c->kv->prefix_len);
+    ERCHK(prefill_run(c, embeds, B, S, pick(c, stream)));
+    return c->kv->prefix_len ? prefix_groups_check(c, pick(c, stream)) : ER_OK;
+}
+
+// ------------------------------------------------------------------------------------ prefix groups
+extern "C" int er_set_prefix_groups(er_ctx* c, const int32_t* leader, int n, int prefix_len) {
+    if (!c) return fail(ER_ERR_INVALID, "er_set_prefix_groups: null context");
+    KvMem& kv = *c->kv;
+    const int B = kv.plan.B;
+    if (B <= 0) return fail(ER_ERR_INVALID, "er_set_prefix_groups: no cache reserved (call er_kv_reserve)");
+    if (c->q.active) return fail(ER_ERR_INVALID, "er_set_prefix_groups: a queue is open on this context (er_queue_end first)");
+    const bool clear = !leader || prefix_len == 0;
+    if (clear && !kv.prefix_len) return ER_OK;
+    std::vector<int> rows, off, followers;
+    if (!clear) {
+        if (n != B) return fail(ER_ERR_INVALID, "er_set_prefix_groups: %d leaders for a batch of %d rows", n, B);
+        if (prefix_len < 1 || prefix_len >= kv.plan.Lcap) return fail(ER_ERR_INVALID, "er_set_prefix_groups: prefix_len %d outside [1, %d)", prefix_len, kv.plan.Lcap);
+        for (int b = 0; b < B; ++b) {
+            if (leader[b] < 0 || leader[b] > b) return fail(ER_ERR_INVALID, "er_set_prefix_groups: leader[%d] = %d outside [0, %d]", b, leader[b], b);
+            if (leader[leader[b]] != leader[b]) return fail(ER_ERR_INVALID, "er_set_prefix_groups: leader[%d] = %d is itself led by row %d (name the group's lowest row)", b, leader[b], leader[leader[b]]);
+        }
+        if (!shared_attn_supported(kv.plan.sel, c->D))
+            return fail(ER_ERR_UNSUPPORTED, "er_set_prefix_groups: prefix groups need the batched decode path (B > 4 or ER_FORCE_BATCHED=1) and head_dim 96; reserved: %d rows, head_dim %d", B, c->D);
+        for (int b = 0; b < B; ++b) {
+            if (leader[b] != b) { followers.push_back(b); continue; }
+            off.push_back((int)rows.size());
+            for (int r = b; r < B; ++r) if (leader[r] == b) rows.push_back(r);      // the leader first, then its followers in row order
+        }
+        off.push_back((int)rows.size());
+    }
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipDeviceSynchronize());           // a running step still reads the old tables
+    if (kv.step_exec) { hipGraphExecDestroy(kv.step_exec); kv.step_exec = nullptr; }      // the next step is captured with the new launches
+    const er_config& g = c->cfg;
+    kv.plan = make_decode_plan(c->knobs, kv.plan.rk, c->fast, B, kv.plan.Lcap, g.num_layers, g.num_heads, c->D, g.hidden_dim, attn_chunking(g.num_heads), !clear);
+    c->have_hidden = false;                   // groups come before the prefill whose cache they describe
+    kv.prefix_len = 0; kv.n_groups = 0; kv.grp_leader.clear();
+    kv.grp_followers = DevBuf<int>();
+    if (clear) return ER_OK;
+    ERCHK(kv.grp_rows.ensure(rows.size()));
+    ERCHK(kv.grp_off.ensure(off.size()));
+    ERCHK(kv.grp_leader_dev.ensure((size_t)B));
+    ERCHK(kv.grp_first.ensure(1));
+    if (!followers.empty()) ERCHK(kv.grp_followers.ensure(followers.size()));
+    HIPCHK(hipMemcpy(kv.grp_rows.p, rows.data(), rows.size() * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(kv.grp_off.p, off.data(), off.size() * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(kv.grp_leader_dev.p, leader, (size_t)B * sizeof(int), hipMemcpyHostToDevice));
+    if (!followers.empty()) HIPCHK(hipMemcpy(kv.grp_followers.p, followers.data(), followers.size() * sizeof(int), hipMemcpyHostToDevice));
+    kv.grp_leader.assign(leader, leader + B);
+    kv.n_groups = (int)off.size() - 1;
+    kv.prefix_len = prefix_len;
+    return ER_OK;
 }
 
 // ------------------------------------------------------------------------------------ scoring (LMM.forward, eval mode)
 extern "C" int er_score(er_ctx* c, const float* embeds, const int32_t* labels, int B, int S, float* nll_out, int32_t* pred_out,
                         float* logits_out, float* loss_out, void* stream) {
     ERCHK(forward_check(c, "er_score", embeds, B, S));
+    if (c->kv->prefix_len) return fail(ER_ERR_INVALID, "er_score: prefix groups are set on this context (clear them with er_set_prefix_groups(ctx, NULL, 0, 0))");
     if (!labels || !nll_out || !loss_out) return fail(ER_ERR_INVALID, "er_score: labels, nll_out and loss_out are required");
     hipStream_t st = pick(c, stream);
     ERCHK(prefill_run(c, embeds, B, S, st));
@@ -1275,6 +1374,7 @@ extern "C" int er_queue_begin(er_ctx* c, const er_decode_params* p, int check_ev
     if (c->q.active) return fail(ER_ERR_INVALID, "er_queue_begin: a queue is already open (er_queue_end first)");
     const int B = c->kv->plan.B, Lcap = c->kv->plan.Lcap;
     if (B <= 0) return fail(ER_ERR_INVALID, "er_queue_begin: no cache reserved (call er_kv_reserve)");
+    if (c->kv->prefix_len) return fail(ER_ERR_INVALID, "er_queue_begin: prefix groups are set on this context (clear them with er_set_prefix_groups(ctx, NULL, 0, 0))");
     if (p->max_new_tokens <= 0) return fail(ER_ERR_INVALID, "max_new_tokens must be > 0");
     if (p->mode != ER_GREEDY && p->mode != ER_SAMPLE) return fail(ER_ERR_INVALID, "bad mode");
     if (p->grammar < 0 || p->grammar > 2) return fail(ER_ERR_INVALID, "bad grammar");
@@ -1462,6 +1562,11 @@ static int profile_impl(er_ctx* c, int repeats, int use_graph, float* avg_us, do
     bytes[6] = ((double)V * H) * w + (double)B * (H + V) * w;
     bytes[7] = (double)B * V * w;
 
+    if (p.shared_attn) {   // kind 1 reads the prefix once per group and writes a partial per (row, head, chunk); kind 2 reads the suffixes and the partials
+        const double P = c->kv->prefix_len, parts = (double)B * g.num_heads * attn_shared_chunks(c->kv->prefix_len) * (c->D + 2) * 4.0;
+        bytes[1] = (double)c->kv->n_groups * 2.0 * P * H * w + parts;
+        bytes[2] = (double)B * 2.0 * std::max(0.0, len - P) * H * w + parts + (double)B * H * 4.0;
+    }
     if (p.v3) {   // the merge is part of the out_proj launch: its partial reads are charged there
         bytes[3] += (double)g.num_heads * p.nch3 * (c->D + 2) * 4.0;
         bytes[2] = 0.0;
@@ -1645,6 +1750,46 @@ extern "C" int er_k_attn_stream_xt(const float* q, const void* k, const void* v,
     AttnDecArgs a = attn_dec_args(heads, D, l_cap);
     a.q = q; a.kcache = k; a.vcache = v; a.len_dev = len_dev.p; a.out = out; a.out_xt = out_xt;      // as attn_args: xt_att when out_proj reads the tiled image
     hipError_t e = launch_attn_stream_d<D>(a, kv_half != 0, B, st);      // launch_kind_t case 1, stream_attn
+    hipError_t e2 = hipStreamSynchronize(st);
+    HIPRET(e);
+    HIPRET(e2);
+    return ER_OK;
+}
+
+extern "C" int er_k_attn_shared(const float* q, const void* k, const void* v, const int32_t* len_host, const int32_t* leader, int prefix_len,
+                                float* out, void* out_xt, int B, int heads, int l_cap, int kv_half, void* stream) {
+    constexpr int D = 96;
+    if (!q || !k || !v || !len_host || !leader || !out || B < 1 || heads < 1 || l_cap < 1) return fail(ER_ERR_INVALID, "er_k_attn_shared: bad argument");
+    if (prefix_len < 1 || prefix_len > l_cap) return fail(ER_ERR_INVALID, "er_k_attn_shared: prefix_len %d outside [1, %d]", prefix_len, l_cap);
+    std::vector<int> rows, off;
+    for (int b = 0; b < B; ++b) {
+        if (leader[b] < 0 || leader[b] > b || leader[leader[b]] != leader[b]) return fail(ER_ERR_INVALID, "er_k_attn_shared: leader[%d] = %d", b, leader[b]);
+        if (len_host[b] < prefix_len || len_host[b] > l_cap) return fail(ER_ERR_CAPACITY, "er_k_attn_shared: len[%d] = %d outside [%d, %d]", b, len_host[b], prefix_len, l_cap);
+    }
+    for (int b = 0; b < B; ++b) {
+        if (leader[b] != b) continue;
+        off.push_back((int)rows.size());
+        for (int r = b; r < B; ++r) if (leader[r] == b) rows.push_back(r);
+    }
+    off.push_back((int)rows.size());
+    hipStream_t st = (hipStream_t)stream;
+    DevBuf<int> len_dev, rows_dev, off_dev;
+    DevBuf<float> part;
+    AttnSharedArgs s{};
+    s.a = attn_dec_args(heads, D, l_cap);
+    s.prefix_len = prefix_len;
+    s.a.S = attn_shared_chunks(prefix_len);
+    ERCHK(len_dev.ensure(B));
+    ERCHK(rows_dev.ensure(rows.size()));
+    ERCHK(off_dev.ensure(off.size()));
+    ERCHK(part.ensure((size_t)B * heads * s.a.S * (D + 2)));
+    HIPCHK(hipMemcpy(len_dev.p, len_host, B * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(rows_dev.p, rows.data(), rows.size() * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(off_dev.p, off.data(), off.size() * sizeof(int), hipMemcpyHostToDevice));
+    s.a.q = q; s.a.kcache = k; s.a.vcache = v; s.a.len_dev = len_dev.p; s.a.part = part.p; s.a.out = out; s.a.out_xt = out_xt;
+    s.grp_rows = rows_dev.p; s.grp_off = off_dev.p;
+    hipError_t e = launch_attn_prefix_d<D>(s, kv_half != 0, (int)off.size() - 1, st);      // launch_kind_t kinds 1 and 2, shared_attn
+    if (e == hipSuccess) e = launch_attn_suffix_merge_d<D>(s, kv_half != 0, B, st);
     hipError_t e2 = hipStreamSynchronize(st);
     HIPRET(e);
     HIPRET(e2);

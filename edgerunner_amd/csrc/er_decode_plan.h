@@ -48,10 +48,12 @@ struct DecodePlan {
     bool mfma = false;          // batched and not valu: the projections run on the matrix cores and read the tiled weight copies
     bool xt = false;            // fast-mode batches read the tiled activation images (KvMem::xt_*); ER_XT=0 keeps the row-major fp32 inputs (A/B + parity matrix)
     bool stream_attn = false;   // batched, D == 96 and (forced or B*H >= 256: at least one streaming workgroup per CU)
+    bool shared_attn = false;   // prefix groups are set (er_set_prefix_groups; batched, D == 96): prefix pass + suffix / merge launch (k_attn_shared.h) in place of either batched kernel
+    ReserveKnobs rk{};          // the switches of the reserve, kept so that setting or clearing groups can derive the plan again
     bool v3 = false;            // decode_v == 3 and the reserved cache qualifies
     bool mlp_fused = false;     // mlp_v != 0, one row, not batched, hidden 1536: kinds 4 and 5 are the fused MLP launch and its finish
     bool outproj_rows8 = false; // mfma and 5..8 rows: out_proj is ONE pass of the VALU kernel (ER_FORM_ROWS8)
-    // xt, streaming attention and B > 8: the attention writes the tiled image xt_att, out_proj reads it and leaves SK_SLICES_OUTPROJ partials, fc1's LayerNorm launch finishes them
+    // xt, streaming (or shared) attention and B > 8: the attention writes the tiled image xt_att, out_proj reads it and leaves SK_SLICES_OUTPROJ partials, fc1's LayerNorm launch finishes them
     bool outproj_partials = false;
     // fc2 of `layer` leaves SK_SLICES_FC2 partials to the next layer's LayerNorm launch; the last layer finishes into ypre, which the lm_head reads
     bool fc2_defers(int layer) const { return xt && layer >= 0 && layer + 1 < layers; }
@@ -76,21 +78,29 @@ inline void plan_decode(int decode_v, int attn_v_batched, bool force_batched, in
     p->launches_per_layer = p->batched ? 0 : 5 + p->merge_launch;       // qkv, attention, (merge,) out_proj, fc1, fc2
 }
 
-// the plan of one (batch, Lcap) of a model with `layers` layers of H heads of D (hid = hidden width), `fast` = fp16 weights and cache
+// prefix groups need the batched class and the kernels' head_dim
+inline bool shared_attn_supported(const er_decode_plan& sel, int D) { return sel.batched != 0 && D == 96; }
+
+// the plan of one (batch, Lcap) of a model with `layers` layers of H heads of D (hid = hidden width), `fast` = fp16 weights and cache;
+// shared: prefix groups are set on the reserved batch (the caller has asked shared_attn_supported), which replaces the attention kernel
+// of plan_decode's shape-only rule by ER_ATTN_SHARED with its own merge launch
 inline DecodePlan make_decode_plan(const DecodeKnobs& k, const ReserveKnobs& rk, bool fast, int batch, int Lcap, int layers, int H, int D,
-                                   int hid, const AttnChunking& ch) {
+                                   int hid, const AttnChunking& ch, bool shared = false) {
     DecodePlan p;
     p.B = batch; p.Lcap = Lcap; p.layers = layers;
     p.kv_bstride = (long long)H * Lcap * D; p.kv_lstride = p.kv_bstride * batch;
     p.S_splits = (Lcap + ch.chunk - 1) / ch.chunk;   // decode attention: one workgroup per (row, head, chunk of 32*steps keys)
     p.nch3 = ch.nch3;
     p.force_batched = rk.force_batched; p.valu = rk.batched_valu;
+    p.rk = rk;
     plan_decode(k.decode_v, k.attn_v_batched, p.force_batched, batch, H, D, hid, Lcap, ch, &p.sel);
+    p.shared_attn = shared && shared_attn_supported(p.sel, D);
+    if (p.shared_attn) { p.sel.attn_kernel = ER_ATTN_SHARED; p.sel.merge_launch = 1; }
     p.batched = p.sel.batched != 0; p.mfma = p.batched && !p.valu; p.xt = fast && p.mfma && rk.xt;
     p.stream_attn = p.sel.attn_kernel == ER_ATTN_STREAM; p.v3 = p.sel.decode_version == 3;
     p.mlp_fused = k.mlp_v != 0 && batch == 1 && !p.batched && hid == 1536;      // the kernel's fixed widths (intermediate = 4 * hidden)
     p.outproj_rows8 = p.mfma && batch >= 5 && batch <= 8;
-    p.outproj_partials = p.xt && p.stream_attn && batch > 8;
+    p.outproj_partials = p.xt && (p.stream_attn || p.shared_attn) && batch > 8;      // the shared attention's last launch writes what the streaming kernel writes
     return p;
 }
 

@@ -11,6 +11,7 @@ num-face dropout) and the image conditioner are not part of this path.
 """
 from __future__ import annotations
 
+import os
 from typing import Dict, List, Optional
 
 import numpy as np
@@ -38,6 +39,15 @@ def score_row_groups(batch: int, seq_len: int, dims, max_rows: int = 1023) -> Li
         raise ValueError(f"one row of {seq_len} positions exceeds the 32-bit index range of the prefill ({seq_len} x {width})")
     per = min(per, max_rows)
     return [(b, min(b + per, batch)) for b in range(0, batch, per)]
+
+
+def prefix_leaders(conds) -> List[int]:
+    """The grouping behind ``share_prefix``: leaders[b] = the first row whose ``conds`` entry is bit-equal to row b's (b itself when
+    there is none before it).  ``conds`` is a tensor or array [B, ...]; equality is on the stored bits, so -0.0 and 0.0 differ and
+    a NaN equals the same NaN.  A pure function of the host copy of ``conds``."""
+    a = conds.detach().cpu().numpy() if isinstance(conds, torch.Tensor) else np.asarray(conds)
+    first: Dict[bytes, int] = {}
+    return [first.setdefault(np.ascontiguousarray(a[b]).tobytes(), b) for b in range(a.shape[0])]
 
 
 class _QueueJob:
@@ -324,8 +334,14 @@ class LMM:
     # -- generation ---------------------------------------------------------------------------
     @torch.no_grad()
     def generate_ids(self, conds, num_faces=1000, resume_ids=None, tokenizer=None, max_new_tokens=None,
-                     min_new_tokens: int = 0, seed: Optional[int] = None, row_streams=None) -> torch.Tensor:
-        """Everything of LMM.generate up to the HF call's return value (core/models.py:215-303)."""
+                     min_new_tokens: int = 0, seed: Optional[int] = None, row_streams=None, share_prefix: bool = False) -> torch.Tensor:
+        """Everything of LMM.generate up to the HF call's return value (core/models.py:215-303).
+
+        ``share_prefix=True``: rows whose ``conds`` entries are bit-equal (``prefix_leaders``) form a group, and every decode step reads
+        the group's cond + BOS prefix (num_cond_tokens + 1 cache positions; one ``num_faces`` per call, so ``resume_ids`` may differ
+        behind it) once from the first such row's cache instead of once per row (``er_set_prefix_groups``).  The tokens are those
+        of ``share_prefix=False`` up to the rounding of a different summation order.  It acts on the batched decode path only: with
+        B <= 4 and no ``ER_FORCE_BATCHED=1`` it has no effect."""
         opt = self.opt
         B = conds.shape[0]
         cond_embeds = self.encode_cond(conds, [num_faces] * B)["cond_embeds"]
@@ -346,6 +362,8 @@ class LMM:
         kwargs = dict(inputs_embeds=inputs_embeds, num_tokens=num_tokens, pad_token_id=opt.pad_token_id,
                       bos_token_id=opt.bos_token_id, eos_token_id=opt.eos_token_id, max_new_tokens=max_new_tokens,
                       prefix_allowed_tokens_fn=fn, min_new_tokens=min_new_tokens, seed=seed, row_streams=row_streams)
+        if share_prefix and (B > 4 or os.environ.get("ER_FORCE_BATCHED", "")[:1] == "1"):
+            kwargs["prefix_groups"] = (prefix_leaders(conds), opt.num_cond_tokens + 1)
         if opt.generate_mode == "greedy":
             kwargs["num_beams"] = 1
         elif opt.generate_mode == "sample":
@@ -403,12 +421,12 @@ class LMM:
 
     @torch.no_grad()
     def generate(self, conds, num_faces=1000, resume_ids=None, tokenizer=None, max_new_tokens=None, clean=True,
-                 min_new_tokens: int = 0, seed: Optional[int] = None, row_streams=None):
-        """-> (meshes, all_tokens) like core/models.py:204-319.  ``tokenizer`` is a
+                 min_new_tokens: int = 0, seed: Optional[int] = None, row_streams=None, share_prefix: bool = False):
+        """-> (meshes, all_tokens) like core/models.py:204-319.  ``share_prefix``: see ``generate_ids``.  ``tokenizer`` is a
         ``edgerunner_amd.meto.Engine`` (or None for the 9-coordinate layout); each mesh is a
         ``edgerunner_amd.meto.Mesh`` - ``.vertices``, ``.faces``, ``.export(path)``, the members the reference's callers
         use of the trimesh objects it returns (trimesh itself is absent here); it still unpacks as ``v, f = mesh``."""
-        output_ids = self.generate_ids(conds, num_faces, resume_ids, tokenizer, max_new_tokens, min_new_tokens, seed, row_streams)
+        output_ids = self.generate_ids(conds, num_faces, resume_ids, tokenizer, max_new_tokens, min_new_tokens, seed, row_streams, share_prefix)
         from .meto import Engine, save_mesh
         meshes: List[Optional[object]] = []
         all_tokens: List[np.ndarray] = []

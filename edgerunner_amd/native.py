@@ -32,14 +32,14 @@ EXPORTS = [
     "er_meto_decode", "er_meto_encode", "er_dit_create", "er_dit_destroy", "er_dit_load_tensor",
     "er_dit_finalize_weights", "er_dit_project_cond", "er_dit_encode_image", "er_dit_forward", "er_dit_sample",
     "er_dit_set_prediction_type", "er_dit_attach_point_encoder", "er_dit_point_latent", "er_dit_set_point_encoder_mode", "er_dit_loss", "er_k_dit_loss",
-    "er_set_row_streams", "er_plan_decode", "er_ctx_plan", "er_plan_gemm_tile", "er_kernel_kind_name", "er_profile_decode_kernels", "er_profile_decode_kernels_at", "er_last_decode_ms",
-    "er_k_gemv", "er_k_gemv_form", "er_k_mlp_transpose", "er_k_mlp_sparse", "er_mlp_nnz", "er_k_attn_decode", "er_k_attn_stream_xt", "er_k_attn_outproj3", "er_k_gemm", "er_k_gemm_f16", "er_k_gemm_hh", "er_k_gemm_hh_qkv", "er_k_gemm_hh_geglu", "er_k_gemm_f16s", "er_k_gemm_epi", "er_k_flash_attn_f16", "er_k_flash_attn_hh", "er_k_flash_attn_f32", "er_k_flash_attn_f16s", "er_k_layernorm", "er_k_softmax", "er_k_score_rows", "er_k_fps", "er_k_sample_head",
+    "er_set_row_streams", "er_set_prefix_groups", "er_plan_decode", "er_ctx_plan", "er_plan_gemm_tile", "er_kernel_kind_name", "er_profile_decode_kernels", "er_profile_decode_kernels_at", "er_last_decode_ms",
+    "er_k_gemv", "er_k_gemv_form", "er_k_mlp_transpose", "er_k_mlp_sparse", "er_mlp_nnz", "er_k_attn_decode", "er_k_attn_stream_xt", "er_k_attn_shared", "er_k_attn_outproj3", "er_k_gemm", "er_k_gemm_f16", "er_k_gemm_hh", "er_k_gemm_hh_qkv", "er_k_gemm_hh_geglu", "er_k_gemm_f16s", "er_k_gemm_epi", "er_k_flash_attn_f16", "er_k_flash_attn_hh", "er_k_flash_attn_f32", "er_k_flash_attn_f16s", "er_k_layernorm", "er_k_softmax", "er_k_score_rows", "er_k_fps", "er_k_sample_head",
     "er_k_nn_dist2", "er_k_surface_sample", "er_k_fidelity_metrics",
     "er_queue_begin", "er_queue_admit", "er_queue_run", "er_queue_take", "er_queue_stats", "er_queue_end",
 ]
 
 
-ER_ATTN_SPLIT1, ER_ATTN_SPLIT2, ER_ATTN_BALANCED, ER_ATTN_STREAM = 1, 2, 3, 4
+ER_ATTN_SPLIT1, ER_ATTN_SPLIT2, ER_ATTN_BALANCED, ER_ATTN_STREAM, ER_ATTN_SHARED = 1, 2, 3, 4, 5
 
 
 class ErDecodePlan(C.Structure):
@@ -164,6 +164,7 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.er_plan_decode.argtypes = [ci, ci, ci, ci, ci, C.POINTER(ErDecodePlan)]
     lib.er_ctx_plan.argtypes = [vp, C.POINTER(ErDecodePlan)]
     lib.er_set_row_streams.argtypes = [vp, C.POINTER(C.c_uint32), ci]
+    lib.er_set_prefix_groups.argtypes = [vp, C.POINTER(C.c_int32), ci, ci]
     lib.er_plan_gemm_tile.argtypes = [ci, ci, ci]
     lib.er_queue_begin.argtypes = [vp, C.POINTER(ErDecodeParams), ci, vp]
     lib.er_queue_admit.argtypes = [vp, ci, ci, vp, ci, C.POINTER(C.c_uint32), C.POINTER(C.c_int32), vp]
@@ -177,6 +178,7 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.er_k_mlp_sparse.argtypes = [C.POINTER(ErKMlpSparseArgs), vp]
     lib.er_mlp_nnz.argtypes = [vp, C.POINTER(C.c_int32), ci]
     lib.er_k_attn_stream_xt.argtypes = [vp, vp, vp, C.POINTER(C.c_int32), vp, vp, ci, ci, ci, ci, vp]
+    lib.er_k_attn_shared.argtypes = [vp, vp, vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), ci, vp, vp, ci, ci, ci, ci, vp]
     lib.er_k_attn_decode.argtypes = [vp, vp, vp, C.POINTER(C.c_int32), vp, ci, ci, ci, ci, ci, ci, ci, vp]
     lib.er_k_attn_outproj3.argtypes = [vp, vp, vp, ci, vp, vp, vp, vp, ci, ci, ci, vp]
     lib.er_k_gemm.argtypes = [vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, cf, vp]

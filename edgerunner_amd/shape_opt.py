@@ -185,12 +185,26 @@ class NativeShapeOPT:
         self._exit()
         return out
 
-    def prefill(self, inputs_embeds: torch.Tensor, max_new_tokens: int):
+    def set_prefix_groups(self, prefix_groups=None):
+        """``er_set_prefix_groups`` on the reserved batch: ``(leaders, prefix_len)`` with leaders[b] = the lowest row that shares row
+        b's first prefix_len cache positions (b itself for a row of its own); None clears the groups."""
+        if prefix_groups is None:
+            native.check(self.lib.er_set_prefix_groups(self._ctx, None, 0, 0), "er_set_prefix_groups")
+            return
+        leaders, prefix_len = prefix_groups
+        leaders = [int(v) for v in leaders]
+        native.check(self.lib.er_set_prefix_groups(self._ctx, native.i32_array(leaders), len(leaders), int(prefix_len)),
+                     "er_set_prefix_groups")
+
+    def prefill(self, inputs_embeds: torch.Tensor, max_new_tokens: int, prefix_groups=None):
+        """``prefix_groups``: None, or ``(leaders, prefix_len)`` as for set_prefix_groups - set (or cleared) after the lazy reserve and
+        before the forward pass, which then checks on the device that the rows of a group hold the same prefix."""
         x = inputs_embeds.to(self.device, torch.float32).contiguous()
         B, S, _ = x.shape
         need = S + max_new_tokens + 1
         if self._reserved[0] != B or self._reserved[1] < need:
             self.reserve(B, need)
+        self.set_prefix_groups(prefix_groups)
         with self._enter():
             native.check(self.lib.er_prefill(self._ctx, native.ptr(x), B, S, self._sp()), "er_prefill")
         self._exit()
@@ -255,10 +269,10 @@ class NativeShapeOPT:
                  eos_token_id=None, max_new_tokens: Optional[int] = None,
                  prefix_allowed_tokens_fn: Optional[Callable] = None, num_beams: int = 1, do_sample: bool = False,
                  top_k: int = 50, min_new_tokens: int = 0, seed: Optional[int] = None, row_streams=None,
-                 **unused) -> torch.Tensor:
+                 prefix_groups=None, **unused) -> torch.Tensor:
         """Drop-in for ``ShapeOPT.generate`` as called at core/models.py:303.
         ``num_tokens`` is accepted and ignored exactly like the reference decoder
-        ignores it (modeling_opt.py:324,467,546)."""
+        ignores it (modeling_opt.py:324,467,546).  ``prefix_groups`` goes to ``prefill``."""
         if num_beams != 1:
             raise NotImplementedError("beam search is not part of the reference's call (num_beams=1)")
         for name, got, want in (("pad", pad_token_id, self.opt.pad_token_id), ("bos", bos_token_id, self.opt.bos_token_id),
@@ -268,7 +282,7 @@ class NativeShapeOPT:
         if max_new_tokens is None:
             max_new_tokens = self.opt.max_seq_length
         B = inputs_embeds.shape[0]
-        self.prefill(inputs_embeds, max_new_tokens)
+        self.prefill(inputs_embeds, max_new_tokens, prefix_groups=prefix_groups)
         # sample mode: the Philox stream of row b (default b; a sharding / batching caller passes global job indices)
         if row_streams is not None and len(row_streams) != B:
             raise ValueError(f"row_streams has {len(row_streams)} entries for a batch of {B}")

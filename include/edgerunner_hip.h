@@ -216,6 +216,21 @@ int er_queue_stats(er_ctx* ctx, er_queue_counters* out);
  * identity again, every row's budget is er_decode's max_new_tokens, er_prefill is required before er_decode. */
 int er_queue_end(er_ctx* ctx);
 
+/* ---- shared prefix: rows of one reserved batch whose first prefix_len cache positions hold bit-identical K/V in every layer (the
+ * same cloud, face count and BOS: many samples of one input) form a GROUP, named by its lowest row, the leader.  With groups set a decode
+ * step computes row b's attention over keys [0, prefix_len) read from its LEADER's cache slice and keys [prefix_len, len_b) read from its
+ * own, so the prefix crosses HBM once per group and step instead of once per row; nothing else of the step changes, the cache layout and
+ * the prefill included (a follower's own [0, prefix_len) entries are written as always and not read by the step).  A row's tokens do not
+ * depend on the size of its group, its place in it or the other groups.
+ *   leader_host int32[n]: n = the reserved batch, 0 <= leader[b] <= b and leader[leader[b]] == leader[b] (a singleton is its own leader);
+ *   prefix_len >= 1.  NULL or prefix_len == 0 clears the groups, and so does the next er_kv_reserve.
+ * Call it after er_kv_reserve and before er_prefill.  ER_ERR_INVALID: a bad table, or a queue is open.  ER_ERR_UNSUPPORTED: the reserved
+ * plan is not the batched class (B > 4 or ER_FORCE_BATCHED) with head_dim 96.  Setting or clearing rebuilds the stored plan (er_ctx_plan:
+ * attn_kernel ER_ATTN_SHARED, merge_launch 1) and drops the captured step.  While groups are set er_prefill refuses seq_len < prefix_len
+ * and, after its forward pass, compares every follower's K/V [0, prefix_len) of all layers with its leader's on the device: a mismatch
+ * fails with ER_ERR_INVALID naming row and layer, and the context needs a new er_prefill; er_score and er_queue_begin refuse. */
+int er_set_prefix_groups(er_ctx* ctx, const int32_t* leader_host, int n, int prefix_len);
+
 /* ---- mesh tokenizer (host code, no device work): the reference's pybind11 module meto (meto/src/bindings.cpp,
  * meto.Engine(discrete_bins, verbose, backend), meto/meto/__init__.py:21-54) for the backends Options.meto_backend
  * admits (core/options.py:26). */
@@ -306,7 +321,9 @@ int er_dit_loss(er_dit_ctx* ctx, const float* latents_dev, const float* noise_de
  * The rules live in ONE function.  er_kv_reserve evaluates it once for the shape it reserves and stores the result, with everything
  * the step derives from it, beside that shape's memory; er_plan_decode evaluates it for a hypothetical shape under the environment
  * of the call (ER_DECODE_V, ER_ATTN_V_BATCHED, ER_FORCE_BATCHED are honoured, l_cap is rounded up to 32 like er_kv_reserve). */
-typedef enum { ER_ATTN_SPLIT1 = 1, ER_ATTN_SPLIT2 = 2, ER_ATTN_BALANCED = 3, ER_ATTN_STREAM = 4 } er_attn_kernel;
+typedef enum { ER_ATTN_SPLIT1 = 1, ER_ATTN_SPLIT2 = 2, ER_ATTN_BALANCED = 3, ER_ATTN_STREAM = 4,
+               ER_ATTN_SHARED = 5    /* prefix groups are set (er_set_prefix_groups): er_ctx_plan only, never er_plan_decode's shape-only rule */
+} er_attn_kernel;
 typedef struct {
     int32_t batched;            /* 1: B > 4 path (matrix-core projections, weights once per 32 rows) */
     int32_t decode_version;     /* single-row path: 3 = balanced chunks + merge fused into out_proj, 2 = fixed chunks + merge kernel */
@@ -432,6 +449,12 @@ int er_mlp_nnz(er_ctx* ctx, int32_t* out, int n);
  * out_xt_dev (heads * 96 * 128 bytes per 32 rows; rows the batch does not have are left alone), as out_proj's tiled forms read it. */
 int er_k_attn_stream_xt(const float* q_dev, const void* k_dev, const void* v_dev, const int32_t* len_host, float* out_dev,
                         void* out_xt_dev, int batch, int heads, int l_cap, int kv_half, void* stream);
+/* The two launches of a decode step under prefix groups (er_set_prefix_groups; csrc/k_attn_shared.h), head_dim 96, on a [B,H,Lcap,96]
+ * cache: out[b] = attention of q[b] over keys [0, prefix_len) of row leader[b]'s slice and keys [prefix_len, len[b]) of row b's own.
+ * leader_host as for er_set_prefix_groups, prefix_len in [1, l_cap], prefix_len <= len[b] <= l_cap.  out_xt_dev (nullable) as for
+ * er_k_attn_stream_xt.  Blocks until the work is complete. */
+int er_k_attn_shared(const float* q_dev, const void* k_dev, const void* v_dev, const int32_t* len_host, const int32_t* leader_host,
+                     int prefix_len, float* out_dev, void* out_xt_dev, int batch, int heads, int l_cap, int kv_half, void* stream);
 /* Version 3 of the single-row decode attention (env ER_DECODE_V=3), one row, 16 heads of 96:
  * y[1536] = Wo . softmax(q K^T / sqrt(D)) V + bo + resid over a [16,Lcap,96] cache holding len keys (Lcap <= 8192):
  * balanced chunks (16 per head) + the partial merge fused into the out_proj GEMV; w_half: Wo is fp16 */

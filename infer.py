@@ -28,6 +28,11 @@ ER_INFER_QUEUE=1 serves the rank's jobs through ``LMM.generate_queue`` instead: 
 all face counts, a job leaves its row when it emits EOS and the next job is prefilled into that row, so no row rides on to the end
 of the longest job of its call.  Same output files and ``tokens_all.npz``; the log line of a job carries its own token count and
 the row it ran in.  Without the variable nothing changes.
+
+ER_INFER_SHARE_PREFIX=1 passes ``share_prefix=True`` to the batched path's ``LMM.generate`` calls: the jobs of one call that come from
+the same cloud (--test_repeat samples of one input) read their common cond + BOS prefix once per decode step instead of once per job
+(calls of more than 4 jobs; see ``LMM.generate_ids``).  Same output files.  It cannot be combined with ER_INFER_QUEUE=1 (the queue's
+rows change owners; groups in queue mode are not built): both together are refused at start.  Without the variable nothing changes.
 """
 from __future__ import annotations
 
@@ -93,6 +98,9 @@ def max_rows_per_call(opt, model, max_new_tokens, device) -> int:
 
 def main(argv=None):
     opt = parse_cli(argv)
+    share_prefix = os.environ.get("ER_INFER_SHARE_PREFIX") == "1"
+    if share_prefix and os.environ.get("ER_INFER_QUEUE") == "1":
+        raise SystemExit("[ERROR] ER_INFER_SHARE_PREFIX=1 and ER_INFER_QUEUE=1 cannot be combined: prefix groups are not built for queue mode")
     rank, world, local = D.init_process_group()
     seed_everything(opt.seed)
     if opt.cond_mode not in ("point", "none"):
@@ -183,7 +191,8 @@ def main(argv=None):
         t0 = time.time()
         # sample mode: job j draws from the Philox stream (opt.seed, step, j) whatever rows share its call
         meshes, tokens = model.generate(cond, num_faces=num_faces, max_new_tokens=opt.test_max_seq_length,
-                                        tokenizer=tokenizer, clean=True, seed=opt.seed, row_streams=list(chunk))
+                                        tokenizer=tokenizer, clean=True, seed=opt.seed, row_streams=list(chunk),
+                                        **({"share_prefix": True} if share_prefix else {}))
         torch.cuda.synchronize()
         dt = time.time() - t0
         for r, j in enumerate(chunk):
