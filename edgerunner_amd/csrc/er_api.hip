@@ -132,6 +132,17 @@ struct KvMem {
     DevBuf<int> d_row_budget;     // [B] token budget per row: INT_MAX (= er_decode's max_new_tokens decides) outside the queue mode
     DevBuf<long long> d_out_ids;  // [B][Lcap] generated ids (graph writes here; copied to the caller at the end)
     hipGraphExec_t step_exec = nullptr;  // hipGraph of one step
+    // the head with controls (er_set_sampling): which head the current generation ends its step in, that step's own capture, the device
+    // copy of the controls and the log-prob tables beside d_out_ids (allocated when log-probs are first asked for)
+    bool head_ctl = false, lp_on = false, lp_valid = false, ctl_exec_lp = false;
+    // A generation that keeps log-probs runs a one-row exact plan as the kernels that 2 .. 4 rows run: split attention + merge + plain out_proj
+    // in place of version 3, the row fc1 / fc2 in place of the fused MLP.  Those one-row kernels associate their sums differently, their logits
+    // differ in the last place, and a job's log-probs are promised to be the same bits whether it runs alone or in a queue of a few slots.
+    // The stored plan (er_ctx_plan) and the default step do not change.
+    bool row_class = false;
+    hipGraphExec_t step_exec_ctl = nullptr;   // captured with the log-prob pointers of the time (ctl_exec_lp: they were set)
+    DevBuf<HeadCtlDev> d_ctl;
+    DevBuf<float> d_lp_model, d_lp_policy;    // [B][Lcap]
     // prefix groups (er_set_prefix_groups; prefix_len == 0: none): the leader of every row, and for the prefix pass the rows of every group,
     // group after group with the leader first, behind the groups' offsets
     std::vector<int> grp_leader;
@@ -140,7 +151,12 @@ struct KvMem {
     KvMem() = default;
     KvMem(const KvMem&) = delete;
     KvMem& operator=(const KvMem&) = delete;
-    ~KvMem() { if (step_exec) hipGraphExecDestroy(step_exec); }
+    void drop_steps() {
+        if (step_exec) hipGraphExecDestroy(step_exec);
+        if (step_exec_ctl) hipGraphExecDestroy(step_exec_ctl);
+        step_exec = step_exec_ctl = nullptr;
+    }
+    ~KvMem() { drop_steps(); }
 };
 
 struct er_ctx {
@@ -162,6 +178,7 @@ struct er_ctx {
     int base_pos = 0;             // prefill length of the current generation
     bool have_hidden = false;     // ypre holds a valid last-position state
     DecodeKnobs knobs;        // environment of er_create
+    er_sampling samp{1.0f, 1.0f, 0, 0, 0};   // er_set_sampling: sticky, kept across er_kv_reserve
     bool tiled_valid = false; // LayerW::*_t match the loaded weights
     bool kmajor_valid = false; // LayerW::w2_kt match the loaded weights
     void* zero_row = nullptr;  // hidden zeros (fp32 size): what the fused MLP reads in place of a dead neuron's row
@@ -472,6 +489,7 @@ static int kv_alloc(er_ctx* c, KvMem& m, int batch, int Lcap) {
     ERCHK(m.state_block.ensure(gen_state_ints(b)));
     m.st = gen_state_carve(m.state_block.p, b);
     ERCHK(m.d_params.ensure(1));
+    ERCHK(m.d_ctl.ensure(1));
     ERCHK(m.d_ids_tmp.ensure(b));
     ERCHK(m.d_row_stream.ensure(b));
     {
@@ -570,6 +588,7 @@ static hipError_t launch_kind_t(er_ctx* c, int kind, int layer, hipStream_t st, 
     const int H = g.hidden_dim, I = g.intermediate_dim, B = p.B;
     const SkPart sk{kv.skpart.p, kv.skpart.n};
     const auto form_of = [&](Proj proj, int l) { return proj_form(p, c->knobs, HALF, proj, l); };
+    const bool v3 = p.v3 && !kv.row_class, fused = p.mlp_fused && !kv.row_class;
     GemvArgs a{};
     a.eps = g.ln_eps;
     a.hidden = H; a.head_dim = c->D; a.l_cap = p.Lcap; a.kv_bstride = p.kv_bstride; a.kv_half = HALF ? 1 : 0;
@@ -595,17 +614,17 @@ static hipError_t launch_kind_t(er_ctx* c, int kind, int layer, hipStream_t st, 
         // v2 holds a wave's whole K/V slice in flight (latency-bound single rows); with hundreds of workgroups per CU's
         // worth of work (B > 4) the leaner v1 (66-74 VGPRs, 6-7 waves per SIMD) streams faster: 570 vs 636 us at B = 32, L = 18050
         case 1:
-            if (p.v3) return launch_attn_partial3_d<96>(attn_args(c, layer), HALF, p.nch3, B, st);
+            if (v3) return launch_attn_partial3_d<96>(attn_args(c, layer), HALF, p.nch3, B, st);
             if (p.shared_attn) return launch_attn_prefix_d<96>(attn_shared_args(c, layer), HALF, kv.n_groups, st);
             if (p.stream_attn) return launch_attn_stream_d<96>(attn_args(c, layer), HALF, B, st);
             return launch_attn_partial(attn_args(c, layer), c->D, ATTN_STEPS_DEFAULT, HALF, B, st, p.batched ? 1 : 2);
         case 2:
-            if (!p.sel.merge_launch) return hipSuccess;      // the merge runs inside the out_proj kernel (version 3) / there are no partials (streaming)
+            if (!p.sel.merge_launch && !(p.v3 && !v3)) return hipSuccess;      // the merge runs inside the out_proj kernel (version 3) / there are no partials (streaming)
             if (p.shared_attn) return launch_attn_suffix_merge_d<96>(attn_shared_args(c, layer), HALF, B, st);
             return launch_attn_combine(attn_args(c, layer), c->D, B, st);
         case 3: {   // out_proj + bias + residual(h) -> ypre1
             const LayerW& L = c->layers[layer];
-            if (p.v3) {
+            if (v3) {
                 OutMergeArgs m{};
                 m.W = HALF ? (const void*)L.wo_h : (const void*)L.wo; m.bias = L.bo; m.resid = c->kv->hbuf.p; m.out = c->kv->ypre1.p;
                 m.part_o = c->kv->part.p; m.part_ml = c->kv->part_ml.p; m.N = H;
@@ -617,7 +636,7 @@ static hipError_t launch_kind_t(er_ctx* c, int kind, int layer, hipStream_t st, 
         }
         case 4: {   // h1 = LN1(ypre1); f = relu(fc1 h1 + b)
             const LayerW& L = c->layers[layer];
-            if (p.mlp_fused) {      // ... and the chain sums of fc2 over the live neurons; f stays in the workgroups
+            if (fused) {      // ... and the chain sums of fc2 over the live neurons; f stays in the workgroups
                 if (!c->kmajor_valid) return hipErrorInvalidValue;
                 return launch_mlp_fused<WT>(mlp_args(c, layer), st);
             }
@@ -631,7 +650,7 @@ static hipError_t launch_kind_t(er_ctx* c, int kind, int layer, hipStream_t st, 
         }
         case 5: {   // ypre = fc2 f + b + h1
             const LayerW& L = c->layers[layer];
-            if (p.mlp_fused) return launch_mlp_finish(mlp_args(c, layer), st);
+            if (fused) return launch_mlp_finish(mlp_args(c, layer), st);
             a.W = HALF ? (const void*)L.w2_h : (const void*)L.w2; a.bias = L.b2; a.N = H; a.xin = kv.fbuf.p; a.out = kv.ypre.p; a.resid = kv.h1buf.p;
             io.w_tiled = L.w2_t; io.x_image = kv.xt_f.p;
             return run_proj<WT>(PROJ_FC2, form_of(PROJ_FC2, layer), io, a, B, I, sk, st);
@@ -643,6 +662,12 @@ static hipError_t launch_kind_t(er_ctx* c, int kind, int layer, hipStream_t st, 
             return run_proj<WT>(PROJ_HEAD, form_of(PROJ_HEAD, layer), io, a, B, H, sk, st);
         }
         case 7:
+            if (kv.head_ctl) {
+                const HeadCtlOut lp{kv.lp_on ? kv.d_lp_model.p : nullptr, kv.lp_on ? kv.d_lp_policy.p : nullptr, nullptr, p.Lcap};
+                hipLaunchKernelGGL(sample_head_ctl_kernel, dim3(B), dim3(ER_WG), sample_head_lds(g.vocab_size), st, kv.logits.p,
+                                   kv.d_params.p, kv.d_ctl.p, kv.st, out_ids, out_ld, lp);
+                return hipGetLastError();
+            }
             hipLaunchKernelGGL(sample_head_kernel, dim3(B), dim3(ER_WG), sample_head_lds(g.vocab_size), st, c->kv->logits.p,
                                c->kv->d_params.p, c->kv->st, out_ids, out_ld);
             return hipGetLastError();
@@ -1087,6 +1112,7 @@ static int prefix_groups_check(er_ctx* c, hipStream_t st) {
 extern "C" int er_prefill(er_ctx* c, const float* embeds, int B, int S, void* stream) {
     ERCHK(forward_check(c, "er_prefill", embeds, B, S));
     if (c->kv->prefix_len > S) return fail(ER_ERR_INVALID, "er_prefill: %d positions but the prefix groups share %d", S, c->kv->prefix_len);
+    c->kv->row_class = false;                  // er_feed / er_logits after this prefill run the plan's own kinds; er_decode chooses again
     ERCHK(prefill_run(c, embeds, B, S, pick(c, stream)));
     return c->kv->prefix_len ? prefix_groups_check(c, pick(c, stream)) : ER_OK;
 }
@@ -1119,7 +1145,7 @@ extern "C" int er_set_prefix_groups(er_ctx* c, const int32_t* leader, int n, int
     }
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(hipDeviceSynchronize());           // a running step still reads the old tables
-    if (kv.step_exec) { hipGraphExecDestroy(kv.step_exec); kv.step_exec = nullptr; }      // the next step is captured with the new launches
+    kv.drop_steps();                          // the next step is captured with the new launches
     const er_config& g = c->cfg;
     kv.plan = make_decode_plan(c->knobs, kv.plan.rk, c->fast, B, kv.plan.Lcap, g.num_layers, g.num_heads, c->D, g.hidden_dim, attn_chunking(g.num_heads), !clear);
     c->have_hidden = false;                   // groups come before the prefill whose cache they describe
@@ -1147,6 +1173,7 @@ extern "C" int er_score(er_ctx* c, const float* embeds, const int32_t* labels, i
     ERCHK(forward_check(c, "er_score", embeds, B, S));
     if (c->kv->prefix_len) return fail(ER_ERR_INVALID, "er_score: prefix groups are set on this context (clear them with er_set_prefix_groups(ctx, NULL, 0, 0))");
     if (!labels || !nll_out || !loss_out) return fail(ER_ERR_INVALID, "er_score: labels, nll_out and loss_out are required");
+    c->kv->row_class = false;                  // as er_prefill
     hipStream_t st = pick(c, stream);
     ERCHK(prefill_run(c, embeds, B, S, st));
     const er_config& g = c->cfg;
@@ -1239,7 +1266,12 @@ __global__ void reset_gen_kernel(GenState st, int B) {
 // one step = lm_head -> sampling head -> 24 layers on the chosen token; captured once per reserved shape, replayed by er_decode and
 // er_queue_run
 static int ensure_step_graph(er_ctx* c) {
-    if (!c->knobs.use_graph || c->kv->step_exec) return 0;
+    KvMem& kv = *c->kv;
+    if (!c->knobs.use_graph) return 0;
+    // the step that ends in the head with controls is a capture of its own; one taken without the log-prob tables is taken again with them
+    if (kv.head_ctl && kv.step_exec_ctl && kv.ctl_exec_lp != kv.lp_on) { hipGraphExecDestroy(kv.step_exec_ctl); kv.step_exec_ctl = nullptr; }
+    hipGraphExec_t* slot = kv.head_ctl ? &kv.step_exec_ctl : &kv.step_exec;
+    if (*slot) return 0;
     const int Lcap = c->kv->plan.Lcap;
     hipGraph_t graph = nullptr;
     HIPCHK(hipStreamBeginCapture(c->own_stream, hipStreamCaptureModeRelaxed));
@@ -1249,8 +1281,33 @@ static int ensure_step_graph(er_ctx* c) {
         if (graph) hipGraphDestroy(graph);
         return fail(ER_ERR_HIP, "graph capture failed: %s / %s", hipGetErrorString(e), hipGetErrorString(e2));
     }
-    HIPCHK(hipGraphInstantiate(&c->kv->step_exec, graph, nullptr, nullptr, 0));
+    HIPCHK(hipGraphInstantiate(slot, graph, nullptr, nullptr, 0));
     hipGraphDestroy(graph);
+    if (kv.head_ctl) kv.ctl_exec_lp = kv.lp_on;
+    return 0;
+}
+static hipGraphExec_t step_graph(er_ctx* c) { return c->kv->head_ctl ? c->kv->step_exec_ctl : c->kv->step_exec; }
+
+// What er_decode and er_queue_begin make of er_decode_params.top_k and the context's er_sampling: the top_k the head works with, which
+// head ends the step, the device copy of the controls and the log-prob tables.
+static int head_setup(er_ctx* c, const er_decode_params* p, int* top_k) {
+    KvMem& kv = *c->kv;
+    const er_sampling& s = c->samp;
+    *top_k = s.top_k_set ? s.top_k : p->top_k;
+    if (p->mode == ER_SAMPLE && !s.top_k_set && p->top_k <= 0) return fail(ER_ERR_INVALID, "top_k must be > 0 in sample mode");
+    const bool sample = p->mode == ER_SAMPLE;
+    kv.lp_on = s.logprobs != 0;
+    kv.lp_valid = false;
+    kv.row_class = kv.lp_on;
+    kv.head_ctl = kv.lp_on || (sample && (s.temperature != 1.0f || s.top_p != 1.0f || *top_k <= 0));
+    if (!kv.head_ctl) return 0;
+    if (kv.lp_on) {
+        const size_t n = (size_t)kv.plan.B * kv.plan.Lcap;
+        ERCHK(kv.d_lp_model.ensure(n));
+        ERCHK(kv.d_lp_policy.ensure(n));
+    }
+    const HeadCtlDev h{s.temperature, s.top_p};
+    HIPCHK(hipMemcpy(kv.d_ctl.p, &h, sizeof(h), hipMemcpyHostToDevice));
     return 0;
 }
 
@@ -1260,16 +1317,18 @@ extern "C" int er_decode(er_ctx* c, const er_decode_params* p, int64_t* out_ids,
     if (p->max_new_tokens <= 0) return fail(ER_ERR_INVALID, "max_new_tokens must be > 0");
     if (p->mode != ER_GREEDY && p->mode != ER_SAMPLE) return fail(ER_ERR_INVALID, "bad mode");
     if (p->grammar < 0 || p->grammar > 2) return fail(ER_ERR_INVALID, "bad grammar");
-    if (p->mode == ER_SAMPLE && p->top_k <= 0) return fail(ER_ERR_INVALID, "top_k must be > 0 in sample mode");
+    if (p->mode == ER_SAMPLE && !c->samp.top_k_set && p->top_k <= 0) return fail(ER_ERR_INVALID, "top_k must be > 0 in sample mode");
     HIPCHK(hipSetDevice(c->device));
     hipStream_t st = pick(c, stream);
     const int B = c->kv->plan.B, Lcap = c->kv->plan.Lcap, T = p->max_new_tokens;
     HIPCHK(hipStreamSynchronize(st));
     ERCHK(check_room(c, T));
     if (c->h_pinned[0] != 0) return fail(ER_ERR_INVALID, "er_decode must directly follow er_prefill (%d tokens already fed)", c->h_pinned[0]);
+    int top_k = 0;
+    ERCHK(head_setup(c, p, &top_k));
 
     DecodeParamsDev dp{};
-    dp.mode = p->mode; dp.top_k = p->top_k; dp.grammar = p->grammar; dp.max_new = T; dp.min_new = p->min_new_tokens;
+    dp.mode = p->mode; dp.top_k = top_k; dp.grammar = p->grammar; dp.max_new = T; dp.min_new = p->min_new_tokens;
     dp.eos = c->cfg.eos_token_id; dp.pad = c->cfg.pad_token_id; dp.vocab = c->cfg.vocab_size;
     dp.seed_lo = (unsigned int)(p->seed & 0xffffffffu); dp.seed_hi = (unsigned int)(p->seed >> 32);
     HIPCHK(hipMemcpy(c->kv->d_params.p, &dp, sizeof(dp), hipMemcpyHostToDevice));
@@ -1285,7 +1344,7 @@ extern "C" int er_decode(er_ctx* c, const er_decode_params* p, int64_t* out_ids,
     int steps_run = 0;
     HIPCHK(hipEventRecord(c->ev0, st));
     for (int t = 0; t < T; ++t) {
-        if (c->knobs.use_graph) HIPCHK(hipGraphLaunch(c->kv->step_exec, st));
+        if (c->knobs.use_graph) HIPCHK(hipGraphLaunch(step_graph(c), st));
         else HIPRET(enqueue_step(c, st, c->kv->d_out_ids.p, Lcap));
         steps_run = t + 1;
         if (steps_run >= p->min_new_tokens && steps_run < T && (steps_run % check_every) == 0) {
@@ -1312,6 +1371,36 @@ extern "C" int er_decode(er_ctx* c, const er_decode_params* p, int64_t* out_ids,
     }
     *n_steps = finished ? last + 1 : T;
     if (!finished && steps_run < T) return fail(ER_ERR_INVALID, "internal: stopped early with unfinished rows");
+    c->kv->lp_valid = c->kv->lp_on;
+    return ER_OK;
+}
+
+extern "C" int er_set_sampling(er_ctx* c, const er_sampling* s) {
+    if (!c) return fail(ER_ERR_INVALID, "er_set_sampling: null context");
+    const er_sampling dflt{1.0f, 1.0f, 0, 0, 0};
+    if (!s) s = &dflt;
+    if (!(s->temperature > 0.0f) || !(s->temperature <= 3.402823466e38f))
+        return fail(ER_ERR_INVALID, "er_set_sampling: temperature %g is not a finite number > 0", (double)s->temperature);
+    if (!(s->top_p > 0.0f) || !(s->top_p <= 1.0f)) return fail(ER_ERR_INVALID, "er_set_sampling: top_p %g outside (0, 1]", (double)s->top_p);
+    if (s->top_k_set && s->top_k < 0) return fail(ER_ERR_INVALID, "er_set_sampling: top_k %d is negative", s->top_k);
+    if (c->q.active) return fail(ER_ERR_INVALID, "er_set_sampling: a queue is open on this context (er_queue_begin read the controls; er_queue_end first)");
+    c->samp = *s;
+    c->samp.top_k_set = s->top_k_set ? 1 : 0;
+    if (!c->samp.top_k_set) c->samp.top_k = 0;
+    c->samp.logprobs = s->logprobs ? 1 : 0;
+    return ER_OK;
+}
+
+extern "C" int er_get_logprobs(er_ctx* c, float* model_out, float* policy_out, int ld, int n_steps, void* stream) {
+    if (!c) return fail(ER_ERR_INVALID, "er_get_logprobs: null context");
+    const KvMem& kv = *c->kv;
+    if (!kv.lp_valid) return fail(ER_ERR_INVALID, "er_get_logprobs: the last er_decode kept no log-probs (er_set_sampling with logprobs on, then er_decode)");
+    if (n_steps <= 0 || n_steps > kv.plan.Lcap || ld < n_steps) return fail(ER_ERR_INVALID, "er_get_logprobs: n_steps %d, ld %d (reserved %d)", n_steps, ld, kv.plan.Lcap);
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t st = pick(c, stream);
+    const size_t w = (size_t)n_steps * sizeof(float);
+    if (model_out) HIPCHK(hipMemcpy2DAsync(model_out, (size_t)ld * sizeof(float), kv.d_lp_model.p, (size_t)kv.plan.Lcap * sizeof(float), w, kv.plan.B, hipMemcpyDeviceToDevice, st));
+    if (policy_out) HIPCHK(hipMemcpy2DAsync(policy_out, (size_t)ld * sizeof(float), kv.d_lp_policy.p, (size_t)kv.plan.Lcap * sizeof(float), w, kv.plan.B, hipMemcpyDeviceToDevice, st));
     return ER_OK;
 }
 
@@ -1378,7 +1467,7 @@ extern "C" int er_queue_begin(er_ctx* c, const er_decode_params* p, int check_ev
     if (p->max_new_tokens <= 0) return fail(ER_ERR_INVALID, "max_new_tokens must be > 0");
     if (p->mode != ER_GREEDY && p->mode != ER_SAMPLE) return fail(ER_ERR_INVALID, "bad mode");
     if (p->grammar < 0 || p->grammar > 2) return fail(ER_ERR_INVALID, "bad grammar");
-    if (p->mode == ER_SAMPLE && p->top_k <= 0) return fail(ER_ERR_INVALID, "top_k must be > 0 in sample mode");
+    if (p->mode == ER_SAMPLE && !c->samp.top_k_set && p->top_k <= 0) return fail(ER_ERR_INVALID, "top_k must be > 0 in sample mode");
     if (check_every < 0) return fail(ER_ERR_INVALID, "er_queue_begin: check_every %d", check_every);
     ERCHK(er_finalize_weights(c));
     HIPCHK(hipSetDevice(c->device));
@@ -1389,9 +1478,11 @@ extern "C" int er_queue_begin(er_ctx* c, const er_decode_params* p, int check_ev
     if (c->q_pinned) { hipHostFree(c->q_pinned); c->q_pinned = nullptr; }
     HIPCHK(hipHostMalloc((void**)&c->q_pinned, ((size_t)3 * B + 1) * sizeof(int), hipHostMallocDefault));
     HIPCHK(hipStreamSynchronize(st));
+    int top_k = 0;
+    ERCHK(head_setup(c, p, &top_k));
 
     DecodeParamsDev dp{};
-    dp.mode = p->mode; dp.top_k = p->top_k; dp.grammar = p->grammar; dp.max_new = p->max_new_tokens; dp.min_new = p->min_new_tokens;
+    dp.mode = p->mode; dp.top_k = top_k; dp.grammar = p->grammar; dp.max_new = p->max_new_tokens; dp.min_new = p->min_new_tokens;
     dp.eos = c->cfg.eos_token_id; dp.pad = c->cfg.pad_token_id; dp.vocab = c->cfg.vocab_size;
     dp.seed_lo = (unsigned int)(p->seed & 0xffffffffu); dp.seed_hi = (unsigned int)(p->seed >> 32);
     HIPCHK(hipMemcpy(c->kv->d_params.p, &dp, sizeof(dp), hipMemcpyHostToDevice));
@@ -1447,7 +1538,7 @@ extern "C" int er_queue_run(er_ctx* c, int32_t* done_rows, int32_t* n_done, void
         const int burst = c->q.next_burst();
         if (burst <= 0) return fail(ER_ERR_INVALID, "internal: er_queue_run has occupied rows but none is running");
         for (int t = 0; t < burst; ++t) {
-            if (c->knobs.use_graph) HIPCHK(hipGraphLaunch(c->kv->step_exec, st));
+            if (c->knobs.use_graph) HIPCHK(hipGraphLaunch(step_graph(c), st));
             else HIPRET(enqueue_step(c, st, c->kv->d_out_ids.p, Lcap));
         }
         c->q.advance(burst);
@@ -1480,6 +1571,17 @@ extern "C" int er_queue_take(er_ctx* c, int row, int64_t* ids_out, int capacity,
     HIPCHK(hipStreamSynchronize(c->own_stream));
     *n_tokens = n;
     c->q.release(row);
+    return ER_OK;
+}
+
+extern "C" int er_queue_row_logprobs(er_ctx* c, int row, float* model_out, float* policy_out, int capacity) {
+    ERCHK(queue_open(c, "er_queue_row_logprobs"));
+    if (!c->kv->lp_on) return fail(ER_ERR_INVALID, "er_queue_row_logprobs: the queue keeps no log-probs (er_set_sampling with logprobs on before er_queue_begin)");
+    const int rc = c->q.check_take(row, capacity);
+    if (rc < 0) return fail(rc, "%s", c->q.why);
+    const size_t n = (size_t)c->q.rows[(size_t)row].n_tokens, at = (size_t)row * c->kv->plan.Lcap;
+    if (model_out) HIPCHK(hipMemcpy(model_out, c->kv->d_lp_model.p + at, n * sizeof(float), hipMemcpyDeviceToHost));
+    if (policy_out) HIPCHK(hipMemcpy(policy_out, c->kv->d_lp_policy.p + at, n * sizeof(float), hipMemcpyDeviceToHost));
     return ER_OK;
 }
 
@@ -1548,6 +1650,7 @@ static int profile_impl(er_ctx* c, int repeats, int use_graph, float* avg_us, do
     dp.mode = 0; dp.top_k = 10; dp.grammar = 2; dp.max_new = 1 << 30; dp.min_new = 0;
     dp.eos = g.eos_token_id; dp.pad = g.pad_token_id; dp.vocab = V;
     HIPCHK(hipMemcpy(c->kv->d_params.p, &dp, sizeof(dp), hipMemcpyHostToDevice));
+    c->kv->head_ctl = c->kv->row_class = false;   // the plan's own kinds 4, 5 and 7 here; er_decode / er_queue_begin choose again
     DevBuf<long long> dummy;             // freed on every return path; a failing one frees behind hipFree's own device synchronisation
     ERCHK(dummy.ensure((size_t)B * 8));
     long long* dummy_ids = dummy.p;
@@ -2217,6 +2320,64 @@ extern "C" int er_k_sample_head(const float* logits, const er_decode_params* p, 
     if (e == hipSuccess && e2 == hipSuccess) {
         hipMemcpy(h.data(), sb.p, h.size() * sizeof(int), hipMemcpyDeviceToHost);
         for (size_t i = 0; i < b; ++i) { next_tok[i] = hs.tok[i]; counter_out[i] = hs.counter[i]; unfinished_out[i] = hs.unfinished[i]; }
+    }
+    HIPRET(e);
+    HIPRET(e2);
+    return ER_OK;
+}
+
+extern "C" int er_k_sample_head_ctl(const float* logits, const er_decode_params* p, const er_sampling* s, int vocab, int eos, int pad,
+                                    int B, int step, const int32_t* last_tok, const int32_t* counter, const int32_t* unfinished,
+                                    int32_t* next_tok, int32_t* counter_out, int32_t* unfinished_out, float* lp_model, float* lp_policy,
+                                    int32_t* n_kept, void* stream) {
+    if (!logits || !p || B <= 0 || step < 0 || vocab <= 0 || vocab > ER_HEAD_MAX_VOCAB || !last_tok || !counter || !unfinished ||
+        !next_tok || !counter_out || !unfinished_out)
+        return fail(ER_ERR_INVALID, "er_k_sample_head_ctl: bad argument");
+    const er_sampling dflt{1.0f, 1.0f, 0, 0, 0};
+    if (!s) s = &dflt;
+    if (!(s->temperature > 0.0f) || !(s->temperature <= 3.402823466e38f) || !(s->top_p > 0.0f) || !(s->top_p <= 1.0f) || (s->top_k_set && s->top_k < 0))
+        return fail(ER_ERR_INVALID, "er_k_sample_head_ctl: temperature %g / top_p %g / top_k %d out of range", (double)s->temperature, (double)s->top_p, s->top_k);
+    hipStream_t st = (hipStream_t)stream;
+    const size_t b = (size_t)B;
+    DevBuf<int> sb, nk;
+    DevBuf<DecodeParamsDev> dpd;
+    DevBuf<HeadCtlDev> ctl;
+    DevBuf<long long> ids;
+    DevBuf<float> lpm, lpp;
+    ERCHK(sb.ensure(gen_state_ints(b)));
+    ERCHK(nk.ensure(b));
+    ERCHK(dpd.ensure(1));
+    ERCHK(ctl.ensure(1));
+    ERCHK(ids.ensure(b * (size_t)(step + 1)));
+    ERCHK(lpm.ensure(b * (size_t)(step + 1)));
+    ERCHK(lpp.ensure(b * (size_t)(step + 1)));
+    std::vector<int> h(gen_state_ints(b), 0);
+    const GenState hs = gen_state_carve(h.data(), b);      // the same state on the host
+    for (size_t i = 0; i < b; ++i) {
+        hs.tok[i] = last_tok[i]; hs.counter[i] = counter[i]; hs.ngen[i] = step;
+        hs.unfinished[i] = unfinished[i]; hs.eos_step[i] = -1;
+    }
+    *hs.n_unfinished = B;
+    HIPCHK(hipMemcpy(sb.p, h.data(), h.size() * sizeof(int), hipMemcpyHostToDevice));
+    const GenState gs = gen_state_carve(sb.p, b);
+    DecodeParamsDev dp{};
+    dp.mode = p->mode; dp.top_k = s->top_k_set ? s->top_k : p->top_k; dp.grammar = p->grammar; dp.max_new = step + 1; dp.min_new = p->min_new_tokens;
+    dp.eos = eos; dp.pad = pad; dp.vocab = vocab;
+    dp.seed_lo = (unsigned int)(p->seed & 0xffffffffu); dp.seed_hi = (unsigned int)(p->seed >> 32);
+    HIPCHK(hipMemcpy(dpd.p, &dp, sizeof(dp), hipMemcpyHostToDevice));
+    const HeadCtlDev hc{s->temperature, s->top_p};
+    HIPCHK(hipMemcpy(ctl.p, &hc, sizeof(hc), hipMemcpyHostToDevice));
+    const HeadCtlOut lp{lpm.p, lpp.p, nk.p, step + 1};
+    hipLaunchKernelGGL(sample_head_ctl_kernel, dim3(B), dim3(ER_WG), sample_head_lds(vocab), st, logits, dpd.p, ctl.p, gs, ids.p, step + 1, lp);
+    hipError_t e = hipGetLastError();
+    hipError_t e2 = hipStreamSynchronize(st);
+    if (e == hipSuccess && e2 == hipSuccess) {
+        hipMemcpy(h.data(), sb.p, h.size() * sizeof(int), hipMemcpyDeviceToHost);
+        for (size_t i = 0; i < b; ++i) { next_tok[i] = hs.tok[i]; counter_out[i] = hs.counter[i]; unfinished_out[i] = hs.unfinished[i]; }
+        const size_t pitch = (size_t)(step + 1) * sizeof(float);
+        if (lp_model) hipMemcpy2D(lp_model, sizeof(float), lpm.p + step, pitch, sizeof(float), b, hipMemcpyDeviceToHost);
+        if (lp_policy) hipMemcpy2D(lp_policy, sizeof(float), lpp.p + step, pitch, sizeof(float), b, hipMemcpyDeviceToHost);
+        if (n_kept) hipMemcpy(n_kept, nk.p, b * sizeof(int), hipMemcpyDeviceToHost);
     }
     HIPRET(e);
     HIPRET(e2);

@@ -237,4 +237,303 @@ __global__ void init_state_kernel(GenState st, int B, int base_pos) {
 
 inline size_t sample_head_lds(int vocab) { return (size_t)vocab * 3 * sizeof(float); }
 
+// ------------------------------------------------------------------------------------ the head with controls and log-probs
+// sample_head_ctl_kernel: sample_head_kernel plus what HF's warpers add above TopK(10) - temperature, top-k of any width (0: none) and
+// top-p, applied in HF's order - and the two log-probabilities of the chosen id:
+//   lp_model  = logits[next] - logsumexp(logits) over the RAW row (what LMM.score reports as -nll)
+//   lp_policy = log of the probability the id had in the distribution it was drawn from (greedy: log_softmax(masked)[next])
+// er_decode / er_queue_begin launch it only when a control is off its default or log-probs are asked for (er_set_sampling): the default
+// path keeps sample_head_kernel and its captured step.  With temperature 1, top_p 1 and top_k > 0 it picks the id sample_head_kernel picks
+// (same compaction, same expf(s - gmax), same ascending serial sum by one lane).  Every other setting may keep hundreds of candidates, so
+// it sums, filters and draws with the whole workgroup instead: a sort in LDS for the nucleus, a scan for the inverse CDF.
+struct HeadCtlDev {            // device copy of er_sampling (the effective top_k travels in DecodeParamsDev)
+    float temperature, top_p;
+};
+struct HeadCtlOut {            // where a step leaves its log-probs (null: not kept); n_kept is the unit entry's view of the filters
+    float* lp_model;           // [B][ld] at [b][t]
+    float* lp_policy;
+    int* n_kept;               // [B]: candidates the draw of this step chose from (0: greedy, finished row, no candidate)
+    int ld;
+};
+
+constexpr int HEAD_CTL_PER_THREAD = 5;   // candidates per thread in the workgroup-wide passes: a contiguous run of the compacted list
+constexpr int HEAD_CTL_RANKS = 8;        // ranks per thread of the nucleus' sorted order: 2048 keys, the vocabulary padded to a power of two
+static_assert(ER_HEAD_MAX_VOCAB <= HEAD_CTL_PER_THREAD * ER_WG && ER_HEAD_MAX_VOCAB <= HEAD_CTL_RANKS * ER_WG,
+              "the workgroup-wide passes cover the whole vocabulary");
+
+// sum of a[0, n) in LDS, the same bits from run to run: every thread adds its strided elements in ascending order, block_sum the rest
+__device__ __forceinline__ float head_block_sum(const float* a, int n, float* red) {
+    float v = 0.f;
+    for (int i = threadIdx.x; i < n; i += ER_WG) v += fmaxf(a[i], 0.f);      // a candidate the nucleus dropped carries -1
+    return block_sum(v, red);
+}
+
+// grid (B), 256 threads.  Dynamic LDS: sample_head_lds(vocab), as sample_head_kernel.
+__global__ __launch_bounds__(ER_WG) void sample_head_ctl_kernel(const float* logits, const DecodeParamsDev* pp, const HeadCtlDev* cp,
+                                                                GenState st, long long* out_ids, int out_ld, HeadCtlOut lp) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    __shared__ float red[8];
+    __shared__ int redi[8];
+    __shared__ int chosen_s, n_cand_s, n_kept_s, first_hit_s, last_kept_s;
+    __shared__ float lp_policy_s;
+    __shared__ float scan[2][ER_WG];
+    __shared__ unsigned long long keys[HEAD_CTL_RANKS * ER_WG];   // the nucleus' sort
+    const DecodeParamsDev P = *pp;
+    const HeadCtlDev Cc = *cp;
+    const int V = P.vocab;
+    float* sc = smem;                              // [V] masked scores
+    float* cand_e = smem + V;                      // [V] candidate weights (compacted)
+    int* cand_i = reinterpret_cast<int*>(smem + 2 * V);   // [V] candidate ids (compacted)
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int t = st.ngen[b];
+    const int max_new = st.row_budget ? min(P.max_new, st.row_budget[b]) : P.max_new;
+    if (t >= max_new) return;                      // replay past the end (or a parked row of the queue mode): no-op
+    const int last = st.tok[b];
+    const bool running = st.unfinished[b] != 0;
+    int counter = st.counter[b];
+    if (running) counter = grammar_update(P.grammar, t, counter, last);
+
+    // masked scores, and the raw row's maximum for lp_model
+    const float* lg = logits + (long long)b * V;
+    float rmax = -INFINITY;
+    for (int i = tid; i < V; i += ER_WG) {
+        bool ok = grammar_allowed(P.grammar, t, counter, i, V, P.eos);
+        if (i == P.eos && t < P.min_new) ok = false;
+        const float x = lg[i];
+        rmax = fmaxf(rmax, x);
+        sc[i] = ok ? x : -INFINITY;
+    }
+    __syncthreads();
+    rmax = block_max(rmax, red);
+    float rsum = 0.f;
+    for (int i = tid; i < V; i += ER_WG) rsum += expf(lg[i] - rmax);
+    rsum = block_sum(rsum, red);
+    const float raw_lse = rmax + logf(rsum);
+
+    // argmax with first-index tie-break (torch.argmax): used by greedy and as softmax max
+    float bv = -INFINITY;
+    int bi = 0x7fffffff;
+    for (int i = tid; i < V; i += ER_WG) {
+        const float v = sc[i];
+        if (v > bv) { bv = v; bi = i; }
+    }
+    auto take = [&](float ov, int oi) { if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; } };
+    take(lane_xor_any<32>(bv, lane), (int)lane_xor_bits<32>((unsigned)bi, lane));
+    take(lane_xor_any<16>(bv, lane), (int)lane_xor_bits<16>((unsigned)bi, lane));
+    take(lane_xor_any<8>(bv, lane), (int)lane_xor_bits<8>((unsigned)bi, lane));
+    take(lane_xor_any<4>(bv, lane), (int)lane_xor_bits<4>((unsigned)bi, lane));
+    take(lane_xor_any<2>(bv, lane), (int)lane_xor_bits<2>((unsigned)bi, lane));
+    take(lane_xor_any<1>(bv, lane), (int)lane_xor_bits<1>((unsigned)bi, lane));
+    if (lane == 0) { red[wid] = bv; redi[wid] = bi; }
+    __syncthreads();
+    float gmax = red[0];
+    int gidx = redi[0];
+#pragma unroll
+    for (int w = 1; w < ER_NWAVES; ++w)
+        if (red[w] > gmax || (red[w] == gmax && redi[w] < gidx)) { gmax = red[w]; gidx = redi[w]; }
+    __syncthreads();                               // red is reused below
+    int chosen = gidx;
+    const bool no_candidate = gidx < 0 || gidx >= V || !(gmax > -INFINITY);
+    if (no_candidate) chosen = P.eos;
+    float lp_policy = 0.f;
+    int n_kept = 0;
+
+    if (P.mode != 1 && !no_candidate) {            // greedy: log_softmax(masked)[argmax] = -log(sum exp(s - gmax))
+        float e = 0.f;
+        for (int i = tid; i < V; i += ER_WG) e += expf(sc[i] - gmax);
+        lp_policy = -logf(block_sum(e, red));
+    }
+
+    if (P.mode == 1 && !no_candidate) {            // sample: temperature -> TopK -> TopP -> softmax -> categorical
+        // TemperatureLogitsWarper: a true division (x / 1 is x: the default leaves every bit alone).  It is monotone, so gidx stays
+        // a first maximum and the maximum is gmax / temperature
+        for (int i = tid; i < V; i += ER_WG) sc[i] = sc[i] / Cc.temperature;
+        gmax = gmax / Cc.temperature;
+        __syncthreads();
+        if (wid == 0) {
+            // k-th largest value counting duplicates, as sample_head_kernel; top_k 0: no threshold
+            float kth = -INFINITY;
+            if (P.top_k > 0) {
+                constexpr int MAXPL = ER_HEAD_MAX_VOCAB / 64;
+                float v[MAXPL];
+#pragma unroll
+                for (int j = 0; j < MAXPL; ++j) { const int i = j * 64 + lane; v[j] = (i < V) ? sc[i] : -INFINITY; }
+                const int k = min(P.top_k, V);
+                kth = gmax;
+                for (int it = 0; it < k; ++it) {
+                    float mv = -INFINITY; int mj = 0;
+#pragma unroll
+                    for (int j = 0; j < MAXPL; ++j) if (v[j] > mv) { mv = v[j]; mj = j; }
+                    const float wmax = wave_max(mv);
+                    kth = wmax;
+                    if (wmax == -INFINITY) break;
+                    const unsigned long long holders = __ballot(mv == wmax);
+                    const int first = __ffsll((long long)holders) - 1;
+                    if (lane == first) {
+#pragma unroll
+                        for (int j = 0; j < MAXPL; ++j) if (j == mj) v[j] = -INFINITY;
+                    }
+                }
+            }
+            // candidates: s >= kth and finite; compact in ascending token id
+            int base = 0;
+            for (int j = 0; j * 64 < V; ++j) {
+                const int i = j * 64 + lane;
+                const float s = (i < V) ? sc[i] : -INFINITY;
+                const bool c = (s >= kth) && (s > -INFINITY);
+                const unsigned long long mask = __ballot(c);
+                if (c) {
+                    const int slot = base + __popcll(mask & ((1ull << lane) - 1ull));
+                    cand_i[slot] = i;
+                    cand_e[slot] = expf(s - gmax);
+                }
+                base += __popcll(mask);
+            }
+            __builtin_amdgcn_wave_barrier();
+            __threadfence_block();
+            if (lane == 0) { n_cand_s = base; first_hit_s = 0x7fffffff; last_kept_s = -1; n_kept_s = 0; }
+            if (P.top_k > 0 && !(Cc.top_p < 1.0f) && lane == 0) {   // sample_head_kernel's draw, sum for sum
+                float total = 0.f;
+                for (int c = 0; c < base; ++c) total += cand_e[c];
+                unsigned int r[4];
+                philox4x32_10((unsigned int)t, st.row_stream ? st.row_stream[b] : (unsigned int)b, 0u, 0u, P.seed_lo, P.seed_hi, r);
+                const float u = (float)(r[0] >> 8) * (1.0f / 16777216.0f);
+                const float target = u * total;
+                float acc = 0.f;
+                int pick = base > 0 ? cand_i[base - 1] : P.eos;
+                float pe = base > 0 ? cand_e[base - 1] : 1.f;
+                for (int c = 0; c < base; ++c) {
+                    acc += cand_e[c];
+                    if (acc > target) { pick = cand_i[c]; pe = cand_e[c]; break; }
+                }
+                chosen_s = pick;
+                lp_policy_s = logf(pe / total);
+                n_kept_s = base;
+            }
+        }
+        __syncthreads();
+        if (P.top_k <= 0 || Cc.top_p < 1.0f) {     // wide sets: every pass over the candidates is the whole workgroup's
+            const int n = n_cand_s;
+            const int c0 = tid * HEAD_CTL_PER_THREAD;
+            if (Cc.top_p < 1.0f) {
+                // TopPLogitsWarper(min_tokens_to_keep=1): in the order (weight descending, id ascending) a candidate stays iff the mass
+                // strictly ahead of it is < top_p.  The order comes from a bitonic sort of 64-bit keys in LDS - inverted weight bits (a
+                // positive float orders as its bit pattern) over the compacted index, padded to a power of two with keys that sort last:
+                // log2(n) (log2(n) + 1) / 2 passes of n / 512 exchanges per thread, 55 for the 518-id vocabulary, whatever the
+                // distribution - then one scan over the ranks gives every candidate the mass ahead of it.
+                const float total = head_block_sum(cand_e, n, red);
+                int n2 = 2;
+                while (n2 < n) n2 <<= 1;
+                for (int i = tid; i < n2; i += ER_WG)
+                    keys[i] = i < n ? ((unsigned long long)(~__float_as_uint(cand_e[i])) << 32) | (unsigned)i : ~0ull;
+                __syncthreads();
+                for (int k = 2; k <= n2; k <<= 1)
+                    for (int jj = k >> 1; jj > 0; jj >>= 1) {
+                        for (int i = tid; i < n2; i += ER_WG) {
+                            const int o = i ^ jj;
+                            if (o > i) {
+                                const unsigned long long x = keys[i], y = keys[o];
+                                if ((x > y) == ((i & k) == 0)) { keys[i] = y; keys[o] = x; }
+                            }
+                        }
+                        __syncthreads();
+                    }
+                // rank r holds the r-th candidate of the order; thread tid owns ranks [8 tid, 8 tid + 8)
+                const int r0 = tid * HEAD_CTL_RANKS;
+                float w[HEAD_CTL_RANKS];
+                float mine_r = 0.f;
+#pragma unroll
+                for (int q = 0; q < HEAD_CTL_RANKS; ++q) {
+                    w[q] = (r0 + q < n) ? __uint_as_float(~(unsigned)(keys[r0 + q] >> 32)) : 0.f;
+                    mine_r += w[q];
+                }
+                int cur = 0;
+                scan[0][tid] = mine_r;
+                __syncthreads();
+#pragma unroll
+                for (int off = 1; off < ER_WG; off <<= 1) {
+                    const float x = scan[cur][tid] + (tid >= off ? scan[cur][tid - off] : 0.f);
+                    scan[cur ^ 1][tid] = x;
+                    cur ^= 1;
+                    __syncthreads();
+                }
+                const float limit = Cc.top_p * total;
+                float ahead = tid > 0 ? scan[cur][tid - 1] : 0.f;
+#pragma unroll
+                for (int q = 0; q < HEAD_CTL_RANKS; ++q) {
+                    if (r0 + q < n && !(ahead < limit)) cand_e[(unsigned)keys[r0 + q]] = -1.f;      // dropped (a weight is >= 0)
+                    ahead += w[q];
+                }
+                __syncthreads();
+            }
+            // a dropped candidate weighs 0 from here on: it takes no part in the sums and is never drawn
+            const float total = head_block_sum(cand_e, n, red);
+            float e[HEAD_CTL_PER_THREAD];
+            bool in[HEAD_CTL_PER_THREAD];
+            float mine = 0.f;
+            int kept = 0, my_last = -1;
+#pragma unroll
+            for (int q = 0; q < HEAD_CTL_PER_THREAD; ++q) {
+                const float x = (c0 + q < n) ? cand_e[c0 + q] : -1.f;
+                in[q] = x >= 0.f;
+                e[q] = fmaxf(x, 0.f);
+                mine += e[q];
+                if (in[q]) { ++kept; my_last = c0 + q; }
+            }
+            // inclusive scan of the threads' sums (Hillis-Steele, 8 steps): scan[.][tid] = weight of candidates [0, c0 + 5)
+            int cur = 0;
+            scan[0][tid] = mine;
+            __syncthreads();
+#pragma unroll
+            for (int off = 1; off < ER_WG; off <<= 1) {
+                const float x = scan[cur][tid] + (tid >= off ? scan[cur][tid - off] : 0.f);
+                scan[cur ^ 1][tid] = x;
+                cur ^= 1;
+                __syncthreads();
+            }
+            unsigned int r[4];
+            philox4x32_10((unsigned int)t, st.row_stream ? st.row_stream[b] : (unsigned int)b, 0u, 0u, P.seed_lo, P.seed_hi, r);
+            const float u = (float)(r[0] >> 8) * (1.0f / 16777216.0f);
+            const float target = u * total;
+            float acc = tid > 0 ? scan[cur][tid - 1] : 0.f;
+            int hit = 0x7fffffff;
+#pragma unroll
+            for (int q = 0; q < HEAD_CTL_PER_THREAD; ++q) {
+                acc += e[q];
+                if (in[q] && acc > target && hit == 0x7fffffff) hit = c0 + q;
+            }
+            if (hit != 0x7fffffff) atomicMin(&first_hit_s, hit);
+            if (kept) { atomicMax(&last_kept_s, my_last); atomicAdd(&n_kept_s, kept); }
+            __syncthreads();
+            if (tid == 0) {
+                const int slot = first_hit_s != 0x7fffffff ? first_hit_s : last_kept_s;   // rounding left u * total above the last sum
+                chosen_s = slot >= 0 ? cand_i[slot] : P.eos;
+                lp_policy_s = slot >= 0 ? logf(cand_e[slot] / total) : 0.f;
+            }
+            __syncthreads();
+        }
+        chosen = chosen_s;
+        lp_policy = lp_policy_s;
+        n_kept = n_kept_s;
+    }
+
+    if (tid == 0) {
+        if (no_candidate && running) *st.error = 1;
+        int next = running ? chosen : P.pad;
+        out_ids[(long long)b * out_ld + t] = (long long)next;
+        if (lp.lp_model) lp.lp_model[(long long)b * lp.ld + t] = (running && !no_candidate) ? lg[next] - raw_lse : 0.f;
+        if (lp.lp_policy) lp.lp_policy[(long long)b * lp.ld + t] = (running && !no_candidate) ? lp_policy : 0.f;
+        if (lp.n_kept) lp.n_kept[b] = running ? n_kept : 0;
+        st.tok[b] = next;
+        st.counter[b] = counter;
+        st.pos[b] = st.base_pos[b] + t;
+        st.ngen[b] = t + 1;
+        if (running && next == P.eos) {
+            st.unfinished[b] = 0;
+            st.eos_step[b] = t;
+            atomicSub(st.n_unfinished, 1);
+        }
+    }
+}
+
 }  // namespace er

@@ -486,6 +486,25 @@ def sample_head(logits, mode, grammar, step, last_tok, counter, unfinished, top_
     return list(nt), list(co), list(uo)
 
 
+def sample_head_ctl(logits, mode, grammar, step, last_tok, counter, unfinished, top_k=10, min_new=0, seed=0, eos=2, pad=0,
+                    temperature=1.0, top_p=1.0, sampling_top_k=None):
+    """One step of the sampling head with controls (``er_k_sample_head_ctl``).  ``top_k`` goes into ``er_decode_params`` as for
+    ``sample_head``; ``sampling_top_k`` (None: unset) is ``er_sampling.top_k``, where 0 means no top-k filter.  Returns
+    (next_tok, counter, unfinished, lp_model, lp_policy, n_kept) lists."""
+    lib = native.load_library()
+    B, V = logits.shape
+    p = native.ErDecodeParams(mode=mode, top_k=top_k, grammar=grammar, max_new_tokens=step + 1,
+                              min_new_tokens=min_new, seed=seed)
+    s = native.ErSampling(temperature=float(temperature), top_p=float(top_p), top_k=int(sampling_top_k or 0),
+                          top_k_set=0 if sampling_top_k is None else 1, logprobs=1)
+    nt, co, uo, nk = (C.c_int32 * B)(), (C.c_int32 * B)(), (C.c_int32 * B)(), (C.c_int32 * B)()
+    lm, lq = (C.c_float * B)(), (C.c_float * B)()
+    native.check(lib.er_k_sample_head_ctl(native.ptr(logits), C.byref(p), C.byref(s), V, eos, pad, B, step, native.i32_array(last_tok),
+                                          native.i32_array(counter), native.i32_array(unfinished), nt, co, uo, lm, lq, nk, _st()),
+                 "er_k_sample_head_ctl")
+    return list(nt), list(co), list(uo), list(lm), list(lq), list(nk)
+
+
 def philox4x32_10(counter, key):
     """Philox4x32-10 (Salmon et al., Random123) on the host: counter = 4 words, key = 2 words -> 4 words.
     The same rounds and constants as ``philox4x32_10`` in csrc/k_head.h."""

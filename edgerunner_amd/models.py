@@ -73,12 +73,15 @@ class _QueueJob:
 class _QueueEngine:
     """The engine ``edgerunner_amd.queue.QueueScheduler`` drives: admissions are prefills into cache rows of the native context."""
 
-    def __init__(self, lmm: "LMM", jobs: List[_QueueJob]):
+    def __init__(self, lmm: "LMM", jobs: List[_QueueJob], logprobs: bool = False):
         self.lmm, self.jobs, self.dec = lmm, jobs, lmm.mesh_decoder
+        self.logprobs = logprobs      # take() then returns (ids, float32 [2, n]): the job's model / policy log-probs
         # exact mode: the jobs of one admit call that share a prefix length go through ONE forward pass (rows of a batched prefill
         # give the ids of their single runs, as LMM.generate's batches do).  Fast mode: one row per pass - the fp16-weight Linears of
         # the prefill pick their kernel by the row count of the pass, so only a one-row pass is bit-identical to the job run alone.
-        self.rows_per_pass = 1 if lmm.precision == "fp16" else 32
+        # With log-probs kept, exact mode prefills one row per pass too: a batched prefill gives a job the ids of its single run but may
+        # round its first logits differently in the last place, and the job's log-probs are promised bit for bit.
+        self.rows_per_pass = 1 if lmm.precision == "fp16" or logprobs else 32
 
     def embeds(self, job: _QueueJob) -> torch.Tensor:
         """inputs_embeds [1, S, hidden] of the job, built exactly as LMM.generate_ids builds them for a batch of one."""
@@ -105,7 +108,10 @@ class _QueueEngine:
         return self.dec.queue_run()
 
     def take(self, slot: int):
-        return self.dec.queue_take(slot, max(j.budget for j in self.jobs))
+        cap = max(j.budget for j in self.jobs)
+        lp = self.dec.queue_row_logprobs(slot, cap) if self.logprobs else None
+        ids = self.dec.queue_take(slot, cap)
+        return ids if lp is None else (ids, lp[:, : len(ids)].copy())
 
 
 class _Embd:
@@ -156,6 +162,8 @@ class LMM:
         self._sources: List[tuple] = []        # (state_dict reference, strict) of every load_state_dict call, for re-creation
         self.training = False
         self._released = False                 # release_checkpoint() was called: the context cannot be re-created
+        self.last_logprobs = None              # generate(output_logprobs=True): {"model", "policy"} float32 [B, n] on the device
+        self.last_queue_logprobs = None        # generate_queue(output_logprobs=True): per job (model, policy) numpy arrays
         if precision is not None:
             self._materialize()
 
@@ -334,8 +342,16 @@ class LMM:
     # -- generation ---------------------------------------------------------------------------
     @torch.no_grad()
     def generate_ids(self, conds, num_faces=1000, resume_ids=None, tokenizer=None, max_new_tokens=None,
-                     min_new_tokens: int = 0, seed: Optional[int] = None, row_streams=None, share_prefix: bool = False) -> torch.Tensor:
+                     min_new_tokens: int = 0, seed: Optional[int] = None, row_streams=None, share_prefix: bool = False, *,
+                     temperature: Optional[float] = None, top_p: Optional[float] = None, top_k: Optional[int] = None,
+                     output_logprobs: bool = False) -> torch.Tensor:
         """Everything of LMM.generate up to the HF call's return value (core/models.py:215-303).
+
+        ``temperature`` / ``top_p`` / ``top_k`` (None: the reference's call, ``top_k=10`` in sample mode; ``top_k=0``: no top-k
+        filter) shape the draw of sample mode as HF's warpers do; greedy mode accepts them and picks the same ids.
+        ``output_logprobs=True`` leaves ``last_logprobs = {"model", "policy"}``, float32 [B, n] on the device for the n id columns
+        returned: the model's log-softmax at the chosen id (``score``'s ``-nll``) and the id's log-probability in the distribution
+        it was taken from (greedy: log-softmax of the grammar-masked row).  Otherwise ``last_logprobs`` is None.
 
         ``share_prefix=True``: rows whose ``conds`` entries are bit-equal (``prefix_leaders``) form a group, and every decode step reads
         the group's cond + BOS prefix (num_cond_tokens + 1 cache positions; one ``num_faces`` per call, so ``resume_ids`` may differ
@@ -368,12 +384,24 @@ class LMM:
             kwargs["num_beams"] = 1
         elif opt.generate_mode == "sample":
             kwargs["do_sample"] = True
-            kwargs["top_k"] = 10
-        return self.mesh_decoder.generate(**kwargs)
+            kwargs["top_k"] = 10 if top_k is None else top_k
+        if temperature is not None:
+            kwargs["temperature"] = temperature
+        if top_p is not None:
+            kwargs["top_p"] = top_p
+        if top_k is not None and opt.generate_mode != "sample":
+            kwargs["top_k"] = top_k          # checked like the others; greedy does not use it
+        if output_logprobs:
+            kwargs["output_logprobs"] = True
+        self.last_logprobs = None
+        out = self.mesh_decoder.generate(**kwargs)
+        self.last_logprobs = self.mesh_decoder.last_logprobs
+        return out
 
     @torch.no_grad()
     def generate_queue(self, jobs, slots: int, tokenizer=None, max_new_tokens=None, min_new_tokens: int = 0,
-                       seed: Optional[int] = None, clean=True, check_every: int = 0):
+                       seed: Optional[int] = None, clean=True, check_every: int = 0, *, temperature: Optional[float] = None,
+                       top_p: Optional[float] = None, top_k: Optional[int] = None, output_logprobs: bool = False):
         """Serves independent jobs from ``slots`` cache rows (continuous batching, ``er_queue_*``) -> ``(meshes, all_tokens)`` in job
         order, as ``generate`` returns them for one job each.  A job is ``(conds [N,3] or [1,N,3], num_faces, resume_ids=None,
         stream=None, max_new_tokens=None)``; clouds of different sizes, different face counts and resume lengths may be mixed.  A job
@@ -381,13 +409,15 @@ class LMM:
         ``generate`` batch - no row rides on after its end.  ``all_tokens[j]`` has the job's own length (no PAD) with the resume
         prefix echoed; ``stream`` (default: the job's index) is the Philox stream of sample mode.  A job's ids are those of
         ``generate`` on that job alone (fp32; fp16: within one kernel class, slots <= 4 or slots > 4).  Afterwards
-        ``last_queue_stats`` holds the ``er_queue_stats`` counters and ``last_queue_slots[j]`` the slot job j ran in."""
+        ``last_queue_stats`` holds the ``er_queue_stats`` counters and ``last_queue_slots[j]`` the slot job j ran in.  The sampling
+        controls and ``output_logprobs`` are those of ``generate_ids``; with ``output_logprobs=True`` ``last_queue_logprobs[j]`` is the
+        pair (model, policy) of float32 numpy arrays over job j's generated tokens (its own length, the resume prefix not counted)."""
         from .meto import Engine, save_mesh
         from .queue import QueueScheduler
         opt = self.opt
         budget = opt.max_seq_length if max_new_tokens is None else int(max_new_tokens)
         jobs = [_QueueJob(j, spec, budget) for j, spec in enumerate(jobs)]
-        self.last_queue_stats, self.last_queue_slots = {}, []
+        self.last_queue_stats, self.last_queue_slots, self.last_queue_logprobs = {}, [], None
         if not jobs:
             return [], []
         fn = BuiltinGrammar(select_grammar(opt, tokenizer is not None), self.vocab_size, opt.eos_token_id)
@@ -399,14 +429,20 @@ class LMM:
         dec = self.mesh_decoder
         prefix = lambda j: opt.num_cond_tokens + 1 + (0 if j.resume is None else j.resume.shape[1])
         l_cap = max(prefix(j) + j.budget + 1 for j in jobs)
-        dec.queue_begin(int(slots), l_cap, max(j.budget for j in jobs), min_new_tokens, do_sample, 10, fn.er_grammar, seed, check_every)
+        dec.queue_begin(int(slots), l_cap, max(j.budget for j in jobs), min_new_tokens, do_sample, 10 if top_k is None else top_k,
+                        fn.er_grammar, seed, check_every, 1.0 if temperature is None else temperature,
+                        1.0 if top_p is None else top_p, output_logprobs)
         try:
             sched = QueueScheduler(int(slots))
-            ids = sched.serve(_QueueEngine(self, jobs), len(jobs))
+            ids = sched.serve(_QueueEngine(self, jobs, output_logprobs), len(jobs))
+            if output_logprobs:
+                self.last_queue_logprobs = [(lp[0], lp[1]) for _, lp in ids]
+                ids = [i for i, _ in ids]
             self.last_queue_stats = dec.queue_stats()
             self.last_queue_slots = list(sched.slot_of)
         finally:
             dec.queue_end()
+            dec.set_sampling()                 # the controls were the queue's: the context is back at its defaults
         meshes: List[Optional[object]] = []
         all_tokens: List[np.ndarray] = []
         for job, tokens in zip(jobs, ids):
@@ -421,12 +457,16 @@ class LMM:
 
     @torch.no_grad()
     def generate(self, conds, num_faces=1000, resume_ids=None, tokenizer=None, max_new_tokens=None, clean=True,
-                 min_new_tokens: int = 0, seed: Optional[int] = None, row_streams=None, share_prefix: bool = False):
-        """-> (meshes, all_tokens) like core/models.py:204-319.  ``share_prefix``: see ``generate_ids``.  ``tokenizer`` is a
+                 min_new_tokens: int = 0, seed: Optional[int] = None, row_streams=None, share_prefix: bool = False, *,
+                 temperature: Optional[float] = None, top_p: Optional[float] = None, top_k: Optional[int] = None,
+                 output_logprobs: bool = False):
+        """-> (meshes, all_tokens) like core/models.py:204-319.  ``share_prefix``, the sampling controls and ``output_logprobs``
+        (-> ``last_logprobs``, columns = the generated ids, without the resume prefix ``all_tokens`` echoes): see ``generate_ids``.  ``tokenizer`` is a
         ``edgerunner_amd.meto.Engine`` (or None for the 9-coordinate layout); each mesh is a
         ``edgerunner_amd.meto.Mesh`` - ``.vertices``, ``.faces``, ``.export(path)``, the members the reference's callers
         use of the trimesh objects it returns (trimesh itself is absent here); it still unpacks as ``v, f = mesh``."""
-        output_ids = self.generate_ids(conds, num_faces, resume_ids, tokenizer, max_new_tokens, min_new_tokens, seed, row_streams, share_prefix)
+        output_ids = self.generate_ids(conds, num_faces, resume_ids, tokenizer, max_new_tokens, min_new_tokens, seed, row_streams, share_prefix,
+                                       temperature=temperature, top_p=top_p, top_k=top_k, output_logprobs=output_logprobs)
         from .meto import Engine, save_mesh
         meshes: List[Optional[object]] = []
         all_tokens: List[np.ndarray] = []

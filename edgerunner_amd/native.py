@@ -36,6 +36,7 @@ EXPORTS = [
     "er_k_gemv", "er_k_gemv_form", "er_k_mlp_transpose", "er_k_mlp_sparse", "er_mlp_nnz", "er_k_attn_decode", "er_k_attn_stream_xt", "er_k_attn_shared", "er_k_attn_outproj3", "er_k_gemm", "er_k_gemm_f16", "er_k_gemm_hh", "er_k_gemm_hh_qkv", "er_k_gemm_hh_geglu", "er_k_gemm_f16s", "er_k_gemm_epi", "er_k_flash_attn_f16", "er_k_flash_attn_hh", "er_k_flash_attn_f32", "er_k_flash_attn_f16s", "er_k_layernorm", "er_k_softmax", "er_k_score_rows", "er_k_fps", "er_k_sample_head",
     "er_k_nn_dist2", "er_k_surface_sample", "er_k_fidelity_metrics",
     "er_queue_begin", "er_queue_admit", "er_queue_run", "er_queue_take", "er_queue_stats", "er_queue_end",
+    "er_set_sampling", "er_get_logprobs", "er_queue_row_logprobs", "er_k_sample_head_ctl",
 ]
 
 
@@ -92,6 +93,12 @@ class ErDitConfig(C.Structure):
 class ErDecodeParams(C.Structure):
     _fields_ = [("mode", C.c_int32), ("top_k", C.c_int32), ("grammar", C.c_int32),
                 ("max_new_tokens", C.c_int32), ("min_new_tokens", C.c_int32), ("seed", C.c_uint64)]
+
+
+class ErSampling(C.Structure):
+    """er_sampling: the controls above TopK and the log-prob switch (top_k is read only when top_k_set != 0; 0 then means no filter)."""
+    _fields_ = [("temperature", C.c_float), ("top_p", C.c_float), ("top_k", C.c_int32), ("top_k_set", C.c_int32),
+                ("logprobs", C.c_int32)]
 
 
 class ErQueueCounters(C.Structure):
@@ -198,6 +205,12 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.er_k_sample_head.argtypes = [vp, C.POINTER(ErDecodeParams), ci, ci, ci, ci, ci, C.POINTER(C.c_int32),
                                      C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                      C.POINTER(C.c_int32), C.POINTER(C.c_int32), vp]
+    f32p = C.POINTER(C.c_float)
+    lib.er_set_sampling.argtypes = [vp, C.POINTER(ErSampling)]
+    lib.er_get_logprobs.argtypes = [vp, vp, vp, ci, ci, vp]
+    lib.er_queue_row_logprobs.argtypes = [vp, ci, f32p, f32p, ci]
+    lib.er_k_sample_head_ctl.argtypes = [vp, C.POINTER(ErDecodeParams), C.POINTER(ErSampling), ci, ci, ci, ci, ci, i32p, i32p, i32p,
+                                         i32p, i32p, i32p, f32p, f32p, i32p, vp]
     for name in EXPORTS:
         fn = getattr(lib, name)
         if name not in ("er_last_error", "er_kernel_kind_name"):

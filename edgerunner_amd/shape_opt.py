@@ -61,6 +61,17 @@ def check_clouds(points: torch.Tensor, dims) -> None:
         raise ValueError("point_encoder_mode='downsample': the point clouds hold non-finite coordinates")
 
 
+def check_sampling(temperature, top_p, top_k) -> None:
+    """The ranges ``er_set_sampling`` accepts, refused here with the argument's name."""
+    import math
+    if not (isinstance(temperature, (int, float)) and math.isfinite(temperature) and temperature > 0):
+        raise ValueError(f"temperature={temperature!r}: a finite number > 0")
+    if not (isinstance(top_p, (int, float)) and 0 < top_p <= 1):
+        raise ValueError(f"top_p={top_p!r}: in (0, 1]")
+    if int(top_k) != top_k or top_k < 0:
+        raise ValueError(f"top_k={top_k!r}: an integer >= 0 (0: no top-k filter)")
+
+
 class NativeShapeOPT:
     def __init__(self, dims: ModelDims, opt, device: torch.device, weight_dtype=torch.float32,
                  kv_dtype=torch.float32):
@@ -90,6 +101,7 @@ class NativeShapeOPT:
         self.stream = torch.cuda.Stream(device=self.device)
         self._reserved = (0, 0)
         self.last_decode_ms = 0.0
+        self.last_logprobs = None     # {"model", "policy"}: float32 [B, n] on the device after a generate(output_logprobs=True)
         self.direct_loads = False     # weights loaded on this object directly (LMM.half()/float() cannot replay them)
 
     # -- lifetime ---------------------------------------------------------------------------
@@ -269,12 +281,20 @@ class NativeShapeOPT:
                  eos_token_id=None, max_new_tokens: Optional[int] = None,
                  prefix_allowed_tokens_fn: Optional[Callable] = None, num_beams: int = 1, do_sample: bool = False,
                  top_k: int = 50, min_new_tokens: int = 0, seed: Optional[int] = None, row_streams=None,
-                 prefix_groups=None, **unused) -> torch.Tensor:
+                 prefix_groups=None, temperature: float = 1.0, top_p: float = 1.0, output_logprobs: bool = False,
+                 **unused) -> torch.Tensor:
         """Drop-in for ``ShapeOPT.generate`` as called at core/models.py:303.
         ``num_tokens`` is accepted and ignored exactly like the reference decoder
-        ignores it (modeling_opt.py:324,467,546).  ``prefix_groups`` goes to ``prefill``."""
+        ignores it (modeling_opt.py:324,467,546).  ``prefix_groups`` goes to ``prefill``.
+
+        ``temperature``, ``top_k`` (0: no top-k filter) and ``top_p`` act in sample mode, in the order of HF's warpers; greedy mode
+        accepts them and picks the same ids.  ``output_logprobs=True`` leaves ``last_logprobs = {"model", "policy"}`` (float32
+        [B, n] on the device, n = the id columns returned; ``er_set_sampling`` in include/edgerunner_hip.h defines both), otherwise
+        ``last_logprobs`` is None.  With the defaults a call runs exactly the kernels it ran before the controls existed."""
         if num_beams != 1:
             raise NotImplementedError("beam search is not part of the reference's call (num_beams=1)")
+        check_sampling(temperature, top_p, top_k)
+        self.last_logprobs = None
         for name, got, want in (("pad", pad_token_id, self.opt.pad_token_id), ("bos", bos_token_id, self.opt.bos_token_id),
                                 ("eos", eos_token_id, self.opt.eos_token_id)):
             if got is not None and got != want:
@@ -290,10 +310,25 @@ class NativeShapeOPT:
         native.check(self.lib.er_set_row_streams(self._ctx, arr, B), "er_set_row_streams")
         if prefix_allowed_tokens_fn is None or isinstance(prefix_allowed_tokens_fn, BuiltinGrammar):
             grammar = native.ER_GRAMMAR_NONE if prefix_allowed_tokens_fn is None else prefix_allowed_tokens_fn.er_grammar
-            return self._decode_device(B, max_new_tokens, min_new_tokens, do_sample, top_k, grammar, seed)
-        return self._decode_stepwise(B, max_new_tokens, min_new_tokens, do_sample, top_k, prefix_allowed_tokens_fn)
+            return self._decode_device(B, max_new_tokens, min_new_tokens, do_sample, top_k, grammar, seed,
+                                       temperature, top_p, output_logprobs)
+        return self._decode_stepwise(B, max_new_tokens, min_new_tokens, do_sample, top_k, prefix_allowed_tokens_fn,
+                                     temperature, top_p, output_logprobs)
 
-    def _decode_device(self, B, T, min_new, do_sample, top_k, grammar, seed):
+    def set_sampling(self, temperature: float = 1.0, top_p: float = 1.0, top_k: Optional[int] = None, logprobs: bool = False):
+        """``er_set_sampling``: sticky until the next call; all defaults restore the library's (``top_k=None`` leaves top-k to the
+        decode parameters, 0 switches the filter off)."""
+        check_sampling(temperature, top_p, 0 if top_k is None else top_k)
+        if temperature == 1.0 and top_p == 1.0 and top_k is None and not logprobs:
+            native.check(self.lib.er_set_sampling(self._ctx, None), "er_set_sampling")
+            return
+        s = native.ErSampling(temperature=float(temperature), top_p=float(top_p), top_k=int(top_k or 0),
+                              top_k_set=0 if top_k is None else 1, logprobs=1 if logprobs else 0)
+        native.check(self.lib.er_set_sampling(self._ctx, C.byref(s)), "er_set_sampling")
+
+    def _decode_device(self, B, T, min_new, do_sample, top_k, grammar, seed, temperature=1.0, top_p=1.0, output_logprobs=False):
+        # top_k > 0 travels in the decode parameters, as it always has; only "no filter" needs the controls' own field
+        self.set_sampling(temperature, top_p, 0 if (do_sample and int(top_k) == 0) else None, output_logprobs)
         if seed is None:
             # the reference draws with torch.multinomial on the GLOBAL generator, which advances on every call:
             # repeated generate() calls give different samples and torch.manual_seed() reproduces a whole script.
@@ -310,16 +345,26 @@ class NativeShapeOPT:
         ms = C.c_float(0)
         self.lib.er_last_decode_ms(self._ctx, C.byref(ms))
         self.last_decode_ms = float(ms.value)
+        if output_logprobs:
+            with self._enter():
+                lp = torch.empty((2, B, n.value), dtype=torch.float32, device=self.device)
+                native.check(self.lib.er_get_logprobs(self._ctx, native.ptr(lp[0]), native.ptr(lp[1]), n.value, n.value, self._sp()),
+                             "er_get_logprobs")
+            self._exit()
+            self.last_logprobs = {"model": lp[0], "policy": lp[1]}
         return out[:, : n.value]
 
-    def _decode_stepwise(self, B, T, min_new, do_sample, top_k, fn):
+    def _decode_stepwise(self, B, T, min_new, do_sample, top_k, fn, temperature=1.0, top_p=1.0, output_logprobs=False):
         """Arbitrary host callable: logits come back every step (like the reference's
-        host loop); the forward passes still run in the HIP library."""
+        host loop); the forward passes still run in the HIP library.  Temperature, top-k (0: none) and top-p mean what they mean
+        to the device head, and the same two log-probs are kept."""
         eos, pad = self.opt.eos_token_id, self.opt.pad_token_id
         ids = torch.empty((B, 0), dtype=torch.long)
         unfinished = torch.ones(B, dtype=torch.long)
+        lp_model, lp_policy = [], []
         for t in range(T):
             s = self.logits().float().cpu()
+            raw_lsm = torch.log_softmax(s, dim=-1) if output_logprobs else None
             if t < min_new:
                 s[:, eos] = -float("inf")
             mask = torch.full_like(s, -float("inf"))
@@ -330,26 +375,44 @@ class NativeShapeOPT:
                 mask[b, allowed] = 0
             s = s + mask
             if do_sample:
-                k = min(top_k, s.shape[-1])
-                kth = torch.topk(s, k)[0][..., -1, None]
-                s = s.masked_fill(s < kth, -float("inf"))
+                s = s / temperature
+                if top_k > 0:
+                    k = min(top_k, s.shape[-1])
+                    kth = torch.topk(s, k)[0][..., -1, None]
+                    s = s.masked_fill(s < kth, -float("inf"))
+                if top_p < 1.0:      # TopPLogitsWarper, min_tokens_to_keep=1: keep while the mass strictly ahead is < top_p
+                    srt, order = torch.sort(s, dim=-1, descending=True, stable=True)
+                    probs = torch.softmax(srt, dim=-1)
+                    drop = (probs.cumsum(dim=-1) - probs) >= top_p
+                    drop[..., 0] = False
+                    s = s.masked_fill(drop.scatter(-1, order, drop), -float("inf"))
                 nxt = torch.multinomial(torch.softmax(s, dim=-1), 1).squeeze(1)
             else:
                 nxt = torch.argmax(s, dim=-1)
+            if output_logprobs:
+                live = unfinished.float()
+                lp_model.append(raw_lsm.gather(-1, nxt[:, None]).squeeze(1) * live)
+                lp_policy.append(torch.log_softmax(s, dim=-1).gather(-1, nxt[:, None]).squeeze(1) * live)
             nxt = nxt * unfinished + pad * (1 - unfinished)
             ids = torch.cat([ids, nxt[:, None]], dim=-1)
             unfinished = unfinished & (nxt != eos).long()
             if unfinished.max() == 0 or t == T - 1:
                 break
             self.feed(nxt)
+        if output_logprobs:
+            self.last_logprobs = {"model": torch.stack(lp_model, dim=1).to(self.device, torch.float32),
+                                  "policy": torch.stack(lp_policy, dim=1).to(self.device, torch.float32)}
         return ids.to(self.device)
 
     # -- queue mode (continuous batching): thin bindings of er_queue_* -------------------------
     def queue_begin(self, slots: int, l_cap: int, max_new_tokens: int, min_new_tokens: int = 0, do_sample: bool = False,
-                    top_k: int = 10, grammar: int = native.ER_GRAMMAR_NONE, seed: int = 0, check_every: int = 0):
-        """Reserves ``slots`` cache rows of ``l_cap`` positions and opens the queue on them (every row parked)."""
+                    top_k: int = 10, grammar: int = native.ER_GRAMMAR_NONE, seed: int = 0, check_every: int = 0,
+                    temperature: float = 1.0, top_p: float = 1.0, output_logprobs: bool = False):
+        """Reserves ``slots`` cache rows of ``l_cap`` positions and opens the queue on them (every row parked).  The sampling controls
+        and ``output_logprobs`` are those of ``generate``; they hold for the whole queue (``queue_row_logprobs``)."""
         if self._reserved[0] != slots or self._reserved[1] < l_cap:
             self.reserve(slots, l_cap)
+        self.set_sampling(temperature, top_p, 0 if (do_sample and int(top_k) == 0) else None, output_logprobs)
         p = native.ErDecodeParams(mode=native.ER_SAMPLE if do_sample else native.ER_GREEDY, top_k=int(top_k), grammar=int(grammar),
                                   max_new_tokens=int(max_new_tokens), min_new_tokens=int(min_new_tokens),
                                   seed=int(seed) & 0xFFFFFFFFFFFFFFFF)
@@ -386,6 +449,16 @@ class NativeShapeOPT:
         native.check(self.lib.er_queue_take(self._ctx, int(row), buf.ctypes.data_as(C.POINTER(C.c_int64)), int(capacity), C.byref(n)),
                      "er_queue_take")
         return buf[: n.value].copy()
+
+    def queue_row_logprobs(self, row: int, capacity: int):
+        """(model, policy) float32 numpy arrays of the finished job in ``row``, of the job's own length; call it before ``queue_take``."""
+        import numpy as np
+        cap = max(1, int(capacity))
+        buf = np.zeros((2, cap), dtype=np.float32)
+        f32p = C.POINTER(C.c_float)
+        native.check(self.lib.er_queue_row_logprobs(self._ctx, int(row), buf[0].ctypes.data_as(f32p), buf[1].ctypes.data_as(f32p), cap),
+                     "er_queue_row_logprobs")
+        return buf
 
     def queue_stats(self) -> Dict[str, float]:
         s = native.ErQueueCounters()

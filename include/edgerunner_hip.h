@@ -175,6 +175,34 @@ int er_decode(er_ctx* ctx, const er_decode_params* p, int64_t* out_ids_dev,
  * same property for its serial loop). */
 int er_set_row_streams(er_ctx* ctx, const uint32_t* ids_host, int n);
 
+/* ---- sampling controls and per-token log-probs.  What HF's warpers add above the reference's TopK(10), in HF's order (temperature,
+ * top-k, top-p), and the two log-probabilities of every chosen id:
+ *   model  = logits[id] - logsumexp(logits) over the raw row of the step (-nll of er_score at that position);
+ *   policy = log of the probability the id had in the distribution it was taken from: after mask, temperature, top-k and top-p in
+ *            sample mode, log_softmax of the masked row in greedy mode.  A finished row's PAD carries 0 and 0.
+ * temperature: s / temperature, finite and > 0.  top_k: used when top_k_set != 0, and then 0 means no top-k filter; otherwise
+ * er_decode_params.top_k decides, as before.  top_p in (0, 1]: in the order (probability descending, lower id first) a candidate stays
+ * iff the mass strictly ahead of it is < top_p (TopPLogitsWarper, min_tokens_to_keep = 1).  The draw stays the inverse CDF in ascending
+ * token id from the Philox uniform of (seed, step, row stream).
+ * Sticky until changed, like er_set_row_streams, and kept across er_kv_reserve; NULL restores the defaults {1, 1, unset, off}.  er_decode
+ * and er_queue_begin read it.  While everything is at its default a call launches exactly the kernels and the captured step it launched
+ * before this entry existed; otherwise the step ends in a second head kernel (captured separately, er_ctx_plan is unchanged) which, at
+ * temperature 1, top_p 1 and top_k > 0, picks the ids of the first.  ER_ERR_INVALID names the field that is out of range; it is also
+ * the answer while a queue is open (er_queue_begin has read the controls: er_queue_end first).
+ * With logprobs on, a one-row context runs its step with the kernels that 2 .. 4 rows run (split attention + merge, row fc1 /
+ * fc2) in place of its own (version 3, the fused MLP): in exact mode a job's log-probs are then the same bits alone and in a queue of up to 4 slots. */
+typedef struct {
+    float   temperature;
+    float   top_p;
+    int32_t top_k;
+    int32_t top_k_set;           /* 0: er_decode_params.top_k decides */
+    int32_t logprobs;            /* != 0: keep model / policy log-probs of every step (device buffers [B][l_cap], allocated at first use) */
+} er_sampling;
+int er_set_sampling(er_ctx* ctx, const er_sampling* s);
+/* After an er_decode that ran with logprobs on: the first n_steps columns (n_steps <= what er_decode returned) of the two tables into
+ * float[B, ld] device buffers (either may be NULL). */
+int er_get_logprobs(er_ctx* ctx, float* model_out_dev, float* policy_out_dev, int ld, int n_steps, void* stream);
+
 /* ---- queue mode (continuous batching): a list of independent jobs served from the fixed rows ("slots") of one reserved cache.
  * er_decode runs a batch until its LONGEST row ends; here a row is handed back as soon as its job emits EOS or spends its token
  * budget, and the next job is prefilled into that row while the other rows keep their state.  Between two steps a row's whole state
@@ -211,6 +239,9 @@ int er_queue_admit(er_ctx* ctx, int row0, int n_rows, const float* embeds_dev, i
 int er_queue_run(er_ctx* ctx, int32_t* done_rows_host, int32_t* n_done, void* stream);
 /* The ids of the finished job in `row`: ids_out_host[0, *n_tokens), *n_tokens = index of EOS + 1, or the budget; no PAD.  Parks the row. */
 int er_queue_take(er_ctx* ctx, int row, int64_t* ids_out_host, int capacity, int32_t* n_tokens);
+/* The log-probs of the finished job in `row` (queue opened with er_sampling.logprobs on): as many entries as er_queue_take will give ids,
+ * into host arrays of `capacity` floats (either may be NULL).  Valid for a done row until that row is taken. */
+int er_queue_row_logprobs(er_ctx* ctx, int row, float* model_out_host, float* policy_out_host, int capacity);
 int er_queue_stats(er_ctx* ctx, er_queue_counters* out);
 /* Closes the queue (jobs still in their rows are dropped) and leaves the context as a fresh er_kv_reserve does: row streams are the
  * identity again, every row's budget is er_decode's max_new_tokens, er_prefill is required before er_decode. */
@@ -576,6 +607,13 @@ int er_k_sample_head(const float* logits_dev, const er_decode_params* p, int voc
                      int batch, int step, const int32_t* last_tok_host, const int32_t* counter_host,
                      const int32_t* unfinished_host, int32_t* next_tok_host, int32_t* counter_out_host,
                      int32_t* unfinished_out_host, void* stream);
+/* The same step through the head with controls (er_set_sampling; s == NULL: the defaults), and what it adds: the two log-probs of the
+ * chosen id and the number of candidates the draw chose from (0: greedy, a finished row), each [batch] on the host. */
+int er_k_sample_head_ctl(const float* logits_dev, const er_decode_params* p, const er_sampling* s, int vocab, int eos, int pad,
+                         int batch, int step, const int32_t* last_tok_host, const int32_t* counter_host,
+                         const int32_t* unfinished_host, int32_t* next_tok_host, int32_t* counter_out_host,
+                         int32_t* unfinished_out_host, float* lp_model_host, float* lp_policy_host, int32_t* n_kept_host,
+                         void* stream);
 
 #ifdef __cplusplus
 }

@@ -33,6 +33,13 @@ ER_INFER_SHARE_PREFIX=1 passes ``share_prefix=True`` to the batched path's ``LMM
 the same cloud (--test_repeat samples of one input) read their common cond + BOS prefix once per decode step instead of once per job
 (calls of more than 4 jobs; see ``LMM.generate_ids``).  Same output files.  It cannot be combined with ER_INFER_QUEUE=1 (the queue's
 rows change owners; groups in queue mode are not built): both together are refused at start.  Without the variable nothing changes.
+
+ER_INFER_TEMPERATURE, ER_INFER_TOP_P and ER_INFER_TOP_K (0: no top-k filter) shape the draws of ``--generate_mode sample`` as HF's
+warpers do, in that order; unset, the reference's TopK(10) at temperature 1 stays.  ER_INFER_LOGPROBS=1 writes
+``{name}_{i}_{n}f_logprobs.npy`` beside every tokens file: float32 [n, 2], one row per token of the tokens file (cut at EOS the same way),
+columns = the model's log-probability of the token and its log-probability under the distribution it was drawn from
+(``LMM.generate_ids``); the log line of a job carries the sum of the model column.  Batch, queue and share-prefix mode alike.  A value
+that does not parse or is out of range ends the run with the variable's name.  Without the variables nothing changes.
 """
 from __future__ import annotations
 
@@ -54,6 +61,39 @@ from edgerunner_amd.models import LMM  # noqa: E402
 from edgerunner_amd.options import parse_cli  # noqa: E402
 from edgerunner_amd.meto import get_tokenizer  # noqa: E402
 from edgerunner_amd.utils import seed_everything, trim_tokens  # noqa: E402
+
+
+def sampling_from_env(env=None) -> dict:
+    """The keyword arguments ER_INFER_TEMPERATURE / ER_INFER_TOP_P / ER_INFER_TOP_K / ER_INFER_LOGPROBS add to ``LMM.generate`` and
+    ``LMM.generate_queue`` ({} when none is set).  A bad value ends with SystemExit naming the variable."""
+    env = os.environ if env is None else env
+    out = {}
+
+    def read(name, conv, ok, want):
+        raw = env.get(name)
+        if raw is None or raw == "":
+            return None
+        try:
+            v = conv(raw)
+        except ValueError:
+            v = None
+        if v is None or not ok(v):
+            raise SystemExit(f"[ERROR] {name}={raw!r}: {want}")
+        return v
+
+    t = read("ER_INFER_TEMPERATURE", float, lambda v: np.isfinite(v) and v > 0, "a finite number > 0")
+    p = read("ER_INFER_TOP_P", float, lambda v: 0 < v <= 1, "a number in (0, 1]")
+    k = read("ER_INFER_TOP_K", int, lambda v: v >= 0, "an integer >= 0 (0: no top-k filter)")
+    lp = read("ER_INFER_LOGPROBS", int, lambda v: v in (0, 1), "0 or 1")
+    if t is not None:
+        out["temperature"] = t
+    if p is not None:
+        out["top_p"] = p
+    if k is not None:
+        out["top_k"] = k
+    if lp:
+        out["output_logprobs"] = True
+    return out
 
 
 def load_points(opt, path):
@@ -98,6 +138,7 @@ def max_rows_per_call(opt, model, max_new_tokens, device) -> int:
 
 def main(argv=None):
     opt = parse_cli(argv)
+    sampling = sampling_from_env()
     share_prefix = os.environ.get("ER_INFER_SHARE_PREFIX") == "1"
     if share_prefix and os.environ.get("ER_INFER_QUEUE") == "1":
         raise SystemExit("[ERROR] ER_INFER_SHARE_PREFIX=1 and ER_INFER_QUEUE=1 cannot be combined: prefix groups are not built for queue mode")
@@ -156,12 +197,16 @@ def main(argv=None):
     rows_max = max_rows_per_call(opt, model, opt.test_max_seq_length, device)
     local_streams = {}
 
-    def save_job(j, mesh, tokens, note):
+    def save_job(j, mesh, tokens, note, logprobs=None):
         path, i, num_faces = jobs[j]
         name = os.path.splitext(os.path.basename(path))[0]
         toks = trim_tokens(tokens)
         filename = f"{name}_{i}" + (f"_{num_faces}f" if opt.use_num_face_cond else "")
         np.save(f"{opt.workspace}/{filename}_tokens.npy", toks)
+        if logprobs is not None:      # (model, policy) over the generated ids: the rows of the tokens the file above holds
+            lp = np.stack([np.asarray(logprobs[0], dtype=np.float32)[: len(toks)], np.asarray(logprobs[1], dtype=np.float32)[: len(toks)]], axis=1)
+            np.save(f"{opt.workspace}/{filename}_logprobs.npy", lp)
+            note = f"{note}, model log-prob {float(lp[:, 0].sum()):.4f}"
         if mesh is not None:
             mesh.export(f"{opt.workspace}/{filename}.ply")               # reference infer.py:120
         local_streams[j] = toks
@@ -174,12 +219,14 @@ def main(argv=None):
         specs = [(torch.from_numpy(clouds[jobs[j][0]]).float(), jobs[j][2], None, j) for j in mine]
         t0 = time.time()
         meshes, tokens = model.generate_queue(specs, slots, tokenizer=tokenizer, max_new_tokens=opt.test_max_seq_length,
-                                              clean=True, seed=opt.seed)
+                                              clean=True, seed=opt.seed, **sampling)
         torch.cuda.synchronize()
         dt = time.time() - t0
         st = model.last_queue_stats
+        qlp = model.last_queue_logprobs
         for r, j in enumerate(mine):
-            save_job(j, meshes[r], tokens[r], f"{len(tokens[r])} generated, slot {model.last_queue_slots[r]} of {slots}")
+            save_job(j, meshes[r], tokens[r], f"{len(tokens[r])} generated, slot {model.last_queue_slots[r]} of {slots}",
+                     None if qlp is None else qlp[r])
         print(f"[INFO] queue: {len(mine)} jobs on {slots} slots in {dt:.4f}s, {st['steps']} steps, {st['occupied_row_steps']} occupied / "
               f"{st['wait_row_steps']} waiting / {st['parked_row_steps']} parked row-steps, prefill {st['prefill_ms']:.1f} ms, "
               f"decode {st['decode_ms']:.1f} ms")
@@ -192,11 +239,15 @@ def main(argv=None):
         # sample mode: job j draws from the Philox stream (opt.seed, step, j) whatever rows share its call
         meshes, tokens = model.generate(cond, num_faces=num_faces, max_new_tokens=opt.test_max_seq_length,
                                         tokenizer=tokenizer, clean=True, seed=opt.seed, row_streams=list(chunk),
-                                        **({"share_prefix": True} if share_prefix else {}))
+                                        **({"share_prefix": True} if share_prefix else {}), **sampling)
         torch.cuda.synchronize()
         dt = time.time() - t0
+        blp = model.last_logprobs
+        if blp is not None:
+            blp = (blp["model"].cpu().numpy(), blp["policy"].cpu().numpy())
         for r, j in enumerate(chunk):
-            save_job(j, meshes[r], tokens[r], f"time = {dt:.4f}s ({len(chunk)} jobs in this call)")
+            save_job(j, meshes[r], tokens[r], f"time = {dt:.4f}s ({len(chunk)} jobs in this call)",
+                     None if blp is None else (blp[0][r], blp[1][r]))
     # the one exchange of the sharded path: RCCL all-gather of the token streams (ids - 3, >= -3, so shift to >= 0)
     gathered = D.gather_token_streams([local_streams[j] + 3 for j in mine], len(jobs), device=device)
     if rank == 0:

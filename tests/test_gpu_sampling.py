@@ -1,0 +1,391 @@
+"""Temperature, top-k, top-p and per-token log-probs of the decode head on the GPU (csrc/k_head.h sample_head_ctl_kernel,
+er_set_sampling / er_get_logprobs / er_queue_row_logprobs): the new head picks the old head's ids at the defaults, filters as
+HF's warpers do (float64 restatement: tests/sampling_ref.py, checked against transformers in tests/test_sampling_cpu.py), reports the
+log-probs LMM.score reports, and leaves the default path - kernels, captured step, plan - as it was."""
+import contextlib
+import dataclasses
+import math
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import sampling_ref as R  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+DEV = "cuda:0"
+LOGIT_TOL = 1e-3          # as tests/test_gpu_parity.py / test_gpu_score.py
+B = 256
+CONFIGS = [(0.7, 10, 0.9), (1.3, 0, 0.8), (1.0, 50, 0.5), (0.5, 0, 0.95), (2.0, 10, 1.0), (2.0, 0, 0.99)]
+_CACHE = {}
+
+
+def make_lmm(num_layers=2, seed=0, style="perturbed", precision="fp32", fresh=False):
+    from edgerunner_amd import weights as W
+    from edgerunner_amd.models import LMM
+    from edgerunner_amd.options import config_defaults
+    key = (num_layers, seed, style, precision)
+    if fresh or key not in _CACHE:
+        opt = dataclasses.replace(config_defaults["ArAE"], num_layers=num_layers, generate_mode="greedy")
+        m = LMM(opt, DEV, precision=precision)
+        missing, unexpected = m.mesh_decoder.load_state_iter(W.iter_state_dict(opt, seed, style), strict=True)
+        assert not missing and not unexpected
+        if fresh:
+            return m
+        _CACHE[key] = m
+    return _CACHE[key]
+
+
+@contextlib.contextmanager
+def mode(lmm, generate_mode):
+    """LMM reads opt.generate_mode at every call: the same context serves greedy and sample calls."""
+    keep = lmm.opt
+    lmm.opt = dataclasses.replace(keep, generate_mode=generate_mode)
+    try:
+        yield lmm
+    finally:
+        lmm.opt = keep
+
+
+def clouds(ids, n=256):
+    from edgerunner_amd import weights as W
+    return torch.cat([W.synthetic_point_cloud(i, n) for i in ids]).to(DEV)
+
+
+def rows_with_a_tie(V, seed):
+    """B rows of randn * 3 with a tie inside every row's top-10: the 4th largest value repeats the 3rd."""
+    x = torch.randn(B, V, generator=torch.Generator().manual_seed(seed)) * 3
+    top = torch.topk(x, 4, dim=-1).indices
+    x[torch.arange(B), top[:, 3]] = x[torch.arange(B), top[:, 2]]
+    return x
+
+
+def head_state(step, grammar):
+    """(last_tok, counter, unfinished) of B rows that exercise the grammar's branches; every 19th row is finished."""
+    last = [3 if b % 2 == 0 else 6 for b in range(B)]
+    counter = [0 if b % 2 == 0 else 1 + (b % 3) for b in range(B)]
+    unfinished = [0 if b % 19 == 7 else 1 for b in range(B)]
+    return last, counter, unfinished
+
+
+# ------------------------------------------------------------------ 1. at the defaults the new head is the old one
+@pytest.mark.parametrize("V", [518, 1030])
+def test_defaults_pick_what_sample_head_kernel_picks(V):
+    from edgerunner_amd import kernels as K
+    logits = rows_with_a_tie(V, 52).to(DEV)
+    for grammar in (0, 2):
+        for md in (0, 1):
+            for step in (0, 1, 17):
+                last, counter, unfinished = head_state(step, grammar)
+                old = K.sample_head(logits, md, grammar, step, last, counter, unfinished, top_k=10, seed=1234)
+                new = K.sample_head_ctl(logits, md, grammar, step, last, counter, unfinished, top_k=10, seed=1234)
+                assert new[0] == old[0], (grammar, md, step, "ids")
+                assert new[1] == old[1], (grammar, md, step, "counters")
+                assert new[2] == old[2], (grammar, md, step, "unfinished flags")
+                if md == 1 and grammar == 0:
+                    live = [b for b in range(B) if unfinished[b]]
+                    assert all(new[5][b] >= 10 for b in live) and len({new[0][b] for b in live}) > 10
+    # top_k wider than the default, and given through er_sampling: still the old kernel's draw
+    last, counter, unfinished = head_state(1, 0)
+    old = K.sample_head(logits, 1, 0, 1, last, counter, unfinished, top_k=50, seed=77)
+    new = K.sample_head_ctl(logits, 1, 0, 1, last, counter, unfinished, top_k=10, seed=77, sampling_top_k=50)
+    assert new[:3] == old
+
+
+# ------------------------------------------------------------------ 2. filters
+@pytest.fixture(scope="module")
+def row60():
+    return torch.randn(518, generator=torch.Generator().manual_seed(60)) * 3
+
+
+@pytest.mark.parametrize("temperature,top_k,top_p", CONFIGS)
+def test_filters_match_the_float64_restatement(row60, temperature, top_k, top_p):
+    from edgerunner_amd import kernels as K
+    s, keep, margin = R.filtered(row60, temperature, top_k, top_p)
+    n_ref = int(keep.sum())
+    print(f"(T={temperature}, k={top_k}, p={top_p}): reference keeps {n_ref}, margin {margin:.3e}, bound {n_ref * 2.0 ** -23:.3e}")
+    assert margin > n_ref * 2.0 ** -23, "the case sits too close to the nucleus boundary for an fp32 running sum"
+    logits = row60[None].repeat(B, 1).to(DEV)
+    step, seed = 3, 1234
+    nt, _, uo, lpm, lpp, nk = K.sample_head_ctl(logits, 1, 0, step, [7] * B, [0] * B, [1] * B, top_k=10, seed=seed,
+                                                temperature=temperature, top_p=top_p, sampling_top_k=top_k)
+    ref_policy, ref_model = R.policy_logprobs(s, keep), R.model_logprobs(row60)
+    worst_p = worst_m = 0.0
+    off_boundary = 0
+    for b in range(B):
+        assert nk[b] == n_ref, (b, nk[b], n_ref)
+        assert bool(keep[nt[b]]), (b, nt[b], "outside the reference's kept set")
+        worst_p = max(worst_p, abs(lpp[b] - float(ref_policy[nt[b]])))
+        worst_m = max(worst_m, abs(lpm[b] - float(ref_model[nt[b]])))
+        u = K.philox_uniform(seed, step, b)
+        ref, cdf = R.pick(s, keep, u)
+        if nt[b] != ref:      # only where u sits on a CDF boundary (fp32 summation)
+            off_boundary += 1
+            assert min(abs(float(cdf[nt[b]]) - u), abs(float(cdf[ref]) - u)) < 1e-5, (b, nt[b], ref, u)
+    print(f"  max |lp_policy - ref| {worst_p:.2e}, max |lp_model - ref| {worst_m:.2e}, {off_boundary} draws on a CDF boundary")
+    assert worst_p < 1e-5 and worst_m < 1e-5
+    if n_ref >= 3:
+        assert len(set(nt)) >= 3, "the sampler is not exploring the kept set"
+    assert all(uo[b] == (0 if nt[b] == 2 else 1) for b in range(B)), "only EOS closes a row"
+
+
+def test_filter_edges(row60):
+    from edgerunner_amd import kernels as K
+    V = 518
+    logits = row60[None].repeat(B, 1).to(DEV)
+    # top_p so small that one candidate survives: the argmax, with probability 1
+    nt, _, _, lpm, lpp, nk = K.sample_head_ctl(logits, 1, 0, 2, [7] * B, [0] * B, [1] * B, seed=5, temperature=1.3, top_p=1e-6,
+                                               sampling_top_k=0)
+    assert set(nt) == {int(row60.argmax())} and set(nk) == {1} and all(v == 0.0 for v in lpp)
+    assert max(abs(v - float(R.model_logprobs(row60)[nt[0]])) for v in lpm) < 1e-5
+    # grammar 2 with four legal ids (counter 1 -> 0: {3, 4, 5, eos}), uniform logits: masses ahead 0, .25, .5, .75 < 0.9
+    zeros = torch.zeros(B, V, device=DEV)
+    nt, co, _, lpm, lpp, nk = K.sample_head_ctl(zeros, 1, 2, 4, [6] * B, [1] * B, [1] * B, seed=7, temperature=0.8, top_p=0.9,
+                                                sampling_top_k=0)
+    assert set(nt) == {2, 3, 4, 5} and set(nk) == {4} and set(co) == {0}
+    assert max(abs(v - math.log(0.25)) for v in lpp) < 1e-5 and max(abs(v + math.log(V)) for v in lpm) < 1e-5
+    # ... and 0.7 drops the fourth (mass ahead 0.75): ids in (weight desc, id asc) order are 2, 3, 4 | 5
+    nt, _, _, _, lpp, nk = K.sample_head_ctl(zeros, 1, 2, 4, [6] * B, [1] * B, [1] * B, seed=7, temperature=0.8, top_p=0.7,
+                                             sampling_top_k=0)
+    assert set(nt) == {2, 3, 4} and set(nk) == {3} and max(abs(v - math.log(1 / 3)) for v in lpp) < 1e-5
+    # a finished row gives PAD, 0 and 0; its neighbours are untouched by it
+    unfinished = [0 if b % 5 == 0 else 1 for b in range(B)]
+    nt, _, uo, lpm, lpp, nk = K.sample_head_ctl(logits, 1, 0, 2, [7] * B, [0] * B, unfinished, seed=5, temperature=0.7, top_p=0.9)
+    for b in range(B):
+        if not unfinished[b]:
+            assert (nt[b], uo[b], lpm[b], lpp[b], nk[b]) == (0, 0, 0.0, 0.0, 0)
+        else:
+            assert nt[b] != 0 or row60.argmax() == 0
+            assert lpm[b] < 0 and lpp[b] <= 0 and nk[b] >= 1
+    # a row without a finite candidate closes with EOS, as sample_head_kernel's does (er_decode then fails on the error flag)
+    bad = logits.clone()
+    bad[3] = -math.inf
+    bad[4] = math.nan
+    old = K.sample_head(bad, 1, 0, 2, [7] * B, [0] * B, [1] * B, top_k=10, seed=5)
+    new = K.sample_head_ctl(bad, 1, 0, 2, [7] * B, [0] * B, [1] * B, top_k=10, seed=5, temperature=0.7, top_p=0.9)
+    for b in (3, 4):
+        assert new[0][b] == old[0][b] == 2 and new[2][b] == old[2][b] == 0
+    assert all(new[2][b] == 1 for b in range(B) if b not in (3, 4))
+
+
+# ------------------------------------------------------------------ 3. greedy log-probs
+@pytest.mark.parametrize("grammar", [0, 2])
+def test_greedy_logprobs(grammar):
+    from edgerunner_amd import kernels as K
+    V, step = 518, 5
+    x = rows_with_a_tie(V, 53)
+    last, counter, unfinished = head_state(step, grammar)
+    old = K.sample_head(x.to(DEV), 0, grammar, step, last, counter, unfinished)
+    nt, co, uo, lpm, lpp, nk = K.sample_head_ctl(x.to(DEV), 0, grammar, step, last, counter, unfinished, temperature=0.7, top_p=0.5)
+    assert (nt, co, uo) == tuple(old), "the controls do not change greedy ids"
+    worst = 0.0
+    for b in range(B):
+        if not unfinished[b]:
+            assert (nt[b], lpm[b], lpp[b]) == (0, 0.0, 0.0)
+            continue
+        masked = torch.where(R.grammar_mask(grammar, step, co[b], V), x[b], torch.full((V,), -math.inf))
+        assert nt[b] == int(masked.argmax())
+        worst = max(worst, abs(lpp[b] - float(torch.log_softmax(masked.double(), 0)[nt[b]])),
+                    abs(lpm[b] - float(R.model_logprobs(x[b])[nt[b]])))
+    print(f"greedy, grammar {grammar}: max log-prob error {worst:.2e}")
+    assert worst < 1e-5 and set(nk) == {0}
+
+
+# ------------------------------------------------------------------ er_set_sampling refuses what is out of range, by name
+def test_set_sampling_validation():
+    import ctypes as C
+    from edgerunner_amd import native
+    dec = make_lmm().mesh_decoder
+    for kw, name in ((dict(temperature=0.0), "temperature"), (dict(temperature=-1.0), "temperature"),
+                     (dict(temperature=float("inf")), "temperature"), (dict(temperature=float("nan")), "temperature"),
+                     (dict(top_p=0.0), "top_p"), (dict(top_p=1.5), "top_p"), (dict(top_p=float("nan")), "top_p"),
+                     (dict(top_k=-1, top_k_set=1), "top_k")):
+        s = native.ErSampling(**dict(dict(temperature=1.0, top_p=1.0, top_k=0, top_k_set=0, logprobs=0), **kw))
+        assert dec.lib.er_set_sampling(dec._ctx, C.byref(s)) == -1
+        assert name in dec.lib.er_last_error().decode(), (kw, dec.lib.er_last_error())
+    assert dec.lib.er_set_sampling(dec._ctx, None) == 0
+    with pytest.raises(NotImplementedError):
+        dec.generate(torch.zeros(1, 2, 1536), num_beams=2)
+
+
+# ------------------------------------------------------------------ 4. end to end against score()
+def scored_logprobs(lmm, pcs, ids):
+    """-nll of LMM.score at the positions that predict ids[b][t], data built as tests/test_gpu_score.py builds it."""
+    from edgerunner_amd.provider import collate_fn
+    items = [{"cond": pcs[b].cpu().numpy(), "num_faces": 1000, "coords": np.asarray(ids[b], dtype=np.int64), "len": len(ids[b]),
+              "azimuth": 0, "path": None} for b in range(len(ids))]
+    C = lmm.opt.num_cond_tokens
+    nll = lmm.score(collate_fn(items, lmm.opt))["nll"].cpu().numpy()
+    return -nll[:, C: C + len(ids[0])]           # position C + t (BOS at C) predicts ids[t]
+
+
+@pytest.mark.parametrize("generate_mode,kw", [("greedy", {}), ("sample", dict(temperature=0.8, top_p=0.9, top_k=0, seed=3))])
+def test_model_logprobs_are_what_score_reports(generate_mode, kw):
+    lmm = make_lmm()
+    pcs = clouds([0, 3])
+    with mode(lmm, generate_mode):
+        runs = []
+        for _ in range(2):
+            ids = lmm.generate_ids(pcs, 1000, tokenizer=object(), max_new_tokens=40, min_new_tokens=40, output_logprobs=True, **kw)
+            runs.append((ids.cpu().numpy(), {k: v.cpu().numpy() for k, v in lmm.last_logprobs.items()}))
+        assert lmm.generate_ids(pcs, 1000, tokenizer=object(), max_new_tokens=8, **kw) is not None and lmm.last_logprobs is None
+    (ids, lp), (ids2, lp2) = runs
+    assert ids.shape == (2, 40) and lp["model"].shape == lp["policy"].shape == (2, 40) and lp["model"].dtype == np.float32
+    assert np.array_equal(ids, ids2) and lp["model"].tobytes() == lp2["model"].tobytes() and lp["policy"].tobytes() == lp2["policy"].tobytes()
+    want = scored_logprobs(lmm, pcs, ids)
+    worst = float(np.abs(want - lp["model"]).max())
+    print(f"{generate_mode}: max |last_logprobs['model'] + nll| = {worst:.3e} over {ids.size} tokens")
+    assert worst < 2 * LOGIT_TOL
+    assert (lp["model"] < 0).all() and (lp["policy"] <= 0).all()
+    if generate_mode == "sample":
+        assert len(set(ids[0].tolist())) > 3 and not np.array_equal(ids[0], ids[1])
+        assert (lp["policy"] >= lp["model"] - 2 * LOGIT_TOL).sum() > 0
+
+
+# ------------------------------------------------------------------ 5. the default path is untouched
+@pytest.mark.parametrize("nb", [1, 5])
+def test_default_calls_do_not_see_the_controls(nb):
+    lmm = make_lmm()
+    pcs = clouds(list(range(nb)))
+    T = 24
+    call = lambda m, **kw: m.generate_ids(pcs, 1000, tokenizer=object(), max_new_tokens=T, min_new_tokens=T, **kw).cpu().numpy()
+    fresh = make_lmm(fresh=True)
+    with mode(fresh, "greedy"):
+        want_greedy = call(fresh)
+    with mode(fresh, "sample"):
+        want_sample = call(fresh, seed=3)
+    plan_fresh = fresh.mesh_decoder.plan()
+    fresh.mesh_decoder.close()
+    with mode(lmm, "greedy"):
+        g0 = call(lmm)
+        plan0 = lmm.mesh_decoder.plan()
+    with mode(lmm, "sample"):
+        c1 = call(lmm, temperature=0.8, top_p=0.9, seed=3)
+    with mode(lmm, "greedy"):
+        g1 = call(lmm)
+        glp = call(lmm, output_logprobs=True)
+        g2 = call(lmm)
+    with mode(lmm, "sample"):
+        s0 = call(lmm, seed=3)
+        c2 = call(lmm, temperature=0.8, top_p=0.9, top_k=0, seed=3, output_logprobs=True)
+        assert lmm.last_logprobs["model"].shape == (nb, T)
+        s1 = call(lmm, seed=3)
+        assert lmm.last_logprobs is None
+    assert lmm.mesh_decoder.plan() == plan0 == plan_fresh and plan0["batched"] == (1 if nb > 4 else 0)
+    for got in (g0, g1, glp, g2):
+        assert np.array_equal(got, want_greedy)
+    for got in (s0, s1):
+        assert np.array_equal(got, want_sample)
+    assert c1.shape == c2.shape == (nb, T)
+
+
+# ------------------------------------------------------------------ 6. queue
+def queue_against_single_runs(gold_eos, slots):
+    """3 jobs of the EOS model (tests/test_gpu_queue.py) through `slots` rows in sample mode with controls and log-probs, each against
+    generate() on that job alone with the same stream: ids and lengths asserted here; returns per job the largest |difference| of the
+    log-probs and whether both tables are equal bit for bit."""
+    lmm = make_lmm(4, 2, "reference")
+    from edgerunner_amd import weights as W
+    n = int(gold_eos["num_points"][0])
+    order = [0, 1, 3]
+    kw = dict(temperature=0.8, top_p=0.9, top_k=0, output_logprobs=True)
+    worst, same = [], []
+    with mode(lmm, "sample"):
+        jobs = [(W.synthetic_point_cloud(i, n).to(DEV), 1000, None, 100 + j) for j, i in enumerate(order)]
+        _, toks = lmm.generate_queue(jobs, slots=slots, tokenizer=object(), max_new_tokens=48, seed=5, check_every=4, **kw)
+        qlp = lmm.last_queue_logprobs
+        assert len(qlp) == 3 and max(lmm.last_queue_slots) == slots - 1
+        for j, i in enumerate(order):
+            _, alone = lmm.generate(W.synthetic_point_cloud(i, n).to(DEV), 1000, tokenizer=object(), max_new_tokens=48, seed=5,
+                                    row_streams=[100 + j], **kw)
+            want = alone[0]
+            cut = int(np.argmax(want == 2)) + 1 if 2 in want else len(want)
+            assert np.array_equal(toks[j], want[:cut]), j
+            ref = [lmm.last_logprobs[name][0, :cut].cpu().numpy() for name in ("model", "policy")]
+            for k in (0, 1):
+                assert qlp[j][k].dtype == np.float32 and qlp[j][k].shape == (cut,), (j, k)
+            assert (qlp[j][0] < 0).all() and (qlp[j][1] <= 0).all()
+            worst.append(max(float(np.abs(qlp[j][k] - ref[k]).max()) for k in (0, 1)))
+            same.append(all(qlp[j][k].tobytes() == ref[k].tobytes() for k in (0, 1)))
+        lmm.generate_queue(jobs[:1], slots=slots, tokenizer=object(), max_new_tokens=8, seed=5)
+        assert lmm.last_queue_logprobs is None
+    print(f"slots={slots}: lengths {[len(t) for t in toks]}, max |log-prob difference| per job {worst}, bit-equal {same}")
+    return worst, same
+
+
+def test_queue_jobs_carry_their_own_logprobs(gold_eos):
+    """3 jobs on 2 slots; ids, lengths and log-probs of every job against generate() on that job alone, the log-probs bit for bit.
+    The single run reserves one row, whose plan has kernels of its own (version-3 attention, the fused MLP); a generation that keeps
+    log-probs runs the kernels of 2 .. 4 rows in their place (KvMem::row_class), which makes the two runs the same arithmetic."""
+    worst, same = queue_against_single_runs(gold_eos, 2)
+    assert all(same), worst
+
+
+def test_queue_one_slot_logprobs_bit_for_bit(gold_eos):
+    """The same three jobs through ONE slot (the kernels of the single run): the slot's log-prob rows are rewritten job after job and
+    each job's are those of its single run, bit for bit."""
+    worst, same = queue_against_single_runs(gold_eos, 1)
+    assert all(same) and max(worst) == 0.0
+
+
+# ------------------------------------------------------------------ 7. infer.py
+def run_infer(args, env_extra):
+    env = dict(os.environ)
+    for k in ("ER_NO_GRAPH", "ER_INFER_QUEUE", "ER_INFER_SHARE_PREFIX", "ER_INFER_LOGPROBS", "ER_INFER_TEMPERATURE", "ER_INFER_TOP_P",
+              "ER_INFER_TOP_K"):
+        env.pop(k, None)
+    env.update(env_extra)
+    return subprocess.run([sys.executable, os.path.join(ROOT, "infer.py")] + [str(a) for a in args], env=env, cwd=ROOT,
+                          stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=600)
+
+
+@pytest.fixture(scope="module")
+def infer_inputs(tmp_path_factory):
+    from safetensors.torch import save_file
+    from edgerunner_amd import weights as W
+    from edgerunner_amd.options import config_defaults
+    d = tmp_path_factory.mktemp("sampling_infer")
+    opt = dataclasses.replace(config_defaults["ArAE"], num_layers=2, generate_mode="sample")
+    ckpt = str(d / "arae_2layers.safetensors")
+    save_file({k: v.contiguous() for k, v in W.make_state_dict(opt, 0, "perturbed").items()}, ckpt)
+    np.save(d / "a.npy", W.synthetic_point_cloud(0, 256)[0].numpy())
+    return d, ckpt
+
+
+@pytest.mark.parametrize("how", ["batch", "queue", "share_prefix"])
+def test_infer_py_writes_logprobs(infer_inputs, tmp_path, how):
+    d, ckpt = infer_inputs
+    extra = {"batch": {}, "queue": {"ER_INFER_QUEUE": "1"}, "share_prefix": {"ER_INFER_SHARE_PREFIX": "1"}}[how]
+    env = dict(extra, EDGERUNNER_PRECISION="fp32", ER_INFER_LOGPROBS="1", ER_INFER_TEMPERATURE="0.8", ER_INFER_TOP_P="0.9")
+    p = run_infer(["ArAE", "--num_layers", 2, "--resume", ckpt, "--test_path", d / "a.npy", "--generate_mode", "sample", "--test_num_face",
+                   1000, "--test_repeat", 5, "--test_max_seq_length", 32, "--seed", 5, "--workspace", tmp_path], env)
+    assert p.returncode == 0, p.stdout[-3000:]
+    assert "model log-prob" in p.stdout
+    for i in range(5):
+        toks = np.load(tmp_path / f"a_{i}_1000f_tokens.npy")
+        lp = np.load(tmp_path / f"a_{i}_1000f_logprobs.npy")
+        assert lp.dtype == np.float32 and lp.shape == (len(toks), 2), (i, lp.shape, toks.shape)
+        assert np.isfinite(lp).all() and (lp <= 0).all()
+    if how == "batch":
+        bad = run_infer(["ArAE", "--num_layers", 2, "--resume", ckpt, "--test_path", d / "a.npy", "--workspace", tmp_path / "bad"],
+                        {"ER_INFER_TOP_P": "1.5"})
+        assert bad.returncode != 0 and "ER_INFER_TOP_P" in bad.stdout
+
+
+# ------------------------------------------------------------------ 8. fast mode
+def test_fp16_context_with_controls_and_logprobs():
+    lmm = make_lmm(precision="fp16")
+    pcs = clouds([0, 3])
+    with mode(lmm, "sample"):
+        runs = []
+        for _ in range(2):
+            ids = lmm.generate_ids(pcs, 1000, tokenizer=object(), max_new_tokens=32, min_new_tokens=32, seed=3, temperature=0.8,
+                                   top_p=0.9, top_k=0, output_logprobs=True)
+            runs.append((ids.cpu().numpy(), lmm.last_logprobs["model"].cpu().numpy(), lmm.last_logprobs["policy"].cpu().numpy()))
+    assert np.array_equal(runs[0][0], runs[1][0]) and runs[0][1].tobytes() == runs[1][1].tobytes() and runs[0][2].tobytes() == runs[1][2].tobytes()
+    assert runs[0][1].shape == (2, 32) and (runs[0][1] <= 0).all() and (runs[0][2] <= 0).all() and np.isfinite(runs[0][1]).all()
