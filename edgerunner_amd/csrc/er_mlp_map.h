@@ -28,4 +28,26 @@ constexpr MlpSlot mlp_slot(int epl, int k) {
     return MlpSlot{s * 64 + q % 64, (q / 64) * epl + e};
 }
 
+// ---- The finish launch (mlp_finish_kernel<NC>; launched with NC = 32, the map holds for 8 and 16 as well): NC consecutive outputs per
+// workgroup, wave s = slice s.  The wave reads the NC * 4 bytes of each of its 64 chain vectors as 16-byte pieces: g = NC / 4 adjacent
+// lanes share one chain, so one wave-load covers 64 / g chains with g * 16 contiguous bytes each (NC = 32: eight whole 128-byte
+// lines), and a lane issues g loads.
+//     load j of lane l reads chain j * (64 / g) + l / g of the slice, piece l % g
+// The sum over the 64 chains is wave_sum's butterfly on the CHAIN index (xor 32, 16, 8, 4, 2, 1 in that order).  The chain's high bits
+// are the load index, its low bits sit in the lane's high bits, so level k (xor 32 >> k) is either an add of two of the lane's own
+// registers, r[j] + r[j ^ off], or the lanes l and l ^ off meeting: mlp_fin_level says which.  Both operands of every add are the ones
+// the butterfly adds at that level, hence the same bits (tests/host/mlp_finish_tree_check.cpp).
+constexpr bool mlp_fin_nc_ok(int nc) { return nc == 8 || nc == 16 || nc == 32; }
+constexpr int mlp_fin_group(int nc) { return nc / 4; }                           // g: lanes per chain = 16-byte pieces per chain = loads per lane
+constexpr int mlp_fin_chains_per_load(int nc) { return 64 / mlp_fin_group(nc); }
+constexpr int mlp_fin_chain(int nc, int load, int lane) { return load * mlp_fin_chains_per_load(nc) + lane / mlp_fin_group(nc); }
+constexpr int mlp_fin_piece(int nc, int lane) { return lane % mlp_fin_group(nc); }
+
+struct MlpFinLevel { bool reg; int off; };      // reg: r[j] + r[j ^ off] in every lane; else: lane l + lane l ^ off
+constexpr int MLP_FIN_LEVELS = 6;
+constexpr MlpFinLevel mlp_fin_level(int nc, int k) {      // level k = 0 .. 5 pairs the chains c and c ^ (32 >> k)
+    const int x = 32 >> k, cpl = mlp_fin_chains_per_load(nc);
+    return x >= cpl ? MlpFinLevel{true, x / cpl} : MlpFinLevel{false, x * mlp_fin_group(nc)};
+}
+
 }   // namespace er

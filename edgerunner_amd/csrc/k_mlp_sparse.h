@@ -15,8 +15,9 @@
 //                       either way.  FINITE weights are assumed: the row kernel would turn an Inf / NaN weight behind a zero activation
 //                       into NaN, here it is never read.  The 6 KB zero row is served by the caches: the HBM counters show
 //                       W1 + live rows * 6 KB per launch within 0.8 %.
-//   mlp_finish_kernel   rebuilds the row kernel's tree from the 256 partial vectors: the 64 chains of a slice through the same
-//                       wave_sum, the four slice sums in the order ((0 + p0) + p1) + p2) + p3, then + b2 + residual.
+//   mlp_finish_kernel   rebuilds the row kernel's tree from the 256 partial vectors: the 64 chains of a slice in wave_sum's order
+//                       (read as whole 128-byte lines, 32 outputs per workgroup), the four slice sums in the order
+//                       ((0 + p0) + p1) + p2) + p3, then + b2 + residual.
 //
 // Both results are therefore bit-identical to fc1 + fc2 of the row kernels (tests/test_gpu_mlp_sparse.py).  No inter-workgroup
 // wait: the finish is a launch, every word of the partial block is rewritten by every launch.
@@ -191,35 +192,53 @@ __global__ __launch_bounds__(MLP_TPB) void mlp_sparse_kernel(const void* pW1, co
         s.z = fmaf((float)wv[u].z, f[u], s.z);
         s.w = fmaf((float)wv[u].w, f[u], s.w);
     }
+    // a plain store: as a write-through (sc1) store it measured equal or slower in the decode loop (profiles/mlp_finish_bench.log)
     reinterpret_cast<f32x4*>(a.part + (long long)wg * K)[col] = s;
 }
 
-// NC consecutive outputs per workgroup: the wave of slice s reads the NC values of its 64 chains (lane l: chain (s, l)), sums them with
-// wave_sum, and NC threads add the four slice sums in slice order, + b2, + residual (gemv_kernel's split-K tail and
-// gemv_epilogue<EPI_RESID>).  The partial block is [chain][1536]: the fused kernel writes whole rows, this one gathers NC * 4 bytes
-// per chain.
-constexpr int MLP_FIN_NC = 8;
+// NC consecutive outputs per workgroup, wave s = slice s.  The partial block is [chain][1536] and the fused kernel writes whole rows,
+// so the finish gathers NC * 4 bytes per chain: g = NC / 4 adjacent lanes read one chain's bytes as 16-byte pieces, a wave-load
+// covers 64 / g chains and a lane issues g loads (er_mlp_map.h).  At NC = 32 a wave-load is eight whole 128-byte lines and no line
+// of the block is requested twice on the chip (48 workgroups); that form is the one launched.  With 32-byte pieces (NC = 8, 192
+// workgroups, every line wanted by four of them) the HBM-side counters showed 6.38 MB read for the 1.57 MB block, and the decode
+// loop ran 2.4 % slower; NC = 16 lay between.  The sum over the 64 chains is wave_sum's butterfly on the chain
+// index: the levels that pair two loads are adds of the lane's own registers, the others xor_sum steps across lanes (mlp_fin_level),
+// four outputs at a time.  Then NC threads add the four slice sums in slice order, + b2, + residual (gemv_kernel's split-K tail and
+// gemv_epilogue<EPI_RESID>).
+constexpr int MLP_FIN_NC = 32;
+template <int NC, int K>
+__device__ __forceinline__ void mlp_fin_tree_level(f32x4 (&r)[NC / 4]) {
+    constexpr MlpFinLevel lv = mlp_fin_level(NC, K);
+    if constexpr (lv.reg) {
+#pragma unroll
+        for (int j = 0; j < lv.off; ++j) r[j] = r[j] + r[j ^ lv.off];      // the loads above 2 * off are already folded in
+    } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) r[0][e] = xor_sum<lv.off>(r[0][e]);
+    }
+}
+
+template <int NC>
 __global__ __launch_bounds__(ER_WG) void mlp_finish_kernel(MlpArgs a) {
-    constexpr int NC = MLP_FIN_NC;
-    static_assert(MLP_HIDDEN % NC == 0 && NC % 4 == 0 && MLP_SLICES == ER_NWAVES, "finish shape");
-    __shared__ float red[NC * MLP_SLICES];
+    static_assert(mlp_fin_nc_ok(NC) && MLP_HIDDEN % NC == 0 && MLP_SLICES == ER_NWAVES && MLP_FIN_LEVELS == 6, "finish shape");
+    constexpr int G = mlp_fin_group(NC);
+    __shared__ __attribute__((aligned(16))) float red[MLP_SLICES * NC];
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, n0 = blockIdx.x * NC;
     float bias = 0.f, resid = 0.f;
     if (tid < NC) { bias = a.b2[n0 + tid]; resid = a.resid[n0 + tid]; }
-    const f32x4* p = reinterpret_cast<const f32x4*>(a.part + (long long)(wid * 64 + lane) * MLP_HIDDEN + n0);
-    f32x4 pv[NC / 4];
+    const float* p = a.part + (long long)wid * 64 * MLP_HIDDEN + n0 + mlp_fin_piece(NC, lane) * 4;
+    f32x4 r[G];
 #pragma unroll
-    for (int c = 0; c < NC / 4; ++c) pv[c] = p[c];
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-        const float t = wave_sum(pv[c / 4][c % 4]);
-        if (lane == 0) red[c * MLP_SLICES + wid] = t;
-    }
+    for (int j = 0; j < G; ++j) r[j] = *reinterpret_cast<const f32x4*>(p + (long long)mlp_fin_chain(NC, j, lane) * MLP_HIDDEN);
+    __builtin_amdgcn_sched_barrier(0);         // every chain request is out before the first one is consumed
+    mlp_fin_tree_level<NC, 0>(r); mlp_fin_tree_level<NC, 1>(r); mlp_fin_tree_level<NC, 2>(r);
+    mlp_fin_tree_level<NC, 3>(r); mlp_fin_tree_level<NC, 4>(r); mlp_fin_tree_level<NC, 5>(r);
+    if (lane < G) reinterpret_cast<f32x4*>(red + wid * NC)[lane] = r[0];      // the lanes of chain 0: one per piece
     __syncthreads();
     if (tid < NC) {
         float s = 0.f;
 #pragma unroll
-        for (int k = 0; k < MLP_SLICES; ++k) s += red[tid * MLP_SLICES + k];
+        for (int k = 0; k < MLP_SLICES; ++k) s += red[k * NC + tid];
         s += bias;
         s += resid;
         a.out[n0 + tid] = s;
@@ -233,7 +252,7 @@ inline hipError_t launch_mlp_fused(const MlpArgs& a, hipStream_t st) {
     return hipGetLastError();
 }
 inline hipError_t launch_mlp_finish(const MlpArgs& a, hipStream_t st) {
-    hipLaunchKernelGGL(mlp_finish_kernel, dim3(MLP_HIDDEN / MLP_FIN_NC), dim3(ER_WG), 0, st, a);
+    hipLaunchKernelGGL(mlp_finish_kernel<MLP_FIN_NC>, dim3(MLP_HIDDEN / MLP_FIN_NC), dim3(ER_WG), 0, st, a);
     return hipGetLastError();
 }
 
