@@ -2234,12 +2234,7 @@ extern "C" int er_k_flash_attn_f32(const float* q, const float* k, const float* 
     // q/o: [B, N, H*D], k/v: [B, M, H*D] fp32, heads side by side in a row; causal: key j visible to query i iff j <= i + (M - N)
     if (D != 64 && D != 96) return fail(ER_ERR_UNSUPPORTED, "er_k_flash_attn_f32: head_dim %d (64, 96)", D);
     if (causal && M < N) return fail(ER_ERR_INVALID, "er_k_flash_attn_f32: causal needs M >= N");
-    Flash32Args a{};
-    a.Q = q; a.K = k; a.V = v; a.O = o; a.N = N; a.M = M;
-    a.ldq = a.ldk = a.ldv = a.ldo = H * D;
-    a.qs_b = (long long)N * H * D; a.os_b = a.qs_b; a.ks_b = (long long)M * H * D; a.vs_b = a.ks_b;
-    a.qs_h = a.ks_h = a.vs_h = a.os_h = D;
-    a.sqrt_d = sqrtf((float)D); a.causal_off = M - N;
+    Flash32Args a = flash32_packed_args(q, k, v, o, H, N, M, D);
     DevBuf<float> po, pml;                                 // key-range split of the causal prefill shape (k_flash_attn_f32.h, KSP)
     if (flash32_ksplit(N, H, B, D, causal != 0)) {
         ERCHK(po.ensure(flash32_part_o_floats(B, H, N, D)));
@@ -2254,16 +2249,10 @@ extern "C" int er_k_flash_attn_f32(const float* q, const float* k, const float* 
 
 extern "C" int er_k_flash_attn_f16s(const float* q, const float* k, const float* v, float* o, int B, int H, int N, int M, int causal,
                                     void* stream) {
-    // STAGED (unmeasured): q/o [B, N, H*96], k/v [B, M, H*96] fp32 holding fp16-representable k / v values
+    // q/o [B, N, H*96], k/v [B, M, H*96] fp32 holding fp16-representable k / v values (the fast-mode prefill attention)
     if (causal && M < N) return fail(ER_ERR_INVALID, "er_k_flash_attn_f16s: causal needs M >= N");
     constexpr int D = 96;
-    Flash32Args a{};
-    a.Q = q; a.K = k; a.V = v; a.O = o; a.N = N; a.M = M;
-    a.ldq = a.ldk = a.ldv = a.ldo = H * D;
-    a.qs_b = (long long)N * H * D; a.os_b = a.qs_b; a.ks_b = (long long)M * H * D; a.vs_b = a.ks_b;
-    a.qs_h = a.ks_h = a.vs_h = a.os_h = D;
-    a.sqrt_d = sqrtf((float)D); a.causal_off = M - N;
-    HIPRET(launch_flash_attn_f16s(a, D, causal != 0, H, B, (hipStream_t)stream));
+    HIPRET(launch_flash_attn_f16s(flash32_packed_args(q, k, v, o, H, N, M, D), D, causal != 0, H, B, (hipStream_t)stream));
     return ER_OK;
 }
 

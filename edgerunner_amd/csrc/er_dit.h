@@ -423,6 +423,29 @@ static int dit_cross_kv(er_dit_ctx* c, const float* cond, int B, int M, hipStrea
     return 0;
 }
 
+// Fused-attention arguments of a DiT layer: N latent queries per sample over M keys, H heads of D side by side in rows of C; q, k (and v)
+// rows ldqkv apart (3 C inside the self-attention's fused qkv rows, C for the cross-attention's separate buffers), the output in rows of C.
+// LDS-DMA form: fp16 operands, V^T per head in rows of Mp keys (M padded to a multiple of 64)
+static FlashHArgs dit_flash_hh_args(const _Float16* q, const _Float16* k, const _Float16* vt, _Float16* o16, int N, int M, int Mp, int ldqkv,
+                                    int C, int H, int D) {
+    FlashHArgs fh{};
+    fh.Q = q; fh.K = k; fh.Vt = vt; fh.O16 = o16; fh.N = N; fh.M = M;
+    fh.ldq = fh.ldk = ldqkv; fh.ldvt = Mp; fh.ldo = C;
+    fh.qs_b = (long long)N * ldqkv; fh.ks_b = (long long)M * ldqkv; fh.vts_h = 64LL * Mp; fh.vts_b = (long long)H * 64 * Mp; fh.os_b = (long long)N * C;
+    fh.head_stride = D; fh.scale = 1.0f / sqrtf((float)D);
+    return fh;
+}
+// register-staged form: fp32 operands; the output goes to o16 INSTEAD of o when o16 is not null
+static FlashArgs dit_flash_args(const float* q, const float* k, const float* v, float* o, _Float16* o16, int N, int M, int ldqkv, int C, int D) {
+    FlashArgs fa{};
+    fa.Q = q; fa.K = k; fa.V = v; fa.O = o; fa.N = N; fa.M = M;
+    fa.ldq = fa.ldk = fa.ldv = ldqkv; fa.ldo = C;
+    fa.qs_b = (long long)N * ldqkv; fa.ks_b = fa.vs_b = (long long)M * ldqkv; fa.os_b = (long long)N * C;
+    fa.head_stride = D; fa.scale = 1.0f / sqrtf((float)D);
+    fa.O16 = o16;
+    return fa;
+}
+
 // DiT.forward body for B rows; their time embeddings temb [B][C] / tada [B][6 C] (dit_time_embed), cross K/V in c->kv2 (dit_cross_kv)
 static int dit_forward_impl(er_dit_ctx* c, const float* xin, int B, int M, float* out, const float* temb, const float* tada, hipStream_t st) {
     const er_dit_config& g = c->cfg;
@@ -488,22 +511,12 @@ static int dit_forward_impl(er_dit_ctx* c, const float* xin, int B, int M, float
         // x = x + gate_msa * attn1(x)                                               dit.py:133
         if (hh) {     // q, k leave the GEMM in fp16 only and V as V^T per head (its epilogue); K and V^T tiles then reach LDS by DMA
             HIPRET(dlin16(c, x16, C, L.qkv_w, L.qkv_b, nullptr, 3 * C, R, 3 * C, C, nullptr, 0, nullptr, 1, qkv16, st, vt16, N));
-            FlashHArgs fh{};
-            fh.Q = qkv16; fh.K = qkv16 + C; fh.Vt = vt16; fh.O16 = att16; fh.N = N; fh.M = N;
-            fh.ldq = fh.ldk = 3 * C; fh.ldvt = N; fh.ldo = C;
-            fh.qs_b = fh.ks_b = (long long)N * 3 * C; fh.vts_h = 64LL * N; fh.vts_b = (long long)H * 64 * N; fh.os_b = (long long)N * C;
-            fh.head_stride = D; fh.scale = 1.0f / sqrtf((float)D);
-            HIPRET(launch_flash_attn_hh(fh, H, B, st));
+            HIPRET(launch_flash_attn_hh(dit_flash_hh_args(qkv16, qkv16 + C, vt16, att16, N, N, N, 3 * C, C, H, D), H, B, st));
         } else {
         HIPRET(dlin(c, x, C, L.qkv_w, L.qkv_b, c->qkv.p, 3 * C, R, 3 * C, C, nullptr, 0, nullptr, 1, st));
         if (flash) {
-            FlashArgs fa{};
-            fa.Q = c->qkv.p; fa.K = c->qkv.p + C; fa.V = c->qkv.p + 2 * C; fa.O = c->att.p; fa.N = N; fa.M = N;
-            fa.ldq = fa.ldk = fa.ldv = 3 * C; fa.ldo = C;
-            fa.qs_b = fa.ks_b = fa.vs_b = (long long)N * 3 * C; fa.os_b = (long long)N * C;
-            fa.head_stride = D; fa.scale = 1.0f / sqrtf((float)D);
-            fa.O16 = att16;
-            HIPRET(launch_flash_attn_f16(fa, H, B, st));
+            const float* qkv = c->qkv.p;
+            HIPRET(launch_flash_attn_f16(dit_flash_args(qkv, qkv + C, qkv + 2 * C, c->att.p, att16, N, N, 3 * C, C, D), H, B, st));
         } else {
             for (int b = 0; b < B; ++b) {
                 float* base = c->qkv.p + (size_t)b * N * 3 * C;
@@ -524,21 +537,11 @@ static int dit_forward_impl(er_dit_ctx* c, const float* xin, int B, int M, float
         const float* v2 = k2 + (size_t)B * M * C;
         if (hh) {
             const int Mp = c->kv2_mp;
-            FlashHArgs fh{};
-            fh.Q = q2_16; fh.K = c->k2_16.p + (size_t)l * B * M * C;
-            fh.Vt = c->v2t16.p + (size_t)l * B * H * 64 * Mp; fh.O16 = att16; fh.N = N; fh.M = M;
-            fh.ldq = fh.ldk = C; fh.ldvt = Mp; fh.ldo = C;
-            fh.qs_b = (long long)N * C; fh.ks_b = (long long)M * C; fh.vts_h = 64LL * Mp; fh.vts_b = (long long)H * 64 * Mp; fh.os_b = (long long)N * C;
-            fh.head_stride = D; fh.scale = 1.0f / sqrtf((float)D);
-            HIPRET(launch_flash_attn_hh(fh, H, B, st));
+            const _Float16* k16 = c->k2_16.p + (size_t)l * B * M * C;
+            const _Float16* v16t = c->v2t16.p + (size_t)l * B * H * 64 * Mp;
+            HIPRET(launch_flash_attn_hh(dit_flash_hh_args(q2_16, k16, v16t, att16, N, M, Mp, C, C, H, D), H, B, st));
         } else if (flash) {
-            FlashArgs fa{};
-            fa.Q = c->q2.p; fa.K = k2; fa.V = v2; fa.O = c->att.p; fa.N = N; fa.M = M;
-            fa.ldq = fa.ldk = fa.ldv = fa.ldo = C;
-            fa.qs_b = fa.os_b = (long long)N * C; fa.ks_b = fa.vs_b = (long long)M * C;
-            fa.head_stride = D; fa.scale = 1.0f / sqrtf((float)D);
-            fa.O16 = att16;
-            HIPRET(launch_flash_attn_f16(fa, H, B, st));
+            HIPRET(launch_flash_attn_f16(dit_flash_args(c->q2.p, k2, v2, c->att.p, att16, N, M, C, C, D), H, B, st));
         } else {
             for (int b = 0; b < B; ++b)
                 ERCHK(attention_full(c->q2.p + (size_t)b * N * C, C, k2 + (size_t)b * M * C, C, D, v2 + (size_t)b * M * C, C, D,

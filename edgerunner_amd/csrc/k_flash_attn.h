@@ -9,8 +9,10 @@
 //   O^T = V^T P^T (A = V^T rows from LDS,    B = P^T = the S^T registers repacked to fp16, no data movement)
 // so the row max / sum need one xor-32 exchange and the O rescale factor is lane-local.  The MFMA sums over k in
 // whatever internal order it likes: A and B are always fed the same (lane-half, element) -> k assignment.
+// The fragment map, the base-2 softmax step and the fp16 LDS image both kernels share with the prefill kernels are in k_flash_lanes.h.
 #pragma once
 #include "er_common.h"
+#include "k_flash_lanes.h"
 
 namespace er {
 
@@ -24,10 +26,7 @@ struct FlashArgs {
     _Float16* O16;                  // optional: the output rounded to fp16 INSTEAD of O (same strides): it only feeds an fp16 Linear
 };
 
-constexpr int FA_D = 64, FA_QW = 32, FA_KT = 64, FA_LD = 72;   // head dim, q rows per wave, keys per tile, LDS row stride (halves)
-typedef _Float16 fa_h8 __attribute__((ext_vector_type(8)));
-typedef _Float16 fa_h4 __attribute__((ext_vector_type(4)));
-typedef float fa_f16v __attribute__((ext_vector_type(16)));
+constexpr int FA_D = 64, FA_LD = 72;   // head dim, LDS row stride (halves)
 
 // grid (ceil(N / 128), H, B), 256 threads: wave w owns q rows [128*bx + 32*w, +32)
 __global__ __launch_bounds__(ER_WG) void flash_attn_f16_kernel(FlashArgs a) {
@@ -50,24 +49,18 @@ __global__ __launch_bounds__(ER_WG) void flash_attn_f16_kernel(FlashArgs a) {
         const float* qr = Q + (long long)q * a.ldq;
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) {
-            const f32x4 lo = *reinterpret_cast<const f32x4*>(qr + ks * 16 + half * 8);
-            const f32x4 hi = *reinterpret_cast<const f32x4*>(qr + ks * 16 + half * 8 + 4);
-            qb[ks] = (fa_h8){(_Float16)lo.x, (_Float16)lo.y, (_Float16)lo.z, (_Float16)lo.w,
-                             (_Float16)hi.x, (_Float16)hi.y, (_Float16)hi.z, (_Float16)hi.w};
+            float x[8];
+            fa_q8(qr, ks, half, x);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) qb[ks][e] = (_Float16)x[e];
         }
     }
-    fa_f16v ot[2];                    // O^T accumulators: rows d = db*32 + (r&3)+8*(r>>2)+4*half, column q = li
-#pragma unroll
-    for (int db = 0; db < 2; ++db)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) ot[db][r] = 0.f;
+    fa_acc ot[2];                     // O^T accumulators: rows d = db*32 + fa_row(r, half), column q = li
+    fa_zero(ot);
     float m_run = -INFINITY, l_run = 0.f;     // per query (lane column); l_run covers this lane-half's keys only
 
     const int ntiles = (a.M + FA_KT - 1) / FA_KT;
-    // softmax in base 2 on the hardware exponential (v_exp_f32): p = 2^((s - m) scale log2 e).  The probabilities are rounded to fp16
-    // before P.V, far coarser than the 1-ulp difference to expf; the accurate expf cost ~10 instructions x 32 scores per lane and
-    // tile and made the kernel VALU-bound at 9 % of the matrix rate (profiles/r03_dit_fp16_kernel_stats_*.csv)
-    const float sl2 = a.scale * 1.4426950408889634f;
+    const float sl2 = a.scale * 1.4426950408889634f;       // base-2 softmax (fa_softmax_exp2)
     for (int t = 0; t < ntiles; ++t) {
         const int kbase = t * FA_KT;
         __syncthreads();              // previous tile fully consumed
@@ -77,69 +70,23 @@ __global__ __launch_bounds__(ER_WG) void flash_attn_f16_kernel(FlashArgs a) {
             const int idx = tid + ER_WG * u, key = idx >> 4, c4 = idx & 15;
             const int gk = min(kbase + key, a.M - 1);
             const f32x4 kv = *reinterpret_cast<const f32x4*>(K + (long long)gk * a.ldk + 4 * c4);
-            *reinterpret_cast<fa_h4*>(&Ks[key * FA_LD + 4 * c4]) = (fa_h4){(_Float16)kv.x, (_Float16)kv.y, (_Float16)kv.z, (_Float16)kv.w};
             const f32x4 vv = *reinterpret_cast<const f32x4*>(V + (long long)gk * a.ldv + 4 * c4);
-            Vt[(4 * c4 + 0) * FA_LD + key] = (_Float16)vv.x;
-            Vt[(4 * c4 + 1) * FA_LD + key] = (_Float16)vv.y;
-            Vt[(4 * c4 + 2) * FA_LD + key] = (_Float16)vv.z;
-            Vt[(4 * c4 + 3) * FA_LD + key] = (_Float16)vv.w;
+            fa_stage_h16<FA_LD, FA_LD>(Ks, Vt, key, c4, kv, vv);
         }
         __syncthreads();
 
-        // S^T = K Q^T: two 32-key blocks, keys kbase + kb*32 + (r&3)+8*(r>>2)+4*half
-        fa_f16v st[2];
+        // S^T = K Q^T: two 32-key blocks, keys kbase + kb*32 + fa_row(r, half)
+        fa_acc st[2];
 #pragma unroll
         for (int kb = 0; kb < 2; ++kb) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) st[kb][r] = 0.f;
+            fa_zero(st[kb]);
 #pragma unroll
             for (int ks = 0; ks < 4; ++ks) {
                 const fa_h8 ka = *reinterpret_cast<const fa_h8*>(&Ks[(kb * 32 + li) * FA_LD + ks * 16 + half * 8]);
                 st[kb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ka, qb[ks], st[kb], 0, 0, 0);
             }
         }
-        // online softmax for query li
-        float mloc = -INFINITY;
-        if (kbase + FA_KT <= a.M) {                  // wave-uniform: only the last tile can hold keys beyond M
-#pragma unroll
-            for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-                for (int r = 0; r < 16; r += 2) mloc = fmaxf(fmaxf(mloc, st[kb][r]), st[kb][r + 1]);      // RAW scores (v_max3_f32); scaled below
-        } else {
-#pragma unroll
-            for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int key = kbase + kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-                    const float s = key < a.M ? st[kb][r] : -INFINITY;
-                    st[kb][r] = s;
-                    mloc = fmaxf(mloc, s);
-                }
-        }
-        // log2 units: exp(x * scale) = exp2(x * sl2).  The maximum is taken over the raw scores (sl2 > 0) and every probability is ONE
-        // fma + exp2: exp2(fma(s, sl2, -m)) - round 3 spent a multiply and a subtract per score here, and this VALU loop, not the 16
-        // MFMAs of a key tile, bounds the kernel at head_dim 64.  (Packed v_pk_fma_f32 / v_pk_add_f32 forms of the same loop and
-        // a zero C operand instead of clearing the score registers measured no different on the same box: profiles/r04_dit_softmax_ab.log)
-        mloc = xor_max<32>(mloc) * sl2;
-        const float m_new = fmaxf(m_run, mloc);
-        const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);          // m_run = -inf on the first tile -> 0
-        float psum = 0.f;
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const float p = __builtin_amdgcn_exp2f(fmaf(st[kb][r], sl2, -m_new));  // masked keys: exp2(-inf) = 0
-                st[kb][r] = p;
-                psum += p;
-            }
-        l_run = l_run * alpha + psum;
-        if (__builtin_amdgcn_ballot_w64(m_new != m_run) != 0ull) {      // wave-uniform: no query of this wave met a new maximum -> alpha = 1
-#pragma unroll
-            for (int db = 0; db < 2; ++db)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) ot[db][r] *= alpha;
-        }
-        m_run = m_new;
+        fa_softmax_exp2(st, ot, m_run, l_run, kbase, a.M, half, sl2);      // online softmax for query li
 
         // O^T += V^T P^T: per 32-key block two 16-key steps; B = P registers 8*step .. +8 of this lane (keys
         // 16*step + 4*half + {0..3} and + 8 + {0..3}); A = the same keys of row d from Vt
@@ -147,28 +94,24 @@ __global__ __launch_bounds__(ER_WG) void flash_attn_f16_kernel(FlashArgs a) {
         for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
             for (int stp = 0; stp < 2; ++stp) {
-                const fa_h8 pb = {(_Float16)st[kb][8 * stp + 0], (_Float16)st[kb][8 * stp + 1], (_Float16)st[kb][8 * stp + 2],
-                                  (_Float16)st[kb][8 * stp + 3], (_Float16)st[kb][8 * stp + 4], (_Float16)st[kb][8 * stp + 5],
-                                  (_Float16)st[kb][8 * stp + 6], (_Float16)st[kb][8 * stp + 7]};
+                const fa_h8 pb = fa_p8(st[kb], stp);
                 const int kcol = kb * 32 + 16 * stp + 4 * half;
 #pragma unroll
-                for (int db = 0; db < 2; ++db) {
-                    const _Float16* vr = &Vt[(db * 32 + li) * FA_LD + kcol];
-                    const fa_h4 v0 = *reinterpret_cast<const fa_h4*>(vr);
-                    const fa_h4 v1 = *reinterpret_cast<const fa_h4*>(vr + 8);
-                    const fa_h8 va = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
-                    ot[db] = __builtin_amdgcn_mfma_f32_32x32x16_f16(va, pb, ot[db], 0, 0, 0);
-                }
+                for (int db = 0; db < 2; ++db)
+                    ot[db] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa_vt_frag<FA_LD>(Vt, db * 32 + li, kcol), pb, ot[db], 0, 0, 0);
             }
     }
     const float l_tot = xor_sum<32>(l_run);
     const int q = q0 + li;
     if (q < a.N) {
+        // (not fa_store_rows: one call per output type doubles the 32 divisions, and the fp16 stores then merge four to one - a different
+        // kernel from the one measured; the choice per element keeps one division and one store per element)
+        const long long o0 = (long long)q * a.ldo + 4 * half;      // fa_row(r, half) = fa_row(r, 0) + 4 half: the rest is an immediate offset
 #pragma unroll
         for (int db = 0; db < 2; ++db)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const long long o = (long long)q * a.ldo + db * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
+                const long long o = o0 + db * 32 + fa_row(r, 0);
                 const float v = ot[db][r] / l_tot;
                 if (O16) O16[o] = (_Float16)v;
                 else O[o] = v;
@@ -263,15 +206,12 @@ __global__ __launch_bounds__(ER_WG) void flash_attn_hh_kernel(FlashHArgs a) {
         for (int j = 0; j < 2; ++j) fa_glds16(pv[j] + kbase, vs_ + j * 8 * 64 * 2u);
     };
 
-    fa_f16v ot[2];
-#pragma unroll
-    for (int db = 0; db < 2; ++db)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) ot[db][r] = 0.f;
+    fa_acc ot[2];
+    fa_zero(ot);
     float m_run = -INFINITY, l_run = 0.f;
     const int swz = (li >> 1) & 7;
     const int ntiles = (a.M + FA_KT - 1) / FA_KT;
-    const float sl2 = a.scale * 1.4426950408889634f;       // base-2 softmax, see flash_attn_f16_kernel
+    const float sl2 = a.scale * 1.4426950408889634f;       // base-2 softmax (fa_softmax_exp2)
 #pragma unroll
     for (int p = 0; p < NST - 1; ++p)
         if (p < ntiles) issue(p, p);
@@ -289,61 +229,22 @@ __global__ __launch_bounds__(ER_WG) void flash_attn_hh_kernel(FlashHArgs a) {
         if (t + NST - 1 < ntiles) issue(t + NST - 1, (t + NST - 1) & (NST - 1));      // into the stage tile t - 1 just vacated
         const _Float16* Ks = lds + cur * 2 * TILE;
         const _Float16* Vs = Ks + TILE;
-        fa_f16v st[2];
+        fa_acc st[2];
 #pragma unroll
         for (int kb = 0; kb < 2; ++kb) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) st[kb][r] = 0.f;
+            fa_zero(st[kb]);
 #pragma unroll
             for (int ks = 0; ks < 4; ++ks) {
                 const fa_h8 ka = *reinterpret_cast<const fa_h8*>(Ks + (kb * 32 + li) * 64 + (((2 * ks + half) ^ swz) << 3));
                 st[kb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ka, qb[ks], st[kb], 0, 0, 0);
             }
         }
-        float mloc = -INFINITY;
-        if (kbase + FA_KT <= a.M) {                  // wave-uniform: only the last tile can hold keys beyond M
-#pragma unroll
-            for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-                for (int r = 0; r < 16; r += 2) mloc = fmaxf(fmaxf(mloc, st[kb][r]), st[kb][r + 1]);      // RAW scores (v_max3_f32); scaled below
-        } else {
-#pragma unroll
-            for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int key = kbase + kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-                    const float s = key < a.M ? st[kb][r] : -INFINITY;
-                    st[kb][r] = s;
-                    mloc = fmaxf(mloc, s);
-                }
-        }
-        mloc = xor_max<32>(mloc) * sl2;
-        const float m_new = fmaxf(m_run, mloc);
-        const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
-        float psum = 0.f;
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const float p = __builtin_amdgcn_exp2f(fmaf(st[kb][r], sl2, -m_new));
-                st[kb][r] = p;
-                psum += p;
-            }
-        l_run = l_run * alpha + psum;
-        if (__builtin_amdgcn_ballot_w64(m_new != m_run) != 0ull) {      // wave-uniform: no query of this wave met a new maximum -> alpha = 1
-#pragma unroll
-            for (int db = 0; db < 2; ++db)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) ot[db][r] *= alpha;
-        }
-        m_run = m_new;
+        fa_softmax_exp2(st, ot, m_run, l_run, kbase, a.M, half, sl2);
 #pragma unroll
         for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
             for (int stp = 0; stp < 2; ++stp) {
-                const fa_h8 pb = {(_Float16)st[kb][8 * stp + 0], (_Float16)st[kb][8 * stp + 1], (_Float16)st[kb][8 * stp + 2],
-                                  (_Float16)st[kb][8 * stp + 3], (_Float16)st[kb][8 * stp + 4], (_Float16)st[kb][8 * stp + 5],
-                                  (_Float16)st[kb][8 * stp + 6], (_Float16)st[kb][8 * stp + 7]};
+                const fa_h8 pb = fa_p8(st[kb], stp);
                 // V^T keys are stored in the order the P registers hold them (fa_vt_pos): this lane-half's 8 keys of the step
                 // - 16 stp + 4 half + {0..3} and + 8 + {0..3} - are ONE 16-byte chunk, number kb*4 + 2*stp + half of the row
                 const int c0 = kb * 4 + 2 * stp + half;

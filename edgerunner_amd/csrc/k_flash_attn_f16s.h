@@ -13,11 +13,11 @@
 // fp16 x fp16 products are exact in the fp32 accumulator, so the result is the fp16-K/V x fp32-Q/P product to fp32 round-off:
 // the arithmetic of core/transformer/attention.py:27-62 on fp16-rounded storage, which is what the fast-mode parity tests
 // check (oracle on fp16-rounded storage).  Same transposed formulation, fragment maps and online softmax as
-// k_flash_attn.h / k_flash_attn_f32.h (a query's statistics stay in one lane column); causal tiles beyond a wave's last key
-// are skipped.
+// k_flash_attn.h / k_flash_attn_f32.h (a query's statistics stay in one lane column), all of them from k_flash_lanes.h: the exact softmax
+// step and tile-ahead fetch of the fp32 kernel, the fp16 LDS image of the fp16 kernel; causal tiles beyond a wave's last key are skipped.
 #pragma once
 #include "er_common.h"
-#include "k_flash_attn.h"
+#include "k_flash_lanes.h"
 #include "k_flash_attn_f32.h"
 
 namespace er {
@@ -33,16 +33,16 @@ constexpr float FAS_QSCALE = 16.0f, FAS_PSCALE = 1024.0f;
 template <int D, bool CAUSAL, int NWV>
 __global__ __launch_bounds__(64 * NWV) void flash_attn_f16s_kernel(Flash32Args a) {
     constexpr int THREADS = 64 * NWV;
-    constexpr int KT = 64, KLD = D + 8, VLD = KT + 8;     // keys per tile; LDS row strides in halves (KLD / 8 and VLD / 8 odd)
+    constexpr int KLD = D + 8, VLD = FA_KT + 8;           // LDS row strides in halves (KLD / 8 and VLD / 8 odd)
     constexpr int KS = D / 16, NDB = D / 32, F4 = D / 4;
     static_assert(D % 32 == 0 && ((KLD / 8) & 1) == 1 && ((VLD / 8) & 1) == 1, "head_dim 64 or 96");
-    __shared__ __attribute__((aligned(16))) _Float16 Ks[KT * KLD];   // [key][d]
-    __shared__ __attribute__((aligned(16))) _Float16 Vt[D * VLD];    // [d][key]
+    __shared__ __attribute__((aligned(16))) _Float16 Ks[FA_KT * KLD];   // [key][d]
+    __shared__ __attribute__((aligned(16))) _Float16 Vt[D * VLD];       // [d][key]
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int li = lane & 31, half = lane >> 5;
     const int h = blockIdx.y, b = blockIdx.z;
     const int qt = CAUSAL ? (int)(gridDim.x - 1 - blockIdx.x) : (int)blockIdx.x;
-    const int q0 = qt * (NWV * 32) + wid * 32;
+    const int q0 = qt * (NWV * FA_QW) + wid * FA_QW;
     const float* Q = a.Q + b * a.qs_b + h * a.qs_h;
     const float* K = a.K + b * a.ks_b + h * a.ks_h;
     const float* V = a.V + b * a.vs_b + h * a.vs_h;
@@ -55,9 +55,8 @@ __global__ __launch_bounds__(64 * NWV) void flash_attn_f16s_kernel(Flash32Args a
         const float* qr = Q + (long long)min(qi, a.N - 1) * a.ldq;
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
-            const f32x4 x0 = *reinterpret_cast<const f32x4*>(qr + ks * 16 + half * 8);
-            const f32x4 x1 = *reinterpret_cast<const f32x4*>(qr + ks * 16 + half * 8 + 4);
-            const float x[8] = {x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w};
+            float x[8];
+            fa_q8(qr, ks, half, x);
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
                 const float s = x[e] * FAS_QSCALE;
@@ -67,58 +66,34 @@ __global__ __launch_bounds__(64 * NWV) void flash_attn_f16s_kernel(Flash32Args a
             }
         }
     }
-    fa_f16v ot[NDB];                 // O^T: rows d = db*32 + (r&3) + 8*(r>>2) + 4*half, column q = li (scaled by FAS_PSCALE)
-#pragma unroll
-    for (int db = 0; db < NDB; ++db)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) ot[db][r] = 0.f;
+    fa_acc ot[NDB];                  // O^T: rows d = db*32 + fa_row(r, half), column q = li (scaled by FAS_PSCALE)
+    fa_zero(ot);
     float m_run = -INFINITY, l_run = 0.f;     // l_run covers this lane half's keys only
-
-    const int wg_last_q = min(a.N - 1, qt * (NWV * 32) + NWV * 32 - 1);
-    const int kmax = CAUSAL ? min(a.M, wg_last_q + a.causal_off + 1) : a.M;
-    const int ntiles = (kmax + KT - 1) / KT;
-    const int wave_last_key = CAUSAL ? (q0 + 31 + a.causal_off) : (a.M - 1);
-    const float sdiv = a.sqrt_d * FAS_QSCALE;
+    const auto [ntiles, wave_last_key] = fa_key_bounds<CAUSAL, NWV>(a.N, a.M, a.causal_off, qt, q0);
+    const float sdiv = a.sqrt_d * FAS_QSCALE;     // sqrt(D) times a power of two: the three-instruction division stays exact
     const float inv_sdiv = 1.0f / sdiv;
 
-    constexpr int NST = (KT * F4) / THREADS;
-    static_assert((KT * F4) % THREADS == 0, "staging loop shape");
+    constexpr int NST = (FA_KT * F4) / THREADS;
     f32x4 kpre[NST], vpre[NST];
-    auto fetch = [&](int kbase, int u, f32x4& kv, f32x4& vv) {
-        const int idx = tid + THREADS * u, key = idx / F4, c4 = idx - key * F4;
-        const int gk = min(kbase + key, a.M - 1);
-        kv = *reinterpret_cast<const f32x4*>(K + (long long)gk * a.ldk + 4 * c4);
-        vv = *reinterpret_cast<const f32x4*>(V + (long long)gk * a.ldv + 4 * c4);
-    };
-    auto stage = [&](int u, const f32x4& kv, const f32x4& vv) {
-        const int idx = tid + THREADS * u, key = idx / F4, c4 = idx - key * F4;
-        *reinterpret_cast<fa_h4*>(&Ks[key * KLD + 4 * c4]) = (fa_h4){(_Float16)kv.x, (_Float16)kv.y, (_Float16)kv.z, (_Float16)kv.w};
-        Vt[(4 * c4 + 0) * VLD + key] = (_Float16)vv.x;
-        Vt[(4 * c4 + 1) * VLD + key] = (_Float16)vv.y;
-        Vt[(4 * c4 + 2) * VLD + key] = (_Float16)vv.z;
-        Vt[(4 * c4 + 3) * VLD + key] = (_Float16)vv.w;
-    };
-#pragma unroll
-    for (int u = 0; u < NST; ++u) fetch(0, u, kpre[u], vpre[u]);
+    fa_fetch_tile<F4, THREADS>(K, V, a.ldk, a.ldv, 0, a.M, tid, kpre, vpre);
     for (int t = 0; t < ntiles; ++t) {
-        const int kbase = t * KT;
+        const int kbase = t * FA_KT;
         __syncthreads();                     // previous tile fully consumed
         // stage K -> Ks[key][d], V -> Vt[d][key] as fp16 (exact: the values are fp16 already)
 #pragma unroll
-        for (int u = 0; u < NST; ++u) stage(u, kpre[u], vpre[u]);
-        __syncthreads();
-        if (t + 1 < ntiles) {
-#pragma unroll
-            for (int u = 0; u < NST; ++u) fetch(kbase + KT, u, kpre[u], vpre[u]);
+        for (int u = 0; u < NST; ++u) {
+            const auto [key, c4] = fa_slot<F4, THREADS>(tid, u);
+            fa_stage_h16<KLD, VLD>(Ks, Vt, key, c4, kpre[u], vpre[u]);
         }
+        __syncthreads();
+        if (t + 1 < ntiles) fa_fetch_tile<F4, THREADS>(K, V, a.ldk, a.ldv, kbase + FA_KT, a.M, tid, kpre, vpre);
         if (kbase > wave_last_key) continue;   // wave-uniform: the barriers above are still hit by every wave
 
-        // S^T = K Q^T: two 32-key blocks; lane (li, half) holds keys kbase + kb*32 + (r&3) + 8*(r>>2) + 4*half
-        fa_f16v st[2];
+        // S^T = K Q^T: two 32-key blocks; lane (li, half) holds keys kbase + kb*32 + fa_row(r, half)
+        fa_acc st[2];
 #pragma unroll
         for (int kb = 0; kb < 2; ++kb) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) st[kb][r] = 0.f;
+            fa_zero(st[kb]);
 #pragma unroll
             for (int ks = 0; ks < KS; ++ks) {
                 const fa_h8 ka = *reinterpret_cast<const fa_h8*>(&Ks[(kb * 32 + li) * KLD + ks * 16 + half * 8]);
@@ -126,39 +101,7 @@ __global__ __launch_bounds__(64 * NWV) void flash_attn_f16s_kernel(Flash32Args a
                 st[kb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ka, qh[ks], st[kb], 0, 0, 0);
             }
         }
-        float mloc = -INFINITY;
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int key = kbase + kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-                bool ok = key < a.M;
-                if (CAUSAL) ok = ok && key <= qi + a.causal_off;
-                // the correctly rounded quotient in three instructions (see k_flash_attn_f32.h; sdiv is sqrt(D) times a power of two,
-                // so the exhaustive check of scripts/probes/div_const_probe.hip carries over)
-                const float q0 = st[kb][r] * inv_sdiv;
-                const float s = ok ? fmaf(fmaf(-q0, sdiv, st[kb][r]), inv_sdiv, q0) : -INFINITY;
-                st[kb][r] = s;
-                mloc = fmaxf(mloc, s);
-            }
-        mloc = xor_max<32>(mloc);
-        const float m_new = fmaxf(m_run, mloc);
-        const float alpha = (m_new == -INFINITY) ? 1.0f : expf(m_run - m_new);   // m_run = -inf -> exp(-inf) = 0
-        float psum = 0.f;
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const float p = (st[kb][r] == -INFINITY) ? 0.f : expf(st[kb][r] - m_new);
-                st[kb][r] = p;
-                psum += p;
-            }
-        l_run = l_run * alpha + psum;
-        m_run = m_new;
-#pragma unroll
-        for (int db = 0; db < NDB; ++db)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) ot[db][r] *= alpha;
+        fa_softmax_exact<CAUSAL>(st, ot, m_run, l_run, kbase, a.M, qi, a.causal_off, half, sdiv, inv_sdiv);
 
         // O^T += V^T P^T: per 32-key block two 16-key steps; B = P registers 8*step .. +8 of this lane (keys
         // 16*step + 4*half + {0..3} and + 8 + {0..3}) as hi + lo parts of 1024 p; A = the same keys of row d from Vt
@@ -177,38 +120,23 @@ __global__ __launch_bounds__(64 * NWV) void flash_attn_f16s_kernel(Flash32Args a
                 const int kcol = kb * 32 + 16 * stp + 4 * half;
 #pragma unroll
                 for (int db = 0; db < NDB; ++db) {
-                    const _Float16* vr = &Vt[(db * 32 + li) * VLD + kcol];
-                    const fa_h4 v0 = *reinterpret_cast<const fa_h4*>(vr);
-                    const fa_h4 v1 = *reinterpret_cast<const fa_h4*>(vr + 8);
-                    const fa_h8 va = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
+                    const fa_h8 va = fa_vt_frag<VLD>(Vt, db * 32 + li, kcol);
                     ot[db] = __builtin_amdgcn_mfma_f32_32x32x16_f16(va, pl, ot[db], 0, 0, 0);
                     ot[db] = __builtin_amdgcn_mfma_f32_32x32x16_f16(va, ph, ot[db], 0, 0, 0);
                 }
             }
     }
     const float l_tot = (xor_sum<32>(l_run)) * FAS_PSCALE;
-    if (qi < a.N) {
-        float* orow = O + (long long)qi * a.ldo;
-#pragma unroll
-        for (int db = 0; db < NDB; ++db)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) orow[db * 32 + (r & 3) + 8 * (r >> 2) + 4 * half] = ot[db][r] / l_tot;
-    }
+    if (qi < a.N) fa_store_rows(O + (long long)qi * a.ldo, ot, l_tot, half);
 }
 
 inline hipError_t launch_flash_attn_f16s(const Flash32Args& a, int D, bool causal, int H, int B, hipStream_t st) {
-    const long long wg4 = (long long)((a.N + 127) / 128) * H * B;
-    const int nwv = wg4 < 768 ? 2 : 4;          // same rule as launch_flash_attn_f32
-    dim3 grid((a.N + nwv * 32 - 1) / (nwv * 32), H, B), blk(64 * nwv);
-    if (D != 96) return hipErrorInvalidValue;
-    if (nwv == 4) {
-        if (causal) hipLaunchKernelGGL((flash_attn_f16s_kernel<96, true, 4>), grid, blk, 0, st, a);
-        else hipLaunchKernelGGL((flash_attn_f16s_kernel<96, false, 4>), grid, blk, 0, st, a);
-    } else {
-        if (causal) hipLaunchKernelGGL((flash_attn_f16s_kernel<96, true, 2>), grid, blk, 0, st, a);
-        else hipLaunchKernelGGL((flash_attn_f16s_kernel<96, false, 2>), grid, blk, 0, st, a);
-    }
-    return hipGetLastError();
+    const int nwv = fa_auto_waves(a.N, H, B);       // (the ER_FLASH32_NWV override is the fp32 kernel's alone)
+    dim3 grid((a.N + nwv * FA_QW - 1) / (nwv * FA_QW), H, B), blk(64 * nwv);
+    const bool known = fa_dispatch<96>(D, causal, nwv, [&](auto d, auto c, auto w) {
+        hipLaunchKernelGGL((flash_attn_f16s_kernel<decltype(d)::value, decltype(c)::value, decltype(w)::value>), grid, blk, 0, st, a);
+    });
+    return known ? hipGetLastError() : hipErrorInvalidValue;
 }
 
 }  // namespace er

@@ -514,7 +514,8 @@ def test_gemm_f16s_forms_agree(M, N, K, monkeypatch):
     close(out["reg"][0], ref, 2e-6 + 1e-7 * K, 2e-6, "register-staged split fp16 gemm")
 
 
-@pytest.mark.parametrize("B,H,N,M", [(1, 16, 2048, 2048), (2, 16, 2048, 257), (1, 2, 100, 70), (1, 1, 33, 1)])
+@pytest.mark.parametrize("B,H,N,M", [(1, 16, 2048, 2048), (2, 16, 2048, 257), (1, 2, 100, 70), (1, 1, 33, 1),
+                                     (2, 3, 130, 257)])     # five key tiles with a ragged last one, a ragged query tile, B and H > 1
 def test_flash_attn_f16(B, H, N, M):
     from edgerunner_amd import kernels as K_
     q, k, v = rnd(B, N, H * 64, seed=80), rnd(B, M, H * 64, seed=81), rnd(B, M, H * 64, seed=82)
@@ -593,6 +594,58 @@ def test_flash_attn_f32_batch_invariance():
     o1 = K_.flash_attn_f32(q[:1].contiguous(), k[:1].contiguous(), v[:1].contiguous(), H, causal=True)
     assert torch.equal(o2, o3[:2]), "rows of a pair must equal the same rows of a batch of three"
     close(o1[0], o3[0].double(), 2e-6, 2e-6, "single sample (key-range split) vs the same sample in a batch")
+
+
+def _attn_ref64(q, k, v, H, D, causal):
+    """attention() of core/transformer/attention.py:47-62 in float64 on packed [B, rows, H*D] tensors."""
+    B, N, M = q.shape[0], q.shape[1], k.shape[1]
+    qh, kh, vh = (t.double().view(B, -1, H, D).transpose(1, 2) for t in (q, k, v))
+    sc = qh @ kh.transpose(-1, -2) / math.sqrt(D)
+    if causal:
+        i = torch.arange(N, device=DEV)[:, None]
+        j = torch.arange(M, device=DEV)[None, :]
+        sc = sc.masked_fill(j > i + (M - N), float("-inf"))
+    return (torch.softmax(sc, dim=-1) @ vh).transpose(1, 2).reshape(B, N, H * D)
+
+
+# ceil(N / 128) * H * B >= 768: the launchers pick four-wave workgroups (k_flash_lanes.h fa_auto_waves), the form every batched prefill runs
+def _four_wave_case(kind, B, H, N, M, D, causal):
+    """(q, k, v, kernel, atol, rtol): inputs and tolerances of test_flash_attn_f32 / test_flash_attn_f16s at a four-wave shape."""
+    from edgerunner_amd import kernels as K_
+    assert (N + 127) // 128 * H * B >= 768
+    if kind == "f32":
+        q, k, v = rnd(B, N, H * D, seed=83), rnd(B, M, H * D, seed=84), rnd(B, M, H * D, seed=85)
+        k[:, M // 2] *= 3.0                                 # a spiky key row forces the running-max rescale
+        return q, k, v, lambda q_, k_, v_: K_.flash_attn_f32(q_, k_, v_, H, causal=causal), 5e-6, 2e-5
+    q = rnd(B, N, H * D, seed=80)
+    k, v = rnd(B, M, H * D, seed=81).half().float(), rnd(B, M, H * D, seed=82).half().float()       # fp16-valued k / v
+    return q, k, v, lambda q_, k_, v_: K_.flash_attn_f16s(q_, k_, v_, H, causal=causal), 3e-6, 1e-5
+
+
+@pytest.mark.parametrize("kind,B,H,N,M,D,causal", [
+    ("f32", 6, 128, 40, 70, 64, False),       # ragged query tile (40 of 128) and key tile (70 = 64 + 6)
+    ("f32", 6, 128, 70, 70, 96, True),
+    ("f32", 3, 256, 100, 200, 96, True),      # causal with M > N: key j visible iff j <= i + (M - N)
+    ("f16s", 6, 128, 70, 70, 96, True),
+    ("f16s", 6, 128, 40, 333, 96, False)])
+def test_flash_attn_four_wave_forms(kind, B, H, N, M, D, causal):
+    """The NWV = 4 instantiations of flash_attn_f32_kernel and flash_attn_f16s_kernel on tiny sequences, against the fp64 reference
+    and with the tolerances of test_flash_attn_f32 / test_flash_attn_f16s."""
+    q, k, v, run, atol, rtol = _four_wave_case(kind, B, H, N, M, D, causal)
+    close(run(q, k, v), _attn_ref64(q, k, v, H, D, causal), atol, rtol, f"four-wave {kind} flash attention")
+
+
+@pytest.mark.parametrize("kind", ["f32", "f16s"])
+def test_flash_attn_two_and_four_wave_forms_agree(kind):
+    """The first two samples of a batch of six (four-wave workgroups) run as a batch of two (two-wave workgroups, and unsplit because
+    B != 1) give the same bits: a wave walks the same key tiles in the same order over the same staged values whatever the number of
+    waves that share them."""
+    B, H, N, M, D = 6, 128, 70, 70, 96
+    q, k, v, run, _, _ = _four_wave_case(kind, B, H, N, M, D, True)
+    assert (N + 127) // 128 * H * 2 < 768
+    o6 = run(q, k, v)
+    o2 = run(q[:2].contiguous(), k[:2].contiguous(), v[:2].contiguous())
+    assert torch.equal(o2, o6[:2]), f"two-wave and four-wave {kind} kernels differ: max {float((o2 - o6[:2]).abs().max()):.3e}"
 
 
 # ------------------------------------------------------------------ row ops
