@@ -700,21 +700,13 @@ static hipError_t enqueue_step(er_ctx* c, hipStream_t st, long long* out_ids, in
 // ------------------------------------------------------------------------------------ GEMM helpers (prefill / encoder)
 static hipError_t linear(const float* A, int lda, const float* W, const float* bias, float* C, int ldc, int M, int N, int K,
                          bool relu, const float* resid, int ldr, hipStream_t st) {
-    GemmArgs g = gemm_args_default();
-    g.A = A; g.B = W; g.C = C; g.bias = bias; g.resid = resid;
-    g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = K; g.ldc = ldc; g.ldr = ldr;
-    g.relu = relu ? 1 : 0;
-    return launch_gemm(g, 1, st);
+    return launch_gemm(gemm_args_linear(A, lda, W, bias, C, ldc, M, N, K, relu, resid, ldr), 1, st);
 }
 
-// fast mode: C = epilogue((A_hi + A_lo) . W_fp16^T) on the fp16 matrix cores (k_gemm.h, gemm_f16s_mfma_kernel)
+// fast mode: C = epilogue((A_hi + A_lo) . W_fp16^T) on the fp16 matrix cores (k_gemm.h, gemm_f16_mfma_kernel<SPLIT>)
 static hipError_t linear_h(const float* A, int lda, const _Float16* W, const float* bias, float* C, int ldc, int M, int N, int K,
                            bool relu, const float* resid, int ldr, hipStream_t st) {
-    GemmArgs g = gemm_args_default();
-    g.A = A; g.B = reinterpret_cast<const float*>(W); g.C = C; g.bias = bias; g.resid = resid;
-    g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = K; g.ldc = ldc; g.ldr = ldr;
-    g.relu = relu ? 1 : 0;
-    return launch_gemm_f16s(g, st);
+    return launch_gemm_f16s(gemm_args_linear(A, lda, W, bias, C, ldc, M, N, K, relu, resid, ldr), st);
 }
 
 // the same product through the LDS-DMA kernel (k_gemm.h, split form): the fp32 activation is split into hi / lo fp16 arrays by one
@@ -745,10 +737,8 @@ static int linear_hs(er_ctx* c, const float* A, int lda, const _Float16* W, cons
     _Float16 *hi = c->p_hi.p, *lo = c->p_lo.p;
     hipLaunchKernelGGL(split_rows_f16_kernel, split_rows_grid(M, K), dim3(ER_WG), 0, st, A, hi, lo, (long long)M, K, lda);
     HIPRET(hipGetLastError());
-    GemmArgs g = gemm_args_default();
-    g.A = reinterpret_cast<const float*>(hi); g.a_lo = lo; g.B = reinterpret_cast<const float*>(W); g.C = C; g.bias = bias; g.resid = resid;
-    g.M = M; g.N = N; g.K = K; g.lda = K; g.ldb = K; g.ldc = ldc; g.ldr = ldr;
-    g.relu = relu ? 1 : 0;
+    GemmArgs g = gemm_args_linear(hi, K, W, bias, C, ldc, M, N, K, relu, resid, ldr);
+    g.a_lo = lo;
     HIPRET(launch_gemm_hh_split(g, st));
     return 0;
 }
@@ -2035,9 +2025,8 @@ extern "C" int er_k_attn_outproj3(const float* q, const void* k, const void* v, 
 extern "C" int er_k_gemm(const float* a, const float* b, const float* bias, const float* resid, float* cc, int m, int n, int k,
                          int lda, int ldb, int ldc, int b_is_kn, int relu, float div, void* stream) {
     if (k % 16) return fail(ER_ERR_INVALID, "er_k_gemm: k must be a multiple of 16");
-    GemmArgs g = gemm_args_default();
-    g.A = a; g.B = b; g.C = cc; g.bias = bias; g.resid = resid; g.M = m; g.N = n; g.K = k;
-    g.lda = lda; g.ldb = ldb; g.ldc = ldc; g.ldr = ldc; g.b_is_kn = b_is_kn; g.kb_valid = k; g.relu = relu; g.div = div;
+    GemmArgs g = gemm_args_linear(a, lda, b, bias, cc, ldc, m, n, k, relu != 0, resid, ldc);
+    g.ldb = ldb; g.b_is_kn = b_is_kn; g.kb_valid = k; g.div = div;
     HIPRET(launch_gemm(g, 1, (hipStream_t)stream));
     return ER_OK;
 }
@@ -2045,32 +2034,39 @@ extern "C" int er_k_gemm(const float* a, const float* b, const float* bias, cons
 extern "C" int er_k_gemm_f16(const float* a, const void* w, const float* bias, const float* resid, float* cc, int m, int n, int k,
                              int lda, int ldb, int ldc, int relu, void* stream) {
     if (k % 32) return fail(ER_ERR_INVALID, "er_k_gemm_f16: k must be a multiple of 32");
-    GemmArgs g = gemm_args_default();
-    g.A = a; g.B = reinterpret_cast<const float*>(w); g.C = cc; g.bias = bias; g.resid = resid; g.M = m; g.N = n; g.K = k;
-    g.lda = lda; g.ldb = ldb; g.ldc = ldc; g.ldr = ldc; g.relu = relu;
+    GemmArgs g = gemm_args_linear(a, lda, w, bias, cc, ldc, m, n, k, relu != 0, resid, ldc);
+    g.ldb = ldb;
     HIPRET(launch_gemm_f16(g, (hipStream_t)stream));
     return ER_OK;
 }
 
-// fp16 x fp16 LDS-DMA GEMM (gemm_hh_mfma_kernel): a is converted to an fp16 copy first (in the product the producer writes it),
+// tail of the test entries that launch and wait: both errors are reported, the launch's first
+static int gemm_sync_report(hipError_t e, hipStream_t st) {
+    hipError_t e2 = hipStreamSynchronize(st);
+    HIPRET(e);
+    HIPRET(e2);
+    return ER_OK;
+}
+// the er_k_gemm_hh* entries: fp32 a [M][lda] -> an fp16 copy [M][K] that becomes g.A (in the product the producer writes it), then
+// launch(g) and the wait
+template <typename L>
+static int gemm_hh_entry(const float* a, int lda, GemmArgs& g, hipStream_t st, L&& launch) {
+    DevBuf<_Float16> a16;
+    ERCHK(a16.ensure((size_t)g.M * g.K));
+    hipLaunchKernelGGL(cvt_rows_f16_kernel, dim3(ew_grid((long long)g.M * g.K)), dim3(ER_WG), 0, st, a, a16.p, (long long)g.M, g.K, lda, g.K);
+    g.A = reinterpret_cast<const float*>(a16.p); g.lda = g.K;
+    return gemm_sync_report(launch(g), st);
+}
+
+// fp16 x fp16 LDS-DMA GEMM (gemm_hh_mfma_kernel): a is converted to an fp16 copy first,
 // c16_out (optional, device fp16 [m][n]) receives the epilogue's fp16 copy of the result
 extern "C" int er_k_gemm_hh(const float* a, const void* w, const float* bias, const float* resid, float* cc, void* c16_out, int m,
                             int n, int k, int lda, int ldb, int ldc, int relu, void* stream) {
     if (k % 64 || (ldb & 7)) return fail(ER_ERR_INVALID, "er_k_gemm_hh: k must be a multiple of 64, ldb of 8");
     hipStream_t st = (hipStream_t)stream;
-    DevBuf<_Float16> a16b;
-    ERCHK(a16b.ensure((size_t)m * k));
-    _Float16* a16 = a16b.p;
-    hipLaunchKernelGGL(cvt_rows_f16_kernel, dim3(ew_grid((long long)m * k)), dim3(ER_WG), 0, st, a, a16, (long long)m, k, lda, k);
-    GemmArgs g = gemm_args_default();
-    g.A = reinterpret_cast<const float*>(a16); g.B = reinterpret_cast<const float*>(w); g.C = cc; g.bias = bias; g.resid = resid;
-    g.M = m; g.N = n; g.K = k; g.lda = k; g.ldb = ldb; g.ldc = ldc; g.ldr = ldc; g.relu = relu;
-    g.c16 = reinterpret_cast<_Float16*>(c16_out); g.ldc16 = n;
-    hipError_t e = launch_gemm_hh(g, st);
-    hipError_t e2 = hipStreamSynchronize(st);
-    HIPRET(e);
-    HIPRET(e2);
-    return ER_OK;
+    GemmArgs g = gemm_args_linear(nullptr, k, w, bias, cc, ldc, m, n, k, relu != 0, resid, ldc);
+    g.ldb = ldb; g.c16 = reinterpret_cast<_Float16*>(c16_out); g.ldc16 = n;
+    return gemm_hh_entry(a, lda, g, st, [&](const GemmArgs& ga) { return launch_gemm_hh(ga, st); });
 }
 
 // ---- er_k_gemm_epi: one GEMM family with the WHOLE plain epilogue the product uses (bias, / div, relu, adaLN gate rows, a residual
@@ -2094,25 +2090,14 @@ extern "C" int er_k_gemm_epi(const er_k_gemm_epi_args* f, void* stream) {
     if (f->resid && f->ldr < f->n) return fail(ER_ERR_INVALID, "er_k_gemm_epi: ldr %d below n %d", f->ldr, f->n);
     if (f->resid_mod < 0 || (f->resid_mod && !f->resid)) return fail(ER_ERR_INVALID, "er_k_gemm_epi: resid_mod %d (>= 0, with a residual)", f->resid_mod);
     hipStream_t st = (hipStream_t)stream;
-    GemmArgs g = gemm_args_default();
-    g.A = f->a; g.B = reinterpret_cast<const float*>(f->w); g.C = f->c; g.bias = f->bias;
-    g.resid = f->resid; g.ldr = f->ldr; g.resid_mod = f->resid_mod;
+    GemmArgs g = gemm_args_linear(f->a, f->lda, f->w, f->bias, f->c, f->ldc, f->m, f->n, f->k, false, f->resid, f->ldr);
+    g.ldb = f->ldb; g.kb_valid = f->k; g.relu = f->relu; g.div = f->div; g.resid_mod = f->resid_mod;
     g.gate = f->gate; g.gate_rows = f->gate_rows; g.gate_bstride = f->gate_bstride;
-    g.M = f->m; g.N = f->n; g.K = f->k; g.lda = f->lda; g.ldb = f->ldb; g.ldc = f->ldc; g.kb_valid = f->k;
-    g.relu = f->relu; g.div = f->div;
     if (fam == ER_GEMM_F32) { HIPRET(launch_gemm(g, 1, st)); return ER_OK; }
     if (fam == ER_GEMM_F16) { HIPRET(launch_gemm_f16(g, st)); return ER_OK; }
     if (fam == ER_GEMM_F16S) { HIPRET(launch_gemm_f16s(g, st)); return ER_OK; }
-    DevBuf<_Float16> a16b;      // the fp16 copy of A, as er_k_gemm_hh makes it
-    ERCHK(a16b.ensure((size_t)f->m * f->k));
-    hipLaunchKernelGGL(cvt_rows_f16_kernel, dim3(ew_grid((long long)f->m * f->k)), dim3(ER_WG), 0, st, f->a, a16b.p, (long long)f->m, f->k, f->lda, f->k);
-    g.A = reinterpret_cast<const float*>(a16b.p); g.lda = f->k;
     g.c16 = reinterpret_cast<_Float16*>(f->c16); g.ldc16 = f->ldc;
-    hipError_t e = launch_gemm_hh(g, st, f->force_tile);
-    hipError_t e2 = hipStreamSynchronize(st);
-    HIPRET(e);
-    HIPRET(e2);
-    return ER_OK;
+    return gemm_hh_entry(f->a, f->lda, g, st, [&](const GemmArgs& ga) { return launch_gemm_hh(ga, st, f->force_tile); });
 }
 
 extern "C" int er_k_gemm_hh_qkv(const float* a, const void* w, const float* bias, void* qk16_out, void* vt_out, int m, int n, int k,
@@ -2120,20 +2105,10 @@ extern "C" int er_k_gemm_hh_qkv(const float* a, const void* w, const float* bias
     if (k % 64 || n % 192 || m % 64 || rows_per_batch <= 0 || rows_per_batch % 64 || m % rows_per_batch)
         return fail(ER_ERR_INVALID, "er_k_gemm_hh_qkv: k, m, rows_per_batch multiples of 64, n of 192");
     hipStream_t st = (hipStream_t)stream;
-    DevBuf<_Float16> a16b;
-    ERCHK(a16b.ensure((size_t)m * k));
-    _Float16* a16 = a16b.p;
-    hipLaunchKernelGGL(cvt_rows_f16_kernel, dim3(ew_grid((long long)m * k)), dim3(ER_WG), 0, st, a, a16, (long long)m, k, k, k);
-    GemmArgs g = gemm_args_default();
-    g.A = reinterpret_cast<const float*>(a16); g.B = reinterpret_cast<const float*>(w); g.bias = bias;
-    g.M = m; g.N = n; g.K = k; g.lda = k; g.ldb = k; g.ldc = n; g.ldr = n;
+    GemmArgs g = gemm_args_linear(nullptr, k, w, bias, nullptr, n, m, n, k, false, nullptr, n);
     g.c16 = reinterpret_cast<_Float16*>(qk16_out); g.ldc16 = n;
     g.vt16 = reinterpret_cast<_Float16*>(vt_out); g.vt_col0 = 2 * (n / 3); g.vt_rows = rows_per_batch; g.vt_ld = rows_per_batch;
-    hipError_t e = launch_gemm_hh(g, st, force_tile);
-    hipError_t e2 = hipStreamSynchronize(st);
-    HIPRET(e);
-    HIPRET(e2);
-    return ER_OK;
+    return gemm_hh_entry(a, k, g, st, [&](const GemmArgs& ga) { return launch_gemm_hh(ga, st, force_tile); });
 }
 
 extern "C" int er_k_gemm_hh_geglu(const float* a, const void* w, const float* bias, void* out16, int m, int f, int k, int force_tile,
@@ -2144,33 +2119,22 @@ extern "C" int er_k_gemm_hh_geglu(const float* a, const void* w, const float* bi
     if (k % 64 || f % 64 || m <= 0) return fail(ER_ERR_INVALID, "er_k_gemm_hh_geglu: k and f must be multiples of 64");
     if (force_tile != 0 && force_tile != 1 && force_tile != 2 && force_tile != 4) return fail(ER_ERR_INVALID, "er_k_gemm_hh_geglu: force_tile 0 / 1 / 2 / 4");
     hipStream_t st = (hipStream_t)stream;
-    DevBuf<_Float16> a16b, wpb;      // fp16 copy of a, permuted weight
+    DevBuf<_Float16> wpb;            // permuted weight
     DevBuf<float> bpb;               // permuted bias
-    ERCHK(a16b.ensure((size_t)m * k));
     ERCHK(wpb.ensure((size_t)2 * f * k));
     ERCHK(bpb.ensure((size_t)2 * f));
-    _Float16 *a16 = a16b.p, *wp = wpb.p;
-    float* bp = bpb.p;
-    hipLaunchKernelGGL(cvt_rows_f16_kernel, dim3(ew_grid((long long)m * k)), dim3(ER_WG), 0, st, a, a16, (long long)m, k, k, k);
-    hipLaunchKernelGGL(geglu_permute_kernel, dim3(2 * f), dim3(ER_WG), 0, st, reinterpret_cast<const _Float16*>(w), bias, wp, bp, f, k);
-    GemmArgs g = gemm_args_default();
-    g.A = reinterpret_cast<const float*>(a16); g.B = reinterpret_cast<const float*>(wp); g.bias = bp;
-    g.M = m; g.N = 2 * f; g.K = k; g.lda = k; g.ldb = k; g.ldc = 2 * f; g.ldr = 2 * f;
+    hipLaunchKernelGGL(geglu_permute_kernel, dim3(2 * f), dim3(ER_WG), 0, st, reinterpret_cast<const _Float16*>(w), bias, wpb.p, bpb.p, f, k);
+    GemmArgs g = gemm_args_linear(nullptr, k, wpb.p, bpb.p, nullptr, 2 * f, m, 2 * f, k, false, nullptr, 2 * f);
     g.c16 = reinterpret_cast<_Float16*>(out16); g.ldc16 = f;
-    hipError_t e = launch_gemm_hh_geglu(g, st, force_tile);
-    hipError_t e2 = hipStreamSynchronize(st);
-    HIPRET(e);
-    HIPRET(e2);
-    return ER_OK;
+    return gemm_hh_entry(a, k, g, st, [&](const GemmArgs& ga) { return launch_gemm_hh_geglu(ga, st, force_tile); });
 }
 
 extern "C" int er_k_gemm_f16s(const float* a, const void* w, const float* bias, const float* resid, float* cc, int m, int n, int k,
                               int lda, int ldb, int ldc, int relu, void* stream) {
     if (k % 32) return fail(ER_ERR_INVALID, "er_k_gemm_f16s: k must be a multiple of 32");
     hipStream_t st = (hipStream_t)stream;
-    GemmArgs g = gemm_args_default();
-    g.A = a; g.B = reinterpret_cast<const float*>(w); g.C = cc; g.bias = bias; g.resid = resid; g.M = m; g.N = n; g.K = k;
-    g.lda = lda; g.ldb = ldb; g.ldc = ldc; g.ldr = ldc; g.relu = relu;
+    GemmArgs g = gemm_args_linear(a, lda, w, bias, cc, ldc, m, n, k, relu != 0, resid, ldc);
+    g.ldb = ldb;
     // ER_K_GEMM_F16S_FORM = reg / dma pins one of the two forms linear_hs chooses between (unit tests compare them bit for bit)
     const bool force_reg = env_is("ER_K_GEMM_F16S_FORM", 'r');
     if (k % XBK == 0 && !(ldb & 7) && !force_reg) {      // the product path of the fast-mode prefill: split pass + LDS-DMA kernel (linear_hs)
@@ -2179,11 +2143,7 @@ extern "C" int er_k_gemm_f16s(const float* a, const void* w, const float* bias, 
         ERCHK(lo.ensure((size_t)m * k));
         hipLaunchKernelGGL(split_rows_f16_kernel, split_rows_grid(m, k), dim3(ER_WG), 0, st, a, hi.p, lo.p, (long long)m, k, lda);
         g.A = reinterpret_cast<const float*>(hi.p); g.a_lo = lo.p; g.lda = k;
-        hipError_t e = launch_gemm_hh_split(g, st);
-        hipError_t e2 = hipStreamSynchronize(st);
-        HIPRET(e);
-        HIPRET(e2);
-        return ER_OK;
+        return gemm_sync_report(launch_gemm_hh_split(g, st), st);
     }
     HIPRET(launch_gemm_f16s(g, st));      // k % 64 != 0: the register-staged kernel
     return ER_OK;

@@ -172,6 +172,19 @@ __device__ __forceinline__ float row_bcast(float v, float fill) {
     return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(fill), __float_as_int(v), CTRL, ROW_MASK, 0xF, false));
 }
 
+// ---- LDS-DMA (global_load_lds_dwordx4)
+typedef __attribute__((address_space(1))) const void* er_gptr;
+typedef __attribute__((address_space(3))) void* er_lptr;
+// One 16-byte-per-lane piece: LDS[lds_byte_addr + 16 lane] <- gsrc (per lane).  Inline asm ON PURPOSE: hipcc treats the builtin as an
+// LDS write that every later ds_read may alias and parks a vmcnt(0) in front of the fragment reads of EVERY tile (or inside
+// __syncthreads), which serialises a multi-stage pipeline; an asm statement is invisible to that bookkeeping, so the waits are the
+// counted ones the kernel writes itself (flash_attn_hh_kernel, gemm_hh256_kernel).  M0 (the DMA's LDS base) is saved and restored.
+__device__ __forceinline__ void er_glds16(const void* gsrc, unsigned lds_byte_addr) {
+    unsigned keep;
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep) : "v"(gsrc), "s"(lds_byte_addr) : "memory");
+}
+
 __device__ __forceinline__ float dot4(const f32x4& a, const f32x4& b, float acc) {
     acc = fmaf(a.x, b.x, acc);
     acc = fmaf(a.y, b.y, acc);

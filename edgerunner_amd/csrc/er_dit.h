@@ -242,8 +242,7 @@ static int dit_loss_coefs(const int32_t* t, int B, int pred_type, float gamma, s
 // Linear layer: fp32 MFMA, or (fast mode) fp16-input MFMA with the activation rounded to fp16 on the way in
 static hipError_t dlin(er_dit_ctx* c, const float* A, int lda, const float* W, const float* bias, float* C, int ldc, int M, int N,
                        int K, const float* resid, int ldr, const float* gate, int gate_rows, hipStream_t st) {
-    GemmArgs g = gemm_args_default();
-    g.A = A; g.B = W; g.C = C; g.bias = bias; g.resid = resid; g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = K; g.ldc = ldc; g.ldr = ldr;
+    GemmArgs g = gemm_args_linear(A, lda, W, bias, C, ldc, M, N, K, false, resid, ldr);
     g.gate = gate; g.gate_rows = gate_rows; g.gate_bstride = N;
     if (c->fast && K % 32 == 0) {
         auto it = c->w.half_of.find(W);
@@ -357,9 +356,7 @@ static int dit_build_geglu_perm(er_dit_ctx* c, hipStream_t st) {
 static hipError_t dlin16(er_dit_ctx* c, const _Float16* A16, int lda, const float* W, const float* bias, float* C, int ldc, int M,
                          int N, int K, const float* resid, int ldr, const float* gate, int gate_rows, _Float16* c16, hipStream_t st,
                          _Float16* vt16 = nullptr, int vt_rows = 0) {
-    GemmArgs g = gemm_args_default();
-    g.A = reinterpret_cast<const float*>(A16); g.C = C; g.bias = bias; g.resid = resid; g.M = M; g.N = N; g.K = K;
-    g.lda = lda; g.ldb = K; g.ldc = ldc; g.ldr = ldr;
+    GemmArgs g = gemm_args_linear(A16, lda, nullptr, bias, C, ldc, M, N, K, false, resid, ldr);      // (B: the fp16 copy of W, below)
     g.gate = gate; g.gate_rows = gate_rows; g.gate_bstride = N;
     g.c16 = c16; g.ldc16 = N;
     if (vt16) { g.vt16 = vt16; g.vt_col0 = 2 * (N / 3); g.vt_rows = vt_rows; g.vt_ld = vt_rows; }

@@ -127,7 +127,7 @@ inline hipError_t launch_flash_attn_f16(const FlashArgs& a, int H, int B, hipStr
 
 // ---------------------------------------------------------------------------------------------------
 // The same attention with q / k / v ALREADY in fp16 (written by the qkv GEMM's epilogue) and V pre-transposed: the K and V^T tiles
-// come in by LDS-DMA (global_load_lds_dwordx4) into the XOR-swizzled image of k_gemm.h (chunk c of row r at slot c ^ ((r >> 1) & 7)),
+// come in by LDS-DMA (global_load_lds_dwordx4) into the XOR-swizzled image of er_gemm_map.h (chunk c of row r at slot swz_slot(r, c)),
 // two LDS stages, one barrier per key tile - no staging registers, no conversion, no ds_write (flash_attn_f16_kernel spends its
 // time there: fp32 loads, 12 conversions and 16 two-byte transposing LDS stores per thread and tile: 183 TFLOP/s on the DiT
 // self-attention).  Arithmetic identical to flash_attn_f16_kernel: the operands are the same fp16 roundings.
@@ -141,18 +141,7 @@ struct FlashHArgs {
     int head_stride;
     float scale;
 };
-typedef __attribute__((address_space(3))) void* fa_lptr;
-
-// One 16-byte-per-lane LDS-DMA piece: LDS[lds_byte_addr + 16 lane] <- gsrc (per lane).  Inline asm ON PURPOSE: hipcc treats the
-// builtin as an LDS write that every later ds_read may alias and drains vmcnt(0) before the first fragment read of EVERY tile, which
-// serialises a multi-stage pipeline (seen in the ISA of the 4-stage loop below); an asm statement is invisible to that bookkeeping,
-// so the waits are the counted ones written in the loop.  M0 (the DMA's LDS base) is saved and restored inside the statement.
-__device__ __forceinline__ void fa_glds16(const void* gsrc, unsigned lds_byte_addr) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(lds_byte_addr) : "memory");
-}
-
+// (the LDS-DMA pieces go out through er_common.h er_glds16: inline asm, so that the waits are the counted ones written in the loop)
 __global__ __launch_bounds__(ER_WG) void flash_attn_hh_kernel(FlashHArgs a) {
     constexpr int TILE = 64 * 64;                                   // halves per K (or V^T) tile image
     // FOUR stages: a key tile is only 16 MFMAs per wave (~0.25 us) while a tile's LDS-DMA takes 1-3 us to land with 512 workgroups
@@ -187,12 +176,12 @@ __global__ __launch_bounds__(ER_WG) void flash_attn_hh_kernel(FlashHArgs a) {
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
         const int r = 8 * (2 * wid + j) + lrow;
-        const int sl = (lslot ^ ((r >> 1) & 7)) << 3;
+        const int sl = swz_chunk_off<2>(r, lslot);
         krow[j] = r;
         pk[j] = K + sl;                                             // + (clamped key) * ldk per tile
         pv[j] = Vt + (long long)r * a.ldvt + sl;                    // + kbase per tile
     }
-    const unsigned lds_base = (unsigned)(unsigned long long)(fa_lptr)lds;
+    const unsigned lds_base = (unsigned)(unsigned long long)(er_lptr)lds;
     auto issue = [&](int t, int s) {
         const int kbase = t * FA_KT;
         const unsigned ks_ = lds_base + (unsigned)(s * 2 * TILE + 8 * 2 * wid * 64) * 2u;      // bytes; this wave's first piece
@@ -200,16 +189,15 @@ __global__ __launch_bounds__(ER_WG) void flash_attn_hh_kernel(FlashHArgs a) {
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
             const _Float16* src = pk[j] + (long long)min(kbase + krow[j], a.M - 1) * a.ldk;
-            fa_glds16(src, ks_ + j * 8 * 64 * 2u);
+            er_glds16(src, ks_ + j * 8 * 64 * 2u);
         }
 #pragma unroll
-        for (int j = 0; j < 2; ++j) fa_glds16(pv[j] + kbase, vs_ + j * 8 * 64 * 2u);
+        for (int j = 0; j < 2; ++j) er_glds16(pv[j] + kbase, vs_ + j * 8 * 64 * 2u);
     };
 
     fa_acc ot[2];
     fa_zero(ot);
     float m_run = -INFINITY, l_run = 0.f;
-    const int swz = (li >> 1) & 7;
     const int ntiles = (a.M + FA_KT - 1) / FA_KT;
     const float sl2 = a.scale * 1.4426950408889634f;       // base-2 softmax (fa_softmax_exp2)
 #pragma unroll
@@ -235,7 +223,7 @@ __global__ __launch_bounds__(ER_WG) void flash_attn_hh_kernel(FlashHArgs a) {
             fa_zero(st[kb]);
 #pragma unroll
             for (int ks = 0; ks < 4; ++ks) {
-                const fa_h8 ka = *reinterpret_cast<const fa_h8*>(Ks + (kb * 32 + li) * 64 + (((2 * ks + half) ^ swz) << 3));
+                const fa_h8 ka = *reinterpret_cast<const fa_h8*>(Ks + (kb * 32 + li) * 64 + swz_frag_off<2, 8>(ks, half, li));
                 st[kb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ka, qb[ks], st[kb], 0, 0, 0);
             }
         }
@@ -250,7 +238,7 @@ __global__ __launch_bounds__(ER_WG) void flash_attn_hh_kernel(FlashHArgs a) {
                 const int c0 = kb * 4 + 2 * stp + half;
 #pragma unroll
                 for (int db = 0; db < 2; ++db) {
-                    const fa_h8 va = *reinterpret_cast<const fa_h8*>(Vs + (db * 32 + li) * 64 + ((c0 ^ swz) << 3));
+                    const fa_h8 va = *reinterpret_cast<const fa_h8*>(Vs + (db * 32 + li) * 64 + swz_chunk_off<2>(li, c0));
                     ot[db] = __builtin_amdgcn_mfma_f32_32x32x16_f16(va, pb, ot[db], 0, 0, 0);
                 }
             }
@@ -262,7 +250,7 @@ __global__ __launch_bounds__(ER_WG) void flash_attn_hh_kernel(FlashHArgs a) {
         for (int db = 0; db < 2; ++db)
 #pragma unroll
             for (int r = 0; r < 16; r += 4) {                        // registers r .. r+3 = 4 consecutive head dims
-                const long long o = (long long)q * a.ldo + db * 32 + 8 * (r >> 2) + 4 * half;
+                const long long o = (long long)q * a.ldo + db * 32 + fa_row(r, half);
                 *reinterpret_cast<fa_h4*>(O16 + o) = (fa_h4){(_Float16)(ot[db][r] / l_tot), (_Float16)(ot[db][r + 1] / l_tot),
                                                              (_Float16)(ot[db][r + 2] / l_tot), (_Float16)(ot[db][r + 3] / l_tot)};
             }

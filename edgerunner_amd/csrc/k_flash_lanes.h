@@ -10,6 +10,7 @@
 #pragma once
 #include <type_traits>
 #include "er_common.h"
+#include "er_gemm_map.h"
 
 namespace er {
 
@@ -22,7 +23,7 @@ typedef float fa_acc __attribute__((ext_vector_type(16)));      // one 32 x 32 f
 //   S^T / P^T block kb of a tile: the KEY kbase + 32 kb + fa_row(r, half)
 //   O^T block db:                 the HEAD DIM 32 db + fa_row(r, half)
 // (registers 4g .. 4g+3 are four consecutive rows starting at 8g + 4 half)
-__host__ __device__ __forceinline__ constexpr int fa_row(int r, int half) { return (r & 3) + 8 * (r >> 2) + 4 * half; }
+__host__ __device__ __forceinline__ constexpr int fa_row(int r, int half) { return mfma32_row(r, half); }
 
 __device__ __forceinline__ void fa_zero(fa_acc& x) {
 #pragma unroll

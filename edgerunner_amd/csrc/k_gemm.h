@@ -14,8 +14,10 @@
 // is a conflict-free ds_read_b32; the next k-tile is prefetched into registers while
 // the current one is multiplied.
 #pragma once
+#include <type_traits>
 #include "er_common.h"
 #include "er_gemm_rows.h"
+#include "k_gemm_lanes.h"
 
 namespace er {
 
@@ -59,10 +61,8 @@ struct GemmArgs {
 
 constexpr int GBK = 32;
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 // epilogue shared by the fp32 and fp16-input kernels: C/D fragment map of the 32x32 MFMA (dtype independent):
-// col = lane&31, row = (r&3) + 8*(r>>2) + 4*(lane>>5).
+// col = lane & 31, row = mfma32_row(r, lane >> 5).
 // Everything that depends on the column only (bias, the q/k/v split of GEPI_QKV) is resolved once per 32-column block, and the
 // row -> batch maps (adaLN gate row, shared residual table, cache row of GEPI_QKV) without a division per element: a wave's 32
 // rows cross at most one batch boundary when the batch has >= 32 rows (otherwise the generic division path runs).  Round 2
@@ -100,7 +100,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& g, float* C, const
                            sb(row0, qkv ? g.S : 0);
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int gm = row0 + (r & 3) + 8 * (r >> 2) + 4 * kh;
+                const int gm = row0 + mfma32_row(r, kh);
                 if (gm >= g.M) continue;
                 float v = acc[i][j][r];
                 if (has_div) v = v / g.div;
@@ -214,12 +214,7 @@ __global__ __launch_bounds__(ER_WG) void gemm_f32_mfma_kernel(GemmArgs g) {
     };
 
     f32x16 acc[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    gm_zero(acc);
 
     if (nk > 0) {
         load_tile(0);
@@ -239,10 +234,7 @@ __global__ __launch_bounds__(ER_WG) void gemm_f32_mfma_kernel(GemmArgs g) {
             for (int i = 0; i < TM; ++i) av[i] = ap[32 * i];
 #pragma unroll
             for (int j = 0; j < TN; ++j) bv[j] = bp[32 * j];
-#pragma unroll
-            for (int i = 0; i < TM; ++i)
-#pragma unroll
-                for (int j = 0; j < TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[i], bv[j], acc[i][j], 0, 0, 0);
+            gm_mfma_f32(acc, av, bv);
         }
         // the other stage was last read in iteration kt-1, and every wave passed that iteration's barrier since
         if (kt + 1 < nk) store_tile(cur ^ 1);
@@ -253,113 +245,29 @@ __global__ __launch_bounds__(ER_WG) void gemm_f32_mfma_kernel(GemmArgs g) {
 }
 
 // ---------------------------------------------------------------------------------------------------
-// fp16-input variant for the compute-bound front-end GEMMs (DiT / CLIP linears in fast mode):
-//   C[M,N] = epilogue( fp16(A[M,K] fp32) . fp16 W[N,K]^T ), fp32 accumulate on v_mfma_f32_32x32x16_f16
-// (16x the fp32 matrix rate).  Tile 128x128x32; A is rounded to fp16 on its way into LDS, W is stored fp16.
-// LDS rows are [row][32 k] halves padded to 80 bytes so the 16-byte operand reads (lane l: row l&31,
-// k-block (l>>5)*8) hit 16 distinct 4-bank slots per 16-lane group.  Both operands use the same
-// (lane-half, element) -> k assignment, so the product sum is independent of the instruction's internal k order.
-constexpr int HBK = 32, HLD = 40;            // halves per LDS row (32 + 8 pad)
-typedef _Float16 h16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 h16x4 __attribute__((ext_vector_type(4)));
-
-template <int TM, int TN>
+// fp16-weight variant with a register-staged fp32 A, in two forms of one body:
+//   plain (SPLIT = false), for the compute-bound front-end GEMMs (DiT / CLIP linears in fast mode):
+//     C[M,N] = epilogue( fp16(A[M,K] fp32) . fp16 W[N,K]^T ), fp32 accumulate on v_mfma_f32_32x32x16_f16 (16x the fp32 matrix rate);
+//     A is rounded to fp16 on its way into LDS, W is stored fp16;
+//   split (SPLIT = true), for the FAST-mode prefill (fp16-stored decoder weights, fp32 activations, fp32 accumulate - the arithmetic
+//     the per-token GEMV path performs): the fp32 activation is split on its way into LDS into two fp16 numbers,
+//       a = hi + lo,  hi = fp16(a),  lo = fp16(a - hi)      (|a - hi - lo| <= 2^-22 |a|: fp32-grade operand),
+//     and every weight fragment is multiplied by both (two MFMAs per fragment pair, fp16 x fp16 products are exact in the fp32
+//     accumulator).  16x the fp32 matrix rate at twice the instruction count = 8x, with results within fp32 round-off of the
+//     fp32-activation product - so prefill and decode keep seeing one model and the fast-mode parity tests (ids exact / logits vs the
+//     fp16-STORAGE emulation) hold unchanged.
+// LDS rows are [row][BK k] halves padded by 8 (80 / 144 bytes) so the 16-byte operand reads (lane l: row l & 31, k-block (l >> 5) * 8)
+// hit 16 distinct 4-bank slots per 16-lane group.  Both operands use the same (lane-half, element) -> k assignment, so the product
+// sum is independent of the instruction's internal k order.
+// ONE LDS stage (20 KB plain, 30 KB split -> 5 workgroups per CU): a k-tile is only 8 MFMAs (256 cycles) per wave, far shorter than a
+// global-load round trip, so what hides that latency is the number of workgroups per CU, not a second LDS stage (a two-stage version
+// measured slower: 21.4 vs 20.4 ms per DiT forward; PMC: the split form sat at 16 % MFMA busy with two stages).
+template <int BK, int TM, int TN, bool SPLIT>
 __global__ __launch_bounds__(ER_WG) void gemm_f16_mfma_kernel(GemmArgs g) {
     constexpr int GBM = 64 * TM, GBN = 64 * TN;
-    // ONE LDS stage (20 KB): a k-tile is only 8 MFMAs (256 cycles) per wave, far shorter than a global-load round trip, so
-    // what hides that latency is the number of workgroups per CU, not a second LDS stage (a two-stage version measured
-    // slower: 21.4 vs 20.4 ms per DiT forward; PMC: the split kernel below sat at 16 % MFMA busy with two stages)
-    __shared__ __attribute__((aligned(16))) _Float16 As[1][GBM * HLD];
-    __shared__ __attribute__((aligned(16))) _Float16 Bs[1][GBN * HLD];
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    const int wm = wid >> 1, wn = wid & 1;
-    const int m0 = blockIdx.y * GBM, n0 = blockIdx.x * GBN;
-    const float* A = g.A;
-    const _Float16* B = reinterpret_cast<const _Float16*>(g.B);
-    const int nk = g.K / HBK;
-    constexpr int NA = GBM / 32, NB = (GBN + 63) / 64;      // float4 of A / 16-byte pieces of B per thread and k-tile
-    f32x4 ra[NA];
-    f32x4 rb[NB];
-    const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
-    auto load_tile = [&](int kt) {
-        const int k0 = kt * HBK;
-#pragma unroll
-        for (int u = 0; u < NA; ++u) {
-            const int idx = tid + ER_WG * u, row = idx >> 3, c4 = idx & 7;
-            const int gm = m0 + row;
-            ra[u] = (gm < g.M) ? *reinterpret_cast<const f32x4*>(A + (long long)gm * g.lda + k0 + 4 * c4) : zero4;
-        }
-#pragma unroll
-        for (int u = 0; u < NB; ++u) {
-            const int idx = tid + ER_WG * u, row = idx >> 2, c8 = idx & 3;
-            const int gn = n0 + row;
-            rb[u] = (gn < g.N && row < GBN) ? *reinterpret_cast<const f32x4*>(B + (long long)gn * g.ldb + k0 + 8 * c8) : zero4;
-        }
-    };
-    auto store_tile = [&](int s) {
-#pragma unroll
-        for (int u = 0; u < NA; ++u) {
-            const int idx = tid + ER_WG * u, row = idx >> 3, c4 = idx & 7;
-            h16x4 hv = {(_Float16)ra[u].x, (_Float16)ra[u].y, (_Float16)ra[u].z, (_Float16)ra[u].w};
-            *reinterpret_cast<h16x4*>(&As[s][row * HLD + 4 * c4]) = hv;
-        }
-#pragma unroll
-        for (int u = 0; u < NB; ++u) {
-            const int idx = tid + ER_WG * u, row = idx >> 2, c8 = idx & 3;
-            if (row < GBN) *reinterpret_cast<f32x4*>(&Bs[s][row * HLD + 8 * c8]) = rb[u];
-        }
-    };
-    f32x16 acc[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-    if (nk > 0) {
-        load_tile(0);
-        store_tile(0);
-    }
-    __syncthreads();
-    const int kh = lane >> 5, li = lane & 31;
-    for (int kt = 0; kt < nk; ++kt) {
-        constexpr int cur = 0;
-        if (kt + 1 < nk) load_tile(kt + 1);
-#pragma unroll
-        for (int ks = 0; ks < HBK / 16; ++ks) {
-            const int ko = ks * 16 + kh * 8;
-            h16x8 av[TM], bv[TN];
-#pragma unroll
-            for (int i = 0; i < TM; ++i) av[i] = *reinterpret_cast<const h16x8*>(&As[cur][(wm * 32 * TM + 32 * i + li) * HLD + ko]);
-#pragma unroll
-            for (int j = 0; j < TN; ++j) bv[j] = *reinterpret_cast<const h16x8*>(&Bs[cur][(wn * 32 * TN + 32 * j + li) * HLD + ko]);
-#pragma unroll
-            for (int i = 0; i < TM; ++i)
-#pragma unroll
-                for (int j = 0; j < TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(av[i], bv[j], acc[i][j], 0, 0, 0);
-        }
-        __syncthreads();
-        if (kt + 1 < nk) store_tile(0);
-        __syncthreads();
-    }
-    gemm_epilogue<TM, TN>(g, g.C, acc, m0, n0, wm, wn, kh, li);
-}
-
-// ---------------------------------------------------------------------------------------------------
-// "Split" fp16 variant for the FAST-mode prefill (fp16-stored decoder weights, fp32 activations, fp32 accumulate - the
-// arithmetic the per-token GEMV path performs): the fp32 activation is split on its way into LDS into two fp16 numbers,
-//   a = hi + lo,  hi = fp16(a),  lo = fp16(a - hi)      (|a - hi - lo| <= 2^-22 |a|: fp32-grade operand),
-// and every weight fragment is multiplied by both (two v_mfma_f32_32x32x16_f16 per fragment pair, fp16 x fp16 products
-// are exact in the fp32 accumulator).  16x the fp32 matrix rate at twice the instruction count = 8x, with results within
-// fp32 round-off of the fp32-activation product - so prefill and decode keep seeing one model and the fast-mode parity
-// tests (ids exact / logits vs the fp16-STORAGE emulation) hold unchanged.  Tile 128x128x32, two LDS stages.
-template <int BK, int TM, int TN>
-__global__ __launch_bounds__(ER_WG) void gemm_f16s_mfma_kernel(GemmArgs g) {
-    constexpr int GBM = 64 * TM, GBN = 64 * TN;
-    constexpr int LDH = BK + 8;            // halves per LDS row (16-byte reads of a 16-lane group hit 16 distinct 4-bank slots for 40 and 72)
-    // one LDS stage (30 KB -> 5 workgroups per CU): see gemm_f16_mfma_kernel
+    constexpr int LDH = BK + 8;            // halves per LDS row
     __shared__ __attribute__((aligned(16))) _Float16 Ah[1][GBM * LDH];
-    __shared__ __attribute__((aligned(16))) _Float16 Al[1][GBM * LDH];
+    __shared__ __attribute__((aligned(16))) _Float16 Al[1][SPLIT ? GBM * LDH : 8];
     __shared__ __attribute__((aligned(16))) _Float16 Bs[1][GBN * LDH];
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int wm = wid >> 1, wn = wid & 1;
@@ -392,10 +300,12 @@ __global__ __launch_bounds__(ER_WG) void gemm_f16s_mfma_kernel(GemmArgs g) {
         for (int u = 0; u < NA; ++u) {
             const int idx = tid + ER_WG * u, row = idx / C4, c4 = idx % C4;
             const h16x4 hv = {(_Float16)ra[u].x, (_Float16)ra[u].y, (_Float16)ra[u].z, (_Float16)ra[u].w};
-            const h16x4 lv = {(_Float16)(ra[u].x - (float)hv[0]), (_Float16)(ra[u].y - (float)hv[1]),
-                              (_Float16)(ra[u].z - (float)hv[2]), (_Float16)(ra[u].w - (float)hv[3])};
             *reinterpret_cast<h16x4*>(&Ah[s][row * LDH + 4 * c4]) = hv;
-            *reinterpret_cast<h16x4*>(&Al[s][row * LDH + 4 * c4]) = lv;
+            if constexpr (SPLIT) {
+                const h16x4 lv = {(_Float16)(ra[u].x - (float)hv[0]), (_Float16)(ra[u].y - (float)hv[1]),
+                                  (_Float16)(ra[u].z - (float)hv[2]), (_Float16)(ra[u].w - (float)hv[3])};
+                *reinterpret_cast<h16x4*>(&Al[s][row * LDH + 4 * c4]) = lv;
+            }
         }
 #pragma unroll
         for (int u = 0; u < NB; ++u) {
@@ -404,12 +314,7 @@ __global__ __launch_bounds__(ER_WG) void gemm_f16s_mfma_kernel(GemmArgs g) {
         }
     };
     f32x16 acc[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    gm_zero(acc);
     if (nk > 0) {
         load_tile(0);
         store_tile(0);
@@ -422,23 +327,19 @@ __global__ __launch_bounds__(ER_WG) void gemm_f16s_mfma_kernel(GemmArgs g) {
 #pragma unroll
         for (int ks = 0; ks < BK / 16; ++ks) {
             const int ko = ks * 16 + kh * 8;
-            h16x8 bv[TN], ah[TM], al[TM];
+            // (both A images read before the first MFMA: with the lo reads and MFMAs first and one fragment array re-used, the split
+            // 128 x 128 forms took 6 / 2 more registers - profiles/gemm_lanes_ab.log)
+            h16x8 bv[TN], ah[TM], al[SPLIT ? TM : 1];
 #pragma unroll
             for (int j = 0; j < TN; ++j) bv[j] = *reinterpret_cast<const h16x8*>(&Bs[cur][(wn * 32 * TN + 32 * j + li) * LDH + ko]);
 #pragma unroll
             for (int i = 0; i < TM; ++i) {
                 ah[i] = *reinterpret_cast<const h16x8*>(&Ah[cur][(wm * 32 * TM + 32 * i + li) * LDH + ko]);
-                al[i] = *reinterpret_cast<const h16x8*>(&Al[cur][(wm * 32 * TM + 32 * i + li) * LDH + ko]);
+                if constexpr (SPLIT) al[i] = *reinterpret_cast<const h16x8*>(&Al[cur][(wm * 32 * TM + 32 * i + li) * LDH + ko]);
             }
-            // the small (lo) products first, then the large ones: the accumulator sees them in increasing magnitude
-#pragma unroll
-            for (int i = 0; i < TM; ++i)
-#pragma unroll
-                for (int j = 0; j < TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[i], bv[j], acc[i][j], 0, 0, 0);
-#pragma unroll
-            for (int i = 0; i < TM; ++i)
-#pragma unroll
-                for (int j = 0; j < TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bv[j], acc[i][j], 0, 0, 0);
+            // split: the small (lo) products first, then the large ones: the accumulator sees them in increasing magnitude
+            if constexpr (SPLIT) gm_mfma_f16(acc, al, bv);
+            gm_mfma_f16(acc, ah, bv);
         }
         __syncthreads();
         if (kt + 1 < nk) store_tile(0);
@@ -450,7 +351,7 @@ __global__ __launch_bounds__(ER_WG) void gemm_f16s_mfma_kernel(GemmArgs g) {
 // ---------------------------------------------------------------------------------------------------
 // fp16 x fp16 variant with BOTH operands brought in by LDS-DMA (global_load_lds_dwordx4): for the compute-bound front-end GEMMs
 // whose activations already exist in fp16 (the producing kernel - adaLN-modulated LayerNorm, attention, GEGLU, a GEMM epilogue -
-// writes an fp16 copy of what it hands to the next Linear, rounding exactly where gemm_f16_mfma_kernel rounds on its way in, so
+// writes an fp16 copy of what it hands to the next Linear, rounding exactly where gemm_f16_mfma_kernel (plain form) rounds on its way in, so
 // the results are bit-identical to that kernel's).  Round 2's kernel staged both operands through registers (fp32 A converted in
 // the loop, one LDS stage, two barriers per 32-deep k-tile): 19-25 % MFMA-busy with a third of the LDS cycles lost to bank conflicts
 // (profiles/r02_pmc_sq_prefill_fp16.json).  Here:
@@ -464,8 +365,6 @@ __global__ __launch_bounds__(ER_WG) void gemm_f16s_mfma_kernel(GemmArgs g) {
 // Requires K % 64 == 0, lda / ldb multiples of 8 halves, 16-byte aligned operands.  Rows beyond M / N are clamped on load and
 // dropped by the epilogue.
 constexpr int XBK = 64;
-typedef __attribute__((address_space(1))) const void* er_gptr;
-typedef __attribute__((address_space(3))) void* er_lptr;
 typedef _Float16 h16x2 __attribute__((ext_vector_type(2)));
 
 // Epilogue of the LDS-DMA kernel.  The MFMA accumulator holds a COLUMN per lane (4 consecutive rows per register quad), so storing
@@ -478,14 +377,6 @@ typedef _Float16 h16x2 __attribute__((ext_vector_type(2)));
 //               [32,64) the gate part of the SAME 32 outputs: out16[m][j] = fp16((x + bx) * gelu_erf(gt + bg))
 //               (core/transformer/dit.py FeedForward / point.py:68-71), the [M][2F] pre-activation never reaches HBM.
 enum { HEPI_PLAIN = 0, HEPI_GEGLU = 1 };
-
-// row of the ORIGINAL [2F][K] GEGLU weight that sits at row p of the permuted copy (tile = 128 columns = 4 blocks of 32:
-// {value j0..j0+31, gate j0..j0+31, value j0+32.., gate j0+32..}); host and device agree through this one function
-__host__ __device__ inline int gemm_hh_geglu_row(int p, int F) {
-    const int tile = p >> 7, local = p & 127, wn = local >> 6, blk = (local >> 5) & 1, l = local & 31;
-    const int j = tile * 64 + wn * 32 + l;
-    return blk == 0 ? j : F + j;
-}
 
 // Operands of the plain row-wise epilogue a caller already holds in registers (k_gemm_stream.h requests them when a tile STARTS, so
 // they arrive under the k-loop): bias at the lane's four columns, the gate rows of the two batches the wave's rows can lie in, the
@@ -522,7 +413,7 @@ __device__ __forceinline__ void hh_epi_stage(float* sw, const f32x16 (&acc)[TM][
 #pragma unroll
         for (int j = 0; j < TN; ++j)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) sw[(32 * i + (r & 3) + 8 * (r >> 2) + 4 * kh) * WC + 32 * j + li] = acc[i][j][r];
+            for (int r = 0; r < 16; ++r) sw[(32 * i + mfma32_row(r, kh)) * WC + 32 * j + li] = acc[i][j][r];
 }
 
 // the row-wise part: LDS slice -> bias / gate / residual / stores.  PARTS = 2: this call handles half `part` (0 / 1) of the slice's row
@@ -585,7 +476,7 @@ __device__ __forceinline__ void hh_epi_rows(const GemmArgs& g, const float* sw, 
         // keep the 4-fold unrolled loop: sixteen unrolled passes cost the q/k/v product 41.7 -> 47.5 us (same log; the round-3 lesson about
         // unrolled per-element option code and the instruction cache).  The gate row depends on the batch only: the wave's rows span at
         // most two batches (RowBatch fast path), one float4 each.
-        constexpr int NPASS = WR / RPP / PARTS, CH = NPASS < 8 ? NPASS : 8;
+        constexpr int NPASS = WR / RPP / PARTS;
         static_assert((WR / RPP) % PARTS == 0, "whole passes per part");
         const int t0 = part * NPASS;
         f32x4 gate0 = {1.f, 1.f, 1.f, 1.f}, gate1 = gate0;
@@ -599,77 +490,52 @@ __device__ __forceinline__ void hh_epi_rows(const GemmArgs& g, const float* sw, 
             gate1 = *reinterpret_cast<const f32x4*>(g.gate + (long long)gb1 * g.gate_bstride + gn);
         }
         const bool gate_pair = g.gate && vec && gb.fast;       // every row of the wave is in batch gb0 or gb1
-        if constexpr (NPASS > 8) {
-#pragma unroll 4
-            for (int t_ = 0; t_ < NPASS; ++t_) {
-                const int rr = rr0 + RPP * (t0 + t_), gm = mw + rr;
-                if (gm >= g.M) continue;
-                f32x4 v = *reinterpret_cast<const f32x4*>(sw + rr * WC + 4 * c4);
-                if (g.div != 0.f) { v.x = v.x / g.div; v.y = v.y / g.div; v.z = v.z / g.div; v.w = v.w / g.div; }
-                v += bias;
-                if (g.relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
-                const long long rrow = g.resid ? (long long)(g.resid_mod > 0 ? rb.inner(gm) : gm) * g.ldr + gn : 0;
-                const long long grow = g.gate ? (long long)gb.batch(gm) * g.gate_bstride + gn : 0;
-                if (vec) {
-                    if (g.gate) v *= gate_pair ? (gb.batch(gm) == gb0 ? gate0 : gate1) : *reinterpret_cast<const f32x4*>(g.gate + grow);
-                    if (g.resid) v += *reinterpret_cast<const f32x4*>(g.resid + rrow);
-                    if (g.C) *reinterpret_cast<f32x4*>(g.C + (long long)gm * g.ldc + gn) = v;
-                    if (g.c16) *reinterpret_cast<h16x4*>(g.c16 + (long long)gm * g.ldc16 + gn) = (h16x4){(_Float16)v.x, (_Float16)v.y, (_Float16)v.z, (_Float16)v.w};
-                } else {
-                    const float e[4] = {v.x, v.y, v.z, v.w};
+        // ONE pass loop for both forms.  AHEAD (32-row blocks): fully unrolled, the residual float4 of every pass requested (or handed in)
+        // before the first pass; otherwise (64-row blocks) 4-fold unrolled, the residual loaded in place.
+        constexpr bool AHEAD = NPASS <= 8;                         // (HhEpiPre holds at most eight passes)
+        constexpr int UNR = AHEAD ? NPASS : 4;
+        f32x4 rres[AHEAD ? NPASS : 1];
+        if constexpr (AHEAD) {
+            if (use_pre) {
 #pragma unroll
-                    for (int u = 0; u < 4; ++u) {
-                        if (gn + u >= g.N) break;
-                        float w = e[u];
-                        if (g.gate) w *= g.gate[grow + u];
-                        if (g.resid) w += g.resid[rrow + u];
-                        if (g.C) g.C[(long long)gm * g.ldc + gn + u] = w;
-                        if (g.c16) g.c16[(long long)gm * g.ldc16 + gn + u] = (_Float16)w;
-                    }
+                for (int t = 0; t < NPASS; ++t) rres[t] = pre_->res[t];
+            } else if (g.resid && vec) {
+#pragma unroll
+                for (int t = 0; t < NPASS; ++t) {
+                    const int gm = mw + rr0 + RPP * (t0 + t);
+                    const int rrow_ = g.resid_mod > 0 ? rb.inner(min(gm, g.M - 1)) : min(gm, g.M - 1);
+                    rres[t] = *reinterpret_cast<const f32x4*>(g.resid + (long long)rrow_ * g.ldr + gn);
                 }
             }
-        } else {
-#pragma unroll
-            for (int c0 = 0; c0 < NPASS; c0 += CH) {
-                f32x4 rres[CH];
-                if (NPASS <= 8 && use_pre) {                       // (HhEpiPre holds at most eight passes: 32-row blocks only)
-#pragma unroll
-                    for (int t = 0; t < CH; ++t) rres[t] = pre_->res[(c0 + t) & 7];
-                } else if (g.resid && vec) {
-#pragma unroll
-                    for (int t = 0; t < CH; ++t) {
-                        const int gm = mw + rr0 + RPP * (t0 + c0 + t);
-                        const int rrow_ = g.resid_mod > 0 ? rb.inner(min(gm, g.M - 1)) : min(gm, g.M - 1);
-                        rres[t] = *reinterpret_cast<const f32x4*>(g.resid + (long long)rrow_ * g.ldr + gn);
-                    }
+        }
+#pragma unroll UNR
+        for (int t = 0; t < NPASS; ++t) {
+            const int rr = rr0 + RPP * (t0 + t), gm = mw + rr;
+            if (gm >= g.M) continue;
+            f32x4 v = *reinterpret_cast<const f32x4*>(sw + rr * WC + 4 * c4);
+            if (g.div != 0.f) { v.x = v.x / g.div; v.y = v.y / g.div; v.z = v.z / g.div; v.w = v.w / g.div; }
+            v += bias;
+            if (g.relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
+            const long long rrow = g.resid ? (long long)(g.resid_mod > 0 ? rb.inner(gm) : gm) * g.ldr + gn : 0;
+            const long long grow = g.gate ? (long long)gb.batch(gm) * g.gate_bstride + gn : 0;
+            if (vec) {
+                if (g.gate) v *= gate_pair ? (gb.batch(gm) == gb0 ? gate0 : gate1) : *reinterpret_cast<const f32x4*>(g.gate + grow);
+                if (g.resid) {
+                    if constexpr (AHEAD) v += rres[t];
+                    else v += *reinterpret_cast<const f32x4*>(g.resid + rrow);
                 }
+                if (g.C) *reinterpret_cast<f32x4*>(g.C + (long long)gm * g.ldc + gn) = v;     // null: only the fp16 copy is wanted
+                if (g.c16) *reinterpret_cast<h16x4*>(g.c16 + (long long)gm * g.ldc16 + gn) = (h16x4){(_Float16)v.x, (_Float16)v.y, (_Float16)v.z, (_Float16)v.w};
+            } else {
+                const float e[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
-                for (int t = 0; t < CH; ++t) {
-                    const int rr = rr0 + RPP * (t0 + c0 + t), gm = mw + rr;
-                    if (gm >= g.M) continue;
-                    f32x4 v = *reinterpret_cast<const f32x4*>(sw + rr * WC + 4 * c4);
-                    if (g.div != 0.f) { v.x = v.x / g.div; v.y = v.y / g.div; v.z = v.z / g.div; v.w = v.w / g.div; }
-                    v += bias;
-                    if (g.relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
-                    const long long rrow = g.resid ? (long long)(g.resid_mod > 0 ? rb.inner(gm) : gm) * g.ldr + gn : 0;
-                    const long long grow = g.gate ? (long long)gb.batch(gm) * g.gate_bstride + gn : 0;
-                    if (vec) {
-                        if (g.gate) v *= gate_pair ? (gb.batch(gm) == gb0 ? gate0 : gate1) : *reinterpret_cast<const f32x4*>(g.gate + grow);
-                        if (g.resid) v += rres[t];
-                        if (g.C) *reinterpret_cast<f32x4*>(g.C + (long long)gm * g.ldc + gn) = v;     // null: only the fp16 copy is wanted
-                        if (g.c16) *reinterpret_cast<h16x4*>(g.c16 + (long long)gm * g.ldc16 + gn) = (h16x4){(_Float16)v.x, (_Float16)v.y, (_Float16)v.z, (_Float16)v.w};
-                    } else {
-                        const float e[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-                        for (int u = 0; u < 4; ++u) {
-                            if (gn + u >= g.N) break;
-                            float w = e[u];
-                            if (g.gate) w *= g.gate[grow + u];
-                            if (g.resid) w += g.resid[rrow + u];
-                            if (g.C) g.C[(long long)gm * g.ldc + gn + u] = w;
-                            if (g.c16) g.c16[(long long)gm * g.ldc16 + gn + u] = (_Float16)w;
-                        }
-                    }
+                for (int u = 0; u < 4; ++u) {
+                    if (gn + u >= g.N) break;
+                    float w = e[u];
+                    if (g.gate) w *= g.gate[grow + u];
+                    if (g.resid) w += g.resid[rrow + u];
+                    if (g.C) g.C[(long long)gm * g.ldc + gn + u] = w;
+                    if (g.c16) g.c16[(long long)gm * g.ldc16 + gn + u] = (_Float16)w;
                 }
             }
         }
@@ -710,7 +576,7 @@ __device__ __forceinline__ void gemm_hh_epilogue(const GemmArgs& g, float* sw, c
 
 // SPLIT: the A operand is hi + lo (two fp16 arrays: a = fp16(x), lo = fp16(x - hi), |x - hi - lo| <= 2^-22 |x|), every weight fragment
 // is multiplied by both (the lo products first), i.e. the fp16-weight x fp32-activation product to fp32 round-off - what
-// gemm_f16s_mfma_kernel computes from an fp32 A with a register-staged split; same MFMA order per accumulator -> same bits.
+// gemm_f16_mfma_kernel<SPLIT> computes from an fp32 A with a register-staged split; same MFMA order per accumulator -> same bits.
 template <int TM, int TN, int HEPI = HEPI_PLAIN, bool SPLIT = false>
 __global__ __launch_bounds__(ER_WG) void gemm_hh_mfma_kernel(GemmArgs g, int ntx) {
     constexpr int GBM = 64 * TM, GBN = 64 * TN, AROWS = SPLIT ? 2 * GBM : GBM;
@@ -721,32 +587,25 @@ __global__ __launch_bounds__(ER_WG) void gemm_hh_mfma_kernel(GemmArgs g, int ntx
     const int tid = threadIdx.x, lane = tid & 63;
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wid >> 1, wn = wid & 1;
-    // XCD-aware tile order (bijective for any grid size)
-    const int nwg = gridDim.x, xq = nwg >> 3, xr = nwg & 7, xcd = blockIdx.x & 7, within = blockIdx.x >> 3;
-    const int lin = (xcd < xr ? xcd * (xq + 1) : xr * (xq + 1) + (xcd - xr) * xq) + within;
-    const int ty = lin / ntx, tx = lin - ty * ntx;
-    const int m0 = ty * GBM, n0 = tx * GBN;
+    const TileYX tile = xcd_tile(blockIdx.x, gridDim.x, ntx);
+    const int m0 = tile.ty * GBM, n0 = tile.tx * GBN;
     const _Float16* A = reinterpret_cast<const _Float16*>(g.A);
     const _Float16* B = reinterpret_cast<const _Float16*>(g.B);
     const int nk = g.K / XBK;
 
     // per-lane source pointers of this wave's LDS-DMA pieces: piece i covers tile rows 8i .. 8i+7, lane -> (row 8i + lane/8, slot lane%8)
-    const int lrow = lane >> 3, lslot = lane & 7;
+    const int lrow = lane >> 3;
     const _Float16* pa[NAI];
     const _Float16* pl[SPLIT ? NAI : 1];
     const _Float16* pb[NBI];
 #pragma unroll
     for (int j = 0; j < NAI; ++j) {
-        const int r = 8 * (wid * NAI + j) + lrow;
-        const long long off = (long long)min(m0 + r, g.M - 1) * g.lda + ((lslot ^ ((r >> 1) & 7)) << 3);
+        const long long off = gm_dma_src<_Float16>(m0, 8 * (wid * NAI + j) + lrow, g.M - 1, g.lda, lane);
         pa[j] = A + off;
         if (SPLIT) pl[j] = g.a_lo + off;
     }
 #pragma unroll
-    for (int j = 0; j < NBI; ++j) {
-        const int r = 8 * (wid * NBI + j) + lrow;
-        pb[j] = B + (long long)min(n0 + r, g.N - 1) * g.ldb + ((lslot ^ ((r >> 1) & 7)) << 3);
-    }
+    for (int j = 0; j < NBI; ++j) pb[j] = B + gm_dma_src<_Float16>(n0, 8 * (wid * NBI + j) + lrow, g.N - 1, g.ldb, lane);
     auto issue = [&](int kt, int s) {
         _Float16* as = lds + s * STAGE;
         _Float16* bs = as + AROWS * XBK;
@@ -764,14 +623,9 @@ __global__ __launch_bounds__(ER_WG) void gemm_hh_mfma_kernel(GemmArgs g, int ntx
     };
 
     f32x16 acc[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    gm_zero(acc);
 
-    const int kh = lane >> 5, li = lane & 31, swz = (li >> 1) & 7;
+    const int kh = lane >> 5, li = lane & 31;
     if (nk > 0) issue(0, 0);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
@@ -782,24 +636,15 @@ __global__ __launch_bounds__(ER_WG) void gemm_hh_mfma_kernel(GemmArgs g, int ntx
         const _Float16* bs = lds + cur * STAGE + AROWS * XBK + (wn * 32 * TN + li) * XBK;
 #pragma unroll
         for (int ks = 0; ks < XBK / 16; ++ks) {
-            const int co = ((2 * ks + kh) ^ swz) << 3;
+            const int co = swz_frag_off<2, 8>(ks, kh, li);
             h16x8 av[TM], bv[TN];
-#pragma unroll
-            for (int j = 0; j < TN; ++j) bv[j] = *reinterpret_cast<const h16x8*>(bs + 32 * j * XBK + co);
+            gm_frags(bv, bs, co);
             if (SPLIT) {      // the small (lo) products first, then the large ones: the accumulator sees them in increasing magnitude
-#pragma unroll
-                for (int i = 0; i < TM; ++i) av[i] = *reinterpret_cast<const h16x8*>(as + (GBM + 32 * i) * XBK + co);
-#pragma unroll
-                for (int i = 0; i < TM; ++i)
-#pragma unroll
-                    for (int j = 0; j < TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(av[i], bv[j], acc[i][j], 0, 0, 0);
+                gm_frags(av, as + GBM * XBK, co);
+                gm_mfma_f16(acc, av, bv);
             }
-#pragma unroll
-            for (int i = 0; i < TM; ++i) av[i] = *reinterpret_cast<const h16x8*>(as + 32 * i * XBK + co);
-#pragma unroll
-            for (int i = 0; i < TM; ++i)
-#pragma unroll
-                for (int j = 0; j < TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(av[i], bv[j], acc[i][j], 0, 0, 0);
+            gm_frags(av, as, co);
+            gm_mfma_f16(acc, av, bv);
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's pieces of the next tile have landed ...
         __syncthreads();                                    // ... and everybody's; everybody is done reading `cur`
@@ -822,14 +667,7 @@ __global__ __launch_bounds__(ER_WG) void gemm_hh_mfma_kernel(GemmArgs g, int ntx
 // epilogue runs the 64 x 64 row-wise epilogue of the 4-wave kernel twice per wave (rows 0..63, 64..127 of its block) through
 // its 16 KB slice of the idle stage buffers.  For the wide products only (launch_gemm_hh / launch_gemm_hh_geglu pick it when it
 // fills the chip: N = 8192 feed-forward-in and N = 3072 qkv of the DiT front-end).
-// LDS-DMA pieces issued from inline asm (hipcc treats the builtin as an LDS write every later ds_read may alias and parks a
-// vmcnt(0) in front of the fragment reads / inside __syncthreads; an asm statement is invisible to that bookkeeping, so the waits are
-// the counted ones written in the loop - same helper as k_flash_attn.h fa_glds16).  M0 (the LDS base) is saved and restored.
-__device__ __forceinline__ void gm_glds16(const void* gsrc, unsigned lds_byte_addr) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(lds_byte_addr) : "memory");
-}
+// LDS-DMA pieces issued from inline asm (er_common.h er_glds16): the waits are the counted ones written in the loop.
 constexpr int X256_BM = 256, X256_BN = 256, X256_THREADS = 512;
 template <int HEPI = HEPI_PLAIN>
 __global__ __launch_bounds__(X256_THREADS) void gemm_hh256_kernel(GemmArgs g, int ntx) {
@@ -839,43 +677,36 @@ __global__ __launch_bounds__(X256_THREADS) void gemm_hh256_kernel(GemmArgs g, in
     const int tid = threadIdx.x, lane = tid & 63;
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wid >> 2, wn = wid & 3;
-    const int nwg = gridDim.x, xq = nwg >> 3, xr = nwg & 7, xcd = blockIdx.x & 7, within = blockIdx.x >> 3;
-    const int lin = (xcd < xr ? xcd * (xq + 1) : xr * (xq + 1) + (xcd - xr) * xq) + within;
-    const int ty = lin / ntx, tx = lin - ty * ntx;
-    const int m0 = ty * X256_BM, n0 = tx * X256_BN;
+    const TileYX tile = xcd_tile(blockIdx.x, gridDim.x, ntx);
+    const int m0 = tile.ty * X256_BM, n0 = tile.tx * X256_BN;
     const _Float16* A = reinterpret_cast<const _Float16*>(g.A);
     const _Float16* B = reinterpret_cast<const _Float16*>(g.B);
     const int nk = g.K / XBK;
 
-    const int lrow = lane >> 3, lslot = lane & 7;
+    const int lrow = lane >> 3;
     const _Float16* pa[NPI];
     const _Float16* pb[NPI];
 #pragma unroll
     for (int j = 0; j < NPI; ++j) {
         const int r = 8 * (wid * NPI + j) + lrow;
-        pa[j] = A + (long long)min(m0 + r, g.M - 1) * g.lda + ((lslot ^ ((r >> 1) & 7)) << 3);
-        pb[j] = B + (long long)min(n0 + r, g.N - 1) * g.ldb + ((lslot ^ ((r >> 1) & 7)) << 3);
+        pa[j] = A + gm_dma_src<_Float16>(m0, r, g.M - 1, g.lda, lane);
+        pb[j] = B + gm_dma_src<_Float16>(n0, r, g.N - 1, g.ldb, lane);
     }
     const unsigned lds0 = (unsigned)(unsigned long long)(er_lptr)lds;              // LDS byte address of the array
     auto issue = [&](int kt, int s) {
         const unsigned as = lds0 + (unsigned)(s * STAGE) * 2u, bs = as + X256_BM * XBK * 2u;
 #pragma unroll
-        for (int j = 0; j < NPI; ++j) gm_glds16(pa[j] + kt * XBK, as + 8u * (wid * NPI + j) * XBK * 2u);
+        for (int j = 0; j < NPI; ++j) er_glds16(pa[j] + kt * XBK, as + 8u * (wid * NPI + j) * XBK * 2u);
 #pragma unroll
-        for (int j = 0; j < NPI; ++j) gm_glds16(pb[j] + kt * XBK, bs + 8u * (wid * NPI + j) * XBK * 2u);
+        for (int j = 0; j < NPI; ++j) er_glds16(pb[j] + kt * XBK, bs + 8u * (wid * NPI + j) * XBK * 2u);
     };
     // (an L2 prefetch of the k-tile two steps ahead - one 4-byte LDS-DMA per lane and line into a dump area, left out of the counted
     // wait - measured SLOWER: 942 vs 990 TFLOP/s at 4096^3, 910 vs 1045 at 8192^3; profiles/r05_gemm_hh256_probe_with_l2_prefetch.log)
     constexpr int TM = 4, TN = 2;
     f32x16 acc[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    gm_zero(acc);
 
-    const int kh = lane >> 5, li = lane & 31, swz = (li >> 1) & 7;
+    const int kh = lane >> 5, li = lane & 31;
     if (nk > 0) issue(0, 0);
     asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
     for (int kt = 0; kt < nk; ++kt) {
@@ -887,21 +718,16 @@ __global__ __launch_bounds__(X256_THREADS) void gemm_hh256_kernel(GemmArgs g, in
         // (left to itself hipcc re-used one register set and put an lgkmcnt(0) in front of every group of four MFMAs)
         h16x8 av[2][TM], bv[2][TN];
         auto frags = [&](int ks, int buf) {
-            const int co = ((2 * ks + kh) ^ swz) << 3;
-#pragma unroll
-            for (int j = 0; j < TN; ++j) bv[buf][j] = *reinterpret_cast<const h16x8*>(bs + 32 * j * XBK + co);
-#pragma unroll
-            for (int i = 0; i < TM; ++i) av[buf][i] = *reinterpret_cast<const h16x8*>(as + 32 * i * XBK + co);
+            const int co = swz_frag_off<2, 8>(ks, kh, li);
+            gm_frags(bv[buf], bs, co);
+            gm_frags(av[buf], as, co);
         };
         frags(0, 0);
 #pragma unroll
         for (int ks = 0; ks < XBK / 16; ++ks) {
             if (ks + 1 < XBK / 16) frags(ks + 1, (ks + 1) & 1);
             __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int i = 0; i < TM; ++i)
-#pragma unroll
-                for (int j = 0; j < TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(av[ks & 1][i], bv[ks & 1][j], acc[i][j], 0, 0, 0);
+            gm_mfma_f16(acc, av[ks & 1], bv[ks & 1]);
             __builtin_amdgcn_sched_barrier(0);
         }
         // this wave's pieces of the next tile have landed, every fragment read of `cur` has returned (its MFMAs are issued) - then
@@ -950,27 +776,19 @@ __global__ __launch_bounds__(ER_WG) void gemm_f32d_mfma_kernel(GemmArgs g, int n
     const int tid = threadIdx.x, lane = tid & 63;
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wid >> 1, wn = wid & 1;
-    const int nwg = gridDim.x, xq = nwg >> 3, xr = nwg & 7, xcd = blockIdx.x & 7, within = blockIdx.x >> 3;
-    const int lin = (xcd < xr ? xcd * (xq + 1) : xr * (xq + 1) + (xcd - xr) * xq) + within;      // XCD-aware tile order (bijective)
-    const int ty = lin / ntx, tx = lin - ty * ntx;
-    const int m0 = ty * GBM, n0 = tx * GBN;
+    const TileYX tile = xcd_tile(blockIdx.x, gridDim.x, ntx);
+    const int m0 = tile.ty * GBM, n0 = tile.tx * GBN;
     const int nk = g.K / FBK;
     // (Measured and not kept, profiles/r04_gemm_f32d_ab.log: skipping the MFMAs of 32-row blocks that lie outside the matrix and running
     // the ragged last row tile first - the prefill's 2050 rows are 16 full 128-row tiles + 2 rows, i.e. 3.19 tiles per CU - made encode +
     // prefill SLOWER on the same box, 42.7 -> 44.9 ms.)
-    const int lrow = lane >> 3, lslot = lane & 7;
+    const int lrow = lane >> 3;
     const float* pa[NAI];
     const float* pb[NBI];
 #pragma unroll
-    for (int j = 0; j < NAI; ++j) {
-        const int r = 8 * (wid * NAI + j) + lrow;
-        pa[j] = g.A + (long long)min(m0 + r, g.M - 1) * g.lda + ((lslot ^ ((r >> 1) & 7)) << 2);
-    }
+    for (int j = 0; j < NAI; ++j) pa[j] = g.A + gm_dma_src<float>(m0, 8 * (wid * NAI + j) + lrow, g.M - 1, g.lda, lane);
 #pragma unroll
-    for (int j = 0; j < NBI; ++j) {
-        const int r = 8 * (wid * NBI + j) + lrow;
-        pb[j] = g.B + (long long)min(n0 + r, g.N - 1) * g.ldb + ((lslot ^ ((r >> 1) & 7)) << 2);
-    }
+    for (int j = 0; j < NBI; ++j) pb[j] = g.B + gm_dma_src<float>(n0, 8 * (wid * NBI + j) + lrow, g.N - 1, g.ldb, lane);
     auto issue = [&](int kt, int s) {
         float* as = lds + s * STAGE;
         float* bs = as + GBM * FBK;
@@ -982,16 +800,9 @@ __global__ __launch_bounds__(ER_WG) void gemm_f32d_mfma_kernel(GemmArgs g, int n
             __builtin_amdgcn_global_load_lds((er_gptr)(pb[j] + kt * FBK), (er_lptr)(bs + 8 * (wid * NBI + j) * FBK), 16, 0, 0);
     };
     f32x16 acc[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    gm_zero(acc);
     const int kh = lane >> 5, li = lane & 31;
-    // float index of (row, k) inside a tile image: row * 32 + ((k >> 2) ^ ((row >> 1) & 7)) * 4 + (k & 3); the rows this lane reads
-    // are wm * 32 TM + 32 i + li: (row >> 1) & 7 = (li >> 1) & 7 for every i (32 i and wm * 32 TM are multiples of 16 rows)
-    const int swz = (li >> 1) & 7;
+    // (the rows this lane reads are wm * 32 TM + 32 i + li: multiples of 16 rows apart, one swizzle key - that of row li - for every i)
     if (nk > 0) issue(0, 0);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
@@ -1005,17 +816,11 @@ __global__ __launch_bounds__(ER_WG) void gemm_f32d_mfma_kernel(GemmArgs g, int n
         // 38.3 -> 39.2 ms same box, profiles/r05_gemm_f32d_b128.log: twice the LDS bytes and two selects per operand beside 64-cycle MFMAs.)
 #pragma unroll
         for (int kk = 0; kk < FBK / 2; ++kk) {
-            const int k = 2 * kk + kh;                                          // kh is 0 / 1: the chunk index is uniform per lane half
-            const int off = (((k >> 2) ^ swz) << 2) + (k & 3);
+            const int off = swz_frag_off<4, 1>(kk, kh, li);                      // k = 2 kk + kh; kh is 0 / 1: the chunk index is uniform per lane half
             float av[TM], bv[TN];
-#pragma unroll
-            for (int i = 0; i < TM; ++i) av[i] = as[32 * i * FBK + off];
-#pragma unroll
-            for (int j = 0; j < TN; ++j) bv[j] = bs[32 * j * FBK + off];
-#pragma unroll
-            for (int i = 0; i < TM; ++i)
-#pragma unroll
-                for (int j = 0; j < TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[i], bv[j], acc[i][j], 0, 0, 0);
+            gm_frags(av, as, off);
+            gm_frags(bv, bs, off);
+            gm_mfma_f32(acc, av, bv);
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
@@ -1023,11 +828,20 @@ __global__ __launch_bounds__(ER_WG) void gemm_f32d_mfma_kernel(GemmArgs g, int n
     gemm_epilogue<TM, TN>(g, g.C, acc, m0, n0, wm, wn, kh, li);
 }
 
-inline int gemm_pick_tile(int M, int N, int batch);
 inline GemmArgs gemm_args_default() {
     GemmArgs g{};
     g.Z2 = 1;
     g.epi = GEPI_PLAIN;
+    return g;
+}
+// a plain Linear: C[M][ldc] = f(A[M][lda] . W[N][K]^T + bias) (+ resid[M][ldr]); A and W in the element type the kernel family reads
+// (fp32 or fp16), ldb = K.  Callers set what else they use (gate, c16, vt16, a_lo, another ldb) afterwards.
+inline GemmArgs gemm_args_linear(const void* A, int lda, const void* W, const float* bias, float* C, int ldc, int M, int N, int K, bool relu,
+                                 const float* resid, int ldr) {
+    GemmArgs g = gemm_args_default();
+    g.A = static_cast<const float*>(A); g.B = static_cast<const float*>(W); g.C = C; g.bias = bias; g.resid = resid;
+    g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = K; g.ldc = ldc; g.ldr = ldr;
+    g.relu = relu ? 1 : 0;
     return g;
 }
 
@@ -1047,23 +861,37 @@ inline int gemm_pick_tile(int M, int N, int batch) {
     if (wgs(64, 128) >= want) return 2;
     return 3;
 }
-#define ER_GEMM_DISPATCH(KERNEL_T, g, batch, st)                                                                       \
-    do {                                                                                                               \
-        const int tile_ = gemm_pick_tile((g).M, (g).N, (batch));                                                       \
-        const int bm_ = tile_ == 1 ? 128 : 64, bn_ = tile_ == 3 ? 64 : 128;                                            \
-        const dim3 grid_(((g).N + bn_ - 1) / bn_, ((g).M + bm_ - 1) / bm_, (batch));                                   \
-        if (tile_ == 1) hipLaunchKernelGGL((KERNEL_T(2, 2)), grid_, dim3(ER_WG), 0, (st), (g));                        \
-        else if (tile_ == 2) hipLaunchKernelGGL((KERNEL_T(1, 2)), grid_, dim3(ER_WG), 0, (st), (g));                   \
-        else hipLaunchKernelGGL((KERNEL_T(1, 1)), grid_, dim3(ER_WG), 0, (st), (g));                                   \
-    } while (0)
-#define ER_K_F16(TM, TN) gemm_f16_mfma_kernel<TM, TN>
-#define ER_K_F16S32(TM, TN) gemm_f16s_mfma_kernel<32, TM, TN>
-#define ER_K_F16S64(TM, TN) gemm_f16s_mfma_kernel<64, TM, TN>
-#define ER_K_F32(TM, TN) gemm_f32_mfma_kernel<TM, TN>
+
+// ---- the launch table of the 4-wave kernels: tile code 1 / 2 / 3 -> workgroup tile, a wave's TM x TN blocks of 32 x 32, the grid
+struct GemmTile { int bm, bn; };
+inline GemmTile gemm_tile_dims(int tile) { return {tile == 1 ? 128 : 64, tile == 3 ? 64 : 128}; }
+// f(TM, TN) with the two as integral constants (fa_dispatch is the precedent).  TILES: bit t set = tile code t is one the caller's
+// kernel has a form for - the others are not instantiated, and asking for one returns false.
+constexpr int GEMM_TILES_ALL = 0b1110;
+template <int TILES, typename F>
+inline bool gemm_tile_dispatch(int tile, F&& f) {
+    using one = std::integral_constant<int, 1>;
+    using two = std::integral_constant<int, 2>;
+    if constexpr ((TILES & 2) != 0) { if (tile == 1) { f(two{}, two{}); return true; } }
+    if constexpr ((TILES & 4) != 0) { if (tile == 2) { f(one{}, two{}); return true; } }
+    if constexpr ((TILES & 8) != 0) { if (tile == 3) { f(one{}, one{}); return true; } }
+    return false;
+}
+// kernel_of(TM, TN) = the instantiation for that tile.  GRID1D: the kernel takes (g, ntx) on a 1-D grid it walks in XCD order (xcd_tile);
+// otherwise (g) on a (column tile, row tile, batch) grid.
+template <bool GRID1D, int TILES = GEMM_TILES_ALL, typename F>
+inline hipError_t gemm_launch_tile(int tile, const GemmArgs& g, int batch, hipStream_t st, F&& kernel_of) {
+    const GemmTile d = gemm_tile_dims(tile);
+    const int ntx = (g.N + d.bn - 1) / d.bn, nty = (g.M + d.bm - 1) / d.bm;
+    const bool known = gemm_tile_dispatch<TILES>(tile, [&](auto tm, auto tn) {
+        if constexpr (GRID1D) hipLaunchKernelGGL(kernel_of(tm, tn), dim3(ntx * nty), dim3(ER_WG), 0, st, g, ntx);
+        else hipLaunchKernelGGL(kernel_of(tm, tn), dim3(ntx, nty, batch), dim3(ER_WG), 0, st, g);
+    });
+    return known ? hipGetLastError() : hipErrorInvalidValue;
+}
 
 inline hipError_t launch_gemm_f16(const GemmArgs& g, hipStream_t st) {   // NT only, K % 32 == 0, B = fp16 weights
-    ER_GEMM_DISPATCH(ER_K_F16, g, 1, st);
-    return hipGetLastError();
+    return gemm_launch_tile<false>(gemm_pick_tile(g.M, g.N, 1), g, 1, st, [](auto tm, auto tn) { return &gemm_f16_mfma_kernel<32, tm(), tn(), false>; });
 }
 
 // tile choice of the LDS-DMA kernel (see gemm_pick_tile): placeholder rule, tuned by scripts/probes/gemm_hh_probe.hip
@@ -1102,30 +930,31 @@ inline bool gemm_hh_use_stream(int M, int N, int K) {
     const long long t = (long long)((M + 127) / 128) * ((N + 127) / 128);
     return K >= 2048 && t >= 128 && t <= 512;
 }
+// the V^T form (GemmArgs::vt16) of the fp16 LDS-DMA kernels: whole 64-row runs per batch entry, whole heads, V columns from a multiple
+// of col_align on (the wave-uniform `nw >= vt_col0` branch of hh_epi_rows needs whole wave blocks), and the plain epilogue options off
+inline bool gemm_hh_vt_ok(const GemmArgs& g, int col_align) {
+    return !((g.M & 63) || (g.vt_rows & 63) || (g.vt_col0 & (col_align - 1)) || ((g.N - g.vt_col0) & 63) || (g.vt_ld & 7) || g.div != 0.f || g.relu ||
+             g.gate || g.resid);
+}
+template <int HEPI>
+inline hipError_t launch_gemm_hh256(const GemmArgs& g, hipStream_t st) {      // 256 x 256, 8 waves
+    const int ntx = (g.N + X256_BN - 1) / X256_BN;
+    hipLaunchKernelGGL((gemm_hh256_kernel<HEPI>), dim3(ntx * ((g.M + X256_BM - 1) / X256_BM)), dim3(X256_THREADS), 0, st, g, ntx);
+    return hipGetLastError();
+}
 inline hipError_t launch_gemm_hh(const GemmArgs& g, hipStream_t st, int force_tile = 0) {
     if (g.K % XBK != 0 || (g.lda & 7) || (g.ldb & 7)) return hipErrorInvalidValue;
     if (!force_tile && gemm_hh_use_stream(g.M, g.N, g.K)) return launch_gemm_hh_stream(g, st, false);
-    if (g.vt16 && ((g.M & 63) || (g.vt_rows & 63) || (g.vt_col0 & 127) || ((g.N - g.vt_col0) & 63) || (g.vt_ld & 7) || g.div != 0.f || g.relu ||
-                   g.gate || g.resid))
-        return hipErrorInvalidValue;
+    // V columns from a multiple of 128 on: the widest 4-wave tile (a 64-column wave block would do for every tile here - the streamed
+    // launcher asks for 64 with the same 64-column blocks; why this one asks for more is not recorded.  Each refuses what it always did.)
+    if (g.vt16 && !gemm_hh_vt_ok(g, 128)) return hipErrorInvalidValue;
     const int tile = force_tile ? force_tile : gemm_hh_pick_tile(g.M, g.N);
-    if (tile == 4) {          // 256 x 256, 8 waves (the V^T epilogue walks 64-row runs: fine, 64 | 256)
-        const int ntx4 = (g.N + X256_BN - 1) / X256_BN;
-        const dim3 grid4(ntx4 * ((g.M + X256_BM - 1) / X256_BM));
-        hipLaunchKernelGGL((gemm_hh256_kernel<HEPI_PLAIN>), grid4, dim3(X256_THREADS), 0, st, g, ntx4);
-        return hipGetLastError();
-    }
-    const int bm = tile == 1 ? 128 : 64, bn = tile == 3 ? 64 : 128;
-    const int ntx = (g.N + bn - 1) / bn, nty = (g.M + bm - 1) / bm;
-    const dim3 grid(ntx * nty);
-    if (tile == 1) hipLaunchKernelGGL((gemm_hh_mfma_kernel<2, 2>), grid, dim3(ER_WG), 0, st, g, ntx);
-    else if (tile == 2) hipLaunchKernelGGL((gemm_hh_mfma_kernel<1, 2>), grid, dim3(ER_WG), 0, st, g, ntx);
-    else hipLaunchKernelGGL((gemm_hh_mfma_kernel<1, 1>), grid, dim3(ER_WG), 0, st, g, ntx);
-    return hipGetLastError();
+    if (tile == 4) return launch_gemm_hh256<HEPI_PLAIN>(g, st);      // (the V^T epilogue walks 64-row runs: fine, 64 | 256)
+    return gemm_launch_tile<true>(tile, g, 1, st, [](auto tm, auto tn) { return &gemm_hh_mfma_kernel<tm(), tn()>; });
 }
 
 // x (fp32 rows) -> hi = fp16(x), lo = fp16(x - hi): the two A operands of the split form (exactly the split the register-staged
-// gemm_f16s_mfma_kernel performs on its way into LDS)
+// gemm_f16_mfma_kernel<SPLIT> performs on its way into LDS)
 // grid (ceil(cols / 4 / 256), rows' worth of blocks): a row per blockIdx.y (strided), a float4 per thread - no index division
 __global__ __launch_bounds__(ER_WG) void split_rows_f16_kernel(const float* x, _Float16* hi, _Float16* lo, long long rows, int cols, int ldx) {
     const int c = (blockIdx.x * ER_WG + threadIdx.x) * 4;
@@ -1146,14 +975,8 @@ inline dim3 split_rows_grid(long long rows, int cols) {
 inline hipError_t launch_gemm_hh_split(const GemmArgs& g, hipStream_t st) {
     if (g.K % XBK != 0 || (g.lda & 7) || (g.ldb & 7) || !g.a_lo) return hipErrorInvalidValue;
     const long long w2 = (long long)((g.M + 63) / 64) * ((g.N + 127) / 128);
-    if (w2 >= 256) {
-        const int ntx = (g.N + 127) / 128;
-        hipLaunchKernelGGL((gemm_hh_mfma_kernel<1, 2, HEPI_PLAIN, true>), dim3(ntx * ((g.M + 63) / 64)), dim3(ER_WG), 0, st, g, ntx);
-    } else {
-        const int ntx = (g.N + 63) / 64;
-        hipLaunchKernelGGL((gemm_hh_mfma_kernel<1, 1, HEPI_PLAIN, true>), dim3(ntx * ((g.M + 63) / 64)), dim3(ER_WG), 0, st, g, ntx);
-    }
-    return hipGetLastError();
+    // tile 2 (64 x 128) while it gives every CU a workgroup, else 3 (64 x 64); the split form has no 128-row tile
+    return gemm_launch_tile<true, 0b1100>(w2 >= 256 ? 2 : 3, g, 1, st, [](auto tm, auto tn) { return &gemm_hh_mfma_kernel<tm(), tn(), HEPI_PLAIN, true>; });
 }
 
 // builds the permuted GEGLU operands: wp[p][:] = w[gemm_hh_geglu_row(p, F)][:], bp[p] = b[gemm_hh_geglu_row(p, F)]   (p < 2F)
@@ -1170,26 +993,17 @@ __global__ __launch_bounds__(ER_WG) void geglu_permute_kernel(const _Float16* w,
 inline hipError_t launch_gemm_hh_geglu(const GemmArgs& g, hipStream_t st, int force_tile = 0) {
     if (g.K % XBK != 0 || (g.lda & 7) || (g.ldb & 7) || (g.N & 127) || !g.c16 || !g.bias) return hipErrorInvalidValue;
     if (force_tile == 4 && (g.N & 255)) return hipErrorInvalidValue;
-    if (force_tile == 4 || (force_tile == 0 && (g.N & 255) == 0 && gemm_hh_use_256(g.M, g.N))) {
-        const int ntx4 = g.N / 256;
-        const dim3 grid4(ntx4 * ((g.M + 255) / 256));
-        hipLaunchKernelGGL((gemm_hh256_kernel<HEPI_GEGLU>), grid4, dim3(X256_THREADS), 0, st, g, ntx4);
-        return hipGetLastError();
-    }
-    const int ntx = g.N / 128;
-    if (force_tile == 1 || (force_tile == 0 && (long long)((g.M + 127) / 128) * ntx >= 768)) {
-        hipLaunchKernelGGL((gemm_hh_mfma_kernel<2, 2, HEPI_GEGLU>), dim3(ntx * ((g.M + 127) / 128)), dim3(ER_WG), 0, st, g, ntx);
-    } else {
-        hipLaunchKernelGGL((gemm_hh_mfma_kernel<1, 2, HEPI_GEGLU>), dim3(ntx * ((g.M + 63) / 64)), dim3(ER_WG), 0, st, g, ntx);
-    }
-    return hipGetLastError();
+    if (force_tile == 4 || (force_tile == 0 && (g.N & 255) == 0 && gemm_hh_use_256(g.M, g.N))) return launch_gemm_hh256<HEPI_GEGLU>(g, st);
+    // tile 1 (128 x 128) from three workgroups per CU on, else 2 (64 x 128); the pairing needs 128-column tiles: no tile 3
+    const bool big = force_tile == 1 || (force_tile == 0 && (long long)((g.M + 127) / 128) * (g.N / 128) >= 768);
+    return gemm_launch_tile<true, 0b0110>(big ? 1 : 2, g, 1, st, [](auto tm, auto tn) { return &gemm_hh_mfma_kernel<tm(), tn(), HEPI_GEGLU>; });
 }
 
 inline hipError_t launch_gemm_f16s(const GemmArgs& g, hipStream_t st) {  // NT only, K % 32 == 0, B = fp16 weights, A split hi/lo
     static const bool bk64 = [] { const char* v = getenv("ER_F16S_BK"); return v && atoi(v) == 64; }();
-    if (bk64 && g.K % 64 == 0) ER_GEMM_DISPATCH(ER_K_F16S64, g, 1, st);
-    else ER_GEMM_DISPATCH(ER_K_F16S32, g, 1, st);
-    return hipGetLastError();
+    const int tile = gemm_pick_tile(g.M, g.N, 1);
+    if (bk64 && g.K % 64 == 0) return gemm_launch_tile<false>(tile, g, 1, st, [](auto tm, auto tn) { return &gemm_f16_mfma_kernel<64, tm(), tn(), true>; });
+    return gemm_launch_tile<false>(tile, g, 1, st, [](auto tm, auto tn) { return &gemm_f16_mfma_kernel<32, tm(), tn(), true>; });
 }
 
 // the plain NT products (no batch, no causal bound, K-major B) with K % 32 == 0 and 16-byte aligned rows take the LDS-DMA kernel;
@@ -1209,15 +1023,9 @@ inline hipError_t launch_gemm(const GemmArgs& g, int batch, hipStream_t st) {
         const long long min128 = 256LL * (mv ? atoi(mv) : 4);
         int tile = gemm_pick_tile(g.M, g.N, 1);
         if (!getenv("ER_GEMM_TILE") && tile == 1 && (long long)((g.M + 127) / 128) * ((g.N + 127) / 128) < min128) tile = 2;
-        const int bm = tile == 1 ? 128 : 64, bn = tile == 3 ? 64 : 128;
-        const int ntx = (g.N + bn - 1) / bn, nty = (g.M + bm - 1) / bm;
-        if (tile == 1) hipLaunchKernelGGL((gemm_f32d_mfma_kernel<2, 2>), dim3(ntx * nty), dim3(ER_WG), 0, st, g, ntx);
-        else if (tile == 2) hipLaunchKernelGGL((gemm_f32d_mfma_kernel<1, 2>), dim3(ntx * nty), dim3(ER_WG), 0, st, g, ntx);
-        else hipLaunchKernelGGL((gemm_f32d_mfma_kernel<1, 1>), dim3(ntx * nty), dim3(ER_WG), 0, st, g, ntx);
-        return hipGetLastError();
+        return gemm_launch_tile<true>(tile, g, 1, st, [](auto tm, auto tn) { return &gemm_f32d_mfma_kernel<tm(), tn()>; });
     }
-    ER_GEMM_DISPATCH(ER_K_F32, g, batch, st);
-    return hipGetLastError();
+    return gemm_launch_tile<false>(gemm_pick_tile(g.M, g.N, batch), g, batch, st, [](auto tm, auto tn) { return &gemm_f32_mfma_kernel<tm(), tn()>; });
 }
 
 }  // namespace er

@@ -38,18 +38,7 @@ namespace er {
 constexpr int GS_BM = 128, GS_BN = 128, GS_THREADS = 512;
 constexpr int GS_STAGE_B = (GS_BM + GS_BN) * XBK * 2;        // bytes per ring stage: 128 A rows, then 128 B rows, 128 bytes each (32 KB)
 
-// Tile order inside the stream: bands of GS_GH tile rows, walked column by column.  The tiles an XCD's 32 workgroups hold at the same
-// time are 32 consecutive indices = a GS_GH x 8 block: per k-step the XCD's L2 fetches 4 A slices + 8 B slices (192 KB) for the 1 MB its
-// CUs pull, instead of 1 + 32 (528 KB) with row-major order - the row-major first version of this kernel ran 4096^3 at 575 TFLOP/s,
-// fabric-bound (profiles/r06_gemm_stream_probe_v1.log, r06_dma_rate_probe.log: a CU pulls 130 GB/s from L2 but 24 GB/s from HBM).
-constexpr int GS_GH = 4;
-__device__ __forceinline__ void gs_tile_coords(int lin, int ntx, int nty, int& ty, int& tx) {
-    const int band = lin / (GS_GH * ntx), r0 = band * GS_GH;
-    const int gh = min(GS_GH, nty - r0), in = lin - band * GS_GH * ntx;
-    tx = in / gh;
-    ty = r0 + in - tx * gh;
-}
-
+// (tile order inside the stream and the dealing of tiles to workgroups: er_gemm_map.h gs_tile_coords / gs_deal)
 // (a loader wave issues EIGHT LDS-DMA pieces per k-tile - 32 pieces of 8 rows over 4 loaders: the vmcnt counts below are multiples of 8)
 template <int NT>
 __device__ __forceinline__ void gs_wait_tiles(int n) {      // at most n (<= NT) of this wave's k-tiles may still be in flight
@@ -96,13 +85,9 @@ __global__ __launch_bounds__(GS_THREADS) void gemm_hh_stream_kernel(GemmArgs g, 
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int nk = g.K / XBK, nty = ntiles / ntx;
     // the tiles of this workgroup: each XCD owns a contiguous run of tiles (neighbours share their A row panel in that XCD's L2),
-    // the run is dealt round-robin to the XCD's workgroups (block b runs on XCD b % 8: a speed assumption only)
-    const int G = gridDim.x, xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-    const int wx = (G >> 3) + (xcd < (G & 7) ? 1 : 0);
-    const int tq = ntiles >> 3, tr = ntiles & 7;
-    const int nx = tq + (xcd < tr ? 1 : 0);
-    const int base = xcd < tr ? xcd * (tq + 1) : tr * (tq + 1) + (xcd - tr) * tq;
-    const int mine = slot < nx ? (nx - slot + wx - 1) / wx : 0;                    // tiles base + slot + j wx, j < mine
+    // the run is dealt round-robin to the XCD's workgroups
+    const GsDeal deal = gs_deal(blockIdx.x, gridDim.x, ntiles);
+    const int first = deal.base + deal.slot, wx = deal.wx, mine = deal.mine;      // tiles first + j wx, j < mine
     const int total = mine * nk;                                                   // k-tiles in this workgroup's stream
     if (total == 0) return;
     // EPILOGUE of a tile, all eight waves: the 64 x 64 block of matrix wave b goes through LDS in two halves of 32 rows - b stages a
@@ -133,10 +118,10 @@ __global__ __launch_bounds__(GS_THREADS) void gemm_hh_stream_kernel(GemmArgs g, 
         unsigned va[4], vb[4];
         auto set_tile = [&](int j) {
             int ty, tx;
-            gs_tile_coords(base + slot + j * wx, ntx, nty, ty, tx);
+            gs_tile_coords(first + j * wx, ntx, nty, ty, tx);
 #pragma unroll
             for (int jj = 0; jj < 4; ++jj) {
-                const int r = 8 * (lw * 4 + jj) + lrow, sw = (lslot ^ ((r >> 1) & 7)) << 4;
+                const int r = 8 * (lw * 4 + jj) + lrow, sw = swz_chunk_off<1>(r, lslot);
                 va[jj] = (unsigned)min(ty * GS_BM + r, g.M - 1) * (unsigned)(g.lda * 2) + sw + 3072u - 1024u * jj;
                 vb[jj] = (unsigned)min(tx * GS_BN + r, g.N - 1) * (unsigned)(g.ldb * 2) + sw + 3072u - 1024u * jj;
             }
@@ -172,7 +157,7 @@ __global__ __launch_bounds__(GS_THREADS) void gemm_hh_stream_kernel(GemmArgs g, 
         int u = 0, est = 0;                                                         // est: ring stage of k-tile u
         for (int jt = 0; jt < mine; ++jt) {
             int ty, tx;
-            gs_tile_coords(base + slot + jt * wx, ntx, nty, ty, tx);
+            gs_tile_coords(first + jt * wx, ntx, nty, ty, tx);
             const int mwb = ty * GS_BM + (lw >> 1) * 64, nwb = tx * GS_BN + (lw & 1) * 64;     // the block of matrix wave lw
             HhEpiPre pre[2];
             bool use_pre = false;
@@ -216,7 +201,7 @@ __global__ __launch_bounds__(GS_THREADS) void gemm_hh_stream_kernel(GemmArgs g, 
 
     // ---------------- matrix waves ----------------
     const int wm = wid >> 1, wn = wid & 1;
-    const int kh = lane >> 5, li = lane & 31, swz = (li >> 1) & 7;
+    const int kh = lane >> 5, li = lane & 31;
     const char* a_row = lds + (wm * 64 + li) * (XBK * 2);                           // + 32 i rows
     const char* b_row = lds + GS_BM * XBK * 2 + (wn * 64 + li) * (XBK * 2);
     h16x8 av[4][2], bv[4][2];                                                       // four fragment sets: sub-step ks uses set ks
@@ -225,11 +210,9 @@ __global__ __launch_bounds__(GS_THREADS) void gemm_hh_stream_kernel(GemmArgs g, 
     asm volatile("s_barrier" ::: "memory");                                         // k-tiles 0 and 1 are in LDS
 #define GS_FRAGS(STAGE, KS, SET)                                                                                        \
     do {                                                                                                                \
-        const int co_ = (((2 * (KS) + kh) ^ swz) << 4) + (STAGE) * GS_STAGE_B;                                          \
-        bv[SET][0] = *reinterpret_cast<const h16x8*>(b_row + co_);                                                      \
-        bv[SET][1] = *reinterpret_cast<const h16x8*>(b_row + 32 * XBK * 2 + co_);                                       \
-        av[SET][0] = *reinterpret_cast<const h16x8*>(a_row + co_);                                                      \
-        av[SET][1] = *reinterpret_cast<const h16x8*>(a_row + 32 * XBK * 2 + co_);                                       \
+        const int co_ = swz_frag_off<1, 16>(KS, kh, li) + (STAGE) * GS_STAGE_B;                                         \
+        gm_frags(bv[SET], b_row, co_);                                                                                  \
+        gm_frags(av[SET], a_row, co_);                                                                                  \
     } while (0)
     GS_FRAGS(0, 0, 0);
     GS_FRAGS(0, 1, 1);
@@ -239,14 +222,9 @@ __global__ __launch_bounds__(GS_THREADS) void gemm_hh_stream_kernel(GemmArgs g, 
 #endif
     for (int jt = 0; jt < mine; ++jt) {
         int ty, tx;
-        gs_tile_coords(base + slot + jt * wx, ntx, nty, ty, tx);
+        gs_tile_coords(first + jt * wx, ntx, nty, ty, tx);
         const int mw = ty * GS_BM + wm * 64, nw = tx * GS_BN + wn * 64;
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+        gm_zero(acc);
         // plain epilogue: this wave's global operands (bias, the two possible gate rows, the residual of its 2 x 4 row passes) are requested
         // NOW and arrive under the k-loop.  Wave-uniform condition: the wave's 64 columns lie inside N and every row-wise access is a
         // 16-byte one (else hh_epi_rows loads by itself); lane map and conditions of hh_epi_rows<1, 2>.
@@ -277,6 +255,8 @@ __global__ __launch_bounds__(GS_THREADS) void gemm_hh_stream_kernel(GemmArgs g, 
                 if (ks == 0) acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bv[0][0] + bv[1][1] + bv[2][0] + bv[3][1], av[0][0] + av[1][1] + av[2][0] + av[3][1], acc[0][0], 0, 0, 0);
                 if (ks < 0)
 #endif
+                // (written out: through gm_mfma_f16 - the same sixteen MFMAs in the same order - hipcc grouped the GEGLU form's epilogue loads
+                // differently, two compiler-placed vmcnt waits fewer; the kernel keeps the form its timeline was measured on)
 #pragma unroll
                 for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -341,8 +321,9 @@ inline int gs_num_cus() {
 inline hipError_t launch_gemm_hh_stream(const GemmArgs& g, hipStream_t st, bool geglu) {
     if (g.K % XBK != 0 || g.K <= 0 || (g.lda & 7) || (g.ldb & 7)) return hipErrorInvalidValue;
     if (geglu && ((g.N & 127) || !g.c16 || !g.bias)) return hipErrorInvalidValue;
-    if (g.vt16 && ((g.M & 63) || (g.vt_rows & 63) || (g.vt_col0 & 63) || ((g.N - g.vt_col0) & 63) || (g.vt_ld & 7) || g.div != 0.f || g.relu || g.gate || g.resid))
-        return hipErrorInvalidValue;
+    // V columns from a multiple of 64 on - the 64-column block of a matrix wave, all the wave-uniform V^T branch of hh_epi_rows needs.
+    // (launch_gemm_hh asks for 128 although its wave blocks are no wider; why is not recorded.  Each refuses what it always did.)
+    if (g.vt16 && !gemm_hh_vt_ok(g, 64)) return hipErrorInvalidValue;
     const int ntx = (g.N + GS_BN - 1) / GS_BN, ntiles = ntx * ((g.M + GS_BM - 1) / GS_BM);
     const int grid = ntiles < gs_num_cus() ? ntiles : gs_num_cus();
     if (geglu) hipLaunchKernelGGL((gemm_hh_stream_kernel<5, HEPI_GEGLU>), dim3(grid), dim3(GS_THREADS), 0, st, g, ntx, ntiles);

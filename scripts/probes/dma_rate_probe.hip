@@ -2,7 +2,7 @@
 // four loader waves - the bound of its k-step.  This probe prices the delivery path by itself: W loader waves per workgroup (one
 // workgroup per CU, 160 KB of LDS), each moving 1 KB pieces (64 lanes x 16 B, eight 128-byte rows) of a tile stream into a ring, with
 // two k-tiles' worth of pieces in flight per wave, in four forms:
-//   0  global_load_lds_dwordx4, 64-bit per-lane address, M0 saved / set / restored around every piece (gm_glds16 of k_gemm.h)
+//   0  global_load_lds_dwordx4, 64-bit per-lane address, M0 saved / set / restored around every piece (er_glds16 of er_common.h)
 //   1  the same, M0 written once per FOUR pieces: the instruction offset (+1024 j) moves the LDS destination and the global address
 //      alike, so the per-lane pointer of piece j is pre-decremented by 1024 j
 //   2  global_load_dwordx4 into registers, then ds_write_b128 (register staging by the loader wave)

@@ -8,8 +8,8 @@ against float64 torch, and form against form where the kernels promise equal bit
 Forms (17) - every case runs on every form:
   f32r-t1 / t2 / t3     gemm_f32_mfma_kernel   (ER_GEMM_F32_DMA=0, ER_GEMM_TILE=1 / 2 / 3)       scalar epilogue (gemm_epilogue), 32-row blocks
   f32d-t1 / t2 / t3     gemm_f32d_mfma_kernel  (ER_GEMM_F32_DMA=1, ER_GEMM_TILE)                  the same epilogue
-  f16-t1 / t2 / t3      gemm_f16_mfma_kernel   (ER_GEMM_TILE)                                     the same epilogue
-  f16s-t1 / t2 / t3     gemm_f16s_mfma_kernel  (ER_GEMM_TILE)                                     the same epilogue
+  f16-t1 / t2 / t3      gemm_f16_mfma_kernel   (plain form, ER_GEMM_TILE)                         the same epilogue
+  f16s-t1 / t2 / t3     gemm_f16_mfma_kernel   (split form, ER_GEMM_TILE)                         the same epilogue
   hh-t1, hh-t4          gemm_hh_mfma_kernel<2, 2> / gemm_hh256_kernel (ER_GEMM_STREAM=0)          row-wise epilogue (hh_epi_rows), 64-row waves:
                                                                                                   gate pair, residual loaded in the pass loop
   hh-t2, hh-t3          gemm_hh_mfma_kernel<1, 2> / <1, 1>                                        hh_epi_rows, 32-row waves: gate pair, the
