@@ -28,6 +28,28 @@ constexpr MlpSlot mlp_slot(int epl, int k) {
     return MlpSlot{s * 64 + q % 64, (q / 64) * epl + e};
 }
 
+// ---- Which fc2 rows the fused kernel requests.  The chain is cut into two halves of 12 places (waves 0-5 and 6-11 of fc1); per half
+// the live places (f != 0) are bit i of a 12-bit mask, i = place - 12 * half.  The kernel requests rows by SLOT: slot u holds the u-th
+// live place in ascending order, the slots behind the live ones are pads (zero row, f = 0) up to the next multiple of 4, and the slots
+// behind those are not requested at all.  Running the chain over the slots leaves out only steps fmaf(+0, +0, s), in the chain's order.
+constexpr int MLP_HALF = MLP_CHAIN / 2;                 // 12 places per half
+constexpr int MLP_LIVE_BLOCK = 4;                       // rows are requested in blocks of 4 slots
+constexpr unsigned MLP_HALF_MASK = (1u << MLP_HALF) - 1u;
+constexpr int mlp_live_count(unsigned mask) { return __builtin_popcount(mask & MLP_HALF_MASK); }
+// slots to request for a half: the live count rounded up to whole blocks; 0 for the empty mask
+constexpr int mlp_live_slots(unsigned mask) { return (mlp_live_count(mask) + MLP_LIVE_BLOCK - 1) / MLP_LIVE_BLOCK * MLP_LIVE_BLOCK; }
+// the mask behind its lowest live place (the kernel walks the slots by peeling)
+constexpr unsigned mlp_live_peel(unsigned mask) { return mask & (mask - 1u); }
+// the lane the next slot of a (peeled) mask reads: its lowest live place, or lane 12 for a pad - the column waves keep place i's f and
+// row in lane i, and f = 0 and the zero row in the lanes from 12 on
+constexpr int MLP_PAD_LANE = MLP_HALF;
+constexpr int mlp_live_lane(unsigned mask) { return __builtin_ctz((mask & MLP_HALF_MASK) | (1u << MLP_PAD_LANE)); }
+// the place (0 .. 11) slot u holds, or -1 for a pad
+constexpr int mlp_live_place(unsigned mask, int u) {
+    for (int i = 0; i < u; ++i) mask = mlp_live_peel(mask);
+    return mlp_live_lane(mask) < MLP_PAD_LANE ? mlp_live_lane(mask) : -1;
+}
+
 // ---- The finish launch (mlp_finish_kernel<NC>; launched with NC = 32, the map holds for 8 and 16 as well): NC consecutive outputs per
 // workgroup, wave s = slice s.  The wave reads the NC * 4 bytes of each of its 64 chain vectors as 16-byte pieces: g = NC / 4 adjacent
 // lanes share one chain, so one wave-load covers 64 / g chains with g * 16 contiguous bytes each (NC = 32: eight whole 128-byte
