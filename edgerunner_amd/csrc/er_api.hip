@@ -107,6 +107,16 @@ static GenState gen_state_carve(int* sb, size_t b) {
     return s;
 }
 
+// What the sampling heads read of a call: its decode parameters (top_k as the call resolved it, max_new as the caller counts
+// steps), the model's token ids and the seed as the two Philox key words.
+static DecodeParamsDev decode_params_dev(const er_decode_params& p, int top_k, int max_new, int eos, int pad, int vocab) {
+    DecodeParamsDev dp{};
+    dp.mode = p.mode; dp.top_k = top_k; dp.grammar = p.grammar; dp.max_new = max_new; dp.min_new = p.min_new_tokens;
+    dp.eos = eos; dp.pad = pad; dp.vocab = vocab;
+    dp.seed_lo = (unsigned int)(p.seed & 0xffffffffu); dp.seed_hi = (unsigned int)(p.seed >> 32);
+    return dp;
+}
+
 // K-range partials per row that a 4-wave split-K launch leaves to a LATER launch: out_proj 1536 / 384, fc2 6144 / 384 (4 is also the most
 // a 16-wave launch leaves to its own finish: 6144 / 1536).  KvMem::skpart is sized from them; the launches that write and read pass them.
 constexpr int SK_SLICES_OUTPROJ = 4, SK_SLICES_FC2 = 16;
@@ -1317,10 +1327,7 @@ extern "C" int er_decode(er_ctx* c, const er_decode_params* p, int64_t* out_ids,
     int top_k = 0;
     ERCHK(head_setup(c, p, &top_k));
 
-    DecodeParamsDev dp{};
-    dp.mode = p->mode; dp.top_k = top_k; dp.grammar = p->grammar; dp.max_new = T; dp.min_new = p->min_new_tokens;
-    dp.eos = c->cfg.eos_token_id; dp.pad = c->cfg.pad_token_id; dp.vocab = c->cfg.vocab_size;
-    dp.seed_lo = (unsigned int)(p->seed & 0xffffffffu); dp.seed_hi = (unsigned int)(p->seed >> 32);
+    const DecodeParamsDev dp = decode_params_dev(*p, top_k, T, c->cfg.eos_token_id, c->cfg.pad_token_id, c->cfg.vocab_size);
     HIPCHK(hipMemcpy(c->kv->d_params.p, &dp, sizeof(dp), hipMemcpyHostToDevice));
     hipLaunchKernelGGL(reset_gen_kernel, dim3((B + 63) / 64), dim3(64), 0, st, c->kv->st, B);
     HIPRET(hipGetLastError());
@@ -1408,7 +1415,7 @@ extern "C" int er_set_row_streams(er_ctx* c, const uint32_t* ids, int n) {
 }
 
 // ------------------------------------------------------------------------------------ queue mode (continuous batching)
-// A free row: budget 0 (sample_head_kernel returns before it reads or writes anything of the row) and position 0 (its forward writes
+// A free row: budget 0 (the sampling heads return before they write anything of the row) and position 0 (its forward writes
 // K/V slot 0 of its own slice and attends that one key).  Nothing of it grows, and nothing reads what its forward leaves.
 __global__ void queue_park_kernel(GenState st, int* budget, int row0, int n) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1471,10 +1478,7 @@ extern "C" int er_queue_begin(er_ctx* c, const er_decode_params* p, int check_ev
     int top_k = 0;
     ERCHK(head_setup(c, p, &top_k));
 
-    DecodeParamsDev dp{};
-    dp.mode = p->mode; dp.top_k = top_k; dp.grammar = p->grammar; dp.max_new = p->max_new_tokens; dp.min_new = p->min_new_tokens;
-    dp.eos = c->cfg.eos_token_id; dp.pad = c->cfg.pad_token_id; dp.vocab = c->cfg.vocab_size;
-    dp.seed_lo = (unsigned int)(p->seed & 0xffffffffu); dp.seed_hi = (unsigned int)(p->seed >> 32);
+    const DecodeParamsDev dp = decode_params_dev(*p, top_k, p->max_new_tokens, c->cfg.eos_token_id, c->cfg.pad_token_id, c->cfg.vocab_size);
     HIPCHK(hipMemcpy(c->kv->d_params.p, &dp, sizeof(dp), hipMemcpyHostToDevice));
     hipLaunchKernelGGL(queue_park_kernel, dim3((B + 63) / 64), dim3(64), 0, st, c->kv->st, c->kv->d_row_budget.p, 0, B);
     HIPRET(hipGetLastError());
@@ -1636,9 +1640,9 @@ static int profile_impl(er_ctx* c, int repeats, int use_graph, float* avg_us, do
     HIPCHK(hipMemcpy(save_state.data(), c->kv->state_block.p, save_state.size() * sizeof(int), hipMemcpyDeviceToHost));
     std::vector<int> head_state = save_state;          // the head sweep runs at step 0 so it writes dummy_ids[b][0]
     for (int b = 0; b < B; ++b) gen_state_carve(head_state.data(), B).ngen[b] = 0;
-    DecodeParamsDev dp{};
-    dp.mode = 0; dp.top_k = 10; dp.grammar = 2; dp.max_new = 1 << 30; dp.min_new = 0;
-    dp.eos = g.eos_token_id; dp.pad = g.pad_token_id; dp.vocab = V;
+    er_decode_params greedy{};                         // greedy under the LR_ABSCO grammar, no budget in the way, seed 0
+    greedy.mode = 0; greedy.grammar = 2;
+    const DecodeParamsDev dp = decode_params_dev(greedy, 10, 1 << 30, g.eos_token_id, g.pad_token_id, V);
     HIPCHK(hipMemcpy(c->kv->d_params.p, &dp, sizeof(dp), hipMemcpyHostToDevice));
     c->kv->head_ctl = c->kv->row_class = false;   // the plan's own kinds 4, 5 and 7 here; er_decode / er_queue_begin choose again
     DevBuf<long long> dummy;             // freed on every return path; a failing one frees behind hipFree's own device synchronisation
@@ -2238,68 +2242,28 @@ extern "C" int er_k_score_rows(const float* logits, const int32_t* labels, int b
     return ER_OK;
 }
 
-extern "C" int er_k_sample_head(const float* logits, const er_decode_params* p, int vocab, int eos, int pad, int B, int step,
-                                const int32_t* last_tok, const int32_t* counter, const int32_t* unfinished, int32_t* next_tok,
-                                int32_t* counter_out, int32_t* unfinished_out, void* stream) {
-    hipStream_t st = (hipStream_t)stream;
-    const size_t b = (size_t)B;
+// One step of a sampling head on row state the caller gives: what er_k_sample_head and er_k_sample_head_ctl share.  `who` names the
+// entry in the error text; ctl null: sample_head_kernel, else sample_head_ctl_kernel with the controls ctl->s, leaving its log-probs
+// and kept counts of this step in ctl's buffers for the entry to copy.  Returns after the stream has drained.
+struct HeadUnitCtl {
+    const er_sampling* s;
+    DevBuf<HeadCtlDev> dev;
+    DevBuf<float> lpm, lpp;            // [B][step + 1]
+    DevBuf<int> nk;                    // [B]
+};
+static int head_unit_step(const char* who, const float* logits, const er_decode_params* p, int vocab, int eos, int pad, int B, int step,
+                          const int32_t* last_tok, const int32_t* counter, const int32_t* unfinished, int32_t* next_tok,
+                          int32_t* counter_out, int32_t* unfinished_out, HeadUnitCtl* ctl, hipStream_t st) {
+    if (!logits || !p || B <= 0 || step < 0 || vocab <= 0 || vocab > ER_HEAD_MAX_VOCAB || !last_tok || !counter || !unfinished ||
+        !next_tok || !counter_out || !unfinished_out)
+        return fail(ER_ERR_INVALID, "%s: bad argument", who);
+    const size_t b = (size_t)B, ld = (size_t)step + 1;
     DevBuf<int> sb;
     DevBuf<DecodeParamsDev> dpd;
     DevBuf<long long> ids;
     ERCHK(sb.ensure(gen_state_ints(b)));
     ERCHK(dpd.ensure(1));
-    ERCHK(ids.ensure(b * (size_t)(step + 1)));
-    std::vector<int> h(gen_state_ints(b), 0);
-    const GenState hs = gen_state_carve(h.data(), b);      // the same state on the host
-    for (size_t i = 0; i < b; ++i) {
-        hs.tok[i] = last_tok[i]; hs.counter[i] = counter[i]; hs.ngen[i] = step;
-        hs.unfinished[i] = unfinished[i]; hs.eos_step[i] = -1;
-    }
-    *hs.n_unfinished = B;
-    HIPCHK(hipMemcpy(sb.p, h.data(), h.size() * sizeof(int), hipMemcpyHostToDevice));
-    const GenState s = gen_state_carve(sb.p, b);
-    DecodeParamsDev dp{};
-    dp.mode = p->mode; dp.top_k = p->top_k; dp.grammar = p->grammar; dp.max_new = step + 1; dp.min_new = p->min_new_tokens;
-    dp.eos = eos; dp.pad = pad; dp.vocab = vocab;
-    dp.seed_lo = (unsigned int)(p->seed & 0xffffffffu); dp.seed_hi = (unsigned int)(p->seed >> 32);
-    HIPCHK(hipMemcpy(dpd.p, &dp, sizeof(dp), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(sample_head_kernel, dim3(B), dim3(ER_WG), sample_head_lds(vocab), st, logits, dpd.p, s, ids.p, step + 1);
-    hipError_t e = hipGetLastError();
-    hipError_t e2 = hipStreamSynchronize(st);
-    if (e == hipSuccess && e2 == hipSuccess) {
-        hipMemcpy(h.data(), sb.p, h.size() * sizeof(int), hipMemcpyDeviceToHost);
-        for (size_t i = 0; i < b; ++i) { next_tok[i] = hs.tok[i]; counter_out[i] = hs.counter[i]; unfinished_out[i] = hs.unfinished[i]; }
-    }
-    HIPRET(e);
-    HIPRET(e2);
-    return ER_OK;
-}
-
-extern "C" int er_k_sample_head_ctl(const float* logits, const er_decode_params* p, const er_sampling* s, int vocab, int eos, int pad,
-                                    int B, int step, const int32_t* last_tok, const int32_t* counter, const int32_t* unfinished,
-                                    int32_t* next_tok, int32_t* counter_out, int32_t* unfinished_out, float* lp_model, float* lp_policy,
-                                    int32_t* n_kept, void* stream) {
-    if (!logits || !p || B <= 0 || step < 0 || vocab <= 0 || vocab > ER_HEAD_MAX_VOCAB || !last_tok || !counter || !unfinished ||
-        !next_tok || !counter_out || !unfinished_out)
-        return fail(ER_ERR_INVALID, "er_k_sample_head_ctl: bad argument");
-    const er_sampling dflt{1.0f, 1.0f, 0, 0, 0};
-    if (!s) s = &dflt;
-    if (!(s->temperature > 0.0f) || !(s->temperature <= 3.402823466e38f) || !(s->top_p > 0.0f) || !(s->top_p <= 1.0f) || (s->top_k_set && s->top_k < 0))
-        return fail(ER_ERR_INVALID, "er_k_sample_head_ctl: temperature %g / top_p %g / top_k %d out of range", (double)s->temperature, (double)s->top_p, s->top_k);
-    hipStream_t st = (hipStream_t)stream;
-    const size_t b = (size_t)B;
-    DevBuf<int> sb, nk;
-    DevBuf<DecodeParamsDev> dpd;
-    DevBuf<HeadCtlDev> ctl;
-    DevBuf<long long> ids;
-    DevBuf<float> lpm, lpp;
-    ERCHK(sb.ensure(gen_state_ints(b)));
-    ERCHK(nk.ensure(b));
-    ERCHK(dpd.ensure(1));
-    ERCHK(ctl.ensure(1));
-    ERCHK(ids.ensure(b * (size_t)(step + 1)));
-    ERCHK(lpm.ensure(b * (size_t)(step + 1)));
-    ERCHK(lpp.ensure(b * (size_t)(step + 1)));
+    ERCHK(ids.ensure(b * ld));
     std::vector<int> h(gen_state_ints(b), 0);
     const GenState hs = gen_state_carve(h.data(), b);      // the same state on the host
     for (size_t i = 0; i < b; ++i) {
@@ -2309,27 +2273,54 @@ extern "C" int er_k_sample_head_ctl(const float* logits, const er_decode_params*
     *hs.n_unfinished = B;
     HIPCHK(hipMemcpy(sb.p, h.data(), h.size() * sizeof(int), hipMemcpyHostToDevice));
     const GenState gs = gen_state_carve(sb.p, b);
-    DecodeParamsDev dp{};
-    dp.mode = p->mode; dp.top_k = s->top_k_set ? s->top_k : p->top_k; dp.grammar = p->grammar; dp.max_new = step + 1; dp.min_new = p->min_new_tokens;
-    dp.eos = eos; dp.pad = pad; dp.vocab = vocab;
-    dp.seed_lo = (unsigned int)(p->seed & 0xffffffffu); dp.seed_hi = (unsigned int)(p->seed >> 32);
+    const DecodeParamsDev dp = decode_params_dev(*p, ctl && ctl->s->top_k_set ? ctl->s->top_k : p->top_k, step + 1, eos, pad, vocab);
     HIPCHK(hipMemcpy(dpd.p, &dp, sizeof(dp), hipMemcpyHostToDevice));
-    const HeadCtlDev hc{s->temperature, s->top_p};
-    HIPCHK(hipMemcpy(ctl.p, &hc, sizeof(hc), hipMemcpyHostToDevice));
-    const HeadCtlOut lp{lpm.p, lpp.p, nk.p, step + 1};
-    hipLaunchKernelGGL(sample_head_ctl_kernel, dim3(B), dim3(ER_WG), sample_head_lds(vocab), st, logits, dpd.p, ctl.p, gs, ids.p, step + 1, lp);
-    hipError_t e = hipGetLastError();
-    hipError_t e2 = hipStreamSynchronize(st);
-    if (e == hipSuccess && e2 == hipSuccess) {
-        hipMemcpy(h.data(), sb.p, h.size() * sizeof(int), hipMemcpyDeviceToHost);
-        for (size_t i = 0; i < b; ++i) { next_tok[i] = hs.tok[i]; counter_out[i] = hs.counter[i]; unfinished_out[i] = hs.unfinished[i]; }
-        const size_t pitch = (size_t)(step + 1) * sizeof(float);
-        if (lp_model) hipMemcpy2D(lp_model, sizeof(float), lpm.p + step, pitch, sizeof(float), b, hipMemcpyDeviceToHost);
-        if (lp_policy) hipMemcpy2D(lp_policy, sizeof(float), lpp.p + step, pitch, sizeof(float), b, hipMemcpyDeviceToHost);
-        if (n_kept) hipMemcpy(n_kept, nk.p, b * sizeof(int), hipMemcpyDeviceToHost);
+    if (ctl) {
+        ERCHK(ctl->dev.ensure(1));
+        ERCHK(ctl->lpm.ensure(b * ld));
+        ERCHK(ctl->lpp.ensure(b * ld));
+        ERCHK(ctl->nk.ensure(b));
+        const HeadCtlDev hc{ctl->s->temperature, ctl->s->top_p};
+        HIPCHK(hipMemcpy(ctl->dev.p, &hc, sizeof(hc), hipMemcpyHostToDevice));
+        const HeadCtlOut lp{ctl->lpm.p, ctl->lpp.p, ctl->nk.p, step + 1};
+        hipLaunchKernelGGL(sample_head_ctl_kernel, dim3(B), dim3(ER_WG), sample_head_lds(vocab), st, logits, dpd.p, ctl->dev.p, gs, ids.p,
+                           step + 1, lp);
+    } else {
+        hipLaunchKernelGGL(sample_head_kernel, dim3(B), dim3(ER_WG), sample_head_lds(vocab), st, logits, dpd.p, gs, ids.p, step + 1);
     }
+    const hipError_t e = hipGetLastError();
+    const hipError_t e2 = hipStreamSynchronize(st);
     HIPRET(e);
     HIPRET(e2);
+    HIPCHK(hipMemcpy(h.data(), sb.p, h.size() * sizeof(int), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < b; ++i) { next_tok[i] = hs.tok[i]; counter_out[i] = hs.counter[i]; unfinished_out[i] = hs.unfinished[i]; }
+    return ER_OK;
+}
+
+extern "C" int er_k_sample_head(const float* logits, const er_decode_params* p, int vocab, int eos, int pad, int B, int step,
+                                const int32_t* last_tok, const int32_t* counter, const int32_t* unfinished, int32_t* next_tok,
+                                int32_t* counter_out, int32_t* unfinished_out, void* stream) {
+    if (p && p->mode == ER_SAMPLE && p->top_k <= 0)        // as er_decode: only er_sampling can switch the top-k filter off
+        return fail(ER_ERR_INVALID, "er_k_sample_head: top_k must be > 0 in sample mode");
+    return head_unit_step("er_k_sample_head", logits, p, vocab, eos, pad, B, step, last_tok, counter, unfinished, next_tok, counter_out,
+                          unfinished_out, nullptr, (hipStream_t)stream);
+}
+
+extern "C" int er_k_sample_head_ctl(const float* logits, const er_decode_params* p, const er_sampling* s, int vocab, int eos, int pad,
+                                    int B, int step, const int32_t* last_tok, const int32_t* counter, const int32_t* unfinished,
+                                    int32_t* next_tok, int32_t* counter_out, int32_t* unfinished_out, float* lp_model, float* lp_policy,
+                                    int32_t* n_kept, void* stream) {
+    const er_sampling dflt{1.0f, 1.0f, 0, 0, 0};
+    if (!s) s = &dflt;
+    if (!(s->temperature > 0.0f) || !(s->temperature <= 3.402823466e38f) || !(s->top_p > 0.0f) || !(s->top_p <= 1.0f) || (s->top_k_set && s->top_k < 0))
+        return fail(ER_ERR_INVALID, "er_k_sample_head_ctl: temperature %g / top_p %g / top_k %d out of range", (double)s->temperature, (double)s->top_p, s->top_k);
+    HeadUnitCtl ctl{s};
+    ERCHK(head_unit_step("er_k_sample_head_ctl", logits, p, vocab, eos, pad, B, step, last_tok, counter, unfinished, next_tok, counter_out,
+                         unfinished_out, &ctl, (hipStream_t)stream));
+    const size_t pitch = (size_t)(step + 1) * sizeof(float);
+    if (lp_model) HIPCHK(hipMemcpy2D(lp_model, sizeof(float), ctl.lpm.p + step, pitch, sizeof(float), (size_t)B, hipMemcpyDeviceToHost));
+    if (lp_policy) HIPCHK(hipMemcpy2D(lp_policy, sizeof(float), ctl.lpp.p + step, pitch, sizeof(float), (size_t)B, hipMemcpyDeviceToHost));
+    if (n_kept) HIPCHK(hipMemcpy(n_kept, ctl.nk.p, (size_t)B * sizeof(int), hipMemcpyDeviceToHost));
     return ER_OK;
 }
 

@@ -13,6 +13,12 @@
 // (`0 in attention_mask`, reading input_ids[-1], the EOS check).  One workgroup per
 // batch row; all state (token, position, grammar counter, finished flag, output ids)
 // lives in HBM so the step can be replayed from a hipGraph.
+//
+// Two kernels, one set of pieces.  sample_head_kernel (the default step) and sample_head_ctl_kernel (temperature, wide top-k,
+// top-p, log-probs) are both written in terms of the head_* functions below: row entry, masked-score fill, block argmax, k-th
+// largest on wave 0, ballot compaction, lane-0 serial draw, Philox uniform and state commit each have ONE definition, so the
+// grammar, the NaN guard, the queue's row budget and the EOS bookkeeping cannot drift apart.  The ctl kernel's own are the raw
+// row's logsumexp, the temperature division, the nucleus sort, the workgroup scan and the inverse-CDF draw.
 #pragma once
 #include "er_common.h"
 
@@ -85,37 +91,56 @@ __device__ __forceinline__ int grammar_update(int grammar, int t, int counter, i
 // core/models.py:78-84).
 constexpr int ER_HEAD_MAX_VOCAB = 1088;
 
-// grid (B), 256 threads.  Dynamic LDS: vocab floats + 2*vocab ints-ish scratch (see launch).
-__global__ __launch_bounds__(ER_WG) void sample_head_kernel(const float* logits, const DecodeParamsDev* pp, GenState st,
-                                                            long long* out_ids, int out_ld) {
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    __shared__ float red[8];
-    __shared__ int redi[8];
-    __shared__ int chosen_s;
-    const DecodeParamsDev P = *pp;
-    const int V = P.vocab;
-    float* sc = smem;                              // [V] masked scores
-    float* cand_e = smem + V;                      // [V] candidate weights (compacted)
-    int* cand_i = reinterpret_cast<int*>(smem + 2 * V);   // [V] candidate ids (compacted)
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    const int t = st.ngen[b];
-    const int max_new = st.row_budget ? min(P.max_new, st.row_budget[b]) : P.max_new;
-    if (t >= max_new) return;                      // replay past the end (or a parked row of the queue mode): no-op
-    const int last = st.tok[b];
-    const bool running = st.unfinished[b] != 0;
-    int counter = st.counter[b];
-    if (running) counter = grammar_update(P.grammar, t, counter, last);
+// ------------------------------------------------------------------------------------ the pieces both heads are made of
+struct HeadRow {               // a row at the entry of its step
+    int t, counter;            // tokens generated so far; the grammar counter after the last token
+    bool running, past_end;    // not yet closed by EOS; replay past the end (or a parked row of the queue mode): the step is a no-op
+};
 
-    // masked scores
-    const float* lg = logits + (long long)b * V;
-    for (int i = tid; i < V; i += ER_WG) {
-        bool ok = grammar_allowed(P.grammar, t, counter, i, V, P.eos);
-        if (i == P.eos && t < P.min_new) ok = false;
-        sc[i] = ok ? lg[i] : -INFINITY;
+// Reads only.  Uniform per workgroup: the caller returns on past_end before any barrier, and before it writes anything of the row.
+__device__ __forceinline__ HeadRow head_row_entry(const DecodeParamsDev& P, const GenState& st, int b) {
+    HeadRow r{};
+    r.t = st.ngen[b];
+    const int max_new = st.row_budget ? min(P.max_new, st.row_budget[b]) : P.max_new;
+    r.past_end = r.t >= max_new;
+    const int last = st.tok[b];
+    r.running = st.unfinished[b] != 0;
+    r.counter = st.counter[b];
+    if (r.running) r.counter = grammar_update(P.grammar, r.t, r.counter, last);
+    return r;
+}
+
+// sc[0, V) = the row's scores with the grammar's and min_new's ids at -inf; ends with the barrier that publishes them.  RAW_MAX:
+// the thread's maximum over the RAW scores it read, in the same pass (the ctl head's lp_model); otherwise nothing is kept.
+template <bool RAW_MAX>
+__device__ __forceinline__ float head_fill_scores(const DecodeParamsDev& P, const HeadRow& r, const float* lg, float* sc) {
+    float rmax = -INFINITY;
+    for (int i = threadIdx.x; i < P.vocab; i += ER_WG) {
+        bool ok = grammar_allowed(P.grammar, r.t, r.counter, i, P.vocab, P.eos);
+        if (i == P.eos && r.t < P.min_new) ok = false;
+        if constexpr (RAW_MAX) {
+            const float x = lg[i];
+            rmax = fmaxf(rmax, x);
+            sc[i] = ok ? x : -INFINITY;
+        } else {
+            sc[i] = ok ? lg[i] : -INFINITY;
+        }
     }
     __syncthreads();
+    return rmax;
+}
 
-    // argmax with first-index tie-break (torch.argmax): used by greedy and as softmax max
+struct HeadMax {
+    float gmax;                // largest masked score: greedy's value and the softmax maximum
+    int gidx;                  // its first index (torch.argmax)
+    bool no_candidate;         // every masked score is NaN or -inf (fp16 overflow upstream, corrupt weights): HF would raise inside
+                               // torch.multinomial; here the row is closed with EOS and the error flag makes er_decode fail loudly
+};
+
+// Block argmax with first-index tie-break.  Every thread returns the same triple.  No trailing barrier: a caller that writes red
+// again synchronises first.
+__device__ __forceinline__ HeadMax head_block_argmax(const float* sc, int V, float* red, int* redi) {
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     float bv = -INFINITY;
     int bi = 0x7fffffff;
     for (int i = tid; i < V; i += ER_WG) {
@@ -131,90 +156,134 @@ __global__ __launch_bounds__(ER_WG) void sample_head_kernel(const float* logits,
     take(lane_xor_any<1>(bv, lane), (int)lane_xor_bits<1>((unsigned)bi, lane));
     if (lane == 0) { red[wid] = bv; redi[wid] = bi; }
     __syncthreads();
-    float gmax = red[0];
-    int gidx = redi[0];
+    HeadMax m{red[0], redi[0], false};
 #pragma unroll
     for (int w = 1; w < ER_NWAVES; ++w)
-        if (red[w] > gmax || (red[w] == gmax && redi[w] < gidx)) { gmax = red[w]; gidx = redi[w]; }
-    int chosen = gidx;
-    // every masked score is NaN or -inf (fp16 overflow upstream, corrupt weights): HF would raise inside
-    // torch.multinomial; here the row is closed with EOS and the error flag makes er_decode fail loudly
-    const bool no_candidate = gidx < 0 || gidx >= V || !(gmax > -INFINITY);
-    if (no_candidate) chosen = P.eos;
+        if (red[w] > m.gmax || (red[w] == m.gmax && redi[w] < m.gidx)) { m.gmax = red[w]; m.gidx = redi[w]; }
+    m.no_candidate = m.gidx < 0 || m.gidx >= V || !(m.gmax > -INFINITY);
+    return m;
+}
 
-    if (P.mode == 1 && !no_candidate) {   // sample: TopK(top_k) -> softmax -> categorical
-        // k-th largest value counting duplicates: remove one maximum k-1 times (wave 0, scores in registers)
+// Wave 0: the k-th largest score counting duplicates - remove one maximum k times, the lowest lane first, the scores of the whole
+// vocabulary in the wave's registers.  Fewer than k finite scores: -inf.  top_k <= 0: no threshold (-inf) - the ctl head's rule,
+// reached through er_sampling only: head_setup and er_k_sample_head guarantee top_k > 0 wherever sample_head_kernel draws.
+__device__ __forceinline__ float head_kth_largest(const float* sc, int V, int top_k, float gmax, int lane) {
+    if (top_k <= 0) return -INFINITY;
+    constexpr int MAXPL = ER_HEAD_MAX_VOCAB / 64;
+    float v[MAXPL];
+#pragma unroll
+    for (int j = 0; j < MAXPL; ++j) { const int i = j * 64 + lane; v[j] = (i < V) ? sc[i] : -INFINITY; }
+    const int k = min(top_k, V);
+    float kth = gmax;
+    for (int it = 0; it < k; ++it) {
+        float mv = -INFINITY; int mj = 0;
+#pragma unroll
+        for (int j = 0; j < MAXPL; ++j) if (v[j] > mv) { mv = v[j]; mj = j; }
+        const float wmax = wave_max(mv);
+        kth = wmax;
+        if (wmax == -INFINITY) break;
+        const unsigned long long holders = __ballot(mv == wmax);
+        const int first = __ffsll((long long)holders) - 1;
+        if (lane == first) {
+#pragma unroll
+            for (int j = 0; j < MAXPL; ++j) if (j == mj) v[j] = -INFINITY;
+        }
+    }
+    return kth;
+}
+
+// Wave 0: the candidates - s >= kth and finite - compacted in ascending token id into cand_i / cand_e (weight expf(s - gmax)), and
+// visible to the wave's lanes on return.  Returns their number.
+__device__ __forceinline__ int head_compact(const float* sc, int V, float kth, float gmax, int* cand_i, float* cand_e, int lane) {
+    int base = 0;
+    for (int j = 0; j * 64 < V; ++j) {
+        const int i = j * 64 + lane;
+        const float s = (i < V) ? sc[i] : -INFINITY;
+        const bool c = (s >= kth) && (s > -INFINITY);
+        const unsigned long long mask = __ballot(c);
+        if (c) {
+            const int slot = base + __popcll(mask & ((1ull << lane) - 1ull));
+            cand_i[slot] = i;
+            cand_e[slot] = expf(s - gmax);
+        }
+        base += __popcll(mask);
+    }
+    __builtin_amdgcn_wave_barrier();
+    __threadfence_block();
+    return base;
+}
+
+// the step's uniform in [0, 1): 24 bits of Philox word 0 at counter (t, the row's stream), key = seed
+__device__ __forceinline__ float head_uniform(const DecodeParamsDev& P, const GenState& st, int t, int b) {
+    unsigned int r[4];
+    philox4x32_10((unsigned int)t, st.row_stream ? st.row_stream[b] : (unsigned int)b, 0u, 0u, P.seed_lo, P.seed_hi, r);
+    return (float)(r[0] >> 8) * (1.0f / 16777216.0f);
+}
+
+struct HeadDraw { int pick; float pe, total; };   // the id drawn, its weight and the weight of all n candidates
+
+// One lane: ascending serial total, then the first candidate whose ascending running sum exceeds u * total; rounding may leave
+// u * total above the last sum, then the last candidate.
+__device__ __forceinline__ HeadDraw head_serial_draw(const int* cand_i, const float* cand_e, int n, float u, int eos) {
+    HeadDraw d{n > 0 ? cand_i[n - 1] : eos, n > 0 ? cand_e[n - 1] : 1.f, 0.f};
+    for (int c = 0; c < n; ++c) d.total += cand_e[c];
+    const float target = u * d.total;
+    float acc = 0.f;
+    for (int c = 0; c < n; ++c) {
+        acc += cand_e[c];
+        if (acc > target) { d.pick = cand_i[c]; d.pe = cand_e[c]; break; }
+    }
+    return d;
+}
+
+// Thread 0 closes the step: the id goes out (PAD for a finished row) and the row's state moves on.  Returns the id written.
+__device__ __forceinline__ int head_commit(const DecodeParamsDev& P, const GenState& st, int b, const HeadRow& r, int chosen,
+                                           bool no_candidate, long long* out_ids, int out_ld) {
+    if (no_candidate && r.running) *st.error = 1;
+    const int next = r.running ? chosen : P.pad;
+    out_ids[(long long)b * out_ld + r.t] = (long long)next;
+    st.tok[b] = next;
+    st.counter[b] = r.counter;
+    st.pos[b] = st.base_pos[b] + r.t;
+    st.ngen[b] = r.t + 1;
+    if (r.running && next == P.eos) {
+        st.unfinished[b] = 0;
+        st.eos_step[b] = r.t;
+        atomicSub(st.n_unfinished, 1);
+    }
+    return next;
+}
+
+// grid (B), 256 threads.  Dynamic LDS: vocab floats + 2*vocab ints-ish scratch (see launch).
+__global__ __launch_bounds__(ER_WG) void sample_head_kernel(const float* logits, const DecodeParamsDev* pp, GenState st,
+                                                            long long* out_ids, int out_ld) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    __shared__ float red[8];
+    __shared__ int redi[8];
+    __shared__ int chosen_s;
+    const DecodeParamsDev P = *pp;
+    const int V = P.vocab;
+    float* sc = smem;                              // [V] masked scores
+    float* cand_e = smem + V;                      // [V] candidate weights (compacted)
+    int* cand_i = reinterpret_cast<int*>(smem + 2 * V);   // [V] candidate ids (compacted)
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const HeadRow row = head_row_entry(P, st, b);
+    if (row.past_end) return;
+    head_fill_scores<false>(P, row, logits + (long long)b * V, sc);
+    const HeadMax m = head_block_argmax(sc, V, red, redi);
+    int chosen = m.no_candidate ? P.eos : m.gidx;
+
+    if (P.mode == 1 && !m.no_candidate) {   // sample: TopK(top_k) -> softmax -> categorical
         if (wid == 0) {
-            constexpr int MAXPL = ER_HEAD_MAX_VOCAB / 64;   // scores of the whole vocabulary in wave 0's registers
-            float v[MAXPL];
-#pragma unroll
-            for (int j = 0; j < MAXPL; ++j) { const int i = j * 64 + lane; v[j] = (i < V) ? sc[i] : -INFINITY; }
-            const int k = min(P.top_k, V);
-            float kth = gmax;
-            for (int it = 0; it < k; ++it) {
-                float mv = -INFINITY; int mj = 0;
-#pragma unroll
-                for (int j = 0; j < MAXPL; ++j) if (v[j] > mv) { mv = v[j]; mj = j; }
-                const float wmax = wave_max(mv);
-                kth = wmax;
-                if (wmax == -INFINITY) break;      // fewer than k finite scores: threshold is -inf
-                const unsigned long long holders = __ballot(mv == wmax);
-                const int first = __ffsll((long long)holders) - 1;
-                if (lane == first) {
-#pragma unroll
-                    for (int j = 0; j < MAXPL; ++j) if (j == mj) v[j] = -INFINITY;
-                }
-            }
-            // candidates: s >= kth and finite; compact in ascending token id
-            int base = 0;
-            for (int j = 0; j * 64 < V; ++j) {
-                const int i = j * 64 + lane;
-                const float s = (i < V) ? sc[i] : -INFINITY;
-                const bool c = (s >= kth) && (s > -INFINITY);
-                const unsigned long long mask = __ballot(c);
-                if (c) {
-                    const int slot = base + __popcll(mask & ((1ull << lane) - 1ull));
-                    cand_i[slot] = i;
-                    cand_e[slot] = expf(s - gmax);
-                }
-                base += __popcll(mask);
-            }
-            __builtin_amdgcn_wave_barrier();
-            __threadfence_block();
-            if (lane == 0) {
-                float total = 0.f;
-                for (int c = 0; c < base; ++c) total += cand_e[c];
-                unsigned int r[4];
-                philox4x32_10((unsigned int)t, st.row_stream ? st.row_stream[b] : (unsigned int)b, 0u, 0u, P.seed_lo, P.seed_hi, r);
-                const float u = (float)(r[0] >> 8) * (1.0f / 16777216.0f);
-                const float target = u * total;
-                float acc = 0.f;
-                int pick = base > 0 ? cand_i[base - 1] : P.eos;
-                for (int c = 0; c < base; ++c) {
-                    acc += cand_e[c];
-                    if (acc > target) { pick = cand_i[c]; break; }
-                }
-                chosen_s = pick;
-            }
+            const float kth = head_kth_largest(sc, V, P.top_k, m.gmax, lane);
+            const int n = head_compact(sc, V, kth, m.gmax, cand_i, cand_e, lane);
+            if (lane == 0) chosen_s = head_serial_draw(cand_i, cand_e, n, head_uniform(P, st, row.t, b), P.eos).pick;
         }
         __syncthreads();
         chosen = chosen_s;
     }
 
-    if (tid == 0) {
-        if (no_candidate && running) *st.error = 1;
-        int next = running ? chosen : P.pad;
-        out_ids[(long long)b * out_ld + t] = (long long)next;
-        st.tok[b] = next;
-        st.counter[b] = counter;
-        st.pos[b] = st.base_pos[b] + t;
-        st.ngen[b] = t + 1;
-        if (running && next == P.eos) {
-            st.unfinished[b] = 0;
-            st.eos_step[b] = t;
-            atomicSub(st.n_unfinished, 1);
-        }
-    }
+    if (tid == 0) head_commit(P, st, b, row, chosen, m.no_candidate, out_ids, out_ld);
 }
 
 // er_feed: teacher-forced token (host-chosen ids copied to ids_dev beforehand)
@@ -243,9 +312,9 @@ inline size_t sample_head_lds(int vocab) { return (size_t)vocab * 3 * sizeof(flo
 //   lp_model  = logits[next] - logsumexp(logits) over the RAW row (what LMM.score reports as -nll)
 //   lp_policy = log of the probability the id had in the distribution it was drawn from (greedy: log_softmax(masked)[next])
 // er_decode / er_queue_begin launch it only when a control is off its default or log-probs are asked for (er_set_sampling): the default
-// path keeps sample_head_kernel and its captured step.  With temperature 1, top_p 1 and top_k > 0 it picks the id sample_head_kernel picks
-// (same compaction, same expf(s - gmax), same ascending serial sum by one lane).  Every other setting may keep hundreds of candidates, so
-// it sums, filters and draws with the whole workgroup instead: a sort in LDS for the nucleus, a scan for the inverse CDF.
+// path keeps sample_head_kernel and its captured step.  With temperature 1, top_p 1 and top_k > 0 it picks the id sample_head_kernel picks:
+// the entry, fill, argmax, threshold, compaction, draw and commit are the same functions.  Every other setting may keep hundreds of
+// candidates, so it sums, filters and draws with the whole workgroup instead: a sort in LDS for the nucleus, a scan for the inverse CDF.
 struct HeadCtlDev {            // device copy of er_sampling (the effective top_k travels in DecodeParamsDev)
     float temperature, top_p;
 };
@@ -268,6 +337,23 @@ __device__ __forceinline__ float head_block_sum(const float* a, int n, float* re
     return block_sum(v, red);
 }
 
+// Inclusive scan of one value per thread (Hillis-Steele, 8 steps through scan[2][ER_WG]); returns the sum of the threads BEFORE this
+// one.  Ends with a barrier; a caller that scans again has one more between its reads and the next call.
+__device__ __forceinline__ float head_block_scan_before(float (*scan)[ER_WG], float mine) {
+    const int tid = threadIdx.x;
+    int cur = 0;
+    scan[0][tid] = mine;
+    __syncthreads();
+#pragma unroll
+    for (int off = 1; off < ER_WG; off <<= 1) {
+        const float x = scan[cur][tid] + (tid >= off ? scan[cur][tid - off] : 0.f);
+        scan[cur ^ 1][tid] = x;
+        cur ^= 1;
+        __syncthreads();
+    }
+    return tid > 0 ? scan[cur][tid - 1] : 0.f;
+}
+
 // grid (B), 256 threads.  Dynamic LDS: sample_head_lds(vocab), as sample_head_kernel.
 __global__ __launch_bounds__(ER_WG) void sample_head_ctl_kernel(const float* logits, const DecodeParamsDev* pp, const HeadCtlDev* cp,
                                                                 GenState st, long long* out_ids, int out_ld, HeadCtlOut lp) {
@@ -285,130 +371,45 @@ __global__ __launch_bounds__(ER_WG) void sample_head_ctl_kernel(const float* log
     float* cand_e = smem + V;                      // [V] candidate weights (compacted)
     int* cand_i = reinterpret_cast<int*>(smem + 2 * V);   // [V] candidate ids (compacted)
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    const int t = st.ngen[b];
-    const int max_new = st.row_budget ? min(P.max_new, st.row_budget[b]) : P.max_new;
-    if (t >= max_new) return;                      // replay past the end (or a parked row of the queue mode): no-op
-    const int last = st.tok[b];
-    const bool running = st.unfinished[b] != 0;
-    int counter = st.counter[b];
-    if (running) counter = grammar_update(P.grammar, t, counter, last);
+    const HeadRow row = head_row_entry(P, st, b);
+    if (row.past_end) return;
 
-    // masked scores, and the raw row's maximum for lp_model
+    // masked scores, and the raw row's logsumexp for lp_model
     const float* lg = logits + (long long)b * V;
-    float rmax = -INFINITY;
-    for (int i = tid; i < V; i += ER_WG) {
-        bool ok = grammar_allowed(P.grammar, t, counter, i, V, P.eos);
-        if (i == P.eos && t < P.min_new) ok = false;
-        const float x = lg[i];
-        rmax = fmaxf(rmax, x);
-        sc[i] = ok ? x : -INFINITY;
-    }
-    __syncthreads();
-    rmax = block_max(rmax, red);
+    const float rmax = block_max(head_fill_scores<true>(P, row, lg, sc), red);
     float rsum = 0.f;
     for (int i = tid; i < V; i += ER_WG) rsum += expf(lg[i] - rmax);
     rsum = block_sum(rsum, red);
     const float raw_lse = rmax + logf(rsum);
 
-    // argmax with first-index tie-break (torch.argmax): used by greedy and as softmax max
-    float bv = -INFINITY;
-    int bi = 0x7fffffff;
-    for (int i = tid; i < V; i += ER_WG) {
-        const float v = sc[i];
-        if (v > bv) { bv = v; bi = i; }
-    }
-    auto take = [&](float ov, int oi) { if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; } };
-    take(lane_xor_any<32>(bv, lane), (int)lane_xor_bits<32>((unsigned)bi, lane));
-    take(lane_xor_any<16>(bv, lane), (int)lane_xor_bits<16>((unsigned)bi, lane));
-    take(lane_xor_any<8>(bv, lane), (int)lane_xor_bits<8>((unsigned)bi, lane));
-    take(lane_xor_any<4>(bv, lane), (int)lane_xor_bits<4>((unsigned)bi, lane));
-    take(lane_xor_any<2>(bv, lane), (int)lane_xor_bits<2>((unsigned)bi, lane));
-    take(lane_xor_any<1>(bv, lane), (int)lane_xor_bits<1>((unsigned)bi, lane));
-    if (lane == 0) { red[wid] = bv; redi[wid] = bi; }
-    __syncthreads();
-    float gmax = red[0];
-    int gidx = redi[0];
-#pragma unroll
-    for (int w = 1; w < ER_NWAVES; ++w)
-        if (red[w] > gmax || (red[w] == gmax && redi[w] < gidx)) { gmax = red[w]; gidx = redi[w]; }
+    const HeadMax m = head_block_argmax(sc, V, red, redi);
     __syncthreads();                               // red is reused below
-    int chosen = gidx;
-    const bool no_candidate = gidx < 0 || gidx >= V || !(gmax > -INFINITY);
-    if (no_candidate) chosen = P.eos;
+    float gmax = m.gmax;
+    int chosen = m.no_candidate ? P.eos : m.gidx;
     float lp_policy = 0.f;
     int n_kept = 0;
 
-    if (P.mode != 1 && !no_candidate) {            // greedy: log_softmax(masked)[argmax] = -log(sum exp(s - gmax))
+    if (P.mode != 1 && !m.no_candidate) {          // greedy: log_softmax(masked)[argmax] = -log(sum exp(s - gmax))
         float e = 0.f;
         for (int i = tid; i < V; i += ER_WG) e += expf(sc[i] - gmax);
         lp_policy = -logf(block_sum(e, red));
     }
 
-    if (P.mode == 1 && !no_candidate) {            // sample: temperature -> TopK -> TopP -> softmax -> categorical
+    if (P.mode == 1 && !m.no_candidate) {          // sample: temperature -> TopK -> TopP -> softmax -> categorical
         // TemperatureLogitsWarper: a true division (x / 1 is x: the default leaves every bit alone).  It is monotone, so gidx stays
         // a first maximum and the maximum is gmax / temperature
         for (int i = tid; i < V; i += ER_WG) sc[i] = sc[i] / Cc.temperature;
         gmax = gmax / Cc.temperature;
         __syncthreads();
         if (wid == 0) {
-            // k-th largest value counting duplicates, as sample_head_kernel; top_k 0: no threshold
-            float kth = -INFINITY;
-            if (P.top_k > 0) {
-                constexpr int MAXPL = ER_HEAD_MAX_VOCAB / 64;
-                float v[MAXPL];
-#pragma unroll
-                for (int j = 0; j < MAXPL; ++j) { const int i = j * 64 + lane; v[j] = (i < V) ? sc[i] : -INFINITY; }
-                const int k = min(P.top_k, V);
-                kth = gmax;
-                for (int it = 0; it < k; ++it) {
-                    float mv = -INFINITY; int mj = 0;
-#pragma unroll
-                    for (int j = 0; j < MAXPL; ++j) if (v[j] > mv) { mv = v[j]; mj = j; }
-                    const float wmax = wave_max(mv);
-                    kth = wmax;
-                    if (wmax == -INFINITY) break;
-                    const unsigned long long holders = __ballot(mv == wmax);
-                    const int first = __ffsll((long long)holders) - 1;
-                    if (lane == first) {
-#pragma unroll
-                        for (int j = 0; j < MAXPL; ++j) if (j == mj) v[j] = -INFINITY;
-                    }
-                }
-            }
-            // candidates: s >= kth and finite; compact in ascending token id
-            int base = 0;
-            for (int j = 0; j * 64 < V; ++j) {
-                const int i = j * 64 + lane;
-                const float s = (i < V) ? sc[i] : -INFINITY;
-                const bool c = (s >= kth) && (s > -INFINITY);
-                const unsigned long long mask = __ballot(c);
-                if (c) {
-                    const int slot = base + __popcll(mask & ((1ull << lane) - 1ull));
-                    cand_i[slot] = i;
-                    cand_e[slot] = expf(s - gmax);
-                }
-                base += __popcll(mask);
-            }
-            __builtin_amdgcn_wave_barrier();
-            __threadfence_block();
-            if (lane == 0) { n_cand_s = base; first_hit_s = 0x7fffffff; last_kept_s = -1; n_kept_s = 0; }
+            const float kth = head_kth_largest(sc, V, P.top_k, gmax, lane);
+            const int n = head_compact(sc, V, kth, gmax, cand_i, cand_e, lane);
+            if (lane == 0) { n_cand_s = n; first_hit_s = 0x7fffffff; last_kept_s = -1; n_kept_s = 0; }
             if (P.top_k > 0 && !(Cc.top_p < 1.0f) && lane == 0) {   // sample_head_kernel's draw, sum for sum
-                float total = 0.f;
-                for (int c = 0; c < base; ++c) total += cand_e[c];
-                unsigned int r[4];
-                philox4x32_10((unsigned int)t, st.row_stream ? st.row_stream[b] : (unsigned int)b, 0u, 0u, P.seed_lo, P.seed_hi, r);
-                const float u = (float)(r[0] >> 8) * (1.0f / 16777216.0f);
-                const float target = u * total;
-                float acc = 0.f;
-                int pick = base > 0 ? cand_i[base - 1] : P.eos;
-                float pe = base > 0 ? cand_e[base - 1] : 1.f;
-                for (int c = 0; c < base; ++c) {
-                    acc += cand_e[c];
-                    if (acc > target) { pick = cand_i[c]; pe = cand_e[c]; break; }
-                }
-                chosen_s = pick;
-                lp_policy_s = logf(pe / total);
-                n_kept_s = base;
+                const HeadDraw d = head_serial_draw(cand_i, cand_e, n, head_uniform(P, st, row.t, b), P.eos);
+                chosen_s = d.pick;
+                lp_policy_s = logf(d.pe / d.total);
+                n_kept_s = n;
             }
         }
         __syncthreads();
@@ -447,18 +448,8 @@ __global__ __launch_bounds__(ER_WG) void sample_head_ctl_kernel(const float* log
                     w[q] = (r0 + q < n) ? __uint_as_float(~(unsigned)(keys[r0 + q] >> 32)) : 0.f;
                     mine_r += w[q];
                 }
-                int cur = 0;
-                scan[0][tid] = mine_r;
-                __syncthreads();
-#pragma unroll
-                for (int off = 1; off < ER_WG; off <<= 1) {
-                    const float x = scan[cur][tid] + (tid >= off ? scan[cur][tid - off] : 0.f);
-                    scan[cur ^ 1][tid] = x;
-                    cur ^= 1;
-                    __syncthreads();
-                }
                 const float limit = Cc.top_p * total;
-                float ahead = tid > 0 ? scan[cur][tid - 1] : 0.f;
+                float ahead = head_block_scan_before(scan, mine_r);
 #pragma unroll
                 for (int q = 0; q < HEAD_CTL_RANKS; ++q) {
                     if (r0 + q < n && !(ahead < limit)) cand_e[(unsigned)keys[r0 + q]] = -1.f;      // dropped (a weight is >= 0)
@@ -480,22 +471,9 @@ __global__ __launch_bounds__(ER_WG) void sample_head_ctl_kernel(const float* log
                 mine += e[q];
                 if (in[q]) { ++kept; my_last = c0 + q; }
             }
-            // inclusive scan of the threads' sums (Hillis-Steele, 8 steps): scan[.][tid] = weight of candidates [0, c0 + 5)
-            int cur = 0;
-            scan[0][tid] = mine;
-            __syncthreads();
-#pragma unroll
-            for (int off = 1; off < ER_WG; off <<= 1) {
-                const float x = scan[cur][tid] + (tid >= off ? scan[cur][tid - off] : 0.f);
-                scan[cur ^ 1][tid] = x;
-                cur ^= 1;
-                __syncthreads();
-            }
-            unsigned int r[4];
-            philox4x32_10((unsigned int)t, st.row_stream ? st.row_stream[b] : (unsigned int)b, 0u, 0u, P.seed_lo, P.seed_hi, r);
-            const float u = (float)(r[0] >> 8) * (1.0f / 16777216.0f);
-            const float target = u * total;
-            float acc = tid > 0 ? scan[cur][tid - 1] : 0.f;
+            // inverse CDF: acc = weight of candidates [0, c0) before the thread's own run
+            float acc = head_block_scan_before(scan, mine);
+            const float target = head_uniform(P, st, row.t, b) * total;
             int hit = 0x7fffffff;
 #pragma unroll
             for (int q = 0; q < HEAD_CTL_PER_THREAD; ++q) {
@@ -518,21 +496,11 @@ __global__ __launch_bounds__(ER_WG) void sample_head_ctl_kernel(const float* log
     }
 
     if (tid == 0) {
-        if (no_candidate && running) *st.error = 1;
-        int next = running ? chosen : P.pad;
-        out_ids[(long long)b * out_ld + t] = (long long)next;
-        if (lp.lp_model) lp.lp_model[(long long)b * lp.ld + t] = (running && !no_candidate) ? lg[next] - raw_lse : 0.f;
-        if (lp.lp_policy) lp.lp_policy[(long long)b * lp.ld + t] = (running && !no_candidate) ? lp_policy : 0.f;
-        if (lp.n_kept) lp.n_kept[b] = running ? n_kept : 0;
-        st.tok[b] = next;
-        st.counter[b] = counter;
-        st.pos[b] = st.base_pos[b] + t;
-        st.ngen[b] = t + 1;
-        if (running && next == P.eos) {
-            st.unfinished[b] = 0;
-            st.eos_step[b] = t;
-            atomicSub(st.n_unfinished, 1);
-        }
+        const int next = head_commit(P, st, b, row, chosen, m.no_candidate, out_ids, out_ld);
+        const bool scored = row.running && !m.no_candidate;
+        if (lp.lp_model) lp.lp_model[(long long)b * lp.ld + row.t] = scored ? lg[next] - raw_lse : 0.f;
+        if (lp.lp_policy) lp.lp_policy[(long long)b * lp.ld + row.t] = scored ? lp_policy : 0.f;
+        if (lp.n_kept) lp.n_kept[b] = row.running ? n_kept : 0;
     }
 }
 

@@ -74,7 +74,7 @@ def head_state(step, grammar):
 
 
 # ------------------------------------------------------------------ 1. at the defaults the new head is the old one
-@pytest.mark.parametrize("V", [518, 1030])
+@pytest.mark.parametrize("V", [70, 518, 1030, 1088])      # 70: most threads own no score; 1088: ER_HEAD_MAX_VOCAB, no ragged tail
 def test_defaults_pick_what_sample_head_kernel_picks(V):
     from edgerunner_amd import kernels as K
     logits = rows_with_a_tie(V, 52).to(DEV)
@@ -98,23 +98,39 @@ def test_defaults_pick_what_sample_head_kernel_picks(V):
 
 
 # ------------------------------------------------------------------ 2. filters
+def seeded_row(V, seed):
+    if ("row", V, seed) not in _CACHE:
+        _CACHE["row", V, seed] = torch.randn(V, generator=torch.Generator().manual_seed(seed)) * 3
+    return _CACHE["row", V, seed]
+
+
 @pytest.fixture(scope="module")
 def row60():
-    return torch.randn(518, generator=torch.Generator().manual_seed(60)) * 3
+    return seeded_row(518, 60)
 
 
-@pytest.mark.parametrize("temperature,top_k,top_p", CONFIGS)
-def test_filters_match_the_float64_restatement(row60, temperature, top_k, top_p):
+# The vocabulary edges: 70 ids (two registers' worth in wave 0, most threads own no candidate) and ER_HEAD_MAX_VOCAB = 1088, where
+# top_k = 0 is the 2048-key sort with ranks above 1024.  Rows and configs chosen on the CPU with tests/sampling_ref.py so that the
+# reference margin clears the bound below: the smallest is 7.5e-3 against 1.6e-6 (V = 70, seed 62) and 8.7e-4 against 1.0e-5 (V = 1088,
+# seed 61).  (2.0, 0, 0.99) is left out at V >= 1030: the reference itself sits inside the bound there.
+EDGE_CONFIGS = [(1.3, 0, 0.8), (0.7, 10, 0.9), (1.0, 50, 0.5)]
+FILTER_CASES = [pytest.param(518, 60, *c, id="-".join(str(x) for x in c)) for c in CONFIGS] + \
+               [pytest.param(V, seed, *c, id=f"V{V}-" + "-".join(str(x) for x in c)) for V, seed in ((70, 62), (1088, 61)) for c in EDGE_CONFIGS]
+
+
+@pytest.mark.parametrize("V,seed,temperature,top_k,top_p", FILTER_CASES)
+def test_filters_match_the_float64_restatement(V, seed, temperature, top_k, top_p):
     from edgerunner_amd import kernels as K
-    s, keep, margin = R.filtered(row60, temperature, top_k, top_p)
+    row = seeded_row(V, seed)
+    s, keep, margin = R.filtered(row, temperature, top_k, top_p)
     n_ref = int(keep.sum())
     print(f"(T={temperature}, k={top_k}, p={top_p}): reference keeps {n_ref}, margin {margin:.3e}, bound {n_ref * 2.0 ** -23:.3e}")
     assert margin > n_ref * 2.0 ** -23, "the case sits too close to the nucleus boundary for an fp32 running sum"
-    logits = row60[None].repeat(B, 1).to(DEV)
+    logits = row[None].repeat(B, 1).to(DEV)
     step, seed = 3, 1234
     nt, _, uo, lpm, lpp, nk = K.sample_head_ctl(logits, 1, 0, step, [7] * B, [0] * B, [1] * B, top_k=10, seed=seed,
                                                 temperature=temperature, top_p=top_p, sampling_top_k=top_k)
-    ref_policy, ref_model = R.policy_logprobs(s, keep), R.model_logprobs(row60)
+    ref_policy, ref_model = R.policy_logprobs(s, keep), R.model_logprobs(row)
     worst_p = worst_m = 0.0
     off_boundary = 0
     for b in range(B):

@@ -72,6 +72,31 @@ def test_library_exports_the_new_entry_points():
     assert lib.er_abi_version() == 1
 
 
+def test_plain_unit_entry_refuses_what_it_cannot_handle():
+    """er_k_sample_head shares er_k_sample_head_ctl's argument check, which runs before any HIP call (there is no GPU here: a HIP
+    call would fail with ER_ERR_HIP): a vocabulary above ER_HEAD_MAX_VOCAB = 1088 and a null pointer are ER_ERR_INVALID by name.  So is
+    top_k <= 0 in sample mode, as in er_decode: the shared k-th-largest piece reads it as "no threshold", which only er_sampling may
+    ask for (er_k_sample_head_ctl)."""
+    import ctypes as C
+    from edgerunner_amd import build, native
+    build.build(verbose=False)
+    lib = native.load_library()
+    B = 2
+    p = native.ErDecodeParams(mode=1, top_k=10, grammar=0, max_new_tokens=1, min_new_tokens=0, seed=0)
+    logits = (C.c_float * (B * 1089))()              # never read: the entry refuses first
+    state = native.i32_array([0] * B)
+    outs = [(C.c_int32 * B)() for _ in range(3)]
+    calls = {"vocab 1089": (C.addressof(logits), C.byref(p), 1089, 2, 0, B, 0, state, state, state, *outs, None),
+             "null last_tok": (C.addressof(logits), C.byref(p), 518, 2, 0, B, 0, None, state, state, *outs, None),
+             "null logits": (None, C.byref(p), 518, 2, 0, B, 0, state, state, state, *outs, None)}
+    p0 = native.ErDecodeParams(mode=1, top_k=0, grammar=0, max_new_tokens=1, min_new_tokens=0, seed=0)
+    calls["top_k 0 in sample mode"] = (C.addressof(logits), C.byref(p0), 518, 2, 0, B, 0, state, state, state, *outs, None)
+    for what, args in calls.items():
+        assert lib.er_k_sample_head(*args) == -1, what                      # ER_ERR_INVALID
+        assert lib.er_last_error().decode().startswith("er_k_sample_head:"), (what, lib.er_last_error())
+    assert "top_k" in lib.er_last_error().decode()
+
+
 def _infer():
     spec = importlib.util.spec_from_file_location("infer_under_test", os.path.join(ROOT, "infer.py"))
     mod = importlib.util.module_from_spec(spec)
