@@ -70,6 +70,9 @@ struct LayerW {
     // fast mode (fp16 storage): *_h hold the streamed fp16 matrices; the fp32 copies then hold the SAME
     // fp16-rounded values (used by the prefill GEMMs), so prefill and decode see one model
     _Float16 *wqkv_h = nullptr, *wo_h = nullptr, *w1_h = nullptr, *w2_h = nullptr;
+    // fp8 mode (er_w8.h): the byte blocks of the same four matrices (e4m3 [N][K], then 2^e per row); *_h and the fp32 copies then hold
+    // the dequantised values
+    unsigned char *wqkv_q = nullptr, *wo_q = nullptr, *w1_q = nullptr, *w2_q = nullptr;
     void *wqkv_t = nullptr, *wo_t = nullptr, *w1_t = nullptr, *w2_t = nullptr;   // tiled copies for the matrix-core batched kernels (k_gemv_mfma.h)
     void* w2_kt = nullptr;   // fc2.weight k-major, [intermediate][hidden] in the streamed weight type: the fused single-row MLP (k_mlp_sparse.h)
     float *wqkv = nullptr, *bqkv = nullptr;   // fused [3*hidden][hidden] in q,k,v order
@@ -179,6 +182,7 @@ struct er_ctx {
     float *embd = nullptr, *posemb = nullptr, *lm_head = nullptr, *embed_num_face = nullptr;
     _Float16* lm_head_h = nullptr;
     bool fast = false;       // fp16 weights + fp16 KV cache, fp32 accumulate
+    bool w8 = false;         // fp8 mode: fast, with the six decoder matrices per layer quantised by row; the row forms of the step stream the bytes
     float *proj_w = nullptr, *proj_b = nullptr, *normc_w = nullptr, *normc_b = nullptr;
     PointEnc pe;             // point encoder (cond_mode POINT)
     WeightTable w;           // every checkpoint key (register_weights)
@@ -283,6 +287,7 @@ static void register_weights(er_ctx* c) {
     const er_config& g = c->cfg;
     const size_t H = g.hidden_dim, I = g.intermediate_dim, V = g.vocab_size;
     t.fp16 = c->fast;
+    t.w8 = c->w8;
     if (g.cond_mode == ER_COND_POINT) pe_attach(t, c->pe, ER_PE_EMBED, "er_create", "");
     if (g.cond_mode != ER_COND_NONE) {
         t.lin("proj_cond", &c->proj_w, &c->proj_b, H, g.point_latent_dim);
@@ -297,13 +302,13 @@ static void register_weights(er_ctx* c) {
         const char* qkv[3] = {"q_proj", "k_proj", "v_proj"};     // fused [3 H][H] (+ bias [3 H]) in q, k, v order
         for (size_t j = 0; j < 3; ++j) {
             const std::string q = p + "self_attn." + qkv[j];
-            t.add(q + ".weight", &L.wqkv, H * H).slice(3 * H * H, j * H * H).half(&L.wqkv_h);
+            t.add(q + ".weight", &L.wqkv, H * H).slice(3 * H * H, j * H * H).half(&L.wqkv_h).rows8(&L.wqkv_q, H);
             t.add(q + ".bias", &L.bqkv, H).slice(3 * H, j * H);
         }
-        t.lin(p + "self_attn.out_proj", &L.wo, &L.bo, H, H).half(&L.wo_h);
+        t.lin(p + "self_attn.out_proj", &L.wo, &L.bo, H, H).half(&L.wo_h).rows8(&L.wo_q, H);
         t.lin(p + "self_attn_layer_norm", &L.ln1w, &L.ln1b, H, 1);
-        t.lin(p + "fc1", &L.w1, &L.b1, I, H).half(&L.w1_h);
-        t.lin(p + "fc2", &L.w2, &L.b2, H, I).half(&L.w2_h);
+        t.lin(p + "fc1", &L.w1, &L.b1, I, H).half(&L.w1_h).rows8(&L.w1_q, H);
+        t.lin(p + "fc2", &L.w2, &L.b2, H, I).half(&L.w2_h).rows8(&L.w2_q, I);
         t.lin(p + "final_layer_norm", &L.ln2w, &L.ln2b, H, 1);
     }
     t.add("mesh_decoder.lm_head.weight", &c->lm_head, V * H).half(&c->lm_head_h);
@@ -318,9 +323,10 @@ extern "C" int er_create(const er_config* cfg, int device, er_ctx** out) {
     const int D = cfg->hidden_dim / cfg->num_heads;
     if (D != 96 && D != 64) return fail(ER_ERR_UNSUPPORTED, "head_dim %d not built (96, 64)", D);
     const bool exact = cfg->weight_dtype == ER_F32 && cfg->kv_dtype == ER_F32;
-    const bool fast = cfg->weight_dtype == ER_F16 && cfg->kv_dtype == ER_F16;
+    const bool w8 = cfg->weight_dtype == ER_F8E4M3 && cfg->kv_dtype == ER_F16;
+    const bool fast = w8 || (cfg->weight_dtype == ER_F16 && cfg->kv_dtype == ER_F16);
     if (!exact && !fast)
-        return fail(ER_ERR_UNSUPPORTED, "built modes: fp32 weights + fp32 KV (exact) or fp16 weights + fp16 KV (fast)");
+        return fail(ER_ERR_UNSUPPORTED, "built modes: fp32 weights + fp32 KV (exact), fp16 weights + fp16 KV (fast) or e4m3 row-scaled weights + fp16 KV (fp8)");
     if (cfg->vocab_size > ER_HEAD_MAX_VOCAB) return fail(ER_ERR_UNSUPPORTED, "vocab_size > %d", ER_HEAD_MAX_VOCAB);
     if (cfg->cond_mode == ER_COND_POINT && (cfg->point_hidden_dim != 1024 || cfg->point_hidden_dim % cfg->point_num_heads))
         return fail(ER_ERR_UNSUPPORTED, "point encoder width %d not built (1024)", cfg->point_hidden_dim);
@@ -330,6 +336,7 @@ extern "C" int er_create(const er_config* cfg, int device, er_ctx** out) {
     c->device = device;
     c->D = D;
     c->fast = fast;
+    c->w8 = w8;
     c->kv_esz = fast ? 2 : 4;
     c->layers.resize(cfg->num_layers);
     c->pe.PH = cfg->point_hidden_dim; c->pe.heads = cfg->point_num_heads; c->pe.Lq = cfg->point_latent_size;
@@ -619,6 +626,7 @@ static hipError_t launch_kind_t(er_ctx* c, int kind, int layer, hipStream_t st, 
                 if (form_of(PROJ_FC2, layer - 1).defer) io.rd = {sk.p, c->layers[layer - 1].b2, kv.h1buf.p, SK_SLICES_FC2};
             }
             io.w_tiled = L.wqkv_t; io.x_image = kv.xt_h.p; io.pro_image = p.xt ? kv.xt_h.p : nullptr;
+            if (c->w8) io.w8 = L.wqkv_q;
             return run_proj<WT>(PROJ_QKV, form_of(PROJ_QKV, layer), io, a, B, H, sk, st);
         }
         // v2 holds a wave's whole K/V slice in flight (latency-bound single rows); with hundreds of workgroups per CU's
@@ -638,10 +646,15 @@ static hipError_t launch_kind_t(er_ctx* c, int kind, int layer, hipStream_t st, 
                 OutMergeArgs m{};
                 m.W = HALF ? (const void*)L.wo_h : (const void*)L.wo; m.bias = L.bo; m.resid = c->kv->hbuf.p; m.out = c->kv->ypre1.p;
                 m.part_o = c->kv->part.p; m.part_ml = c->kv->part_ml.p; m.N = H;
+                if (c->w8 && w8_streams(PROJ_OUT, 1)) {      // the row form of out_proj at one row: the same decision as launch_proj's
+                    m.W = L.wo_q;
+                    return launch_outproj_merge<w8_t, 96>(m, p.nch3, st);
+                }
                 return launch_outproj_merge<WT, 96>(m, p.nch3, st);
             }
             a.W = HALF ? (const void*)L.wo_h : (const void*)L.wo; a.bias = L.bo; a.N = H; a.xin = kv.abuf.p; a.out = kv.ypre1.p; a.resid = kv.hbuf.p;
             io.w_tiled = L.wo_t; io.x_image = kv.xt_att.p;      // the streaming attention wrote the image (attn_args: out_xt)
+            if (c->w8) io.w8 = L.wo_q;
             return run_proj<WT>(PROJ_OUT, form_of(PROJ_OUT, layer), io, a, B, H, sk, st);
         }
         case 4: {   // h1 = LN1(ypre1); f = relu(fc1 h1 + b)
@@ -656,6 +669,7 @@ static hipError_t launch_kind_t(er_ctx* c, int kind, int layer, hipStream_t st, 
             // out_proj (case 3) left four K-range partials: ypre1 = ((sum) + bo) + h
             if (form_of(PROJ_OUT, layer).defer) io.rd = {sk.p, L.bo, kv.hbuf.p, SK_SLICES_OUTPROJ};
             io.w_tiled = L.w1_t; io.x_image = kv.xt_h.p; io.pro_image = p.xt ? kv.xt_h.p : nullptr; io.out_image = kv.xt_f.p;
+            if (c->w8) io.w8 = L.w1_q;
             return run_proj<WT>(PROJ_FC1, form_of(PROJ_FC1, layer), io, a, B, H, sk, st);
         }
         case 5: {   // ypre = fc2 f + b + h1
@@ -663,6 +677,7 @@ static hipError_t launch_kind_t(er_ctx* c, int kind, int layer, hipStream_t st, 
             if (fused) return launch_mlp_finish(mlp_args(c, layer), st);
             a.W = HALF ? (const void*)L.w2_h : (const void*)L.w2; a.bias = L.b2; a.N = H; a.xin = kv.fbuf.p; a.out = kv.ypre.p; a.resid = kv.h1buf.p;
             io.w_tiled = L.w2_t; io.x_image = kv.xt_f.p;
+            if (c->w8) io.w8 = L.w2_q;
             return run_proj<WT>(PROJ_FC2, form_of(PROJ_FC2, layer), io, a, B, I, sk, st);
         }
         case 6: {   // logits = lm_head LN2_last(ypre)
@@ -1658,6 +1673,13 @@ static int profile_impl(er_ctx* c, int repeats, int use_graph, float* avg_us, do
     bytes[5] = ((double)I * H + H) * w + (double)B * (I + 2 * H) * w;
     bytes[6] = ((double)V * H) * w + (double)B * (H + V) * w;
     bytes[7] = (double)B * V * w;
+    if (c->w8 && !p.batched) {   // the row forms that stream bytes: 1 byte per weight + 4 per row scale in place of 2 per weight
+        const auto less = [&](Proj proj, double n, double k) { return w8_streams(proj, B) ? n * k * (w - 1.0) - n * 4.0 : 0.0; };
+        bytes[0] -= less(PROJ_QKV, 3.0 * H, H);
+        bytes[3] -= less(PROJ_OUT, H, H);
+        bytes[4] -= less(PROJ_FC1, I, H);
+        bytes[5] -= less(PROJ_FC2, H, I);
+    }
 
     if (p.shared_attn) {   // kind 1 reads the prefix once per group and writes a partial per (row, head, chunk); kind 2 reads the suffixes and the partials
         const double P = c->kv->prefix_len, parts = (double)B * g.num_heads * attn_shared_chunks(c->kv->prefix_len) * (c->D + 2) * 4.0;
@@ -1970,6 +1992,70 @@ extern "C" int er_k_gemv_form(const er_k_gemv_form_args* f, void* stream) {
     return f->w_half ? gemv_form_t<_Float16>(*f, proj, (hipStream_t)stream) : gemv_form_t<float>(*f, proj, (hipStream_t)stream);
 }
 
+// ---- fp8 mode on caller-owned operands: the row quantiser of the weight loader, and the byte kernels behind the row forms.
+extern "C" int er_k_w8_quantize(const void* src, int dtype, int on_device, int n, int k, void* q_dev, int32_t* e_dev, void* w16_dev,
+                                float* wscale_dev, void* stream) {
+    if (!src || n < 1 || k < 1) return fail(ER_ERR_INVALID, "er_k_w8_quantize: bad argument");
+    if (dtype != ER_F32 && dtype != ER_F16 && dtype != ER_BF16) return fail(ER_ERR_INVALID, "er_k_w8_quantize: dtype %d", dtype);
+    hipStream_t st = (hipStream_t)stream;
+    DevBuf<char> stage;
+    DevBuf<int> bad;
+    ERCHK(bad.ensure(1));
+    if (!on_device) {
+        const size_t bytes = (size_t)n * k * (dtype == ER_F32 ? 4 : 2);
+        ERCHK(stage.ensure((bytes + 3) / 4 * 4));
+        HIPCHK(hipMemcpy(stage.p, src, bytes, hipMemcpyHostToDevice));
+        src = stage.p;
+    }
+    HIPCHK(hipMemsetAsync(bad.p, 0, sizeof(int), st));
+    hipLaunchKernelGGL(quant_rows_kernel, dim3((unsigned)n), dim3(ER_WG), 0, st, src, dtype, (size_t)k, (float*)nullptr, (_Float16*)w16_dev,
+                       (unsigned char*)q_dev, wscale_dev, (int*)e_dev, bad.p);
+    hipError_t e = hipGetLastError();
+    hipError_t e2 = hipStreamSynchronize(st);
+    HIPRET(e);
+    HIPRET(e2);
+    int flag = 0;
+    HIPCHK(hipMemcpy(&flag, bad.p, sizeof(int), hipMemcpyDeviceToHost));
+    if (flag) return fail(ER_ERR_INVALID, "er_k_w8_quantize: the matrix holds a NaN or an infinity");
+    return ER_OK;
+}
+
+// the byte block the kernels stream (k_gemv.h w8_scales) from a caller's separate bytes [n][k] and scales [n]
+static int w8_block_of(DevBuf<char>& blk, const void* q_dev, const float* wscale_dev, int n, int k, hipStream_t st) {
+    if ((size_t)n * k % 4) return fail(ER_ERR_INVALID, "w8: n * k must be a multiple of 4");
+    ERCHK(blk.ensure(w8_block_bytes(n, k)));
+    HIPCHK(hipMemcpyAsync(blk.p, q_dev, (size_t)n * k, hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipMemcpyAsync(blk.p + (size_t)n * k, wscale_dev, (size_t)n * sizeof(float), hipMemcpyDeviceToDevice, st));
+    return 0;
+}
+
+// er_k_gemv_form's checks and launch table on (bytes, wscale): the fp16 row shapes of qkv, out_proj, fc1 and fc2.  args->w is not read.
+extern "C" int er_k_gemv_form_w8(const er_k_gemv_form_args* f, const void* q_dev, const float* wscale_dev, void* stream) {
+    if (!f || !q_dev || !wscale_dev) return fail(ER_ERR_INVALID, "er_k_gemv_form_w8: null argument");
+    er_k_gemv_form_args g = *f;
+    g.w = q_dev;
+    if (!g.w_half) return fail(ER_ERR_UNSUPPORTED, "er_k_gemv_form_w8: the bytes run the fp16 row shapes (set w_half)");
+    if (g.form != ER_FORM_ROW) return fail(ER_ERR_UNSUPPORTED, "er_k_gemv_form_w8: only the row forms stream bytes (form %d)", g.form);
+    Proj proj = PROJ_QKV;
+    ERCHK(gemv_form_check(g, &proj));
+    if (proj == PROJ_HEAD) return fail(ER_ERR_UNSUPPORTED, "er_k_gemv_form_w8: the lm_head is not quantised");
+    hipStream_t st = (hipStream_t)stream;
+    DevBuf<char> blk;
+    ERCHK(w8_block_of(blk, q_dev, wscale_dev, g.n, g.k, st));
+    GemvArgs a{};
+    a.W = blk.p; a.bias = g.bias; a.N = g.n; a.xin = g.x; a.ln_w = g.ln_w; a.ln_b = g.ln_b; a.eps = g.eps; a.hout = g.xnorm_out;
+    a.embd = g.embd; a.posemb = g.posemb; a.tok = g.tok; a.pos = g.pos;
+    a.out = g.y; a.resid = g.resid; a.q = g.q_out; a.kcache = g.kcache; a.vcache = g.vcache; a.kv_half = g.kv_half ? 1 : 0;
+    a.hidden = proj == PROJ_QKV ? g.heads * g.head_dim : 1536; a.head_dim = g.head_dim; a.l_cap = g.l_cap;
+    a.kv_bstride = (long long)g.heads * g.l_cap * g.head_dim;
+    const int pro = g.prologue == ER_PRO_NONE ? PRO_NONE : g.prologue == ER_PRO_EMBED ? PRO_EMBED : PRO_LN;
+    hipError_t e = launch_proj<w8_t>(proj, ProjForm{g.form, g.nw, g.rw, false}, pro, a, g.batch, g.k, SkPart{nullptr, 0}, st);
+    hipError_t e2 = hipStreamSynchronize(st);
+    HIPRET(e);
+    HIPRET(e2);
+    return ER_OK;
+}
+
 // ---- the fused single-row MLP on caller-owned operands.  er_k_mlp_transpose makes the k-major copy the decode context keeps per
 // layer; er_k_mlp_sparse enqueues one layer's two launches and returns - it allocates nothing and does not synchronise, so a caller
 // can capture it into a graph.
@@ -2004,8 +2090,9 @@ extern "C" int er_mlp_nnz(er_ctx* c, int32_t* out, int n) {
     return ER_OK;
 }
 
-extern "C" int er_k_attn_outproj3(const float* q, const void* k, const void* v, int len, const void* wo, const float* bo,
-                                  const float* resid, float* y, int l_cap, int kv_half, int w_half, void* stream) {
+// wscale: wo is e4m3 bytes with these row scales (er_k_attn_outproj3_w8); otherwise fp32 or (w_half) fp16
+static int attn_outproj3_entry(const float* q, const void* k, const void* v, int len, const void* wo, const float* wscale, const float* bo,
+                               const float* resid, float* y, int l_cap, int kv_half, int w_half, void* stream) {
     // version 3 of the single-row decode attention: balanced chunks (16 heads x 16 chunks) + the merge fused into out_proj
     constexpr int H = 16, D = 96;
     if (len <= 0 || len > l_cap || !attn3_fits(l_cap, H)) return fail(ER_ERR_CAPACITY, "er_k_attn_outproj3: len %d / l_cap %d (<= %d)", len, l_cap, attn3_num_chunks(H) * ATTN3_CAP);
@@ -2014,16 +2101,34 @@ extern "C" int er_k_attn_outproj3(const float* q, const void* k, const void* v, 
     DevBuf<float> blk;                         // partial outputs, then their {m, l}
     ERCHK(blk.ensure((size_t)H * nch * (D + 2)));
     float *part = blk.p, *part_ml = part + (size_t)H * nch * D;
+    DevBuf<char> wblk;                         // allocated and filled in front of the first launch
+    if (wscale) {
+        ERCHK(w8_block_of(wblk, wo, wscale, H * D, H * D, st));
+        wo = wblk.p;
+    }
     AttnDecArgs a = attn_dec_args(H, D, l_cap);
     a.q = q; a.kcache = k; a.vcache = v; a.fixed_len = len; a.part = part; a.part_ml = part_ml;
     hipError_t e = launch_attn_partial3_d<D>(a, kv_half != 0, nch, 1, st);
     OutMergeArgs m{};
     m.W = wo; m.bias = bo; m.resid = resid; m.out = y; m.part_o = part; m.part_ml = part_ml; m.N = H * D;
-    if (e == hipSuccess) e = w_half ? launch_outproj_merge<_Float16, D>(m, nch, st) : launch_outproj_merge<float, D>(m, nch, st);
+    if (e == hipSuccess)
+        e = wscale ? launch_outproj_merge<w8_t, D>(m, nch, st)
+                   : w_half ? launch_outproj_merge<_Float16, D>(m, nch, st) : launch_outproj_merge<float, D>(m, nch, st);
     hipError_t e2 = hipStreamSynchronize(st);
     HIPRET(e);
     HIPRET(e2);
     return ER_OK;
+}
+
+extern "C" int er_k_attn_outproj3(const float* q, const void* k, const void* v, int len, const void* wo, const float* bo,
+                                  const float* resid, float* y, int l_cap, int kv_half, int w_half, void* stream) {
+    return attn_outproj3_entry(q, k, v, len, wo, nullptr, bo, resid, y, l_cap, kv_half, w_half, stream);
+}
+
+extern "C" int er_k_attn_outproj3_w8(const float* q, const void* k, const void* v, int len, const void* wo_q, const float* wo_scale,
+                                     const float* bo, const float* resid, float* y, int l_cap, int kv_half, void* stream) {
+    if (!wo_q || !wo_scale) return fail(ER_ERR_INVALID, "er_k_attn_outproj3_w8: null weights");
+    return attn_outproj3_entry(q, k, v, len, wo_q, wo_scale, bo, resid, y, l_cap, kv_half, 0, stream);
 }
 
 extern "C" int er_k_gemm(const float* a, const float* b, const float* bias, const float* resid, float* cc, int m, int n, int k,

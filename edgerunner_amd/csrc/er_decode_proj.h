@@ -118,9 +118,29 @@ static hipError_t prep_rows(const GemvArgs& a, int B, hipStream_t st) {
 // three); pro names the prologue FUSED into the qkv row kernel (PRO_LN, or PRO_EMBED for layer 0; fc1 and lm_head always fuse PRO_LN).
 // Shapes: qkv 4608 rows = 192 VALU workgroups x 24 (one round) or 144 matrix-core tiles of 32; fc1 6144 rows = 256 x 24 or 192 tiles;
 // fc2 48 tiles x 4 (narrow: 16) K-ranges.  The XT kernels exist for fp16 weights only: their forms are compiled out for float.
+//
+// fp8 context (w8 = the byte block of the same matrix, k_gemv.h w8_scales; WT = _Float16 and a.W = the fp16 copy of the dequantised
+// values): a row form of a projection that w8_streams() names runs the same (waves x rows) shape of the byte kernel on w8; every other
+// form, and the lm_head, runs the fp16 copy as in fast mode.  The byte type has the fp16 row shapes and nothing else.
+
+// Which projections of an fp8 context stream bytes in their row forms at B rows.  Measured in situ against the fp16 forms of the same
+// build in the same session (profiles/w8_bench.json): a projection streams bytes only where its byte form is faster
+// by more than the run-to-run spread of the fp16 runs.  qkv, fc1 and fc2 are at B = 1, 2 and 4; out_proj is at B = 1 (the fused merge
+// launch) and 2, and is not at B = 4 (4.10 against 4.15 us, spread 0.18) - B = 3 was not measured and goes with 4.
+constexpr bool w8_streams(Proj proj, int B) {
+    return proj == PROJ_QKV || proj == PROJ_FC1 || proj == PROJ_FC2 || (proj == PROJ_OUT && B <= 2);
+}
+
 template <typename WT>
-static hipError_t launch_proj(Proj proj, const ProjForm& f, int pro, const GemvArgs& a, int B, int K, SkPart sk, hipStream_t st) {
-    constexpr bool HALF = sizeof(WT) == 2;
+static hipError_t launch_proj(Proj proj, const ProjForm& f, int pro, const GemvArgs& a, int B, int K, SkPart sk, hipStream_t st, const void* w8 = nullptr) {
+    constexpr bool W8 = sizeof(WT) == 1, HALF = sizeof(WT) <= 2;
+    if constexpr (sizeof(WT) == 2) {
+        if (w8 && f.form == ER_FORM_ROW && w8_streams(proj, B)) {
+            GemvArgs b = a;
+            b.W = w8;
+            return launch_proj<w8_t>(proj, f, pro, b, B, K, sk, st);
+        }
+    }
     switch (f.form) {
         case ER_FORM_ROW:
             switch (proj) {
@@ -142,9 +162,15 @@ static hipError_t launch_proj(Proj proj, const ProjForm& f, int pro, const GemvA
                         }
                     }
                     return gemv_groups<WT, 4, 2, PRO_NONE, EPI_RESID>(a, B, K, st);
-                case PROJ_HEAD: return gemv_groups<WT, 1, 1, PRO_LN, EPI_STORE>(a, B, K, st);
+                case PROJ_HEAD:
+                    if constexpr (!W8) return gemv_groups<WT, 1, 1, PRO_LN, EPI_STORE>(a, B, K, st);
+                    break;
             }
             break;
+        default: break;
+    }
+    if constexpr (!W8) switch (f.form) {      // the batched forms (never instantiated for the bytes)
+        case ER_FORM_ROW: break;
         case ER_FORM_ROWS8:
             if (proj == PROJ_OUT) return gemv_outproj_rows8<WT>(a, B, st);
             break;
@@ -205,6 +231,7 @@ struct ProjIo {
     const void* w_tiled = nullptr;    // the weights as the matrix-core forms stream them (tile_weights_kernel)
     const void* x_image = nullptr;    // the input as the tiled-input forms read it
     void* out_image = nullptr;        // fc1, ER_FORM_MFMA_XT: the tiled image of the output
+    const void* w8 = nullptr;         // fp8 context: the byte block of the same matrix (launch_proj decides who streams it)
 };
 
 // (projection, form) -> launches: the prologue launch of a batched form, the operands the form reads, launch_proj.
@@ -217,7 +244,7 @@ static hipError_t run_proj(Proj proj, const ProjForm& f, const ProjIo& io, GemvA
     if (form_mfma(f.form)) a.W = io.w_tiled;
     if (form_tiled_in(f.form)) a.xin = (const float*)io.x_image;
     if (f.form == ER_FORM_MFMA_XT && proj == PROJ_FC1) a.xt_out = io.out_image;
-    return launch_proj<WT>(proj, f, io.pro, a, B, K, sk, st);
+    return launch_proj<WT>(proj, f, io.pro, a, B, K, sk, st, io.w8);
 }
 
 }   // namespace er

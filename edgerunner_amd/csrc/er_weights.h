@@ -9,6 +9,9 @@ struct WeightEntry {
     size_t cols = 0, pitch = 0;   // rows of `cols` values stored `pitch` apart (pitch > cols: zero-padded rows)
     bool f16 = false;             // fp16 mode: keep an fp16 copy (WeightTable::half_of); the fp32 block holds the same rounded values
     _Float16** dst16 = nullptr;   // ... and publish it here too (nullable)
+    bool q8 = false;              // fp8 mode: quantised by row (er_w8.h) - a byte block [rows][cols] e4m3 + [rows] 2^e (WeightTable::q8_of,
+    unsigned char** dstq = nullptr;   // k_gemv.h w8_scales), published here; the fp16 copy and the fp32 block then hold the dequantised values
+    size_t qcols = 0;             // ... values per quantised row
     bool loaded = false;
 
     // [off, off + n) of a fused block of `total` elements (q / k / v of one layer)
@@ -16,14 +19,18 @@ struct WeightEntry {
     // rows of kin values stored zero-padded to kpad columns, so that a GEMM's K is a whole number of tiles
     WeightEntry& pad(size_t kin, size_t kpad) { cols = kin; pitch = kpad; total = n / kin * kpad; return *this; }
     WeightEntry& half(_Float16** p = nullptr) { f16 = true; dst16 = p; return *this; }
+    WeightEntry& rows8(unsigned char** q, size_t in) { q8 = true; dstq = q; qcols = in; return *this; }      // rows of `in` values ([out][in])
 };
 
 struct WeightTable {
     std::map<std::string, WeightEntry> keys;
     std::map<const float*, _Float16*> half_of;   // fp32 block -> its fp16 copy (fp16 mode, entries with half())
     std::vector<DevBuf<char>> owned;             // every weight block (derived copies included); the entries and weight structs hold views
+    std::map<const float*, unsigned char*> q8_of;   // fp32 block -> its byte block (fp8 mode, entries with rows8())
     DevBuf<char> stage;                          // upload of one host tensor: grow-only, freed by weights_finalize
+    DevBuf<int> bad;                             // fp8 mode: the quantiser's "non-finite source value" flag
     bool fp16 = false;
+    bool w8 = false;                             // fp8 mode (implies fp16: every other tensor is stored as fast mode stores it)
 
     // a block of n T that lives as long as the table
     template <typename T>
@@ -70,6 +77,43 @@ __global__ void cvt_weights_kernel(const void* src, int dtype, float* dst32, _Fl
     }
 }
 
+// Row-wise e4m3 quantiser (er_w8.h): one workgroup per row of `cols` source values.  Row maximum -> exponent e -> bytes q, wscale = 2^e,
+// and the dequantised values q * 2^e as fp16 and fp32 (both exact).  Every output pointer is nullable; eout takes e itself.  A NaN or
+// an infinity anywhere in the source raises *bad (the row's outputs are then meaningless).  Rows are independent, so the three slices
+// of a fused q / k / v block are quantised by three calls on their own row ranges.
+__global__ __launch_bounds__(ER_WG) void quant_rows_kernel(const void* src, int dtype, size_t cols, float* dst32, _Float16* dst16,
+                                                          unsigned char* q, float* wscale, int* eout, int* bad) {
+    __shared__ float red[ER_NWAVES];
+    const size_t base = (size_t)blockIdx.x * cols;
+    const int tid = threadIdx.x;
+    float amax = 0.f;
+    bool finite = true;
+    for (size_t k = tid; k < cols; k += ER_WG) {
+        const float a = fabsf(raw_to_f32(src, dtype, base + k));
+        finite = finite && a <= 3.402823466e38f;      // false for NaN and infinity
+        amax = fmaxf(amax, a);
+    }
+    if (!finite) *bad = 1;
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) amax = fmaxf(amax, __shfl_xor(amax, m, 64));
+    if ((tid & 63) == 0) red[tid >> 6] = amax;
+    __syncthreads();
+    amax = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+    const int e = w8_row_exponent(amax);
+    const float up = w8_pow2(e), down = w8_pow2(-e);      // both exact powers of two
+    if (tid == 0) {
+        if (wscale) wscale[blockIdx.x] = up;
+        if (eout) eout[blockIdx.x] = e;
+    }
+    for (size_t k = tid; k < cols; k += ER_WG) {
+        const unsigned char c = w8_encode(raw_to_f32(src, dtype, base + k) * down);
+        const float v = w8_decode(c) * up;
+        if (q) q[base + k] = c;
+        if (dst16) dst16[base + k] = (_Float16)v;
+        if (dst32) dst32[base + k] = v;
+    }
+}
+
 template <typename T>
 static int weights_alloc(WeightTable& t, T** p, size_t n) {   // once per block, zeroed
     if (*p) return 0;
@@ -104,6 +148,27 @@ static int weights_load(WeightTable& t, hipStream_t st, const char* who, const s
         ERCHK(weights_alloc(t, &hb, e.total));
         if (e.dst16) *e.dst16 = hb;
         h = hb + e.off;
+    }
+    if (t.w8 && e.q8) {      // rows of e.cols values, unpadded: bytes + row scales, the fp16 and fp32 blocks get the dequantised values
+        const size_t qc = e.qcols;
+        if (!h || e.cols != e.pitch || !qc || e.n % qc || e.off % qc || e.total % qc) return fail(ER_ERR_INVALID, "%s(%s): not a row-quantised matrix", who, key.c_str());
+        unsigned char*& qb = t.q8_of[*e.dst];
+        const size_t rows = e.total / qc;
+        ERCHK(weights_alloc(t, &qb, w8_block_bytes(rows, qc)));
+        if (e.dstq) *e.dstq = qb;
+        float* wscale = const_cast<float*>(w8_scales(qb, (long long)rows, (long long)qc));
+        ERCHK(t.bad.ensure(1));
+        e.loaded = false;                 // until the new values are known to be finite: a refused reload leaves the key unloaded
+        HIPCHK(hipMemsetAsync(t.bad.p, 0, sizeof(int), st));
+        hipLaunchKernelGGL(quant_rows_kernel, dim3((unsigned)(e.n / qc)), dim3(ER_WG), 0, st, src, dtype, qc, *e.dst + e.off, h, qb + e.off,
+                           wscale + e.off / qc, (int*)nullptr, t.bad.p);
+        HIPCHK(hipGetLastError());
+        int bad = 0;
+        HIPCHK(hipMemcpyAsync(&bad, t.bad.p, sizeof(int), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        if (bad) return fail(ER_ERR_INVALID, "%s(%s): the tensor holds a NaN or an infinity; fp8 rows are quantised from finite values only", who, key.c_str());
+        e.loaded = true;
+        return 0;
     }
     const unsigned grid = (unsigned)std::min<size_t>((n + 255) / 256, 4096);
     hipLaunchKernelGGL(cvt_weights_kernel, dim3(grid), dim3(256), 0, st, src, dtype, *e.dst + e.off, h, n, e.cols, e.pitch);

@@ -1,5 +1,6 @@
 // Weight-streaming GEMV for the decode step (batch 1..4 rows per pass; 16 per pass in the batched
-// variant below); weights fp32 (exact mode) or fp16 (fast mode), fp32 accumulate.
+// variant below); weights fp32 (exact mode), fp16 (fast mode) or - the row kernel only - e4m3 bytes with a power-of-two scale per row
+// (fp8 mode, er_w8.h), fp32 accumulate.
 //
 // Replaces the per-token nn.Linear calls of the reference decoder
 // (core/transformer/modeling_opt.py:185,189-190 q/k/v, :232 out_proj, :281 fc1,
@@ -19,6 +20,7 @@
 // a workgroup split K and combine through LDS.
 #pragma once
 #include "er_common.h"
+#include "er_w8.h"
 
 namespace er {
 
@@ -82,12 +84,22 @@ __device__ __forceinline__ xt_h8 xt_pack(float x0, float x1, float x2, float x3)
     return r;
 }
 
-// Weight storage types: fp32 (exact mode) or fp16 (fast mode, fp32 accumulate).  One 16-byte load
-// carries EPL weights; the matching EPL inputs are EPL/4 consecutive float4.
+// Weight storage types: fp32 (exact mode), fp16 (fast mode, fp32 accumulate) or e4m3 bytes with a power-of-two scale per row (fp8
+// mode, er_w8.h; the row kernels only).  One load of a lane (16 bytes; 8 for the bytes) carries EPL weights; the matching EPL inputs
+// are EPL/4 consecutive float4.  The byte type keeps fp16's lane -> element map (load j of a lane = elements (j * 64 + lane) * 8 .. + 8)
+// and its fmaf chain, so that acc * 2^e is the fp16 kernel's accumulator on the dequantised matrix, bit for bit.
+// A byte matrix [N][K] is ONE block: the N * K bytes, then wscale[N] = 2^e as fp32 (w8_scales) - the kernels keep their argument lists.
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+typedef unsigned char w8_t;
 template <typename WT> struct WTraits;
-template <> struct WTraits<float> { static constexpr int EPL = 4; };
-template <> struct WTraits<_Float16> { static constexpr int EPL = 8; };
+template <> struct WTraits<float> { static constexpr int EPL = 4; typedef f32x4 Load; };
+template <> struct WTraits<_Float16> { static constexpr int EPL = 8; typedef f32x4 Load; };
+template <> struct WTraits<w8_t> { static constexpr int EPL = 8; typedef er_u32x2 Load; };
+
+__host__ __device__ __forceinline__ size_t w8_block_bytes(size_t n, size_t k) { return n * k + n * sizeof(float); }      // n * k is a multiple of 4
+__host__ __device__ __forceinline__ const float* w8_scales(const void* w, long long n, long long k) {
+    return reinterpret_cast<const float*>(reinterpret_cast<const unsigned char*>(w) + n * k);
+}
 
 template <typename WT>
 __device__ __forceinline__ float dot_w(const f32x4& wraw, const f32x4* x, float s) {
@@ -101,6 +113,18 @@ __device__ __forceinline__ float dot_w(const f32x4& wraw, const f32x4* x, float 
         s = fmaf((float)h[6], x[1].z, s); s = fmaf((float)h[7], x[1].w, s);
         return s;
     }
+}
+
+// eight e4m3 bytes (element k of the load in byte k) against two float4 of the input: dot_w<_Float16>'s chain, element for element
+__device__ __forceinline__ float dot_w8(const er_u32x2& wraw, const f32x4* x, float s) {
+    typedef float f32x2 __attribute__((ext_vector_type(2)));
+    const f32x2 w01 = __builtin_amdgcn_cvt_pk_f32_fp8((int)wraw.x, false), w23 = __builtin_amdgcn_cvt_pk_f32_fp8((int)wraw.x, true);
+    const f32x2 w45 = __builtin_amdgcn_cvt_pk_f32_fp8((int)wraw.y, false), w67 = __builtin_amdgcn_cvt_pk_f32_fp8((int)wraw.y, true);
+    s = fmaf(w01.x, x[0].x, s); s = fmaf(w01.y, x[0].y, s);
+    s = fmaf(w23.x, x[0].z, s); s = fmaf(w23.y, x[0].w, s);
+    s = fmaf(w45.x, x[1].x, s); s = fmaf(w45.y, x[1].y, s);
+    s = fmaf(w67.x, x[1].z, s); s = fmaf(w67.y, x[1].w, s);
+    return s;
 }
 
 // bias / residual / cache position are fetched at kernel entry (EpiPre) and the destination ADDRESS is finished there too, so that
@@ -192,6 +216,8 @@ __global__ __launch_bounds__(64 * NW) void gemv_kernel(const void* pW, const flo
     constexpr int TPB = 64 * NW;
     constexpr int EPL = WTraits<WT>::EPL, XV = EPL / 4, SL = 1536, J = SL / (64 * EPL);
     constexpr int K = KS * SL;
+    constexpr bool W8 = sizeof(WT) == 1;       // e4m3 bytes: the accumulator times wscale[n] after the reduction and the split-K combine, in front of the bias
+    typedef typename WTraits<WT>::Load WLoad;
     // the prologue (LayerNorm / embedding) always runs on at most 4 waves with the 256-thread element mapping and reduction
     // order, so a 6-wave workgroup (768 qkv workgroups = 3 per CU) produces bit-identical inputs; waves 4 and 5 only take
     // part in its barriers
@@ -242,15 +268,25 @@ __global__ __launch_bounds__(64 * NW) void gemv_kernel(const void* pW, const flo
         const int t = min(tid, RW * NB - 1);
         pre[0][0] = gemv_epi_loads<EPI>(a, row0 + t / NB, t % NB);
     }
+    float ws[RW];                              // fp8 rows: the scale of every row this thread will finish (a small operand like the bias)
+    if constexpr (W8) {
+        const float* wscale = w8_scales(a.W, a.N, K);
+        if (KS == 1) {
+#pragma unroll
+            for (int r = 0; r < RW; ++r) ws[r] = wscale[min(row0 + r, a.N - 1)];
+        } else {
+            ws[0] = wscale[min(row0 + min(tid, RW * NB - 1) / NB, a.N - 1)];
+        }
+    }
     // (Round 3 shipped, unmeasured, a variant that loaded PRO_NONE's input slice HERE, in front of the weight stream; measured in
     // round 4 it made fc2 SLOWER - 8.10 vs 7.97 us, profiles/r04_ab_b5b758c_and_om_rpw.log - the six extra 16-byte loads per lane delay
     // the first weight request of every wave by more than the L2 round trip they take off the tail.  The input is read in the main
     // loop again.)
-    f32x4 w[RW][J];
+    WLoad w[RW][J];
 #pragma unroll
     for (int r = 0; r < RW; ++r) {
         const int row = min(row0 + r, a.N - 1);            // clamp: out-of-range rows are loaded but never stored
-        const f32x4* wr = reinterpret_cast<const f32x4*>(reinterpret_cast<const WT*>(a.W) + (long long)row * K + slice * SL);
+        const WLoad* wr = reinterpret_cast<const WLoad*>(reinterpret_cast<const WT*>(a.W) + (long long)row * K + slice * SL);
 #pragma unroll
         for (int j = 0; j < J; ++j) w[r][j] = __builtin_nontemporal_load(wr + j * 64 + lane);
     }
@@ -334,7 +370,10 @@ __global__ __launch_bounds__(64 * NW) void gemv_kernel(const void* pW, const flo
         for (int r = 0; r < RW; ++r) {
             float s = 0.f;
 #pragma unroll
-            for (int j = 0; j < J; ++j) s = dot_w<WT>(w[r][j], &xr[j * XV], s);
+            for (int j = 0; j < J; ++j) {
+                if constexpr (W8) s = dot_w8(w[r][j], &xr[j * XV], s);
+                else s = dot_w<WT>(w[r][j], &xr[j * XV], s);
+            }
             acc[r][b] = wave_sum(s);
         }
     }
@@ -345,7 +384,10 @@ __global__ __launch_bounds__(64 * NW) void gemv_kernel(const void* pW, const flo
             for (int r = 0; r < RW; ++r)
                 if (row0 + r < a.N) {
 #pragma unroll
-                    for (int b = 0; b < NB; ++b) gemv_epilogue<EPI>(a, row0 + r, b, acc[r][b], pre[r][b]);
+                    for (int b = 0; b < NB; ++b) {
+                        if constexpr (W8) acc[r][b] *= ws[r];
+                        gemv_epilogue<EPI>(a, row0 + r, b, acc[r][b], pre[r][b]);
+                    }
                 }
         }
     } else {
@@ -361,6 +403,7 @@ __global__ __launch_bounds__(64 * NW) void gemv_kernel(const void* pW, const flo
             float s = 0.f;
 #pragma unroll
             for (int k = 0; k < KS; ++k) s += red[tid * KS + k];
+            if constexpr (W8) s *= ws[0];
             if (row0 + r < a.N) gemv_epilogue<EPI>(a, row0 + r, b, s, pre[0][0]);
         }
     }

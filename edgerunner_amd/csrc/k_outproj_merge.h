@@ -41,6 +41,8 @@ __global__ __launch_bounds__(OM_THREADS) void outproj_merge_kernel(const void* p
     OutMergeArgs a;
     a.W = pW; a.bias = pbias; a.resid = presid; a.part_o = ppart_o; a.part_ml = ppart_ml; a.out = pout; a.N = pN;
     constexpr int EPL = WTraits<WT>::EPL, XV = EPL / 4, K = 1536, J = K / (64 * EPL);
+    constexpr bool W8 = sizeof(WT) == 1;      // e4m3 bytes + row scales behind them (k_gemv.h w8_scales): the reduced sum times 2^e in front of the bias
+    typedef typename WTraits<WT>::Load WLoad;
     constexpr int C4 = D / 4;                 // float4 columns per head (24)
     static_assert(D == 96 && NCH <= 32 && C4 <= 32 && K == 16 * D, "two 96-wide heads per wave, 16 heads");
     __shared__ __attribute__((aligned(16))) float xs[K];
@@ -52,13 +54,15 @@ __global__ __launch_bounds__(OM_THREADS) void outproj_merge_kernel(const void* p
     // ---- loads, in consumer order
     const float bias = a.bias ? a.bias[row] : 0.f;
     const float resid = a.resid[row];
+    float ws = 1.f;
+    if constexpr (W8) ws = w8_scales(a.W, a.N, K)[row];
     const int sl = min(li, NCH - 1);
     const float2 ml = *reinterpret_cast<const float2*>(a.part_ml + ((long long)head * NCH + sl) * 2);
     const int c4 = min(li, C4 - 1);           // lanes 24..31 of a half re-read column 23 (never stored)
     const f32x4* pcol = reinterpret_cast<const f32x4*>(a.part_o + (long long)head * NCH * D) + c4;
     f32x4 pv[NCH];
-    f32x4 w[J];
-    const f32x4* wr = reinterpret_cast<const f32x4*>(reinterpret_cast<const WT*>(a.W) + (long long)row * K);
+    WLoad w[J];
+    const WLoad* wr = reinterpret_cast<const WLoad*>(reinterpret_cast<const WT*>(a.W) + (long long)row * K);
 #pragma unroll
     for (int s = 0; s < NCH; ++s) pv[s] = pcol[s * C4];
     // (the weight row issued FIRST - its HBM round trip started before the address unit has worked through the 8 x 17 partial loads -
@@ -100,9 +104,11 @@ __global__ __launch_bounds__(OM_THREADS) void outproj_merge_kernel(const void* p
         f32x4 x[XV];
 #pragma unroll
         for (int u = 0; u < XV; ++u) x[u] = reinterpret_cast<const f32x4*>(xs)[(j * 64 + lane) * XV + u];
-        s = dot_w<WT>(w[j], x, s);
+        if constexpr (W8) s = dot_w8(w[j], x, s);
+        else s = dot_w<WT>(w[j], x, s);
     }
     s = wave_sum(s);
+    if constexpr (W8) s *= ws;
     if (lane == 0 && wid < OM_ROWS) a.out[row] = (s + bias) + resid;
 }
 

@@ -71,7 +71,7 @@ def _i32_dev(values, device, hi, what):
 
 
 def gemv_form(form, epilogue, w, B, *, x=None, bias=None, ln=None, embed=None, sk=None, resid=None, qkv=None, nw=4, rw=1, eps=1e-5,
-              n=None, k=None, w_half=None, return_xnorm=False, prep_xt=False, prep_xt_image=None, xt_out_image=None):
+              n=None, k=None, w_half=None, return_xnorm=False, prep_xt=False, prep_xt_image=None, xt_out_image=None, w8=None):
     """One decode projection in one of the forms the decode step launches it in (``er_k_gemv_form``; native.ER_FORM_* / ER_EPI_*).
     w [n, k] fp32 or fp16 (None with ER_FORM_PREP).  The prologue is chosen by what is given:
       ln=(ln_w, ln_b) with x [B, k]            LayerNorm rows
@@ -81,12 +81,16 @@ def gemv_form(form, epilogue, w, B, *, x=None, bias=None, ln=None, embed=None, s
     qkv=(kcache, vcache, pos[, q_out]) for ER_EPI_QKV: caches [B, heads, l_cap, head_dim] fp32 or fp16 are written in place at
     pos[b].  prep_xt: also return the image the batched prologue launch writes (prep_xt_image: write into this one);
     xt_out_image: the image the tiled fc1 writes (allocated zeroed when the form needs one).
+    w8=(q uint8 [n, k], wscale fp32 [n]): the row form on e4m3 bytes and row scales in place of w (``er_k_gemv_form_w8``; gemv_form_w8).
     Returns a dict: y, xnorm, q, part (ER_FORM_NARROW_DEFER: [groups, k / 384 * 32 * n] raw block), prep_xt, xt_out - those the call produced."""
     lib = native.load_library()
     dev = (x if x is not None else (embed[0] if embed is not None else sk[0])).device
     if w is not None:
         n, k = w.shape
         w_half = w.dtype == torch.float16
+    if w8 is not None:
+        assert w is None and w8[0].dtype == torch.uint8 and w8[1].dtype == torch.float32 and w8[1].numel() == w8[0].shape[0]
+        (n, k), w_half = w8[0].shape, True
     a = native.ErKGemvFormArgs()
     keep = [w, x, bias, resid]
     a.w, a.bias, a.x, a.resid = (native.ptr(t).value for t in (w, bias, x, resid))
@@ -142,9 +146,37 @@ def gemv_form(form, epilogue, w, B, *, x=None, bias=None, ln=None, embed=None, s
     elif form != native.ER_FORM_PREP:
         out["y"] = torch.empty((B, n), dtype=torch.float32, device=dev)
         a.y = native.ptr(out["y"]).value
-    native.check(lib.er_k_gemv_form(C.byref(a), _st()), "er_k_gemv_form")
+    if w8 is not None:
+        native.check(lib.er_k_gemv_form_w8(C.byref(a), native.ptr(w8[0]), native.ptr(w8[1]), _st()), "er_k_gemv_form_w8")
+    else:
+        native.check(lib.er_k_gemv_form(C.byref(a), _st()), "er_k_gemv_form")
     del keep
     return out
+
+
+def gemv_form_w8(form, epilogue, q, wscale, B, **kw):
+    """``gemv_form`` on the e4m3 bytes q [n, k] (uint8) and row scales wscale [n] of fp8 mode: the fp16 row shapes of qkv, out_proj,
+    fc1 and fc2, bit-identical to ``gemv_form`` on the fp16 matrix q * wscale."""
+    return gemv_form(form, epilogue, None, B, w8=(q, wscale), **kw)
+
+
+_W8_SRC = {torch.float32: native.ER_F32, torch.float16: native.ER_F16, torch.bfloat16: native.ER_BF16}
+
+
+def w8_quantize(w, device=None):
+    """The fp8 weight loader's row quantiser on a matrix w [n, k] (fp32 / fp16 / bf16, host or device memory; ``er_k_w8_quantize``):
+    returns (q uint8 [n, k], e int32 [n], w16 fp16 [n, k] = q * 2^e, wscale fp32 [n] = 2^e) on the device.  Raises on NaN / infinity."""
+    assert w.dim() == 2 and w.dtype in _W8_SRC
+    w = w.contiguous()
+    dev = torch.device(device) if device is not None else (w.device if w.is_cuda else torch.device("cuda", torch.cuda.current_device()))
+    n, k = w.shape
+    q = torch.empty((n, k), dtype=torch.uint8, device=dev)
+    e = torch.empty((n,), dtype=torch.int32, device=dev)
+    w16 = torch.empty((n, k), dtype=torch.float16, device=dev)
+    ws = torch.empty((n,), dtype=torch.float32, device=dev)
+    native.check(native.load_library().er_k_w8_quantize(native.ptr(w), _W8_SRC[w.dtype], 1 if w.is_cuda else 0, n, k, native.ptr(q), native.ptr(e),
+                                                        native.ptr(w16), native.ptr(ws), _st()), "er_k_w8_quantize")
+    return q, e, w16, ws
 
 
 def mlp_transpose(w2):
@@ -216,6 +248,18 @@ def attn_outproj3(q, k_cache, v_cache, length, wo, bo, resid):
                                         native.ptr(bo), native.ptr(resid), native.ptr(y), Lcap,
                                         int(k_cache.dtype == torch.float16), int(wo.dtype == torch.float16), _st()),
                  "er_k_attn_outproj3")
+    return y
+
+
+def attn_outproj3_w8(q, k_cache, v_cache, length, wo_q, wo_scale, bo, resid):
+    """``attn_outproj3`` with Wo as e4m3 bytes [1536, 1536] (uint8) and row scales [1536] (``er_k_attn_outproj3_w8``)."""
+    lib = native.load_library()
+    H, Lcap, D = k_cache.shape
+    assert (H, D) == (16, 96) and wo_q.dtype == torch.uint8 and wo_q.shape == (H * D, H * D) and wo_scale.dtype == torch.float32 and wo_scale.numel() == H * D
+    y = torch.empty((H * D,), dtype=torch.float32, device=q.device)
+    native.check(lib.er_k_attn_outproj3_w8(native.ptr(q), native.ptr(k_cache), native.ptr(v_cache), int(length), native.ptr(wo_q),
+                                           native.ptr(wo_scale), native.ptr(bo), native.ptr(resid), native.ptr(y), Lcap,
+                                           int(k_cache.dtype == torch.float16), _st()), "er_k_attn_outproj3_w8")
     return y
 
 

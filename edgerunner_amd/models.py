@@ -81,7 +81,7 @@ class _QueueEngine:
         # the prefill pick their kernel by the row count of the pass, so only a one-row pass is bit-identical to the job run alone.
         # With log-probs kept, exact mode prefills one row per pass too: a batched prefill gives a job the ids of its single run but may
         # round its first logits differently in the last place, and the job's log-probs are promised bit for bit.
-        self.rows_per_pass = 1 if lmm.precision == "fp16" or logprobs else 32
+        self.rows_per_pass = 1 if lmm.precision != "fp32" or logprobs else 32      # fp16 and fp8 are both "fast mode" here
 
     def embeds(self, job: _QueueJob) -> torch.Tensor:
         """inputs_embeds [1, S, hidden] of the job, built exactly as LMM.generate_ids builds them for a batch of one."""
@@ -133,11 +133,12 @@ class LMM:
     def __init__(self, opt, device="cuda:0", precision: Optional[str] = "fp32"):
         """precision: 'fp32' = exact mode (fp32 weights + KV; greedy ids bit-exact vs the CPU path), 'fp16' = fast mode
         (decoder matrices and KV cache stored in fp16 like the reference's ``model.half()`` GPU path, fp32 accumulate),
-        or None = module style: fp32 until ``.half()`` is called, the native context being created on first use, so
+        'fp8' = fast mode on a checkpoint whose q / k / v / out_proj / fc1 / fc2 matrices are rounded to e4m3 times a power of two
+        per output row (csrc/er_w8.h; the single-row decode projections stream the bytes), or None = module style: fp32 until ``.half()`` is called, the native context being created on first use, so
         that the reference's ``LMM(opt)`` -> ``load_state_dict`` -> ``.half().eval().to(device)`` (infer.py:41-56)
         selects the fp16 context exactly as it selects fp16 storage there."""
         self.opt = opt
-        if precision not in (None, "fp32", "fp16"):
+        if precision not in (None, "fp32", "fp16", "fp8"):
             raise ValueError(precision)
         if opt.cond_mode == "image":
             raise NotImplementedError("cond_mode='image' (CLIP conditioner) is outside the ArAE decode path")
@@ -157,7 +158,8 @@ class LMM:
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise native.NativeError("this LMM only runs on a HIP device (cuda:N); there is no CPU fallback")
-        self._dtype = torch.float16 if precision == "fp16" else torch.float32
+        self._dtype = torch.float16 if precision in ("fp16", "fp8") else torch.float32      # activations' storage: the KV cache, the prefill's operands
+        self._w8 = precision == "fp8"
         self._dec: Optional[NativeShapeOPT] = None
         self._sources: List[tuple] = []        # (state_dict reference, strict) of every load_state_dict call, for re-creation
         self.training = False
@@ -170,13 +172,13 @@ class LMM:
     # -- native context ------------------------------------------------------------------------
     @property
     def precision(self) -> str:
-        return "fp16" if self._dtype == torch.float16 else "fp32"
+        return "fp8" if self._w8 else "fp16" if self._dtype == torch.float16 else "fp32"
 
     def _materialize(self):
         if self._released:
             raise native.NativeError("LMM: the checkpoint was released (release_checkpoint()) and the native context is gone; "
                                      "create a new LMM and load the checkpoint again")
-        dec = NativeShapeOPT(self.dims, self.opt, self.device, weight_dtype=self._dtype, kv_dtype=self._dtype)
+        dec = NativeShapeOPT(self.dims, self.opt, self.device, weight_dtype="fp8" if self._w8 else self._dtype, kv_dtype=self._dtype)
         dec.model = _DecoderModel(dec)
         for sd, strict in self._sources:
             dec.load_state_dict(sd, strict=strict)
@@ -216,15 +218,16 @@ class LMM:
         self._released = True
         return self
 
-    def _cast(self, dtype):
-        if dtype == self._dtype:
+    def _cast(self, dtype, w8: bool = False):
+        if dtype == self._dtype and w8 == self._w8:
             return self
         if self._dec is not None and self._dec.direct_loads:
+            want = "fp8" if w8 else "fp16" if dtype == torch.float16 else "fp32"
             raise native.NativeError(
-                f"LMM.{'half' if dtype == torch.float16 else 'float'}(): this context's weights were streamed directly into "
+                f"LMM.{'fp8' if w8 else 'half' if dtype == torch.float16 else 'float'}(): this context's weights were streamed directly into "
                 f"the {self.precision} native context (mesh_decoder.load_state_iter / load_state_dict); they cannot be "
-                f"re-stored. Create LMM(opt, device, precision='{'fp16' if dtype == torch.float16 else 'fp32'}') instead.")
-        self._dtype = dtype
+                f"re-stored. Create LMM(opt, device, precision='{want}') instead.")
+        self._dtype, self._w8 = dtype, w8
         if self._dec is not None:            # rebuild lazily from the retained checkpoints in the new storage precision
             self._dec.close()
             self._dec = None
@@ -233,6 +236,10 @@ class LMM:
     def half(self):
         """The reference casts to fp16 here (infer.py:56): selects the fp16-storage context (fp32 accumulate)."""
         return self._cast(torch.float16)
+
+    def fp8(self):
+        """Selects the fp8 context: fast mode with the decoder matrices of every layer stored as e4m3 bytes times 2^e per row."""
+        return self._cast(torch.float16, w8=True)
 
     def float(self):
         return self._cast(torch.float32)

@@ -16,7 +16,7 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 # does not exist fails as loudly as a missing default build
 LIB_PATH = os.environ.get("ER_LIB_PATH") or os.path.join(PKG, "libedgerunner_hip.so")
 
-ER_F32, ER_F16, ER_BF16 = 0, 1, 2
+ER_F32, ER_F16, ER_BF16, ER_F8E4M3 = 0, 1, 2, 3
 ER_COND_NONE, ER_COND_POINT, ER_COND_POINT_LATENT = 0, 1, 2
 ER_GREEDY, ER_SAMPLE = 0, 1
 ER_GRAMMAR_NONE, ER_GRAMMAR_NAIVE9, ER_GRAMMAR_LR_ABSCO = 0, 1, 2
@@ -37,6 +37,7 @@ EXPORTS = [
     "er_k_nn_dist2", "er_k_surface_sample", "er_k_fidelity_metrics",
     "er_queue_begin", "er_queue_admit", "er_queue_run", "er_queue_take", "er_queue_stats", "er_queue_end",
     "er_set_sampling", "er_get_logprobs", "er_queue_row_logprobs", "er_k_sample_head_ctl",
+    "er_k_w8_quantize", "er_k_gemv_form_w8", "er_k_attn_outproj3_w8",
 ]
 
 
@@ -188,6 +189,9 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.er_k_attn_shared.argtypes = [vp, vp, vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), ci, vp, vp, ci, ci, ci, ci, vp]
     lib.er_k_attn_decode.argtypes = [vp, vp, vp, C.POINTER(C.c_int32), vp, ci, ci, ci, ci, ci, ci, ci, vp]
     lib.er_k_attn_outproj3.argtypes = [vp, vp, vp, ci, vp, vp, vp, vp, ci, ci, ci, vp]
+    lib.er_k_w8_quantize.argtypes = [vp, ci, ci, ci, ci, vp, vp, vp, vp, vp]
+    lib.er_k_gemv_form_w8.argtypes = [C.POINTER(ErKGemvFormArgs), vp, vp, vp]
+    lib.er_k_attn_outproj3_w8.argtypes = [vp, vp, vp, ci, vp, vp, vp, vp, vp, ci, ci, vp]
     lib.er_k_gemm.argtypes = [vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, cf, vp]
     lib.er_k_gemm_f16.argtypes = [vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, vp]
     lib.er_k_gemm_f16s.argtypes = [vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, vp]

@@ -20,7 +20,10 @@ from . import native
 from .weights import ModelDims
 
 _COND = {"none": native.ER_COND_NONE, "point": native.ER_COND_POINT, "point_latent": native.ER_COND_POINT_LATENT}
-_DT = {torch.float32: native.ER_F32, torch.float16: native.ER_F16, torch.bfloat16: native.ER_BF16}
+# storage dtypes of a context; "fp8" (or torch.float8_e4m3fn) = e4m3 bytes times 2^e per row for the six decoder matrices of a layer
+_DT = {torch.float32: native.ER_F32, torch.float16: native.ER_F16, torch.bfloat16: native.ER_BF16, "fp8": native.ER_F8E4M3}
+if hasattr(torch, "float8_e4m3fn"):
+    _DT[torch.float8_e4m3fn] = native.ER_F8E4M3
 
 
 class BuiltinGrammar:

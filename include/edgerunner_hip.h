@@ -45,10 +45,12 @@ typedef enum {
 } er_status;
 
 /* Element types.  As the dtype of a CHECKPOINT tensor handed to er_load_tensor / er_dit_load_tensor all three are accepted
- * (converted on the device).  As a context's STORAGE precision (er_config.weight_dtype / kv_dtype) two combinations are
- * built: ER_F32 + ER_F32 (exact mode) and ER_F16 + ER_F16 (fast mode, the reference's GPU dtype); ER_BF16 storage is
- * rejected by er_create with ER_ERR_UNSUPPORTED (the reference never runs this path in bf16). */
-typedef enum { ER_F32 = 0, ER_F16 = 1, ER_BF16 = 2 } er_dtype;
+ * (converted on the device).  As a context's STORAGE precision (er_config.weight_dtype / kv_dtype) three combinations are
+ * built: ER_F32 + ER_F32 (exact mode), ER_F16 + ER_F16 (fast mode, the reference's GPU dtype) and ER_F8E4M3 + ER_F16 (fp8 mode:
+ * fast mode with the q / k / v / out_proj / fc1 / fc2 matrices of every decoder layer stored as OCP e4m3fn bytes times 2^e per
+ * output row, csrc/er_w8.h; it computes what fast mode computes on a checkpoint rounded that way).  Every other combination, ER_BF16
+ * storage included, is rejected by er_create with ER_ERR_UNSUPPORTED.  ER_F8E4M3 is a storage mode only, never a checkpoint dtype. */
+typedef enum { ER_F32 = 0, ER_F16 = 1, ER_BF16 = 2, ER_F8E4M3 = 3 } er_dtype;
 typedef enum { ER_COND_NONE = 0, ER_COND_POINT = 1, ER_COND_POINT_LATENT = 2 } er_cond_mode;
 typedef enum { ER_GREEDY = 0, ER_SAMPLE = 1 } er_gen_mode;
 /* prefix_allowed_tokens_fn variants LMM.generate can build (core/models.py:236-275) */
@@ -492,6 +494,20 @@ int er_k_attn_shared(const float* q_dev, const void* k_dev, const void* v_dev, c
 int er_k_attn_outproj3(const float* q_dev, const void* k_dev, const void* v_dev, int len, const void* wo_dev,
                        const float* bo_dev, const float* resid_dev, float* y_dev, int l_cap, int kv_half, int w_half,
                        void* stream);
+/* fp8 mode on caller-owned operands (csrc/er_w8.h).  er_k_w8_quantize: the weight loader's row quantiser on a matrix [n][k] of
+ * fp32 / fp16 / bf16 values in host (on_device = 0) or device memory - per row e = the smallest integer with amax * 2^-e <= 448 in
+ * [-15, 7], bytes q = e4m3fn(w * 2^-e) (saturating, round to nearest even), and the dequantised values q * 2^e as fp16.  The four
+ * outputs are device memory and nullable: q_dev uint8 [n][k], e_dev int32 [n], w16_dev fp16 [n][k], wscale_dev fp32 [n] = 2^e.
+ * A NaN or an infinity in the source is ER_ERR_INVALID.
+ * er_k_gemv_form_w8: er_k_gemv_form on (q_dev, wscale_dev) in place of args->w (not read) - ER_FORM_ROW and the fp16 row shapes
+ * (w_half set) of qkv, out_proj, fc1 and fc2 only, with er_k_gemv_form's refusals before any launch; bit-identical to er_k_gemv_form
+ * on the fp16 matrix q * 2^e.  er_k_attn_outproj3_w8: er_k_attn_outproj3 with Wo as bytes and row scales.  All block. */
+int er_k_w8_quantize(const void* src, int dtype, int on_device, int n, int k, void* q_dev, int32_t* e_dev, void* w16_dev,
+                     float* wscale_dev, void* stream);
+int er_k_gemv_form_w8(const er_k_gemv_form_args* args, const void* q_dev, const float* wscale_dev, void* stream);
+int er_k_attn_outproj3_w8(const float* q_dev, const void* k_dev, const void* v_dev, int len, const void* wo_q_dev,
+                          const float* wo_scale_dev, const float* bo_dev, const float* resid_dev, float* y_dev, int l_cap,
+                          int kv_half, void* stream);
 /* C[M,N] = A[M,K] op(B) (+bias)(relu)(+resid); b_is_kn=0: B is [N,K] (Linear weight), 1: B is [K,N] */
 int er_k_gemm(const float* a_dev, const float* b_dev, const float* bias_dev, const float* resid_dev,
               float* c_dev, int m, int n, int k, int lda, int ldb, int ldc, int b_is_kn, int relu,

@@ -115,7 +115,7 @@ def max_rows_per_call(opt, model, max_new_tokens, device) -> int:
     the rows' KV cache + prefill / encoder scratch must fit in the HBM that is free once the weights are resident (the native
     context is created here, before the measurement)."""
     d = model.dims
-    esz = 2 if model.precision == "fp16" else 4
+    esz = 4 if model.precision == "fp32" else 2      # fp16 and fp8 keep an fp16 cache
     l_cap = d.num_cond_tokens + 2 + max_new_tokens
     kv_row = 2 * d.num_layers * d.hidden_dim * esz * l_cap
     scratch_row = (d.num_cond_tokens + 1) * (6 * d.hidden_dim + d.intermediate_dim) * 4
@@ -167,9 +167,11 @@ def main(argv=None):
         print("[WARN] model randomly initialized, are you sane?")
         model.load_state_dict(W.make_state_dict(opt, opt.seed, "reference"), strict=True)
     # the reference runs fp16 on the GPU (infer.py:56,105): .half() selects the fp16-storage context (fp32 accumulate);
-    # EDGERUNNER_PRECISION=fp32 keeps the exact mode (greedy ids bit-exact vs the CPU path)
+    # EDGERUNNER_PRECISION=fp32 keeps the exact mode (greedy ids bit-exact vs the CPU path), fp8 selects e4m3 row-scaled decoder matrices
     if os.environ.get("EDGERUNNER_PRECISION", "fp16") == "fp32":
         model = model.float().eval().to(device)
+    elif os.environ.get("EDGERUNNER_PRECISION") == "fp8":
+        model = model.fp8().eval().to(device)
     else:
         model = model.half().eval().to(device)
     model.release_checkpoint()        # the weights are on the device in their final precision: drop the host copy (~2.7 GB per rank)

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """A/B of library BUILDS on the single-row decode path (GPU box only): for every ER_LIB_PATH given, one subprocess that builds the
 24-layer context, decodes T tokens twice and prints decode tok/s + the per-kernel-kind HIP-event sweep (24 graph-replayed launches of a
-kind at the run's mean context).  Usage: python scripts/ab_decode.py [fp32|fp16] T label=[path][:ENV=V,...] ...   (empty path = the default build)"""
+kind at the run's mean context).  Usage: python scripts/ab_decode.py [fp32|fp16|fp8] T label=[path][:ENV=V,...] ...   (empty path = the default build)"""
 import dataclasses
 import json
 import os
