@@ -182,6 +182,8 @@ struct er_ctx {
     float *embd = nullptr, *posemb = nullptr, *lm_head = nullptr, *embed_num_face = nullptr;
     _Float16* lm_head_h = nullptr;
     bool fast = false;       // fp16 weights + fp16 KV cache, fp32 accumulate
+    bool kv8 = false;        // kv8 mode: fast (or fp8), with the KV cache stored as e4m3 bytes without a scale (er_w8.h kv8_encode)
+    int kv_type = 0;         // the cache type as the kernels' kv_half argument takes it: 0 = fp32, 1 = fp16, 2 = e4m3 bytes
     bool w8 = false;         // fp8 mode: fast, with the six decoder matrices per layer quantised by row; the row forms of the step stream the bytes
     float *proj_w = nullptr, *proj_b = nullptr, *normc_w = nullptr, *normc_b = nullptr;
     PointEnc pe;             // point encoder (cond_mode POINT)
@@ -323,10 +325,13 @@ extern "C" int er_create(const er_config* cfg, int device, er_ctx** out) {
     const int D = cfg->hidden_dim / cfg->num_heads;
     if (D != 96 && D != 64) return fail(ER_ERR_UNSUPPORTED, "head_dim %d not built (96, 64)", D);
     const bool exact = cfg->weight_dtype == ER_F32 && cfg->kv_dtype == ER_F32;
-    const bool w8 = cfg->weight_dtype == ER_F8E4M3 && cfg->kv_dtype == ER_F16;
-    const bool fast = w8 || (cfg->weight_dtype == ER_F16 && cfg->kv_dtype == ER_F16);
+    const bool kv8 = cfg->kv_dtype == ER_F8E4M3 && (cfg->weight_dtype == ER_F16 || cfg->weight_dtype == ER_F8E4M3);
+    const bool w8 = cfg->weight_dtype == ER_F8E4M3 && (cfg->kv_dtype == ER_F16 || kv8);
+    const bool fast = w8 || kv8 || (cfg->weight_dtype == ER_F16 && cfg->kv_dtype == ER_F16);
     if (!exact && !fast)
-        return fail(ER_ERR_UNSUPPORTED, "built modes: fp32 weights + fp32 KV (exact), fp16 weights + fp16 KV (fast) or e4m3 row-scaled weights + fp16 KV (fp8)");
+        return fail(ER_ERR_UNSUPPORTED, "built modes: fp32 weights + fp32 KV (exact), fp16 weights + fp16 KV (fast) or e4m3 row-scaled weights + fp16 KV (fp8); "
+                                        "the fast and fp8 weights also run on an e4m3 byte KV cache (kv8)");
+    if (kv8 && D != 96) return fail(ER_ERR_UNSUPPORTED, "the e4m3 KV cache (kv8) is built for head_dim 96; got %d", D);
     if (cfg->vocab_size > ER_HEAD_MAX_VOCAB) return fail(ER_ERR_UNSUPPORTED, "vocab_size > %d", ER_HEAD_MAX_VOCAB);
     if (cfg->cond_mode == ER_COND_POINT && (cfg->point_hidden_dim != 1024 || cfg->point_hidden_dim % cfg->point_num_heads))
         return fail(ER_ERR_UNSUPPORTED, "point encoder width %d not built (1024)", cfg->point_hidden_dim);
@@ -337,7 +342,9 @@ extern "C" int er_create(const er_config* cfg, int device, er_ctx** out) {
     c->D = D;
     c->fast = fast;
     c->w8 = w8;
-    c->kv_esz = fast ? 2 : 4;
+    c->kv8 = kv8;
+    c->kv_type = kv8 ? 2 : fast ? 1 : 0;
+    c->kv_esz = kv8 ? 1 : fast ? 2 : 4;
     c->layers.resize(cfg->num_layers);
     c->pe.PH = cfg->point_hidden_dim; c->pe.heads = cfg->point_num_heads; c->pe.Lq = cfg->point_latent_size;
     c->pe.LD = cfg->point_latent_dim; c->pe.freq = cfg->point_freq_dim; c->pe.eps = cfg->ln_eps;
@@ -492,7 +499,7 @@ extern "C" int er_kv_reserve(er_ctx* c, int batch, int max_len) {
 static int kv_alloc(er_ctx* c, KvMem& m, int batch, int Lcap) {
     const er_config& g = c->cfg;
     const int H = g.num_heads, D = c->D, hid = g.hidden_dim;
-    m.plan = make_decode_plan(c->knobs, read_reserve_knobs(), c->fast, batch, Lcap, g.num_layers, H, D, hid, attn_chunking(H));
+    m.plan = make_decode_plan(c->knobs, read_reserve_knobs(), c->fast, batch, Lcap, g.num_layers, H, D, hid, attn_chunking(H), false, c->kv8);
     const DecodePlan& p = m.plan;
     const size_t kv_bytes = (size_t)p.kv_lstride * g.num_layers * c->kv_esz;
     ERCHK(m.kc.ensure(kv_bytes));
@@ -575,7 +582,7 @@ static AttnSharedArgs attn_shared_args(er_ctx* c, int layer) {
     return s;
 }
 
-static hipError_t launch_attn_partial(const AttnDecArgs& a, int D, int steps, bool kv_half, int B, hipStream_t st, int ver = 2) {
+static hipError_t launch_attn_partial(const AttnDecArgs& a, int D, int steps, int kv_half, int B, hipStream_t st, int ver = 2) {
     return D == 96 ? launch_attn_partial_d<96>(a, steps, kv_half, B, st, ver) : launch_attn_partial_d<64>(a, steps, kv_half, B, st, ver);
 }
 static hipError_t launch_attn_combine(const AttnDecArgs& a, int D, int B, hipStream_t st) {
@@ -598,7 +605,7 @@ static MlpArgs mlp_args(er_ctx* c, int layer) {
 // the form comes from proj_form and the launches from run_proj (er_decode_proj.h).
 template <typename WT>
 static hipError_t launch_kind_t(er_ctx* c, int kind, int layer, hipStream_t st, long long* out_ids, int out_ld) {
-    constexpr bool HALF = sizeof(WT) == 2;
+    constexpr bool HALF = sizeof(WT) == 2;      // fp16 weights; the cache type is the context's own (c->kv_type: kv8 stores bytes under fp16 weights)
     const er_config& g = c->cfg;
     const DecodePlan& p = c->kv->plan;
     const KvMem& kv = *c->kv;
@@ -608,7 +615,7 @@ static hipError_t launch_kind_t(er_ctx* c, int kind, int layer, hipStream_t st, 
     const bool v3 = p.v3 && !kv.row_class, fused = p.mlp_fused && !kv.row_class;
     GemvArgs a{};
     a.eps = g.ln_eps;
-    a.hidden = H; a.head_dim = c->D; a.l_cap = p.Lcap; a.kv_bstride = p.kv_bstride; a.kv_half = HALF ? 1 : 0;
+    a.hidden = H; a.head_dim = c->D; a.l_cap = p.Lcap; a.kv_bstride = p.kv_bstride; a.kv_half = c->kv_type;
     ProjIo io;
     switch (kind) {
         case 0: {   // qkv
@@ -634,8 +641,8 @@ static hipError_t launch_kind_t(er_ctx* c, int kind, int layer, hipStream_t st, 
         case 1:
             if (v3) return launch_attn_partial3_d<96>(attn_args(c, layer), HALF, p.nch3, B, st);
             if (p.shared_attn) return launch_attn_prefix_d<96>(attn_shared_args(c, layer), HALF, kv.n_groups, st);
-            if (p.stream_attn) return launch_attn_stream_d<96>(attn_args(c, layer), HALF, B, st);
-            return launch_attn_partial(attn_args(c, layer), c->D, ATTN_STEPS_DEFAULT, HALF, B, st, p.batched ? 1 : 2);
+            if (p.stream_attn) return launch_attn_stream_d<96>(attn_args(c, layer), c->kv_type, B, st);
+            return launch_attn_partial(attn_args(c, layer), c->D, ATTN_STEPS_DEFAULT, c->kv_type, B, st, p.batched ? 1 : 2);
         case 2:
             if (!p.sel.merge_launch && !(p.v3 && !v3)) return hipSuccess;      // the merge runs inside the out_proj kernel (version 3) / there are no partials (streaming)
             if (p.shared_attn) return launch_attn_suffix_merge_d<96>(attn_shared_args(c, layer), HALF, B, st);
@@ -1047,13 +1054,17 @@ static int prefill_run(er_ctx* c, const float* embeds, int B, int S, hipStream_t
                 HIPRET(launch_flash_attn_f32(f, D, true, NH, B, st));
             }
         } else {
-            // fast mode: fused projection into fp32 scratch [M][3H]; K/V rounded to the cache dtype (fp16) both in
+            // fast mode: fused projection into fp32 scratch [M][3H]; K/V rounded to the cache dtype (fp16; kv8: e4m3) both in
             // the cache and in the scratch the prefix attention reads
             ERCHK(c->p_qkv.ensure((size_t)M * 3 * H));
             float* qkv = c->p_qkv.p;
             ERCHK(linear_hs(c, h, H, L.wqkv_h, L.bqkv, qkv, 3 * H, M, 3 * H, H, false, nullptr, 0, st));
-            hipLaunchKernelGGL(kv_scatter_half_kernel, kv_scatter_grid(M, H), dim3(ER_WG), 0, st, qkv,
-                               (_Float16*)kc, (_Float16*)vc, M, S, H, D, p.Lcap, p.kv_bstride);
+            if (c->kv8)      // kv8: bytes into the cache, decode(encode(v)) back into the scratch
+                hipLaunchKernelGGL(kv_scatter_f8_kernel, kv_scatter_grid(M, H), dim3(ER_WG), 0, st, qkv,
+                                   (unsigned char*)kc, (unsigned char*)vc, M, S, H, D, p.Lcap, p.kv_bstride);
+            else
+                hipLaunchKernelGGL(kv_scatter_half_kernel, kv_scatter_grid(M, H), dim3(ER_WG), 0, st, qkv,
+                                   (_Float16*)kc, (_Float16*)vc, M, S, H, D, p.Lcap, p.kv_bstride);
             HIPRET(hipGetLastError());
             {
                 Flash32Args f{};
@@ -1141,6 +1152,7 @@ extern "C" int er_set_prefix_groups(er_ctx* c, const int32_t* leader, int n, int
     if (c->q.active) return fail(ER_ERR_INVALID, "er_set_prefix_groups: a queue is open on this context (er_queue_end first)");
     const bool clear = !leader || prefix_len == 0;
     if (clear && !kv.prefix_len) return ER_OK;
+    if (!clear && c->kv8) return fail(ER_ERR_UNSUPPORTED, "er_set_prefix_groups: the shared-prefix kernels read fp32 and fp16 caches only; this context keeps an e4m3 cache (kv8)");
     std::vector<int> rows, off, followers;
     if (!clear) {
         if (n != B) return fail(ER_ERR_INVALID, "er_set_prefix_groups: %d leaders for a batch of %d rows", n, B);
@@ -1162,7 +1174,7 @@ extern "C" int er_set_prefix_groups(er_ctx* c, const int32_t* leader, int n, int
     HIPCHK(hipDeviceSynchronize());           // a running step still reads the old tables
     kv.drop_steps();                          // the next step is captured with the new launches
     const er_config& g = c->cfg;
-    kv.plan = make_decode_plan(c->knobs, kv.plan.rk, c->fast, B, kv.plan.Lcap, g.num_layers, g.num_heads, c->D, g.hidden_dim, attn_chunking(g.num_heads), !clear);
+    kv.plan = make_decode_plan(c->knobs, kv.plan.rk, c->fast, B, kv.plan.Lcap, g.num_layers, g.num_heads, c->D, g.hidden_dim, attn_chunking(g.num_heads), !clear, c->kv8);
     c->have_hidden = false;                   // groups come before the prefill whose cache they describe
     kv.prefix_len = 0; kv.n_groups = 0; kv.grp_leader.clear();
     kv.grp_followers = DevBuf<int>();
@@ -1666,7 +1678,7 @@ static int profile_impl(er_ctx* c, int repeats, int use_graph, float* avg_us, do
 
     const double w = c->fast ? 2.0 : 4.0;   // bytes per streamed weight / KV element
     bytes[0] = ((double)3 * H * H + 3 * H) * w + (double)B * (H + 3 * H) * w;
-    bytes[1] = (double)B * 2.0 * len * H * w;
+    bytes[1] = (double)B * 2.0 * len * H * (double)c->kv_esz;
     bytes[2] = (double)B * g.num_heads * p.S_splits * (c->D + 2) * w + (double)B * H * w;
     bytes[3] = ((double)H * H + H) * w + (double)B * 3 * H * w;
     bytes[4] = ((double)I * H + I) * w + (double)B * (H + I) * w;
@@ -1833,6 +1845,9 @@ extern "C" int er_k_attn_decode(const float* q, const void* k, const void* v, co
     if (variant == ER_ATTN_STREAM && head_dim != 96) return fail(ER_ERR_UNSUPPORTED, "the streaming kernel is built for head_dim 96");
     if (head_dim != 96 && head_dim != 64) return fail(ER_ERR_UNSUPPORTED, "head_dim %d", head_dim);
     if (steps != 2 && steps != 4 && steps != 8) return fail(ER_ERR_INVALID, "steps must be 2, 4 or 8 (chunk = 32*steps keys)");
+    if (kv_half < 0 || kv_half > 2) return fail(ER_ERR_INVALID, "er_k_attn_decode: kv_half %d (0 = fp32, 1 = fp16, 2 = e4m3 bytes)", kv_half);
+    if (kv_half == 2 && (head_dim != 96 || variant == ER_ATTN_SPLIT1 || (variant == ER_ATTN_SPLIT2 && steps != ATTN_STEPS_DEFAULT)))
+        return fail(ER_ERR_UNSUPPORTED, "er_k_attn_decode: the byte cache runs ER_ATTN_SPLIT2 (steps 4) and ER_ATTN_STREAM at head_dim 96");
     hipStream_t st = (hipStream_t)stream;
     const int S = attn_num_chunks(l_cap, attn_chunk(steps));
     DevBuf<int> len_dev;
@@ -1845,9 +1860,9 @@ extern "C" int er_k_attn_decode(const float* q, const void* k, const void* v, co
     a.S = S; a.chunk = attn_chunk(steps);
     hipError_t e;
     if (variant == ER_ATTN_STREAM) {       // the streaming kernel of the batched decode step (no partials)
-        e = launch_attn_stream_d<96>(a, kv_half != 0, B, st);
+        e = launch_attn_stream_d<96>(a, kv_half, B, st);
     } else {
-        e = launch_attn_partial(a, head_dim, steps, kv_half != 0, B, st, variant == ER_ATTN_SPLIT1 ? 1 : 2);
+        e = launch_attn_partial(a, head_dim, steps, kv_half, B, st, variant == ER_ATTN_SPLIT1 ? 1 : 2);
         if (e == hipSuccess) e = launch_attn_combine(a, head_dim, B, st);
     }
     hipError_t e2 = hipStreamSynchronize(st);
@@ -1860,6 +1875,7 @@ extern "C" int er_k_attn_stream_xt(const float* q, const void* k, const void* v,
                                    int heads, int l_cap, int kv_half, void* stream) {
     constexpr int D = 96;
     if (!q || !k || !v || !len_host || !out || B < 1 || heads < 1 || l_cap < 1) return fail(ER_ERR_INVALID, "er_k_attn_stream_xt: bad argument");
+    if (kv_half < 0 || kv_half > 2) return fail(ER_ERR_INVALID, "er_k_attn_stream_xt: kv_half %d (0 = fp32, 1 = fp16, 2 = e4m3 bytes)", kv_half);
     for (int b = 0; b < B; ++b)
         if (len_host[b] < 1 || len_host[b] > l_cap) return fail(ER_ERR_CAPACITY, "er_k_attn_stream_xt: len[%d] = %d / l_cap %d", b, len_host[b], l_cap);
     hipStream_t st = (hipStream_t)stream;
@@ -1868,7 +1884,7 @@ extern "C" int er_k_attn_stream_xt(const float* q, const void* k, const void* v,
     HIPCHK(hipMemcpy(len_dev.p, len_host, B * sizeof(int), hipMemcpyHostToDevice));
     AttnDecArgs a = attn_dec_args(heads, D, l_cap);
     a.q = q; a.kcache = k; a.vcache = v; a.len_dev = len_dev.p; a.out = out; a.out_xt = out_xt;      // as attn_args: xt_att when out_proj reads the tiled image
-    hipError_t e = launch_attn_stream_d<D>(a, kv_half != 0, B, st);      // launch_kind_t case 1, stream_attn
+    hipError_t e = launch_attn_stream_d<D>(a, kv_half, B, st);      // launch_kind_t case 1, stream_attn
     hipError_t e2 = hipStreamSynchronize(st);
     HIPRET(e);
     HIPRET(e2);
@@ -1952,6 +1968,7 @@ static int gemv_form_check(const er_k_gemv_form_args& f, Proj* proj_out) {
         if (!f.q_out || !f.kcache || !f.vcache || !f.pos) return fail(ER_ERR_INVALID, "er_k_gemv_form: EPI_QKV needs q_out, kcache, vcache, pos");
         if (f.heads < 1 || f.head_dim < 1 || f.l_cap < 1 || f.heads * f.head_dim != k || n != 3 * k)
             return fail(ER_ERR_INVALID, "er_k_gemv_form: EPI_QKV needs heads * head_dim == k and n == 3 k");
+        if (f.kv_half == 2 && !half) return fail(ER_ERR_UNSUPPORTED, "er_k_gemv_form: the e4m3 byte cache (kv_half 2) goes with fp16 or byte weights");
     } else if (!prep) {
         if (!f.y && !(form == ER_FORM_MFMA_XT && proj == PROJ_FC1) && form != ER_FORM_NARROW_DEFER) return fail(ER_ERR_INVALID, "er_k_gemv_form: null y");
         if (epi == ER_EPI_RESID && !f.resid && form != ER_FORM_NARROW_DEFER) return fail(ER_ERR_INVALID, "er_k_gemv_form: EPI_RESID needs resid");
@@ -1975,7 +1992,7 @@ static int gemv_form_t(const er_k_gemv_form_args& f, Proj proj, hipStream_t st) 
     GemvArgs a{};
     a.W = f.w; a.bias = f.bias; a.N = f.n; a.xin = f.x; a.ln_w = f.ln_w; a.ln_b = f.ln_b; a.eps = f.eps; a.hout = f.xnorm_out;
     a.embd = f.embd; a.posemb = f.posemb; a.tok = f.tok; a.pos = f.pos;
-    a.out = f.y; a.resid = f.resid; a.q = f.q_out; a.kcache = f.kcache; a.vcache = f.vcache; a.kv_half = f.kv_half ? 1 : 0;
+    a.out = f.y; a.resid = f.resid; a.q = f.q_out; a.kcache = f.kcache; a.vcache = f.vcache; a.kv_half = f.kv_half == 2 ? 2 : f.kv_half ? 1 : 0;
     a.hidden = f.form != ER_FORM_PREP && proj == PROJ_QKV ? f.heads * f.head_dim : 1536; a.head_dim = f.head_dim; a.l_cap = f.l_cap;
     a.kv_bstride = (long long)f.heads * f.l_cap * f.head_dim;
     ProjIo io;
@@ -1990,6 +2007,18 @@ extern "C" int er_k_gemv_form(const er_k_gemv_form_args* f, void* stream) {
     Proj proj = PROJ_QKV;
     ERCHK(gemv_form_check(*f, &proj));
     return f->w_half ? gemv_form_t<_Float16>(*f, proj, (hipStream_t)stream) : gemv_form_t<float>(*f, proj, (hipStream_t)stream);
+}
+
+// ---- kv8 mode: the device encoder the K/V producers store with (k_gemv.h gemv_epilogue, k_rowops.h kv_scatter_f8_kernel) on a flat array
+extern "C" int er_k_kv8_encode(const float* src, void* dst, long long n, void* stream) {
+    if (!src || !dst || n < 1) return fail(ER_ERR_INVALID, "er_k_kv8_encode: bad argument");
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(kv8_encode_kernel, dim3(ew_grid(n)), dim3(ER_WG), 0, st, src, (unsigned char*)dst, n);
+    hipError_t e = hipGetLastError();
+    hipError_t e2 = hipStreamSynchronize(st);
+    HIPRET(e);
+    HIPRET(e2);
+    return ER_OK;
 }
 
 // ---- fp8 mode on caller-owned operands: the row quantiser of the weight loader, and the byte kernels behind the row forms.
@@ -2045,7 +2074,7 @@ extern "C" int er_k_gemv_form_w8(const er_k_gemv_form_args* f, const void* q_dev
     GemvArgs a{};
     a.W = blk.p; a.bias = g.bias; a.N = g.n; a.xin = g.x; a.ln_w = g.ln_w; a.ln_b = g.ln_b; a.eps = g.eps; a.hout = g.xnorm_out;
     a.embd = g.embd; a.posemb = g.posemb; a.tok = g.tok; a.pos = g.pos;
-    a.out = g.y; a.resid = g.resid; a.q = g.q_out; a.kcache = g.kcache; a.vcache = g.vcache; a.kv_half = g.kv_half ? 1 : 0;
+    a.out = g.y; a.resid = g.resid; a.q = g.q_out; a.kcache = g.kcache; a.vcache = g.vcache; a.kv_half = g.kv_half == 2 ? 2 : g.kv_half ? 1 : 0;
     a.hidden = proj == PROJ_QKV ? g.heads * g.head_dim : 1536; a.head_dim = g.head_dim; a.l_cap = g.l_cap;
     a.kv_bstride = (long long)g.heads * g.l_cap * g.head_dim;
     const int pro = g.prologue == ER_PRO_NONE ? PRO_NONE : g.prologue == ER_PRO_EMBED ? PRO_EMBED : PRO_LN;

@@ -50,6 +50,7 @@ struct DecodePlan {
     bool stream_attn = false;   // batched, D == 96 and (forced or B*H >= 256: at least one streaming workgroup per CU)
     bool shared_attn = false;   // prefix groups are set (er_set_prefix_groups; batched, D == 96): prefix pass + suffix / merge launch (k_attn_shared.h) in place of either batched kernel
     ReserveKnobs rk{};          // the switches of the reserve, kept so that setting or clearing groups can derive the plan again
+    bool kv8 = false;           // the cache holds e4m3 bytes (kv8 mode): version 2 at B <= 4, the streaming kernel at every batched shape, no prefix groups
     bool v3 = false;            // decode_v == 3 and the reserved cache qualifies
     bool mlp_fused = false;     // mlp_v != 0, one row, not batched, hidden 1536: kinds 4 and 5 are the fused MLP launch and its finish
     bool outproj_rows8 = false; // mfma and 5..8 rows: out_proj is ONE pass of the VALU kernel (ER_FORM_ROWS8)
@@ -65,13 +66,15 @@ struct DecodePlan {
 //   version 3   : one row, 16 heads of 96, hidden 1536, reserved cache <= 16 chunks x 512 keys; else version 2
 //   attention B>4: streaming kernel when forced or (auto and B * heads >= 256: at least one workgroup per CU - at B = 16 it
 //                  ties the split kernel and saves the merge launch, at B = 8 it is 1.5x slower), else split + merge
+//   kv8 (e4m3 byte cache, D = 96): only attn_decode2_kernel and attn_stream_kernel have a byte form - never version 3, and every
+//                  batched shape streams (also 5 <= B < 16 and ER_ATTN_V_BATCHED=1: the round-1 split kernel reads no bytes)
 inline void plan_decode(int decode_v, int attn_v_batched, bool force_batched, int batch, int H, int D, int hid, int Lcap,
-                        const AttnChunking& ch, er_decode_plan* p) {
+                        const AttnChunking& ch, er_decode_plan* p, bool kv8 = false) {
     p->batched = (batch > 4 || force_batched) ? 1 : 0;
     p->attn_chunks = ch.nch3;
-    const bool v3 = decode_v == 3 && batch == 1 && !p->batched && D == 96 && H == 16 && hid == 1536 && Lcap <= ch.cap3;
+    const bool v3 = !kv8 && decode_v == 3 && batch == 1 && !p->batched && D == 96 && H == 16 && hid == 1536 && Lcap <= ch.cap3;
     p->decode_version = v3 ? 3 : 2;
-    const bool stream = p->batched && D == 96 && (attn_v_batched == 3 || (attn_v_batched == 0 && batch * H >= 256));
+    const bool stream = p->batched && D == 96 && (kv8 || attn_v_batched == 3 || (attn_v_batched == 0 && batch * H >= 256));
     p->attn_kernel = !p->batched ? (v3 ? ER_ATTN_BALANCED : ER_ATTN_SPLIT2)
                                  : (stream ? ER_ATTN_STREAM : ER_ATTN_SPLIT1);
     p->merge_launch = (p->attn_kernel == ER_ATTN_SPLIT1 || p->attn_kernel == ER_ATTN_SPLIT2) ? 1 : 0;
@@ -82,10 +85,10 @@ inline void plan_decode(int decode_v, int attn_v_batched, bool force_batched, in
 inline bool shared_attn_supported(const er_decode_plan& sel, int D) { return sel.batched != 0 && D == 96; }
 
 // the plan of one (batch, Lcap) of a model with `layers` layers of H heads of D (hid = hidden width), `fast` = fp16 weights and cache;
-// shared: prefix groups are set on the reserved batch (the caller has asked shared_attn_supported), which replaces the attention kernel
+// kv8: the cache holds e4m3 bytes (with fast's fp16 weights or fp8 mode's bytes); shared: prefix groups are set on the reserved batch (the caller has asked shared_attn_supported), which replaces the attention kernel
 // of plan_decode's shape-only rule by ER_ATTN_SHARED with its own merge launch
 inline DecodePlan make_decode_plan(const DecodeKnobs& k, const ReserveKnobs& rk, bool fast, int batch, int Lcap, int layers, int H, int D,
-                                   int hid, const AttnChunking& ch, bool shared = false) {
+                                   int hid, const AttnChunking& ch, bool shared = false, bool kv8 = false) {
     DecodePlan p;
     p.B = batch; p.Lcap = Lcap; p.layers = layers;
     p.kv_bstride = (long long)H * Lcap * D; p.kv_lstride = p.kv_bstride * batch;
@@ -93,8 +96,9 @@ inline DecodePlan make_decode_plan(const DecodeKnobs& k, const ReserveKnobs& rk,
     p.nch3 = ch.nch3;
     p.force_batched = rk.force_batched; p.valu = rk.batched_valu;
     p.rk = rk;
-    plan_decode(k.decode_v, k.attn_v_batched, p.force_batched, batch, H, D, hid, Lcap, ch, &p.sel);
-    p.shared_attn = shared && shared_attn_supported(p.sel, D);
+    plan_decode(k.decode_v, k.attn_v_batched, p.force_batched, batch, H, D, hid, Lcap, ch, &p.sel, kv8);
+    p.kv8 = kv8;
+    p.shared_attn = shared && !kv8 && shared_attn_supported(p.sel, D);      // the shared-prefix kernels have no byte form
     if (p.shared_attn) { p.sel.attn_kernel = ER_ATTN_SHARED; p.sel.merge_launch = 1; }
     p.batched = p.sel.batched != 0; p.mfma = p.batched && !p.valu; p.xt = fast && p.mfma && rk.xt;
     p.stream_attn = p.sel.attn_kernel == ER_ATTN_STREAM; p.v3 = p.sel.decode_version == 3;

@@ -25,7 +25,7 @@ static GemvArgs gemv_args_at(const GemvArgs& a, int row0, int K) {
     if (g.out) g.out += (long long)row0 * a.N;
     if (g.resid) g.resid += (long long)row0 * a.N;
     if (g.q) g.q += (long long)row0 * a.hidden;
-    const long long kvb = (long long)row0 * a.kv_bstride * (a.kv_half ? 2 : 4);
+    const long long kvb = (long long)row0 * a.kv_bstride * kv_elem_bytes(a.kv_half);
     if (g.kcache) g.kcache = (char*)g.kcache + kvb;
     if (g.vcache) g.vcache = (char*)g.vcache + kvb;
     return g;
@@ -57,7 +57,7 @@ static hipError_t gemv_nw(int nw, GemvArgs a, int B, int K, hipStream_t st) {
     if (nw == 6) return gemv_groups<WT, 1, 1, PRO, EPI, 6>(a, B, K, st);
     if (nw == 9) return gemv_groups<WT, 1, 2, PRO, EPI, 9>(a, B, K, st);
     if (nw == 12) return gemv_groups<WT, 1, 2, PRO, EPI, 12>(a, B, K, st);
-    if (EPI == EPI_QKV) return gemv_groups<WT, 1, 1, PRO, EPI>(a, B, K, st);
+    if (epi_qkv(EPI)) return gemv_groups<WT, 1, 1, PRO, EPI>(a, B, K, st);
     return gemv_groups<WT, 1, 2, PRO, EPI>(a, B, K, st);
 }
 
@@ -122,6 +122,9 @@ static hipError_t prep_rows(const GemvArgs& a, int B, hipStream_t st) {
 // fp8 context (w8 = the byte block of the same matrix, k_gemv.h w8_scales; WT = _Float16 and a.W = the fp16 copy of the dequantised
 // values): a row form of a projection that w8_streams() names runs the same (waves x rows) shape of the byte kernel on w8; every other
 // form, and the lm_head, runs the fp16 copy as in fast mode.  The byte type has the fp16 row shapes and nothing else.
+//
+// kv8 context (a.kv_half == 2: the KV cache holds e4m3 bytes): every QKV form - row, VALU, both matrix-core forms, with fp16 or byte
+// weights - is launched with EPI_QKV8, the epilogue that encodes (k_gemv.h); nothing else depends on the cache type.
 
 // Which projections of an fp8 context stream bytes in their row forms at B rows.  Measured in situ against the fp16 forms of the same
 // build in the same session (profiles/w8_bench.json): a projection streams bytes only where its byte form is faster
@@ -145,6 +148,13 @@ static hipError_t launch_proj(Proj proj, const ProjForm& f, int pro, const GemvA
         case ER_FORM_ROW:
             switch (proj) {
                 case PROJ_QKV:
+                    if (a.kv_half == 2) {      // byte cache: the epilogue that encodes (fp16 and byte weights only)
+                        if constexpr (HALF) {
+                            if (pro == PRO_EMBED) return gemv_nw<WT, PRO_EMBED, EPI_QKV8>(f.nw, a, B, K, st);
+                            return gemv_nw<WT, PRO_LN, EPI_QKV8>(f.nw, a, B, K, st);
+                        }
+                        break;
+                    }
                     if (pro == PRO_EMBED) return gemv_nw<WT, PRO_EMBED, EPI_QKV>(f.nw, a, B, K, st);
                     return gemv_nw<WT, PRO_LN, EPI_QKV>(f.nw, a, B, K, st);
                 case PROJ_OUT:
@@ -169,6 +179,15 @@ static hipError_t launch_proj(Proj proj, const ProjForm& f, int pro, const GemvA
             break;
         default: break;
     }
+    if constexpr (sizeof(WT) == 2) {
+        if (proj == PROJ_QKV && a.kv_half == 2) switch (f.form) {      // the batched QKV forms into a byte cache
+            case ER_FORM_VALU: return gemv_batched_groups<WT, 1, 3, EPI_QKV8>(a, B, K, st);
+            case ER_FORM_MFMA: return gemv_mfma_groups<WT, EPI_QKV8>(a, B, K, sk, st);
+            case ER_FORM_MFMA_XT: return gemv_mfma_groups<WT, EPI_QKV8, true>(a, B, K, sk, st);
+            default: return hipErrorInvalidValue;
+        }
+    }
+    if (proj == PROJ_QKV && a.kv_half == 2) return hipErrorInvalidValue;      // fp32 weights keep an fp32 cache
     if constexpr (!W8) switch (f.form) {      // the batched forms (never instantiated for the bytes)
         case ER_FORM_ROW: break;
         case ER_FORM_ROWS8:

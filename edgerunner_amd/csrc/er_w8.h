@@ -1,3 +1,6 @@
+// The two 8-bit storage modes, both OCP e4m3fn.  kv8 mode (KV cache): one byte per element and NO scale - kv8_encode below; the
+// post-LN decoder's K/V are O(1), e4m3's own exponent covers 2^-9 .. 448, and a power-of-two row scale would add no relative precision
+// inside that range.
 // Row-scaled 8-bit weight storage (fp8 mode): OCP e4m3fn bytes times a power of two per output row.
 //   e[n]    = the smallest integer with amax(row n) * 2^-e <= 448, clamped to [-15, 7]; a zero row gets -15
 //   q[n][k] = e4m3fn(clamp(w * 2^-e, +-448)), round to nearest even; the NaN bytes 0x7F / 0xFF are never produced
@@ -55,6 +58,14 @@ ER_W8_FN uint8_t w8_encode(float v) {
     const uint32_t rem = m24 & ((1u << s) - 1u), half = 1u << (s - 1);
     if (rem > half || (rem == half && (q & 1u))) ++q;
     return (uint8_t)(sign | q);
+}
+
+// The KV cache's byte (kv8 mode: one e4m3fn byte per element, no scale): w8_encode, and a NaN keeps being one - 0x7F | sign - so that a
+// poisoned activation still reaches the sampling head's NaN guard instead of reading back as 448.
+ER_W8_FN uint8_t kv8_encode(float v) {
+    const uint32_t u = w8_f32_bits(v);
+    if ((u & 0x7fffffffu) > 0x7f800000u) return (uint8_t)(((u >> 24) & 0x80u) | 0x7fu);
+    return w8_encode(v);
 }
 
 // e4m3fn byte -> fp32 (exact); 0x7F / 0xFF are NaN

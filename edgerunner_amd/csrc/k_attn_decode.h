@@ -24,7 +24,7 @@ namespace er {
 
 struct AttnDecArgs {
     const float* q;        // [B][hidden]
-    const void* kcache;    // [B][H][Lcap][D], fp32 or fp16 (the kernel's KT)
+    const void* kcache;    // [B][H][Lcap][D], fp32, fp16 or e4m3 bytes (the kernel's KT)
     const void* vcache;
     const int* pos;        // device, per row: index of the newest key (len = pos+1); or
     int fixed_len;         // >0: use this length for every row instead of pos
@@ -33,7 +33,7 @@ struct AttnDecArgs {
     float* part_ml;        // version 3: [B][H][NCH][2] = {m, l}
     float* out;            // combine: [B][hidden]
     int H, l_cap, S, hidden;   // S = number of chunks the grid covers = ceil(l_cap / chunk)
-    int chunk;             // keys per workgroup (fp32: 32*STEPS, fp16: 64*STEPS with half the steps)
+    int chunk;             // keys per workgroup (fp32: 32*STEPS, fp16: 64*STEPS with half the steps, bytes: 128*STEPS with a quarter)
     long long kv_bstride;
     float sqrt_d;          // sqrt(D): scores are divided by it, as the reference does
     const int* len_src;    // filled by the version-3 launcher: len = len_src[b] + len_add (len_dev + 0, or pos + 1) unless fixed_len > 0
@@ -535,6 +535,12 @@ __device__ __forceinline__ void attn_stream_reduce(const AttnTile<KT, D, STEPS>&
             sc[i][0] = kk < len ? d[0] / sqrt_d : -INFINITY;
             sc[i][1] = kk + 1 < len ? d[1] / sqrt_d : -INFINITY;
             mloc = fmaxf(mloc, fmaxf(sc[i][0], sc[i][1]));
+        } else if constexpr (NK == 4) {           // the quad mapping's four keys, written out the same way
+            sc[i][0] = kk < len ? d[0] / sqrt_d : -INFINITY;
+            sc[i][1] = kk + 1 < len ? d[1] / sqrt_d : -INFINITY;
+            sc[i][2] = kk + 2 < len ? d[2] / sqrt_d : -INFINITY;
+            sc[i][3] = kk + 3 < len ? d[3] / sqrt_d : -INFINITY;
+            mloc = fmaxf(mloc, fmaxf(fmaxf(sc[i][0], sc[i][1]), fmaxf(sc[i][2], sc[i][3])));
         } else {
             sc[i][0] = kk < len ? d[0] / sqrt_d : -INFINITY;
             mloc = fmaxf(mloc, sc[i][0]);
@@ -619,10 +625,14 @@ __global__ __launch_bounds__(ER_WG) void attn_stream_kernel(AttnDecArgs a) {
     }
 }
 
+// kv_half: the cache type - 0 = fp32, 1 = fp16, 2 = e4m3 bytes (D = 96 only; 256-key tiles like the fp16 form: the same bytes in flight per wave)
 template <int D>
-inline hipError_t launch_attn_stream_d(const AttnDecArgs& a, bool kv_half, int B, hipStream_t st) {
+inline hipError_t launch_attn_stream_d(const AttnDecArgs& a, int kv_half, int B, hipStream_t st) {
     const dim3 grid(a.H, B), blk(ER_WG);
-    if (!kv_half) hipLaunchKernelGGL((attn_stream_kernel<float, D, 2>), grid, blk, 0, st, a);
+    if (kv_half == 2) {
+        if constexpr (D == 96) hipLaunchKernelGGL((attn_stream_kernel<kv8_t, D, 2>), grid, blk, 0, st, a);
+        else return hipErrorInvalidValue;
+    } else if (!kv_half) hipLaunchKernelGGL((attn_stream_kernel<float, D, 2>), grid, blk, 0, st, a);
     else hipLaunchKernelGGL((attn_stream_kernel<_Float16, D, 2>), grid, blk, 0, st, a);
     return hipGetLastError();
 }
@@ -638,10 +648,18 @@ inline void launch_attn_partial_t(const AttnDecArgs& a, dim3 grid, hipStream_t s
     else hipLaunchKernelGGL((attn_decode_kernel<KT, D, NS>), grid, dim3(ER_WG), 0, st, a);
 }
 // `steps` is the fp32 step count (chunk = 32*steps keys); fp16 KV uses half as many steps for the same chunk.
+// e4m3 bytes (kv_half == 2): version 2 only, D = 96, the 128-key chunk = one wave-step of 32 keys per wave.
 template <int D>
-inline hipError_t launch_attn_partial_d(const AttnDecArgs& a, int steps, bool kv_half, int B, hipStream_t st, int version = 2) {
+inline hipError_t launch_attn_partial_d(const AttnDecArgs& a, int steps, int kv_half, int B, hipStream_t st, int version = 2) {
     const dim3 grid(a.H, a.S, B);                  // heads fastest: XCD = head mod 8 (see attn_decode_kernel)
-    if (!kv_half) {
+    if (kv_half == 2) {
+        if constexpr (D == 96) {
+            if (version != 2 || steps != ATTN_STEPS_DEFAULT) return hipErrorInvalidValue;
+            hipLaunchKernelGGL((attn_decode2_kernel<kv8_t, D, 1>), grid, dim3(ER_WG), 0, st, a);
+        } else {
+            return hipErrorInvalidValue;
+        }
+    } else if (!kv_half) {
         if (steps == 2) launch_attn_partial_t<float, D, 2>(a, grid, st, version);
         else if (steps == 8) launch_attn_partial_t<float, D, 8>(a, grid, st, version);
         else launch_attn_partial_t<float, D, 4>(a, grid, st, version);

@@ -1,12 +1,14 @@
 // How the lanes of a wave cover the keys of the decode KV cache, and the one pass every wave of the split kernels runs over its keys.
 //
 // KMap<KT, D> is the lane mapping: which 16 bytes of which key row a lane loads, how a wave-step's q.k products come out of those registers,
-// how a wave-step of V is accumulated and how the wave's accumulators are folded into rows of 16 lanes and stored to LDS.  It has two
-// forms - the ROW mapping (fp32 caches, and fp16 caches whose rows are whole 128-byte lines) and the PAIR mapping (fp16 cache, D = 96) -
-// and the kernels of k_attn_decode.h are written once over it.  attn_wave_pass is "load NS wave-steps of K and V, score, soften,
-// accumulate, fold" of the per-wave-softmax kernels; attn_merge4 merges the four waves of a 256-thread workgroup.
+// how a wave-step of V is accumulated and how the wave's accumulators are folded into rows of 16 lanes and stored to LDS.  It has three
+// forms - the ROW mapping (fp32 caches, and fp16 caches whose rows are whole 128-byte lines), the PAIR mapping (fp16 cache, D = 96) and
+// the QUAD mapping (e4m3 byte cache, D = 96) - and the kernels of k_attn_decode.h are written once over it.  attn_wave_pass is "load NS
+// wave-steps of K and V, score, soften, accumulate, fold" of the per-wave-softmax kernels; attn_merge4 merges the four waves of a
+// 256-thread workgroup.
 #pragma once
 #include "er_common.h"
+#include "er_kv8_map.h"
 
 // timeline hooks of scripts/probes/attn_timeline_probe.hip (expand to nothing in the library build)
 #ifndef ER_TP
@@ -214,6 +216,127 @@ struct KMap<KT, D, true> {
     }
 };
 
+// ---- byte cache (kv8 mode, one e4m3fn byte per element, D = 96): lanes mapped over QUADS of key rows.
+//
+// A byte row is 96 bytes, three quarters of a line; four consecutive rows from a key that is a multiple of 4 are three whole lines, so
+// 8 lanes x 3 loads take a quad the way the PAIR mapping takes two fp16 rows: lane p of load j reads the p-th 16 bytes of line j, which is
+// piece (8 j + p) % 6 of row (8 j + p) / 6.  The index arithmetic - slot -> (row, piece), which slots make up a score, how the fold adds
+// the four slots of a piece - is er_kv8_map.h, enumerated on the host by tests/host/kv8_map_check.cpp.  Every slot takes the row index
+// of its own row (a masked key reads a valid row and gets weight 0; 0 x NaN is never formed, so the unused tail may hold anything).
+typedef unsigned char kv8_t;
+
+// 16 e4m3 bytes (element k of the load in byte k) as floats: two packed conversions per dword, as k_gemv.h dot_w8
+__device__ __forceinline__ void kv8_unpack(const f32x4& raw, float (&f)[16]) {
+    typedef float f32x2 __attribute__((ext_vector_type(2)));
+    const int w[4] = {__float_as_int(raw.x), __float_as_int(raw.y), __float_as_int(raw.z), __float_as_int(raw.w)};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const f32x2 a = __builtin_amdgcn_cvt_pk_f32_fp8(w[i], false), b = __builtin_amdgcn_cvt_pk_f32_fp8(w[i], true);
+        f[4 * i] = a.x; f[4 * i + 1] = a.y; f[4 * i + 2] = b.x; f[4 * i + 3] = b.y;
+    }
+}
+
+// v of lane (l + K) mod 8 of the lane's group of 8, for a value that both groups of a row of 16 lanes hold alike (after fold_rows):
+// row_ror:N hands lane l the value of lane (l - N) mod 16
+template <int K>
+__device__ __forceinline__ float quad_from_above(float v) { return row_ror<8 - K>(v); }
+
+template <int D>
+struct KMap<kv8_t, D, false> {
+    static_assert(D == kv8::D, "quad mapping: 96 bytes per row");
+    static constexpr int EPL = kv8::EPL, NV = kv8::NV;
+    static constexpr int KPW = kv8::KPW, NK = kv8::ROWS, GL = kv8::GL;
+    int p, g;
+    bool lo[NV];       // load j holds row j (else row j + 1) in this lane
+    int piece[NV];     // and this piece of it
+    __device__ __forceinline__ explicit KMap(int lane) : p(lane & 7), g(lane >> 3) {
+#pragma unroll
+        for (int j = 0; j < NV; ++j) { lo[j] = p < kv8::load_split(j); piece[j] = kv8::load_piece(j, p); }
+    }
+    __device__ __forceinline__ int key0() const { return NK * g; }
+    __device__ __forceinline__ bool counts() const { return p == 0; }
+    __device__ __forceinline__ void load_q(const float* qp, float (&qv)[NV][EPL]) const {
+#pragma unroll
+        for (int j = 0; j < NV; ++j)
+#pragma unroll
+            for (int e = 0; e < EPL; e += 4) {
+                const f32x4 t = *reinterpret_cast<const f32x4*>(qp + piece[j] * EPL + e);
+                qv[j][e] = t.x; qv[j][e + 1] = t.y; qv[j][e + 2] = t.z; qv[j][e + 3] = t.w;
+            }
+    }
+    __device__ __forceinline__ void load(const kv8_t* base, const int (&row)[NK], f32x4 (&r)[NV]) const {
+#pragma unroll
+        for (int j = 0; j < NV; ++j)
+            r[j] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(base + (long long)(lo[j] ? row[j] : row[j + 1]) * D + piece[j] * EPL));
+    }
+    static __device__ __forceinline__ float dot16(const f32x4& raw, const float (&q)[EPL]) {
+        float f[EPL];
+        kv8_unpack(raw, f);
+        float acc = 0.f;
+#pragma unroll
+        for (int e = 0; e < EPL; ++e) acc = fmaf(q[e], f[e], acc);
+        return acc;
+    }
+    __device__ __forceinline__ void dots(const f32x4 (&k)[NV], const float (&qv)[NV][EPL], float (&s)[NK]) const {
+        const float t[NV] = {dot16(k[0], qv[0]), dot16(k[1], qv[1]), dot16(k[2], qv[2])};
+#pragma unroll
+        for (int r = 0; r < NK; ++r) {         // row r: what kv8::score_takes names of the loads that can hold it (r - 1 and r)
+            float acc = 0.f;
+            bool first = true;
+#pragma unroll
+            for (int j = 0; j < NV; ++j) {
+                if (!kv8::score_load(r, j)) continue;
+                const float term = kv8::score_takes(r, j, p) ? t[j] : 0.f;
+                acc = first ? term : acc + term;
+                first = false;
+            }
+            s[r] = lane_group_sum<8>(acc);
+        }
+    }
+    // the accumulator kv8::fold_load(I, p) names for fold term I of this lane: one of two registers, picked by a select (no indexing)
+    template <int I>
+    __device__ __forceinline__ float fold_term(const float (&o)[NV][EPL], int e) const {
+        constexpr int A = kv8::fold_load(I, 0), B = kv8::fold_load(I, GL - 1);
+        static_assert(kv8::fold_load_two_valued(I), "a fold term sends one of two accumulators");
+        if constexpr (A == B) return o[A][e];
+        else return kv8::fold_load(I, p) == A ? o[A][e] : o[B][e];
+    }
+    static __device__ __forceinline__ float wsum(const float (&w)[NK]) { return (w[0] + w[1]) + (w[2] + w[3]); }
+    __device__ __forceinline__ void accum(const f32x4 (&v)[NV], const float (&w)[NK], float (&o)[NV][EPL]) const {
+#pragma unroll
+        for (int j = 0; j < NV; ++j) {
+            const float wj = lo[j] ? w[j] : w[j + 1];
+            float f[EPL];
+            kv8_unpack(v[j], f);
+#pragma unroll
+            for (int e = 0; e < EPL; ++e) o[j][e] = fmaf(wj, f[e], o[j][e]);
+        }
+    }
+    __device__ __forceinline__ void fold_rows(float (&o)[NV][EPL]) const {
+#pragma unroll
+        for (int j = 0; j < NV; ++j)
+#pragma unroll
+            for (int e = 0; e < EPL; ++e) o[j][e] += row_ror<8>(o[j][e]);
+    }
+    // every piece sits in four (lane, load) slots 2 lanes apart: all lanes fold - term i is the accumulator kv8::fold_load(i, sender)
+    // of the lane kv8::fold_shift(i) above - and the lanes kv8::fold_stores names store their piece (active: the row's first group)
+    __device__ __forceinline__ void store(const float (&o)[NV][EPL], float* dst, bool active) const {
+        static_assert(kv8::FOLD_TERMS == 4 && kv8::fold_shift(0) == 0, "the fold is written out for its four terms");
+        float om[EPL];
+#pragma unroll
+        for (int e = 0; e < EPL; ++e) {
+            const float s1 = quad_from_above<kv8::fold_shift(1)>(fold_term<1>(o, e));
+            const float s2 = quad_from_above<kv8::fold_shift(2)>(fold_term<2>(o, e));
+            const float s3 = quad_from_above<kv8::fold_shift(3)>(fold_term<3>(o, e));
+            om[e] = (fold_term<0>(o, e) + s1) + (s2 + s3);
+        }
+        if (active && kv8::fold_stores(p)) {
+#pragma unroll
+            for (int e = 0; e < EPL; ++e) dst[kv8::store_piece(p) * EPL + e] = om[e];
+        }
+    }
+};
+
 // the wave's accumulators as four rows of D floats (one per row of 16 lanes) at ored[(wid * 4 + row) * LD]
 template <int LD, typename M>
 __device__ __forceinline__ void attn_fold_store(const M& m, float (&o)[M::NV][M::EPL], float* ored, int wid, int lane) {
@@ -274,6 +397,12 @@ __device__ __forceinline__ void attn_wave_pass(const A& a, const KT* kb, const K
             sc[i][0] = valid[i][0] ? d[0] / a.sqrt_d : -INFINITY;
             sc[i][1] = valid[i][1] ? d[1] / a.sqrt_d : -INFINITY;
             mloc = fmaxf(mloc, fmaxf(sc[i][0], sc[i][1]));
+        } else if constexpr (NK == 4) {           // the quad mapping's four keys, written out the same way
+            sc[i][0] = valid[i][0] ? d[0] / a.sqrt_d : -INFINITY;
+            sc[i][1] = valid[i][1] ? d[1] / a.sqrt_d : -INFINITY;
+            sc[i][2] = valid[i][2] ? d[2] / a.sqrt_d : -INFINITY;
+            sc[i][3] = valid[i][3] ? d[3] / a.sqrt_d : -INFINITY;
+            mloc = fmaxf(mloc, fmaxf(fmaxf(sc[i][0], sc[i][1]), fmaxf(sc[i][2], sc[i][3])));
         } else {
             sc[i][0] = valid[i][0] ? d[0] / a.sqrt_d : -INFINITY;
             mloc = fmaxf(mloc, sc[i][0]);

@@ -25,7 +25,12 @@
 namespace er {
 
 enum { PRO_NONE = 0, PRO_LN = 1, PRO_EMBED = 2 };
-enum { EPI_STORE = 0, EPI_RELU = 1, EPI_RESID = 2, EPI_QKV = 3 };
+// EPI_QKV8: EPI_QKV into an e4m3 byte cache (kv8 mode).  The cache type is a compile-time property of the epilogue: as a run-time
+// branch the encoder's ~75 instructions per (row, batch row) sat in the tail of every fp16-cache QKV kernel and cost fast mode's qkv
+// launch 0.12 us (4.90 -> 5.03; profiles/kv8_ab_decode.log), so the fp32 / fp16-cache kernels keep their code and the byte cache
+// gets instantiations of its own.
+enum { EPI_STORE = 0, EPI_RELU = 1, EPI_RESID = 2, EPI_QKV = 3, EPI_QKV8 = 4 };
+constexpr bool epi_qkv(int epi) { return epi == EPI_QKV || epi == EPI_QKV8; }
 
 struct GemvArgs {
     const void* W;         // [N][K] in the kernel's weight type
@@ -47,7 +52,7 @@ struct GemvArgs {
     float* q;              // EPI_QKV: [NB][hidden]
     void* kcache;          //          [B][H][Lcap][D] (this layer), fp32 or fp16
     void* vcache;
-    int kv_half;           //          1: the cache holds _Float16
+    int kv_half;           //          the cache type: 0 = fp32, 1 = _Float16, 2 = e4m3 bytes (kv8 mode, er_w8.h kv8_encode: launched as EPI_QKV8)
     int hidden, head_dim, l_cap;
     long long kv_bstride;  // H*Lcap*D
     // fast-mode batches on the matrix cores (k_gemv_mfma.h, XT): activations exchanged in the matrix cores' own operand layout
@@ -134,6 +139,9 @@ __device__ __forceinline__ float dot_w8(const er_u32x2& wraw, const f32x4* x, fl
 // prologue's first barrier sat out the whole memory round trip of that load (the ~0.9 us the qkv launch was above fc1's shape for
 // shape, round 3).  pos[b] is therefore read with a VECTOR load (an opaque zero in the index keeps hipcc from proving the address
 // uniform): it queues first in vmcnt order and nobody waits for it before the tail.
+// bytes per element of the cache type GemvArgs::kv_half names
+__host__ __device__ __forceinline__ int kv_elem_bytes(int kv_half) { return kv_half == 2 ? 1 : kv_half ? 2 : 4; }
+
 struct EpiPre { float bias; float resid; char* dst; int half; int pos; int pos_scale; };   // final address = dst + pos * pos_scale
 
 __device__ __forceinline__ int opaque_zero() {
@@ -151,21 +159,21 @@ __device__ __forceinline__ EpiPre gemv_epi_loads(const GemvArgs& a, int n, int b
     n = min(n, a.N - 1);
     if (a.bias) e.bias = a.bias[n];
     if (EPI == EPI_RESID) e.resid = a.resid[(long long)b * a.N + n];
-    if (EPI == EPI_QKV) e.pos = a.pos[b + opaque_zero()];      // in flight until the tail: nothing before it may depend on it
+    if (epi_qkv(EPI)) e.pos = a.pos[b + opaque_zero()];      // in flight until the tail: nothing before it may depend on it
     return e;
 }
 
 template <int EPI>
 __device__ __forceinline__ void gemv_epi_address(const GemvArgs& a, int n, int b, EpiPre& e) {
     n = min(n, a.N - 1);
-    if (EPI == EPI_QKV) {   // rows [0,hidden) = q, [hidden,2h) = k, [2h,3h) = v
+    if (epi_qkv(EPI)) {   // rows [0,hidden) = q, [hidden,2h) = k, [2h,3h) = v
         const int which = n / a.hidden;
         const int c = n - which * a.hidden;
         if (which == 0) {
             e.dst = reinterpret_cast<char*>(a.q + (long long)b * a.hidden + c);
         } else {
             const int h = c / a.head_dim, d = c - h * a.head_dim;
-            const int esz = a.kv_half ? 2 : 4;
+            const int esz = EPI == EPI_QKV8 ? 1 : a.kv_half ? 2 : 4;
             char* cache = reinterpret_cast<char*>((which == 1) ? a.kcache : a.vcache);
             e.dst = cache + ((long long)b * a.kv_bstride + (long long)h * a.l_cap * a.head_dim + d) * esz;
             e.pos_scale = a.head_dim * esz;
@@ -192,8 +200,9 @@ __device__ __forceinline__ void gemv_epilogue(const GemvArgs& a, int n, int b, f
     if (EPI == EPI_RELU) v = fmaxf(v, 0.0f);
     if (EPI == EPI_RESID) v += e.resid;
     char* dst = e.dst;
-    if (EPI == EPI_QKV) dst += (long long)e.pos * e.pos_scale;
-    if (EPI == EPI_QKV && e.half) *reinterpret_cast<_Float16*>(dst) = (_Float16)v;     // round-to-nearest-even
+    if (epi_qkv(EPI)) dst += (long long)e.pos * e.pos_scale;
+    if (EPI == EPI_QKV8 && e.half) *reinterpret_cast<unsigned char*>(dst) = kv8_encode(v);      // saturate, round to nearest even, NaN stays NaN
+    else if (EPI == EPI_QKV && e.half) *reinterpret_cast<_Float16*>(dst) = (_Float16)v;     // round-to-nearest-even
     else *reinterpret_cast<float*>(dst) = v;
 }
 

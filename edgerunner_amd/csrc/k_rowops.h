@@ -3,6 +3,7 @@
 // row fits in registers.
 #pragma once
 #include "er_common.h"
+#include "er_w8.h"
 
 namespace er {
 
@@ -178,6 +179,30 @@ __global__ __launch_bounds__(ER_WG) void kv_scatter_half_kernel(float* qkv, _Flo
         *src = (f32x4){(float)hv[0], (float)hv[1], (float)hv[2], (float)hv[3]};
         *reinterpret_cast<h4*>(cache + (long long)b * kv_bstride + ((long long)h * l_cap + s) * head_dim + d) = hv;
     }
+}
+// kv8 mode: the same move into the byte cache (one e4m3fn byte per element, er_w8.h kv8_encode), the scratch rounded in place to
+// decode(encode(v)) - every e4m3 value is an fp16 value, so the prefix attention runs as in fast mode.  Four columns per thread, one
+// 4-byte store (head_dim % 4 == 0: 4-byte aligned).
+__global__ __launch_bounds__(ER_WG) void kv_scatter_f8_kernel(float* qkv, unsigned char* kcache, unsigned char* vcache, int M,
+                                                              int S, int hidden, int head_dim, int l_cap,
+                                                              long long kv_bstride) {
+    const int c2 = (blockIdx.x * ER_WG + threadIdx.x) * 4;
+    if (c2 >= 2 * hidden) return;
+    const int which = c2 >= hidden ? 1 : 0, c = c2 - which * hidden;       // 0 = K, 1 = V
+    const int h = c / head_dim, d = c - h * head_dim;
+    unsigned char* cache = which == 0 ? kcache : vcache;
+    for (int m = blockIdx.y; m < M; m += gridDim.y) {
+        const int b = m / S, s = m - b * S;
+        f32x4* src = reinterpret_cast<f32x4*>(qkv + (long long)m * 3 * hidden + hidden + c2);
+        const f32x4 v = *src;
+        const unsigned b0 = kv8_encode(v.x), b1 = kv8_encode(v.y), b2 = kv8_encode(v.z), b3 = kv8_encode(v.w);
+        *src = (f32x4){w8_decode((unsigned char)b0), w8_decode((unsigned char)b1), w8_decode((unsigned char)b2), w8_decode((unsigned char)b3)};
+        *reinterpret_cast<unsigned*>(cache + (long long)b * kv_bstride + ((long long)h * l_cap + s) * head_dim + d) = b0 | (b1 << 8) | (b2 << 16) | (b3 << 24);
+    }
+}
+// the device encoder on a flat array (er_k_kv8_encode: the unit entry of what the producers store)
+__global__ __launch_bounds__(ER_WG) void kv8_encode_kernel(const float* src, unsigned char* dst, long long n) {
+    for (long long i = (long long)blockIdx.x * ER_WG + threadIdx.x; i < n; i += (long long)gridDim.x * ER_WG) dst[i] = kv8_encode(src[i]);
 }
 inline dim3 kv_scatter_grid(int M, int hidden) {
     return dim3((unsigned)((2 * hidden / 4 + ER_WG - 1) / ER_WG), (unsigned)(M < 65535 ? (M > 0 ? M : 1) : 65535));

@@ -28,14 +28,36 @@ def gemv(w, x, bias=None, ln_w=None, ln_b=None, resid=None, relu=False, eps=1e-5
 
 
 def attn_decode(q, k_cache, v_cache, lens, steps=4, variant=native.ER_ATTN_SPLIT2):
-    """q [B,H*D] fp32; caches [B,H,Lcap,D] fp32 or fp16; lens: list[int] -> out [B,H*D].
+    """q [B,H*D] fp32; caches [B,H,Lcap,D] fp32, fp16 or e4m3 bytes (uint8 / float8_e4m3fn: ER_ATTN_SPLIT2 and ER_ATTN_STREAM, D = 96);
+    lens: list[int] -> out [B,H*D].
     variant: native.ER_ATTN_SPLIT2 (single-row fallback), ER_ATTN_SPLIT1 (mid-size batches) or ER_ATTN_STREAM (B * heads >= 256)."""
     lib = native.load_library()
     B, H, Lcap, D = k_cache.shape
     out = torch.empty((B, H * D), dtype=torch.float32, device=q.device)
     native.check(lib.er_k_attn_decode(native.ptr(q), native.ptr(k_cache), native.ptr(v_cache), native.i32_array(lens),
-                                      native.ptr(out), B, H, D, Lcap, steps, int(k_cache.dtype == torch.float16), int(variant), _st()),
+                                      native.ptr(out), B, H, D, Lcap, steps, kv_type(k_cache), int(variant), _st()),
                  "er_k_attn_decode")
+    return out
+
+
+def kv_type(cache):
+    """The kernels' cache type argument (kv_half) of a cache tensor: 0 = fp32, 1 = fp16, 2 = e4m3 bytes (uint8 or float8_e4m3fn)."""
+    if cache.dtype == torch.float32:
+        return 0
+    if cache.dtype == torch.float16:
+        return 1
+    assert cache.dtype in (torch.uint8, torch.float8_e4m3fn), cache.dtype
+    return 2
+
+
+def kv8_encode(x):
+    """The device encoder of the byte KV cache on an fp32 device tensor (``er_k_kv8_encode``): uint8 of x's shape, one e4m3fn byte per
+    element - saturating at +-448, round to nearest even, the sign of zero and NaN kept (csrc/er_w8.h kv8_encode)."""
+    assert x.dtype == torch.float32 and x.is_cuda
+    x = x.contiguous()
+    out = torch.empty(x.shape, dtype=torch.uint8, device=x.device)
+    if x.numel():
+        native.check(native.load_library().er_k_kv8_encode(native.ptr(x), native.ptr(out), x.numel(), _st()), "er_k_kv8_encode")
     return out
 
 
@@ -78,7 +100,7 @@ def gemv_form(form, epilogue, w, B, *, x=None, bias=None, ln=None, embed=None, s
       embed=(embd [V, k], posemb [P, k], tok, pos)   token + position rows (tok / pos: B ints)
       ln=... with sk=(part, bias [k], resid [B, k], slices)   LayerNorm over a deferred split-K finish
       none of them                             x itself - in the tiled forms (ER_FORM_NARROW*) x is xt_pack_image of the input
-    qkv=(kcache, vcache, pos[, q_out]) for ER_EPI_QKV: caches [B, heads, l_cap, head_dim] fp32 or fp16 are written in place at
+    qkv=(kcache, vcache, pos[, q_out]) for ER_EPI_QKV: caches [B, heads, l_cap, head_dim] fp32, fp16 or uint8 (e4m3 bytes) are written in place at
     pos[b].  prep_xt: also return the image the batched prologue launch writes (prep_xt_image: write into this one);
     xt_out_image: the image the tiled fc1 writes (allocated zeroed when the form needs one).
     w8=(q uint8 [n, k], wscale fp32 [n]): the row form on e4m3 bytes and row scales in place of w (``er_k_gemv_form_w8``; gemv_form_w8).
@@ -127,7 +149,7 @@ def gemv_form(form, epilogue, w, B, *, x=None, bias=None, ln=None, embed=None, s
     if epilogue == native.ER_EPI_QKV and form != native.ER_FORM_PREP:
         kc, vc, pos = qkv[:3]
         _, heads, l_cap, hd = kc.shape
-        assert kc.shape == vc.shape and kc.shape[0] == B and kc.dtype == vc.dtype and kc.dtype in (torch.float32, torch.float16)
+        assert kc.shape == vc.shape and kc.shape[0] == B and kc.dtype == vc.dtype and kc.dtype in (torch.float32, torch.float16, torch.uint8, torch.float8_e4m3fn)
         pos_d = _i32_dev(pos, dev, l_cap, "cache position")
         assert len(pos_d) == B
         out["q"] = qkv[3] if len(qkv) > 3 else torch.empty((B, heads * hd), dtype=torch.float32, device=dev)
@@ -135,7 +157,7 @@ def gemv_form(form, epilogue, w, B, *, x=None, bias=None, ln=None, embed=None, s
         keep += [pos_d]
         a.pos = native.ptr(pos_d).value      # the decode step feeds the embedding and the cache append the same positions
         a.q_out, a.kcache, a.vcache = native.ptr(out["q"]).value, native.ptr(kc).value, native.ptr(vc).value
-        a.kv_half, a.heads, a.head_dim, a.l_cap = int(kc.dtype == torch.float16), heads, hd, l_cap
+        a.kv_half, a.heads, a.head_dim, a.l_cap = kv_type(kc), heads, hd, l_cap
     elif form == native.ER_FORM_NARROW_DEFER:
         out["part"] = torch.empty(((B + 31) // 32, (k // 384) * 32 * n), dtype=torch.float32, device=dev)
         a.part_out = native.ptr(out["part"]).value

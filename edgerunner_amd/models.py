@@ -129,17 +129,30 @@ class _DecoderModel:
         self.embd = _Embd(dec)
 
 
+_KV8_RULE = ("kv_precision='fp8' (the e4m3 KV cache) goes with precision 'fp16' or 'fp8' only: exact mode (fp32 weights) keeps an fp32 cache. "
+             "Use LMM(opt, device, precision='fp16', kv_precision='fp8'), or call .half() / .fp8() in module style.")
+
+
 class LMM:
-    def __init__(self, opt, device="cuda:0", precision: Optional[str] = "fp32"):
+    def __init__(self, opt, device="cuda:0", precision: Optional[str] = "fp32", kv_precision: Optional[str] = None):
         """precision: 'fp32' = exact mode (fp32 weights + KV; greedy ids bit-exact vs the CPU path), 'fp16' = fast mode
         (decoder matrices and KV cache stored in fp16 like the reference's ``model.half()`` GPU path, fp32 accumulate),
         'fp8' = fast mode on a checkpoint whose q / k / v / out_proj / fc1 / fc2 matrices are rounded to e4m3 times a power of two
         per output row (csrc/er_w8.h; the single-row decode projections stream the bytes), or None = module style: fp32 until ``.half()`` is called, the native context being created on first use, so
         that the reference's ``LMM(opt)`` -> ``load_state_dict`` -> ``.half().eval().to(device)`` (infer.py:41-56)
-        selects the fp16 context exactly as it selects fp16 storage there."""
+        selects the fp16 context exactly as it selects fp16 storage there.
+
+        kv_precision: None = the KV cache in the precision's own activation dtype (fp32 / fp16), 'fp8' = one e4m3 byte per cached
+        element without a scale (kv8 mode: half the cache bytes of fp16; head_dim 96).  The byte cache goes with 'fp16' or 'fp8'
+        weights only: with 'fp32', or in module style once ``.float()`` selects fp32, it raises ValueError."""
         self.opt = opt
         if precision not in (None, "fp32", "fp16", "fp8"):
             raise ValueError(precision)
+        if kv_precision not in (None, "fp8"):
+            raise ValueError(f"kv_precision={kv_precision!r}: None (the cache follows precision) or 'fp8'")
+        if kv_precision == "fp8" and precision == "fp32":
+            raise ValueError(_KV8_RULE)
+        self._kv8 = kv_precision == "fp8"
         if opt.cond_mode == "image":
             raise NotImplementedError("cond_mode='image' (CLIP conditioner) is outside the ArAE decode path")
         if opt.cond_mode == "point" and opt.point_encoder_mode not in ("embed", "downsample"):
@@ -174,11 +187,19 @@ class LMM:
     def precision(self) -> str:
         return "fp8" if self._w8 else "fp16" if self._dtype == torch.float16 else "fp32"
 
+    @property
+    def kv_precision(self) -> Optional[str]:
+        """'fp8' when the KV cache holds e4m3 bytes (kv8 mode), else None: the cache is stored in the precision's activation dtype."""
+        return "fp8" if self._kv8 else None
+
     def _materialize(self):
+        if self._kv8 and self._dtype != torch.float16:
+            raise ValueError(_KV8_RULE)
         if self._released:
             raise native.NativeError("LMM: the checkpoint was released (release_checkpoint()) and the native context is gone; "
                                      "create a new LMM and load the checkpoint again")
-        dec = NativeShapeOPT(self.dims, self.opt, self.device, weight_dtype="fp8" if self._w8 else self._dtype, kv_dtype=self._dtype)
+        dec = NativeShapeOPT(self.dims, self.opt, self.device, weight_dtype="fp8" if self._w8 else self._dtype,
+                             kv_dtype="fp8" if self._kv8 else self._dtype)
         dec.model = _DecoderModel(dec)
         for sd, strict in self._sources:
             dec.load_state_dict(sd, strict=strict)
@@ -219,6 +240,8 @@ class LMM:
         return self
 
     def _cast(self, dtype, w8: bool = False):
+        if self._kv8 and dtype != torch.float16:
+            raise ValueError(_KV8_RULE)
         if dtype == self._dtype and w8 == self._w8:
             return self
         if self._dec is not None and self._dec.direct_loads:

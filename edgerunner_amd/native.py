@@ -37,7 +37,7 @@ EXPORTS = [
     "er_k_nn_dist2", "er_k_surface_sample", "er_k_fidelity_metrics",
     "er_queue_begin", "er_queue_admit", "er_queue_run", "er_queue_take", "er_queue_stats", "er_queue_end",
     "er_set_sampling", "er_get_logprobs", "er_queue_row_logprobs", "er_k_sample_head_ctl",
-    "er_k_w8_quantize", "er_k_gemv_form_w8", "er_k_attn_outproj3_w8",
+    "er_k_w8_quantize", "er_k_gemv_form_w8", "er_k_attn_outproj3_w8", "er_k_kv8_encode",
 ]
 
 
@@ -190,6 +190,7 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.er_k_attn_decode.argtypes = [vp, vp, vp, C.POINTER(C.c_int32), vp, ci, ci, ci, ci, ci, ci, ci, vp]
     lib.er_k_attn_outproj3.argtypes = [vp, vp, vp, ci, vp, vp, vp, vp, ci, ci, ci, vp]
     lib.er_k_w8_quantize.argtypes = [vp, ci, ci, ci, ci, vp, vp, vp, vp, vp]
+    lib.er_k_kv8_encode.argtypes = [vp, vp, C.c_longlong, vp]
     lib.er_k_gemv_form_w8.argtypes = [C.POINTER(ErKGemvFormArgs), vp, vp, vp]
     lib.er_k_attn_outproj3_w8.argtypes = [vp, vp, vp, ci, vp, vp, vp, vp, vp, ci, ci, vp]
     lib.er_k_gemm.argtypes = [vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, cf, vp]

@@ -45,10 +45,13 @@ typedef enum {
 } er_status;
 
 /* Element types.  As the dtype of a CHECKPOINT tensor handed to er_load_tensor / er_dit_load_tensor all three are accepted
- * (converted on the device).  As a context's STORAGE precision (er_config.weight_dtype / kv_dtype) three combinations are
+ * (converted on the device).  As a context's STORAGE precision (er_config.weight_dtype / kv_dtype) five combinations are
  * built: ER_F32 + ER_F32 (exact mode), ER_F16 + ER_F16 (fast mode, the reference's GPU dtype) and ER_F8E4M3 + ER_F16 (fp8 mode:
  * fast mode with the q / k / v / out_proj / fc1 / fc2 matrices of every decoder layer stored as OCP e4m3fn bytes times 2^e per
- * output row, csrc/er_w8.h; it computes what fast mode computes on a checkpoint rounded that way).  Every other combination, ER_BF16
+ * output row, csrc/er_w8.h; it computes what fast mode computes on a checkpoint rounded that way), and ER_F16 + ER_F8E4M3 and
+ * ER_F8E4M3 + ER_F8E4M3 (kv8: fast or fp8 mode with the KV cache stored as one OCP e4m3fn byte per element and no scale -
+ * saturating at +-448, round to nearest even, NaN kept, csrc/er_w8.h kv8_encode; head_dim 96 only; single rows decode with version 2,
+ * every batched shape with ER_ATTN_STREAM, er_set_prefix_groups is ER_ERR_UNSUPPORTED).  Every other combination, ER_BF16
  * storage included, is rejected by er_create with ER_ERR_UNSUPPORTED.  ER_F8E4M3 is a storage mode only, never a checkpoint dtype. */
 typedef enum { ER_F32 = 0, ER_F16 = 1, ER_BF16 = 2, ER_F8E4M3 = 3 } er_dtype;
 typedef enum { ER_COND_NONE = 0, ER_COND_POINT = 1, ER_COND_POINT_LATENT = 2 } er_cond_mode;
@@ -401,7 +404,9 @@ int er_k_gemv(const float* w_dev, const float* bias_dev, const float* x_dev, con
 /* softmax(q K^T / sqrt(D)) V for one new token over a [B,H,Lcap,D] cache holding len[b] keys;
  * steps in {2,4,8}: one workgroup per chunk of 32*steps keys (split kernels); variant = ER_ATTN_SPLIT2 (the single-row fallback:
  * per-wave softmax + one-round-trip merge kernel), ER_ATTN_SPLIT1 (the leaner split kernel of mid-size batches + the same merge)
- * or ER_ATTN_STREAM (one workgroup per (row, head) walks the whole key range, head_dim 96 only) */
+ * or ER_ATTN_STREAM (one workgroup per (row, head) walks the whole key range, head_dim 96 only).  kv_half, here and in
+ * er_k_attn_stream_xt and er_k_gemv_form_args, names the cache type: 0 = fp32, 1 = fp16, 2 = e4m3 bytes (head_dim 96; of the
+ * attention variants ER_ATTN_SPLIT2 with steps 4 and ER_ATTN_STREAM read bytes) */
 int er_k_attn_decode(const float* q_dev, const void* k_dev, const void* v_dev, const int32_t* len_host,
                      float* out_dev, int batch, int heads, int head_dim, int l_cap, int steps, int kv_half,
                      int variant, void* stream);
@@ -439,7 +444,7 @@ typedef struct {
     float* y;                  /* [B][n] (EPI_STORE / RELU / RESID) */
     const float* resid;        /* EPI_RESID: [B][n] */
     float* q_out;              /* EPI_QKV: [B][k] */
-    void *kcache, *vcache;     /* EPI_QKV: [B][heads][l_cap][head_dim], fp32 or (kv_half) fp16; row pos[b] is written */
+    void *kcache, *vcache;     /* EPI_QKV: [B][heads][l_cap][head_dim], fp32, (kv_half 1) fp16 or (kv_half 2) e4m3 bytes; row pos[b] is written */
     void* prep_xt_out;         /* tiled image the batched prologue launch also writes (fp16 weights; caller zeroes it), nullable */
     void* xt_out;              /* ER_FORM_MFMA_XT fc1: the tiled image of the output, n * 128 bytes per 32 rows (caller zeroes it) */
     float* part_out;           /* ER_FORM_NARROW_DEFER: [groups][k / 384][rows of the group][n]; group g starts g * (k / 384) * 32 * n floats in */
@@ -508,6 +513,9 @@ int er_k_gemv_form_w8(const er_k_gemv_form_args* args, const void* q_dev, const 
 int er_k_attn_outproj3_w8(const float* q_dev, const void* k_dev, const void* v_dev, int len, const void* wo_q_dev,
                           const float* wo_scale_dev, const float* bo_dev, const float* resid_dev, float* y_dev, int l_cap,
                           int kv_half, void* stream);
+/* The device encoder of the byte KV cache (kv8; csrc/er_w8.h kv8_encode, what the K/V producers store with) on n fp32 values in
+ * device memory: dst_dev receives n e4m3fn bytes.  Blocks. */
+int er_k_kv8_encode(const float* src_dev, void* dst_dev, long long n, void* stream);
 /* C[M,N] = A[M,K] op(B) (+bias)(relu)(+resid); b_is_kn=0: B is [N,K] (Linear weight), 1: B is [K,N] */
 int er_k_gemm(const float* a_dev, const float* b_dev, const float* bias_dev, const float* resid_dev,
               float* c_dev, int m, int n, int k, int lda, int ldb, int ldc, int b_is_kn, int relu,

@@ -115,7 +115,7 @@ def max_rows_per_call(opt, model, max_new_tokens, device) -> int:
     the rows' KV cache + prefill / encoder scratch must fit in the HBM that is free once the weights are resident (the native
     context is created here, before the measurement)."""
     d = model.dims
-    esz = 4 if model.precision == "fp32" else 2      # fp16 and fp8 keep an fp16 cache
+    esz = 4 if model.precision == "fp32" else 1 if model.kv_precision == "fp8" else 2      # fp16 and fp8 keep an fp16 cache unless EDGERUNNER_KV_PRECISION=fp8
     l_cap = d.num_cond_tokens + 2 + max_new_tokens
     kv_row = 2 * d.num_layers * d.hidden_dim * esz * l_cap
     scratch_row = (d.num_cond_tokens + 1) * (6 * d.hidden_dim + d.intermediate_dim) * 4
@@ -142,6 +142,8 @@ def main(argv=None):
     share_prefix = os.environ.get("ER_INFER_SHARE_PREFIX") == "1"
     if share_prefix and os.environ.get("ER_INFER_QUEUE") == "1":
         raise SystemExit("[ERROR] ER_INFER_SHARE_PREFIX=1 and ER_INFER_QUEUE=1 cannot be combined: prefix groups are not built for queue mode")
+    if share_prefix and os.environ.get("EDGERUNNER_KV_PRECISION") == "fp8":
+        raise SystemExit("[ERROR] ER_INFER_SHARE_PREFIX=1 and EDGERUNNER_KV_PRECISION=fp8 cannot be combined: the shared-prefix kernels read fp32 and fp16 caches only")
     rank, world, local = D.init_process_group()
     seed_everything(opt.seed)
     if opt.cond_mode not in ("point", "none"):
@@ -153,7 +155,8 @@ def main(argv=None):
         raise SystemExit("no HIP device visible: this path has no CPU fallback")
     device = torch.device("cuda", local)
     torch.cuda.set_device(device)
-    model = LMM(opt, device, precision=None)          # module style: storage precision follows .half() / .float()
+    # module style: storage precision follows .half() / .float(); EDGERUNNER_KV_PRECISION=fp8 stores the KV cache as e4m3 bytes (fp16 / fp8 weights only)
+    model = LMM(opt, device, precision=None, kv_precision=os.environ.get("EDGERUNNER_KV_PRECISION") or None)
     if opt.resume is not None:
         if opt.resume.endswith("safetensors"):
             from safetensors.torch import load_file

@@ -41,7 +41,8 @@ def main(argv=None):
         raise SystemExit("no HIP device visible: this path has no CPU fallback")
     device = torch.device("cuda", 0)
     torch.cuda.set_device(device)
-    model = LMM(opt, device, precision=None)
+    # EDGERUNNER_KV_PRECISION=fp8: the KV cache as e4m3 bytes - what that costs THIS checkpoint, against the fp16 run's loss
+    model = LMM(opt, device, precision=None, kv_precision=os.environ.get("EDGERUNNER_KV_PRECISION") or None)
     if opt.resume is not None:
         if opt.resume.endswith("safetensors"):
             from safetensors.torch import load_file
@@ -101,7 +102,7 @@ def main(argv=None):
     print(f"[INFO] mean over {len(per_mesh)} meshes: loss_ce = {mean['loss_ce']:.6f}, ppl = {mean['perplexity']:.4f}, "
           f"acc = {mean['accuracy']:.4f}")
     with open(os.path.join(opt.workspace, "scores.json"), "w") as f:
-        json.dump({"precision": model.precision, "meshes": per_mesh, "mean": mean}, f, indent=1)
+        json.dump({"precision": model.precision, "kv_precision": model.kv_precision, "meshes": per_mesh, "mean": mean}, f, indent=1)
 
 
 if __name__ == "__main__":
