@@ -20,6 +20,7 @@
 #include "k_attn_lanes.h"
 #include "k_attn_decode.h"
 #include "k_attn_shared.h"
+#include "k_attn_shared_mfma.h"
 #include "k_outproj_merge.h"
 #include "k_flash_attn_f16s.h"
 #include "k_gemm.h"
@@ -241,6 +242,8 @@ static DecodeKnobs read_knobs(bool fast) {
     // of launches lost its A/B (1542 -> 1501 tok/s decode, profiles/mlp_sparse_ab_decode.log)
     k.mlp_v = env_int("ER_MLP_V", fast ? 0 : 1);
     if (k.mlp_v != 1) k.mlp_v = 0;
+    const char* pp = getenv("ER_PREFIX_PASS");      // valu | mfma; er_create keeps "mfma" for an fp16 cache only (er_set_prefix_pass)
+    k.prefix_pass = (pp && !strcmp(pp, "mfma")) ? ER_PREFIX_PASS_MFMA : ER_PREFIX_PASS_VALU;
     return k;
 }
 
@@ -349,6 +352,7 @@ extern "C" int er_create(const er_config* cfg, int device, er_ctx** out) {
     c->pe.PH = cfg->point_hidden_dim; c->pe.heads = cfg->point_num_heads; c->pe.Lq = cfg->point_latent_size;
     c->pe.LD = cfg->point_latent_dim; c->pe.freq = cfg->point_freq_dim; c->pe.eps = cfg->ln_eps;
     c->knobs = read_knobs(fast);
+    if (c->kv_type != 1) c->knobs.prefix_pass = ER_PREFIX_PASS_VALU;      // the matrix-core prefix pass reads fp16 caches only
     HIPCHK(hipStreamCreateWithFlags(&c->own_stream, hipStreamDefault));
     HIPCHK(hipEventCreate(&c->ev0));
     HIPCHK(hipEventCreate(&c->ev1));
@@ -640,6 +644,7 @@ static hipError_t launch_kind_t(er_ctx* c, int kind, int layer, hipStream_t st, 
         // worth of work (B > 4) the leaner v1 (66-74 VGPRs, 6-7 waves per SIMD) streams faster: 570 vs 636 us at B = 32, L = 18050
         case 1:
             if (v3) return launch_attn_partial3_d<96>(attn_args(c, layer), HALF, p.nch3, B, st);
+            if (p.shared_mfma) return launch_attn_prefix_mfma_d<96>(attn_shared_args(c, layer), kv.n_groups, st);
             if (p.shared_attn) return launch_attn_prefix_d<96>(attn_shared_args(c, layer), HALF, kv.n_groups, st);
             if (p.stream_attn) return launch_attn_stream_d<96>(attn_args(c, layer), c->kv_type, B, st);
             return launch_attn_partial(attn_args(c, layer), c->D, ATTN_STEPS_DEFAULT, c->kv_type, B, st, p.batched ? 1 : 2);
@@ -1191,6 +1196,19 @@ extern "C" int er_set_prefix_groups(er_ctx* c, const int32_t* leader, int n, int
     kv.grp_leader.assign(leader, leader + B);
     kv.n_groups = (int)off.size() - 1;
     kv.prefix_len = prefix_len;
+    return ER_OK;
+}
+
+// The prefix pass of the next grouping: a knob of the context, read by make_decode_plan when er_set_prefix_groups derives the plan again
+// (the plan and the captured step of groups that are set now stay as they are until then).
+extern "C" int er_set_prefix_pass(er_ctx* c, int pass) {
+    if (!c) return fail(ER_ERR_INVALID, "er_set_prefix_pass: null context");
+    if (pass != ER_PREFIX_PASS_VALU && pass != ER_PREFIX_PASS_MFMA) return fail(ER_ERR_INVALID, "er_set_prefix_pass: pass %d is neither ER_PREFIX_PASS_VALU nor ER_PREFIX_PASS_MFMA", pass);
+    if (c->q.active) return fail(ER_ERR_INVALID, "er_set_prefix_pass: a queue is open on this context (er_queue_end first)");
+    if (pass == ER_PREFIX_PASS_MFMA && (c->kv_type != 1 || c->D != 96))
+        return fail(ER_ERR_UNSUPPORTED, "er_set_prefix_pass: the matrix-core prefix pass reads fp16 caches at head_dim 96 only; this context keeps %s at head_dim %d",
+                    c->kv_type == 0 ? "an fp32 cache" : c->kv_type == 1 ? "an fp16 cache" : "an e4m3 cache (kv8)", c->D);
+    c->knobs.prefix_pass = pass;
     return ER_OK;
 }
 
@@ -1891,15 +1909,29 @@ extern "C" int er_k_attn_stream_xt(const float* q, const void* k, const void* v,
     return ER_OK;
 }
 
+static int k_attn_shared_run(const char* who, bool mfma, const float* q, const void* k, const void* v, const int32_t* len_host, const int32_t* leader,
+                             int prefix_len, float* out, void* out_xt, int B, int heads, int l_cap, int kv_half, void* stream);
+
 extern "C" int er_k_attn_shared(const float* q, const void* k, const void* v, const int32_t* len_host, const int32_t* leader, int prefix_len,
                                 float* out, void* out_xt, int B, int heads, int l_cap, int kv_half, void* stream) {
+    return k_attn_shared_run("er_k_attn_shared", false, q, k, v, len_host, leader, prefix_len, out, out_xt, B, heads, l_cap, kv_half, stream);
+}
+
+extern "C" int er_k_attn_shared_mfma(const float* q, const void* k, const void* v, const int32_t* len_host, const int32_t* leader, int prefix_len,
+                                     float* out, void* out_xt, int B, int heads, int l_cap, int kv_half, void* stream) {
+    if (kv_half != 1) return fail(ER_ERR_UNSUPPORTED, "er_k_attn_shared_mfma: the matrix-core prefix pass reads fp16 caches only (kv_half = 1; got %d)", kv_half);
+    return k_attn_shared_run("er_k_attn_shared_mfma", true, q, k, v, len_host, leader, prefix_len, out, out_xt, B, heads, l_cap, kv_half, stream);
+}
+
+static int k_attn_shared_run(const char* who, bool mfma, const float* q, const void* k, const void* v, const int32_t* len_host, const int32_t* leader,
+                             int prefix_len, float* out, void* out_xt, int B, int heads, int l_cap, int kv_half, void* stream) {
     constexpr int D = 96;
-    if (!q || !k || !v || !len_host || !leader || !out || B < 1 || heads < 1 || l_cap < 1) return fail(ER_ERR_INVALID, "er_k_attn_shared: bad argument");
-    if (prefix_len < 1 || prefix_len > l_cap) return fail(ER_ERR_INVALID, "er_k_attn_shared: prefix_len %d outside [1, %d]", prefix_len, l_cap);
+    if (!q || !k || !v || !len_host || !leader || !out || B < 1 || heads < 1 || l_cap < 1) return fail(ER_ERR_INVALID, "%s: bad argument", who);
+    if (prefix_len < 1 || prefix_len > l_cap) return fail(ER_ERR_INVALID, "%s: prefix_len %d outside [1, %d]", who, prefix_len, l_cap);
     std::vector<int> rows, off;
     for (int b = 0; b < B; ++b) {
-        if (leader[b] < 0 || leader[b] > b || leader[leader[b]] != leader[b]) return fail(ER_ERR_INVALID, "er_k_attn_shared: leader[%d] = %d", b, leader[b]);
-        if (len_host[b] < prefix_len || len_host[b] > l_cap) return fail(ER_ERR_CAPACITY, "er_k_attn_shared: len[%d] = %d outside [%d, %d]", b, len_host[b], prefix_len, l_cap);
+        if (leader[b] < 0 || leader[b] > b || leader[leader[b]] != leader[b]) return fail(ER_ERR_INVALID, "%s: leader[%d] = %d", who, b, leader[b]);
+        if (len_host[b] < prefix_len || len_host[b] > l_cap) return fail(ER_ERR_CAPACITY, "%s: len[%d] = %d outside [%d, %d]", who, b, len_host[b], prefix_len, l_cap);
     }
     for (int b = 0; b < B; ++b) {
         if (leader[b] != b) continue;
@@ -1923,7 +1955,9 @@ extern "C" int er_k_attn_shared(const float* q, const void* k, const void* v, co
     HIPCHK(hipMemcpy(off_dev.p, off.data(), off.size() * sizeof(int), hipMemcpyHostToDevice));
     s.a.q = q; s.a.kcache = k; s.a.vcache = v; s.a.len_dev = len_dev.p; s.a.part = part.p; s.a.out = out; s.a.out_xt = out_xt;
     s.grp_rows = rows_dev.p; s.grp_off = off_dev.p;
-    hipError_t e = launch_attn_prefix_d<D>(s, kv_half != 0, (int)off.size() - 1, st);      // launch_kind_t kinds 1 and 2, shared_attn
+    const int groups = (int)off.size() - 1;
+    hipError_t e = mfma ? launch_attn_prefix_mfma_d<D>(s, groups, st)                      // launch_kind_t kinds 1 and 2, shared_mfma / shared_attn
+                        : launch_attn_prefix_d<D>(s, kv_half != 0, groups, st);
     if (e == hipSuccess) e = launch_attn_suffix_merge_d<D>(s, kv_half != 0, B, st);
     hipError_t e2 = hipStreamSynchronize(st);
     HIPRET(e);

@@ -22,6 +22,9 @@ struct DecodeKnobs {          // the environment knobs of the decode step, read 
     // single-row MLP (env ER_MLP_V): 0 = fc1 and fc2 as two row GEMVs, 1 = fused launch that skips the fc2 weights behind zero ReLU outputs
     // + finish launch (k_mlp_sparse.h)
     int mlp_v = 0;
+    // the prefix pass under prefix groups (env ER_PREFIX_PASS=valu|mfma at er_create, er_set_prefix_pass later): ER_PREFIX_PASS_VALU =
+    // attn_prefix_kernel, ER_PREFIX_PASS_MFMA = attn_prefix_mfma_kernel where the plan qualifies (make_decode_plan: shared_mfma)
+    int prefix_pass = ER_PREFIX_PASS_VALU;
 };
 
 // the three switches er_kv_reserve reads for the shape it reserves (tests flip them between two reserves of one context)
@@ -49,6 +52,7 @@ struct DecodePlan {
     bool xt = false;            // fast-mode batches read the tiled activation images (KvMem::xt_*); ER_XT=0 keeps the row-major fp32 inputs (A/B + parity matrix)
     bool stream_attn = false;   // batched, D == 96 and (forced or B*H >= 256: at least one streaming workgroup per CU)
     bool shared_attn = false;   // prefix groups are set (er_set_prefix_groups; batched, D == 96): prefix pass + suffix / merge launch (k_attn_shared.h) in place of either batched kernel
+    bool shared_mfma = false;   // shared_attn, knobs.prefix_pass == ER_PREFIX_PASS_MFMA, fp16 cache (fast, not kv8) and D == 96: kind 1 is the matrix-core prefix pass (k_attn_shared_mfma.h)
     ReserveKnobs rk{};          // the switches of the reserve, kept so that setting or clearing groups can derive the plan again
     bool kv8 = false;           // the cache holds e4m3 bytes (kv8 mode): version 2 at B <= 4, the streaming kernel at every batched shape, no prefix groups
     bool v3 = false;            // decode_v == 3 and the reserved cache qualifies
@@ -86,7 +90,8 @@ inline bool shared_attn_supported(const er_decode_plan& sel, int D) { return sel
 
 // the plan of one (batch, Lcap) of a model with `layers` layers of H heads of D (hid = hidden width), `fast` = fp16 weights and cache;
 // kv8: the cache holds e4m3 bytes (with fast's fp16 weights or fp8 mode's bytes); shared: prefix groups are set on the reserved batch (the caller has asked shared_attn_supported), which replaces the attention kernel
-// of plan_decode's shape-only rule by ER_ATTN_SHARED with its own merge launch
+// of plan_decode's shape-only rule by ER_ATTN_SHARED with its own merge launch - ER_ATTN_SHARED_MFMA when the knobs ask for the matrix-core
+// prefix pass and the cache is fp16 (the kernel reads fp16 K/V at head_dim 96 only; anything else keeps the VALU pass)
 inline DecodePlan make_decode_plan(const DecodeKnobs& k, const ReserveKnobs& rk, bool fast, int batch, int Lcap, int layers, int H, int D,
                                    int hid, const AttnChunking& ch, bool shared = false, bool kv8 = false) {
     DecodePlan p;
@@ -99,7 +104,8 @@ inline DecodePlan make_decode_plan(const DecodeKnobs& k, const ReserveKnobs& rk,
     plan_decode(k.decode_v, k.attn_v_batched, p.force_batched, batch, H, D, hid, Lcap, ch, &p.sel, kv8);
     p.kv8 = kv8;
     p.shared_attn = shared && !kv8 && shared_attn_supported(p.sel, D);      // the shared-prefix kernels have no byte form
-    if (p.shared_attn) { p.sel.attn_kernel = ER_ATTN_SHARED; p.sel.merge_launch = 1; }
+    p.shared_mfma = p.shared_attn && k.prefix_pass == ER_PREFIX_PASS_MFMA && fast && D == 96;
+    if (p.shared_attn) { p.sel.attn_kernel = p.shared_mfma ? ER_ATTN_SHARED_MFMA : ER_ATTN_SHARED; p.sel.merge_launch = 1; }
     p.batched = p.sel.batched != 0; p.mfma = p.batched && !p.valu; p.xt = fast && p.mfma && rk.xt;
     p.stream_attn = p.sel.attn_kernel == ER_ATTN_STREAM; p.v3 = p.sel.decode_version == 3;
     p.mlp_fused = k.mlp_v != 0 && batch == 1 && !p.batched && hid == 1536;      // the kernel's fixed widths (intermediate = 4 * hidden)

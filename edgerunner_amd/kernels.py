@@ -244,18 +244,22 @@ def attn_stream_xt(q, k_cache, v_cache, lens, out_xt):
     return out
 
 
-def attn_shared(q, k_cache, v_cache, lens, leaders, prefix_len, out_xt=None):
+def attn_shared(q, k_cache, v_cache, lens, leaders, prefix_len, out_xt=None, prefix_pass="valu"):
     """The decode attention under prefix groups (head_dim 96; er_set_prefix_groups): row b attends keys [0, prefix_len) of row
-    leaders[b]'s cache slice and keys [prefix_len, lens[b]) of its own -> out [B, heads * 96].  out_xt (optional) as for attn_stream_xt."""
+    leaders[b]'s cache slice and keys [prefix_len, lens[b]) of its own -> out [B, heads * 96].  out_xt (optional) as for attn_stream_xt.
+    prefix_pass: "valu" (er_k_attn_shared) or "mfma" (er_k_attn_shared_mfma: the matrix-core prefix pass, fp16 caches only)."""
+    if prefix_pass not in native.PREFIX_PASSES:
+        raise ValueError(f"prefix_pass must be 'valu' or 'mfma', got {prefix_pass!r}")
     lib = native.load_library()
     B, H, Lcap, D = k_cache.shape
     assert D == 96 and len(lens) == B and len(leaders) == B
     if out_xt is not None:
         assert out_xt.dtype == torch.float16 and out_xt.numel() == (B + 31) // 32 * H * D * 64
     out = torch.empty((B, H * D), dtype=torch.float32, device=q.device)
-    native.check(lib.er_k_attn_shared(native.ptr(q), native.ptr(k_cache), native.ptr(v_cache), native.i32_array(lens),
-                                      native.i32_array(leaders), int(prefix_len), native.ptr(out), native.ptr(out_xt), B, H, Lcap,
-                                      int(k_cache.dtype == torch.float16), _st()), "er_k_attn_shared")
+    name = "er_k_attn_shared_mfma" if prefix_pass == "mfma" else "er_k_attn_shared"
+    native.check(getattr(lib, name)(native.ptr(q), native.ptr(k_cache), native.ptr(v_cache), native.i32_array(lens),
+                                    native.i32_array(leaders), int(prefix_len), native.ptr(out), native.ptr(out_xt), B, H, Lcap,
+                                    int(k_cache.dtype == torch.float16), _st()), name)
     return out
 
 

@@ -372,7 +372,7 @@ class LMM:
     # -- generation ---------------------------------------------------------------------------
     @torch.no_grad()
     def generate_ids(self, conds, num_faces=1000, resume_ids=None, tokenizer=None, max_new_tokens=None,
-                     min_new_tokens: int = 0, seed: Optional[int] = None, row_streams=None, share_prefix: bool = False, *,
+                     min_new_tokens: int = 0, seed: Optional[int] = None, row_streams=None, share_prefix=False, *,
                      temperature: Optional[float] = None, top_p: Optional[float] = None, top_k: Optional[int] = None,
                      output_logprobs: bool = False) -> torch.Tensor:
         """Everything of LMM.generate up to the HF call's return value (core/models.py:215-303).
@@ -387,7 +387,11 @@ class LMM:
         the group's cond + BOS prefix (num_cond_tokens + 1 cache positions; one ``num_faces`` per call, so ``resume_ids`` may differ
         behind it) once from the first such row's cache instead of once per row (``er_set_prefix_groups``).  The tokens are those
         of ``share_prefix=False`` up to the rounding of a different summation order.  It acts on the batched decode path only: with
-        B <= 4 and no ``ER_FORCE_BATCHED=1`` it has no effect."""
+        B <= 4 and no ``ER_FORCE_BATCHED=1`` it has no effect.  ``share_prefix="mfma"`` is ``True`` with the prefix pass of this call on the
+        matrix cores (``er_set_prefix_pass``; fast mode's fp16 cache only, ``NativeError`` otherwise) and is ignored where ``True`` is;
+        ``True`` runs the pass the context is set to (``NativeShapeOPT.set_prefix_pass``, env ``ER_PREFIX_PASS``; the VALU pass by default)."""
+        if share_prefix not in (False, True, None, "mfma", "valu"):
+            raise ValueError(f"share_prefix must be a bool, 'valu' or 'mfma', got {share_prefix!r}")
         opt = self.opt
         B = conds.shape[0]
         cond_embeds = self.encode_cond(conds, [num_faces] * B)["cond_embeds"]
@@ -410,6 +414,8 @@ class LMM:
                       prefix_allowed_tokens_fn=fn, min_new_tokens=min_new_tokens, seed=seed, row_streams=row_streams)
         if share_prefix and (B > 4 or os.environ.get("ER_FORCE_BATCHED", "")[:1] == "1"):
             kwargs["prefix_groups"] = (prefix_leaders(conds), opt.num_cond_tokens + 1)
+            if isinstance(share_prefix, str):
+                kwargs["prefix_pass"] = share_prefix
         if opt.generate_mode == "greedy":
             kwargs["num_beams"] = 1
         elif opt.generate_mode == "sample":
@@ -487,7 +493,7 @@ class LMM:
 
     @torch.no_grad()
     def generate(self, conds, num_faces=1000, resume_ids=None, tokenizer=None, max_new_tokens=None, clean=True,
-                 min_new_tokens: int = 0, seed: Optional[int] = None, row_streams=None, share_prefix: bool = False, *,
+                 min_new_tokens: int = 0, seed: Optional[int] = None, row_streams=None, share_prefix=False, *,
                  temperature: Optional[float] = None, top_p: Optional[float] = None, top_k: Optional[int] = None,
                  output_logprobs: bool = False):
         """-> (meshes, all_tokens) like core/models.py:204-319.  ``share_prefix``, the sampling controls and ``output_logprobs``

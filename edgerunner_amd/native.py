@@ -38,10 +38,13 @@ EXPORTS = [
     "er_queue_begin", "er_queue_admit", "er_queue_run", "er_queue_take", "er_queue_stats", "er_queue_end",
     "er_set_sampling", "er_get_logprobs", "er_queue_row_logprobs", "er_k_sample_head_ctl",
     "er_k_w8_quantize", "er_k_gemv_form_w8", "er_k_attn_outproj3_w8", "er_k_kv8_encode",
+    "er_set_prefix_pass", "er_k_attn_shared_mfma",
 ]
 
 
-ER_ATTN_SPLIT1, ER_ATTN_SPLIT2, ER_ATTN_BALANCED, ER_ATTN_STREAM, ER_ATTN_SHARED = 1, 2, 3, 4, 5
+ER_ATTN_SPLIT1, ER_ATTN_SPLIT2, ER_ATTN_BALANCED, ER_ATTN_STREAM, ER_ATTN_SHARED, ER_ATTN_SHARED_MFMA = 1, 2, 3, 4, 5, 6
+ER_PREFIX_PASS_VALU, ER_PREFIX_PASS_MFMA = 0, 1
+PREFIX_PASSES = {"valu": ER_PREFIX_PASS_VALU, "mfma": ER_PREFIX_PASS_MFMA}
 
 
 class ErDecodePlan(C.Structure):
@@ -173,6 +176,7 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.er_ctx_plan.argtypes = [vp, C.POINTER(ErDecodePlan)]
     lib.er_set_row_streams.argtypes = [vp, C.POINTER(C.c_uint32), ci]
     lib.er_set_prefix_groups.argtypes = [vp, C.POINTER(C.c_int32), ci, ci]
+    lib.er_set_prefix_pass.argtypes = [vp, ci]
     lib.er_plan_gemm_tile.argtypes = [ci, ci, ci]
     lib.er_queue_begin.argtypes = [vp, C.POINTER(ErDecodeParams), ci, vp]
     lib.er_queue_admit.argtypes = [vp, ci, ci, vp, ci, C.POINTER(C.c_uint32), C.POINTER(C.c_int32), vp]
@@ -187,6 +191,7 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.er_mlp_nnz.argtypes = [vp, C.POINTER(C.c_int32), ci]
     lib.er_k_attn_stream_xt.argtypes = [vp, vp, vp, C.POINTER(C.c_int32), vp, vp, ci, ci, ci, ci, vp]
     lib.er_k_attn_shared.argtypes = [vp, vp, vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), ci, vp, vp, ci, ci, ci, ci, vp]
+    lib.er_k_attn_shared_mfma.argtypes = lib.er_k_attn_shared.argtypes
     lib.er_k_attn_decode.argtypes = [vp, vp, vp, C.POINTER(C.c_int32), vp, ci, ci, ci, ci, ci, ci, ci, vp]
     lib.er_k_attn_outproj3.argtypes = [vp, vp, vp, ci, vp, vp, vp, vp, ci, ci, ci, vp]
     lib.er_k_w8_quantize.argtypes = [vp, ci, ci, ci, ci, vp, vp, vp, vp, vp]

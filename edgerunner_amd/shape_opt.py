@@ -12,6 +12,7 @@ ids.  All arithmetic runs in the HIP library behind the C ABI
 from __future__ import annotations
 
 import ctypes as C
+import os
 from typing import Callable, Dict, Optional
 
 import torch
@@ -105,6 +106,8 @@ class NativeShapeOPT:
         self._reserved = (0, 0)
         self.last_decode_ms = 0.0
         self.last_logprobs = None     # {"model", "policy"}: float32 [B, n] on the device after a generate(output_logprobs=True)
+        # the prefix pass of the next grouping, as er_create read it (env ER_PREFIX_PASS; "mfma" holds on an fp16 cache only)
+        self.prefix_pass = "mfma" if os.environ.get("ER_PREFIX_PASS") == "mfma" and kv_dtype == torch.float16 else "valu"
         self.direct_loads = False     # weights loaded on this object directly (LMM.half()/float() cannot replay them)
 
     # -- lifetime ---------------------------------------------------------------------------
@@ -211,15 +214,32 @@ class NativeShapeOPT:
         native.check(self.lib.er_set_prefix_groups(self._ctx, native.i32_array(leaders), len(leaders), int(prefix_len)),
                      "er_set_prefix_groups")
 
-    def prefill(self, inputs_embeds: torch.Tensor, max_new_tokens: int, prefix_groups=None):
+    def set_prefix_pass(self, prefix_pass: str):
+        """``er_set_prefix_pass``: the kernel of the prefix pass under prefix groups, "valu" (the default) or "mfma" (the matrix-core
+        pass: fp16 caches at head_dim 96, ER_ERR_UNSUPPORTED on any other context).  It takes effect at the next ``set_prefix_groups``."""
+        if prefix_pass not in native.PREFIX_PASSES:
+            raise ValueError(f"prefix_pass must be 'valu' or 'mfma', got {prefix_pass!r}")
+        native.check(self.lib.er_set_prefix_pass(self._ctx, native.PREFIX_PASSES[prefix_pass]), "er_set_prefix_pass")
+        self.prefix_pass = prefix_pass
+
+    def prefill(self, inputs_embeds: torch.Tensor, max_new_tokens: int, prefix_groups=None, prefix_pass=None):
         """``prefix_groups``: None, or ``(leaders, prefix_len)`` as for set_prefix_groups - set (or cleared) after the lazy reserve and
-        before the forward pass, which then checks on the device that the rows of a group hold the same prefix."""
+        before the forward pass, which then checks on the device that the rows of a group hold the same prefix.  ``prefix_pass``
+        ("valu" | "mfma"): the prefix pass of THIS grouping; the context's own setting (``set_prefix_pass``) is put back behind it."""
         x = inputs_embeds.to(self.device, torch.float32).contiguous()
         B, S, _ = x.shape
         need = S + max_new_tokens + 1
         if self._reserved[0] != B or self._reserved[1] < need:
             self.reserve(B, need)
-        self.set_prefix_groups(prefix_groups)
+        if prefix_pass is None or prefix_groups is None:
+            self.set_prefix_groups(prefix_groups)
+        else:
+            mine = self.prefix_pass
+            self.set_prefix_pass(prefix_pass)
+            try:
+                self.set_prefix_groups(prefix_groups)
+            finally:
+                self.set_prefix_pass(mine)
         with self._enter():
             native.check(self.lib.er_prefill(self._ctx, native.ptr(x), B, S, self._sp()), "er_prefill")
         self._exit()
@@ -285,10 +305,10 @@ class NativeShapeOPT:
                  prefix_allowed_tokens_fn: Optional[Callable] = None, num_beams: int = 1, do_sample: bool = False,
                  top_k: int = 50, min_new_tokens: int = 0, seed: Optional[int] = None, row_streams=None,
                  prefix_groups=None, temperature: float = 1.0, top_p: float = 1.0, output_logprobs: bool = False,
-                 **unused) -> torch.Tensor:
+                 prefix_pass=None, **unused) -> torch.Tensor:
         """Drop-in for ``ShapeOPT.generate`` as called at core/models.py:303.
         ``num_tokens`` is accepted and ignored exactly like the reference decoder
-        ignores it (modeling_opt.py:324,467,546).  ``prefix_groups`` goes to ``prefill``.
+        ignores it (modeling_opt.py:324,467,546).  ``prefix_groups`` and ``prefix_pass`` go to ``prefill``.
 
         ``temperature``, ``top_k`` (0: no top-k filter) and ``top_p`` act in sample mode, in the order of HF's warpers; greedy mode
         accepts them and picks the same ids.  ``output_logprobs=True`` leaves ``last_logprobs = {"model", "policy"}`` (float32
@@ -305,7 +325,7 @@ class NativeShapeOPT:
         if max_new_tokens is None:
             max_new_tokens = self.opt.max_seq_length
         B = inputs_embeds.shape[0]
-        self.prefill(inputs_embeds, max_new_tokens, prefix_groups=prefix_groups)
+        self.prefill(inputs_embeds, max_new_tokens, prefix_groups=prefix_groups, prefix_pass=prefix_pass)
         # sample mode: the Philox stream of row b (default b; a sharding / batching caller passes global job indices)
         if row_streams is not None and len(row_streams) != B:
             raise ValueError(f"row_streams has {len(row_streams)} entries for a batch of {B}")

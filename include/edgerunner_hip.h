@@ -266,6 +266,14 @@ int er_queue_end(er_ctx* ctx);
  * and, after its forward pass, compares every follower's K/V [0, prefix_len) of all layers with its leader's on the device: a mismatch
  * fails with ER_ERR_INVALID naming row and layer, and the context needs a new er_prefill; er_score and er_queue_begin refuse. */
 int er_set_prefix_groups(er_ctx* ctx, const int32_t* leader_host, int n, int prefix_len);
+/* Which kernel runs the prefix pass of a step under prefix groups.  ER_PREFIX_PASS_VALU (the default): attn_prefix_kernel, fp32 and
+ * fp16 caches.  ER_PREFIX_PASS_MFMA: attn_prefix_mfma_kernel (csrc/k_attn_shared_mfma.h) - the rows of a group as columns of the fp16
+ * matrix cores, fp16 caches (fast mode) at head_dim 96 only; er_ctx_plan then reports ER_ATTN_SHARED_MFMA.  The initial value comes
+ * from env ER_PREFIX_PASS (valu | mfma) at er_create; an fp32- or byte-cache context ignores "mfma" there.  The setting takes effect at
+ * the next er_set_prefix_groups, which derives the plan again and drops the captured step.  ER_ERR_UNSUPPORTED: ER_PREFIX_PASS_MFMA on
+ * a context whose cache is not fp16 (nothing changes).  ER_ERR_INVALID: another value, or a queue is open. */
+enum er_prefix_pass { ER_PREFIX_PASS_VALU = 0, ER_PREFIX_PASS_MFMA = 1 };
+int er_set_prefix_pass(er_ctx* ctx, int pass);
 
 /* ---- mesh tokenizer (host code, no device work): the reference's pybind11 module meto (meto/src/bindings.cpp,
  * meto.Engine(discrete_bins, verbose, backend), meto/meto/__init__.py:21-54) for the backends Options.meto_backend
@@ -358,7 +366,8 @@ int er_dit_loss(er_dit_ctx* ctx, const float* latents_dev, const float* noise_de
  * the step derives from it, beside that shape's memory; er_plan_decode evaluates it for a hypothetical shape under the environment
  * of the call (ER_DECODE_V, ER_ATTN_V_BATCHED, ER_FORCE_BATCHED are honoured, l_cap is rounded up to 32 like er_kv_reserve). */
 typedef enum { ER_ATTN_SPLIT1 = 1, ER_ATTN_SPLIT2 = 2, ER_ATTN_BALANCED = 3, ER_ATTN_STREAM = 4,
-               ER_ATTN_SHARED = 5    /* prefix groups are set (er_set_prefix_groups): er_ctx_plan only, never er_plan_decode's shape-only rule */
+               ER_ATTN_SHARED = 5,   /* prefix groups are set (er_set_prefix_groups): er_ctx_plan only, never er_plan_decode's shape-only rule */
+               ER_ATTN_SHARED_MFMA = 6   /* ER_ATTN_SHARED with the matrix-core prefix pass (er_set_prefix_pass): er_ctx_plan only */
 } er_attn_kernel;
 typedef struct {
     int32_t batched;            /* 1: B > 4 path (matrix-core projections, weights once per 32 rows) */
@@ -493,6 +502,10 @@ int er_k_attn_stream_xt(const float* q_dev, const void* k_dev, const void* v_dev
  * er_k_attn_stream_xt.  Blocks until the work is complete. */
 int er_k_attn_shared(const float* q_dev, const void* k_dev, const void* v_dev, const int32_t* len_host, const int32_t* leader_host,
                      int prefix_len, float* out_dev, void* out_xt_dev, int batch, int heads, int l_cap, int kv_half, void* stream);
+/* er_k_attn_shared with the matrix-core prefix pass (csrc/k_attn_shared_mfma.h) in front of the same suffix / merge launch: fp16
+ * caches only (kv_half = 1; anything else is ER_ERR_UNSUPPORTED). */
+int er_k_attn_shared_mfma(const float* q_dev, const void* k_dev, const void* v_dev, const int32_t* len_host, const int32_t* leader_host,
+                          int prefix_len, float* out_dev, void* out_xt_dev, int batch, int heads, int l_cap, int kv_half, void* stream);
 /* Version 3 of the single-row decode attention (env ER_DECODE_V=3), one row, 16 heads of 96:
  * y[1536] = Wo . softmax(q K^T / sqrt(D)) V + bo + resid over a [16,Lcap,96] cache holding len keys (Lcap <= 8192):
  * balanced chunks (16 per head) + the partial merge fused into the out_proj GEMV; w_half: Wo is fp16 */

@@ -33,6 +33,8 @@ ER_INFER_SHARE_PREFIX=1 passes ``share_prefix=True`` to the batched path's ``LMM
 the same cloud (--test_repeat samples of one input) read their common cond + BOS prefix once per decode step instead of once per job
 (calls of more than 4 jobs; see ``LMM.generate_ids``).  Same output files.  It cannot be combined with ER_INFER_QUEUE=1 (the queue's
 rows change owners; groups in queue mode are not built): both together are refused at start.  Without the variable nothing changes.
+ER_INFER_PREFIX_PASS=mfma beside it passes ``share_prefix="mfma"``: the shared prefix is read by the matrix-core prefix pass (fast mode's
+fp16 cache only; ``LMM.generate_ids``).  Alone, or with any other value than ``mfma``, it does nothing.
 
 ER_INFER_TEMPERATURE, ER_INFER_TOP_P and ER_INFER_TOP_K (0: no top-k filter) shape the draws of ``--generate_mode sample`` as HF's
 warpers do, in that order; unset, the reference's TopK(10) at temperature 1 stays.  ER_INFER_LOGPROBS=1 writes
@@ -140,6 +142,8 @@ def main(argv=None):
     opt = parse_cli(argv)
     sampling = sampling_from_env()
     share_prefix = os.environ.get("ER_INFER_SHARE_PREFIX") == "1"
+    if share_prefix and os.environ.get("ER_INFER_PREFIX_PASS") == "mfma":
+        share_prefix = "mfma"
     if share_prefix and os.environ.get("ER_INFER_QUEUE") == "1":
         raise SystemExit("[ERROR] ER_INFER_SHARE_PREFIX=1 and ER_INFER_QUEUE=1 cannot be combined: prefix groups are not built for queue mode")
     if share_prefix and os.environ.get("EDGERUNNER_KV_PRECISION") == "fp8":
@@ -244,7 +248,7 @@ def main(argv=None):
         # sample mode: job j draws from the Philox stream (opt.seed, step, j) whatever rows share its call
         meshes, tokens = model.generate(cond, num_faces=num_faces, max_new_tokens=opt.test_max_seq_length,
                                         tokenizer=tokenizer, clean=True, seed=opt.seed, row_streams=list(chunk),
-                                        **({"share_prefix": True} if share_prefix else {}), **sampling)
+                                        **({"share_prefix": share_prefix} if share_prefix else {}), **sampling)
         torch.cuda.synchronize()
         dt = time.time() - t0
         blp = model.last_logprobs

@@ -7,7 +7,12 @@ shared.  Per batch and mode it records the decode tok/s (``er_last_decode_ms``) 
 kinds 1 and 2 (``er_profile_decode_kernels_at`` at the run's mean context, replayed from a graph); per batch the byte ratio
 (sum over groups of P + rows * (L - P)) / (B * L) that the attention time is to be compared with.  Prints one JSON object.
 
-    python scripts/bench_shared_prefix.py [--precision fp16 fp32] [--tokens 1000] [--rows 32] [--layers 24] [--rounds 2] [--out FILE]
+``--prefix-pass valu mfma`` gives every named prefix pass (``er_set_prefix_pass``) a shared run of its own, each alternated with the
+unshared run in the same process; the object then holds ``shared_valu`` / ``shared_mfma`` per batch beside ``shared`` (the first pass
+named).  The matrix-core pass reads fp16 caches only: name it with ``--precision fp16``.
+
+    python scripts/bench_shared_prefix.py [--precision fp16 fp32] [--prefix-pass valu mfma] [--tokens 1000] [--rows 32] [--layers 24]
+                                          [--rounds 2] [--out FILE]
 """
 import argparse
 import dataclasses
@@ -39,8 +44,11 @@ def main():
     ap.add_argument("--layers", type=int, default=24)
     ap.add_argument("--rounds", type=int, default=2)
     ap.add_argument("--points", type=int, default=4096)
+    ap.add_argument("--prefix-pass", nargs="+", default=["valu"], choices=["valu", "mfma"])
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if "mfma" in a.prefix_pass and "fp32" in a.precision:
+        ap.error("--prefix-pass mfma reads fp16 caches only: run it with --precision fp16")
     B, T = a.rows, a.tokens
     opt = dataclasses.replace(config_defaults["ArAE"], num_layers=a.layers, generate_mode="greedy")
     P = opt.num_cond_tokens + 1
@@ -51,6 +59,7 @@ def main():
         "singletons": list(range(B)),
     }
     res = {"rows": B, "layers": a.layers, "tokens": T, "prefix_len": P, "mean_context": L, "device": torch.cuda.get_device_name(0),
+           "prefix_passes": list(a.prefix_pass),
            "precisions": {}}
     for precision in a.precision:
         lmm = LMM(opt, "cuda:0", precision=precision)
@@ -64,12 +73,13 @@ def main():
             for l in leaders:
                 groups[l] = groups.get(l, 0) + 1
             byte_ratio = sum(P + n * (L - P) for n in groups.values()) / (B * L)
-            modes = {False: {"decode_ms": [], "tok_s": []}, True: {"decode_ms": [], "tok_s": []}}
+            shares = [False] + list(a.prefix_pass)            # False = unshared, then one shared run per prefix pass
+            modes = {sh: {"decode_ms": [], "tok_s": []} for sh in shares}
             ids = {}
-            for share in (False, True):                      # warm-up of each
+            for share in shares:                             # warm-up of each
                 run(lmm, batch, T, share)
             for _ in range(a.rounds):                        # alternated
-                for share in (False, True):
+                for share in shares:
                     toks, ms = run(lmm, batch, T, share)
                     ids[share] = toks
                     modes[share]["decode_ms"].append(round(ms, 2))
@@ -78,17 +88,25 @@ def main():
                     modes[share]["attn_kernel"] = dec.plan()["attn_kernel"]
                     modes[share].setdefault("kind1_us", []).append(round(prof["attn_decode"]["avg_us"], 2))
                     modes[share].setdefault("kind2_us", []).append(round(prof["attn_combine"]["avg_us"], 2))
-            assert modes[True]["attn_kernel"] == native.ER_ATTN_SHARED and modes[False]["attn_kernel"] != native.ER_ATTN_SHARED
+            want = {"valu": native.ER_ATTN_SHARED, "mfma": native.ER_ATTN_SHARED_MFMA}
+            assert modes[False]["attn_kernel"] not in want.values() and all(modes[sh]["attn_kernel"] == want[sh] for sh in a.prefix_pass)
             mean = lambda v: sum(v) / len(v)
-            attn = {s: mean(modes[s]["kind1_us"]) + mean(modes[s]["kind2_us"]) for s in (False, True)}
+            attn = {s: mean(modes[s]["kind1_us"]) + mean(modes[s]["kind2_us"]) for s in shares}
+            first = a.prefix_pass[0]
             out[name] = {
                 "groups": len(groups), "byte_ratio": round(byte_ratio, 4),
-                "unshared": modes[False], "shared": modes[True],
-                "tok_s_ratio": round(mean(modes[True]["tok_s"]) / mean(modes[False]["tok_s"]), 4),
-                "attn_us_per_layer": {"unshared": round(attn[False], 2), "shared": round(attn[True], 2)},
-                "attn_time_ratio": round(attn[True] / attn[False], 4),
-                "rows_with_equal_ids": sum(int((x == y).all()) for x, y in zip(ids[False], ids[True])),
+                "unshared": modes[False], "shared": modes[first],
+                "tok_s_ratio": round(mean(modes[first]["tok_s"]) / mean(modes[False]["tok_s"]), 4),
+                "attn_us_per_layer": {"unshared": round(attn[False], 2), "shared": round(attn[first], 2)},
+                "attn_time_ratio": round(attn[first] / attn[False], 4),
+                "rows_with_equal_ids": sum(int((x == y).all()) for x, y in zip(ids[False], ids[first])),
             }
+            if len(a.prefix_pass) > 1 or first != "valu":
+                for sh in a.prefix_pass:
+                    out[name]["shared_" + sh] = dict(
+                        modes[sh], tok_s_ratio=round(mean(modes[sh]["tok_s"]) / mean(modes[False]["tok_s"]), 4),
+                        attn_us_per_layer=round(attn[sh], 2), attn_time_ratio=round(attn[sh] / attn[False], 4),
+                        rows_with_equal_ids=sum(int((x == y).all()) for x, y in zip(ids[False], ids[sh])))
             print(f"[{precision}] {name}: {json.dumps(out[name])}", file=sys.stderr, flush=True)
         res["precisions"][precision] = out
         dec.close()
