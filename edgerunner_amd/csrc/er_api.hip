@@ -75,6 +75,7 @@ struct LayerW {
     // the dequantised values
     unsigned char *wqkv_q = nullptr, *wo_q = nullptr, *w1_q = nullptr, *w2_q = nullptr;
     void *wqkv_t = nullptr, *wo_t = nullptr, *w1_t = nullptr, *w2_t = nullptr;   // tiled copies for the matrix-core batched kernels (k_gemv_mfma.h)
+    void *wqkv_t8 = nullptr, *wo_t8 = nullptr, *w1_t8 = nullptr, *w2_t8 = nullptr;   // fp8 mode: tiled BYTE copies (er_w8_tile_map.h) of the projections a plan streams as bytes
     void* w2_kt = nullptr;   // fc2.weight k-major, [intermediate][hidden] in the streamed weight type: the fused single-row MLP (k_mlp_sparse.h)
     float *wqkv = nullptr, *bqkv = nullptr;   // fused [3*hidden][hidden] in q,k,v order
     float *wo = nullptr, *bo = nullptr, *ln1w = nullptr, *ln1b = nullptr;
@@ -185,7 +186,7 @@ struct er_ctx {
     bool fast = false;       // fp16 weights + fp16 KV cache, fp32 accumulate
     bool kv8 = false;        // kv8 mode: fast (or fp8), with the KV cache stored as e4m3 bytes without a scale (er_w8.h kv8_encode)
     int kv_type = 0;         // the cache type as the kernels' kv_half argument takes it: 0 = fp32, 1 = fp16, 2 = e4m3 bytes
-    bool w8 = false;         // fp8 mode: fast, with the six decoder matrices per layer quantised by row; the row forms of the step stream the bytes
+    bool w8 = false;         // fp8 mode: fast, with the six decoder matrices per layer quantised by row; the row forms and (w8_streams_batched) the matrix-core forms of the step stream the bytes
     float *proj_w = nullptr, *proj_b = nullptr, *normc_w = nullptr, *normc_b = nullptr;
     PointEnc pe;             // point encoder (cond_mode POINT)
     WeightTable w;           // every checkpoint key (register_weights)
@@ -196,7 +197,8 @@ struct er_ctx {
     bool have_hidden = false;     // ypre holds a valid last-position state
     DecodeKnobs knobs;        // environment of er_create
     er_sampling samp{1.0f, 1.0f, 0, 0, 0};   // er_set_sampling: sticky, kept across er_kv_reserve
-    bool tiled_valid = false; // LayerW::*_t match the loaded weights
+    bool tiled_valid = false; // LayerW::*_t / *_t8 match the loaded weights, as far as tiled_have says they exist
+    bool tiled_have[2][4] = {};   // [0]: the fp16 / fp32 tiled copy, [1]: the tiled byte copy of qkv / out_proj / fc1 / fc2 has been made (every layer)
     bool kmajor_valid = false; // LayerW::w2_kt match the loaded weights
     void* zero_row = nullptr;  // hidden zeros (fp32 size): what the fused MLP reads in place of a dead neuron's row
     int prof_len = 0;         // > 0: attention kernels run at this fixed length (er_profile_decode_kernels_at)
@@ -244,6 +246,7 @@ static DecodeKnobs read_knobs(bool fast) {
     if (k.mlp_v != 1) k.mlp_v = 0;
     const char* pp = getenv("ER_PREFIX_PASS");      // valu | mfma; er_create keeps "mfma" for an fp16 cache only (er_set_prefix_pass)
     k.prefix_pass = (pp && !strcmp(pp, "mfma")) ? ER_PREFIX_PASS_MFMA : ER_PREFIX_PASS_VALU;
+    k.w8_batched = env_is("ER_W8_BATCHED", '0') ? 0 : env_is("ER_W8_BATCHED", '1') ? 1 : -1;
     return k;
 }
 
@@ -405,9 +408,33 @@ static int make_tiled(er_ctx* c, const void* src, void** dst, int N, int K) {
     HIPCHK(hipGetLastError());
     return 0;
 }
-static int make_tiled_weights(er_ctx* c) {
-    if (c->tiled_valid || weights_missing(c->w)) return 0;   // weights still loading: er_prefill comes back here
+// fp8 mode: a projection that `plan` streams as bytes in its matrix-core form (plan_w8_batched) gets the tiled byte copy and NO fp16
+// tiled copy (1.36 GB at 24 layers when all four stream bytes); a later reserve whose plan needs the other copy makes it then.
+static int make_tiled_weights(er_ctx* c, const DecodePlan& plan) {
+    if (weights_missing(c->w)) return 0;   // weights still loading: er_prefill comes back here
     const int H = c->cfg.hidden_dim, I = c->cfg.intermediate_dim;
+    if (!c->tiled_valid) memset(c->tiled_have, 0, sizeof(c->tiled_have));
+    if (c->w8) {
+        bool made = false;
+        for (int pj = 0; pj < 4; ++pj) {
+            const int bytes = plan_w8_batched(plan, c->knobs, (Proj)pj) ? 1 : 0;
+            if (c->tiled_have[bytes][pj]) continue;
+            const int N = pj == PROJ_QKV ? 3 * H : pj == PROJ_FC1 ? I : H, K = pj == PROJ_FC2 ? I : H;
+            for (LayerW& L : c->layers) {
+                const void* src16[4] = {L.wqkv_h, L.wo_h, L.w1_h, L.w2_h};
+                const void* src8[4] = {L.wqkv_q, L.wo_q, L.w1_q, L.w2_q};
+                void** dst16[4] = {&L.wqkv_t, &L.wo_t, &L.w1_t, &L.w2_t};
+                void** dst8[4] = {&L.wqkv_t8, &L.wo_t8, &L.w1_t8, &L.w2_t8};
+                if (bytes) ERCHK(make_tiled<w8_t>(c, src8[pj], dst8[pj], N, K));
+                else ERCHK(make_tiled<_Float16>(c, src16[pj], dst16[pj], N, K));
+            }
+            c->tiled_have[bytes][pj] = made = true;
+        }
+        if (made) HIPCHK(hipStreamSynchronize(c->own_stream));
+        c->tiled_valid = true;
+        return 0;
+    }
+    if (c->tiled_valid) return 0;
     for (LayerW& L : c->layers) {
         if (c->fast) {
             ERCHK(make_tiled<_Float16>(c, L.wqkv_h, &L.wqkv_t, 3 * H, H));
@@ -472,6 +499,26 @@ extern "C" int er_ctx_plan(er_ctx* c, er_decode_plan* out) {
     return ER_OK;
 }
 
+// which of qkv / out_proj / fc1 / fc2 the stored plan of a live context streams as e4m3 bytes (fp8 mode; all zero in every other mode)
+extern "C" int er_ctx_w8_streams(er_ctx* c, int32_t out[4]) {
+    if (!c || !out) return fail(ER_ERR_INVALID, "er_ctx_w8_streams: null argument");
+    const DecodePlan& p = c->kv->plan;
+    if (p.B <= 0) return fail(ER_ERR_INVALID, "er_ctx_w8_streams: no cache reserved (call er_kv_reserve)");
+    const bool v3 = p.v3 && !c->kv->row_class, fused = p.mlp_fused && !c->kv->row_class;
+    for (int pj = 0; pj < 4; ++pj) {
+        const Proj proj = (Proj)pj;
+        const ProjForm f = proj_form(p, c->knobs, true, proj, 0);
+        bool bytes = false;
+        if (!c->w8) bytes = false;
+        else if (proj == PROJ_OUT && v3) bytes = w8_streams(PROJ_OUT, 1);               // the fused merge + out_proj launch
+        else if ((proj == PROJ_FC1 || proj == PROJ_FC2) && fused) bytes = false;        // the fused single-row MLP reads fp16
+        else if (f.form == ER_FORM_ROW) bytes = w8_streams(proj, p.B);
+        else bytes = plan_w8_batched(p, c->knobs, proj);
+        out[pj] = bytes ? 1 : 0;
+    }
+    return ER_OK;
+}
+
 extern "C" int er_plan_gemm_tile(int m, int n, int batch) {
     if (m <= 0 || n <= 0 || batch <= 0) return fail(ER_ERR_INVALID, "er_plan_gemm_tile: bad argument");
     return gemm_pick_tile(m, n, batch);
@@ -533,7 +580,7 @@ static int kv_alloc(er_ctx* c, KvMem& m, int batch, int Lcap) {
     }
     m.st.row_budget = m.d_row_budget.p;
     ERCHK(m.d_out_ids.ensure(b * (size_t)Lcap));
-    if (p.mfma) ERCHK(make_tiled_weights(c));
+    if (p.mfma) ERCHK(make_tiled_weights(c, p));
     if (p.mlp_fused) {
         ERCHK(make_kmajor_weights(c));
         ERCHK(m.mlp_part.ensure((size_t)MLP_WGS * hid));
@@ -616,6 +663,7 @@ static hipError_t launch_kind_t(er_ctx* c, int kind, int layer, hipStream_t st, 
     const int H = g.hidden_dim, I = g.intermediate_dim, B = p.B;
     const SkPart sk{kv.skpart.p, kv.skpart.n};
     const auto form_of = [&](Proj proj, int l) { return proj_form(p, c->knobs, HALF, proj, l); };
+    const auto bytes_of = [&](Proj proj, const void* t8) { return c->w8 && plan_w8_batched(p, c->knobs, proj) ? t8 : nullptr; };      // null t8 (copy not made): the launch fails
     const bool v3 = p.v3 && !kv.row_class, fused = p.mlp_fused && !kv.row_class;
     GemvArgs a{};
     a.eps = g.ln_eps;
@@ -638,6 +686,7 @@ static hipError_t launch_kind_t(er_ctx* c, int kind, int layer, hipStream_t st, 
             }
             io.w_tiled = L.wqkv_t; io.x_image = kv.xt_h.p; io.pro_image = p.xt ? kv.xt_h.p : nullptr;
             if (c->w8) io.w8 = L.wqkv_q;
+            io.w8_tiled = bytes_of(PROJ_QKV, L.wqkv_t8);
             return run_proj<WT>(PROJ_QKV, form_of(PROJ_QKV, layer), io, a, B, H, sk, st);
         }
         // v2 holds a wave's whole K/V slice in flight (latency-bound single rows); with hundreds of workgroups per CU's
@@ -667,6 +716,7 @@ static hipError_t launch_kind_t(er_ctx* c, int kind, int layer, hipStream_t st, 
             a.W = HALF ? (const void*)L.wo_h : (const void*)L.wo; a.bias = L.bo; a.N = H; a.xin = kv.abuf.p; a.out = kv.ypre1.p; a.resid = kv.hbuf.p;
             io.w_tiled = L.wo_t; io.x_image = kv.xt_att.p;      // the streaming attention wrote the image (attn_args: out_xt)
             if (c->w8) io.w8 = L.wo_q;
+            io.w8_tiled = bytes_of(PROJ_OUT, L.wo_t8);
             return run_proj<WT>(PROJ_OUT, form_of(PROJ_OUT, layer), io, a, B, H, sk, st);
         }
         case 4: {   // h1 = LN1(ypre1); f = relu(fc1 h1 + b)
@@ -682,6 +732,7 @@ static hipError_t launch_kind_t(er_ctx* c, int kind, int layer, hipStream_t st, 
             if (form_of(PROJ_OUT, layer).defer) io.rd = {sk.p, L.bo, kv.hbuf.p, SK_SLICES_OUTPROJ};
             io.w_tiled = L.w1_t; io.x_image = kv.xt_h.p; io.pro_image = p.xt ? kv.xt_h.p : nullptr; io.out_image = kv.xt_f.p;
             if (c->w8) io.w8 = L.w1_q;
+            io.w8_tiled = bytes_of(PROJ_FC1, L.w1_t8);
             return run_proj<WT>(PROJ_FC1, form_of(PROJ_FC1, layer), io, a, B, H, sk, st);
         }
         case 5: {   // ypre = fc2 f + b + h1
@@ -690,6 +741,7 @@ static hipError_t launch_kind_t(er_ctx* c, int kind, int layer, hipStream_t st, 
             a.W = HALF ? (const void*)L.w2_h : (const void*)L.w2; a.bias = L.b2; a.N = H; a.xin = kv.fbuf.p; a.out = kv.ypre.p; a.resid = kv.h1buf.p;
             io.w_tiled = L.w2_t; io.x_image = kv.xt_f.p;
             if (c->w8) io.w8 = L.w2_q;
+            io.w8_tiled = bytes_of(PROJ_FC2, L.w2_t8);
             return run_proj<WT>(PROJ_FC2, form_of(PROJ_FC2, layer), io, a, B, I, sk, st);
         }
         case 6: {   // logits = lm_head LN2_last(ypre)
@@ -1011,7 +1063,7 @@ static int forward_check(er_ctx* c, const char* who, const float* embeds, int B,
 static int prefill_run(er_ctx* c, const float* embeds, int B, int S, hipStream_t st, int row0 = 0, bool in_queue = false) {
     HIPCHK(hipSetDevice(c->device));
     const DecodePlan& p = c->kv->plan;
-    if (p.mfma) ERCHK(make_tiled_weights(c));
+    if (p.mfma) ERCHK(make_tiled_weights(c, p));
     if (p.mlp_fused) ERCHK(make_kmajor_weights(c));
     const er_config& g = c->cfg;
     const int H = g.hidden_dim, I = g.intermediate_dim, NH = g.num_heads, D = c->D;
@@ -1514,7 +1566,7 @@ extern "C" int er_queue_begin(er_ctx* c, const er_decode_params* p, int check_ev
     ERCHK(er_finalize_weights(c));
     HIPCHK(hipSetDevice(c->device));
     hipStream_t st = pick(c, stream);
-    if (c->kv->plan.mfma) ERCHK(make_tiled_weights(c));
+    if (c->kv->plan.mfma) ERCHK(make_tiled_weights(c, c->kv->plan));
     if (c->kv->plan.mlp_fused) ERCHK(make_kmajor_weights(c));
     ERCHK(c->q_look.ensure((size_t)3 * B + 1));
     if (c->q_pinned) { hipHostFree(c->q_pinned); c->q_pinned = nullptr; }
@@ -1703,8 +1755,11 @@ static int profile_impl(er_ctx* c, int repeats, int use_graph, float* avg_us, do
     bytes[5] = ((double)I * H + H) * w + (double)B * (I + 2 * H) * w;
     bytes[6] = ((double)V * H) * w + (double)B * (H + V) * w;
     bytes[7] = (double)B * V * w;
-    if (c->w8 && !p.batched) {   // the row forms that stream bytes: 1 byte per weight + 4 per row scale in place of 2 per weight
-        const auto less = [&](Proj proj, double n, double k) { return w8_streams(proj, B) ? n * k * (w - 1.0) - n * 4.0 : 0.0; };
+    if (c->w8) {   // the row and matrix-core forms that stream bytes: 1 byte per weight + 4 per row scale in place of 2 per weight
+        const auto less = [&](Proj proj, double n, double k) {
+            const bool bytes = p.batched ? plan_w8_batched(p, c->knobs, proj) : w8_streams(proj, B);
+            return bytes ? n * k * (w - 1.0) - n * 4.0 : 0.0;
+        };
         bytes[0] -= less(PROJ_QKV, 3.0 * H, H);
         bytes[3] -= less(PROJ_OUT, H, H);
         bytes[4] -= less(PROJ_FC1, I, H);
@@ -2092,31 +2147,23 @@ static int w8_block_of(DevBuf<char>& blk, const void* q_dev, const float* wscale
     return 0;
 }
 
-// er_k_gemv_form's checks and launch table on (bytes, wscale): the fp16 row shapes of qkv, out_proj, fc1 and fc2.  args->w is not read.
+// er_k_gemv_form's checks and launch table on (bytes, wscale): the fp16 row shapes and the four matrix-core forms of qkv, out_proj, fc1
+// and fc2.  args->w is not read.
 extern "C" int er_k_gemv_form_w8(const er_k_gemv_form_args* f, const void* q_dev, const float* wscale_dev, void* stream) {
     if (!f || !q_dev || !wscale_dev) return fail(ER_ERR_INVALID, "er_k_gemv_form_w8: null argument");
     er_k_gemv_form_args g = *f;
     g.w = q_dev;
     if (!g.w_half) return fail(ER_ERR_UNSUPPORTED, "er_k_gemv_form_w8: the bytes run the fp16 row shapes (set w_half)");
-    if (g.form != ER_FORM_ROW) return fail(ER_ERR_UNSUPPORTED, "er_k_gemv_form_w8: only the row forms stream bytes (form %d)", g.form);
+    if (g.form != ER_FORM_ROW && !form_mfma(g.form))
+        return fail(ER_ERR_UNSUPPORTED, "er_k_gemv_form_w8: only the row forms and the matrix-core forms stream bytes (form %d)", g.form);
     Proj proj = PROJ_QKV;
     ERCHK(gemv_form_check(g, &proj));
     if (proj == PROJ_HEAD) return fail(ER_ERR_UNSUPPORTED, "er_k_gemv_form_w8: the lm_head is not quantised");
     hipStream_t st = (hipStream_t)stream;
     DevBuf<char> blk;
     ERCHK(w8_block_of(blk, q_dev, wscale_dev, g.n, g.k, st));
-    GemvArgs a{};
-    a.W = blk.p; a.bias = g.bias; a.N = g.n; a.xin = g.x; a.ln_w = g.ln_w; a.ln_b = g.ln_b; a.eps = g.eps; a.hout = g.xnorm_out;
-    a.embd = g.embd; a.posemb = g.posemb; a.tok = g.tok; a.pos = g.pos;
-    a.out = g.y; a.resid = g.resid; a.q = g.q_out; a.kcache = g.kcache; a.vcache = g.vcache; a.kv_half = g.kv_half == 2 ? 2 : g.kv_half ? 1 : 0;
-    a.hidden = proj == PROJ_QKV ? g.heads * g.head_dim : 1536; a.head_dim = g.head_dim; a.l_cap = g.l_cap;
-    a.kv_bstride = (long long)g.heads * g.l_cap * g.head_dim;
-    const int pro = g.prologue == ER_PRO_NONE ? PRO_NONE : g.prologue == ER_PRO_EMBED ? PRO_EMBED : PRO_LN;
-    hipError_t e = launch_proj<w8_t>(proj, ProjForm{g.form, g.nw, g.rw, false}, pro, a, g.batch, g.k, SkPart{nullptr, 0}, st);
-    hipError_t e2 = hipStreamSynchronize(st);
-    HIPRET(e);
-    HIPRET(e2);
-    return ER_OK;
+    g.w = blk.p;      // proj_entry tiles the block for the matrix-core forms (tile_weights_kernel<w8_t>) and synchronises before blk goes
+    return gemv_form_t<w8_t>(g, proj, st);
 }
 
 // ---- the fused single-row MLP on caller-owned operands.  er_k_mlp_transpose makes the k-major copy the decode context keeps per

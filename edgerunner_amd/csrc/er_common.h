@@ -25,6 +25,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));   // native vector: usa
 // followed by quad_perm [3,2,1,0] (l ^ 3), 2 and 1 apart through quad_perm.  Each lane still computes op(v[l], v[l ^ OFF]): the
 // association of the butterfly - and with it every bit of every result - is unchanged.
 typedef unsigned er_u32x2 __attribute__((ext_vector_type(2)));
+typedef unsigned er_u32x4 __attribute__((ext_vector_type(4)));
 template <int CTRL>
 __device__ __forceinline__ float dpp_mov(float v) {
     return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), CTRL, 0xF, 0xF, true));

@@ -25,6 +25,9 @@ struct DecodeKnobs {          // the environment knobs of the decode step, read 
     // the prefix pass under prefix groups (env ER_PREFIX_PASS=valu|mfma at er_create, er_set_prefix_pass later): ER_PREFIX_PASS_VALU =
     // attn_prefix_kernel, ER_PREFIX_PASS_MFMA = attn_prefix_mfma_kernel where the plan qualifies (make_decode_plan: shared_mfma)
     int prefix_pass = ER_PREFIX_PASS_VALU;
+    // fp8 mode, matrix-core batched forms (env ER_W8_BATCHED): -1 = stream bytes where the measured rule says so (er_decode_proj.h
+    // w8_streams_batched: qkv, fc1, fc2 at B > 4), 0 = the fp16 tiled copies everywhere, 1 = bytes in every matrix-core form
+    int w8_batched = -1;
 };
 
 // the three switches er_kv_reserve reads for the shape it reserves (tests flip them between two reserves of one context)

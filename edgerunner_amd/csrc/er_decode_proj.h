@@ -120,8 +120,10 @@ static hipError_t prep_rows(const GemvArgs& a, int B, hipStream_t st) {
 // fc2 48 tiles x 4 (narrow: 16) K-ranges.  The XT kernels exist for fp16 weights only: their forms are compiled out for float.
 //
 // fp8 context (w8 = the byte block of the same matrix, k_gemv.h w8_scales; WT = _Float16 and a.W = the fp16 copy of the dequantised
-// values): a row form of a projection that w8_streams() names runs the same (waves x rows) shape of the byte kernel on w8; every other
-// form, and the lm_head, runs the fp16 copy as in fast mode.  The byte type has the fp16 row shapes and nothing else.
+// values): a row form of a projection that w8_streams() names runs the same (waves x rows) shape of the byte kernel on w8, and a
+// matrix-core form of a projection that w8_streams_batched() names runs the same form of gemv_mfma_kernel<w8_t> on the tiled byte copy
+// (run_proj: io.w8_tiled); the VALU batched kernel, the eight-row out_proj and the lm_head run the fp16 copy as in fast mode.  The byte
+// type has the fp16 row shapes and the four matrix-core forms, nothing else.
 //
 // kv8 context (a.kv_half == 2: the KV cache holds e4m3 bytes): every QKV form - row, VALU, both matrix-core forms, with fp16 or byte
 // weights - is launched with EPI_QKV8, the epilogue that encodes (k_gemv.h); nothing else depends on the cache type.
@@ -133,10 +135,28 @@ static hipError_t prep_rows(const GemvArgs& a, int B, hipStream_t st) {
 constexpr bool w8_streams(Proj proj, int B) {
     return proj == PROJ_QKV || proj == PROJ_FC1 || proj == PROJ_FC2 || (proj == PROJ_OUT && B <= 2);
 }
+// The same question for the matrix-core forms (ER_FORM_MFMA, _MFMA_XT, _NARROW, _NARROW_DEFER) of a batch of B rows.  knob = ER_W8_BATCHED
+// as er_create read it: 0 = the fp16 tiled copies everywhere, 1 = bytes in every matrix-core form, anything else = the measured rule.
+// The rule, by the criterion above (profiles/w8_batched_bench.json, scripts/bench_w8_batched.py: fp16 and byte caches, B = 8, 16, 32;
+// DESIGN.md section 4): qkv, fc1 and fc2 are faster beyond the fp16 spread in all six cases (0.65 - 1.36 us of 5.6 - 12.1); out_proj is
+// not - its 0.04 - 0.31 us of 3.2 - 4.0 are inside the spread in three of the four cases it has a matrix-core form in - and keeps the fp16 copy.
+// Batches other than 8, 16 and 32 were not measured: they launch the same two instantiations per form (one batch half up to 16 rows, two
+// up to 32, groups of 32 above that) and go with them; B <= 4 gets here under ER_FORCE_BATCHED=1 only and keeps the fp16 copies.
+constexpr bool w8_streams_batched(Proj proj, int B, int knob) {
+    if (proj == PROJ_HEAD || knob == 0) return false;
+    if (knob == 1) return true;
+    return B > 4 && (proj == PROJ_QKV || proj == PROJ_FC1 || proj == PROJ_FC2);
+}
+// ... and for the stored plan of an fp8 context: does the step stream `proj` as bytes?  (fc2's two tiled forms are both matrix-core forms,
+// so the layer does not matter.)
+inline bool plan_w8_batched(const DecodePlan& p, const DecodeKnobs& k, Proj proj) {
+    return proj != PROJ_HEAD && form_mfma(proj_form(p, k, true, proj, 0).form) && w8_streams_batched(proj, p.B, k.w8_batched);
+}
 
 template <typename WT>
 static hipError_t launch_proj(Proj proj, const ProjForm& f, int pro, const GemvArgs& a, int B, int K, SkPart sk, hipStream_t st, const void* w8 = nullptr) {
     constexpr bool W8 = sizeof(WT) == 1, HALF = sizeof(WT) <= 2;
+    if (W8 && proj == PROJ_HEAD) return hipErrorInvalidValue;      // the lm_head is not quantised
     if constexpr (sizeof(WT) == 2) {
         if (w8 && f.form == ER_FORM_ROW && w8_streams(proj, B)) {
             GemvArgs b = a;
@@ -179,22 +199,26 @@ static hipError_t launch_proj(Proj proj, const ProjForm& f, int pro, const GemvA
             break;
         default: break;
     }
-    if constexpr (sizeof(WT) == 2) {
+    if constexpr (HALF) {
         if (proj == PROJ_QKV && a.kv_half == 2) switch (f.form) {      // the batched QKV forms into a byte cache
-            case ER_FORM_VALU: return gemv_batched_groups<WT, 1, 3, EPI_QKV8>(a, B, K, st);
+            case ER_FORM_VALU:
+                if constexpr (!W8) return gemv_batched_groups<WT, 1, 3, EPI_QKV8>(a, B, K, st);
+                return hipErrorInvalidValue;
             case ER_FORM_MFMA: return gemv_mfma_groups<WT, EPI_QKV8>(a, B, K, sk, st);
             case ER_FORM_MFMA_XT: return gemv_mfma_groups<WT, EPI_QKV8, true>(a, B, K, sk, st);
             default: return hipErrorInvalidValue;
         }
     }
     if (proj == PROJ_QKV && a.kv_half == 2) return hipErrorInvalidValue;      // fp32 weights keep an fp32 cache
-    if constexpr (!W8) switch (f.form) {      // the batched forms (never instantiated for the bytes)
+    switch (f.form) {      // the batched forms (the bytes: the matrix-core forms only)
         case ER_FORM_ROW: break;
         case ER_FORM_ROWS8:
-            if (proj == PROJ_OUT) return gemv_outproj_rows8<WT>(a, B, st);
+            if constexpr (!W8) {
+                if (proj == PROJ_OUT) return gemv_outproj_rows8<WT>(a, B, st);
+            }
             break;
         case ER_FORM_VALU:
-            switch (proj) {
+            if constexpr (!W8) switch (proj) {
                 case PROJ_QKV: return gemv_batched_groups<WT, 1, 3, EPI_QKV>(a, B, K, st);
                 case PROJ_OUT: return gemv_batched_groups<WT, 1, 1, EPI_RESID>(a, B, K, st);
                 case PROJ_FC1: return gemv_batched_groups<WT, 1, 3, EPI_RELU>(a, B, K, st);
@@ -251,6 +275,7 @@ struct ProjIo {
     const void* x_image = nullptr;    // the input as the tiled-input forms read it
     void* out_image = nullptr;        // fc1, ER_FORM_MFMA_XT: the tiled image of the output
     const void* w8 = nullptr;         // fp8 context: the byte block of the same matrix (launch_proj decides who streams it)
+    const void* w8_tiled = nullptr;   // fp8 context whose plan streams this projection's matrix-core form as bytes: the tiled byte copy (er_w8_tile_map.h)
 };
 
 // (projection, form) -> launches: the prologue launch of a batched form, the operands the form reads, launch_proj.
@@ -260,9 +285,12 @@ static hipError_t run_proj(Proj proj, const ProjForm& f, const ProjIo& io, GemvA
         const hipError_t e = launch_prologue(io.pro, a, B, io.rd, io.pro_image, st);
         if (e != hipSuccess) return e;
     }
-    if (form_mfma(f.form)) a.W = io.w_tiled;
+    const bool bytes = sizeof(WT) == 2 && form_mfma(f.form) && io.w8_tiled;
+    if (form_mfma(f.form)) a.W = bytes ? io.w8_tiled : io.w_tiled;
+    if (form_mfma(f.form) && !a.W) return hipErrorInvalidValue;      // the tiled copy this plan streams has not been made
     if (form_tiled_in(f.form)) a.xin = (const float*)io.x_image;
     if (f.form == ER_FORM_MFMA_XT && proj == PROJ_FC1) a.xt_out = io.out_image;
+    if (bytes) return launch_proj<w8_t>(proj, f, io.pro, a, B, K, sk, st);
     return launch_proj<WT>(proj, f, io.pro, a, B, K, sk, st, io.w8);
 }
 

@@ -90,7 +90,7 @@ __device__ __forceinline__ xt_h8 xt_pack(float x0, float x1, float x2, float x3)
 }
 
 // Weight storage types: fp32 (exact mode), fp16 (fast mode, fp32 accumulate) or e4m3 bytes with a power-of-two scale per row (fp8
-// mode, er_w8.h; the row kernels only).  One load of a lane (16 bytes; 8 for the bytes) carries EPL weights; the matching EPL inputs
+// mode, er_w8.h; the row kernels here and the matrix-core batched kernel of k_gemv_mfma.h).  One load of a lane (16 bytes; 8 for the bytes) carries EPL weights; the matching EPL inputs
 // are EPL/4 consecutive float4.  The byte type keeps fp16's lane -> element map (load j of a lane = elements (j * 64 + lane) * 8 .. + 8)
 // and its fmaf chain, so that acc * 2^e is the fp16 kernel's accumulator on the dequantised matrix, bit for bit.
 // A byte matrix [N][K] is ONE block: the N * K bytes, then wscale[N] = 2^e as fp32 (w8_scales) - the kernels keep their argument lists.

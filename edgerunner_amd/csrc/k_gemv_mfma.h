@@ -18,6 +18,7 @@
 // the other batch rows).  K = 6144 (fc2) is additionally split across workgroups (grid.y = 4); those partials go to
 // scratch and splitk_finish_kernel applies the epilogue.
 #pragma once
+#include "er_w8_tile_map.h"
 #include "k_gemv.h"
 
 // timeline hooks of scripts/probes/gemv_mfma_timeline_probe.hip (expand to nothing in the library build)
@@ -31,6 +32,18 @@ namespace er {
 typedef float gm_f4 __attribute__((ext_vector_type(4)));
 constexpr int GM_WAVES = 16, GM_THREADS = GM_WAVES * 64, GM_R2 = 2, GM_ROWS = 16 * GM_R2, GM_KW = 96;
 
+// The eight e4m3 bytes of a piece (element k in byte k: lo = bytes 0..3, hi = 4..7) times the row's scale 2^e as the eight halves the
+// fp16 tiled copy holds in that piece: every q * 2^e is an fp16 number (er_w8.h), and v_cvt_scalef32_pk_f16_fp8 returns it exactly -
+// fp16 subnormals (bytes 0x01 .. 0x07 at e = -15 give 2^-24 .. 7 * 2^-24) and the sign of 0x80 included: all 254 finite codes x
+// e = -15 .. 7 x the four byte positions were compared with cvt_pk_f32_fp8 -> * 2^e -> (_Float16) on an MI355X, and
+// tests/test_gpu_w8_batched.py holds the table against the fp16 form.  Four instructions per piece where that route takes twenty.
+__device__ __forceinline__ f16x8 w8_piece_f16(unsigned lo, unsigned hi, float scale) {
+    typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+    const f16x2 a = __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(lo, scale, false), b = __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(lo, scale, true);
+    const f16x2 c = __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(hi, scale, false), d = __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(hi, scale, true);
+    return (f16x8){a[0], a[1], b[0], b[1], c[0], c[1], d[0], d[1]};
+}
+
 // A workgroup = 16 waves = a 32-row tile (two 16-row A tiles per wave, sharing the X registers: X comes from L2 once
 // per 32 weight rows) x 16 K-slices of 96 = K-range 1536.  NBH = 16-row batch halves (1 or 2); SPLIT: raw partials.
 // XT (fast mode only): a.xin is the tiled hi | lo image of the input (k_gemv.h xt_entry) instead of row-major fp32 - same values, same
@@ -38,9 +51,14 @@ constexpr int GM_WAVES = 16, GM_THREADS = GM_WAVES * 64, GM_R2 = 2, GM_ROWS = 16
 // NWV = waves per workgroup = 96-wide K-slices it reduces through LDS: 16 (K-range 1536, the round-1..3 shape) or 4 (K-range 384:
 // four times the workgroups, each with a quarter of the input image to fetch - for the projections whose split-K partials a later
 // LayerNorm launch finishes anyway: out_proj and fc2 in the tiled fast-mode path).
+// WT = w8_t (fp8 mode): the fp16 form on the TILED BYTE copy (er_w8_tile_map.h).  A lane's 16-byte load for step c carries its piece of
+// both row tiles; the two row scales are loaded in front of everything else (loads retire in issue order, and the conversion is the
+// first consumer behind the weights), and w8_piece_f16 rebuilds in registers the f16x8 the fp16 copy holds for the same (lane, load) -
+// same slots, same MFMA sequence, same reduction and epilogues: bit-identical to the fp16 form on the dequantised matrix.
 template <typename WT, int NBH, int EPI, bool SPLIT, bool XT = false, int NWV = GM_WAVES>
 __global__ __launch_bounds__(64 * NWV) void gemv_mfma_kernel(GemvArgs a, int nb_valid, int K, float* part) {
-    static_assert(!XT || sizeof(WT) == 2, "the tiled activation layout feeds the fp16 matrix cores");
+    static_assert(!XT || sizeof(WT) <= 2, "the tiled activation layout feeds the fp16 matrix cores");
+    constexpr bool W8 = sizeof(WT) == 1;             // e4m3 bytes, paired tiles
     static_assert(NWV == 16 || (NWV == 4 && SPLIT), "4-wave workgroups only produce split-K partials");
     constexpr int GM_WAVES = NWV;               // shadows the namespace constant inside this kernel
     constexpr int EPL = WTraits<WT>::EPL;            // weights per 16-byte load: 4 (fp32) or 8 (fp16)
@@ -55,6 +73,12 @@ __global__ __launch_bounds__(64 * NWV) void gemv_mfma_kernel(GemvArgs a, int nb_
 
     // issue order = arrival order (vmcnt is in-order): first X (L2-resident, back within a microsecond), then the weights
     // chunk by chunk, so the MFMAs of chunk c start as soon as that chunk lands while the later chunks still stream
+    float wsc[GM_R2] = {1.f, 1.f};
+    if constexpr (W8) {                 // rows n0 + li and n0 + 16 + li: lane-indexed, so vector loads; the padding keeps them in range
+        const float* sc = w8t_scales(a.W, a.N, K) + n0 + li;
+#pragma unroll
+        for (int t = 0; t < GM_R2; ++t) wsc[t] = sc[16 * t];
+    }
     f32x4 x[NBH][NLD][XV];
 #pragma unroll
     for (int h = 0; h < NBH; ++h) {
@@ -73,16 +97,21 @@ __global__ __launch_bounds__(64 * NWV) void gemv_mfma_kernel(GemvArgs a, int nb_
                 for (int u = 0; u < XV; ++u) x[h][c][u] = *reinterpret_cast<const f32x4*>(xp + c * 4 * EPL + 4 * u);
         }
     }
-    f32x4 w[GM_R2][NLD];
-    const f32x4* wp[GM_R2];
+    constexpr int NWT = W8 ? 1 : GM_R2;              // weight loads per step: the byte copy pairs the two row tiles in one piece
+    f32x4 w[NWT][NLD];
+    const f32x4* wp[NWT];
     const int KT = K / (4 * EPL), kt0 = (blockIdx.y * GM_WAVES + wid) * NLD, NT = (a.N + 15) / 16;
+    if constexpr (W8) {
+        wp[0] = reinterpret_cast<const f32x4*>(a.W) + w8t_piece(K, blockIdx.x, kt0, lane);
+    } else {
 #pragma unroll
-    for (int t = 0; t < GM_R2; ++t)     // tile (nt, kt) starts at piece (nt*KT + kt)*64; this lane's piece is number `lane`
-        wp[t] = reinterpret_cast<const f32x4*>(a.W) + ((long long)min(n0 / 16 + t, NT - 1) * KT + kt0) * 64 + lane;
+        for (int t = 0; t < GM_R2; ++t)     // tile (nt, kt) starts at piece (nt*KT + kt)*64; this lane's piece is number `lane`
+            wp[t] = reinterpret_cast<const f32x4*>(a.W) + ((long long)min(n0 / 16 + t, NT - 1) * KT + kt0) * 64 + lane;
+    }
 #pragma unroll
     for (int c = 0; c < NLD; ++c)
 #pragma unroll
-        for (int t = 0; t < GM_R2; ++t) w[t][c] = __builtin_nontemporal_load(wp[t] + c * 64);
+        for (int t = 0; t < NWT; ++t) w[t][c] = __builtin_nontemporal_load(wp[t] + c * 64);
     // (weights issued in front of X measured equal at B = 16 / 32: profiles/r05_ab_gm_wfirst.log)
     // the output this thread finishes: slot = tid >> 8 = (row tile t, batch half h), lane image ol, register orr
     //   n = n0 + 16*t + 4*(ol >> 4) + orr,  b = 16*h + (ol & 15)
@@ -99,7 +128,7 @@ __global__ __launch_bounds__(64 * NWV) void gemv_mfma_kernel(GemvArgs a, int nb_
     // registers, and a wave then has a few hundred bytes in flight instead of its whole slice
     __builtin_amdgcn_sched_barrier(0);
     ER_TPG(1);                          // every load issued
-    ER_TPG_WAIT(GM_R2 * NLD);           // probe only: the input image has landed (the weight loads are the youngest GM_R2 * NLD)
+    ER_TPG_WAIT(NWT * NLD);           // probe only: the input image has landed (the weight loads are the youngest NWT * NLD)
     ER_TPG(2);
     ER_TPG_WAIT(0);                     // probe only: the weights have landed
     ER_TPG(3);
@@ -108,7 +137,7 @@ __global__ __launch_bounds__(64 * NWV) void gemv_mfma_kernel(GemvArgs a, int nb_
     for (int t = 0; t < GM_R2; ++t)
 #pragma unroll
         for (int h = 0; h < NBH; ++h) acc[t][h] = (gm_f4){0.f, 0.f, 0.f, 0.f};
-    if constexpr (sizeof(WT) == 2) {
+    if constexpr (sizeof(WT) <= 2) {
         // fast mode: fp16 weights go to the fp16 matrix cores as they are (v_mfma_f32_16x16x16_f16, 16x the fp32 matrix
         // rate: the fp32-MFMA form of this loop was MFMA-issue-bound at 32 rows, 3072 cycles per wave); the fp32
         // activations keep fp32 grade by entering as two fp16 numbers x = hi + lo (|x - hi - lo| <= 2^-22 |x|), one MFMA
@@ -140,7 +169,13 @@ __global__ __launch_bounds__(64 * NWV) void gemv_mfma_kernel(GemvArgs a, int nb_
                 }
 #pragma unroll
             for (int t = 0; t < GM_R2; ++t) {
-                const f16x8 av = __builtin_bit_cast(f16x8, w[t][c]);
+                f16x8 av;
+                if constexpr (W8) {
+                    const er_u32x4 wb = __builtin_bit_cast(er_u32x4, w[0][c]);
+                    av = t == 0 ? w8_piece_f16(wb.x, wb.y, wsc[0]) : w8_piece_f16(wb.z, wb.w, wsc[1]);
+                } else {
+                    av = __builtin_bit_cast(f16x8, w[t][c]);
+                }
 #pragma unroll
                 for (int h = 0; h < NBH; ++h) {
                     acc[t][h] = __builtin_amdgcn_mfma_f32_16x16x32_f16(av, xl[h], acc[t][h], 0, 0, 0);
@@ -210,9 +245,25 @@ __global__ __launch_bounds__(64 * NWV) void gemv_mfma_kernel(GemvArgs a, int nb_
     ER_TPG(6);
 }
 
-// row-major [N][K] -> the tiled layout above; N is padded to a multiple of 16 with zero rows
+// row-major [N][K] -> the tiled layout above; N is padded to a multiple of 16 with zero rows.  WT = w8_t: src is the byte block (bytes,
+// then row scales: k_gemv.h w8_scales), dst the tiled byte block of er_w8_tile_map.h (N padded to 32 rows, pad scales 1)
 template <typename WT>
 __global__ __launch_bounds__(ER_WG) void tile_weights_kernel(const WT* src, f32x4* dst, int N, int K) {
+    if constexpr (sizeof(WT) == 1) {
+        const long long total = w8t_pieces(N, K), stride = (long long)gridDim.x * ER_WG, first = (long long)blockIdx.x * ER_WG + threadIdx.x;
+        for (long long p = first; p < total; p += stride) {
+            int n, k;
+            w8t_piece_source(K, p, &n, &k);
+            er_u32x4 v = {0u, 0u, 0u, 0u};
+            if (n < N) { const er_u32x2 lo = *reinterpret_cast<const er_u32x2*>(src + (long long)n * K + k); v.x = lo.x; v.y = lo.y; }
+            if (n + 16 < N) { const er_u32x2 hi = *reinterpret_cast<const er_u32x2*>(src + (long long)(n + 16) * K + k); v.z = hi.x; v.w = hi.y; }
+            dst[p] = __builtin_bit_cast(f32x4, v);
+        }
+        const float* sc = w8_scales(src, N, K);
+        float* sd = reinterpret_cast<float*>(reinterpret_cast<unsigned char*>(dst) + w8t_rows(N) * K);
+        for (long long i = first; i < w8t_rows(N); i += stride) sd[i] = i < N ? sc[i] : 1.0f;
+        return;
+    }
     constexpr int EPL = WTraits<WT>::EPL;
     const int KT = K / (4 * EPL), NT = (N + 15) / 16;
     const long long total = (long long)NT * KT * 64;
@@ -227,7 +278,10 @@ __global__ __launch_bounds__(ER_WG) void tile_weights_kernel(const WT* src, f32x
     }
 }
 template <typename WT>
-inline size_t tiled_weight_bytes(int N, int K) { return (size_t)((N + 15) / 16) * 16 * K * sizeof(WT); }
+inline size_t tiled_weight_bytes(int N, int K) {
+    if constexpr (sizeof(WT) == 1) return w8t_block_bytes(N, K);
+    else return (size_t)((N + 15) / 16) * 16 * K * sizeof(WT);
+}
 
 // out(b, n) = epilogue(sum_s part[s][b][n]) in slice order.  (Round 3 tried this finish fused with the NEXT layer's LayerNorm - one
 // workgroup per batch row, saving the prep_rows launch in front of qkv: measured SLOWER, 12.7 -> 18.5 us for fc2 against 11.6 -> 9.3

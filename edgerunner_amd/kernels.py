@@ -103,7 +103,8 @@ def gemv_form(form, epilogue, w, B, *, x=None, bias=None, ln=None, embed=None, s
     qkv=(kcache, vcache, pos[, q_out]) for ER_EPI_QKV: caches [B, heads, l_cap, head_dim] fp32, fp16 or uint8 (e4m3 bytes) are written in place at
     pos[b].  prep_xt: also return the image the batched prologue launch writes (prep_xt_image: write into this one);
     xt_out_image: the image the tiled fc1 writes (allocated zeroed when the form needs one).
-    w8=(q uint8 [n, k], wscale fp32 [n]): the row form on e4m3 bytes and row scales in place of w (``er_k_gemv_form_w8``; gemv_form_w8).
+    w8=(q uint8 [n, k], wscale fp32 [n]): the row form or a matrix-core form (ER_FORM_MFMA, _MFMA_XT, _NARROW, _NARROW_DEFER) on e4m3 bytes
+    and row scales in place of w (``er_k_gemv_form_w8``; gemv_form_w8).
     Returns a dict: y, xnorm, q, part (ER_FORM_NARROW_DEFER: [groups, k / 384 * 32 * n] raw block), prep_xt, xt_out - those the call produced."""
     lib = native.load_library()
     dev = (x if x is not None else (embed[0] if embed is not None else sk[0])).device
@@ -177,8 +178,9 @@ def gemv_form(form, epilogue, w, B, *, x=None, bias=None, ln=None, embed=None, s
 
 
 def gemv_form_w8(form, epilogue, q, wscale, B, **kw):
-    """``gemv_form`` on the e4m3 bytes q [n, k] (uint8) and row scales wscale [n] of fp8 mode: the fp16 row shapes of qkv, out_proj,
-    fc1 and fc2, bit-identical to ``gemv_form`` on the fp16 matrix q * wscale."""
+    """``gemv_form`` on the e4m3 bytes q [n, k] (uint8) and row scales wscale [n] of fp8 mode: the fp16 row shapes and the four
+    matrix-core batched forms of qkv, out_proj, fc1 and fc2 (ER_FORM_VALU and ER_FORM_ROWS8 have no byte kernel and raise),
+    bit-identical to ``gemv_form`` on the fp16 matrix q * wscale."""
     return gemv_form(form, epilogue, None, B, w8=(q, wscale), **kw)
 
 

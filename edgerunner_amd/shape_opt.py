@@ -497,6 +497,13 @@ class NativeShapeOPT:
         native.check(self.lib.er_ctx_plan(self._ctx, C.byref(p)), "er_ctx_plan")
         return {n: int(getattr(p, n)) for n, _ in native.ErDecodePlan._fields_}
 
+    def w8_streams(self):
+        """fp8 mode: which projections the reserved shape's decode step streams as e4m3 bytes (``er_ctx_w8_streams``): dict of 0 / 1 for
+        qkv, out_proj, fc1 and fc2.  All zero in the other precisions."""
+        out = (C.c_int32 * 4)()
+        native.check(self.lib.er_ctx_w8_streams(self._ctx, out), "er_ctx_w8_streams")
+        return dict(zip(("qkv", "out_proj", "fc1", "fc2"), (int(v) for v in out)))
+
     def mlp_nnz(self):
         """Live fc1 neurons per (layer, workgroup) that the fused single-row MLP counted in the last decode step (``er_mlp_nnz``):
         int32 [num_layers, 256], each 0 .. 24.  Raises unless the reserved shape runs the fused MLP (one row, ``ER_MLP_V`` on)."""

@@ -381,6 +381,10 @@ typedef struct {
 int er_plan_decode(int batch, int heads, int head_dim, int hidden, int l_cap, er_decode_plan* out);
 /* the stored plan of a live context (knobs as read by er_create, cache and ER_FORCE_BATCHED as of the last er_kv_reserve) */
 int er_ctx_plan(er_ctx* ctx, er_decode_plan* out);
+/* fp8 mode: which of qkv / out_proj / fc1 / fc2 (out[0..3]) the stored plan streams as e4m3 bytes - the row forms at batch <= 4, the
+ * matrix-core batched forms above that where the measured rule (or ER_W8_BATCHED=1 at er_create; 0 = nowhere above batch 4) says so.
+ * All zero in every other mode.  er_decode_plan keeps its layout. */
+int er_ctx_w8_streams(er_ctx* ctx, int32_t out[4]);
 /* tile shape launch_gemm* picks for an [m, n] output in `batch` slices: 1 = 128x128, 2 = 64x128, 3 = 64x64 (ER_GEMM_TILE forces) */
 int er_plan_gemm_tile(int m, int n, int batch);
 
@@ -517,9 +521,10 @@ int er_k_attn_outproj3(const float* q_dev, const void* k_dev, const void* v_dev,
  * [-15, 7], bytes q = e4m3fn(w * 2^-e) (saturating, round to nearest even), and the dequantised values q * 2^e as fp16.  The four
  * outputs are device memory and nullable: q_dev uint8 [n][k], e_dev int32 [n], w16_dev fp16 [n][k], wscale_dev fp32 [n] = 2^e.
  * A NaN or an infinity in the source is ER_ERR_INVALID.
- * er_k_gemv_form_w8: er_k_gemv_form on (q_dev, wscale_dev) in place of args->w (not read) - ER_FORM_ROW and the fp16 row shapes
- * (w_half set) of qkv, out_proj, fc1 and fc2 only, with er_k_gemv_form's refusals before any launch; bit-identical to er_k_gemv_form
- * on the fp16 matrix q * 2^e.  er_k_attn_outproj3_w8: er_k_attn_outproj3 with Wo as bytes and row scales.  All block. */
+ * er_k_gemv_form_w8: er_k_gemv_form on (q_dev, wscale_dev) in place of args->w (not read) - ER_FORM_ROW with the fp16 row shapes and
+ * the four matrix-core forms (ER_FORM_MFMA, _MFMA_XT, _NARROW, _NARROW_DEFER; the entry tiles the bytes itself), w_half set, of qkv,
+ * out_proj, fc1 and fc2 only, with er_k_gemv_form's refusals before any launch; ER_FORM_VALU and ER_FORM_ROWS8 have no byte kernel and
+ * are refused.  Bit-identical to er_k_gemv_form on the fp16 matrix q * 2^e.  er_k_attn_outproj3_w8: er_k_attn_outproj3 with Wo as bytes and row scales.  All block. */
 int er_k_w8_quantize(const void* src, int dtype, int on_device, int n, int k, void* q_dev, int32_t* e_dev, void* w16_dev,
                      float* wscale_dev, void* stream);
 int er_k_gemv_form_w8(const er_k_gemv_form_args* args, const void* q_dev, const float* wscale_dev, void* stream);
