@@ -76,6 +76,11 @@ struct LayerW {
     unsigned char *wqkv_q = nullptr, *wo_q = nullptr, *w1_q = nullptr, *w2_q = nullptr;
     void *wqkv_t = nullptr, *wo_t = nullptr, *w1_t = nullptr, *w2_t = nullptr;   // tiled copies for the matrix-core batched kernels (k_gemv_mfma.h)
     void *wqkv_t8 = nullptr, *wo_t8 = nullptr, *w1_t8 = nullptr, *w2_t8 = nullptr;   // fp8 mode: tiled BYTE copies (er_w8_tile_map.h) of the projections a plan streams as bytes
+    // fp4 mode (er_w4.h): the canonical MXFP4 blocks of the same four matrices (nibble bytes [N][K / 2], then e8m0 bytes [N][K / 32]) - *_h and
+    // the fp32 copies hold the dequantised values - and the quad-interleaved copies the nibble row kernels stream (er_w4_map.h; made by
+    // make_w4_streams for the projections that have a nibble form)
+    unsigned char *wqkv_q4 = nullptr, *wo_q4 = nullptr, *w1_q4 = nullptr, *w2_q4 = nullptr;
+    void *wqkv_s4 = nullptr, *w1_s4 = nullptr, *w2_s4 = nullptr;
     void* w2_kt = nullptr;   // fc2.weight k-major, [intermediate][hidden] in the streamed weight type: the fused single-row MLP (k_mlp_sparse.h)
     float *wqkv = nullptr, *bqkv = nullptr;   // fused [3*hidden][hidden] in q,k,v order
     float *wo = nullptr, *bo = nullptr, *ln1w = nullptr, *ln1b = nullptr;
@@ -187,6 +192,8 @@ struct er_ctx {
     bool kv8 = false;        // kv8 mode: fast (or fp8), with the KV cache stored as e4m3 bytes without a scale (er_w8.h kv8_encode)
     int kv_type = 0;         // the cache type as the kernels' kv_half argument takes it: 0 = fp32, 1 = fp16, 2 = e4m3 bytes
     bool w8 = false;         // fp8 mode: fast, with the six decoder matrices per layer quantised by row; the row forms and (w8_streams_batched) the matrix-core forms of the step stream the bytes
+    bool w4 = false;         // fp4 mode: fast, with the six decoder matrices per layer quantised by blocks of 32 (MXFP4); the row forms w4_streams names stream the nibbles
+    bool w4_valid = false;   // LayerW::*_s4 match the loaded weights
     float *proj_w = nullptr, *proj_b = nullptr, *normc_w = nullptr, *normc_b = nullptr;
     PointEnc pe;             // point encoder (cond_mode POINT)
     WeightTable w;           // every checkpoint key (register_weights)
@@ -247,6 +254,7 @@ static DecodeKnobs read_knobs(bool fast) {
     const char* pp = getenv("ER_PREFIX_PASS");      // valu | mfma; er_create keeps "mfma" for an fp16 cache only (er_set_prefix_pass)
     k.prefix_pass = (pp && !strcmp(pp, "mfma")) ? ER_PREFIX_PASS_MFMA : ER_PREFIX_PASS_VALU;
     k.w8_batched = env_is("ER_W8_BATCHED", '0') ? 0 : env_is("ER_W8_BATCHED", '1') ? 1 : -1;
+    k.w4_rows = env_is("ER_W4_ROWS", '0') ? 0 : env_is("ER_W4_ROWS", '1') ? 1 : -1;
     return k;
 }
 
@@ -296,6 +304,7 @@ static void register_weights(er_ctx* c) {
     const size_t H = g.hidden_dim, I = g.intermediate_dim, V = g.vocab_size;
     t.fp16 = c->fast;
     t.w8 = c->w8;
+    t.w4 = c->w4;
     if (g.cond_mode == ER_COND_POINT) pe_attach(t, c->pe, ER_PE_EMBED, "er_create", "");
     if (g.cond_mode != ER_COND_NONE) {
         t.lin("proj_cond", &c->proj_w, &c->proj_b, H, g.point_latent_dim);
@@ -310,13 +319,13 @@ static void register_weights(er_ctx* c) {
         const char* qkv[3] = {"q_proj", "k_proj", "v_proj"};     // fused [3 H][H] (+ bias [3 H]) in q, k, v order
         for (size_t j = 0; j < 3; ++j) {
             const std::string q = p + "self_attn." + qkv[j];
-            t.add(q + ".weight", &L.wqkv, H * H).slice(3 * H * H, j * H * H).half(&L.wqkv_h).rows8(&L.wqkv_q, H);
+            t.add(q + ".weight", &L.wqkv, H * H).slice(3 * H * H, j * H * H).half(&L.wqkv_h).rows8(&L.wqkv_q, H).blocks4(&L.wqkv_q4, H);
             t.add(q + ".bias", &L.bqkv, H).slice(3 * H, j * H);
         }
-        t.lin(p + "self_attn.out_proj", &L.wo, &L.bo, H, H).half(&L.wo_h).rows8(&L.wo_q, H);
+        t.lin(p + "self_attn.out_proj", &L.wo, &L.bo, H, H).half(&L.wo_h).rows8(&L.wo_q, H).blocks4(&L.wo_q4, H);
         t.lin(p + "self_attn_layer_norm", &L.ln1w, &L.ln1b, H, 1);
-        t.lin(p + "fc1", &L.w1, &L.b1, I, H).half(&L.w1_h).rows8(&L.w1_q, H);
-        t.lin(p + "fc2", &L.w2, &L.b2, H, I).half(&L.w2_h).rows8(&L.w2_q, I);
+        t.lin(p + "fc1", &L.w1, &L.b1, I, H).half(&L.w1_h).rows8(&L.w1_q, H).blocks4(&L.w1_q4, H);
+        t.lin(p + "fc2", &L.w2, &L.b2, H, I).half(&L.w2_h).rows8(&L.w2_q, I).blocks4(&L.w2_q4, I);
         t.lin(p + "final_layer_norm", &L.ln2w, &L.ln2b, H, 1);
     }
     t.add("mesh_decoder.lm_head.weight", &c->lm_head, V * H).half(&c->lm_head_h);
@@ -331,12 +340,13 @@ extern "C" int er_create(const er_config* cfg, int device, er_ctx** out) {
     const int D = cfg->hidden_dim / cfg->num_heads;
     if (D != 96 && D != 64) return fail(ER_ERR_UNSUPPORTED, "head_dim %d not built (96, 64)", D);
     const bool exact = cfg->weight_dtype == ER_F32 && cfg->kv_dtype == ER_F32;
-    const bool kv8 = cfg->kv_dtype == ER_F8E4M3 && (cfg->weight_dtype == ER_F16 || cfg->weight_dtype == ER_F8E4M3);
+    const bool kv8 = cfg->kv_dtype == ER_F8E4M3 && (cfg->weight_dtype == ER_F16 || cfg->weight_dtype == ER_F8E4M3 || cfg->weight_dtype == ER_F4E2M1);
     const bool w8 = cfg->weight_dtype == ER_F8E4M3 && (cfg->kv_dtype == ER_F16 || kv8);
-    const bool fast = w8 || kv8 || (cfg->weight_dtype == ER_F16 && cfg->kv_dtype == ER_F16);
+    const bool w4 = cfg->weight_dtype == ER_F4E2M1 && (cfg->kv_dtype == ER_F16 || kv8);
+    const bool fast = w8 || w4 || kv8 || (cfg->weight_dtype == ER_F16 && cfg->kv_dtype == ER_F16);
     if (!exact && !fast)
-        return fail(ER_ERR_UNSUPPORTED, "built modes: fp32 weights + fp32 KV (exact), fp16 weights + fp16 KV (fast) or e4m3 row-scaled weights + fp16 KV (fp8); "
-                                        "the fast and fp8 weights also run on an e4m3 byte KV cache (kv8)");
+        return fail(ER_ERR_UNSUPPORTED, "built modes: fp32 weights + fp32 KV (exact), fp16 weights + fp16 KV (fast), e4m3 row-scaled weights + fp16 KV (fp8) or "
+                                        "e2m1 block-scaled weights + fp16 KV (fp4); the fast, fp8 and fp4 weights also run on an e4m3 byte KV cache (kv8)");
     if (kv8 && D != 96) return fail(ER_ERR_UNSUPPORTED, "the e4m3 KV cache (kv8) is built for head_dim 96; got %d", D);
     if (cfg->vocab_size > ER_HEAD_MAX_VOCAB) return fail(ER_ERR_UNSUPPORTED, "vocab_size > %d", ER_HEAD_MAX_VOCAB);
     if (cfg->cond_mode == ER_COND_POINT && (cfg->point_hidden_dim != 1024 || cfg->point_hidden_dim % cfg->point_num_heads))
@@ -348,6 +358,7 @@ extern "C" int er_create(const er_config* cfg, int device, er_ctx** out) {
     c->D = D;
     c->fast = fast;
     c->w8 = w8;
+    c->w4 = w4;
     c->kv8 = kv8;
     c->kv_type = kv8 ? 2 : fast ? 1 : 0;
     c->kv_esz = kv8 ? 1 : fast ? 2 : 4;
@@ -385,7 +396,7 @@ extern "C" int er_load_tensor(er_ctx* c, const char* key, const void* data, int 
     if (!c || !key) return fail(ER_ERR_INVALID, "er_load_tensor: bad argument");
     HIPCHK(hipSetDevice(c->device));
     const int rc = weights_load(c->w, c->own_stream, "er_load_tensor", key, data, dtype, ndim, shape, on_device);
-    if (rc != 1) c->tiled_valid = c->kmajor_valid = false;  // any reload invalidates the tiled copies of the batched path and the k-major fc2 copies
+    if (rc != 1) c->tiled_valid = c->kmajor_valid = c->w4_valid = false;  // any reload invalidates the tiled copies of the batched path, the k-major fc2 copies and the streamed nibble copies
     return rc;
 }
 
@@ -450,6 +461,38 @@ static int make_tiled_weights(er_ctx* c, const DecodePlan& plan) {
     }
     HIPCHK(hipStreamSynchronize(c->own_stream));
     c->tiled_valid = true;
+    return 0;
+}
+
+// fp4 mode: the quad-interleaved copies of qkv, fc1 and fc2 the nibble row kernels stream (er_w4_map.h; 15.4 MB per layer), made the
+// first time a shape is reserved whose row forms stream nibbles under this context's ER_W4_ROWS; owned by the weight table.  A reload
+// invalidates them (w4_valid): until they are made again the step gets no copy and a launch that wants one fails (launch_proj)
+static bool plan_w4_rows(const DecodePlan& p, const DecodeKnobs& k, Proj proj) {
+    return !p.batched && !(p.mlp_fused && proj != PROJ_QKV) && w4_streams(proj, p.B, k.w4_rows);
+}
+static int make_w4_streams(er_ctx* c, const DecodePlan& plan) {
+    if (!c->w4 || c->w4_valid || weights_missing(c->w)) return 0;   // weights still loading: er_prefill comes back here
+    // whatever the fused MLP takes over: a row class (er_decode) runs fc1 and fc2 as row GEMVs on the same reserved shape
+    const auto wants = [&](Proj proj) { return !plan.batched && w4_streams(proj, plan.B, c->knobs.w4_rows); };
+    if (!wants(PROJ_QKV) && !wants(PROJ_FC1) && !wants(PROJ_FC2)) return 0;
+    const int H = c->cfg.hidden_dim, I = c->cfg.intermediate_dim;
+    for (LayerW& L : c->layers) {
+        const unsigned char* src[3] = {L.wqkv_q4, L.w1_q4, L.w2_q4};
+        void** dst[3] = {&L.wqkv_s4, &L.w1_s4, &L.w2_s4};
+        const int N[3] = {3 * H, I, H}, K[3] = {H, H, I};
+        for (int i = 0; i < 3; ++i) {
+            if (!w4map::shape_ok(N[i], K[i])) return fail(ER_ERR_UNSUPPORTED, "fp4: a %d x %d matrix has no quad-interleaved copy", N[i], K[i]);
+            if (!*dst[i]) {
+                char* blk = nullptr;
+                ERCHK(c->w.alloc(&blk, (size_t)w4map::stream_bytes(N[i], K[i])));
+                *dst[i] = blk;
+            }
+            hipLaunchKernelGGL(w4_interleave_kernel, dim3(2048), dim3(ER_WG), 0, c->own_stream, src[i], (unsigned char*)*dst[i], (long long)N[i], K[i]);
+            HIPCHK(hipGetLastError());
+        }
+    }
+    HIPCHK(hipStreamSynchronize(c->own_stream));
+    c->w4_valid = true;
     return 0;
 }
 
@@ -519,6 +562,17 @@ extern "C" int er_ctx_w8_streams(er_ctx* c, int32_t out[4]) {
     return ER_OK;
 }
 
+// which of qkv / out_proj / fc1 / fc2 the stored plan of a live context streams as e2m1 nibbles (fp4 mode; all zero in every other mode)
+extern "C" int er_ctx_w4_streams(er_ctx* c, int32_t out[4]) {
+    if (!c || !out) return fail(ER_ERR_INVALID, "er_ctx_w4_streams: null argument");
+    const DecodePlan& p = c->kv->plan;
+    if (p.B <= 0) return fail(ER_ERR_INVALID, "er_ctx_w4_streams: no cache reserved (call er_kv_reserve)");
+    DecodePlan q = p;
+    if (c->kv->row_class) q.mlp_fused = false;      // a row class runs fc1 and fc2 as row GEMVs
+    for (int pj = 0; pj < 4; ++pj) out[pj] = c->w4 && plan_w4_rows(q, c->knobs, (Proj)pj) ? 1 : 0;
+    return ER_OK;
+}
+
 extern "C" int er_plan_gemm_tile(int m, int n, int batch) {
     if (m <= 0 || n <= 0 || batch <= 0) return fail(ER_ERR_INVALID, "er_plan_gemm_tile: bad argument");
     return gemm_pick_tile(m, n, batch);
@@ -581,6 +635,7 @@ static int kv_alloc(er_ctx* c, KvMem& m, int batch, int Lcap) {
     m.st.row_budget = m.d_row_budget.p;
     ERCHK(m.d_out_ids.ensure(b * (size_t)Lcap));
     if (p.mfma) ERCHK(make_tiled_weights(c, p));
+    ERCHK(make_w4_streams(c, p));
     if (p.mlp_fused) {
         ERCHK(make_kmajor_weights(c));
         ERCHK(m.mlp_part.ensure((size_t)MLP_WGS * hid));
@@ -686,6 +741,7 @@ static hipError_t launch_kind_t(er_ctx* c, int kind, int layer, hipStream_t st, 
             }
             io.w_tiled = L.wqkv_t; io.x_image = kv.xt_h.p; io.pro_image = p.xt ? kv.xt_h.p : nullptr;
             if (c->w8) io.w8 = L.wqkv_q;
+            if (c->w4) io.w4 = {true, c->w4_valid ? L.wqkv_s4 : nullptr, c->knobs.w4_rows};
             io.w8_tiled = bytes_of(PROJ_QKV, L.wqkv_t8);
             return run_proj<WT>(PROJ_QKV, form_of(PROJ_QKV, layer), io, a, B, H, sk, st);
         }
@@ -732,6 +788,7 @@ static hipError_t launch_kind_t(er_ctx* c, int kind, int layer, hipStream_t st, 
             if (form_of(PROJ_OUT, layer).defer) io.rd = {sk.p, L.bo, kv.hbuf.p, SK_SLICES_OUTPROJ};
             io.w_tiled = L.w1_t; io.x_image = kv.xt_h.p; io.pro_image = p.xt ? kv.xt_h.p : nullptr; io.out_image = kv.xt_f.p;
             if (c->w8) io.w8 = L.w1_q;
+            if (c->w4) io.w4 = {true, c->w4_valid ? L.w1_s4 : nullptr, c->knobs.w4_rows};
             io.w8_tiled = bytes_of(PROJ_FC1, L.w1_t8);
             return run_proj<WT>(PROJ_FC1, form_of(PROJ_FC1, layer), io, a, B, H, sk, st);
         }
@@ -741,6 +798,7 @@ static hipError_t launch_kind_t(er_ctx* c, int kind, int layer, hipStream_t st, 
             a.W = HALF ? (const void*)L.w2_h : (const void*)L.w2; a.bias = L.b2; a.N = H; a.xin = kv.fbuf.p; a.out = kv.ypre.p; a.resid = kv.h1buf.p;
             io.w_tiled = L.w2_t; io.x_image = kv.xt_f.p;
             if (c->w8) io.w8 = L.w2_q;
+            if (c->w4) io.w4 = {true, c->w4_valid ? L.w2_s4 : nullptr, c->knobs.w4_rows};
             io.w8_tiled = bytes_of(PROJ_FC2, L.w2_t8);
             return run_proj<WT>(PROJ_FC2, form_of(PROJ_FC2, layer), io, a, B, I, sk, st);
         }
@@ -1064,6 +1122,7 @@ static int prefill_run(er_ctx* c, const float* embeds, int B, int S, hipStream_t
     HIPCHK(hipSetDevice(c->device));
     const DecodePlan& p = c->kv->plan;
     if (p.mfma) ERCHK(make_tiled_weights(c, p));
+    ERCHK(make_w4_streams(c, p));
     if (p.mlp_fused) ERCHK(make_kmajor_weights(c));
     const er_config& g = c->cfg;
     const int H = g.hidden_dim, I = g.intermediate_dim, NH = g.num_heads, D = c->D;
@@ -1567,6 +1626,7 @@ extern "C" int er_queue_begin(er_ctx* c, const er_decode_params* p, int check_ev
     HIPCHK(hipSetDevice(c->device));
     hipStream_t st = pick(c, stream);
     if (c->kv->plan.mfma) ERCHK(make_tiled_weights(c, c->kv->plan));
+    ERCHK(make_w4_streams(c, c->kv->plan));
     if (c->kv->plan.mlp_fused) ERCHK(make_kmajor_weights(c));
     ERCHK(c->q_look.ensure((size_t)3 * B + 1));
     if (c->q_pinned) { hipHostFree(c->q_pinned); c->q_pinned = nullptr; }
@@ -1762,6 +1822,12 @@ static int profile_impl(er_ctx* c, int repeats, int use_graph, float* avg_us, do
         };
         bytes[0] -= less(PROJ_QKV, 3.0 * H, H);
         bytes[3] -= less(PROJ_OUT, H, H);
+        bytes[4] -= less(PROJ_FC1, I, H);
+        bytes[5] -= less(PROJ_FC2, H, I);
+    }
+    if (c->w4) {   // the row forms that stream nibbles: half a byte per weight + a scale byte per 32 in place of 2 bytes per weight
+        const auto less = [&](Proj proj, double n, double k) { return plan_w4_rows(p, c->knobs, proj) ? n * k * (w - 0.5 - 1.0 / 32.0) : 0.0; };
+        bytes[0] -= less(PROJ_QKV, 3.0 * H, H);
         bytes[4] -= less(PROJ_FC1, I, H);
         bytes[5] -= less(PROJ_FC2, H, I);
     }
@@ -2164,6 +2230,94 @@ extern "C" int er_k_gemv_form_w8(const er_k_gemv_form_args* f, const void* q_dev
     ERCHK(w8_block_of(blk, q_dev, wscale_dev, g.n, g.k, st));
     g.w = blk.p;      // proj_entry tiles the block for the matrix-core forms (tile_weights_kernel<w8_t>) and synchronises before blk goes
     return gemv_form_t<w8_t>(g, proj, st);
+}
+
+// ---- fp4 mode on caller-owned operands: the block quantiser of the weight loader, the hardware conversion the nibble kernels read
+// with, and the nibble kernels behind the row forms.
+extern "C" int er_k_w4_quantize(const void* src, int dtype, int on_device, int n, int k, void* block_dev, int32_t* e_dev, void* w16_dev, void* stream) {
+    if (!src || n < 1 || k < 1) return fail(ER_ERR_INVALID, "er_k_w4_quantize: bad argument");
+    if (k % W4_BLOCK) return fail(ER_ERR_INVALID, "er_k_w4_quantize: k must be a multiple of %d", W4_BLOCK);
+    if (dtype != ER_F32 && dtype != ER_F16 && dtype != ER_BF16) return fail(ER_ERR_INVALID, "er_k_w4_quantize: dtype %d", dtype);
+    hipStream_t st = (hipStream_t)stream;
+    DevBuf<char> stage;
+    DevBuf<int> bad;
+    ERCHK(bad.ensure(1));
+    if (!on_device) {
+        const size_t bytes = (size_t)n * k * (dtype == ER_F32 ? 4 : 2);
+        ERCHK(stage.ensure((bytes + 3) / 4 * 4));
+        HIPCHK(hipMemcpy(stage.p, src, bytes, hipMemcpyHostToDevice));
+        src = stage.p;
+    }
+    HIPCHK(hipMemsetAsync(bad.p, 0, sizeof(int), st));
+    unsigned char* nib = (unsigned char*)block_dev;
+    hipLaunchKernelGGL(quant_blocks_kernel, dim3((unsigned)n), dim3(ER_WG), 0, st, src, dtype, (size_t)k, (float*)nullptr, (_Float16*)w16_dev, nib,
+                       nib ? nib + w4_nibble_bytes(n, k) : nullptr, (int*)e_dev, bad.p);
+    hipError_t e = hipGetLastError();
+    hipError_t e2 = hipStreamSynchronize(st);
+    HIPRET(e);
+    HIPRET(e2);
+    int flag = 0;
+    HIPCHK(hipMemcpy(&flag, bad.p, sizeof(int), hipMemcpyDeviceToHost));
+    if (flag) return fail(ER_ERR_INVALID, "er_k_w4_quantize: the matrix holds a NaN or an infinity");
+    return ER_OK;
+}
+
+// out[((e - W4_E_MIN) * 256 + byte) * 4 + sel] = the two numbers v_cvt_scalef32_pk_f32_fp4 makes of byte `byte`, placed as byte `sel` of a
+// dword whose other bytes hold other codes, under the scale 2^e
+__global__ __launch_bounds__(256) void w4_cvt_probe_kernel(float* out) {
+    typedef float f32x2 __attribute__((ext_vector_type(2)));
+    const unsigned int byte = threadIdx.x, e = blockIdx.x;
+    const float scale = w4_scale_f32(w4_scale_byte((int)e + W4_E_MIN));
+    f32x2* o = reinterpret_cast<f32x2*>(out) + ((size_t)e * 256 + byte) * 4;
+    const unsigned int fill = 0x5a3c96e1u;
+    o[0] = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4((fill & ~0xffu) | byte, scale, 0);
+    o[1] = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4((fill & ~0xff00u) | (byte << 8), scale, 1);
+    o[2] = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4((fill & ~0xff0000u) | (byte << 16), scale, 2);
+    o[3] = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4((fill & ~0xff000000u) | (byte << 24), scale, 3);
+}
+extern "C" int er_k_w4_cvt_probe(float* out_dev, void* stream) {
+    if (!out_dev) return fail(ER_ERR_INVALID, "er_k_w4_cvt_probe: null argument");
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(w4_cvt_probe_kernel, dim3(W4_E_MAX - W4_E_MIN + 1), dim3(256), 0, st, out_dev);
+    hipError_t e = hipGetLastError();
+    hipError_t e2 = hipStreamSynchronize(st);
+    HIPRET(e);
+    HIPRET(e2);
+    return ER_OK;
+}
+
+// er_k_gemv_form's checks on a canonical MXFP4 block in place of args->w (not read): ER_FORM_ROW of qkv, fc1 and fc2 with fp16 or e4m3
+// caches.  args names the fp16 row form the step would launch (w_half, nw, rw: checked like er_k_gemv_form's); the nibble kernel runs in
+// the projection's own nibble shape (er_decode_proj.h launch_proj_w4).  Builds the interleaved copy itself.  Everything else is refused
+// before any launch.
+extern "C" int er_k_gemv_form_w4(const er_k_gemv_form_args* f, const void* block_dev, void* stream) {
+    if (!f || !block_dev) return fail(ER_ERR_INVALID, "er_k_gemv_form_w4: null argument");
+    er_k_gemv_form_args g = *f;
+    g.w = block_dev;
+    if (!g.w_half) return fail(ER_ERR_UNSUPPORTED, "er_k_gemv_form_w4: the nibbles stand in for fp16 row forms (set w_half)");
+    if (g.form != ER_FORM_ROW) return fail(ER_ERR_UNSUPPORTED, "er_k_gemv_form_w4: only the row forms stream nibbles (form %d)", g.form);
+    Proj proj = PROJ_QKV;
+    ERCHK(gemv_form_check(g, &proj));
+    if (!w4_has_row_form(proj)) return fail(ER_ERR_UNSUPPORTED, "er_k_gemv_form_w4: %s has no nibble form", proj == PROJ_OUT ? "out_proj" : "the lm_head");
+    if (!w4map::shape_ok(g.n, g.k)) return fail(ER_ERR_UNSUPPORTED, "er_k_gemv_form_w4: n %d must be a multiple of 4 (rows are streamed in quads)", g.n);
+    if (proj == PROJ_QKV && !g.kv_half) return fail(ER_ERR_UNSUPPORTED, "er_k_gemv_form_w4: fp4 weights go with an fp16 or an e4m3 cache, not fp32");
+    hipStream_t st = (hipStream_t)stream;
+    DevBuf<char> copy;
+    ERCHK(copy.ensure((size_t)w4map::stream_bytes(g.n, g.k)));
+    hipLaunchKernelGGL(w4_interleave_kernel, dim3(1024), dim3(ER_WG), 0, st, (const unsigned char*)block_dev, (unsigned char*)copy.p, (long long)g.n, g.k);
+    hipError_t e = hipGetLastError();
+    GemvArgs a{};
+    a.W = copy.p; a.bias = g.bias; a.N = g.n; a.xin = g.x; a.ln_w = g.ln_w; a.ln_b = g.ln_b; a.eps = g.eps; a.hout = g.xnorm_out;
+    a.embd = g.embd; a.posemb = g.posemb; a.tok = g.tok; a.pos = g.pos;
+    a.out = g.y; a.resid = g.resid; a.q = g.q_out; a.kcache = g.kcache; a.vcache = g.vcache; a.kv_half = g.kv_half == 2 ? 2 : g.kv_half ? 1 : 0;
+    a.hidden = proj == PROJ_QKV ? g.heads * g.head_dim : 1536; a.head_dim = g.head_dim; a.l_cap = g.l_cap;
+    a.kv_bstride = (long long)g.heads * g.l_cap * g.head_dim;
+    const int pro = g.prologue == ER_PRO_NONE ? PRO_NONE : g.prologue == ER_PRO_EMBED ? PRO_EMBED : PRO_LN;
+    if (e == hipSuccess) e = launch_proj_w4(proj, pro, a, g.batch, g.k, st);
+    hipError_t e2 = hipStreamSynchronize(st);
+    HIPRET(e);
+    HIPRET(e2);
+    return ER_OK;
 }
 
 // ---- the fused single-row MLP on caller-owned operands.  er_k_mlp_transpose makes the k-major copy the decode context keeps per

@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 
 #include "er_decode_plan.h"
+#include "er_w4_rule.h"
 #include "k_gemv.h"
 #include "k_gemv_mfma.h"
 
@@ -153,11 +154,54 @@ inline bool plan_w8_batched(const DecodePlan& p, const DecodeKnobs& k, Proj proj
     return proj != PROJ_HEAD && form_mfma(proj_form(p, k, true, proj, 0).form) && w8_streams_batched(proj, p.B, k.w8_batched);
 }
 
+// fp4 context (w4 = the streamed nibble copy of the same matrix, er_w4_map.h; WT = _Float16 and a.W = the fp16 copy of the dequantised
+// values): a row form of a projection that w4_streams() names runs the nibble kernel on w4 in the projection's OWN nibble shape - a wave
+// owns whole row quads, so the (waves x rows) of the fp16 form do not carry over:
+//     qkv  4 waves x 4 rows        = 288 workgroups for 4608 rows
+//     fc1  6 waves x 4 rows        = 256 workgroups for 6144 rows
+//     fc2  4 K-slices x 4 rows     = 384 workgroups for 1536 rows
+// (qkv with 6 waves and fc1 with 4 were measured too and lost: DESIGN.md section 4).  Both keep the four-wave prologue (gemv_kernel: PW),
+// so the LayerNorm'd input - and with fp16's lane -> element map, fmaf chain and butterfly every output - is the fp16 form's bit for
+// bit.  out_proj (the fused merge launch included), the lm_head, every batched form and the fused sparse MLP have no nibble form and run
+// the fp16 copy.
+// w4_has_row_form(proj) and w4_streams(proj, B, knob) - which projections of an fp4 context stream nibbles in their row forms at B rows -
+// are host-only code in er_w4_rule.h, so that tests/host/w4_map_check.cpp can enumerate them.
+
+// the nibble row form of `proj` on the streamed copy a.W; a.kv_half names the cache type
+static hipError_t launch_proj_w4(Proj proj, int pro, const GemvArgs& a, int B, int K, hipStream_t st) {
+    if (!w4_has_row_form(proj) || B < 1 || B > 4 || !w4map::shape_ok(a.N, K)) return hipErrorInvalidValue;
+    switch (proj) {
+        case PROJ_QKV:
+            if (a.kv_half == 2) {
+                if (pro == PRO_EMBED) return gemv_groups<w4_t, 1, 4, PRO_EMBED, EPI_QKV8, 4>(a, B, K, st);
+                return gemv_groups<w4_t, 1, 4, PRO_LN, EPI_QKV8, 4>(a, B, K, st);
+            }
+            if (a.kv_half != 1) return hipErrorInvalidValue;      // fp32 caches go with fp32 weights
+            if (pro == PRO_EMBED) return gemv_groups<w4_t, 1, 4, PRO_EMBED, EPI_QKV, 4>(a, B, K, st);
+            return gemv_groups<w4_t, 1, 4, PRO_LN, EPI_QKV, 4>(a, B, K, st);
+        case PROJ_FC1: return gemv_groups<w4_t, 1, 4, PRO_LN, EPI_RELU, 6>(a, B, K, st);
+        case PROJ_FC2: return gemv_groups<w4_t, 4, 4, PRO_NONE, EPI_RESID>(a, B, K, st);
+        default: break;
+    }
+    return hipErrorInvalidValue;
+}
+
+// fp4 context (on): the streamed copy of the projection's matrix - null while the copies do not match the loaded weights - and the
+// ER_W4_ROWS knob
+struct W4Io { bool on = false; const void* w = nullptr; int knob = -1; };
+
 template <typename WT>
-static hipError_t launch_proj(Proj proj, const ProjForm& f, int pro, const GemvArgs& a, int B, int K, SkPart sk, hipStream_t st, const void* w8 = nullptr) {
-    constexpr bool W8 = sizeof(WT) == 1, HALF = sizeof(WT) <= 2;
+static hipError_t launch_proj(Proj proj, const ProjForm& f, int pro, const GemvArgs& a, int B, int K, SkPart sk, hipStream_t st, const void* w8 = nullptr,
+                              const W4Io& w4 = W4Io{}) {
+    constexpr bool W8 = WTraits<WT>::E4M3, HALF = sizeof(WT) <= 2;
     if (W8 && proj == PROJ_HEAD) return hipErrorInvalidValue;      // the lm_head is not quantised
     if constexpr (sizeof(WT) == 2) {
+        if (w4.on && f.form == ER_FORM_ROW && w4_streams(proj, B, w4.knob)) {
+            if (!w4.w) return hipErrorInvalidValue;      // the plan streams nibbles and the copy is not there: an error, never the fp16 copy quietly
+            GemvArgs b = a;
+            b.W = w4.w;
+            return launch_proj_w4(proj, pro, b, B, K, st);
+        }
         if (w8 && f.form == ER_FORM_ROW && w8_streams(proj, B)) {
             GemvArgs b = a;
             b.W = w8;
@@ -276,6 +320,7 @@ struct ProjIo {
     void* out_image = nullptr;        // fc1, ER_FORM_MFMA_XT: the tiled image of the output
     const void* w8 = nullptr;         // fp8 context: the byte block of the same matrix (launch_proj decides who streams it)
     const void* w8_tiled = nullptr;   // fp8 context whose plan streams this projection's matrix-core form as bytes: the tiled byte copy (er_w8_tile_map.h)
+    W4Io w4;                          // fp4 context: the streamed nibble copy of the same matrix (launch_proj decides who streams it)
 };
 
 // (projection, form) -> launches: the prologue launch of a batched form, the operands the form reads, launch_proj.
@@ -291,7 +336,7 @@ static hipError_t run_proj(Proj proj, const ProjForm& f, const ProjIo& io, GemvA
     if (form_tiled_in(f.form)) a.xin = (const float*)io.x_image;
     if (f.form == ER_FORM_MFMA_XT && proj == PROJ_FC1) a.xt_out = io.out_image;
     if (bytes) return launch_proj<w8_t>(proj, f, io.pro, a, B, K, sk, st);
-    return launch_proj<WT>(proj, f, io.pro, a, B, K, sk, st, io.w8);
+    return launch_proj<WT>(proj, f, io.pro, a, B, K, sk, st, io.w8, io.w4);
 }
 
 }   // namespace er

@@ -12,6 +12,8 @@ struct WeightEntry {
     bool q8 = false;              // fp8 mode: quantised by row (er_w8.h) - a byte block [rows][cols] e4m3 + [rows] 2^e (WeightTable::q8_of,
     unsigned char** dstq = nullptr;   // k_gemv.h w8_scales), published here; the fp16 copy and the fp32 block then hold the dequantised values
     size_t qcols = 0;             // ... values per quantised row
+    bool q4 = false;              // fp4 mode: quantised by blocks of 32 along a row (er_w4.h) - the canonical block [rows][cols / 2] nibble bytes +
+    unsigned char** dstq4 = nullptr;  // [rows][cols / 32] e8m0 bytes (WeightTable::q4_of), published here; the fp16 copy and the fp32 block hold the dequantised values
     bool loaded = false;
 
     // [off, off + n) of a fused block of `total` elements (q / k / v of one layer)
@@ -20,6 +22,7 @@ struct WeightEntry {
     WeightEntry& pad(size_t kin, size_t kpad) { cols = kin; pitch = kpad; total = n / kin * kpad; return *this; }
     WeightEntry& half(_Float16** p = nullptr) { f16 = true; dst16 = p; return *this; }
     WeightEntry& rows8(unsigned char** q, size_t in) { q8 = true; dstq = q; qcols = in; return *this; }      // rows of `in` values ([out][in])
+    WeightEntry& blocks4(unsigned char** q, size_t in) { q4 = true; dstq4 = q; qcols = in; return *this; }   // ... the same rows, for fp4 mode
 };
 
 struct WeightTable {
@@ -27,10 +30,12 @@ struct WeightTable {
     std::map<const float*, _Float16*> half_of;   // fp32 block -> its fp16 copy (fp16 mode, entries with half())
     std::vector<DevBuf<char>> owned;             // every weight block (derived copies included); the entries and weight structs hold views
     std::map<const float*, unsigned char*> q8_of;   // fp32 block -> its byte block (fp8 mode, entries with rows8())
+    std::map<const float*, unsigned char*> q4_of;   // fp32 block -> its canonical MXFP4 block (fp4 mode, entries with blocks4())
     DevBuf<char> stage;                          // upload of one host tensor: grow-only, freed by weights_finalize
-    DevBuf<int> bad;                             // fp8 mode: the quantiser's "non-finite source value" flag
+    DevBuf<int> bad;                             // fp8 / fp4 mode: the quantiser's "non-finite source value" flag
     bool fp16 = false;
     bool w8 = false;                             // fp8 mode (implies fp16: every other tensor is stored as fast mode stores it)
+    bool w4 = false;                             // fp4 mode (implies fp16 in the same way)
 
     // a block of n T that lives as long as the table
     template <typename T>
@@ -114,6 +119,62 @@ __global__ __launch_bounds__(ER_WG) void quant_rows_kernel(const void* src, int 
     }
 }
 
+// Block-wise MXFP4 quantiser (er_w4.h): one workgroup per row of `cols` source values (a multiple of 32), four consecutive lanes per
+// block of 32 - a lane holds 8 consecutive elements, i.e. 4 nibble bytes.  Block maximum -> exponent e -> e2m1 codes, the e8m0 byte
+// e + 127, and the dequantised values q * 2^e as fp16 and fp32 (both exact).  Every output pointer is nullable; eout takes e itself
+// ([rows][cols / 32]).  A NaN or an infinity anywhere in the source raises *bad.  Rows are independent (quant_rows_kernel's remark).
+__global__ __launch_bounds__(ER_WG) void quant_blocks_kernel(const void* src, int dtype, size_t cols, float* dst32, _Float16* dst16,
+                                                            unsigned char* nib, unsigned char* scale, int* eout, int* bad) {
+    const size_t row = blockIdx.x, base = row * cols;
+    bool finite = true;
+    for (size_t g = threadIdx.x; g < cols / 8; g += ER_WG) {      // cols / 8 is a multiple of 4: the four lanes of a block run together
+        float v[8], amax = 0.f;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            v[i] = raw_to_f32(src, dtype, base + g * 8 + i);
+            const float a = fabsf(v[i]);
+            finite = finite && a <= 3.402823466e38f;      // false for NaN and infinity
+            amax = fmaxf(amax, a);
+        }
+        amax = fmaxf(amax, __shfl_xor(amax, 1, 64));
+        amax = fmaxf(amax, __shfl_xor(amax, 2, 64));
+        const int e = w4_block_exponent(amax);
+        const float up = w4_pow2(e), down = w4_pow2(-e);      // both exact powers of two
+        if ((g & 3) == 0) {
+            const size_t blk = row * (cols / W4_BLOCK) + g / 4;
+            if (scale) scale[blk] = w4_scale_byte(e);
+            if (eout) eout[blk] = e;
+        }
+        unsigned int packed = 0;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const unsigned char c = w4_encode(v[i] * down);
+            const float d = w4_decode(c) * up;
+            packed |= (unsigned int)c << (4 * i);      // element 2 b in the low nibble of byte b
+            if (dst16) dst16[base + g * 8 + i] = (_Float16)d;
+            if (dst32) dst32[base + g * 8 + i] = d;
+        }
+        if (nib) reinterpret_cast<unsigned int*>(nib)[(base + g * 8) / 8] = packed;
+    }
+    if (!finite) *bad = 1;
+}
+
+// The canonical block of a matrix [n][k] (nibble bytes, then scale bytes) into the copy the nibble kernels stream (er_w4_map.h): one
+// thread per nibble byte and per scale byte.  n a multiple of 4, k of 1536.
+__global__ __launch_bounds__(ER_WG) void w4_interleave_kernel(const unsigned char* canon, unsigned char* stream, long long n, int k) {
+    const long long nb = n * k / 2, ns = n * k / W4_BLOCK;
+    const unsigned char* scales = canon + nb;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < nb + ns; i += (long long)gridDim.x * blockDim.x) {
+        if (i < nb) {
+            const long long row = i / (k / 2), kk = (i - row * (k / 2)) * 2;      // the byte's even element
+            stream[w4map::byte_offset(w4map::where(row, kk), k)] = canon[i];
+        } else {
+            const long long b = i - nb, row = b / (k / W4_BLOCK), kk = (b - row * (k / W4_BLOCK)) * W4_BLOCK;
+            stream[w4map::scale_offset(w4map::where(row, kk), k)] = scales[b];
+        }
+    }
+}
+
 template <typename T>
 static int weights_alloc(WeightTable& t, T** p, size_t n) {   // once per block, zeroed
     if (*p) return 0;
@@ -167,6 +228,27 @@ static int weights_load(WeightTable& t, hipStream_t st, const char* who, const s
         HIPCHK(hipMemcpyAsync(&bad, t.bad.p, sizeof(int), hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
         if (bad) return fail(ER_ERR_INVALID, "%s(%s): the tensor holds a NaN or an infinity; fp8 rows are quantised from finite values only", who, key.c_str());
+        e.loaded = true;
+        return 0;
+    }
+    if (t.w4 && e.q4) {      // rows of e.qcols values: the canonical MXFP4 block, the fp16 and fp32 blocks get the dequantised values
+        const size_t qc = e.qcols;
+        if (!h || e.cols != e.pitch || !qc || qc % W4_BLOCK || e.n % qc || e.off % qc || e.total % qc) return fail(ER_ERR_INVALID, "%s(%s): not a block-quantised matrix", who, key.c_str());
+        unsigned char*& qb = t.q4_of[*e.dst];
+        const size_t rows = e.total / qc;
+        ERCHK(weights_alloc(t, &qb, w4_block_bytes(rows, qc)));
+        if (e.dstq4) *e.dstq4 = qb;
+        unsigned char* scales = const_cast<unsigned char*>(w4_scales(qb, rows, qc));
+        ERCHK(t.bad.ensure(1));
+        e.loaded = false;                 // until the new values are known to be finite: a refused reload leaves the key unloaded
+        HIPCHK(hipMemsetAsync(t.bad.p, 0, sizeof(int), st));
+        hipLaunchKernelGGL(quant_blocks_kernel, dim3((unsigned)(e.n / qc)), dim3(ER_WG), 0, st, src, dtype, qc, *e.dst + e.off, h, qb + e.off / 2,
+                           scales + e.off / W4_BLOCK, (int*)nullptr, t.bad.p);
+        HIPCHK(hipGetLastError());
+        int bad = 0;
+        HIPCHK(hipMemcpyAsync(&bad, t.bad.p, sizeof(int), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        if (bad) return fail(ER_ERR_INVALID, "%s(%s): the tensor holds a NaN or an infinity; fp4 blocks are quantised from finite values only", who, key.c_str());
         e.loaded = true;
         return 0;
     }

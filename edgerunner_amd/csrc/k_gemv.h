@@ -20,6 +20,8 @@
 // a workgroup split K and combine through LDS.
 #pragma once
 #include "er_common.h"
+#include "er_w4.h"
+#include "er_w4_map.h"
 #include "er_w8.h"
 
 namespace er {
@@ -97,9 +99,15 @@ __device__ __forceinline__ xt_h8 xt_pack(float x0, float x1, float x2, float x3)
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned char w8_t;
 template <typename WT> struct WTraits;
-template <> struct WTraits<float> { static constexpr int EPL = 4; typedef f32x4 Load; };
-template <> struct WTraits<_Float16> { static constexpr int EPL = 8; typedef f32x4 Load; };
-template <> struct WTraits<w8_t> { static constexpr int EPL = 8; typedef er_u32x2 Load; };
+// e2m1 nibbles with an e8m0 scale per block of 32 (fp4 mode, er_w4.h): a tag type - the kernels address the streamed copy of er_w4_map.h
+// by byte offsets, never as an array of w4_t.  The row kernel only; a wave owns whole row quads (RW a multiple of 4).
+struct w4_t { unsigned char pair; };
+// E4M3: one e4m3 byte per element and a power-of-two scale per row behind the matrix; NIBBLES: the quad-interleaved MXFP4 copy.  The
+// kernels ask these, not sizeof(WT): two storage types are one byte wide.
+template <> struct WTraits<float> { static constexpr int EPL = 4; typedef f32x4 Load; static constexpr bool E4M3 = false, NIBBLES = false; };
+template <> struct WTraits<_Float16> { static constexpr int EPL = 8; typedef f32x4 Load; static constexpr bool E4M3 = false, NIBBLES = false; };
+template <> struct WTraits<w8_t> { static constexpr int EPL = 8; typedef er_u32x2 Load; static constexpr bool E4M3 = true, NIBBLES = false; };
+template <> struct WTraits<w4_t> { static constexpr int EPL = 8; typedef er_u32x4 Load; static constexpr bool E4M3 = false, NIBBLES = true; };
 
 __host__ __device__ __forceinline__ size_t w8_block_bytes(size_t n, size_t k) { return n * k + n * sizeof(float); }      // n * k is a multiple of 4
 __host__ __device__ __forceinline__ const float* w8_scales(const void* w, long long n, long long k) {
@@ -131,6 +139,22 @@ __device__ __forceinline__ float dot_w8(const er_u32x2& wraw, const f32x4* x, fl
     s = fmaf(w67.x, x[1].z, s); s = fmaf(w67.y, x[1].w, s);
     return s;
 }
+
+// eight e2m1 nibbles of one row (dword d: element k in nibble k, er_w4.h) times the block's scale (the fp32 image of its e8m0 byte)
+// against two float4 of the input: v_cvt_scalef32_pk_f32_fp4 delivers q * 2^e exactly, so this is dot_w<_Float16>'s chain on the
+// dequantised values, element for element, and nothing is left to multiply after the reduction
+__device__ __forceinline__ float dot_w4(unsigned int d, float scale, const f32x4* x, float s) {
+    typedef float f32x2 __attribute__((ext_vector_type(2)));
+    const f32x2 w01 = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(d, scale, 0), w23 = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(d, scale, 1);
+    const f32x2 w45 = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(d, scale, 2), w67 = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(d, scale, 3);
+    s = fmaf(w01.x, x[0].x, s); s = fmaf(w01.y, x[0].y, s);
+    s = fmaf(w23.x, x[0].z, s); s = fmaf(w23.y, x[0].w, s);
+    s = fmaf(w45.x, x[1].x, s); s = fmaf(w45.y, x[1].y, s);
+    s = fmaf(w67.x, x[1].z, s); s = fmaf(w67.y, x[1].w, s);
+    return s;
+}
+// row `row` (0..3) of a lane's quad load and of its scale dword
+__device__ __forceinline__ float w4_lane_scale(unsigned int sc, int row) { return __uint_as_float(((sc >> (8 * row)) & 0xffu) << 23); }
 
 // bias / residual / cache position are fetched at kernel entry (EpiPre) and the destination ADDRESS is finished there too, so that
 // the epilogue after the reduction is one add and one store.  Left to the compiler, the tail of the qkv kernel re-read five kernel
@@ -225,7 +249,13 @@ __global__ __launch_bounds__(64 * NW) void gemv_kernel(const void* pW, const flo
     constexpr int TPB = 64 * NW;
     constexpr int EPL = WTraits<WT>::EPL, XV = EPL / 4, SL = 1536, J = SL / (64 * EPL);
     constexpr int K = KS * SL;
-    constexpr bool W8 = sizeof(WT) == 1;       // e4m3 bytes: the accumulator times wscale[n] after the reduction and the split-K combine, in front of the bias
+    constexpr bool W8 = WTraits<WT>::E4M3;     // e4m3 bytes: the accumulator times wscale[n] after the reduction and the split-K combine, in front of the bias
+    // e2m1 nibbles: the wave's RW rows are RW / 4 row quads of the streamed copy (er_w4_map.h); one 16-byte load carries a lane's 8
+    // elements of all four rows and one dword load their four block scales.  Everything else - prologue, lane -> element map, fmaf
+    // chain, butterfly, split-K combine, epilogue - is the fp16 kernel's
+    constexpr bool W4 = WTraits<WT>::NIBBLES;
+    constexpr int WR = W4 ? RW / 4 : RW;       // weight loads per (slice, load): one per row, or one per row quad
+    static_assert(!W4 || (RW % 4 == 0 && J == w4map::LOADS && SL == w4map::SLICE), "the nibble kernels own whole row quads");
     typedef typename WTraits<WT>::Load WLoad;
     // the prologue (LayerNorm / embedding) always runs on at most 4 waves with the 256-thread element mapping and reduction
     // order, so a 6-wave workgroup (768 qkv workgroups = 3 per CU) produces bit-identical inputs; waves 4 and 5 only take
@@ -287,17 +317,39 @@ __global__ __launch_bounds__(64 * NW) void gemv_kernel(const void* pW, const flo
             ws[0] = wscale[min(row0 + min(tid, RW * NB - 1) / NB, a.N - 1)];
         }
     }
+    unsigned int sc[W4 ? WR : 1][J];           // fp4 quads: the block scales of every load, small operands like the bias - requested in front of the weight stream
+    if constexpr (W4) {
+        const long long last_quad = a.N / 4 - 1;
+#pragma unroll
+        for (int q = 0; q < WR; ++q) {
+            const long long quad = min((long long)(row0 / 4 + q), last_quad);      // clamp: out-of-range quads are loaded but never stored
+#pragma unroll
+            for (int j = 0; j < J; ++j)
+                sc[q][j] = *reinterpret_cast<const unsigned int*>(reinterpret_cast<const char*>(a.W) + w4map::lane_scale_offset(w4map::unit(quad, K, slice, j), lane));
+        }
+    }
     // (Round 3 shipped, unmeasured, a variant that loaded PRO_NONE's input slice HERE, in front of the weight stream; measured in
     // round 4 it made fc2 SLOWER - 8.10 vs 7.97 us, profiles/r04_ab_b5b758c_and_om_rpw.log - the six extra 16-byte loads per lane delay
     // the first weight request of every wave by more than the L2 round trip they take off the tail.  The input is read in the main
     // loop again.)
-    WLoad w[RW][J];
+    WLoad w[WR][J];
+    if constexpr (W4) {
+        const long long last_quad = a.N / 4 - 1;
 #pragma unroll
-    for (int r = 0; r < RW; ++r) {
-        const int row = min(row0 + r, a.N - 1);            // clamp: out-of-range rows are loaded but never stored
-        const WLoad* wr = reinterpret_cast<const WLoad*>(reinterpret_cast<const WT*>(a.W) + (long long)row * K + slice * SL);
+        for (int q = 0; q < WR; ++q) {
+            const long long quad = min((long long)(row0 / 4 + q), last_quad);
 #pragma unroll
-        for (int j = 0; j < J; ++j) w[r][j] = __builtin_nontemporal_load(wr + j * 64 + lane);
+            for (int j = 0; j < J; ++j)
+                w[q][j] = __builtin_nontemporal_load(reinterpret_cast<const WLoad*>(reinterpret_cast<const char*>(a.W) + w4map::lane_offset(w4map::unit(quad, K, slice, j), lane)));
+        }
+    } else {
+#pragma unroll
+        for (int r = 0; r < RW; ++r) {
+            const int row = min(row0 + r, a.N - 1);            // clamp: out-of-range rows are loaded but never stored
+            const WLoad* wr = reinterpret_cast<const WLoad*>(reinterpret_cast<const WT*>(a.W) + (long long)row * K + slice * SL);
+#pragma unroll
+            for (int j = 0; j < J; ++j) w[r][j] = __builtin_nontemporal_load(wr + j * 64 + lane);
+        }
     }
     __builtin_amdgcn_sched_barrier(0);         // keep the whole stream issued before the prologue arithmetic
     if (KS == 1) {                             // destination addresses of the epilogue: behind the weight issue, long before the tail
@@ -380,7 +432,8 @@ __global__ __launch_bounds__(64 * NW) void gemv_kernel(const void* pW, const flo
             float s = 0.f;
 #pragma unroll
             for (int j = 0; j < J; ++j) {
-                if constexpr (W8) s = dot_w8(w[r][j], &xr[j * XV], s);
+                if constexpr (W4) s = dot_w4(w[r / 4][j][r % 4], w4_lane_scale(sc[r / 4][j], r % 4), &xr[j * XV], s);
+                else if constexpr (W8) s = dot_w8(w[r][j], &xr[j * XV], s);
                 else s = dot_w<WT>(w[r][j], &xr[j * XV], s);
             }
             acc[r][b] = wave_sum(s);

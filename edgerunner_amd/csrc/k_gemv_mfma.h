@@ -58,7 +58,7 @@ __device__ __forceinline__ f16x8 w8_piece_f16(unsigned lo, unsigned hi, float sc
 template <typename WT, int NBH, int EPI, bool SPLIT, bool XT = false, int NWV = GM_WAVES>
 __global__ __launch_bounds__(64 * NWV) void gemv_mfma_kernel(GemvArgs a, int nb_valid, int K, float* part) {
     static_assert(!XT || sizeof(WT) <= 2, "the tiled activation layout feeds the fp16 matrix cores");
-    constexpr bool W8 = sizeof(WT) == 1;             // e4m3 bytes, paired tiles
+    constexpr bool W8 = WTraits<WT>::E4M3;            // e4m3 bytes, paired tiles
     static_assert(NWV == 16 || (NWV == 4 && SPLIT), "4-wave workgroups only produce split-K partials");
     constexpr int GM_WAVES = NWV;               // shadows the namespace constant inside this kernel
     constexpr int EPL = WTraits<WT>::EPL;            // weights per 16-byte load: 4 (fp32) or 8 (fp16)
@@ -249,7 +249,7 @@ __global__ __launch_bounds__(64 * NWV) void gemv_mfma_kernel(GemvArgs a, int nb_
 // then row scales: k_gemv.h w8_scales), dst the tiled byte block of er_w8_tile_map.h (N padded to 32 rows, pad scales 1)
 template <typename WT>
 __global__ __launch_bounds__(ER_WG) void tile_weights_kernel(const WT* src, f32x4* dst, int N, int K) {
-    if constexpr (sizeof(WT) == 1) {
+    if constexpr (WTraits<WT>::E4M3) {
         const long long total = w8t_pieces(N, K), stride = (long long)gridDim.x * ER_WG, first = (long long)blockIdx.x * ER_WG + threadIdx.x;
         for (long long p = first; p < total; p += stride) {
             int n, k;
@@ -279,7 +279,7 @@ __global__ __launch_bounds__(ER_WG) void tile_weights_kernel(const WT* src, f32x
 }
 template <typename WT>
 inline size_t tiled_weight_bytes(int N, int K) {
-    if constexpr (sizeof(WT) == 1) return w8t_block_bytes(N, K);
+    if constexpr (WTraits<WT>::E4M3) return w8t_block_bytes(N, K);
     else return (size_t)((N + 15) / 16) * 16 * K * sizeof(WT);
 }
 

@@ -41,7 +41,7 @@ __global__ __launch_bounds__(OM_THREADS) void outproj_merge_kernel(const void* p
     OutMergeArgs a;
     a.W = pW; a.bias = pbias; a.resid = presid; a.part_o = ppart_o; a.part_ml = ppart_ml; a.out = pout; a.N = pN;
     constexpr int EPL = WTraits<WT>::EPL, XV = EPL / 4, K = 1536, J = K / (64 * EPL);
-    constexpr bool W8 = sizeof(WT) == 1;      // e4m3 bytes + row scales behind them (k_gemv.h w8_scales): the reduced sum times 2^e in front of the bias
+    constexpr bool W8 = WTraits<WT>::E4M3;     // e4m3 bytes + row scales behind them (k_gemv.h w8_scales): the reduced sum times 2^e in front of the bias
     typedef typename WTraits<WT>::Load WLoad;
     constexpr int C4 = D / 4;                 // float4 columns per head (24)
     static_assert(D == 96 && NCH <= 32 && C4 <= 32 && K == 16 * D, "two 96-wide heads per wave, 16 heads");

@@ -93,7 +93,7 @@ def _i32_dev(values, device, hi, what):
 
 
 def gemv_form(form, epilogue, w, B, *, x=None, bias=None, ln=None, embed=None, sk=None, resid=None, qkv=None, nw=4, rw=1, eps=1e-5,
-              n=None, k=None, w_half=None, return_xnorm=False, prep_xt=False, prep_xt_image=None, xt_out_image=None, w8=None):
+              n=None, k=None, w_half=None, return_xnorm=False, prep_xt=False, prep_xt_image=None, xt_out_image=None, w8=None, w4=None):
     """One decode projection in one of the forms the decode step launches it in (``er_k_gemv_form``; native.ER_FORM_* / ER_EPI_*).
     w [n, k] fp32 or fp16 (None with ER_FORM_PREP).  The prologue is chosen by what is given:
       ln=(ln_w, ln_b) with x [B, k]            LayerNorm rows
@@ -105,6 +105,8 @@ def gemv_form(form, epilogue, w, B, *, x=None, bias=None, ln=None, embed=None, s
     xt_out_image: the image the tiled fc1 writes (allocated zeroed when the form needs one).
     w8=(q uint8 [n, k], wscale fp32 [n]): the row form or a matrix-core form (ER_FORM_MFMA, _MFMA_XT, _NARROW, _NARROW_DEFER) on e4m3 bytes
     and row scales in place of w (``er_k_gemv_form_w8``; gemv_form_w8).
+    w4=(block uint8 [n * k / 2 + n * k / 32], n, k): the row form of qkv / fc1 / fc2 on a canonical MXFP4 block in place of w
+    (``er_k_gemv_form_w4``; gemv_form_w4); nw / rw still name the fp16 row form it stands in for.
     Returns a dict: y, xnorm, q, part (ER_FORM_NARROW_DEFER: [groups, k / 384 * 32 * n] raw block), prep_xt, xt_out - those the call produced."""
     lib = native.load_library()
     dev = (x if x is not None else (embed[0] if embed is not None else sk[0])).device
@@ -114,6 +116,10 @@ def gemv_form(form, epilogue, w, B, *, x=None, bias=None, ln=None, embed=None, s
     if w8 is not None:
         assert w is None and w8[0].dtype == torch.uint8 and w8[1].dtype == torch.float32 and w8[1].numel() == w8[0].shape[0]
         (n, k), w_half = w8[0].shape, True
+    if w4 is not None:
+        assert w is None and w8 is None and w4[0].dtype == torch.uint8 and w4[0].is_contiguous()
+        n, k, w_half = int(w4[1]), int(w4[2]), True
+        assert w4[0].numel() == n * k // 2 + n * k // 32
     a = native.ErKGemvFormArgs()
     keep = [w, x, bias, resid]
     a.w, a.bias, a.x, a.resid = (native.ptr(t).value for t in (w, bias, x, resid))
@@ -169,7 +175,9 @@ def gemv_form(form, epilogue, w, B, *, x=None, bias=None, ln=None, embed=None, s
     elif form != native.ER_FORM_PREP:
         out["y"] = torch.empty((B, n), dtype=torch.float32, device=dev)
         a.y = native.ptr(out["y"]).value
-    if w8 is not None:
+    if w4 is not None:
+        native.check(lib.er_k_gemv_form_w4(C.byref(a), native.ptr(w4[0]), _st()), "er_k_gemv_form_w4")
+    elif w8 is not None:
         native.check(lib.er_k_gemv_form_w8(C.byref(a), native.ptr(w8[0]), native.ptr(w8[1]), _st()), "er_k_gemv_form_w8")
     else:
         native.check(lib.er_k_gemv_form(C.byref(a), _st()), "er_k_gemv_form")
@@ -201,6 +209,44 @@ def w8_quantize(w, device=None):
     native.check(native.load_library().er_k_w8_quantize(native.ptr(w), _W8_SRC[w.dtype], 1 if w.is_cuda else 0, n, k, native.ptr(q), native.ptr(e),
                                                         native.ptr(w16), native.ptr(ws), _st()), "er_k_w8_quantize")
     return q, e, w16, ws
+
+
+def gemv_form_w4(form, epilogue, block, n, k, B, **kw):
+    """``gemv_form`` on the canonical MXFP4 block of a matrix [n, k] (uint8: n * k / 2 nibble bytes, then n * k / 32 e8m0 bytes;
+    ``w4_quantize``): the row forms of qkv, fc1 and fc2 only, n a multiple of 4 - everything else raises before any launch.
+    nw / rw name the fp16 row form the nibble kernel stands in for.  Bit-identical to ``gemv_form`` on the fp16 matrix of the dequantised
+    values."""
+    return gemv_form(form, epilogue, None, B, w4=(block, n, k), **kw)
+
+
+def w4_quantize(w, device=None):
+    """The fp4 weight loader's block quantiser on a matrix w [n, k] (fp32 / fp16 / bf16, host or device memory, k a multiple of 32;
+    ``er_k_w4_quantize``): returns (block uint8 = the canonical block, n * k / 2 nibble bytes then n * k / 32 e8m0 scale bytes,
+    e int32 [n, k / 32], w16 fp16 [n, k] = q * 2^e) on the device.  Raises on NaN / infinity."""
+    assert w.dim() == 2 and w.dtype in _W8_SRC and w.shape[1] % 32 == 0
+    w = w.contiguous()
+    dev = torch.device(device) if device is not None else (w.device if w.is_cuda else torch.device("cuda", torch.cuda.current_device()))
+    n, k = w.shape
+    block = torch.empty((n * k // 2 + n * k // 32,), dtype=torch.uint8, device=dev)
+    e = torch.empty((n, k // 32), dtype=torch.int32, device=dev)
+    w16 = torch.empty((n, k), dtype=torch.float16, device=dev)
+    native.check(native.load_library().er_k_w4_quantize(native.ptr(w), _W8_SRC[w.dtype], 1 if w.is_cuda else 0, n, k, native.ptr(block), native.ptr(e),
+                                                        native.ptr(w16), _st()), "er_k_w4_quantize")
+    return block, e, w16
+
+
+def w4_block_parts(block, n, k):
+    """(nibble bytes uint8 [n, k / 2], scale bytes uint8 [n, k / 32]) views of a canonical MXFP4 block."""
+    return block[: n * k // 2].view(n, k // 2), block[n * k // 2:].view(n, k // 32)
+
+
+def w4_cvt_probe(device=None):
+    """What the hardware's scaled fp4 conversion makes of every byte (``er_k_w4_cvt_probe``): fp32 [23, 256, 4, 2] - block exponent
+    -15 .. 7, byte value, byte select, (low nibble, high nibble)."""
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    out = torch.empty((23, 256, 4, 2), dtype=torch.float32, device=dev)
+    native.check(native.load_library().er_k_w4_cvt_probe(native.ptr(out), _st()), "er_k_w4_cvt_probe")
+    return out
 
 
 def mlp_transpose(w2):

@@ -129,8 +129,8 @@ class _DecoderModel:
         self.embd = _Embd(dec)
 
 
-_KV8_RULE = ("kv_precision='fp8' (the e4m3 KV cache) goes with precision 'fp16' or 'fp8' only: exact mode (fp32 weights) keeps an fp32 cache. "
-             "Use LMM(opt, device, precision='fp16', kv_precision='fp8'), or call .half() / .fp8() in module style.")
+_KV8_RULE = ("kv_precision='fp8' (the e4m3 KV cache) goes with the fp16-activation precisions 'mxfp4', 'fp16' or 'fp8' only: exact mode (fp32 weights) keeps an fp32 cache. "
+             "Use LMM(opt, device, precision='fp16', kv_precision='fp8'), or call .half() / .fp8() / .fp4() in module style.")
 
 
 class LMM:
@@ -138,16 +138,18 @@ class LMM:
         """precision: 'fp32' = exact mode (fp32 weights + KV; greedy ids bit-exact vs the CPU path), 'fp16' = fast mode
         (decoder matrices and KV cache stored in fp16 like the reference's ``model.half()`` GPU path, fp32 accumulate),
         'fp8' = fast mode on a checkpoint whose q / k / v / out_proj / fc1 / fc2 matrices are rounded to e4m3 times a power of two
-        per output row (csrc/er_w8.h; the single-row decode projections stream the bytes), or None = module style: fp32 until ``.half()`` is called, the native context being created on first use, so
+        per output row (csrc/er_w8.h; the single-row decode projections stream the bytes), 'mxfp4' = fp4 mode, fast mode on a checkpoint whose same six
+        matrices are rounded to MXFP4 - e2m1 values times a power of two per block of 32 elements along a row (csrc/er_w4.h; the
+        single-row qkv / fc1 / fc2 projections stream the nibbles where ``ER_W4_ROWS`` or the measured rule says so), or None = module style: fp32 until ``.half()`` is called, the native context being created on first use, so
         that the reference's ``LMM(opt)`` -> ``load_state_dict`` -> ``.half().eval().to(device)`` (infer.py:41-56)
         selects the fp16 context exactly as it selects fp16 storage there.
 
         kv_precision: None = the KV cache in the precision's own activation dtype (fp32 / fp16), 'fp8' = one e4m3 byte per cached
-        element without a scale (kv8 mode: half the cache bytes of fp16; head_dim 96).  The byte cache goes with 'fp16' or 'fp8'
+        element without a scale (kv8 mode: half the cache bytes of fp16; head_dim 96).  The byte cache goes with 'fp16', 'fp8' or 'mxfp4'
         weights only: with 'fp32', or in module style once ``.float()`` selects fp32, it raises ValueError."""
         self.opt = opt
-        if precision not in (None, "fp32", "fp16", "fp8"):
-            raise ValueError(precision)
+        if precision not in (None, "fp32", "fp16", "fp8", "mxfp4"):      # fp4 mode is spelled by its format: the bare "fp4" stays refused
+            raise ValueError(f"{precision!r}: 'fp32', 'fp16', 'fp8', 'mxfp4' (fp4 mode) or None" if precision == "fp4" else precision)
         if kv_precision not in (None, "fp8"):
             raise ValueError(f"kv_precision={kv_precision!r}: None (the cache follows precision) or 'fp8'")
         if kv_precision == "fp8" and precision == "fp32":
@@ -171,8 +173,9 @@ class LMM:
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise native.NativeError("this LMM only runs on a HIP device (cuda:N); there is no CPU fallback")
-        self._dtype = torch.float16 if precision in ("fp16", "fp8") else torch.float32      # activations' storage: the KV cache, the prefill's operands
+        self._dtype = torch.float16 if precision in ("fp16", "fp8", "mxfp4") else torch.float32      # activations' storage: the KV cache, the prefill's operands
         self._w8 = precision == "fp8"
+        self._w4 = precision == "mxfp4"
         self._dec: Optional[NativeShapeOPT] = None
         self._sources: List[tuple] = []        # (state_dict reference, strict) of every load_state_dict call, for re-creation
         self.training = False
@@ -185,7 +188,7 @@ class LMM:
     # -- native context ------------------------------------------------------------------------
     @property
     def precision(self) -> str:
-        return "fp8" if self._w8 else "fp16" if self._dtype == torch.float16 else "fp32"
+        return "mxfp4" if self._w4 else "fp8" if self._w8 else "fp16" if self._dtype == torch.float16 else "fp32"
 
     @property
     def kv_precision(self) -> Optional[str]:
@@ -198,7 +201,7 @@ class LMM:
         if self._released:
             raise native.NativeError("LMM: the checkpoint was released (release_checkpoint()) and the native context is gone; "
                                      "create a new LMM and load the checkpoint again")
-        dec = NativeShapeOPT(self.dims, self.opt, self.device, weight_dtype="fp8" if self._w8 else self._dtype,
+        dec = NativeShapeOPT(self.dims, self.opt, self.device, weight_dtype="fp4" if self._w4 else "fp8" if self._w8 else self._dtype,
                              kv_dtype="fp8" if self._kv8 else self._dtype)
         dec.model = _DecoderModel(dec)
         for sd, strict in self._sources:
@@ -239,18 +242,18 @@ class LMM:
         self._released = True
         return self
 
-    def _cast(self, dtype, w8: bool = False):
+    def _cast(self, dtype, w8: bool = False, w4: bool = False):
         if self._kv8 and dtype != torch.float16:
             raise ValueError(_KV8_RULE)
-        if dtype == self._dtype and w8 == self._w8:
+        if dtype == self._dtype and w8 == self._w8 and w4 == self._w4:
             return self
         if self._dec is not None and self._dec.direct_loads:
-            want = "fp8" if w8 else "fp16" if dtype == torch.float16 else "fp32"
+            want = "mxfp4" if w4 else "fp8" if w8 else "fp16" if dtype == torch.float16 else "fp32"
             raise native.NativeError(
-                f"LMM.{'fp8' if w8 else 'half' if dtype == torch.float16 else 'float'}(): this context's weights were streamed directly into "
+                f"LMM.{'fp4' if w4 else 'fp8' if w8 else 'half' if dtype == torch.float16 else 'float'}(): this context's weights were streamed directly into "
                 f"the {self.precision} native context (mesh_decoder.load_state_iter / load_state_dict); they cannot be "
                 f"re-stored. Create LMM(opt, device, precision='{want}') instead.")
-        self._dtype, self._w8 = dtype, w8
+        self._dtype, self._w8, self._w4 = dtype, w8, w4
         if self._dec is not None:            # rebuild lazily from the retained checkpoints in the new storage precision
             self._dec.close()
             self._dec = None
@@ -263,6 +266,11 @@ class LMM:
     def fp8(self):
         """Selects the fp8 context: fast mode with the decoder matrices of every layer stored as e4m3 bytes times 2^e per row."""
         return self._cast(torch.float16, w8=True)
+
+    def fp4(self):
+        """Selects the fp4 context: fast mode with the decoder matrices of every layer stored as MXFP4 (e2m1 nibbles, one e8m0 scale
+        byte per block of 32 along a row)."""
+        return self._cast(torch.float16, w4=True)
 
     def float(self):
         return self._cast(torch.float32)

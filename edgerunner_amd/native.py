@@ -16,7 +16,7 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 # does not exist fails as loudly as a missing default build
 LIB_PATH = os.environ.get("ER_LIB_PATH") or os.path.join(PKG, "libedgerunner_hip.so")
 
-ER_F32, ER_F16, ER_BF16, ER_F8E4M3 = 0, 1, 2, 3
+ER_F32, ER_F16, ER_BF16, ER_F8E4M3, ER_F4E2M1 = 0, 1, 2, 3, 4
 ER_COND_NONE, ER_COND_POINT, ER_COND_POINT_LATENT = 0, 1, 2
 ER_GREEDY, ER_SAMPLE = 0, 1
 ER_GRAMMAR_NONE, ER_GRAMMAR_NAIVE9, ER_GRAMMAR_LR_ABSCO = 0, 1, 2
@@ -39,6 +39,7 @@ EXPORTS = [
     "er_set_sampling", "er_get_logprobs", "er_queue_row_logprobs", "er_k_sample_head_ctl",
     "er_k_w8_quantize", "er_k_gemv_form_w8", "er_k_attn_outproj3_w8", "er_k_kv8_encode",
     "er_set_prefix_pass", "er_k_attn_shared_mfma", "er_ctx_w8_streams",
+    "er_ctx_w4_streams", "er_k_w4_quantize", "er_k_gemv_form_w4", "er_k_w4_cvt_probe",
 ]
 
 
@@ -175,6 +176,7 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.er_plan_decode.argtypes = [ci, ci, ci, ci, ci, C.POINTER(ErDecodePlan)]
     lib.er_ctx_plan.argtypes = [vp, C.POINTER(ErDecodePlan)]
     lib.er_ctx_w8_streams.argtypes = [vp, C.POINTER(C.c_int32)]
+    lib.er_ctx_w4_streams.argtypes = [vp, C.POINTER(C.c_int32)]
     lib.er_set_row_streams.argtypes = [vp, C.POINTER(C.c_uint32), ci]
     lib.er_set_prefix_groups.argtypes = [vp, C.POINTER(C.c_int32), ci, ci]
     lib.er_set_prefix_pass.argtypes = [vp, ci]
@@ -197,6 +199,9 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.er_k_attn_outproj3.argtypes = [vp, vp, vp, ci, vp, vp, vp, vp, ci, ci, ci, vp]
     lib.er_k_w8_quantize.argtypes = [vp, ci, ci, ci, ci, vp, vp, vp, vp, vp]
     lib.er_k_kv8_encode.argtypes = [vp, vp, C.c_longlong, vp]
+    lib.er_k_w4_quantize.argtypes = [vp, ci, ci, ci, ci, vp, vp, vp, vp]
+    lib.er_k_gemv_form_w4.argtypes = [C.POINTER(ErKGemvFormArgs), vp, vp]
+    lib.er_k_w4_cvt_probe.argtypes = [vp, vp]
     lib.er_k_gemv_form_w8.argtypes = [C.POINTER(ErKGemvFormArgs), vp, vp, vp]
     lib.er_k_attn_outproj3_w8.argtypes = [vp, vp, vp, ci, vp, vp, vp, vp, vp, ci, ci, vp]
     lib.er_k_gemm.argtypes = [vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, cf, vp]

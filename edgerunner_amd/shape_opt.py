@@ -22,7 +22,8 @@ from .weights import ModelDims
 
 _COND = {"none": native.ER_COND_NONE, "point": native.ER_COND_POINT, "point_latent": native.ER_COND_POINT_LATENT}
 # storage dtypes of a context; "fp8" (or torch.float8_e4m3fn) = e4m3 bytes times 2^e per row for the six decoder matrices of a layer
-_DT = {torch.float32: native.ER_F32, torch.float16: native.ER_F16, torch.bfloat16: native.ER_BF16, "fp8": native.ER_F8E4M3}
+# "fp4" = MXFP4 for the same matrices: e2m1 nibbles with an e8m0 scale byte per block of 32 along a row
+_DT = {torch.float32: native.ER_F32, torch.float16: native.ER_F16, torch.bfloat16: native.ER_BF16, "fp8": native.ER_F8E4M3, "fp4": native.ER_F4E2M1}
 if hasattr(torch, "float8_e4m3fn"):
     _DT[torch.float8_e4m3fn] = native.ER_F8E4M3
 
@@ -502,6 +503,13 @@ class NativeShapeOPT:
         qkv, out_proj, fc1 and fc2.  All zero in the other precisions."""
         out = (C.c_int32 * 4)()
         native.check(self.lib.er_ctx_w8_streams(self._ctx, out), "er_ctx_w8_streams")
+        return dict(zip(("qkv", "out_proj", "fc1", "fc2"), (int(v) for v in out)))
+
+    def w4_streams(self):
+        """fp4 mode: which projections the reserved shape's decode step streams as e2m1 nibbles (``er_ctx_w4_streams``): dict of 0 / 1 for
+        qkv, out_proj, fc1 and fc2.  All zero in the other precisions."""
+        out = (C.c_int32 * 4)()
+        native.check(self.lib.er_ctx_w4_streams(self._ctx, out), "er_ctx_w4_streams")
         return dict(zip(("qkv", "out_proj", "fc1", "fc2"), (int(v) for v in out)))
 
     def mlp_nnz(self):

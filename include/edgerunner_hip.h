@@ -51,9 +51,13 @@ typedef enum {
  * output row, csrc/er_w8.h; it computes what fast mode computes on a checkpoint rounded that way), and ER_F16 + ER_F8E4M3 and
  * ER_F8E4M3 + ER_F8E4M3 (kv8: fast or fp8 mode with the KV cache stored as one OCP e4m3fn byte per element and no scale -
  * saturating at +-448, round to nearest even, NaN kept, csrc/er_w8.h kv8_encode; head_dim 96 only; single rows decode with version 2,
- * every batched shape with ER_ATTN_STREAM, er_set_prefix_groups is ER_ERR_UNSUPPORTED).  Every other combination, ER_BF16
- * storage included, is rejected by er_create with ER_ERR_UNSUPPORTED.  ER_F8E4M3 is a storage mode only, never a checkpoint dtype. */
-typedef enum { ER_F32 = 0, ER_F16 = 1, ER_BF16 = 2, ER_F8E4M3 = 3 } er_dtype;
+ * every batched shape with ER_ATTN_STREAM, er_set_prefix_groups is ER_ERR_UNSUPPORTED).  ER_F4E2M1 + ER_F16 and ER_F4E2M1 + ER_F8E4M3
+ * are fp4 mode: fast mode (or kv8) with the same six matrices stored as OCP MXFP4 - e2m1 nibbles with one e8m0 scale byte per block of
+ * 32 elements along a row, csrc/er_w4.h; it computes what fast mode computes on a checkpoint rounded that way, and the single-row
+ * forms of qkv, fc1 and fc2 stream the nibbles where ER_W4_ROWS / the measured rule say so (er_ctx_w4_streams).  Every other
+ * combination, ER_BF16 storage and ER_F4E2M1 with an fp32 cache included, is rejected by er_create with ER_ERR_UNSUPPORTED.
+ * ER_F8E4M3 and ER_F4E2M1 are storage modes only, never checkpoint dtypes. */
+typedef enum { ER_F32 = 0, ER_F16 = 1, ER_BF16 = 2, ER_F8E4M3 = 3, ER_F4E2M1 = 4 } er_dtype;
 typedef enum { ER_COND_NONE = 0, ER_COND_POINT = 1, ER_COND_POINT_LATENT = 2 } er_cond_mode;
 typedef enum { ER_GREEDY = 0, ER_SAMPLE = 1 } er_gen_mode;
 /* prefix_allowed_tokens_fn variants LMM.generate can build (core/models.py:236-275) */
@@ -385,6 +389,10 @@ int er_ctx_plan(er_ctx* ctx, er_decode_plan* out);
  * matrix-core batched forms above that where the measured rule (or ER_W8_BATCHED=1 at er_create; 0 = nowhere above batch 4) says so.
  * All zero in every other mode.  er_decode_plan keeps its layout. */
 int er_ctx_w8_streams(er_ctx* ctx, int32_t out[4]);
+/* fp4 mode: which of qkv / out_proj / fc1 / fc2 (out[0..3]) the stored plan streams as e2m1 nibbles - row forms at batch <= 4 only, and
+ * only qkv, fc1 and fc2 have one.  ER_W4_ROWS at er_create: 0 = nowhere, 1 = every row form that has a nibble kernel, unset = the
+ * measured rule (csrc/er_decode_proj.h w4_streams).  All zero in every other mode. */
+int er_ctx_w4_streams(er_ctx* ctx, int32_t out[4]);
 /* tile shape launch_gemm* picks for an [m, n] output in `batch` slices: 1 = 128x128, 2 = 64x128, 3 = 64x64 (ER_GEMM_TILE forces) */
 int er_plan_gemm_tile(int m, int n, int batch);
 
@@ -531,6 +539,21 @@ int er_k_gemv_form_w8(const er_k_gemv_form_args* args, const void* q_dev, const 
 int er_k_attn_outproj3_w8(const float* q_dev, const void* k_dev, const void* v_dev, int len, const void* wo_q_dev,
                           const float* wo_scale_dev, const float* bo_dev, const float* resid_dev, float* y_dev, int l_cap,
                           int kv_half, void* stream);
+/* fp4 mode on caller-owned operands (csrc/er_w4.h).  er_k_w4_quantize: the weight loader's block quantiser on a matrix [n][k] (k a
+ * multiple of 32) of fp32 / fp16 / bf16 values in host (on_device = 0) or device memory - per block of 32 elements along a row e = the
+ * smallest integer with amax * 2^-e <= 6 in [-15, 7], codes q = e2m1(w * 2^-e) (saturating, round to nearest, ties to even), and the
+ * dequantised values q * 2^e as fp16.  The three outputs are device memory and nullable: block_dev = the canonical block, n * k / 2
+ * nibble bytes row-major (element 2 i in the low nibble of byte i) followed by n * k / 32 e8m0 bytes (e + 127) row-major; e_dev int32
+ * [n][k / 32]; w16_dev fp16 [n][k].  A NaN or an infinity in the source is ER_ERR_INVALID.
+ * er_k_gemv_form_w4: er_k_gemv_form on a canonical block in place of args->w (not read) - ER_FORM_ROW of qkv, fc1 and fc2 only, w_half
+ * set, args->nw / rw naming the fp16 row form the nibble kernel stands in for, n a multiple of 4, an fp16 or e4m3 cache for qkv; out_proj,
+ * the lm_head, every batched form and an fp32 cache are ER_ERR_UNSUPPORTED before any launch.  The entry interleaves the block itself
+ * (csrc/er_w4_map.h).  Bit-identical to er_k_gemv_form on the fp16 matrix q * 2^e.
+ * er_k_w4_cvt_probe: what the hardware's scaled conversion makes of every byte - out_dev fp32 [23][256][4][2]: exponent e = -15 .. 7,
+ * byte value, byte select 0 .. 3, (low nibble, high nibble).  All block. */
+int er_k_w4_quantize(const void* src, int dtype, int on_device, int n, int k, void* block_dev, int32_t* e_dev, void* w16_dev, void* stream);
+int er_k_gemv_form_w4(const er_k_gemv_form_args* args, const void* block_dev, void* stream);
+int er_k_w4_cvt_probe(float* out_dev, void* stream);
 /* The device encoder of the byte KV cache (kv8; csrc/er_w8.h kv8_encode, what the K/V producers store with) on n fp32 values in
  * device memory: dst_dev receives n e4m3fn bytes.  Blocks. */
 int er_k_kv8_encode(const float* src_dev, void* dst_dev, long long n, void* stream);

@@ -179,6 +179,8 @@ def main(argv=None):
         model = model.float().eval().to(device)
     elif os.environ.get("EDGERUNNER_PRECISION") == "fp8":
         model = model.fp8().eval().to(device)
+    elif os.environ.get("EDGERUNNER_PRECISION") in ("fp4", "mxfp4"):      # MXFP4 decoder matrices (e2m1 nibbles, one e8m0 scale per block of 32)
+        model = model.fp4().eval().to(device)
     else:
         model = model.half().eval().to(device)
     model.release_checkpoint()        # the weights are on the device in their final precision: drop the host copy (~2.7 GB per rank)

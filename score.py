@@ -9,7 +9,7 @@ dataset do (``edgerunner_amd.provider.mesh_item``), padded into batches of ``--b
 ``LMM.forward``.  Printed per mesh: loss_ce (mean NLL of the next token over its supervised positions), perplexity
 exp(loss_ce) and next-token accuracy (argmax == label) over the same positions; then the means over meshes (and
 ``loss_ce_tokens``, the mean over all supervised positions: LMM.forward's loss_ce when everything fits one batch).  Written:
-``{workspace}/scores.json``.  EDGERUNNER_PRECISION=fp32 selects the exact mode, fp8 the e4m3 row-scaled mode (default fp16, like infer.py).  No CPU fallback.
+``{workspace}/scores.json``.  EDGERUNNER_PRECISION=fp32 selects the exact mode, fp8 the e4m3 row-scaled mode, fp4 the MXFP4 block-scaled mode (default fp16, like infer.py).  No CPU fallback.
 """
 from __future__ import annotations
 
@@ -59,6 +59,8 @@ def main(argv=None):
         model = model.float().eval().to(device)
     elif os.environ.get("EDGERUNNER_PRECISION") == "fp8":      # what e4m3 rows cost THIS checkpoint: compare the loss with the fp16 run's
         model = model.fp8().eval().to(device)
+    elif os.environ.get("EDGERUNNER_PRECISION") in ("fp4", "mxfp4"):      # what MXFP4 blocks cost THIS checkpoint: compare the loss with the fp16 run's
+        model = model.fp4().eval().to(device)
     else:
         model = model.half().eval().to(device)
     model.release_checkpoint()

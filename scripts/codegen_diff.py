@@ -47,7 +47,9 @@ def main():
         scratch = sum(l.startswith("scratch_") for l in ins)
         print(f"  {n}: {len(ins)} instructions, vgpr {vg.group(1) if vg else '?'}, scratch accesses {scratch}, "
               f"v_cvt_pk_f32_fp8 {sum('v_cvt_pk_f32_fp8' in l for l in ins)}, ds_bpermute {sum('ds_bpermute' in l for l in ins)}, "
-              f"nt dwordx2 loads {sum(l.startswith('global_load_dwordx2') and l.endswith(' nt') for l in ins)}")
+              f"nt dwordx2 loads {sum(l.startswith('global_load_dwordx2') and l.endswith(' nt') for l in ins)}, "
+              f"v_cvt_scalef32_pk_f32_fp4 {sum('v_cvt_scalef32_pk_f32_fp4' in l for l in ins)}, "
+              f"nt dwordx4 loads {sum(l.startswith('global_load_dwordx4') and l.endswith(' nt') for l in ins)}")
     return 1 if (changed or missing) else 0
 
 
