@@ -81,6 +81,7 @@ struct LayerW {
     // make_w4_streams for the projections that have a nibble form)
     unsigned char *wqkv_q4 = nullptr, *wo_q4 = nullptr, *w1_q4 = nullptr, *w2_q4 = nullptr;
     void *wqkv_s4 = nullptr, *w1_s4 = nullptr, *w2_s4 = nullptr;
+    void *wqkv_t4 = nullptr, *wo_t4 = nullptr, *w1_t4 = nullptr, *w2_t4 = nullptr;   // fp4 mode: tiled NIBBLE copies (er_w4_tile_map.h) of the projections a plan streams as nibbles in its matrix-core forms
     void* w2_kt = nullptr;   // fc2.weight k-major, [intermediate][hidden] in the streamed weight type: the fused single-row MLP (k_mlp_sparse.h)
     float *wqkv = nullptr, *bqkv = nullptr;   // fused [3*hidden][hidden] in q,k,v order
     float *wo = nullptr, *bo = nullptr, *ln1w = nullptr, *ln1b = nullptr;
@@ -192,7 +193,7 @@ struct er_ctx {
     bool kv8 = false;        // kv8 mode: fast (or fp8), with the KV cache stored as e4m3 bytes without a scale (er_w8.h kv8_encode)
     int kv_type = 0;         // the cache type as the kernels' kv_half argument takes it: 0 = fp32, 1 = fp16, 2 = e4m3 bytes
     bool w8 = false;         // fp8 mode: fast, with the six decoder matrices per layer quantised by row; the row forms and (w8_streams_batched) the matrix-core forms of the step stream the bytes
-    bool w4 = false;         // fp4 mode: fast, with the six decoder matrices per layer quantised by blocks of 32 (MXFP4); the row forms w4_streams names stream the nibbles
+    bool w4 = false;         // fp4 mode: fast, with the six decoder matrices per layer quantised by blocks of 32 (MXFP4); the row forms w4_streams names and the matrix-core forms w4_streams_batched names stream the nibbles
     bool w4_valid = false;   // LayerW::*_s4 match the loaded weights
     float *proj_w = nullptr, *proj_b = nullptr, *normc_w = nullptr, *normc_b = nullptr;
     PointEnc pe;             // point encoder (cond_mode POINT)
@@ -204,8 +205,8 @@ struct er_ctx {
     bool have_hidden = false;     // ypre holds a valid last-position state
     DecodeKnobs knobs;        // environment of er_create
     er_sampling samp{1.0f, 1.0f, 0, 0, 0};   // er_set_sampling: sticky, kept across er_kv_reserve
-    bool tiled_valid = false; // LayerW::*_t / *_t8 match the loaded weights, as far as tiled_have says they exist
-    bool tiled_have[2][4] = {};   // [0]: the fp16 / fp32 tiled copy, [1]: the tiled byte copy of qkv / out_proj / fc1 / fc2 has been made (every layer)
+    bool tiled_valid = false; // LayerW::*_t / *_t8 / *_t4 match the loaded weights, as far as tiled_have says they exist
+    bool tiled_have[2][4] = {};   // [0]: the fp16 / fp32 tiled copy, [1]: the tiled byte (fp8 mode) or nibble (fp4 mode) copy of qkv / out_proj / fc1 / fc2 has been made (every layer)
     bool kmajor_valid = false; // LayerW::w2_kt match the loaded weights
     void* zero_row = nullptr;  // hidden zeros (fp32 size): what the fused MLP reads in place of a dead neuron's row
     int prof_len = 0;         // > 0: attention kernels run at this fixed length (er_profile_decode_kernels_at)
@@ -255,6 +256,7 @@ static DecodeKnobs read_knobs(bool fast) {
     k.prefix_pass = (pp && !strcmp(pp, "mfma")) ? ER_PREFIX_PASS_MFMA : ER_PREFIX_PASS_VALU;
     k.w8_batched = env_is("ER_W8_BATCHED", '0') ? 0 : env_is("ER_W8_BATCHED", '1') ? 1 : -1;
     k.w4_rows = env_is("ER_W4_ROWS", '0') ? 0 : env_is("ER_W4_ROWS", '1') ? 1 : -1;
+    k.w4_batched = env_is("ER_W4_BATCHED", '0') ? 0 : env_is("ER_W4_BATCHED", '1') ? 1 : -1;
     return k;
 }
 
@@ -407,6 +409,17 @@ extern "C" int er_finalize_weights(er_ctx* c) {
 
 // second copy of the qkv / fc1 / fc2 matrices in the layout the matrix-core batched kernels stream (made the first
 // time a batch > 4 is reserved: 2.5 GB fp32 / 1.3 GB fp16 of the 288 GB)
+// src: the row-major matrix, the byte block (w8_t) or the canonical MXFP4 block (w4_t: w4_tile_kernel)
+template <typename WT>
+static hipError_t launch_tile_weights(const void* src, void* dst, int N, int K, hipStream_t st) {
+    if constexpr (WTraits<WT>::NIBBLES) {
+        if (!w4t::shape_ok(N, K)) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(w4_tile_kernel, dim3(2048), dim3(ER_WG), 0, st, reinterpret_cast<const unsigned char*>(src), reinterpret_cast<unsigned int*>(dst), (long long)N, K);
+    } else {
+        hipLaunchKernelGGL((tile_weights_kernel<WT>), dim3(2048), dim3(ER_WG), 0, st, reinterpret_cast<const WT*>(src), reinterpret_cast<f32x4*>(dst), N, K);
+    }
+    return hipGetLastError();
+}
 template <typename WT>
 static int make_tiled(er_ctx* c, const void* src, void** dst, int N, int K) {
     if (!*dst) {
@@ -414,21 +427,20 @@ static int make_tiled(er_ctx* c, const void* src, void** dst, int N, int K) {
         ERCHK(c->w.alloc(&blk, tiled_weight_bytes<WT>(N, K)));
         *dst = blk;
     }
-    hipLaunchKernelGGL((tile_weights_kernel<WT>), dim3(2048), dim3(ER_WG), 0, c->own_stream, reinterpret_cast<const WT*>(src),
-                       reinterpret_cast<f32x4*>(*dst), N, K);
-    HIPCHK(hipGetLastError());
+    HIPCHK(launch_tile_weights<WT>(src, *dst, N, K, c->own_stream));
     return 0;
 }
 // fp8 mode: a projection that `plan` streams as bytes in its matrix-core form (plan_w8_batched) gets the tiled byte copy and NO fp16
 // tiled copy (1.36 GB at 24 layers when all four stream bytes); a later reserve whose plan needs the other copy makes it then.
+// fp4 mode: the same with plan_w4_batched and the tiled nibble copy (src: the canonical MXFP4 block).
 static int make_tiled_weights(er_ctx* c, const DecodePlan& plan) {
     if (weights_missing(c->w)) return 0;   // weights still loading: er_prefill comes back here
     const int H = c->cfg.hidden_dim, I = c->cfg.intermediate_dim;
     if (!c->tiled_valid) memset(c->tiled_have, 0, sizeof(c->tiled_have));
-    if (c->w8) {
+    if (c->w8 || c->w4) {
         bool made = false;
         for (int pj = 0; pj < 4; ++pj) {
-            const int bytes = plan_w8_batched(plan, c->knobs, (Proj)pj) ? 1 : 0;
+            const int bytes = (c->w4 ? plan_w4_batched(plan, c->knobs, (Proj)pj) : plan_w8_batched(plan, c->knobs, (Proj)pj)) ? 1 : 0;
             if (c->tiled_have[bytes][pj]) continue;
             const int N = pj == PROJ_QKV ? 3 * H : pj == PROJ_FC1 ? I : H, K = pj == PROJ_FC2 ? I : H;
             for (LayerW& L : c->layers) {
@@ -436,7 +448,10 @@ static int make_tiled_weights(er_ctx* c, const DecodePlan& plan) {
                 const void* src8[4] = {L.wqkv_q, L.wo_q, L.w1_q, L.w2_q};
                 void** dst16[4] = {&L.wqkv_t, &L.wo_t, &L.w1_t, &L.w2_t};
                 void** dst8[4] = {&L.wqkv_t8, &L.wo_t8, &L.w1_t8, &L.w2_t8};
-                if (bytes) ERCHK(make_tiled<w8_t>(c, src8[pj], dst8[pj], N, K));
+                const void* src4[4] = {L.wqkv_q4, L.wo_q4, L.w1_q4, L.w2_q4};
+                void** dst4[4] = {&L.wqkv_t4, &L.wo_t4, &L.w1_t4, &L.w2_t4};
+                if (bytes && c->w4) ERCHK(make_tiled<w4_t>(c, src4[pj], dst4[pj], N, K));
+                else if (bytes) ERCHK(make_tiled<w8_t>(c, src8[pj], dst8[pj], N, K));
                 else ERCHK(make_tiled<_Float16>(c, src16[pj], dst16[pj], N, K));
             }
             c->tiled_have[bytes][pj] = made = true;
@@ -570,6 +585,16 @@ extern "C" int er_ctx_w4_streams(er_ctx* c, int32_t out[4]) {
     DecodePlan q = p;
     if (c->kv->row_class) q.mlp_fused = false;      // a row class runs fc1 and fc2 as row GEMVs
     for (int pj = 0; pj < 4; ++pj) out[pj] = c->w4 && plan_w4_rows(q, c->knobs, (Proj)pj) ? 1 : 0;
+    return ER_OK;
+}
+
+// ... and as nibbles in their matrix-core batched forms (fp4 mode; all zero in every other mode, and for a plan that is not batched):
+// er_ctx_w4_streams keeps reporting the row forms only
+extern "C" int er_ctx_w4_streams_batched(er_ctx* c, int32_t out[4]) {
+    if (!c || !out) return fail(ER_ERR_INVALID, "er_ctx_w4_streams_batched: null argument");
+    const DecodePlan& p = c->kv->plan;
+    if (p.B <= 0) return fail(ER_ERR_INVALID, "er_ctx_w4_streams_batched: no cache reserved (call er_kv_reserve)");
+    for (int pj = 0; pj < 4; ++pj) out[pj] = c->w4 && p.batched && plan_w4_batched(p, c->knobs, (Proj)pj) ? 1 : 0;
     return ER_OK;
 }
 
@@ -719,6 +744,9 @@ static hipError_t launch_kind_t(er_ctx* c, int kind, int layer, hipStream_t st, 
     const SkPart sk{kv.skpart.p, kv.skpart.n};
     const auto form_of = [&](Proj proj, int l) { return proj_form(p, c->knobs, HALF, proj, l); };
     const auto bytes_of = [&](Proj proj, const void* t8) { return c->w8 && plan_w8_batched(p, c->knobs, proj) ? t8 : nullptr; };      // null t8 (copy not made): the launch fails
+    // fp4: the plan's word, and the tiled nibble copy only while it matches the loaded weights - a launch that wants a missing one fails (run_proj)
+    const auto nib_on = [&](Proj proj) { return c->w4 && p.batched && plan_w4_batched(p, c->knobs, proj); };
+    const auto nib_of = [&](Proj proj, const void* t4) { return nib_on(proj) && c->tiled_valid && c->tiled_have[1][proj] ? t4 : nullptr; };
     const bool v3 = p.v3 && !kv.row_class, fused = p.mlp_fused && !kv.row_class;
     GemvArgs a{};
     a.eps = g.ln_eps;
@@ -743,6 +771,7 @@ static hipError_t launch_kind_t(er_ctx* c, int kind, int layer, hipStream_t st, 
             if (c->w8) io.w8 = L.wqkv_q;
             if (c->w4) io.w4 = {true, c->w4_valid ? L.wqkv_s4 : nullptr, c->knobs.w4_rows};
             io.w8_tiled = bytes_of(PROJ_QKV, L.wqkv_t8);
+            io.w4_batched = nib_on(PROJ_QKV); io.w4_tiled = nib_of(PROJ_QKV, L.wqkv_t4);
             return run_proj<WT>(PROJ_QKV, form_of(PROJ_QKV, layer), io, a, B, H, sk, st);
         }
         // v2 holds a wave's whole K/V slice in flight (latency-bound single rows); with hundreds of workgroups per CU's
@@ -773,6 +802,7 @@ static hipError_t launch_kind_t(er_ctx* c, int kind, int layer, hipStream_t st, 
             io.w_tiled = L.wo_t; io.x_image = kv.xt_att.p;      // the streaming attention wrote the image (attn_args: out_xt)
             if (c->w8) io.w8 = L.wo_q;
             io.w8_tiled = bytes_of(PROJ_OUT, L.wo_t8);
+            io.w4_batched = nib_on(PROJ_OUT); io.w4_tiled = nib_of(PROJ_OUT, L.wo_t4);
             return run_proj<WT>(PROJ_OUT, form_of(PROJ_OUT, layer), io, a, B, H, sk, st);
         }
         case 4: {   // h1 = LN1(ypre1); f = relu(fc1 h1 + b)
@@ -790,6 +820,7 @@ static hipError_t launch_kind_t(er_ctx* c, int kind, int layer, hipStream_t st, 
             if (c->w8) io.w8 = L.w1_q;
             if (c->w4) io.w4 = {true, c->w4_valid ? L.w1_s4 : nullptr, c->knobs.w4_rows};
             io.w8_tiled = bytes_of(PROJ_FC1, L.w1_t8);
+            io.w4_batched = nib_on(PROJ_FC1); io.w4_tiled = nib_of(PROJ_FC1, L.w1_t4);
             return run_proj<WT>(PROJ_FC1, form_of(PROJ_FC1, layer), io, a, B, H, sk, st);
         }
         case 5: {   // ypre = fc2 f + b + h1
@@ -800,6 +831,7 @@ static hipError_t launch_kind_t(er_ctx* c, int kind, int layer, hipStream_t st, 
             if (c->w8) io.w8 = L.w2_q;
             if (c->w4) io.w4 = {true, c->w4_valid ? L.w2_s4 : nullptr, c->knobs.w4_rows};
             io.w8_tiled = bytes_of(PROJ_FC2, L.w2_t8);
+            io.w4_batched = nib_on(PROJ_FC2); io.w4_tiled = nib_of(PROJ_FC2, L.w2_t4);
             return run_proj<WT>(PROJ_FC2, form_of(PROJ_FC2, layer), io, a, B, I, sk, st);
         }
         case 6: {   // logits = lm_head LN2_last(ypre)
@@ -1825,9 +1857,13 @@ static int profile_impl(er_ctx* c, int repeats, int use_graph, float* avg_us, do
         bytes[4] -= less(PROJ_FC1, I, H);
         bytes[5] -= less(PROJ_FC2, H, I);
     }
-    if (c->w4) {   // the row forms that stream nibbles: half a byte per weight + a scale byte per 32 in place of 2 bytes per weight
-        const auto less = [&](Proj proj, double n, double k) { return plan_w4_rows(p, c->knobs, proj) ? n * k * (w - 0.5 - 1.0 / 32.0) : 0.0; };
+    if (c->w4) {   // the row and matrix-core forms that stream nibbles: half a byte per weight + a scale byte per 32 (the tiled copy: 4 bytes per 96) in place of 2 bytes per weight
+        const auto less = [&](Proj proj, double n, double k) {
+            if (p.batched) return plan_w4_batched(p, c->knobs, proj) ? n * k * w - (double)w4t::block_bytes((long long)n, (long long)k) : 0.0;
+            return plan_w4_rows(p, c->knobs, proj) ? n * k * (w - 0.5 - 1.0 / 32.0) : 0.0;
+        };
         bytes[0] -= less(PROJ_QKV, 3.0 * H, H);
+        bytes[3] -= less(PROJ_OUT, H, H);
         bytes[4] -= less(PROJ_FC1, I, H);
         bytes[5] -= less(PROJ_FC2, H, I);
     }
@@ -1933,8 +1969,7 @@ static int proj_entry(Proj proj, const ProjForm& f, ProjIo io, GemvArgs a, int B
             io.x_image = io.pro_image;
         }
         if (form_mfma(form)) {
-            hipLaunchKernelGGL((tile_weights_kernel<WT>), dim3(2048), dim3(ER_WG), 0, st, reinterpret_cast<const WT*>(a.W), reinterpret_cast<f32x4*>(wt.p), n, K);
-            e = hipGetLastError();
+            e = launch_tile_weights<WT>(a.W, wt.p, n, K, st);
             io.w_tiled = wt.p;
         }
     }
@@ -2288,16 +2323,25 @@ extern "C" int er_k_w4_cvt_probe(float* out_dev, void* stream) {
 
 // er_k_gemv_form's checks on a canonical MXFP4 block in place of args->w (not read): ER_FORM_ROW of qkv, fc1 and fc2 with fp16 or e4m3
 // caches.  args names the fp16 row form the step would launch (w_half, nw, rw: checked like er_k_gemv_form's); the nibble kernel runs in
-// the projection's own nibble shape (er_decode_proj.h launch_proj_w4).  Builds the interleaved copy itself.  Everything else is refused
-// before any launch.
+// the projection's own nibble shape (er_decode_proj.h launch_proj_w4).  Builds the interleaved copy itself.  Also the four matrix-core
+// forms (ER_FORM_MFMA, _MFMA_XT, _NARROW, _NARROW_DEFER) of qkv, out_proj, fc1 and fc2, through er_k_gemv_form's own path: proj_entry
+// builds the tiled nibble copy (er_w4_tile_map.h) and launches gemv_mfma_kernel<w4_t>.  Everything else - ER_FORM_VALU, ER_FORM_ROWS8,
+// the lm_head - is refused before any launch.
 extern "C" int er_k_gemv_form_w4(const er_k_gemv_form_args* f, const void* block_dev, void* stream) {
     if (!f || !block_dev) return fail(ER_ERR_INVALID, "er_k_gemv_form_w4: null argument");
     er_k_gemv_form_args g = *f;
     g.w = block_dev;
     if (!g.w_half) return fail(ER_ERR_UNSUPPORTED, "er_k_gemv_form_w4: the nibbles stand in for fp16 row forms (set w_half)");
-    if (g.form != ER_FORM_ROW) return fail(ER_ERR_UNSUPPORTED, "er_k_gemv_form_w4: only the row forms stream nibbles (form %d)", g.form);
+    if (g.form != ER_FORM_ROW && !form_mfma(g.form))
+        return fail(ER_ERR_UNSUPPORTED, "er_k_gemv_form_w4: only the row forms and the matrix-core forms stream nibbles (form %d)", g.form);
     Proj proj = PROJ_QKV;
     ERCHK(gemv_form_check(g, &proj));
+    if (form_mfma(g.form)) {
+        if (proj == PROJ_HEAD) return fail(ER_ERR_UNSUPPORTED, "er_k_gemv_form_w4: the lm_head has no nibble form");
+        if (!w4t::shape_ok(g.n, g.k)) return fail(ER_ERR_UNSUPPORTED, "er_k_gemv_form_w4: k %d must be a multiple of %d", g.k, w4t::KW);
+        if (proj == PROJ_QKV && !g.kv_half) return fail(ER_ERR_UNSUPPORTED, "er_k_gemv_form_w4: fp4 weights go with an fp16 or an e4m3 cache, not fp32");
+        return gemv_form_t<w4_t>(g, proj, (hipStream_t)stream);      // proj_entry tiles the block (w4_tile_kernel) and synchronises
+    }
     if (!w4_has_row_form(proj)) return fail(ER_ERR_UNSUPPORTED, "er_k_gemv_form_w4: %s has no nibble form", proj == PROJ_OUT ? "out_proj" : "the lm_head");
     if (!w4map::shape_ok(g.n, g.k)) return fail(ER_ERR_UNSUPPORTED, "er_k_gemv_form_w4: n %d must be a multiple of 4 (rows are streamed in quads)", g.n);
     if (proj == PROJ_QKV && !g.kv_half) return fail(ER_ERR_UNSUPPORTED, "er_k_gemv_form_w4: fp4 weights go with an fp16 or an e4m3 cache, not fp32");

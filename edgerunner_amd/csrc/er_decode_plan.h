@@ -31,6 +31,9 @@ struct DecodeKnobs {          // the environment knobs of the decode step, read 
     // fp4 mode, row forms (env ER_W4_ROWS): -1 = stream nibbles where the measured rule says so (er_decode_proj.h w4_streams), 0 = the
     // fp16 copies everywhere, 1 = nibbles in every row form that has one (qkv, fc1, fc2 at B <= 4)
     int w4_rows = -1;
+    // fp4 mode, matrix-core batched forms (env ER_W4_BATCHED): -1 = stream nibbles where the measured rule says so (er_w4_rule.h
+    // w4_streams_batched: all four at B > 4), 0 = the fp16 tiled copies everywhere, 1 = nibbles in every matrix-core form of qkv, out_proj, fc1 and fc2
+    int w4_batched = -1;
 };
 
 // the three switches er_kv_reserve reads for the shape it reserves (tests flip them between two reserves of one context)

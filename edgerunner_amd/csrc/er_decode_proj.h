@@ -162,10 +162,17 @@ inline bool plan_w8_batched(const DecodePlan& p, const DecodeKnobs& k, Proj proj
 //     fc2  4 K-slices x 4 rows     = 384 workgroups for 1536 rows
 // (qkv with 6 waves and fc1 with 4 were measured too and lost: DESIGN.md section 4).  Both keep the four-wave prologue (gemv_kernel: PW),
 // so the LayerNorm'd input - and with fp16's lane -> element map, fmaf chain and butterfly every output - is the fp16 form's bit for
-// bit.  out_proj (the fused merge launch included), the lm_head, every batched form and the fused sparse MLP have no nibble form and run
-// the fp16 copy.
-// w4_has_row_form(proj) and w4_streams(proj, B, knob) - which projections of an fp4 context stream nibbles in their row forms at B rows -
-// are host-only code in er_w4_rule.h, so that tests/host/w4_map_check.cpp can enumerate them.
+// bit.  A matrix-core form (ER_FORM_MFMA, _MFMA_XT, _NARROW, _NARROW_DEFER) of qkv, out_proj, fc1 or fc2 that w4_streams_batched() names
+// runs the same form of gemv_mfma_kernel<w4_t> on the tiled nibble copy (er_w4_tile_map.h; run_proj: io.w4_tiled).  The single-row
+// out_proj (the fused merge launch included), the lm_head, the VALU batched kernel, the eight-row out_proj and the fused sparse MLP have
+// no nibble form and run the fp16 copy.
+// w4_has_row_form(proj), w4_streams(proj, B, knob) - which projections of an fp4 context stream nibbles in their row forms at B rows -
+// and w4_streams_batched(proj, B, knob) - the same question for the matrix-core forms - are host-only code in er_w4_rule.h, so that
+// tests/host/w4_map_check.cpp and tests/host/w4_tile_check.cpp can enumerate them.
+// ... and for the stored plan of an fp4 context: does the step stream `proj` as nibbles in a matrix-core form?  (plan_w8_batched's remark.)
+inline bool plan_w4_batched(const DecodePlan& p, const DecodeKnobs& k, Proj proj) {
+    return proj != PROJ_HEAD && form_mfma(proj_form(p, k, true, proj, 0).form) && w4_streams_batched(proj, p.B, k.w4_batched);
+}
 
 // the nibble row form of `proj` on the streamed copy a.W; a.kv_half names the cache type
 static hipError_t launch_proj_w4(Proj proj, int pro, const GemvArgs& a, int B, int K, hipStream_t st) {
@@ -193,8 +200,10 @@ struct W4Io { bool on = false; const void* w = nullptr; int knob = -1; };
 template <typename WT>
 static hipError_t launch_proj(Proj proj, const ProjForm& f, int pro, const GemvArgs& a, int B, int K, SkPart sk, hipStream_t st, const void* w8 = nullptr,
                               const W4Io& w4 = W4Io{}) {
-    constexpr bool W8 = WTraits<WT>::E4M3, HALF = sizeof(WT) <= 2;
+    constexpr bool W4 = WTraits<WT>::NIBBLES, W8 = WTraits<WT>::E4M3 || W4, HALF = sizeof(WT) <= 2;      // W8: a packed type (bytes or nibbles) - matrix-core forms only among the batched ones
     if (W8 && proj == PROJ_HEAD) return hipErrorInvalidValue;      // the lm_head is not quantised
+    if (W4 && !form_mfma(f.form)) return hipErrorInvalidValue;     // the tiled nibble copy has the four matrix-core forms, nothing else (the row forms: launch_proj_w4)
+    if (W4 && proj == PROJ_QKV && a.kv_half == 0) return hipErrorInvalidValue;      // fp4 weights go with an fp16 or a byte cache
     if constexpr (sizeof(WT) == 2) {
         if (w4.on && f.form == ER_FORM_ROW && w4_streams(proj, B, w4.knob)) {
             if (!w4.w) return hipErrorInvalidValue;      // the plan streams nibbles and the copy is not there: an error, never the fp16 copy quietly
@@ -208,7 +217,7 @@ static hipError_t launch_proj(Proj proj, const ProjForm& f, int pro, const GemvA
             return launch_proj<w8_t>(proj, f, pro, b, B, K, sk, st);
         }
     }
-    switch (f.form) {
+    if constexpr (!W4) switch (f.form) {
         case ER_FORM_ROW:
             switch (proj) {
                 case PROJ_QKV:
@@ -320,15 +329,26 @@ struct ProjIo {
     void* out_image = nullptr;        // fc1, ER_FORM_MFMA_XT: the tiled image of the output
     const void* w8 = nullptr;         // fp8 context: the byte block of the same matrix (launch_proj decides who streams it)
     const void* w8_tiled = nullptr;   // fp8 context whose plan streams this projection's matrix-core form as bytes: the tiled byte copy (er_w8_tile_map.h)
+    bool w4_batched = false;          // fp4 context whose plan streams this projection's matrix-core form as nibbles ...
+    const void* w4_tiled = nullptr;   // ... and the tiled nibble copy (er_w4_tile_map.h); null while it does not match the loaded weights: the launch fails
     W4Io w4;                          // fp4 context: the streamed nibble copy of the same matrix (launch_proj decides who streams it)
 };
 
 // (projection, form) -> launches: the prologue launch of a batched form, the operands the form reads, launch_proj.
 template <typename WT>
 static hipError_t run_proj(Proj proj, const ProjForm& f, const ProjIo& io, GemvArgs a, int B, int K, SkPart sk, hipStream_t st) {
+    const bool nibbles = sizeof(WT) == 2 && form_mfma(f.form) && io.w4_batched;
+    // the plan streams nibbles and the copy is not there: an error in front of every launch, never the fp16 copy quietly
+    if (nibbles && (!io.w4_tiled || !w4t::shape_ok(a.N, K))) return hipErrorInvalidValue;
     if (io.pro != PRO_NONE && form_batched(f.form)) {
         const hipError_t e = launch_prologue(io.pro, a, B, io.rd, io.pro_image, st);
         if (e != hipSuccess) return e;
+    }
+    if (nibbles) {
+        a.W = io.w4_tiled;
+        if (form_tiled_in(f.form)) a.xin = (const float*)io.x_image;
+        if (f.form == ER_FORM_MFMA_XT && proj == PROJ_FC1) a.xt_out = io.out_image;
+        return launch_proj<w4_t>(proj, f, io.pro, a, B, K, sk, st);
     }
     const bool bytes = sizeof(WT) == 2 && form_mfma(f.form) && io.w8_tiled;
     if (form_mfma(f.form)) a.W = bytes ? io.w8_tiled : io.w_tiled;

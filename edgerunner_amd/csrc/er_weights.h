@@ -175,6 +175,27 @@ __global__ __launch_bounds__(ER_WG) void w4_interleave_kernel(const unsigned cha
     }
 }
 
+// The canonical block of a matrix [n][k] into the tiled copy the matrix-core batched forms stream (er_w4_tile_map.h): one thread per
+// dword of the copy - a lane's piece (eight consecutive elements of one row: one aligned dword of the canonical nibbles), or the three
+// scales of a row's blocks 3 s .. 3 s + 2 and the padding byte.  Rows n .. rows(n) - 1 are the padding: zero nibbles, scale byte 127.
+// k a multiple of 96.
+__global__ __launch_bounds__(ER_WG) void w4_tile_kernel(const unsigned char* canon, unsigned int* tiled, long long n, int k) {
+    const long long total = w4t::block_bytes(n, k) / 4;
+    const unsigned char* scales = canon + n * k / 2;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        const w4t::What w = w4t::what(k, i * 4);
+        unsigned int v = 0;
+        if (w.kind == w4t::WEIGHT) {
+            if (w.n < n) v = *reinterpret_cast<const unsigned int*>(canon + (w.n * k + w.k) / 2);
+        } else {      // the dword starts at a row's first scale of the unit: blocks w.k .. w.k + 2, then the padding byte
+            const unsigned char* s = scales + w.n * (k / W4_BLOCK) + w.k;
+            v = w.n < n ? (unsigned int)s[0] | (unsigned int)s[1] << 8 | (unsigned int)s[2] << 16
+                        : (unsigned int)w4t::PAD_SCALE * 0x010101u;
+        }
+        tiled[i] = v;
+    }
+}
+
 template <typename T>
 static int weights_alloc(WeightTable& t, T** p, size_t n) {   // once per block, zeroed
     if (*p) return 0;

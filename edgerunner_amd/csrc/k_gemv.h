@@ -100,7 +100,8 @@ typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned char w8_t;
 template <typename WT> struct WTraits;
 // e2m1 nibbles with an e8m0 scale per block of 32 (fp4 mode, er_w4.h): a tag type - the kernels address the streamed copy of er_w4_map.h
-// by byte offsets, never as an array of w4_t.  The row kernel only; a wave owns whole row quads (RW a multiple of 4).
+// by byte offsets, never as an array of w4_t.  In the row kernel a wave owns whole row quads (RW a multiple of 4); the matrix-core
+// batched kernel (k_gemv_mfma.h) streams the tiled copy of er_w4_tile_map.h under the same tag.
 struct w4_t { unsigned char pair; };
 // E4M3: one e4m3 byte per element and a power-of-two scale per row behind the matrix; NIBBLES: the quad-interleaved MXFP4 copy.  The
 // kernels ask these, not sizeof(WT): two storage types are one byte wide.

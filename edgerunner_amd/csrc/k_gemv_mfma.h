@@ -18,6 +18,7 @@
 // the other batch rows).  K = 6144 (fc2) is additionally split across workgroups (grid.y = 4); those partials go to
 // scratch and splitk_finish_kernel applies the epilogue.
 #pragma once
+#include "er_w4_tile_map.h"
 #include "er_w8_tile_map.h"
 #include "k_gemv.h"
 
@@ -44,6 +45,28 @@ __device__ __forceinline__ f16x8 w8_piece_f16(unsigned lo, unsigned hi, float sc
     return (f16x8){a[0], a[1], b[0], b[1], c[0], c[1], d[0], d[1]};
 }
 
+// The eight e2m1 nibbles of a piece (dword d: element k in nibble k, er_w4.h - byte i holds elements 2 i and 2 i + 1, low nibble first)
+// times the block's scale (the fp32 image of its e8m0 byte, w4_scale_f32) as the eight halves the fp16 tiled copy holds in that piece:
+// every q * 2^e is an fp16 number down to 2^-16 (er_w4.h).  W4_PIECE_VIA_F32 = 0: four v_cvt_scalef32_pk_f16_fp4, one per byte select;
+// = 1: four v_cvt_scalef32_pk_f32_fp4 (exact: tests/test_gpu_w4.py holds its table) and eight casts, each exact because the value is an
+// fp16 number.  tests/test_gpu_w4_batched.py holds the route that ships against the fp16 form for every code, exponent and nibble position.
+#ifndef W4_PIECE_VIA_F32
+#define W4_PIECE_VIA_F32 0
+#endif
+__device__ __forceinline__ f16x8 w4_piece_f16(unsigned d, float scale) {
+#if W4_PIECE_VIA_F32
+    typedef float f32x2 __attribute__((ext_vector_type(2)));
+    const f32x2 a = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(d, scale, 0), b = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(d, scale, 1);
+    const f32x2 c = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(d, scale, 2), e = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(d, scale, 3);
+    return (f16x8){(_Float16)a[0], (_Float16)a[1], (_Float16)b[0], (_Float16)b[1], (_Float16)c[0], (_Float16)c[1], (_Float16)e[0], (_Float16)e[1]};
+#else
+    typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+    const f16x2 a = __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(d, scale, 0), b = __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(d, scale, 1);
+    const f16x2 c = __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(d, scale, 2), e = __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(d, scale, 3);
+    return (f16x8){a[0], a[1], b[0], b[1], c[0], c[1], e[0], e[1]};
+#endif
+}
+
 // A workgroup = 16 waves = a 32-row tile (two 16-row A tiles per wave, sharing the X registers: X comes from L2 once
 // per 32 weight rows) x 16 K-slices of 96 = K-range 1536.  NBH = 16-row batch halves (1 or 2); SPLIT: raw partials.
 // XT (fast mode only): a.xin is the tiled hi | lo image of the input (k_gemv.h xt_entry) instead of row-major fp32 - same values, same
@@ -55,10 +78,17 @@ __device__ __forceinline__ f16x8 w8_piece_f16(unsigned lo, unsigned hi, float sc
 // both row tiles; the two row scales are loaded in front of everything else (loads retire in issue order, and the conversion is the
 // first consumer behind the weights), and w8_piece_f16 rebuilds in registers the f16x8 the fp16 copy holds for the same (lane, load) -
 // same slots, same MFMA sequence, same reduction and epilogues: bit-identical to the fp16 form on the dequantised matrix.
+// WT = w4_t (fp4 mode): the fp16 form on the TILED NIBBLE copy (er_w4_tile_map.h).  A wave's unit (32 rows x its 96-wide slice) is 1664
+// bytes: the lane requests its rows' six scale bytes (8 bytes, shared by the four kq lanes of a row) first, then X, then a 16-byte and an
+// 8-byte nibble load - the pieces of steps 0, 1 and of step 2, both row tiles - and w4_piece_f16 rebuilds the f16x8 of the fp16 copy for
+// the same (lane, step, row tile).  A step is one scale block of 32.  Bit-identical to the fp16 form on the dequantised matrix.
+// hipcc -save-temps, gfx950: the 40 w4_t instantiations take 50 - 58 VGPRs with one batch half and 78 - 86 with two (w8_t: 52 - 64 and
+// 84 - 92, fp16: 62 - 70 and 90 - 98), the fp16 forms' LDS, no scratch, 24 conversions each (6 pieces x 4) and every load above the first MFMA.
 template <typename WT, int NBH, int EPI, bool SPLIT, bool XT = false, int NWV = GM_WAVES>
 __global__ __launch_bounds__(64 * NWV) void gemv_mfma_kernel(GemvArgs a, int nb_valid, int K, float* part) {
     static_assert(!XT || sizeof(WT) <= 2, "the tiled activation layout feeds the fp16 matrix cores");
     constexpr bool W8 = WTraits<WT>::E4M3;            // e4m3 bytes, paired tiles
+    constexpr bool W4 = WTraits<WT>::NIBBLES;         // e2m1 nibbles + block scales, one unit per (row tile pair, wave slice)
     static_assert(NWV == 16 || (NWV == 4 && SPLIT), "4-wave workgroups only produce split-K partials");
     constexpr int GM_WAVES = NWV;               // shadows the namespace constant inside this kernel
     constexpr int EPL = WTraits<WT>::EPL;            // weights per 16-byte load: 4 (fp32) or 8 (fp16)
@@ -79,6 +109,13 @@ __global__ __launch_bounds__(64 * NWV) void gemv_mfma_kernel(GemvArgs a, int nb_
 #pragma unroll
         for (int t = 0; t < GM_R2; ++t) wsc[t] = sc[16 * t];
     }
+    // fp4: this wave's unit; blockIdx.x < rows(N) / 32 and the slice index < K / 96, so every offset is inside the block
+    const char* w4u = nullptr;
+    er_u32x2 w4s = {0u, 0u};            // [row tile]: the scale bytes of steps 0, 1, 2 (and a padding byte)
+    if constexpr (W4) {
+        w4u = reinterpret_cast<const char*>(a.W);
+        w4s = *reinterpret_cast<const er_u32x2*>(w4u + w4t::lane_scale_offset(w4t::unit(K, blockIdx.x, blockIdx.y * GM_WAVES + wid), lane));
+    }
     f32x4 x[NBH][NLD][XV];
 #pragma unroll
     for (int h = 0; h < NBH; ++h) {
@@ -97,21 +134,31 @@ __global__ __launch_bounds__(64 * NWV) void gemv_mfma_kernel(GemvArgs a, int nb_
                 for (int u = 0; u < XV; ++u) x[h][c][u] = *reinterpret_cast<const f32x4*>(xp + c * 4 * EPL + 4 * u);
         }
     }
-    constexpr int NWT = W8 ? 1 : GM_R2;              // weight loads per step: the byte copy pairs the two row tiles in one piece
+    constexpr int NWT = (W8 || W4) ? 1 : GM_R2;      // weight loads per step: the byte copy pairs the two row tiles in one piece
+    constexpr int NWL = W4 ? 2 : NWT * NLD;          // weight loads per lane
+    er_u32x4 w4a = {0u, 0u, 0u, 0u};    // fp4: pieces (step 0, t 0), (0, 1), (1, 0), (1, 1)
+    er_u32x2 w4b = {0u, 0u};            //      pieces (step 2, t 0), (2, 1)
     f32x4 w[NWT][NLD];
     const f32x4* wp[NWT];
     const int KT = K / (4 * EPL), kt0 = (blockIdx.y * GM_WAVES + wid) * NLD, NT = (a.N + 15) / 16;
-    if constexpr (W8) {
+    if constexpr (W4) {
+        const long long u = w4t::unit(K, blockIdx.x, blockIdx.y * GM_WAVES + wid);
+        w4a = __builtin_nontemporal_load(reinterpret_cast<const er_u32x4*>(w4u + w4t::lane_a_offset(u, lane)));
+        w4b = __builtin_nontemporal_load(reinterpret_cast<const er_u32x2*>(w4u + w4t::lane_b_offset(u, lane)));
+        wp[0] = nullptr;
+    } else if constexpr (W8) {
         wp[0] = reinterpret_cast<const f32x4*>(a.W) + w8t_piece(K, blockIdx.x, kt0, lane);
     } else {
 #pragma unroll
         for (int t = 0; t < GM_R2; ++t)     // tile (nt, kt) starts at piece (nt*KT + kt)*64; this lane's piece is number `lane`
             wp[t] = reinterpret_cast<const f32x4*>(a.W) + ((long long)min(n0 / 16 + t, NT - 1) * KT + kt0) * 64 + lane;
     }
+    if constexpr (!W4) {
 #pragma unroll
-    for (int c = 0; c < NLD; ++c)
+        for (int c = 0; c < NLD; ++c)
 #pragma unroll
-        for (int t = 0; t < NWT; ++t) w[t][c] = __builtin_nontemporal_load(wp[t] + c * 64);
+            for (int t = 0; t < NWT; ++t) w[t][c] = __builtin_nontemporal_load(wp[t] + c * 64);
+    }
     // (weights issued in front of X measured equal at B = 16 / 32: profiles/r05_ab_gm_wfirst.log)
     // the output this thread finishes: slot = tid >> 8 = (row tile t, batch half h), lane image ol, register orr
     //   n = n0 + 16*t + 4*(ol >> 4) + orr,  b = 16*h + (ol & 15)
@@ -128,7 +175,7 @@ __global__ __launch_bounds__(64 * NWV) void gemv_mfma_kernel(GemvArgs a, int nb_
     // registers, and a wave then has a few hundred bytes in flight instead of its whole slice
     __builtin_amdgcn_sched_barrier(0);
     ER_TPG(1);                          // every load issued
-    ER_TPG_WAIT(NWT * NLD);           // probe only: the input image has landed (the weight loads are the youngest NWT * NLD)
+    ER_TPG_WAIT(NWL);                 // probe only: the input image has landed (the weight loads are the youngest NWL)
     ER_TPG(2);
     ER_TPG_WAIT(0);                     // probe only: the weights have landed
     ER_TPG(3);
@@ -170,7 +217,10 @@ __global__ __launch_bounds__(64 * NWV) void gemv_mfma_kernel(GemvArgs a, int nb_
 #pragma unroll
             for (int t = 0; t < GM_R2; ++t) {
                 f16x8 av;
-                if constexpr (W8) {
+                if constexpr (W4) {
+                    const unsigned d = c < 2 ? w4a[2 * c + t] : w4b[t];
+                    av = w4_piece_f16(d, w4_lane_scale(w4s[t], c));
+                } else if constexpr (W8) {
                     const er_u32x4 wb = __builtin_bit_cast(er_u32x4, w[0][c]);
                     av = t == 0 ? w8_piece_f16(wb.x, wb.y, wsc[0]) : w8_piece_f16(wb.z, wb.w, wsc[1]);
                 } else {
@@ -279,7 +329,8 @@ __global__ __launch_bounds__(ER_WG) void tile_weights_kernel(const WT* src, f32x
 }
 template <typename WT>
 inline size_t tiled_weight_bytes(int N, int K) {
-    if constexpr (WTraits<WT>::E4M3) return w8t_block_bytes(N, K);
+    if constexpr (WTraits<WT>::NIBBLES) return (size_t)w4t::block_bytes(N, K);      // made by w4_tile_kernel (er_weights.h), not by tile_weights_kernel
+    else if constexpr (WTraits<WT>::E4M3) return w8t_block_bytes(N, K);
     else return (size_t)((N + 15) / 16) * 16 * K * sizeof(WT);
 }
 

@@ -105,8 +105,9 @@ def gemv_form(form, epilogue, w, B, *, x=None, bias=None, ln=None, embed=None, s
     xt_out_image: the image the tiled fc1 writes (allocated zeroed when the form needs one).
     w8=(q uint8 [n, k], wscale fp32 [n]): the row form or a matrix-core form (ER_FORM_MFMA, _MFMA_XT, _NARROW, _NARROW_DEFER) on e4m3 bytes
     and row scales in place of w (``er_k_gemv_form_w8``; gemv_form_w8).
-    w4=(block uint8 [n * k / 2 + n * k / 32], n, k): the row form of qkv / fc1 / fc2 on a canonical MXFP4 block in place of w
-    (``er_k_gemv_form_w4``; gemv_form_w4); nw / rw still name the fp16 row form it stands in for.
+    w4=(block uint8 [n * k / 2 + n * k / 32], n, k): the row form of qkv / fc1 / fc2, or a matrix-core form (ER_FORM_MFMA, _MFMA_XT, _NARROW,
+    _NARROW_DEFER) of qkv / out_proj / fc1 / fc2, on a canonical MXFP4 block in place of w (``er_k_gemv_form_w4``; gemv_form_w4); nw / rw
+    still name the fp16 row form a row launch stands in for.
     Returns a dict: y, xnorm, q, part (ER_FORM_NARROW_DEFER: [groups, k / 384 * 32 * n] raw block), prep_xt, xt_out - those the call produced."""
     lib = native.load_library()
     dev = (x if x is not None else (embed[0] if embed is not None else sk[0])).device
@@ -213,9 +214,10 @@ def w8_quantize(w, device=None):
 
 def gemv_form_w4(form, epilogue, block, n, k, B, **kw):
     """``gemv_form`` on the canonical MXFP4 block of a matrix [n, k] (uint8: n * k / 2 nibble bytes, then n * k / 32 e8m0 bytes;
-    ``w4_quantize``): the row forms of qkv, fc1 and fc2 only, n a multiple of 4 - everything else raises before any launch.
-    nw / rw name the fp16 row form the nibble kernel stands in for.  Bit-identical to ``gemv_form`` on the fp16 matrix of the dequantised
-    values."""
+    ``w4_quantize``): the row forms of qkv, fc1 and fc2 (n a multiple of 4; nw / rw name the fp16 row form the nibble kernel stands in
+    for) and the four matrix-core batched forms of qkv, out_proj, fc1 and fc2 (any n; x, ``prep_xt``, ``xt_out_image`` and the deferred
+    finish's ``part`` as for ``gemv_form_w8``) - ER_FORM_VALU, ER_FORM_ROWS8, the lm_head and an fp32 cache raise before any launch.
+    Bit-identical to ``gemv_form`` on the fp16 matrix of the dequantised values."""
     return gemv_form(form, epilogue, None, B, w4=(block, n, k), **kw)
 
 

@@ -39,7 +39,7 @@ EXPORTS = [
     "er_set_sampling", "er_get_logprobs", "er_queue_row_logprobs", "er_k_sample_head_ctl",
     "er_k_w8_quantize", "er_k_gemv_form_w8", "er_k_attn_outproj3_w8", "er_k_kv8_encode",
     "er_set_prefix_pass", "er_k_attn_shared_mfma", "er_ctx_w8_streams",
-    "er_ctx_w4_streams", "er_k_w4_quantize", "er_k_gemv_form_w4", "er_k_w4_cvt_probe",
+    "er_ctx_w4_streams", "er_ctx_w4_streams_batched", "er_k_w4_quantize", "er_k_gemv_form_w4", "er_k_w4_cvt_probe",
 ]
 
 
@@ -177,6 +177,7 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.er_ctx_plan.argtypes = [vp, C.POINTER(ErDecodePlan)]
     lib.er_ctx_w8_streams.argtypes = [vp, C.POINTER(C.c_int32)]
     lib.er_ctx_w4_streams.argtypes = [vp, C.POINTER(C.c_int32)]
+    lib.er_ctx_w4_streams_batched.argtypes = [vp, C.POINTER(C.c_int32)]
     lib.er_set_row_streams.argtypes = [vp, C.POINTER(C.c_uint32), ci]
     lib.er_set_prefix_groups.argtypes = [vp, C.POINTER(C.c_int32), ci, ci]
     lib.er_set_prefix_pass.argtypes = [vp, ci]

@@ -512,6 +512,14 @@ class NativeShapeOPT:
         native.check(self.lib.er_ctx_w4_streams(self._ctx, out), "er_ctx_w4_streams")
         return dict(zip(("qkv", "out_proj", "fc1", "fc2"), (int(v) for v in out)))
 
+    def w4_streams_batched(self):
+        """fp4 mode: which projections the reserved shape's batched decode step (batch > 4) streams as e2m1 nibbles in their matrix-core
+        forms (``er_ctx_w4_streams_batched``; ``ER_W4_BATCHED`` at creation: 0 / 1 / unset = the measured rule): dict of 0 / 1 for qkv,
+        out_proj, fc1 and fc2.  All zero in the other precisions and for single-row shapes; ``w4_streams`` reports the row forms only."""
+        out = (C.c_int32 * 4)()
+        native.check(self.lib.er_ctx_w4_streams_batched(self._ctx, out), "er_ctx_w4_streams_batched")
+        return dict(zip(("qkv", "out_proj", "fc1", "fc2"), (int(v) for v in out)))
+
     def mlp_nnz(self):
         """Live fc1 neurons per (layer, workgroup) that the fused single-row MLP counted in the last decode step (``er_mlp_nnz``):
         int32 [num_layers, 256], each 0 .. 24.  Raises unless the reserved shape runs the fused MLP (one row, ``ER_MLP_V`` on)."""

@@ -54,7 +54,8 @@ typedef enum {
  * every batched shape with ER_ATTN_STREAM, er_set_prefix_groups is ER_ERR_UNSUPPORTED).  ER_F4E2M1 + ER_F16 and ER_F4E2M1 + ER_F8E4M3
  * are fp4 mode: fast mode (or kv8) with the same six matrices stored as OCP MXFP4 - e2m1 nibbles with one e8m0 scale byte per block of
  * 32 elements along a row, csrc/er_w4.h; it computes what fast mode computes on a checkpoint rounded that way, and the single-row
- * forms of qkv, fc1 and fc2 stream the nibbles where ER_W4_ROWS / the measured rule say so (er_ctx_w4_streams).  Every other
+ * forms of qkv, fc1 and fc2 stream the nibbles where ER_W4_ROWS / the measured rule say so (er_ctx_w4_streams), the matrix-core
+ * batched forms of qkv, out_proj, fc1 and fc2 where ER_W4_BATCHED / the measured rule say so (er_ctx_w4_streams_batched).  Every other
  * combination, ER_BF16 storage and ER_F4E2M1 with an fp32 cache included, is rejected by er_create with ER_ERR_UNSUPPORTED.
  * ER_F8E4M3 and ER_F4E2M1 are storage modes only, never checkpoint dtypes. */
 typedef enum { ER_F32 = 0, ER_F16 = 1, ER_BF16 = 2, ER_F8E4M3 = 3, ER_F4E2M1 = 4 } er_dtype;
@@ -393,6 +394,11 @@ int er_ctx_w8_streams(er_ctx* ctx, int32_t out[4]);
  * only qkv, fc1 and fc2 have one.  ER_W4_ROWS at er_create: 0 = nowhere, 1 = every row form that has a nibble kernel, unset = the
  * measured rule (csrc/er_decode_proj.h w4_streams).  All zero in every other mode. */
 int er_ctx_w4_streams(er_ctx* ctx, int32_t out[4]);
+/* fp4 mode: which of qkv / out_proj / fc1 / fc2 (out[0..3]) the stored plan streams as e2m1 nibbles in their matrix-core batched forms
+ * (batch > 4; a tiled nibble copy, csrc/er_w4_tile_map.h, in place of the fp16 tiled copy).  ER_W4_BATCHED at er_create: 0 = nowhere,
+ * 1 = every matrix-core form of the four, unset = the measured rule (csrc/er_w4_rule.h w4_streams_batched).  All zero in every other
+ * mode and for a plan that is not batched; er_ctx_w4_streams keeps reporting the row forms only. */
+int er_ctx_w4_streams_batched(er_ctx* ctx, int32_t out[4]);
 /* tile shape launch_gemm* picks for an [m, n] output in `batch` slices: 1 = 128x128, 2 = 64x128, 3 = 64x64 (ER_GEMM_TILE forces) */
 int er_plan_gemm_tile(int m, int n, int batch);
 
@@ -545,10 +551,12 @@ int er_k_attn_outproj3_w8(const float* q_dev, const void* k_dev, const void* v_d
  * dequantised values q * 2^e as fp16.  The three outputs are device memory and nullable: block_dev = the canonical block, n * k / 2
  * nibble bytes row-major (element 2 i in the low nibble of byte i) followed by n * k / 32 e8m0 bytes (e + 127) row-major; e_dev int32
  * [n][k / 32]; w16_dev fp16 [n][k].  A NaN or an infinity in the source is ER_ERR_INVALID.
- * er_k_gemv_form_w4: er_k_gemv_form on a canonical block in place of args->w (not read) - ER_FORM_ROW of qkv, fc1 and fc2 only, w_half
- * set, args->nw / rw naming the fp16 row form the nibble kernel stands in for, n a multiple of 4, an fp16 or e4m3 cache for qkv; out_proj,
- * the lm_head, every batched form and an fp32 cache are ER_ERR_UNSUPPORTED before any launch.  The entry interleaves the block itself
- * (csrc/er_w4_map.h).  Bit-identical to er_k_gemv_form on the fp16 matrix q * 2^e.
+ * er_k_gemv_form_w4: er_k_gemv_form on a canonical block in place of args->w (not read), w_half set, an fp16 or e4m3 cache for qkv.
+ * ER_FORM_ROW of qkv, fc1 and fc2: args->nw / rw name the fp16 row form the nibble kernel stands in for, n a multiple of 4; the entry
+ * interleaves the block itself (csrc/er_w4_map.h).  ER_FORM_MFMA, _MFMA_XT, _NARROW and _NARROW_DEFER of qkv, out_proj, fc1 and fc2, with
+ * the operands er_k_gemv_form takes for them: the entry tiles the block itself (csrc/er_w4_tile_map.h; any n, padded to 32 rows).  The
+ * row form of out_proj, the lm_head, ER_FORM_VALU, ER_FORM_ROWS8 and an fp32 cache are ER_ERR_UNSUPPORTED before any launch.
+ * Bit-identical to er_k_gemv_form on the fp16 matrix q * 2^e.
  * er_k_w4_cvt_probe: what the hardware's scaled conversion makes of every byte - out_dev fp32 [23][256][4][2]: exponent e = -15 .. 7,
  * byte value, byte select 0 .. 3, (low nibble, high nibble).  All block. */
 int er_k_w4_quantize(const void* src, int dtype, int on_device, int n, int k, void* block_dev, int32_t* e_dev, void* w16_dev, void* stream);

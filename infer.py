@@ -179,7 +179,7 @@ def main(argv=None):
         model = model.float().eval().to(device)
     elif os.environ.get("EDGERUNNER_PRECISION") == "fp8":
         model = model.fp8().eval().to(device)
-    elif os.environ.get("EDGERUNNER_PRECISION") in ("fp4", "mxfp4"):      # MXFP4 decoder matrices (e2m1 nibbles, one e8m0 scale per block of 32)
+    elif os.environ.get("EDGERUNNER_PRECISION") in ("fp4", "mxfp4"):      # MXFP4 decoder matrices (e2m1 nibbles, one e8m0 scale per block of 32); ER_W4_ROWS / ER_W4_BATCHED = 0 / 1 force the nibble kernels of the single-row / batched step off / on
         model = model.fp4().eval().to(device)
     else:
         model = model.half().eval().to(device)
