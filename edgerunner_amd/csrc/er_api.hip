@@ -21,6 +21,7 @@
 #include "k_attn_decode.h"
 #include "k_attn_shared.h"
 #include "k_attn_shared_mfma.h"
+#include "k_kv_fork.h"
 #include "k_outproj_merge.h"
 #include "k_flash_attn_f16s.h"
 #include "k_gemm.h"
@@ -1132,11 +1133,13 @@ static hipError_t linear_tail(const float* A, const float* W, const float* bias,
 // Size checks of a full forward over B x S positions (er_prefill, er_score), before anything is launched.  The prefill kernels index
 // their [B * S][width] scratch rows with 32-bit products up to B * S * max(intermediate_dim, 3 * hidden_dim) (fc1's output is the widest):
 // such a product must stay below 2^31 (B = 8 at S = 43 011 and intermediate_dim 6144 is 2.11e9 - the edge).
-static int forward_check(er_ctx* c, const char* who, const float* embeds, int B, int S) {
+// reserved >= 0 (er_prefill_fork): the pass runs B rows of a cache reserved for `reserved`.
+static int forward_check(er_ctx* c, const char* who, const float* embeds, int B, int S, int reserved = -1) {
     if (!c || !embeds || B <= 0 || S <= 0) return fail(ER_ERR_INVALID, "%s: bad argument", who);
     if (c->q.active) return fail(ER_ERR_INVALID, "%s: a queue is open on this context (er_queue_end first)", who);
     ERCHK(er_finalize_weights(c));
-    if (c->kv->plan.B != B) return fail(ER_ERR_INVALID, "%s: batch %d but KV cache reserved for %d (call er_kv_reserve)", who, B, c->kv->plan.B);
+    if (reserved < 0) reserved = B;
+    if (c->kv->plan.B != reserved) return fail(ER_ERR_INVALID, "%s: batch %d but KV cache reserved for %d (call er_kv_reserve)", who, reserved, c->kv->plan.B);
     if (S >= c->kv->plan.Lcap) return fail(ER_ERR_CAPACITY, "prefix length %d does not fit the reserved KV cache (%d)", S, c->kv->plan.Lcap);
     const long long width = std::max({(long long)c->cfg.intermediate_dim, 3LL * c->cfg.hidden_dim, (long long)c->cfg.vocab_size});
     if ((long long)B * S * width > 0x7fffffffLL)
@@ -1289,6 +1292,81 @@ extern "C" int er_prefill(er_ctx* c, const float* embeds, int B, int S, void* st
     c->kv->row_class = false;                  // er_feed / er_logits after this prefill run the plan's own kinds; er_decode chooses again
     ERCHK(prefill_run(c, embeds, B, S, pick(c, stream)));
     return c->kv->prefix_len ? prefix_groups_check(c, pick(c, stream)) : ER_OK;
+}
+
+// ------------------------------------------------------------------------------------ forked prefill
+// What a fork launch needs of its arguments, before anything is launched: rows inside the batch, no destination that is also a source or
+// named twice, len inside the cache, a slab of whole 16-byte pieces at 16-byte aligned bases.
+static int kv_fork_check(const char* who, const void* kc, const void* vc, int esz, int layers, int B, int H, int Lcap, int D,
+                         const int32_t* src, const int32_t* dst, int n_pairs, int len) {
+    if (!kc || !vc || !src || !dst || layers < 1 || B < 1 || H < 1 || Lcap < 1 || D < 1 || n_pairs < 1) return fail(ER_ERR_INVALID, "%s: bad argument", who);
+    if (esz != 1 && esz != 2 && esz != 4) return fail(ER_ERR_INVALID, "%s: element size %d is not 1, 2 or 4", who, esz);
+    if (len < 1 || len > Lcap) return fail(ER_ERR_INVALID, "%s: len %d outside [1, %d]", who, len, Lcap);
+    if (((long long)len * D * esz) % 16 || ((long long)Lcap * D * esz) % 16 || ((uintptr_t)kc | (uintptr_t)vc) % 16)
+        return fail(ER_ERR_INVALID, "%s: a head's first %d positions (%lld bytes of %lld) are not whole 16-byte pieces at a 16-byte aligned base", who, len,
+                    (long long)len * D * esz, (long long)Lcap * D * esz);
+    std::vector<char> is_src((size_t)B, 0), is_dst((size_t)B, 0);
+    for (int i = 0; i < n_pairs; ++i) {
+        if (src[i] < 0 || src[i] >= B || dst[i] < 0 || dst[i] >= B) return fail(ER_ERR_INVALID, "%s: pair %d (%d -> %d) outside the %d rows", who, i, src[i], dst[i], B);
+        is_src[(size_t)src[i]] = 1;
+    }
+    for (int i = 0; i < n_pairs; ++i) {
+        if (is_src[(size_t)dst[i]]) return fail(ER_ERR_INVALID, "%s: row %d is a destination and a source", who, dst[i]);
+        if (is_dst[(size_t)dst[i]]) return fail(ER_ERR_INVALID, "%s: row %d is a destination twice", who, dst[i]);
+        is_dst[(size_t)dst[i]] = 1;
+    }
+    return ER_OK;
+}
+
+static KvForkArgs kv_fork_args(void* kc, void* vc, int esz, int B, int H, int Lcap, int D, int len) {
+    KvForkArgs a{};
+    a.kc = (char*)kc; a.vc = (char*)vc;
+    a.head_bytes = (long long)Lcap * D * esz; a.row_bytes = a.head_bytes * H; a.layer_bytes = a.row_bytes * B;
+    a.slab_vecs = (long long)len * D * esz / 16;
+    return a;
+}
+
+// The launch on caller-owned caches.  It does not block and allocates nothing (the table travels in the kernel arguments), so it can be
+// captured in a graph.
+extern "C" int er_k_kv_fork(void* kc, void* vc, int esz, int layers, int B, int H, int Lcap, int D, const int32_t* src, const int32_t* dst,
+                            int n_pairs, int len, void* stream) {
+    ERCHK(kv_fork_check("er_k_kv_fork", kc, vc, esz, layers, B, H, Lcap, D, src, dst, n_pairs, len));
+    HIPRET(launch_kv_fork(kv_fork_args(kc, vc, esz, B, H, Lcap, D, len), H, layers, src, dst, n_pairs, (hipStream_t)stream));
+    return ER_OK;
+}
+
+// er_prefill for a batch whose rows [n_leaders, n) repeat rows [0, n_leaders): the forward pass runs over the leaders alone, every follower
+// receives its leader's K/V [0, S) (kv_fork_kernel) and ypre row, and the generation state of all n rows starts at position S.  With prefix
+// groups set to the same table prefix_groups_check is NOT run: it compares a follower's [0, P) with its leader's, which here are the
+// bytes kv_fork_kernel has just copied from there.
+extern "C" int er_prefill_fork(er_ctx* c, const float* embeds, int n_leaders, int S, const int32_t* leader, int n, void* stream) {
+    if (!c || !leader || n <= 0) return fail(ER_ERR_INVALID, "er_prefill_fork: bad argument");
+    ERCHK(forward_check(c, "er_prefill_fork", embeds, n_leaders, S, n));
+    if (n_leaders > n) return fail(ER_ERR_INVALID, "er_prefill_fork: %d leaders for a batch of %d rows", n_leaders, n);
+    for (int b = 0; b < n; ++b)
+        if (b < n_leaders ? leader[b] != b : (leader[b] < 0 || leader[b] >= n_leaders))
+            return fail(ER_ERR_INVALID, "er_prefill_fork: leader[%d] = %d (leaders first: leader[b] == b below %d, a row below %d behind them)", b, leader[b], n_leaders, n_leaders);
+    KvMem& kv = *c->kv;
+    if (kv.prefix_len > S) return fail(ER_ERR_INVALID, "er_prefill_fork: %d positions but the prefix groups share %d", S, kv.prefix_len);
+    if (kv.prefix_len && !std::equal(kv.grp_leader.begin(), kv.grp_leader.end(), leader))
+        return fail(ER_ERR_INVALID, "er_prefill_fork: prefix groups are set with another leader table (set the groups from the table of the fork)");
+    const DecodePlan& p = kv.plan;
+    std::vector<int32_t> src, dst;
+    for (int b = n_leaders; b < n; ++b) { src.push_back(leader[b]); dst.push_back(b); }
+    if (!src.empty()) ERCHK(kv_fork_check("er_prefill_fork", kv.kc.p, kv.vc.p, c->kv_esz, p.layers, n, c->cfg.num_heads, p.Lcap, c->D, src.data(), dst.data(), (int)src.size(), S));
+    kv.row_class = false;                      // as er_prefill
+    hipStream_t st = pick(c, stream);
+    ERCHK(prefill_run(c, embeds, n_leaders, S, st));
+    if (src.empty()) return ER_OK;
+    c->have_hidden = false;                    // until the followers hold their state
+    HIPRET(launch_kv_fork(kv_fork_args(kv.kc.p, kv.vc.p, c->kv_esz, n, c->cfg.num_heads, p.Lcap, c->D, S), c->cfg.num_heads, p.layers, src.data(), dst.data(), (int)src.size(), st));
+    const size_t H = (size_t)c->cfg.hidden_dim;
+    for (int b = n_leaders; b < n; ++b)
+        HIPCHK(hipMemcpyAsync(kv.ypre.p + (size_t)b * H, kv.ypre.p + (size_t)leader[b] * H, H * 4, hipMemcpyDeviceToDevice, st));
+    hipLaunchKernelGGL(init_state_kernel, dim3((n + 63) / 64), dim3(64), 0, st, kv.st, n, S);
+    HIPRET(hipGetLastError());
+    c->have_hidden = true;
+    return ER_OK;
 }
 
 // ------------------------------------------------------------------------------------ prefix groups
@@ -1614,11 +1692,12 @@ __global__ void queue_park_kernel(GenState st, int* budget, int row0, int n) {
     budget[b] = 0;
 }
 // The generation state of rows [row0, row0 + n) right after their prefill of S positions (init_state_kernel for a row range), with the
-// rows' Philox stream ids and budgets from stage = {ids[n], budgets[n]}.
-__global__ void queue_admit_kernel(GenState st, unsigned int* row_stream, int* budget, const int* stage, int row0, int n, int S) {
+// rows' Philox stream ids and budgets from stage = {ids[n], budgets[n]}.  rows != nullptr (er_queue_admit_copy): row rows[i] in place of
+// row0 + i.
+__global__ void queue_admit_kernel(GenState st, unsigned int* row_stream, int* budget, const int* stage, int row0, int n, int S, const int* rows) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const int b = row0 + i;
+    const int b = rows ? rows[i] : row0 + i;
     st.tok[b] = 0; st.pos[b] = S; st.counter[b] = 0; st.ngen[b] = 0;
     st.unfinished[b] = 1; st.eos_step[b] = -1; st.base_pos[b] = S;
     row_stream[b] = (unsigned int)stage[i];
@@ -1698,7 +1777,7 @@ extern "C" int er_queue_admit(er_ctx* c, int row0, int n_rows, const float* embe
     HIPCHK(hipEventRecord(c->ev0, st));
     ERCHK(prefill_run(c, embeds, n_rows, S, st, row0, true));
     hipLaunchKernelGGL(queue_admit_kernel, dim3((n_rows + 63) / 64), dim3(64), 0, st, c->kv->st, c->kv->d_row_stream.p,
-                       c->kv->d_row_budget.p, c->q_stage.p, row0, n_rows, S);
+                       c->kv->d_row_budget.p, c->q_stage.p, row0, n_rows, S, (const int*)nullptr);
     HIPRET(hipGetLastError());
     HIPCHK(hipEventRecord(c->ev1, st));
     HIPCHK(hipStreamSynchronize(st));         // `stage` and the caller's arrays are host memory
@@ -1706,6 +1785,42 @@ extern "C" int er_queue_admit(er_ctx* c, int row0, int n_rows, const float* embe
     HIPCHK(hipEventElapsedTime(&ms, c->ev0, c->ev1));
     c->q.stats.prefill_ms += ms;
     c->q.admit(row0, n_rows, S, max_new);
+    return ER_OK;
+}
+
+extern "C" int er_queue_admit_copy(er_ctx* c, int src_row, const int32_t* dst_rows, int n, const uint32_t* stream_ids, const int32_t* max_new,
+                                   void* stream) {
+    ERCHK(queue_open(c, "er_queue_admit_copy"));
+    const int rc = c->q.check_admit_copy(src_row, dst_rows, n, max_new);
+    if (rc < 0) return fail(rc, "%s", c->q.why);
+    KvMem& kv = *c->kv;
+    const DecodePlan& p = kv.plan;
+    const int S = c->q.rows[(size_t)src_row].S, NH = c->cfg.num_heads;
+    std::vector<int32_t> src((size_t)n, src_row);
+    ERCHK(kv_fork_check("er_queue_admit_copy", kv.kc.p, kv.vc.p, c->kv_esz, p.layers, p.B, NH, p.Lcap, c->D, src.data(), dst_rows, n, S));
+    hipStream_t st = pick(c, stream);
+    std::vector<int> stage((size_t)3 * n);      // ids | budgets | rows
+    for (int i = 0; i < n; ++i) {
+        stage[(size_t)i] = (int)(stream_ids ? stream_ids[i] : (uint32_t)dst_rows[i]);
+        stage[(size_t)n + i] = c->q.budget_of(max_new, i);
+        stage[(size_t)2 * n + i] = dst_rows[i];
+    }
+    ERCHK(c->q_stage.ensure(stage.size()));
+    HIPCHK(hipMemcpyAsync(c->q_stage.p, stage.data(), stage.size() * sizeof(int), hipMemcpyHostToDevice, st));
+    HIPCHK(hipEventRecord(c->ev0, st));
+    HIPRET(launch_kv_fork(kv_fork_args(kv.kc.p, kv.vc.p, c->kv_esz, p.B, NH, p.Lcap, c->D, S), NH, p.layers, src.data(), dst_rows, n, st));
+    const size_t H = (size_t)c->cfg.hidden_dim;
+    for (int i = 0; i < n; ++i)
+        HIPCHK(hipMemcpyAsync(kv.ypre.p + (size_t)dst_rows[i] * H, kv.ypre.p + (size_t)src_row * H, H * 4, hipMemcpyDeviceToDevice, st));
+    hipLaunchKernelGGL(queue_admit_kernel, dim3((n + 63) / 64), dim3(64), 0, st, kv.st, kv.d_row_stream.p, kv.d_row_budget.p, c->q_stage.p, 0, n, S,
+                       (const int*)(c->q_stage.p + 2 * n));
+    HIPRET(hipGetLastError());
+    HIPCHK(hipEventRecord(c->ev1, st));
+    HIPCHK(hipStreamSynchronize(st));         // `stage` and the caller's arrays are host memory
+    float ms = 0.f;
+    HIPCHK(hipEventElapsedTime(&ms, c->ev0, c->ev1));
+    c->q.stats.prefill_ms += ms;              // the copy IS these rows' admission
+    c->q.admit_copy(src_row, dst_rows, n, max_new);
     return ER_OK;
 }
 

@@ -70,6 +70,44 @@ struct QueueHost {
         stats.admissions += n_rows;
     }
 
+    // er_queue_admit_copy: n free rows dst_rows[i] start as copies of the FRESH job in src_row (occupied, not done, no step replayed since
+    // its admission: only then do its K/V [0, S), its last hidden state and its generation state still describe "right after the prefill").
+    int check_admit_copy(int src_row, const int32_t* dst_rows, int n, const int32_t* max_new_host) {
+        if (!active) return say(ER_ERR_INVALID, "er_queue_admit_copy: no queue is open (call er_queue_begin)");
+        if (src_row < 0 || src_row >= slots) return say(ER_ERR_INVALID, "er_queue_admit_copy: source row %d outside the %d slots", src_row, slots);
+        const Row& s = rows[(size_t)src_row];
+        if (!s.occupied || s.done || s.steps != 0)
+            return say(ER_ERR_INVALID, "er_queue_admit_copy: source row %d holds no fresh job (%s)", src_row,
+                       !s.occupied ? "it is free" : s.done ? "its job is done" : "its job has run a step");
+        if (n <= 0 || n >= slots || !dst_rows) return say(ER_ERR_INVALID, "er_queue_admit_copy: %d destination rows", n);
+        for (int i = 0; i < n; ++i) {
+            const int d = dst_rows[i];
+            if (d < 0 || d >= slots) return say(ER_ERR_INVALID, "er_queue_admit_copy: destination row %d outside the %d slots", d, slots);
+            if (d == src_row) return say(ER_ERR_INVALID, "er_queue_admit_copy: row %d is the source and a destination", d);
+            if (rows[(size_t)d].occupied) return say(ER_ERR_INVALID, "er_queue_admit_copy: row %d is occupied", d);
+            for (int k = 0; k < i; ++k)
+                if (dst_rows[k] == d) return say(ER_ERR_INVALID, "er_queue_admit_copy: row %d is a destination twice", d);
+        }
+        for (int i = 0; i < n; ++i) {
+            const int b = budget_of(max_new_host, i);
+            if (b <= 0 || b > max_new)
+                return say(ER_ERR_INVALID, "er_queue_admit_copy: budget %d of row %d outside [1, %d] (er_queue_begin's max_new_tokens)", b, dst_rows[i], max_new);
+            const long long need = (long long)s.S + b + 1;
+            if (need > l_cap) return say(ER_ERR_CAPACITY, "er_queue_admit_copy: prefix %d + budget %d + 1 > reserved cache (%d)", s.S, b, l_cap);
+            if (need > max_positions) return say(ER_ERR_CAPACITY, "er_queue_admit_copy: prefix %d + budget %d + 1 > position table (%d)", s.S, b, max_positions);
+        }
+        return ER_OK;
+    }
+    void admit_copy(int src_row, const int32_t* dst_rows, int n, const int32_t* max_new_host) {
+        const int S = rows[(size_t)src_row].S;
+        for (int i = 0; i < n; ++i) {
+            Row& r = rows[(size_t)dst_rows[i]];
+            r = Row{};
+            r.occupied = true; r.S = S; r.budget = budget_of(max_new_host, i);
+        }
+        stats.admissions += n;      // a copied row is an admitted row
+    }
+
     int occupied() const { return (int)std::count_if(rows.begin(), rows.end(), [](const Row& r) { return r.occupied; }); }
     int list_done(int32_t* out) const {
         int n = 0;

@@ -61,6 +61,17 @@ def kv8_encode(x):
     return out
 
 
+def kv_fork(k_cache, v_cache, src_rows, dst_rows, length):
+    """``er_k_kv_fork`` in place on caches [layers, B, H, Lcap, D] of 4-, 2- or 1-byte elements: positions [0, length) of every layer
+    and head of row src_rows[i] are copied to row dst_rows[i].  Enqueued on the current stream without blocking (capturable)."""
+    assert k_cache.shape == v_cache.shape and k_cache.dtype == v_cache.dtype and k_cache.dim() == 5
+    layers, B, H, Lcap, D = k_cache.shape
+    assert len(src_rows) == len(dst_rows)
+    native.check(native.load_library().er_k_kv_fork(native.ptr(k_cache), native.ptr(v_cache), k_cache.element_size(), layers, B, H, Lcap, D,
+                                                    native.i32_array(src_rows), native.i32_array(dst_rows), len(src_rows), int(length),
+                                                    _st()), "er_k_kv_fork")
+
+
 def xt_pack_image(x):
     """The tiled hi | lo activation image of x [B, K] fp32 (K a multiple of 4), as the fast-mode matrix-core projections exchange
     it: a plain restatement of ``xt_entry`` / ``xt_pack`` in csrc/k_gemv.h.  Returns a half tensor [groups, K / 4, 32, 8]:

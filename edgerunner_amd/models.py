@@ -50,6 +50,44 @@ def prefix_leaders(conds) -> List[int]:
     return [first.setdefault(np.ascontiguousarray(a[b]).tobytes(), b) for b in range(a.shape[0])]
 
 
+def fork_plan(conds, resume_ids=None):
+    """The plan behind ``fork_prefill``: ``(order, leader, n_leaders)`` for a batch whose rows are EQUAL when their ``conds`` entry and
+    their ``resume_ids`` row are both bit-equal (as ``prefix_leaders``: -0.0 and 0.0 differ; one ``num_faces`` per call).  ``order`` is
+    the stable permutation that puts each class's first row in front - the row at permuted place i is the caller's row ``order[i]``:
+    first the classes' first rows in first-occurrence order (``n_leaders`` of them), then every other row in the caller's order.
+    ``leader[i]`` is the permuted place of the first row of place i's class, so ``leader[i] == i`` below ``n_leaders`` and
+    ``leader[i] < n_leaders`` behind: the table ``er_prefill_fork`` takes, and a valid ``er_set_prefix_groups`` table.  A pure function
+    of the host copies; ``conds`` may be None (no conditioning: the rows are told apart by ``resume_ids`` alone, which then gives B)."""
+    host = lambda t: None if t is None else (t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t))
+    c, r = host(conds), host(resume_ids)
+    if c is None and r is None:
+        raise ValueError("fork_plan: neither conds nor resume_ids")
+    B = (c if c is not None else r).shape[0]
+    if c is not None and r is not None and r.shape[0] != B:
+        raise ValueError(f"fork_plan: {B} conds entries but {r.shape[0]} resume_ids rows")
+    key = lambda b: (b"" if c is None else np.ascontiguousarray(c[b]).tobytes(), b"" if r is None else np.ascontiguousarray(r[b]).tobytes())
+    place: Dict[tuple, int] = {}
+    firsts, cls = [], []
+    for b in range(B):
+        k = key(b)
+        if k not in place:
+            place[k] = len(firsts)
+            firsts.append(b)
+        cls.append(place[k])
+    is_first = set(firsts)
+    rest = [b for b in range(B) if b not in is_first]
+    order = firsts + rest
+    return order, [cls[b] for b in order], len(firsts)
+
+
+def fork_streams(order, row_streams=None) -> List[int]:
+    """The Philox stream of every permuted place under ``fork_prefill``: the stream the caller's row ``order[i]`` would have had - its
+    original index, or the caller's ``row_streams`` entry - so that sample-mode ids do not depend on the permutation."""
+    if row_streams is not None and len(row_streams) != len(order):
+        raise ValueError(f"row_streams has {len(row_streams)} entries for a batch of {len(order)}")
+    return [int(o) if row_streams is None else int(row_streams[o]) for o in order]
+
+
 class _QueueJob:
     """One job of ``LMM.generate_queue``: ``(conds, num_faces, resume_ids=None, stream=None, max_new_tokens=None)``."""
 
@@ -69,12 +107,29 @@ class _QueueJob:
         if self.budget < 1:
             raise ValueError(f"job {index}: max_new_tokens={self.budget}")
 
+    def input_key(self) -> tuple:
+        """What decides the job's prefill, as bytes: two jobs with equal keys are repeats of one input (``fork_repeats``)."""
+        c = self.conds.detach().cpu().numpy()
+        return (c.dtype.str, c.shape, np.ascontiguousarray(c).tobytes(), self.num_faces,
+                b"" if self.resume is None else self.resume.numpy().tobytes())
+
+
+def queue_fork_split(keys) -> List[int]:
+    """For the jobs of ONE admit call, by their ``input_key``: source[i] = the place in the call of the first job with job i's key (i
+    itself for a job that is prefilled).  A pure host function; ``sum(source[i] != i)`` jobs are admitted by copy."""
+    first: Dict[tuple, int] = {}
+    return [first.setdefault(k, i) for i, k in enumerate(keys)]
+
 
 class _QueueEngine:
     """The engine ``edgerunner_amd.queue.QueueScheduler`` drives: admissions are prefills into cache rows of the native context."""
 
-    def __init__(self, lmm: "LMM", jobs: List[_QueueJob], logprobs: bool = False):
+    def __init__(self, lmm: "LMM", jobs: List[_QueueJob], logprobs: bool = False, fork_repeats: bool = False):
         self.lmm, self.jobs, self.dec = lmm, jobs, lmm.mesh_decoder
+        # fork_repeats: inside one admit call a job whose input repeats an earlier job's is not prefilled: it starts as a copy of that
+        # job's row (er_queue_admit_copy), taken before any step runs.  The prefilled job's pass is the one it would have had anyway.
+        self.fork_repeats = fork_repeats
+        self.forked = 0               # rows admitted by copy
         self.logprobs = logprobs      # take() then returns (ids, float32 [2, n]): the job's model / policy log-probs
         # exact mode: the jobs of one admit call that share a prefix length go through ONE forward pass (rows of a batched prefill
         # give the ids of their single runs, as LMM.generate's batches do).  Fast mode: one row per pass - the fp16-weight Linears of
@@ -94,15 +149,26 @@ class _QueueEngine:
         return torch.cat((cond, tok), dim=1) if cond is not None else tok
 
     def admit(self, slot0: int, job_ids) -> None:
-        embeds = [self.embeds(self.jobs[j]) for j in job_ids]
+        n = len(job_ids)
+        source = queue_fork_split([self.jobs[j].input_key() for j in job_ids]) if self.fork_repeats else list(range(n))
+        embeds = [self.embeds(self.jobs[j]) if source[i] == i else None for i, j in enumerate(job_ids)]
         i = 0
-        while i < len(job_ids):
+        while i < n:
+            if embeds[i] is None:     # a repeat: its row is filled below, from its source's
+                i += 1
+                continue
             k = i + 1
-            while k < len(job_ids) and k - i < self.rows_per_pass and embeds[k].shape[1] == embeds[i].shape[1]:
+            while k < n and k - i < self.rows_per_pass and embeds[k] is not None and embeds[k].shape[1] == embeds[i].shape[1]:
                 k += 1
             part = [self.jobs[j] for j in job_ids[i:k]]
             self.dec.queue_admit(slot0 + i, torch.cat(embeds[i:k], dim=0), [p.stream for p in part], [p.budget for p in part])
             i = k
+        for s in range(n):
+            copies = [i for i in range(n) if source[i] == s and i != s]
+            if copies:
+                part = [self.jobs[job_ids[i]] for i in copies]
+                self.dec.queue_admit_copy(slot0 + s, [slot0 + i for i in copies], [p.stream for p in part], [p.budget for p in part])
+                self.forked += len(copies)
 
     def run(self):
         return self.dec.queue_run()
@@ -382,8 +448,17 @@ class LMM:
     def generate_ids(self, conds, num_faces=1000, resume_ids=None, tokenizer=None, max_new_tokens=None,
                      min_new_tokens: int = 0, seed: Optional[int] = None, row_streams=None, share_prefix=False, *,
                      temperature: Optional[float] = None, top_p: Optional[float] = None, top_k: Optional[int] = None,
-                     output_logprobs: bool = False) -> torch.Tensor:
+                     output_logprobs: bool = False, fork_prefill: bool = False) -> torch.Tensor:
         """Everything of LMM.generate up to the HF call's return value (core/models.py:215-303).
+
+        ``fork_prefill=True``: rows whose ``conds`` entry and ``resume_ids`` row are both bit-equal (``fork_plan``) are encoded and
+        prefilled ONCE; the repeats start from a copy of that row's cache rows and last hidden state (``er_prefill_fork``), which is
+        bit for bit what their own pass would have written next to that row.  Any batch size, precision and cache type.  Ids and
+        ``last_logprobs`` come back in the caller's row order, and in sample mode a row draws from the stream it would have had
+        (its index, or its ``row_streams`` entry).  The first rows of the classes are prefilled as a batch of their own, so their
+        state is that of ``generate_ids`` on those rows alone (exact mode: the ids of the unforked call; fast mode: the GEMMs of the
+        prefill pick their kernels by the row count of the pass).  With ``share_prefix`` the groups are the plan's classes (rows of one
+        cloud whose ``resume_ids`` differ are then not grouped).  A batch without repeats takes the path of ``fork_prefill=False``.
 
         ``temperature`` / ``top_p`` / ``top_k`` (None: the reference's call, ``top_k=10`` in sample mode; ``top_k=0``: no top-k
         filter) shape the draw of sample mode as HF's warpers do; greedy mode accepts them and picks the same ids.
@@ -402,8 +477,18 @@ class LMM:
             raise ValueError(f"share_prefix must be a bool, 'valu' or 'mfma', got {share_prefix!r}")
         opt = self.opt
         B = conds.shape[0]
-        cond_embeds = self.encode_cond(conds, [num_faces] * B)["cond_embeds"]
-        input_ids = torch.full((B, 1), opt.bos_token_id, dtype=torch.long)
+        fork = None
+        if fork_prefill:
+            order, leader, n_leaders = fork_plan(conds, resume_ids)
+            if n_leaders < B:
+                fork = (order, leader)
+                row_streams = fork_streams(order, row_streams)
+                first = torch.as_tensor(order[:n_leaders], dtype=torch.long)
+                conds = conds[first.to(conds.device)]
+                resume_ids = None if resume_ids is None else resume_ids[first.to(resume_ids.device)]
+        N = conds.shape[0]                     # rows that are encoded and prefilled: B, or the leaders of a fork
+        cond_embeds = self.encode_cond(conds, [num_faces] * N)["cond_embeds"]
+        input_ids = torch.full((N, 1), opt.bos_token_id, dtype=torch.long)
         if resume_ids is not None:
             input_ids = torch.cat((input_ids, resume_ids.to("cpu", torch.long)), dim=1)
         tokens_embeds = self.mesh_decoder.model.embd(input_ids)
@@ -420,8 +505,10 @@ class LMM:
         kwargs = dict(inputs_embeds=inputs_embeds, num_tokens=num_tokens, pad_token_id=opt.pad_token_id,
                       bos_token_id=opt.bos_token_id, eos_token_id=opt.eos_token_id, max_new_tokens=max_new_tokens,
                       prefix_allowed_tokens_fn=fn, min_new_tokens=min_new_tokens, seed=seed, row_streams=row_streams)
+        if fork is not None:
+            kwargs["fork_leaders"] = fork[1]
         if share_prefix and (B > 4 or os.environ.get("ER_FORCE_BATCHED", "")[:1] == "1"):
-            kwargs["prefix_groups"] = (prefix_leaders(conds), opt.num_cond_tokens + 1)
+            kwargs["prefix_groups"] = (fork[1] if fork is not None else prefix_leaders(conds), opt.num_cond_tokens + 1)
             if isinstance(share_prefix, str):
                 kwargs["prefix_pass"] = share_prefix
         if opt.generate_mode == "greedy":
@@ -440,12 +527,20 @@ class LMM:
         self.last_logprobs = None
         out = self.mesh_decoder.generate(**kwargs)
         self.last_logprobs = self.mesh_decoder.last_logprobs
+        if fork is not None:                   # back to the caller's row order: permuted place i holds the caller's row order[i]
+            back = torch.empty(B, dtype=torch.long)
+            back[torch.as_tensor(fork[0], dtype=torch.long)] = torch.arange(B)
+            back = back.to(out.device)
+            out = out[back]
+            if self.last_logprobs is not None:
+                self.last_logprobs = {k: v[back] for k, v in self.last_logprobs.items()}
         return out
 
     @torch.no_grad()
     def generate_queue(self, jobs, slots: int, tokenizer=None, max_new_tokens=None, min_new_tokens: int = 0,
                        seed: Optional[int] = None, clean=True, check_every: int = 0, *, temperature: Optional[float] = None,
-                       top_p: Optional[float] = None, top_k: Optional[int] = None, output_logprobs: bool = False):
+                       top_p: Optional[float] = None, top_k: Optional[int] = None, output_logprobs: bool = False,
+                       fork_repeats: bool = False):
         """Serves independent jobs from ``slots`` cache rows (continuous batching, ``er_queue_*``) -> ``(meshes, all_tokens)`` in job
         order, as ``generate`` returns them for one job each.  A job is ``(conds [N,3] or [1,N,3], num_faces, resume_ids=None,
         stream=None, max_new_tokens=None)``; clouds of different sizes, different face counts and resume lengths may be mixed.  A job
@@ -455,13 +550,19 @@ class LMM:
         ``generate`` on that job alone (fp32; fp16: within one kernel class, slots <= 4 or slots > 4).  Afterwards
         ``last_queue_stats`` holds the ``er_queue_stats`` counters and ``last_queue_slots[j]`` the slot job j ran in.  The sampling
         controls and ``output_logprobs`` are those of ``generate_ids``; with ``output_logprobs=True`` ``last_queue_logprobs[j]`` is the
-        pair (model, policy) of float32 numpy arrays over job j's generated tokens (its own length, the resume prefix not counted)."""
+        pair (model, policy) of float32 numpy arrays over job j's generated tokens (its own length, the resume prefix not counted).
+        ``fork_repeats=True``: jobs that are admitted together (one scheduler ``admit`` call) and whose (conds, num_faces, resume_ids)
+        are bit-equal are prefilled once; the others start as copies of that job's row (``er_queue_admit_copy``) with their own stream
+        and budget.  Every job's tokens and log-probs stay those of ``fork_repeats=False``; ``last_queue_stats["forked"]`` counts the
+        rows admitted by copy (0 with the option off), ``last_queue_stats["admissions"]`` counts every job either way, and
+        ``last_queue_admissions`` lists the scheduler's admit calls as (first slot, [job indices])."""
         from .meto import Engine, save_mesh
         from .queue import QueueScheduler
         opt = self.opt
         budget = opt.max_seq_length if max_new_tokens is None else int(max_new_tokens)
         jobs = [_QueueJob(j, spec, budget) for j, spec in enumerate(jobs)]
         self.last_queue_stats, self.last_queue_slots, self.last_queue_logprobs = {}, [], None
+        self.last_queue_admissions = []        # the scheduler's admit calls in order: (first slot, [job indices])
         if not jobs:
             return [], []
         fn = BuiltinGrammar(select_grammar(opt, tokenizer is not None), self.vocab_size, opt.eos_token_id)
@@ -478,12 +579,15 @@ class LMM:
                         1.0 if top_p is None else top_p, output_logprobs)
         try:
             sched = QueueScheduler(int(slots))
-            ids = sched.serve(_QueueEngine(self, jobs, output_logprobs), len(jobs))
+            engine = _QueueEngine(self, jobs, output_logprobs, fork_repeats)
+            ids = sched.serve(engine, len(jobs))
             if output_logprobs:
                 self.last_queue_logprobs = [(lp[0], lp[1]) for _, lp in ids]
                 ids = [i for i, _ in ids]
             self.last_queue_stats = dec.queue_stats()
+            self.last_queue_stats["forked"] = engine.forked
             self.last_queue_slots = list(sched.slot_of)
+            self.last_queue_admissions = [(s, list(j)) for s, j in sched.admissions]
         finally:
             dec.queue_end()
             dec.set_sampling()                 # the controls were the queue's: the context is back at its defaults
@@ -503,14 +607,15 @@ class LMM:
     def generate(self, conds, num_faces=1000, resume_ids=None, tokenizer=None, max_new_tokens=None, clean=True,
                  min_new_tokens: int = 0, seed: Optional[int] = None, row_streams=None, share_prefix=False, *,
                  temperature: Optional[float] = None, top_p: Optional[float] = None, top_k: Optional[int] = None,
-                 output_logprobs: bool = False):
-        """-> (meshes, all_tokens) like core/models.py:204-319.  ``share_prefix``, the sampling controls and ``output_logprobs``
+                 output_logprobs: bool = False, fork_prefill: bool = False):
+        """-> (meshes, all_tokens) like core/models.py:204-319.  ``share_prefix``, ``fork_prefill``, the sampling controls and ``output_logprobs``
         (-> ``last_logprobs``, columns = the generated ids, without the resume prefix ``all_tokens`` echoes): see ``generate_ids``.  ``tokenizer`` is a
         ``edgerunner_amd.meto.Engine`` (or None for the 9-coordinate layout); each mesh is a
         ``edgerunner_amd.meto.Mesh`` - ``.vertices``, ``.faces``, ``.export(path)``, the members the reference's callers
         use of the trimesh objects it returns (trimesh itself is absent here); it still unpacks as ``v, f = mesh``."""
         output_ids = self.generate_ids(conds, num_faces, resume_ids, tokenizer, max_new_tokens, min_new_tokens, seed, row_streams, share_prefix,
-                                       temperature=temperature, top_p=top_p, top_k=top_k, output_logprobs=output_logprobs)
+                                       temperature=temperature, top_p=top_p, top_k=top_k, output_logprobs=output_logprobs,
+                                       fork_prefill=fork_prefill)
         from .meto import Engine, save_mesh
         meshes: List[Optional[object]] = []
         all_tokens: List[np.ndarray] = []

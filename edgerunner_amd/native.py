@@ -40,6 +40,7 @@ EXPORTS = [
     "er_k_w8_quantize", "er_k_gemv_form_w8", "er_k_attn_outproj3_w8", "er_k_kv8_encode",
     "er_set_prefix_pass", "er_k_attn_shared_mfma", "er_ctx_w8_streams",
     "er_ctx_w4_streams", "er_ctx_w4_streams_batched", "er_k_w4_quantize", "er_k_gemv_form_w4", "er_k_w4_cvt_probe",
+    "er_prefill_fork", "er_k_kv_fork", "er_queue_admit_copy",
 ]
 
 
@@ -142,6 +143,8 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.er_encode_cond.argtypes = [vp, vp, ci, ci, C.POINTER(C.c_int32), vp, vp]
     lib.er_embed_tokens.argtypes = [vp, C.POINTER(C.c_int32), ci, ci, vp, vp]
     lib.er_prefill.argtypes = [vp, vp, ci, ci, vp]
+    lib.er_prefill_fork.argtypes = [vp, vp, ci, ci, C.POINTER(C.c_int32), ci, vp]
+    lib.er_k_kv_fork.argtypes = [vp, vp, ci, ci, ci, ci, ci, ci, C.POINTER(C.c_int32), C.POINTER(C.c_int32), ci, ci, vp]
     lib.er_logits.argtypes = [vp, vp, vp]
     lib.er_score.argtypes = [vp, vp, vp, ci, ci, vp, vp, vp, vp, vp]
     lib.er_point_latent.argtypes = [vp, vp, ci, ci, vp, vp, vp]
@@ -184,6 +187,7 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.er_plan_gemm_tile.argtypes = [ci, ci, ci]
     lib.er_queue_begin.argtypes = [vp, C.POINTER(ErDecodeParams), ci, vp]
     lib.er_queue_admit.argtypes = [vp, ci, ci, vp, ci, C.POINTER(C.c_uint32), C.POINTER(C.c_int32), vp]
+    lib.er_queue_admit_copy.argtypes = [vp, ci, C.POINTER(C.c_int32), ci, C.POINTER(C.c_uint32), C.POINTER(C.c_int32), vp]
     lib.er_queue_run.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), vp]
     lib.er_queue_take.argtypes = [vp, ci, C.POINTER(C.c_int64), ci, C.POINTER(C.c_int32)]
     lib.er_queue_stats.argtypes = [vp, C.POINTER(ErQueueCounters)]

@@ -229,6 +229,12 @@ class NativeShapeOPT:
         ("valu" | "mfma"): the prefix pass of THIS grouping; the context's own setting (``set_prefix_pass``) is put back behind it."""
         x = inputs_embeds.to(self.device, torch.float32).contiguous()
         B, S, _ = x.shape
+        self._reserve_and_group(B, S, max_new_tokens, prefix_groups, prefix_pass)
+        with self._enter():
+            native.check(self.lib.er_prefill(self._ctx, native.ptr(x), B, S, self._sp()), "er_prefill")
+        self._exit()
+
+    def _reserve_and_group(self, B, S, max_new_tokens, prefix_groups, prefix_pass):
         need = S + max_new_tokens + 1
         if self._reserved[0] != B or self._reserved[1] < need:
             self.reserve(B, need)
@@ -241,8 +247,19 @@ class NativeShapeOPT:
                 self.set_prefix_groups(prefix_groups)
             finally:
                 self.set_prefix_pass(mine)
+
+    def prefill_fork(self, inputs_embeds: torch.Tensor, leaders, max_new_tokens: int, prefix_groups=None, prefix_pass=None):
+        """``er_prefill_fork``: ``prefill`` for a batch of ``len(leaders)`` rows of which only the first ``inputs_embeds.shape[0]`` are
+        distinct.  ``leaders`` is leaders-first (``leaders[b] == b`` for the rows that have embeds, the index of such a row behind them):
+        the forward pass runs over the leaders alone and every other row receives its leader's cache rows and last hidden state as a
+        copy.  ``prefix_groups`` / ``prefix_pass`` as for ``prefill``; groups must name the same leader table."""
+        x = inputs_embeds.to(self.device, torch.float32).contiguous()
+        n_leaders, S, _ = x.shape
+        leaders = [int(v) for v in leaders]
+        self._reserve_and_group(len(leaders), S, max_new_tokens, prefix_groups, prefix_pass)
         with self._enter():
-            native.check(self.lib.er_prefill(self._ctx, native.ptr(x), B, S, self._sp()), "er_prefill")
+            native.check(self.lib.er_prefill_fork(self._ctx, native.ptr(x), n_leaders, S, native.i32_array(leaders), len(leaders),
+                                                  self._sp()), "er_prefill_fork")
         self._exit()
 
     def logits(self) -> torch.Tensor:
@@ -306,10 +323,12 @@ class NativeShapeOPT:
                  prefix_allowed_tokens_fn: Optional[Callable] = None, num_beams: int = 1, do_sample: bool = False,
                  top_k: int = 50, min_new_tokens: int = 0, seed: Optional[int] = None, row_streams=None,
                  prefix_groups=None, temperature: float = 1.0, top_p: float = 1.0, output_logprobs: bool = False,
-                 prefix_pass=None, **unused) -> torch.Tensor:
+                 prefix_pass=None, fork_leaders=None, **unused) -> torch.Tensor:
         """Drop-in for ``ShapeOPT.generate`` as called at core/models.py:303.
         ``num_tokens`` is accepted and ignored exactly like the reference decoder
-        ignores it (modeling_opt.py:324,467,546).  ``prefix_groups`` and ``prefix_pass`` go to ``prefill``.
+        ignores it (modeling_opt.py:324,467,546).  ``prefix_groups`` and ``prefix_pass`` go to ``prefill``.  ``fork_leaders``: a
+        leaders-first table for a batch of ``len(fork_leaders)`` rows; ``inputs_embeds`` then holds the leaders only and the prefill is
+        ``prefill_fork``.
 
         ``temperature``, ``top_k`` (0: no top-k filter) and ``top_p`` act in sample mode, in the order of HF's warpers; greedy mode
         accepts them and picks the same ids.  ``output_logprobs=True`` leaves ``last_logprobs = {"model", "policy"}`` (float32
@@ -325,8 +344,12 @@ class NativeShapeOPT:
                 raise ValueError(f"{name}_token_id={got} differs from the context's {want}")
         if max_new_tokens is None:
             max_new_tokens = self.opt.max_seq_length
-        B = inputs_embeds.shape[0]
-        self.prefill(inputs_embeds, max_new_tokens, prefix_groups=prefix_groups, prefix_pass=prefix_pass)
+        if fork_leaders is None:
+            B = inputs_embeds.shape[0]
+            self.prefill(inputs_embeds, max_new_tokens, prefix_groups=prefix_groups, prefix_pass=prefix_pass)
+        else:
+            B = len(fork_leaders)
+            self.prefill_fork(inputs_embeds, fork_leaders, max_new_tokens, prefix_groups=prefix_groups, prefix_pass=prefix_pass)
         # sample mode: the Philox stream of row b (default b; a sharding / batching caller passes global job indices)
         if row_streams is not None and len(row_streams) != B:
             raise ValueError(f"row_streams has {len(row_streams)} entries for a batch of {B}")
@@ -454,6 +477,20 @@ class NativeShapeOPT:
             raise ValueError(f"queue_admit: {n} rows need {n} stream ids / budgets")
         with self._enter():
             native.check(self.lib.er_queue_admit(self._ctx, int(row0), n, native.ptr(x), S, ids, bud, self._sp()), "er_queue_admit")
+        self._exit()
+
+    def queue_admit_copy(self, src_row: int, dst_rows, stream_ids=None, budgets=None):
+        """``er_queue_admit_copy``: starts jobs in the free rows ``dst_rows`` as copies of the fresh job in ``src_row`` (admitted and
+        not yet stepped): its cache rows and last hidden state, with stream ids and budgets of their own."""
+        dst = [int(v) for v in dst_rows]
+        n = len(dst)
+        if (stream_ids is not None and len(stream_ids) != n) or (budgets is not None and len(budgets) != n):
+            raise ValueError(f"queue_admit_copy: {n} rows need {n} stream ids / budgets")
+        ids = None if stream_ids is None else (C.c_uint32 * n)(*[int(v) & 0xFFFFFFFF for v in stream_ids])
+        bud = None if budgets is None else native.i32_array(budgets)
+        with self._enter():
+            native.check(self.lib.er_queue_admit_copy(self._ctx, int(src_row), native.i32_array(dst), n, ids, bud, self._sp()),
+                         "er_queue_admit_copy")
         self._exit()
 
     def queue_run(self):

@@ -226,7 +226,7 @@ int er_get_logprobs(er_ctx* ctx, float* model_out_dev, float* policy_out_dev, in
  * All calls block until their device work is complete.  While a queue is open er_prefill / er_score / er_decode / er_feed fail. */
 typedef struct {
     int64_t steps;               /* step replays so far                                                    */
-    int64_t admissions;          /* rows admitted                                                          */
+    int64_t admissions;          /* rows admitted (er_queue_admit and er_queue_admit_copy)                 */
     int64_t occupied_row_steps;  /* sum over steps of the rows that held a job (running or waiting)        */
     int64_t wait_row_steps;      /* steps finished jobs spent in their row before er_queue_run listed them */
     int64_t parked_row_steps;    /* sum over steps of the free rows                                        */
@@ -242,6 +242,16 @@ int er_queue_begin(er_ctx* ctx, const er_decode_params* p, int check_every, void
  * ER_ERR_CAPACITY: S + budget + 1 exceeds the reserved cache or the position table. */
 int er_queue_admit(er_ctx* ctx, int row0, int n_rows, const float* embeds_dev, int S, const uint32_t* stream_ids_host,
                    const int32_t* max_new_host, void* stream);
+/* Starts n jobs in the free rows dst_rows_host[n] (distinct, not src_row, need not be contiguous) as COPIES of the job in src_row, which
+ * must be fresh: occupied, not done and not stepped since its admission (no er_queue_run between).  K/V [0, S) of every layer
+ * (kv_fork_kernel, csrc/k_kv_fork.h) and the last hidden state are copied from src_row, S being that job's prefill length; the
+ * generation state at position S, the stream ids (NULL: the row index) and the budgets (NULL: p->max_new_tokens) are set as er_queue_admit
+ * sets them.  No other row is written.  The copies are the jobs er_queue_admit would have started from the source's embeds, one per row:
+ * the queue's contract holds for them.  er_queue_counters.admissions counts copied rows too, and prefill_ms includes the copies' time.
+ * ER_ERR_INVALID: src_row holds no fresh job, a destination is occupied / named twice / the source / outside the slots, a bad budget;
+ * ER_ERR_CAPACITY: S + budget + 1 exceeds the reserved cache or the position table. */
+int er_queue_admit_copy(er_ctx* ctx, int src_row, const int32_t* dst_rows_host, int n, const uint32_t* stream_ids_host,
+                        const int32_t* max_new_host, void* stream);
 /* Replays the step until at least one occupied row is done (EOS emitted or budget spent) and lists every done row in
  * done_rows_host[<= slots].  The host looks every check_every steps, and earlier when a row is about to spend its budget, so a done
  * job waits fewer than check_every steps.  Returns at once with the rows that are already done, or with *n_done = 0 when no row is
@@ -279,6 +289,23 @@ int er_set_prefix_groups(er_ctx* ctx, const int32_t* leader_host, int n, int pre
  * a context whose cache is not fp16 (nothing changes).  ER_ERR_INVALID: another value, or a queue is open. */
 enum er_prefix_pass { ER_PREFIX_PASS_VALU = 0, ER_PREFIX_PASS_MFMA = 1 };
 int er_set_prefix_pass(er_ctx* ctx, int pass);
+
+/* ---- forked prefill: er_prefill for a reserved batch of n rows of which only the first n_leaders are distinct inputs (many samples of
+ * one cloud).  Between two steps a row's whole state is its K/V slice, its row of the last hidden state and its generation-state entries;
+ * after a prefill the third is the same for every row and the first two are plain bytes, so a repeat is started by copying.
+ *   embeds_dev  float[n_leaders, seq_len, hidden]: the inputs of the leaders only;
+ *   leader_host int32[n], n = the reserved batch, leaders first: leader[b] == b for b < n_leaders, leader[b] < n_leaders behind them
+ *   (a table of this shape is also a valid er_set_prefix_groups table).
+ * Runs exactly the forward pass er_prefill(embeds_dev, n_leaders, seq_len) runs on this context (rows [0, n_leaders) of the cache; the
+ * scratch is sized for n_leaders rows), copies every follower's K/V [0, seq_len) of all layers (one kv_fork_kernel launch per 64
+ * followers, csrc/k_kv_fork.h; any cache type, the e4m3 byte cache included) and its last hidden state from its leader, and starts the
+ * generation state of all n rows at position seq_len.  The context is left as er_prefill leaves it.  Contract: a follower's state equals
+ * its leader's bit for bit; the leaders' state is what er_prefill(embeds_dev, n_leaders, seq_len) computes for those rows.  Row stream ids
+ * (er_set_row_streams) and budgets are not touched.  With n_leaders == n the call is er_prefill.
+ * ER_ERR_INVALID: a table that is not leaders-first, n is not the reserved batch, a queue is open, prefix groups are set with a
+ * different leader table, or seq_len < their prefix_len.  ER_ERR_CAPACITY: as er_prefill.  With prefix groups set to the SAME table the
+ * call is allowed and er_prefill's device comparison of the followers' prefixes is skipped: those bytes were just copied from the leader. */
+int er_prefill_fork(er_ctx* ctx, const float* embeds_dev, int n_leaders, int seq_len, const int32_t* leader_host, int n, void* stream);
 
 /* ---- mesh tokenizer (host code, no device work): the reference's pybind11 module meto (meto/src/bindings.cpp,
  * meto.Engine(discrete_bins, verbose, backend), meto/meto/__init__.py:21-54) for the backends Options.meto_backend
@@ -565,6 +592,14 @@ int er_k_w4_cvt_probe(float* out_dev, void* stream);
 /* The device encoder of the byte KV cache (kv8; csrc/er_w8.h kv8_encode, what the K/V producers store with) on n fp32 values in
  * device memory: dst_dev receives n e4m3fn bytes.  Blocks. */
 int er_k_kv8_encode(const float* src_dev, void* dst_dev, long long n, void* stream);
+/* kv_fork_kernel (csrc/k_kv_fork.h) on caller-owned caches kc_dev / vc_dev [layers][batch][heads][l_cap][head_dim] of esz-byte elements
+ * (4, 2 or 1): positions [0, len) of every layer and head, K and V, of row src_host[i] are copied to row dst_host[i], i < n_pairs; the
+ * pairs of one source form one group (the source is read once for all of them).  ER_ERR_INVALID, before anything is launched: a row
+ * outside [0, batch), a destination that is also a source or named twice, len outside [1, l_cap], esz not 1, 2 or 4, a slab len *
+ * head_dim * esz that is not a multiple of 16 bytes (or caches not 16-byte aligned).  Unlike the other unit entries it does NOT block
+ * and allocates nothing, so that the launch can be captured in a graph. */
+int er_k_kv_fork(void* kc_dev, void* vc_dev, int esz, int layers, int batch, int heads, int l_cap, int head_dim, const int32_t* src_host,
+                 const int32_t* dst_host, int n_pairs, int len, void* stream);
 /* C[M,N] = A[M,K] op(B) (+bias)(relu)(+resid); b_is_kn=0: B is [N,K] (Linear weight), 1: B is [K,N] */
 int er_k_gemm(const float* a_dev, const float* b_dev, const float* bias_dev, const float* resid_dev,
               float* c_dev, int m, int n, int k, int lda, int ldb, int ldc, int b_is_kn, int relu,

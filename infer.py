@@ -36,6 +36,11 @@ rows change owners; groups in queue mode are not built): both together are refus
 ER_INFER_PREFIX_PASS=mfma beside it passes ``share_prefix="mfma"``: the shared prefix is read by the matrix-core prefix pass (fast mode's
 fp16 cache only; ``LMM.generate_ids``).  Alone, or with any other value than ``mfma``, it does nothing.
 
+ER_INFER_FORK_PREFILL=1 encodes and prefills every distinct input of a call once and starts its repeats (--test_repeat samples of one
+cloud at one face count) from a copy of that row's cache (``LMM.generate(fork_prefill=True)``; in queue mode
+``LMM.generate_queue(fork_repeats=True)``, for repeats that are admitted together).  Same output files; it combines with every other
+variable here.  Without the variable nothing changes.
+
 ER_INFER_TEMPERATURE, ER_INFER_TOP_P and ER_INFER_TOP_K (0: no top-k filter) shape the draws of ``--generate_mode sample`` as HF's
 warpers do, in that order; unset, the reference's TopK(10) at temperature 1 stays.  ER_INFER_LOGPROBS=1 writes
 ``{name}_{i}_{n}f_logprobs.npy`` beside every tokens file: float32 [n, 2], one row per token of the tokens file (cut at EOS the same way),
@@ -142,6 +147,7 @@ def main(argv=None):
     opt = parse_cli(argv)
     sampling = sampling_from_env()
     share_prefix = os.environ.get("ER_INFER_SHARE_PREFIX") == "1"
+    fork_prefill = os.environ.get("ER_INFER_FORK_PREFILL") == "1"
     if share_prefix and os.environ.get("ER_INFER_PREFIX_PASS") == "mfma":
         share_prefix = "mfma"
     if share_prefix and os.environ.get("ER_INFER_QUEUE") == "1":
@@ -230,7 +236,7 @@ def main(argv=None):
         specs = [(torch.from_numpy(clouds[jobs[j][0]]).float(), jobs[j][2], None, j) for j in mine]
         t0 = time.time()
         meshes, tokens = model.generate_queue(specs, slots, tokenizer=tokenizer, max_new_tokens=opt.test_max_seq_length,
-                                              clean=True, seed=opt.seed, **sampling)
+                                              clean=True, seed=opt.seed, **({"fork_repeats": True} if fork_prefill else {}), **sampling)
         torch.cuda.synchronize()
         dt = time.time() - t0
         st = model.last_queue_stats
@@ -250,7 +256,8 @@ def main(argv=None):
         # sample mode: job j draws from the Philox stream (opt.seed, step, j) whatever rows share its call
         meshes, tokens = model.generate(cond, num_faces=num_faces, max_new_tokens=opt.test_max_seq_length,
                                         tokenizer=tokenizer, clean=True, seed=opt.seed, row_streams=list(chunk),
-                                        **({"share_prefix": share_prefix} if share_prefix else {}), **sampling)
+                                        **({"share_prefix": share_prefix} if share_prefix else {}),
+                                        **({"fork_prefill": True} if fork_prefill else {}), **sampling)
         torch.cuda.synchronize()
         dt = time.time() - t0
         blp = model.last_logprobs
