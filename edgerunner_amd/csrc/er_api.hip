@@ -75,15 +75,13 @@ struct LayerW {
     // fp8 mode (er_w8.h): the byte blocks of the same four matrices (e4m3 [N][K], then 2^e per row); *_h and the fp32 copies then hold
     // the dequantised values
     unsigned char *wqkv_q = nullptr, *wo_q = nullptr, *w1_q = nullptr, *w2_q = nullptr;
-    void *wqkv_t = nullptr, *wo_t = nullptr, *w1_t = nullptr, *w2_t = nullptr;   // tiled copies for the matrix-core batched kernels (k_gemv_mfma.h)
-    void *wqkv_t8 = nullptr, *wo_t8 = nullptr, *w1_t8 = nullptr, *w2_t8 = nullptr;   // fp8 mode: tiled BYTE copies (er_w8_tile_map.h) of the projections a plan streams as bytes
     // fp4 mode (er_w4.h): the canonical MXFP4 blocks of the same four matrices (nibble bytes [N][K / 2], then e8m0 bytes [N][K / 32]) - *_h and
-    // the fp32 copies hold the dequantised values - and the quad-interleaved copies the nibble row kernels stream (er_w4_map.h; made by
-    // make_w4_streams for the projections that have a nibble form)
+    // the fp32 copies hold the dequantised values
     unsigned char *wqkv_q4 = nullptr, *wo_q4 = nullptr, *w1_q4 = nullptr, *w2_q4 = nullptr;
-    void *wqkv_s4 = nullptr, *w1_s4 = nullptr, *w2_s4 = nullptr;
-    void *wqkv_t4 = nullptr, *wo_t4 = nullptr, *w1_t4 = nullptr, *w2_t4 = nullptr;   // fp4 mode: tiled NIBBLE copies (er_w4_tile_map.h) of the projections a plan streams as nibbles in its matrix-core forms
-    void* w2_kt = nullptr;   // fc2.weight k-major, [intermediate][hidden] in the streamed weight type: the fused single-row MLP (k_mlp_sparse.h)
+    // What the context derives from them, by (projection, source): the tiled copies of the matrix-core kernels (k_gemv_mfma.h, er_w8_tile_map.h,
+    // er_w4_tile_map.h), the quad-interleaved nibble copies (er_w4_map.h) and fc2 k-major (k_mlp_sparse.h).  ensure_weight_copies makes the
+    // ones a reserved plan streams, er_ctx::copy_made says which match the loaded weights, weight_ptr hands them out.
+    void* copy[4][WSRC_COUNT] = {};
     float *wqkv = nullptr, *bqkv = nullptr;   // fused [3*hidden][hidden] in q,k,v order
     float *wo = nullptr, *bo = nullptr, *ln1w = nullptr, *ln1b = nullptr;
     float *w1 = nullptr, *b1 = nullptr, *w2 = nullptr, *b2 = nullptr, *ln2w = nullptr, *ln2b = nullptr;
@@ -195,7 +193,6 @@ struct er_ctx {
     int kv_type = 0;         // the cache type as the kernels' kv_half argument takes it: 0 = fp32, 1 = fp16, 2 = e4m3 bytes
     bool w8 = false;         // fp8 mode: fast, with the six decoder matrices per layer quantised by row; the row forms and (w8_streams_batched) the matrix-core forms of the step stream the bytes
     bool w4 = false;         // fp4 mode: fast, with the six decoder matrices per layer quantised by blocks of 32 (MXFP4); the row forms w4_streams names and the matrix-core forms w4_streams_batched names stream the nibbles
-    bool w4_valid = false;   // LayerW::*_s4 match the loaded weights
     float *proj_w = nullptr, *proj_b = nullptr, *normc_w = nullptr, *normc_b = nullptr;
     PointEnc pe;             // point encoder (cond_mode POINT)
     WeightTable w;           // every checkpoint key (register_weights)
@@ -206,9 +203,7 @@ struct er_ctx {
     bool have_hidden = false;     // ypre holds a valid last-position state
     DecodeKnobs knobs;        // environment of er_create
     er_sampling samp{1.0f, 1.0f, 0, 0, 0};   // er_set_sampling: sticky, kept across er_kv_reserve
-    bool tiled_valid = false; // LayerW::*_t / *_t8 / *_t4 match the loaded weights, as far as tiled_have says they exist
-    bool tiled_have[2][4] = {};   // [0]: the fp16 / fp32 tiled copy, [1]: the tiled byte (fp8 mode) or nibble (fp4 mode) copy of qkv / out_proj / fc1 / fc2 has been made (every layer)
-    bool kmajor_valid = false; // LayerW::w2_kt match the loaded weights
+    bool copy_made[4][WSRC_COUNT] = {};   // LayerW::copy[proj][source] of every layer has been made of the weights as loaded now (any reload clears the table)
     void* zero_row = nullptr;  // hidden zeros (fp32 size): what the fused MLP reads in place of a dead neuron's row
     int prof_len = 0;         // > 0: attention kernels run at this fixed length (er_profile_decode_kernels_at)
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -399,7 +394,7 @@ extern "C" int er_load_tensor(er_ctx* c, const char* key, const void* data, int 
     if (!c || !key) return fail(ER_ERR_INVALID, "er_load_tensor: bad argument");
     HIPCHK(hipSetDevice(c->device));
     const int rc = weights_load(c->w, c->own_stream, "er_load_tensor", key, data, dtype, ndim, shape, on_device);
-    if (rc != 1) c->tiled_valid = c->kmajor_valid = c->w4_valid = false;  // any reload invalidates the tiled copies of the batched path, the k-major fc2 copies and the streamed nibble copies
+    if (rc != 1) memset(c->copy_made, 0, sizeof(c->copy_made));      // any reload invalidates every derived copy
     return rc;
 }
 
@@ -408,9 +403,7 @@ extern "C" int er_finalize_weights(er_ctx* c) {
     return weights_finalize(c->w);
 }
 
-// second copy of the qkv / fc1 / fc2 matrices in the layout the matrix-core batched kernels stream (made the first
-// time a batch > 4 is reserved: 2.5 GB fp32 / 1.3 GB fp16 of the 288 GB)
-// src: the row-major matrix, the byte block (w8_t) or the canonical MXFP4 block (w4_t: w4_tile_kernel)
+// the tiled copy of a matrix (k_gemv_mfma.h); src: the row-major matrix, the byte block (w8_t) or the canonical MXFP4 block (w4_t: w4_tile_kernel)
 template <typename WT>
 static hipError_t launch_tile_weights(const void* src, void* dst, int N, int K, hipStream_t st) {
     if constexpr (WTraits<WT>::NIBBLES) {
@@ -421,117 +414,87 @@ static hipError_t launch_tile_weights(const void* src, void* dst, int N, int K, 
     }
     return hipGetLastError();
 }
-template <typename WT>
-static int make_tiled(er_ctx* c, const void* src, void** dst, int N, int K) {
-    if (!*dst) {
-        char* blk = nullptr;
-        ERCHK(c->w.alloc(&blk, tiled_weight_bytes<WT>(N, K)));
-        *dst = blk;
-    }
-    HIPCHK(launch_tile_weights<WT>(src, *dst, N, K, c->own_stream));
-    return 0;
+
+// ------------------------------------------------------------------------------------ the weight copies
+static WMode ctx_mode(const er_ctx* c) { return c->w4 ? W_FP4 : c->w8 ? W_FP8 : c->fast ? W_FAST : W_EXACT; }
+
+// Where copy `s` of `proj` in layer L is: the loaded matrix or byte block, or a derived copy while it matches the loaded weights - else
+// null, and the launch that wants it fails (run_proj)
+static const void* weight_ptr(const er_ctx* c, const LayerW& L, Proj proj, WSrc s) {
+    if (proj == PROJ_HEAD) return s != WSRC_PLAIN ? nullptr : c->fast ? (const void*)c->lm_head_h : (const void*)c->lm_head;
+    const void* const w32[4] = {L.wqkv, L.wo, L.w1, L.w2};
+    const void* const w16[4] = {L.wqkv_h, L.wo_h, L.w1_h, L.w2_h};
+    const void* const w8[4] = {L.wqkv_q, L.wo_q, L.w1_q, L.w2_q};
+    if (s == WSRC_PLAIN) return c->fast ? w16[proj] : w32[proj];
+    if (s == WSRC_BYTES) return w8[proj];
+    return c->copy_made[proj][s] ? L.copy[proj][s] : nullptr;
 }
-// fp8 mode: a projection that `plan` streams as bytes in its matrix-core form (plan_w8_batched) gets the tiled byte copy and NO fp16
-// tiled copy (1.36 GB at 24 layers when all four stream bytes); a later reserve whose plan needs the other copy makes it then.
-// fp4 mode: the same with plan_w4_batched and the tiled nibble copy (src: the canonical MXFP4 block).
-static int make_tiled_weights(er_ctx* c, const DecodePlan& plan) {
+// ... and what a derived copy is made of: the plain matrix, the byte block or the canonical MXFP4 block
+static const void* weight_origin(const er_ctx* c, const LayerW& L, Proj proj, WSrc s) {
+    const void* const w4[4] = {L.wqkv_q4, L.wo_q4, L.w1_q4, L.w2_q4};
+    return wsrc_nibbles(s) ? w4[proj] : weight_ptr(c, L, proj, s == WSRC_TILED_BYTES ? WSRC_BYTES : WSRC_PLAIN);
+}
+
+// Derived copy `s` of an [N][K] matrix (half: fp16 plain weights): its size, and the launch that makes it of `src` (weight_origin).
+// The tiled copies are a second copy of the matrix in the layout the matrix-core batched kernels stream (2.5 GB fp32 / 1.3 GB fp16 of
+// the 288 GB at 24 layers, 1.36 GB as bytes); the quad-interleaved copies are 15.4 MB per layer, fc2 k-major 0.9 GB fp32 / 0.45 GB fp16.
+static size_t weight_copy_bytes(WSrc s, bool half, int N, int K) {
+    switch (s) {
+        case WSRC_TILED: return half ? tiled_weight_bytes<_Float16>(N, K) : tiled_weight_bytes<float>(N, K);
+        case WSRC_TILED_BYTES: return tiled_weight_bytes<w8_t>(N, K);
+        case WSRC_TILED_NIBBLES: return tiled_weight_bytes<w4_t>(N, K);
+        case WSRC_QUADS: return (size_t)w4map::stream_bytes(N, K);
+        case WSRC_KMAJOR: return (size_t)N * K * (half ? 2 : 4);
+        default: return 0;
+    }
+}
+static hipError_t launch_weight_copy(WSrc s, bool half, const void* src, void* dst, int N, int K, hipStream_t st) {
+    if (!src || !dst) return hipErrorInvalidValue;
+    switch (s) {
+        case WSRC_TILED: return half ? launch_tile_weights<_Float16>(src, dst, N, K, st) : launch_tile_weights<float>(src, dst, N, K, st);
+        case WSRC_TILED_BYTES: return launch_tile_weights<w8_t>(src, dst, N, K, st);
+        case WSRC_TILED_NIBBLES: return launch_tile_weights<w4_t>(src, dst, N, K, st);
+        case WSRC_QUADS:
+            if (!w4map::shape_ok(N, K)) return hipErrorInvalidValue;
+            hipLaunchKernelGGL(w4_interleave_kernel, dim3(2048), dim3(ER_WG), 0, st, (const unsigned char*)src, (unsigned char*)dst, (long long)N, K);
+            return hipGetLastError();
+        case WSRC_KMAJOR:
+            if (N != MLP_HIDDEN || K != MLP_INTER) return hipErrorInvalidValue;
+            return half ? launch_transpose_w2<_Float16>(src, dst, st) : launch_transpose_w2<float>(src, dst, st);
+        default: return hipErrorInvalidValue;
+    }
+}
+
+// The ONE owner of the derived copies: for each of qkv / out_proj / fc1 / fc2, and for the plan as stored and as a row class runs it
+// (er_decode: fc1 and fc2 as row GEMVs on the same reserved shape), the copy weight_source names is made unless it has been, in every
+// layer, in blocks of the weight table.  An fp8 or fp4 context so gets the tiled byte or nibble copy of a projection its plan streams
+// packed and NO fp16 tiled copy of it; a later reserve whose plan names another copy makes it then.  The zero row goes with fc2 k-major.
+static int ensure_weight_copies(er_ctx* c, const DecodePlan& plan) {
     if (weights_missing(c->w)) return 0;   // weights still loading: er_prefill comes back here
     const int H = c->cfg.hidden_dim, I = c->cfg.intermediate_dim;
-    if (!c->tiled_valid) memset(c->tiled_have, 0, sizeof(c->tiled_have));
-    if (c->w8 || c->w4) {
-        bool made = false;
+    bool made = false;
+    for (int row_class = 0; row_class < 2; ++row_class)
         for (int pj = 0; pj < 4; ++pj) {
-            const int bytes = (c->w4 ? plan_w4_batched(plan, c->knobs, (Proj)pj) : plan_w8_batched(plan, c->knobs, (Proj)pj)) ? 1 : 0;
-            if (c->tiled_have[bytes][pj]) continue;
+            const WSrc s = weight_source(plan, c->knobs, ctx_mode(c), row_class != 0, (Proj)pj, 0);
+            if (!wsrc_derived(s) || c->copy_made[pj][s]) continue;
             const int N = pj == PROJ_QKV ? 3 * H : pj == PROJ_FC1 ? I : H, K = pj == PROJ_FC2 ? I : H;
+            if (s == WSRC_QUADS && !w4map::shape_ok(N, K)) return fail(ER_ERR_UNSUPPORTED, "fp4: a %d x %d matrix has no quad-interleaved copy", N, K);
+            if (s == WSRC_KMAJOR && !c->zero_row) {
+                char* z = nullptr;
+                ERCHK(weights_alloc(c->w, &z, (size_t)H * 4));
+                c->zero_row = z;
+            }
             for (LayerW& L : c->layers) {
-                const void* src16[4] = {L.wqkv_h, L.wo_h, L.w1_h, L.w2_h};
-                const void* src8[4] = {L.wqkv_q, L.wo_q, L.w1_q, L.w2_q};
-                void** dst16[4] = {&L.wqkv_t, &L.wo_t, &L.w1_t, &L.w2_t};
-                void** dst8[4] = {&L.wqkv_t8, &L.wo_t8, &L.w1_t8, &L.w2_t8};
-                const void* src4[4] = {L.wqkv_q4, L.wo_q4, L.w1_q4, L.w2_q4};
-                void** dst4[4] = {&L.wqkv_t4, &L.wo_t4, &L.w1_t4, &L.w2_t4};
-                if (bytes && c->w4) ERCHK(make_tiled<w4_t>(c, src4[pj], dst4[pj], N, K));
-                else if (bytes) ERCHK(make_tiled<w8_t>(c, src8[pj], dst8[pj], N, K));
-                else ERCHK(make_tiled<_Float16>(c, src16[pj], dst16[pj], N, K));
+                if (!L.copy[pj][s]) {
+                    char* blk = nullptr;
+                    ERCHK(c->w.alloc(&blk, weight_copy_bytes(s, c->fast, N, K)));
+                    L.copy[pj][s] = blk;
+                }
+                HIPCHK(launch_weight_copy(s, c->fast, weight_origin(c, L, (Proj)pj, s), L.copy[pj][s], N, K, c->own_stream));
             }
-            c->tiled_have[bytes][pj] = made = true;
+            c->copy_made[pj][s] = made = true;
         }
-        if (made) HIPCHK(hipStreamSynchronize(c->own_stream));
-        c->tiled_valid = true;
-        return 0;
-    }
-    if (c->tiled_valid) return 0;
-    for (LayerW& L : c->layers) {
-        if (c->fast) {
-            ERCHK(make_tiled<_Float16>(c, L.wqkv_h, &L.wqkv_t, 3 * H, H));
-            ERCHK(make_tiled<_Float16>(c, L.wo_h, &L.wo_t, H, H));
-            ERCHK(make_tiled<_Float16>(c, L.w1_h, &L.w1_t, I, H));
-            ERCHK(make_tiled<_Float16>(c, L.w2_h, &L.w2_t, H, I));
-        } else {
-            ERCHK(make_tiled<float>(c, L.wqkv, &L.wqkv_t, 3 * H, H));
-            ERCHK(make_tiled<float>(c, L.wo, &L.wo_t, H, H));
-            ERCHK(make_tiled<float>(c, L.w1, &L.w1_t, I, H));
-            ERCHK(make_tiled<float>(c, L.w2, &L.w2_t, H, I));
-        }
-    }
-    HIPCHK(hipStreamSynchronize(c->own_stream));
-    c->tiled_valid = true;
-    return 0;
-}
-
-// fp4 mode: the quad-interleaved copies of qkv, fc1 and fc2 the nibble row kernels stream (er_w4_map.h; 15.4 MB per layer), made the
-// first time a shape is reserved whose row forms stream nibbles under this context's ER_W4_ROWS; owned by the weight table.  A reload
-// invalidates them (w4_valid): until they are made again the step gets no copy and a launch that wants one fails (launch_proj)
-static bool plan_w4_rows(const DecodePlan& p, const DecodeKnobs& k, Proj proj) {
-    return !p.batched && !(p.mlp_fused && proj != PROJ_QKV) && w4_streams(proj, p.B, k.w4_rows);
-}
-static int make_w4_streams(er_ctx* c, const DecodePlan& plan) {
-    if (!c->w4 || c->w4_valid || weights_missing(c->w)) return 0;   // weights still loading: er_prefill comes back here
-    // whatever the fused MLP takes over: a row class (er_decode) runs fc1 and fc2 as row GEMVs on the same reserved shape
-    const auto wants = [&](Proj proj) { return !plan.batched && w4_streams(proj, plan.B, c->knobs.w4_rows); };
-    if (!wants(PROJ_QKV) && !wants(PROJ_FC1) && !wants(PROJ_FC2)) return 0;
-    const int H = c->cfg.hidden_dim, I = c->cfg.intermediate_dim;
-    for (LayerW& L : c->layers) {
-        const unsigned char* src[3] = {L.wqkv_q4, L.w1_q4, L.w2_q4};
-        void** dst[3] = {&L.wqkv_s4, &L.w1_s4, &L.w2_s4};
-        const int N[3] = {3 * H, I, H}, K[3] = {H, H, I};
-        for (int i = 0; i < 3; ++i) {
-            if (!w4map::shape_ok(N[i], K[i])) return fail(ER_ERR_UNSUPPORTED, "fp4: a %d x %d matrix has no quad-interleaved copy", N[i], K[i]);
-            if (!*dst[i]) {
-                char* blk = nullptr;
-                ERCHK(c->w.alloc(&blk, (size_t)w4map::stream_bytes(N[i], K[i])));
-                *dst[i] = blk;
-            }
-            hipLaunchKernelGGL(w4_interleave_kernel, dim3(2048), dim3(ER_WG), 0, c->own_stream, src[i], (unsigned char*)*dst[i], (long long)N[i], K[i]);
-            HIPCHK(hipGetLastError());
-        }
-    }
-    HIPCHK(hipStreamSynchronize(c->own_stream));
-    c->w4_valid = true;
-    return 0;
-}
-
-// k-major copy of every fc2.weight and the zero row, made the first time a shape is reserved whose plan runs the fused single-row
-// MLP (0.9 GB fp32 / 0.45 GB fp16 at 24 layers: batch-only contexts never pay them); owned by the weight table like the tiled copies
-static int make_kmajor_weights(er_ctx* c) {
-    if (c->kmajor_valid || weights_missing(c->w)) return 0;   // weights still loading: er_prefill comes back here
-    const size_t H = c->cfg.hidden_dim, I = c->cfg.intermediate_dim, esz = c->fast ? 2 : 4;
-    if (!c->zero_row) {
-        char* z = nullptr;
-        ERCHK(weights_alloc(c->w, &z, H * 4));
-        c->zero_row = z;
-    }
-    for (LayerW& L : c->layers) {
-        if (!L.w2_kt) {
-            char* blk = nullptr;
-            ERCHK(c->w.alloc(&blk, I * H * esz));
-            L.w2_kt = blk;
-        }
-        HIPCHK(c->fast ? launch_transpose_w2<_Float16>(L.w2_h, L.w2_kt, c->own_stream) : launch_transpose_w2<float>(L.w2, L.w2_kt, c->own_stream));
-    }
-    HIPCHK(hipStreamSynchronize(c->own_stream));
-    c->kmajor_valid = true;
+    if (made) HIPCHK(hipStreamSynchronize(c->own_stream));
     return 0;
 }
 
@@ -558,45 +521,24 @@ extern "C" int er_ctx_plan(er_ctx* c, er_decode_plan* out) {
     return ER_OK;
 }
 
+// The reporters project the step's own rule (weight_source, with the context's row class) onto their question.
+static int report_sources(er_ctx* c, const char* who, int32_t out[4], bool (*asks)(WSrc)) {
+    if (!c || !out) return fail(ER_ERR_INVALID, "%s: null argument", who);
+    const DecodePlan& p = c->kv->plan;
+    if (p.B <= 0) return fail(ER_ERR_INVALID, "%s: no cache reserved (call er_kv_reserve)", who);
+    for (int pj = 0; pj < 4; ++pj) out[pj] = asks(weight_source(p, c->knobs, ctx_mode(c), c->kv->row_class, (Proj)pj, 0)) ? 1 : 0;
+    return ER_OK;
+}
 // which of qkv / out_proj / fc1 / fc2 the stored plan of a live context streams as e4m3 bytes (fp8 mode; all zero in every other mode)
-extern "C" int er_ctx_w8_streams(er_ctx* c, int32_t out[4]) {
-    if (!c || !out) return fail(ER_ERR_INVALID, "er_ctx_w8_streams: null argument");
-    const DecodePlan& p = c->kv->plan;
-    if (p.B <= 0) return fail(ER_ERR_INVALID, "er_ctx_w8_streams: no cache reserved (call er_kv_reserve)");
-    const bool v3 = p.v3 && !c->kv->row_class, fused = p.mlp_fused && !c->kv->row_class;
-    for (int pj = 0; pj < 4; ++pj) {
-        const Proj proj = (Proj)pj;
-        const ProjForm f = proj_form(p, c->knobs, true, proj, 0);
-        bool bytes = false;
-        if (!c->w8) bytes = false;
-        else if (proj == PROJ_OUT && v3) bytes = w8_streams(PROJ_OUT, 1);               // the fused merge + out_proj launch
-        else if ((proj == PROJ_FC1 || proj == PROJ_FC2) && fused) bytes = false;        // the fused single-row MLP reads fp16
-        else if (f.form == ER_FORM_ROW) bytes = w8_streams(proj, p.B);
-        else bytes = plan_w8_batched(p, c->knobs, proj);
-        out[pj] = bytes ? 1 : 0;
-    }
-    return ER_OK;
-}
-
-// which of qkv / out_proj / fc1 / fc2 the stored plan of a live context streams as e2m1 nibbles (fp4 mode; all zero in every other mode)
+extern "C" int er_ctx_w8_streams(er_ctx* c, int32_t out[4]) { return report_sources(c, "er_ctx_w8_streams", out, wsrc_bytes); }
+// ... as e2m1 nibbles in their row forms (fp4 mode; all zero in every other mode)
 extern "C" int er_ctx_w4_streams(er_ctx* c, int32_t out[4]) {
-    if (!c || !out) return fail(ER_ERR_INVALID, "er_ctx_w4_streams: null argument");
-    const DecodePlan& p = c->kv->plan;
-    if (p.B <= 0) return fail(ER_ERR_INVALID, "er_ctx_w4_streams: no cache reserved (call er_kv_reserve)");
-    DecodePlan q = p;
-    if (c->kv->row_class) q.mlp_fused = false;      // a row class runs fc1 and fc2 as row GEMVs
-    for (int pj = 0; pj < 4; ++pj) out[pj] = c->w4 && plan_w4_rows(q, c->knobs, (Proj)pj) ? 1 : 0;
-    return ER_OK;
+    return report_sources(c, "er_ctx_w4_streams", out, [](WSrc s) { return s == WSRC_QUADS; });
 }
-
 // ... and as nibbles in their matrix-core batched forms (fp4 mode; all zero in every other mode, and for a plan that is not batched):
 // er_ctx_w4_streams keeps reporting the row forms only
 extern "C" int er_ctx_w4_streams_batched(er_ctx* c, int32_t out[4]) {
-    if (!c || !out) return fail(ER_ERR_INVALID, "er_ctx_w4_streams_batched: null argument");
-    const DecodePlan& p = c->kv->plan;
-    if (p.B <= 0) return fail(ER_ERR_INVALID, "er_ctx_w4_streams_batched: no cache reserved (call er_kv_reserve)");
-    for (int pj = 0; pj < 4; ++pj) out[pj] = c->w4 && p.batched && plan_w4_batched(p, c->knobs, (Proj)pj) ? 1 : 0;
-    return ER_OK;
+    return report_sources(c, "er_ctx_w4_streams_batched", out, [](WSrc s) { return s == WSRC_TILED_NIBBLES; });
 }
 
 extern "C" int er_plan_gemm_tile(int m, int n, int batch) {
@@ -660,10 +602,8 @@ static int kv_alloc(er_ctx* c, KvMem& m, int batch, int Lcap) {
     }
     m.st.row_budget = m.d_row_budget.p;
     ERCHK(m.d_out_ids.ensure(b * (size_t)Lcap));
-    if (p.mfma) ERCHK(make_tiled_weights(c, p));
-    ERCHK(make_w4_streams(c, p));
+    ERCHK(ensure_weight_copies(c, p));
     if (p.mlp_fused) {
-        ERCHK(make_kmajor_weights(c));
         ERCHK(m.mlp_part.ensure((size_t)MLP_WGS * hid));
         ERCHK(m.mlp_nnz.ensure((size_t)g.num_layers * MLP_WGS));
         HIPCHK(hipMemset(m.mlp_nnz.p, 0, m.mlp_nnz.n * sizeof(int)));
@@ -721,20 +661,27 @@ static hipError_t launch_attn_combine(const AttnDecArgs& a, int D, int B, hipStr
     return D == 96 ? launch_attn_combine_d<96>(a, B, st) : launch_attn_combine_d<64>(a, B, st);
 }
 
-// the fused single-row MLP of `layer` on the context's buffers (kinds 4 and 5 of a plan with mlp_fused)
+// The copy of its matrix the step streams for `proj` of `layer` (weight_source) and where it is (null: not made of the loaded weights)
+struct StepWeight { WSrc src; const void* w; };
+static StepWeight step_weight(const er_ctx* c, Proj proj, int layer) {
+    const WSrc s = weight_source(c->kv->plan, c->knobs, ctx_mode(c), c->kv->row_class, proj, layer);
+    return {s, weight_ptr(c, c->layers[proj == PROJ_HEAD ? 0 : layer], proj, s)};
+}
+
+// the fused single-row MLP of `layer` on the context's buffers (kinds 4 and 5 of a plan with mlp_fused): fc1 plain, fc2 k-major
 static MlpArgs mlp_args(er_ctx* c, int layer) {
     const LayerW& L = c->layers[layer];
     const KvMem& kv = *c->kv;
     MlpArgs m{};
-    m.W1 = c->fast ? (const void*)L.w1_h : (const void*)L.w1; m.b1 = L.b1; m.W2T = L.w2_kt; m.zero_row = c->zero_row;
+    m.W1 = step_weight(c, PROJ_FC1, layer).w; m.b1 = L.b1; m.W2T = step_weight(c, PROJ_FC2, layer).w; m.zero_row = c->zero_row;
     m.xin = kv.ypre1.p; m.ln_w = L.ln1w; m.ln_b = L.ln1b; m.eps = c->cfg.ln_eps; m.hout = kv.h1buf.p;
     m.part = kv.mlp_part.p; m.nnz = kv.mlp_nnz.p + (size_t)layer * MLP_WGS;
     m.b2 = L.b2; m.resid = kv.h1buf.p; m.out = kv.ypre.p;
     return m;
 }
 
-// A projection kind fills the operands from the context (plain weights, row-major input, and in io what the other forms read instead);
-// the form comes from proj_form and the launches from run_proj (er_decode_proj.h).
+// A projection kind fills the operands from the context (row-major input, and in io what the other forms read instead); the form comes
+// from proj_form, the weight copy from weight_source (weights_of: one lookup per projection) and the launches from run_proj (er_decode_proj.h).
 template <typename WT>
 static hipError_t launch_kind_t(er_ctx* c, int kind, int layer, hipStream_t st, long long* out_ids, int out_ld) {
     constexpr bool HALF = sizeof(WT) == 2;      // fp16 weights; the cache type is the context's own (c->kv_type: kv8 stores bytes under fp16 weights)
@@ -744,19 +691,16 @@ static hipError_t launch_kind_t(er_ctx* c, int kind, int layer, hipStream_t st, 
     const int H = g.hidden_dim, I = g.intermediate_dim, B = p.B;
     const SkPart sk{kv.skpart.p, kv.skpart.n};
     const auto form_of = [&](Proj proj, int l) { return proj_form(p, c->knobs, HALF, proj, l); };
-    const auto bytes_of = [&](Proj proj, const void* t8) { return c->w8 && plan_w8_batched(p, c->knobs, proj) ? t8 : nullptr; };      // null t8 (copy not made): the launch fails
-    // fp4: the plan's word, and the tiled nibble copy only while it matches the loaded weights - a launch that wants a missing one fails (run_proj)
-    const auto nib_on = [&](Proj proj) { return c->w4 && p.batched && plan_w4_batched(p, c->knobs, proj); };
-    const auto nib_of = [&](Proj proj, const void* t4) { return nib_on(proj) && c->tiled_valid && c->tiled_have[1][proj] ? t4 : nullptr; };
+    ProjIo io;
+    const auto weights_of = [&](Proj proj) { const StepWeight w = step_weight(c, proj, layer); io.src = w.src; io.w = w.w; };
     const bool v3 = p.v3 && !kv.row_class, fused = p.mlp_fused && !kv.row_class;
     GemvArgs a{};
     a.eps = g.ln_eps;
     a.hidden = H; a.head_dim = c->D; a.l_cap = p.Lcap; a.kv_bstride = p.kv_bstride; a.kv_half = c->kv_type;
-    ProjIo io;
     switch (kind) {
         case 0: {   // qkv
             const LayerW& L = c->layers[layer];
-            a.W = HALF ? (const void*)L.wqkv_h : (const void*)L.wqkv; a.bias = L.bqkv; a.N = 3 * H;
+            weights_of(PROJ_QKV); a.bias = L.bqkv; a.N = 3 * H;
             a.hout = kv.hbuf.p; a.pos = kv.st.pos;
             a.q = kv.qbuf.p;
             a.kcache = kv.kc.p + (long long)layer * p.kv_lstride * c->kv_esz;
@@ -768,11 +712,7 @@ static hipError_t launch_kind_t(er_ctx* c, int kind, int layer, hipStream_t st, 
                 // the previous layer's fc2 deferred its split-K finish to this LayerNorm
                 if (form_of(PROJ_FC2, layer - 1).defer) io.rd = {sk.p, c->layers[layer - 1].b2, kv.h1buf.p, SK_SLICES_FC2};
             }
-            io.w_tiled = L.wqkv_t; io.x_image = kv.xt_h.p; io.pro_image = p.xt ? kv.xt_h.p : nullptr;
-            if (c->w8) io.w8 = L.wqkv_q;
-            if (c->w4) io.w4 = {true, c->w4_valid ? L.wqkv_s4 : nullptr, c->knobs.w4_rows};
-            io.w8_tiled = bytes_of(PROJ_QKV, L.wqkv_t8);
-            io.w4_batched = nib_on(PROJ_QKV); io.w4_tiled = nib_of(PROJ_QKV, L.wqkv_t4);
+            io.x_image = kv.xt_h.p; io.pro_image = p.xt ? kv.xt_h.p : nullptr;
             return run_proj<WT>(PROJ_QKV, form_of(PROJ_QKV, layer), io, a, B, H, sk, st);
         }
         // v2 holds a wave's whole K/V slice in flight (latency-bound single rows); with hundreds of workgroups per CU's
@@ -791,52 +731,40 @@ static hipError_t launch_kind_t(er_ctx* c, int kind, int layer, hipStream_t st, 
             const LayerW& L = c->layers[layer];
             if (v3) {
                 OutMergeArgs m{};
-                m.W = HALF ? (const void*)L.wo_h : (const void*)L.wo; m.bias = L.bo; m.resid = c->kv->hbuf.p; m.out = c->kv->ypre1.p;
+                weights_of(PROJ_OUT);      // the byte block or the plain copy
+                m.W = io.w; m.bias = L.bo; m.resid = c->kv->hbuf.p; m.out = c->kv->ypre1.p;
                 m.part_o = c->kv->part.p; m.part_ml = c->kv->part_ml.p; m.N = H;
-                if (c->w8 && w8_streams(PROJ_OUT, 1)) {      // the row form of out_proj at one row: the same decision as launch_proj's
-                    m.W = L.wo_q;
-                    return launch_outproj_merge<w8_t, 96>(m, p.nch3, st);
-                }
-                return launch_outproj_merge<WT, 96>(m, p.nch3, st);
+                if (!m.W || (io.src != WSRC_BYTES && io.src != WSRC_PLAIN)) return hipErrorInvalidValue;
+                return io.src == WSRC_BYTES ? launch_outproj_merge<w8_t, 96>(m, p.nch3, st) : launch_outproj_merge<WT, 96>(m, p.nch3, st);
             }
-            a.W = HALF ? (const void*)L.wo_h : (const void*)L.wo; a.bias = L.bo; a.N = H; a.xin = kv.abuf.p; a.out = kv.ypre1.p; a.resid = kv.hbuf.p;
-            io.w_tiled = L.wo_t; io.x_image = kv.xt_att.p;      // the streaming attention wrote the image (attn_args: out_xt)
-            if (c->w8) io.w8 = L.wo_q;
-            io.w8_tiled = bytes_of(PROJ_OUT, L.wo_t8);
-            io.w4_batched = nib_on(PROJ_OUT); io.w4_tiled = nib_of(PROJ_OUT, L.wo_t4);
+            weights_of(PROJ_OUT); a.bias = L.bo; a.N = H; a.xin = kv.abuf.p; a.out = kv.ypre1.p; a.resid = kv.hbuf.p;
+            io.x_image = kv.xt_att.p;      // the streaming attention wrote the image (attn_args: out_xt)
             return run_proj<WT>(PROJ_OUT, form_of(PROJ_OUT, layer), io, a, B, H, sk, st);
         }
         case 4: {   // h1 = LN1(ypre1); f = relu(fc1 h1 + b)
             const LayerW& L = c->layers[layer];
             if (fused) {      // ... and the chain sums of fc2 over the live neurons; f stays in the workgroups
-                if (!c->kmajor_valid) return hipErrorInvalidValue;
-                return launch_mlp_fused<WT>(mlp_args(c, layer), st);
+                const MlpArgs m = mlp_args(c, layer);
+                if (!m.W1 || !m.W2T) return hipErrorInvalidValue;      // fc2 k-major does not match the loaded weights
+                return launch_mlp_fused<WT>(m, st);
             }
-            a.W = HALF ? (const void*)L.w1_h : (const void*)L.w1; a.bias = L.b1; a.N = I; a.xin = kv.ypre1.p; a.ln_w = L.ln1w; a.ln_b = L.ln1b;
+            weights_of(PROJ_FC1); a.bias = L.b1; a.N = I; a.xin = kv.ypre1.p; a.ln_w = L.ln1w; a.ln_b = L.ln1b;
             a.hout = kv.h1buf.p; a.out = kv.fbuf.p;
             io.pro = PRO_LN;
             // out_proj (case 3) left four K-range partials: ypre1 = ((sum) + bo) + h
             if (form_of(PROJ_OUT, layer).defer) io.rd = {sk.p, L.bo, kv.hbuf.p, SK_SLICES_OUTPROJ};
-            io.w_tiled = L.w1_t; io.x_image = kv.xt_h.p; io.pro_image = p.xt ? kv.xt_h.p : nullptr; io.out_image = kv.xt_f.p;
-            if (c->w8) io.w8 = L.w1_q;
-            if (c->w4) io.w4 = {true, c->w4_valid ? L.w1_s4 : nullptr, c->knobs.w4_rows};
-            io.w8_tiled = bytes_of(PROJ_FC1, L.w1_t8);
-            io.w4_batched = nib_on(PROJ_FC1); io.w4_tiled = nib_of(PROJ_FC1, L.w1_t4);
+            io.x_image = kv.xt_h.p; io.pro_image = p.xt ? kv.xt_h.p : nullptr; io.out_image = kv.xt_f.p;
             return run_proj<WT>(PROJ_FC1, form_of(PROJ_FC1, layer), io, a, B, H, sk, st);
         }
         case 5: {   // ypre = fc2 f + b + h1
             const LayerW& L = c->layers[layer];
             if (fused) return launch_mlp_finish(mlp_args(c, layer), st);
-            a.W = HALF ? (const void*)L.w2_h : (const void*)L.w2; a.bias = L.b2; a.N = H; a.xin = kv.fbuf.p; a.out = kv.ypre.p; a.resid = kv.h1buf.p;
-            io.w_tiled = L.w2_t; io.x_image = kv.xt_f.p;
-            if (c->w8) io.w8 = L.w2_q;
-            if (c->w4) io.w4 = {true, c->w4_valid ? L.w2_s4 : nullptr, c->knobs.w4_rows};
-            io.w8_tiled = bytes_of(PROJ_FC2, L.w2_t8);
-            io.w4_batched = nib_on(PROJ_FC2); io.w4_tiled = nib_of(PROJ_FC2, L.w2_t4);
+            weights_of(PROJ_FC2); a.bias = L.b2; a.N = H; a.xin = kv.fbuf.p; a.out = kv.ypre.p; a.resid = kv.h1buf.p;
+            io.x_image = kv.xt_f.p;
             return run_proj<WT>(PROJ_FC2, form_of(PROJ_FC2, layer), io, a, B, I, sk, st);
         }
         case 6: {   // logits = lm_head LN2_last(ypre)
-            a.W = HALF ? (const void*)c->lm_head_h : (const void*)c->lm_head; a.bias = nullptr; a.N = g.vocab_size; a.xin = kv.ypre.p;
+            weights_of(PROJ_HEAD); a.bias = nullptr; a.N = g.vocab_size; a.xin = kv.ypre.p;
             a.ln_w = c->layers[p.layers - 1].ln2w; a.ln_b = c->layers[p.layers - 1].ln2b; a.hout = p.batched ? kv.hbuf.p : nullptr; a.out = kv.logits.p;
             io.pro = PRO_LN;
             return run_proj<WT>(PROJ_HEAD, form_of(PROJ_HEAD, layer), io, a, B, H, sk, st);
@@ -1156,9 +1084,7 @@ static int forward_check(er_ctx* c, const char* who, const float* embeds, int B,
 static int prefill_run(er_ctx* c, const float* embeds, int B, int S, hipStream_t st, int row0 = 0, bool in_queue = false) {
     HIPCHK(hipSetDevice(c->device));
     const DecodePlan& p = c->kv->plan;
-    if (p.mfma) ERCHK(make_tiled_weights(c, p));
-    ERCHK(make_w4_streams(c, p));
-    if (p.mlp_fused) ERCHK(make_kmajor_weights(c));
+    ERCHK(ensure_weight_copies(c, p));
     const er_config& g = c->cfg;
     const int H = g.hidden_dim, I = g.intermediate_dim, NH = g.num_heads, D = c->D;
     const int M = B * S;
@@ -1736,9 +1662,7 @@ extern "C" int er_queue_begin(er_ctx* c, const er_decode_params* p, int check_ev
     ERCHK(er_finalize_weights(c));
     HIPCHK(hipSetDevice(c->device));
     hipStream_t st = pick(c, stream);
-    if (c->kv->plan.mfma) ERCHK(make_tiled_weights(c, c->kv->plan));
-    ERCHK(make_w4_streams(c, c->kv->plan));
-    if (c->kv->plan.mlp_fused) ERCHK(make_kmajor_weights(c));
+    ERCHK(ensure_weight_copies(c, c->kv->plan));
     ERCHK(c->q_look.ensure((size_t)3 * B + 1));
     if (c->q_pinned) { hipHostFree(c->q_pinned); c->q_pinned = nullptr; }
     HIPCHK(hipHostMalloc((void**)&c->q_pinned, ((size_t)3 * B + 1) * sizeof(int), hipHostMallocDefault));
@@ -1962,20 +1886,15 @@ static int profile_impl(er_ctx* c, int repeats, int use_graph, float* avg_us, do
     bytes[5] = ((double)I * H + H) * w + (double)B * (I + 2 * H) * w;
     bytes[6] = ((double)V * H) * w + (double)B * (H + V) * w;
     bytes[7] = (double)B * V * w;
-    if (c->w8) {   // the row and matrix-core forms that stream bytes: 1 byte per weight + 4 per row scale in place of 2 per weight
+    {   // what the step streams packed in place of 2 bytes per weight (weight_source; row_class was cleared above) - bytes: 1 per weight + 4 per
+        // row scale; nibbles: half a byte per weight + a scale byte per 32 (the tiled copy: 4 bytes per 96).  The fused MLP's bytes are counted below.
         const auto less = [&](Proj proj, double n, double k) {
-            const bool bytes = p.batched ? plan_w8_batched(p, c->knobs, proj) : w8_streams(proj, B);
-            return bytes ? n * k * (w - 1.0) - n * 4.0 : 0.0;
-        };
-        bytes[0] -= less(PROJ_QKV, 3.0 * H, H);
-        bytes[3] -= less(PROJ_OUT, H, H);
-        bytes[4] -= less(PROJ_FC1, I, H);
-        bytes[5] -= less(PROJ_FC2, H, I);
-    }
-    if (c->w4) {   // the row and matrix-core forms that stream nibbles: half a byte per weight + a scale byte per 32 (the tiled copy: 4 bytes per 96) in place of 2 bytes per weight
-        const auto less = [&](Proj proj, double n, double k) {
-            if (p.batched) return plan_w4_batched(p, c->knobs, proj) ? n * k * w - (double)w4t::block_bytes((long long)n, (long long)k) : 0.0;
-            return plan_w4_rows(p, c->knobs, proj) ? n * k * (w - 0.5 - 1.0 / 32.0) : 0.0;
+            switch (weight_source(p, c->knobs, ctx_mode(c), false, proj, 0)) {
+                case WSRC_BYTES: case WSRC_TILED_BYTES: return n * k * (w - 1.0) - n * 4.0;
+                case WSRC_TILED_NIBBLES: return n * k * w - (double)w4t::block_bytes((long long)n, (long long)k);
+                case WSRC_QUADS: return n * k * (w - 0.5 - 1.0 / 32.0);
+                default: return 0.0;
+            }
         };
         bytes[0] -= less(PROJ_QKV, 3.0 * H, H);
         bytes[3] -= less(PROJ_OUT, H, H);
@@ -2056,8 +1975,8 @@ static int profile_impl(er_ctx* c, int repeats, int use_graph, float* avg_us, do
 // Their temporaries are local DevBufs: allocated before the first launch, and freed by every return path - behind the explicit
 // hipStreamSynchronize on the paths that launched something.
 // One projection on caller-owned operands in a batched form, as er_k_gemv and er_k_gemv_form run it.  It first gets what a decode context
-// keeps per reserved shape: rows for the prologue's output when the caller wants none back, the tiled copy of the weights (make_tiled),
-// the split-K block (a deferred form leaves its partials in part_out instead) and, for the wide tiled form, one zeroed image of
+// keeps per reserved shape: rows for the prologue's output when the caller wants none back, the derived copy of the weights that io.src
+// names (io.w comes in as what that copy is made of: launch_weight_copy), the split-K block (a deferred form leaves its partials in part_out instead) and, for the wide tiled form, one zeroed image of
 // K * 128 bytes per group of 32 rows unless the caller passed one.  Then run_proj - or, for ER_FORM_PREP, the prologue launch alone.
 template <typename WT>
 static int proj_entry(Proj proj, const ProjForm& f, ProjIo io, GemvArgs a, int B, int K, float* part_out, hipStream_t st) {
@@ -2065,13 +1984,12 @@ static int proj_entry(Proj proj, const ProjForm& f, ProjIo io, GemvArgs a, int B
     const size_t groups = (size_t)(B + NBM - 1) / NBM;
     const int slices = form == ER_FORM_NARROW || form == ER_FORM_NARROW_DEFER ? K / (4 * GM_KW) : K / (GM_WAVES * GM_KW);
     DevBuf<float> tmp, part;
-    DevBuf<char> wt, img;
+    DevBuf<char> wcopy, img;
     SkPart sk{nullptr, 0};
     hipError_t e = hipSuccess;
     if (form != ER_FORM_ROW && form != ER_FORM_ROWS8) {
         if (io.pro != PRO_NONE && !a.hout) { ERCHK(tmp.ensure((size_t)B * K)); a.hout = tmp.p; }
         if (form_mfma(form)) {
-            ERCHK(wt.ensure(tiled_weight_bytes<WT>(n, K)));
             if (form != ER_FORM_NARROW_DEFER) ERCHK(part.ensure((size_t)slices * NBM * n));
             sk = form == ER_FORM_NARROW_DEFER ? SkPart{part_out, groups * slices * NBM * (size_t)n} : SkPart{part.p, part.n};
         }
@@ -2083,10 +2001,11 @@ static int proj_entry(Proj proj, const ProjForm& f, ProjIo io, GemvArgs a, int B
             }
             io.x_image = io.pro_image;
         }
-        if (form_mfma(form)) {
-            e = launch_tile_weights<WT>(a.W, wt.p, n, K, st);
-            io.w_tiled = wt.p;
-        }
+    }
+    if (wsrc_derived(io.src) && form != ER_FORM_PREP) {
+        ERCHK(wcopy.ensure(weight_copy_bytes(io.src, sizeof(WT) == 2, n, K)));
+        e = launch_weight_copy(io.src, sizeof(WT) == 2, io.w, wcopy.p, n, K, st);
+        io.w = wcopy.p;
     }
     if (e == hipSuccess) e = form == ER_FORM_PREP ? launch_prologue(io.pro, a, B, io.rd, io.pro_image, st) : run_proj<WT>(proj, f, io, a, B, K, sk, st);
     hipError_t e2 = hipStreamSynchronize(st);
@@ -2101,7 +2020,7 @@ extern "C" int er_k_gemv(const float* w, const float* bias, const float* x, cons
                          const float* resid, float* y, float* xnorm_out, int B, int n, int k, int relu, float eps, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     GemvArgs a{};
-    a.W = w; a.bias = bias; a.N = n; a.xin = x; a.ln_w = ln_w; a.ln_b = ln_b; a.eps = eps; a.hout = xnorm_out;
+    a.bias = bias; a.N = n; a.xin = x; a.ln_w = ln_w; a.ln_b = ln_b; a.eps = eps; a.hout = xnorm_out;
     a.out = y; a.resid = resid;
     const bool batched = B > 4;
     if (batched && ln_w && k != 1536) return fail(ER_ERR_UNSUPPORTED, "er_k_gemv: LayerNorm prologue needs k=1536");
@@ -2118,9 +2037,10 @@ extern "C" int er_k_gemv(const float* w, const float* bias, const float* x, cons
     }
     const bool wide = proj == PROJ_FC1 || proj == PROJ_FC2;
     ProjIo io;
-    io.pro = ln_w ? PRO_LN : PRO_NONE;
+    io.pro = ln_w ? PRO_LN : PRO_NONE; io.w = w;
     if (batched) {   // matrix cores for the fc1- and fc2-shaped cases unless ER_BATCHED_VALU=1, the VALU kernel for the narrow ones
         const ProjForm f{wide && !env_is("ER_BATCHED_VALU", '1') ? ER_FORM_MFMA : ER_FORM_VALU, 0, 0, false};
+        io.src = form_mfma(f.form) ? WSRC_TILED : WSRC_PLAIN;
         return proj_entry<float>(proj, f, io, a, B, k, nullptr, st);
     }
     HIPRET(run_proj<float>(proj, ProjForm{ER_FORM_ROW, ER_NWAVES, wide ? 2 : 1, false}, io, a, B, k, SkPart{nullptr, 0}, st));
@@ -2292,10 +2212,11 @@ static int gemv_form_check(const er_k_gemv_form_args& f, Proj* proj_out) {
     return ER_OK;
 }
 
+// row / tiled: the source of f.w's family in a row form / a matrix-core form (f.w: the plain matrix, the byte block or the canonical MXFP4 block)
 template <typename WT>
-static int gemv_form_t(const er_k_gemv_form_args& f, Proj proj, hipStream_t st) {
+static int gemv_form_t(const er_k_gemv_form_args& f, Proj proj, hipStream_t st, WSrc row = WSRC_PLAIN, WSrc tiled = WSRC_TILED) {
     GemvArgs a{};
-    a.W = f.w; a.bias = f.bias; a.N = f.n; a.xin = f.x; a.ln_w = f.ln_w; a.ln_b = f.ln_b; a.eps = f.eps; a.hout = f.xnorm_out;
+    a.bias = f.bias; a.N = f.n; a.xin = f.x; a.ln_w = f.ln_w; a.ln_b = f.ln_b; a.eps = f.eps; a.hout = f.xnorm_out;
     a.embd = f.embd; a.posemb = f.posemb; a.tok = f.tok; a.pos = f.pos;
     a.out = f.y; a.resid = f.resid; a.q = f.q_out; a.kcache = f.kcache; a.vcache = f.vcache; a.kv_half = f.kv_half == 2 ? 2 : f.kv_half ? 1 : 0;
     a.hidden = f.form != ER_FORM_PREP && proj == PROJ_QKV ? f.heads * f.head_dim : 1536; a.head_dim = f.head_dim; a.l_cap = f.l_cap;
@@ -2304,6 +2225,7 @@ static int gemv_form_t(const er_k_gemv_form_args& f, Proj proj, hipStream_t st) 
     io.pro = f.prologue == ER_PRO_NONE ? PRO_NONE : f.prologue == ER_PRO_EMBED ? PRO_EMBED : PRO_LN;
     if (f.prologue == ER_PRO_LN_SK) io.rd = {f.sk_part, f.sk_bias, f.sk_resid, f.sk_slices};
     io.pro_image = f.prep_xt_out; io.x_image = f.x; io.out_image = f.xt_out;      // the narrow forms' x IS the tiled image
+    io.src = form_mfma(f.form) ? tiled : row; io.w = f.w;
     return proj_entry<WT>(proj, ProjForm{f.form, f.nw, f.rw, f.form == ER_FORM_NARROW_DEFER}, io, a, f.batch, f.k, f.part_out, st);
 }
 
@@ -2379,7 +2301,7 @@ extern "C" int er_k_gemv_form_w8(const er_k_gemv_form_args* f, const void* q_dev
     DevBuf<char> blk;
     ERCHK(w8_block_of(blk, q_dev, wscale_dev, g.n, g.k, st));
     g.w = blk.p;      // proj_entry tiles the block for the matrix-core forms (tile_weights_kernel<w8_t>) and synchronises before blk goes
-    return gemv_form_t<w8_t>(g, proj, st);
+    return gemv_form_t<_Float16>(g, proj, st, WSRC_BYTES, WSRC_TILED_BYTES);
 }
 
 // ---- fp4 mode on caller-owned operands: the block quantiser of the weight loader, the hardware conversion the nibble kernels read
@@ -2438,9 +2360,9 @@ extern "C" int er_k_w4_cvt_probe(float* out_dev, void* stream) {
 
 // er_k_gemv_form's checks on a canonical MXFP4 block in place of args->w (not read): ER_FORM_ROW of qkv, fc1 and fc2 with fp16 or e4m3
 // caches.  args names the fp16 row form the step would launch (w_half, nw, rw: checked like er_k_gemv_form's); the nibble kernel runs in
-// the projection's own nibble shape (er_decode_proj.h launch_proj_w4).  Builds the interleaved copy itself.  Also the four matrix-core
-// forms (ER_FORM_MFMA, _MFMA_XT, _NARROW, _NARROW_DEFER) of qkv, out_proj, fc1 and fc2, through er_k_gemv_form's own path: proj_entry
-// builds the tiled nibble copy (er_w4_tile_map.h) and launches gemv_mfma_kernel<w4_t>.  Everything else - ER_FORM_VALU, ER_FORM_ROWS8,
+// the projection's own nibble shape (er_decode_proj.h launch_proj_w4).  Also the four matrix-core forms (ER_FORM_MFMA, _MFMA_XT, _NARROW,
+// _NARROW_DEFER) of qkv, out_proj, fc1 and fc2.  Both go through er_k_gemv_form's own path: proj_entry builds the quad-interleaved or the
+// tiled nibble copy (er_w4_map.h, er_w4_tile_map.h) and run_proj launches the nibble kernels.  Everything else - ER_FORM_VALU, ER_FORM_ROWS8,
 // the lm_head - is refused before any launch.
 extern "C" int er_k_gemv_form_w4(const er_k_gemv_form_args* f, const void* block_dev, void* stream) {
     if (!f || !block_dev) return fail(ER_ERR_INVALID, "er_k_gemv_form_w4: null argument");
@@ -2454,29 +2376,13 @@ extern "C" int er_k_gemv_form_w4(const er_k_gemv_form_args* f, const void* block
     if (form_mfma(g.form)) {
         if (proj == PROJ_HEAD) return fail(ER_ERR_UNSUPPORTED, "er_k_gemv_form_w4: the lm_head has no nibble form");
         if (!w4t::shape_ok(g.n, g.k)) return fail(ER_ERR_UNSUPPORTED, "er_k_gemv_form_w4: k %d must be a multiple of %d", g.k, w4t::KW);
-        if (proj == PROJ_QKV && !g.kv_half) return fail(ER_ERR_UNSUPPORTED, "er_k_gemv_form_w4: fp4 weights go with an fp16 or an e4m3 cache, not fp32");
-        return gemv_form_t<w4_t>(g, proj, (hipStream_t)stream);      // proj_entry tiles the block (w4_tile_kernel) and synchronises
+    } else {
+        if (!w4_has_row_form(proj)) return fail(ER_ERR_UNSUPPORTED, "er_k_gemv_form_w4: %s has no nibble form", proj == PROJ_OUT ? "out_proj" : "the lm_head");
+        if (!w4map::shape_ok(g.n, g.k)) return fail(ER_ERR_UNSUPPORTED, "er_k_gemv_form_w4: n %d must be a multiple of 4 (rows are streamed in quads)", g.n);
     }
-    if (!w4_has_row_form(proj)) return fail(ER_ERR_UNSUPPORTED, "er_k_gemv_form_w4: %s has no nibble form", proj == PROJ_OUT ? "out_proj" : "the lm_head");
-    if (!w4map::shape_ok(g.n, g.k)) return fail(ER_ERR_UNSUPPORTED, "er_k_gemv_form_w4: n %d must be a multiple of 4 (rows are streamed in quads)", g.n);
     if (proj == PROJ_QKV && !g.kv_half) return fail(ER_ERR_UNSUPPORTED, "er_k_gemv_form_w4: fp4 weights go with an fp16 or an e4m3 cache, not fp32");
-    hipStream_t st = (hipStream_t)stream;
-    DevBuf<char> copy;
-    ERCHK(copy.ensure((size_t)w4map::stream_bytes(g.n, g.k)));
-    hipLaunchKernelGGL(w4_interleave_kernel, dim3(1024), dim3(ER_WG), 0, st, (const unsigned char*)block_dev, (unsigned char*)copy.p, (long long)g.n, g.k);
-    hipError_t e = hipGetLastError();
-    GemvArgs a{};
-    a.W = copy.p; a.bias = g.bias; a.N = g.n; a.xin = g.x; a.ln_w = g.ln_w; a.ln_b = g.ln_b; a.eps = g.eps; a.hout = g.xnorm_out;
-    a.embd = g.embd; a.posemb = g.posemb; a.tok = g.tok; a.pos = g.pos;
-    a.out = g.y; a.resid = g.resid; a.q = g.q_out; a.kcache = g.kcache; a.vcache = g.vcache; a.kv_half = g.kv_half == 2 ? 2 : g.kv_half ? 1 : 0;
-    a.hidden = proj == PROJ_QKV ? g.heads * g.head_dim : 1536; a.head_dim = g.head_dim; a.l_cap = g.l_cap;
-    a.kv_bstride = (long long)g.heads * g.l_cap * g.head_dim;
-    const int pro = g.prologue == ER_PRO_NONE ? PRO_NONE : g.prologue == ER_PRO_EMBED ? PRO_EMBED : PRO_LN;
-    if (e == hipSuccess) e = launch_proj_w4(proj, pro, a, g.batch, g.k, st);
-    hipError_t e2 = hipStreamSynchronize(st);
-    HIPRET(e);
-    HIPRET(e2);
-    return ER_OK;
+    // proj_entry interleaves (w4_interleave_kernel) or tiles (w4_tile_kernel) the block and synchronises
+    return gemv_form_t<_Float16>(g, proj, (hipStream_t)stream, WSRC_QUADS, WSRC_TILED_NIBBLES);
 }
 
 // ---- the fused single-row MLP on caller-owned operands.  er_k_mlp_transpose makes the k-major copy the decode context keeps per

@@ -1,7 +1,8 @@
 // Which kernels a reserved cache shape decodes with, and in which form each of its five projections is launched: the knobs, the plan
 // and the two functions launch_kind_t and the single-kernel entries take their decisions from.  Pure C++ with no device call
 // (csrc/er_queue_host.h is the precedent), so that the whole decision table can be enumerated by a stand-alone program
-// (tests/host/decode_plan_check.cpp).  csrc/er_decode_proj.h turns a (projection, form) into launches.
+// (tests/host/decode_plan_check.cpp).  csrc/er_weight_source.h decides, from the plan and the form, which copy of its matrix a projection
+// streams (weight_source: the one rule), and csrc/er_decode_proj.h turns a (projection, form, source) into launches.
 #pragma once
 #include "../../include/edgerunner_hip.h"
 
@@ -25,10 +26,10 @@ struct DecodeKnobs {          // the environment knobs of the decode step, read 
     // the prefix pass under prefix groups (env ER_PREFIX_PASS=valu|mfma at er_create, er_set_prefix_pass later): ER_PREFIX_PASS_VALU =
     // attn_prefix_kernel, ER_PREFIX_PASS_MFMA = attn_prefix_mfma_kernel where the plan qualifies (make_decode_plan: shared_mfma)
     int prefix_pass = ER_PREFIX_PASS_VALU;
-    // fp8 mode, matrix-core batched forms (env ER_W8_BATCHED): -1 = stream bytes where the measured rule says so (er_decode_proj.h
+    // fp8 mode, matrix-core batched forms (env ER_W8_BATCHED): -1 = stream bytes where the measured rule says so (er_weight_source.h
     // w8_streams_batched: qkv, fc1, fc2 at B > 4), 0 = the fp16 tiled copies everywhere, 1 = bytes in every matrix-core form
     int w8_batched = -1;
-    // fp4 mode, row forms (env ER_W4_ROWS): -1 = stream nibbles where the measured rule says so (er_decode_proj.h w4_streams), 0 = the
+    // fp4 mode, row forms (env ER_W4_ROWS): -1 = stream nibbles where the measured rule says so (er_w4_rule.h w4_streams), 0 = the
     // fp16 copies everywhere, 1 = nibbles in every row form that has one (qkv, fc1, fc2 at B <= 4)
     int w4_rows = -1;
     // fp4 mode, matrix-core batched forms (env ER_W4_BATCHED): -1 = stream nibbles where the measured rule says so (er_w4_rule.h

@@ -1,12 +1,12 @@
 // The launch table of the decode projections (qkv, out_proj, fc1, fc2, lm_head): the group loops over batch rows and launch_proj, the
 // ONLY function of the library that names a launcher with its template arguments for a decode projection.  The decode step
-// (launch_kind_t) and the two single-kernel entries (er_k_gemv, er_k_gemv_form) all get here through run_proj; which form a
-// projection takes is decided in csrc/er_decode_plan.h (proj_form), host-only.
+// (launch_kind_t) and the single-kernel entries (er_k_gemv, er_k_gemv_form and its _w8 / _w4 variants) all get here through run_proj.
+// Which form a projection takes (csrc/er_decode_plan.h proj_form) and which copy of its matrix it streams (csrc/er_weight_source.h
+// weight_source) are decided in host-only code; this file turns (projection, form, source) into launches and decides neither.
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include "er_decode_plan.h"
-#include "er_w4_rule.h"
+#include "er_weight_source.h"
 #include "k_gemv.h"
 #include "k_gemv_mfma.h"
 
@@ -114,65 +114,33 @@ static hipError_t prep_rows(const GemvArgs& a, int B, hipStream_t st) {
 }
 
 // ------------------------------------------------------------------------------------ the launch table
-// Projection `proj` in form `f` on the operands `a` (K = width of an input row).  The caller has pointed a.W at the tiled copy for the
-// matrix-core forms and a.xin at the tiled image for the tiled-input forms, and has run the batched forms' prologue (run_proj does all
+// Projection `proj` in form `f` on the operands `a` (K = width of an input row).  The caller has pointed a.W at the copy the source names
+// (WT is that copy's type) and a.xin at the tiled image for the tiled-input forms, and has run the batched forms' prologue (run_proj does all
 // three); pro names the prologue FUSED into the qkv row kernel (PRO_LN, or PRO_EMBED for layer 0; fc1 and lm_head always fuse PRO_LN).
 // Shapes: qkv 4608 rows = 192 VALU workgroups x 24 (one round) or 144 matrix-core tiles of 32; fc1 6144 rows = 256 x 24 or 192 tiles;
 // fc2 48 tiles x 4 (narrow: 16) K-ranges.  The XT kernels exist for fp16 weights only: their forms are compiled out for float.
 //
-// fp8 context (w8 = the byte block of the same matrix, k_gemv.h w8_scales; WT = _Float16 and a.W = the fp16 copy of the dequantised
-// values): a row form of a projection that w8_streams() names runs the same (waves x rows) shape of the byte kernel on w8, and a
-// matrix-core form of a projection that w8_streams_batched() names runs the same form of gemv_mfma_kernel<w8_t> on the tiled byte copy
-// (run_proj: io.w8_tiled); the VALU batched kernel, the eight-row out_proj and the lm_head run the fp16 copy as in fast mode.  The byte
-// type has the fp16 row shapes and the four matrix-core forms, nothing else.
+// Which copy of its matrix a projection streams is decided in csrc/er_weight_source.h (weight_source), host-only like the form; run_proj
+// maps the source to the kernel's weight type and nothing here asks a rule.
+//
+// fp8 context (WSRC_BYTES: the byte block of the matrix, k_gemv.h w8_scales; WSRC_TILED_BYTES: its tiled copy, er_w8_tile_map.h): a row
+// form runs the same (waves x rows) shape of the byte kernel, a matrix-core form the same form of gemv_mfma_kernel<w8_t>; the VALU batched
+// kernel, the eight-row out_proj and the lm_head run the fp16 copy as in fast mode.  The byte type has the fp16 row shapes and the four
+// matrix-core forms, nothing else.
 //
 // kv8 context (a.kv_half == 2: the KV cache holds e4m3 bytes): every QKV form - row, VALU, both matrix-core forms, with fp16 or byte
 // weights - is launched with EPI_QKV8, the epilogue that encodes (k_gemv.h); nothing else depends on the cache type.
-
-// Which projections of an fp8 context stream bytes in their row forms at B rows.  Measured in situ against the fp16 forms of the same
-// build in the same session (profiles/w8_bench.json): a projection streams bytes only where its byte form is faster
-// by more than the run-to-run spread of the fp16 runs.  qkv, fc1 and fc2 are at B = 1, 2 and 4; out_proj is at B = 1 (the fused merge
-// launch) and 2, and is not at B = 4 (4.10 against 4.15 us, spread 0.18) - B = 3 was not measured and goes with 4.
-constexpr bool w8_streams(Proj proj, int B) {
-    return proj == PROJ_QKV || proj == PROJ_FC1 || proj == PROJ_FC2 || (proj == PROJ_OUT && B <= 2);
-}
-// The same question for the matrix-core forms (ER_FORM_MFMA, _MFMA_XT, _NARROW, _NARROW_DEFER) of a batch of B rows.  knob = ER_W8_BATCHED
-// as er_create read it: 0 = the fp16 tiled copies everywhere, 1 = bytes in every matrix-core form, anything else = the measured rule.
-// The rule, by the criterion above (profiles/w8_batched_bench.json, scripts/bench_w8_batched.py: fp16 and byte caches, B = 8, 16, 32;
-// DESIGN.md section 4): qkv, fc1 and fc2 are faster beyond the fp16 spread in all six cases (0.65 - 1.36 us of 5.6 - 12.1); out_proj is
-// not - its 0.04 - 0.31 us of 3.2 - 4.0 are inside the spread in three of the four cases it has a matrix-core form in - and keeps the fp16 copy.
-// Batches other than 8, 16 and 32 were not measured: they launch the same two instantiations per form (one batch half up to 16 rows, two
-// up to 32, groups of 32 above that) and go with them; B <= 4 gets here under ER_FORCE_BATCHED=1 only and keeps the fp16 copies.
-constexpr bool w8_streams_batched(Proj proj, int B, int knob) {
-    if (proj == PROJ_HEAD || knob == 0) return false;
-    if (knob == 1) return true;
-    return B > 4 && (proj == PROJ_QKV || proj == PROJ_FC1 || proj == PROJ_FC2);
-}
-// ... and for the stored plan of an fp8 context: does the step stream `proj` as bytes?  (fc2's two tiled forms are both matrix-core forms,
-// so the layer does not matter.)
-inline bool plan_w8_batched(const DecodePlan& p, const DecodeKnobs& k, Proj proj) {
-    return proj != PROJ_HEAD && form_mfma(proj_form(p, k, true, proj, 0).form) && w8_streams_batched(proj, p.B, k.w8_batched);
-}
-
-// fp4 context (w4 = the streamed nibble copy of the same matrix, er_w4_map.h; WT = _Float16 and a.W = the fp16 copy of the dequantised
-// values): a row form of a projection that w4_streams() names runs the nibble kernel on w4 in the projection's OWN nibble shape - a wave
-// owns whole row quads, so the (waves x rows) of the fp16 form do not carry over:
+//
+// fp4 context (WSRC_QUADS: the quad-interleaved nibble copy of the matrix, er_w4_map.h): a row form runs the nibble kernel in the
+// projection's OWN nibble shape - a wave owns whole row quads, so the (waves x rows) of the fp16 form do not carry over:
 //     qkv  4 waves x 4 rows        = 288 workgroups for 4608 rows
 //     fc1  6 waves x 4 rows        = 256 workgroups for 6144 rows
 //     fc2  4 K-slices x 4 rows     = 384 workgroups for 1536 rows
 // (qkv with 6 waves and fc1 with 4 were measured too and lost: DESIGN.md section 4).  Both keep the four-wave prologue (gemv_kernel: PW),
 // so the LayerNorm'd input - and with fp16's lane -> element map, fmaf chain and butterfly every output - is the fp16 form's bit for
-// bit.  A matrix-core form (ER_FORM_MFMA, _MFMA_XT, _NARROW, _NARROW_DEFER) of qkv, out_proj, fc1 or fc2 that w4_streams_batched() names
-// runs the same form of gemv_mfma_kernel<w4_t> on the tiled nibble copy (er_w4_tile_map.h; run_proj: io.w4_tiled).  The single-row
-// out_proj (the fused merge launch included), the lm_head, the VALU batched kernel, the eight-row out_proj and the fused sparse MLP have
-// no nibble form and run the fp16 copy.
-// w4_has_row_form(proj), w4_streams(proj, B, knob) - which projections of an fp4 context stream nibbles in their row forms at B rows -
-// and w4_streams_batched(proj, B, knob) - the same question for the matrix-core forms - are host-only code in er_w4_rule.h, so that
-// tests/host/w4_map_check.cpp and tests/host/w4_tile_check.cpp can enumerate them.
-// ... and for the stored plan of an fp4 context: does the step stream `proj` as nibbles in a matrix-core form?  (plan_w8_batched's remark.)
-inline bool plan_w4_batched(const DecodePlan& p, const DecodeKnobs& k, Proj proj) {
-    return proj != PROJ_HEAD && form_mfma(proj_form(p, k, true, proj, 0).form) && w4_streams_batched(proj, p.B, k.w4_batched);
-}
+// bit.  A matrix-core form (ER_FORM_MFMA, _MFMA_XT, _NARROW, _NARROW_DEFER) of qkv, out_proj, fc1 or fc2 on WSRC_TILED_NIBBLES runs the
+// same form of gemv_mfma_kernel<w4_t> on the tiled nibble copy (er_w4_tile_map.h).  The single-row out_proj (the fused merge launch
+// included), the lm_head, the VALU batched kernel, the eight-row out_proj and the fused sparse MLP have no nibble form.
 
 // the nibble row form of `proj` on the streamed copy a.W; a.kv_half names the cache type
 static hipError_t launch_proj_w4(Proj proj, int pro, const GemvArgs& a, int B, int K, hipStream_t st) {
@@ -193,30 +161,12 @@ static hipError_t launch_proj_w4(Proj proj, int pro, const GemvArgs& a, int B, i
     return hipErrorInvalidValue;
 }
 
-// fp4 context (on): the streamed copy of the projection's matrix - null while the copies do not match the loaded weights - and the
-// ER_W4_ROWS knob
-struct W4Io { bool on = false; const void* w = nullptr; int knob = -1; };
-
 template <typename WT>
-static hipError_t launch_proj(Proj proj, const ProjForm& f, int pro, const GemvArgs& a, int B, int K, SkPart sk, hipStream_t st, const void* w8 = nullptr,
-                              const W4Io& w4 = W4Io{}) {
+static hipError_t launch_proj(Proj proj, const ProjForm& f, int pro, const GemvArgs& a, int B, int K, SkPart sk, hipStream_t st) {
     constexpr bool W4 = WTraits<WT>::NIBBLES, W8 = WTraits<WT>::E4M3 || W4, HALF = sizeof(WT) <= 2;      // W8: a packed type (bytes or nibbles) - matrix-core forms only among the batched ones
     if (W8 && proj == PROJ_HEAD) return hipErrorInvalidValue;      // the lm_head is not quantised
     if (W4 && !form_mfma(f.form)) return hipErrorInvalidValue;     // the tiled nibble copy has the four matrix-core forms, nothing else (the row forms: launch_proj_w4)
     if (W4 && proj == PROJ_QKV && a.kv_half == 0) return hipErrorInvalidValue;      // fp4 weights go with an fp16 or a byte cache
-    if constexpr (sizeof(WT) == 2) {
-        if (w4.on && f.form == ER_FORM_ROW && w4_streams(proj, B, w4.knob)) {
-            if (!w4.w) return hipErrorInvalidValue;      // the plan streams nibbles and the copy is not there: an error, never the fp16 copy quietly
-            GemvArgs b = a;
-            b.W = w4.w;
-            return launch_proj_w4(proj, pro, b, B, K, st);
-        }
-        if (w8 && f.form == ER_FORM_ROW && w8_streams(proj, B)) {
-            GemvArgs b = a;
-            b.W = w8;
-            return launch_proj<w8_t>(proj, f, pro, b, B, K, sk, st);
-        }
-    }
     if constexpr (!W4) switch (f.form) {
         case ER_FORM_ROW:
             switch (proj) {
@@ -319,44 +269,39 @@ static hipError_t launch_prologue(int pro, GemvArgs& a, int B, const SkRead& rd,
     return e;
 }
 
-// What a projection launches with beside the GemvArgs of its row-major form (`a` of run_proj: plain weights, row-major input)
+// What a projection launches with beside the GemvArgs of its row-major form (`a` of run_proj: row-major input; a.W is not read)
 struct ProjIo {
     int pro = PRO_NONE;               // PRO_LN / PRO_EMBED: fused into the row kernels, launch_prologue in front of the batched forms
     SkRead rd;                        // ... which then also finishes the previous producer's partials
     void* pro_image = nullptr;        // ... and writes the tiled image of its rows
-    const void* w_tiled = nullptr;    // the weights as the matrix-core forms stream them (tile_weights_kernel)
     const void* x_image = nullptr;    // the input as the tiled-input forms read it
     void* out_image = nullptr;        // fc1, ER_FORM_MFMA_XT: the tiled image of the output
-    const void* w8 = nullptr;         // fp8 context: the byte block of the same matrix (launch_proj decides who streams it)
-    const void* w8_tiled = nullptr;   // fp8 context whose plan streams this projection's matrix-core form as bytes: the tiled byte copy (er_w8_tile_map.h)
-    bool w4_batched = false;          // fp4 context whose plan streams this projection's matrix-core form as nibbles ...
-    const void* w4_tiled = nullptr;   // ... and the tiled nibble copy (er_w4_tile_map.h); null while it does not match the loaded weights: the launch fails
-    W4Io w4;                          // fp4 context: the streamed nibble copy of the same matrix (launch_proj decides who streams it)
+    WSrc src = WSRC_PLAIN;            // the copy of the matrix this launch streams (weight_source; the unit entries: the caller's word) ...
+    const void* w = nullptr;          // ... and where it is; null while that copy does not match the loaded weights: the launch fails
 };
 
-// (projection, form) -> launches: the prologue launch of a batched form, the operands the form reads, launch_proj.
+// (projection, form, source) -> launches: the prologue launch of a batched form, the operands the form reads, and launch_proj in the
+// weight type of the source - WT (float or _Float16) for the plain and the tiled copy, w8_t for the bytes, w4_t for the nibbles.
 template <typename WT>
 static hipError_t run_proj(Proj proj, const ProjForm& f, const ProjIo& io, GemvArgs a, int B, int K, SkPart sk, hipStream_t st) {
-    const bool nibbles = sizeof(WT) == 2 && form_mfma(f.form) && io.w4_batched;
-    // the plan streams nibbles and the copy is not there: an error in front of every launch, never the fp16 copy quietly
-    if (nibbles && (!io.w4_tiled || !w4t::shape_ok(a.N, K))) return hipErrorInvalidValue;
+    // the copy the source names is not there: an error in front of every launch, never the fp16 copy quietly
+    if (!io.w || io.src == WSRC_KMAJOR || wsrc_tiled(io.src) != form_mfma(f.form)) return hipErrorInvalidValue;
+    if ((wsrc_bytes(io.src) || wsrc_nibbles(io.src)) && sizeof(WT) != 2) return hipErrorInvalidValue;      // the packed copies stand in for fp16
+    if (io.src == WSRC_TILED_NIBBLES && !w4t::shape_ok(a.N, K)) return hipErrorInvalidValue;
     if (io.pro != PRO_NONE && form_batched(f.form)) {
         const hipError_t e = launch_prologue(io.pro, a, B, io.rd, io.pro_image, st);
         if (e != hipSuccess) return e;
     }
-    if (nibbles) {
-        a.W = io.w4_tiled;
-        if (form_tiled_in(f.form)) a.xin = (const float*)io.x_image;
-        if (f.form == ER_FORM_MFMA_XT && proj == PROJ_FC1) a.xt_out = io.out_image;
-        return launch_proj<w4_t>(proj, f, io.pro, a, B, K, sk, st);
-    }
-    const bool bytes = sizeof(WT) == 2 && form_mfma(f.form) && io.w8_tiled;
-    if (form_mfma(f.form)) a.W = bytes ? io.w8_tiled : io.w_tiled;
-    if (form_mfma(f.form) && !a.W) return hipErrorInvalidValue;      // the tiled copy this plan streams has not been made
+    a.W = io.w;
     if (form_tiled_in(f.form)) a.xin = (const float*)io.x_image;
     if (f.form == ER_FORM_MFMA_XT && proj == PROJ_FC1) a.xt_out = io.out_image;
-    if (bytes) return launch_proj<w8_t>(proj, f, io.pro, a, B, K, sk, st);
-    return launch_proj<WT>(proj, f, io.pro, a, B, K, sk, st, io.w8, io.w4);
+    switch (io.src) {
+        case WSRC_QUADS: return f.form == ER_FORM_ROW ? launch_proj_w4(proj, io.pro, a, B, K, st) : hipErrorInvalidValue;
+        case WSRC_TILED_NIBBLES: return launch_proj<w4_t>(proj, f, io.pro, a, B, K, sk, st);
+        case WSRC_BYTES: return f.form == ER_FORM_ROW ? launch_proj<w8_t>(proj, f, io.pro, a, B, K, sk, st) : hipErrorInvalidValue;
+        case WSRC_TILED_BYTES: return launch_proj<w8_t>(proj, f, io.pro, a, B, K, sk, st);
+        default: return launch_proj<WT>(proj, f, io.pro, a, B, K, sk, st);
+    }
 }
 
 }   // namespace er

@@ -1,6 +1,6 @@
 // The launch rules of fp4 mode (er_w4.h): which decode projections stream e2m1 nibbles in their row forms (w4_streams) and in their
-// matrix-core batched forms (w4_streams_batched).  Pure constexpr C++ with no device call, included by er_decode_proj.h (whose launch_proj
-// and run_proj ask it) and enumerated on the host by tests/host/w4_map_check.cpp and tests/host/w4_tile_check.cpp.
+// matrix-core batched forms (w4_streams_batched).  Pure constexpr C++ with no device call, included by er_weight_source.h (whose weight_source
+// alone asks it) and enumerated on the host by tests/host/w4_map_check.cpp and tests/host/w4_tile_check.cpp.
 #pragma once
 #include "er_decode_plan.h"
 
@@ -31,7 +31,7 @@ constexpr bool w4_streams(Proj proj, int B, int knob = -1) {
 //     fc1       8.63 - 11.19 -> 7.27 -  9.68    1.35 - 1.88 us faster, spread 0.01 - 0.31:     in all six cases
 //     fc2       5.64 -  7.83 -> 4.09 -  6.19    1.55 - 1.96 us faster, spread 0.01 - 0.03:     in all six cases
 //     out_proj  3.30 -  3.84 -> 3.02 -  3.67    0.17 - 0.36 us faster, spread 0.05 - 0.20:     in the four cases (B = 16, 32) in which it
-//               has a matrix-core form - at B = 8 it is the eight-row VALU pass on the fp16 copy in both contexts (plan_w4_batched says no)
+//               has a matrix-core form - at B = 8 it is the eight-row VALU pass on the fp16 copy in both contexts (weight_source says plain)
 // So the rule is all four projections at every B > 4, the same set as ER_W4_BATCHED=1.  The fp8 forms of the same session: qkv 8.59 - 11.18,
 // fc1 7.67 - 10.10, fc2 4.50 - 6.54, out_proj (fp16 copy under fp8 mode's rule) 3.23 - 4.41 - the nibble forms are 0.2 - 0.8 us below them.
 // Batches other than 8, 16 and 32 were not measured: they launch the same two instantiations per form (one batch half up to 16 rows, two

@@ -302,7 +302,7 @@ def test_knob_0_keeps_the_fp16_copies():
 
 @pytest.mark.parametrize("B", [8, 17])
 def test_default_rule_streams_qkv_fc1_fc2(B):
-    """ER_W8_BATCHED unset: what profiles/w8_batched_bench.json supports (csrc/er_decode_proj.h w8_streams_batched) - out_proj keeps fp16."""
+    """ER_W8_BATCHED unset: what profiles/w8_batched_bench.json supports (csrc/er_weight_source.h w8_streams_batched) - out_proj keeps fp16."""
     assert_context_pair(model("fp16"), model("fp8"), B, dict(ALL, out_proj=0))
 
 
