@@ -30,6 +30,7 @@
 #include "k_gemv_mfma.h"
 #include "k_head.h"
 #include "k_rowops.h"
+#include "k_dit.h"
 #include "k_score.h"
 #include "k_flash_attn.h"
 #include "k_flash_attn_f32.h"
@@ -843,8 +844,7 @@ static int linear_hs(er_ctx* c, const float* A, int lda, const _Float16* W, cons
     ERCHK(c->p_hi.ensure((size_t)M * K + F16_TAIL));
     ERCHK(c->p_lo.ensure((size_t)M * K + F16_TAIL));
     _Float16 *hi = c->p_hi.p, *lo = c->p_lo.p;
-    hipLaunchKernelGGL(split_rows_f16_kernel, split_rows_grid(M, K), dim3(ER_WG), 0, st, A, hi, lo, (long long)M, K, lda);
-    HIPRET(hipGetLastError());
+    HIPRET(launch_split_rows_f16(A, hi, lo, (long long)M, K, lda, st));
     GemmArgs g = gemm_args_linear(hi, K, W, bias, C, ldc, M, N, K, relu, resid, ldr);
     g.a_lo = lo;
     HIPRET(launch_gemm_hh_split(g, st));
@@ -912,9 +912,7 @@ static int point_latent_chunk(PointEnc& p, const float* pts, int nb, int N, hipS
         HIPRET(launch_fps(pts, nb, N, Lq, fidx, p.fdist.p, st));
     }
     // x = ln(point_embed(pts))                                          point.py:194
-    hipLaunchKernelGGL(point_embed_kernel, dim3(ew_grid((long long)R * p.kpad)), dim3(ER_WG), 0, st, pts,
-                       p.basis, p.a0.p, (long long)R, p.freq, p.kpad);
-    HIPRET(hipGetLastError());
+    HIPRET(launch_point_embed(pts, p.basis, p.a0.p, (long long)R, p.freq, p.kpad, st));
     HIPRET(linear(p.a0.p, p.kpad, p.mlp_w, p.mlp_b, p.x.p, PH, (int)R, PH, p.kpad, false, nullptr, 0, st));
     if (ds) {   // q = point_embed(pc[fps_indices]): the sampled rows of the point_embed output, before ln      point.py:157-158
         hipLaunchKernelGGL(fps_gather_rows_kernel, dim3((unsigned)RQ), dim3(ER_WG), 0, st, p.x.p, fidx, N, Lq, PH, p.q0.p);
@@ -952,9 +950,7 @@ static int point_latent_chunk(PointEnc& p, const float* pts, int nb, int N, hipS
     // l = l + net2(GEGLU(net0(ln2(l))))                                   point.py:125, 68-84
     HIPRET(launch_layernorm(p.l.p, p.ca_ln2_w, p.ca_ln2_b, p.ln.p, (int)RQ, PH, PH, PH, p.eps, st));
     HIPRET(linear(p.ln.p, PH, p.ff0_w, p.ff0_b, p.u.p, 8 * PH, (int)RQ, 8 * PH, PH, false, nullptr, 0, st));
-    hipLaunchKernelGGL(geglu_kernel, dim3(ew_grid((long long)RQ * 4 * PH)), dim3(ER_WG), 0, st, p.u.p, p.g.p,
-                       (long long)RQ, 4 * PH);
-    HIPRET(hipGetLastError());
+    HIPRET(launch_geglu(p.u.p, p.g.p, (long long)RQ, 4 * PH, st));
     HIPRET(linear(p.g.p, 4 * PH, p.ff2_w, p.ff2_b, p.l.p, PH, (int)RQ, PH, 4 * PH, false, p.l.p, PH, st));
     // latent mean = linear(l)                                              point.py:201
     HIPRET(linear(p.l.p, PH, p.lin_w, p.lin_b, p.lat.p, LD, (int)RQ, LD, PH, false, nullptr, 0, st));
@@ -1026,8 +1022,7 @@ extern "C" int er_embed_tokens(er_ctx* c, const int32_t* ids, int B, int R, floa
     ERCHK(c->e_ids.ensure((size_t)n));
     int* d_ids = c->e_ids.p;
     HIPCHK(hipMemcpyAsync(d_ids, ids, (size_t)n * sizeof(int), hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(gather_rows_kernel, dim3(n), dim3(ER_WG), 0, st, c->embd, d_ids, out, n, H, (long long)H);
-    HIPRET(hipGetLastError());
+    HIPRET(launch_gather_rows(c->embd, d_ids, out, n, H, (long long)H, st));
     HIPCHK(hipStreamSynchronize(st));     // `ids` is caller-owned host memory
     return ER_OK;
 }
@@ -1106,8 +1101,7 @@ static int prefill_run(er_ctx* c, const float* embeds, int B, int S, hipStream_t
     }
 
     // hidden = inputs_embeds + pos_embeds(0..S)                       modeling_opt.py:355-357
-    hipLaunchKernelGGL(add_pos_kernel, dim3(ew_grid((long long)M * H / 4)), dim3(ER_WG), 0, st, embeds, c->posemb, h, B, S, H, 0);
-    HIPRET(hipGetLastError());
+    HIPRET(launch_add_pos(embeds, c->posemb, h, B, S, H, 0, st));
     for (int l = 0; l < g.num_layers; ++l) {
         const LayerW& L = c->layers[l];
         char* kc = c->kv->kc.p + ((long long)l * p.kv_lstride + (long long)row0 * p.kv_bstride) * c->kv_esz;
@@ -1136,13 +1130,8 @@ static int prefill_run(er_ctx* c, const float* embeds, int B, int S, hipStream_t
             ERCHK(c->p_qkv.ensure((size_t)M * 3 * H));
             float* qkv = c->p_qkv.p;
             ERCHK(linear_hs(c, h, H, L.wqkv_h, L.bqkv, qkv, 3 * H, M, 3 * H, H, false, nullptr, 0, st));
-            if (c->kv8)      // kv8: bytes into the cache, decode(encode(v)) back into the scratch
-                hipLaunchKernelGGL(kv_scatter_f8_kernel, kv_scatter_grid(M, H), dim3(ER_WG), 0, st, qkv,
-                                   (unsigned char*)kc, (unsigned char*)vc, M, S, H, D, p.Lcap, p.kv_bstride);
-            else
-                hipLaunchKernelGGL(kv_scatter_half_kernel, kv_scatter_grid(M, H), dim3(ER_WG), 0, st, qkv,
-                                   (_Float16*)kc, (_Float16*)vc, M, S, H, D, p.Lcap, p.kv_bstride);
-            HIPRET(hipGetLastError());
+            // (kv8: bytes into the cache, decode(encode(v)) back into the scratch)
+            HIPRET(launch_kv_scatter(qkv, kc, vc, c->kv8, M, S, H, D, p.Lcap, p.kv_bstride, st));
             {
                 Flash32Args f{};
                 f.Q = qkv; f.ldq = 3 * H; f.qs_b = (long long)S * 3 * H; f.qs_h = D;
@@ -2579,7 +2568,7 @@ extern "C" int er_k_gemm_f16s(const float* a, const void* w, const float* bias, 
         DevBuf<_Float16> hi, lo;
         ERCHK(hi.ensure((size_t)m * k));
         ERCHK(lo.ensure((size_t)m * k));
-        hipLaunchKernelGGL(split_rows_f16_kernel, split_rows_grid(m, k), dim3(ER_WG), 0, st, a, hi.p, lo.p, (long long)m, k, lda);
+        HIPRET(launch_split_rows_f16(a, hi.p, lo.p, (long long)m, k, lda, st));
         g.A = reinterpret_cast<const float*>(hi.p); g.a_lo = lo.p; g.lda = k;
         return gemm_sync_report(launch_gemm_hh_split(g, st), st);
     }
@@ -2661,6 +2650,142 @@ extern "C" int er_k_layernorm(const float* x, const float* w, const float* b, fl
 
 extern "C" int er_k_softmax(float* s, int rows, int cols, int ld, int causal, void* stream) {
     HIPRET(launch_softmax_rows(s, rows, cols, (long long)ld, ld, 0LL, 1, causal, 0, (hipStream_t)stream));
+    return ER_OK;
+}
+
+extern "C" int er_k_softmax_batched(float* s, int rows, int cols, long long ld, int ld_pad, int batch, long long batch_stride, int causal,
+                                    int causal_off, void* stream) {
+    if (!s || rows < 1 || cols < 1 || ld_pad < cols || ld < ld_pad || batch < 1 || batch > 65535 || causal_off < 0 ||
+        (batch > 1 && batch_stride < (long long)rows * ld))
+        return fail(ER_ERR_INVALID, "er_k_softmax_batched: bad argument");
+    HIPRET(launch_softmax_rows(s, rows, cols, ld, ld_pad, batch_stride, batch, causal ? 1 : 0, causal_off, (hipStream_t)stream));
+    return ER_OK;
+}
+
+// ---- the once-per-sample row, element-wise and K/V scatter kernels (k_rowops.h, k_dit.h, k_gemm.h split_rows_f16_kernel) through the
+// launchers the prefill, the point encoder, the CLIP front and the DiT sampler call.  Every entry refuses before it launches.
+extern "C" int er_k_kv_scatter(float* qkv, void* kcache, void* vcache, int kv_half, int m, int s, int hidden, int head_dim, int l_cap,
+                               long long kv_bstride, void* stream) {
+    if (!qkv || !kcache || !vcache || (kv_half != 1 && kv_half != 2) || m < 1 || s < 1 || m % s || s > l_cap || hidden < 4 || hidden % 4 ||
+        head_dim < 4 || head_dim % 4 || hidden % head_dim || kv_bstride % 4 || kv_bstride < (long long)hidden * l_cap)
+        return fail(ER_ERR_INVALID, "er_k_kv_scatter: bad argument");
+    HIPRET(launch_kv_scatter(qkv, kcache, vcache, kv_half == 2, m, s, hidden, head_dim, l_cap, kv_bstride, (hipStream_t)stream));
+    return ER_OK;
+}
+
+extern "C" int er_k_split_rows_f16(const float* x, void* hi, void* lo, long long rows, int cols, int ldx, void* stream) {
+    if (!x || !hi || !lo || rows < 1 || cols < 4 || cols % 4 || ldx < cols || ldx % 4)
+        return fail(ER_ERR_INVALID, "er_k_split_rows_f16: bad argument");
+    HIPRET(launch_split_rows_f16(x, (_Float16*)hi, (_Float16*)lo, rows, cols, ldx, (hipStream_t)stream));
+    return ER_OK;
+}
+
+extern "C" int er_k_add_pos(const float* emb, const float* pos, float* out, int batch, int s, int c, int pos0, void* stream) {
+    if (!emb || !pos || !out || batch < 1 || s < 1 || c < 4 || c % 4 || pos0 < 0) return fail(ER_ERR_INVALID, "er_k_add_pos: bad argument");
+    HIPRET(launch_add_pos(emb, pos, out, batch, s, c, pos0, (hipStream_t)stream));
+    return ER_OK;
+}
+
+extern "C" int er_k_gather_rows(const float* table, int table_rows, const int32_t* ids_host, float* out, int rows, int c, long long ldo,
+                                void* stream) {
+    if (!table || !ids_host || !out || table_rows < 1 || rows < 1 || c < 1 || ldo < c) return fail(ER_ERR_INVALID, "er_k_gather_rows: bad argument");
+    for (int i = 0; i < rows; ++i)
+        if (ids_host[i] < 0 || ids_host[i] >= table_rows) return fail(ER_ERR_INVALID, "er_k_gather_rows: id %d out of range", ids_host[i]);
+    hipStream_t st = (hipStream_t)stream;
+    DevBuf<int> ids;
+    ERCHK(ids.ensure((size_t)rows));
+    HIPCHK(hipMemcpyAsync(ids.p, ids_host, (size_t)rows * sizeof(int), hipMemcpyHostToDevice, st));
+    hipError_t e = launch_gather_rows(table, ids.p, out, rows, c, ldo, st);
+    hipError_t e2 = hipStreamSynchronize(st);      // ids is freed on return
+    HIPRET(e);
+    HIPRET(e2);
+    return ER_OK;
+}
+
+extern "C" int er_k_point_embed(const float* pts, const float* basis, float* out, long long m, int f, int ldo, void* stream) {
+    if (!pts || !basis || !out || m < 1 || f < 1 || ldo < 2 * f + 3) return fail(ER_ERR_INVALID, "er_k_point_embed: bad argument");
+    HIPRET(launch_point_embed(pts, basis, out, m, f, ldo, (hipStream_t)stream));
+    return ER_OK;
+}
+
+extern "C" int er_k_geglu(const float* u, float* out, long long rows, int f, void* stream) {
+    if (!u || !out || rows < 1 || f < 1) return fail(ER_ERR_INVALID, "er_k_geglu: bad argument");
+    HIPRET(launch_geglu(u, out, rows, f, (hipStream_t)stream));
+    return ER_OK;
+}
+
+extern "C" int er_k_gelu(const float* x, float* y, long long n, void* stream) {
+    if (!x || !y || n < 1) return fail(ER_ERR_INVALID, "er_k_gelu: bad argument");
+    HIPRET(launch_gelu(x, y, n, (hipStream_t)stream));
+    return ER_OK;
+}
+
+extern "C" int er_k_silu(const float* x, float* y, long long n, void* stream) {
+    if (!x || !y || n < 1) return fail(ER_ERR_INVALID, "er_k_silu: bad argument");
+    HIPRET(launch_silu(x, y, n, (hipStream_t)stream));
+    return ER_OK;
+}
+
+extern "C" int er_k_ln_modulate(const float* x, float* y, int rows, int rows_per_batch, int cols, const float* table, const float* tvec,
+                                long long t_bstride, long long t_cstride, int shift_idx, int scale_idx, void* y16, void* stream) {
+    if (!x || !y || !table || !tvec || rows < 1 || rows_per_batch < 1 || rows % rows_per_batch || t_bstride < 0 || t_bstride % 4 ||
+        t_cstride < 0 || t_cstride % 4 || shift_idx < 0 || scale_idx < 0)
+        return fail(ER_ERR_INVALID, "er_k_ln_modulate: bad argument");
+    if (cols != 1024) return fail(ER_ERR_INVALID, "er_k_ln_modulate: width %d (1024)", cols);
+    HIPRET(dit_ln_mod(x, y, rows, rows_per_batch, table, tvec, t_bstride, t_cstride, shift_idx, scale_idx, (hipStream_t)stream, (_Float16*)y16));
+    return ER_OK;
+}
+
+extern "C" int er_k_adaln_gate(const float* table, const float* tada, float* out, int batch, int c, int idx, void* stream) {
+    if (!table || !tada || !out || batch < 1 || c < 1 || idx < 0 || idx > 5) return fail(ER_ERR_INVALID, "er_k_adaln_gate: bad argument");
+    HIPRET(launch_adaln_gate(table, tada, out, batch, c, idx, (hipStream_t)stream));
+    return ER_OK;
+}
+
+extern "C" int er_k_adaln_gate_all(const float* const* tables_host, const float* tada, float* out, int layers, int batch, int c, void* stream) {
+    if (!tables_host || !tada || !out || layers < 1 || batch < 1 || c < 1) return fail(ER_ERR_INVALID, "er_k_adaln_gate_all: bad argument");
+    for (int l = 0; l < layers; ++l)
+        if (!tables_host[l]) return fail(ER_ERR_INVALID, "er_k_adaln_gate_all: null table %d", l);
+    hipStream_t st = (hipStream_t)stream;
+    DevBuf<const float*> tabs;
+    ERCHK(tabs.ensure((size_t)layers));
+    HIPCHK(hipMemcpyAsync(tabs.p, tables_host, (size_t)layers * sizeof(float*), hipMemcpyHostToDevice, st));
+    hipError_t e = launch_adaln_gate_all(tabs.p, tada, out, layers, batch, c, st);
+    hipError_t e2 = hipStreamSynchronize(st);      // tabs is freed on return
+    HIPRET(e);
+    HIPRET(e2);
+    return ER_OK;
+}
+
+extern "C" int er_k_timestep_embed(const float* t, float* out, int batch, int half, void* stream) {
+    if (!t || !out || batch < 1 || half < 1) return fail(ER_ERR_INVALID, "er_k_timestep_embed: bad argument");
+    HIPRET(launch_timestep_embed(t, out, batch, half, (hipStream_t)stream));
+    return ER_OK;
+}
+
+extern "C" int er_k_ddim_cfg_step(float* latents, const float* pred, long long n, int prediction_type, float guidance, float sa_t,
+                                  float sb_t, float sa_p, float sb_p, void* stream) {
+    if (!latents || !pred || n < 1 || (prediction_type != ER_PRED_V_PREDICTION && prediction_type != ER_PRED_EPSILON))
+        return fail(ER_ERR_INVALID, "er_k_ddim_cfg_step: bad argument");
+    HIPRET(launch_ddim_cfg_step(prediction_type == ER_PRED_EPSILON, latents, pred, n, guidance, sa_t, sb_t, sa_p, sb_p, (hipStream_t)stream));
+    return ER_OK;
+}
+
+extern "C" int er_k_clip_preprocess(const float* img, float* out, int batch, int h, int w, int out_size, void* stream) {
+    if (!img || !out || batch < 1 || h < 1 || w < 1 || out_size < 1) return fail(ER_ERR_INVALID, "er_k_clip_preprocess: bad argument");
+    HIPRET(launch_clip_preprocess(img, out, batch, h, w, out_size, (hipStream_t)stream));
+    return ER_OK;
+}
+
+extern "C" int er_k_clip_im2col(const float* px, float* a, int batch, int s, int p, int lda, void* stream) {
+    if (!px || !a || batch < 1 || p < 1 || s < p || s % p || lda < 3 * p * p) return fail(ER_ERR_INVALID, "er_k_clip_im2col: bad argument");
+    HIPRET(launch_clip_im2col(px, a, batch, s, p, lda, (hipStream_t)stream));
+    return ER_OK;
+}
+
+extern "C" int er_k_clip_assemble(const float* patches, const float* cls, const float* pos, float* x, int batch, int np, int c, void* stream) {
+    if (!patches || !cls || !pos || !x || batch < 1 || np < 1 || c < 1) return fail(ER_ERR_INVALID, "er_k_clip_assemble: bad argument");
+    HIPRET(launch_clip_assemble(patches, cls, pos, x, batch, np, c, (hipStream_t)stream));
     return ER_OK;
 }
 

@@ -286,15 +286,11 @@ extern "C" int er_dit_encode_image(er_dit_ctx* c, const float* images, int B, in
     ERCHK(c->catt.ensure((size_t)R * W));
     ERCHK(c->cf.ensure((size_t)R * F));
     ERCHK(c->sc.ensure((size_t)H * NT * ldS));
-    auto blocks = [](long long n) { return dim3((unsigned)((n + 255) / 256)); };
-    hipLaunchKernelGGL(clip_preprocess_kernel, blocks((long long)B * 3 * S * S), dim3(256), 0, st, images, c->cpx.p, B, Himg, Wimg, S);
-    HIPRET(hipGetLastError());
-    hipLaunchKernelGGL(clip_im2col_kernel, blocks((long long)B * NP * c->clip_kpad), dim3(256), 0, st, c->cpx.p, c->ccol.p, B, S, P, c->clip_kpad);
-    HIPRET(hipGetLastError());
+    HIPRET(launch_clip_preprocess(images, c->cpx.p, B, Himg, Wimg, S, st));
+    HIPRET(launch_clip_im2col(c->cpx.p, c->ccol.p, B, S, P, c->clip_kpad, st));
     HIPRET(dlin(c, c->ccol.p, c->clip_kpad, c->clip_patch_w, nullptr, c->cpatch.p, W, B * NP, W, c->clip_kpad, nullptr, 0, nullptr, 1, st));
     float* x = c->cx.p;
-    hipLaunchKernelGGL(clip_assemble_kernel, blocks((long long)R * W), dim3(256), 0, st, c->cpatch.p, c->clip_cls, c->clip_pos, x, B, NP, W);
-    HIPRET(hipGetLastError());
+    HIPRET(launch_clip_assemble(c->cpatch.p, c->clip_cls, c->clip_pos, x, B, NP, W, st));
     HIPRET(launch_layernorm(x, c->clip_prew, c->clip_preb, x, R, W, W, W, 1e-5f, st));
     for (int l = 0; l < g.clip_layers; ++l) {           // CLIPEncoderLayer: pre-LN attention + pre-LN MLP, both residual
         const ClipLayerW& L = c->clip[l];
@@ -309,28 +305,11 @@ extern "C" int er_dit_encode_image(er_dit_ctx* c, const float* images, int B, in
         HIPRET(dlin(c, c->catt.p, W, L.ow, L.ob, x, W, R, W, W, x, W, nullptr, 1, st));
         HIPRET(launch_layernorm(x, L.ln2w, L.ln2b, c->ch.p, R, W, W, W, 1e-5f, st));
         HIPRET(dlin(c, c->ch.p, W, L.f1w, L.f1b, c->cf.p, F, R, F, W, nullptr, 0, nullptr, 1, st));
-        hipLaunchKernelGGL(gelu_kernel, blocks((long long)R * F), dim3(256), 0, st, c->cf.p, c->cf.p, (long long)R * F);
-        HIPRET(hipGetLastError());
+        HIPRET(launch_gelu(c->cf.p, c->cf.p, (long long)R * F, st));
         HIPRET(dlin(c, c->cf.p, F, L.f2w, L.f2b, x, W, R, W, F, x, W, nullptr, 1, st));
     }
     HIPCHK(hipMemcpyAsync(out, x, (size_t)R * W * 4, hipMemcpyDeviceToDevice, st));
     return ER_OK;
-}
-
-static hipError_t dit_ln_mod(const float* x, float* y, int rows, int rows_per_batch, const float* table, const float* tvec,
-                             long long t_bstride, long long t_cstride, int shift_idx, int scale_idx, hipStream_t st,
-                             _Float16* y16 = nullptr) {
-    // four rows per wave share one copy of the modulation vectors when the rows of a batch element come in whole groups of four and
-    // there are enough rows to keep >= 4 workgroups per CU (ER_DIT_LN_RPW=1: one row per wave, A/B)
-    static const bool one = [] { const char* e = getenv("ER_DIT_LN_RPW"); return e && e[0] == '1'; }();
-    if (!one && rows_per_batch % 4 == 0 && rows % 4 == 0 && rows >= 16384 / 4) {
-        hipLaunchKernelGGL((ln_modulate_rows_kernel<16, 4>), dim3((rows / 4 + ER_NWAVES - 1) / ER_NWAVES), dim3(ER_WG), 0, st, x, y, rows,
-                           rows_per_batch, table, tvec, t_bstride, t_cstride, shift_idx, scale_idx, 1e-6f, y16);
-        return hipGetLastError();
-    }
-    hipLaunchKernelGGL((ln_modulate_rows_kernel<16>), dim3((rows + ER_NWAVES - 1) / ER_NWAVES), dim3(ER_WG), 0, st, x, y, rows,
-                       rows_per_batch, table, tvec, t_bstride, t_cstride, shift_idx, scale_idx, 1e-6f, y16);
-    return hipGetLastError();
 }
 
 // fp16 mode: permuted ff0 operands of every layer (once per set of weights)
@@ -375,14 +354,11 @@ static int dit_time_embed(er_dit_ctx* c, int B, hipStream_t st) {
     ERCHK(c->temb.ensure((size_t)B * C));
     ERCHK(c->tsil.ensure((size_t)B * C));
     ERCHK(c->tada.ensure((size_t)B * 6 * C));
-    hipLaunchKernelGGL(timestep_embed_kernel, dim3((B * 128 + 255) / 256), dim3(256), 0, st, c->t_dev.p, c->tin.p, B, 128);
-    HIPRET(hipGetLastError());
+    HIPRET(launch_timestep_embed(c->t_dev.p, c->tin.p, B, 128, st));
     HIPRET(dlin(c, c->tin.p, 256, c->tp1_w, c->tp1_b, c->temb0.p, C, B, C, 256, nullptr, 0, nullptr, 1, st));
-    hipLaunchKernelGGL(silu_kernel, dim3((B * C + 255) / 256), dim3(256), 0, st, c->temb0.p, c->temb1.p, (long long)B * C);
-    HIPRET(hipGetLastError());
+    HIPRET(launch_silu(c->temb0.p, c->temb1.p, (long long)B * C, st));
     HIPRET(dlin(c, c->temb1.p, C, c->tp2_w, c->tp2_b, c->temb.p, C, B, C, C, nullptr, 0, nullptr, 1, st));
-    hipLaunchKernelGGL(silu_kernel, dim3((B * C + 255) / 256), dim3(256), 0, st, c->temb.p, c->tsil.p, (long long)B * C);
-    HIPRET(hipGetLastError());
+    HIPRET(launch_silu(c->temb.p, c->tsil.p, (long long)B * C, st));
     HIPRET(dlin(c, c->tsil.p, C, c->adaln_w, c->adaln_b, c->tada.p, 6 * C, B, 6 * C, C, nullptr, 0, nullptr, 1, st));
     return 0;
 }
@@ -490,17 +466,11 @@ static int dit_forward_impl(er_dit_ctx* c, const float* xin, int B, int M, float
     _Float16* qkv16 = hh ? c->qkv16.p : nullptr;
     _Float16* vt16 = hh ? c->vt16.p : nullptr;
     _Float16* q2_16 = hh ? c->q2_16.p : nullptr;
-    {
-        const long long ng = (long long)g.num_layers * 2 * B * C;
-        hipLaunchKernelGGL(adaln_gate_all_kernel, dim3((unsigned)((ng + 255) / 256)), dim3(256), 0, st, c->sst_ptrs.p, tada, c->gates.p,
-                           g.num_layers, B, C);
-        HIPRET(hipGetLastError());
-    }
+    HIPRET(launch_adaln_gate_all(c->sst_ptrs.p, tada, c->gates.p, g.num_layers, B, C, st));
     float* x = c->x.p;
     // x = proj_in(x) + pos_embed                                                  dit.py:177-180
     HIPRET(dlin(c, xin, LD, c->proj_in_w, c->proj_in_b, x, C, R, C, LD, nullptr, 0, nullptr, 1, st));
-    hipLaunchKernelGGL(add_pos_kernel, dim3(ew_grid((long long)R * C / 4)), dim3(ER_WG), 0, st, x, c->pos_embed, x, B, N, C, 0);
-    HIPRET(hipGetLastError());
+    HIPRET(launch_add_pos(x, c->pos_embed, x, B, N, C, 0, st));
     for (int l = 0; l < g.num_layers; ++l) {
         const DitLayerW& L = c->layers[l];
         // x = norm1(x) * (1 + scale_msa) + shift_msa   (chunks 0 = shift, 1 = scale, 2 = gate)     dit.py:129-132
@@ -555,8 +525,7 @@ static int dit_forward_impl(er_dit_ctx* c, const float* xin, int B, int M, float
             HIPRET(launch_gemm_hh_geglu(fg, st));
         } else {
             HIPRET(dlin(c, x, C, L.ff0_w, L.ff0_b, c->u.p, 8 * C, R, 8 * C, C, nullptr, 0, nullptr, 1, st));
-            hipLaunchKernelGGL(geglu_kernel, dim3(ew_grid((long long)R * 4 * C)), dim3(ER_WG), 0, st, c->u.p, c->g.p, (long long)R, 4 * C);
-            HIPRET(hipGetLastError());
+            HIPRET(launch_geglu(c->u.p, c->g.p, (long long)R, 4 * C, st));
         }
         if (hh) HIPRET(dlin16(c, g16, 4 * C, L.ff2_w, L.ff2_b, x, C, R, C, 4 * C, x, C, gate_mlp, N, nullptr, st));
         else HIPRET(dlin(c, c->g.p, 4 * C, L.ff2_w, L.ff2_b, x, C, R, C, 4 * C, x, C, gate_mlp, N, st));
@@ -627,13 +596,8 @@ extern "C" int er_dit_sample(er_dit_ctx* c, const float* cond, int B, int M, flo
         if (dit_forward_impl(c, c->xin.p, B2, M, c->pred.p, c->temb.p + (size_t)k * B2 * C, c->tada.p + (size_t)k * B2 * 6 * C, st) < 0) return -1;
         const int prev = t - ratio;
         const float a_t = ac[t], a_p = prev >= 0 ? ac[prev] : ac[0];
-        if (c->pred_type == ER_PRED_EPSILON)
-            hipLaunchKernelGGL(ddim_cfg_step_eps_kernel, dim3((unsigned)((nlat + 255) / 256)), dim3(256), 0, st, latents, c->pred.p,
-                               (long long)nlat, guidance, sqrtf(a_t), sqrtf(1.0f - a_t), sqrtf(a_p), sqrtf(1.0f - a_p));
-        else
-            hipLaunchKernelGGL(ddim_cfg_step_kernel, dim3((unsigned)((nlat + 255) / 256)), dim3(256), 0, st, latents, c->pred.p,
-                               (long long)nlat, guidance, sqrtf(a_t), sqrtf(1.0f - a_t), sqrtf(a_p), sqrtf(1.0f - a_p));
-        HIPRET(hipGetLastError());
+        HIPRET(launch_ddim_cfg_step(c->pred_type == ER_PRED_EPSILON, latents, c->pred.p, (long long)nlat, guidance, sqrtf(a_t),
+                                    sqrtf(1.0f - a_t), sqrtf(a_p), sqrtf(1.0f - a_p), st));
     }
     HIPCHK(hipStreamSynchronize(st));
     return ER_OK;

@@ -1,6 +1,8 @@
 // Element-wise / row kernels of the DiT denoiser (scope row f3): adaLN-single modulation, timestep
 // embedding, SiLU, and the DDIM + classifier-free-guidance update.  HBM-bound streaming kernels.
 #pragma once
+#include <cstdlib>
+
 #include "er_common.h"
 
 namespace er {
@@ -73,6 +75,22 @@ __global__ __launch_bounds__(ER_WG) void ln_modulate_rows_kernel(const float* x,
         }
     }
 }
+// the DiT's launch of it (hidden width 1024, eps 1e-6)
+inline hipError_t dit_ln_mod(const float* x, float* y, int rows, int rows_per_batch, const float* table, const float* tvec,
+                             long long t_bstride, long long t_cstride, int shift_idx, int scale_idx, hipStream_t st,
+                             _Float16* y16 = nullptr) {
+    // four rows per wave share one copy of the modulation vectors when the rows of a batch element come in whole groups of four and
+    // there are enough rows to keep >= 4 workgroups per CU (ER_DIT_LN_RPW=1: one row per wave, A/B)
+    static const bool one = [] { const char* e = getenv("ER_DIT_LN_RPW"); return e && e[0] == '1'; }();
+    if (!one && rows_per_batch % 4 == 0 && rows % 4 == 0 && rows >= 16384 / 4) {
+        hipLaunchKernelGGL((ln_modulate_rows_kernel<16, 4>), dim3((rows / 4 + ER_NWAVES - 1) / ER_NWAVES), dim3(ER_WG), 0, st, x, y, rows,
+                           rows_per_batch, table, tvec, t_bstride, t_cstride, shift_idx, scale_idx, 1e-6f, y16);
+        return hipGetLastError();
+    }
+    hipLaunchKernelGGL((ln_modulate_rows_kernel<16>), dim3((rows + ER_NWAVES - 1) / ER_NWAVES), dim3(ER_WG), 0, st, x, y, rows,
+                       rows_per_batch, table, tvec, t_bstride, t_cstride, shift_idx, scale_idx, 1e-6f, y16);
+    return hipGetLastError();
+}
 
 // gate_b[c] = table[idx][c] + t_adaln[b][idx][c]  -> out [B][C]   (the adaLN gates fed to the GEMM epilogue)
 __global__ void adaln_gate_kernel(const float* table, const float* tada, float* out, int B, int C, int idx) {
@@ -80,6 +98,10 @@ __global__ void adaln_gate_kernel(const float* table, const float* tada, float* 
     if (i >= B * C) return;
     const int b = i / C, c = i - b * C;
     out[i] = table[idx * C + c] + tada[((long long)b * 6 + idx) * C + c];
+}
+inline hipError_t launch_adaln_gate(const float* table, const float* tada, float* out, int B, int C, int idx, hipStream_t st) {
+    hipLaunchKernelGGL(adaln_gate_kernel, dim3((B * C + 255) / 256), dim3(256), 0, st, table, tada, out, B, C, idx);
+    return hipGetLastError();
 }
 
 // the gates of EVERY layer in one launch: out[(layer * 2 + which) * B * C + b * C + c], which 0 -> chunk 2 (gate_msa), 1 -> chunk 5
@@ -92,6 +114,12 @@ __global__ void adaln_gate_all_kernel(const float* const* tables, const float* t
     const int r = (int)(i - lw * per), b = r / C, c = r - b * C;
     out[i] = tables[l][idx * C + c] + tada[((long long)b * 6 + idx) * C + c];
 }
+inline hipError_t launch_adaln_gate_all(const float* const* tables, const float* tada, float* out, int layers, int B, int C,
+                                        hipStream_t st) {
+    const long long ng = (long long)layers * 2 * B * C;
+    hipLaunchKernelGGL(adaln_gate_all_kernel, dim3((unsigned)((ng + 255) / 256)), dim3(256), 0, st, tables, tada, out, layers, B, C);
+    return hipGetLastError();
+}
 
 // Timesteps(256) (dit.py:45-77): emb[b] = [sin(t*w_k), cos(t*w_k)], w_k = exp(-ln(10000) * k / 128)
 __global__ void timestep_embed_kernel(const float* t, float* out, int B, int half) {
@@ -103,10 +131,20 @@ __global__ void timestep_embed_kernel(const float* t, float* out, int B, int hal
     out[(long long)b * 2 * half + k] = sinf(a);
     out[(long long)b * 2 * half + half + k] = cosf(a);
 }
+inline hipError_t launch_timestep_embed(const float* t, float* out, int B, int half, hipStream_t st) {
+    hipLaunchKernelGGL(timestep_embed_kernel, dim3((B * half + 255) / 256), dim3(256), 0, st, t, out, B, half);
+    return hipGetLastError();
+}
 
 __global__ void silu_kernel(const float* x, float* y, long long n) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) { const float v = x[i]; y[i] = v / (1.0f + expf(-v)); }
+}
+// a thread per element, 256 per workgroup: the grid of silu, gelu, the DDIM steps and the CLIP front
+inline dim3 dit_ew_blocks(long long n) { return dim3((unsigned)((n + 255) / 256)); }
+inline hipError_t launch_silu(const float* x, float* y, long long n, hipStream_t st) {
+    hipLaunchKernelGGL(silu_kernel, dit_ew_blocks(n), dim3(256), 0, st, x, y, n);
+    return hipGetLastError();
 }
 
 // One DDIM (eta = 0, v-prediction) step with classifier-free guidance (core/models_dit.py:222-227):
@@ -134,6 +172,15 @@ __global__ void ddim_cfg_step_eps_kernel(float* latents, const float* pred, long
     const float x0 = (x - sb_t * eps) / sa_t;
     latents[i] = sa_p * x0 + sb_p * eps;
 }
+// eps_pred: the model predicts the noise (prediction_type 'epsilon'), else v
+inline hipError_t launch_ddim_cfg_step(bool eps_pred, float* latents, const float* pred, long long n, float guidance, float sa_t,
+                                       float sb_t, float sa_p, float sb_p, hipStream_t st) {
+    if (eps_pred)
+        hipLaunchKernelGGL(ddim_cfg_step_eps_kernel, dit_ew_blocks(n), dim3(256), 0, st, latents, pred, n, guidance, sa_t, sb_t, sa_p, sb_p);
+    else
+        hipLaunchKernelGGL(ddim_cfg_step_kernel, dit_ew_blocks(n), dim3(256), 0, st, latents, pred, n, guidance, sa_t, sb_t, sa_p, sb_p);
+    return hipGetLastError();
+}
 
 }  // namespace er
 
@@ -160,6 +207,10 @@ __global__ void clip_preprocess_kernel(const float* img, float* out, int B, int 
     const float v10 = (p[(long long)y1 * W + x0] - mean) / stdv, v11 = (p[(long long)y1 * W + x1] - mean) / stdv;
     out[i] = (1.f - ly) * ((1.f - lx) * v00 + lx * v01) + ly * ((1.f - lx) * v10 + lx * v11);
 }
+inline hipError_t launch_clip_preprocess(const float* img, float* out, int B, int H, int W, int OUT, hipStream_t st) {
+    hipLaunchKernelGGL(clip_preprocess_kernel, dit_ew_blocks((long long)B * 3 * OUT * OUT), dim3(256), 0, st, img, out, B, H, W, OUT);
+    return hipGetLastError();
+}
 
 // Conv2d(3, width, kernel P, stride P, no bias) as a GEMM: A[b*G*G + py*G + px][c*P*P + ky*P + kx] (zero-padded to lda)
 __global__ void clip_im2col_kernel(const float* px, float* A, int B, int S, int P, int lda) {
@@ -178,6 +229,11 @@ __global__ void clip_im2col_kernel(const float* px, float* A, int B, int S, int 
     }
     A[i] = v;
 }
+inline hipError_t launch_clip_im2col(const float* px, float* A, int B, int S, int P, int lda, hipStream_t st) {
+    const int G = S / P;
+    hipLaunchKernelGGL(clip_im2col_kernel, dit_ew_blocks((long long)B * G * G * lda), dim3(256), 0, st, px, A, B, S, P, lda);
+    return hipGetLastError();
+}
 
 // x[b][0] = class_embedding + pos[0]; x[b][1+p] = patches[b][p] + pos[1+p]     (CLIPVisionEmbeddings.forward)
 __global__ void clip_assemble_kernel(const float* patches, const float* cls, const float* pos, float* x, int B, int NP, int C) {
@@ -190,10 +246,19 @@ __global__ void clip_assemble_kernel(const float* patches, const float* cls, con
     const float base = tkn == 0 ? cls[c] : patches[(b * NP + (tkn - 1)) * C + c];
     x[i] = base + pos[(long long)tkn * C + c];
 }
+inline hipError_t launch_clip_assemble(const float* patches, const float* cls, const float* pos, float* x, int B, int NP, int C,
+                                       hipStream_t st) {
+    hipLaunchKernelGGL(clip_assemble_kernel, dit_ew_blocks((long long)B * (NP + 1) * C), dim3(256), 0, st, patches, cls, pos, x, B, NP, C);
+    return hipGetLastError();
+}
 
 __global__ void gelu_kernel(const float* x, float* y, long long n) {       // exact (erf) GELU, in place allowed
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) { const float v = x[i]; y[i] = v * 0.5f * (1.0f + erff(v * 0.70710678118654752440f)); }
+}
+inline hipError_t launch_gelu(const float* x, float* y, long long n, hipStream_t st) {
+    hipLaunchKernelGGL(gelu_kernel, dit_ew_blocks(n), dim3(256), 0, st, x, y, n);
+    return hipGetLastError();
 }
 
 }  // namespace er

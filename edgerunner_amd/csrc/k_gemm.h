@@ -970,6 +970,10 @@ __global__ __launch_bounds__(ER_WG) void split_rows_f16_kernel(const float* x, _
 inline dim3 split_rows_grid(long long rows, int cols) {
     return dim3((unsigned)((cols / 4 + ER_WG - 1) / ER_WG), (unsigned)(rows < 65535 ? (rows > 0 ? rows : 1) : 65535));
 }
+inline hipError_t launch_split_rows_f16(const float* x, _Float16* hi, _Float16* lo, long long rows, int cols, int ldx, hipStream_t st) {
+    hipLaunchKernelGGL(split_rows_f16_kernel, split_rows_grid(rows, cols), dim3(ER_WG), 0, st, x, hi, lo, rows, cols, ldx);
+    return hipGetLastError();
+}
 
 // split form: A = a_hi (g.A) + a_lo (g.a_lo), fp16 [M][lda]; 64-row tiles
 inline hipError_t launch_gemm_hh_split(const GemmArgs& g, hipStream_t st) {

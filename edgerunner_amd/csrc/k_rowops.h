@@ -7,6 +7,14 @@
 
 namespace er {
 
+// grid of the element-wise kernels that stride: a workgroup per ER_WG elements, at most 2048 of them
+inline int ew_grid(long long total) {
+    long long g = (total + ER_WG - 1) / ER_WG;
+    if (g > 2048) g = 2048;
+    if (g < 1) g = 1;
+    return (int)g;
+}
+
 // y[r,:] = LayerNorm(x[r,:]) * w + b   (nn.LayerNorm, biased variance, eps inside sqrt;
 // core/transformer/modeling_opt.py:274,288, core/transformer/point.py:137,112-114, core/models.py:65).
 // One wave per row, the row lives in registers (CPL = cols/64 values per lane).
@@ -106,6 +114,10 @@ __global__ __launch_bounds__(ER_WG) void geglu_kernel(const float* u, float* out
         out[i] = x * gelu;
     }
 }
+inline hipError_t launch_geglu(const float* u, float* out, long long rows, int F, hipStream_t st) {
+    hipLaunchKernelGGL(geglu_kernel, dim3(ew_grid(rows * F)), dim3(ER_WG), 0, st, u, out, rows, F);
+    return hipGetLastError();
+}
 
 // hidden = inputs_embeds + embed_positions(arange(S))   (core/transformer/modeling_opt.py:355-357)
 __global__ __launch_bounds__(ER_WG) void add_pos_kernel(const float* emb, const float* pos, float* out, int B, int S,
@@ -120,6 +132,10 @@ __global__ __launch_bounds__(ER_WG) void add_pos_kernel(const float* emb, const 
         const f32x4 p = reinterpret_cast<const f32x4*>(pos)[(long long)(pos0 + s) * c4 + c];
         reinterpret_cast<f32x4*>(out)[i] = a + p;
     }
+}
+inline hipError_t launch_add_pos(const float* emb, const float* pos, float* out, int B, int S, int C, int pos0, hipStream_t st) {
+    hipLaunchKernelGGL(add_pos_kernel, dim3(ew_grid((long long)B * S * C / 4)), dim3(ER_WG), 0, st, emb, pos, out, B, S, C, pos0);
+    return hipGetLastError();
 }
 
 // PointEmbed features (core/transformer/point.py:53-63): for point m,
@@ -145,6 +161,10 @@ __global__ __launch_bounds__(ER_WG) void point_embed_kernel(const float* pts, co
         out[i] = v;
     }
 }
+inline hipError_t launch_point_embed(const float* pts, const float* basis, float* out, long long M, int F, int ldo, hipStream_t st) {
+    hipLaunchKernelGGL(point_embed_kernel, dim3(ew_grid(M * ldo)), dim3(ER_WG), 0, st, pts, basis, out, M, F, ldo);
+    return hipGetLastError();
+}
 
 // out[r, :] = table[ids[r], :]   (nn.Embedding lookups: core/models.py:137,228)
 __global__ __launch_bounds__(ER_WG) void gather_rows_kernel(const float* table, const int* ids, float* out, int rows,
@@ -154,6 +174,10 @@ __global__ __launch_bounds__(ER_WG) void gather_rows_kernel(const float* table, 
     const float* src = table + (long long)ids[r] * C;
     float* dst = out + (long long)r * ldo;
     for (int c = threadIdx.x; c < C; c += ER_WG) dst[c] = src[c];
+}
+inline hipError_t launch_gather_rows(const float* table, const int* ids, float* out, int rows, int C, long long ldo, hipStream_t st) {
+    hipLaunchKernelGGL(gather_rows_kernel, dim3(rows), dim3(ER_WG), 0, st, table, ids, out, rows, C, ldo);
+    return hipGetLastError();
 }
 
 // Fast mode prefill: move the K/V columns of the fused projection output qkv[M][3*hidden] into the fp16
@@ -207,12 +231,16 @@ __global__ __launch_bounds__(ER_WG) void kv8_encode_kernel(const float* src, uns
 inline dim3 kv_scatter_grid(int M, int hidden) {
     return dim3((unsigned)((2 * hidden / 4 + ER_WG - 1) / ER_WG), (unsigned)(M < 65535 ? (M > 0 ? M : 1) : 65535));
 }
-
-inline int ew_grid(long long total) {
-    long long g = (total + ER_WG - 1) / ER_WG;
-    if (g > 2048) g = 2048;
-    if (g < 1) g = 1;
-    return (int)g;
+// f8: the byte cache of kv8 mode, else the fp16 cache of fast mode
+inline hipError_t launch_kv_scatter(float* qkv, void* kcache, void* vcache, bool f8, int M, int S, int hidden, int head_dim, int l_cap,
+                                    long long kv_bstride, hipStream_t st) {
+    if (f8)
+        hipLaunchKernelGGL(kv_scatter_f8_kernel, kv_scatter_grid(M, hidden), dim3(ER_WG), 0, st, qkv, (unsigned char*)kcache,
+                           (unsigned char*)vcache, M, S, hidden, head_dim, l_cap, kv_bstride);
+    else
+        hipLaunchKernelGGL(kv_scatter_half_kernel, kv_scatter_grid(M, hidden), dim3(ER_WG), 0, st, qkv, (_Float16*)kcache,
+                           (_Float16*)vcache, M, S, hidden, head_dim, l_cap, kv_bstride);
+    return hipGetLastError();
 }
 
 }  // namespace er

@@ -655,3 +655,92 @@ def philox_uniform(seed: int, step: int, row: int) -> float:
     counter = (step, row, 0, 0), u = (x0 >> 8) * 2^-24)."""
     x = philox4x32_10((step, row, 0, 0), (seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF))
     return float(x[0] >> 8) / 16777216.0
+
+
+# ---- the once-per-sample row, element-wise and K/V scatter kernels (er_k_* of csrc/k_rowops.h, k_dit.h, split_rows_f16_kernel).
+# The caller owns every buffer - the tests put sentinels around them - so these take the tensors (or views: only the first element's
+# address is passed, the strides are arguments) and the sizes as the C entries do, and enqueue on the current stream.
+def _at(t):
+    """Address of a tensor's or view's first element (None -> NULL); the layout behind it is the caller's argument."""
+    return C.c_void_p(0) if t is None else C.c_void_p(t.data_ptr())
+
+
+def _rowop(name, *args):
+    native.check(getattr(native.load_library(), name)(*args, _st()), name)
+
+
+def softmax_batched_(s, rows, cols, ld, ld_pad, batch, batch_stride, causal=False, causal_off=0):
+    _rowop("er_k_softmax_batched", _at(s), rows, cols, ld, ld_pad, batch, batch_stride, int(causal), causal_off)
+    return s
+
+
+def kv_scatter_(qkv, kcache, vcache, M, S, hidden, head_dim, l_cap, kv_bstride):
+    """In place: qkv [M][3 * hidden] fp32; caches fp16, or uint8 for the e4m3 byte cache (first element of batch row 0)."""
+    assert kcache.dtype == vcache.dtype and kcache.dtype in (torch.float16, torch.uint8)
+    _rowop("er_k_kv_scatter", _at(qkv), _at(kcache), _at(vcache), 1 if kcache.dtype == torch.float16 else 2, M, S, hidden, head_dim,
+           l_cap, kv_bstride)
+
+
+def split_rows_f16_(x, hi, lo, rows, cols, ldx):
+    _rowop("er_k_split_rows_f16", _at(x), _at(hi), _at(lo), rows, cols, ldx)
+
+
+def add_pos_(emb, pos, out, B, S, Cc, pos0=0):
+    _rowop("er_k_add_pos", _at(emb), _at(pos), _at(out), B, S, Cc, pos0)
+
+
+def gather_rows_(table, ids, out, Cc, ldo):
+    """ids: list of ints (host); table [rows][Cc] dense."""
+    _rowop("er_k_gather_rows", _at(table), table.shape[0], native.i32_array(ids), _at(out), len(ids), Cc, ldo)
+
+
+def point_embed_(pts, basis, out, M, F, ldo):
+    _rowop("er_k_point_embed", _at(pts), _at(basis), _at(out), M, F, ldo)
+
+
+def geglu_(u, out, rows, F):
+    _rowop("er_k_geglu", _at(u), _at(out), rows, F)
+
+
+def gelu_(x, y, n):
+    _rowop("er_k_gelu", _at(x), _at(y), n)
+
+
+def silu_(x, y, n):
+    _rowop("er_k_silu", _at(x), _at(y), n)
+
+
+def ln_modulate_(x, y, rows, rows_per_batch, cols, table, tvec, t_bstride, t_cstride, shift_idx, scale_idx, y16=None):
+    _rowop("er_k_ln_modulate", _at(x), _at(y), rows, rows_per_batch, cols, _at(table), _at(tvec), t_bstride, t_cstride, shift_idx,
+           scale_idx, _at(y16))
+
+
+def adaln_gate_(table, tada, out, B, Cc, idx):
+    _rowop("er_k_adaln_gate", _at(table), _at(tada), _at(out), B, Cc, idx)
+
+
+def adaln_gate_all_(tables, tada, out, B, Cc):
+    """tables: one device tensor [6][Cc] per layer."""
+    ptrs = (C.c_void_p * len(tables))(*[t.data_ptr() for t in tables])
+    _rowop("er_k_adaln_gate_all", C.cast(ptrs, C.c_void_p), _at(tada), _at(out), len(tables), B, Cc)
+
+
+def timestep_embed_(t, out, B, half):
+    _rowop("er_k_timestep_embed", _at(t), _at(out), B, half)
+
+
+def ddim_cfg_step_(latents, pred, n, prediction_type, guidance, sa_t, sb_t, sa_p, sb_p):
+    _rowop("er_k_ddim_cfg_step", _at(latents), _at(pred), n, prediction_type, float(guidance), float(sa_t), float(sb_t), float(sa_p),
+           float(sb_p))
+
+
+def clip_preprocess_(img, out, B, H, W, OUT):
+    _rowop("er_k_clip_preprocess", _at(img), _at(out), B, H, W, OUT)
+
+
+def clip_im2col_(px, a, B, S, P, lda):
+    _rowop("er_k_clip_im2col", _at(px), _at(a), B, S, P, lda)
+
+
+def clip_assemble_(patches, cls, pos, x, B, NP, Cc):
+    _rowop("er_k_clip_assemble", _at(patches), _at(cls), _at(pos), _at(x), B, NP, Cc)

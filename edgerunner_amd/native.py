@@ -41,6 +41,9 @@ EXPORTS = [
     "er_set_prefix_pass", "er_k_attn_shared_mfma", "er_ctx_w8_streams",
     "er_ctx_w4_streams", "er_ctx_w4_streams_batched", "er_k_w4_quantize", "er_k_gemv_form_w4", "er_k_w4_cvt_probe",
     "er_prefill_fork", "er_k_kv_fork", "er_queue_admit_copy",
+    "er_k_softmax_batched", "er_k_kv_scatter", "er_k_split_rows_f16", "er_k_add_pos", "er_k_gather_rows", "er_k_point_embed", "er_k_geglu",
+    "er_k_gelu", "er_k_silu", "er_k_ln_modulate", "er_k_adaln_gate", "er_k_adaln_gate_all", "er_k_timestep_embed", "er_k_ddim_cfg_step",
+    "er_k_clip_preprocess", "er_k_clip_im2col", "er_k_clip_assemble",
 ]
 
 
@@ -222,6 +225,24 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.er_k_flash_attn_f16s.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, ci, vp]
     lib.er_k_layernorm.argtypes = [vp, vp, vp, vp, ci, ci, cf, vp]
     lib.er_k_softmax.argtypes = [vp, ci, ci, ci, ci, vp]
+    ll = C.c_longlong
+    lib.er_k_softmax_batched.argtypes = [vp, ci, ci, ll, ci, ci, ll, ci, ci, vp]
+    lib.er_k_kv_scatter.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, ci, ll, vp]
+    lib.er_k_split_rows_f16.argtypes = [vp, vp, vp, ll, ci, ci, vp]
+    lib.er_k_add_pos.argtypes = [vp, vp, vp, ci, ci, ci, ci, vp]
+    lib.er_k_gather_rows.argtypes = [vp, ci, vp, vp, ci, ci, ll, vp]
+    lib.er_k_point_embed.argtypes = [vp, vp, vp, ll, ci, ci, vp]
+    lib.er_k_geglu.argtypes = [vp, vp, ll, ci, vp]
+    lib.er_k_gelu.argtypes = [vp, vp, ll, vp]
+    lib.er_k_silu.argtypes = [vp, vp, ll, vp]
+    lib.er_k_ln_modulate.argtypes = [vp, vp, ci, ci, ci, vp, vp, ll, ll, ci, ci, vp, vp]
+    lib.er_k_adaln_gate.argtypes = [vp, vp, vp, ci, ci, ci, vp]
+    lib.er_k_adaln_gate_all.argtypes = [vp, vp, vp, ci, ci, ci, vp]
+    lib.er_k_timestep_embed.argtypes = [vp, vp, ci, ci, vp]
+    lib.er_k_ddim_cfg_step.argtypes = [vp, vp, ll, ci, cf, cf, cf, cf, cf, vp]
+    lib.er_k_clip_preprocess.argtypes = [vp, vp, ci, ci, ci, ci, vp]
+    lib.er_k_clip_im2col.argtypes = [vp, vp, ci, ci, ci, ci, vp]
+    lib.er_k_clip_assemble.argtypes = [vp, vp, vp, vp, ci, ci, ci, vp]
     lib.er_k_score_rows.argtypes = [vp, vp, ci, ci, ci, vp, vp, vp, vp]
     lib.er_k_sample_head.argtypes = [vp, C.POINTER(ErDecodeParams), ci, ci, ci, ci, ci, C.POINTER(C.c_int32),
                                      C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),

@@ -676,6 +676,61 @@ int er_k_layernorm(const float* x_dev, const float* w_dev, const float* b_dev, f
                    int rows, int cols, float eps, void* stream);
 /* rows of scores[rows, ld]: softmax over the first n_valid(row) columns (causal: row+1+causal_offset), zeros after */
 int er_k_softmax(float* s_dev, int rows, int cols, int ld, int causal, void* stream);
+/* er_k_softmax's kernel as the attention calls it: batch score matrices [rows][ld], batch_stride floats apart (>= rows * ld), one
+ * launch; row r keeps n_valid = causal ? min(cols, r + 1 + causal_off) : cols columns and columns [n_valid, ld_pad) become 0.
+ * ER_ERR_INVALID unless cols <= ld_pad <= ld, causal_off >= 0 and 1 <= batch <= 65535. */
+int er_k_softmax_batched(float* s_dev, int rows, int cols, long long ld, int ld_pad, int batch, long long batch_stride, int causal,
+                         int causal_off, void* stream);
+
+/* The once-per-sample row, element-wise and K/V scatter kernels (csrc/k_rowops.h, k_dit.h, k_gemm.h split_rows_f16_kernel) on
+ * caller-owned device buffers, through the launchers the prefill, the point encoder, the CLIP front and the DiT sampler call.
+ * Every entry returns ER_ERR_INVALID before anything is launched for a null pointer, a non-positive size or a shape the kernel's
+ * vector accesses or its launcher do not have; a refused call writes nothing.  They enqueue on `stream` and return, except the two
+ * that copy a host array (er_k_gather_rows, er_k_adaln_gate_all), which block.
+ *
+ * er_k_kv_scatter: the fast / kv8 prefill's move of the K and V thirds of qkv_dev [m][3 * hidden] (m = batch * s tokens) into caches
+ * [batch][hidden / head_dim][l_cap][head_dim] whose batch rows lie kv_bstride ELEMENTS apart, kv_half 1 = fp16, 2 = e4m3 bytes; the
+ * scratch's K / V thirds are rounded in place to the stored values.  Needs m % s == 0, s <= l_cap, hidden % 4 == 0, head_dim % 4 == 0,
+ * hidden % head_dim == 0, kv_bstride % 4 == 0 and kv_bstride >= hidden * l_cap. */
+int er_k_kv_scatter(float* qkv_dev, void* kcache_dev, void* vcache_dev, int kv_half, int m, int s, int hidden, int head_dim, int l_cap,
+                    long long kv_bstride, void* stream);
+/* hi = fp16(x), lo = fp16(x - hi) of x_dev [rows][ldx] into dense fp16 [rows][cols]; cols % 4 == 0, ldx % 4 == 0, ldx >= cols */
+int er_k_split_rows_f16(const float* x_dev, void* hi_dev, void* lo_dev, long long rows, int cols, int ldx, void* stream);
+/* out[b][t][:] = emb[b][t][:] + pos[pos0 + t][:], t < s; c % 4 == 0; out may be emb */
+int er_k_add_pos(const float* emb_dev, const float* pos_dev, float* out_dev, int batch, int s, int c, int pos0, void* stream);
+/* out[r][0 .. c) = table[ids_host[r]][0 .. c), output rows ldo floats apart; every id in [0, table_rows) */
+int er_k_gather_rows(const float* table_dev, int table_rows, const int32_t* ids_host, float* out_dev, int rows, int c, long long ldo,
+                     void* stream);
+/* PointEmbed features of pts_dev [m][3] with basis_dev [3][f]: [sin | cos | xyz | zeros] in rows of ldo >= 2 f + 3 floats */
+int er_k_point_embed(const float* pts_dev, const float* basis_dev, float* out_dev, long long m, int f, int ldo, void* stream);
+/* out[r][j] = u[r][j] * gelu_erf(u[r][f + j]), u_dev [rows][2 f] */
+int er_k_geglu(const float* u_dev, float* out_dev, long long rows, int f, void* stream);
+/* y = gelu_erf(x) / y = x * sigmoid(x) over n elements; y may be x */
+int er_k_gelu(const float* x_dev, float* y_dev, long long n, void* stream);
+int er_k_silu(const float* x_dev, float* y_dev, long long n, void* stream);
+/* The DiT's adaLN modulation y = LayerNorm(x, eps 1e-6, no affine) * (1 + scale_b) + shift_b over x_dev [rows][cols], rows_per_batch
+ * rows per batch element (rows % rows_per_batch == 0), with scale_b = table[scale_idx][:] + tvec[b * t_bstride + scale_idx * t_cstride + :]
+ * and shift_b likewise; y16_dev (nullable) receives the same rows in fp16; y may be x.  cols must be 1024, strides multiples of 4. */
+int er_k_ln_modulate(const float* x_dev, float* y_dev, int rows, int rows_per_batch, int cols, const float* table_dev,
+                     const float* tvec_dev, long long t_bstride, long long t_cstride, int shift_idx, int scale_idx, void* y16_dev,
+                     void* stream);
+/* out[b][:] = table[idx][:] + tada[b][idx][:] with table_dev [6][c], tada_dev [batch][6][c]; idx in [0, 6) */
+int er_k_adaln_gate(const float* table_dev, const float* tada_dev, float* out_dev, int batch, int c, int idx, void* stream);
+/* the same for chunks 2 and 5 of `layers` tables (tables_host: their device pointers): out_dev [layers][2][batch][c] */
+int er_k_adaln_gate_all(const float* const* tables_host, const float* tada_dev, float* out_dev, int layers, int batch, int c, void* stream);
+/* out[b] = [sin(t_b w_k) | cos(t_b w_k)], w_k = exp(-ln(10000) k / half), k < half: out_dev [batch][2 * half] */
+int er_k_timestep_embed(const float* t_dev, float* out_dev, int batch, int half, void* stream);
+/* one DDIM (eta 0) step with classifier-free guidance in place on latents_dev [n]; pred_dev [2][n] = uncond | cond rows;
+ * prediction_type an er_pred_type; sa = sqrt(alpha_cumprod), sb = sqrt(1 - alpha_cumprod) at the current (t) and previous (p) step */
+int er_k_ddim_cfg_step(float* latents_dev, const float* pred_dev, long long n, int prediction_type, float guidance, float sa_t,
+                       float sb_t, float sa_p, float sb_p, void* stream);
+/* CLIP normalisation then bilinear resize (align_corners false) of img_dev [batch][3][h][w] to out_dev [batch][3][out_size][out_size] */
+int er_k_clip_preprocess(const float* img_dev, float* out_dev, int batch, int h, int w, int out_size, void* stream);
+/* the patch Conv2d's A operand: a_dev [batch * (s / p)^2][lda], column c * p * p + ky * p + kx, zeros from 3 p p to lda; s % p == 0 */
+int er_k_clip_im2col(const float* px_dev, float* a_dev, int batch, int s, int p, int lda, void* stream);
+/* x[b][0] = cls + pos[0]; x[b][1 + i] = patches[b][i] + pos[1 + i], i < np: x_dev [batch][np + 1][c] */
+int er_k_clip_assemble(const float* patches_dev, const float* cls_dev, const float* pos_dev, float* x_dev, int batch, int np, int c,
+                       void* stream);
 /* er_score's head on given logits float[B,S,V] (V <= 1088): nll / pred per position as er_score defines them; loss_out_dev
  * (nullable) = {mean NLL over supervised positions, count} from the fixed-order double reduction */
 int er_k_score_rows(const float* logits_dev, const int32_t* labels_dev, int batch, int seq_len, int vocab, float* nll_out_dev,
