@@ -21,6 +21,7 @@
 #include "k_attn_decode.h"
 #include "k_attn_shared.h"
 #include "k_attn_shared_mfma.h"
+#include "k_attn_extend.h"
 #include "k_kv_fork.h"
 #include "k_outproj_merge.h"
 #include "k_flash_attn_f16s.h"
@@ -40,6 +41,7 @@
 #include "meto_encode.h"
 #include "er_queue_host.h"
 #include "er_decode_plan.h"
+#include "er_extend_plan.h"
 #include "er_decode_proj.h"
 #include "k_mlp_sparse.h"
 
@@ -168,6 +170,9 @@ struct KvMem {
     // group after group with the leader first, behind the groups' offsets
     std::vector<int> grp_leader;
     int prefix_len = 0, n_groups = 0;
+    // the past er_prefill_extend may keep: positions [0, valid_prefix) were written for ALL rows by the last er_prefill / er_prefill_fork /
+    // er_score / er_prefill_extend on this reservation (0: by none, or that pass failed); it counts while have_hidden holds
+    int valid_prefix = 0;
     DevBuf<int> grp_rows, grp_off, grp_leader_dev, grp_followers, grp_first;
     KvMem() = default;
     KvMem(const KvMem&) = delete;
@@ -211,7 +216,7 @@ struct er_ctx {
     float last_decode_ms = 0.f;
     // scratch for prefill / encoder: grow-only, freed with the context
     DevBuf<_Float16> p_hi, p_lo;   // fast-mode prefill: hi / lo fp16 halves of the activation a Linear is about to read (LDS-DMA GEMM, split form)
-    DevBuf<float> p_h, p_q, p_a, p_y, p_f, p_qkv, p_ap, p_aml, e_tmp;
+    DevBuf<float> p_h, p_q, p_a, p_y, p_f, p_qkv, p_ap, p_aml, p_kx, e_tmp;   // p_kx: er_prefill_extend's gathered K | V rows (flash route, fast mode)
     DevBuf<int> e_ids;             // er_embed_tokens: the ids on the device
     DevBuf<float> s_lg;            // er_score: logits of every position when the caller passes no buffer for them
     // queue mode (er_queue_*): the host's view of the rows, the staging of an admission and of a look at the rows
@@ -558,7 +563,10 @@ extern "C" int er_kv_reserve(er_ctx* c, int batch, int max_len) {
     if (max_len > g.max_positions)
         return fail(ER_ERR_CAPACITY, "max_len %d exceeds the position table (%d)", max_len, g.max_positions);
     const int Lcap = (max_len + 31) / 32 * 32;
-    if (c->kv->plan.B == batch && c->kv->plan.Lcap == Lcap) return c->kv->prefix_len ? er_set_prefix_groups(c, nullptr, 0, 0) : ER_OK;
+    if (c->kv->plan.B == batch && c->kv->plan.Lcap == Lcap) {
+        c->kv->valid_prefix = 0;                 // a reserve starts over: nothing of the rows' earlier content is promised
+        return c->kv->prefix_len ? er_set_prefix_groups(c, nullptr, 0, 0) : ER_OK;
+    }
     HIPCHK(hipDeviceSynchronize());
     c->kv = std::make_unique<KvMem>();           // first: the old shape's memory makes room for the new one (this plan says: no cache)
     c->have_hidden = false;
@@ -1076,9 +1084,16 @@ static int forward_check(er_ctx* c, const char* who, const float* embeds, int B,
 // row0 >= 0 with in_queue: the B samples are cache rows [row0, row0 + B) of a larger reservation (er_queue_admit) - the cache base
 // pointers move by row0 rows, ypre receives rows [row0, row0 + B), and the generation state is left to the caller, so that no other
 // row is touched.
-static int prefill_run(er_ctx* c, const float* embeds, int B, int S, hipStream_t st, int row0 = 0, bool in_queue = false) {
+// pos0 > 0 (er_prefill_extend): the S inputs are positions [pos0, pos0 + S) behind a past the cache already holds - position embeddings
+// from pos0 + t (modeling_opt.py:345-357 with past_key_values), K/V into cache positions [pos0, pos0 + S) (the cache-writing launches
+// take the cache moved on by pos0 rows of a head), every query over keys [0, pos0 + t] (extend_attention), the state at position pos0 + S.
+static int extend_attention(er_ctx* c, const float* q, int ldq, const char* kc, const char* vc, float* out, int B, int n_new, int past_len,
+                            hipStream_t st);
+
+static int prefill_run(er_ctx* c, const float* embeds, int B, int S, hipStream_t st, int row0 = 0, bool in_queue = false, int pos0 = 0) {
     HIPCHK(hipSetDevice(c->device));
     const DecodePlan& p = c->kv->plan;
+    if (!in_queue) c->kv->valid_prefix = 0;      // until this pass has written its positions for every row
     ERCHK(ensure_weight_copies(c, p));
     const er_config& g = c->cfg;
     const int H = g.hidden_dim, I = g.intermediate_dim, NH = g.num_heads, D = c->D;
@@ -1094,27 +1109,30 @@ static int prefill_run(er_ctx* c, const float* embeds, int B, int S, hipStream_t
     const int tail = c->kv->prefix_len ? 0 : prefill_tail_rows(c, M), Mm = M - tail;
     // the causal attention of a single prefix is split over two key ranges per query tile (k_flash_attn_f32.h, KSP; same rule as the launcher)
     bool attn_ksplit = false;
-    if (!c->fast && flash32_ksplit(S, NH, B, D, true)) {
+    if (!c->fast && !pos0 && flash32_ksplit(S, NH, B, D, true)) {
         ERCHK(c->p_ap.ensure(flash32_part_o_floats(B, NH, S, D)));
         ERCHK(c->p_aml.ensure(flash32_part_ml_floats(B, NH, S)));
         attn_ksplit = true;
     }
 
-    // hidden = inputs_embeds + pos_embeds(0..S)                       modeling_opt.py:355-357
-    HIPRET(launch_add_pos(embeds, c->posemb, h, B, S, H, 0, st));
+    // hidden = inputs_embeds + pos_embeds(pos0 .. pos0 + S)           modeling_opt.py:355-357
+    HIPRET(launch_add_pos(embeds, c->posemb, h, B, S, H, pos0, st));
     for (int l = 0; l < g.num_layers; ++l) {
         const LayerW& L = c->layers[l];
         char* kc = c->kv->kc.p + ((long long)l * p.kv_lstride + (long long)row0 * p.kv_bstride) * c->kv_esz;
         char* vc = c->kv->vc.p + ((long long)l * p.kv_lstride + (long long)row0 * p.kv_bstride) * c->kv_esz;
+        // where this pass's first position lies in a head's slice: the cache-writing launches index positions from here
+        char *kc_new = kc + (long long)pos0 * D * c->kv_esz, *vc_new = vc + (long long)pos0 * D * c->kv_esz;
         if (!c->fast) {
             // q,k,v projections; k,v go straight into the cache layout      modeling_opt.py:185-196
             GemmArgs qa = gemm_args_default();
             qa.A = h; qa.lda = H; qa.B = L.wqkv; qa.ldb = H; qa.bias = L.bqkv; qa.C = q; qa.ldc = H;
             qa.M = M; qa.N = 3 * H; qa.K = H; qa.epi = GEPI_QKV;
-            qa.q = q; qa.kcache = (float*)kc; qa.vcache = (float*)vc; qa.S = S; qa.hidden = H; qa.head_dim = D; qa.l_cap = p.Lcap;
+            qa.q = q; qa.kcache = (float*)kc_new; qa.vcache = (float*)vc_new; qa.S = S; qa.hidden = H; qa.head_dim = D; qa.l_cap = p.Lcap;
             qa.kv_bstride = p.kv_bstride;
             HIPRET(launch_gemm(qa, 1, st));
-            {       // causal attention over the prefix, all samples and heads in one launch   modeling_opt.py:229
+            if (pos0) ERCHK(extend_attention(c, q, H, kc, vc, a, B, S, pos0, st));
+            else {  // causal attention over the prefix, all samples and heads in one launch   modeling_opt.py:229
                 Flash32Args f{};
                 f.Q = q; f.ldq = H; f.qs_b = (long long)S * H; f.qs_h = D;
                 f.K = (float*)kc; f.ldk = D; f.ks_b = p.kv_bstride; f.ks_h = (long long)p.Lcap * D;
@@ -1131,8 +1149,9 @@ static int prefill_run(er_ctx* c, const float* embeds, int B, int S, hipStream_t
             float* qkv = c->p_qkv.p;
             ERCHK(linear_hs(c, h, H, L.wqkv_h, L.bqkv, qkv, 3 * H, M, 3 * H, H, false, nullptr, 0, st));
             // (kv8: bytes into the cache, decode(encode(v)) back into the scratch)
-            HIPRET(launch_kv_scatter(qkv, kc, vc, c->kv8, M, S, H, D, p.Lcap, p.kv_bstride, st));
-            {
+            HIPRET(launch_kv_scatter(qkv, kc_new, vc_new, c->kv8, M, S, H, D, p.Lcap, p.kv_bstride, st));
+            if (pos0) ERCHK(extend_attention(c, qkv, 3 * H, kc, vc, a, B, S, pos0, st));
+            else {
                 Flash32Args f{};
                 f.Q = qkv; f.ldq = 3 * H; f.qs_b = (long long)S * 3 * H; f.qs_h = D;
                 f.K = qkv + H; f.ldk = 3 * H; f.ks_b = f.qs_b; f.ks_h = D;
@@ -1168,9 +1187,10 @@ static int prefill_run(er_ctx* c, const float* embeds, int B, int S, hipStream_t
     for (int b = 0; b < B; ++b)
         HIPCHK(hipMemcpyAsync(c->kv->ypre.p + (size_t)(row0 + b) * H, y + ((size_t)b * S + S - 1) * H, (size_t)H * 4, hipMemcpyDeviceToDevice, st));
     if (in_queue) return ER_OK;
-    hipLaunchKernelGGL(init_state_kernel, dim3((B + 63) / 64), dim3(64), 0, st, c->kv->st, B, S);
+    hipLaunchKernelGGL(init_state_kernel, dim3((B + 63) / 64), dim3(64), 0, st, c->kv->st, B, pos0 + S);
     HIPRET(hipGetLastError());
-    c->base_pos = S;
+    c->base_pos = pos0 + S;
+    c->kv->valid_prefix = pos0 + S;
     c->have_hidden = true;
     return ER_OK;
 }
@@ -1207,6 +1227,86 @@ extern "C" int er_prefill(er_ctx* c, const float* embeds, int B, int S, void* st
     c->kv->row_class = false;                  // er_feed / er_logits after this prefill run the plan's own kinds; er_decode chooses again
     ERCHK(prefill_run(c, embeds, B, S, pick(c, stream)));
     return c->kv->prefix_len ? prefix_groups_check(c, pick(c, stream)) : ER_OK;
+}
+
+// ------------------------------------------------------------------------------------ prefill with a past
+// One layer's attention of n_new new positions per row behind past_len cached ones: query (b, t) at q[(b * n_new + t) * ldq + h * D]
+// over keys [0, past_len + t] of row b's cache slice (kc / vc: this layer's, at the pass's first row), out rows [B * n_new][hidden].
+// The new positions' K/V are in the cache when this runs.  The route is extend_attn_route (er_extend_plan.h; ER_EXTEND_ATTN, read
+// per call: the tests and the bench compare both routes in one process).
+static int extend_attention(er_ctx* c, const float* q, int ldq, const char* kc, const char* vc, float* out, int B, int n_new, int past_len,
+                            hipStream_t st) {
+    const DecodePlan& p = c->kv->plan;
+    const int H = c->cfg.hidden_dim, NH = c->cfg.num_heads, D = c->D, T = past_len + n_new;
+    if (extend_attn_route(n_new, attn_extend_supported(D, c->kv_type), getenv("ER_EXTEND_ATTN")) == EXTEND_ROWS) {
+        ERCHK(c->p_ap.ensure(attn_extend_part_floats(B, n_new, NH, T, D)));
+        AttnExtendArgs a{};
+        a.q = q; a.ldq = ldq; a.kcache = kc; a.vcache = vc; a.part = c->p_ap.p; a.out = out; a.ldo = H;
+        a.H = NH; a.l_cap = p.Lcap; a.S = attn_extend_chunks(T); a.past_len = past_len; a.n_new = n_new;
+        a.kv_bstride = p.kv_bstride; a.sqrt_d = sqrtf((float)D);
+        HIPRET(launch_attn_extend(a, D, c->kv_type, B, st));
+        return ER_OK;
+    }
+    Flash32Args f{};
+    f.Q = q; f.ldq = ldq; f.qs_b = (long long)n_new * ldq; f.qs_h = D;
+    f.O = out; f.ldo = H; f.os_b = (long long)n_new * H; f.os_h = D;
+    f.N = n_new; f.M = T; f.sqrt_d = sqrtf((float)D); f.causal_off = past_len;
+    if (!c->fast) {         // the fp32 cache in place
+        f.K = (const float*)kc; f.ldk = D; f.ks_b = p.kv_bstride; f.ks_h = (long long)p.Lcap * D;
+        f.V = (const float*)vc; f.ldv = D; f.vs_b = p.kv_bstride; f.vs_h = (long long)p.Lcap * D;
+        HIPRET(launch_flash_attn_f32(f, D, true, NH, B, st));
+        return ER_OK;
+    }
+    // fast / kv8 mode: the fast prefill's kernels read fp32 rows - positions [0, T) of the cache, exact in fp32, gathered into scratch
+    ERCHK(c->p_kx.ensure((size_t)B * T * 2 * H));
+    float* kx = c->p_kx.p;
+    HIPRET(launch_kv_gather(kc, vc, kx, c->kv8, B * T, T, H, D, p.Lcap, p.kv_bstride, st));
+    f.K = kx; f.ldk = 2 * H; f.ks_b = (long long)T * 2 * H; f.ks_h = D;
+    f.V = kx + H; f.ldv = 2 * H; f.vs_b = f.ks_b; f.vs_h = D;
+    const bool f16s = D == 96 && c->knobs.prefill_attn_f16s != 0;
+    if (f16s) HIPRET(launch_flash_attn_f16s(f, D, true, NH, B, st));
+    else HIPRET(launch_flash_attn_f32(f, D, true, NH, B, st));
+    return ER_OK;
+}
+
+extern "C" int er_prefill_extend(er_ctx* c, const float* embeds, int B, int past_len, int n_new, void* stream) {
+    if (!c || !embeds || B <= 0 || n_new <= 0 || past_len <= 0) return fail(ER_ERR_INVALID, "er_prefill_extend: bad argument");
+    if (past_len > 0x3fffffff - n_new) return fail(ER_ERR_CAPACITY, "er_prefill_extend: past_len %d + n_new %d", past_len, n_new);
+    // the forward pass's own checks at the length the cache will hold, and its 32-bit row rule over the rows this pass runs
+    ERCHK(forward_check(c, "er_prefill_extend", embeds, B, past_len + n_new));
+    KvMem& kv = *c->kv;
+    if (past_len + n_new > c->cfg.max_positions) return fail(ER_ERR_CAPACITY, "er_prefill_extend: position table exhausted (%d)", c->cfg.max_positions);
+    const int valid = c->have_hidden ? kv.valid_prefix : 0;
+    switch (extend_past_check(past_len, valid, kv.prefix_len)) {
+        case 1:
+            return fail(ER_ERR_INVALID, "er_prefill_extend: past_len %d outside the prefix this reservation holds for all rows, [1, %d] (%s)", past_len, valid,
+                        valid ? "positions behind it are rewritten, positions beyond it were never prefilled" : "call er_prefill first");
+        case 2:
+            return fail(ER_ERR_INVALID, "er_prefill_extend: past_len %d is below the %d positions the prefix groups share (keep the shared prefix, or clear the groups)",
+                        past_len, kv.prefix_len);
+    }
+    if ((long long)B * (past_len + n_new) > 0x7fffffffLL)
+        return fail(ER_ERR_CAPACITY, "er_prefill_extend: %d x %d positions overflow the 32-bit row indexing of the K/V gather (split the batch)", B, past_len + n_new);
+    kv.row_class = false;                      // as er_prefill
+    ERCHK(prefill_run(c, embeds, B, n_new, pick(c, stream), 0, false, past_len));
+    return ER_OK;
+}
+
+// rows of the embed_num_face table (core/models.py:137): what encode_cond appends behind the cloud's tokens, without the point encoder
+extern "C" int er_embed_num_face(er_ctx* c, const int32_t* face_bucket, int B, float* out, void* stream) {
+    if (!c || !face_bucket || !out || B <= 0) return fail(ER_ERR_INVALID, "er_embed_num_face: bad argument");
+    if (c->cfg.num_face_buckets == 0) return fail(ER_ERR_UNSUPPORTED, "er_embed_num_face: the model has no face-count condition (num_face_buckets == 0)");
+    ERCHK(er_finalize_weights(c));
+    for (int b = 0; b < B; ++b)
+        if (face_bucket[b] < 0 || face_bucket[b] >= c->cfg.num_face_buckets)
+            return fail(ER_ERR_INVALID, "er_embed_num_face: bucket %d outside [0, %d)", face_bucket[b], c->cfg.num_face_buckets);
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t st = pick(c, stream);
+    ERCHK(c->e_ids.ensure((size_t)B));
+    HIPCHK(hipMemcpyAsync(c->e_ids.p, face_bucket, (size_t)B * sizeof(int), hipMemcpyHostToDevice, st));
+    HIPRET(launch_gather_rows(c->embed_num_face, c->e_ids.p, out, B, c->cfg.hidden_dim, (long long)c->cfg.hidden_dim, st));
+    HIPCHK(hipStreamSynchronize(st));     // `face_bucket` is caller-owned host memory
+    return ER_OK;
 }
 
 // ------------------------------------------------------------------------------------ forked prefill
@@ -2139,6 +2239,29 @@ static int k_attn_shared_run(const char* who, bool mfma, const float* q, const v
     hipError_t e = mfma ? launch_attn_prefix_mfma_d<D>(s, groups, st)                      // launch_kind_t kinds 1 and 2, shared_mfma / shared_attn
                         : launch_attn_prefix_d<D>(s, kv_half != 0, groups, st);
     if (e == hipSuccess) e = launch_attn_suffix_merge_d<D>(s, kv_half != 0, B, st);
+    hipError_t e2 = hipStreamSynchronize(st);
+    HIPRET(e);
+    HIPRET(e2);
+    return ER_OK;
+}
+
+// the rows route of extend_attention (attn_extend_kernel + attn_extend_merge_kernel) on caller-owned q and caches
+extern "C" int er_k_attn_extend(const float* q, const void* k, const void* v, int past_len, int n_new, float* out, int B, int heads, int l_cap,
+                                int head_dim, int kv_half, void* stream) {
+    if (!q || !k || !v || !out || B < 1 || B > 65535 || heads < 1 || l_cap < 1) return fail(ER_ERR_INVALID, "er_k_attn_extend: bad argument");
+    if (kv_half < 0 || kv_half > 2) return fail(ER_ERR_INVALID, "er_k_attn_extend: kv_half %d (0 = fp32, 1 = fp16, 2 = e4m3 bytes)", kv_half);
+    if (!attn_extend_supported(head_dim, kv_half))
+        return fail(ER_ERR_UNSUPPORTED, "er_k_attn_extend: head_dim %d with cache type %d (96: every cache type; 64: fp32 and fp16)", head_dim, kv_half);
+    if (past_len < 1 || n_new < 1 || n_new > 65535) return fail(ER_ERR_INVALID, "er_k_attn_extend: past_len %d, n_new %d", past_len, n_new);
+    if (past_len > l_cap - n_new) return fail(ER_ERR_CAPACITY, "er_k_attn_extend: past_len %d + n_new %d > l_cap %d", past_len, n_new, l_cap);
+    hipStream_t st = (hipStream_t)stream;
+    DevBuf<float> part;
+    ERCHK(part.ensure(attn_extend_part_floats(B, n_new, heads, past_len + n_new, head_dim)));
+    AttnExtendArgs a{};
+    a.q = q; a.ldq = heads * head_dim; a.kcache = k; a.vcache = v; a.part = part.p; a.out = out; a.ldo = heads * head_dim;
+    a.H = heads; a.l_cap = l_cap; a.S = attn_extend_chunks(past_len + n_new); a.past_len = past_len; a.n_new = n_new;
+    a.kv_bstride = (long long)heads * l_cap * head_dim; a.sqrt_d = sqrtf((float)head_dim);
+    hipError_t e = launch_attn_extend(a, head_dim, kv_half, B, st);       // extend_attention, rows route
     hipError_t e2 = hipStreamSynchronize(st);
     HIPRET(e);
     HIPRET(e2);

@@ -135,3 +135,25 @@ def group_jobs(jobs, mine: Sequence[int], n_points_of, rows_max: int):
         for c0 in range(0, len(members), max(1, rows_max)):
             out.append((nf, members[c0:c0 + max(1, rows_max)]))
     return out
+
+
+def group_jobs_keep_cond(jobs, mine: Sequence[int], n_points_of, rows_max: int):
+    """``group_jobs`` ordered for ``LMM.generate(keep_cond=True)``: the (path, repeat) items of this rank are chunked first - same number
+    of points, the same face counts in the same order, at most rows_max items - and every chunk then runs its face counts one after the
+    other, so consecutive calls carry the SAME clouds in the same rows and only the first of them pays the point encoder and the cond
+    positions.  Same jobs, each exactly once, in calls of the same shape as ``group_jobs`` makes when every item has every face count.
+    -> [(num_faces, [job index])]."""
+    items = {}                                   # (path, repeat) -> [(num_faces, job)] in job order
+    for j in mine:
+        items.setdefault((jobs[j][0], jobs[j][1]), []).append((jobs[j][2], j))
+    classes = {}
+    for it, by_nf in items.items():
+        classes.setdefault((n_points_of(it[0]), tuple(nf for nf, _ in by_nf)), []).append(it)
+    out = []
+    step = max(1, rows_max)
+    for (_, nfs), members in classes.items():
+        for c0 in range(0, len(members), step):
+            chunk = members[c0:c0 + step]
+            for k, nf in enumerate(nfs):
+                out.append((nf, [items[it][k][1] for it in chunk]))
+    return out

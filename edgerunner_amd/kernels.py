@@ -324,6 +324,23 @@ def attn_shared(q, k_cache, v_cache, lens, leaders, prefix_len, out_xt=None, pre
     return out
 
 
+def attn_extend(q, k_cache, v_cache, past_len, out=None):
+    """The rows route of ``er_prefill_extend``'s attention (csrc/k_attn_extend.h; ``er_k_attn_extend``): q [B, n_new, heads * D] fp32,
+    caches [B, heads, Lcap, D] fp32 / fp16 / uint8 (e4m3 bytes) holding positions [0, past_len + n_new) -> out [B, n_new, heads * D],
+    query (b, t) over keys [0, past_len + t] of row b.  ``out``: a caller's buffer of that size (the tests put guards around it)."""
+    lib = native.load_library()
+    B, H, Lcap, D = k_cache.shape
+    n_new = q.shape[1]
+    assert q.shape == (B, n_new, H * D) and q.dtype == torch.float32 and q.is_contiguous() and v_cache.shape == k_cache.shape
+    kv_half = {torch.float32: 0, torch.float16: 1, torch.uint8: 2}[k_cache.dtype]
+    if out is None:
+        out = torch.empty((B, n_new, H * D), dtype=torch.float32, device=q.device)
+    assert out.numel() == B * n_new * H * D and out.dtype == torch.float32 and out.is_contiguous()
+    native.check(lib.er_k_attn_extend(native.ptr(q), native.ptr(k_cache), native.ptr(v_cache), int(past_len), n_new, native.ptr(out), B, H,
+                                      Lcap, D, kv_half, _st()), "er_k_attn_extend")
+    return out
+
+
 def attn_outproj3(q, k_cache, v_cache, length, wo, bo, resid):
     """Version-3 single-row path: y = Wo . attention(q, K[:length], V[:length]) + bo + resid.
     q [1536] fp32; caches [16,Lcap,96] fp32 or fp16; wo [1536,1536] fp32 or fp16."""

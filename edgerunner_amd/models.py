@@ -80,6 +80,46 @@ def fork_plan(conds, resume_ids=None):
     return order, [cls[b] for b in order], len(firsts)
 
 
+def cond_key(conds) -> bytes:
+    """The stored bits of a ``conds`` batch with its shape and dtype: two batches are the same input to the point encoder exactly when
+    their keys are equal (the comparison of ``prefix_leaders`` / ``fork_plan``: -0.0 and 0.0 differ, a NaN equals the same NaN)."""
+    a = conds.detach().cpu().numpy() if isinstance(conds, torch.Tensor) else np.asarray(conds)
+    return repr((a.shape, a.dtype.str)).encode() + b"|" + np.ascontiguousarray(a).tobytes()
+
+
+def kept_prefix_len(num_cond_tokens: int, use_num_face_cond: bool) -> int:
+    """Cache positions that depend on the cloud alone: ``encode_cond`` appends the face-count token BEHIND the conditioning tokens
+    (core/models.py:134-141) and the decoder is causal, so everything before that token survives another face count."""
+    return num_cond_tokens - 1 if use_num_face_cond else num_cond_tokens
+
+
+class CondRecord:
+    """What ``generate_ids(keep_cond=True)`` remembers of a prefill: the clouds' bits, the batch, the kept prefix length, and the decoder
+    context with its reservation and ``cache_epoch`` right after that prefill.  ``usable`` says whether a later call may extend that
+    prefix instead of running the full pass; any mismatch means the full pass (which records again).  Host data only."""
+
+    def __init__(self):
+        self.forget()
+
+    def forget(self):
+        self.key, self.batch, self.past, self.dec_id, self.reserved, self.epoch = None, 0, 0, None, (0, 0), -1
+
+    def remember(self, conds, batch: int, past: int, dec_id: int, reserved, epoch: int):
+        self.key, self.batch, self.past = cond_key(conds), int(batch), int(past)
+        self.dec_id, self.reserved, self.epoch = dec_id, tuple(reserved), int(epoch)
+
+    def usable(self, conds, batch: int, need_len: int, dec_id: int, reserved, epoch: int, queue_open: bool = False) -> bool:
+        """``need_len``: positions the call will hold at most (prefix + new tokens + 1).  The context must be the recorded one, its
+        reservation and cache untouched since (``cache_epoch``), no queue open, and the reservation must already fit."""
+        if self.key is None or queue_open or conds is None:
+            return False
+        if dec_id != self.dec_id or tuple(reserved) != self.reserved or int(epoch) != self.epoch:
+            return False
+        if int(batch) != self.batch or self.reserved[0] != self.batch or self.reserved[1] < int(need_len) or self.past < 1:
+            return False
+        return cond_key(conds) == self.key
+
+
 def fork_streams(order, row_streams=None) -> List[int]:
     """The Philox stream of every permuted place under ``fork_prefill``: the stream the caller's row ``order[i]`` would have had - its
     original index, or the caller's ``row_streams`` entry - so that sample-mode ids do not depend on the permutation."""
@@ -248,6 +288,8 @@ class LMM:
         self._released = False                 # release_checkpoint() was called: the context cannot be re-created
         self.last_logprobs = None              # generate(output_logprobs=True): {"model", "policy"} float32 [B, n] on the device
         self.last_queue_logprobs = None        # generate_queue(output_logprobs=True): per job (model, policy) numpy arrays
+        self._cond_record = CondRecord()       # generate_ids(keep_cond=True): the prefix a later call may extend
+        self.last_prefill = None               # "full" | "extend": which prefill the last generate_ids call ran
         if precision is not None:
             self._materialize()
 
@@ -286,6 +328,7 @@ class LMM:
         """Returns (missing, unexpected) like nn.Module.load_state_dict.  The dict is kept by reference (no copy) so a
         later ``.half()`` / ``.float()`` can rebuild the native context in the other storage precision."""
         self._sources.append((sd, strict))
+        self._cond_record.forget()
         if self._dec is not None:
             prev = self._dec.direct_loads
             out = self._dec.load_state_dict(sd, strict=strict)
@@ -320,6 +363,7 @@ class LMM:
                 f"the {self.precision} native context (mesh_decoder.load_state_iter / load_state_dict); they cannot be "
                 f"re-stored. Create LMM(opt, device, precision='{want}') instead.")
         self._dtype, self._w8, self._w4 = dtype, w8, w4
+        self._cond_record.forget()
         if self._dec is not None:            # rebuild lazily from the retained checkpoints in the new storage precision
             self._dec.close()
             self._dec = None
@@ -448,8 +492,17 @@ class LMM:
     def generate_ids(self, conds, num_faces=1000, resume_ids=None, tokenizer=None, max_new_tokens=None,
                      min_new_tokens: int = 0, seed: Optional[int] = None, row_streams=None, share_prefix=False, *,
                      temperature: Optional[float] = None, top_p: Optional[float] = None, top_k: Optional[int] = None,
-                     output_logprobs: bool = False, fork_prefill: bool = False) -> torch.Tensor:
+                     output_logprobs: bool = False, fork_prefill: bool = False, keep_cond: bool = False) -> torch.Tensor:
         """Everything of LMM.generate up to the HF call's return value (core/models.py:215-303).
+
+        ``keep_cond=True``: after the prefill the model remembers a host copy of ``conds``, the batch and the cache positions that
+        depend on the clouds alone (``kept_prefix_len``: num_cond_tokens - 1, the face-count token comes behind them).  A later call
+        with ``keep_cond=True``, bit-equal ``conds`` (``cond_key``), the same batch, no queue open, the decoder's cache untouched in
+        between (decoding does not count) and a reservation that already fits skips the point encoder and the cond positions: it runs
+        ``prefill_extend`` over [face-count token, BOS, resume_ids ...] behind the kept prefix - another face count or another resume
+        tail costs its few positions.  Anything else silently takes the full path and records again; ``.half()`` / ``.float()`` /
+        ``load_state_dict`` and any re-reserve forget the record.  ``last_prefill`` says which path ran ("full" | "extend").  The extend
+        path with ``fork_prefill=True`` or ``share_prefix`` raises NotImplementedError for now; a full-path call with them is fine.
 
         ``fork_prefill=True``: rows whose ``conds`` entry and ``resume_ids`` row are both bit-equal (``fork_plan``) are encoded and
         prefilled ONCE; the repeats start from a copy of that row's cache rows and last hidden state (``er_prefill_fork``), which is
@@ -477,6 +530,15 @@ class LMM:
             raise ValueError(f"share_prefix must be a bool, 'valu' or 'mfma', got {share_prefix!r}")
         opt = self.opt
         B = conds.shape[0]
+        max_new_tokens = opt.max_seq_length if max_new_tokens is None else max_new_tokens
+        rec, dec = self._cond_record, self.mesh_decoder
+        past = kept_prefix_len(opt.num_cond_tokens, self.dims.use_num_face_cond)
+        n_resume = 0 if resume_ids is None else resume_ids.shape[1]
+        extend = bool(keep_cond) and rec.usable(conds, B, opt.num_cond_tokens + 1 + n_resume + max_new_tokens + 1, id(dec), dec._reserved,
+                                                dec.cache_epoch)
+        if extend and (fork_prefill or share_prefix):
+            raise NotImplementedError("generate_ids: keep_cond=True would extend the kept cond prefix here, which does not combine with "
+                                      "fork_prefill / share_prefix yet; drop one of them for this call")
         fork = None
         if fork_prefill:
             order, leader, n_leaders = fork_plan(conds, resume_ids)
@@ -487,7 +549,10 @@ class LMM:
                 conds = conds[first.to(conds.device)]
                 resume_ids = None if resume_ids is None else resume_ids[first.to(resume_ids.device)]
         N = conds.shape[0]                     # rows that are encoded and prefilled: B, or the leaders of a fork
-        cond_embeds = self.encode_cond(conds, [num_faces] * N)["cond_embeds"]
+        if extend:      # the positions behind the kept prefix: the face-count token (when the model has one), then BOS and the resume ids
+            cond_embeds = dec.embed_num_face([quantize_num_faces(int(num_faces))] * N)[:, None, :] if self.dims.use_num_face_cond else None
+        else:
+            cond_embeds = self.encode_cond(conds, [num_faces] * N)["cond_embeds"]
         input_ids = torch.full((N, 1), opt.bos_token_id, dtype=torch.long)
         if resume_ids is not None:
             input_ids = torch.cat((input_ids, resume_ids.to("cpu", torch.long)), dim=1)
@@ -497,7 +562,6 @@ class LMM:
         if fn.er_grammar == native.ER_GRAMMAR_NONE:
             print("[WARN] prefix_allowed_tokens_fn is not defined for meto backend:", opt.meto_backend)
             fn = None
-        max_new_tokens = opt.max_seq_length if max_new_tokens is None else max_new_tokens
         if num_faces < 0:
             num_tokens = torch.full((B,), -1, dtype=torch.long)
         else:
@@ -507,6 +571,8 @@ class LMM:
                       prefix_allowed_tokens_fn=fn, min_new_tokens=min_new_tokens, seed=seed, row_streams=row_streams)
         if fork is not None:
             kwargs["fork_leaders"] = fork[1]
+        if extend:
+            kwargs["extend_past"] = past
         if share_prefix and (B > 4 or os.environ.get("ER_FORCE_BATCHED", "")[:1] == "1"):
             kwargs["prefix_groups"] = (fork[1] if fork is not None else prefix_leaders(conds), opt.num_cond_tokens + 1)
             if isinstance(share_prefix, str):
@@ -525,8 +591,12 @@ class LMM:
         if output_logprobs:
             kwargs["output_logprobs"] = True
         self.last_logprobs = None
+        rec.forget()                           # whatever happens in the call, the old record is not the cache's any more
         out = self.mesh_decoder.generate(**kwargs)
         self.last_logprobs = self.mesh_decoder.last_logprobs
+        self.last_prefill = "extend" if extend else "full"
+        if keep_cond and fork is None and not kwargs.get("prefix_groups"):      # every row holds its own cloud's prefix
+            rec.remember(conds, B, past, id(dec), dec._reserved, dec.cache_epoch)
         if fork is not None:                   # back to the caller's row order: permuted place i holds the caller's row order[i]
             back = torch.empty(B, dtype=torch.long)
             back[torch.as_tensor(fork[0], dtype=torch.long)] = torch.arange(B)
@@ -607,15 +677,15 @@ class LMM:
     def generate(self, conds, num_faces=1000, resume_ids=None, tokenizer=None, max_new_tokens=None, clean=True,
                  min_new_tokens: int = 0, seed: Optional[int] = None, row_streams=None, share_prefix=False, *,
                  temperature: Optional[float] = None, top_p: Optional[float] = None, top_k: Optional[int] = None,
-                 output_logprobs: bool = False, fork_prefill: bool = False):
-        """-> (meshes, all_tokens) like core/models.py:204-319.  ``share_prefix``, ``fork_prefill``, the sampling controls and ``output_logprobs``
+                 output_logprobs: bool = False, fork_prefill: bool = False, keep_cond: bool = False):
+        """-> (meshes, all_tokens) like core/models.py:204-319.  ``keep_cond``: see ``generate_ids``.  ``share_prefix``, ``fork_prefill``, the sampling controls and ``output_logprobs``
         (-> ``last_logprobs``, columns = the generated ids, without the resume prefix ``all_tokens`` echoes): see ``generate_ids``.  ``tokenizer`` is a
         ``edgerunner_amd.meto.Engine`` (or None for the 9-coordinate layout); each mesh is a
         ``edgerunner_amd.meto.Mesh`` - ``.vertices``, ``.faces``, ``.export(path)``, the members the reference's callers
         use of the trimesh objects it returns (trimesh itself is absent here); it still unpacks as ``v, f = mesh``."""
         output_ids = self.generate_ids(conds, num_faces, resume_ids, tokenizer, max_new_tokens, min_new_tokens, seed, row_streams, share_prefix,
                                        temperature=temperature, top_p=top_p, top_k=top_k, output_logprobs=output_logprobs,
-                                       fork_prefill=fork_prefill)
+                                       fork_prefill=fork_prefill, keep_cond=keep_cond)
         from .meto import Engine, save_mesh
         meshes: List[Optional[object]] = []
         all_tokens: List[np.ndarray] = []

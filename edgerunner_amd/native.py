@@ -44,6 +44,7 @@ EXPORTS = [
     "er_k_softmax_batched", "er_k_kv_scatter", "er_k_split_rows_f16", "er_k_add_pos", "er_k_gather_rows", "er_k_point_embed", "er_k_geglu",
     "er_k_gelu", "er_k_silu", "er_k_ln_modulate", "er_k_adaln_gate", "er_k_adaln_gate_all", "er_k_timestep_embed", "er_k_ddim_cfg_step",
     "er_k_clip_preprocess", "er_k_clip_im2col", "er_k_clip_assemble",
+    "er_prefill_extend", "er_embed_num_face", "er_k_attn_extend",
 ]
 
 
@@ -147,6 +148,8 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.er_embed_tokens.argtypes = [vp, C.POINTER(C.c_int32), ci, ci, vp, vp]
     lib.er_prefill.argtypes = [vp, vp, ci, ci, vp]
     lib.er_prefill_fork.argtypes = [vp, vp, ci, ci, C.POINTER(C.c_int32), ci, vp]
+    lib.er_prefill_extend.argtypes = [vp, vp, ci, ci, ci, vp]
+    lib.er_embed_num_face.argtypes = [vp, C.POINTER(C.c_int32), ci, vp, vp]
     lib.er_k_kv_fork.argtypes = [vp, vp, ci, ci, ci, ci, ci, ci, C.POINTER(C.c_int32), C.POINTER(C.c_int32), ci, ci, vp]
     lib.er_logits.argtypes = [vp, vp, vp]
     lib.er_score.argtypes = [vp, vp, vp, ci, ci, vp, vp, vp, vp, vp]
@@ -203,6 +206,7 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.er_k_attn_stream_xt.argtypes = [vp, vp, vp, C.POINTER(C.c_int32), vp, vp, ci, ci, ci, ci, vp]
     lib.er_k_attn_shared.argtypes = [vp, vp, vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), ci, vp, vp, ci, ci, ci, ci, vp]
     lib.er_k_attn_shared_mfma.argtypes = lib.er_k_attn_shared.argtypes
+    lib.er_k_attn_extend.argtypes = [vp, vp, vp, ci, ci, vp, ci, ci, ci, ci, ci, vp]
     lib.er_k_attn_decode.argtypes = [vp, vp, vp, C.POINTER(C.c_int32), vp, ci, ci, ci, ci, ci, ci, ci, vp]
     lib.er_k_attn_outproj3.argtypes = [vp, vp, vp, ci, vp, vp, vp, vp, ci, ci, ci, vp]
     lib.er_k_w8_quantize.argtypes = [vp, ci, ci, ci, ci, vp, vp, vp, vp, vp]

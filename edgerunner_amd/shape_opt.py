@@ -105,6 +105,9 @@ class NativeShapeOPT:
                          "er_set_point_encoder_mode")
         self.stream = torch.cuda.Stream(device=self.device)
         self._reserved = (0, 0)
+        # counts every call that rewrites the cache rows from position 0 (or may): what a caller that keeps a prefix for
+        # ``prefill_extend`` compares to know that the prefix is still its own (LMM.generate_ids(keep_cond=True))
+        self.cache_epoch = 0
         self.last_decode_ms = 0.0
         self.last_logprobs = None     # {"model", "policy"}: float32 [B, n] on the device after a generate(output_logprobs=True)
         # the prefix pass of the next grouping, as er_create read it (env ER_PREFIX_PASS; "mfma" holds on an fp16 cache only)
@@ -148,6 +151,7 @@ class NativeShapeOPT:
             unexpected.append(key)
 
     def _finish_load(self, strict, unexpected):
+        self.cache_epoch += 1                  # a cache written under other weights is nobody's prefix
         rc = self.lib.er_finalize_weights(self._ctx)
         missing = []
         if rc < 0:
@@ -175,6 +179,7 @@ class NativeShapeOPT:
     def reserve(self, batch: int, max_len: int):
         native.check(self.lib.er_kv_reserve(self._ctx, batch, max_len), "er_kv_reserve")
         self._reserved = (batch, max_len)
+        self.cache_epoch += 1
 
     # -- pieces of LMM.generate --------------------------------------------------------------
     def encode_cond(self, conds: Optional[torch.Tensor], face_buckets) -> torch.Tensor:
@@ -233,6 +238,29 @@ class NativeShapeOPT:
         with self._enter():
             native.check(self.lib.er_prefill(self._ctx, native.ptr(x), B, S, self._sp()), "er_prefill")
         self._exit()
+        self.cache_epoch += 1
+
+    def embed_num_face(self, buckets) -> torch.Tensor:
+        """``er_embed_num_face``: rows of the embed_num_face table for ``buckets`` (``quantize_num_faces`` of the face counts) ->
+        float32 [B, hidden] on the device: the token ``encode_cond`` appends behind the cloud's, without the point encoder."""
+        buckets = [int(v) for v in buckets]
+        with self._enter():
+            out = torch.empty((len(buckets), self.dims.hidden_dim), dtype=torch.float32, device=self.device)
+            native.check(self.lib.er_embed_num_face(self._ctx, native.i32_array(buckets), len(buckets), native.ptr(out), self._sp()),
+                         "er_embed_num_face")
+        self._exit()
+        return out
+
+    def prefill_extend(self, embeds_new: torch.Tensor, past_len: int):
+        """``er_prefill_extend``: the forward pass over the ``embeds_new.shape[1]`` positions behind ``past_len`` cache positions that
+        the last full or extending pass on this reservation wrote and that are kept.  The reservation is the caller's: the call never
+        reserves (a new reservation has no past), so ``past_len + n_new`` plus what is to be decoded must fit the reserved length."""
+        x = embeds_new.to(self.device, torch.float32).contiguous()
+        B, n_new, _ = x.shape
+        with self._enter():
+            native.check(self.lib.er_prefill_extend(self._ctx, native.ptr(x), B, int(past_len), n_new, self._sp()), "er_prefill_extend")
+        self._exit()
+        self.cache_epoch += 1
 
     def _reserve_and_group(self, B, S, max_new_tokens, prefix_groups, prefix_pass):
         need = S + max_new_tokens + 1
@@ -261,6 +289,7 @@ class NativeShapeOPT:
             native.check(self.lib.er_prefill_fork(self._ctx, native.ptr(x), n_leaders, S, native.i32_array(leaders), len(leaders),
                                                   self._sp()), "er_prefill_fork")
         self._exit()
+        self.cache_epoch += 1
 
     def logits(self) -> torch.Tensor:
         with self._enter():
@@ -293,6 +322,7 @@ class NativeShapeOPT:
             native.check(self.lib.er_score(self._ctx, native.ptr(x), native.ptr(lab), B, S, native.ptr(nll), native.ptr(pred),
                                            native.ptr(logits), native.ptr(loss), self._sp()), "er_score")
         self._exit()
+        self.cache_epoch += 1
         return {"nll": nll, "pred": pred, "logits": logits, "loss": loss}
 
     def point_latent(self, conds: torch.Tensor):
@@ -323,12 +353,13 @@ class NativeShapeOPT:
                  prefix_allowed_tokens_fn: Optional[Callable] = None, num_beams: int = 1, do_sample: bool = False,
                  top_k: int = 50, min_new_tokens: int = 0, seed: Optional[int] = None, row_streams=None,
                  prefix_groups=None, temperature: float = 1.0, top_p: float = 1.0, output_logprobs: bool = False,
-                 prefix_pass=None, fork_leaders=None, **unused) -> torch.Tensor:
+                 prefix_pass=None, fork_leaders=None, extend_past: Optional[int] = None, **unused) -> torch.Tensor:
         """Drop-in for ``ShapeOPT.generate`` as called at core/models.py:303.
         ``num_tokens`` is accepted and ignored exactly like the reference decoder
         ignores it (modeling_opt.py:324,467,546).  ``prefix_groups`` and ``prefix_pass`` go to ``prefill``.  ``fork_leaders``: a
         leaders-first table for a batch of ``len(fork_leaders)`` rows; ``inputs_embeds`` then holds the leaders only and the prefill is
-        ``prefill_fork``.
+        ``prefill_fork``.  ``extend_past``: ``inputs_embeds`` holds only the positions behind that many kept cache positions and
+        the prefill is ``prefill_extend`` on the reservation as it stands (ValueError when it does not fit).
 
         ``temperature``, ``top_k`` (0: no top-k filter) and ``top_p`` act in sample mode, in the order of HF's warpers; greedy mode
         accepts them and picks the same ids.  ``output_logprobs=True`` leaves ``last_logprobs = {"model", "policy"}`` (float32
@@ -344,7 +375,15 @@ class NativeShapeOPT:
                 raise ValueError(f"{name}_token_id={got} differs from the context's {want}")
         if max_new_tokens is None:
             max_new_tokens = self.opt.max_seq_length
-        if fork_leaders is None:
+        if extend_past is not None:
+            if fork_leaders is not None or prefix_groups is not None:
+                raise ValueError("extend_past combines with neither fork_leaders nor prefix_groups")
+            B = inputs_embeds.shape[0]
+            need = int(extend_past) + inputs_embeds.shape[1] + max_new_tokens + 1
+            if self._reserved[0] != B or self._reserved[1] < need:
+                raise ValueError(f"extend_past: the reservation {self._reserved} does not fit {B} rows of {need} positions")
+            self.prefill_extend(inputs_embeds, extend_past)
+        elif fork_leaders is None:
             B = inputs_embeds.shape[0]
             self.prefill(inputs_embeds, max_new_tokens, prefix_groups=prefix_groups, prefix_pass=prefix_pass)
         else:
@@ -466,6 +505,7 @@ class NativeShapeOPT:
         with self._enter():
             native.check(self.lib.er_queue_begin(self._ctx, C.byref(p), int(check_every), self._sp()), "er_queue_begin")
         self._exit()
+        self.cache_epoch += 1
 
     def queue_admit(self, row0: int, inputs_embeds: torch.Tensor, stream_ids=None, budgets=None):
         """Prefills rows [row0, row0 + n) from ``inputs_embeds`` [n, S, hidden] in one forward pass and starts their jobs."""

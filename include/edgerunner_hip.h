@@ -307,6 +307,30 @@ int er_set_prefix_pass(er_ctx* ctx, int pass);
  * call is allowed and er_prefill's device comparison of the followers' prefixes is skipped: those bytes were just copied from the leader. */
 int er_prefill_fork(er_ctx* ctx, const float* embeds_dev, int n_leaders, int seq_len, const int32_t* leader_host, int n, void* stream);
 
+/* Prefill with a past: the forward pass over n_new new positions [past_len, past_len + n_new) of every row of the reserved batch, behind
+ * past_len cache positions that are kept (modeling_opt.py:191-192, 345-357 with past_key_values).  embeds_new_dev float[batch, n_new,
+ * hidden].  Position embeddings come from past_len + t; query t attends to the row's cached keys [0, past_len) and the new keys up to
+ * itself; the new positions' K/V go into the cache at their positions, rounded as the mode's prefill rounds them (fp16; kv8: e4m3, in
+ * the cache and in what the attention reads); the generation state starts at position past_len + n_new.  Afterwards the context is what
+ * er_prefill leaves: er_logits, er_feed and er_decode follow as usual.  The decoder is causal and encode_cond puts the face-count token
+ * BEHIND the cloud's tokens (core/models.py:134-141), so another face count, another BOS / resume tail or a rewind of one row batch
+ * costs its few positions, not the cloud's 2049.
+ * The past: the context records the prefix [0, n) that the last er_prefill / er_prefill_fork / er_score / er_prefill_extend on this
+ * reservation wrote for ALL rows; er_decode and er_feed write behind it; er_kv_reserve, er_set_prefix_groups, a queue and a failed
+ * forward pass reset it to 0.  1 <= past_len <= n; positions >= past_len are overwritten (rewinding is the point of the call).
+ * Attention: n_new up to a measured threshold (csrc/er_extend_plan.h) walks the new queries over 128-key chunks of the row's cache
+ * held in registers (csrc/k_attn_extend.h, every cache type); beyond it the prefill's flash kernels run with a causal offset - on the
+ * fp32 cache in place, in fast / kv8 mode on fp32 rows gathered from the cache.  ER_EXTEND_ATTN=rows|flash forces a route.
+ * ER_ERR_INVALID: bad arguments, batch != the reserved batch, a queue is open, past_len outside [1, n], prefix groups set and past_len
+ * < their prefix_len.  ER_ERR_CAPACITY: past_len + n_new >= the reserved length or > max_positions, or er_prefill's 32-bit row rule.
+ * All before any launch. */
+int er_prefill_extend(er_ctx* ctx, const float* embeds_new_dev, int batch, int past_len, int n_new, void* stream);
+
+/* Rows of the embed_num_face table (core/models.py:137): face_bucket_host int[batch] = quantize_num_faces(num_faces) -> out_dev
+ * float[batch, hidden], the token encode_cond appends behind the cloud's - for er_prefill_extend's inputs, without the point encoder.
+ * ER_ERR_UNSUPPORTED when num_face_buckets == 0; ER_ERR_INVALID for a bucket outside the table. */
+int er_embed_num_face(er_ctx* ctx, const int32_t* face_bucket_host, int batch, float* out_dev, void* stream);
+
 /* ---- mesh tokenizer (host code, no device work): the reference's pybind11 module meto (meto/src/bindings.cpp,
  * meto.Engine(discrete_bins, verbose, backend), meto/meto/__init__.py:21-54) for the backends Options.meto_backend
  * admits (core/options.py:26). */
@@ -551,6 +575,14 @@ int er_k_attn_shared(const float* q_dev, const void* k_dev, const void* v_dev, c
  * caches only (kv_half = 1; anything else is ER_ERR_UNSUPPORTED). */
 int er_k_attn_shared_mfma(const float* q_dev, const void* k_dev, const void* v_dev, const int32_t* len_host, const int32_t* leader_host,
                           int prefix_len, float* out_dev, void* out_xt_dev, int batch, int heads, int l_cap, int kv_half, void* stream);
+/* The rows route of er_prefill_extend's attention (csrc/k_attn_extend.h: attn_extend_kernel + attn_extend_merge_kernel) on caller-owned
+ * memory: q_dev float[batch, n_new, heads * head_dim], caches [batch, heads, l_cap, head_dim] of the type kv_half names (0 = fp32,
+ * 1 = fp16, 2 = e4m3 bytes) holding positions [0, past_len + n_new); out_dev float[batch, n_new, heads * head_dim], row (b, t) = the
+ * attention of query (b, t) over keys [0, past_len + t] of row b.  Cache positions >= past_len + n_new are never read.  head_dim 96
+ * with every cache type, 64 with fp32 and fp16 (else ER_ERR_UNSUPPORTED).  ER_ERR_INVALID: past_len < 1, n_new outside [1, 65535];
+ * ER_ERR_CAPACITY: past_len + n_new > l_cap - all before anything is allocated or launched.  Blocks until the work is complete. */
+int er_k_attn_extend(const float* q_dev, const void* k_dev, const void* v_dev, int past_len, int n_new, float* out_dev, int batch, int heads,
+                     int l_cap, int head_dim, int kv_half, void* stream);
 /* Version 3 of the single-row decode attention (env ER_DECODE_V=3), one row, 16 heads of 96:
  * y[1536] = Wo . softmax(q K^T / sqrt(D)) V + bo + resid over a [16,Lcap,96] cache holding len keys (Lcap <= 8192):
  * balanced chunks (16 per head) + the partial merge fused into the out_proj GEMV; w_half: Wo is fp16 */

@@ -41,6 +41,12 @@ cloud at one face count) from a copy of that row's cache (``LMM.generate(fork_pr
 ``LMM.generate_queue(fork_repeats=True)``, for repeats that are admitted together).  Same output files; it combines with every other
 variable here.  Without the variable nothing changes.
 
+ER_INFER_KEEP_COND=1 orders the rank's calls so that the face counts of one set of clouds follow each other
+(``edgerunner_amd.dist.group_jobs_keep_cond``) and passes ``keep_cond=True``: the first call of a set runs the point encoder and the full
+prefill, the others prefill only the face-count token and BOS behind the kept cond positions (``LMM.generate_ids``).  Every call
+reserves for --test-max-seq-length, so one reservation serves all face counts.  Same output files.  It cannot be combined with
+ER_INFER_QUEUE=1, ER_INFER_SHARE_PREFIX=1 or ER_INFER_FORK_PREFILL=1 (refused at start).  Without the variable nothing changes.
+
 ER_INFER_TEMPERATURE, ER_INFER_TOP_P and ER_INFER_TOP_K (0: no top-k filter) shape the draws of ``--generate_mode sample`` as HF's
 warpers do, in that order; unset, the reference's TopK(10) at temperature 1 stays.  ER_INFER_LOGPROBS=1 writes
 ``{name}_{i}_{n}f_logprobs.npy`` beside every tokens file: float32 [n, 2], one row per token of the tokens file (cut at EOS the same way),
@@ -154,6 +160,10 @@ def main(argv=None):
         raise SystemExit("[ERROR] ER_INFER_SHARE_PREFIX=1 and ER_INFER_QUEUE=1 cannot be combined: prefix groups are not built for queue mode")
     if share_prefix and os.environ.get("EDGERUNNER_KV_PRECISION") == "fp8":
         raise SystemExit("[ERROR] ER_INFER_SHARE_PREFIX=1 and EDGERUNNER_KV_PRECISION=fp8 cannot be combined: the shared-prefix kernels read fp32 and fp16 caches only")
+    keep_cond = os.environ.get("ER_INFER_KEEP_COND") == "1"
+    if keep_cond and (share_prefix or fork_prefill or os.environ.get("ER_INFER_QUEUE") == "1"):
+        raise SystemExit("[ERROR] ER_INFER_KEEP_COND=1 cannot be combined with ER_INFER_QUEUE=1, ER_INFER_SHARE_PREFIX=1 or ER_INFER_FORK_PREFILL=1: "
+                         "the prefill behind a kept cond prefix is built for plain batched calls")
     rank, world, local = D.init_process_group()
     seed_everything(opt.seed)
     if opt.cond_mode not in ("point", "none"):
@@ -249,7 +259,7 @@ def main(argv=None):
               f"decode {st['decode_ms']:.1f} ms")
         mine_groups = []
     else:
-        mine_groups = D.group_jobs(jobs, mine, lambda p: clouds[p].shape[0], rows_max)
+        mine_groups = (D.group_jobs_keep_cond if keep_cond else D.group_jobs)(jobs, mine, lambda p: clouds[p].shape[0], rows_max)
     for num_faces, chunk in mine_groups:
         cond = torch.from_numpy(np.stack([clouds[jobs[j][0]] for j in chunk])).float().to(device)
         t0 = time.time()
@@ -257,7 +267,8 @@ def main(argv=None):
         meshes, tokens = model.generate(cond, num_faces=num_faces, max_new_tokens=opt.test_max_seq_length,
                                         tokenizer=tokenizer, clean=True, seed=opt.seed, row_streams=list(chunk),
                                         **({"share_prefix": share_prefix} if share_prefix else {}),
-                                        **({"fork_prefill": True} if fork_prefill else {}), **sampling)
+                                        **({"fork_prefill": True} if fork_prefill else {}),
+                                        **({"keep_cond": True} if keep_cond else {}), **sampling)
         torch.cuda.synchronize()
         dt = time.time() - t0
         blp = model.last_logprobs
